@@ -11,7 +11,7 @@ One "step" = one launch of the blend kernel over the synthetic grid resident in 
 [64r, 64r+64) — the path shards over views with no data-path collective (weak scaling: per-GPU work is fixed); the
 input grid is generated on rank 0 and broadcast ONCE over RCCL/xGMI before the timed region.
 
-Rank 0 prints ONE JSON line (contract in the task statement) with these extra objects:
+Rank 0 prints ONE JSON line (contract in the task statement), last on stdout, with these extra objects:
   roofline     — HBM roofline of the blend kernel: the bytes the kernel has to move in the layouts in use (3 B per pixel on an
                  alpha-free side, 4 B on an RGBA side) ÷ the kernel's average launch time measured with HIP events on the launch
                  stream (through the C-ABI timer) = `achieved`, `frac`; `frac_algorithmic` is the same on SURVEY.md §8(d)'s
@@ -19,11 +19,17 @@ Rank 0 prints ONE JSON line (contract in the task statement) with these extra ob
   cpu_baseline — the CPU oracle (a port of the reference's STD arithmetic) timed on the host cores on the same
                  workload (N = 1 only).  oracle/ is used here ONLY as that baseline, never in the GPU path;
   cpu_baseline_1thread — the same scalar code on one thread, four full-frame views (SURVEY.md §8(d) (a));
-  also_detail  — (N = 1) the other BASELINE configurations and methods, timed in the same run after the headline step:
+  also         — (N = 1) the other BASELINE configurations and methods, timed in the same run after the headline step:
                  config 3 (15×15 @1080p, 45 views; TEN_WM and STD), config 4 per rank and whole, config 5 fixed focus (TEN_WM, STD,
                  the non-tensor wavefront kernel) and end to end (focus map + all-focus render), cold one-shot renders of configs 2
-                 and 5 — each with ms, algorithmic bytes, roofline fraction and the kernel that ran;
-  also         — the same table, compact ([ms, fraction, kernel] per key), LAST on the line.
+                 and 5 — compact ([ms, fraction, kernel] per key), LAST on the line.
+The same table in full (ms, algorithmic bytes, roofline fraction, kernel and a note per entry) is printed just before the result
+line, on a line of its own: `also_detail: {…}`.  It stays off the result line so that the line fits a log tail of 8,000 characters.
+
+--dump-outputs DIR  after the timed steps, every rank writes what the last timed step computed, as a caller downloads it (RGBA u8
+              per view, as float32): DIR/views.npy [views][pixels][4] at a fixed, seeded sample of pixel positions (the same for
+              every run with the same arguments), DIR/pixel_yx.npy [pixels][y, x] and DIR/view_ids.npy (trajectory indices of the
+              views), both float64; with N > 1 the names start with rank<r>_.  At most 48 MB of views in all, whatever N.
 
 Other modes:  --config 4  strong-scaled BASELINE config 4 (8×8 @4K, one 256-view trajectory split over the GPUs);
               --distribute allgather  every rank generates 1/G of the images, one all-gather instead of the broadcast;
@@ -44,6 +50,7 @@ SEED = 0x1F1F
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8 TB/s
 FP32_PEAK_TFLOPS = 157.3  # dense fp32 vector = fp32 matrix peak: 256 CUs x 4 SIMDs x 64 flop/cycle x 2.4 GHz
 F16_MFMA_PEAK_TFLOPS = 2500.0
+DUMP_BYTES = 48 << 20  # --dump-outputs: bytes of sampled views over all ranks (the coordinates add under 1 MB per rank)
 
 # BASELINE.json configs (index = position in `configs`, 1-based like SURVEY.md §8(d)); parameters: reference README.md:7 for the
 # 8×8 grids, scripts/focusMapCompare.sh:1-5 (-s 7, focus / range / aspect table) for the focus sweep of config 5
@@ -88,6 +95,24 @@ def cpu_baseline(cfg, hp, threads: int, sample_views: int | None = None, budget_
         res["ten_wm_vs_m16"] = {"exact_match_fraction": same / total, "max_abs_diff_lsb": worst, "bytes_compared": total,
                                 "rows": {str(v): [y0, y1] for v, (y0, y1, _) in gpu_rows.items()}}
     return res
+
+
+def dump_outputs(out_dir: str, ctx, view0: int, rows: tuple, world: int, rank: int) -> None:
+    """--dump-outputs: the views of the context's last render at a seeded sample of pixels (module docstring)."""
+    import numpy as np
+    y0, y1 = rows
+    n_pix = (y1 - y0) * ctx.width
+    n = min(n_pix, DUMP_BYTES // world // (ctx.views * 4 * 4))
+    idx = np.sort(np.random.default_rng(SEED).choice(n_pix, size=n, replace=False))
+    ys, xs = y0 + idx // ctx.width, idx % ctx.width
+    sample = np.empty((ctx.views, n, 4), dtype=np.float32)
+    for v in range(ctx.views):
+        sample[v] = ctx.download_view(v)[ys, xs]
+    prefix = "" if world == 1 else f"rank{rank}_"
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, prefix + "views.npy"), sample)
+    np.save(os.path.join(out_dir, prefix + "pixel_yx.npy"), np.stack([ys, xs], 1).astype(np.float64))
+    np.save(os.path.join(out_dir, prefix + "view_ids.npy"), np.arange(view0, view0 + ctx.views, dtype=np.float64))
 
 
 def b_alg(W, rows_in, n_images, rows_out, views):
@@ -432,6 +457,9 @@ def main() -> int:
                     help="untimed launches during set-up, before the W warm-up steps, so that the clocks have ramped "
                          "(with 5 warm-up launches = 1 ms of work the first timed launches still run at idle clocks; the first process "
                          "on a fresh box measured 0.167 ms per step after 150 ms of them and 0.150 ms after 600 ms)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed to DIR/*.npy (a seeded sample of the views; "
+                         "module docstring)")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -546,6 +574,7 @@ def main() -> int:
         # one render split into row bands: no collective at all with synthetic data (every rank generates the rows it
         # holds; real data would be scattered band + halo per rank)
         hp = L.build_params(COLS, ROWS, WIDTH, HEIGHT, cfg["traj"], cfg["focus"], 0.0, cfg["effect"], cfg["aspect"], total_views)
+        v0 = 0
         band = L.row_band(HEIGHT, world, rank)
         held = L.input_rows(band, hp.focused_offsets, HEIGHT)
         ctx.set_row_window(band[0], band[1], held[0], held[1])
@@ -607,6 +636,8 @@ def main() -> int:
         gpu_rows = {}
         for view, y0 in ((0, 0), (views_per_gpu // 2, HEIGHT // 2 - 8), (views_per_gpu - 1, HEIGHT - 16)):
             gpu_rows[view] = (y0, y0 + 16, ctx.download_view(view)[y0:y0 + 16].copy())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, ctx, v0, ctx.out_rows, world, rank)
 
     if rank == 0:
         value = total_views * args.steps / elapsed_max
@@ -701,14 +732,14 @@ def main() -> int:
                 detail = also_table(L, device_index, args.also_iters, args.layout)
             except Exception as e:      # the headline line must come out whatever happens to the extra configurations
                 detail = {"error": f"{type(e).__name__}: {e}"}
-            line["also_detail"] = detail
             # the headline's two companions (same kernel family, same inputs): one sweep direction only, and the reference's RGBA views
             for key, name in (("config2_ten_wm_single_sweep_direction", "single_sweep_direction_ms"), ("config2_ten_wm_rgba_views", "rgba_views_ms")):
                 if isinstance(detail.get(key), dict):
                     line["roofline"][name] = detail[key]["ms"]
             # LAST on the line, compact, so that a reader who keeps only the tail of the output still has every configuration:
             # [ms per launch, fraction of the bound (HBM 8 TB/s on the bytes MOVED in the layouts in use — as the headline's roofline.frac —, or
-            # fp32 157.3 TFLOP/s where the kernel is fp32-bound), kernel]; the fraction on 4·W·H·(N+V) bytes is also_detail's frac_algorithmic
+            # fp32 157.3 TFLOP/s where the kernel is fp32-bound), kernel]; the fraction on 4·W·H·(N+V) bytes is also_detail's frac_algorithmic.
+            # The full table goes on a line of its own, before the result line (module docstring).
             compact = {"legend": "[ms, frac of 8 TB/s on layout bytes moved | 'fp32:' frac of 157.3 TFLOP/s, kernel]"}
             for key, e in detail.items():
                 if isinstance(e, dict) and "ms" in e:
@@ -721,6 +752,7 @@ def main() -> int:
             if "cpu_baseline" in line:
                 compact["cpu_baseline_views_per_s"] = [round(line["cpu_baseline"]["value"], 1), line["cpu_baseline"]["cores"]]
             line["also"] = compact
+            print("also_detail: " + json.dumps(detail), flush=True)
         print(json.dumps(line), flush=True)
     if collectives:
         dist.destroy_process_group()

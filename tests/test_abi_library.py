@@ -21,6 +21,9 @@ def test_header_and_binding_agree(native):
 
 def test_library_exports_every_declared_symbol(native):
     from conftest import ROOT
+    # through the package's loader first: it imports torch before the library pulls in a HIP runtime (lfinterpolator_amd/abi.py).
+    # A bare CDLL would load /opt/rocm's runtime beside torch's, and the GPU tests later in the same process would find no device.
+    native.load_hip_library()
     lib = ctypes.CDLL(native.build.HIP_LIB)
     for name in _declared_symbols(ROOT):
         assert hasattr(lib, name), name

@@ -99,12 +99,16 @@ def test_single_process_broadcast(gpu):
     b.close()
 
 
-def test_bench_json_contract(gpu):
+def test_bench_json_contract(gpu, tmp_path):
+    dump = tmp_path / "outputs"
     res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
-                          "--prewarm-ms", "0", "--also-iters", "2"], capture_output=True, text=True, timeout=900, cwd=ROOT)
+                          "--prewarm-ms", "0", "--also-iters", "2", "--dump-outputs", str(dump)],
+                         capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
+    # the result line is the last line of stdout, and a reader that keeps 8,000 characters of the output's tail can parse it
+    assert res.stdout.splitlines()[-1] == lines[0] and json.loads(res.stdout[-8000:].splitlines()[-1]) is not None
     d = json.loads(lines[0])
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                 "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
@@ -125,8 +129,11 @@ def test_bench_json_contract(gpu):
     assert d["config"]["derived_copy_bytes"] > 0 and d["config"]["kernel"] and d["config"]["view_ranges"] == [[0, 64]]
     c1 = d["cpu_baseline_1thread"]
     assert c1["cores"] == 1 and c1["kind"] == "port" and 0 < c1["value"] <= c["value"]
-    # the other BASELINE configurations, timed in the same run: verbose in also_detail, compact — and LAST on the line — in also
-    detail, also = d["also_detail"], d["also"]
+    # the other BASELINE configurations, timed in the same run: verbose in also_detail (a line of its own, before the result line),
+    # compact — and LAST on the line — in also
+    detail_lines = [l for l in res.stdout.splitlines() if l.startswith("also_detail: ")]
+    assert len(detail_lines) == 1
+    detail, also = json.loads(detail_lines[0][len("also_detail: "):]), d["also"]
     assert list(d.keys())[-1] == "also"
     # round 5 hygiene: the box's core count beside the threads used; how the timed TEN_WM launches compare with M16; the fixed-focus sweeps
     assert c["host_cores"] >= c["cores"] and c1["host_cores"] == c["host_cores"]
@@ -143,6 +150,15 @@ def test_bench_json_contract(gpu):
         assert also[key][0] == round(detail[key]["ms"], 4), key
     assert detail["config5_fixed_focus_std_nontensor"]["kernel"] == "blend_std_vfma" and detail["config5_allfocus_std_nontensor"]["kernel"] == "blend_std_vfma"
     assert len(json.dumps(also)) < 3000          # fits the tail a log reader keeps (the driver keeps 8,000 characters)
+    # --dump-outputs: the last timed step's views at a seeded sample of pixels, float32 / float64, at most 64 MB in all
+    files = sorted(p.name for p in dump.iterdir())
+    assert files == ["pixel_yx.npy", "view_ids.npy", "views.npy"]
+    assert sum((dump / f).stat().st_size for f in files) <= 64 << 20
+    views, yx, ids = (np.load(dump / f) for f in ("views.npy", "pixel_yx.npy", "view_ids.npy"))
+    assert views.dtype == np.float32 and yx.dtype == np.float64 and ids.dtype == np.float64
+    assert views.shape == (64, len(yx), 4) and len(yx) >= 1 << 14 and (ids == np.arange(64)).all()
+    assert (yx[:, 0] >= 0).all() and (yx[:, 0] < 1080).all() and (yx[:, 1] >= 0).all() and (yx[:, 1] < 1920).all()
+    assert (views[..., 3] == 255).all() and views[..., :3].std() > 0 and (views == np.round(views)).all() and views.max() <= 255
 
 
 def test_pinned_host_buffers(gpu, oracle_c):

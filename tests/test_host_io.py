@@ -1,5 +1,6 @@
 """CPU: the steps either side of the hot path — PNG/PPM decode and encode (csrc/host/image_io.cpp) and the grid loader
 (csrc/host/lfLoader.cpp, reference src/lfLoader.cpp:8-67) — against Pillow."""
+import hashlib
 import os
 
 import numpy as np
@@ -92,13 +93,42 @@ def test_loader_grid_order_and_errors(native, tmp_path):
         native.load_grid(str(d))
 
 
-# ---- against the reference's own codec (oracle/_ref/libref_codec.so = stb_image / stb_image_write built from the reference
-# tree by `make -C oracle ref`): what the reference's LfLoader would have handed to its kernels, pixel for pixel -------------
-def _ref_codec():
-    from oracle import ref_codec
-    if not ref_codec.available():
-        pytest.skip("oracle/_ref/libref_codec.so not built (needs /root/reference)")
-    return ref_codec
+# ---- against the reference's own codec (stb_image / stb_image_write, built from the reference tree into oracle/_ref/ by
+# `make -C oracle ref`): what the reference's LfLoader would have handed to its kernels, pixel for pixel.  The tests write their
+# files as before; what stb made of them is stored in tests/golden/codec_stb.npz (tests/golden/make_codec_golden.py) ---------
+CODEC_GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "codec_stb.npz")
+WRITER_ARR = _rand(31, 47, 4, 5)
+ADAM7_SHAPES = [(37, 53, 4), (5, 3, 3), (1, 1, 4), (9, 2, 3)]
+JPEG_SIZES = [(64, 96), (67, 101), (8, 8), (1, 1), (17, 3), (250, 333)]
+JPEG_KINDS = ["444", "422", "420", "grey", "420_restart", "444_progressive", "420_progressive", "q30_420", "q100_444"]
+
+
+@pytest.fixture(scope="module")
+def stb():
+    with np.load(CODEC_GOLDEN) as g:
+        return {k: g[k] for k in g.files}
+
+
+def _sha256(data: bytes) -> str:
+    return hashlib.sha256(data).hexdigest()
+
+
+def _assert_matches_stb(got, stb, key):
+    """got == stbi_load's RGBA for case `key`: stored whole (PNG), or as shape + SHA-256 of the bytes (JPEG)."""
+    if key + "_want" in stb:
+        want = stb[key + "_want"]
+        assert got.shape == want.shape, key
+        assert (got == want).all(), (key, int((got != want).sum()), int(np.abs(got.astype(int) - want.astype(int)).max()))
+    else:
+        assert got.shape == tuple(stb[key + "_shape"]), key
+        assert _sha256(np.ascontiguousarray(got).tobytes()) == str(stb[key + "_sha256"]), key
+
+
+def _assert_is_stb_input(path, stb, key):
+    """A JPEG's decode depends on every choice of its encoder: the file just written must be the one stb decoded for the fixture."""
+    assert _sha256(open(path, "rb").read()) == str(stb[key + "_file_sha256"]), (
+        f"{key}: Pillow wrote another file than the one the stored result belongs to; regenerate tests/golden/codec_stb.npz "
+        "with tests/golden/make_codec_golden.py")
 
 
 def _png_cases(tmp_path):
@@ -113,7 +143,7 @@ def _png_cases(tmp_path):
     pal = Image.fromarray((grad[..., 0] // 4).astype(np.uint8), "P")
     pal.putpalette(list(rng.integers(0, 256, 768, dtype=np.uint8)))
     cases["palette"] = pal
-    cases["grey16"] = Image.fromarray((np.arange(29 * 45, dtype=np.uint16).reshape(29, 45) * 47), "I;16")
+    cases["grey16"] = Image.fromarray(np.arange(29 * 45, dtype=np.uint16).reshape(29, 45) * 47)    # mode I;16
     cases["bilevel"] = Image.fromarray(((x + y) % 3 == 0).astype(np.uint8) * 255, "L").convert("1")
     paths = {}
     for name, img in cases.items():
@@ -130,23 +160,39 @@ def _png_cases(tmp_path):
     return paths
 
 
-def test_png_decode_matches_reference_codec(native, tmp_path):
-    ref = _ref_codec()
+def test_png_decode_matches_reference_codec(native, stb, tmp_path):
+    # PNG is lossless: stb's output depends on the image, not on how Pillow encoded it
     for name, path in _png_cases(tmp_path).items():
-        want = ref.load_rgba(path)
-        got = native.load_image(path)
-        assert got.shape == want.shape, name
-        assert (got == want).all(), (name, int((got != want).sum()))
+        _assert_matches_stb(native.load_image(path), stb, f"png_{name}")
 
 
-def test_png_writers_round_trip_through_each_other(native, tmp_path):
-    ref = _ref_codec()
-    arr = _rand(31, 47, 4, 5)
+def _png_content(data):
+    """A PNG up to its deflate encoding: every chunk but IDAT (CRCs checked), and the joined IDAT bodies inflated."""
+    import struct
+    import zlib
+    assert data[:8] == b"\x89PNG\r\n\x1a\n"
+    chunks, idat, i = [], b"", 8
+    while i < len(data):
+        n, kind = struct.unpack(">I4s", data[i:i + 8])
+        body = data[i + 8:i + 8 + n]
+        assert struct.unpack(">I", data[i + 8 + n:i + 12 + n])[0] == zlib.crc32(kind + body)
+        if kind == b"IDAT":
+            idat += body
+        else:
+            chunks.append((kind, body))
+        i += 12 + n
+    return chunks, zlib.decompress(idat)
+
+
+def test_png_writers_round_trip_through_each_other(native, stb, tmp_path):
+    arr = WRITER_ARR
     ours = str(tmp_path / "ours.png")
     native.write_png(ours, arr)
-    assert (ref.load_rgba(ours) == arr).all()          # the reference's decoder reads our files
+    # the reference's decoder reads our files: make_codec_golden.py checked that stbi_load gives arr back for the stored file,
+    # and ours carries the same header, chunks and filtered rows (the deflate encoding may differ between zlib builds)
+    assert _png_content(open(ours, "rb").read()) == _png_content(stb["writer_ours_file"].tobytes())
     theirs = str(tmp_path / "theirs.png")
-    ref.write_png(theirs, arr)
+    stb["writer_theirs_file"].tofile(theirs)
     assert (native.load_image(theirs) == arr).all()    # we read what stbi_write_png (src/interpolator.cu:313) writes
 
 
@@ -167,14 +213,14 @@ def _adam7_png(arr):
     return b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", ihdr) + chunk(b"IDAT", zlib.compress(raw)) + chunk(b"IEND", b"")
 
 
-@pytest.mark.parametrize("shape", [(37, 53, 4), (5, 3, 3), (1, 1, 4), (9, 2, 3)], ids=lambda s: "x".join(map(str, s)))
-def test_interlaced_png_matches_reference_codec(shape, native, tmp_path):
-    ref = _ref_codec()
+@pytest.mark.parametrize("shape", ADAM7_SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_interlaced_png_matches_reference_codec(shape, native, stb, tmp_path):
     arr = _rand(*shape, 21)
     path = str(tmp_path / "adam7.png")
     with open(path, "wb") as f:
         f.write(_adam7_png(arr))
-    want = ref.load_rgba(path)
+    key = "adam7_" + "x".join(map(str, shape))
+    want = stb[key + "_want"]
     assert (want[..., :shape[2]] == arr).all()
     got = native.load_image(path)
     assert got.shape == want.shape and (got == want).all()
@@ -190,14 +236,9 @@ def _photo(h, w, seed):
     return np.clip(np.stack([r, g, b], -1), 0, 255).astype(np.uint8)
 
 
-@pytest.mark.parametrize("size", [(64, 96), (67, 101), (8, 8), (1, 1), (17, 3), (250, 333)], ids=lambda s: f"{s[0]}x{s[1]}")
-@pytest.mark.parametrize("kind", ["444", "422", "420", "grey", "420_restart", "444_progressive", "420_progressive", "q30_420", "q100_444"])
-def test_jpeg_decode_matches_reference_codec(kind, size, native, tmp_path):
-    """JPEG input (csrc/host/jpeg.cpp) against stb_image as the reference builds it: bit-exact RGBA."""
-    ref = _ref_codec()
+def _jpeg_file(path, kind, size):
     h, w = size
-    arr = _photo(h, w, 7 + h)
-    img = Image.fromarray(arr, "RGB")
+    img = Image.fromarray(_photo(h, w, 7 + h), "RGB")
     opts = {"quality": 85}
     if kind == "grey":
         img = img.convert("L")
@@ -215,31 +256,40 @@ def test_jpeg_decode_matches_reference_codec(kind, size, native, tmp_path):
         opts["quality"] = 30
     if kind.startswith("q100"):
         opts["quality"] = 100
-    path = str(tmp_path / f"{kind}.jpg")
-    img.save(path, "JPEG", **opts)
-    want = ref.load_rgba(path)
-    got = native.load_image(path)
-    assert got.shape == want.shape
-    assert (got == want).all(), (int((got != want).sum()), int(np.abs(got.astype(int) - want.astype(int)).max()))
+    img.save(str(path), "JPEG", **opts)
+    return str(path)
 
 
-def test_jpeg_colour_models_match_reference_codec(native, tmp_path):
-    """Adobe-marked files: CMYK (four components), RGB kept as RGB (no YCbCr transform)."""
-    ref = _ref_codec()
+def _jpeg_colour_model_files(tmp_path):
     arr = _photo(40, 56, 3)
-    cases = {"cmyk": (Image.fromarray(arr, "RGB").convert("CMYK"), {"quality": 90})}
-    try:
-        probe = str(tmp_path / "probe.jpg")
-        Image.fromarray(arr, "RGB").save(probe, "JPEG", keep_rgb=True)
-        cases["rgb_kept"] = (Image.fromarray(arr, "RGB"), {"quality": 90, "keep_rgb": True})
-    except (TypeError, OSError, ValueError):
-        pass
-    for name, (img, opts) in cases.items():
-        path = str(tmp_path / f"{name}.jpg")
-        img.save(path, "JPEG", **opts)
-        want = ref.load_rgba(path)
-        got = native.load_image(path)
-        assert got.shape == want.shape and (got == want).all(), name
+    paths = {"cmyk": str(tmp_path / "cmyk.jpg"), "rgb_kept": str(tmp_path / "rgb_kept.jpg")}
+    Image.fromarray(arr, "RGB").convert("CMYK").save(paths["cmyk"], "JPEG", quality=90)
+    Image.fromarray(arr, "RGB").save(paths["rgb_kept"], "JPEG", quality=90, keep_rgb=True)
+    return paths
+
+
+def _jpeg_grid(tmp_path):
+    """column_row.jpg files (reference naming, src/lfLoader.cpp:22-31): 2 columns, 3 rows."""
+    for col in range(2):
+        for row in range(3):
+            Image.fromarray(_photo(24, 40, 10 * col + row), "RGB").save(str(tmp_path / f"{row}_{col}.jpg"), "JPEG", quality=92)
+
+
+@pytest.mark.parametrize("size", JPEG_SIZES, ids=lambda s: f"{s[0]}x{s[1]}")
+@pytest.mark.parametrize("kind", JPEG_KINDS)
+def test_jpeg_decode_matches_reference_codec(kind, size, native, stb, tmp_path):
+    """JPEG input (csrc/host/jpeg.cpp) against stb_image as the reference builds it: bit-exact RGBA."""
+    key = f"jpeg_{kind}_{size[0]}x{size[1]}"
+    path = _jpeg_file(tmp_path / f"{kind}.jpg", kind, size)
+    _assert_is_stb_input(path, stb, key)
+    _assert_matches_stb(native.load_image(path), stb, key)
+
+
+def test_jpeg_colour_models_match_reference_codec(native, stb, tmp_path):
+    """Adobe-marked files: CMYK (four components), RGB kept as RGB (no YCbCr transform)."""
+    for name, path in _jpeg_colour_model_files(tmp_path).items():
+        _assert_is_stb_input(path, stb, f"jpegcm_{name}")
+        _assert_matches_stb(native.load_image(path), stb, f"jpegcm_{name}")
 
 
 def test_jpeg_truncated_and_corrupt_files_do_not_crash(native, tmp_path):
@@ -268,14 +318,12 @@ def test_jpeg_truncated_and_corrupt_files_do_not_crash(native, tmp_path):
             assert "Cannot load image" in str(e)
 
 
-def test_loader_reads_a_jpeg_grid(native, tmp_path):
+def test_loader_reads_a_jpeg_grid(native, stb, tmp_path):
     """LfLoader on a directory of column_row.jpg files (reference naming, src/lfLoader.cpp:22-31)."""
-    ref = _ref_codec()
-    for col in range(2):
-        for row in range(3):
-            Image.fromarray(_photo(24, 40, 10 * col + row), "RGB").save(str(tmp_path / f"{row}_{col}.jpg"), "JPEG", quality=92)
+    _jpeg_grid(tmp_path)
     cols, rows, lf = native.load_grid(str(tmp_path))
     assert (cols, rows) == (2, 3) and lf.shape == (6, 24, 40, 4)
     for col in range(2):
         for row in range(3):
-            assert (lf[col * rows + row] == ref.load_rgba(str(tmp_path / f"{row}_{col}.jpg"))).all()
+            _assert_is_stb_input(str(tmp_path / f"{row}_{col}.jpg"), stb, f"grid_{row}_{col}")
+            _assert_matches_stb(lf[col * rows + row], stb, f"grid_{row}_{col}")
