@@ -340,6 +340,18 @@ int lfi_debug_pk_minmax3_f16(lfi_ctx *ctx, uint32_t *out_mismatches);
  * v_mfma_f32_32x32x16_f16, shape 1: k/32 chained v_mfma_f32_16x16x32_f16 per quadrant; k a multiple of 32, ≤ 256.  Measures the
  * matrix pipe's fp32 accumulation error, which the default STD kernel's rounding band assumes a bound for. */
 int lfi_debug_mfma_f16_chain(lfi_ctx *ctx, int shape, int k, const uint16_t *a_32xk, const uint16_t *b_kx32, float *c_32x32);
+/* Test hook: fill the selected device buffers of the context with `byte` (hipMemsetAsync on the context's stream, ordered like every
+ * other call), so that a test which renders or builds a focus map afterwards sees every byte the call leaves unwritten.  Buffers not
+ * allocated yet are skipped.  Poisoning never changes the result of a later call: caches in the poisoned memory are marked stale and
+ * rebuilt in full by their next user (the estimate's padded planes; the planar copy, as after lfi_grid_modified).
+ *   VIEWS            the views in the current layout (attached ones too)
+ *   SCRATCH          the planar layout's RGBA scratch copy of the views, the download staging plane, the pre-quantisation buffer, the
+ *                    quilt buffer and lfi_render_stream's second set of views
+ *   MAPS             both focus maps
+ *   FOCUS_WORKSPACE  all of the focus-map estimate's workspace
+ *   DERIVED          the planar copy of the inputs — refused (LFI_EINVAL) after lfi_release_inputs: it is then the only copy */
+enum { LFI_POISON_VIEWS = 1, LFI_POISON_SCRATCH = 2, LFI_POISON_MAPS = 4, LFI_POISON_FOCUS_WORKSPACE = 8, LFI_POISON_DERIVED = 16 };
+int lfi_debug_poison(lfi_ctx *ctx, uint32_t what, uint8_t byte);
 
 #ifdef __cplusplus
 }

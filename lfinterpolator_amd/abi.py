@@ -18,6 +18,11 @@ LFI_FLAG_STD_ANALYTIC_BAND = 8
 LFI_FLAG_STD_MEASURED_BAND = 16
 LFI_FLAG_STD_BAND_PROBE_FAIL = 32
 LFI_KERNEL_FOCUS_ESTIMATE = 2
+LFI_POISON_VIEWS = 1
+LFI_POISON_SCRATCH = 2
+LFI_POISON_MAPS = 4
+LFI_POISON_FOCUS_WORKSPACE = 8
+LFI_POISON_DERIVED = 16
 METHODS = {"STD": LFI_METHOD_STD, "TEN_WM": LFI_METHOD_TEN_WM, "FOCUS": LFI_KERNEL_FOCUS_ESTIMATE}
 
 # every symbol include/lfi.h declares
@@ -28,6 +33,7 @@ ABI_SYMBOLS = [
     "lfi_timer_stop", "lfi_sync", "lfi_download_view", "lfi_download_map", "lfi_download_quilt", "lfi_download_quilt_tiles", "lfi_release_inputs", "lfi_alloc_pinned", "lfi_free_pinned", "lfi_upload_map", "lfi_set_stream",
     "lfi_set_variant", "lfi_list_variants", "lfi_download_coords", "lfi_download_prequant", "lfi_debug_mfma_f16",
     "lfi_grid_modified", "lfi_prepare", "lfi_memory_info", "lfi_last_kernel_name", "lfi_fill_synthetic_images", "lfi_set_output_layout", "lfi_view_layout", "lfi_fill_synthetic_scene", "lfi_upload_image_async", "lfi_upload_wait", "lfi_render_stream", "lfi_compare_view", "lfi_debug_mfma_f16_chain", "lfi_debug_pk_minmax3_f16", "lfi_std_band_info",
+    "lfi_debug_poison",
 ]
 
 
@@ -136,6 +142,7 @@ def load_hip_library() -> C.CDLL:
         "lfi_fill_synthetic_scene": (i, [vp, C.c_uint32]),
         "lfi_debug_mfma_f16_chain": (i, [vp, i, i, vp, vp, vp]),
         "lfi_debug_pk_minmax3_f16": (i, [vp, vp]),
+        "lfi_debug_poison": (i, [vp, C.c_uint32, C.c_uint8]),
         "lfi_set_output_layout": (i, [vp, i]),
         "lfi_view_layout": (i, [vp, C.POINTER(ViewLayout)]),
         "lfi_fill_synthetic_images": (i, [vp, C.c_uint32, i, i]),
@@ -415,7 +422,7 @@ class Context:
         self._check(self._lib.lfi_download_quilt_tiles(self._h, tiles_x, tiles_y, first_tile, n, v0, _ptr(out), tiles_x * self.width * 4))
 
     def download_quilt(self, tiles_x: int, tiles_y: int, v0: int = 0) -> np.ndarray:
-        out = np.empty((tiles_y * self.height, tiles_x * self.width, 4), dtype=np.uint8)
+        out = np.full((tiles_y * self.height, tiles_x * self.width, 4), 0xC3, dtype=np.uint8)   # a sentinel, not zeros: every byte is written
         self._check(self._lib.lfi_download_quilt(self._h, tiles_x, tiles_y, v0, _ptr(out), tiles_x * self.width * 4))
         return out
 
@@ -455,6 +462,10 @@ class Context:
         out = C.c_uint32(0xffffffff)
         self._check(self._lib.lfi_debug_pk_minmax3_f16(self._h, C.byref(out)))
         return int(out.value)
+
+    def poison(self, what: int, byte: int) -> None:
+        """Fill the buffers selected by the LFI_POISON_* bits in `what` with `byte` (stream-ordered; caches are rebuilt by their next user)."""
+        self._check(self._lib.lfi_debug_poison(self._h, what, byte))
 
     def debug_mfma_f16(self, a_bits: np.ndarray, b_bits: np.ndarray) -> np.ndarray:
         a = np.ascontiguousarray(a_bits, dtype=np.uint16)

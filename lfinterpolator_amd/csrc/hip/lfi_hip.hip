@@ -1520,6 +1520,54 @@ int lfi_debug_mfma_f16_chain(lfi_ctx *ctx, int shape, int k, const uint16_t *a_3
     return LFI_OK;
 }
 
+int lfi_debug_poison(lfi_ctx *ctx, uint32_t what, uint8_t byte)
+{
+    if(!ctx)
+        return LFI_EINVAL;
+    if(what & ~uint32_t(LFI_POISON_VIEWS | LFI_POISON_SCRATCH | LFI_POISON_MAPS | LFI_POISON_FOCUS_WORKSPACE | LFI_POISON_DERIVED))
+        return fail(ctx, LFI_EINVAL, "lfi_debug_poison: unknown LFI_POISON_* bits");
+    if((what & LFI_POISON_DERIVED) && ctx->inputs_released)
+        return fail(ctx, LFI_EINVAL, "lfi_debug_poison: the planar copy is the only copy of the inputs after lfi_release_inputs");
+    if(int rc = bind(ctx))
+        return rc;
+    // in stream order like every other call: behind the uploads (the eager planar refresh) and the focus map's filter on the side stream
+    if(int rc = join_uploads(ctx))
+        return rc;
+    if(int rc = join_filter(ctx))
+        return rc;
+    hipStream_t st = ctx->stream;
+    auto fill = [&](void *p, size_t bytes) -> int {
+        if(p && bytes)
+            LFI_HIP(ctx, hipMemsetAsync(p, byte, bytes, st));
+        return LFI_OK;
+    };
+    int rc = LFI_OK;
+    if(what & LFI_POISON_VIEWS)
+        rc = rc ? rc : fill(ctx->views, ctx->views ? out_plane_bytes(ctx) * ctx->views_n : 0);
+    if(what & LFI_POISON_SCRATCH)
+    {
+        rc = rc ? rc : fill(ctx->rgba_scratch, ctx->rgba_scratch_bytes);
+        rc = rc ? rc : fill(ctx->dl_plane, ctx->dl_plane_bytes);
+        rc = rc ? rc : fill(ctx->prequant, sizeof(float) * 3 * (size_t)ctx->width * ctx->height);
+        rc = rc ? rc : fill(ctx->quilt, ctx->quilt_bytes);
+        rc = rc ? rc : fill(ctx->views2, ctx->views2_bytes);
+    }
+    if(what & LFI_POISON_MAPS)
+        rc = rc ? rc : fill(ctx->maps, ctx->maps ? plane_bytes(ctx) * 2 : 0);
+    if(what & LFI_POISON_FOCUS_WORKSPACE)
+    {
+        rc = rc ? rc : fill(ctx->focus_ws, ctx->focus_ws_bytes);
+        ctx->pad_version = 0; // the padded planes of the estimate are rebuilt in full by the next lfi_focus_map
+    }
+    if(what & LFI_POISON_DERIVED)
+    {
+        rc = rc ? rc : fill(ctx->planar, ctx->planar_bytes);
+        if(ctx->planar)
+            touch_all(ctx); // as lfi_grid_modified: the next render that reads the copy rebuilds all of it
+    }
+    return rc;
+}
+
 #if LFI_SX_TRACE
 // measurement builds only (blend_stdx.hpp): the per-workgroup unit clocks of the last blend_stdx launch; not part of include/lfi.h
 int lfi_debug_sx_trace(unsigned long long *out, int n_words)

@@ -7,6 +7,8 @@ focus maps bit-exact, TEN_WM within one LSB of the fp16-accumulate model M16 —
 """
 import numpy as np
 
+import poison
+
 TEN_TOL_LSB = 1
 
 
@@ -40,49 +42,43 @@ def fuzz_blend(L, oc, n_cases: int, seed: int, log=None) -> list:
         v1 = int(rng.integers(v0 + 1, V + 1))
         for var in std_variants:
             ctx.set_variant("STD", var)
-            ctx.render("STD")
-            ctx.sync()
+            poison.render(ctx, "STD")
             if not (ctx.download_views() == want_std).all():
                 bad.append(dict(case, what="STD", variant=var))
         for var in ten_variants:
             ctx.set_variant("TEN_WM", var)
-            ctx.render("TEN_WM")
-            ctx.sync()
+            poison.render(ctx, "TEN_WM")
             full = ctx.download_views()
             d = int(np.abs(full.astype(int) - want_ten.astype(int)).max())
-            ctx.render("TEN_WM", v0=v0, v1=v1)
-            ctx.sync()
-            if d > TEN_TOL_LSB or not (ctx.download_views() == full).all():
+            b = poison.render(ctx, "TEN_WM", v0=v0, v1=v1)
+            if d > TEN_TOL_LSB or poison.written_outside(ctx, v0, v1, b) or not (ctx.download_views(v0, v1) == full[v0:v1]).all():
                 bad.append(dict(case, what="TEN_WM", variant=var, lsb=d, v0=v0, v1=v1))
         # the planar view layout: TEN_WM within one LSB of the oracle and byte-identical to the RGBA layout's default kernel, view ranges
         # included; STD bit-exact (round 4: blend_stdx writes the byte planes itself, one to four chunks of images), a view range over it too
         ctx.set_variant("TEN_WM", "auto")
         ctx.set_variant("STD", "auto")
-        ctx.render("TEN_WM")
-        ctx.sync()
+        poison.render(ctx, "TEN_WM")
         want_rgba = ctx.download_views()
         ctx.set_output_layout("planar")
-        ctx.render("TEN_WM")
-        ctx.sync()
+        poison.render(ctx, "TEN_WM")
         got = ctx.download_views()
         kernel = ctx.last_kernel_name()
-        ctx.render("TEN_WM", v0=v0, v1=v1)
-        ctx.sync()
-        part = ctx.download_views()
-        ctx.render("STD")
-        ctx.render("STD", v0=v0, v1=v1)
-        ctx.sync()
+        b = poison.render(ctx, "TEN_WM", v0=v0, v1=v1)
+        part_ok = not poison.written_outside(ctx, v0, v1, b) and (ctx.download_views(v0, v1) == got[v0:v1]).all()
+        poison.render(ctx, "STD")
+        std_ok = (ctx.download_views() == want_std).all()
+        b = poison.render(ctx, "STD", v0=v0, v1=v1)
+        std_ok = std_ok and not poison.written_outside(ctx, v0, v1, b) and (ctx.download_views(v0, v1) == want_std[v0:v1]).all()
         d = int(np.abs(got.astype(int) - want_ten.astype(int)).max())
-        if d > TEN_TOL_LSB or not (got == want_rgba).all() or not (part == got).all() or not (ctx.download_views() == want_std).all():
+        if d > TEN_TOL_LSB or not (got == want_rgba).all() or not part_ok or not std_ok:
             bad.append(dict(case, what="planar layout", kernel=kernel, lsb=d, v0=v0, v1=v1))
         # round 4: the quilt of a random tiling (assembled on the device, filled in two parts) is the montage of the views; and after
         # lfi_release_inputs — the planar copy is the only copy of the inputs — STD stays the oracle's and TEN_WM the same bytes
-        ctx.render("TEN_WM")
-        ctx.sync()
+        poison.render(ctx, "TEN_WM")
         tx = int(rng.integers(1, 5))
         ty = int(rng.integers(1, max(2, min(4, V // tx) + 1)))
         if tx * ty <= V:
-            quilt = np.zeros((ty * H, tx * W, 4), np.uint8)
+            quilt = poison.sentinel((ty * H, tx * W, 4))
             cut = int(rng.integers(0, tx * ty + 1))
             if cut > 0:
                 ctx.download_quilt_tiles(quilt, tx, ty, 0, cut)
@@ -93,11 +89,9 @@ def fuzz_blend(L, oc, n_cases: int, seed: int, log=None) -> list:
                 bad.append(dict(case, what="quilt", tiles=(tx, ty), cut=cut))
         try:
             ctx.release_inputs()
-            ctx.render("TEN_WM")
-            ctx.sync()
+            poison.render(ctx, "TEN_WM")
             same = bool((ctx.download_views() == got).all())
-            ctx.render("STD")
-            ctx.sync()
+            poison.render(ctx, "STD")
             if not same or not (ctx.download_views() == want_std).all():
                 bad.append(dict(case, what="released inputs", ten_same=same))
         except L.LfiError as e:
@@ -139,8 +133,7 @@ def fuzz_focus(L, oc, n_cases: int, seed: int, log=None) -> list:
         ctx.set_params(hp)
         for var in ("factored", "factored_direct", "plain", "lds"):
             ctx.set_variant("FOCUS", var)
-            ctx.focus_map()
-            ctx.sync()
+            poison.focus_map(ctx)
             m0, m1 = ctx.download_map(0), ctx.download_map(1)
             if not ((m0 == want0).all() and (m1 == want1).all()):
                 bad.append(dict(case, what="focus map", variant=var, wrong=int((m0 != want0).any(-1).sum())))
@@ -185,19 +178,16 @@ def fuzz_allfocus(L, oc, n_cases: int, seed: int, log=None) -> list:
         ctx.upload_map(1, m)
         for layout in ("rgba", "planar"):
             ctx.set_output_layout(layout)
-            ctx.render("STD", all_focus=True)
-            ctx.sync()
+            poison.render(ctx, "STD", all_focus=True)
             ok_std = bool((ctx.download_views() == want_std).all())
-            ctx.render("TEN_WM", all_focus=True)
-            ctx.sync()
+            poison.render(ctx, "TEN_WM", all_focus=True)
             d = int(np.abs(ctx.download_views().astype(int) - want_ten.astype(int)).max())
             if not ok_std or d > TEN_TOL_LSB:
                 bad.append(dict(case, what="all-focus", layout=layout, std_exact=ok_std, lsb=d, kernel=ctx.last_kernel_name()))
             if cols * rows > 128 and layout == "rgba":
                 # three or four chunks of images: blend_afs (every sample gathered once; round 4) must give the same bytes
                 ctx.set_variant("STD", "filtered_gather_once")
-                ctx.render("STD", all_focus=True)
-                ctx.sync()
+                poison.render(ctx, "STD", all_focus=True)
                 if ctx.last_kernel_name() != "blend_afs<STD,allfocus>" or not (ctx.download_views() == want_std).all():
                     bad.append(dict(case, what="all-focus", layout=layout, std_exact=False, kernel=ctx.last_kernel_name()))
                 ctx.set_variant("STD", "auto")

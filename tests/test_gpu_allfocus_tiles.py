@@ -7,6 +7,7 @@ Bit-exact against the oracle for STD, within the one-LSB contract for TEN_WM, in
 import numpy as np
 import pytest
 
+import poison
 from conftest import SEED
 
 pytestmark = pytest.mark.gpu
@@ -78,30 +79,23 @@ def test_structured_maps_match_the_oracle(case, gpu, oracle_c):
         ctx = _ctx(gpu, cols, rows, W, H, hp, lf, flags)
         for k in (0, 1):
             ctx.upload_map(k, maps[k])
-        ctx.render("STD", all_focus=True)          # reads map 1 (src/kernels.cu:326)
-        ctx.sync()
+        poison.render(ctx, "STD", all_focus=True)  # reads map 1 (src/kernels.cu:326)
         std = ctx.download_views()
         if cols * rows > 128:                      # three or four chunks of images: blend_afs (every sample gathered once) gives the same bytes
             ctx.set_variant("STD", "filtered_gather_once")
-            ctx.render("STD", all_focus=True)
-            ctx.sync()
+            poison.render(ctx, "STD", all_focus=True)
             assert ctx.last_kernel_name() == "blend_afs<STD,allfocus>" and (ctx.download_views() == want_std).all(), flags
             ctx.set_variant("STD", "auto")
-        ctx.render("TEN_WM", all_focus=True)       # reads map 0 (src/kernels.cu:430)
-        ctx.sync()
+        poison.render(ctx, "TEN_WM", all_focus=True)   # reads map 0 (src/kernels.cu:430)
         ten = ctx.download_views()
         assert (std == want_std).all(), (flags, int((std != want_std).sum()))
         assert np.abs(ten.astype(int) - want_ten.astype(int)).max() <= TEN_TOL_LSB, flags
         # a view range, and the planar view layout (RGBA kernel + conversion)
-        ctx.render("TEN_WM", all_focus=True, v0=V // 2, v1=V // 2 + 1)
-        ctx.sync()
-        assert (ctx.download_views() == ten).all()
+        assert (poison.render_range(ctx, "TEN_WM", V // 2, V // 2 + 1, all_focus=True) == ten[V // 2:V // 2 + 1]).all()
         ctx.set_output_layout("planar")
-        ctx.render("TEN_WM", all_focus=True)
-        ctx.sync()
+        poison.render(ctx, "TEN_WM", all_focus=True)
         assert (ctx.download_views() == ten).all()
-        ctx.render("STD", all_focus=True)
-        ctx.sync()
+        poison.render(ctx, "STD", all_focus=True)
         assert (ctx.download_views() == std).all()
         ctx.close()
 
@@ -121,8 +115,7 @@ def test_structured_map_row_bands(world, cols, gpu, oracle_c):
         full.upload_map(k, m)
     want = {}
     for method in ("STD", "TEN_WM"):
-        full.render(method, all_focus=True)
-        full.sync()
+        poison.render(full, method, all_focus=True)
         want[method] = full.download_views()
     full.close()
     # the checker is the oracle: STD bit-exact, TEN_WM within one LSB of M16 (both maps hold the same plane here)
@@ -142,8 +135,7 @@ def test_structured_map_row_bands(world, cols, gpu, oracle_c):
                 ctx.upload_map(k, m)
             if cols * rows > 128:
                 ctx.set_variant("STD", "filtered_gather_once")
-            ctx.render(method, all_focus=True)
-            ctx.sync()
+            poison.render(ctx, method, all_focus=True)
             got |= ctx.download_views()
             ctx.close()
         if method == "STD":

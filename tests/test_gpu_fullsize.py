@@ -4,14 +4,16 @@ Configs 2, 3 and one rank of config 4: EVERY view, FULL frame, STD bit-exact aga
 second per configuration on the GPU box's host cores), a handful of full-frame TEN_WM views within one LSB of the oracle's M16
 model in both view layouts, plus the size-independent properties (identity under one-hot weights, view-range invariance).
 Config 5 (15×15 @4K, 7.5 GB of inputs): the light field is generated on the host plane by plane with the oracle's generator,
-and oracle row bands (top edge, interior, bottom edge) check the fixed-focus renders, the focus map and the all-focus renders
-that read it."""
+and oracle row bands (the edges, the middle, the estimate's flagged-row boundaries, an 8-row interior band) check the fixed-focus
+renders, the focus map and the all-focus renders that read it.  Config 4 whole (256 views on one GPU): probe views of every view
+pass on three bands.  Every render and focus map runs under poison (tests/poison.py): bytes a launch leaves unwritten fail."""
 from concurrent.futures import ThreadPoolExecutor
 import os
 
 import numpy as np
 import pytest
 
+import poison
 from conftest import SEED
 
 pytestmark = pytest.mark.gpu
@@ -62,8 +64,7 @@ def test_full_frame_parity(cfg, gpu, oracle_c):
     hp.weights = onehot
     ctx.set_params(hp)
     for method in ("STD", "TEN_WM"):
-        ctx.render(method)
-        ctx.sync()
+        poison.render(ctx, method)
         for v in probe:
             g = int(picks[v])
             want = _shifted(oracle_c.synthetic_plane(g, W, H, SEED), int(hp.focused_offsets[g, 0]), int(hp.focused_offsets[g, 1]))
@@ -74,8 +75,7 @@ def test_full_frame_parity(cfg, gpu, oracle_c):
     ctx.set_params(hp)
     lf = _host_lf(oracle_c, n, W, H)
     want_std = oracle_c.blend_std(lf, hp.focused_offsets, hp.offsets, hp.weights, threads=THREADS)
-    ctx.render("STD")
-    ctx.sync()
+    poison.render(ctx, "STD")
     std_probe = {}
     for v in range(V):
         got = ctx.download_view(v)
@@ -90,8 +90,7 @@ def test_full_frame_parity(cfg, gpu, oracle_c):
     ten_views = {}
     for layout in ("rgba", "planar"):
         ctx.set_output_layout(layout)
-        ctx.render("TEN_WM")
-        ctx.sync()
+        poison.render(ctx, "TEN_WM")
         for v in probe:
             got = ctx.download_view(v)
             assert np.abs(got.astype(int) - want_ten[v].astype(int)).max() <= 1, ("TEN_WM", layout, v)
@@ -102,10 +101,9 @@ def test_full_frame_parity(cfg, gpu, oracle_c):
                 assert (got == ten_views[v]).all(), ("planar layout differs from RGBA layout", v)
             # RN of the fp32 sum vs fp16-truncation of the same sum: at most one step apart, everywhere
             assert np.abs(std_probe[v].astype(int) - got.astype(int)).max() <= 1
-        # a one-view range renders the same bytes as the full launch
-        ctx.render("TEN_WM", v0=V // 2, v1=V // 2 + 1)
-        ctx.sync()
-        assert (ctx.download_view(V // 2) == ten_views[V // 2]).all()
+        # a one-view range renders the same bytes as the full launch, and no other view
+        one = poison.render_range(ctx, "TEN_WM", V // 2, V // 2 + 1, outside=[0, V // 2 - 1, V // 2 + 1, V - 1])
+        assert (one[0] == ten_views[V // 2]).all()
     ctx.close()
 
 
@@ -122,17 +120,16 @@ def test_config5_15x15_4k_bands(gpu, oracle_c):
     ctx.set_params(hp)
     lf = _host_lf(oracle_c, n, W, H)                       # 7.5 GB on the host, generated plane by plane
     probe = [0, 31, 63]
-    bands = ((0, 2), (H // 2 - 1, H // 2 + 1), (H - 2, H))
+    # the edges, the middle, the rows around the estimate's flagged-row boundaries (100-102, 166-170) and one 8-row band inside
+    bands = ((0, 2), (100, 103), (166, 171), (1200, 1208), (H // 2 - 1, H // 2 + 1), (H - 2, H))
 
     # fixed focus: STD bit-exact, TEN_WM ≤ 1 LSB (both layouts), on the bands
-    ctx.render("STD")
-    ctx.sync()
+    poison.render(ctx, "STD")
     std = {v: ctx.download_view(v) for v in probe}
     ten = {}
     for layout in ("rgba", "planar"):
         ctx.set_output_layout(layout)
-        ctx.render("TEN_WM")
-        ctx.sync()
+        poison.render(ctx, "TEN_WM")
         ten[layout] = {v: ctx.download_view(v) for v in probe}
     for v in probe:
         assert (ten["planar"][v] == ten["rgba"][v]).all()
@@ -147,8 +144,9 @@ def test_config5_15x15_4k_bands(gpu, oracle_c):
     maps = {}
     for variant in ("factored", "factored_direct", "lds"):
         ctx.set_variant("FOCUS", variant)
-        ctx.focus_map()
-        ctx.focus_map()   # a second call reuses the workspace and the side stream
+        poison.focus_map(ctx)
+        ctx.poison(gpu.LFI_POISON_MAPS, poison.POISON[1])
+        ctx.focus_map()   # a second call reuses the workspace (its padded planes) and the side stream
         ctx.sync()
         maps[variant] = (ctx.download_map(0), ctx.download_map(1))
     assert (maps["factored"][0] == maps["lds"][0]).all(), int((maps["factored"][0] != maps["lds"][0]).sum())
@@ -164,11 +162,9 @@ def test_config5_15x15_4k_bands(gpu, oracle_c):
         assert (map1[y0:y1] == ref1[y0:y1]).all(), ("map 1", y0)
 
     # all-focus renders: STD reads map 1, TEN_WM map 0 (the reference's kernels, src/kernels.cu:326 / :430)
-    ctx.render("STD", all_focus=True)
-    ctx.sync()
+    poison.render(ctx, "STD", all_focus=True)
     af_std = {v: ctx.download_view(v) for v in probe}
-    ctx.render("TEN_WM", all_focus=True)
-    ctx.sync()
+    poison.render(ctx, "TEN_WM", all_focus=True)
     af_ten = {v: ctx.download_view(v) for v in probe}
     for v in probe:
         for y0, y1 in bands:
@@ -183,8 +179,7 @@ def test_config5_15x15_4k_bands(gpu, oracle_c):
     # blend_stdxa / blend_persist with quad transposes in their epilogues): whole frames byte-identical to the RGBA layout's, no scratch copy
     ctx.set_output_layout("planar")
     for what, all_focus, method, want in (("STD", False, "STD", std), ("all-focus STD", True, "STD", af_std), ("all-focus TEN_WM", True, "TEN_WM", af_ten)):
-        ctx.render(method, all_focus=all_focus)
-        ctx.sync()
+        poison.render(ctx, method, all_focus=all_focus)
         for v in probe:
             got = ctx.download_view(v)
             assert (got == want[v]).all(), (what, "planar layout", v, int((got != want[v]).sum()))
@@ -203,9 +198,39 @@ def test_focus_map_1080p_variants_agree(gpu):
     maps = {}
     for variant in ("factored", "lds"):
         ctx.set_variant("FOCUS", variant)
-        ctx.focus_map()
-        ctx.sync()
+        poison.focus_map(ctx)
         maps[variant] = (ctx.download_map(0), ctx.download_map(1))
     assert (maps["factored"][0] == maps["lds"][0]).all(), int((maps["factored"][0] != maps["lds"][0]).sum())
     assert (maps["factored"][1] == maps["lds"][1]).all()
+    ctx.close()
+
+
+def test_config4_whole_8x8_4k_256_views(gpu, oracle_c):
+    """BASELINE config 4 on one GPU: 8×8 @3840×2160 and all 256 views in one launch — four in-kernel view passes of 64 (blend_planar with
+    RGBA views, blend_p3 with planar views).  Probe views 0, 64, 129 and 255 (one per pass) on three row bands, under poison: STD bit-exact,
+    TEN_WM within one LSB of M16 in both layouts (identical bytes)."""
+    cols = rows = 8
+    W, H, V, n = 3840, 2160, 256, 64
+    hp = gpu.build_params(cols, rows, W, H, "0,0,1,1", 0.23, 0.0, 3.0, 1.783, V)
+    ctx = gpu.Context(0)
+    ctx.set_grid(cols, rows, W, H)
+    ctx.fill_synthetic(SEED)
+    ctx.set_params(hp)
+    lf = _host_lf(oracle_c, n, W, H)
+    probe = [0, 64, 129, 255]
+    bands = ((0, 3), (H // 2 - 2, H // 2 + 2), (H - 3, H))
+    poison.render(ctx, "STD")
+    got = {v: ctx.download_view(v) for v in probe}
+    ten = {}
+    for layout in ("rgba", "planar"):
+        ctx.set_output_layout(layout)
+        poison.render(ctx, "TEN_WM")
+        ten[layout] = {v: ctx.download_view(v) for v in probe}
+    for v in probe:
+        assert (ten["planar"][v] == ten["rgba"][v]).all(), v
+        for y0, y1 in bands:
+            ref = oracle_c.blend_std(lf, hp.focused_offsets, hp.offsets, hp.weights, v0=v, v1=v + 1, rows=(y0, y1), threads=THREADS)
+            assert (got[v][y0:y1] == ref[v, y0:y1]).all(), ("STD", v, y0)
+            ref = oracle_c.blend_ten(lf, hp.focused_offsets, hp.offsets, hp.weights, v0=v, v1=v + 1, rows=(y0, y1), threads=THREADS)
+            assert np.abs(ten["rgba"][v][y0:y1].astype(int) - ref[v, y0:y1].astype(int)).max() <= 1, ("TEN_WM", v, y0)
     ctx.close()

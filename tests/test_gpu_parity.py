@@ -11,6 +11,7 @@ import os
 import numpy as np
 import pytest
 
+import poison
 from conftest import GOLDEN_DIR, SEED, SMALL_CASES
 
 pytestmark = pytest.mark.gpu
@@ -83,8 +84,7 @@ def test_synthetic_fill_matches_oracle(gpu, oracle_c):
     hp.weights = onehot
     hp.focused_offsets = np.zeros((6, 2), np.int32)
     ctx.set_params(hp)
-    ctx.render("STD")
-    ctx.sync()
+    poison.render(ctx, "STD")
     assert (ctx.download_views() == oracle_c.synthetic_lf(6, 37, 11, 1234)).all()
     ctx.close()
 
@@ -100,13 +100,11 @@ def test_golden_fixtures(case, gpu, oracle_c):
     exact = oracle_c.blend_f64(g["lf"], hp.focused_offsets, hp.offsets, hp.weights)
     for variant in ctx.list_variants("STD"):
         ctx.set_variant("STD", variant)
-        ctx.render("STD")
-        ctx.sync()
+        poison.render(ctx, "STD")
         assert (ctx.download_views() == g["std"]).all(), variant
     for variant in ctx.list_variants("TEN_WM"):
         ctx.set_variant("TEN_WM", variant)
-        ctx.render("TEN_WM")
-        ctx.sync()
+        poison.render(ctx, "TEN_WM")
         out = ctx.download_views()
         assert np.abs(out.astype(int) - g["ten_m16"].astype(int)).max() <= TEN_TOL_LSB, variant
         assert (out[..., 3] == 255).all()
@@ -118,29 +116,24 @@ def test_golden_fixtures(case, gpu, oracle_c):
     # focus map + all-focus renders
     ctx.set_variant("STD", "auto")
     ctx.set_variant("TEN_WM", "auto")
-    ctx.focus_map()
-    ctx.sync()
+    poison.focus_map(ctx)
     assert (ctx.download_map(0) == g["map0"]).all()
     assert (ctx.download_map(1) == g["map1"]).all()
     for variant in ctx.list_variants("STD"):
         ctx.set_variant("STD", variant)
-        ctx.render("STD", all_focus=True)
-        ctx.sync()
+        poison.render(ctx, "STD", all_focus=True)
         assert (ctx.download_views() == g["af_std"]).all(), variant
     # default: the reference's maps — Tensors::process<true> reads the unfiltered map 0 (src/kernels.cu:430)
     for variant in ctx.list_variants("TEN_WM"):
         ctx.set_variant("TEN_WM", variant)
-        ctx.render("TEN_WM", all_focus=True)
-        ctx.sync()
+        poison.render(ctx, "TEN_WM", all_focus=True)
         assert np.abs(ctx.download_views().astype(int) - g["af_ten_m16_map0"].astype(int)).max() <= TEN_TOL_LSB, variant
     # opt-in: both methods read the filtered map 1
     ctx.set_params(hp, flags=gpu.LFI_FLAG_UNIFIED_FOCUS_MAP)
     ctx.set_variant("TEN_WM", "auto")
-    ctx.render("TEN_WM", all_focus=True)
-    ctx.sync()
+    poison.render(ctx, "TEN_WM", all_focus=True)
     assert np.abs(ctx.download_views().astype(int) - g["af_ten_m16"].astype(int)).max() <= TEN_TOL_LSB
-    ctx.render("STD", all_focus=True)
-    ctx.sync()
+    poison.render(ctx, "STD", all_focus=True)
     assert (ctx.download_views() == g["af_std"]).all()
     ctx.close()
 
@@ -176,8 +169,7 @@ def test_std_accumulators_bit_exact_and_ten_per_batch_mode(gpu, oracle_c):
     # of a batch in double precision on the vector pipe, one rounding to fp16: blend_ten_m16; the matrix pipe's fp32 accumulation made ≈ 1e-4
     # of the bytes differ), fixed focus and all-focus, also on a 15×15 grid (K padded from 225 to 240) with subnormal weights (-s 7)
     ctx = _ctx(gpu, cols, rows, W, H, hp, flags=gpu.LFI_FLAG_TEN_ROUND_PER_BATCH)
-    ctx.render("TEN_WM")
-    ctx.sync()
+    poison.render(ctx, "TEN_WM")
     assert ctx.last_kernel_name() == "blend_ten_m16"
     m16, pre16 = oracle_c.blend_ten(lf, hp.focused_offsets, hp.offsets, hp.weights, model=oracle_c.TEN_M16, return_prequant=True)
     assert (ctx.download_views() == m16).all()
@@ -191,8 +183,7 @@ def test_std_accumulators_bit_exact_and_ten_per_batch_mode(gpu, oracle_c):
     ctx = _ctx(gpu, cols, rows, W, H, hp, lf=lf, flags=gpu.LFI_FLAG_TEN_ROUND_PER_BATCH)
     ctx.upload_map(0, map0)
     for all_focus in (False, True):
-        ctx.render("TEN_WM", all_focus=all_focus)
-        ctx.sync()
+        poison.render(ctx, "TEN_WM", all_focus=all_focus)
         want = oracle_c.blend_ten(lf, hp.focused_offsets, hp.offsets, hp.weights, model=oracle_c.TEN_M16, all_focus=all_focus, map_plane=map0,
                                   focus=hp.focus, rng=hp.range)
         assert (ctx.download_views() == want).all(), all_focus
@@ -213,13 +204,11 @@ def test_ragged_shapes_all_variants(shape, gpu, oracle_c):
     m16 = oracle_c.blend_ten(lf, hp.focused_offsets, hp.offsets, hp.weights, threads=8)
     for variant in ctx.list_variants("STD"):
         ctx.set_variant("STD", variant)
-        ctx.render("STD")
-        ctx.sync()
+        poison.render(ctx, "STD")
         assert (ctx.download_views() == std).all(), variant
     for variant in ctx.list_variants("TEN_WM"):
         ctx.set_variant("TEN_WM", variant)
-        ctx.render("TEN_WM")
-        ctx.sync()
+        poison.render(ctx, "TEN_WM")
         assert np.abs(ctx.download_views().astype(int) - m16.astype(int)).max() <= TEN_TOL_LSB, variant
     ctx.close()
 
@@ -235,14 +224,12 @@ def test_offsets_larger_than_image_and_subnormal_weights(gpu, oracle_c):
     ctx = _ctx(gpu, cols, rows, W, H, hp, seed=5)
     for variant in ctx.list_variants("STD"):
         ctx.set_variant("STD", variant)
-        ctx.render("STD")
-        ctx.sync()
+        poison.render(ctx, "STD")
         assert (ctx.download_views() == oracle_c.blend_std(lf, hp.focused_offsets, hp.offsets, hp.weights)).all()
     m16 = oracle_c.blend_ten(lf, hp.focused_offsets, hp.offsets, hp.weights)
     for variant in ctx.list_variants("TEN_WM"):
         ctx.set_variant("TEN_WM", variant)
-        ctx.render("TEN_WM")
-        ctx.sync()
+        poison.render(ctx, "TEN_WM")
         assert np.abs(ctx.download_views().astype(int) - m16.astype(int)).max() <= TEN_TOL_LSB
     ctx.close()
 
@@ -254,18 +241,13 @@ def test_view_range_sharding_is_exact(gpu):
     hp = gpu.build_params(cols, rows, W, H, "0,0,1,1", 0.23, 0.0, 3.0, 1.783, V)
     ctx = _ctx(gpu, cols, rows, W, H, hp)
     for method in ("STD", "TEN_WM"):
-        ctx.render(method)
-        ctx.sync()
+        poison.render(ctx, method)
         full = ctx.download_views()
         for v0, v1 in ((0, 8), (8, 16), (24, 56), (63, 64)):
-            ctx.render(method, v0=0, v1=V)  # refill
-            ctx.render(method, v0=v0, v1=v1)
-            ctx.sync()
-            assert (ctx.download_views(v0, v1) == full[v0:v1]).all()
+            assert (poison.render_range(ctx, method, v0, v1) == full[v0:v1]).all()
         # a rank that only owns rows [16,24) of the weight matrix
         ctx2 = _ctx(gpu, cols, rows, W, H, hp.rows(16, 24))
-        ctx2.render(method)
-        ctx2.sync()
+        poison.render(ctx2, method)
         assert (ctx2.download_views() == full[16:24]).all()
         ctx2.close()
     ctx.close()
@@ -285,8 +267,7 @@ def test_row_band_sharding_matches_full_render(world, gpu, oracle_c):
                     "TEN_WM": oracle_c.blend_ten(lf, hp.focused_offsets, hp.offsets, hp.weights, model=oracle_c.TEN_M16, threads=8)}
     full = _ctx(gpu, cols, rows, W, H, hp, lf=lf)
     for method in ("STD", "TEN_WM"):
-        full.render(method)
-        full.sync()
+        poison.render(full, method)
         want = full.download_views()
         got = np.zeros_like(want)
         held = []
@@ -303,8 +284,7 @@ def test_row_band_sharding_matches_full_render(world, gpu, oracle_c):
                 ctx.upload_grid(lf)          # whole-image host pointers, only the held rows are copied
             ctx.set_params(hp)
             assert ctx.grid_device_ptr()[1] == 64 * (in_rows[1] - in_rows[0]) * W * 4
-            ctx.render(method)
-            ctx.sync()
+            poison.render(ctx, method)
             part = ctx.download_views()
             assert (part[:, :band[0]] == 0).all() and (part[:, band[1]:] == 0).all()
             got |= part
@@ -337,8 +317,7 @@ def test_quilt_download(layout, gpu):
     hp = gpu.build_params(cols, rows, W, H, "0,0,1,1", 0.2, 0.0, 3.0, 1.0, V)
     ctx = _ctx(gpu, cols, rows, W, H, hp)
     ctx.set_output_layout(layout)
-    ctx.render("TEN_WM")
-    ctx.sync()
+    poison.render(ctx, "TEN_WM")
     views = ctx.download_views()
     quilt = ctx.download_quilt(4, 2, v0=1)
     for i in range(8):
@@ -349,12 +328,11 @@ def test_quilt_download(layout, gpu):
     # the same quilt from "three GPUs": contexts that hold views [0, 3), [3, 8), [8, 10) of the trajectory fill tiles 0-2, 3-7, 8-9 of a 5 x 2 quilt
     want = ctx.download_quilt(5, 2)
     ctx.close()
-    got = np.zeros_like(want)
+    got = poison.sentinel(want.shape)
     for v0, v1 in ((0, 3), (3, 8), (8, 10)):
         part = _ctx(gpu, cols, rows, W, H, hp.rows(v0, v1))
         part.set_output_layout(layout)
-        part.render("TEN_WM")
-        part.sync()
+        poison.render(part, "TEN_WM")
         part.download_quilt_tiles(got, 5, 2, v0, v1 - v0)
         with pytest.raises(gpu.LfiError, match="quilt needs"):
             part.download_quilt_tiles(got, 5, 2, 9, 2)
@@ -369,8 +347,7 @@ def test_quilt_download(layout, gpu):
     win.fill_synthetic(SEED)
     win.set_params(hp)
     win.set_output_layout(layout)
-    win.render("TEN_WM")
-    win.sync()
+    poison.render(win, "TEN_WM")
     got = np.zeros_like(want)
     win.download_quilt_tiles(got, 5, 2, 2, 6, v0=2)
     win.close()
@@ -423,8 +400,7 @@ def test_weights_outside_unit_range_use_the_generic_kernel(gpu, oracle_c):
     assert (m16[0] == 255)[..., :3].mean() > 0.5 and (m16[1][..., :3] == 0).all()
     for variant in ctx.list_variants("TEN_WM"):
         ctx.set_variant("TEN_WM", variant)
-        ctx.render("TEN_WM")
-        ctx.sync()
+        poison.render(ctx, "TEN_WM")
         assert np.abs(ctx.download_views().astype(int) - m16.astype(int)).max() <= TEN_TOL_LSB, variant
     # in-range but large weights (1 ≤ w < 2) stay on the packed path and saturate there
     hp2 = gpu.build_params(cols, rows, W, H, "0,0,1,1", 0.2, 0.0, 3.0, 1.0, V)
@@ -437,8 +413,7 @@ def test_weights_outside_unit_range_use_the_generic_kernel(gpu, oracle_c):
     assert (m16b == 255).mean() > 0.3
     for variant in ctx.list_variants("TEN_WM"):
         ctx.set_variant("TEN_WM", variant)
-        ctx.render("TEN_WM")
-        ctx.sync()
+        poison.render(ctx, "TEN_WM")
         assert np.abs(ctx.download_views().astype(int) - m16b.astype(int)).max() <= TEN_TOL_LSB, variant
     ctx.close()
 
@@ -457,8 +432,7 @@ def test_focus_map_wide_rows(shape, gpu, oracle_c):
     want0 = oracle_c.focus_estimate(lf, hp.offsets, hp.focus_map_ids, hp.focus, hp.range, hp.block_radius, threads=8)
     for variant in ctx.list_variants("FOCUS"):
         ctx.set_variant("FOCUS", variant)
-        ctx.focus_map()
-        ctx.sync()
+        poison.focus_map(ctx)
         assert (ctx.download_map(0) == want0).all(), variant
         assert (ctx.download_map(1) == oracle_c.focus_filter(want0, hp.block_radius)).all(), variant
     # an all-black grid exercises the reference's FLT_MIN initial maximum (src/kernels.cu:178): every candidate ties at
@@ -467,8 +441,7 @@ def test_focus_map_wide_rows(shape, gpu, oracle_c):
     want_black = oracle_c.focus_estimate(np.zeros_like(lf), hp.offsets, hp.focus_map_ids, hp.focus, hp.range, hp.block_radius, threads=8)
     for variant in ctx2.list_variants("FOCUS"):
         ctx2.set_variant("FOCUS", variant)
-        ctx2.focus_map()
-        ctx2.sync()
+        poison.focus_map(ctx2)
         assert (ctx2.download_map(0) == want_black).all(), variant
     ctx.close()
     ctx2.close()
@@ -492,8 +465,7 @@ def test_focus_map_realistic_geometry(radius, gpu, oracle_c):
     assert len(np.unique(want0)) > 8
     for variant in ("factored", "factored_direct", "lds"):
         ctx.set_variant("FOCUS", variant)
-        ctx.focus_map()
-        ctx.sync()
+        poison.focus_map(ctx)
         got = ctx.download_map(0)
         assert (got == want0).all(), (variant, int((got != want0).sum()))
         assert (ctx.download_map(1) == oracle_c.focus_filter(want0, hp.block_radius)).all(), variant
@@ -514,8 +486,7 @@ def test_focus_filter_window_sizes(case, gpu, oracle_c):
     lf = oracle_c.synthetic_lf(cols * rows, W, H, 5 + W)
     lf[..., 3] = 255
     ctx = _ctx(gpu, cols, rows, W, H, hp, lf=lf)
-    ctx.focus_map()
-    ctx.sync()
+    poison.focus_map(ctx)
     map0 = ctx.download_map(0)
     assert len(np.unique(map0)) > 4
     want1 = oracle_c.focus_filter(map0, hp.block_radius)
@@ -544,9 +515,10 @@ def test_focus_map_edge_shapes_both_range_passes(case, gpu, oracle_c):
     ctx = _ctx(gpu, cols, rows, W, H, hp, lf=lf)
     for variant in ("factored", "factored_direct"):
         ctx.set_variant("FOCUS", variant)
-        for _ in range(2):
-            ctx.focus_map()
-            ctx.sync()
+        byte = poison.focus_map(ctx)
+        ctx.poison(gpu.LFI_POISON_MAPS, poison.POISON[0] ^ poison.POISON[1] ^ byte)
+        ctx.focus_map()         # the second call keeps the padded planes: only the maps are poisoned before it
+        ctx.sync()
         assert (ctx.download_map(0) == want0).all() and (ctx.download_map(1) == want1).all(), variant
     ctx.close()
 
@@ -574,8 +546,7 @@ def test_focus_map_pick_and_keys_at_their_dispatch_edges(case, gpu, oracle_c):
     ctx = _ctx(gpu, cols, rows, W, H, hp, lf=lf)
     for variant in ("factored", "factored_direct"):
         ctx.set_variant("FOCUS", variant)
-        ctx.focus_map()
-        ctx.sync()
+        poison.focus_map(ctx)
         got0 = ctx.download_map(0)
         assert (got0 == want0).all(), (variant, int((got0 != want0).any(-1).sum()))
         assert (ctx.download_map(1) == want1).all(), variant
@@ -600,6 +571,7 @@ def test_focus_map_padded_planes_are_kept_between_calls(gpu, oracle_c):
 
     def check(ctx, hp, lf_now, what):
         ctx.set_params(hp)
+        ctx.poison(gpu.LFI_POISON_MAPS, poison.POISON[len(what) & 1])   # the maps only: the workspace's padded planes are what is kept
         ctx.focus_map()
         ctx.sync()
         want0 = oracle_c.focus_estimate(lf_now, hp.offsets, hp.focus_map_ids, hp.focus, hp.range, hp.block_radius, threads=8)
@@ -652,20 +624,13 @@ def test_random_shapes_default_kernels(case, gpu, oracle_c):
     ctx = _ctx(gpu, cols, rows, W, H, hp, lf=lf)
     want_std = oracle_c.blend_std(lf, hp.focused_offsets, hp.offsets, hp.weights)
     want_ten = oracle_c.blend_ten(lf, hp.focused_offsets, hp.offsets, hp.weights, model=oracle_c.TEN_M16)
-    ctx.render("STD")
-    ctx.sync()
+    poison.render(ctx, "STD")
     assert (ctx.download_views() == want_std).all()
-    ctx.render("TEN_WM")
-    ctx.sync()
+    poison.render(ctx, "TEN_WM")
     assert np.abs(ctx.download_views().astype(int) - want_ten.astype(int)).max() <= TEN_TOL_LSB
-    if V >= 3:      # a view sub-range leaves the other views untouched
-        before = ctx.download_views()
+    if V >= 3:      # a view sub-range leaves the other views untouched (render_range: they still hold the poison)
         v0, v1 = 1, V - 1
-        ctx.render("STD", v0=v0, v1=v1)
-        ctx.sync()
-        after = ctx.download_views()
-        assert (after[v0:v1] == want_std[v0:v1]).all()
-        assert (after[:v0] == before[:v0]).all() and (after[v1:] == before[v1:]).all()
+        assert (poison.render_range(ctx, "STD", v0, v1) == want_std[v0:v1]).all()
     ctx.close()
 
 
@@ -711,16 +676,14 @@ def test_std_rounding_band_adversarial(kind, gpu, oracle_c):
         ctx = _ctx(gpu, cols, rows, W, H, hp, lf=lf, flags=flags)
         for variant in ("auto", "wave_m2_nt", "persist_m2_nt") if flags == 0 else ("auto",):
             ctx.set_variant("STD", variant)
-            ctx.render("STD")
-            ctx.sync()
+            poison.render(ctx, "STD")
             got = ctx.download_views()
             assert (got == want).all(), (kind, variant, flags, int((got != want).sum()))
         # the planar view layout: blend_stdx with ONE chunk of images writes the byte planes itself (round 4; blend_planar<STDF> would need an
         # RGBA scratch copy of the views and a conversion pass)
         ctx.set_variant("STD", "auto")
         ctx.set_output_layout("planar")
-        ctx.render("STD")
-        ctx.sync()
+        poison.render(ctx, "STD")
         if kind != "sum_above_2":   # (weights summing above 2: the exact kernel through the scratch copy, as in the RGBA layout)
             assert ctx.last_kernel_name() == "blend_stdx<STD>" and ctx.memory_info().workspace_bytes == 0
         got = ctx.download_views()
@@ -769,29 +732,23 @@ def test_std_band_method_over_several_chunks(cols, rows, W, H, V, kind, gpu, ora
     want = oracle_c.blend_std(lf, hp.focused_offsets, hp.offsets, hp.weights, threads=8)
     for flags in (0, gpu.LFI_FLAG_STD_ANALYTIC_BAND, gpu.LFI_FLAG_SINGLE_SWEEP_DIRECTION):
         ctx = _ctx(gpu, cols, rows, W, H, hp, lf=lf, flags=flags)
-        ctx.render("STD")
-        ctx.sync()
+        poison.render(ctx, "STD")
         assert ctx.last_kernel_name() == "blend_stdx<STD>"
         got = ctx.download_views()
         assert (got == want).all(), (kind, flags, int((got != want).sum()))
         if flags == 0:
-            ctx.render("STD")          # the second launch walks the image in the other direction
-            ctx.sync()
+            poison.render(ctx, "STD")          # the second launch walks the image in the other direction
             assert (ctx.download_views() == want).all(), (kind, "reverse sweep")
             v0, v1 = V // 3, V // 3 + min(20, V - V // 3)
-            ctx.render("STD", v0=v0, v1=v1)
-            ctx.sync()
-            assert (ctx.download_views(v0, v1) == want[v0:v1]).all(), (kind, "view range")
+            assert (poison.render_range(ctx, "STD", v0, v1) == want[v0:v1]).all(), (kind, "view range")
             ctx.set_output_layout("planar")      # byte planes written by blend_stdx itself (round 4; before: RGBA scratch + conversion)
-            ctx.render("STD")
-            ctx.sync()
+            poison.render(ctx, "STD")
             assert ctx.last_kernel_name() == "blend_stdx<STD>"
             assert ctx.memory_info().workspace_bytes == 0, "no RGBA scratch copy of the views"
             assert (ctx.download_views() == want).all(), (kind, "planar layout")
-            ctx.render("STD")                    # the other sweep direction
-            ctx.render("STD", v0=v0, v1=v1)      # and a view range over it
-            ctx.sync()
-            assert (ctx.download_views() == want).all(), (kind, "planar layout, reverse sweep + view range")
+            poison.render(ctx, "STD")            # the other sweep direction
+            assert (ctx.download_views() == want).all(), (kind, "planar layout, reverse sweep")
+            assert (poison.render_range(ctx, "STD", v0, v1) == want[v0:v1]).all(), (kind, "planar layout, view range")
         ctx.close()
 
 
@@ -841,30 +798,24 @@ def test_all_focus_std_band_method(cols, rows, W, H, V, kind, gpu, oracle_c):
     for flags in (0, gpu.LFI_FLAG_STD_ANALYTIC_BAND):
         ctx = _ctx(gpu, cols, rows, W, H, hp, lf=lf, flags=flags)
         ctx.upload_map(1, m)                   # Standard::process<true> reads map 1 (src/kernels.cu:326)
-        ctx.render("STD", all_focus=True)
-        ctx.sync()
+        poison.render(ctx, "STD", all_focus=True)
         assert ctx.last_kernel_name() == "blend_stdxa<STD,allfocus>"
         got = ctx.download_views()
         assert (got == want).all(), (kind, flags, int((got != want).sum()))
         if n > 128:
             ctx.set_variant("STD", "filtered_gather_once")
-            ctx.render("STD", all_focus=True)
-            ctx.sync()
+            poison.render(ctx, "STD", all_focus=True)
             assert ctx.last_kernel_name() == "blend_afs<STD,allfocus>" and (ctx.download_views() == want).all(), (kind, flags, "blend_afs")
             ctx.set_variant("STD", "auto")
         if flags == 0:
             v0, v1 = V // 3, V // 3 + min(20, V - V // 3)
-            ctx.render("STD", all_focus=True, v0=v0, v1=v1)
-            ctx.sync()
-            assert (ctx.download_views(v0, v1) == want[v0:v1]).all(), (kind, "view range")
+            assert (poison.render_range(ctx, "STD", v0, v1, all_focus=True) == want[v0:v1]).all(), (kind, "view range")
             ctx.set_variant("STD", "wave_m2_nt")          # the exact-fp32 kernel agrees
-            ctx.render("STD", all_focus=True)
-            ctx.sync()
+            poison.render(ctx, "STD", all_focus=True)
             assert ctx.last_kernel_name() == "blend_persist<STD,allfocus>" and (ctx.download_views() == want).all()
             ctx.set_variant("STD", "auto")
             ctx.set_output_layout("planar")               # round 4: blend_stdxa writes the byte planes itself (quad transposes, byte patches into planes)
-            ctx.render("STD", all_focus=True)
-            ctx.sync()
+            poison.render(ctx, "STD", all_focus=True)
             assert ctx.last_kernel_name() == "blend_stdxa<STD,allfocus>" and ctx.memory_info().workspace_bytes == 0
             assert (ctx.download_views() == want).all(), (kind, "planar layout")
         ctx.close()
@@ -877,8 +828,7 @@ def test_all_focus_std_band_method(cols, rows, W, H, V, kind, gpu, oracle_c):
         ctx.upload_grid(lf)
         ctx.set_params(hp)
         ctx.upload_map(1, m)
-        ctx.render("STD", all_focus=True)
-        ctx.sync()
+        poison.render(ctx, "STD", all_focus=True)
         assert (ctx.download_views()[:, band[0]:band[1]] == want[:, band[0]:band[1]]).all(), (kind, "row band")
         ctx.close()
 
@@ -893,8 +843,7 @@ def test_std_analytic_band_flag(gpu, oracle_c):
     want = oracle_c.blend_std(lf, hp.focused_offsets, hp.offsets, hp.weights)
     for flags in (0, gpu.LFI_FLAG_STD_ANALYTIC_BAND, gpu.LFI_FLAG_STD_MEASURED_BAND):
         ctx = _ctx(gpu, cols, rows, W, H, hp, lf=lf, flags=flags)
-        ctx.render("STD")
-        ctx.sync()
+        poison.render(ctx, "STD")
         assert ctx.last_kernel_name() == "blend_planar<STDF>"
         assert (ctx.download_views() == want).all(), flags
         ctx.close()
@@ -1029,13 +978,11 @@ def test_std_band_self_check_on_the_device(gpu, oracle_c):
     want_af = oracle_c.blend_std(lf, hp.focused_offsets, hp.offsets, hp.weights, all_focus=True, map_plane=map1, focus=hp.focus, rng=hp.range, threads=8)
     for flags, forced in ((0, False), (gpu.LFI_FLAG_STD_BAND_PROBE_FAIL, True), (gpu.LFI_FLAG_STD_BAND_PROBE_FAIL | gpu.LFI_FLAG_STD_ANALYTIC_BAND, False)):
         ctx = _ctx(gpu, cols, rows, W, H, hp, lf=lf, flags=flags)
-        ctx.render("STD")
-        ctx.sync()
+        poison.render(ctx, "STD")
         assert ctx.last_kernel_name() == "blend_stdx<STD>"
         assert (ctx.download_views() == want).all(), flags
         ctx.upload_map(1, map1)
-        ctx.render("STD", all_focus=True)
-        ctx.sync()
+        poison.render(ctx, "STD", all_focus=True)
         assert (ctx.download_views() == want_af).all(), (flags, "all-focus")
         info = ctx.std_band_info()
         assert info.probed == 1 and info.within_budget == 1 and info.sums >= 20000 and 0.0 < info.worst_fraction <= 1.0, info.message
@@ -1079,8 +1026,7 @@ def test_std_near_half_integer_sums_from_precise_weights(gpu, oracle_c):
     want = oracle_c.blend_std(lf, hp.focused_offsets, hp.offsets, hp.weights)
     for variant in ("auto", "wave_m2_nt"):
         ctx.set_variant("STD", variant)
-        ctx.render("STD")
-        ctx.sync()
+        poison.render(ctx, "STD")
         got = ctx.download_views()
         assert (got == want).all(), (variant, int((got != want).sum()))
     ctx.set_variant("STD", "auto")
@@ -1099,13 +1045,11 @@ def test_row_band_sharding_all_focus(world, gpu, oracle_c):
     hp = gpu.build_params(cols, rows, W, H, "0.071,0.071,0.93,0.93", 0.05, 0.12, 7.0, 1.783, V)
     lf = oracle_c.synthetic_lf(64, W, H, SEED)
     full = _ctx(gpu, cols, rows, W, H, hp, lf=lf)
-    full.focus_map()
-    full.sync()
+    poison.focus_map(full)
     want_maps = (full.download_map(0), full.download_map(1))
     want = {}
     for method in ("STD", "TEN_WM"):
-        full.render(method, all_focus=True)
-        full.sync()
+        poison.render(full, method, all_focus=True)
         want[method] = full.download_views()
     full.close()
     got = {m: np.zeros_like(want[m]) for m in want}
@@ -1120,21 +1064,18 @@ def test_row_band_sharding_all_focus(world, gpu, oracle_c):
         ctx.set_row_window(band[0], band[1], in_rows[0], in_rows[1])
         ctx.upload_grid(lf)
         ctx.set_params(hp)
-        ctx.focus_map()
-        ctx.sync()
+        poison.focus_map(ctx)
         m0, m1 = ctx.download_map(0), ctx.download_map(1)
         assert (m0[band[0]:band[1]] == want_maps[0][band[0]:band[1]]).all()
         assert (m1[band[0]:band[1]] == want_maps[1][band[0]:band[1]]).all()
         got_map1[band[0]:band[1]] = m1[band[0]:band[1]]
         for method in ("STD", "TEN_WM"):
-            ctx.render(method, all_focus=True)
-            ctx.sync()
+            poison.render(ctx, method, all_focus=True)
             part = ctx.download_views()
             got[method] |= part
             # the band into the planar view layout (round 4: the all-focus kernels write the byte planes themselves): the same bytes
             ctx.set_output_layout("planar")
-            ctx.render(method, all_focus=True)
-            ctx.sync()
+            poison.render(ctx, method, all_focus=True)
             assert (ctx.download_views() == part).all(), (method, "planar views of the band", rank)
             ctx.set_output_layout("rgba")
         ctx.close()

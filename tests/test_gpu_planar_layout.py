@@ -8,6 +8,7 @@ of the RGBA layout."""
 import numpy as np
 import pytest
 
+import poison
 from conftest import GOLDEN_DIR, SEED, SMALL_CASES
 import os
 
@@ -38,25 +39,21 @@ def test_golden_fixtures_planar_layout(case, gpu):
     vl = ctx.view_layout()
     assert vl.layout == gpu.LFI_LAYOUT_PLANAR_RGB and vl.row_pitch_bytes % 16 == 0 and vl.row_pitch_bytes >= W
     assert vl.view_stride_bytes == 3 * H * vl.row_pitch_bytes and ctx.views_device_ptr()[1] == V * vl.view_stride_bytes
-    ctx.render("TEN_WM")
-    ctx.sync()
+    poison.render(ctx, "TEN_WM")
     assert ctx.last_kernel_name() == "blend_p3<TEN_WM>"
     out = ctx.download_views()
     assert np.abs(out.astype(int) - g["ten_m16"].astype(int)).max() <= TEN_TOL_LSB
     assert (out[..., 3] == 255).all()
     assert (out != g["ten_exact"]).mean() < 1e-3
     # STD: blend_stdx writes the byte planes itself (round 4); all-focus renders go through the RGBA kernels and a conversion: same bytes as ever
-    ctx.render("STD")
-    ctx.sync()
+    poison.render(ctx, "STD")
     assert ctx.last_kernel_name() == "blend_stdx<STD>"
     assert (ctx.download_views() == g["std"]).all()
     ctx.focus_map()
-    ctx.render("STD", all_focus=True)
-    ctx.sync()
+    poison.render(ctx, "STD", all_focus=True)
     assert (ctx.download_views() == g["af_std"]).all()
     ws_before = ctx.memory_info().workspace_bytes
-    ctx.render("TEN_WM", all_focus=True)
-    ctx.sync()
+    poison.render(ctx, "TEN_WM", all_focus=True)
     # round 4: blend_persist writes the byte planes itself (quad transposes in its epilogue): no growth of the RGBA scratch copy
     assert ctx.last_kernel_name() == "blend_persist<TEN_WM,allfocus>" and ctx.memory_info().workspace_bytes == ws_before
     assert np.abs(ctx.download_views().astype(int) - g["af_ten_m16_map0"].astype(int)).max() <= TEN_TOL_LSB
@@ -75,16 +72,13 @@ def test_ragged_shapes_planar_equals_rgba(shape, gpu, oracle_c):
     lf = oracle_c.synthetic_lf(cols * rows, W, H, SEED)
     m16 = oracle_c.blend_ten(lf, hp.focused_offsets, hp.offsets, hp.weights, threads=8)
     rgba = _ctx(gpu, cols, rows, W, H, hp, layout="rgba")
-    rgba.render("TEN_WM")
-    rgba.sync()
+    poison.render(rgba, "TEN_WM")
     want = rgba.download_views()
-    rgba.render("STD")
-    rgba.sync()
+    poison.render(rgba, "STD")
     want_std = rgba.download_views()
     rgba.close()
     ctx = _ctx(gpu, cols, rows, W, H, hp)
-    ctx.render("TEN_WM")
-    ctx.sync()
+    poison.render(ctx, "TEN_WM")
     assert ctx.last_kernel_name() == "blend_p3<TEN_WM>"
     got = ctx.download_views()
     assert np.abs(got.astype(int) - m16.astype(int)).max() <= TEN_TOL_LSB
@@ -93,17 +87,13 @@ def test_ragged_shapes_planar_equals_rgba(shape, gpu, oracle_c):
     for flags in (0, gpu.LFI_FLAG_SINGLE_SWEEP_DIRECTION):
         ctx.set_params(hp, flags)
         for _ in range(3):
-            ctx.render("TEN_WM")
-            ctx.sync()
+            poison.render(ctx, "TEN_WM")
             assert (ctx.download_views() == want).all()
     ctx.set_params(hp)
     # a second launch over a sub-range leaves the other views alone and reproduces its own
     v0, v1 = V // 3, max(V // 3 + 1, (2 * V) // 3)
-    ctx.render("TEN_WM", v0=v0, v1=v1)
-    ctx.sync()
-    assert (ctx.download_views() == want).all()
-    ctx.render("STD")
-    ctx.sync()
+    assert (poison.render_range(ctx, "TEN_WM", v0, v1) == want[v0:v1]).all()
+    poison.render(ctx, "STD")
     assert (ctx.download_views() == want_std).all()
     ctx.close()
 
@@ -115,8 +105,7 @@ def test_planar_layout_offsets_larger_than_image(gpu, oracle_c):
     lf = oracle_c.synthetic_lf(225, W, H, 5)
     ctx = _ctx(gpu, cols, rows, W, H, hp, seed=5)
     m16 = oracle_c.blend_ten(lf, hp.focused_offsets, hp.offsets, hp.weights)
-    ctx.render("TEN_WM")
-    ctx.sync()
+    poison.render(ctx, "TEN_WM")
     assert ctx.last_kernel_name() == "blend_p3<TEN_WM>"
     assert np.abs(ctx.download_views().astype(int) - m16.astype(int)).max() <= TEN_TOL_LSB
     ctx.close()
@@ -132,8 +121,7 @@ def test_planar_layout_weights_outside_unit_range_fall_back(gpu, oracle_c):
     hp.weights = w.view(np.uint16)
     lf = oracle_c.synthetic_lf(16, W, H, SEED)
     ctx = _ctx(gpu, cols, rows, W, H, hp)
-    ctx.render("TEN_WM")
-    ctx.sync()
+    poison.render(ctx, "TEN_WM")
     assert ctx.last_kernel_name() != "blend_p3<TEN_WM>"
     m16 = oracle_c.blend_ten(lf, hp.focused_offsets, hp.offsets, hp.weights)
     assert np.abs(ctx.download_views().astype(int) - m16.astype(int)).max() <= TEN_TOL_LSB
@@ -153,11 +141,9 @@ def test_planar_layout_row_bands(world, cols, W, gpu, oracle_c):
     lf = oracle_c.synthetic_lf(cols * rows, W, H, SEED)
     m16 = oracle_c.blend_ten(lf, hp.focused_offsets, hp.offsets, hp.weights, model=oracle_c.TEN_M16, threads=8)
     full = _ctx(gpu, cols, rows, W, H, hp, layout="rgba")
-    full.render("TEN_WM")
-    full.sync()
+    poison.render(full, "TEN_WM")
     want = full.download_views()
-    full.render("STD")
-    full.sync()
+    poison.render(full, "STD")
     want_std = full.download_views()
     full.close()
     got = np.zeros_like(want)
@@ -172,14 +158,12 @@ def test_planar_layout_row_bands(world, cols, W, gpu, oracle_c):
         ctx.set_params(hp)
         ctx.set_output_layout("planar")
         assert ctx.view_layout().rows == band[1] - band[0]
-        ctx.render("TEN_WM")
-        ctx.sync()
+        poison.render(ctx, "TEN_WM")
         assert ctx.last_kernel_name() == "blend_p3<TEN_WM>"
         part = ctx.download_views()
         assert (part[:, :band[0]] == 0).all() and (part[:, band[1]:] == 0).all()
         got |= part
-        ctx.render("STD")           # round 4: blend_stdx writes the band's byte planes itself (one chunk of images or several)
-        ctx.sync()
+        poison.render(ctx, "STD")   # round 4: blend_stdx writes the band's byte planes itself (one chunk of images or several)
         assert ctx.last_kernel_name() == "blend_stdx<STD>"
         got_std |= ctx.download_views()
         ctx.close()
@@ -201,17 +185,14 @@ def test_planar_layout_three_and_more_view_passes(V, W, H, gpu, oracle_c):
     m16 = oracle_c.blend_ten(lf, hp.focused_offsets, hp.offsets, hp.weights, model=oracle_c.TEN_M16, threads=8)
     ctx = _ctx(gpu, cols, rows, W, H, hp, lf=lf)
     for sweep in range(2):
-        ctx.render("TEN_WM")
-        ctx.sync()
+        poison.render(ctx, "TEN_WM")
         assert ctx.last_kernel_name() == "blend_p3<TEN_WM>"
         got = ctx.download_views()
         assert np.abs(got.astype(int) - m16.astype(int)).max() <= TEN_TOL_LSB, sweep
-    ctx.render("TEN_WM", v0=5, v1=V - 3)            # 3 or 4 passes from an odd first view
-    ctx.sync()
-    assert (ctx.download_views(5, V - 3) == got[5:V - 3]).all()
+    # 3 or 4 passes from an odd first view
+    assert (poison.render_range(ctx, "TEN_WM", 5, V - 3) == got[5:V - 3]).all()
     ctx.set_output_layout("rgba")
-    ctx.render("TEN_WM")
-    ctx.sync()
+    poison.render(ctx, "TEN_WM")
     assert (ctx.download_views() == got).all()
     ctx.close()
     if H >= 7:
@@ -223,8 +204,7 @@ def test_planar_layout_three_and_more_view_passes(V, W, H, gpu, oracle_c):
         ctx.upload_grid(lf)
         ctx.set_params(hp)
         ctx.set_output_layout("planar")
-        ctx.render("TEN_WM")
-        ctx.sync()
+        poison.render(ctx, "TEN_WM")
         assert (ctx.download_views()[:, band[0]:band[1]] == got[:, band[0]:band[1]]).all()
         ctx.close()
 
@@ -244,12 +224,10 @@ def test_contexts_after_planar_view_contexts_render_correctly(gpu, oracle_c):
             ctx = _ctx(gpu, cols, rows, W, H, hp, layout="rgba")
             for variant in ("persist_m2_nt", "auto"):
                 ctx.set_variant("TEN_WM", variant)
-                ctx.render("TEN_WM")
-                ctx.sync()
+                poison.render(ctx, "TEN_WM")
                 assert np.abs(ctx.download_views().astype(int) - m16.astype(int)).max() <= TEN_TOL_LSB, (cols, W, rep, variant)
             ctx.set_output_layout("planar")
-            ctx.render("TEN_WM")
-            ctx.sync()
+            poison.render(ctx, "TEN_WM")
             assert np.abs(ctx.download_views().astype(int) - m16.astype(int)).max() <= TEN_TOL_LSB, (cols, W, rep, "planar")
             ctx.close()
 
@@ -265,8 +243,7 @@ def test_planar_layout_quilt_and_attached_views(gpu):
     with pytest.raises(gpu.LfiError):
         ctx.attach_views(buf.data_ptr(), buf.numel() - 1)
     ctx.attach_views(buf.data_ptr(), buf.numel())
-    ctx.render("TEN_WM")
-    ctx.sync()
+    poison.render(ctx, "TEN_WM")
     views = ctx.download_views()
     quilt = ctx.download_quilt(3, 2)
     for v in range(V):
@@ -277,7 +254,6 @@ def test_planar_layout_quilt_and_attached_views(gpu):
     assert (planes.transpose(0, 2, 3, 1) == views[..., :3]).all()
     # back to the reference's layout: views are reallocated, renders write RGBA again
     ctx.set_output_layout("rgba")
-    ctx.render("TEN_WM")
-    ctx.sync()
+    poison.render(ctx, "TEN_WM")
     assert ctx.last_kernel_name().startswith("blend_planar") and (ctx.download_views() == views).all()
     ctx.close()

@@ -8,6 +8,7 @@ import sys
 import numpy as np
 import pytest
 
+import poison
 from conftest import ROOT, SEED
 
 pytestmark = pytest.mark.gpu
@@ -172,8 +173,7 @@ def test_pinned_host_buffers(gpu, oracle_c):
     pin_in[...] = lf
     ctx.upload_grid(pin_in)
     ctx.set_params(hp)
-    ctx.render("STD")
-    ctx.sync()
+    poison.render(ctx, "STD")
     want = ctx.download_views()
     pin_out = ctx.pinned_empty(want.shape)
     got = ctx.download_views(out=pin_out)
@@ -235,35 +235,35 @@ def test_input_changes_reach_the_renders(gpu, oracle_c):
     ctx.set_grid(cols, rows, W, H)
     ctx.upload_grid(lf_a)
     ctx.set_params(hp)
-    ctx.render("TEN_WM"); ctx.sync()
+    poison.render(ctx, "TEN_WM")
     assert close(ctx.download_views(), lf_a)
     ctx.upload_image(3, lf_b[3])                       # one image replaced through the ABI
     mixed = lf_a.copy(); mixed[3] = lf_b[3]
-    ctx.render("TEN_WM"); ctx.sync()
+    poison.render(ctx, "TEN_WM")
     assert close(ctx.download_views(), mixed)
     ctx.fill_synthetic(0x77)                           # all of them regenerated on the device
-    ctx.render("TEN_WM"); ctx.sync()
+    poison.render(ctx, "TEN_WM")
     assert close(ctx.download_views(), oracle_c.synthetic_lf(cols * rows, W, H, 0x77))
     # caller-owned planes: no announcement yet → every launch reads them as they are
     t = torch.from_numpy(lf_a).cuda()
     ctx.attach_grid(t.data_ptr(), t.numel())
-    ctx.render("TEN_WM"); ctx.sync()
+    poison.render(ctx, "TEN_WM")
     assert close(ctx.download_views(), lf_a)
     t.copy_(torch.from_numpy(lf_b)); torch.cuda.synchronize()
-    ctx.render("TEN_WM"); ctx.sync()
+    poison.render(ctx, "TEN_WM")
     assert close(ctx.download_views(), lf_b)
     # from the first announcement on, the copy is used and refreshed on every further announcement
     ctx.grid_modified()
-    ctx.render("TEN_WM"); ctx.sync()
+    poison.render(ctx, "TEN_WM")
     assert close(ctx.download_views(), lf_b)
     t.copy_(torch.from_numpy(lf_a)); torch.cuda.synchronize()
     ctx.grid_modified()
-    ctx.render("TEN_WM"); ctx.sync()
+    poison.render(ctx, "TEN_WM")
     assert close(ctx.download_views(), lf_a)
     # a new parameter set with larger offsets rebuilds the copy with more padding
     hp2 = gpu.build_params(cols, rows, W, H, "0.1,0.2,0.8,0.9", 0.9, 0.0, 2.0, 1.5, 8)
     ctx.set_params(hp2)
-    ctx.render("TEN_WM"); ctx.sync()
+    poison.render(ctx, "TEN_WM")
     w2 = oracle_c.blend_ten(lf_a, hp2.focused_offsets, hp2.offsets, hp2.weights, model=oracle_c.TEN_M16)
     assert np.abs(ctx.download_views().astype(int) - w2.astype(int)).max() <= 1
     ctx.close()
@@ -282,8 +282,7 @@ def test_stream_switch_orders_derived_state(gpu):
     ref.set_grid(cols, rows, W, H)
     ref.fill_synthetic(31)
     ref.set_params(hp)
-    ref.render("TEN_WM")
-    ref.sync()
+    poison.render(ref, "TEN_WM")
     want = ref.download_views()
     ref.close()
     ctx = gpu.Context(0)
@@ -318,16 +317,16 @@ def test_render_stream_matches_block_by_block_renders(gpu, oracle_c):
         for b in range(0, total, V):
             hp = hp_all.rows(b, min(b + V, total))
             ctx.set_params(hp)
-            ctx.render(method)
-            ctx.sync()
+            poison.render(ctx, method)
             want[b:b + hp.weights.shape[0]] = ctx.download_views()
         ctx.set_params(hp_all.rows(0, V))                    # the block size of the stream = the views of the parameters
         out = ctx.pinned_empty((total, H, W, 4))
-        out[...] = 0
+        out[...] = poison.SENTINEL
         ctx.render_stream(method, hp_all.weights, out)
         assert (out == want).all(), method
         if method == "STD":
             assert (want == oracle_c.blend_std(lf, hp_all.focused_offsets, hp_all.offsets, hp_all.weights)).all()
+        ctx.poison(poison.RENDER, poison.POISON[0])
         ctx.render_stream(method, hp_all.weights, None)     # render only: the last block's views stay on the device
         assert (ctx.download_views(0, total - (total // V) * V) == want[(total // V) * V:]).all()
     ctx.close()
@@ -364,13 +363,11 @@ def test_compare_view_psnr_ssim(gpu, oracle_c):
     ctx.set_grid(cols, rows, W, H)
     ctx.upload_grid(lf)
     ctx.set_params(hp)
-    ctx.render("STD")
-    ctx.sync()
+    poison.render(ctx, "STD")
     std = ctx.download_views()
     for layout in ("rgba", "planar"):
         ctx.set_output_layout(layout)
-        ctx.render("TEN_WM")
-        ctx.sync()
+        poison.render(ctx, "TEN_WM")
         ten = ctx.download_view(1)
         for ref in (std[1], lf[3], ten):
             q = ctx.compare_view(1, ref)
@@ -403,19 +400,16 @@ def test_prepare_memory_info_and_partial_fills(gpu, oracle_c):
     # ONE padded byte plane per image and channel (round 3; rounds 1–2 kept four byte-shifted copies: 12 B per pixel·image)
     assert 3 * 16 * W * H <= mi.derived_bytes <= 3 * 16 * (W + 2 * 300) * H and mi.derived_build_ms > 0
     assert mi.derived_bytes < mi.grid_bytes * 3
-    ctx.render("STD")
-    ctx.sync()
+    poison.render(ctx, "STD")
     lf = oracle_c.synthetic_lf(16, W, H, SEED)
     assert (ctx.download_views() == oracle_c.blend_std(lf, hp.focused_offsets, hp.offsets, hp.weights)).all()
     with pytest.raises(gpu.LfiError):
         ctx.fill_synthetic(SEED, 3, 17)
     ctx.fill_synthetic_scene(SEED)
-    ctx.render("STD")
-    ctx.sync()
+    poison.render(ctx, "STD")
     scene = ctx.download_views()
     assert (scene[..., 3] == 255).all() and (scene != oracle_c.blend_std(lf, hp.focused_offsets, hp.offsets, hp.weights)).any()
-    ctx.focus_map()
-    ctx.sync()
+    poison.focus_map(ctx)
     assert len(np.unique(ctx.download_map(0)[..., 0])) >= 1
     ctx.close()
 
@@ -441,8 +435,7 @@ def test_set_params_in_place_is_stream_ordered(gpu, oracle_c):
         got = ctx.download_views()                          # (synchronises)
         assert (got == want[i]).all(), (i, int((got != want[i]).sum()))
     # TEN_WM after the sweep came round: the first parameters again
-    ctx.render("TEN_WM")
-    ctx.sync()
+    poison.render(ctx, "TEN_WM")
     m16 = oracle_c.blend_ten(lf, hps[0].focused_offsets, hps[0].offsets, hps[0].weights, model=oracle_c.TEN_M16, threads=8)
     assert np.abs(ctx.download_views().astype(int) - m16.astype(int)).max() <= 1
     ctx.close()
@@ -486,13 +479,13 @@ def test_replaced_images_refresh_only_their_planes(gpu, oracle_c):
     def check(cur, what):
         for layout in ("rgba", "planar"):
             ctx.set_output_layout(layout)
-            ctx.render("STD"); ctx.sync()
+            poison.render(ctx, "STD")
             assert (ctx.download_views() == oracle_c.blend_std(cur, hp.focused_offsets, hp.offsets, hp.weights, threads=8)).all(), (what, layout, "STD")
-            ctx.render("TEN_WM"); ctx.sync()
+            poison.render(ctx, "TEN_WM")
             m16 = oracle_c.blend_ten(cur, hp.focused_offsets, hp.offsets, hp.weights, model=oracle_c.TEN_M16, threads=8)
             assert np.abs(ctx.download_views().astype(int) - m16.astype(int)).max() <= 1, (what, layout, "TEN_WM")
         ctx.set_output_layout("rgba")
-        ctx.focus_map(); ctx.sync()
+        poison.focus_map(ctx)
         map0 = oracle_c.focus_estimate(cur, hp.offsets, hp.focus_map_ids, hp.focus, hp.range, hp.block_radius, threads=8)
         assert (ctx.download_map(0) == map0).all(), (what, "map")
 
@@ -543,9 +536,9 @@ def test_release_inputs(cols, rows, V, gpu, oracle_c):
     def check(cur, p, what):
         for layout in ("rgba", "planar"):
             ctx.set_output_layout(layout)
-            ctx.render("STD"); ctx.sync()
+            poison.render(ctx, "STD")
             assert (ctx.download_views() == oracle_c.blend_std(cur, p.focused_offsets, p.offsets, p.weights, threads=8)).all(), (what, layout, "STD")
-            ctx.render("TEN_WM"); ctx.sync()
+            poison.render(ctx, "TEN_WM")
             m16 = oracle_c.blend_ten(cur, p.focused_offsets, p.offsets, p.weights, model=oracle_c.TEN_M16, threads=8)
             assert np.abs(ctx.download_views().astype(int) - m16.astype(int)).max() <= 1, (what, layout, "TEN_WM")
         ctx.set_output_layout("rgba")
@@ -577,7 +570,7 @@ def test_release_inputs(cols, rows, V, gpu, oracle_c):
     ctx.set_grid(cols, rows, W, H)
     ctx.upload_grid(cur)
     ctx.set_params(hp_large)
-    ctx.render("STD", all_focus=False); ctx.sync()
+    poison.render(ctx, "STD", all_focus=False)
     assert (ctx.download_views() == oracle_c.blend_std(cur, hp_large.focused_offsets, hp_large.offsets, hp_large.weights, threads=8)).all()
     ctx.close()
     # release, upload, a LARGER row window, release, upload (the one-image staging plane kept the first window's size and the second
@@ -594,7 +587,7 @@ def test_release_inputs(cols, rows, V, gpu, oracle_c):
         for g in (1, n - 2):
             cur[g] = other[g]
             ctx.upload_image(g, other[g])
-        ctx.render("STD"); ctx.sync()
+        poison.render(ctx, "STD")
         want = oracle_c.blend_std(cur, hp_small.focused_offsets, hp_small.offsets, hp_small.weights, threads=8)
         assert (ctx.download_views()[:, band[0]:band[1]] == want[:, band[0]:band[1]]).all(), band
     ctx.close()
