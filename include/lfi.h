@@ -194,6 +194,24 @@ int lfi_fill_synthetic_scene(lfi_ctx *ctx, uint32_t seed);
  * enqueued keep the parameters they were enqueued with, later ones see the new ones, and the context's stream is not drained.  A call
  * that changes the number of views synchronises and reallocates. */
 int lfi_set_params(lfi_ctx *ctx, const lfi_params *params);
+/* Per-view focus: focal stacks (one camera position at V focus values) and focus pulls (the focus changing along the trajectory) in
+ * one launch.  No counterpart in the reference, whose kernels apply one focus to all views (focusedOffsets, src/interpolator.cu:226-246).
+ * focused_offsets_vn is [views][N] (host memory, copied before the call returns): view v of a fixed-focus render samples image g at
+ * pixel + focused_offsets_vn[v][g] instead of pixel + lfi_params.focused_offsets[g] — row v of round(offset_g * f_v) for a focus f_v per
+ * view (lfi_host_build_view_offsets).  Weights, clamping and the numerics of both methods are those of the ordinary render.
+ *  - call after lfi_set_params; views must equal lfi_params.views (else LFI_EINVAL).  NULL clears the per-view offsets; so does any
+ *    later lfi_set_params, lfi_set_grid or lfi_set_row_window;
+ *  - stream-ordered, like lfi_set_params: the offsets go to the device through page-locked staging behind the work already enqueued, so
+ *    renders enqueued before the call keep the offsets they were enqueued with and the stream is not drained;
+ *  - with a row window, the held input rows must cover every row any view samples (else LFI_EINVAL);
+ *  - while they are set, lfi_render (all_focus = 0), lfi_prepare and lfi_benchmark launch one kernel for all views of the range
+ *    (csrc/hip/blend_vfocus.hpp; lfi_last_kernel_name names it, lfi_set_variant choices do not apply) — a vector-pipe gather-blend:
+ *    STD is bit-exact, TEN_WM is the fp32-accumulated sum rounded once to fp16 and truncated (the TEN_WM contract) and does NOT use the
+ *    matrix cores.  Downloads, quilts, lfi_compare_view, both view layouts and attached views work unchanged.  All-focus renders,
+ *    lfi_render_stream, lfi_download_prequant and LFI_FLAG_TEN_ROUND_PER_BATCH return LFI_EINVAL;
+ *  - after lfi_release_inputs, renders are served while the planar copy's padding covers every per-view horizontal shift (else LFI_EINVAL).
+ * Shifts beyond the image are clamped to ±width / ±height (the same samples: every pixel then reads the edge). */
+int lfi_set_view_offsets(lfi_ctx *ctx, const lfi_int2 *focused_offsets_vn, int views);
 /* Device layout of the rendered views.  LFI_LAYOUT_RGBA (default): [V][rows][W] RGBA8 dwords — the linear image of the
  * reference's 64 output surfaces.  LFI_LAYOUT_PLANAR_RGB (opt-in): alpha-free byte planes [V][3: R,G,B][rows][pitch] — the alpha
  * the reference's kernels write is the constant 255 (uchar4{…, 255}, src/kernels.cu:393, :309), a quarter of the bytes a render

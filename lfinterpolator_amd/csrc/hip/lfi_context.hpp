@@ -142,6 +142,18 @@ struct lfi_ctx
     mutable const char *last_kernel = ""; // the blend kernel the last render launched (lfi_last_kernel_name)
     mutable unsigned sweep_launches = 0;  // blend_p3 / blend_planar alternate their sweep direction from launch to launch
     float derived_build_ms = 0.0f;        // duration of the last planar_build (measured by lfi_prepare only)
+    // lfi_set_view_offsets: one integer offset per (view, image) on the device, [N][vo_pitch] (views contiguous, zero padded; vo_pitch = v_pad),
+    // written in stream order from one of two page-locked staging buffers; cleared (not freed: renders in flight may still read it) by
+    // lfi_set_params / lfi_set_grid / lfi_set_row_window
+    bool view_offsets_set = false;
+    lfi_int2 *d_view_offsets = nullptr;
+    size_t view_offsets_bytes = 0;
+    int vo_pitch = 0;
+    int vo_reach = 0;                       // max |D.x| over the rows set: the padding the planar copy needs to serve them
+    lfi_int2 *vo_staging[2] = {nullptr, nullptr};
+    size_t vo_staging_bytes = 0;
+    hipEvent_t ev_vo[2] = {nullptr, nullptr};
+    int vo_slot = 0;
     std::string err;
 };
 
@@ -397,6 +409,27 @@ void free_params(lfi_ctx *c)
     c->param_half = 0;
     c->half_done_recorded[0] = c->half_done_recorded[1] = false;
     c->have_params = false;
+    c->view_offsets_set = false;
+}
+
+// the per-view offsets' buffers (lfi_set_view_offsets); the caller has drained the stream
+void free_view_offsets(lfi_ctx *c)
+{
+    c->view_offsets_set = false;
+    if(c->d_view_offsets)
+        (void)hipFree(c->d_view_offsets);
+    c->d_view_offsets = nullptr;
+    c->view_offsets_bytes = 0;
+    for(int i = 0; i < 2; i++)
+    {
+        if(c->vo_staging[i])
+            (void)hipHostFree(c->vo_staging[i]);
+        c->vo_staging[i] = nullptr;
+        if(c->ev_vo[i])
+            (void)hipEventDestroy(c->ev_vo[i]);
+        c->ev_vo[i] = nullptr;
+    }
+    c->vo_staging_bytes = 0;
 }
 
 // the copy of the parameter arrays that launches enqueued from now on read

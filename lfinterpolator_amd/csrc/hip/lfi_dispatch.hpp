@@ -14,6 +14,7 @@
 #include "blend_stdxa.hpp"
 #include "blend_af.hpp"
 #include "blend_wave.hpp"
+#include "blend_vfocus.hpp"
 #include "lfi_band_probe.hpp"
 
 namespace {
@@ -376,11 +377,13 @@ bool planar_phases_tuned(const lfi_ctx *c)
     return true;
 }
 
-bool ensure_planar(lfi_ctx *c, bool tune = false)
+// min_reach: pad the copy for horizontal shifts up to this many pixels even where the current integer offsets reach less (the per-view
+// offsets of lfi_set_view_offsets); 0 for every other caller
+bool ensure_planar(lfi_ctx *c, bool tune = false, int min_reach = 0)
 {
     if(!c->grid_tracked)
         return false;
-    const int reach = std::max(std::max(std::abs(c->fo_min[0]), std::abs(c->fo_max[0])), 0);
+    const int reach = std::max(std::max(std::abs(c->fo_min[0]), std::abs(c->fo_max[0])), min_reach);
     if(reach > 4 * c->width + 4096)
         return false;
     // a tile's 128-byte run starts up to `reach` pixels left of column 0 (left padding: reach, rounded up to whole dwords so that the
@@ -677,10 +680,14 @@ void launch_p3(const lfi_ctx *c, const KernelArgs &a_in, bool rgba_out)
 // after launch_blend had committed to kernels that write byte planes)
 int launch_blend_rgba(lfi_ctx *c, int method, int all_focus, const KernelArgs &a_in, bool planar_decided = false);
 
+int launch_vfocus(lfi_ctx *c, int method, int all_focus, const KernelArgs &a_in);
+
 int launch_blend(lfi_ctx *c, int method, int all_focus, const KernelArgs &a_in)
 {
     if(int rc = join_uploads(c))
         return rc;
+    if(c->view_offsets_set)
+        return launch_vfocus(c, method, all_focus, a_in);
     if(all_focus && a_in.map_index == 1)
         if(int rc = join_filter(c)) // the filtered map may still be in the making on the side stream
             return rc;
@@ -802,6 +809,68 @@ int launch_blend_rgba(lfi_ctx *c, int method, int all_focus, const KernelArgs &a
     else
         // the reference throws here (src/interpolator.cu:289-290)
         return fail(c, LFI_EINVAL, "The specified interpolation method does not exist!");
+    LFI_HIP(c, hipGetLastError());
+    return LFI_OK;
+}
+
+// ---- per-view focus (lfi_set_view_offsets): blend_vfocus.hpp ----------------------------------------------------------------------------
+
+// Can this render be served while per-view offsets are set?  (fixed focus only, no debug modes; after lfi_release_inputs only from a planar
+// copy padded for every per-view shift)  *planar: read the planar copy (made valid here for the per-view shifts) rather than the RGBA planes.
+int vfocus_source(lfi_ctx *c, int all_focus, const KernelArgs &a, bool *planar)
+{
+    if(all_focus)
+        return fail(c, LFI_EINVAL, "per-view offsets are set (lfi_set_view_offsets): all-focus renders are not supported - clear them with NULL");
+    if(a.prequant)
+        return fail(c, LFI_EINVAL, "per-view offsets are set (lfi_set_view_offsets): lfi_download_prequant is not supported - clear them with NULL");
+    if(c->flags & LFI_FLAG_TEN_ROUND_PER_BATCH)
+        return fail(c, LFI_EINVAL, "per-view offsets are set (lfi_set_view_offsets): LFI_FLAG_TEN_ROUND_PER_BATCH is not supported");
+    *planar = ensure_planar(c, false, c->vo_reach);
+    if(c->inputs_released && !*planar)
+        return fail(c, LFI_EINVAL, "the RGBA inputs were released (lfi_release_inputs) and the planar copy's padding does not cover the per-view "
+                                   "offsets - upload the images again");
+    return LFI_OK;
+}
+
+int launch_vfocus(lfi_ctx *c, int method, int all_focus, const KernelArgs &a_in)
+{
+    bool planar = false;
+    if(int rc = vfocus_source(c, all_focus, a_in, &planar))
+        return rc;
+    KernelArgs a = a_in;
+    if(planar)
+    {
+        a.planar = c->planar;
+        a.planar_pitch = c->planar_pitch;
+        a.planar_padx = c->planar_padx;
+        a.planar_phase = c->d_planar_phase;
+    }
+    const bool ten = method == LFI_METHOD_TEN_WM, planar_out = c->out_layout == LFI_LAYOUT_PLANAR_RGB;
+    const int n_chunks = (a.v1 - a.v0 + lfi::VF_VIEWS - 1) / lfi::VF_VIEWS;
+    const int tiles_x = (c->width + lfi::VF_TILE_W - 1) / lfi::VF_TILE_W;
+    const int tiles_y = (c->out_rows + lfi::VF_ROWS - 1) / lfi::VF_ROWS;
+    const size_t blocks = (size_t)n_chunks * tiles_x * tiles_y;
+    if(blocks >= (1ull << 31))
+        return fail(c, LFI_EINVAL, "per-view focus: too many views x pixels for one launch - render the views in ranges");
+    static const char *const names[2][2] = {{"blend_vfocus<STD>", "blend_vfocus<STD,rgba_src>"},
+                                            {"blend_vfocus<TEN_WM>", "blend_vfocus<TEN_WM,rgba_src>"}};
+    note_kernel(c, names[ten][!planar]);
+#define LFI_VF_LAUNCH(T, P, O)                                                                                                                   \
+    hipLaunchKernelGGL((lfi::blend_vfocus<T, P, O>), dim3((unsigned)blocks), dim3(256), 0, stream_of(c), a, c->d_view_offsets, c->vo_pitch, n_chunks, \
+                       tiles_x)
+    const int kind = (ten ? 4 : 0) | (planar ? 2 : 0) | (planar_out ? 1 : 0);
+    switch(kind)
+    {
+        case 0: LFI_VF_LAUNCH(false, false, false); break;
+        case 1: LFI_VF_LAUNCH(false, false, true); break;
+        case 2: LFI_VF_LAUNCH(false, true, false); break;
+        case 3: LFI_VF_LAUNCH(false, true, true); break;
+        case 4: LFI_VF_LAUNCH(true, false, false); break;
+        case 5: LFI_VF_LAUNCH(true, false, true); break;
+        case 6: LFI_VF_LAUNCH(true, true, false); break;
+        default: LFI_VF_LAUNCH(true, true, true); break;
+    }
+#undef LFI_VF_LAUNCH
     LFI_HIP(c, hipGetLastError());
     return LFI_OK;
 }

@@ -80,6 +80,7 @@ int lfi_destroy(lfi_ctx *ctx)
     ctx->filter_pending = false;
     free_params(ctx);
     free_param_staging(ctx);
+    free_view_offsets(ctx);
     free_views(ctx);
     free_grid(ctx);
     if(ctx->ev0)
@@ -166,6 +167,7 @@ int lfi_set_grid(lfi_ctx *ctx, int cols, int rows, int width, int height)
         return rc;
     LFI_HIP(ctx, hipStreamSynchronize(ctx->stream));
     free_params(ctx);
+    free_view_offsets(ctx);
     free_views(ctx);
     free_grid(ctx);
     ctx->cols = cols;
@@ -534,6 +536,7 @@ int lfi_set_params(lfi_ctx *ctx, const lfi_params *p)
             if(lo < ctx->in_y0 || hi >= ctx->in_y0 + ctx->in_rows)
                 return fail(ctx, LFI_EINVAL, "the input row window does not cover the rows image " + std::to_string(g) + " is sampled at");
         }
+    ctx->view_offsets_set = false; // per-view offsets belong to the parameters they were set for
     const int n = ctx->n, V = p->views;
     const int k_pad = (n + 15) / 16 * 16;
     // 64 spare rows: a view range may start anywhere, and a wave always reads whole 32-row tiles
@@ -675,6 +678,92 @@ int lfi_set_params(lfi_ctx *ctx, const lfi_params *p)
         }
     }
     ctx->have_params = true;
+    return LFI_OK;
+}
+
+int lfi_set_view_offsets(lfi_ctx *ctx, const lfi_int2 *focused_offsets_vn, int views)
+{
+    if(!ctx)
+        return LFI_EINVAL;
+    if(!ctx->have_params)
+        return fail(ctx, LFI_EINVAL, "lfi_set_params has not been called");
+    if(!focused_offsets_vn)
+    {
+        ctx->view_offsets_set = false;
+        return LFI_OK;
+    }
+    if(views != ctx->views_n)
+        return fail(ctx, LFI_EINVAL, "lfi_set_view_offsets: views (" + std::to_string(views) + ") differs from lfi_params.views (" +
+                                         std::to_string(ctx->views_n) + ")");
+    if(int rc = bind(ctx))
+        return rc;
+    const int n = ctx->n, W = ctx->width, H = ctx->height;
+    // A shift beyond the image samples its edge for every pixel, exactly as a shift of ±W / ±H does (clamp to edge): clamping here keeps
+    // every coordinate the kernel forms far from int overflow and changes no result.
+    auto at = [&](int v, int g) {
+        lfi_int2 d = focused_offsets_vn[(size_t)v * n + g];
+        d.x = std::min(std::max(d.x, -W), W);
+        d.y = std::min(std::max(d.y, -H), H);
+        return d;
+    };
+    if(ctx->windowed)
+        for(int v = 0; v < views; v++)
+            for(int g = 0; g < n; g++)
+            {
+                const int oy = at(v, g).y;
+                const int lo = std::min(std::max(ctx->out_y0 + oy, 0), H - 1), hi = std::min(std::max(ctx->out_y0 + ctx->out_rows - 1 + oy, 0), H - 1);
+                if(lo < ctx->in_y0 || hi >= ctx->in_y0 + ctx->in_rows)
+                    return fail(ctx, LFI_EINVAL, "the input row window does not cover the rows image " + std::to_string(g) + " is sampled at in view " +
+                                                     std::to_string(v));
+            }
+    // [N][v_pad], views contiguous (one scalar run per image and chunk of views), zero padding views
+    const int pitch = ctx->v_pad;
+    const size_t bytes = sizeof(lfi_int2) * (size_t)n * pitch;
+    if(bytes > ctx->view_offsets_bytes)
+    {
+        LFI_HIP(ctx, hipStreamSynchronize(ctx->stream)); // renders in flight may read the old buffer
+        free_view_offsets(ctx);
+        LFI_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->d_view_offsets), bytes));
+        ctx->view_offsets_bytes = bytes;
+    }
+    // stream order, as lfi_set_params: the copy runs behind the renders already enqueued, out of one of two page-locked buffers
+    if(ctx->vo_staging_bytes < bytes)
+    {
+        for(int i = 0; i < 2; i++)
+        {
+            if(ctx->ev_vo[i])
+                LFI_HIP(ctx, hipEventSynchronize(ctx->ev_vo[i]));
+            if(ctx->vo_staging[i])
+                (void)hipHostFree(ctx->vo_staging[i]);
+            ctx->vo_staging[i] = nullptr;
+        }
+        ctx->vo_staging_bytes = 0;
+        for(int i = 0; i < 2; i++)
+        {
+            LFI_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->vo_staging[i]), bytes, hipHostMallocDefault));
+            if(!ctx->ev_vo[i])
+                LFI_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_vo[i], hipEventDisableTiming));
+        }
+        ctx->vo_staging_bytes = bytes;
+    }
+    else
+        LFI_HIP(ctx, hipEventSynchronize(ctx->ev_vo[ctx->vo_slot])); // the copy out of this buffer, two calls ago, has run
+    lfi_int2 *staged = ctx->vo_staging[ctx->vo_slot];
+    std::memset(staged, 0, bytes);
+    int reach = 0;
+    for(int v = 0; v < views; v++)
+        for(int g = 0; g < n; g++)
+        {
+            const lfi_int2 d = at(v, g);
+            staged[(size_t)g * pitch + v] = d;
+            reach = std::max(reach, std::abs(d.x));
+        }
+    LFI_HIP(ctx, hipMemcpyAsync(ctx->d_view_offsets, staged, bytes, hipMemcpyHostToDevice, ctx->stream));
+    LFI_HIP(ctx, hipEventRecord(ctx->ev_vo[ctx->vo_slot], ctx->stream));
+    ctx->vo_slot ^= 1;
+    ctx->vo_pitch = pitch;
+    ctx->vo_reach = reach;
+    ctx->view_offsets_set = true;
     return LFI_OK;
 }
 
@@ -869,6 +958,19 @@ int lfi_prepare(lfi_ctx *ctx, int method, int all_focus, int v0, int v1)
         return rc;
     const KernelArgs a = make_args(ctx, v0, v1, method);
     ctx->derived_build_ms = 0.0f;
+    if(ctx->view_offsets_set) // per-view focus: the copy padded for the per-view shifts, as launch_vfocus makes it
+    {
+        const uint64_t before = ctx->planar_version;
+        bool planar = false;
+        LFI_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+        if(int rc = vfocus_source(ctx, all_focus, a, &planar))
+            return rc;
+        LFI_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+        LFI_HIP(ctx, hipEventSynchronize(ctx->ev1));
+        if(planar && ctx->planar_version != before)
+            LFI_HIP(ctx, hipEventElapsedTime(&ctx->derived_build_ms, ctx->ev0, ctx->ev1));
+        return LFI_OK;
+    }
     if(wants_derived_copy(ctx, method, all_focus, a)) // the same predicate chain as launch_blend
     {
         ctx->eager_planar = true; // images that arrive from now on refresh their planes of the copy at once
@@ -929,6 +1031,8 @@ int lfi_render_stream(lfi_ctx *ctx, int method, int all_focus, const uint16_t *w
 {
     if(int rc = check_render_args(ctx, method, 0, 1))
         return rc;
+    if(ctx->view_offsets_set)
+        return fail(ctx, LFI_EINVAL, "per-view offsets are set (lfi_set_view_offsets): lfi_render_stream is not supported - clear them with NULL");
     if(!weights_fp16 || total_views < 1)
         return fail(ctx, LFI_EINVAL, "lfi_render_stream: weights are NULL or total_views < 1");
     if(host_out && (ctx->out_layout != LFI_LAYOUT_RGBA || pitch_bytes < (size_t)ctx->width * 4))
@@ -1120,7 +1224,13 @@ int lfi_benchmark(lfi_ctx *ctx, int method, int all_focus, int v0, int v1, int w
         return rc;
     const KernelArgs a = make_args(ctx, v0, v1, method);
     // the derived input copy is (re)built here, not inside the first timed launch
-    if(wants_derived_copy(ctx, method, all_focus, a))
+    if(ctx->view_offsets_set)
+    {
+        bool planar = false;
+        if(int rc = vfocus_source(ctx, all_focus, a, &planar))
+            return rc;
+    }
+    else if(wants_derived_copy(ctx, method, all_focus, a))
         (void)ensure_planar(ctx, true);
     for(int i = 0; i < warmup; i++)
         if(int rc = launch_blend(ctx, method, all_focus, a))

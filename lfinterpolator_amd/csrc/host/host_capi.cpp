@@ -2,6 +2,8 @@
 // the kernel parameters with the very code the C++ Interpolator uses (params.cpp).
 #include <cstring>
 #include <exception>
+#include <stdexcept>
+#include <vector>
 
 #include "params.h"
 
@@ -23,6 +25,40 @@ int lfi_host_build_params(int cols, int rows, int width, int height, const char 
         *n_ids = static_cast<int32_t>(hp.focusMapIDs.size());
         block_radius[0] = hp.blockRadius[0];
         block_radius[1] = hp.blockRadius[1];
+        return 0;
+    }
+    catch(const std::exception &e)
+    {
+        if(err && err_len)
+        {
+            std::strncpy(err, e.what(), err_len - 1);
+            err[err_len - 1] = 0;
+        }
+        return -1;
+    }
+}
+
+// per-view focus: out[views] = f0 + ((f1 − f0) / (views − 1))·i in float (views = 1: f0); returns 0, or -1 for views < 1
+int lfi_host_focus_ramp(float f0, float f1, int views, float *out)
+{
+    if(views < 1 || !out)
+        return -1;
+    const std::vector<float> ramp = lfi::focusRamp(f0, f1, views);
+    std::memcpy(out, ramp.data(), sizeof(float) * ramp.size());
+    return 0;
+}
+
+// per-view focus: out_vn[views][N] = the focused offsets of Parameterizer::offsets at focus_v[v] (the rows lfi_set_view_offsets takes)
+int lfi_host_build_view_offsets(int cols, int rows, int width, int height, const char *trajectory, float aspect, const float *focus_v,
+                                int views, lfi_int2 *out_vn, char *err, size_t err_len)
+{
+    try
+    {
+        if(views < 1 || !focus_v || !out_vn)
+            throw std::runtime_error("views must be positive and the arrays non-NULL");
+        lfi::Parameterizer p({cols, rows}, {width, height, 4});
+        const std::vector<lfi_int2> d = p.viewOffsets(aspect, std::vector<float>(focus_v, focus_v + views), p.interpretTrajectory(trajectory));
+        std::memcpy(out_vn, d.data(), sizeof(lfi_int2) * d.size());
         return 0;
     }
     catch(const std::exception &e)

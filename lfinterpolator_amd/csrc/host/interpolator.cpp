@@ -140,6 +140,17 @@ void Interpolator::interpolate(std::string outputPath, std::string trajectory, f
         check(lfi_set_output_layout(c, (methodID == LFI_METHOD_TEN_WM && !(inRange > 0)) ? LFI_LAYOUT_PLANAR_RGB : LFI_LAYOUT_RGBA), c);
 
     const int allFocus = inRange > 0;
+    if(perViewFocus)
+    {
+        if(allFocus)
+            throw std::runtime_error("A focus per view cannot be combined with all-focus rendering (-r)!");
+        // every GPU gets the rows of its own views
+        const std::vector<lfi_int2> rowsVn = parameterizer.viewOffsets(aspect, lfi::focusRamp(focus, focusEnd, viewCount),
+                                                                        parameterizer.interpretTrajectory(trajectory));
+        const size_t n = params.offsets.size();
+        for(int g = 0; g < gpuCount; g++)
+            check(lfi_set_view_offsets(contexts[g], rowsVn.data() + viewStart[g] * n, viewStart[g + 1] - viewStart[g]), contexts[g]);
+    }
     if(allFocus)
     {
         std::cout << "Estimating focus map..." << std::endl;

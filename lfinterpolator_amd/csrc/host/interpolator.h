@@ -29,6 +29,9 @@ class Interpolator
         float lastAverageTime() const { return averageTime; }
         // render on GPUs 0 … count-1 of this node: views are split into contiguous ranges, the grid is broadcast once (RCCL)
         void setGpuCount(int count) { gpuCount = count; }
+        // a focus per view: view i is rendered at focus + ((end − focus) / (views − 1))·i (a focus pull; with a single-point trajectory a
+        // focal stack) through lfi_set_view_offsets — fixed-focus renders only
+        void setFocusEnd(float end) { focusEnd = end; perViewFocus = true; }
 
         // synthetic cols×rows grid of width×height images instead of a directory
         Interpolator(lfi::IVec2 colsRows, lfi::IVec2 resolution, uint32_t seed, int device = 0);
@@ -42,6 +45,8 @@ class Interpolator
         lfi::IVec2 quiltTiles{0, 0};
         lfi_ctx *context{nullptr};
         int gpuCount{1};
+        bool perViewFocus{false};
+        float focusEnd{0};
         std::vector<lfi_ctx *> contexts; // one per GPU; contexts[0] == context
         std::vector<int> viewStart;      // first view of each GPU's range (size gpuCount + 1)
         float focus{0};

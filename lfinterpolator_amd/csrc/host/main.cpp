@@ -1,5 +1,6 @@
 // main.cpp — command line of the interpolator; flags, defaults, messages and exit codes as in reference src/main.cpp:4-57
-// (-i -t -o -f -r -m -s -a -h), plus -n (views), -b (benchmark runs), -d (device) and --synthetic for runs without a dataset.
+// (-i -t -o -f -r -m -s -a -h), plus -n (views), -b (benchmark runs), -d (device), -F (focus at the last view) and --synthetic for runs
+// without a dataset.
 #include <iostream>
 #include <memory>
 #include <sstream>
@@ -31,6 +32,7 @@ int main(int argc, char **argv)
                           "The following arguments are normalized offsets of the images in shift & sum\n"
                           "-f - focusing value (default=0)\n"
                           "-r - focusing range (will be added to the focusing value) - will produce all-focused result if used\n"
+                          "-F - focusing value at the last view: the focus ramps from -f at the first view to -F at the last (a focus pull; a focal stack with a single-point trajectory such as -t 0.5,0.5,0.5,0.5); not with -r\n"
                           "Additional arguments:\n"
                           "-n - number of views rendered along the trajectory (default=64)\n"
                           "-b - number of timed kernel launches (default=100)\n"
@@ -55,6 +57,12 @@ int main(int argc, char **argv)
     if((!args["-i"] && !synthetic) || !args["-t"] || !args["-o"] || !args["-m"])
     {
         std::cerr << "Missing required parameters. Use -h for help." << std::endl;
+        return EXIT_FAILURE;
+    }
+
+    if(args["-F"] && args["-r"])
+    {
+        std::cerr << "-F (a focus per view) cannot be combined with -r (all-focus rendering)." << std::endl;
         return EXIT_FAILURE;
     }
 
@@ -87,6 +95,8 @@ int main(int argc, char **argv)
             interpolator->setBenchmarkRuns(static_cast<size_t>(static_cast<int>(args["-b"])));
         if(args["--unified-map"])
             interpolator->setUnifiedFocusMap(true);
+        if(args["-F"])
+            interpolator->setFocusEnd(static_cast<float>(args["-F"]));
         if(args["-q"])
         {
             std::stringstream spec(static_cast<std::string>(args["-q"]));

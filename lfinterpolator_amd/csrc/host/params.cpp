@@ -211,6 +211,31 @@ void Parameterizer::offsets(float aspect, float focus, Vec4 startEndPoints, std:
     }
 }
 
+std::vector<lfi_int2> Parameterizer::viewOffsets(float aspect, const std::vector<float> &focus, Vec4 startEndPoints) const
+{
+    const size_t n = static_cast<size_t>(colsRows.x) * colsRows.y;
+    std::vector<lfi_int2> out(focus.size() * n);
+    std::vector<lfi_float2> shifts;
+    std::vector<lfi_int2> row;
+    for(size_t v = 0; v < focus.size(); v++)
+    {
+        offsets(aspect, focus[v], startEndPoints, shifts, row);
+        std::copy(row.begin(), row.end(), out.begin() + v * n);
+    }
+    return out;
+}
+
+std::vector<float> focusRamp(float f0, float f1, int views)
+{
+    std::vector<float> ramp(static_cast<size_t>(std::max(views, 1)), f0);
+    if(views <= 1)
+        return ramp;
+    const float step = (f1 - f0) / static_cast<float>(views - 1);
+    for(int i = 0; i < views; i++)
+        ramp[i] = f0 + step * static_cast<float>(i);
+    return ramp;
+}
+
 // reference src/interpolator.cu:194-207; at most 32 ids (the reference indexes 32 unconditionally: SURVEY.md D4) and ties
 // ordered by id (std::sort leaves them unspecified there)
 std::vector<int32_t> Parameterizer::selectFocusMapViews(Vec4 startEndPoints) const

@@ -45,6 +45,8 @@ class Parameterizer
         std::vector<uint16_t> weightMatrix(Vec4 startEndPoints, float effect, int views) const;
         void offsets(float aspect, float focus, Vec4 startEndPoints, std::vector<lfi_float2> &offsets,
                      std::vector<lfi_int2> &focusedOffsets) const;
+        // per-view focus (lfi_set_view_offsets): [views][N] integer offsets, row v = offsets(aspect, focus[v], …)'s focused offsets
+        std::vector<lfi_int2> viewOffsets(float aspect, const std::vector<float> &focus, Vec4 startEndPoints) const;
         std::vector<int32_t> selectFocusMapViews(Vec4 startEndPoints) const;
         IVec2 blockRadius() const;
 
@@ -58,5 +60,9 @@ class Parameterizer
 };
 
 Vec2 trajectoryCenter(Vec4 startEndPoints);
+
+// views focus values from f0 to f1, equally spaced: f0 + ((f1 − f0) / (views − 1))·i in float — the rounding of generateTrajectory; one
+// view gets f0
+std::vector<float> focusRamp(float f0, float f1, int views);
 
 } // namespace lfi

@@ -23,6 +23,11 @@ def load_host_library() -> C.CDLL:
                                               C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32 * 2), C.c_char_p,
                                               C.c_size_t]
+        lib.lfi_host_focus_ramp.restype = C.c_int
+        lib.lfi_host_focus_ramp.argtypes = [C.c_float, C.c_float, C.c_int, C.c_void_p]
+        lib.lfi_host_build_view_offsets.restype = C.c_int
+        lib.lfi_host_build_view_offsets.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_float, C.c_void_p, C.c_int,
+                                                    C.c_void_p, C.c_char_p, C.c_size_t]
         lib.lfi_host_float_to_half.restype = C.c_uint16
         lib.lfi_host_float_to_half.argtypes = [C.c_float]
         lib.lfi_host_half_to_float.restype = C.c_float
@@ -72,6 +77,24 @@ def build_params(cols: int, rows: int, width: int, height: int, trajectory: str,
     if rc != 0:
         raise ValueError(err.value.decode())
     return HostParams(foc, off, w, ids[:n_ids.value].copy(), focus, range, np.array([radius[0], radius[1]], np.int32))
+
+
+def focus_ramp(f0: float, f1: float, views: int) -> np.ndarray:
+    """Per-view focus values from f0 (first view) to f1 (last view): f0 + ((f1 − f0) / (views − 1))·i in float32 (one view: f0)."""
+    out = np.zeros(max(views, 1), dtype=np.float32)
+    if load_host_library().lfi_host_focus_ramp(f0, f1, views, out.ctypes.data) != 0:
+        raise ValueError("views must be positive")
+    return out
+
+
+def build_view_offsets(cols: int, rows: int, width: int, height: int, trajectory: str, aspect: float, focus_v) -> np.ndarray:
+    """[V][N][2] int32 rows for Context.set_view_offsets: row v = the focused offsets of the trajectory's centre at focus_v[v]
+    (Parameterizer::offsets)."""
+    f = np.ascontiguousarray(np.atleast_1d(focus_v), dtype=np.float32)
+    out = np.zeros((len(f), cols * rows, 2), dtype=np.int32)
+    _err_call(load_host_library().lfi_host_build_view_offsets, cols, rows, width, height, trajectory.encode(), aspect, f.ctypes.data,
+              len(f), out.ctypes.data)
+    return out
 
 
 def _err_call(fn, *args):
