@@ -212,6 +212,27 @@ int lfi_set_params(lfi_ctx *ctx, const lfi_params *params);
  *  - after lfi_release_inputs, renders are served while the planar copy's padding covers every per-view horizontal shift (else LFI_EINVAL).
  * Shifts beyond the image are clamped to ±width / ±height (the same samples: every pixel then reads the edge). */
 int lfi_set_view_offsets(lfi_ctx *ctx, const lfi_int2 *focused_offsets_vn, int views);
+/* Per-view float offsets for all-focus renders: every view shifted about its own camera.  The reference computes one row of offsets for
+ * the trajectory's centre (loadGPUOffsets → trajectoryCenter, src/interpolator.cu:226-246) and applies it to every view; its author left a
+ * per-view centre commented out there and, in scripts/focusMapCompare.sh, a note to edit the offsets per view id — one run per view.
+ * offsets_vn is [views][N] (host memory, copied before the call returns): view v of an all-focus render samples image g at
+ * (int)fma(f(x,y), offsets_vn[v][g], pixel) instead of (int)fma(f(x,y), lfi_params.offsets[g], pixel) — row v of lfi_host_build_view_centred_offsets
+ * is lfi_params.offsets for the trajectory collapsed onto camera v.  It is the per-view counterpart of lfi_params.offsets:
+ *  - call after lfi_set_params; views must equal lfi_params.views and every offset be finite (else LFI_EINVAL).  NULL clears them; so
+ *    does any later lfi_set_params, lfi_set_grid or lfi_set_row_window;
+ *  - stream-ordered like lfi_set_view_offsets: renders enqueued before the call keep the offsets they were enqueued with;
+ *  - all-focus renders only: fixed-focus renders keep lfi_params.focused_offsets, or the integer rows of lfi_set_view_offsets (both may be
+ *    set at once; all-focus renders with only the integer rows set stay refused);
+ *  - with a row window, the held input rows must cover every row any view of the range samples for f in [focus, focus + range] (else
+ *    LFI_EINVAL at the render);
+ *  - while they are set, all-focus lfi_render, lfi_prepare and lfi_benchmark launch one kernel for all views of the range
+ *    (csrc/hip/blend_vfocus_af.hpp; lfi_last_kernel_name names it, lfi_set_variant choices do not apply) — a vector-pipe gather-blend over
+ *    the RGBA planes: STD is bit-exact, TEN_WM is the fp32-accumulated sum rounded once to fp16 and truncated (the TEN_WM contract) and does
+ *    NOT use the matrix cores.  Each view reads the same focus map as the ordinary render (map 1 for STD, map 0 for TEN_WM unless
+ *    LFI_FLAG_UNIFIED_FOCUS_MAP), at its own pixel.  Downloads, quilts, lfi_compare_view, both view layouts and attached views work
+ *    unchanged.  All-focus lfi_render_stream, all-focus lfi_download_prequant and LFI_FLAG_TEN_ROUND_PER_BATCH return LFI_EINVAL.
+ * lfi_focus_map is unchanged: it estimates the map at the trajectory's centre from lfi_params.offsets and focus_map_ids. */
+int lfi_set_view_float_offsets(lfi_ctx *ctx, const lfi_float2 *offsets_vn, int views);
 /* Device layout of the rendered views.  LFI_LAYOUT_RGBA (default): [V][rows][W] RGBA8 dwords — the linear image of the
  * reference's 64 output surfaces.  LFI_LAYOUT_PLANAR_RGB (opt-in): alpha-free byte planes [V][3: R,G,B][rows][pitch] — the alpha
  * the reference's kernels write is the constant 255 (uchar4{…, 255}, src/kernels.cu:393, :309), a quarter of the bytes a render
@@ -239,7 +260,8 @@ int lfi_views_device_ptr(lfi_ctx *ctx, void **out_ptr, size_t *out_bytes);
  * The estimate reads edge-padded copies of the <= 32 sampled images; they depend on the inputs only (and on a bound of the shifts),
  * so they are kept between calls and rebuilt when the images change (any upload / fill through this library, lfi_grid_modified for
  * writes through the raw pointer), when other images are sampled, or when the shifts outgrow the padding: a focus sweep over one
- * light field (the reference's focusMapCompare.sh loop) pads once. */
+ * light field (the reference's focusMapCompare.sh loop) pads once.  The map is estimated at the trajectory's centre from lfi_params.offsets
+ * and focus_map_ids, whether or not per-view float offsets (lfi_set_view_float_offsets) are set. */
 int lfi_focus_map(lfi_ctx *ctx);
 /* One launch of Tensors::process / Standard::process (src/interpolator.cu:274-288) for views [v0, v1).
  * all_focus != 0 selects the <true> instantiations (per-pixel focus from the focus map). */

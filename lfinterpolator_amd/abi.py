@@ -33,7 +33,7 @@ ABI_SYMBOLS = [
     "lfi_timer_stop", "lfi_sync", "lfi_download_view", "lfi_download_map", "lfi_download_quilt", "lfi_download_quilt_tiles", "lfi_release_inputs", "lfi_alloc_pinned", "lfi_free_pinned", "lfi_upload_map", "lfi_set_stream",
     "lfi_set_variant", "lfi_list_variants", "lfi_download_coords", "lfi_download_prequant", "lfi_debug_mfma_f16",
     "lfi_grid_modified", "lfi_prepare", "lfi_memory_info", "lfi_last_kernel_name", "lfi_fill_synthetic_images", "lfi_set_output_layout", "lfi_view_layout", "lfi_fill_synthetic_scene", "lfi_upload_image_async", "lfi_upload_wait", "lfi_render_stream", "lfi_compare_view", "lfi_debug_mfma_f16_chain", "lfi_debug_pk_minmax3_f16", "lfi_std_band_info",
-    "lfi_debug_poison", "lfi_set_view_offsets",
+    "lfi_debug_poison", "lfi_set_view_offsets", "lfi_set_view_float_offsets",
 ]
 
 
@@ -112,6 +112,7 @@ def load_hip_library() -> C.CDLL:
         "lfi_fill_synthetic": (i, [vp, C.c_uint32]),
         "lfi_set_params": (i, [vp, C.POINTER(_Params)]),
         "lfi_set_view_offsets": (i, [vp, vp, i]),
+        "lfi_set_view_float_offsets": (i, [vp, vp, i]),
         "lfi_attach_views": (i, [vp, vp, sz]),
         "lfi_views_device_ptr": (i, [vp, C.POINTER(vp), C.POINTER(sz)]),
         "lfi_focus_map": (i, [vp]),
@@ -308,6 +309,16 @@ class Context:
         d = np.ascontiguousarray(offsets_vn, dtype=np.int32)
         assert d.ndim == 3 and d.shape[1:] == (self.n_images, 2), d.shape
         self._check(self._lib.lfi_set_view_offsets(self._h, _ptr(d), d.shape[0]))
+
+    def set_view_float_offsets(self, offsets_vn: np.ndarray | None) -> None:
+        """Per-view float offsets for all-focus renders (lfi_set_view_float_offsets): offsets_vn is [views][N][2] float32 — view v samples
+        image g at (int)fma(f, offsets_vn[v][g], pixel) (lfinterpolator_amd.build_view_centred_offsets computes them); None clears them."""
+        if offsets_vn is None:
+            self._check(self._lib.lfi_set_view_float_offsets(self._h, None, 0))
+            return
+        o = np.ascontiguousarray(offsets_vn, dtype=np.float32)
+        assert o.ndim == 3 and o.shape[1:] == (self.n_images, 2), o.shape
+        self._check(self._lib.lfi_set_view_float_offsets(self._h, _ptr(o), o.shape[0]))
 
     def set_output_layout(self, layout) -> None:
         """'rgba' (the reference's planes) or 'planar' (alpha-free byte planes; downloads re-create alpha = 255)."""

@@ -154,6 +154,17 @@ struct lfi_ctx
     size_t vo_staging_bytes = 0;
     hipEvent_t ev_vo[2] = {nullptr, nullptr};
     int vo_slot = 0;
+    // lfi_set_view_float_offsets: one float offset per (view, image) for all-focus renders, [N][vfo_pitch] on the device (views contiguous,
+    // zero padded) and [views][N] on the host (the row-window check), staged and cleared exactly like the integer per-view offsets above
+    bool view_float_offsets_set = false;
+    lfi_float2 *d_view_float_offsets = nullptr;
+    size_t view_float_offsets_bytes = 0;
+    int vfo_pitch = 0;
+    std::vector<lfi_float2> h_view_float_offsets;
+    lfi_float2 *vfo_staging[2] = {nullptr, nullptr};
+    size_t vfo_staging_bytes = 0;
+    hipEvent_t ev_vfo[2] = {nullptr, nullptr};
+    int vfo_slot = 0;
     std::string err;
 };
 
@@ -410,6 +421,7 @@ void free_params(lfi_ctx *c)
     c->half_done_recorded[0] = c->half_done_recorded[1] = false;
     c->have_params = false;
     c->view_offsets_set = false;
+    c->view_float_offsets_set = false;
 }
 
 // the per-view offsets' buffers (lfi_set_view_offsets); the caller has drained the stream
@@ -430,6 +442,27 @@ void free_view_offsets(lfi_ctx *c)
         c->ev_vo[i] = nullptr;
     }
     c->vo_staging_bytes = 0;
+}
+
+// the per-view float offsets' buffers (lfi_set_view_float_offsets); the caller has drained the stream
+void free_view_float_offsets(lfi_ctx *c)
+{
+    c->view_float_offsets_set = false;
+    if(c->d_view_float_offsets)
+        (void)hipFree(c->d_view_float_offsets);
+    c->d_view_float_offsets = nullptr;
+    c->view_float_offsets_bytes = 0;
+    c->h_view_float_offsets.clear();
+    for(int i = 0; i < 2; i++)
+    {
+        if(c->vfo_staging[i])
+            (void)hipHostFree(c->vfo_staging[i]);
+        c->vfo_staging[i] = nullptr;
+        if(c->ev_vfo[i])
+            (void)hipEventDestroy(c->ev_vfo[i]);
+        c->ev_vfo[i] = nullptr;
+    }
+    c->vfo_staging_bytes = 0;
 }
 
 // the copy of the parameter arrays that launches enqueued from now on read

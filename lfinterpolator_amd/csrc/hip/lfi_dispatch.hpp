@@ -15,6 +15,7 @@
 #include "blend_af.hpp"
 #include "blend_wave.hpp"
 #include "blend_vfocus.hpp"
+#include "blend_vfocus_af.hpp"
 #include "lfi_band_probe.hpp"
 
 namespace {
@@ -681,11 +682,31 @@ void launch_p3(const lfi_ctx *c, const KernelArgs &a_in, bool rgba_out)
 int launch_blend_rgba(lfi_ctx *c, int method, int all_focus, const KernelArgs &a_in, bool planar_decided = false);
 
 int launch_vfocus(lfi_ctx *c, int method, int all_focus, const KernelArgs &a_in);
+int launch_vfocus_af(lfi_ctx *c, int method, const KernelArgs &a_in);
+
+// Every image row an all-focus render of the output band can sample is held: (int)fma(f, offset.y, y) for f between the ends of the focus
+// range (the map decodes to focus + m/255·range), y in the band, over the n offsets o; ±1 for float rounding
+bool allfocus_rows_held(const lfi_ctx *c, const lfi_float2 *o, size_t n)
+{
+    const float f_lo = std::min(c->focus, c->focus + c->range), f_hi = std::max(c->focus, c->focus + c->range);
+    const int H = c->height;
+    for(size_t g = 0; g < n; g++)
+    {
+        const double d_lo = std::min((double)f_lo * o[g].y, (double)f_hi * o[g].y), d_hi = std::max((double)f_lo * o[g].y, (double)f_hi * o[g].y);
+        const int lo = std::min(std::max((int)std::floor(c->out_y0 + d_lo) - 1, 0), H - 1);
+        const int hi = std::min(std::max((int)std::ceil(c->out_y0 + c->out_rows - 1 + d_hi) + 1, 0), H - 1);
+        if(lo < c->in_y0 || hi >= c->in_y0 + c->in_rows)
+            return false;
+    }
+    return true;
+}
 
 int launch_blend(lfi_ctx *c, int method, int all_focus, const KernelArgs &a_in)
 {
     if(int rc = join_uploads(c))
         return rc;
+    if(all_focus && c->view_float_offsets_set) // per-view float offsets govern all-focus renders, the integer ones fixed-focus renders
+        return launch_vfocus_af(c, method, a_in);
     if(c->view_offsets_set)
         return launch_vfocus(c, method, all_focus, a_in);
     if(all_focus && a_in.map_index == 1)
@@ -773,21 +794,8 @@ int launch_blend_rgba(lfi_ctx *c, int method, int all_focus, const KernelArgs &a
         const Variant &v = ten ? kTenVariants[c->ten_variant] : kStdVariants[c->std_variant];
         if(a.prequant || !v.row_window || (c->flags & LFI_FLAG_TEN_ROUND_PER_BATCH) || (ten && v.packed_epilogue && !c->weights_scalable))
             return fail(c, LFI_EINVAL, "with a row window only renders with the default (persistent) kernels and weights in [0,2) are supported");
-        if(all_focus)
-        {
-            // every image row an all-focus render of the band can sample must be held: (int)fma(f, offset.y, y) for f between the
-            // ends of the focus range (the map decodes to focus + m/255·range), y in the band; ±1 for float rounding
-            const float f_lo = std::min(c->focus, c->focus + c->range), f_hi = std::max(c->focus, c->focus + c->range);
-            for(const lfi_float2 &o : c->h_offsets)
-            {
-                const double d_lo = std::min((double)f_lo * o.y, (double)f_hi * o.y), d_hi = std::max((double)f_lo * o.y, (double)f_hi * o.y);
-                const int H = c->height;
-                const int lo = std::min(std::max((int)std::floor(c->out_y0 + d_lo) - 1, 0), H - 1);
-                const int hi = std::min(std::max((int)std::ceil(c->out_y0 + c->out_rows - 1 + d_hi) + 1, 0), H - 1);
-                if(lo < c->in_y0 || hi >= c->in_y0 + c->in_rows)
-                    return fail(c, LFI_EINVAL, "the input row window does not cover the rows an all-focus render of this band samples");
-            }
-        }
+        if(all_focus && !allfocus_rows_held(c, c->h_offsets.data(), c->h_offsets.size()))
+            return fail(c, LFI_EINVAL, "the input row window does not cover the rows an all-focus render of this band samples");
     }
     if(method == LFI_METHOD_TEN_WM)
     {
@@ -871,6 +879,58 @@ int launch_vfocus(lfi_ctx *c, int method, int all_focus, const KernelArgs &a_in)
         default: LFI_VF_LAUNCH(true, true, true); break;
     }
 #undef LFI_VF_LAUNCH
+    LFI_HIP(c, hipGetLastError());
+    return LFI_OK;
+}
+
+// ---- per-view float offsets (lfi_set_view_float_offsets): blend_vfocus_af.hpp --------------------------------------------------------------
+
+// Can this all-focus render be served while per-view float offsets are set?  (no debug modes, the RGBA planes present, every row that
+// views [v0, v1) sample held)
+int vfocus_af_check(lfi_ctx *c, const KernelArgs &a)
+{
+    if(a.prequant)
+        return fail(c, LFI_EINVAL, "per-view float offsets are set (lfi_set_view_float_offsets): all-focus lfi_download_prequant is not supported - "
+                                   "clear them with NULL");
+    if(c->flags & LFI_FLAG_TEN_ROUND_PER_BATCH)
+        return fail(c, LFI_EINVAL, "per-view float offsets are set (lfi_set_view_float_offsets): LFI_FLAG_TEN_ROUND_PER_BATCH is not supported");
+    if(c->inputs_released)
+        return fail(c, LFI_EINVAL, "the RGBA inputs were released (lfi_release_inputs): all-focus renders need them - upload the images again");
+    if(c->windowed)
+        for(int v = a.v0; v < a.v1; v++)
+            if(!allfocus_rows_held(c, c->h_view_float_offsets.data() + (size_t)v * c->n, c->n))
+                return fail(c, LFI_EINVAL, "the input row window does not cover the rows an all-focus render of this band samples in view " +
+                                               std::to_string(v));
+    return LFI_OK;
+}
+
+int launch_vfocus_af(lfi_ctx *c, int method, const KernelArgs &a)
+{
+    if(int rc = vfocus_af_check(c, a))
+        return rc;
+    if(a.map_index == 1)
+        if(int rc = join_filter(c)) // the filtered map may still be in the making on the side stream
+            return rc;
+    const bool ten = method == LFI_METHOD_TEN_WM, planar_out = c->out_layout == LFI_LAYOUT_PLANAR_RGB;
+    const int n_chunks = (a.v1 - a.v0 + lfi::VF_VIEWS - 1) / lfi::VF_VIEWS;
+    const int tiles_x = (c->width + lfi::VF_TILE_W - 1) / lfi::VF_TILE_W;
+    const int tiles_y = (c->out_rows + lfi::VF_ROWS - 1) / lfi::VF_ROWS;
+    const size_t blocks = (size_t)n_chunks * tiles_x * tiles_y;
+    if(blocks >= (1ull << 31))
+        return fail(c, LFI_EINVAL, "per-view float offsets: too many views x pixels for one launch - render the views in ranges");
+    static const char *const names[2] = {"blend_vfocus_af<STD>", "blend_vfocus_af<TEN_WM>"};
+    note_kernel(c, names[ten]);
+#define LFI_VFA_LAUNCH(T, O)                                                                                                                     \
+    hipLaunchKernelGGL((lfi::blend_vfocus_af<T, O>), dim3((unsigned)blocks), dim3(256), 0, stream_of(c), a, c->d_view_float_offsets, c->vfo_pitch, \
+                       n_chunks, tiles_x)
+    switch((ten ? 2 : 0) | (planar_out ? 1 : 0))
+    {
+        case 0: LFI_VFA_LAUNCH(false, false); break;
+        case 1: LFI_VFA_LAUNCH(false, true); break;
+        case 2: LFI_VFA_LAUNCH(true, false); break;
+        default: LFI_VFA_LAUNCH(true, true); break;
+    }
+#undef LFI_VFA_LAUNCH
     LFI_HIP(c, hipGetLastError());
     return LFI_OK;
 }

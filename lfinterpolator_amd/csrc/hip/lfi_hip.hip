@@ -81,6 +81,7 @@ int lfi_destroy(lfi_ctx *ctx)
     free_params(ctx);
     free_param_staging(ctx);
     free_view_offsets(ctx);
+    free_view_float_offsets(ctx);
     free_views(ctx);
     free_grid(ctx);
     if(ctx->ev0)
@@ -168,6 +169,7 @@ int lfi_set_grid(lfi_ctx *ctx, int cols, int rows, int width, int height)
     LFI_HIP(ctx, hipStreamSynchronize(ctx->stream));
     free_params(ctx);
     free_view_offsets(ctx);
+    free_view_float_offsets(ctx);
     free_views(ctx);
     free_grid(ctx);
     ctx->cols = cols;
@@ -537,6 +539,7 @@ int lfi_set_params(lfi_ctx *ctx, const lfi_params *p)
                 return fail(ctx, LFI_EINVAL, "the input row window does not cover the rows image " + std::to_string(g) + " is sampled at");
         }
     ctx->view_offsets_set = false; // per-view offsets belong to the parameters they were set for
+    ctx->view_float_offsets_set = false;
     const int n = ctx->n, V = p->views;
     const int k_pad = (n + 15) / 16 * 16;
     // 64 spare rows: a view range may start anywhere, and a wave always reads whole 32-row tiles
@@ -767,6 +770,75 @@ int lfi_set_view_offsets(lfi_ctx *ctx, const lfi_int2 *focused_offsets_vn, int v
     return LFI_OK;
 }
 
+int lfi_set_view_float_offsets(lfi_ctx *ctx, const lfi_float2 *offsets_vn, int views)
+{
+    if(!ctx)
+        return LFI_EINVAL;
+    if(!ctx->have_params)
+        return fail(ctx, LFI_EINVAL, "lfi_set_params has not been called");
+    if(!offsets_vn)
+    {
+        ctx->view_float_offsets_set = false;
+        return LFI_OK;
+    }
+    if(views != ctx->views_n)
+        return fail(ctx, LFI_EINVAL, "lfi_set_view_float_offsets: views (" + std::to_string(views) + ") differs from lfi_params.views (" +
+                                         std::to_string(ctx->views_n) + ")");
+    const int n = ctx->n;
+    for(size_t i = 0; i < (size_t)views * n; i++)
+        if(!std::isfinite(offsets_vn[i].x) || !std::isfinite(offsets_vn[i].y))
+            return fail(ctx, LFI_EINVAL, "lfi_set_view_float_offsets: offsets must be finite");
+    if(int rc = bind(ctx))
+        return rc;
+    // [N][v_pad], views contiguous (one scalar run per image and chunk of views), zero padding views
+    const int pitch = ctx->v_pad;
+    const size_t bytes = sizeof(lfi_float2) * (size_t)n * pitch;
+    if(bytes > ctx->view_float_offsets_bytes)
+    {
+        LFI_HIP(ctx, hipStreamSynchronize(ctx->stream)); // renders in flight may read the old buffer
+        if(ctx->d_view_float_offsets)
+            (void)hipFree(ctx->d_view_float_offsets);
+        ctx->d_view_float_offsets = nullptr;
+        ctx->view_float_offsets_bytes = 0;
+        LFI_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->d_view_float_offsets), bytes));
+        ctx->view_float_offsets_bytes = bytes;
+    }
+    // stream order, as lfi_set_view_offsets: the copy runs behind the renders already enqueued, out of one of two page-locked buffers
+    if(ctx->vfo_staging_bytes < bytes)
+    {
+        for(int i = 0; i < 2; i++)
+        {
+            if(ctx->ev_vfo[i])
+                LFI_HIP(ctx, hipEventSynchronize(ctx->ev_vfo[i]));
+            if(ctx->vfo_staging[i])
+                (void)hipHostFree(ctx->vfo_staging[i]);
+            ctx->vfo_staging[i] = nullptr;
+        }
+        ctx->vfo_staging_bytes = 0;
+        for(int i = 0; i < 2; i++)
+        {
+            LFI_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->vfo_staging[i]), bytes, hipHostMallocDefault));
+            if(!ctx->ev_vfo[i])
+                LFI_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_vfo[i], hipEventDisableTiming));
+        }
+        ctx->vfo_staging_bytes = bytes;
+    }
+    else
+        LFI_HIP(ctx, hipEventSynchronize(ctx->ev_vfo[ctx->vfo_slot])); // the copy out of this buffer, two calls ago, has run
+    lfi_float2 *staged = ctx->vfo_staging[ctx->vfo_slot];
+    std::memset(staged, 0, bytes);
+    for(int v = 0; v < views; v++)
+        for(int g = 0; g < n; g++)
+            staged[(size_t)g * pitch + v] = offsets_vn[(size_t)v * n + g];
+    LFI_HIP(ctx, hipMemcpyAsync(ctx->d_view_float_offsets, staged, bytes, hipMemcpyHostToDevice, ctx->stream));
+    LFI_HIP(ctx, hipEventRecord(ctx->ev_vfo[ctx->vfo_slot], ctx->stream));
+    ctx->vfo_slot ^= 1;
+    ctx->vfo_pitch = pitch;
+    ctx->h_view_float_offsets.assign(offsets_vn, offsets_vn + (size_t)views * n);
+    ctx->view_float_offsets_set = true;
+    return LFI_OK;
+}
+
 int lfi_attach_views(lfi_ctx *ctx, void *device_ptr, size_t bytes)
 {
     if(!ctx)
@@ -958,6 +1030,8 @@ int lfi_prepare(lfi_ctx *ctx, int method, int all_focus, int v0, int v1)
         return rc;
     const KernelArgs a = make_args(ctx, v0, v1, method);
     ctx->derived_build_ms = 0.0f;
+    if(all_focus && ctx->view_float_offsets_set) // per-view float offsets: the RGBA planes are read as they are, nothing to build
+        return vfocus_af_check(ctx, a);
     if(ctx->view_offsets_set) // per-view focus: the copy padded for the per-view shifts, as launch_vfocus makes it
     {
         const uint64_t before = ctx->planar_version;
@@ -1033,6 +1107,9 @@ int lfi_render_stream(lfi_ctx *ctx, int method, int all_focus, const uint16_t *w
         return rc;
     if(ctx->view_offsets_set)
         return fail(ctx, LFI_EINVAL, "per-view offsets are set (lfi_set_view_offsets): lfi_render_stream is not supported - clear them with NULL");
+    if(all_focus && ctx->view_float_offsets_set)
+        return fail(ctx, LFI_EINVAL, "per-view float offsets are set (lfi_set_view_float_offsets): all-focus lfi_render_stream is not supported - "
+                                     "clear them with NULL");
     if(!weights_fp16 || total_views < 1)
         return fail(ctx, LFI_EINVAL, "lfi_render_stream: weights are NULL or total_views < 1");
     if(host_out && (ctx->out_layout != LFI_LAYOUT_RGBA || pitch_bytes < (size_t)ctx->width * 4))
@@ -1224,7 +1301,12 @@ int lfi_benchmark(lfi_ctx *ctx, int method, int all_focus, int v0, int v1, int w
         return rc;
     const KernelArgs a = make_args(ctx, v0, v1, method);
     // the derived input copy is (re)built here, not inside the first timed launch
-    if(ctx->view_offsets_set)
+    if(all_focus && ctx->view_float_offsets_set)
+    {
+        if(int rc = vfocus_af_check(ctx, a))
+            return rc;
+    }
+    else if(ctx->view_offsets_set)
     {
         bool planar = false;
         if(int rc = vfocus_source(ctx, all_focus, a, &planar))

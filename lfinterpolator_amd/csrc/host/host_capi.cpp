@@ -72,6 +72,36 @@ int lfi_host_build_view_offsets(int cols, int rows, int width, int height, const
     }
 }
 
+// each view shifted about its own camera: offsets_vn / focused_vn [views][N] = Parameterizer::offsets at focus_v[v] for the trajectory
+// collapsed onto camera v (the rows lfi_set_view_float_offsets / lfi_set_view_offsets take); either output may be NULL
+int lfi_host_build_view_centred_offsets(int cols, int rows, int width, int height, const char *trajectory, float aspect, const float *focus_v,
+                                        int views, lfi_float2 *offsets_vn, lfi_int2 *focused_vn, char *err, size_t err_len)
+{
+    try
+    {
+        if(views < 1 || !focus_v)
+            throw std::runtime_error("views must be positive and focus_v non-NULL");
+        lfi::Parameterizer p({cols, rows}, {width, height, 4});
+        std::vector<lfi_float2> o;
+        std::vector<lfi_int2> d;
+        p.viewCentredOffsets(aspect, std::vector<float>(focus_v, focus_v + views), p.interpretTrajectory(trajectory), o, d);
+        if(offsets_vn)
+            std::memcpy(offsets_vn, o.data(), sizeof(lfi_float2) * o.size());
+        if(focused_vn)
+            std::memcpy(focused_vn, d.data(), sizeof(lfi_int2) * d.size());
+        return 0;
+    }
+    catch(const std::exception &e)
+    {
+        if(err && err_len)
+        {
+            std::strncpy(err, e.what(), err_len - 1);
+            err[err_len - 1] = 0;
+        }
+        return -1;
+    }
+}
+
 uint16_t lfi_host_float_to_half(float v)
 {
     return lfi::floatToHalfBits(v);

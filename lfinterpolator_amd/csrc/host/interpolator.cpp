@@ -140,14 +140,30 @@ void Interpolator::interpolate(std::string outputPath, std::string trajectory, f
         check(lfi_set_output_layout(c, (methodID == LFI_METHOD_TEN_WM && !(inRange > 0)) ? LFI_LAYOUT_PLANAR_RGB : LFI_LAYOUT_RGBA), c);
 
     const int allFocus = inRange > 0;
-    if(perViewFocus)
+    if(perViewFocus && allFocus)
+        throw std::runtime_error("A focus per view cannot be combined with all-focus rendering (-r)!");
+    const size_t n = params.offsets.size();
+    if(viewCentred)
     {
-        if(allFocus)
-            throw std::runtime_error("A focus per view cannot be combined with all-focus rendering (-r)!");
+        // every view shifted about its own camera; every GPU gets the rows of its own views
+        const std::vector<float> focusVn = perViewFocus ? lfi::focusRamp(focus, focusEnd, viewCount) : std::vector<float>(viewCount, focus);
+        std::vector<lfi_float2> offsetsVn;
+        std::vector<lfi_int2> focusedVn;
+        parameterizer.viewCentredOffsets(aspect, focusVn, parameterizer.interpretTrajectory(trajectory), offsetsVn, focusedVn);
+        for(int g = 0; g < gpuCount; g++)
+        {
+            const int views = viewStart[g + 1] - viewStart[g];
+            if(allFocus)
+                check(lfi_set_view_float_offsets(contexts[g], offsetsVn.data() + viewStart[g] * n, views), contexts[g]);
+            else
+                check(lfi_set_view_offsets(contexts[g], focusedVn.data() + viewStart[g] * n, views), contexts[g]);
+        }
+    }
+    else if(perViewFocus)
+    {
         // every GPU gets the rows of its own views
         const std::vector<lfi_int2> rowsVn = parameterizer.viewOffsets(aspect, lfi::focusRamp(focus, focusEnd, viewCount),
                                                                         parameterizer.interpretTrajectory(trajectory));
-        const size_t n = params.offsets.size();
         for(int g = 0; g < gpuCount; g++)
             check(lfi_set_view_offsets(contexts[g], rowsVn.data() + viewStart[g] * n, viewStart[g + 1] - viewStart[g]), contexts[g]);
     }

@@ -32,6 +32,10 @@ class Interpolator
         // a focus per view: view i is rendered at focus + ((end − focus) / (views − 1))·i (a focus pull; with a single-point trajectory a
         // focal stack) through lfi_set_view_offsets — fixed-focus renders only
         void setFocusEnd(float end) { focusEnd = end; perViewFocus = true; }
+        // each view's shifts taken from its own camera position instead of the trajectory's centre (the reference's only choice): integer
+        // rows through lfi_set_view_offsets for fixed focus (with setFocusEnd: at each view's focus), float rows through
+        // lfi_set_view_float_offsets for all-focus renders
+        void setViewCentred(bool on) { viewCentred = on; }
 
         // synthetic cols×rows grid of width×height images instead of a directory
         Interpolator(lfi::IVec2 colsRows, lfi::IVec2 resolution, uint32_t seed, int device = 0);
@@ -46,6 +50,7 @@ class Interpolator
         lfi_ctx *context{nullptr};
         int gpuCount{1};
         bool perViewFocus{false};
+        bool viewCentred{false};
         float focusEnd{0};
         std::vector<lfi_ctx *> contexts; // one per GPU; contexts[0] == context
         std::vector<int> viewStart;      // first view of each GPU's range (size gpuCount + 1)

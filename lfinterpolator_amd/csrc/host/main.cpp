@@ -1,6 +1,6 @@
 // main.cpp — command line of the interpolator; flags, defaults, messages and exit codes as in reference src/main.cpp:4-57
-// (-i -t -o -f -r -m -s -a -h), plus -n (views), -b (benchmark runs), -d (device), -F (focus at the last view) and --synthetic for runs
-// without a dataset.
+// (-i -t -o -f -r -m -s -a -h), plus -n (views), -b (benchmark runs), -d (device), -F (focus at the last view), -c (shifts about each
+// view's own camera) and --synthetic for runs without a dataset.
 #include <iostream>
 #include <memory>
 #include <sstream>
@@ -33,6 +33,7 @@ int main(int argc, char **argv)
                           "-f - focusing value (default=0)\n"
                           "-r - focusing range (will be added to the focusing value) - will produce all-focused result if used\n"
                           "-F - focusing value at the last view: the focus ramps from -f at the first view to -F at the last (a focus pull; a focal stack with a single-point trajectory such as -t 0.5,0.5,0.5,0.5); not with -r\n"
+                          "-c - shift the images about each view's own camera position instead of the trajectory's centre (the default, as the reference does); with -r and with -f/-F\n"
                           "Additional arguments:\n"
                           "-n - number of views rendered along the trajectory (default=64)\n"
                           "-b - number of timed kernel launches (default=100)\n"
@@ -95,6 +96,8 @@ int main(int argc, char **argv)
             interpolator->setBenchmarkRuns(static_cast<size_t>(static_cast<int>(args["-b"])));
         if(args["--unified-map"])
             interpolator->setUnifiedFocusMap(true);
+        if(args["-c"])
+            interpolator->setViewCentred(true);
         if(args["-F"])
             interpolator->setFocusEnd(static_cast<float>(args["-F"]));
         if(args["-q"])

@@ -225,6 +225,24 @@ std::vector<lfi_int2> Parameterizer::viewOffsets(float aspect, const std::vector
     return out;
 }
 
+void Parameterizer::viewCentredOffsets(float aspect, const std::vector<float> &focus, Vec4 startEndPoints, std::vector<lfi_float2> &outOffsets,
+                                       std::vector<lfi_int2> &outFocused) const
+{
+    const size_t n = static_cast<size_t>(colsRows.x) * colsRows.y;
+    const std::vector<Vec2> cameras = generateTrajectory(startEndPoints, static_cast<int>(focus.size()));
+    outOffsets.assign(focus.size() * n, lfi_float2{0.0f, 0.0f});
+    outFocused.assign(focus.size() * n, lfi_int2{0, 0});
+    std::vector<lfi_float2> shifts;
+    std::vector<lfi_int2> row;
+    for(size_t v = 0; v < focus.size(); v++)
+    {
+        const Vec2 cam = cameras[v];
+        offsets(aspect, focus[v], Vec4{cam.x, cam.y, cam.x, cam.y}, shifts, row);
+        std::copy(shifts.begin(), shifts.end(), outOffsets.begin() + v * n);
+        std::copy(row.begin(), row.end(), outFocused.begin() + v * n);
+    }
+}
+
 std::vector<float> focusRamp(float f0, float f1, int views)
 {
     std::vector<float> ramp(static_cast<size_t>(std::max(views, 1)), f0);

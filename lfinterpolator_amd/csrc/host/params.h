@@ -47,6 +47,11 @@ class Parameterizer
                      std::vector<lfi_int2> &focusedOffsets) const;
         // per-view focus (lfi_set_view_offsets): [views][N] integer offsets, row v = offsets(aspect, focus[v], …)'s focused offsets
         std::vector<lfi_int2> viewOffsets(float aspect, const std::vector<float> &focus, Vec4 startEndPoints) const;
+        // each view shifted about its own camera (lfi_set_view_float_offsets / lfi_set_view_offsets): row v of offsets [views][N] and
+        // focused [views][N] is offsets(aspect, focus[v], {cam_v, cam_v}) for camera v of generateTrajectory(startEndPoints, views) — the
+        // trajectory collapsed onto that camera, whose centre is the camera itself
+        void viewCentredOffsets(float aspect, const std::vector<float> &focus, Vec4 startEndPoints, std::vector<lfi_float2> &offsets,
+                                std::vector<lfi_int2> &focused) const;
         std::vector<int32_t> selectFocusMapViews(Vec4 startEndPoints) const;
         IVec2 blockRadius() const;
 

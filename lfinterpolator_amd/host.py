@@ -28,6 +28,9 @@ def load_host_library() -> C.CDLL:
         lib.lfi_host_build_view_offsets.restype = C.c_int
         lib.lfi_host_build_view_offsets.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_float, C.c_void_p, C.c_int,
                                                     C.c_void_p, C.c_char_p, C.c_size_t]
+        lib.lfi_host_build_view_centred_offsets.restype = C.c_int
+        lib.lfi_host_build_view_centred_offsets.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_float, C.c_void_p, C.c_int,
+                                                            C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]
         lib.lfi_host_float_to_half.restype = C.c_uint16
         lib.lfi_host_float_to_half.argtypes = [C.c_float]
         lib.lfi_host_half_to_float.restype = C.c_float
@@ -95,6 +98,17 @@ def build_view_offsets(cols: int, rows: int, width: int, height: int, trajectory
     _err_call(load_host_library().lfi_host_build_view_offsets, cols, rows, width, height, trajectory.encode(), aspect, f.ctypes.data,
               len(f), out.ctypes.data)
     return out
+
+
+def build_view_centred_offsets(cols: int, rows: int, width: int, height: int, trajectory: str, aspect: float, focus_v):
+    """Each view shifted about its own camera: (O [V][N][2] float32 for Context.set_view_float_offsets, D [V][N][2] int32 for
+    Context.set_view_offsets) — row v = Parameterizer::offsets at focus_v[v] for the trajectory collapsed onto camera v of V."""
+    f = np.ascontiguousarray(np.atleast_1d(focus_v), dtype=np.float32)
+    o = np.zeros((len(f), cols * rows, 2), dtype=np.float32)
+    d = np.zeros((len(f), cols * rows, 2), dtype=np.int32)
+    _err_call(load_host_library().lfi_host_build_view_centred_offsets, cols, rows, width, height, trajectory.encode(), aspect, f.ctypes.data,
+              len(f), o.ctypes.data, d.ctypes.data)
+    return o, d
 
 
 def _err_call(fn, *args):
