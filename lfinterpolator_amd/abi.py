@@ -303,22 +303,20 @@ class Context:
     def set_view_offsets(self, offsets_vn: np.ndarray | None) -> None:
         """Per-view focus (lfi_set_view_offsets): offsets_vn is [views][N][2] int32 — view v samples image g at pixel + offsets_vn[v][g]
         (lfinterpolator_amd.build_view_offsets computes them); None clears them."""
-        if offsets_vn is None:
-            self._check(self._lib.lfi_set_view_offsets(self._h, None, 0))
-            return
-        d = np.ascontiguousarray(offsets_vn, dtype=np.int32)
-        assert d.ndim == 3 and d.shape[1:] == (self.n_images, 2), d.shape
-        self._check(self._lib.lfi_set_view_offsets(self._h, _ptr(d), d.shape[0]))
+        self._set_view_rows(self._lib.lfi_set_view_offsets, offsets_vn, np.int32)
 
     def set_view_float_offsets(self, offsets_vn: np.ndarray | None) -> None:
         """Per-view float offsets for all-focus renders (lfi_set_view_float_offsets): offsets_vn is [views][N][2] float32 — view v samples
         image g at (int)fma(f, offsets_vn[v][g], pixel) (lfinterpolator_amd.build_view_centred_offsets computes them); None clears them."""
-        if offsets_vn is None:
-            self._check(self._lib.lfi_set_view_float_offsets(self._h, None, 0))
+        self._set_view_rows(self._lib.lfi_set_view_float_offsets, offsets_vn, np.float32)
+
+    def _set_view_rows(self, fn, rows_vn, dtype) -> None:
+        if rows_vn is None:
+            self._check(fn(self._h, None, 0))
             return
-        o = np.ascontiguousarray(offsets_vn, dtype=np.float32)
-        assert o.ndim == 3 and o.shape[1:] == (self.n_images, 2), o.shape
-        self._check(self._lib.lfi_set_view_float_offsets(self._h, _ptr(o), o.shape[0]))
+        r = np.ascontiguousarray(rows_vn, dtype=dtype)
+        assert r.ndim == 3 and r.shape[1:] == (self.n_images, 2), r.shape
+        self._check(fn(self._h, _ptr(r), r.shape[0]))
 
     def set_output_layout(self, layout) -> None:
         """'rgba' (the reference's planes) or 'planar' (alpha-free byte planes; downloads re-create alpha = 255)."""

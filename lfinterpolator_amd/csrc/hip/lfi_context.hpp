@@ -26,6 +26,98 @@ thread_local std::string g_create_error;
 
 } // namespace
 
+// Two page-locked buffers, one event each: the host fills the current buffer, a copy out of it is enqueued on a stream, and the buffer is
+// not written again before that copy has run (two uses later) — uploads in stream order without draining the stream.
+struct StagingRing
+{
+    void *buf[2] = {nullptr, nullptr};
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    size_t bytes = 0; // capacity of each buffer
+    int slot = 0;
+
+    // the current buffer, at least `need` bytes and free to write: both buffers grow once their copies have run; else this one's copy has run
+    template <class T>
+    hipError_t acquire(size_t need, T **out)
+    {
+        if(bytes < need)
+        {
+            for(int i = 0; i < 2; i++)
+            {
+                if(ev[i])
+                    if(hipError_t e = hipEventSynchronize(ev[i]))
+                        return e;
+                if(buf[i])
+                    (void)hipHostFree(buf[i]);
+                buf[i] = nullptr;
+            }
+            bytes = 0;
+            for(int i = 0; i < 2; i++)
+            {
+                if(hipError_t e = hipHostMalloc(&buf[i], need, hipHostMallocDefault))
+                    return e;
+                if(!ev[i])
+                    if(hipError_t e = hipEventCreateWithFlags(&ev[i], hipEventDisableTiming))
+                        return e;
+            }
+            bytes = need;
+        }
+        else if(hipError_t e = hipEventSynchronize(ev[slot]))
+            return e;
+        *out = static_cast<T *>(buf[slot]);
+        return hipSuccess;
+    }
+
+    // the copy out of the current buffer has been enqueued on s: mark its end and move to the other buffer
+    hipError_t commit(hipStream_t s)
+    {
+        if(hipError_t e = hipEventRecord(ev[slot], s))
+            return e;
+        slot ^= 1;
+        return hipSuccess;
+    }
+
+    hipEvent_t committed() const { return ev[slot ^ 1]; } // the event the last commit recorded
+
+    void release()
+    {
+        for(int i = 0; i < 2; i++)
+        {
+            if(ev[i])
+                (void)hipEventSynchronize(ev[i]);
+            if(buf[i])
+                (void)hipHostFree(buf[i]);
+            buf[i] = nullptr;
+            if(ev[i])
+                (void)hipEventDestroy(ev[i]);
+            ev[i] = nullptr;
+        }
+        bytes = 0;
+        slot = 0;
+    }
+};
+
+// One element of type T per (view, image), on the device as [N][pitch] (views contiguous, pitch = v_pad, zero padding views), written in
+// stream order out of a staging ring (stage_view_rows)
+template <class T>
+struct ViewRows
+{
+    bool set = false;
+    T *dev = nullptr;
+    size_t dev_bytes = 0;
+    int pitch = 0;
+    StagingRing ring;
+
+    void release() // the caller has drained the stream
+    {
+        set = false;
+        if(dev)
+            (void)hipFree(dev);
+        dev = nullptr;
+        dev_bytes = 0;
+        ring.release();
+    }
+};
+
 struct lfi_ctx
 {
     int device = 0;
@@ -76,12 +168,9 @@ struct lfi_ctx
     int views_n = 0, k_pad = 0, v_pad = 0, n_focus_ids = 0;
     void *param_blob = nullptr; // one allocation holding all parameter arrays
     size_t param_blob_bytes = 0;
-    // lfi_set_params with an unchanged blob size (a focus sweep, a new trajectory with as many views): the new arrays go through one of two
-    // page-locked staging buffers and a stream-ordered copy — no synchronisation, no allocation
-    uint8_t *param_staging[2] = {nullptr, nullptr};
-    size_t param_staging_bytes = 0;
-    hipEvent_t ev_param[2] = {nullptr, nullptr};
-    int param_slot = 0;
+    // lfi_set_params with an unchanged blob size (a focus sweep, a new trajectory with as many views): the new arrays go through the
+    // staging ring and a stream-ordered copy — no synchronisation, no allocation
+    StagingRing param_ring;
     // … and there are TWO copies of the arrays on the device: a replacement is copied into the idle one on the copy stream, beside the renders
     // still running from the other (round 5: in stream order behind them it cost a fixed-focus sweep 22 µs per step, profiles/r05_notes.md)
     size_t param_half_stride = 0;
@@ -118,9 +207,7 @@ struct lfi_ctx
     int planar_pitch = 0, planar_padx = 0, planar_reach = 0; // bytes per plane row; left padding; the largest |x offset| it was built for
     int32_t *d_planar_phase = nullptr;      // [LFI_MAX_IMAGES] per-image phase of the planar copy (device)
     std::vector<int32_t> planar_phase;      // the same on the host
-    int32_t *phase_staging = nullptr;       // page-locked, 2 × LFI_MAX_IMAGES: a rebuild's phases go to the device in stream order, no host wait
-    hipEvent_t ev_phase[2] = {nullptr, nullptr};
-    int phase_slot = 0;
+    StagingRing phase_ring;                 // a rebuild's phases go to the device in stream order, no host wait
     std::vector<lfi_int2> h_focused;        // the integer offsets of the current parameters (host copy)
     unsigned launches_with_offsets = 0;     // fixed-focus launches since the integer offsets last changed
     uint64_t grid_version = 1, planar_version = 0;
@@ -142,29 +229,13 @@ struct lfi_ctx
     mutable const char *last_kernel = ""; // the blend kernel the last render launched (lfi_last_kernel_name)
     mutable unsigned sweep_launches = 0;  // blend_p3 / blend_planar alternate their sweep direction from launch to launch
     float derived_build_ms = 0.0f;        // duration of the last planar_build (measured by lfi_prepare only)
-    // lfi_set_view_offsets: one integer offset per (view, image) on the device, [N][vo_pitch] (views contiguous, zero padded; vo_pitch = v_pad),
-    // written in stream order from one of two page-locked staging buffers; cleared (not freed: renders in flight may still read it) by
-    // lfi_set_params / lfi_set_grid / lfi_set_row_window
-    bool view_offsets_set = false;
-    lfi_int2 *d_view_offsets = nullptr;
-    size_t view_offsets_bytes = 0;
-    int vo_pitch = 0;
-    int vo_reach = 0;                       // max |D.x| over the rows set: the padding the planar copy needs to serve them
-    lfi_int2 *vo_staging[2] = {nullptr, nullptr};
-    size_t vo_staging_bytes = 0;
-    hipEvent_t ev_vo[2] = {nullptr, nullptr};
-    int vo_slot = 0;
-    // lfi_set_view_float_offsets: one float offset per (view, image) for all-focus renders, [N][vfo_pitch] on the device (views contiguous,
-    // zero padded) and [views][N] on the host (the row-window check), staged and cleared exactly like the integer per-view offsets above
-    bool view_float_offsets_set = false;
-    lfi_float2 *d_view_float_offsets = nullptr;
-    size_t view_float_offsets_bytes = 0;
-    int vfo_pitch = 0;
+    // per-view rows (stage_view_rows): cleared (not freed: renders in flight may still read them) by lfi_set_params / lfi_set_grid /
+    // lfi_set_row_window.  lfi_set_view_offsets: integer offsets for fixed-focus renders; lfi_set_view_float_offsets: float offsets for
+    // all-focus renders, also kept as given, [views][N], for the row-window check at render time
+    ViewRows<lfi_int2> view_offsets;
+    int view_offsets_reach = 0;             // max |D.x| over the integer rows set: the padding the planar copy needs to serve them
+    ViewRows<lfi_float2> view_float_offsets;
     std::vector<lfi_float2> h_view_float_offsets;
-    lfi_float2 *vfo_staging[2] = {nullptr, nullptr};
-    size_t vfo_staging_bytes = 0;
-    hipEvent_t ev_vfo[2] = {nullptr, nullptr};
-    int vfo_slot = 0;
     std::string err;
 };
 
@@ -420,72 +491,53 @@ void free_params(lfi_ctx *c)
     c->param_half = 0;
     c->half_done_recorded[0] = c->half_done_recorded[1] = false;
     c->have_params = false;
-    c->view_offsets_set = false;
-    c->view_float_offsets_set = false;
+    c->view_offsets.set = c->view_float_offsets.set = false;
 }
 
-// the per-view offsets' buffers (lfi_set_view_offsets); the caller has drained the stream
-void free_view_offsets(lfi_ctx *c)
+// both sets of per-view rows' buffers; the caller has drained the stream
+void free_view_rows(lfi_ctx *c)
 {
-    c->view_offsets_set = false;
-    if(c->d_view_offsets)
-        (void)hipFree(c->d_view_offsets);
-    c->d_view_offsets = nullptr;
-    c->view_offsets_bytes = 0;
-    for(int i = 0; i < 2; i++)
-    {
-        if(c->vo_staging[i])
-            (void)hipHostFree(c->vo_staging[i]);
-        c->vo_staging[i] = nullptr;
-        if(c->ev_vo[i])
-            (void)hipEventDestroy(c->ev_vo[i]);
-        c->ev_vo[i] = nullptr;
-    }
-    c->vo_staging_bytes = 0;
-}
-
-// the per-view float offsets' buffers (lfi_set_view_float_offsets); the caller has drained the stream
-void free_view_float_offsets(lfi_ctx *c)
-{
-    c->view_float_offsets_set = false;
-    if(c->d_view_float_offsets)
-        (void)hipFree(c->d_view_float_offsets);
-    c->d_view_float_offsets = nullptr;
-    c->view_float_offsets_bytes = 0;
+    c->view_offsets.release();
+    c->view_float_offsets.release();
     c->h_view_float_offsets.clear();
-    for(int i = 0; i < 2; i++)
+}
+
+// The shared tail of lfi_set_view_offsets / lfi_set_view_float_offsets: rows at(v, g) of views [0, views_n) to r's device buffer as
+// [N][v_pad] (views contiguous: one scalar run per image and chunk of views; padding views zero), in stream order like lfi_set_params —
+// the copy runs behind the renders already enqueued, out of r's staging ring.
+template <class T, class At>
+int stage_view_rows(lfi_ctx *ctx, ViewRows<T> &r, At at)
+{
+    const int n = ctx->n, views = ctx->views_n, pitch = ctx->v_pad;
+    const size_t bytes = sizeof(T) * (size_t)n * pitch;
+    if(bytes > r.dev_bytes)
     {
-        if(c->vfo_staging[i])
-            (void)hipHostFree(c->vfo_staging[i]);
-        c->vfo_staging[i] = nullptr;
-        if(c->ev_vfo[i])
-            (void)hipEventDestroy(c->ev_vfo[i]);
-        c->ev_vfo[i] = nullptr;
+        LFI_HIP(ctx, hipStreamSynchronize(ctx->stream)); // renders in flight may read the old buffer
+        r.set = false;
+        if(r.dev)
+            (void)hipFree(r.dev);
+        r.dev = nullptr;
+        r.dev_bytes = 0;
+        LFI_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&r.dev), bytes));
+        r.dev_bytes = bytes;
     }
-    c->vfo_staging_bytes = 0;
+    T *staged = nullptr;
+    LFI_HIP(ctx, r.ring.acquire(bytes, &staged));
+    std::memset(staged, 0, bytes);
+    for(int v = 0; v < views; v++)
+        for(int g = 0; g < n; g++)
+            staged[(size_t)g * pitch + v] = at(v, g);
+    LFI_HIP(ctx, hipMemcpyAsync(r.dev, staged, bytes, hipMemcpyHostToDevice, ctx->stream));
+    LFI_HIP(ctx, r.ring.commit(ctx->stream));
+    r.pitch = pitch;
+    r.set = true;
+    return LFI_OK;
 }
 
 // the copy of the parameter arrays that launches enqueued from now on read
 uint8_t *param_base(const lfi_ctx *c)
 {
     return static_cast<uint8_t *>(c->param_blob) + (size_t)c->param_half * c->param_half_stride;
-}
-
-void free_param_staging(lfi_ctx *c)
-{
-    for(int i = 0; i < 2; i++)
-    {
-        if(c->param_staging[i])
-            (void)hipHostFree(c->param_staging[i]);
-        c->param_staging[i] = nullptr;
-        if(c->ev_param[i])
-            (void)hipEventDestroy(c->ev_param[i]);
-        c->ev_param[i] = nullptr;
-        if(c->ev_half_done[i])
-            (void)hipEventDestroy(c->ev_half_done[i]);
-        c->ev_half_done[i] = nullptr;
-    }
-    c->param_staging_bytes = 0;
 }
 
 void free_views(lfi_ctx *c)
@@ -556,15 +608,7 @@ void free_grid(lfi_ctx *c)
     if(c->d_planar_phase)
         (void)hipFree(c->d_planar_phase);
     c->d_planar_phase = nullptr;
-    if(c->phase_staging)
-        (void)hipHostFree(c->phase_staging);
-    c->phase_staging = nullptr;
-    for(int i = 0; i < 2; i++)
-    {
-        if(c->ev_phase[i])
-            (void)hipEventDestroy(c->ev_phase[i]);
-        c->ev_phase[i] = nullptr;
-    }
+    c->phase_ring.release();
 }
 
 } // namespace

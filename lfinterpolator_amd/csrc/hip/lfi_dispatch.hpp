@@ -463,31 +463,23 @@ bool ensure_planar(lfi_ctx *c, bool tune = false, int min_reach = 0)
         c->d_planar_phase = nullptr;
         return false;
     }
-    // the phases: (offset + padx + phase) ≡ 0 mod LFI_PLANAR_ALIGN for the offsets in use now.  They travel through one of two page-locked buffers and a
+    // the phases: (offset + padx + phase) ≡ 0 mod LFI_PLANAR_ALIGN for the offsets in use now.  They travel through the staging ring and a
     // stream-ordered copy (as lfi_set_params' blob does): kernels of earlier launches that read the old phases are ordered before the
     // copy, the build and every later launch after it, and the host never waits for the stream (round 3 copied from a pageable vector
     // and synchronised the stream inside lfi_render).
-    if(!c->phase_staging)
+    int32_t *staged = nullptr;
+    if(c->phase_ring.acquire(sizeof(int32_t) * LFI_MAX_IMAGES, &staged) != hipSuccess)
     {
-        if(hipHostMalloc(reinterpret_cast<void **>(&c->phase_staging), sizeof(int32_t) * 2 * LFI_MAX_IMAGES, hipHostMallocDefault) != hipSuccess ||
-           hipEventCreateWithFlags(&c->ev_phase[0], hipEventDisableTiming) != hipSuccess ||
-           hipEventCreateWithFlags(&c->ev_phase[1], hipEventDisableTiming) != hipSuccess)
-        {
-            (void)hipGetLastError();
-            return false;
-        }
-    }
-    else if(hipEventSynchronize(c->ev_phase[c->phase_slot]) != hipSuccess) // the copy out of this buffer, two rebuilds ago, has run
+        (void)hipGetLastError();
         return false;
+    }
     c->planar_phase.assign(c->n, 0);
-    int32_t *staged = c->phase_staging + (size_t)c->phase_slot * LFI_MAX_IMAGES;
     for(int g = 0; g < c->n; g++)
         staged[g] = c->planar_phase[g] = (LFI_PLANAR_ALIGN - ((c->h_focused[g].x + padx) & (LFI_PLANAR_ALIGN - 1))) & (LFI_PLANAR_ALIGN - 1);
     c->planar_version = 0;
     if(hipMemcpyAsync(c->d_planar_phase, staged, sizeof(int32_t) * c->n, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-       hipEventRecord(c->ev_phase[c->phase_slot], c->stream) != hipSuccess)
+       c->phase_ring.commit(c->stream) != hipSuccess)
         return false;
-    c->phase_slot ^= 1;
     c->planar_padx = padx;
     c->planar_reach = built_for;
     c->planar_pitch = pitch;
@@ -681,8 +673,24 @@ void launch_p3(const lfi_ctx *c, const KernelArgs &a_in, bool rgba_out)
 // after launch_blend had committed to kernels that write byte planes)
 int launch_blend_rgba(lfi_ctx *c, int method, int all_focus, const KernelArgs &a_in, bool planar_decided = false);
 
-int launch_vfocus(lfi_ctx *c, int method, int all_focus, const KernelArgs &a_in);
-int launch_vfocus_af(lfi_ctx *c, int method, const KernelArgs &a_in);
+// per-view rows (lfi_set_view_offsets / lfi_set_view_float_offsets) and which of them govern a render: the float rows an all-focus one,
+// when set; otherwise the integer rows, when set (which refuse all-focus renders: view_rows_ready)
+enum ViewRowsKind { VIEW_ROWS_NONE, VIEW_ROWS_INT, VIEW_ROWS_FLOAT };
+
+ViewRowsKind view_rows_of(const lfi_ctx *c, int all_focus)
+{
+    if(all_focus && c->view_float_offsets.set)
+        return VIEW_ROWS_FLOAT;
+    return c->view_offsets.set ? VIEW_ROWS_INT : VIEW_ROWS_NONE;
+}
+
+// the start of the message of every render the rows refuse
+std::string view_rows_set(ViewRowsKind k)
+{
+    return k == VIEW_ROWS_INT ? "per-view offsets are set (lfi_set_view_offsets): " : "per-view float offsets are set (lfi_set_view_float_offsets): ";
+}
+
+int launch_view_rows(lfi_ctx *c, ViewRowsKind k, int method, int all_focus, const KernelArgs &a_in);
 
 // Every image row an all-focus render of the output band can sample is held: (int)fma(f, offset.y, y) for f between the ends of the focus
 // range (the map decodes to focus + m/255·range), y in the band, over the n offsets o; ±1 for float rounding
@@ -705,10 +713,8 @@ int launch_blend(lfi_ctx *c, int method, int all_focus, const KernelArgs &a_in)
 {
     if(int rc = join_uploads(c))
         return rc;
-    if(all_focus && c->view_float_offsets_set) // per-view float offsets govern all-focus renders, the integer ones fixed-focus renders
-        return launch_vfocus_af(c, method, a_in);
-    if(c->view_offsets_set)
-        return launch_vfocus(c, method, all_focus, a_in);
+    if(const ViewRowsKind k = view_rows_of(c, all_focus))
+        return launch_view_rows(c, k, method, all_focus, a_in);
     if(all_focus && a_in.map_index == 1)
         if(int rc = join_filter(c)) // the filtered map may still be in the making on the side stream
             return rc;
@@ -821,30 +827,47 @@ int launch_blend_rgba(lfi_ctx *c, int method, int all_focus, const KernelArgs &a
     return LFI_OK;
 }
 
-// ---- per-view focus (lfi_set_view_offsets): blend_vfocus.hpp ----------------------------------------------------------------------------
+// ---- per-view rows (lfi_set_view_offsets / lfi_set_view_float_offsets): blend_vfocus.hpp, blend_vfocus_af.hpp ---------------------------
 
-// Can this render be served while per-view offsets are set?  (fixed focus only, no debug modes; after lfi_release_inputs only from a planar
-// copy padded for every per-view shift)  *planar: read the planar copy (made valid here for the per-view shifts) rather than the RGBA planes.
-int vfocus_source(lfi_ctx *c, int all_focus, const KernelArgs &a, bool *planar)
+// Can this render be served from the per-view rows k?  Neither kind serves debug modes.  Integer rows: fixed focus only, after
+// lfi_release_inputs only from a planar copy padded for every per-view shift; *planar: read the planar copy (made valid here for the
+// per-view shifts) rather than the RGBA planes.  Float rows: the RGBA planes present, every row that views [v0, v1) sample held.
+int view_rows_ready(lfi_ctx *c, ViewRowsKind k, int all_focus, const KernelArgs &a, bool *planar)
 {
-    if(all_focus)
-        return fail(c, LFI_EINVAL, "per-view offsets are set (lfi_set_view_offsets): all-focus renders are not supported - clear them with NULL");
+    *planar = false;
+    if(k == VIEW_ROWS_INT && all_focus)
+        return fail(c, LFI_EINVAL, view_rows_set(k) + "all-focus renders are not supported - clear them with NULL");
     if(a.prequant)
-        return fail(c, LFI_EINVAL, "per-view offsets are set (lfi_set_view_offsets): lfi_download_prequant is not supported - clear them with NULL");
+        return fail(c, LFI_EINVAL, view_rows_set(k) + "lfi_download_prequant is not supported - clear them with NULL");
     if(c->flags & LFI_FLAG_TEN_ROUND_PER_BATCH)
-        return fail(c, LFI_EINVAL, "per-view offsets are set (lfi_set_view_offsets): LFI_FLAG_TEN_ROUND_PER_BATCH is not supported");
-    *planar = ensure_planar(c, false, c->vo_reach);
-    if(c->inputs_released && !*planar)
-        return fail(c, LFI_EINVAL, "the RGBA inputs were released (lfi_release_inputs) and the planar copy's padding does not cover the per-view "
-                                   "offsets - upload the images again");
+        return fail(c, LFI_EINVAL, view_rows_set(k) + "LFI_FLAG_TEN_ROUND_PER_BATCH is not supported");
+    if(k == VIEW_ROWS_INT)
+    {
+        *planar = ensure_planar(c, false, c->view_offsets_reach);
+        if(c->inputs_released && !*planar)
+            return fail(c, LFI_EINVAL, "the RGBA inputs were released (lfi_release_inputs) and the planar copy's padding does not cover the per-view "
+                                       "offsets - upload the images again");
+        return LFI_OK;
+    }
+    if(c->inputs_released)
+        return fail(c, LFI_EINVAL, "the RGBA inputs were released (lfi_release_inputs): all-focus renders need them - upload the images again");
+    if(c->windowed)
+        for(int v = a.v0; v < a.v1; v++)
+            if(!allfocus_rows_held(c, c->h_view_float_offsets.data() + (size_t)v * c->n, c->n))
+                return fail(c, LFI_EINVAL, "the input row window does not cover the rows an all-focus render of this band samples in view " +
+                                               std::to_string(v));
     return LFI_OK;
 }
 
-int launch_vfocus(lfi_ctx *c, int method, int all_focus, const KernelArgs &a_in)
+// blend_vfocus (integer rows) or blend_vfocus_af (float rows) over views [a.v0, a.v1)
+int launch_view_rows(lfi_ctx *c, ViewRowsKind k, int method, int all_focus, const KernelArgs &a_in)
 {
     bool planar = false;
-    if(int rc = vfocus_source(c, all_focus, a_in, &planar))
+    if(int rc = view_rows_ready(c, k, all_focus, a_in, &planar))
         return rc;
+    if(k == VIEW_ROWS_FLOAT && a_in.map_index == 1)
+        if(int rc = join_filter(c)) // the filtered map may still be in the making on the side stream
+            return rc;
     KernelArgs a = a_in;
     if(planar)
     {
@@ -859,78 +882,28 @@ int launch_vfocus(lfi_ctx *c, int method, int all_focus, const KernelArgs &a_in)
     const int tiles_y = (c->out_rows + lfi::VF_ROWS - 1) / lfi::VF_ROWS;
     const size_t blocks = (size_t)n_chunks * tiles_x * tiles_y;
     if(blocks >= (1ull << 31))
-        return fail(c, LFI_EINVAL, "per-view focus: too many views x pixels for one launch - render the views in ranges");
-    static const char *const names[2][2] = {{"blend_vfocus<STD>", "blend_vfocus<STD,rgba_src>"},
-                                            {"blend_vfocus<TEN_WM>", "blend_vfocus<TEN_WM,rgba_src>"}};
-    note_kernel(c, names[ten][!planar]);
-#define LFI_VF_LAUNCH(T, P, O)                                                                                                                   \
-    hipLaunchKernelGGL((lfi::blend_vfocus<T, P, O>), dim3((unsigned)blocks), dim3(256), 0, stream_of(c), a, c->d_view_offsets, c->vo_pitch, n_chunks, \
-                       tiles_x)
-    const int kind = (ten ? 4 : 0) | (planar ? 2 : 0) | (planar_out ? 1 : 0);
-    switch(kind)
+        return fail(c, LFI_EINVAL, view_rows_set(k) + "too many views x pixels for one launch - render the views in ranges");
+    static const char *const names[3][2] = {{"blend_vfocus<STD,rgba_src>", "blend_vfocus<TEN_WM,rgba_src>"},
+                                            {"blend_vfocus<STD>", "blend_vfocus<TEN_WM>"},
+                                            {"blend_vfocus_af<STD>", "blend_vfocus_af<TEN_WM>"}};
+    note_kernel(c, names[k == VIEW_ROWS_FLOAT ? 2 : planar][ten]);
+    if(k == VIEW_ROWS_INT)
     {
-        case 0: LFI_VF_LAUNCH(false, false, false); break;
-        case 1: LFI_VF_LAUNCH(false, false, true); break;
-        case 2: LFI_VF_LAUNCH(false, true, false); break;
-        case 3: LFI_VF_LAUNCH(false, true, true); break;
-        case 4: LFI_VF_LAUNCH(true, false, false); break;
-        case 5: LFI_VF_LAUNCH(true, false, true); break;
-        case 6: LFI_VF_LAUNCH(true, true, false); break;
-        default: LFI_VF_LAUNCH(true, true, true); break;
+        using lfi::blend_vfocus;
+        static const decltype(&blend_vfocus<false, false, false>) kernels[2][2][2] = {
+            {{blend_vfocus<false, false, false>, blend_vfocus<false, false, true>}, {blend_vfocus<false, true, false>, blend_vfocus<false, true, true>}},
+            {{blend_vfocus<true, false, false>, blend_vfocus<true, false, true>}, {blend_vfocus<true, true, false>, blend_vfocus<true, true, true>}}};
+        hipLaunchKernelGGL(kernels[ten][planar][planar_out], dim3((unsigned)blocks), dim3(256), 0, stream_of(c), a, c->view_offsets.dev,
+                           c->view_offsets.pitch, n_chunks, tiles_x);
     }
-#undef LFI_VF_LAUNCH
-    LFI_HIP(c, hipGetLastError());
-    return LFI_OK;
-}
-
-// ---- per-view float offsets (lfi_set_view_float_offsets): blend_vfocus_af.hpp --------------------------------------------------------------
-
-// Can this all-focus render be served while per-view float offsets are set?  (no debug modes, the RGBA planes present, every row that
-// views [v0, v1) sample held)
-int vfocus_af_check(lfi_ctx *c, const KernelArgs &a)
-{
-    if(a.prequant)
-        return fail(c, LFI_EINVAL, "per-view float offsets are set (lfi_set_view_float_offsets): all-focus lfi_download_prequant is not supported - "
-                                   "clear them with NULL");
-    if(c->flags & LFI_FLAG_TEN_ROUND_PER_BATCH)
-        return fail(c, LFI_EINVAL, "per-view float offsets are set (lfi_set_view_float_offsets): LFI_FLAG_TEN_ROUND_PER_BATCH is not supported");
-    if(c->inputs_released)
-        return fail(c, LFI_EINVAL, "the RGBA inputs were released (lfi_release_inputs): all-focus renders need them - upload the images again");
-    if(c->windowed)
-        for(int v = a.v0; v < a.v1; v++)
-            if(!allfocus_rows_held(c, c->h_view_float_offsets.data() + (size_t)v * c->n, c->n))
-                return fail(c, LFI_EINVAL, "the input row window does not cover the rows an all-focus render of this band samples in view " +
-                                               std::to_string(v));
-    return LFI_OK;
-}
-
-int launch_vfocus_af(lfi_ctx *c, int method, const KernelArgs &a)
-{
-    if(int rc = vfocus_af_check(c, a))
-        return rc;
-    if(a.map_index == 1)
-        if(int rc = join_filter(c)) // the filtered map may still be in the making on the side stream
-            return rc;
-    const bool ten = method == LFI_METHOD_TEN_WM, planar_out = c->out_layout == LFI_LAYOUT_PLANAR_RGB;
-    const int n_chunks = (a.v1 - a.v0 + lfi::VF_VIEWS - 1) / lfi::VF_VIEWS;
-    const int tiles_x = (c->width + lfi::VF_TILE_W - 1) / lfi::VF_TILE_W;
-    const int tiles_y = (c->out_rows + lfi::VF_ROWS - 1) / lfi::VF_ROWS;
-    const size_t blocks = (size_t)n_chunks * tiles_x * tiles_y;
-    if(blocks >= (1ull << 31))
-        return fail(c, LFI_EINVAL, "per-view float offsets: too many views x pixels for one launch - render the views in ranges");
-    static const char *const names[2] = {"blend_vfocus_af<STD>", "blend_vfocus_af<TEN_WM>"};
-    note_kernel(c, names[ten]);
-#define LFI_VFA_LAUNCH(T, O)                                                                                                                     \
-    hipLaunchKernelGGL((lfi::blend_vfocus_af<T, O>), dim3((unsigned)blocks), dim3(256), 0, stream_of(c), a, c->d_view_float_offsets, c->vfo_pitch, \
-                       n_chunks, tiles_x)
-    switch((ten ? 2 : 0) | (planar_out ? 1 : 0))
+    else
     {
-        case 0: LFI_VFA_LAUNCH(false, false); break;
-        case 1: LFI_VFA_LAUNCH(false, true); break;
-        case 2: LFI_VFA_LAUNCH(true, false); break;
-        default: LFI_VFA_LAUNCH(true, true); break;
+        using lfi::blend_vfocus_af;
+        static const decltype(&blend_vfocus_af<false, false>) kernels[2][2] = {{blend_vfocus_af<false, false>, blend_vfocus_af<false, true>},
+                                                                                {blend_vfocus_af<true, false>, blend_vfocus_af<true, true>}};
+        hipLaunchKernelGGL(kernels[ten][planar_out], dim3((unsigned)blocks), dim3(256), 0, stream_of(c), a, c->view_float_offsets.dev,
+                           c->view_float_offsets.pitch, n_chunks, tiles_x);
     }
-#undef LFI_VFA_LAUNCH
     LFI_HIP(c, hipGetLastError());
     return LFI_OK;
 }

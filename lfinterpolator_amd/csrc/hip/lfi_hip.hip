@@ -79,9 +79,8 @@ int lfi_destroy(lfi_ctx *ctx)
         (void)hipStreamSynchronize(ctx->aux_stream); // a focus-map filter may still run there
     ctx->filter_pending = false;
     free_params(ctx);
-    free_param_staging(ctx);
-    free_view_offsets(ctx);
-    free_view_float_offsets(ctx);
+    ctx->param_ring.release();
+    free_view_rows(ctx);
     free_views(ctx);
     free_grid(ctx);
     if(ctx->ev0)
@@ -105,6 +104,8 @@ int lfi_destroy(lfi_ctx *ctx)
             (void)hipEventDestroy(ctx->ev_rendered[i]);
         if(ctx->ev_d2h[i])
             (void)hipEventDestroy(ctx->ev_d2h[i]);
+        if(ctx->ev_half_done[i])
+            (void)hipEventDestroy(ctx->ev_half_done[i]);
     }
     if(ctx->quality_sums)
         (void)hipFree(ctx->quality_sums);
@@ -168,8 +169,7 @@ int lfi_set_grid(lfi_ctx *ctx, int cols, int rows, int width, int height)
         return rc;
     LFI_HIP(ctx, hipStreamSynchronize(ctx->stream));
     free_params(ctx);
-    free_view_offsets(ctx);
-    free_view_float_offsets(ctx);
+    free_view_rows(ctx);
     free_views(ctx);
     free_grid(ctx);
     ctx->cols = cols;
@@ -538,8 +538,7 @@ int lfi_set_params(lfi_ctx *ctx, const lfi_params *p)
             if(lo < ctx->in_y0 || hi >= ctx->in_y0 + ctx->in_rows)
                 return fail(ctx, LFI_EINVAL, "the input row window does not cover the rows image " + std::to_string(g) + " is sampled at");
         }
-    ctx->view_offsets_set = false; // per-view offsets belong to the parameters they were set for
-    ctx->view_float_offsets_set = false;
+    ctx->view_offsets.set = ctx->view_float_offsets.set = false; // per-view rows belong to the parameters they were set for
     const int n = ctx->n, V = p->views;
     const int k_pad = (n + 15) / 16 * 16;
     // 64 spare rows: a view range may start anywhere, and a wave always reads whole 32-row tiles
@@ -563,20 +562,10 @@ int lfi_set_params(lfi_ctx *ctx, const lfi_params *p)
     uint8_t *blob_ptr = nullptr;
     if(in_place)
     {
-        if(ctx->param_staging_bytes != total)
-        {
-            free_param_staging(ctx);
-            for(int i = 0; i < 2; i++)
-            {
-                LFI_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->param_staging[i]), total, hipHostMallocDefault));
-                LFI_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_param[i], hipEventDisableTiming));
+        for(int i = 0; i < 2; i++)
+            if(!ctx->ev_half_done[i])
                 LFI_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_half_done[i], hipEventDisableTiming));
-            }
-            ctx->param_staging_bytes = total;
-        }
-        else
-            LFI_HIP(ctx, hipEventSynchronize(ctx->ev_param[ctx->param_slot])); // the copy out of this buffer, two calls ago, has run
-        blob_ptr = ctx->param_staging[ctx->param_slot];
+        LFI_HIP(ctx, ctx->param_ring.acquire(total, &blob_ptr));
         std::memset(blob_ptr, 0, total);
     }
     else
@@ -620,9 +609,8 @@ int lfi_set_params(lfi_ctx *ctx, const lfi_params *p)
             LFI_HIP(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->ev_half_done[next], 0));
         LFI_HIP(ctx, hipMemcpyAsync(static_cast<uint8_t *>(ctx->param_blob) + (size_t)next * ctx->param_half_stride, blob.data(), total, hipMemcpyHostToDevice,
                                     ctx->copy_stream));
-        LFI_HIP(ctx, hipEventRecord(ctx->ev_param[ctx->param_slot], ctx->copy_stream));
-        LFI_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_param[ctx->param_slot], 0));
-        ctx->param_slot ^= 1;
+        LFI_HIP(ctx, ctx->param_ring.commit(ctx->copy_stream));
+        LFI_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->param_ring.committed(), 0));
         ctx->param_half = next;
     }
     else
@@ -692,7 +680,7 @@ int lfi_set_view_offsets(lfi_ctx *ctx, const lfi_int2 *focused_offsets_vn, int v
         return fail(ctx, LFI_EINVAL, "lfi_set_params has not been called");
     if(!focused_offsets_vn)
     {
-        ctx->view_offsets_set = false;
+        ctx->view_offsets.set = false;
         return LFI_OK;
     }
     if(views != ctx->views_n)
@@ -719,54 +707,14 @@ int lfi_set_view_offsets(lfi_ctx *ctx, const lfi_int2 *focused_offsets_vn, int v
                     return fail(ctx, LFI_EINVAL, "the input row window does not cover the rows image " + std::to_string(g) + " is sampled at in view " +
                                                      std::to_string(v));
             }
-    // [N][v_pad], views contiguous (one scalar run per image and chunk of views), zero padding views
-    const int pitch = ctx->v_pad;
-    const size_t bytes = sizeof(lfi_int2) * (size_t)n * pitch;
-    if(bytes > ctx->view_offsets_bytes)
-    {
-        LFI_HIP(ctx, hipStreamSynchronize(ctx->stream)); // renders in flight may read the old buffer
-        free_view_offsets(ctx);
-        LFI_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->d_view_offsets), bytes));
-        ctx->view_offsets_bytes = bytes;
-    }
-    // stream order, as lfi_set_params: the copy runs behind the renders already enqueued, out of one of two page-locked buffers
-    if(ctx->vo_staging_bytes < bytes)
-    {
-        for(int i = 0; i < 2; i++)
-        {
-            if(ctx->ev_vo[i])
-                LFI_HIP(ctx, hipEventSynchronize(ctx->ev_vo[i]));
-            if(ctx->vo_staging[i])
-                (void)hipHostFree(ctx->vo_staging[i]);
-            ctx->vo_staging[i] = nullptr;
-        }
-        ctx->vo_staging_bytes = 0;
-        for(int i = 0; i < 2; i++)
-        {
-            LFI_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->vo_staging[i]), bytes, hipHostMallocDefault));
-            if(!ctx->ev_vo[i])
-                LFI_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_vo[i], hipEventDisableTiming));
-        }
-        ctx->vo_staging_bytes = bytes;
-    }
-    else
-        LFI_HIP(ctx, hipEventSynchronize(ctx->ev_vo[ctx->vo_slot])); // the copy out of this buffer, two calls ago, has run
-    lfi_int2 *staged = ctx->vo_staging[ctx->vo_slot];
-    std::memset(staged, 0, bytes);
     int reach = 0;
-    for(int v = 0; v < views; v++)
-        for(int g = 0; g < n; g++)
-        {
-            const lfi_int2 d = at(v, g);
-            staged[(size_t)g * pitch + v] = d;
-            reach = std::max(reach, std::abs(d.x));
-        }
-    LFI_HIP(ctx, hipMemcpyAsync(ctx->d_view_offsets, staged, bytes, hipMemcpyHostToDevice, ctx->stream));
-    LFI_HIP(ctx, hipEventRecord(ctx->ev_vo[ctx->vo_slot], ctx->stream));
-    ctx->vo_slot ^= 1;
-    ctx->vo_pitch = pitch;
-    ctx->vo_reach = reach;
-    ctx->view_offsets_set = true;
+    if(int rc = stage_view_rows(ctx, ctx->view_offsets, [&](int v, int g) {
+           const lfi_int2 d = at(v, g);
+           reach = std::max(reach, std::abs(d.x));
+           return d;
+       }))
+        return rc;
+    ctx->view_offsets_reach = reach;
     return LFI_OK;
 }
 
@@ -778,7 +726,7 @@ int lfi_set_view_float_offsets(lfi_ctx *ctx, const lfi_float2 *offsets_vn, int v
         return fail(ctx, LFI_EINVAL, "lfi_set_params has not been called");
     if(!offsets_vn)
     {
-        ctx->view_float_offsets_set = false;
+        ctx->view_float_offsets.set = false;
         return LFI_OK;
     }
     if(views != ctx->views_n)
@@ -790,52 +738,9 @@ int lfi_set_view_float_offsets(lfi_ctx *ctx, const lfi_float2 *offsets_vn, int v
             return fail(ctx, LFI_EINVAL, "lfi_set_view_float_offsets: offsets must be finite");
     if(int rc = bind(ctx))
         return rc;
-    // [N][v_pad], views contiguous (one scalar run per image and chunk of views), zero padding views
-    const int pitch = ctx->v_pad;
-    const size_t bytes = sizeof(lfi_float2) * (size_t)n * pitch;
-    if(bytes > ctx->view_float_offsets_bytes)
-    {
-        LFI_HIP(ctx, hipStreamSynchronize(ctx->stream)); // renders in flight may read the old buffer
-        if(ctx->d_view_float_offsets)
-            (void)hipFree(ctx->d_view_float_offsets);
-        ctx->d_view_float_offsets = nullptr;
-        ctx->view_float_offsets_bytes = 0;
-        LFI_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->d_view_float_offsets), bytes));
-        ctx->view_float_offsets_bytes = bytes;
-    }
-    // stream order, as lfi_set_view_offsets: the copy runs behind the renders already enqueued, out of one of two page-locked buffers
-    if(ctx->vfo_staging_bytes < bytes)
-    {
-        for(int i = 0; i < 2; i++)
-        {
-            if(ctx->ev_vfo[i])
-                LFI_HIP(ctx, hipEventSynchronize(ctx->ev_vfo[i]));
-            if(ctx->vfo_staging[i])
-                (void)hipHostFree(ctx->vfo_staging[i]);
-            ctx->vfo_staging[i] = nullptr;
-        }
-        ctx->vfo_staging_bytes = 0;
-        for(int i = 0; i < 2; i++)
-        {
-            LFI_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->vfo_staging[i]), bytes, hipHostMallocDefault));
-            if(!ctx->ev_vfo[i])
-                LFI_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_vfo[i], hipEventDisableTiming));
-        }
-        ctx->vfo_staging_bytes = bytes;
-    }
-    else
-        LFI_HIP(ctx, hipEventSynchronize(ctx->ev_vfo[ctx->vfo_slot])); // the copy out of this buffer, two calls ago, has run
-    lfi_float2 *staged = ctx->vfo_staging[ctx->vfo_slot];
-    std::memset(staged, 0, bytes);
-    for(int v = 0; v < views; v++)
-        for(int g = 0; g < n; g++)
-            staged[(size_t)g * pitch + v] = offsets_vn[(size_t)v * n + g];
-    LFI_HIP(ctx, hipMemcpyAsync(ctx->d_view_float_offsets, staged, bytes, hipMemcpyHostToDevice, ctx->stream));
-    LFI_HIP(ctx, hipEventRecord(ctx->ev_vfo[ctx->vfo_slot], ctx->stream));
-    ctx->vfo_slot ^= 1;
-    ctx->vfo_pitch = pitch;
+    if(int rc = stage_view_rows(ctx, ctx->view_float_offsets, [&](int v, int g) { return offsets_vn[(size_t)v * n + g]; }))
+        return rc;
     ctx->h_view_float_offsets.assign(offsets_vn, offsets_vn + (size_t)views * n);
-    ctx->view_float_offsets_set = true;
     return LFI_OK;
 }
 
@@ -1030,14 +935,15 @@ int lfi_prepare(lfi_ctx *ctx, int method, int all_focus, int v0, int v1)
         return rc;
     const KernelArgs a = make_args(ctx, v0, v1, method);
     ctx->derived_build_ms = 0.0f;
-    if(all_focus && ctx->view_float_offsets_set) // per-view float offsets: the RGBA planes are read as they are, nothing to build
-        return vfocus_af_check(ctx, a);
-    if(ctx->view_offsets_set) // per-view focus: the copy padded for the per-view shifts, as launch_vfocus makes it
+    const ViewRowsKind rows = view_rows_of(ctx, all_focus);
+    bool planar = false;
+    if(rows == VIEW_ROWS_FLOAT) // the RGBA planes are read as they are, nothing to build
+        return view_rows_ready(ctx, rows, all_focus, a, &planar);
+    if(rows == VIEW_ROWS_INT) // the copy padded for the per-view shifts, as launch_view_rows makes it
     {
         const uint64_t before = ctx->planar_version;
-        bool planar = false;
         LFI_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-        if(int rc = vfocus_source(ctx, all_focus, a, &planar))
+        if(int rc = view_rows_ready(ctx, rows, all_focus, a, &planar))
             return rc;
         LFI_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
         LFI_HIP(ctx, hipEventSynchronize(ctx->ev1));
@@ -1105,11 +1011,8 @@ int lfi_render_stream(lfi_ctx *ctx, int method, int all_focus, const uint16_t *w
 {
     if(int rc = check_render_args(ctx, method, 0, 1))
         return rc;
-    if(ctx->view_offsets_set)
-        return fail(ctx, LFI_EINVAL, "per-view offsets are set (lfi_set_view_offsets): lfi_render_stream is not supported - clear them with NULL");
-    if(all_focus && ctx->view_float_offsets_set)
-        return fail(ctx, LFI_EINVAL, "per-view float offsets are set (lfi_set_view_float_offsets): all-focus lfi_render_stream is not supported - "
-                                     "clear them with NULL");
+    if(const ViewRowsKind rows = view_rows_of(ctx, all_focus))
+        return fail(ctx, LFI_EINVAL, view_rows_set(rows) + "lfi_render_stream is not supported - clear them with NULL");
     if(!weights_fp16 || total_views < 1)
         return fail(ctx, LFI_EINVAL, "lfi_render_stream: weights are NULL or total_views < 1");
     if(host_out && (ctx->out_layout != LFI_LAYOUT_RGBA || pitch_bytes < (size_t)ctx->width * 4))
@@ -1301,15 +1204,10 @@ int lfi_benchmark(lfi_ctx *ctx, int method, int all_focus, int v0, int v1, int w
         return rc;
     const KernelArgs a = make_args(ctx, v0, v1, method);
     // the derived input copy is (re)built here, not inside the first timed launch
-    if(all_focus && ctx->view_float_offsets_set)
+    bool planar = false;
+    if(const ViewRowsKind rows = view_rows_of(ctx, all_focus))
     {
-        if(int rc = vfocus_af_check(ctx, a))
-            return rc;
-    }
-    else if(ctx->view_offsets_set)
-    {
-        bool planar = false;
-        if(int rc = vfocus_source(ctx, all_focus, a, &planar))
+        if(int rc = view_rows_ready(ctx, rows, all_focus, a, &planar))
             return rc;
     }
     else if(wants_derived_copy(ctx, method, all_focus, a))

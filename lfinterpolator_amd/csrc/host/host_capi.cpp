@@ -7,6 +7,21 @@
 
 #include "params.h"
 
+namespace {
+
+// the error convention of the entry points below: the message into err (truncated to err_len − 1 bytes), -1
+int report(const std::exception &e, char *err, size_t err_len)
+{
+    if(err && err_len)
+    {
+        std::strncpy(err, e.what(), err_len - 1);
+        err[err_len - 1] = 0;
+    }
+    return -1;
+}
+
+} // namespace
+
 extern "C" {
 
 // Fills the caller's arrays: focused[N], offsets[N], weights[views*N], ids[32]; returns 0 or -1 (message in err).
@@ -29,12 +44,7 @@ int lfi_host_build_params(int cols, int rows, int width, int height, const char 
     }
     catch(const std::exception &e)
     {
-        if(err && err_len)
-        {
-            std::strncpy(err, e.what(), err_len - 1);
-            err[err_len - 1] = 0;
-        }
-        return -1;
+        return report(e, err, err_len);
     }
 }
 
@@ -63,12 +73,7 @@ int lfi_host_build_view_offsets(int cols, int rows, int width, int height, const
     }
     catch(const std::exception &e)
     {
-        if(err && err_len)
-        {
-            std::strncpy(err, e.what(), err_len - 1);
-            err[err_len - 1] = 0;
-        }
-        return -1;
+        return report(e, err, err_len);
     }
 }
 
@@ -93,12 +98,7 @@ int lfi_host_build_view_centred_offsets(int cols, int rows, int width, int heigh
     }
     catch(const std::exception &e)
     {
-        if(err && err_len)
-        {
-            std::strncpy(err, e.what(), err_len - 1);
-            err[err_len - 1] = 0;
-        }
-        return -1;
+        return report(e, err, err_len);
     }
 }
 
@@ -134,12 +134,7 @@ int lfi_host_load_image(const char *path, int *width, int *height, uint8_t *rgba
     }
     catch(const std::exception &e)
     {
-        if(err && err_len)
-        {
-            std::strncpy(err, e.what(), err_len - 1);
-            err[err_len - 1] = 0;
-        }
-        return -1;
+        return report(e, err, err_len);
     }
 }
 
@@ -152,12 +147,7 @@ int lfi_host_write_png(const char *path, int width, int height, int channels, co
     }
     catch(const std::exception &e)
     {
-        if(err && err_len)
-        {
-            std::strncpy(err, e.what(), err_len - 1);
-            err[err_len - 1] = 0;
-        }
-        return -1;
+        return report(e, err, err_len);
     }
 }
 
@@ -182,12 +172,7 @@ int lfi_host_load_grid(const char *path, int *cols, int *rows, int *width, int *
     }
     catch(const std::exception &e)
     {
-        if(err && err_len)
-        {
-            std::strncpy(err, e.what(), err_len - 1);
-            err[err_len - 1] = 0;
-        }
-        return -1;
+        return report(e, err, err_len);
     }
 }
 

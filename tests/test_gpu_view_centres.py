@@ -6,17 +6,16 @@ its float offsets, over the map the context reads, is therefore the exact answer
 contract (≤ 1 LSB from the fp16-accumulator model M16, < 1e-3 of the bytes off the exactly-summed model).  Every render goes through
 tests/poison.py."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import poison
 from conftest import SEED
+from view_rows import TEN_TOL_LSB, check_views, run_cli
 
 pytestmark = pytest.mark.gpu
 
-TEN_TOL_LSB = 1
 KERNEL = {"STD": "blend_vfocus_af<STD>", "TEN_WM": "blend_vfocus_af<TEN_WM>"}
 
 
@@ -38,18 +37,6 @@ def _want(oc, lf, O, hp, method, maps, unified=False, v0=0, v1=None, focused=Non
             out.append((oc.blend_ten(lf, foc, O[v], hp.weights[v:v + 1], model=oc.TEN_M16, **kw)[0],
                         oc.blend_ten(lf, foc, O[v], hp.weights[v:v + 1], model=oc.TEN_EXACT, **kw)[0]))
     return out
-
-
-def _check(got, want, method):
-    if method == "STD":
-        for v, w in enumerate(want):
-            assert (got[v] == w).all(), ("STD view", v, int((got[v] != w).sum()))
-    else:
-        m16 = np.stack([w[0] for w in want])
-        exact = np.stack([w[1] for w in want])
-        assert np.abs(got.astype(int) - m16.astype(int)).max() <= TEN_TOL_LSB
-        assert (got != exact).mean() < 1e-3
-        assert (got[..., 3] == 255).all()
 
 
 def _random_maps(H, W, seed):
@@ -110,7 +97,7 @@ def test_all_focus_per_view_matches_the_oracle(gpu, oracle_c, case, method, layo
     ctx.set_view_float_offsets(O)
     poison.render(ctx, method, all_focus=True)
     assert ctx.last_kernel_name() == KERNEL[method]
-    _check(ctx.download_views(), _want(oracle_c, lf, O, hp, method, maps, unified), method)
+    check_views(ctx.download_views(), _want(oracle_c, lf, O, hp, method, maps, unified), method)
     ctx.close()
 
 
@@ -134,7 +121,7 @@ def test_rows_equal_to_the_offsets_give_the_ordinary_render(gpu, oracle_c, metho
         assert (got == plain).all()
     else:
         assert np.abs(got.astype(int) - plain.astype(int)).max() <= TEN_TOL_LSB
-        _check(got, _want(oracle_c, lf, O, hp, method, maps), method)
+        check_views(got, _want(oracle_c, lf, O, hp, method, maps), method)
     ctx.set_params(hp)  # clears the float offsets: the ordinary kernel is back
     poison.render(ctx, method, all_focus=True)
     assert ctx.last_kernel_name() == plain_kernel
@@ -171,7 +158,7 @@ def test_fixed_focus_rows_and_both_kinds_at_once(gpu, oracle_c, method):
             assert np.abs(fixed[v].astype(int) - want.astype(int)).max() <= TEN_TOL_LSB, v
     poison.render(ctx, method, all_focus=True)  # all-focus: the float rows
     assert ctx.last_kernel_name() == KERNEL[method]
-    _check(ctx.download_views(), _want(oracle_c, lf, O, hp, method, maps), method)
+    check_views(ctx.download_views(), _want(oracle_c, lf, O, hp, method, maps), method)
     ctx.close()
 
 
@@ -187,7 +174,7 @@ def test_sub_ranges_match_the_full_render(gpu, oracle_c, layout):
         poison.render(ctx, method, all_focus=True)
         full = ctx.download_views()
         lf = oracle_c.synthetic_lf(cols * rows, W, H, SEED)
-        _check(full, _want(oracle_c, lf, O, hp, method, maps), method)
+        check_views(full, _want(oracle_c, lf, O, hp, method, maps), method)
         for v0, v1 in [(0, 1), (3, 12), (7, 8), (13, 21), (1, 20)]:
             got = poison.render_range(ctx, method, v0, v1, all_focus=True)
             assert (got == full[v0:v1]).all(), (method, v0, v1)
@@ -211,8 +198,8 @@ def test_new_offsets_do_not_reach_renders_already_enqueued(gpu, oracle_c):
     ctx.sync()
     got = ctx.download_views()
     lf = oracle_c.synthetic_lf(cols * rows, W, H, SEED)
-    _check(got[:4], _want(oracle_c, lf, O1, hp, "STD", maps, v0=0, v1=4), "STD")
-    _check(got[4:], _want(oracle_c, lf, O2, hp, "STD", maps, v0=4, v1=8), "STD")
+    check_views(got[:4], _want(oracle_c, lf, O1, hp, "STD", maps, v0=0, v1=4), "STD")
+    check_views(got[4:], _want(oracle_c, lf, O2, hp, "STD", maps, v0=4, v1=8), "STD")
     ctx.close()
 
 
@@ -237,7 +224,7 @@ def test_row_bands_assemble_the_full_render(gpu, oracle_c, method):
         poison.render(ctx, method, all_focus=True)
         out[:, band[0]:band[1]] = ctx.download_views()[:, band[0]:band[1]]
         ctx.close()
-    _check(out, _want(oracle_c, lf, O, hp, method, maps), method)
+    check_views(out, _want(oracle_c, lf, O, hp, method, maps), method)
 
 
 def test_row_window_shortfall_is_refused(gpu):
@@ -272,7 +259,7 @@ def test_shifts_beyond_the_image_clamp(gpu, oracle_c, method):
     maps = _maps(ctx, "random", H, W)
     ctx.set_view_float_offsets(O)
     poison.render(ctx, method, all_focus=True)
-    _check(ctx.download_views(), _want(oracle_c, lf, O, hp, method, maps), method)
+    check_views(ctx.download_views(), _want(oracle_c, lf, O, hp, method, maps), method)
     ctx.close()
 
 
@@ -289,7 +276,7 @@ def test_benchmark_prepare_quilt_and_compare(gpu, oracle_c):
     ctx.poison(poison.RENDER, poison.POISON[1])
     st = ctx.benchmark("STD", all_focus=True, warmup=1, runs=3)
     assert st.runs == 3 and st.mean_ms > 0 and ctx.last_kernel_name() == KERNEL["STD"]
-    _check(ctx.download_views(), want, "STD")
+    check_views(ctx.download_views(), want, "STD")
     quilt = ctx.download_quilt(3, 2)
     for t in range(6):
         ty, tx = divmod(t, 3)
@@ -342,16 +329,12 @@ def test_errors(gpu):
     ctx.close()
 
 
-def _cli(native, *args):
-    return subprocess.run([native.build.CLI, *args], capture_output=True, text=True, timeout=300)
-
-
 @pytest.mark.parametrize("method", ["STD", "TEN_WM"])
 def test_cli_view_centred_all_focus(gpu, oracle_c, tmp_path, method):
     from PIL import Image
     cols, rows, W, H, V, traj, f, r = 4, 4, 48, 20, 6, "0,0,1,1", 0.1, 0.3
     dst = tmp_path / "out"
-    res = _cli(gpu, "--synthetic", f"{cols},{rows},{W},{H}", "-t", traj, "-f", str(f), "-r", str(r), "-c", "-n", str(V), "-m", method,
+    res = run_cli(gpu, "--synthetic", f"{cols},{rows},{W},{H}", "-t", traj, "-f", str(f), "-r", str(r), "-c", "-n", str(V), "-m", method,
                "-b", "2", "-o", str(dst))
     assert res.returncode == 0, res.stderr
     assert sorted(os.listdir(dst)) == [f"{i:02d}.png" for i in range(V)] + ["map0.png", "map1.png"]
@@ -362,7 +345,7 @@ def test_cli_view_centred_all_focus(gpu, oracle_c, tmp_path, method):
     map1 = oracle_c.focus_filter(map0, hp.block_radius)
     assert (np.array(Image.open(dst / "map0.png")) == map0).all()
     got = np.stack([np.array(Image.open(dst / f"{v:02d}.png")) for v in range(V)])
-    _check(got, _want(oracle_c, lf, O, hp, method, [map0, map1]), method)
+    check_views(got, _want(oracle_c, lf, O, hp, method, [map0, map1]), method)
     # without -c: the centre's offsets, which differ for the outer views
     plain = oracle_c.blend_std(lf, hp.focused_offsets, hp.offsets, hp.weights[:1], all_focus=True, map_plane=map1, focus=f, rng=r)[0]
     assert method != "STD" or not (got[0] == plain).all()
@@ -373,7 +356,7 @@ def test_cli_view_centred_focus_ramp(gpu, oracle_c, tmp_path, method):
     from PIL import Image
     cols, rows, W, H, V, traj = 4, 4, 48, 20, 8, "0,0,1,1"
     dst = tmp_path / "out"
-    res = _cli(gpu, "--synthetic", f"{cols},{rows},{W},{H}", "-t", traj, "-c", "-f", "0.1", "-F", "0.7", "-n", str(V), "-m", method, "-b", "2",
+    res = run_cli(gpu, "--synthetic", f"{cols},{rows},{W},{H}", "-t", traj, "-c", "-f", "0.1", "-F", "0.7", "-n", str(V), "-m", method, "-b", "2",
                "-o", str(dst))
     assert res.returncode == 0, res.stderr
     hp = gpu.build_params(cols, rows, W, H, traj, 0.1, 0.0, 3.0, 1.0, V)
@@ -389,5 +372,5 @@ def test_cli_view_centred_focus_ramp(gpu, oracle_c, tmp_path, method):
 
 
 def test_cli_view_centred_with_range_and_focus_end_fails(gpu, tmp_path):
-    res = _cli(gpu, "--synthetic", "3,3,32,8", "-t", "0,0,1,1", "-c", "-f", "0.1", "-F", "0.5", "-r", "0.2", "-m", "STD", "-o", str(tmp_path / "o"))
+    res = run_cli(gpu, "--synthetic", "3,3,32,8", "-t", "0,0,1,1", "-c", "-f", "0.1", "-F", "0.5", "-r", "0.2", "-m", "STD", "-o", str(tmp_path / "o"))
     assert res.returncode != 0 and "-F" in res.stderr and "-r" in res.stderr

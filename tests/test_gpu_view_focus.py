@@ -4,17 +4,15 @@ View v of a fixed-focus render samples image g at pixel + D[v][g]; the oracle's 
 focused offsets is therefore the exact answer for view v: STD byte for byte, TEN_WM within the TEN_WM contract (≤ 1 LSB from the
 fp16-accumulator model M16, < 1e-3 of the bytes off the exactly-summed model).  Every render goes through tests/poison.py."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import poison
 from conftest import SEED
+from view_rows import check_views, run_cli
 
 pytestmark = pytest.mark.gpu
-
-TEN_TOL_LSB = 1
 
 
 def _want(oc, lf, D, hp, method, v0=0, v1=None, weights=None):
@@ -29,18 +27,6 @@ def _want(oc, lf, D, hp, method, v0=0, v1=None, weights=None):
             out.append((oc.blend_ten(lf, D[v], hp.offsets, w[v:v + 1], model=oc.TEN_M16)[0],
                         oc.blend_ten(lf, D[v], hp.offsets, w[v:v + 1], model=oc.TEN_EXACT)[0]))
     return out
-
-
-def _check(got, want, method):
-    if method == "STD":
-        for v, w in enumerate(want):
-            assert (got[v] == w).all(), ("STD view", v, int((got[v] != w).sum()))
-    else:
-        m16 = np.stack([w[0] for w in want])
-        exact = np.stack([w[1] for w in want])
-        assert np.abs(got.astype(int) - m16.astype(int)).max() <= TEN_TOL_LSB
-        assert (got != exact).mean() < 1e-3
-        assert (got[..., 3] == 255).all()
 
 
 def _ctx(gpu, cols, rows, W, H, hp, D=None, layout="rgba", seed=SEED, flags=0):
@@ -77,7 +63,7 @@ def test_focal_stacks_and_focus_pulls(gpu, oracle_c, case, method, layout):
     ctx = _ctx(gpu, cols, rows, W, H, hp, D, layout)
     poison.render(ctx, method)
     assert ctx.last_kernel_name() == f"blend_vfocus<{method}>"
-    _check(ctx.download_views(), _want(oracle_c, lf, D, hp, method), method)
+    check_views(ctx.download_views(), _want(oracle_c, lf, D, hp, method), method)
     ctx.close()
 
 
@@ -95,7 +81,7 @@ def test_offsets_beyond_the_image_clamp(gpu, oracle_c, method):
     want_D = D.copy()
     want_D[..., 0] = np.clip(want_D[..., 0], -W, W)
     want_D[..., 1] = np.clip(want_D[..., 1], -H, H)
-    _check(ctx.download_views(), _want(oracle_c, lf, want_D, hp, method), method)
+    check_views(ctx.download_views(), _want(oracle_c, lf, want_D, hp, method), method)
     ctx.close()
 
 
@@ -110,7 +96,7 @@ def test_weights_outside_0_2(gpu, oracle_c):
     lf = oracle_c.synthetic_lf(cols * rows, W, H, SEED)
     ctx = _ctx(gpu, cols, rows, W, H, hp, D)
     poison.render(ctx, "STD")
-    _check(ctx.download_views(), _want(oracle_c, lf, D, hp, "STD"), "STD")
+    check_views(ctx.download_views(), _want(oracle_c, lf, D, hp, "STD"), "STD")
     # TEN_WM: one fp16 rounding of the fp32 sum, truncated — within one LSB of the exactly-summed model (M16 re-rounds per batch of 16
     # images, which for sums above 256 is not the contract of any fp32-accumulating kernel here)
     poison.render(ctx, "TEN_WM")
@@ -132,11 +118,11 @@ def test_rgba_source_through_grid_device_ptr(gpu, oracle_c, method):
     poison.render(ctx, method)
     assert ctx.last_kernel_name() == f"blend_vfocus<{method},rgba_src>"
     want = _want(oracle_c, lf, D, hp, method)
-    _check(ctx.download_views(), want, method)
+    check_views(ctx.download_views(), want, method)
     ctx.grid_modified()
     poison.render(ctx, method)
     assert ctx.last_kernel_name() == f"blend_vfocus<{method}>"
-    _check(ctx.download_views(), want, method)
+    check_views(ctx.download_views(), want, method)
     ctx.close()
 
 
@@ -150,7 +136,7 @@ def test_sub_ranges_match_the_full_render(gpu, oracle_c, layout):
     poison.render(ctx, "STD")
     full = ctx.download_views()
     lf = oracle_c.synthetic_lf(cols * rows, W, H, SEED)
-    _check(full, _want(oracle_c, lf, D, hp, "STD"), "STD")
+    check_views(full, _want(oracle_c, lf, D, hp, "STD"), "STD")
     for v0, v1 in [(0, 1), (3, 12), (7, 8), (13, 21), (1, 20)]:
         got = poison.render_range(ctx, "STD", v0, v1)
         assert (got == full[v0:v1]).all(), (v0, v1)
@@ -170,8 +156,8 @@ def test_new_offsets_do_not_reach_renders_already_enqueued(gpu, oracle_c):
     ctx.sync()
     got = ctx.download_views()
     lf = oracle_c.synthetic_lf(cols * rows, W, H, SEED)
-    _check(got[:4], _want(oracle_c, lf, D1, hp, "STD", 0, 4), "STD")
-    _check(got[4:], _want(oracle_c, lf, D2, hp, "STD", 4, 8), "STD")
+    check_views(got[:4], _want(oracle_c, lf, D1, hp, "STD", 0, 4), "STD")
+    check_views(got[4:], _want(oracle_c, lf, D2, hp, "STD", 4, 8), "STD")
     ctx.close()
 
 
@@ -211,7 +197,7 @@ def test_benchmark_prepare_quilt_and_compare(gpu, oracle_c):
     ctx.poison(poison.RENDER, poison.POISON[1])
     st = ctx.benchmark("STD", warmup=1, runs=3)
     assert st.runs == 3 and st.mean_ms > 0 and ctx.last_kernel_name() == "blend_vfocus<STD>"
-    _check(ctx.download_views(), want, "STD")
+    check_views(ctx.download_views(), want, "STD")
     quilt = ctx.download_quilt(3, 2)
     for t in range(6):
         ty, tx = divmod(t, 3)
@@ -287,7 +273,7 @@ def test_row_bands_assemble_the_full_render(gpu, oracle_c, method):
         poison.render(ctx, method)
         out[:, band[0]:band[1]] = ctx.download_views()[:, band[0]:band[1]]
         ctx.close()
-    _check(out, _want(oracle_c, lf, D, hp, method), method)
+    check_views(out, _want(oracle_c, lf, D, hp, method), method)
 
 
 def test_released_inputs(gpu, oracle_c):
@@ -301,16 +287,12 @@ def test_released_inputs(gpu, oracle_c):
     ctx.set_view_offsets(D)  # covered: every |shift| within focus 0.5's
     poison.render(ctx, "STD")
     assert ctx.last_kernel_name() == "blend_vfocus<STD>"
-    _check(ctx.download_views(), _want(oracle_c, lf, D, hp, "STD"), "STD")
+    check_views(ctx.download_views(), _want(oracle_c, lf, D, hp, "STD"), "STD")
     far = gpu.build_view_offsets(cols, rows, W, H, traj, 1.0, gpu.focus_ramp(0.0, 3.0, V))
     ctx.set_view_offsets(far)  # shifts of focus 3: beyond the copy's padding, and the RGBA planes are gone
     with pytest.raises(gpu.LfiError, match="released"):
         ctx.render("STD")
     ctx.close()
-
-
-def _cli(native, *args):
-    return subprocess.run([native.build.CLI, *args], capture_output=True, text=True, timeout=300)
 
 
 @pytest.mark.parametrize("method", ["STD", "TEN_WM"])
@@ -319,7 +301,7 @@ def test_cli_focal_stack(gpu, oracle_c, tmp_path, method):
     cols, rows, W, H, V = 4, 4, 48, 20, 12
     traj = "0.5,0.5,0.5,0.5"
     dst = tmp_path / "out"
-    res = _cli(gpu, "--synthetic", f"{cols},{rows},{W},{H}", "-t", traj, "-f", "0", "-F", "0.6", "-n", str(V), "-m", method, "-b", "2",
+    res = run_cli(gpu, "--synthetic", f"{cols},{rows},{W},{H}", "-t", traj, "-f", "0", "-F", "0.6", "-n", str(V), "-m", method, "-b", "2",
                "-o", str(dst))
     assert res.returncode == 0, res.stderr
     assert sorted(os.listdir(dst)) == [f"{i:02d}.png" for i in range(V)]
@@ -327,9 +309,9 @@ def test_cli_focal_stack(gpu, oracle_c, tmp_path, method):
     D = gpu.build_view_offsets(cols, rows, W, H, traj, 1.0, gpu.focus_ramp(0.0, 0.6, V))
     lf = oracle_c.synthetic_lf(cols * rows, W, H, SEED)
     got = np.stack([np.array(Image.open(dst / f"{v:02d}.png")) for v in range(V)])
-    _check(got, _want(oracle_c, lf, D, hp, method), method)
+    check_views(got, _want(oracle_c, lf, D, hp, method), method)
 
 
 def test_cli_focus_end_with_range_fails(gpu, tmp_path):
-    res = _cli(gpu, "--synthetic", "3,3,32,8", "-t", "0,0,1,1", "-f", "0.1", "-F", "0.5", "-r", "0.2", "-m", "STD", "-o", str(tmp_path / "o"))
+    res = run_cli(gpu, "--synthetic", "3,3,32,8", "-t", "0,0,1,1", "-f", "0.1", "-F", "0.5", "-r", "0.2", "-m", "STD", "-o", str(tmp_path / "o"))
     assert res.returncode != 0 and "-F" in res.stderr and "-r" in res.stderr
