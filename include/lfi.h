@@ -231,8 +231,28 @@ int lfi_set_view_offsets(lfi_ctx *ctx, const lfi_int2 *focused_offsets_vn, int v
  *    NOT use the matrix cores.  Each view reads the same focus map as the ordinary render (map 1 for STD, map 0 for TEN_WM unless
  *    LFI_FLAG_UNIFIED_FOCUS_MAP), at its own pixel.  Downloads, quilts, lfi_compare_view, both view layouts and attached views work
  *    unchanged.  All-focus lfi_render_stream, all-focus lfi_download_prequant and LFI_FLAG_TEN_ROUND_PER_BATCH return LFI_EINVAL.
- * lfi_focus_map is unchanged: it estimates the map at the trajectory's centre from lfi_params.offsets and focus_map_ids. */
+ * lfi_focus_map is unchanged: it estimates the map at the trajectory's centre from lfi_params.offsets and focus_map_ids.  Each view can have
+ * a focus map of its own, estimated at its own camera: lfi_view_focus_maps.  New rows (or NULL) clear those maps. */
 int lfi_set_view_float_offsets(lfi_ctx *ctx, const lfi_float2 *offsets_vn, int views);
+/* Per-view focus maps: every view of a view-centred all-focus render (lfi_set_view_float_offsets) reads a map estimated at its own camera —
+ * what the reference's scripts/focusMapCompare.sh gets from a second run per camera (-t POS,POS,POS,POS -f … -r …).  focus_ids_vk is
+ * [views][n_ids] (host memory, copied before the call returns): row v = the images view v's map samples, FocusMap's selection for the
+ * trajectory collapsed onto camera v (lfi_host_build_view_focus_ids).  View v's map 0 = FocusMap::estimate with offsets_vn[v], ids row v and
+ * lfi_params' focus, range and block radius; its map 1 = FocusMap::filter of it.  The estimate is a min / max over the SET of ids: the order
+ * of a row changes no byte.
+ *  - call after lfi_set_view_float_offsets; views must equal lfi_params.views, 1 <= n_ids <= LFI_MAX_FOCUS_IDS, every id in [0, N) and
+ *    range > 0 (else LFI_EINVAL); LFI_EINVAL too with a row window and after lfi_release_inputs;
+ *  - enqueues maps 0 and 1 of every view on the context's stream, no host synchronisation: the factored estimate of lfi_focus_map view by
+ *    view ("factored_direct" if lfi_set_variant chose it; the other estimate variants do not apply), then one filter launch for all views.  The padded copies
+ *    of the sampled images are shared by the batch: an image that stays among the sampled ones keeps its copy, only the others are padded;
+ *  - the maps live in device memory of their own, [views][2][H][W] RGBA (allocated on first use, counted in lfi_memory.maps_bytes, freed with
+ *    the context); lfi_focus_map and maps 0 / 1 are unaffected;
+ *  - from a successful call until the float rows are cleared (lfi_set_params, lfi_set_grid, lfi_set_row_window, lfi_set_view_float_offsets
+ *    with NULL or new rows), all-focus lfi_render, lfi_prepare and lfi_benchmark read view v's own map (map 1 for STD, map 0 for TEN_WM, map 1
+ *    for both with LFI_FLAG_UNIFIED_FOCUS_MAP) at view v's pixel (blend_vfocus_af's view_maps variant: lfi_last_kernel_name names it).
+ *    Uploads do not clear them.  The refusals of the float rows stay (all-focus lfi_render_stream and lfi_download_prequant,
+ *    LFI_FLAG_TEN_ROUND_PER_BATCH). */
+int lfi_view_focus_maps(lfi_ctx *ctx, const int32_t *focus_ids_vk, int views, int n_ids);
 /* Device layout of the rendered views.  LFI_LAYOUT_RGBA (default): [V][rows][W] RGBA8 dwords — the linear image of the
  * reference's 64 output surfaces.  LFI_LAYOUT_PLANAR_RGB (opt-in): alpha-free byte planes [V][3: R,G,B][rows][pitch] — the alpha
  * the reference's kernels write is the constant 255 (uchar4{…, 255}, src/kernels.cu:393, :309), a quarter of the bytes a render
@@ -286,7 +306,7 @@ typedef struct lfi_memory {
     size_t grid_bytes;      /* input planes (RGBA) */
     size_t derived_bytes;   /* planar copy of the inputs: 3 bytes per pixel and image (+ padding) */
     size_t views_bytes;     /* output planes */
-    size_t maps_bytes;      /* focus maps */
+    size_t maps_bytes;      /* focus maps (maps 0 / 1, and the per-view maps when allocated) */
     size_t workspace_bytes; /* focus-map workspace + (planar view layout) the RGBA scratch copy of the views that renders other than TEN_WM and
                              * STD on more than 64 images go through, and the one-plane staging buffer of downloads */
     float derived_build_ms;
@@ -333,6 +353,10 @@ int lfi_download_quilt(lfi_ctx *ctx, int tiles_x, int tiles_y, int v0, uint8_t *
  * planar view layout is expanded on the fly) and copied in at most three rectangles; lfi_download_quilt is this with every tile. */
 int lfi_download_quilt_tiles(lfi_ctx *ctx, int tiles_x, int tiles_y, int first_tile, int n, int v0, uint8_t *rgba, size_t pitch_bytes);
 int lfi_upload_map(lfi_ctx *ctx, int k, const uint8_t *rgba, size_t pitch_bytes); /* tests: inject a focus map */
+/* view v's map k (0 or 1) of the per-view maps (lfi_view_focus_maps).  Synchronous.  The upload is a test hook like lfi_upload_map (it
+ * allocates the per-view maps if needed and does not put them in use: renders read them after a successful lfi_view_focus_maps). */
+int lfi_download_view_map(lfi_ctx *ctx, int v, int k, uint8_t *rgba, size_t pitch_bytes);
+int lfi_upload_view_map(lfi_ctx *ctx, int v, int k, const uint8_t *rgba, size_t pitch_bytes);
 
 /* PSNR / SSIM of rendered view v against a reference image on the host, reduced on the device — replaces
  * scripts/imageQualityMetrics.sh:1-12 (ffmpeg psnr / ssim on two PNGs).  Definitions (csrc/hip/quality.hpp): PSNR per colour
@@ -389,8 +413,10 @@ int lfi_debug_mfma_f16_chain(lfi_ctx *ctx, int shape, int k, const uint16_t *a_3
  *                    quilt buffer and lfi_render_stream's second set of views
  *   MAPS             both focus maps
  *   FOCUS_WORKSPACE  all of the focus-map estimate's workspace
- *   DERIVED          the planar copy of the inputs — refused (LFI_EINVAL) after lfi_release_inputs: it is then the only copy */
-enum { LFI_POISON_VIEWS = 1, LFI_POISON_SCRATCH = 2, LFI_POISON_MAPS = 4, LFI_POISON_FOCUS_WORKSPACE = 8, LFI_POISON_DERIVED = 16 };
+ *   DERIVED          the planar copy of the inputs — refused (LFI_EINVAL) after lfi_release_inputs: it is then the only copy
+ *   VIEW_MAPS        the per-view focus maps of lfi_view_focus_maps, every view's pair */
+enum { LFI_POISON_VIEWS = 1, LFI_POISON_SCRATCH = 2, LFI_POISON_MAPS = 4, LFI_POISON_FOCUS_WORKSPACE = 8, LFI_POISON_DERIVED = 16,
+       LFI_POISON_VIEW_MAPS = 32 };
 int lfi_debug_poison(lfi_ctx *ctx, uint32_t what, uint8_t byte);
 
 #ifdef __cplusplus

@@ -23,6 +23,7 @@ LFI_POISON_SCRATCH = 2
 LFI_POISON_MAPS = 4
 LFI_POISON_FOCUS_WORKSPACE = 8
 LFI_POISON_DERIVED = 16
+LFI_POISON_VIEW_MAPS = 32
 METHODS = {"STD": LFI_METHOD_STD, "TEN_WM": LFI_METHOD_TEN_WM, "FOCUS": LFI_KERNEL_FOCUS_ESTIMATE}
 
 # every symbol include/lfi.h declares
@@ -33,7 +34,8 @@ ABI_SYMBOLS = [
     "lfi_timer_stop", "lfi_sync", "lfi_download_view", "lfi_download_map", "lfi_download_quilt", "lfi_download_quilt_tiles", "lfi_release_inputs", "lfi_alloc_pinned", "lfi_free_pinned", "lfi_upload_map", "lfi_set_stream",
     "lfi_set_variant", "lfi_list_variants", "lfi_download_coords", "lfi_download_prequant", "lfi_debug_mfma_f16",
     "lfi_grid_modified", "lfi_prepare", "lfi_memory_info", "lfi_last_kernel_name", "lfi_fill_synthetic_images", "lfi_set_output_layout", "lfi_view_layout", "lfi_fill_synthetic_scene", "lfi_upload_image_async", "lfi_upload_wait", "lfi_render_stream", "lfi_compare_view", "lfi_debug_mfma_f16_chain", "lfi_debug_pk_minmax3_f16", "lfi_std_band_info",
-    "lfi_debug_poison", "lfi_set_view_offsets", "lfi_set_view_float_offsets",
+    "lfi_debug_poison", "lfi_set_view_offsets", "lfi_set_view_float_offsets", "lfi_view_focus_maps", "lfi_download_view_map",
+    "lfi_upload_view_map",
 ]
 
 
@@ -113,6 +115,9 @@ def load_hip_library() -> C.CDLL:
         "lfi_set_params": (i, [vp, C.POINTER(_Params)]),
         "lfi_set_view_offsets": (i, [vp, vp, i]),
         "lfi_set_view_float_offsets": (i, [vp, vp, i]),
+        "lfi_view_focus_maps": (i, [vp, vp, i, i]),
+        "lfi_download_view_map": (i, [vp, i, i, vp, sz]),
+        "lfi_upload_view_map": (i, [vp, i, i, vp, sz]),
         "lfi_attach_views": (i, [vp, vp, sz]),
         "lfi_views_device_ptr": (i, [vp, C.POINTER(vp), C.POINTER(sz)]),
         "lfi_focus_map": (i, [vp]),
@@ -339,6 +344,13 @@ class Context:
     def focus_map(self) -> None:
         self._check(self._lib.lfi_focus_map(self._h))
 
+    def view_focus_maps(self, ids_vk: np.ndarray) -> None:
+        """Per-view focus maps (lfi_view_focus_maps): ids_vk is [views][n_ids] int32 — row v = the images view v's map samples
+        (lfinterpolator_amd.build_view_focus_ids computes them); needs the float rows of set_view_float_offsets."""
+        ids = np.ascontiguousarray(ids_vk, dtype=np.int32)
+        assert ids.ndim == 2, ids.shape
+        self._check(self._lib.lfi_view_focus_maps(self._h, _ptr(ids), ids.shape[0], ids.shape[1]))
+
     def render(self, method, all_focus: bool = False, v0: int = 0, v1: int | None = None) -> None:
         m = METHODS[method] if isinstance(method, str) else method
         self._check(self._lib.lfi_render(self._h, m, int(all_focus), v0, self.views if v1 is None else v1))
@@ -455,6 +467,16 @@ class Context:
         rgba = np.ascontiguousarray(rgba, dtype=np.uint8)
         assert rgba.shape == (self.height, self.width, 4)
         self._check(self._lib.lfi_upload_map(self._h, k, _ptr(rgba), self.width * 4))
+
+    def download_view_map(self, v: int, k: int) -> np.ndarray:
+        out = np.empty((self.height, self.width, 4), dtype=np.uint8)
+        self._check(self._lib.lfi_download_view_map(self._h, v, k, _ptr(out), self.width * 4))
+        return out
+
+    def upload_view_map(self, v: int, k: int, rgba: np.ndarray) -> None:
+        rgba = np.ascontiguousarray(rgba, dtype=np.uint8)
+        assert rgba.shape == (self.height, self.width, 4)
+        self._check(self._lib.lfi_upload_view_map(self._h, v, k, _ptr(rgba), self.width * 4))
 
     def download_coords(self, g: int, all_focus: bool = False, map_index: int = 1) -> np.ndarray:
         out = np.empty((self.height, self.width, 2), dtype=np.int32)

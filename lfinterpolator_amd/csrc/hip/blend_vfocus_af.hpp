@@ -5,9 +5,11 @@
 // (int)fma(f(x,y), O[v][g], x): the sample depends on the view, the image and the pixel's focus, so neither a shared pixel operand (no MFMA
 // formulation) nor a shared sample across views exists.  A vector-pipe gather-blend, on the skeleton of blend_vfocus.hpp:
 //
-//   workgroup   4 waves, one output row each, 256 pixels per wave (4 consecutive pixels per lane), VF_VIEWS views
+//   workgroup   4 waves, one output row each, 256 pixels per wave (4 consecutive pixels per lane), VIEWS views (VF_VIEWS)
 //   focus       each lane decodes its 4 pixels' focus once, before the image loop (loadFocusFromMap, src/kernels.cu:134-137): the map the
-//               method reads (map 1 for STD, map 0 for TEN_WM, map 1 for both with LFI_FLAG_UNIFIED_FOCUS_MAP), at the view's own pixel
+//               method reads (map 1 for STD, map 0 for TEN_WM, map 1 for both with LFI_FLAG_UNIFIED_FOCUS_MAP), at the view's own pixel.
+//               VIEW_MAPS (lfi_view_focus_maps): each view of the chunk has its own map pair, f[VIEWS][4] decoded once before the loop
+//               (+(VIEWS − 1)·4 VGPRs; the chunk size of that variant is chosen so that it does not spill: DESIGN.md §4.8)
 //   loop        g outermost (ascending: the chain order of the reference's STD kernel, src/kernels.cu:328-338), the chunk's views inner;
 //               O[v][g] and the weight are wave-uniform scalar loads ([g][view] layouts: one run of VF_VIEWS float2 / floats per g)
 //   sources     the RGBA planes only, one dword gather per (view, image, pixel) with clamp-to-edge (surf2Dread's cudaBoundaryModeClamp,
@@ -25,12 +27,15 @@
 
 namespace lfi {
 
+// views per workgroup of the per-view-map variant (VIEW_MAPS): its focus of VM_VIEWS views stays in registers beside the accumulators
+constexpr int VM_VIEWS = 8;
+
 // grid: n_chunks × tiles_x × ceil(out_rows / VF_ROWS) blocks of 256 threads.
 // vo: [n_images][vo_pitch] float offsets of views [0, vo_pitch), views contiguous; w32t: a.w32t ([k_pad][v_pad]).  Both are zero for the
 // padding views, so a chunk that runs past a.v1 reads defined values; it stores views < a.v1 only.
 // rows: the dispatcher has checked that every row the band samples is held (row windows); the clamp below only keeps a stray index inside
 // the planes.
-template <bool TEN, bool PLANAR_OUT>
+template <bool TEN, bool PLANAR_OUT, int VIEWS = VF_VIEWS, bool VIEW_MAPS = false>
 __global__ void __launch_bounds__(256) blend_vfocus_af(const KernelArgs a, const lfi_float2 *__restrict__ vo, const int vo_pitch, const int n_chunks,
                                                        const int tiles_x)
 {
@@ -43,18 +48,26 @@ __global__ void __launch_bounds__(256) blend_vfocus_af(const KernelArgs a, const
     const int W = a.width, H = a.height;
     const int y = a.out_y0 + yl;
     const int x0 = tx * VF_TILE_W + lane * VF_PX;
-    const int vbase = a.v0 + chunk * VF_VIEWS;
+    const int vbase = a.v0 + chunk * VIEWS;
 
-    // maps are whole-image planes; decode_focus clamps the pixels past the right edge (their results are not stored)
-    const uint8_t *map_plane = a.maps + (size_t)a.map_index * (size_t)W * H * 4;
-    float f[VF_PX];
+    // maps are whole-image planes; decode_focus clamps the pixels past the right edge (their results are not stored).
+    // VIEW_MAPS: a.maps is [views][2][H][W] (lfi_view_focus_maps) and every view of the chunk decodes its own pair's map; the padding views
+    // past a.v1 (not stored) read the last view's, so no read leaves the views' maps
+    constexpr int NF = VIEW_MAPS ? VIEWS : 1;
+    float f[NF][VF_PX];
 #pragma unroll
-    for(int i = 0; i < VF_PX; i++)
-        f[i] = decode_focus(map_plane, W, H, x0 + i, y, a.focus, a.range);
+    for(int j = 0; j < NF; j++)
+    {
+        const size_t pair = VIEW_MAPS ? (size_t)min(vbase + j, a.v1 - 1) * 2 : 0;
+        const uint8_t *map_plane = a.maps + (pair + (size_t)a.map_index) * (size_t)W * H * 4;
+#pragma unroll
+        for(int i = 0; i < VF_PX; i++)
+            f[j][i] = decode_focus(map_plane, W, H, x0 + i, y, a.focus, a.range);
+    }
 
-    float acc[VF_VIEWS][3][VF_PX];
+    float acc[VIEWS][3][VF_PX];
 #pragma unroll
-    for(int j = 0; j < VF_VIEWS; j++)
+    for(int j = 0; j < VIEWS; j++)
 #pragma unroll
         for(int c = 0; c < 3; c++)
 #pragma unroll
@@ -69,7 +82,7 @@ __global__ void __launch_bounds__(256) blend_vfocus_af(const KernelArgs a, const
         const __amdgpu_buffer_rsrc_t plane =
             __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(a.grid) + (size_t)g * plane_bytes, 0, plane_bytes, 0x00020000);
 #pragma unroll
-        for(int j = 0; j < VF_VIEWS; j++)
+        for(int j = 0; j < VIEWS; j++)
         {
             const lfi_float2 oj = o[j];
             const float wj = w[j];
@@ -77,8 +90,9 @@ __global__ void __launch_bounds__(256) blend_vfocus_af(const KernelArgs a, const
 #pragma unroll
             for(int i = 0; i < VF_PX; i++)
             {
-                const int sx = clampi(warp_float(x0 + i, f[i], oj.x), 0, W - 1);
-                const int sy = clampi(clampi(warp_float(y, f[i], oj.y), 0, H - 1) - a.in_y0, 0, a.in_rows - 1);
+                const float fi = f[VIEW_MAPS ? j : 0][i];
+                const int sx = clampi(warp_float(x0 + i, fi, oj.x), 0, W - 1);
+                const int sy = clampi(clampi(warp_float(y, fi, oj.y), 0, H - 1) - a.in_y0, 0, a.in_rows - 1);
                 px[i] = __builtin_amdgcn_raw_buffer_load_b32(plane, (sy * W + sx) * 4, 0, 0);
             }
 #pragma unroll
@@ -93,7 +107,7 @@ __global__ void __launch_bounds__(256) blend_vfocus_af(const KernelArgs a, const
         return;
     const bool full = x0 + VF_PX <= W;
 #pragma unroll
-    for(int j = 0; j < VF_VIEWS; j++)
+    for(int j = 0; j < VIEWS; j++)
     {
         const int v = vbase + j;
         if(v >= a.v1) // wave-uniform

@@ -450,7 +450,8 @@ __global__ void __launch_bounds__(64, 4) focus_estimate_lds(const KernelArgs a)
     }
 }
 
-__global__ void __launch_bounds__(256) focus_filter(const KernelArgs a)
+// maps: the pair [2][H][W] to filter (map 0 → map 1)
+__device__ __forceinline__ void focus_filter_pair(const KernelArgs &a, uint8_t *const maps)
 {
     const int x = blockIdx.x * 64 + (threadIdx.x & 63);
     const int y = a.map_y0 + blockIdx.y * 4 + (threadIdx.x >> 6); // the rows asked for (a row window filters its band)
@@ -458,7 +459,7 @@ __global__ void __launch_bounds__(256) focus_filter(const KernelArgs a)
     if(x >= W || y >= min(H, a.map_y0 + a.map_rows))
         return;
     const int rx = max(a.radius_x / 10, 1), ry = max(a.radius_y / 10, 1); // ≥1: SURVEY.md defect D6
-    const uint32_t *map0 = reinterpret_cast<const uint32_t *>(a.maps);
+    const uint32_t *map0 = reinterpret_cast<const uint32_t *>(maps);
     float avg = 0.0f;
     int count = 0;
     for(int tx = x - rx; tx < x + rx; tx++)
@@ -469,7 +470,12 @@ __global__ void __launch_bounds__(256) focus_filter(const KernelArgs a)
         }
     avg = __fdiv_rn(avg, static_cast<float>(count));
     const uint32_t m = static_cast<uint32_t>(roundf(avg)) & 0xffu;
-    reinterpret_cast<uint32_t *>(a.maps)[(size_t)W * H + (size_t)y * W + x] = m | (m << 8) | (m << 16) | 0xff000000u;
+    reinterpret_cast<uint32_t *>(maps)[(size_t)W * H + (size_t)y * W + x] = m | (m << 8) | (m << 16) | 0xff000000u;
+}
+
+__global__ void __launch_bounds__(256) focus_filter(const KernelArgs a)
+{
+    focus_filter_pair(a, a.maps);
 }
 
 // focus_filter from LDS (round 5).  The box mean sums integers 0…255 — exact in fp32 in any order while the window holds fewer than 65,793 taps —
@@ -482,7 +488,7 @@ __global__ void __launch_bounds__(256) focus_filter(const KernelArgs a)
 constexpr int FF_TW = 64, FF_TH = 32;
 inline size_t focus_filter_tiled_lds(const int rx, const int ry) { return 4u * (size_t(FF_TW + 2 * rx) + FF_TW) * size_t(FF_TH + 2 * ry); }
 
-__global__ void __launch_bounds__(256) focus_filter_tiled(const KernelArgs a)
+__device__ __forceinline__ void focus_filter_tiled_pair(const KernelArgs &a, uint8_t *const maps)
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t ff_lds[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -492,7 +498,7 @@ __global__ void __launch_bounds__(256) focus_filter_tiled(const KernelArgs a)
     const int x0 = blockIdx.x * FF_TW, y0 = a.map_y0 + blockIdx.y * FF_TH;
     const int y_end = min(H, a.map_y0 + a.map_rows);
     uint32_t *const vals = ff_lds, *const hsum = ff_lds + PW * PH;
-    const uint32_t *map0 = reinterpret_cast<const uint32_t *>(a.maps);
+    const uint32_t *map0 = reinterpret_cast<const uint32_t *>(maps);
     // (the staged region is walked linearly by the whole workgroup, twelve elements per thread whose loads are all issued before the first value
     // is stored: one memory latency per tile at the usual radii, not one per row)
     constexpr int STAGE_N = 12;
@@ -535,9 +541,26 @@ __global__ void __launch_bounds__(256) focus_filter_tiled(const KernelArgs a)
     for(int i = 0; i < FF_TH / 4 && y0 + r0 + i < y_end; i++)
     {
         const uint32_t m = static_cast<uint32_t>(roundf(__fdiv_rn(static_cast<float>(s), count))) & 0xffu;
-        reinterpret_cast<uint32_t *>(a.maps)[(size_t)W * H + (size_t)(y0 + r0 + i) * W + x] = m | (m << 8) | (m << 16) | 0xff000000u;
+        reinterpret_cast<uint32_t *>(maps)[(size_t)W * H + (size_t)(y0 + r0 + i) * W + x] = m | (m << 8) | (m << 16) | 0xff000000u;
         s += hsum[(r0 + i + 2 * ry) * FF_TW + lane] - hsum[(r0 + i) * FF_TW + lane];
     }
+}
+
+__global__ void __launch_bounds__(256) focus_filter_tiled(const KernelArgs a)
+{
+    focus_filter_tiled_pair(a, a.maps);
+}
+
+// Both filters over V map pairs in one launch (lfi_view_focus_maps: a.maps is [V][2][H][W]): blockIdx.z is the view.  The arithmetic of
+// the one-pair kernels, pair by pair: the same bytes as V launches of them.
+__global__ void __launch_bounds__(256) focus_filter_views(const KernelArgs a)
+{
+    focus_filter_pair(a, a.maps + (size_t)blockIdx.z * 2 * a.width * a.height * 4);
+}
+
+__global__ void __launch_bounds__(256) focus_filter_tiled_views(const KernelArgs a)
+{
+    focus_filter_tiled_pair(a, a.maps + (size_t)blockIdx.z * 2 * a.width * a.height * 4);
 }
 
 // focusCoords dump for the integer-warp parity test (src/kernels.cu:72-82): unclamped coordinates of image g

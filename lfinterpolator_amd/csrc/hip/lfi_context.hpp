@@ -236,6 +236,16 @@ struct lfi_ctx
     int view_offsets_reach = 0;             // max |D.x| over the integer rows set: the padding the planar copy needs to serve them
     ViewRows<lfi_float2> view_float_offsets;
     std::vector<lfi_float2> h_view_float_offsets;
+    // per-view focus maps (lfi_view_focus_maps): [views][2][H][W] RGBA, each view's pair laid out like maps 0 / 1; allocated on first use,
+    // freed with the context.  view_maps_set: all-focus renders over the float rows read them — cleared with the float rows
+    uint8_t *view_maps = nullptr;
+    size_t view_maps_bytes = 0;
+    bool view_maps_set = false;
+    // the estimate's own copy of the float rows, [V][N], and each view's ids in pad-slot order, [V][n_ids], staged through view_focus_ring
+    void *view_focus_args = nullptr;
+    size_t view_focus_args_bytes = 0;
+    StagingRing view_focus_ring;
+    int view_maps_padded = 0; // planes the last lfi_view_focus_maps padded (focus_pad slots)
     std::string err;
 };
 
@@ -492,14 +502,25 @@ void free_params(lfi_ctx *c)
     c->half_done_recorded[0] = c->half_done_recorded[1] = false;
     c->have_params = false;
     c->view_offsets.set = c->view_float_offsets.set = false;
+    c->view_maps_set = false;
 }
 
-// both sets of per-view rows' buffers; the caller has drained the stream
+// both sets of per-view rows' buffers and the per-view maps; the caller has drained the stream
 void free_view_rows(lfi_ctx *c)
 {
     c->view_offsets.release();
     c->view_float_offsets.release();
     c->h_view_float_offsets.clear();
+    c->view_maps_set = false;
+    if(c->view_maps)
+        (void)hipFree(c->view_maps);
+    c->view_maps = nullptr;
+    c->view_maps_bytes = 0;
+    if(c->view_focus_args)
+        (void)hipFree(c->view_focus_args);
+    c->view_focus_args = nullptr;
+    c->view_focus_args_bytes = 0;
+    c->view_focus_ring.release();
 }
 
 // The shared tail of lfi_set_view_offsets / lfi_set_view_float_offsets: rows at(v, g) of views [0, views_n) to r's device buffer as

@@ -859,16 +859,20 @@ int view_rows_ready(lfi_ctx *c, ViewRowsKind k, int all_focus, const KernelArgs 
     return LFI_OK;
 }
 
-// blend_vfocus (integer rows) or blend_vfocus_af (float rows) over views [a.v0, a.v1)
+// blend_vfocus (integer rows) or blend_vfocus_af (float rows; with per-view maps its view_maps variant) over views [a.v0, a.v1)
 int launch_view_rows(lfi_ctx *c, ViewRowsKind k, int method, int all_focus, const KernelArgs &a_in)
 {
     bool planar = false;
     if(int rc = view_rows_ready(c, k, all_focus, a_in, &planar))
         return rc;
-    if(k == VIEW_ROWS_FLOAT && a_in.map_index == 1)
+    // per-view maps (lfi_view_focus_maps): each view reads its own pair, made on the compute stream
+    const bool view_maps = k == VIEW_ROWS_FLOAT && c->view_maps_set;
+    if(k == VIEW_ROWS_FLOAT && a_in.map_index == 1 && !view_maps)
         if(int rc = join_filter(c)) // the filtered map may still be in the making on the side stream
             return rc;
     KernelArgs a = a_in;
+    if(view_maps)
+        a.maps = c->view_maps;
     if(planar)
     {
         a.planar = c->planar;
@@ -877,16 +881,18 @@ int launch_view_rows(lfi_ctx *c, ViewRowsKind k, int method, int all_focus, cons
         a.planar_phase = c->d_planar_phase;
     }
     const bool ten = method == LFI_METHOD_TEN_WM, planar_out = c->out_layout == LFI_LAYOUT_PLANAR_RGB;
-    const int n_chunks = (a.v1 - a.v0 + lfi::VF_VIEWS - 1) / lfi::VF_VIEWS;
+    const int chunk_views = view_maps ? lfi::VM_VIEWS : lfi::VF_VIEWS;
+    const int n_chunks = (a.v1 - a.v0 + chunk_views - 1) / chunk_views;
     const int tiles_x = (c->width + lfi::VF_TILE_W - 1) / lfi::VF_TILE_W;
     const int tiles_y = (c->out_rows + lfi::VF_ROWS - 1) / lfi::VF_ROWS;
     const size_t blocks = (size_t)n_chunks * tiles_x * tiles_y;
     if(blocks >= (1ull << 31))
         return fail(c, LFI_EINVAL, view_rows_set(k) + "too many views x pixels for one launch - render the views in ranges");
-    static const char *const names[3][2] = {{"blend_vfocus<STD,rgba_src>", "blend_vfocus<TEN_WM,rgba_src>"},
+    static const char *const names[4][2] = {{"blend_vfocus<STD,rgba_src>", "blend_vfocus<TEN_WM,rgba_src>"},
                                             {"blend_vfocus<STD>", "blend_vfocus<TEN_WM>"},
-                                            {"blend_vfocus_af<STD>", "blend_vfocus_af<TEN_WM>"}};
-    note_kernel(c, names[k == VIEW_ROWS_FLOAT ? 2 : planar][ten]);
+                                            {"blend_vfocus_af<STD>", "blend_vfocus_af<TEN_WM>"},
+                                            {"blend_vfocus_af<STD,view_maps>", "blend_vfocus_af<TEN_WM,view_maps>"}};
+    note_kernel(c, names[view_maps ? 3 : k == VIEW_ROWS_FLOAT ? 2 : planar][ten]);
     if(k == VIEW_ROWS_INT)
     {
         using lfi::blend_vfocus;
@@ -899,9 +905,13 @@ int launch_view_rows(lfi_ctx *c, ViewRowsKind k, int method, int all_focus, cons
     else
     {
         using lfi::blend_vfocus_af;
-        static const decltype(&blend_vfocus_af<false, false>) kernels[2][2] = {{blend_vfocus_af<false, false>, blend_vfocus_af<false, true>},
-                                                                                {blend_vfocus_af<true, false>, blend_vfocus_af<true, true>}};
-        hipLaunchKernelGGL(kernels[ten][planar_out], dim3((unsigned)blocks), dim3(256), 0, stream_of(c), a, c->view_float_offsets.dev,
+        using lfi::VF_VIEWS;
+        using lfi::VM_VIEWS;
+        static const decltype(&blend_vfocus_af<false, false>) kernels[2][2][2] = {
+            {{blend_vfocus_af<false, false>, blend_vfocus_af<false, true>}, {blend_vfocus_af<true, false>, blend_vfocus_af<true, true>}},
+            {{blend_vfocus_af<false, false, VM_VIEWS, true>, blend_vfocus_af<false, true, VM_VIEWS, true>},
+             {blend_vfocus_af<true, false, VM_VIEWS, true>, blend_vfocus_af<true, true, VM_VIEWS, true>}}};
+        hipLaunchKernelGGL(kernels[view_maps][ten][planar_out], dim3((unsigned)blocks), dim3(256), 0, stream_of(c), a, c->view_float_offsets.dev,
                            c->view_float_offsets.pitch, n_chunks, tiles_x);
     }
     LFI_HIP(c, hipGetLastError());

@@ -9,35 +9,64 @@
 
 namespace {
 
+// What one factored estimate samples: the host copies of the sampled images' offsets and ids, in pad-slot order (slot k is padded from image
+// ids[k]); the device arrays are the caller's a.offsets / a.focus_ids / a.maps.  The centre map (lfi_focus_map) is ctx->h_focus_offsets /
+// h_focus_ids; a per-view batch (lfi_view_focus_maps) passes each view's, with the padding sized for the whole batch.
+struct FocusJob
+{
+    const lfi_float2 *offsets = nullptr; // [n_ids]: offsets[k] of image ids[k]
+    const int32_t *ids = nullptr;        // [n_ids]
+    int n_ids = 0;
+    int need_shift[2] = {0, 0}; // padding asked for on top of this job's own shifts (a batch's bound over all its views)
+    // slot-stable re-padding: planes of the right geometry are kept slot by slot — only slots whose image differs from pad_ids (or has
+    // changed since) are padded.  Off (the centre map): the planes are kept only when pad_ids equals ids as a whole, else all are re-padded.
+    bool slot_reuse = false;
+    int padded = 0; // out: focus_pad slots enqueued
+};
+
+// largest |shift| any candidate gives any of the n offsets, +1 (candidates are monotone in i, so the ends bound them); false when absurd
+bool focus_pad_shift(const lfi_ctx *ctx, const lfi_float2 *offsets, int n, int *Sx, int *Sy)
+{
+    const float step = ctx->range / 31.0f;
+    const double fmax = std::max(std::fabs((double)ctx->focus), std::fabs((double)std::fmaf(step, 31.0f, ctx->focus)));
+    double ox = 0, oy = 0;
+    for(int k = 0; k < n; k++)
+    {
+        ox = std::max(ox, std::fabs((double)offsets[k].x));
+        oy = std::max(oy, std::fabs((double)offsets[k].y));
+    }
+    if(!(fmax * ox < 1e6 && fmax * oy < 1e6))
+        return false;
+    *Sx = (int)std::ceil(fmax * ox) + 1, *Sy = (int)std::ceil(fmax * oy) + 1; // ≥ |floor(δ)| and ≥ |floor(δ)+1|
+    return true;
+}
+
 // the factored estimate (focus_factored.hpp): carve the workspace, then plan → pad → E → exact keys → pick.
 // Returns LFI_OK with *done = false when the padded planes would be unreasonably large (the caller takes another variant).
 // direct_range: the range pass by focus_range (rounds 1-4's kernel: every use loads and widens its own samples) even where focus_range_t
 // applies (variant "factored_direct": the second implementation in the parity tests, and the A/B partner)
-int launch_focus_factored(lfi_ctx *ctx, const KernelArgs &a, bool *done, bool direct_range)
+int launch_focus_factored(lfi_ctx *ctx, const KernelArgs &a, FocusJob &job, bool *done, bool direct_range)
 {
     *done = false;
+    job.padded = 0;
     const int W = ctx->width, H = ctx->height, rx = ctx->radius[0], ry = ctx->radius[1];
+    const int n_ids = job.n_ids;
     lfi::FocusWork w{};
     w.We_p = (W + 2 * rx + 255) / 256 * 256;
     w.He_p = (H + 2 * ry + 3) / 4 * 4;
-    // largest |shift| any candidate gives any sampled image: candidates are monotone in i, so the ends bound them
     const float step = ctx->range / 31.0f;
-    const double fmax = std::max(std::fabs((double)ctx->focus), std::fabs((double)std::fmaf(step, 31.0f, ctx->focus)));
-    double ox = 0, oy = 0;
-    for(const lfi_float2 &o : ctx->h_focus_offsets)
-    {
-        ox = std::max(ox, std::fabs((double)o.x));
-        oy = std::max(oy, std::fabs((double)o.y));
-    }
-    if(!(fmax * ox < 1e6 && fmax * oy < 1e6))
+    int Sx = 0, Sy = 0;
+    if(!focus_pad_shift(ctx, job.offsets, n_ids, &Sx, &Sy))
         return LFI_OK;
-    int Sx = (int)std::ceil(fmax * ox) + 1, Sy = (int)std::ceil(fmax * oy) + 1; // ≥ |floor(δ)| and ≥ |floor(δ)+1|
+    Sx = std::max(Sx, job.need_shift[0]);
+    Sy = std::max(Sy, job.need_shift[1]);
     // The padded planes of an earlier call serve this one if the inputs have not changed since and their padding covers these shifts
     // (any larger padding gives the same samples): then the geometry is theirs.  New planes are padded to the next multiple of 8, so
     // that the neighbouring steps of a focus sweep find them large enough.
     // (also when only SOME images were replaced since — lfi_upload_image —: then only the planes of the sampled images among them are redone)
+    const bool same_ids = job.slot_reuse ? ctx->pad_ids.size() == (size_t)n_ids : ctx->pad_ids == std::vector<int32_t>(job.ids, job.ids + n_ids);
     const bool pad_kept = ctx->grid_tracked && ctx->focus_ws && ctx->pad_version != 0 && ctx->grid_full_version <= ctx->pad_version &&
-                          ctx->pad_ids == ctx->h_focus_ids && ctx->pad_radius[0] == rx && ctx->pad_radius[1] == ry && ctx->pad_shift[0] >= Sx &&
+                          same_ids && ctx->pad_radius[0] == rx && ctx->pad_radius[1] == ry && ctx->pad_shift[0] >= Sx &&
                           ctx->pad_shift[1] >= Sy;
     // Planes that have to GROW (an ascending sweep) grow by a quarter more than asked for: every change of the geometry rebuilds the planes
     // and may reallocate a workspace of gigabytes (≈ 80 ms per step when it happened on every step of a sweep).
@@ -50,7 +79,7 @@ int launch_focus_factored(lfi_ctx *ctx, const KernelArgs &a, bool *done, bool di
     w.Hp = w.Py + std::max(H + Sy + ry, w.He_p - ry + Sy);
     // (+ FRT_PR + 16 rows of slack behind the last plane: focus_range_t fetches whole patches, also for the rows of its last tiles that
     // lie below the extended image)
-    const size_t pad_bytes = sizeof(uint32_t) * ((size_t)ctx->n_focus_ids * w.Hp + lfi::FRT_PR + 16) * w.Wp;
+    const size_t pad_bytes = sizeof(uint32_t) * ((size_t)n_ids * w.Hp + lfi::FRT_PR + 16) * w.Wp;
     if(pad_bytes > ((size_t)16 << 30))
         return LFI_OK;
     // Can the range pass unpack its samples once into LDS (focus_range_t)?  Within every group of CPW consecutive candidates a view's integer
@@ -61,15 +90,15 @@ int launch_focus_factored(lfi_ctx *ctx, const KernelArgs &a, bool *done, bool di
         for(int cpw : {8, 4})
         {
             bool fits = true;
-            for(size_t k = 0; k < ctx->h_focus_offsets.size() && fits; k++)
+            for(int k = 0; k < n_ids && fits; k++)
                 for(int i0 = 0; i0 < lfi::FOCUS_STEPS && fits; i0 += cpw)
                 {
                     int lo[2] = {INT32_MAX, INT32_MAX}, hi[2] = {INT32_MIN, INT32_MIN};
                     for(int i = i0; i < i0 + cpw; i++)
                     {
                         const float f = std::fmaf(step, static_cast<float>(i), ctx->focus);
-                        const int sx = static_cast<int>(std::floor(static_cast<double>(f) * static_cast<double>(ctx->h_focus_offsets[k].x)));
-                        const int sy = static_cast<int>(std::floor(static_cast<double>(f) * static_cast<double>(ctx->h_focus_offsets[k].y)));
+                        const int sx = static_cast<int>(std::floor(static_cast<double>(f) * static_cast<double>(job.offsets[k].x)));
+                        const int sy = static_cast<int>(std::floor(static_cast<double>(f) * static_cast<double>(job.offsets[k].y)));
                         lo[0] = std::min(lo[0], sx), hi[0] = std::max(hi[0], sx), lo[1] = std::min(lo[1], sy), hi[1] = std::max(hi[1], sy);
                     }
                     fits = hi[0] - lo[0] <= lfi::FRT_MAX_DX && hi[1] - lo[1] <= lfi::FRT_MAX_DY;
@@ -158,23 +187,26 @@ int launch_focus_factored(lfi_ctx *ctx, const KernelArgs &a, bool *done, bool di
     if(pad_kept && ctx->pad_version != 0) // (a reallocated workspace cleared pad_version)
     {
         padded_any = false;
-        for(int k = 0; k < ctx->n_focus_ids; k++)
-            if(image_changed_since(ctx, ctx->h_focus_ids[k], ctx->pad_version))
+        for(int k = 0; k < n_ids; k++)
+            if(ctx->pad_ids[k] != job.ids[k] || image_changed_since(ctx, job.ids[k], ctx->pad_version))
             {
                 hipLaunchKernelGGL(lfi::focus_pad, dim3((w.Wp + 255) / 256, (w.Hp + lfi::FOCUS_PAD_ROWS - 1) / lfi::FOCUS_PAD_ROWS, 1), dim3(64), 0, st, a, w, k);
                 padded_any = true;
+                job.padded++;
             }
         ctx->pad_version = ctx->grid_version;
+        ctx->pad_ids.assign(job.ids, job.ids + n_ids);
     }
     else
     {
-        hipLaunchKernelGGL(lfi::focus_pad, dim3((w.Wp + 255) / 256, (w.Hp + lfi::FOCUS_PAD_ROWS - 1) / lfi::FOCUS_PAD_ROWS, ctx->n_focus_ids), dim3(64), 0, st, a, w, 0);
+        hipLaunchKernelGGL(lfi::focus_pad, dim3((w.Wp + 255) / 256, (w.Hp + lfi::FOCUS_PAD_ROWS - 1) / lfi::FOCUS_PAD_ROWS, n_ids), dim3(64), 0, st, a, w, 0);
+        job.padded = n_ids;
         ctx->pad_version = ctx->grid_tracked ? ctx->grid_version : 0;
         ctx->pad_shift[0] = Sx;
         ctx->pad_shift[1] = Sy;
         ctx->pad_radius[0] = rx;
         ctx->pad_radius[1] = ry;
-        ctx->pad_ids = ctx->h_focus_ids;
+        ctx->pad_ids.assign(job.ids, job.ids + n_ids);
     }
     // (planes kept and nothing re-padded: ev_fork says all the side stream needs to know — one event packet less in front of the range pass)
     if(padded_any)

@@ -539,6 +539,7 @@ int lfi_set_params(lfi_ctx *ctx, const lfi_params *p)
                 return fail(ctx, LFI_EINVAL, "the input row window does not cover the rows image " + std::to_string(g) + " is sampled at");
         }
     ctx->view_offsets.set = ctx->view_float_offsets.set = false; // per-view rows belong to the parameters they were set for
+    ctx->view_maps_set = false;                                   // … and so do the per-view maps
     const int n = ctx->n, V = p->views;
     const int k_pad = (n + 15) / 16 * 16;
     // 64 spare rows: a view range may start anywhere, and a wave always reads whole 32-row tiles
@@ -727,6 +728,7 @@ int lfi_set_view_float_offsets(lfi_ctx *ctx, const lfi_float2 *offsets_vn, int v
     if(!offsets_vn)
     {
         ctx->view_float_offsets.set = false;
+        ctx->view_maps_set = false;
         return LFI_OK;
     }
     if(views != ctx->views_n)
@@ -738,6 +740,7 @@ int lfi_set_view_float_offsets(lfi_ctx *ctx, const lfi_float2 *offsets_vn, int v
             return fail(ctx, LFI_EINVAL, "lfi_set_view_float_offsets: offsets must be finite");
     if(int rc = bind(ctx))
         return rc;
+    ctx->view_maps_set = false; // estimated for the rows these replace
     if(int rc = stage_view_rows(ctx, ctx->view_float_offsets, [&](int v, int g) { return offsets_vn[(size_t)v * n + g]; }))
         return rc;
     ctx->h_view_float_offsets.assign(offsets_vn, offsets_vn + (size_t)views * n);
@@ -821,12 +824,22 @@ int lfi_views_device_ptr(lfi_ctx *ctx, void **out_ptr, size_t *out_bytes)
     return LFI_OK;
 }
 
-// map 1 = the box mean of map 0 over the rows a.map_y0 … + a.map_rows: from LDS (focus_filter_tiled) when the window allows it
-static void launch_focus_filter(lfi_ctx *ctx, const lfi::KernelArgs &a, hipStream_t st)
+// map 1 = the box mean of map 0 over the rows a.map_y0 … + a.map_rows: from LDS (focus_filter_tiled) when the window allows it.
+// views > 0: a.maps holds that many pairs [views][2][H][W] (lfi_view_focus_maps), all filtered by one launch
+static void launch_focus_filter(lfi_ctx *ctx, const lfi::KernelArgs &a, hipStream_t st, int views = 0)
 {
     const int rx = std::max(ctx->radius[0] / 10, 1), ry = std::max(ctx->radius[1] / 10, 1);
     const size_t lds = lfi::focus_filter_tiled_lds(rx, ry);
-    if(rx <= 128 && ry <= 128 && lds <= 64u * 1024u)
+    const bool tiled = rx <= 128 && ry <= 128 && lds <= 64u * 1024u;
+    if(views > 0)
+    {
+        if(tiled)
+            hipLaunchKernelGGL(lfi::focus_filter_tiled_views, dim3((ctx->width + lfi::FF_TW - 1) / lfi::FF_TW, (a.map_rows + lfi::FF_TH - 1) / lfi::FF_TH, views),
+                               dim3(256), lds, st, a);
+        else
+            hipLaunchKernelGGL(lfi::focus_filter_views, dim3((ctx->width + 63) / 64, (a.map_rows + 3) / 4, views), dim3(256), 0, st, a);
+    }
+    else if(tiled)
         hipLaunchKernelGGL(lfi::focus_filter_tiled, dim3((ctx->width + lfi::FF_TW - 1) / lfi::FF_TW, (a.map_rows + lfi::FF_TH - 1) / lfi::FF_TH), dim3(256), lds, st, a);
     else
         hipLaunchKernelGGL(lfi::focus_filter, dim3((ctx->width + 63) / 64, (a.map_rows + 3) / 4), dim3(256), 0, st, a);
@@ -881,8 +894,14 @@ int lfi_focus_map(lfi_ctx *ctx)
     // "factored" (default): W and H must fit the 16-bit column / row lists
     bool done = false;
     if((ctx->focus_variant == 0 || ctx->focus_variant == 4) && ctx->width <= 65535 && ctx->height <= 65535)
-        if(int rc = launch_focus_factored(ctx, a, &done, ctx->focus_variant == 4))
+    {
+        FocusJob job;
+        job.offsets = ctx->h_focus_offsets.data();
+        job.ids = ctx->h_focus_ids.data();
+        job.n_ids = ctx->n_focus_ids;
+        if(int rc = launch_focus_factored(ctx, a, job, &done, ctx->focus_variant == 4))
             return rc;
+    }
     if(done)
         ;
     else if(ctx->focus_variant <= 1 && lds_fits) // "lds"
@@ -912,6 +931,200 @@ int lfi_focus_map(lfi_ctx *ctx)
     }
     launch_focus_filter(ctx, a, ctx->stream);
     LFI_HIP(ctx, hipGetLastError());
+    return LFI_OK;
+}
+
+// the per-view maps [views_n][2][H][W], allocated (or grown) on first use; renders in flight may read the old buffer
+static int ensure_view_maps(lfi_ctx *ctx)
+{
+    const size_t need = plane_bytes(ctx) * 2 * ctx->views_n;
+    if(ctx->view_maps_bytes >= need)
+        return LFI_OK;
+    LFI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->view_maps_set = false;
+    if(ctx->view_maps)
+        (void)hipFree(ctx->view_maps);
+    ctx->view_maps = nullptr;
+    ctx->view_maps_bytes = 0;
+    LFI_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->view_maps), need));
+    ctx->view_maps_bytes = need;
+    return LFI_OK;
+}
+
+// ids (n of them) in pad-slot order after `prev`, the slot layout of the padded planes: an image prev already holds keeps its slot, the
+// others take the remaining slots in ascending order.  The estimate is a min / max over the set, so the order changes no byte.
+static void pad_slot_order(const std::vector<int32_t> &prev, const int32_t *ids, int n, int32_t *out)
+{
+    std::vector<char> placed(n, 0);
+    for(int k = 0; k < n; k++)
+        out[k] = -1;
+    if((int)prev.size() == n)
+        for(int k = 0; k < n; k++)
+            for(int j = 0; j < n; j++)
+                if(!placed[j] && ids[j] == prev[k])
+                {
+                    out[k] = ids[j];
+                    placed[j] = 1;
+                    break;
+                }
+    int k = 0;
+    for(int j = 0; j < n; j++)
+        if(!placed[j])
+        {
+            while(out[k] >= 0)
+                k++;
+            out[k] = ids[j];
+        }
+}
+
+int lfi_view_focus_maps(lfi_ctx *ctx, const int32_t *focus_ids_vk, int views, int n_ids)
+{
+    if(!ctx)
+        return LFI_EINVAL;
+    if(ctx->inputs_released)
+        return fail(ctx, LFI_EINVAL, "the RGBA inputs were released (lfi_release_inputs): the focus maps need them - upload the images again (lfi_set_grid)");
+    if(!ctx->grid || !ctx->have_params)
+        return fail(ctx, LFI_EINVAL, "lfi_set_grid / lfi_set_params have not been called");
+    if(!ctx->view_float_offsets.set)
+        return fail(ctx, LFI_EINVAL, "lfi_view_focus_maps: no per-view float offsets (lfi_set_view_float_offsets)");
+    if(views != ctx->views_n)
+        return fail(ctx, LFI_EINVAL, "lfi_view_focus_maps: views (" + std::to_string(views) + ") differs from lfi_params.views (" +
+                                         std::to_string(ctx->views_n) + ")");
+    if(n_ids < 1 || n_ids > LFI_MAX_FOCUS_IDS || !focus_ids_vk)
+        return fail(ctx, LFI_EINVAL, "lfi_view_focus_maps: n_ids must be in [1, LFI_MAX_FOCUS_IDS] and focus_ids_vk non-NULL");
+    for(size_t i = 0; i < (size_t)views * n_ids; i++)
+        if(focus_ids_vk[i] < 0 || focus_ids_vk[i] >= ctx->n)
+            return fail(ctx, LFI_EINVAL, "lfi_view_focus_maps: id outside the grid in view " + std::to_string(i / n_ids));
+    if(!(ctx->range > 0.0f))
+        return fail(ctx, LFI_EINVAL, "focus range must be > 0 for the focus map");
+    if(ctx->windowed)
+        return fail(ctx, LFI_EINVAL, "lfi_view_focus_maps: per-view focus maps are not supported with a row window");
+    if(ctx->width > 65535 || ctx->height > 65535)
+        return fail(ctx, LFI_EINVAL, "lfi_view_focus_maps: image too large for the factored estimate");
+    if(int rc = bind(ctx))
+        return rc;
+    if(int rc = join_uploads(ctx))
+        return rc;
+    if(int rc = join_filter(ctx)) // the centre map's filter shares the side stream
+        return rc;
+    if(int rc = ensure_view_maps(ctx))
+        return rc;
+    const int n = ctx->n, V = views;
+    // every view's ids in slot order (slots stay with their images from view to view: only the images that change are padded again), the
+    // offsets of its sampled images, and one pad geometry for the whole batch
+    std::vector<int32_t> slots((size_t)V * n_ids);
+    std::vector<lfi_float2> sampled((size_t)V * n_ids);
+    std::vector<int32_t> prev = ctx->pad_ids;
+    int need[2] = {0, 0};
+    for(int v = 0; v < V; v++)
+    {
+        int32_t *row = slots.data() + (size_t)v * n_ids;
+        pad_slot_order(prev, focus_ids_vk + (size_t)v * n_ids, n_ids, row);
+        prev.assign(row, row + n_ids);
+        for(int k = 0; k < n_ids; k++)
+            sampled[(size_t)v * n_ids + k] = ctx->h_view_float_offsets[(size_t)v * n + row[k]];
+        int sx = 0, sy = 0;
+        if(!focus_pad_shift(ctx, sampled.data() + (size_t)v * n_ids, n_ids, &sx, &sy))
+            return fail(ctx, LFI_EINVAL, "lfi_view_focus_maps: the shifts of view " + std::to_string(v) + " are too large");
+        need[0] = std::max(need[0], sx);
+        need[1] = std::max(need[1], sy);
+    }
+    // the estimate's arrays on the device: the float rows as [V][N] (the render's copy is [N][v_pad]) and the slot-ordered ids [V][n_ids]
+    const size_t off_bytes = sizeof(lfi_float2) * (size_t)V * n, ids_at = (off_bytes + 255) / 256 * 256;
+    const size_t total = ids_at + sizeof(int32_t) * (size_t)V * n_ids;
+    if(ctx->view_focus_args_bytes < total)
+    {
+        LFI_HIP(ctx, hipStreamSynchronize(ctx->stream)); // an estimate in flight may read the old buffer
+        if(ctx->view_focus_args)
+            (void)hipFree(ctx->view_focus_args);
+        ctx->view_focus_args = nullptr;
+        ctx->view_focus_args_bytes = 0;
+        LFI_HIP(ctx, hipMalloc(&ctx->view_focus_args, total));
+        ctx->view_focus_args_bytes = total;
+    }
+    uint8_t *staged = nullptr;
+    LFI_HIP(ctx, ctx->view_focus_ring.acquire(total, &staged));
+    std::memcpy(staged, ctx->h_view_float_offsets.data(), off_bytes);
+    std::memcpy(staged + ids_at, slots.data(), sizeof(int32_t) * slots.size());
+    LFI_HIP(ctx, hipMemcpyAsync(ctx->view_focus_args, staged, total, hipMemcpyHostToDevice, ctx->stream));
+    LFI_HIP(ctx, ctx->view_focus_ring.commit(ctx->stream));
+    const lfi_float2 *d_off = static_cast<const lfi_float2 *>(ctx->view_focus_args);
+    const int32_t *d_ids = reinterpret_cast<const int32_t *>(static_cast<const uint8_t *>(ctx->view_focus_args) + ids_at);
+    ctx->view_maps_set = false; // until every view's pair is enqueued
+    KernelArgs a = make_args(ctx, 0, V, LFI_METHOD_STD);
+    a.n_focus_ids = n_ids;
+    int padded = 0;
+    for(int v = 0; v < V; v++)
+    {
+        a.offsets = d_off + (size_t)v * n;
+        a.focus_ids = d_ids + (size_t)v * n_ids;
+        a.maps = ctx->view_maps + plane_bytes(ctx) * 2 * v;
+        FocusJob job;
+        job.offsets = sampled.data() + (size_t)v * n_ids;
+        job.ids = slots.data() + (size_t)v * n_ids;
+        job.n_ids = n_ids;
+        job.need_shift[0] = need[0];
+        job.need_shift[1] = need[1];
+        job.slot_reuse = true;
+        bool done = false;
+        if(int rc = launch_focus_factored(ctx, a, job, &done, ctx->focus_variant == 4))
+            return rc;
+        if(!done)
+            return fail(ctx, LFI_EINVAL, "lfi_view_focus_maps: the padded planes of these shifts would be too large");
+        padded += job.padded;
+    }
+    // maps 1 of all views by one launch, on the compute stream (renders of either map follow in stream order)
+    a.maps = ctx->view_maps;
+    launch_focus_filter(ctx, a, ctx->stream, V);
+    LFI_HIP(ctx, hipGetLastError());
+    ctx->view_maps_padded = padded;
+    ctx->view_maps_set = true;
+    return LFI_OK;
+}
+
+// view v's map k on the device: the per-view maps of the current parameters
+static int view_map_plane(lfi_ctx *ctx, int v, int k, const void *host, size_t pitch_bytes, uint8_t **out)
+{
+    if(!ctx->have_params || !ctx->view_maps || ctx->view_maps_bytes < plane_bytes(ctx) * 2 * ctx->views_n)
+        return fail(ctx, LFI_EINVAL, "no per-view focus maps (lfi_view_focus_maps)");
+    if(v < 0 || v >= ctx->views_n || k < 0 || k > 1 || !host || pitch_bytes < (size_t)ctx->width * 4)
+        return fail(ctx, LFI_EINVAL, "bad view index, map index, pointer or pitch");
+    *out = ctx->view_maps + plane_bytes(ctx) * (2 * (size_t)v + k);
+    return LFI_OK;
+}
+
+int lfi_download_view_map(lfi_ctx *ctx, int v, int k, uint8_t *rgba, size_t pitch_bytes)
+{
+    if(!ctx)
+        return LFI_EINVAL;
+    uint8_t *src = nullptr;
+    if(int rc = view_map_plane(ctx, v, k, rgba, pitch_bytes, &src))
+        return rc;
+    if(int rc = bind(ctx))
+        return rc;
+    LFI_HIP(ctx, hipMemcpy2DAsync(rgba, pitch_bytes, src, (size_t)ctx->width * 4, (size_t)ctx->width * 4, ctx->height, hipMemcpyDeviceToHost,
+                                  ctx->stream));
+    LFI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return LFI_OK;
+}
+
+int lfi_upload_view_map(lfi_ctx *ctx, int v, int k, const uint8_t *rgba, size_t pitch_bytes)
+{
+    if(!ctx)
+        return LFI_EINVAL;
+    if(ctx->have_params)
+    {
+        if(int rc = bind(ctx))
+            return rc;
+        if(int rc = ensure_view_maps(ctx))
+            return rc;
+    }
+    uint8_t *dst = nullptr;
+    if(int rc = view_map_plane(ctx, v, k, rgba, pitch_bytes, &dst))
+        return rc;
+    LFI_HIP(ctx, hipMemcpy2DAsync(dst, (size_t)ctx->width * 4, rgba, pitch_bytes, (size_t)ctx->width * 4, ctx->height, hipMemcpyHostToDevice,
+                                  ctx->stream));
+    LFI_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return LFI_OK;
 }
 
@@ -972,7 +1185,7 @@ int lfi_memory_info(lfi_ctx *ctx, lfi_memory *out)
     out->grid_bytes = ctx->grid ? in_plane_bytes(ctx) * ctx->n : 0;
     out->derived_bytes = ctx->planar ? ctx->planar_bytes : 0;
     out->views_bytes = ctx->views ? ctx->views_bytes : 0;
-    out->maps_bytes = ctx->maps ? plane_bytes(ctx) * 2 : 0;
+    out->maps_bytes = (ctx->maps ? plane_bytes(ctx) * 2 : 0) + ctx->view_maps_bytes;
     out->workspace_bytes = ctx->focus_ws_bytes + ctx->rgba_scratch_bytes + ctx->dl_plane_bytes;
     out->derived_build_ms = ctx->derived_build_ms;
     return LFI_OK;
@@ -1614,7 +1827,7 @@ int lfi_debug_poison(lfi_ctx *ctx, uint32_t what, uint8_t byte)
 {
     if(!ctx)
         return LFI_EINVAL;
-    if(what & ~uint32_t(LFI_POISON_VIEWS | LFI_POISON_SCRATCH | LFI_POISON_MAPS | LFI_POISON_FOCUS_WORKSPACE | LFI_POISON_DERIVED))
+    if(what & ~uint32_t(LFI_POISON_VIEWS | LFI_POISON_SCRATCH | LFI_POISON_MAPS | LFI_POISON_FOCUS_WORKSPACE | LFI_POISON_DERIVED | LFI_POISON_VIEW_MAPS))
         return fail(ctx, LFI_EINVAL, "lfi_debug_poison: unknown LFI_POISON_* bits");
     if((what & LFI_POISON_DERIVED) && ctx->inputs_released)
         return fail(ctx, LFI_EINVAL, "lfi_debug_poison: the planar copy is the only copy of the inputs after lfi_release_inputs");
@@ -1644,6 +1857,8 @@ int lfi_debug_poison(lfi_ctx *ctx, uint32_t what, uint8_t byte)
     }
     if(what & LFI_POISON_MAPS)
         rc = rc ? rc : fill(ctx->maps, ctx->maps ? plane_bytes(ctx) * 2 : 0);
+    if(what & LFI_POISON_VIEW_MAPS)
+        rc = rc ? rc : fill(ctx->view_maps, ctx->view_maps_bytes);
     if(what & LFI_POISON_FOCUS_WORKSPACE)
     {
         rc = rc ? rc : fill(ctx->focus_ws, ctx->focus_ws_bytes);

@@ -102,6 +102,26 @@ int lfi_host_build_view_centred_offsets(int cols, int rows, int width, int heigh
     }
 }
 
+// each view's focus-map images: ids_vk[views][*n_ids] (room for views × 32), row v = the ids lfi_host_build_params selects for the trajectory
+// collapsed onto camera v (the rows lfi_view_focus_maps takes)
+int lfi_host_build_view_focus_ids(int cols, int rows, const char *trajectory, int views, int32_t *ids_vk, int32_t *n_ids, char *err, size_t err_len)
+{
+    try
+    {
+        if(views < 1 || !ids_vk || !n_ids)
+            throw std::runtime_error("views must be positive and the arrays non-NULL");
+        lfi::Parameterizer p({cols, rows}, {1, 1, 4});
+        const std::vector<int32_t> ids = p.viewFocusMapIDs(p.interpretTrajectory(trajectory), views);
+        std::memcpy(ids_vk, ids.data(), sizeof(int32_t) * ids.size());
+        *n_ids = static_cast<int32_t>(ids.size() / views);
+        return 0;
+    }
+    catch(const std::exception &e)
+    {
+        return report(e, err, err_len);
+    }
+}
+
 uint16_t lfi_host_float_to_half(float v)
 {
     return lfi::floatToHalfBits(v);

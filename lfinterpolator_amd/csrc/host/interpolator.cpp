@@ -143,6 +143,8 @@ void Interpolator::interpolate(std::string outputPath, std::string trajectory, f
     if(perViewFocus && allFocus)
         throw std::runtime_error("A focus per view cannot be combined with all-focus rendering (-r)!");
     const size_t n = params.offsets.size();
+    if(viewMaps && !(viewCentred && allFocus))
+        throw std::runtime_error("A focus map per view needs view-centred shifts (-c) and all-focus rendering (-r)!");
     if(viewCentred)
     {
         // every view shifted about its own camera; every GPU gets the rows of its own views
@@ -167,7 +169,17 @@ void Interpolator::interpolate(std::string outputPath, std::string trajectory, f
         for(int g = 0; g < gpuCount; g++)
             check(lfi_set_view_offsets(contexts[g], rowsVn.data() + viewStart[g] * n, viewStart[g + 1] - viewStart[g]), contexts[g]);
     }
-    if(allFocus)
+    if(allFocus && viewMaps)
+    {
+        // every view's map at its own camera; every GPU estimates the maps of its own views
+        std::cout << "Estimating focus maps per view..." << std::endl;
+        const std::vector<int32_t> ids = parameterizer.viewFocusMapIDs(parameterizer.interpretTrajectory(trajectory), viewCount);
+        const int nIds = static_cast<int>(ids.size()) / viewCount;
+        for(int g = 0; g < gpuCount; g++)
+            check(lfi_view_focus_maps(contexts[g], ids.data() + static_cast<size_t>(viewStart[g]) * nIds, viewStart[g + 1] - viewStart[g], nIds),
+                  contexts[g]);
+    }
+    else if(allFocus)
     {
         std::cout << "Estimating focus map..." << std::endl;
         for(lfi_ctx *c : contexts)
@@ -228,7 +240,7 @@ void Interpolator::storeResults(std::string path)
     constexpr int MAP_COUNT{2};
     int count = viewCount;
     if(range > 0)
-        count += MAP_COUNT;
+        count += viewMaps ? MAP_COUNT * viewCount : MAP_COUNT;
     std::filesystem::create_directories(path);
     LoadingBar bar(count);
     const size_t pitch = static_cast<size_t>(resolution.x) * channels;
@@ -259,7 +271,17 @@ void Interpolator::storeResults(std::string path)
         }
         uint8_t *data = ring + imageBytes * slot;
         auto fileName = std::filesystem::path(path) / (std::string(((i < 10) ? "0" : "")) + std::to_string(i) + ".png");
-        if(i >= viewCount)
+        if(i >= viewCount && viewMaps)
+        {
+            // map k of view v: map0_NN.png, map1_NN.png
+            const int v = (i - viewCount) / MAP_COUNT, k = (i - viewCount) % MAP_COUNT;
+            fileName = std::filesystem::path(path) / ("map" + std::to_string(k) + "_" + (v < 10 ? "0" : "") + std::to_string(v) + ".png");
+            int g = 0;
+            while(g + 1 < gpuCount && v >= viewStart[g + 1])
+                g++;
+            check(lfi_download_view_map(contexts[g], v - viewStart[g], k, data, pitch), contexts[g]);
+        }
+        else if(i >= viewCount)
         {
             fileName = std::filesystem::path(path) / ("map" + std::to_string(i - viewCount) + ".png");
             check(lfi_download_map(context, i - viewCount, data, pitch));

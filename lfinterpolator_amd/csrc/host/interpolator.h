@@ -36,6 +36,9 @@ class Interpolator
         // rows through lfi_set_view_offsets for fixed focus (with setFocusEnd: at each view's focus), float rows through
         // lfi_set_view_float_offsets for all-focus renders
         void setViewCentred(bool on) { viewCentred = on; }
+        // with setViewCentred and all-focus rendering: every view's focus map estimated at its own camera (lfi_view_focus_maps) instead of
+        // one at the trajectory's centre; the maps are stored per view (map0_NN.png, map1_NN.png)
+        void setViewMaps(bool on) { viewMaps = on; }
 
         // synthetic cols×rows grid of width×height images instead of a directory
         Interpolator(lfi::IVec2 colsRows, lfi::IVec2 resolution, uint32_t seed, int device = 0);
@@ -51,6 +54,7 @@ class Interpolator
         int gpuCount{1};
         bool perViewFocus{false};
         bool viewCentred{false};
+        bool viewMaps{false};
         float focusEnd{0};
         std::vector<lfi_ctx *> contexts; // one per GPU; contexts[0] == context
         std::vector<int> viewStart;      // first view of each GPU's range (size gpuCount + 1)

@@ -34,6 +34,7 @@ int main(int argc, char **argv)
                           "-r - focusing range (will be added to the focusing value) - will produce all-focused result if used\n"
                           "-F - focusing value at the last view: the focus ramps from -f at the first view to -F at the last (a focus pull; a focal stack with a single-point trajectory such as -t 0.5,0.5,0.5,0.5); not with -r\n"
                           "-c - shift the images about each view's own camera position instead of the trajectory's centre (the default, as the reference does); with -r and with -f/-F\n"
+                          "--view-maps - with -c and -r: estimate every view's focus map at its own camera (the reference's focusMapCompare.sh second run, per view) instead of one map at the trajectory's centre; writes map0_NN.png / map1_NN.png per view\n"
                           "Additional arguments:\n"
                           "-n - number of views rendered along the trajectory (default=64)\n"
                           "-b - number of timed kernel launches (default=100)\n"
@@ -64,6 +65,12 @@ int main(int argc, char **argv)
     if(args["-F"] && args["-r"])
     {
         std::cerr << "-F (a focus per view) cannot be combined with -r (all-focus rendering)." << std::endl;
+        return EXIT_FAILURE;
+    }
+
+    if(args["--view-maps"] && !(args["-c"] && args["-r"]))
+    {
+        std::cerr << "--view-maps (a focus map per view) needs -c (view-centred shifts) and -r (all-focus rendering)." << std::endl;
         return EXIT_FAILURE;
     }
 
@@ -98,6 +105,8 @@ int main(int argc, char **argv)
             interpolator->setUnifiedFocusMap(true);
         if(args["-c"])
             interpolator->setViewCentred(true);
+        if(args["--view-maps"])
+            interpolator->setViewMaps(true);
         if(args["-F"])
             interpolator->setFocusEnd(static_cast<float>(args["-F"]));
         if(args["-q"])

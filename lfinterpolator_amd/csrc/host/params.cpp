@@ -274,6 +274,18 @@ std::vector<int32_t> Parameterizer::selectFocusMapViews(Vec4 startEndPoints) con
     return order;
 }
 
+std::vector<int32_t> Parameterizer::viewFocusMapIDs(Vec4 startEndPoints, int views) const
+{
+    const std::vector<Vec2> cameras = generateTrajectory(startEndPoints, views);
+    std::vector<int32_t> out;
+    for(const Vec2 &cam : cameras)
+    {
+        const std::vector<int32_t> row = selectFocusMapViews(Vec4{cam.x, cam.y, cam.x, cam.y});
+        out.insert(out.end(), row.begin(), row.end());
+    }
+    return out;
+}
+
 // reference src/interpolator.cu:139-146; a zero radius (image narrower than 100 px) never advances the tap loops of the
 // focus-map kernel, so it is raised to 1
 IVec2 Parameterizer::blockRadius() const

@@ -53,6 +53,8 @@ class Parameterizer
         void viewCentredOffsets(float aspect, const std::vector<float> &focus, Vec4 startEndPoints, std::vector<lfi_float2> &offsets,
                                 std::vector<lfi_int2> &focused) const;
         std::vector<int32_t> selectFocusMapViews(Vec4 startEndPoints) const;
+        // each view's focus-map images: row v of [views][min(32, N)] = selectFocusMapViews of the trajectory collapsed onto camera v
+        std::vector<int32_t> viewFocusMapIDs(Vec4 startEndPoints, int views) const;
         IVec2 blockRadius() const;
 
         // everything at once: what Interpolator::interpolate prepares before its launches

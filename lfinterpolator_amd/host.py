@@ -31,6 +31,9 @@ def load_host_library() -> C.CDLL:
         lib.lfi_host_build_view_centred_offsets.restype = C.c_int
         lib.lfi_host_build_view_centred_offsets.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_float, C.c_void_p, C.c_int,
                                                             C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]
+        lib.lfi_host_build_view_focus_ids.restype = C.c_int
+        lib.lfi_host_build_view_focus_ids.argtypes = [C.c_int, C.c_int, C.c_char_p, C.c_int, C.c_void_p, C.POINTER(C.c_int32), C.c_char_p,
+                                                      C.c_size_t]
         lib.lfi_host_float_to_half.restype = C.c_uint16
         lib.lfi_host_float_to_half.argtypes = [C.c_float]
         lib.lfi_host_half_to_float.restype = C.c_float
@@ -109,6 +112,15 @@ def build_view_centred_offsets(cols: int, rows: int, width: int, height: int, tr
     _err_call(load_host_library().lfi_host_build_view_centred_offsets, cols, rows, width, height, trajectory.encode(), aspect, f.ctypes.data,
               len(f), o.ctypes.data, d.ctypes.data)
     return o, d
+
+
+def build_view_focus_ids(cols: int, rows: int, trajectory: str, views: int) -> np.ndarray:
+    """Each view's focus-map images, [V][min(32, N)] int32 for Context.view_focus_maps — row v = the focus_map_ids build_params selects
+    for the trajectory collapsed onto camera v of V."""
+    out = np.zeros(max(views, 1) * 32, dtype=np.int32)
+    n = C.c_int32(0)
+    _err_call(load_host_library().lfi_host_build_view_focus_ids, cols, rows, trajectory.encode(), views, out.ctypes.data, C.byref(n))
+    return out[:views * n.value].reshape(views, n.value).copy()
 
 
 def _err_call(fn, *args):
