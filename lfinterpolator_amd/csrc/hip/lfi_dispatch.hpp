@@ -1,8 +1,14 @@
-// lfi_dispatch.hpp — which kernel serves a render: the variant tables (lfi_set_variant), the launchers of every blend kernel, the
-// derived planar input copy (ensure_planar) and the rules that pick between them (wants_planar, wants_p3, launch_blend).
+// lfi_dispatch.hpp — which kernel serves a render, and how.  route_blend decides each blend launch in one step: the kernel, whether it
+// reads the derived planar copy of the inputs (ensure_planar), and, in the planar view layout, whether it writes the byte planes itself
+// or RGBA into the scratch copy that a conversion pass turns into planes.  In that order: the generic kernels where the others cannot
+// serve (per-batch rounding, weights outside [0, 2), pre-quantisation dumps); the variant's order of preference (lfi_set_variant: its
+// first choice, then the fallbacks below it); the output form, a property of the kernel chosen.  launch_blend makes the copy valid when
+// the route reads it (or routes again without it) and launches; the launchers only compute grids and instantiate kernels.
 // Replaces the method / allFocus dispatch of Interpolator::interpolate (reference src/interpolator.cu:270-290).
 // Included by lfi_hip.hip only (one translation unit), after lfi_context.hpp.
 #pragma once
+
+#include <type_traits>
 
 #include "lfi_context.hpp"
 #include "blend_std.hpp"
@@ -20,255 +26,231 @@
 
 namespace {
 
+// one entry per kernel name that note_kernel reports
+enum class BlendKernel
+{
+    ten_m16,
+    ten_direct,
+    p3,
+    p3_rgba,
+    planar_ten,
+    persist_ten,
+    persist_ten_af,
+    wave_ten,
+    stdx,
+    planar_stdf,
+    stdxa,
+    afs,
+    persist_std,
+    persist_std_af,
+    wave_std,
+    std_mfma,
+    std_valu,
+    std_vfma,
+};
+
+// The generic kernels: plain fp32 epilogue, any weights, pre-quantisation dumps, per-batch rounding (TEN_WM).  They run one pixel grid
+// over the whole image; every other kernel honours a row window.
+bool generic_kernel(BlendKernel k)
+{
+    using K = BlendKernel;
+    return k == K::ten_m16 || k == K::ten_direct || k == K::std_mfma || k == K::std_valu || k == K::std_vfma;
+}
+
+bool kernel_reads_copy(BlendKernel k)
+{
+    using K = BlendKernel;
+    return k == K::p3 || k == K::p3_rgba || k == K::planar_ten || k == K::stdx || k == K::planar_stdf;
+}
+
+// planar view layout: does kernel k write the byte planes itself?  Its planar-view epilogue addresses `planes` byte planes (3 per view)
+// with one 32-bit per-lane offset: blend_p3 / blend_stdx a wave's 16 views, blend_persist's store_tile_planar the 32 views of a pass
+// (all-focus renders only), blend_stdxa the 64 views of a launch
+bool kernel_writes_planar_views(const lfi_ctx *c, BlendKernel k)
+{
+    using K = BlendKernel;
+    const int planes = k == K::p3 || k == K::stdx ? 48 : k == K::persist_ten_af ? 96 : k == K::stdxa ? 192 : 0;
+    return planes && (uint64_t)planes * (uint64_t)c->out_rows * (uint64_t)view_pitch(c) < (1ull << 32);
+}
+
 struct Variant
 {
     const char *name;
-    void (*launch)(const lfi_ctx *, const KernelArgs &, bool all_focus);
-    bool packed_epilogue; // TEN_WM: needs weights in [0,2) (×2^15 copy)
-    bool prequant = false; // can dump pre-quantisation accumulators (the generic kernels only)
-    bool row_window = false; // honours a row window (the persistent kernels)
-    bool planar = false;     // reads the planar copy of the inputs when the launch qualifies (else its launcher falls back)
+    BlendKernel first; // its first choice; route_blend falls back from it where it does not apply
 };
 
-int next_sweep_direction(const lfi_ctx *c);
+// first entry = default ("auto")
+const Variant kTenVariants[] = {
+    {"p3_rgba_nt", BlendKernel::p3_rgba}, // blend_p3 with the RGBA epilogue; blend_planar / blend_persist where it does not apply
+    {"planar_m2_nt", BlendKernel::planar_ten},
+    {"persist_m2_nt", BlendKernel::persist_ten},
+    {"wave_m2_nt", BlendKernel::wave_ten},
+    {"direct_p1m2", BlendKernel::ten_direct}, // generic
+};
+const Variant kStdVariants[] = {
+    {"filtered_m2_nt", BlendKernel::stdx},  // the band method (blend_stdx / blend_planar<STDF>, blend_stdxa all-focus); blend_wave / blend_persist
+    {"filtered_gather_once", BlendKernel::afs}, // the same with blend_afs for all-focus renders of 3–4 chunks
+    {"wave_m2_nt", BlendKernel::wave_std},
+    {"persist_m2_nt", BlendKernel::persist_std},
+    {"mfma_p1m2", BlendKernel::std_mfma}, // generic
+    {"valu", BlendKernel::std_valu},      // the reference-shaped one-pixel-per-thread kernel: exactness anchor
+    {"vfma", BlendKernel::std_vfma},      // the non-tensor wavefront kernel
+};
+const int kNumTenVariants = sizeof(kTenVariants) / sizeof(kTenVariants[0]);
+const int kNumStdVariants = sizeof(kStdVariants) / sizeof(kStdVariants[0]);
 
-template <int PXL, int MT>
-void launch_ten_direct(const lfi_ctx *c, const KernelArgs &a, bool all_focus)
-{
-    const int tiles_x = (a.width + 32 * PXL - 1) / (32 * PXL);
-    const int n_tiles = tiles_x * a.height;
-    const int passes = (a.v1 - a.v0 + 32 * MT - 1) / (32 * MT);
-    const int vpw = passes >= 4 ? 4 : (passes >= 2 ? 2 : 1);
-    const int tiles_per_wg = 4 / vpw;
-    const dim3 grid((n_tiles + tiles_per_wg - 1) / tiles_per_wg), block(256);
-    hipStream_t st = stream_of(c);
-    if(flags_of(c) & LFI_FLAG_TEN_ROUND_PER_BATCH)
-    {
-        // the reference's half-accumulator model (oracle M16), exact: fp64 on the vector pipe, one pixel per lane (blend_ten.hpp)
-        note_kernel(c, "blend_ten_m16");
-        if(all_focus)
-            hipLaunchKernelGGL(lfi::blend_ten_m16<true>, pixel_grid_of(c), dim3(256), 0, st, a);
-        else
-            hipLaunchKernelGGL(lfi::blend_ten_m16<false>, pixel_grid_of(c), dim3(256), 0, st, a);
-        return;
-    }
-    note_kernel(c, "blend_ten_direct");
-    if(all_focus)
-        hipLaunchKernelGGL((lfi::blend_ten_direct<PXL, MT, true>), grid, block, 0, st, a, tiles_x, n_tiles, passes, vpw);
-    else
-        hipLaunchKernelGGL((lfi::blend_ten_direct<PXL, MT, false>), grid, block, 0, st, a, tiles_x, n_tiles, passes, vpw);
-}
-
-template <bool STD, int MT, bool NT_STORE, int KC = 64, int WGS = 2>
-void launch_persist(const lfi_ctx *c, const KernelArgs &a, bool all_focus)
-{
-    constexpr int TPX = 128, VPP = MT * 32;
-    const int tiles_x = (a.width + TPX - 1) / TPX;
-    const int n_tiles = tiles_x * a.out_rows;
-    const int passes = (a.v1 - a.v0 + VPP - 1) / VPP;
-    // persistent: WGS workgroups per CU (2 x 80 KB of LDS at KC = 64), each walks tiles j, j+G, j+2G ...
-    const dim3 grid(std::min(n_tiles, WGS * cu_count_of(c))), block(256);
-    note_kernel(c, STD ? (all_focus ? "blend_persist<STD,allfocus>" : "blend_persist<STD>") : (all_focus ? "blend_persist<TEN_WM,allfocus>" : "blend_persist<TEN_WM>"));
-    if constexpr(!STD && MT == 2 && KC == 64 && WGS == 2)
-        if(all_focus && a.views == c->views && c->out_layout == LFI_LAYOUT_PLANAR_RGB)
-        {
-            // the planar layout's byte planes written by the kernel itself (launch_blend: persist_writes_planar_views)
-            hipLaunchKernelGGL((lfi::blend_persist<false, 2, true, NT_STORE, 64, 2, true>), grid, block, 0, stream_of(c), a, tiles_x, n_tiles, passes);
-            return;
-        }
-    if(all_focus)
-        hipLaunchKernelGGL((lfi::blend_persist<STD, MT, true, NT_STORE, KC, WGS>), grid, block, 0, stream_of(c), a, tiles_x, n_tiles, passes);
-    else
-        hipLaunchKernelGGL((lfi::blend_persist<STD, MT, false, NT_STORE, KC, WGS>), grid, block, 0, stream_of(c), a, tiles_x, n_tiles, passes);
-}
-
-// TEN_WM from the planar copy of the inputs (blend_planar.hpp) when launch_blend has validated it for this launch
-// (a.planar != nullptr: fixed focus), else blend_persist
-template <bool NT_STORE, int RING3 = 1>
-void launch_planar(const lfi_ctx *c, const KernelArgs &a, bool all_focus)
-{
-    if(!a.planar || all_focus)
-    {
-        launch_persist<false, 2, NT_STORE>(c, a, all_focus);
-        return;
-    }
-    const int tiles_x = (a.width + 127) / 128;
-    const int n_tiles = tiles_x * a.out_rows;
-    const int passes = (a.v1 - a.v0 + 63) / 64;
-    const dim3 grid(std::min(n_tiles, 2 * cu_count_of(c))), block(256);
-    note_kernel(c, "blend_planar<TEN_WM>");
-    hipLaunchKernelGGL((lfi::blend_planar<2, NT_STORE>), grid, block, 0, stream_of(c), a, tiles_x, n_tiles, passes, RING3, next_sweep_direction(c));
-}
-
-// RGBA views (the reference's layout, the default) by blend_p3 with its RGBA epilogue (round 4) where it pays — fixed focus, the planar
-// copy of the inputs validated for this launch, TWO TO FOUR chunks of images (15×15 grids: −8 % at configs 3 and 5; with one chunk
-// blend_planar is as fast, and blend_persist faster for several view passes: profiles/r04_rgba_p3_ab.txt), a wave's 16 RGBA planes
-// addressable with 32 bits — else blend_planar / blend_persist.
-void launch_p3(const lfi_ctx *c, const KernelArgs &a_in, bool rgba_out = false);
+// RGBA views by blend_p3 with its RGBA epilogue: a wave's 16 RGBA planes addressable with 32 bits
 bool p3_rgba_planes_fit(const lfi_ctx *c)
 {
     return (uint64_t)16 * (uint64_t)c->out_rows * (uint64_t)c->width * 4u < (1ull << 32);
 }
-void launch_p3_rgba(const lfi_ctx *c, const KernelArgs &a, bool all_focus)
+
+struct BlendRoute
 {
-    if(!a.planar || all_focus || a.k_pad <= lfi::P3_KC || a.k_pad > 4 * lfi::P3_KC || !p3_rgba_planes_fit(c))
-    {
-        launch_planar<true>(c, a, all_focus);
-        return;
-    }
-    launch_p3(c, a, true);
+    BlendKernel kernel;
+    int nch;         // 64-image chunks of the launch (the kernels instantiated per chunk count)
+    bool reads_copy; // reads the derived planar copy of the inputs
+    bool planar_out; // planar view layout: writes the byte planes itself (else RGBA into the scratch copy, converted afterwards)
+};
+
+// The route of a blend launch.  copy_ok = false: the route when the derived copy cannot be made valid.  No side effects, no allocation:
+// it runs on every launch.
+BlendRoute route_blend(const lfi_ctx *c, int method, bool all_focus, const KernelArgs &a, bool copy_ok)
+{
+    using K = BlendKernel;
+    const bool ten = method == LFI_METHOD_TEN_WM, planar_views = c->out_layout == LFI_LAYOUT_PLANAR_RGB;
+    const K first = ten ? kTenVariants[c->ten_variant].first : kStdVariants[c->std_variant].first;
+    const int nch = (a.k_pad + lfi::P3_KC - 1) / lfi::P3_KC;
+    const bool fixed_copy = copy_ok && !all_focus;
+    // wave-private pipelines (blend_wave.hpp) where they apply: fixed focus, one chunk of images, one view pass
+    const bool wave_fits = !all_focus && a.k_pad <= 64 && a.v1 - a.v0 <= 64;
+    const K k = [&] {
+        // 1. the generic kernels serve what the others cannot
+        if(ten && (c->flags & LFI_FLAG_TEN_ROUND_PER_BATCH))
+            return K::ten_m16; // the reference's half-accumulator model (oracle M16), exact: fp64 on the vector pipe (blend_ten.hpp)
+        if(generic_kernel(first))
+            return first;
+        if(a.prequant || (ten && !c->weights_scalable)) // (the packed epilogue of the TEN_WM kernels: weights in [0, 2), the ×2^15 copy)
+            return ten ? K::ten_direct : K::std_mfma;
+        // 2. the variant's order of preference
+        if(ten)
+        {
+            if(first == K::wave_ten && wave_fits)
+                return K::wave_ten;
+            if((first == K::p3_rgba || first == K::planar_ten) && fixed_copy)
+            {
+                // planar views: blend_p3 writes them.  RGBA views: blend_p3 with its RGBA epilogue where it pays — TWO TO FOUR chunks of
+                // images (15×15 grids: −8 % at configs 3 and 5; with one chunk blend_planar is as fast, and blend_persist faster for several
+                // view passes: profiles/r04_rgba_p3_ab.txt)
+                if(planar_views && a.k_pad <= 4 * lfi::P3_KC && kernel_writes_planar_views(c, K::p3))
+                    return K::p3;
+                if(first == K::p3_rgba && a.k_pad > lfi::P3_KC && a.k_pad <= 4 * lfi::P3_KC && p3_rgba_planes_fit(c))
+                    return K::p3_rgba;
+                return K::planar_ten;
+            }
+            return all_focus ? K::persist_ten_af : K::persist_ten;
+        }
+        // STD: the band method (MFMA sum + exact recomputation inside the rounding band) for weights for which its error bounds hold
+        const bool band = c->weights_scalable && c->weights_sum_ok && a.k_pad <= 4 * lfi::P3_KC;
+        if((first == K::stdx || first == K::afs) && band && all_focus)
+            // blend_stdxa, on the per-pixel gather pipeline; "filtered_gather_once": three or four chunks by blend_afs (64-pixel tiles whose
+            // whole stack of samples stays in LDS, every sample gathered once, where blend_stdxa gathers chunks 2 and 3 a second time for the
+            // chain).  Half the fabric traffic, the same bytes — and not faster (4.8 against 4.7 ms at config 5: bound by instruction issue,
+            // profiles/r04_notes.md), so it is a selectable variant and the second implementation in the parity tests, not the default.
+            return first == K::afs && nch >= 3 ? K::afs : K::stdxa;
+        if((first == K::stdx || first == K::afs) && band && fixed_copy)
+            // from the planar copy: blend_stdx for more than one chunk of images (the chain's bytes fetched a second time), and for ONE chunk
+            // where it writes planar views itself — blend_planar<STDF> would go through the scratch copy and the conversion (config 2: 0.45 ms
+            // against 0.23).  With RGBA views blend_planar<STDF> stays: as fast at config 2, 15 % faster for one rank of config 4
+            // (profiles/r04_rgba_p3_ab.txt).
+            return a.k_pad > lfi::P3_KC || (planar_views && kernel_writes_planar_views(c, K::stdx)) ? K::stdx : K::planar_stdf;
+        if(first != K::persist_std && wave_fits)
+            return K::wave_std;
+        return all_focus ? K::persist_std_af : K::persist_std;
+    }();
+    // 3. the output form
+    return {k, nch, kernel_reads_copy(k), planar_views && kernel_writes_planar_views(c, k)};
 }
 
-// wave-private pipelines (blend_wave.hpp) where they apply — fixed focus, one K-chunk, one view pass — else blend_persist
-template <bool STD, int MT, bool NT_STORE>
-void launch_wave(const lfi_ctx *c, const KernelArgs &a, bool all_focus)
+int next_sweep_direction(const lfi_ctx *c);
+
+// one launch per 64 views (blend_stdx / blend_stdxa / blend_afs / blend_p3 over several chunks: a wave's accumulators hold 16 views)
+template <class F>
+void per_64_views(const KernelArgs &a_in, F &&launch)
 {
-    if(all_focus || a.k_pad > 64 || a.v1 - a.v0 > 32 * MT)
+    for(int v0 = a_in.v0; v0 < a_in.v1; v0 += 64)
     {
-        launch_persist<STD, MT, NT_STORE>(c, a, all_focus);
-        return;
+        KernelArgs a = a_in;
+        a.v0 = v0;
+        a.v1 = std::min(v0 + 64, a_in.v1);
+        launch(a);
     }
-    const int tiles_x = (a.width + 127) / 128;
-    const int n_tiles = tiles_x * a.out_rows;
-    const dim3 grid(std::min(n_tiles, 2 * cu_count_of(c))), block(256);
-    note_kernel(c, STD ? "blend_wave<STD>" : "blend_wave<TEN_WM>");
-    hipLaunchKernelGGL((lfi::blend_wave<STD, MT, NT_STORE>), grid, block, 0, stream_of(c), a, tiles_x, n_tiles);
 }
 
-// STD through blend_planar<STDF> (MFMA sum + exact recomputation inside the rounding band) when launch_blend has validated the
-// planar copy and the weights for it, else the exact-fp32 MFMA kernels
-// GATHER_ONCE = true ("filtered_gather_once"): all-focus renders of three or four chunks of images by blend_afs (round 4: 64-pixel tiles whose
-// whole stack of samples stays in LDS, every sample gathered once) instead of blend_stdxa, which gathers chunks 2 and 3 a second time for
-// the chain.  Half the fabric traffic, the same bytes — and not faster (4.8 against 4.7 ms at config 5: bound by instruction issue, see
-// profiles/r04_notes.md), so it is a selectable variant and the second implementation in the parity tests, not the default.
-template <bool GATHER_ONCE>
-void launch_std_filtered_t(const lfi_ctx *c, const KernelArgs &a_in, bool all_focus)
+// launch(std::integral_constant<int, N>) for the chunk count nch, over the forms a kernel is instantiated for: MIN..3, and 4 for more
+template <int MIN, class F>
+void with_chunks(int nch, F &&launch)
 {
-    if(all_focus && c->weights_scalable && c->weights_sum_ok && !a_in.prequant && a_in.k_pad <= 4 * 64)
+    if constexpr(MIN <= 1)
     {
-        // all-focus: blend_stdxa — the band method on the per-pixel gather pipeline (RGBA planes; no derived copy); one launch per 64 views
-        const int tiles_x = (a_in.width + 127) / 128;
-        const int n_tiles = tiles_x * a_in.out_rows;
-        const dim3 grid(std::min(n_tiles, 2 * cu_count_of(c))), block(256);
-        const int nch = (a_in.k_pad + 63) / 64;
-        if(nch >= 3 && GATHER_ONCE)
-        {
-            // three or four chunks of images: blend_afs — 64-pixel tiles whose whole stack of samples stays in LDS, every sample gathered
-            // once (blend_stdxa gathers chunks 2 and 3 a second time for the chain)
-            const int tiles_x64 = (a_in.width + lfi::AF_TPX - 1) / lfi::AF_TPX;
-            const int n_tiles64 = tiles_x64 * a_in.out_rows;
-            const dim3 grid64(std::min(n_tiles64, 2 * cu_count_of(c)));
-            note_kernel(c, "blend_afs<STD,allfocus>");
-            for(int v0 = a_in.v0; v0 < a_in.v1; v0 += 64)
-            {
-                KernelArgs a = a_in;
-                a.v0 = v0;
-                a.v1 = std::min(v0 + 64, a_in.v1);
-                if(nch == 3)
-                    hipLaunchKernelGGL((lfi::blend_afs<true, 3>), grid64, block, 0, stream_of(c), a, tiles_x64, n_tiles64);
-                else
-                    hipLaunchKernelGGL((lfi::blend_afs<true, 4>), grid64, block, 0, stream_of(c), a, tiles_x64, n_tiles64);
-            }
-            return;
-        }
-        note_kernel(c, "blend_stdxa<STD,allfocus>");
-        // the planar layout's byte planes written by the kernel itself (launch_blend: stdxa_writes_planar_views)
-        const bool planar_views_af = a_in.views == c->views && c->out_layout == LFI_LAYOUT_PLANAR_RGB;
-        for(int v0 = a_in.v0; v0 < a_in.v1; v0 += 64)
-        {
-            KernelArgs a = a_in;
-            a.v0 = v0;
-            a.v1 = std::min(v0 + 64, a_in.v1);
-#define LFI_SXA_LAUNCH(N)                                                                                                                       \
-    do                                                                                                                                          \
-    {                                                                                                                                           \
-        if(planar_views_af)                                                                                                                     \
-            hipLaunchKernelGGL((lfi::blend_stdxa<true, N, true>), grid, block, 0, stream_of(c), a, tiles_x, n_tiles);                           \
-        else                                                                                                                                    \
-            hipLaunchKernelGGL((lfi::blend_stdxa<true, N>), grid, block, 0, stream_of(c), a, tiles_x, n_tiles);                                 \
-    } while(0)
-            switch(nch)
-            {
-                case 1: LFI_SXA_LAUNCH(1); break;
-                case 2: LFI_SXA_LAUNCH(2); break;
-                case 3: LFI_SXA_LAUNCH(3); break;
-                default: LFI_SXA_LAUNCH(4); break;
-            }
-#undef LFI_SXA_LAUNCH
-        }
-        return;
+        if(nch == 1)
+            return launch(std::integral_constant<int, 1>());
     }
-    if(!a_in.planar || all_focus || a_in.k_pad > 4 * lfi::P3_KC)
+    if constexpr(MIN <= 2)
     {
-        // (launch_blend hands this launcher the planar byte views only together with a valid planar copy or for the all-focus branch above:
-        // the RGBA-store kernels below never see them)
-        launch_wave<true, 2, true>(c, a_in, all_focus);
-        return;
+        if(nch == 2)
+            return launch(std::integral_constant<int, 2>());
     }
-    // planar views written directly (launch_blend has pointed a.views at the byte planes: stdx_writes_planar_views): blend_stdx also for ONE
-    // chunk of images — blend_planar<STDF> would go through an RGBA scratch copy of all views and a conversion pass (config 2: 0.45 ms
-    // against 0.23).  With RGBA views blend_planar<STDF> stays: as fast at config 2, 15 % faster for one rank of config 4
-    // (profiles/r04_rgba_p3_ab.txt).
-    const bool planar_views = a_in.views == c->views && c->out_layout == LFI_LAYOUT_PLANAR_RGB;
-    if(a_in.k_pad > 64 || planar_views)
-    {
-        // more than one chunk of images (15×15 grids): blend_stdx — the band method with the chain's bytes fetched a second time;
-        // one launch per 64 views (the accumulators of a wave hold 16 views)
-        const int tiles_x = (a_in.width + lfi::P3_TPX - 1) / lfi::P3_TPX;
-        const int n_tiles = tiles_x * a_in.out_rows;
-        const dim3 grid(std::min(n_tiles, 2 * cu_count_of(c))), block(256);
-        const int nch = (a_in.k_pad + lfi::P3_KC - 1) / lfi::P3_KC;
-        const int reverse = next_sweep_direction(c);
-        // planar views written directly: launch_blend has pointed a.views at the byte planes (stdx_writes_planar_views)
-        const bool planar_out = planar_views;
-        note_kernel(c, "blend_stdx<STD>");
-        for(int v0 = a_in.v0; v0 < a_in.v1; v0 += 64)
-        {
-            KernelArgs a = a_in;
-            a.v0 = v0;
-            a.v1 = std::min(v0 + 64, a_in.v1);
-#define LFI_SX_LAUNCH(N)                                                                                                                        \
-    do                                                                                                                                          \
-    {                                                                                                                                           \
-        if(planar_out)                                                                                                                          \
-            hipLaunchKernelGGL((lfi::blend_stdx<true, N, true>), grid, block, 0, stream_of(c), a, tiles_x, n_tiles, reverse);                   \
-        else                                                                                                                                    \
-            hipLaunchKernelGGL((lfi::blend_stdx<true, N>), grid, block, 0, stream_of(c), a, tiles_x, n_tiles, reverse);                         \
-    } while(0)
-            switch(nch)
-            {
-                case 1: LFI_SX_LAUNCH(1); break; // (planar views only)
-                case 2: LFI_SX_LAUNCH(2); break;
-                case 3: LFI_SX_LAUNCH(3); break;
-                default: LFI_SX_LAUNCH(4); break;
-            }
-#undef LFI_SX_LAUNCH
-        }
-        return;
-    }
-    const KernelArgs &a = a_in;
-    const int tiles_x = (a.width + 127) / 128;
-    const int n_tiles = tiles_x * a.out_rows;
-    const int passes = (a.v1 - a.v0 + 63) / 64;
-    const dim3 grid(std::min(n_tiles, 2 * cu_count_of(c))), block(256);
-    note_kernel(c, "blend_planar<STDF>");
-    hipLaunchKernelGGL((lfi::blend_planar<2, true, true>), grid, block, 0, stream_of(c), a, tiles_x, n_tiles, passes, 0, next_sweep_direction(c));
+    if(nch == 3)
+        return launch(std::integral_constant<int, 3>());
+    launch(std::integral_constant<int, 4>());
 }
 
-template <int PXL, int MT>
+// the generic MFMA kernels' grid: tiles of 32 pixels of a row, passes of 64 views, 4 / vpw tiles per workgroup
+struct GenericGrid
+{
+    int tiles_x, n_tiles, passes, vpw;
+    dim3 grid;
+};
+GenericGrid generic_grid(const KernelArgs &a)
+{
+    GenericGrid g;
+    g.tiles_x = (a.width + 31) / 32;
+    g.n_tiles = g.tiles_x * a.height;
+    g.passes = (a.v1 - a.v0 + 63) / 64;
+    g.vpw = g.passes >= 4 ? 4 : (g.passes >= 2 ? 2 : 1);
+    const int tiles_per_wg = 4 / g.vpw;
+    g.grid = dim3((g.n_tiles + tiles_per_wg - 1) / tiles_per_wg);
+    return g;
+}
+
+void launch_ten_m16(const lfi_ctx *c, const KernelArgs &a, bool all_focus)
+{
+    note_kernel(c, "blend_ten_m16");
+    if(all_focus)
+        hipLaunchKernelGGL(lfi::blend_ten_m16<true>, pixel_grid_of(c), dim3(256), 0, stream_of(c), a);
+    else
+        hipLaunchKernelGGL(lfi::blend_ten_m16<false>, pixel_grid_of(c), dim3(256), 0, stream_of(c), a);
+}
+
+void launch_ten_direct(const lfi_ctx *c, const KernelArgs &a, bool all_focus)
+{
+    const GenericGrid g = generic_grid(a);
+    note_kernel(c, "blend_ten_direct");
+    if(all_focus)
+        hipLaunchKernelGGL((lfi::blend_ten_direct<1, 2, true>), g.grid, dim3(256), 0, stream_of(c), a, g.tiles_x, g.n_tiles, g.passes, g.vpw);
+    else
+        hipLaunchKernelGGL((lfi::blend_ten_direct<1, 2, false>), g.grid, dim3(256), 0, stream_of(c), a, g.tiles_x, g.n_tiles, g.passes, g.vpw);
+}
+
 void launch_std_mfma(const lfi_ctx *c, const KernelArgs &a, bool all_focus)
 {
-    const int tiles_x = (a.width + 32 * PXL - 1) / (32 * PXL);
-    const int n_tiles = tiles_x * a.height;
-    const int passes = (a.v1 - a.v0 + 32 * MT - 1) / (32 * MT);
-    const int vpw = passes >= 4 ? 4 : (passes >= 2 ? 2 : 1);
-    const int tiles_per_wg = 4 / vpw;
-    const dim3 grid((n_tiles + tiles_per_wg - 1) / tiles_per_wg), block(256);
+    const GenericGrid g = generic_grid(a);
     note_kernel(c, "blend_std_mfma");
     if(all_focus)
-        hipLaunchKernelGGL((lfi::blend_std_mfma<PXL, MT, true>), grid, block, 0, stream_of(c), a, tiles_x, n_tiles, passes, vpw);
+        hipLaunchKernelGGL((lfi::blend_std_mfma<1, 2, true>), g.grid, dim3(256), 0, stream_of(c), a, g.tiles_x, g.n_tiles, g.passes, g.vpw);
     else
-        hipLaunchKernelGGL((lfi::blend_std_mfma<PXL, MT, false>), grid, block, 0, stream_of(c), a, tiles_x, n_tiles, passes, vpw);
+        hipLaunchKernelGGL((lfi::blend_std_mfma<1, 2, false>), g.grid, dim3(256), 0, stream_of(c), a, g.tiles_x, g.n_tiles, g.passes, g.vpw);
 }
 
 void launch_std_valu(const lfi_ctx *c, const KernelArgs &a, bool all_focus)
@@ -289,35 +271,124 @@ void launch_std_vfma(const lfi_ctx *c, const KernelArgs &a, bool all_focus)
         hipLaunchKernelGGL((lfi::blend_std_vfma<false>), pixel_grid_of(c), dim3(256), 0, stream_of(c), a);
 }
 
-// first entry = default ("auto")
-const Variant kTenVariants[] = {
-    {"p3_rgba_nt", launch_p3_rgba, true, false, true, true},        // blend_p3 with the RGBA epilogue; blend_planar / blend_persist where it does not apply
-    {"planar_m2_nt", launch_planar<true>, true, false, true, true}, // blend_persist where blend_planar does not apply
-    {"persist_m2_nt", launch_persist<false, 2, true>, true, false, true},
-    {"wave_m2_nt", launch_wave<false, 2, true>, true, false, true},
-    {"direct_p1m2", launch_ten_direct<1, 2>, false, true}, // generic: any weights, pre-quantisation dump, per-batch rounding
-};
-const Variant kStdVariants[] = {
-    {"filtered_m2_nt", launch_std_filtered_t<false>, false, false, true, true}, // blend_wave / blend_persist where it does not apply
-    {"filtered_gather_once", launch_std_filtered_t<true>, false, false, true, true}, // the same with blend_afs for all-focus renders of 3–4 chunks
-    {"wave_m2_nt", launch_wave<true, 2, true>, false, false, true},    // blend_persist where blend_wave does not apply
-    {"persist_m2_nt", launch_persist<true, 2, true>, false, false, true},
-    {"mfma_p1m2", launch_std_mfma<1, 2>, false, true}, // generic: pre-quantisation dump
-    {"valu", launch_std_valu, false, true},             // the reference-shaped one-pixel-per-thread kernel: exactness anchor
-    {"vfma", launch_std_vfma, false, true},             // the non-tensor wavefront kernel
-};
-const int kNumTenVariants = sizeof(kTenVariants) / sizeof(kTenVariants[0]);
-const int kNumStdVariants = sizeof(kStdVariants) / sizeof(kStdVariants[0]);
-int find_variant(const Variant *table, int n, const char *name)
+// planar_out: all-focus TEN_WM only (the one planar-view form of blend_persist)
+template <bool STD>
+void launch_persist(const lfi_ctx *c, const KernelArgs &a, bool all_focus, bool planar_out)
 {
-    for(int i = 0; i < n; i++)
-        if(std::strcmp(table[i].name, name) == 0)
-            return i;
-    return 0;
+    const int tiles_x = (a.width + 127) / 128;
+    const int n_tiles = tiles_x * a.out_rows;
+    const int passes = (a.v1 - a.v0 + 63) / 64;
+    // persistent: two workgroups per CU (2 x 80 KB of LDS), each walks tiles j, j+G, j+2G ...
+    const dim3 grid(std::min(n_tiles, 2 * cu_count_of(c))), block(256);
+    note_kernel(c, STD ? (all_focus ? "blend_persist<STD,allfocus>" : "blend_persist<STD>") : (all_focus ? "blend_persist<TEN_WM,allfocus>" : "blend_persist<TEN_WM>"));
+    if constexpr(!STD)
+    {
+        if(planar_out)
+        {
+            hipLaunchKernelGGL((lfi::blend_persist<false, 2, true, true, 64, 2, true>), grid, block, 0, stream_of(c), a, tiles_x, n_tiles, passes);
+            return;
+        }
+    }
+    if(all_focus)
+        hipLaunchKernelGGL((lfi::blend_persist<STD, 2, true, true>), grid, block, 0, stream_of(c), a, tiles_x, n_tiles, passes);
+    else
+        hipLaunchKernelGGL((lfi::blend_persist<STD, 2, false, true>), grid, block, 0, stream_of(c), a, tiles_x, n_tiles, passes);
 }
-// the generic kernels: plain fp32 epilogue, any weights, pre-quantisation dump, per-batch rounding (TEN_WM)
-const int kGenericTenVariant = find_variant(kTenVariants, kNumTenVariants, "direct_p1m2");
-const int kGenericStdVariant = find_variant(kStdVariants, kNumStdVariants, "mfma_p1m2");
+
+template <bool STD>
+void launch_wave(const lfi_ctx *c, const KernelArgs &a)
+{
+    const int tiles_x = (a.width + 127) / 128;
+    const int n_tiles = tiles_x * a.out_rows;
+    const dim3 grid(std::min(n_tiles, 2 * cu_count_of(c))), block(256);
+    note_kernel(c, STD ? "blend_wave<STD>" : "blend_wave<TEN_WM>");
+    hipLaunchKernelGGL((lfi::blend_wave<STD, 2, true>), grid, block, 0, stream_of(c), a, tiles_x, n_tiles);
+}
+
+// from the planar copy of the inputs (blend_planar.hpp): TEN_WM, or STD by the band method (STDF)
+template <bool STDF>
+void launch_planar(const lfi_ctx *c, const KernelArgs &a)
+{
+    const int tiles_x = (a.width + 127) / 128;
+    const int n_tiles = tiles_x * a.out_rows;
+    const int passes = (a.v1 - a.v0 + 63) / 64;
+    const dim3 grid(std::min(n_tiles, 2 * cu_count_of(c))), block(256);
+    note_kernel(c, STDF ? "blend_planar<STDF>" : "blend_planar<TEN_WM>");
+    hipLaunchKernelGGL((lfi::blend_planar<2, true, STDF>), grid, block, 0, stream_of(c), a, tiles_x, n_tiles, passes, STDF ? 0 : 1, next_sweep_direction(c));
+}
+
+void launch_stdx(const lfi_ctx *c, const KernelArgs &a_in, const BlendRoute &r)
+{
+    const int tiles_x = (a_in.width + lfi::P3_TPX - 1) / lfi::P3_TPX;
+    const int n_tiles = tiles_x * a_in.out_rows;
+    const dim3 grid(std::min(n_tiles, 2 * cu_count_of(c))), block(256);
+    const int reverse = next_sweep_direction(c);
+    note_kernel(c, "blend_stdx<STD>");
+    per_64_views(a_in, [&](const KernelArgs &a) {
+        with_chunks<1>(r.nch, [&](auto n) {
+            if(r.planar_out)
+                hipLaunchKernelGGL((lfi::blend_stdx<true, decltype(n)::value, true>), grid, block, 0, stream_of(c), a, tiles_x, n_tiles, reverse);
+            else
+                hipLaunchKernelGGL((lfi::blend_stdx<true, decltype(n)::value>), grid, block, 0, stream_of(c), a, tiles_x, n_tiles, reverse);
+        });
+    });
+}
+
+void launch_stdxa(const lfi_ctx *c, const KernelArgs &a_in, const BlendRoute &r)
+{
+    const int tiles_x = (a_in.width + 127) / 128;
+    const int n_tiles = tiles_x * a_in.out_rows;
+    const dim3 grid(std::min(n_tiles, 2 * cu_count_of(c))), block(256);
+    note_kernel(c, "blend_stdxa<STD,allfocus>");
+    per_64_views(a_in, [&](const KernelArgs &a) {
+        with_chunks<1>(r.nch, [&](auto n) {
+            if(r.planar_out)
+                hipLaunchKernelGGL((lfi::blend_stdxa<true, decltype(n)::value, true>), grid, block, 0, stream_of(c), a, tiles_x, n_tiles);
+            else
+                hipLaunchKernelGGL((lfi::blend_stdxa<true, decltype(n)::value>), grid, block, 0, stream_of(c), a, tiles_x, n_tiles);
+        });
+    });
+}
+
+void launch_afs(const lfi_ctx *c, const KernelArgs &a_in, const BlendRoute &r)
+{
+    const int tiles_x = (a_in.width + lfi::AF_TPX - 1) / lfi::AF_TPX;
+    const int n_tiles = tiles_x * a_in.out_rows;
+    const dim3 grid(std::min(n_tiles, 2 * cu_count_of(c))), block(256);
+    note_kernel(c, "blend_afs<STD,allfocus>");
+    per_64_views(a_in, [&](const KernelArgs &a) {
+        with_chunks<3>(r.nch, [&](auto n) {
+            hipLaunchKernelGGL((lfi::blend_afs<true, decltype(n)::value>), grid, block, 0, stream_of(c), a, tiles_x, n_tiles);
+        });
+    });
+}
+
+void launch_p3(const lfi_ctx *c, const KernelArgs &a_in, int nch, bool rgba_out);
+
+void launch_route(const lfi_ctx *c, const KernelArgs &a, bool all_focus, const BlendRoute &r)
+{
+    switch(r.kernel)
+    {
+        case BlendKernel::ten_m16: launch_ten_m16(c, a, all_focus); break;
+        case BlendKernel::ten_direct: launch_ten_direct(c, a, all_focus); break;
+        case BlendKernel::p3: launch_p3(c, a, r.nch, false); break;
+        case BlendKernel::p3_rgba: launch_p3(c, a, r.nch, true); break;
+        case BlendKernel::planar_ten: launch_planar<false>(c, a); break;
+        case BlendKernel::persist_ten:
+        case BlendKernel::persist_ten_af: launch_persist<false>(c, a, all_focus, r.planar_out); break;
+        case BlendKernel::wave_ten: launch_wave<false>(c, a); break;
+        case BlendKernel::stdx: launch_stdx(c, a, r); break;
+        case BlendKernel::planar_stdf: launch_planar<true>(c, a); break;
+        case BlendKernel::stdxa: launch_stdxa(c, a, r); break;
+        case BlendKernel::afs: launch_afs(c, a, r); break;
+        case BlendKernel::persist_std:
+        case BlendKernel::persist_std_af: launch_persist<true>(c, a, all_focus, false); break;
+        case BlendKernel::wave_std: launch_wave<true>(c, a); break;
+        case BlendKernel::std_mfma: launch_std_mfma(c, a, all_focus); break;
+        case BlendKernel::std_valu: launch_std_valu(c, a, all_focus); break;
+        case BlendKernel::std_vfma: launch_std_vfma(c, a, all_focus); break;
+    }
+}
 
 int launch_blend(lfi_ctx *c, int method, int all_focus, const KernelArgs &a);
 
@@ -390,20 +461,14 @@ bool ensure_planar(lfi_ctx *c, bool tune = false, int min_reach = 0)
     // a tile's 128-byte run starts up to `reach` pixels left of column 0 (left padding: reach, rounded up to whole dwords so that the
     // build's dword stores stay aligned) and, in the last tile of a row, ends up to `reach` pixels past the last tile's 128th pixel
     const bool valid = c->planar && c->planar_version == c->grid_version && c->planar_reach >= reach && (int)c->planar_phase.size() == c->n;
-    auto tuned = [&] {
-        for(int g = 0; g < c->n; g++)
-            if((c->h_focused[g].x + c->planar_padx + c->planar_phase[g]) & (LFI_PLANAR_ALIGN - 1))
-                return false;
-        return true;
-    };
-    if(valid && (!tune || tuned()))
+    if(valid && (!tune || planar_phases_tuned(c)))
         return true;
     if(c->inputs_released)
         return valid; // nothing to rebuild from: the copy serves the offsets it was built for (stale phases cost a launch 6–10 %), or the render is refused
     // the copy in place fits and only SOME images were replaced since it was brought up to date (lfi_upload_image, a partial fill): their
     // planes only — 1/N of a rebuild per image
     if(c->planar && c->planar_version != 0 && c->planar_reach >= reach && (int)c->planar_phase.size() == c->n &&
-       c->grid_full_version <= c->planar_version && (!tune || tuned()))
+       c->grid_full_version <= c->planar_version && (!tune || planar_phases_tuned(c)))
     {
         for(int g = 0; g < c->n;)
         {
@@ -501,67 +566,17 @@ bool tune_planar_now(lfi_ctx *c)
     return c->launches_with_offsets++ >= LFI_RETUNE_AFTER;
 }
 
-// Would this launch read the planar copy of the inputs?
-bool wants_planar(const lfi_ctx *c, int method, int all_focus, const KernelArgs &a)
+// the derived copy's addressing, for a launch that reads it (ensure_planar has made it valid)
+void set_planar_args(const lfi_ctx *c, KernelArgs &a)
 {
-    if(all_focus || a.prequant || !c->weights_scalable)
-        return false;
-    // (Rounds 2–3 kept launches that write many more views than they read images — 256 views from 64 images — off the copy: +6 % then.  With the
-    // line-aligned copy it is the faster source there too: TEN_WM with RGBA views 2.04 against 2.17–2.28 ms, STD 3.6 against 7.2 ms for the
-    // exact-fp32 kernel, profiles/r04_rgba_p3_ab.txt.)
-    if(method == LFI_METHOD_TEN_WM)
-        return kTenVariants[c->ten_variant].planar && !(c->flags & LFI_FLAG_TEN_ROUND_PER_BATCH);
-    // STD: blend_planar<STDF> (one chunk of images) / blend_stdx (up to four) — weights for which their error bounds hold
-    return method == LFI_METHOD_STD && kStdVariants[c->std_variant].planar && c->weights_sum_ok && a.k_pad <= 4 * lfi::P3_KC;
+    a.planar = c->planar;
+    a.planar_pitch = c->planar_pitch;
+    a.planar_padx = c->planar_padx;
+    a.planar_phase = c->d_planar_phase; // allocated by ensure_planar, possibly just now
 }
 
-// planar view layout: does blend_p3 serve this launch?  (TEN_WM, fixed focus, weights in [0, 2) for the packed epilogue, no
-// debug modes; the planar input copy must be usable)
-bool wants_p3(const lfi_ctx *c, int method, int all_focus, const KernelArgs &a)
-{
-    // blend_p3's epilogue addresses a wave's 48 byte planes (16 views × 3 channels) with one 32-bit per-lane offset
-    const bool planes_fit = (uint64_t)48 * (uint64_t)c->out_rows * (uint64_t)view_pitch(c) < (1ull << 32);
-    return c->out_layout == LFI_LAYOUT_PLANAR_RGB && method == LFI_METHOD_TEN_WM && !all_focus && !a.prequant && c->weights_scalable &&
-           !(c->flags & LFI_FLAG_TEN_ROUND_PER_BATCH) && kTenVariants[c->ten_variant].planar && a.k_pad <= 4 * lfi::P3_KC && planes_fit;
-}
-
-// planar view layout: does blend_stdx write the byte planes of this STD launch directly?  (fixed focus, up to 256 images, the default STD
-// variants, weights for which the band method's bounds hold, the planar input copy usable; the addressing of a plane row: 32-bit)
-bool stdx_writes_planar_views(const lfi_ctx *c, int method, int all_focus, const KernelArgs &a)
-{
-    const bool planes_fit = (uint64_t)48 * (uint64_t)c->out_rows * (uint64_t)view_pitch(c) < (1ull << 32);
-    return c->out_layout == LFI_LAYOUT_PLANAR_RGB && method == LFI_METHOD_STD && c->std_variant <= 1 && planes_fit &&
-           wants_planar(c, method, all_focus, a);
-}
-
-// planar view layout: does blend_persist write the byte planes of this all-focus TEN_WM render directly?  (the default variants — both end in
-// blend_persist for all-focus renders —, weights in [0, 2) for the packed epilogue, no debug modes)
-bool persist_writes_planar_views(const lfi_ctx *c, int method, int all_focus, const KernelArgs &a)
-{
-    // store_tile_planar (blend_core.hpp) addresses (3·view + channel)·plane bytes for up to 32 views of a pass with one 32-bit offset
-    const bool planes_fit = (uint64_t)96 * (uint64_t)c->out_rows * (uint64_t)view_pitch(c) < (1ull << 32);
-    return c->out_layout == LFI_LAYOUT_PLANAR_RGB && method == LFI_METHOD_TEN_WM && all_focus && c->ten_variant <= 1 && c->weights_scalable && !a.prequant &&
-           !(c->flags & LFI_FLAG_TEN_ROUND_PER_BATCH) && planes_fit;
-}
-
-// … and blend_stdxa those of this all-focus STD render?  (the default STD variant, weights for which the band method's bounds hold)
-bool stdxa_writes_planar_views(const lfi_ctx *c, int method, int all_focus, const KernelArgs &a)
-{
-    return c->out_layout == LFI_LAYOUT_PLANAR_RGB && method == LFI_METHOD_STD && all_focus && c->std_variant == 0 && c->weights_scalable && c->weights_sum_ok &&
-           !a.prequant && a.k_pad <= 4 * 64 && (uint64_t)192 * (uint64_t)c->out_rows * (uint64_t)view_pitch(c) < (1ull << 32);
-}
-
-// Does a render with these arguments read the derived planar copy of the inputs?  ONE predicate for launch_blend's two branches,
-// lfi_prepare and lfi_benchmark (round 2: lfi_prepare tested wants_planar only and built nothing for launches that blend_p3 serves
-// beyond wants_planar's view limit — 256 views from 64 images — so the first render carried the build).
-bool wants_derived_copy(const lfi_ctx *c, int method, int all_focus, const KernelArgs &a)
-{
-    // planar views: blend_p3 where it serves the launch; everything else — and every launch of the RGBA layout — goes through
-    // launch_blend_rgba, whose kernels read the copy under wants_planar's conditions
-    return (c->out_layout == LFI_LAYOUT_PLANAR_RGB && wants_p3(c, method, all_focus, a)) || wants_planar(c, method, all_focus, a);
-}
-
-void launch_p3(const lfi_ctx *c, const KernelArgs &a_in, bool rgba_out)
+// blend_p3 (TEN_WM from the planar copy): the planar views' epilogue, or (rgba_out: two to four chunks of images) the RGBA epilogue
+void launch_p3(const lfi_ctx *c, const KernelArgs &a_in, int nch, bool rgba_out)
 {
     const int tiles_x = (a_in.width + lfi::P3_TPX - 1) / lfi::P3_TPX;
     const int n_tiles = tiles_x * a_in.out_rows;
@@ -571,7 +586,6 @@ void launch_p3(const lfi_ctx *c, const KernelArgs &a_in, bool rgba_out)
 #else
     const dim3 grid(std::min(n_tiles, 2 * cu_count_of(c))), block(256);
 #endif
-    const int nch = (a_in.k_pad + lfi::P3_KC - 1) / lfi::P3_KC;
     note_kernel(c, rgba_out ? "blend_p3<TEN_WM,rgba>" : "blend_p3<TEN_WM>");
 #ifdef LFI_MEASUREMENT_BUILD
     // measurement builds only (make HIPFLAGS+=-DLFI_MEASUREMENT_BUILD, tools/p3_ablate.py): where does a unit's time go?  The ablated
@@ -627,7 +641,7 @@ void launch_p3(const lfi_ctx *c, const KernelArgs &a_in, bool rgba_out)
                 continue;
             }
 #endif
-            // (one chunk of images: the planar views' epilogue only — launch_p3_rgba keeps blend_planar / blend_persist there)
+            // (one chunk of images: the planar views' epilogue only — route_blend keeps blend_planar for RGBA views there)
             if(passes == 1)
                 hipLaunchKernelGGL((lfi::blend_p3<true, 1>), grid, block, 0, stream_of(c), a, tiles_x, n_tiles, 1, dir);
             else
@@ -635,43 +649,23 @@ void launch_p3(const lfi_ctx *c, const KernelArgs &a_in, bool rgba_out)
         }
         return;
     }
-    // several chunks: one launch per 64 views
-    for(int v0 = a_in.v0; v0 < a_in.v1; v0 += 64)
-    {
-        KernelArgs a = a_in;
-        a.v0 = v0;
-        a.v1 = std::min(v0 + 64, a_in.v1);
-#define LFI_P3_LAUNCH(N)                                                                                                                        \
-    do                                                                                                                                          \
-    {                                                                                                                                           \
-        if(rgba_out)                                                                                                                            \
-            hipLaunchKernelGGL((lfi::blend_p3<true, N, 0, 2, 1, true>), grid, block2, 0, stream_of(c), a, tiles_x, n_tiles, 1, reverse);        \
-        else                                                                                                                                    \
-            hipLaunchKernelGGL((lfi::blend_p3<true, N, 0, 2>), grid, block2, 0, stream_of(c), a, tiles_x, n_tiles, 1, reverse);                 \
-    } while(0)
+    per_64_views(a_in, [&](const KernelArgs &a) {
+        with_chunks<2>(nch, [&](auto n) {
+            constexpr int N = decltype(n)::value;
 #ifdef LFI_MEASUREMENT_BUILD
-        if(vg_env == 1)
-        {
-            if(nch == 2) hipLaunchKernelGGL((lfi::blend_p3<true, 2, 0, 1>), grid, block, 0, stream_of(c), a, tiles_x, n_tiles, 1, reverse);
-            else if(nch == 3) hipLaunchKernelGGL((lfi::blend_p3<true, 3, 0, 1>), grid, block, 0, stream_of(c), a, tiles_x, n_tiles, 1, reverse);
-            else hipLaunchKernelGGL((lfi::blend_p3<true, 4, 0, 1>), grid, block, 0, stream_of(c), a, tiles_x, n_tiles, 1, reverse);
-            continue;
-        }
+            if(vg_env == 1)
+            {
+                hipLaunchKernelGGL((lfi::blend_p3<true, N, 0, 1>), grid, block, 0, stream_of(c), a, tiles_x, n_tiles, 1, reverse);
+                return;
+            }
 #endif
-        switch(nch)
-        {
-            case 2: LFI_P3_LAUNCH(2); break;
-            case 3: LFI_P3_LAUNCH(3); break;
-            default: LFI_P3_LAUNCH(4); break;
-        }
-#undef LFI_P3_LAUNCH
-    }
+            if(rgba_out)
+                hipLaunchKernelGGL((lfi::blend_p3<true, N, 0, 2, 1, true>), grid, block2, 0, stream_of(c), a, tiles_x, n_tiles, 1, reverse);
+            else
+                hipLaunchKernelGGL((lfi::blend_p3<true, N, 0, 2>), grid, block2, 0, stream_of(c), a, tiles_x, n_tiles, 1, reverse);
+        });
+    });
 }
-
-// planar_decided: launch_blend has already made the derived copy valid for this launch (ensure_planar succeeded there) — the copy is
-// taken as it is, no second ensure_planar (the second call counted the launch twice and could be the one that rebuilds and fails,
-// after launch_blend had committed to kernels that write byte planes)
-int launch_blend_rgba(lfi_ctx *c, int method, int all_focus, const KernelArgs &a_in, bool planar_decided = false);
 
 // per-view rows (lfi_set_view_offsets / lfi_set_view_float_offsets) and which of them govern a render: the float rows an all-focus one,
 // when set; otherwise the integer rows, when set (which refuse all-focus renders: view_rows_ready)
@@ -709,6 +703,7 @@ bool allfocus_rows_held(const lfi_ctx *c, const lfi_float2 *o, size_t n)
     return true;
 }
 
+// Renders views [a_in.v0, a_in.v1) into a_in.views
 int launch_blend(lfi_ctx *c, int method, int all_focus, const KernelArgs &a_in)
 {
     if(int rc = join_uploads(c))
@@ -731,99 +726,57 @@ int launch_blend(lfi_ctx *c, int method, int all_focus, const KernelArgs &a_in)
             return launch_blend(c, method, all_focus, a);
         }
     }
-    if(c->inputs_released && !(wants_derived_copy(c, method, all_focus, a_in) && ensure_planar(c)))
+    if(method != LFI_METHOD_STD && method != LFI_METHOD_TEN_WM) // the reference throws here (src/interpolator.cu:289-290)
+        return fail(c, LFI_EINVAL, "The specified interpolation method does not exist!");
+    BlendRoute r = route_blend(c, method, all_focus != 0, a_in, true);
+    if(r.reads_copy && !ensure_planar(c, tune_planar_now(c)))
+        r = route_blend(c, method, all_focus != 0, a_in, false); // the copy may not be used: the same render from the RGBA planes
+    if(c->inputs_released && !r.reads_copy)
         return fail(c, LFI_EINVAL, "the RGBA inputs were released (lfi_release_inputs): only fixed-focus renders whose offsets the planar copy was built for "
                                    "are served (no all-focus render, debug mode, weights outside [0, 2) or larger offsets) - upload the images again");
-    if(c->out_layout != LFI_LAYOUT_PLANAR_RGB)
-        return launch_blend_rgba(c, method, all_focus, a_in);
-    if(wants_p3(c, method, all_focus, a_in) && ensure_planar(c, tune_planar_now(c)))
+    if(c->windowed)
     {
-        KernelArgs a = a_in;
-        a.planar = c->planar;
-        a.planar_pitch = c->planar_pitch;
-        a.planar_padx = c->planar_padx;
-        a.planar_phase = c->d_planar_phase; // allocated by ensure_planar, possibly just now
-        if(planar_phases_tuned(c))
-            a.flags |= lfi::LFI_KFLAG_PLAIN_TILE_ORDER;
-        launch_p3(c, a);
-        LFI_HIP(c, hipGetLastError());
-        return LFI_OK;
-    }
-    if(stdx_writes_planar_views(c, method, all_focus, a_in) && ensure_planar(c, tune_planar_now(c)))
-        // fixed-focus STD: blend_stdx writes the byte planes itself (a.views are the context's planar views)
-        return launch_blend_rgba(c, method, all_focus, a_in, true);
-    if(persist_writes_planar_views(c, method, all_focus, a_in) || stdxa_writes_planar_views(c, method, all_focus, a_in))
-        // all-focus renders: blend_persist / blend_stdxa write the byte planes themselves (quad transposes in their epilogues: store_tile_planar)
-        return launch_blend_rgba(c, method, all_focus, a_in);
-    // every other render (debug modes, non-default variants, weights outside [0, 2) or summing above 2) goes through the RGBA kernels into a
-    // scratch copy of the views and is converted to byte planes afterwards
-    const size_t need = rgba_out_plane_bytes(c) * c->views_n;
-    if(c->rgba_scratch_bytes != need)
-    {
-        if(c->rgba_scratch)
-            (void)hipFree(c->rgba_scratch);
-        c->rgba_scratch = nullptr;
-        c->rgba_scratch_bytes = 0;
-        LFI_HIP(c, hipMalloc(reinterpret_cast<void **>(&c->rgba_scratch), need));
-        c->rgba_scratch_bytes = need;
+        // a row window is honoured by the persistent kernels only (and the per-batch rounding mode refused for either method)
+        if(generic_kernel(r.kernel) || (c->flags & LFI_FLAG_TEN_ROUND_PER_BATCH))
+            return fail(c, LFI_EINVAL, "with a row window only renders with the default (persistent) kernels and weights in [0,2) are supported");
+        if(all_focus && !allfocus_rows_held(c, c->h_offsets.data(), c->h_offsets.size()))
+            return fail(c, LFI_EINVAL, "the input row window does not cover the rows an all-focus render of this band samples");
     }
     KernelArgs a = a_in;
-    a.views = c->rgba_scratch;
-    if(int rc = launch_blend_rgba(c, method, all_focus, a))
-        return rc;
-    const int pitch = view_pitch(c);
-    hipLaunchKernelGGL(lfi::views_rgba_to_planar, dim3((pitch / 4 + 255) / 256, c->out_rows, a.v1 - a.v0), dim3(256), 0, c->stream,
-                       reinterpret_cast<const uint32_t *>(c->rgba_scratch + rgba_out_plane_bytes(c) * a.v0), c->views + out_plane_bytes(c) * a.v0,
-                       c->width, c->out_rows, pitch);
-    LFI_HIP(c, hipGetLastError());
-    return LFI_OK;
-}
-
-int launch_blend_rgba(lfi_ctx *c, int method, int all_focus, const KernelArgs &a_in, bool planar_decided)
-{
-    KernelArgs a = a_in;
-    if(planar_decided || (wants_planar(c, method, all_focus, a) && ensure_planar(c, tune_planar_now(c))))
+    if(r.reads_copy)
     {
-        a.planar = c->planar;
-        a.planar_pitch = c->planar_pitch;
-        a.planar_padx = c->planar_padx;
-        a.planar_phase = c->d_planar_phase; // allocated by ensure_planar, possibly just now
+        set_planar_args(c, a);
         if(planar_phases_tuned(c))
             a.flags |= lfi::LFI_KFLAG_PLAIN_TILE_ORDER;
     }
     if(all_focus)
         a.flags |= lfi::LFI_KFLAG_PLAIN_TILE_ORDER; // per-pixel gathers: no lines shared between neighbouring tiles by construction
-    if(c->windowed)
+    // planar views from a kernel that writes RGBA only: into a scratch copy of the views, converted to byte planes afterwards
+    const bool scratch = c->out_layout == LFI_LAYOUT_PLANAR_RGB && !r.planar_out;
+    if(scratch)
     {
-        // a row window is honoured by the persistent kernels only
-        const bool ten = method == LFI_METHOD_TEN_WM;
-        const Variant &v = ten ? kTenVariants[c->ten_variant] : kStdVariants[c->std_variant];
-        if(a.prequant || !v.row_window || (c->flags & LFI_FLAG_TEN_ROUND_PER_BATCH) || (ten && v.packed_epilogue && !c->weights_scalable))
-            return fail(c, LFI_EINVAL, "with a row window only renders with the default (persistent) kernels and weights in [0,2) are supported");
-        if(all_focus && !allfocus_rows_held(c, c->h_offsets.data(), c->h_offsets.size()))
-            return fail(c, LFI_EINVAL, "the input row window does not cover the rows an all-focus render of this band samples");
+        const size_t need = rgba_out_plane_bytes(c) * c->views_n;
+        if(c->rgba_scratch_bytes != need)
+        {
+            if(c->rgba_scratch)
+                (void)hipFree(c->rgba_scratch);
+            c->rgba_scratch = nullptr;
+            c->rgba_scratch_bytes = 0;
+            LFI_HIP(c, hipMalloc(reinterpret_cast<void **>(&c->rgba_scratch), need));
+            c->rgba_scratch_bytes = need;
+        }
+        a.views = c->rgba_scratch;
     }
-    if(method == LFI_METHOD_TEN_WM)
-    {
-        // the generic kernel (direct_p1m2) serves what the packed-epilogue kernels cannot: the per-batch rounding debug
-        // mode, pre-quantisation dumps, and weights outside [0, 2)
-        int variant = c->ten_variant;
-        if((c->flags & LFI_FLAG_TEN_ROUND_PER_BATCH) || (kTenVariants[variant].packed_epilogue && !c->weights_scalable) ||
-           (a.prequant && !kTenVariants[variant].prequant))
-            variant = kGenericTenVariant;
-        kTenVariants[variant].launch(c, a, all_focus != 0);
-    }
-    else if(method == LFI_METHOD_STD)
-    {
-        int variant = c->std_variant;
-        if(a.prequant && !kStdVariants[variant].prequant)
-            variant = kGenericStdVariant;
-        kStdVariants[variant].launch(c, a, all_focus != 0);
-    }
-    else
-        // the reference throws here (src/interpolator.cu:289-290)
-        return fail(c, LFI_EINVAL, "The specified interpolation method does not exist!");
+    launch_route(c, a, all_focus != 0, r);
     LFI_HIP(c, hipGetLastError());
+    if(scratch)
+    {
+        const int pitch = view_pitch(c);
+        hipLaunchKernelGGL(lfi::views_rgba_to_planar, dim3((pitch / 4 + 255) / 256, c->out_rows, a.v1 - a.v0), dim3(256), 0, c->stream,
+                           reinterpret_cast<const uint32_t *>(c->rgba_scratch + rgba_out_plane_bytes(c) * a.v0), a_in.views + out_plane_bytes(c) * a.v0,
+                           c->width, c->out_rows, pitch);
+        LFI_HIP(c, hipGetLastError());
+    }
     return LFI_OK;
 }
 
@@ -874,12 +827,7 @@ int launch_view_rows(lfi_ctx *c, ViewRowsKind k, int method, int all_focus, cons
     if(view_maps)
         a.maps = c->view_maps;
     if(planar)
-    {
-        a.planar = c->planar;
-        a.planar_pitch = c->planar_pitch;
-        a.planar_padx = c->planar_padx;
-        a.planar_phase = c->d_planar_phase;
-    }
+        set_planar_args(c, a);
     const bool ten = method == LFI_METHOD_TEN_WM, planar_out = c->out_layout == LFI_LAYOUT_PLANAR_RGB;
     const int chunk_views = view_maps ? lfi::VM_VIEWS : lfi::VF_VIEWS;
     const int n_chunks = (a.v1 - a.v0 + chunk_views - 1) / chunk_views;

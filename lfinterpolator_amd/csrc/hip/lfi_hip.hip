@@ -1164,7 +1164,7 @@ int lfi_prepare(lfi_ctx *ctx, int method, int all_focus, int v0, int v1)
             LFI_HIP(ctx, hipEventElapsedTime(&ctx->derived_build_ms, ctx->ev0, ctx->ev1));
         return LFI_OK;
     }
-    if(wants_derived_copy(ctx, method, all_focus, a)) // the same predicate chain as launch_blend
+    if(route_blend(ctx, method, all_focus != 0, a, true).reads_copy) // the route launch_blend takes
     {
         ctx->eager_planar = true; // images that arrive from now on refresh their planes of the copy at once
         const uint64_t before = ctx->planar_version;
@@ -1277,7 +1277,6 @@ int lfi_render_stream(lfi_ctx *ctx, int method, int all_focus, const uint16_t *w
     const int n_blocks = (total_views + V - 1) / V;
     uint8_t *dev_weights = param_base(ctx) + ctx->blob_off_w16;
     uint8_t *const vbuf[2] = {ctx->views, host_out ? ctx->views2 : ctx->views};
-    uint8_t *const views_saved = ctx->views;
     int status = LFI_OK;
     for(int b = 0; b < n_blocks && status == LFI_OK; b++)
     {
@@ -1296,10 +1295,9 @@ int lfi_render_stream(lfi_ctx *ctx, int method, int all_focus, const uint16_t *w
         LFI_HIP(ctx, hipEventRecord(ctx->ev_h2d[slot], ctx->stream));
         if(host_out && b >= 2)
             LFI_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_d2h[slot], 0)); // block b − 2 has left this set of views
-        ctx->views = vbuf[slot];
-        const KernelArgs a = make_args(ctx, 0, nv, method);
+        KernelArgs a = make_args(ctx, 0, nv, method);
+        a.views = vbuf[slot];
         status = launch_blend(ctx, method, all_focus, a);
-        ctx->views = views_saved;
         if(status != LFI_OK || !host_out)
             continue;
         LFI_HIP(ctx, hipEventRecord(ctx->ev_rendered[slot], ctx->stream));
@@ -1423,7 +1421,7 @@ int lfi_benchmark(lfi_ctx *ctx, int method, int all_focus, int v0, int v1, int w
         if(int rc = view_rows_ready(ctx, rows, all_focus, a, &planar))
             return rc;
     }
-    else if(wants_derived_copy(ctx, method, all_focus, a))
+    else if(route_blend(ctx, method, all_focus != 0, a, true).reads_copy)
         (void)ensure_planar(ctx, true);
     for(int i = 0; i < warmup; i++)
         if(int rc = launch_blend(ctx, method, all_focus, a))

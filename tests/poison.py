@@ -72,10 +72,12 @@ def written_outside(ctx, v0, v1, byte, views=None):
     return [v for v in cand if not (ctx.download_view(v) == want).all()]
 
 
-def render_range(ctx, method, v0, v1, all_focus=False, byte=None, outside=None):
+def render_range(ctx, method, v0, v1, all_focus=False, byte=None, outside=None, inspect=None):
     """Render views [v0, v1) under poison, assert that every other view (or those in `outside`) still holds the poison, and return
-    the rendered views [v0, v1)."""
+    the rendered views [v0, v1).  inspect(): called after the render, before anything is downloaded."""
     b = render(ctx, method, all_focus=all_focus, v0=v0, v1=v1, byte=byte)
+    if inspect:
+        inspect()
     bad = written_outside(ctx, v0, v1, b, outside)
     assert not bad, (method, "views outside the range were written", v0, v1, bad[:8])
     return ctx.download_views(v0, v1)

@@ -6,6 +6,11 @@ weights, and the kernel that lfi_last_kernel_name() must report for it.  Every r
 directions of the kernels that alternate them): STD bit-exact, TEN_WM within one LSB of the oracle's M16 model, the per-batch rounding
 debug mode (LFI_FLAG_TEN_ROUND_PER_BATCH) byte for byte M16; views outside the range must still hold the poison.
 
+Two more columns follow from the kernel and the layout: whether the launch reads the derived planar copy of the inputs (READS_COPY), and
+whether, in the planar view layout, it goes through the RGBA scratch copy and the conversion (every kernel outside WRITES_PLANES).  The
+row's fresh context shows both after its first render, before any download: lfi_memory_info's derived_bytes > 0 exactly when the launch
+read the copy, workspace_bytes > 0 exactly when it used the scratch copy (no focus map, no download has run).
+
 Rows marked `persistent` have more tiles than 2 × the device's CUs, so that the persistent kernels walk their tile loops (a small image
 gives every workgroup one tile).  A CPU test (no gpu mark) reads every note_kernel(c, "…") name under csrc/hip/ and fails if the table
 has no row for one of them, or misses one of the chunk counts / output forms a kernel is instantiated for.
@@ -25,6 +30,9 @@ HIP_DIR = os.path.join(ROOT, "lfinterpolator_amd", "csrc", "hip")
 MEASUREMENT_ONLY = {"blend_p3<ABLATION>"}   # LFI_MEASUREMENT_BUILD only: not in the product library
 ROUND = 2    # LFI_FLAG_TEN_ROUND_PER_BATCH
 THREADS = min(os.cpu_count() or 1, 16)
+READS_COPY = {"blend_p3<TEN_WM>", "blend_p3<TEN_WM,rgba>", "blend_planar<TEN_WM>", "blend_planar<STDF>", "blend_stdx<STD>"}
+# planar view layout: the kernels that write the byte planes themselves (every shape here fits their 32-bit plane addressing)
+WRITES_PLANES = {"blend_p3<TEN_WM>", "blend_stdx<STD>", "blend_stdxa<STD,allfocus>", "blend_persist<TEN_WM,allfocus>"}
 
 
 @dataclass(frozen=True)
@@ -46,6 +54,7 @@ class Row:
     expect: str          # lfi_last_kernel_name()
     persistent: int = 0  # pixels per tile of the kernel when the row must run its tile loop, else 0
     order: str = ""      # blend_p3, planar layout: "plain" / "xcd" tile order (see test_dispatch_row)
+    far: bool = False    # one image's focused x offset beyond the derived copy's reach (4·W + 4096): the route without the copy
 
     @property
     def n(self):
@@ -55,10 +64,19 @@ class Row:
     def chunks(self):   # 64-image chunks of k_pad = n rounded up to 16
         return ((self.n + 15) // 16 * 16 + 63) // 64
 
+    @property
+    def reads_copy(self):
+        return self.expect in READS_COPY
 
-def R(name, grid, W, H, V, method, expect, v=None, af=False, layout="rgba", flags=0, variant="auto", weights="default", persistent=0, order=""):
+    @property
+    def scratch(self):
+        return self.layout == "planar" and self.expect not in WRITES_PLANES
+
+
+def R(name, grid, W, H, V, method, expect, v=None, af=False, layout="rgba", flags=0, variant="auto", weights="default", persistent=0, order="",
+      far=False):
     v0, v1 = v if v else (0, V)
-    return Row(name, grid[0], grid[1], W, H, V, v0, v1, method, af, layout, flags, variant, weights, expect, persistent, order)
+    return Row(name, grid[0], grid[1], W, H, V, v0, v1, method, af, layout, flags, variant, weights, expect, persistent, order, far)
 
 
 G1, G1S, G2, G3, G4 = (8, 8), (3, 3), (9, 9), (12, 12), (15, 15)   # k_pad 64, 16, 80..128 (2 chunks), 144 (3), 225 -> 240 (4)
@@ -127,6 +145,13 @@ MATRIX = [
     R("stdxa_planar_3ch", G3, 150, 3, 7, "STD", "blend_stdxa<STD,allfocus>", af=True, layout="planar"),
     R("stdxa_planar_4ch_range", G4, 129, 3, 70, "STD", "blend_stdxa<STD,allfocus>", af=True, layout="planar", v=(6, 68)),
     R("persist_ten_af_planar", G1, 200, 6, 8, "TEN_WM", "blend_persist<TEN_WM,allfocus>", af=True, layout="planar"),
+    # the other variants, where the route reaches a kernel with a planar-view epilogue
+    R("p3_planar_variant", G2, 200, 4, 9, "TEN_WM", "blend_p3<TEN_WM>", layout="planar", variant="planar_m2_nt"),
+    R("stdx_planar_gather_once_2ch", G2, 200, 4, 9, "STD", "blend_stdx<STD>", layout="planar", variant="filtered_gather_once"),
+    R("persist_ten_af_planar_persist", G1, 200, 6, 8, "TEN_WM", "blend_persist<TEN_WM,allfocus>", af=True, layout="planar", variant="persist_m2_nt"),
+    R("persist_ten_af_planar_wave", (4, 4), 150, 5, 8, "TEN_WM", "blend_persist<TEN_WM,allfocus>", af=True, layout="planar", variant="wave_m2_nt"),
+    R("stdxa_planar_gather_once_1ch", G1, 200, 5, 8, "STD", "blend_stdxa<STD,allfocus>", af=True, layout="planar", variant="filtered_gather_once"),
+    R("stdxa_planar_gather_once_2ch", G2, 130, 4, 9, "STD", "blend_stdxa<STD,allfocus>", af=True, layout="planar", variant="filtered_gather_once"),
     # ---- planar views through the RGBA scratch copy and the conversion (debug modes, other variants, weights outside [0, 2)) ----
     R("scratch_ten_m16", G2, 130, 4, 9, "TEN_WM", "blend_ten_m16", layout="planar", flags=ROUND),
     R("scratch_ten_wide_range", G1, 150, 4, 9, "TEN_WM", "blend_ten_direct", layout="planar", weights="wide", v=(2, 7)),
@@ -134,6 +159,10 @@ MATRIX = [
     R("scratch_persist_std_range", G2, 200, 4, 70, "STD", "blend_persist<STD>", layout="planar", variant="persist_m2_nt", v=(3, 67)),
     R("scratch_afs", G4, 129, 3, 9, "STD", "blend_afs<STD,allfocus>", af=True, layout="planar", variant="filtered_gather_once"),
     R("scratch_wave_ten", (4, 4), 300, 5, 8, "TEN_WM", "blend_wave<TEN_WM>", layout="planar", variant="wave_m2_nt"),
+    R("scratch_wave_std", (4, 4), 300, 5, 8, "STD", "blend_wave<STD>", layout="planar", variant="wave_m2_nt"),
+    # ---- the default TEN_WM route when the derived copy cannot serve the offsets ----
+    R("persist_ten_copy_out_of_reach", G1, 130, 4, 9, "TEN_WM", "blend_persist<TEN_WM>", far=True),
+    R("scratch_persist_ten_copy_out_of_reach", G2, 130, 4, 9, "TEN_WM", "blend_persist<TEN_WM>", layout="planar", far=True),
 ]
 
 
@@ -175,6 +204,10 @@ def test_matrix_reaches_every_chunk_count_and_output_form():
                    "blend_persist<TEN_WM,allfocus>", "blend_persist<STD>", "blend_planar<TEN_WM>", "blend_planar<STDF>"):
         assert any(r.persistent for r in MATRIX if r.expect == kernel), kernel
     assert {r.order for r in MATRIX if r.expect == "blend_p3<TEN_WM>" and r.persistent} == {"plain", "xcd"}
+    assert {r.layout for r in MATRIX if r.far} == {"rgba", "planar"}
+    # the output forms: every kernel that writes planar views does so in some row, and some row reaches each kernel that reads the copy
+    assert WRITES_PLANES <= {r.expect for r in MATRIX if r.layout == "planar" and not r.scratch}
+    assert READS_COPY <= {r.expect for r in MATRIX}
 
 
 def _cu_count():
@@ -213,6 +246,9 @@ def test_dispatch_row(row, gpu, oracle_c):
     if row.weights == "wide":
         hp.weights = hp.weights.copy()
         hp.weights[:, n // 2] = 0x4100     # fp16 2.5
+    if row.far:
+        hp.focused_offsets = hp.focused_offsets.copy()
+        hp.focused_offsets[n // 2, 0] = 4 * W + 5000
     lf = oracle_c.synthetic_lf(n, W, H, 0x5EED + n + W)
     ctx = gpu.Context(0)
     ctx.set_grid(row.cols, row.rows, W, H)
@@ -243,8 +279,15 @@ def test_dispatch_row(row, gpu, oracle_c):
         tol = 0 if row.flags & ROUND else TEN_TOL_LSB
     outside = None if row.V <= 80 else [0, row.v0 - 1, row.v1, row.V - 1]
 
+    def paths():
+        # the row's fresh context after its first render, before any download (which may allocate a staging plane)
+        mi = ctx.memory_info()
+        got = {"reads_copy": mi.derived_bytes > 0, "scratch": mi.workspace_bytes > 0}
+        assert got == {"reads_copy": row.reads_copy, "scratch": row.scratch}, (row.name, got)
+
     def check(byte):
-        got = poison.render_range(ctx, row.method, row.v0, row.v1, all_focus=row.all_focus, byte=byte, outside=outside)
+        got = poison.render_range(ctx, row.method, row.v0, row.v1, all_focus=row.all_focus, byte=byte, outside=outside,
+                                  inspect=paths if byte == poison.POISON[0] else None)
         assert ctx.last_kernel_name() == row.expect, (row.name, ctx.last_kernel_name())
         bad = poison.mismatch(got, want[row.v0:row.v1], tol)
         assert bad == 0, (row.name, hex(byte), bad)
