@@ -169,11 +169,12 @@ int run_band_probe(lfi_ctx *c, const BandProbe **out)
         for(int j = 0; j < 32; j++)
             probe_pixel_column(rng, K, (s % SETS == 0) ? j % 6 : rng.below(6), b + j, 32);
     }
-    uint8_t *d = nullptr;
     const size_t in_bytes = host.size() * sizeof(uint16_t), out_bytes = got.size() * sizeof(float);
-    LFI_HIP(c, hipMalloc(reinterpret_cast<void **>(&d), in_bytes + out_bytes));
-    hipError_t e = hipMemcpyAsync(d, host.data(), in_bytes, hipMemcpyHostToDevice, c->stream);
-    for(int s = 0; s < n_sets && e == hipSuccess; s++)
+    DeviceBuffer buf;
+    LFI_HIP(c, buf.reserve(in_bytes + out_bytes));
+    uint8_t *const d = buf.get();
+    LFI_HIP(c, hipMemcpyAsync(d, host.data(), in_bytes, hipMemcpyHostToDevice, c->stream));
+    for(int s = 0; s < n_sets; s++)
     {
         const int K = KS[(s / SETS) & 1], shape = s / (2 * SETS);
         const uint16_t *da = reinterpret_cast<const uint16_t *>(d) + (size_t)s * SET_WORDS, *db = da + 32 * 256;
@@ -182,14 +183,10 @@ int run_band_probe(lfi_ctx *c, const BandProbe **out)
             hipLaunchKernelGGL(lfi::probe_mfma_f16_chain<0>, dim3(1), dim3(64), 0, c->stream, da, db, K, dc);
         else
             hipLaunchKernelGGL(lfi::probe_mfma_f16_chain<1>, dim3(1), dim3(64), 0, c->stream, da, db, K, dc);
-        e = hipGetLastError();
+        LFI_HIP(c, hipGetLastError());
     }
-    if(e == hipSuccess)
-        e = hipMemcpyAsync(got.data(), d + in_bytes, out_bytes, hipMemcpyDeviceToHost, c->stream);
-    if(e == hipSuccess)
-        e = hipStreamSynchronize(c->stream);
-    (void)hipFree(d);
-    LFI_HIP(c, e);
+    LFI_HIP(c, hipMemcpyAsync(got.data(), d + in_bytes, out_bytes, hipMemcpyDeviceToHost, c->stream));
+    LFI_HIP(c, hipStreamSynchronize(c->stream));
     // exact sums: every fp16 is an integer multiple of 2^-24; A ≤ 65504 (< 2^41 units), B ≤ 255 units, ≤ 256 terms: < 2^57 in units of 2^-48
     double worst = 0.0;
     bool representable = true;

@@ -26,44 +26,178 @@ thread_local std::string g_create_error;
 
 } // namespace
 
+// ---- owners: every device allocation, pinned buffer, event and stream below belongs to exactly one of these and goes with it --------------
+// (DESIGN.md §3 "Lifetimes" lists each one: who allocates it under which policy, which calls release it, whether the stream is drained first)
+
+// A device allocation (or, attached, a caller's memory that is only pointed at).  Freed with hipFree, which waits for the work in flight;
+// a site whose stream must be drained BEFORE the old allocation goes synchronises it itself, in front of reserve.
+class DeviceBuffer
+{
+public:
+    DeviceBuffer() = default;
+    DeviceBuffer(DeviceBuffer &&o) noexcept : p_(o.p_), bytes_(o.bytes_), owns_(o.owns_) { o.forget(); }
+    DeviceBuffer &operator=(DeviceBuffer &&o) noexcept
+    {
+        if(this != &o)
+        {
+            release();
+            p_ = o.p_, bytes_ = o.bytes_, owns_ = o.owns_;
+            o.forget();
+        }
+        return *this;
+    }
+    ~DeviceBuffer() { release(); }
+
+    // grow only: nothing happens while the capacity is at least `need` (a larger allocation serves smaller needs too)
+    hipError_t reserve(size_t need, bool *reallocated = nullptr) { return bytes_ >= need ? hipSuccess : replace(need, reallocated); }
+    // exact fit: a new allocation whenever the capacity differs from `need`
+    hipError_t fit(size_t need, bool *reallocated = nullptr) { return bytes_ == need ? hipSuccess : replace(need, reallocated); }
+    void attach(void *p, size_t bytes) { adopt(p, bytes), owns_ = false; } // the caller's memory: never freed here
+    void adopt(void *p, size_t bytes)                                      // an allocation made elsewhere (alloc_views), owned from now on
+    {
+        release();
+        p_ = p, bytes_ = bytes, owns_ = true;
+    }
+    void release()
+    {
+        if(owns_ && p_)
+            (void)hipFree(p_);
+        forget();
+    }
+
+    uint8_t *get() const { return static_cast<uint8_t *>(p_); }
+    template <class T>
+    T *as() const { return static_cast<T *>(p_); }
+    size_t bytes() const { return bytes_; } // capacity; of an attached buffer, the size the caller gave
+    bool owned() const { return owns_; }
+    explicit operator bool() const { return p_ != nullptr; }
+
+private:
+    void *p_ = nullptr;
+    size_t bytes_ = 0;
+    bool owns_ = false;
+
+    void forget() { p_ = nullptr, bytes_ = 0, owns_ = false; }
+    hipError_t replace(size_t need, bool *reallocated)
+    {
+        release();
+        if(reallocated)
+            *reallocated = true; // the old allocation and its contents are gone, whether or not the new one succeeds
+        if(hipError_t e = hipMalloc(&p_, need))
+        {
+            p_ = nullptr;
+            return e;
+        }
+        bytes_ = need, owns_ = true;
+        return hipSuccess;
+    }
+};
+
+// A page-locked host allocation
+class PinnedBuffer
+{
+public:
+    PinnedBuffer() = default;
+    PinnedBuffer(const PinnedBuffer &) = delete;
+    PinnedBuffer &operator=(const PinnedBuffer &) = delete;
+    ~PinnedBuffer() { release(); }
+
+    hipError_t reserve(size_t need) { return bytes_ >= need ? hipSuccess : replace(need); } // grow only
+    hipError_t fit(size_t need) { return bytes_ == need ? hipSuccess : replace(need); }     // exact fit
+    void release()
+    {
+        if(p_)
+            (void)hipHostFree(p_);
+        p_ = nullptr, bytes_ = 0;
+    }
+    uint8_t *get() const { return static_cast<uint8_t *>(p_); }
+    size_t bytes() const { return bytes_; }
+
+private:
+    void *p_ = nullptr;
+    size_t bytes_ = 0;
+
+    hipError_t replace(size_t need)
+    {
+        release();
+        if(hipError_t e = hipHostMalloc(&p_, need, hipHostMallocDefault))
+        {
+            p_ = nullptr;
+            return e;
+        }
+        bytes_ = need;
+        return hipSuccess;
+    }
+};
+
+// An event / a stream handle that destroys itself; ensure() creates it on first use.  Both convert to the bare handle for the runtime's calls.
+struct Event
+{
+    hipEvent_t h = nullptr;
+
+    Event() = default;
+    Event(const Event &) = delete;
+    Event &operator=(const Event &) = delete;
+    ~Event() { release(); }
+    hipError_t ensure(unsigned flags = hipEventDisableTiming) { return h ? hipSuccess : hipEventCreateWithFlags(&h, flags); }
+    void release()
+    {
+        if(h)
+            (void)hipEventDestroy(h);
+        h = nullptr;
+    }
+    operator hipEvent_t() const { return h; }
+};
+
+struct Stream
+{
+    hipStream_t h = nullptr;
+
+    Stream() = default;
+    Stream(const Stream &) = delete;
+    Stream &operator=(const Stream &) = delete;
+    ~Stream()
+    {
+        if(h)
+            (void)hipStreamDestroy(h);
+    }
+    hipError_t ensure() { return h ? hipSuccess : hipStreamCreateWithFlags(&h, hipStreamNonBlocking); }
+    hipError_t ensure_with_priority(int priority) { return h ? hipSuccess : hipStreamCreateWithPriority(&h, hipStreamNonBlocking, priority); }
+    operator hipStream_t() const { return h; }
+};
+
 // Two page-locked buffers, one event each: the host fills the current buffer, a copy out of it is enqueued on a stream, and the buffer is
 // not written again before that copy has run (two uses later) — uploads in stream order without draining the stream.
 struct StagingRing
 {
-    void *buf[2] = {nullptr, nullptr};
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    size_t bytes = 0; // capacity of each buffer
+    PinnedBuffer buf[2]; // of one capacity
+    Event ev[2];
     int slot = 0;
 
     // the current buffer, at least `need` bytes and free to write: both buffers grow once their copies have run; else this one's copy has run
     template <class T>
     hipError_t acquire(size_t need, T **out)
     {
-        if(bytes < need)
+        if(std::min(buf[0].bytes(), buf[1].bytes()) < need)
         {
             for(int i = 0; i < 2; i++)
             {
                 if(ev[i])
                     if(hipError_t e = hipEventSynchronize(ev[i]))
                         return e;
-                if(buf[i])
-                    (void)hipHostFree(buf[i]);
-                buf[i] = nullptr;
+                buf[i].release();
             }
-            bytes = 0;
             for(int i = 0; i < 2; i++)
             {
-                if(hipError_t e = hipHostMalloc(&buf[i], need, hipHostMallocDefault))
+                if(hipError_t e = ev[i].ensure())
                     return e;
-                if(!ev[i])
-                    if(hipError_t e = hipEventCreateWithFlags(&ev[i], hipEventDisableTiming))
-                        return e;
+                if(hipError_t e = buf[i].reserve(need))
+                    return e;
             }
-            bytes = need;
         }
         else if(hipError_t e = hipEventSynchronize(ev[slot]))
             return e;
-        *out = static_cast<T *>(buf[slot]);
+        *out = reinterpret_cast<T *>(buf[slot].get());
         return hipSuccess;
     }
 
@@ -78,20 +212,15 @@ struct StagingRing
 
     hipEvent_t committed() const { return ev[slot ^ 1]; } // the event the last commit recorded
 
-    void release()
+    void release() // waits for the copies out of the buffers
     {
         for(int i = 0; i < 2; i++)
         {
             if(ev[i])
                 (void)hipEventSynchronize(ev[i]);
-            if(buf[i])
-                (void)hipHostFree(buf[i]);
-            buf[i] = nullptr;
-            if(ev[i])
-                (void)hipEventDestroy(ev[i]);
-            ev[i] = nullptr;
+            buf[i].release();
+            ev[i].release();
         }
-        bytes = 0;
         slot = 0;
     }
 };
@@ -102,18 +231,16 @@ template <class T>
 struct ViewRows
 {
     bool set = false;
-    T *dev = nullptr;
-    size_t dev_bytes = 0;
+    DeviceBuffer dev;
     int pitch = 0;
     StagingRing ring;
+
+    const T *rows() const { return dev.as<const T>(); }
 
     void release() // the caller has drained the stream
     {
         set = false;
-        if(dev)
-            (void)hipFree(dev);
-        dev = nullptr;
-        dev_bytes = 0;
+        dev.release();
         ring.release();
     }
 };
@@ -122,52 +249,46 @@ struct lfi_ctx
 {
     int device = 0;
     int cu_count = 256;
-    hipStream_t own_stream = nullptr;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    hipEvent_t ev_order = nullptr; // orders the work of the stream a caller switches away from before the stream it switches to
-    // asynchronous uploads (lfi_upload_image_async) and downloads of lfi_render_stream: a copy stream
-    hipStream_t copy_stream = nullptr;
+    // The streams are declared first: members are destroyed in reverse order of declaration, so every buffer and event below goes before
+    // the streams do (lfi_destroy has synchronised all three and the device is current when `delete` runs).
+    Stream own_stream;
+    // asynchronous uploads (lfi_upload_image_async) and downloads of lfi_render_stream: a copy stream, created on first use
+    Stream copy_stream;
+    // side stream of the factored focus-map estimate (its small passes overlap the large ones), created on first use with high priority
+    Stream aux_stream;
+    hipStream_t stream = nullptr; // the compute stream: own_stream or the caller's (lfi_set_stream)
+    Event ev0, ev1;               // timing events (created with hipEventDefault)
+    Event ev_order;               // orders the work of the stream a caller switches away from before the stream it switches to
     bool uploads_pending = false; // copies enqueued on copy_stream that the compute stream has not been ordered after yet
-    hipEvent_t ev_uploads = nullptr;
-    // side stream of the factored focus-map estimate (its small passes overlap the large ones), created on first use
-    hipStream_t aux_stream = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_pad = nullptr, ev_join = nullptr;
+    Event ev_uploads;
+    Event ev_fork, ev_pad, ev_join;
     // the focus map's filter (map 0 → map 1) runs on the side stream behind the pick: an all-focus TEN_WM render, which reads map 0
     // (src/kernels.cu:430), does not wait for it; whatever reads map 1 or writes either map joins it first (join_filter)
-    hipEvent_t ev_pick = nullptr, ev_filter = nullptr;
+    Event ev_pick, ev_filter;
     bool filter_pending = false;
     int cols = 0, rows = 0, n = 0, width = 0, height = 0;
     // row window (lfi_set_row_window): input rows held / output rows rendered; the whole image by default
     int in_y0 = 0, in_rows = 0, out_y0 = 0, out_rows = 0;
     bool windowed = false;
-    uint8_t *grid = nullptr;
-    bool own_grid = false;
-    size_t grid_bytes = 0;
+    DeviceBuffer grid; // N input planes of in_rows rows: the library's own (lfi_set_grid / lfi_set_row_window) or attached (lfi_attach_grid)
     // lfi_release_inputs: the RGBA planes are gone, the derived planar copy is the only copy of the inputs (fixed-focus renders through
     // the planar kernels only); a later lfi_upload_image goes through a one-image staging plane straight into the copy
     bool inputs_released = false;
-    uint8_t *stage_plane = nullptr;
-    size_t stage_plane_bytes = 0;
+    DeviceBuffer stage_plane;
     // set by lfi_prepare for a render that reads the planar copy: from then on images that arrive (lfi_upload_image, lfi_fill_synthetic_images)
     // refresh their planes of the copy AT ONCE instead of at the next render — the first render after a load is then only a launch
     bool eager_planar = false;
-    uint8_t *maps = nullptr;
-    uint8_t *views = nullptr;
-    bool own_views = false;
-    size_t views_bytes = 0;
-    int out_layout = LFI_LAYOUT_RGBA;  // device layout of the views (lfi_set_output_layout)
-    uint8_t *rgba_scratch = nullptr;   // planar layout: RGBA planes of all views for the kernels that only write RGBA (converted after the launch)
-    size_t rgba_scratch_bytes = 0;
-    uint8_t *dl_plane = nullptr;       // planar layout: one RGBA plane that downloads expand a view into
-    size_t dl_plane_bytes = 0;
-    uint8_t *quilt = nullptr;          // lfi_download_quilt[_tiles]: the quilt's rows of tiles as one RGBA image (grows, kept)
-    size_t quilt_bytes = 0;
+    DeviceBuffer maps;                // focus maps 0 and 1, whole-image planes
+    DeviceBuffer views;               // the library's own (alloc_views) or attached (lfi_attach_views)
+    int out_layout = LFI_LAYOUT_RGBA; // device layout of the views (lfi_set_output_layout)
+    DeviceBuffer rgba_scratch;        // planar layout: RGBA planes of all views for the kernels that only write RGBA (converted after the launch)
+    DeviceBuffer dl_plane;            // planar layout: one RGBA plane that downloads expand a view into
+    DeviceBuffer quilt;               // lfi_download_quilt[_tiles]: the quilt's rows of tiles as one RGBA image (grows, kept)
     // parameter block
     bool have_params = false;
     int views_n = 0, k_pad = 0, v_pad = 0, n_focus_ids = 0;
-    void *param_blob = nullptr; // one allocation holding all parameter arrays
-    size_t param_blob_bytes = 0;
+    DeviceBuffer param_blob; // one allocation holding all parameter arrays, twice (see param_half)
+    size_t param_total = 0;  // bytes of ONE copy of the arrays as lfi_set_params laid them out: an equal total is replaced in place
     // lfi_set_params with an unchanged blob size (a focus sweep, a new trajectory with as many views): the new arrays go through the
     // staging ring and a stream-ordered copy — no synchronisation, no allocation
     StagingRing param_ring;
@@ -175,18 +296,15 @@ struct lfi_ctx
     // still running from the other (round 5: in stream order behind them it cost a fixed-focus sweep 22 µs per step, profiles/r05_notes.md)
     size_t param_half_stride = 0;
     int param_half = 0;
-    hipEvent_t ev_half_done[2] = {nullptr, nullptr}; // recorded on the compute stream when the context switches away from a half
+    Event ev_half_done[2]; // recorded on the compute stream when the context switches away from a half
     bool half_done_recorded[2] = {false, false};
     size_t blob_off_w16 = 0, blob_weights_bytes = 0; // the four weight arrays inside the blob (what lfi_render_stream replaces per block)
     // lfi_render_stream: page-locked staging for two blocks' weight arrays, a second set of views, events
-    uint8_t *stream_staging[2] = {nullptr, nullptr};
-    size_t stream_staging_bytes = 0;
-    uint8_t *views2 = nullptr;
-    size_t views2_bytes = 0;
-    hipEvent_t ev_h2d[2] = {nullptr, nullptr}, ev_rendered[2] = {nullptr, nullptr}, ev_d2h[2] = {nullptr, nullptr};
-    lfi::QualitySums *quality_sums = nullptr; // lfi_compare_view
-    uint8_t *quality_ref = nullptr;
-    size_t quality_ref_bytes = 0;
+    PinnedBuffer stream_staging[2];
+    DeviceBuffer views2;
+    Event ev_h2d[2], ev_rendered[2], ev_d2h[2];
+    DeviceBuffer quality_sums; // lfi_compare_view: one lfi::QualitySums, kept until the context goes
+    DeviceBuffer quality_ref;
     lfi_int2 *d_focused = nullptr;
     lfi_float2 *d_offsets = nullptr;
     uint16_t *d_w16 = nullptr, *d_w16s = nullptr;
@@ -198,14 +316,13 @@ struct lfi_ctx
     int radius[2] = {1, 1};
     int fo_min[2] = {0, 0}, fo_max[2] = {0, 0}; // bounds of the integer offsets
     uint32_t flags = 0;
-    float *prequant = nullptr;
+    DeviceBuffer prequant; // lfi_download_prequant: [3][H][W] floats
     std::vector<lfi_float2> h_focus_offsets; // offsets of the focus_map_ids images (host copy: sizes the padded planes)
     std::vector<lfi_float2> h_offsets;       // offsets of all images (host copy: row-window coverage checks of all-focus renders)
     // planar copy of the inputs for blend_planar (built on demand; valid while planar_version == grid_version)
-    uint8_t *planar = nullptr;
-    size_t planar_bytes = 0;
+    DeviceBuffer planar;
     int planar_pitch = 0, planar_padx = 0, planar_reach = 0; // bytes per plane row; left padding; the largest |x offset| it was built for
-    int32_t *d_planar_phase = nullptr;      // [LFI_MAX_IMAGES] per-image phase of the planar copy (device)
+    DeviceBuffer d_planar_phase;            // [LFI_MAX_IMAGES] int32 per-image phase of the planar copy (device)
     std::vector<int32_t> planar_phase;      // the same on the host
     StagingRing phase_ring;                 // a rebuild's phases go to the device in stream order, no host wait
     std::vector<lfi_int2> h_focused;        // the integer offsets of the current parameters (host copy)
@@ -217,8 +334,7 @@ struct lfi_ctx
     uint64_t grid_full_version = 1;
     std::vector<uint64_t> img_version;
     bool grid_tracked = true; // every write to the planes goes through this library (or is announced by lfi_grid_modified)
-    void *focus_ws = nullptr; // workspace of the factored focus-map estimate (plan, E, K), allocated on first use
-    size_t focus_ws_bytes = 0;
+    DeviceBuffer focus_ws; // workspace of the factored focus-map estimate (plan, E, K), allocated on first use
     // the estimate's padded copies of the sampled images (focus_pad, the tail of focus_ws) depend on the inputs and on a BOUND of the
     // candidates' shifts only: kept between lfi_focus_map calls (a focus sweep over one light field — BASELINE config 5 — pads once)
     // while pad_version == grid_version, the same images are sampled with the same block radius, and pad_shift still covers the request
@@ -229,21 +345,19 @@ struct lfi_ctx
     mutable const char *last_kernel = ""; // the blend kernel the last render launched (lfi_last_kernel_name)
     mutable unsigned sweep_launches = 0;  // blend_p3 / blend_planar alternate their sweep direction from launch to launch
     float derived_build_ms = 0.0f;        // duration of the last planar_build (measured by lfi_prepare only)
-    // per-view rows (stage_view_rows): cleared (not freed: renders in flight may still read them) by lfi_set_params / lfi_set_grid /
-    // lfi_set_row_window.  lfi_set_view_offsets: integer offsets for fixed-focus renders; lfi_set_view_float_offsets: float offsets for
+    // per-view rows (stage_view_rows): cleared (not freed: renders in flight may still read them) by lfi_set_params and
+    // lfi_set_row_window, freed by lfi_set_grid.  lfi_set_view_offsets: integer offsets for fixed-focus renders; lfi_set_view_float_offsets: float offsets for
     // all-focus renders, also kept as given, [views][N], for the row-window check at render time
     ViewRows<lfi_int2> view_offsets;
     int view_offsets_reach = 0;             // max |D.x| over the integer rows set: the padding the planar copy needs to serve them
     ViewRows<lfi_float2> view_float_offsets;
     std::vector<lfi_float2> h_view_float_offsets;
     // per-view focus maps (lfi_view_focus_maps): [views][2][H][W] RGBA, each view's pair laid out like maps 0 / 1; allocated on first use,
-    // freed with the context.  view_maps_set: all-focus renders over the float rows read them — cleared with the float rows
-    uint8_t *view_maps = nullptr;
-    size_t view_maps_bytes = 0;
+    // freed with the per-view rows.  view_maps_set: all-focus renders over the float rows read them — cleared with the float rows
+    DeviceBuffer view_maps;
     bool view_maps_set = false;
     // the estimate's own copy of the float rows, [V][N], and each view's ids in pad-slot order, [V][n_ids], staged through view_focus_ring
-    void *view_focus_args = nullptr;
-    size_t view_focus_args_bytes = 0;
+    DeviceBuffer view_focus_args;
     StagingRing view_focus_ring;
     int view_maps_padded = 0; // planes the last lfi_view_focus_maps padded (focus_pad slots)
     std::string err;
@@ -257,16 +371,21 @@ namespace {
 // ordinary memory rendered garbage (profiles/r03_notes.md section 6).  Round 3's own A/B (profiles/r03_views_memory_ab.txt) shows no gain
 // left from the placement outside box noise, so round 4 removed it together with the immortal pool: no allocation outlives its context.
 // Measurement builds: LFI_VIEWS_MEMORY=uncached|finegrained still selects the other kinds for A/B runs.
-hipError_t alloc_views(uint8_t **out, size_t bytes)
+hipError_t alloc_views(DeviceBuffer &out, size_t bytes)
 {
 #ifdef LFI_MEASUREMENT_BUILD
     const char *e = std::getenv("LFI_VIEWS_MEMORY");
-    if(e && std::strcmp(e, "uncached") == 0)
-        return hipExtMallocWithFlags(reinterpret_cast<void **>(out), bytes, hipDeviceMallocUncached);
-    if(e && std::strcmp(e, "finegrained") == 0)
-        return hipExtMallocWithFlags(reinterpret_cast<void **>(out), bytes, hipDeviceMallocFinegrained);
+    const unsigned kind = e && std::strcmp(e, "uncached") == 0 ? hipDeviceMallocUncached : e && std::strcmp(e, "finegrained") == 0 ? hipDeviceMallocFinegrained : 0;
+    if(kind)
+    {
+        void *p = nullptr;
+        const hipError_t err = hipExtMallocWithFlags(&p, bytes, kind);
+        if(err == hipSuccess)
+            out.adopt(p, bytes);
+        return err;
+    }
 #endif
-    return hipMalloc(reinterpret_cast<void **>(out), bytes);
+    return out.fit(bytes);
 }
 
 int fail(lfi_ctx *ctx, int code, const std::string &msg)
@@ -316,10 +435,8 @@ int join_filter(lfi_ctx *c)
 
 int ensure_copy_stream(lfi_ctx *c)
 {
-    if(c->copy_stream)
-        return LFI_OK;
-    LFI_HIP(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
-    LFI_HIP(c, hipEventCreateWithFlags(&c->ev_uploads, hipEventDisableTiming));
+    LFI_HIP(c, c->copy_stream.ensure());
+    LFI_HIP(c, c->ev_uploads.ensure());
     return LFI_OK;
 }
 
@@ -357,9 +474,9 @@ size_t out_plane_bytes(const lfi_ctx *c) // one view as stored on the device
 KernelArgs make_args(const lfi_ctx *c, int v0, int v1, int all_focus_method)
 {
     KernelArgs a{};
-    a.grid = c->grid;
-    a.views = c->views;
-    a.maps = c->maps;
+    a.grid = c->grid.get();
+    a.views = c->views.get();
+    a.maps = c->maps.get();
     a.focused = c->d_focused;
     a.offsets = c->d_offsets;
     a.w16 = c->d_w16;
@@ -384,7 +501,7 @@ KernelArgs make_args(const lfi_ctx *c, int v0, int v1, int all_focus_method)
     a.v1 = v1;
     a.n_focus_ids = c->n_focus_ids;
     a.planar = nullptr; // set by launch_blend when the copy is valid for this launch
-    a.planar_phase = c->d_planar_phase;
+    a.planar_phase = c->d_planar_phase.as<int32_t>();
     // blend_planar<STDF> (up to 64 images): chain bound N·2^-16 (half an ulp below 512 per fmaf: arithmetic) + the matrix core's accumulation
     // bound + 2^-11 of margin.  Accumulation bound: ANALYTIC by default since round 4, N·2^-15 (one whole fp16-product ulp per addend: true of
     // any accumulator that keeps ≥ 24 bits, nothing measured) — at these sizes the wider band costs nothing (tools/std_band_cost.py: config 2
@@ -492,12 +609,12 @@ bool image_changed_since(const lfi_ctx *c, int g, uint64_t version)
     return c->grid_full_version > version || c->img_version[g] > version;
 }
 
+// ---- what each API call invalidates (DESIGN.md §3 "Lifetimes" is the table these are checked against) -----------------------------------
+
 void free_params(lfi_ctx *c)
 {
-    if(c->param_blob)
-        (void)hipFree(c->param_blob);
-    c->param_blob = nullptr;
-    c->param_blob_bytes = 0;
+    c->param_blob.release();
+    c->param_total = 0;
     c->param_half = 0;
     c->half_done_recorded[0] = c->half_done_recorded[1] = false;
     c->have_params = false;
@@ -512,14 +629,8 @@ void free_view_rows(lfi_ctx *c)
     c->view_float_offsets.release();
     c->h_view_float_offsets.clear();
     c->view_maps_set = false;
-    if(c->view_maps)
-        (void)hipFree(c->view_maps);
-    c->view_maps = nullptr;
-    c->view_maps_bytes = 0;
-    if(c->view_focus_args)
-        (void)hipFree(c->view_focus_args);
-    c->view_focus_args = nullptr;
-    c->view_focus_args_bytes = 0;
+    c->view_maps.release();
+    c->view_focus_args.release();
     c->view_focus_ring.release();
 }
 
@@ -531,16 +642,11 @@ int stage_view_rows(lfi_ctx *ctx, ViewRows<T> &r, At at)
 {
     const int n = ctx->n, views = ctx->views_n, pitch = ctx->v_pad;
     const size_t bytes = sizeof(T) * (size_t)n * pitch;
-    if(bytes > r.dev_bytes)
+    if(r.dev.bytes() < bytes)
     {
         LFI_HIP(ctx, hipStreamSynchronize(ctx->stream)); // renders in flight may read the old buffer
         r.set = false;
-        if(r.dev)
-            (void)hipFree(r.dev);
-        r.dev = nullptr;
-        r.dev_bytes = 0;
-        LFI_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&r.dev), bytes));
-        r.dev_bytes = bytes;
+        LFI_HIP(ctx, r.dev.reserve(bytes));
     }
     T *staged = nullptr;
     LFI_HIP(ctx, r.ring.acquire(bytes, &staged));
@@ -548,7 +654,7 @@ int stage_view_rows(lfi_ctx *ctx, ViewRows<T> &r, At at)
     for(int v = 0; v < views; v++)
         for(int g = 0; g < n; g++)
             staged[(size_t)g * pitch + v] = at(v, g);
-    LFI_HIP(ctx, hipMemcpyAsync(r.dev, staged, bytes, hipMemcpyHostToDevice, ctx->stream));
+    LFI_HIP(ctx, hipMemcpyAsync(r.dev.get(), staged, bytes, hipMemcpyHostToDevice, ctx->stream));
     LFI_HIP(ctx, r.ring.commit(ctx->stream));
     r.pitch = pitch;
     r.set = true;
@@ -558,77 +664,45 @@ int stage_view_rows(lfi_ctx *ctx, ViewRows<T> &r, At at)
 // the copy of the parameter arrays that launches enqueued from now on read
 uint8_t *param_base(const lfi_ctx *c)
 {
-    return static_cast<uint8_t *>(c->param_blob) + (size_t)c->param_half * c->param_half_stride;
+    return c->param_blob.get() + (size_t)c->param_half * c->param_half_stride;
 }
 
 void free_views(lfi_ctx *c)
 {
-    if(c->own_views && c->views)
-        (void)hipFree(c->views);
-    c->views = nullptr;
-    c->own_views = false;
-    c->views_bytes = 0;
-    if(c->rgba_scratch)
-        (void)hipFree(c->rgba_scratch);
-    c->rgba_scratch = nullptr;
-    c->rgba_scratch_bytes = 0;
-    if(c->dl_plane)
-        (void)hipFree(c->dl_plane);
-    c->dl_plane = nullptr;
-    c->dl_plane_bytes = 0;
-    if(c->quilt)
-        (void)hipFree(c->quilt);
-    c->quilt = nullptr;
-    c->quilt_bytes = 0;
-    if(c->views2)
-        (void)hipFree(c->views2);
-    c->views2 = nullptr;
-    c->views2_bytes = 0;
-    if(c->quality_ref)
-        (void)hipFree(c->quality_ref);
-    c->quality_ref = nullptr;
-    c->quality_ref_bytes = 0;
+    c->views.release();
+    c->rgba_scratch.release();
+    c->dl_plane.release();
+    c->quilt.release();
+    c->views2.release();
+    c->quality_ref.release();
 }
 
 // the one-image staging plane of uploads after lfi_release_inputs is sized by the row window in force when it was allocated, and the eager
 // refresh lfi_prepare switched on belongs to the planes it was switched on for: both go whenever the input planes are replaced
 void drop_stage_plane(lfi_ctx *c)
 {
-    if(c->stage_plane)
-        (void)hipFree(c->stage_plane);
-    c->stage_plane = nullptr;
-    c->stage_plane_bytes = 0;
+    c->stage_plane.release();
     c->eager_planar = false;
+}
+
+// the input planes go (lfi_set_grid, lfi_set_row_window, lfi_attach_grid, lfi_release_inputs): an attached grid is only forgotten
+void drop_inputs(lfi_ctx *c)
+{
+    c->grid.release();
+    c->inputs_released = false;
+    drop_stage_plane(c);
 }
 
 void free_grid(lfi_ctx *c)
 {
-    if(c->own_grid && c->grid)
-        (void)hipFree(c->grid);
-    c->grid = nullptr;
-    c->own_grid = false;
-    c->grid_bytes = 0;
-    c->inputs_released = false;
-    drop_stage_plane(c);
-    if(c->maps)
-        (void)hipFree(c->maps);
-    c->maps = nullptr;
-    if(c->prequant)
-        (void)hipFree(c->prequant);
-    c->prequant = nullptr;
-    if(c->focus_ws)
-        (void)hipFree(c->focus_ws);
-    c->focus_ws = nullptr;
-    c->focus_ws_bytes = 0;
+    drop_inputs(c);
+    c->maps.release();
+    c->prequant.release();
+    c->focus_ws.release();
     c->pad_version = 0;
-    if(c->planar)
-        (void)hipFree(c->planar);
-    c->planar = nullptr;
-    c->planar_bytes = 0;
+    c->planar.release();
     c->planar_version = 0;
-    if(c->d_planar_phase)
-        (void)hipFree(c->d_planar_phase);
-    c->d_planar_phase = nullptr;
+    c->d_planar_phase.release();
     c->phase_ring.release();
 }
 

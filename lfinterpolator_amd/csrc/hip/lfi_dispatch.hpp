@@ -480,8 +480,8 @@ bool ensure_planar(lfi_ctx *c, bool tune = false, int min_reach = 0)
             int g1 = g + 1;
             while(g1 < c->n && image_changed_since(c, g1, c->planar_version))
                 g1++;
-            hipLaunchKernelGGL(lfi::planar_build, dim3((c->planar_pitch / 4 + 255) / 256, c->in_rows, g1 - g), dim3(256), 0, c->stream, c->grid,
-                               c->planar, c->width, c->in_rows, c->planar_pitch, c->planar_padx, c->d_planar_phase, g);
+            hipLaunchKernelGGL(lfi::planar_build, dim3((c->planar_pitch / 4 + 255) / 256, c->in_rows, g1 - g), dim3(256), 0, c->stream,
+                               c->grid.get(), c->planar.get(), c->width, c->in_rows, c->planar_pitch, c->planar_padx, c->d_planar_phase.as<int32_t>(), g);
             g = g1;
         }
         if(hipGetLastError() != hipSuccess)
@@ -507,25 +507,13 @@ bool ensure_planar(lfi_ctx *c, bool tune = false, int min_reach = 0)
     if(c->in_rows >= (1 << 24) || pitch >= (1 << 24) || (uint64_t)26 * c->in_rows * pitch >= (1ull << 32))
         return false;
     const size_t bytes = (size_t)c->n * 3 * c->in_rows * pitch; // the rows this context holds (a row window: band + halo)
-    if(bytes > c->planar_bytes) // (a larger allocation serves smaller planes too)
-    {
-        if(c->planar)
-            (void)hipFree(c->planar);
-        c->planar = nullptr;
-        c->planar_bytes = 0;
+    bool fresh = false;
+    const bool fits = c->planar.reserve(bytes, &fresh) == hipSuccess; // (a larger allocation serves smaller planes too)
+    if(fresh)
         c->planar_version = 0;
-        if(hipMalloc(reinterpret_cast<void **>(&c->planar), bytes) != hipSuccess)
-        {
-            (void)hipGetLastError(); // not enough memory for the copy: render from the RGBA planes
-            c->planar = nullptr;
-            return false;
-        }
-        c->planar_bytes = bytes;
-    }
-    if(!c->d_planar_phase && hipMalloc(reinterpret_cast<void **>(&c->d_planar_phase), sizeof(int32_t) * LFI_MAX_IMAGES) != hipSuccess)
+    if(!fits || c->d_planar_phase.reserve(sizeof(int32_t) * LFI_MAX_IMAGES) != hipSuccess)
     {
-        (void)hipGetLastError();
-        c->d_planar_phase = nullptr;
+        (void)hipGetLastError(); // not enough memory for the copy: render from the RGBA planes
         return false;
     }
     // the phases: (offset + padx + phase) ≡ 0 mod LFI_PLANAR_ALIGN for the offsets in use now.  They travel through the staging ring and a
@@ -542,14 +530,14 @@ bool ensure_planar(lfi_ctx *c, bool tune = false, int min_reach = 0)
     for(int g = 0; g < c->n; g++)
         staged[g] = c->planar_phase[g] = (LFI_PLANAR_ALIGN - ((c->h_focused[g].x + padx) & (LFI_PLANAR_ALIGN - 1))) & (LFI_PLANAR_ALIGN - 1);
     c->planar_version = 0;
-    if(hipMemcpyAsync(c->d_planar_phase, staged, sizeof(int32_t) * c->n, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+    if(hipMemcpyAsync(c->d_planar_phase.get(), staged, sizeof(int32_t) * c->n, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
        c->phase_ring.commit(c->stream) != hipSuccess)
         return false;
     c->planar_padx = padx;
     c->planar_reach = built_for;
     c->planar_pitch = pitch;
-    hipLaunchKernelGGL(lfi::planar_build, dim3((pitch / 4 + 255) / 256, c->in_rows, c->n), dim3(256), 0, c->stream, c->grid, c->planar,
-                       c->width, c->in_rows, pitch, padx, c->d_planar_phase, 0);
+    hipLaunchKernelGGL(lfi::planar_build, dim3((pitch / 4 + 255) / 256, c->in_rows, c->n), dim3(256), 0, c->stream, c->grid.get(),
+                       c->planar.get(), c->width, c->in_rows, pitch, padx, c->d_planar_phase.as<int32_t>(), 0);
     if(hipGetLastError() != hipSuccess)
         return false;
     c->planar_version = c->grid_version;
@@ -569,10 +557,10 @@ bool tune_planar_now(lfi_ctx *c)
 // the derived copy's addressing, for a launch that reads it (ensure_planar has made it valid)
 void set_planar_args(const lfi_ctx *c, KernelArgs &a)
 {
-    a.planar = c->planar;
+    a.planar = c->planar.get();
     a.planar_pitch = c->planar_pitch;
     a.planar_padx = c->planar_padx;
-    a.planar_phase = c->d_planar_phase; // allocated by ensure_planar, possibly just now
+    a.planar_phase = c->d_planar_phase.as<int32_t>(); // allocated by ensure_planar, possibly just now
 }
 
 // blend_p3 (TEN_WM from the planar copy): the planar views' epilogue, or (rgba_out: two to four chunks of images) the RGBA epilogue
@@ -755,17 +743,8 @@ int launch_blend(lfi_ctx *c, int method, int all_focus, const KernelArgs &a_in)
     const bool scratch = c->out_layout == LFI_LAYOUT_PLANAR_RGB && !r.planar_out;
     if(scratch)
     {
-        const size_t need = rgba_out_plane_bytes(c) * c->views_n;
-        if(c->rgba_scratch_bytes != need)
-        {
-            if(c->rgba_scratch)
-                (void)hipFree(c->rgba_scratch);
-            c->rgba_scratch = nullptr;
-            c->rgba_scratch_bytes = 0;
-            LFI_HIP(c, hipMalloc(reinterpret_cast<void **>(&c->rgba_scratch), need));
-            c->rgba_scratch_bytes = need;
-        }
-        a.views = c->rgba_scratch;
+        LFI_HIP(c, c->rgba_scratch.fit(rgba_out_plane_bytes(c) * c->views_n)); // nothing happens from the second launch on
+        a.views = c->rgba_scratch.get();
     }
     launch_route(c, a, all_focus != 0, r);
     LFI_HIP(c, hipGetLastError());
@@ -773,7 +752,7 @@ int launch_blend(lfi_ctx *c, int method, int all_focus, const KernelArgs &a_in)
     {
         const int pitch = view_pitch(c);
         hipLaunchKernelGGL(lfi::views_rgba_to_planar, dim3((pitch / 4 + 255) / 256, c->out_rows, a.v1 - a.v0), dim3(256), 0, c->stream,
-                           reinterpret_cast<const uint32_t *>(c->rgba_scratch + rgba_out_plane_bytes(c) * a.v0), a_in.views + out_plane_bytes(c) * a.v0,
+                           reinterpret_cast<const uint32_t *>(c->rgba_scratch.get() + rgba_out_plane_bytes(c) * a.v0), a_in.views + out_plane_bytes(c) * a.v0,
                            c->width, c->out_rows, pitch);
         LFI_HIP(c, hipGetLastError());
     }
@@ -825,7 +804,7 @@ int launch_view_rows(lfi_ctx *c, ViewRowsKind k, int method, int all_focus, cons
             return rc;
     KernelArgs a = a_in;
     if(view_maps)
-        a.maps = c->view_maps;
+        a.maps = c->view_maps.get();
     if(planar)
         set_planar_args(c, a);
     const bool ten = method == LFI_METHOD_TEN_WM, planar_out = c->out_layout == LFI_LAYOUT_PLANAR_RGB;
@@ -847,7 +826,7 @@ int launch_view_rows(lfi_ctx *c, ViewRowsKind k, int method, int all_focus, cons
         static const decltype(&blend_vfocus<false, false, false>) kernels[2][2][2] = {
             {{blend_vfocus<false, false, false>, blend_vfocus<false, false, true>}, {blend_vfocus<false, true, false>, blend_vfocus<false, true, true>}},
             {{blend_vfocus<true, false, false>, blend_vfocus<true, false, true>}, {blend_vfocus<true, true, false>, blend_vfocus<true, true, true>}}};
-        hipLaunchKernelGGL(kernels[ten][planar][planar_out], dim3((unsigned)blocks), dim3(256), 0, stream_of(c), a, c->view_offsets.dev,
+        hipLaunchKernelGGL(kernels[ten][planar][planar_out], dim3((unsigned)blocks), dim3(256), 0, stream_of(c), a, c->view_offsets.rows(),
                            c->view_offsets.pitch, n_chunks, tiles_x);
     }
     else
@@ -859,7 +838,7 @@ int launch_view_rows(lfi_ctx *c, ViewRowsKind k, int method, int all_focus, cons
             {{blend_vfocus_af<false, false>, blend_vfocus_af<false, true>}, {blend_vfocus_af<true, false>, blend_vfocus_af<true, true>}},
             {{blend_vfocus_af<false, false, VM_VIEWS, true>, blend_vfocus_af<false, true, VM_VIEWS, true>},
              {blend_vfocus_af<true, false, VM_VIEWS, true>, blend_vfocus_af<true, true, VM_VIEWS, true>}}};
-        hipLaunchKernelGGL(kernels[view_maps][ten][planar_out], dim3((unsigned)blocks), dim3(256), 0, stream_of(c), a, c->view_float_offsets.dev,
+        hipLaunchKernelGGL(kernels[view_maps][ten][planar_out], dim3((unsigned)blocks), dim3(256), 0, stream_of(c), a, c->view_float_offsets.rows(),
                            c->view_float_offsets.pitch, n_chunks, tiles_x);
     }
     LFI_HIP(c, hipGetLastError());
@@ -872,23 +851,14 @@ int rgba_plane_of_view(lfi_ctx *c, int v, const uint8_t **out)
 {
     if(c->out_layout != LFI_LAYOUT_PLANAR_RGB)
     {
-        *out = c->views + out_plane_bytes(c) * v;
+        *out = c->views.get() + out_plane_bytes(c) * v;
         return LFI_OK;
     }
-    const size_t need = rgba_out_plane_bytes(c);
-    if(c->dl_plane_bytes != need)
-    {
-        if(c->dl_plane)
-            (void)hipFree(c->dl_plane);
-        c->dl_plane = nullptr;
-        c->dl_plane_bytes = 0;
-        LFI_HIP(c, hipMalloc(reinterpret_cast<void **>(&c->dl_plane), need));
-        c->dl_plane_bytes = need;
-    }
+    LFI_HIP(c, c->dl_plane.fit(rgba_out_plane_bytes(c)));
     hipLaunchKernelGGL(lfi::view_planar_to_rgba, dim3(((c->width + 3) / 4 + 255) / 256, c->out_rows), dim3(256), 0, c->stream,
-                       c->views + out_plane_bytes(c) * v, reinterpret_cast<uint32_t *>(c->dl_plane), c->width, c->out_rows, view_pitch(c));
+                       c->views.get() + out_plane_bytes(c) * v, c->dl_plane.as<uint32_t>(), c->width, c->out_rows, view_pitch(c));
     LFI_HIP(c, hipGetLastError());
-    *out = c->dl_plane;
+    *out = c->dl_plane.get();
     return LFI_OK;
 }
 

@@ -133,17 +133,12 @@ int launch_focus_factored(lfi_ctx *ctx, const KernelArgs &a, FocusJob &job, bool
     const size_t o_deltas = carve(sizeof(int64_t) * lfi::FOCUS_STEPS * lfi::FOCUS_MAX_IDS);
     const size_t o_patches = carve(sizeof(lfi::FocusPatch) * (lfi::FOCUS_STEPS / 4) * lfi::FOCUS_MAX_IDS);
     const size_t o_pad = carve(pad_bytes);
-    if(ctx->focus_ws_bytes < at) // a larger workspace serves smaller geometries too
-    {
-        if(ctx->focus_ws)
-            (void)hipFree(ctx->focus_ws);
-        ctx->focus_ws = nullptr;
-        ctx->focus_ws_bytes = 0;
+    bool fresh = false;
+    const hipError_t focus_ws_reserve = ctx->focus_ws.reserve(at, &fresh); // a larger workspace serves smaller geometries too
+    if(fresh)
         ctx->pad_version = 0;
-        LFI_HIP(ctx, hipMalloc(&ctx->focus_ws, at));
-        ctx->focus_ws_bytes = at;
-    }
-    uint8_t *base = static_cast<uint8_t *>(ctx->focus_ws);
+    LFI_HIP(ctx, focus_ws_reserve);
+    uint8_t *base = ctx->focus_ws.get();
     w.shifts = reinterpret_cast<int32_t *>(base + o_shifts);
     w.badx = reinterpret_cast<uint32_t *>(base + o_badx);
     w.bady = reinterpret_cast<uint32_t *>(base + o_bady);
@@ -172,10 +167,10 @@ int launch_focus_factored(lfi_ctx *ctx, const KernelArgs &a, FocusJob &job, bool
     {
         int prio_low = 0, prio_high = 0; // numerically lower = higher priority: the small passes should not queue behind the big ones
         LFI_HIP(ctx, hipDeviceGetStreamPriorityRange(&prio_low, &prio_high));
-        LFI_HIP(ctx, hipStreamCreateWithPriority(&ctx->aux_stream, hipStreamNonBlocking, prio_high));
-        LFI_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
-        LFI_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_pad, hipEventDisableTiming));
-        LFI_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming));
+        LFI_HIP(ctx, ctx->aux_stream.ensure_with_priority(prio_high));
+        LFI_HIP(ctx, ctx->ev_fork.ensure());
+        LFI_HIP(ctx, ctx->ev_pad.ensure());
+        LFI_HIP(ctx, ctx->ev_join.ensure());
     }
     hipStream_t st = ctx->stream;
     hipStream_t aux = ctx->aux_stream;

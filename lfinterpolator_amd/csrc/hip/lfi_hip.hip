@@ -57,11 +57,10 @@ int lfi_create(int device, lfi_ctx **out_ctx)
     lfi_ctx *c = new lfi_ctx();
     c->device = device;
     c->cu_count = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    if(hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking) != hipSuccess ||
-       hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess ||
-       hipEventCreateWithFlags(&c->ev_order, hipEventDisableTiming) != hipSuccess)
+    if(hipSetDevice(device) != hipSuccess || c->own_stream.ensure() != hipSuccess || c->ev0.ensure(hipEventDefault) != hipSuccess ||
+       c->ev1.ensure(hipEventDefault) != hipSuccess || c->ev_order.ensure() != hipSuccess)
     {
-        delete c;
+        delete c; // releases what was created
         return fail(nullptr, LFI_EHIP, "could not create stream/events on the device");
     }
     c->stream = c->own_stream;
@@ -73,58 +72,13 @@ int lfi_destroy(lfi_ctx *ctx)
 {
     if(!ctx)
         return LFI_EINVAL;
-    (void)hipSetDevice(ctx->device);
+    (void)hipSetDevice(ctx->device); // stays current while the members go
     (void)hipStreamSynchronize(ctx->stream);
     if(ctx->aux_stream)
         (void)hipStreamSynchronize(ctx->aux_stream); // a focus-map filter may still run there
-    ctx->filter_pending = false;
-    free_params(ctx);
-    ctx->param_ring.release();
-    free_view_rows(ctx);
-    free_views(ctx);
-    free_grid(ctx);
-    if(ctx->ev0)
-        (void)hipEventDestroy(ctx->ev0);
-    if(ctx->ev1)
-        (void)hipEventDestroy(ctx->ev1);
-    if(ctx->ev_order)
-        (void)hipEventDestroy(ctx->ev_order);
     if(ctx->copy_stream)
-    {
         (void)hipStreamSynchronize(ctx->copy_stream);
-        (void)hipStreamDestroy(ctx->copy_stream);
-    }
-    for(int i = 0; i < 2; i++)
-    {
-        if(ctx->stream_staging[i])
-            (void)hipHostFree(ctx->stream_staging[i]);
-        if(ctx->ev_h2d[i])
-            (void)hipEventDestroy(ctx->ev_h2d[i]);
-        if(ctx->ev_rendered[i])
-            (void)hipEventDestroy(ctx->ev_rendered[i]);
-        if(ctx->ev_d2h[i])
-            (void)hipEventDestroy(ctx->ev_d2h[i]);
-        if(ctx->ev_half_done[i])
-            (void)hipEventDestroy(ctx->ev_half_done[i]);
-    }
-    if(ctx->quality_sums)
-        (void)hipFree(ctx->quality_sums);
-    if(ctx->ev_uploads)
-        (void)hipEventDestroy(ctx->ev_uploads);
-    if(ctx->ev_fork)
-        (void)hipEventDestroy(ctx->ev_fork);
-    if(ctx->ev_pad)
-        (void)hipEventDestroy(ctx->ev_pad);
-    if(ctx->ev_join)
-        (void)hipEventDestroy(ctx->ev_join);
-    if(ctx->ev_pick)
-        (void)hipEventDestroy(ctx->ev_pick);
-    if(ctx->ev_filter)
-        (void)hipEventDestroy(ctx->ev_filter);
-    if(ctx->aux_stream)
-        (void)hipStreamDestroy(ctx->aux_stream);
-    if(ctx->own_stream)
-        (void)hipStreamDestroy(ctx->own_stream);
+    // every buffer, event and stream is a member that releases itself, the streams last (lfi_context.hpp)
     delete ctx;
     return LFI_OK;
 }
@@ -180,13 +134,11 @@ int lfi_set_grid(lfi_ctx *ctx, int cols, int rows, int width, int height)
     ctx->in_y0 = ctx->out_y0 = 0;
     ctx->in_rows = ctx->out_rows = height;
     ctx->windowed = false;
-    ctx->grid_bytes = plane_bytes(ctx) * ctx->n;
-    LFI_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->grid), ctx->grid_bytes));
-    ctx->own_grid = true;
+    LFI_HIP(ctx, ctx->grid.fit(plane_bytes(ctx) * ctx->n));
     touch_all(ctx);
     ctx->grid_tracked = true;
-    LFI_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->maps), plane_bytes(ctx) * 2));
-    LFI_HIP(ctx, hipMemsetAsync(ctx->maps, 0, plane_bytes(ctx) * 2, ctx->stream));
+    LFI_HIP(ctx, ctx->maps.fit(plane_bytes(ctx) * 2));
+    LFI_HIP(ctx, hipMemsetAsync(ctx->maps.get(), 0, plane_bytes(ctx) * 2, ctx->stream));
     LFI_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return LFI_OK;
 }
@@ -206,20 +158,13 @@ int lfi_set_row_window(lfi_ctx *ctx, int out_y0, int out_y1, int in_y0, int in_y
     LFI_HIP(ctx, hipStreamSynchronize(ctx->stream));
     free_params(ctx);
     free_views(ctx);
-    if(ctx->own_grid && ctx->grid)
-        (void)hipFree(ctx->grid);
-    ctx->grid = nullptr;
-    ctx->own_grid = false;
-    ctx->inputs_released = false;
-    drop_stage_plane(ctx); // sized for the window in force when it was allocated (a larger window overflowed it)
+    drop_inputs(ctx); // the staging plane too: sized for the window in force when it was allocated (a larger window overflowed it)
     ctx->in_y0 = in_y0;
     ctx->in_rows = in_y1 - in_y0;
     ctx->out_y0 = out_y0;
     ctx->out_rows = out_y1 - out_y0;
     ctx->windowed = !(in_y0 == 0 && in_y1 == ctx->height && out_y0 == 0 && out_y1 == ctx->height);
-    ctx->grid_bytes = in_plane_bytes(ctx) * ctx->n;
-    LFI_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->grid), ctx->grid_bytes));
-    ctx->own_grid = true;
+    LFI_HIP(ctx, ctx->grid.fit(in_plane_bytes(ctx) * ctx->n));
     touch_all(ctx);
     ctx->grid_tracked = true;
     return LFI_OK;
@@ -240,25 +185,19 @@ int lfi_upload_image(lfi_ctx *ctx, int g, const uint8_t *rgba, size_t pitch_byte
     if(ctx->inputs_released)
     {
         // the RGBA planes are gone: the image goes through a one-image staging plane straight into its planes of the planar copy
-        if(ctx->stage_plane && ctx->stage_plane_bytes < in_plane_bytes(ctx))
-            drop_stage_plane(ctx);
-        if(!ctx->stage_plane)
-        {
-            LFI_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->stage_plane), in_plane_bytes(ctx)));
-            ctx->stage_plane_bytes = in_plane_bytes(ctx);
-        }
-        LFI_HIP(ctx, hipMemcpy2DAsync(ctx->stage_plane, (size_t)ctx->width * 4, rgba + (size_t)ctx->in_y0 * pitch_bytes, pitch_bytes, (size_t)ctx->width * 4,
+        LFI_HIP(ctx, ctx->stage_plane.reserve(in_plane_bytes(ctx))); // (dropped with the row window it was sized for: drop_stage_plane)
+        LFI_HIP(ctx, hipMemcpy2DAsync(ctx->stage_plane.get(), (size_t)ctx->width * 4, rgba + (size_t)ctx->in_y0 * pitch_bytes, pitch_bytes, (size_t)ctx->width * 4,
                                       ctx->in_rows, hipMemcpyHostToDevice, ctx->stream));
         // planar_build reads image g at grid + g·plane: hand it a base that puts the staging plane there
         hipLaunchKernelGGL(lfi::planar_build, dim3((ctx->planar_pitch / 4 + 255) / 256, ctx->in_rows, 1), dim3(256), 0, ctx->stream,
-                           ctx->stage_plane - in_plane_bytes(ctx) * (size_t)g, ctx->planar, ctx->width, ctx->in_rows, ctx->planar_pitch, ctx->planar_padx,
-                           ctx->d_planar_phase, g);
+                           ctx->stage_plane.get() - in_plane_bytes(ctx) * (size_t)g, ctx->planar.get(), ctx->width, ctx->in_rows, ctx->planar_pitch,
+                           ctx->planar_padx, ctx->d_planar_phase.as<int32_t>(), g);
         LFI_HIP(ctx, hipGetLastError());
         LFI_HIP(ctx, hipStreamSynchronize(ctx->stream));
         return LFI_OK;
     }
     // rgba addresses row 0 of the whole image; only the rows this context holds are copied
-    LFI_HIP(ctx, hipMemcpy2DAsync(ctx->grid + in_plane_bytes(ctx) * g, (size_t)ctx->width * 4, rgba + (size_t)ctx->in_y0 * pitch_bytes,
+    LFI_HIP(ctx, hipMemcpy2DAsync(ctx->grid.get() + in_plane_bytes(ctx) * g, (size_t)ctx->width * 4, rgba + (size_t)ctx->in_y0 * pitch_bytes,
                                   pitch_bytes, (size_t)ctx->width * 4, ctx->in_rows, hipMemcpyHostToDevice, ctx->stream));
     LFI_HIP(ctx, hipStreamSynchronize(ctx->stream));
     touch_images(ctx, g, g + 1);
@@ -292,7 +231,7 @@ int lfi_upload_image_async(lfi_ctx *ctx, int g, const uint8_t *rgba, size_t pitc
     // returns (≈45–50 GB/s of host time on this platform — a staging ring of our own with a host memcpy in front measured
     // 20 GB/s, profiles/r02_upload_time.txt), so the caller's buffer is free on return either way.
     const size_t row_bytes = (size_t)ctx->width * 4;
-    LFI_HIP(ctx, hipMemcpy2DAsync(ctx->grid + in_plane_bytes(ctx) * g, row_bytes, rgba + (size_t)ctx->in_y0 * pitch_bytes, pitch_bytes, row_bytes,
+    LFI_HIP(ctx, hipMemcpy2DAsync(ctx->grid.get() + in_plane_bytes(ctx) * g, row_bytes, rgba + (size_t)ctx->in_y0 * pitch_bytes, pitch_bytes, row_bytes,
                                   ctx->in_rows, hipMemcpyHostToDevice, ctx->copy_stream));
     ctx->uploads_pending = true;
     touch_images(ctx, g, g + 1);
@@ -327,13 +266,8 @@ int lfi_attach_grid(lfi_ctx *ctx, void *device_ptr, size_t bytes)
     if(int rc = lfi_upload_wait(ctx))
         return rc;
     LFI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if(ctx->own_grid && ctx->grid)
-        (void)hipFree(ctx->grid);
-    ctx->grid = static_cast<uint8_t *>(device_ptr);
-    ctx->own_grid = false;
-    ctx->inputs_released = false;
-    drop_stage_plane(ctx);
-    ctx->grid_bytes = bytes;
+    drop_inputs(ctx);
+    ctx->grid.attach(device_ptr, bytes);
     touch_all(ctx);
     ctx->grid_tracked = false; // the caller writes this buffer itself: see lfi_grid_modified
     return LFI_OK;
@@ -390,7 +324,7 @@ int lfi_broadcast_grid(lfi_ctx *const *ctxs, int n, int root)
             rc = -1;
             break;
         }
-        rc = nc.Broadcast(r0->grid, ctxs[i]->grid, bytes, NCCL_UINT8, root, comms[i], ctxs[i]->stream);
+        rc = nc.Broadcast(r0->grid.get(), ctxs[i]->grid.get(), bytes, NCCL_UINT8, root, comms[i], ctxs[i]->stream);
     }
     const int rc_end = nc.GroupEnd();
     if(rc != 0 || rc_end != 0)
@@ -427,11 +361,7 @@ int lfi_release_inputs(lfi_ctx *ctx)
     if(!ensure_planar(ctx, true))
         return fail(ctx, LFI_EINVAL, "the planar copy of the inputs cannot be built (inputs the library does not track, absurd offsets, out of memory)");
     LFI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if(ctx->own_grid && ctx->grid)
-        LFI_HIP(ctx, hipFree(ctx->grid));
-    ctx->grid = nullptr;
-    ctx->own_grid = false;
-    ctx->grid_bytes = 0;
+    drop_inputs(ctx);
     ctx->inputs_released = true;
     return LFI_OK;
 }
@@ -444,7 +374,7 @@ int lfi_grid_device_ptr(lfi_ctx *ctx, void **out_ptr, size_t *out_bytes)
         return fail(ctx, LFI_EINVAL, "the RGBA inputs were released (lfi_release_inputs): lfi_set_grid and upload the images again");
     if(ctx->uploads_pending && bind(ctx) == LFI_OK)
         (void)lfi_upload_wait(ctx); // the caller is about to read or write the planes itself
-    *out_ptr = ctx->grid;
+    *out_ptr = ctx->grid.get();
     if(out_bytes)
         *out_bytes = ctx->grid ? in_plane_bytes(ctx) * ctx->n : 0;
     ctx->grid_tracked = false; // the caller may write through the pointer: see lfi_grid_modified
@@ -482,7 +412,7 @@ int lfi_fill_synthetic_images(lfi_ctx *ctx, uint32_t seed, int g0, int g1)
     if(int rc = join_uploads(ctx))
         return rc;
     touch_images(ctx, g0, g1);
-    hipLaunchKernelGGL(lfi::fill_synthetic, dim3(256 * 16), dim3(256), 0, ctx->stream, ctx->grid, g0, g1 - g0, ctx->width,
+    hipLaunchKernelGGL(lfi::fill_synthetic, dim3(256 * 16), dim3(256), 0, ctx->stream, ctx->grid.get(), g0, g1 - g0, ctx->width,
                        ctx->in_rows, ctx->in_y0, seed);
     LFI_HIP(ctx, hipGetLastError());
     if(ctx->eager_planar && ctx->have_params)
@@ -501,7 +431,7 @@ int lfi_fill_synthetic_scene(lfi_ctx *ctx, uint32_t seed)
     if(int rc = bind(ctx))
         return rc;
     touch_all(ctx);
-    hipLaunchKernelGGL(lfi::fill_scene, dim3(256 * 16), dim3(256), 0, ctx->stream, ctx->grid, ctx->d_offsets, ctx->n, ctx->width, ctx->in_rows,
+    hipLaunchKernelGGL(lfi::fill_scene, dim3(256 * 16), dim3(256), 0, ctx->stream, ctx->grid.get(), ctx->d_offsets, ctx->n, ctx->width, ctx->in_rows,
                        ctx->in_y0, seed, ctx->focus, ctx->range);
     LFI_HIP(ctx, hipGetLastError());
     return LFI_OK;
@@ -558,14 +488,13 @@ int lfi_set_params(lfi_ctx *ctx, const lfi_params *p)
     // Same blob size as the arrays in place (and as many views: nothing else to reallocate): stage in page-locked memory and copy in
     // stream order — launches already enqueued keep reading the old arrays, later ones see the new; the context's stream is not
     // drained.  Otherwise (first call, another view count or grid): synchronise, reallocate, copy synchronously.
-    const bool in_place = ctx->param_blob && ctx->param_blob_bytes == total && !views_changed && ctx->views;
+    const bool in_place = ctx->param_blob && ctx->param_total == total && !views_changed && ctx->views;
     std::vector<uint8_t> blob_pageable;
     uint8_t *blob_ptr = nullptr;
     if(in_place)
     {
         for(int i = 0; i < 2; i++)
-            if(!ctx->ev_half_done[i])
-                LFI_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_half_done[i], hipEventDisableTiming));
+            LFI_HIP(ctx, ctx->ev_half_done[i].ensure());
         LFI_HIP(ctx, ctx->param_ring.acquire(total, &blob_ptr));
         std::memset(blob_ptr, 0, total);
     }
@@ -608,7 +537,7 @@ int lfi_set_params(lfi_ctx *ctx, const lfi_params *p)
         ctx->half_done_recorded[cur] = true;
         if(ctx->half_done_recorded[next])
             LFI_HIP(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->ev_half_done[next], 0));
-        LFI_HIP(ctx, hipMemcpyAsync(static_cast<uint8_t *>(ctx->param_blob) + (size_t)next * ctx->param_half_stride, blob.data(), total, hipMemcpyHostToDevice,
+        LFI_HIP(ctx, hipMemcpyAsync(ctx->param_blob.get() + (size_t)next * ctx->param_half_stride, blob.data(), total, hipMemcpyHostToDevice,
                                     ctx->copy_stream));
         LFI_HIP(ctx, ctx->param_ring.commit(ctx->copy_stream));
         LFI_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->param_ring.committed(), 0));
@@ -618,9 +547,9 @@ int lfi_set_params(lfi_ctx *ctx, const lfi_params *p)
     {
         free_params(ctx);
         ctx->param_half_stride = (total + 255) / 256 * 256;
-        LFI_HIP(ctx, hipMalloc(&ctx->param_blob, 2 * ctx->param_half_stride));
-        ctx->param_blob_bytes = total;
-        LFI_HIP(ctx, hipMemcpy(ctx->param_blob, blob.data(), total, hipMemcpyHostToDevice));
+        LFI_HIP(ctx, ctx->param_blob.fit(2 * ctx->param_half_stride));
+        ctx->param_total = total;
+        LFI_HIP(ctx, hipMemcpy(ctx->param_blob.get(), blob.data(), total, hipMemcpyHostToDevice));
     }
     uint8_t *base = param_base(ctx);
     ctx->d_focused = reinterpret_cast<lfi_int2 *>(base + off_focused);
@@ -659,14 +588,12 @@ int lfi_set_params(lfi_ctx *ctx, const lfi_params *p)
 
     if(views_changed || !ctx->views)
     {
-        const bool was_attached = ctx->views && !ctx->own_views;
-        if(!(was_attached && ctx->views_bytes >= out_plane_bytes(ctx) * V))
+        const bool was_attached = ctx->views && !ctx->views.owned();
+        if(!(was_attached && ctx->views.bytes() >= out_plane_bytes(ctx) * V))
         {
             free_views(ctx);
-            ctx->views_bytes = out_plane_bytes(ctx) * V;
             ctx->have_params = false; // until the views exist: a failed allocation must not leave renders a null pointer to store through
-            LFI_HIP(ctx, alloc_views(&ctx->views, ctx->views_bytes));
-            ctx->own_views = true;
+            LFI_HIP(ctx, alloc_views(ctx->views, out_plane_bytes(ctx) * V));
         }
     }
     ctx->have_params = true;
@@ -761,8 +688,7 @@ int lfi_attach_views(lfi_ctx *ctx, void *device_ptr, size_t bytes)
         return rc;
     LFI_HIP(ctx, hipStreamSynchronize(ctx->stream));
     free_views(ctx);
-    ctx->views = static_cast<uint8_t *>(device_ptr);
-    ctx->views_bytes = bytes;
+    ctx->views.attach(device_ptr, bytes);
     return LFI_OK;
 }
 
@@ -783,10 +709,8 @@ int lfi_set_output_layout(lfi_ctx *ctx, int layout)
     ctx->out_layout = layout;
     if(ctx->have_params)
     {
-        ctx->views_bytes = out_plane_bytes(ctx) * ctx->views_n;
         ctx->have_params = false; // a failed allocation leaves the context without parameters (lfi_set_params again), not with null views
-        LFI_HIP(ctx, alloc_views(&ctx->views, ctx->views_bytes));
-        ctx->own_views = true;
+        LFI_HIP(ctx, alloc_views(ctx->views, out_plane_bytes(ctx) * ctx->views_n));
         ctx->have_params = true;
     }
     return LFI_OK;
@@ -818,7 +742,7 @@ int lfi_views_device_ptr(lfi_ctx *ctx, void **out_ptr, size_t *out_bytes)
 {
     if(!ctx || !out_ptr)
         return LFI_EINVAL;
-    *out_ptr = ctx->views;
+    *out_ptr = ctx->views.get();
     if(out_bytes)
         *out_bytes = ctx->views ? out_plane_bytes(ctx) * ctx->views_n : 0;
     return LFI_OK;
@@ -916,11 +840,8 @@ int lfi_focus_map(lfi_ctx *ctx)
         // map 1 = the box mean of map 0 (FocusMap::filter, src/kernels.cu:260-280), on the side stream: the reference's Tensors::process<true>
         // reads map 0 (src/kernels.cu:430), so a TEN_WM all-focus render enqueued next runs BESIDE the filter (0.13 ms at 4K) instead of
         // behind it; everything that reads map 1 or writes a map joins the side stream first (join_filter)
-        if(!ctx->ev_pick)
-        {
-            LFI_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_pick, hipEventDisableTiming));
-            LFI_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_filter, hipEventDisableTiming));
-        }
+        LFI_HIP(ctx, ctx->ev_pick.ensure());
+        LFI_HIP(ctx, ctx->ev_filter.ensure());
         LFI_HIP(ctx, hipEventRecord(ctx->ev_pick, ctx->stream));
         LFI_HIP(ctx, hipStreamWaitEvent(ctx->aux_stream, ctx->ev_pick, 0));
         launch_focus_filter(ctx, a, ctx->aux_stream);
@@ -938,16 +859,11 @@ int lfi_focus_map(lfi_ctx *ctx)
 static int ensure_view_maps(lfi_ctx *ctx)
 {
     const size_t need = plane_bytes(ctx) * 2 * ctx->views_n;
-    if(ctx->view_maps_bytes >= need)
+    if(ctx->view_maps.bytes() >= need)
         return LFI_OK;
     LFI_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ctx->view_maps_set = false;
-    if(ctx->view_maps)
-        (void)hipFree(ctx->view_maps);
-    ctx->view_maps = nullptr;
-    ctx->view_maps_bytes = 0;
-    LFI_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->view_maps), need));
-    ctx->view_maps_bytes = need;
+    LFI_HIP(ctx, ctx->view_maps.reserve(need));
     return LFI_OK;
 }
 
@@ -1032,24 +948,19 @@ int lfi_view_focus_maps(lfi_ctx *ctx, const int32_t *focus_ids_vk, int views, in
     // the estimate's arrays on the device: the float rows as [V][N] (the render's copy is [N][v_pad]) and the slot-ordered ids [V][n_ids]
     const size_t off_bytes = sizeof(lfi_float2) * (size_t)V * n, ids_at = (off_bytes + 255) / 256 * 256;
     const size_t total = ids_at + sizeof(int32_t) * (size_t)V * n_ids;
-    if(ctx->view_focus_args_bytes < total)
+    if(ctx->view_focus_args.bytes() < total)
     {
         LFI_HIP(ctx, hipStreamSynchronize(ctx->stream)); // an estimate in flight may read the old buffer
-        if(ctx->view_focus_args)
-            (void)hipFree(ctx->view_focus_args);
-        ctx->view_focus_args = nullptr;
-        ctx->view_focus_args_bytes = 0;
-        LFI_HIP(ctx, hipMalloc(&ctx->view_focus_args, total));
-        ctx->view_focus_args_bytes = total;
+        LFI_HIP(ctx, ctx->view_focus_args.reserve(total));
     }
     uint8_t *staged = nullptr;
     LFI_HIP(ctx, ctx->view_focus_ring.acquire(total, &staged));
     std::memcpy(staged, ctx->h_view_float_offsets.data(), off_bytes);
     std::memcpy(staged + ids_at, slots.data(), sizeof(int32_t) * slots.size());
-    LFI_HIP(ctx, hipMemcpyAsync(ctx->view_focus_args, staged, total, hipMemcpyHostToDevice, ctx->stream));
+    LFI_HIP(ctx, hipMemcpyAsync(ctx->view_focus_args.get(), staged, total, hipMemcpyHostToDevice, ctx->stream));
     LFI_HIP(ctx, ctx->view_focus_ring.commit(ctx->stream));
-    const lfi_float2 *d_off = static_cast<const lfi_float2 *>(ctx->view_focus_args);
-    const int32_t *d_ids = reinterpret_cast<const int32_t *>(static_cast<const uint8_t *>(ctx->view_focus_args) + ids_at);
+    const lfi_float2 *d_off = ctx->view_focus_args.as<const lfi_float2>();
+    const int32_t *d_ids = reinterpret_cast<const int32_t *>(ctx->view_focus_args.get() + ids_at);
     ctx->view_maps_set = false; // until every view's pair is enqueued
     KernelArgs a = make_args(ctx, 0, V, LFI_METHOD_STD);
     a.n_focus_ids = n_ids;
@@ -1058,7 +969,7 @@ int lfi_view_focus_maps(lfi_ctx *ctx, const int32_t *focus_ids_vk, int views, in
     {
         a.offsets = d_off + (size_t)v * n;
         a.focus_ids = d_ids + (size_t)v * n_ids;
-        a.maps = ctx->view_maps + plane_bytes(ctx) * 2 * v;
+        a.maps = ctx->view_maps.get() + plane_bytes(ctx) * 2 * v;
         FocusJob job;
         job.offsets = sampled.data() + (size_t)v * n_ids;
         job.ids = slots.data() + (size_t)v * n_ids;
@@ -1074,7 +985,7 @@ int lfi_view_focus_maps(lfi_ctx *ctx, const int32_t *focus_ids_vk, int views, in
         padded += job.padded;
     }
     // maps 1 of all views by one launch, on the compute stream (renders of either map follow in stream order)
-    a.maps = ctx->view_maps;
+    a.maps = ctx->view_maps.get();
     launch_focus_filter(ctx, a, ctx->stream, V);
     LFI_HIP(ctx, hipGetLastError());
     ctx->view_maps_padded = padded;
@@ -1085,11 +996,11 @@ int lfi_view_focus_maps(lfi_ctx *ctx, const int32_t *focus_ids_vk, int views, in
 // view v's map k on the device: the per-view maps of the current parameters
 static int view_map_plane(lfi_ctx *ctx, int v, int k, const void *host, size_t pitch_bytes, uint8_t **out)
 {
-    if(!ctx->have_params || !ctx->view_maps || ctx->view_maps_bytes < plane_bytes(ctx) * 2 * ctx->views_n)
+    if(!ctx->have_params || !ctx->view_maps || ctx->view_maps.bytes() < plane_bytes(ctx) * 2 * ctx->views_n)
         return fail(ctx, LFI_EINVAL, "no per-view focus maps (lfi_view_focus_maps)");
     if(v < 0 || v >= ctx->views_n || k < 0 || k > 1 || !host || pitch_bytes < (size_t)ctx->width * 4)
         return fail(ctx, LFI_EINVAL, "bad view index, map index, pointer or pitch");
-    *out = ctx->view_maps + plane_bytes(ctx) * (2 * (size_t)v + k);
+    *out = ctx->view_maps.get() + plane_bytes(ctx) * (2 * (size_t)v + k);
     return LFI_OK;
 }
 
@@ -1183,10 +1094,10 @@ int lfi_memory_info(lfi_ctx *ctx, lfi_memory *out)
     if(!ctx || !out)
         return LFI_EINVAL;
     out->grid_bytes = ctx->grid ? in_plane_bytes(ctx) * ctx->n : 0;
-    out->derived_bytes = ctx->planar ? ctx->planar_bytes : 0;
-    out->views_bytes = ctx->views ? ctx->views_bytes : 0;
-    out->maps_bytes = (ctx->maps ? plane_bytes(ctx) * 2 : 0) + ctx->view_maps_bytes;
-    out->workspace_bytes = ctx->focus_ws_bytes + ctx->rgba_scratch_bytes + ctx->dl_plane_bytes;
+    out->derived_bytes = ctx->planar.bytes();
+    out->views_bytes = ctx->views.bytes();
+    out->maps_bytes = (ctx->maps ? plane_bytes(ctx) * 2 : 0) + ctx->view_maps.bytes();
+    out->workspace_bytes = ctx->focus_ws.bytes() + ctx->rgba_scratch.bytes() + ctx->dl_plane.bytes();
     out->derived_build_ms = ctx->derived_build_ms;
     return LFI_OK;
 }
@@ -1237,46 +1148,24 @@ int lfi_render_stream(lfi_ctx *ctx, int method, int all_focus, const uint16_t *w
     const size_t off_w16s = (sizeof(uint16_t) * (size_t)v_pad * k_pad + 15) / 16 * 16; // the layout lfi_set_params laid out
     const size_t off_w32 = (off_w16s + sizeof(uint16_t) * (size_t)v_pad * k_pad + 15) / 16 * 16;
     const size_t off_w32t = off_w32 + sizeof(float) * (size_t)v_pad * k_pad;
-    if(ctx->stream_staging_bytes != wbytes)
-    {
-        for(int i = 0; i < 2; i++)
-        {
-            if(ctx->stream_staging[i])
-                (void)hipHostFree(ctx->stream_staging[i]);
-            ctx->stream_staging[i] = nullptr;
-        }
-        ctx->stream_staging_bytes = 0;
-        for(int i = 0; i < 2; i++)
-            LFI_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->stream_staging[i]), wbytes, hipHostMallocDefault));
-        ctx->stream_staging_bytes = wbytes;
-    }
     for(int i = 0; i < 2; i++)
-        if(!ctx->ev_h2d[i])
-        {
-            LFI_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_h2d[i], hipEventDisableTiming));
-            LFI_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_rendered[i], hipEventDisableTiming));
-            LFI_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_d2h[i], hipEventDisableTiming));
-        }
+    {
+        LFI_HIP(ctx, ctx->stream_staging[i].fit(wbytes));
+        LFI_HIP(ctx, ctx->ev_h2d[i].ensure());
+        LFI_HIP(ctx, ctx->ev_rendered[i].ensure());
+        LFI_HIP(ctx, ctx->ev_d2h[i].ensure());
+    }
     if(host_out)
     {
         if(int rc = ensure_copy_stream(ctx))
             return rc;
-        const size_t need = out_plane_bytes(ctx) * V;
-        if(ctx->views2_bytes != need)
-        {
-            if(ctx->views2)
-                (void)hipFree(ctx->views2);
-            ctx->views2 = nullptr;
-            ctx->views2_bytes = 0;
-            LFI_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->views2), need));
-            ctx->views2_bytes = need;
-        }
+        LFI_HIP(ctx, ctx->views2.fit(out_plane_bytes(ctx) * V));
     }
     if(int rc = join_uploads(ctx))
         return rc;
     const int n_blocks = (total_views + V - 1) / V;
     uint8_t *dev_weights = param_base(ctx) + ctx->blob_off_w16;
-    uint8_t *const vbuf[2] = {ctx->views, host_out ? ctx->views2 : ctx->views};
+    uint8_t *const vbuf[2] = {ctx->views.get(), host_out ? ctx->views2.get() : ctx->views.get()};
     int status = LFI_OK;
     for(int b = 0; b < n_blocks && status == LFI_OK; b++)
     {
@@ -1285,13 +1174,13 @@ int lfi_render_stream(lfi_ctx *ctx, int method, int all_focus, const uint16_t *w
         // the staging slot is free once the copy of block b − 2 out of it has been executed
         if(b >= 2)
             LFI_HIP(ctx, hipEventSynchronize(ctx->ev_h2d[slot]));
-        std::memset(ctx->stream_staging[slot], 0, wbytes);
+        std::memset(ctx->stream_staging[slot].get(), 0, wbytes);
         bool scalable = true, sums_ok = true;
-        fill_weight_arrays(weights_fp16 + (size_t)b * V * n, nv, n, k_pad, v_pad, ctx->stream_staging[slot], off_w16s, off_w32, off_w32t, &scalable, &sums_ok);
+        fill_weight_arrays(weights_fp16 + (size_t)b * V * n, nv, n, k_pad, v_pad, ctx->stream_staging[slot].get(), off_w16s, off_w32, off_w32t, &scalable, &sums_ok);
         ctx->weights_scalable = scalable; // the dispatch of THIS block's launch (read at enqueue time)
         ctx->weights_sum_ok = sums_ok;
         // stream order protects the device arrays: the previous block's kernel is ahead of this copy on the same stream
-        LFI_HIP(ctx, hipMemcpyAsync(dev_weights, ctx->stream_staging[slot], wbytes, hipMemcpyHostToDevice, ctx->stream));
+        LFI_HIP(ctx, hipMemcpyAsync(dev_weights, ctx->stream_staging[slot].get(), wbytes, hipMemcpyHostToDevice, ctx->stream));
         LFI_HIP(ctx, hipEventRecord(ctx->ev_h2d[slot], ctx->stream));
         if(host_out && b >= 2)
             LFI_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_d2h[slot], 0)); // block b − 2 has left this set of views
@@ -1327,30 +1216,21 @@ int lfi_compare_view(lfi_ctx *ctx, int v, const uint8_t *reference_rgba, size_t 
         return fail(ctx, LFI_EINVAL, "lfi_compare_view needs the whole view (no row window)");
     if(int rc = bind(ctx))
         return rc;
-    const size_t need = plane_bytes(ctx);
-    if(ctx->quality_ref_bytes != need)
-    {
-        if(ctx->quality_ref)
-            (void)hipFree(ctx->quality_ref);
-        ctx->quality_ref = nullptr;
-        ctx->quality_ref_bytes = 0;
-        LFI_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->quality_ref), need));
-        ctx->quality_ref_bytes = need;
-    }
-    if(!ctx->quality_sums)
-        LFI_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->quality_sums), sizeof(lfi::QualitySums)));
-    LFI_HIP(ctx, hipMemcpy2DAsync(ctx->quality_ref, (size_t)ctx->width * 4, reference_rgba, pitch_bytes, (size_t)ctx->width * 4, ctx->height,
+    LFI_HIP(ctx, ctx->quality_ref.fit(plane_bytes(ctx)));
+    LFI_HIP(ctx, ctx->quality_sums.reserve(sizeof(lfi::QualitySums)));
+    lfi::QualitySums *const d_sums = ctx->quality_sums.as<lfi::QualitySums>();
+    LFI_HIP(ctx, hipMemcpy2DAsync(ctx->quality_ref.get(), (size_t)ctx->width * 4, reference_rgba, pitch_bytes, (size_t)ctx->width * 4, ctx->height,
                                   hipMemcpyHostToDevice, ctx->stream));
-    LFI_HIP(ctx, hipMemsetAsync(ctx->quality_sums, 0, sizeof(lfi::QualitySums), ctx->stream));
+    LFI_HIP(ctx, hipMemsetAsync(d_sums, 0, sizeof(lfi::QualitySums), ctx->stream));
     const uint8_t *view = nullptr;
     if(int rc = rgba_plane_of_view(ctx, v, &view))
         return rc;
     const int bw = (ctx->width + 3) / 4, bh = (ctx->height + 3) / 4; // 4×4 blocks
     hipLaunchKernelGGL(lfi::quality_reduce, dim3((bw + 15) / 16, (bh + 15) / 16), dim3(256), 0, ctx->stream, reinterpret_cast<const uint32_t *>(view),
-                       reinterpret_cast<const uint32_t *>(ctx->quality_ref), ctx->width, ctx->height, ctx->quality_sums);
+                       ctx->quality_ref.as<const uint32_t>(), ctx->width, ctx->height, d_sums);
     LFI_HIP(ctx, hipGetLastError());
     lfi::QualitySums sums{};
-    LFI_HIP(ctx, hipMemcpyAsync(&sums, ctx->quality_sums, sizeof(sums), hipMemcpyDeviceToHost, ctx->stream));
+    LFI_HIP(ctx, hipMemcpyAsync(&sums, d_sums, sizeof(sums), hipMemcpyDeviceToHost, ctx->stream));
     LFI_HIP(ctx, hipStreamSynchronize(ctx->stream));
     const double px = (double)ctx->width * ctx->height;
     double mse_all = 0, ssim_all = 0;
@@ -1491,7 +1371,7 @@ int lfi_download_map(lfi_ctx *ctx, int k, uint8_t *rgba, size_t pitch_bytes)
         return rc;
     if(int rc = join_filter(ctx))
         return rc;
-    LFI_HIP(ctx, hipMemcpy2DAsync(rgba, pitch_bytes, ctx->maps + plane_bytes(ctx) * k, (size_t)ctx->width * 4,
+    LFI_HIP(ctx, hipMemcpy2DAsync(rgba, pitch_bytes, ctx->maps.get() + plane_bytes(ctx) * k, (size_t)ctx->width * 4,
                                   (size_t)ctx->width * 4, ctx->height, hipMemcpyDeviceToHost, ctx->stream));
     LFI_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return LFI_OK;
@@ -1516,21 +1396,13 @@ int lfi_download_quilt_tiles(lfi_ctx *ctx, int tiles_x, int tiles_y, int first_t
     const int W = ctx->width, rows = ctx->out_rows;
     const size_t qrow = (size_t)tiles_x * W * 4;
     const size_t need = qrow * rows * (size_t)(tr1 - tr0 + 1);
-    if(ctx->quilt_bytes < need)
-    {
-        if(ctx->quilt)
-            (void)hipFree(ctx->quilt);
-        ctx->quilt = nullptr;
-        ctx->quilt_bytes = 0;
-        LFI_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->quilt), need));
-        ctx->quilt_bytes = need;
-    }
+    LFI_HIP(ctx, ctx->quilt.reserve(need));
     const dim3 grid(((W + 3) / 4 + 255) / 256, rows, n), block(256);
     if(ctx->out_layout == LFI_LAYOUT_PLANAR_RGB)
-        hipLaunchKernelGGL(lfi::quilt_assemble<true>, grid, block, 0, ctx->stream, ctx->views, reinterpret_cast<uint32_t *>(ctx->quilt), W, rows, view_pitch(ctx),
+        hipLaunchKernelGGL(lfi::quilt_assemble<true>, grid, block, 0, ctx->stream, ctx->views.get(), ctx->quilt.as<uint32_t>(), W, rows, view_pitch(ctx),
                            out_plane_bytes(ctx), v0, first_tile, tiles_x);
     else
-        hipLaunchKernelGGL(lfi::quilt_assemble<false>, grid, block, 0, ctx->stream, ctx->views, reinterpret_cast<uint32_t *>(ctx->quilt), W, rows, 0,
+        hipLaunchKernelGGL(lfi::quilt_assemble<false>, grid, block, 0, ctx->stream, ctx->views.get(), ctx->quilt.as<uint32_t>(), W, rows, 0,
                            out_plane_bytes(ctx), v0, first_tile, tiles_x);
     LFI_HIP(ctx, hipGetLastError());
     const int c_first = first_tile % tiles_x, c_last = (first_tile + n - 1) % tiles_x;
@@ -1539,12 +1411,12 @@ int lfi_download_quilt_tiles(lfi_ctx *ctx, int tiles_x, int tiles_y, int first_t
         const size_t w_bytes = (size_t)(cb - ca + 1) * W * 4;
         if(rows == ctx->height) // the tiles' rows are contiguous in the host image too: one copy for all rows of tiles
             return hipMemcpy2DAsync(rgba + (size_t)ra * ctx->height * pitch_bytes + (size_t)ca * W * 4, pitch_bytes,
-                                    ctx->quilt + (size_t)(ra - tr0) * rows * qrow + (size_t)ca * W * 4, qrow, w_bytes, (size_t)(rb - ra + 1) * rows,
+                                    ctx->quilt.get() + (size_t)(ra - tr0) * rows * qrow + (size_t)ca * W * 4, qrow, w_bytes, (size_t)(rb - ra + 1) * rows,
                                     hipMemcpyDeviceToHost, ctx->stream);
         for(int r = ra; r <= rb; r++)
         {
             const hipError_t e = hipMemcpy2DAsync(rgba + ((size_t)r * ctx->height + ctx->out_y0) * pitch_bytes + (size_t)ca * W * 4, pitch_bytes,
-                                                  ctx->quilt + (size_t)(r - tr0) * rows * qrow + (size_t)ca * W * 4, qrow, w_bytes, rows, hipMemcpyDeviceToHost, ctx->stream);
+                                                  ctx->quilt.get() + (size_t)(r - tr0) * rows * qrow + (size_t)ca * W * 4, qrow, w_bytes, rows, hipMemcpyDeviceToHost, ctx->stream);
             if(e != hipSuccess)
                 return e;
         }
@@ -1612,7 +1484,7 @@ int lfi_upload_map(lfi_ctx *ctx, int k, const uint8_t *rgba, size_t pitch_bytes)
         return rc;
     if(int rc = join_filter(ctx))
         return rc;
-    LFI_HIP(ctx, hipMemcpy2DAsync(ctx->maps + plane_bytes(ctx) * k, (size_t)ctx->width * 4, rgba, pitch_bytes,
+    LFI_HIP(ctx, hipMemcpy2DAsync(ctx->maps.get() + plane_bytes(ctx) * k, (size_t)ctx->width * 4, rgba, pitch_bytes,
                                   (size_t)ctx->width * 4, ctx->height, hipMemcpyHostToDevice, ctx->stream));
     LFI_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return LFI_OK;
@@ -1705,18 +1577,14 @@ int lfi_download_coords(lfi_ctx *ctx, int g, int all_focus, int map_index, lfi_i
     if(int rc = join_filter(ctx))
         return rc;
     const size_t bytes = sizeof(lfi_int2) * (size_t)ctx->width * ctx->height;
-    lfi_int2 *d = nullptr;
-    LFI_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&d), bytes));
+    DeviceBuffer d; // freed on every way out
+    LFI_HIP(ctx, d.reserve(bytes));
     KernelArgs a = make_args(ctx, 0, ctx->views_n, LFI_METHOD_STD);
     a.map_index = map_index;
-    hipLaunchKernelGGL(lfi::dump_coords, pixel_grid(ctx), dim3(256), 0, ctx->stream, a, g, all_focus, d);
-    hipError_t e = hipGetLastError();
-    if(e == hipSuccess)
-        e = hipMemcpyAsync(out_hw, d, bytes, hipMemcpyDeviceToHost, ctx->stream);
-    if(e == hipSuccess)
-        e = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d);
-    LFI_HIP(ctx, e);
+    hipLaunchKernelGGL(lfi::dump_coords, pixel_grid(ctx), dim3(256), 0, ctx->stream, a, g, all_focus, d.as<lfi_int2>());
+    LFI_HIP(ctx, hipGetLastError());
+    LFI_HIP(ctx, hipMemcpyAsync(out_hw, d.get(), bytes, hipMemcpyDeviceToHost, ctx->stream));
+    LFI_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return LFI_OK;
 }
 
@@ -1729,14 +1597,13 @@ int lfi_download_prequant(lfi_ctx *ctx, int method, int all_focus, int v, float 
     if(int rc = bind(ctx))
         return rc;
     const size_t bytes = sizeof(float) * 3 * (size_t)ctx->width * ctx->height;
-    if(!ctx->prequant)
-        LFI_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->prequant), bytes));
+    LFI_HIP(ctx, ctx->prequant.reserve(bytes));
     KernelArgs a = make_args(ctx, v, v + 1, method);
-    a.prequant = ctx->prequant;
+    a.prequant = ctx->prequant.as<float>();
     a.prequant_view = v;
     if(int rc = launch_blend(ctx, method, all_focus, a))
         return rc;
-    LFI_HIP(ctx, hipMemcpyAsync(out_hw3, ctx->prequant, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    LFI_HIP(ctx, hipMemcpyAsync(out_hw3, ctx->prequant.get(), bytes, hipMemcpyDeviceToHost, ctx->stream));
     LFI_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return LFI_OK;
 }
@@ -1747,23 +1614,16 @@ int lfi_debug_mfma_f16(lfi_ctx *ctx, const uint16_t *a_32x16, const uint16_t *b_
         return LFI_EINVAL;
     if(int rc = bind(ctx))
         return rc;
-    uint8_t *d = nullptr;
-    LFI_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&d), 1024 + 1024 + 4096));
-    hipError_t e = hipMemcpyAsync(d, a_32x16, 1024, hipMemcpyHostToDevice, ctx->stream);
-    if(e == hipSuccess)
-        e = hipMemcpyAsync(d + 1024, b_16x32, 1024, hipMemcpyHostToDevice, ctx->stream);
-    if(e == hipSuccess)
-    {
-        hipLaunchKernelGGL(lfi::probe_mfma_f16, dim3(1), dim3(64), 0, ctx->stream, reinterpret_cast<const uint16_t *>(d),
-                           reinterpret_cast<const uint16_t *>(d + 1024), reinterpret_cast<float *>(d + 2048));
-        e = hipGetLastError();
-    }
-    if(e == hipSuccess)
-        e = hipMemcpyAsync(c_32x32, d + 2048, 4096, hipMemcpyDeviceToHost, ctx->stream);
-    if(e == hipSuccess)
-        e = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d);
-    LFI_HIP(ctx, e);
+    DeviceBuffer buf;
+    LFI_HIP(ctx, buf.reserve(1024 + 1024 + 4096));
+    uint8_t *const d = buf.get();
+    LFI_HIP(ctx, hipMemcpyAsync(d, a_32x16, 1024, hipMemcpyHostToDevice, ctx->stream));
+    LFI_HIP(ctx, hipMemcpyAsync(d + 1024, b_16x32, 1024, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(lfi::probe_mfma_f16, dim3(1), dim3(64), 0, ctx->stream, reinterpret_cast<const uint16_t *>(d),
+                       reinterpret_cast<const uint16_t *>(d + 1024), reinterpret_cast<float *>(d + 2048));
+    LFI_HIP(ctx, hipGetLastError());
+    LFI_HIP(ctx, hipMemcpyAsync(c_32x32, d + 2048, 4096, hipMemcpyDeviceToHost, ctx->stream));
+    LFI_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return LFI_OK;
 }
 
@@ -1773,20 +1633,14 @@ int lfi_debug_pk_minmax3_f16(lfi_ctx *ctx, uint32_t *out_mismatches)
         return LFI_EINVAL;
     if(int rc = bind(ctx))
         return rc;
-    uint32_t *d = nullptr;
-    LFI_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&d), sizeof(uint32_t)));
-    hipError_t e = hipMemsetAsync(d, 0, sizeof(uint32_t), ctx->stream);
-    if(e == hipSuccess)
-    {
-        hipLaunchKernelGGL(lfi::probe_pk_minmax3, dim3(1u << 16), dim3(256), 0, ctx->stream, d);
-        e = hipGetLastError();
-    }
-    if(e == hipSuccess)
-        e = hipMemcpyAsync(out_mismatches, d, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream);
-    if(e == hipSuccess)
-        e = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d);
-    LFI_HIP(ctx, e);
+    DeviceBuffer buf;
+    LFI_HIP(ctx, buf.reserve(sizeof(uint32_t)));
+    uint32_t *const d = buf.as<uint32_t>();
+    LFI_HIP(ctx, hipMemsetAsync(d, 0, sizeof(uint32_t), ctx->stream));
+    hipLaunchKernelGGL(lfi::probe_pk_minmax3, dim3(1u << 16), dim3(256), 0, ctx->stream, d);
+    LFI_HIP(ctx, hipGetLastError());
+    LFI_HIP(ctx, hipMemcpyAsync(out_mismatches, d, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    LFI_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return LFI_OK;
 }
 
@@ -1797,27 +1651,20 @@ int lfi_debug_mfma_f16_chain(lfi_ctx *ctx, int shape, int k, const uint16_t *a_3
     if(int rc = bind(ctx))
         return rc;
     const size_t ab = (size_t)32 * k * sizeof(uint16_t);
-    uint8_t *d = nullptr;
-    LFI_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&d), 2 * ab + 4096));
-    hipError_t e = hipMemcpyAsync(d, a_32xk, ab, hipMemcpyHostToDevice, ctx->stream);
-    if(e == hipSuccess)
-        e = hipMemcpyAsync(d + ab, b_kx32, ab, hipMemcpyHostToDevice, ctx->stream);
-    if(e == hipSuccess)
-    {
-        const uint16_t *da = reinterpret_cast<const uint16_t *>(d), *db = reinterpret_cast<const uint16_t *>(d + ab);
-        float *dc = reinterpret_cast<float *>(d + 2 * ab);
-        if(shape == 0)
-            hipLaunchKernelGGL(lfi::probe_mfma_f16_chain<0>, dim3(1), dim3(64), 0, ctx->stream, da, db, k, dc);
-        else
-            hipLaunchKernelGGL(lfi::probe_mfma_f16_chain<1>, dim3(1), dim3(64), 0, ctx->stream, da, db, k, dc);
-        e = hipGetLastError();
-    }
-    if(e == hipSuccess)
-        e = hipMemcpyAsync(c_32x32, d + 2 * ab, 4096, hipMemcpyDeviceToHost, ctx->stream);
-    if(e == hipSuccess)
-        e = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d);
-    LFI_HIP(ctx, e);
+    DeviceBuffer buf;
+    LFI_HIP(ctx, buf.reserve(2 * ab + 4096));
+    uint8_t *const d = buf.get();
+    LFI_HIP(ctx, hipMemcpyAsync(d, a_32xk, ab, hipMemcpyHostToDevice, ctx->stream));
+    LFI_HIP(ctx, hipMemcpyAsync(d + ab, b_kx32, ab, hipMemcpyHostToDevice, ctx->stream));
+    const uint16_t *da = reinterpret_cast<const uint16_t *>(d), *db = reinterpret_cast<const uint16_t *>(d + ab);
+    float *dc = reinterpret_cast<float *>(d + 2 * ab);
+    if(shape == 0)
+        hipLaunchKernelGGL(lfi::probe_mfma_f16_chain<0>, dim3(1), dim3(64), 0, ctx->stream, da, db, k, dc);
+    else
+        hipLaunchKernelGGL(lfi::probe_mfma_f16_chain<1>, dim3(1), dim3(64), 0, ctx->stream, da, db, k, dc);
+    LFI_HIP(ctx, hipGetLastError());
+    LFI_HIP(ctx, hipMemcpyAsync(c_32x32, d + 2 * ab, 4096, hipMemcpyDeviceToHost, ctx->stream));
+    LFI_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return LFI_OK;
 }
 
@@ -1837,9 +1684,9 @@ int lfi_debug_poison(lfi_ctx *ctx, uint32_t what, uint8_t byte)
     if(int rc = join_filter(ctx))
         return rc;
     hipStream_t st = ctx->stream;
-    auto fill = [&](void *p, size_t bytes) -> int {
-        if(p && bytes)
-            LFI_HIP(ctx, hipMemsetAsync(p, byte, bytes, st));
+    auto fill = [&](const DeviceBuffer &b, size_t bytes) -> int {
+        if(b && bytes)
+            LFI_HIP(ctx, hipMemsetAsync(b.get(), byte, bytes, st));
         return LFI_OK;
     };
     int rc = LFI_OK;
@@ -1847,24 +1694,24 @@ int lfi_debug_poison(lfi_ctx *ctx, uint32_t what, uint8_t byte)
         rc = rc ? rc : fill(ctx->views, ctx->views ? out_plane_bytes(ctx) * ctx->views_n : 0);
     if(what & LFI_POISON_SCRATCH)
     {
-        rc = rc ? rc : fill(ctx->rgba_scratch, ctx->rgba_scratch_bytes);
-        rc = rc ? rc : fill(ctx->dl_plane, ctx->dl_plane_bytes);
-        rc = rc ? rc : fill(ctx->prequant, sizeof(float) * 3 * (size_t)ctx->width * ctx->height);
-        rc = rc ? rc : fill(ctx->quilt, ctx->quilt_bytes);
-        rc = rc ? rc : fill(ctx->views2, ctx->views2_bytes);
+        rc = rc ? rc : fill(ctx->rgba_scratch, ctx->rgba_scratch.bytes());
+        rc = rc ? rc : fill(ctx->dl_plane, ctx->dl_plane.bytes());
+        rc = rc ? rc : fill(ctx->prequant, ctx->prequant.bytes());
+        rc = rc ? rc : fill(ctx->quilt, ctx->quilt.bytes());
+        rc = rc ? rc : fill(ctx->views2, ctx->views2.bytes());
     }
     if(what & LFI_POISON_MAPS)
         rc = rc ? rc : fill(ctx->maps, ctx->maps ? plane_bytes(ctx) * 2 : 0);
     if(what & LFI_POISON_VIEW_MAPS)
-        rc = rc ? rc : fill(ctx->view_maps, ctx->view_maps_bytes);
+        rc = rc ? rc : fill(ctx->view_maps, ctx->view_maps.bytes());
     if(what & LFI_POISON_FOCUS_WORKSPACE)
     {
-        rc = rc ? rc : fill(ctx->focus_ws, ctx->focus_ws_bytes);
+        rc = rc ? rc : fill(ctx->focus_ws, ctx->focus_ws.bytes());
         ctx->pad_version = 0; // the padded planes of the estimate are rebuilt in full by the next lfi_focus_map
     }
     if(what & LFI_POISON_DERIVED)
     {
-        rc = rc ? rc : fill(ctx->planar, ctx->planar_bytes);
+        rc = rc ? rc : fill(ctx->planar, ctx->planar.bytes());
         if(ctx->planar)
             touch_all(ctx); // as lfi_grid_modified: the next render that reads the copy rebuilds all of it
     }
