@@ -283,6 +283,33 @@ int lfi_views_device_ptr(lfi_ctx *ctx, void **out_ptr, size_t *out_bytes);
  * light field (the reference's focusMapCompare.sh loop) pads once.  The map is estimated at the trajectory's centre from lfi_params.offsets
  * and focus_map_ids, whether or not per-view float offsets (lfi_set_view_float_offsets) are set. */
 int lfi_focus_map(lfi_ctx *ctx);
+/* Autofocus: the focus CURVE of the region [x0, x1) x [y0, y1) and its minimum — "what is the focus of this object?" (click-to-focus, or the
+ * whole frame for a fixed-focus render).  No counterpart in the reference, whose estimate keeps only each pixel's argmin of the cost
+ * (MinDispersion, src/kernels.cu:219-237) and throws the cost away; here the cost is summed over the region per candidate instead, on the
+ * device (csrc/hip/focus_curve.hpp), and steps * 8 + 16 bytes come back.
+ *  - candidates: step = range / (float)(steps - 1), f_i = fmaf(step, (float)i, focus) in fp32 (lfi_host_focus_candidates) — for steps == 32
+ *    exactly the estimate's candidates (src/kernels.cu:245-250).  2 <= steps <= 256, range > 0: [focus, focus + range] is the search interval;
+ *  - cost[i] = the sum over the region's pixels of S_i(x, y), the integer form of focusDispersion(f_i, (x, y)) (src/kernels.cu:196-217): over
+ *    the n_focus_ids images of lfi_params.focus_map_ids, sampled at (int)fmaf(f_i, offsets[g], pixel) +- block_radius (3 x 3 taps, clamp to
+ *    edge), per tap the largest channel's max - min over the images, summed over the nine taps.  It uses the CURRENT lfi_params (offsets, ids,
+ *    focus, range, block radius), i.e. the trajectory's centre, as lfi_focus_map does; per-view offsets of either kind do not affect it.
+ *    The sums are integers: exact, whatever the order;
+ *  - one departure from the float code: the reference starts its running maximum at FLT_MIN (src/kernels.cu:178), so a tap whose samples are
+ *    all zero contributes 1.2e-38 instead of 0.  Those terms cannot be added meaningfully over a region and are dropped.  It only matters where
+ *    several candidates have cost 0: the first of them then wins;
+ *  - out->best_index: the first candidate with the strictly smallest cost (MinDispersion's rule, src/kernels.cu:225-231), out->best_focus =
+ *    f_best_index, out->pixels = (x1 - x0) * (y1 - y0).  out_cost ([steps], may be NULL) receives the curve;
+ *  - synchronous; ordered after pending uploads and the work on the context's stream like lfi_focus_map; it leaves the maps, the views, the
+ *    estimate's padded planes and workspace as they were (a later lfi_focus_map gives the same bytes as without the call).  Its own device
+ *    memory (per-workgroup partial sums, the curve and the result) is counted in lfi_memory.workspace_bytes;
+ *  - LFI_EINVAL: no grid or no parameters; an empty region or one that leaves the image; steps outside [2, 256]; range <= 0; n_focus_ids == 0;
+ *    out == NULL; a row window set; after lfi_release_inputs (it reads the RGBA planes).  The context stays usable. */
+typedef struct lfi_focus_curve_result {
+    int32_t best_index;  /* first candidate with the strictly smallest cost */
+    float best_focus;    /* f_best_index */
+    uint64_t pixels;     /* pixels of the region */
+} lfi_focus_curve_result;
+int lfi_focus_curve(lfi_ctx *ctx, int x0, int y0, int x1, int y1, int steps, uint64_t *out_cost, lfi_focus_curve_result *out);
 /* One launch of Tensors::process / Standard::process (src/interpolator.cu:274-288) for views [v0, v1).
  * all_focus != 0 selects the <true> instantiations (per-pixel focus from the focus map). */
 int lfi_render(lfi_ctx *ctx, int method, int all_focus, int v0, int v1);
@@ -307,7 +334,7 @@ typedef struct lfi_memory {
     size_t derived_bytes;   /* planar copy of the inputs: 3 bytes per pixel and image (+ padding) */
     size_t views_bytes;     /* output planes */
     size_t maps_bytes;      /* focus maps (maps 0 / 1, and the per-view maps when allocated) */
-    size_t workspace_bytes; /* focus-map workspace + (planar view layout) the RGBA scratch copy of the views that renders other than TEN_WM and
+    size_t workspace_bytes; /* focus-map workspace + lfi_focus_curve's partial sums + (planar view layout) the RGBA scratch copy of the views that renders other than TEN_WM and
                              * STD on more than 64 images go through, and the one-plane staging buffer of downloads */
     float derived_build_ms;
 } lfi_memory;
@@ -412,7 +439,7 @@ int lfi_debug_mfma_f16_chain(lfi_ctx *ctx, int shape, int k, const uint16_t *a_3
  *   SCRATCH          the planar layout's RGBA scratch copy of the views, the download staging plane, the pre-quantisation buffer, the
  *                    quilt buffer and lfi_render_stream's second set of views
  *   MAPS             both focus maps
- *   FOCUS_WORKSPACE  all of the focus-map estimate's workspace
+ *   FOCUS_WORKSPACE  all of the focus-map estimate's workspace, and lfi_focus_curve's (the curve, the result and the partial sums)
  *   DERIVED          the planar copy of the inputs — refused (LFI_EINVAL) after lfi_release_inputs: it is then the only copy
  *   VIEW_MAPS        the per-view focus maps of lfi_view_focus_maps, every view's pair */
 enum { LFI_POISON_VIEWS = 1, LFI_POISON_SCRATCH = 2, LFI_POISON_MAPS = 4, LFI_POISON_FOCUS_WORKSPACE = 8, LFI_POISON_DERIVED = 16,

@@ -35,7 +35,7 @@ ABI_SYMBOLS = [
     "lfi_set_variant", "lfi_list_variants", "lfi_download_coords", "lfi_download_prequant", "lfi_debug_mfma_f16",
     "lfi_grid_modified", "lfi_prepare", "lfi_memory_info", "lfi_last_kernel_name", "lfi_fill_synthetic_images", "lfi_set_output_layout", "lfi_view_layout", "lfi_fill_synthetic_scene", "lfi_upload_image_async", "lfi_upload_wait", "lfi_render_stream", "lfi_compare_view", "lfi_debug_mfma_f16_chain", "lfi_debug_pk_minmax3_f16", "lfi_std_band_info",
     "lfi_debug_poison", "lfi_set_view_offsets", "lfi_set_view_float_offsets", "lfi_view_focus_maps", "lfi_download_view_map",
-    "lfi_upload_view_map",
+    "lfi_upload_view_map", "lfi_focus_curve",
 ]
 
 
@@ -71,6 +71,10 @@ class Quality(C.Structure):
 class StdBandInfo(C.Structure):
     _fields_ = [("probed", C.c_int32), ("within_budget", C.c_int32), ("analytic_forced", C.c_int32), ("sums", C.c_int32),
                 ("worst_fraction", C.c_float), ("probe_ms", C.c_float), ("message", C.c_char * 160)]
+
+
+class FocusCurveResult(C.Structure):
+    _fields_ = [("best_index", C.c_int32), ("best_focus", C.c_float), ("pixels", C.c_uint64)]
 
 
 class MemoryInfo(C.Structure):
@@ -121,6 +125,7 @@ def load_hip_library() -> C.CDLL:
         "lfi_attach_views": (i, [vp, vp, sz]),
         "lfi_views_device_ptr": (i, [vp, C.POINTER(vp), C.POINTER(sz)]),
         "lfi_focus_map": (i, [vp]),
+        "lfi_focus_curve": (i, [vp, i, i, i, i, i, vp, C.POINTER(FocusCurveResult)]),
         "lfi_render": (i, [vp, i, i, i, i]),
         "lfi_benchmark": (i, [vp, i, i, i, i, i, i, C.POINTER(BenchStats)]),
         "lfi_timer_start": (i, [vp]),
@@ -343,6 +348,16 @@ class Context:
     # -- kernels -------------------------------------------------------------------------------------------------
     def focus_map(self) -> None:
         self._check(self._lib.lfi_focus_map(self._h))
+
+    def focus_curve(self, x0: int, y0: int, x1: int, y1: int, steps: int = 32):
+        """Autofocus (lfi_focus_curve): the focus curve of the region [x0, x1) x [y0, y1) over `steps` candidates of [focus, focus + range]
+        of the current parameters.  Returns (cost [steps] uint64, best_index, best_focus as np.float32); the candidates themselves are
+        lfinterpolator_amd.focus_candidates(focus, range, steps)."""
+        cost = np.full(max(int(steps), 0), 0xC3C3C3C3C3C3C3C3, dtype=np.uint64)   # a sentinel: every element is written
+        res = FocusCurveResult(-1, float("nan"), 0)
+        self._check(self._lib.lfi_focus_curve(self._h, x0, y0, x1, y1, steps, _ptr(cost), C.byref(res)))
+        self.focus_curve_pixels = int(res.pixels)   # the region's size as the library counted it
+        return cost, int(res.best_index), np.float32(res.best_focus)
 
     def view_focus_maps(self, ids_vk: np.ndarray) -> None:
         """Per-view focus maps (lfi_view_focus_maps): ids_vk is [views][n_ids] int32 — row v = the images view v's map samples

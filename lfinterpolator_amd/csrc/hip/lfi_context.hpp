@@ -341,6 +341,7 @@ struct lfi_ctx
     uint64_t pad_version = 0;
     int pad_shift[2] = {0, 0}, pad_radius[2] = {0, 0};
     std::vector<int32_t> pad_ids, h_focus_ids;
+    DeviceBuffer curve_ws; // lfi_focus_curve: the curve and its result, then the per-workgroup partial sums (grows, kept)
     int ten_variant = 0, std_variant = 0, focus_variant = 0;
     mutable const char *last_kernel = ""; // the blend kernel the last render launched (lfi_last_kernel_name)
     mutable unsigned sweep_launches = 0;  // blend_p3 / blend_planar alternate their sweep direction from launch to launch
@@ -700,6 +701,7 @@ void free_grid(lfi_ctx *c)
     c->prequant.release();
     c->focus_ws.release();
     c->pad_version = 0;
+    c->curve_ws.release();
     c->planar.release();
     c->planar_version = 0;
     c->d_planar_phase.release();

@@ -1,11 +1,13 @@
 // lfi_focus_sched.hpp — scheduling of the focus-map estimate: the factored pipeline's workspace and its two-stream pass graph
-// (focus_factored.hpp), and the choice between it, the row-window path and the other estimate variants.
+// (focus_factored.hpp), and the choice between it, the row-window path and the other estimate variants; the focus curve's workspace and
+// its three launches (focus_curve.hpp).
 // Replaces the FocusMap::estimate / FocusMap::filter launches (reference src/interpolator.cu:261-266).
 // Included by lfi_hip.hip only (one translation unit), after lfi_context.hpp.
 #pragma once
 
 #include "lfi_context.hpp"
 #include "focus_factored.hpp"
+#include "focus_curve.hpp"
 
 namespace {
 
@@ -269,6 +271,42 @@ int launch_focus_factored(lfi_ctx *ctx, const KernelArgs &a, FocusJob &job, bool
     }
     LFI_HIP(ctx, hipGetLastError());
     *done = true;
+    return LFI_OK;
+}
+
+// The focus curve of the region [x0, x1) × [y0, y1) (lfi_focus_curve; the caller has checked the arguments): partial sums per workgroup and
+// candidate, their sum per candidate, the first strict minimum — three launches on the compute stream.  ctx->curve_ws holds the curve and the
+// result (FOCUS_CURVE_HEAD bytes: [steps] u64 + lfi_focus_curve_result) followed by the partials [steps][workgroups]; nothing of the estimate's
+// state (focus_ws, the padded planes, the maps) is touched.  *d_head = the device address of the curve.
+constexpr size_t FOCUS_CURVE_HEAD = (sizeof(uint64_t) * lfi::FOCUS_CURVE_MAX_STEPS + sizeof(lfi_focus_curve_result) + 255) / 256 * 256;
+
+int launch_focus_curve(lfi_ctx *ctx, const KernelArgs &a, int x0, int y0, int x1, int y1, int steps, const uint8_t **d_head)
+{
+    constexpr int PPL = 2; // pixels per lane: focus_estimate_packed<2, 4>'s shape (row-window path, variant "packed_p2"), five waves per SIMD
+    const uint32_t blocks_x = uint32_t((x1 - x0 + 64 * PPL - 1) / (64 * PPL));
+    // One row per wave while the partials stay small (fine-grained dispatch fills the tail: a wave lives ≈ 1 ms per row at 32 images); beyond
+    // 2 Mi partials (16 MB) — whole 4K frames with more than 32 candidates — a wave walks several rows, never fewer than 8192 waves.
+    const uint32_t max_wg = std::min(65536u, std::max(8192u, (2u << 20) / uint32_t(steps)));
+    const uint32_t blocks_y = std::min(uint32_t(y1 - y0), std::max(1u, max_wg / blocks_x));
+    lfi::FocusCurveArgs q{};
+    q.x0 = x0, q.y0 = y0, q.x1 = x1, q.y1 = y1;
+    q.steps = steps;
+    q.n_wg = blocks_x * blocks_y;
+    // A small region (click-to-focus) has too few rows × 128-pixel runs to fill the GPU, and a wave that walks all candidates lives ≈ 1 ms:
+    // the candidates are split over blockIdx.z until there are about four waves per SIMD.  Whole frames keep one wave per row and run.
+    const uint32_t want_z = std::min(uint32_t(steps), std::max(1u, uint32_t(ctx->cu_count) * 16u / q.n_wg));
+    q.steps_per_wg = (steps + int(want_z) - 1) / int(want_z);
+    const uint32_t blocks_z = uint32_t((steps + q.steps_per_wg - 1) / q.steps_per_wg);
+    q.pixels = uint64_t(x1 - x0) * uint64_t(y1 - y0);
+    LFI_HIP(ctx, ctx->curve_ws.reserve(FOCUS_CURVE_HEAD + sizeof(uint64_t) * size_t(steps) * q.n_wg));
+    q.cost = reinterpret_cast<uint64_t *>(ctx->curve_ws.get());
+    q.partial = reinterpret_cast<uint64_t *>(ctx->curve_ws.get() + FOCUS_CURVE_HEAD);
+    hipStream_t st = ctx->stream;
+    hipLaunchKernelGGL((lfi::focus_curve_partial<PPL, 4>), dim3(blocks_x, blocks_y, blocks_z), dim3(64), 0, st, a, q);
+    hipLaunchKernelGGL(lfi::focus_curve_sum, dim3(steps), dim3(256), 0, st, q);
+    hipLaunchKernelGGL(lfi::focus_curve_pick, dim3(1), dim3(256), 0, st, a, q);
+    LFI_HIP(ctx, hipGetLastError());
+    *d_head = ctx->curve_ws.get();
     return LFI_OK;
 }
 

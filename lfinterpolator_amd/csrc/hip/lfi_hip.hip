@@ -3,7 +3,7 @@
 // the parameters stays in the host code above the ABI (lfinterpolator_amd/csrc/host).  Its parts:
 //   lfi_context.hpp      the context (device memory, streams, parameter block) and its helpers
 //   lfi_dispatch.hpp     variant tables, kernel launchers, the derived planar copy, launch_blend
-//   lfi_focus_sched.hpp  the focus-map estimate's workspace and pass graph
+//   lfi_focus_sched.hpp  the focus-map estimate's workspace and pass graph; the focus curve's launches
 //   lfi_rccl.hpp         RCCL loader for lfi_broadcast_grid
 #include "lfi_context.hpp"
 #include "lfi_dispatch.hpp"
@@ -855,6 +855,45 @@ int lfi_focus_map(lfi_ctx *ctx)
     return LFI_OK;
 }
 
+int lfi_focus_curve(lfi_ctx *ctx, int x0, int y0, int x1, int y1, int steps, uint64_t *out_cost, lfi_focus_curve_result *out)
+{
+    if(!ctx)
+        return LFI_EINVAL;
+    if(ctx->inputs_released)
+        return fail(ctx, LFI_EINVAL, "the RGBA inputs were released (lfi_release_inputs): the focus curve needs them - upload the images again (lfi_set_grid)");
+    if(!ctx->grid || !ctx->have_params)
+        return fail(ctx, LFI_EINVAL, "lfi_set_grid / lfi_set_params have not been called");
+    if(ctx->windowed)
+        return fail(ctx, LFI_EINVAL, "lfi_focus_curve does not work on a row window");
+    if(!out)
+        return fail(ctx, LFI_EINVAL, "lfi_focus_curve: out is NULL");
+    if(ctx->n_focus_ids < 1)
+        return fail(ctx, LFI_EINVAL, "no focus_map_ids in the parameters");
+    if(!(ctx->range > 0.0f))
+        return fail(ctx, LFI_EINVAL, "focus range must be > 0 for the focus curve: [focus, focus + range] is the search interval");
+    if(steps < 2 || steps > lfi::FOCUS_CURVE_MAX_STEPS)
+        return fail(ctx, LFI_EINVAL, "lfi_focus_curve: steps must be in [2, 256]");
+    if(x0 < 0 || y0 < 0 || x1 > ctx->width || y1 > ctx->height || x0 >= x1 || y0 >= y1)
+        return fail(ctx, LFI_EINVAL, "lfi_focus_curve: the region is empty or leaves the image");
+    if(int rc = bind(ctx))
+        return rc;
+    if(int rc = join_uploads(ctx))
+        return rc;
+    const KernelArgs a = make_args(ctx, 0, ctx->views_n, LFI_METHOD_STD);
+    const uint8_t *d_head = nullptr;
+    if(int rc = launch_focus_curve(ctx, a, x0, y0, x1, y1, steps, &d_head))
+        return rc;
+    // the curve and the result lie back to back: one copy of steps · 8 + 16 bytes
+    uint64_t head[lfi::FOCUS_CURVE_MAX_STEPS + sizeof(lfi_focus_curve_result) / sizeof(uint64_t)];
+    const size_t head_bytes = sizeof(uint64_t) * steps + sizeof(lfi_focus_curve_result);
+    LFI_HIP(ctx, hipMemcpyAsync(head, d_head, head_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    LFI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if(out_cost)
+        std::memcpy(out_cost, head, sizeof(uint64_t) * steps);
+    std::memcpy(out, head + steps, sizeof(lfi_focus_curve_result));
+    return LFI_OK;
+}
+
 // the per-view maps [views_n][2][H][W], allocated (or grown) on first use; renders in flight may read the old buffer
 static int ensure_view_maps(lfi_ctx *ctx)
 {
@@ -1097,7 +1136,7 @@ int lfi_memory_info(lfi_ctx *ctx, lfi_memory *out)
     out->derived_bytes = ctx->planar.bytes();
     out->views_bytes = ctx->views.bytes();
     out->maps_bytes = (ctx->maps ? plane_bytes(ctx) * 2 : 0) + ctx->view_maps.bytes();
-    out->workspace_bytes = ctx->focus_ws.bytes() + ctx->rgba_scratch.bytes() + ctx->dl_plane.bytes();
+    out->workspace_bytes = ctx->focus_ws.bytes() + ctx->curve_ws.bytes() + ctx->rgba_scratch.bytes() + ctx->dl_plane.bytes();
     out->derived_build_ms = ctx->derived_build_ms;
     return LFI_OK;
 }
@@ -1707,6 +1746,7 @@ int lfi_debug_poison(lfi_ctx *ctx, uint32_t what, uint8_t byte)
     if(what & LFI_POISON_FOCUS_WORKSPACE)
     {
         rc = rc ? rc : fill(ctx->focus_ws, ctx->focus_ws.bytes());
+        rc = rc ? rc : fill(ctx->curve_ws, ctx->curve_ws.bytes());
         ctx->pad_version = 0; // the padded planes of the estimate are rebuilt in full by the next lfi_focus_map
     }
     if(what & LFI_POISON_DERIVED)

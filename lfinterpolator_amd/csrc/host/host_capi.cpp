@@ -58,6 +58,16 @@ int lfi_host_focus_ramp(float f0, float f1, int views, float *out)
     return 0;
 }
 
+// the focus candidates of lfi_focus_curve: out[steps] = fmaf(range / (steps − 1), i, focus) in float; returns 0, or -1 for steps < 2
+int lfi_host_focus_candidates(float focus, float range, int steps, float *out)
+{
+    if(steps < 2 || !out)
+        return -1;
+    const std::vector<float> f = lfi::focusCandidates(focus, range, steps);
+    std::memcpy(out, f.data(), sizeof(float) * f.size());
+    return 0;
+}
+
 // per-view focus: out_vn[views][N] = the focused offsets of Parameterizer::offsets at focus_v[v] (the rows lfi_set_view_offsets takes)
 int lfi_host_build_view_offsets(int cols, int rows, int width, int height, const char *trajectory, float aspect, const float *focus_v,
                                 int views, lfi_int2 *out_vn, char *err, size_t err_len)

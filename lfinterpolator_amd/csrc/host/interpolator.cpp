@@ -8,6 +8,7 @@
 #include <condition_variable>
 #include <filesystem>
 #include <future>
+#include <iomanip>
 #include <iostream>
 #include <mutex>
 #include <stdexcept>
@@ -116,8 +117,6 @@ void Interpolator::loadGPUData()
 
 void Interpolator::interpolate(std::string outputPath, std::string trajectory, float inFocus, float inRange, std::string method, float effect, float aspect)
 {
-    focus = inFocus;
-    range = inRange;
     int methodID;
     if(method == "TEN_WM")
         methodID = LFI_METHOD_TEN_WM;
@@ -127,6 +126,29 @@ void Interpolator::interpolate(std::string outputPath, std::string trajectory, f
         throw std::runtime_error("The specified interpolation method does not exist!");
 
     lfi::Parameterizer parameterizer(colsRows, resolution);
+    if(autofocus)
+    {
+        // [inFocus, inFocus + inRange] is the search interval: the region's focus curve on the first GPU, then a fixed-focus render at its minimum
+        if(perViewFocus || viewCentred || viewMaps)
+            throw std::runtime_error("Autofocus cannot be combined with a focus per view (-F), view-centred shifts (-c) or per-view focus maps (--view-maps)!");
+        if(!(inRange > 0))
+            throw std::runtime_error("Autofocus needs a search interval: a focusing range (-r) greater than zero!");
+        std::array<int, 4> r = autofocusRegion;
+        if(r[0] == 0 && r[1] == 0 && r[2] == 0 && r[3] == 0)
+            r = {0, 0, resolution.x, resolution.y};
+        const lfi::HostParams search = parameterizer.build(trajectory, inFocus, inRange, effect, aspect, viewCount);
+        const lfi_params abi = search.abi();
+        check(lfi_set_params(context, &abi));
+        lfi_focus_curve_result found{};
+        check(lfi_focus_curve(context, r[0], r[1], r[2], r[3], autofocusSteps, nullptr, &found));
+        // nine significant digits: the printed value read back as a float (-f) is the same float
+        std::cout << "autofocus: focus " << std::setprecision(9) << found.best_focus << std::setprecision(6) << " (candidate " << found.best_index << " of "
+                  << autofocusSteps << ", " << found.pixels << " px)" << std::endl;
+        inFocus = found.best_focus;
+        inRange = 0;
+    }
+    focus = inFocus;
+    range = inRange;
     lfi::HostParams params = parameterizer.build(trajectory, focus, range, effect, aspect, viewCount);
     if(unifiedFocusMap)
         params.flags |= LFI_FLAG_UNIFIED_FOCUS_MAP;

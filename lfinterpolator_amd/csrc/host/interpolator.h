@@ -4,6 +4,7 @@
 // include/lfi.h; this file includes no HIP header.
 #pragma once
 
+#include <array>
 #include <string>
 #include <vector>
 
@@ -39,6 +40,11 @@ class Interpolator
         // with setViewCentred and all-focus rendering: every view's focus map estimated at its own camera (lfi_view_focus_maps) instead of
         // one at the trajectory's centre; the maps are stored per view (map0_NN.png, map1_NN.png)
         void setViewMaps(bool on) { viewMaps = on; }
+        // autofocus: interpolate()'s focus and range give the SEARCH interval [focus, focus + range] (range > 0); the focus curve of the
+        // region {x0, y0, x1, y1} (all zero: the whole frame) is taken over `steps` candidates on the first GPU (lfi_focus_curve) and the
+        // views are rendered at its minimum as a fixed-focus render.  Not with setFocusEnd, setViewCentred, setViewMaps
+        void setAutofocus(std::array<int, 4> region, int steps) { autofocus = true; autofocusRegion = region; autofocusSteps = steps; }
+        float lastAutofocus() const { return focus; }
 
         // synthetic cols×rows grid of width×height images instead of a directory
         Interpolator(lfi::IVec2 colsRows, lfi::IVec2 resolution, uint32_t seed, int device = 0);
@@ -56,6 +62,9 @@ class Interpolator
         bool viewCentred{false};
         bool viewMaps{false};
         float focusEnd{0};
+        bool autofocus{false};
+        std::array<int, 4> autofocusRegion{0, 0, 0, 0}; // x0, y0, x1, y1
+        int autofocusSteps{32};
         std::vector<lfi_ctx *> contexts; // one per GPU; contexts[0] == context
         std::vector<int> viewStart;      // first view of each GPU's range (size gpuCount + 1)
         float focus{0};

@@ -1,6 +1,7 @@
 // main.cpp — command line of the interpolator; flags, defaults, messages and exit codes as in reference src/main.cpp:4-57
 // (-i -t -o -f -r -m -s -a -h), plus -n (views), -b (benchmark runs), -d (device), -F (focus at the last view), -c (shifts about each
-// view's own camera) and --synthetic for runs without a dataset.
+// view's own camera), --autofocus (the focus found from a region's focus curve) and --synthetic for runs without a dataset.
+#include <array>
 #include <iostream>
 #include <memory>
 #include <sstream>
@@ -35,6 +36,8 @@ int main(int argc, char **argv)
                           "-F - focusing value at the last view: the focus ramps from -f at the first view to -F at the last (a focus pull; a focal stack with a single-point trajectory such as -t 0.5,0.5,0.5,0.5); not with -r\n"
                           "-c - shift the images about each view's own camera position instead of the trajectory's centre (the default, as the reference does); with -r and with -f/-F\n"
                           "--view-maps - with -c and -r: estimate every view's focus map at its own camera (the reference's focusMapCompare.sh second run, per view) instead of one map at the trajectory's centre; writes map0_NN.png / map1_NN.png per view\n"
+                          "--autofocus [x0,y0,x1,y1] - find the focus of the region [x0,x1) x [y0,y1) (no value: the whole frame) and render all views at it (a fixed-focus render): -f and -r give the search interval [f, f+r] (-r required), the focus with the smallest colour dispersion over the region wins; prints \"autofocus: focus <value> ...\"; not with -F, -c, --view-maps\n"
+                          "--autofocus-steps - number of focus candidates searched, 2 to 256 (default=32)\n"
                           "Additional arguments:\n"
                           "-n - number of views rendered along the trajectory (default=64)\n"
                           "-b - number of timed kernel launches (default=100)\n"
@@ -59,6 +62,24 @@ int main(int argc, char **argv)
     if((!args["-i"] && !synthetic) || !args["-t"] || !args["-o"] || !args["-m"])
     {
         std::cerr << "Missing required parameters. Use -h for help." << std::endl;
+        return EXIT_FAILURE;
+    }
+
+    if(args["--autofocus"] && (args["-F"] || args["-c"] || args["--view-maps"]))
+    {
+        std::cerr << "--autofocus (one focus found for all views) cannot be combined with -F, -c or --view-maps." << std::endl;
+        return EXIT_FAILURE;
+    }
+
+    if(args["--autofocus"] && !(args["-r"] && range > 0))
+    {
+        std::cerr << "--autofocus searches the interval [f, f+r]: it needs -r with a value greater than zero." << std::endl;
+        return EXIT_FAILURE;
+    }
+
+    if(args["--autofocus-steps"] && !args["--autofocus"])
+    {
+        std::cerr << "--autofocus-steps needs --autofocus." << std::endl;
         return EXIT_FAILURE;
     }
 
@@ -109,6 +130,26 @@ int main(int argc, char **argv)
             interpolator->setViewMaps(true);
         if(args["-F"])
             interpolator->setFocusEnd(static_cast<float>(args["-F"]));
+        if(args["--autofocus"])
+        {
+            std::array<int, 4> region{0, 0, 0, 0}; // all zero: the whole frame
+            const std::string text = static_cast<std::string>(args["--autofocus"]);
+            if(!text.empty())
+            {
+                std::stringstream spec(text);
+                std::string token;
+                size_t count = 0;
+                while(std::getline(spec, token, ','))
+                {
+                    if(count < 4)
+                        region[count] = std::stoi(token);
+                    count++;
+                }
+                if(count != 4 || region[0] >= region[2] || region[1] >= region[3])
+                    throw std::runtime_error("--autofocus expects x0,y0,x1,y1 with x0 < x1 and y0 < y1");
+            }
+            interpolator->setAutofocus(region, args["--autofocus-steps"] ? static_cast<int>(args["--autofocus-steps"]) : 32);
+        }
         if(args["-q"])
         {
             std::stringstream spec(static_cast<std::string>(args["-q"]));

@@ -254,6 +254,15 @@ std::vector<float> focusRamp(float f0, float f1, int views)
     return ramp;
 }
 
+std::vector<float> focusCandidates(float focus, float range, int steps)
+{
+    std::vector<float> f(static_cast<size_t>(std::max(steps, 0)));
+    const float step = range / static_cast<float>(steps - 1);
+    for(int i = 0; i < steps; i++)
+        f[i] = std::fmaf(step, static_cast<float>(i), focus);
+    return f;
+}
+
 // reference src/interpolator.cu:194-207; at most 32 ids (the reference indexes 32 unconditionally: SURVEY.md D4) and ties
 // ordered by id (std::sort leaves them unspecified there)
 std::vector<int32_t> Parameterizer::selectFocusMapViews(Vec4 startEndPoints) const

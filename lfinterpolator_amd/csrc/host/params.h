@@ -71,5 +71,8 @@ Vec2 trajectoryCenter(Vec4 startEndPoints);
 // views focus values from f0 to f1, equally spaced: f0 + ((f1 − f0) / (views − 1))·i in float — the rounding of generateTrajectory; one
 // view gets f0
 std::vector<float> focusRamp(float f0, float f1, int views);
+// The focus candidates of lfi_focus_curve (for 32 steps: of FocusMap::estimate, reference src/kernels.cu:245-250), steps ≥ 2:
+// f_i = fmaf(range / (steps − 1), i, focus) in float — the device's arithmetic, so that nobody recomputes them with other rounding
+std::vector<float> focusCandidates(float focus, float range, int steps);
 
 } // namespace lfi

@@ -25,6 +25,8 @@ def load_host_library() -> C.CDLL:
                                               C.c_size_t]
         lib.lfi_host_focus_ramp.restype = C.c_int
         lib.lfi_host_focus_ramp.argtypes = [C.c_float, C.c_float, C.c_int, C.c_void_p]
+        lib.lfi_host_focus_candidates.restype = C.c_int
+        lib.lfi_host_focus_candidates.argtypes = [C.c_float, C.c_float, C.c_int, C.c_void_p]
         lib.lfi_host_build_view_offsets.restype = C.c_int
         lib.lfi_host_build_view_offsets.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_float, C.c_void_p, C.c_int,
                                                     C.c_void_p, C.c_char_p, C.c_size_t]
@@ -90,6 +92,14 @@ def focus_ramp(f0: float, f1: float, views: int) -> np.ndarray:
     out = np.zeros(max(views, 1), dtype=np.float32)
     if load_host_library().lfi_host_focus_ramp(f0, f1, views, out.ctypes.data) != 0:
         raise ValueError("views must be positive")
+    return out
+
+
+def focus_candidates(focus: float, range: float, steps: int = 32) -> np.ndarray:
+    """The focus candidates of Context.focus_curve (for 32 steps: of the focus-map estimate): fmaf(range / (steps − 1), i, focus) in float32."""
+    out = np.zeros(max(steps, 0), dtype=np.float32)
+    if load_host_library().lfi_host_focus_candidates(focus, range, steps, out.ctypes.data) != 0:
+        raise ValueError("steps must be at least 2")
     return out
 
 
