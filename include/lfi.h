@@ -310,6 +310,27 @@ typedef struct lfi_focus_curve_result {
     uint64_t pixels;     /* pixels of the region */
 } lfi_focus_curve_result;
 int lfi_focus_curve(lfi_ctx *ctx, int x0, int y0, int x1, int y1, int steps, uint64_t *out_cost, lfi_focus_curve_result *out);
+/* Focus tiles: the focus curve of EVERY tile of a tiles_x x tiles_y grid over the frame, from one factored estimate — a grid of autofocus
+ * points, a coarse depth layout of the scene, or the interval an all-focus render should search (lfi_host_focus_auto_range).
+ *  - tile (tx, ty) is the rectangle [tx * W / tiles_x, (tx + 1) * W / tiles_x) x [ty * H / tiles_y, (ty + 1) * H / tiles_y), the divisions
+ *    integer divisions of 64-bit products (lfi_host_focus_tile_rect): the tiles cover the frame exactly once and differ by at most one pixel
+ *    per axis.  1 <= tiles_x <= min(W, 256), 1 <= tiles_y <= min(H, 256);
+ *  - out_cost[tile][i] ([tiles_y][tiles_x][LFI_FOCUS_TILE_STEPS], may be NULL) and out[tile] ([tiles_y][tiles_x]) are, BY DEFINITION, what
+ *    lfi_focus_curve(ctx, the tile's rectangle, LFI_FOCUS_TILE_STEPS, ...) returns: the same candidates (the estimate's 32), the same integer
+ *    cost, the same first-strict-minimum rule, the same FLT_MIN departure, the same use of the current lfi_params;
+ *  - it is computed differently: the factored focus-map estimate (lfi_focus_map's default variant) runs up to its last pass, and a tile-cost
+ *    pass in the pick's place adds up the per-pixel cost the pick would throw away (csrc/hip/focus_tiles.hpp) — all tiles for about the price
+ *    of one focus map.  The estimate variant set with lfi_set_variant(LFI_KERNEL_FOCUS_ESTIMATE, ...) is followed: "factored_direct" takes its
+ *    range pass; a variant that is not a factored one (or a factored estimate that declines) computes the tiles with lfi_focus_curve's
+ *    kernels, one region per tile, inside the same call — the same numbers, slower;
+ *  - synchronous; ordered after pending uploads and the work on the context's stream like lfi_focus_map, and joined with the side stream the
+ *    estimate uses; one device-to-host copy of tiles * (32 * 8 + 16) bytes.  It writes neither the maps nor the views.  It builds or reuses
+ *    the estimate's padded planes exactly as lfi_focus_map does and keeps their bookkeeping: a later lfi_focus_map gives the same bytes as
+ *    without the call.  Its device memory is counted in lfi_memory.workspace_bytes;
+ *  - LFI_EINVAL: a grid outside the limits above, and wherever lfi_focus_curve returns it (no grid or no parameters; range <= 0;
+ *    n_focus_ids == 0; out == NULL; a row window set; after lfi_release_inputs).  The context stays usable. */
+#define LFI_FOCUS_TILE_STEPS 32   /* the estimate's candidates, src/kernels.cu:245 */
+int lfi_focus_tiles(lfi_ctx *ctx, int tiles_x, int tiles_y, uint64_t *out_cost, lfi_focus_curve_result *out);
 /* One launch of Tensors::process / Standard::process (src/interpolator.cu:274-288) for views [v0, v1).
  * all_focus != 0 selects the <true> instantiations (per-pixel focus from the focus map). */
 int lfi_render(lfi_ctx *ctx, int method, int all_focus, int v0, int v1);
@@ -334,7 +355,7 @@ typedef struct lfi_memory {
     size_t derived_bytes;   /* planar copy of the inputs: 3 bytes per pixel and image (+ padding) */
     size_t views_bytes;     /* output planes */
     size_t maps_bytes;      /* focus maps (maps 0 / 1, and the per-view maps when allocated) */
-    size_t workspace_bytes; /* focus-map workspace + lfi_focus_curve's partial sums + (planar view layout) the RGBA scratch copy of the views that renders other than TEN_WM and
+    size_t workspace_bytes; /* focus-map workspace + lfi_focus_curve's / lfi_focus_tiles' curves and partial sums + (planar view layout) the RGBA scratch copy of the views that renders other than TEN_WM and
                              * STD on more than 64 images go through, and the one-plane staging buffer of downloads */
     float derived_build_ms;
 } lfi_memory;
@@ -439,7 +460,7 @@ int lfi_debug_mfma_f16_chain(lfi_ctx *ctx, int shape, int k, const uint16_t *a_3
  *   SCRATCH          the planar layout's RGBA scratch copy of the views, the download staging plane, the pre-quantisation buffer, the
  *                    quilt buffer and lfi_render_stream's second set of views
  *   MAPS             both focus maps
- *   FOCUS_WORKSPACE  all of the focus-map estimate's workspace, and lfi_focus_curve's (the curve, the result and the partial sums)
+ *   FOCUS_WORKSPACE  all of the focus-map estimate's workspace, and lfi_focus_curve's / lfi_focus_tiles' (the curves, the results and the partial sums)
  *   DERIVED          the planar copy of the inputs — refused (LFI_EINVAL) after lfi_release_inputs: it is then the only copy
  *   VIEW_MAPS        the per-view focus maps of lfi_view_focus_maps, every view's pair */
 enum { LFI_POISON_VIEWS = 1, LFI_POISON_SCRATCH = 2, LFI_POISON_MAPS = 4, LFI_POISON_FOCUS_WORKSPACE = 8, LFI_POISON_DERIVED = 16,

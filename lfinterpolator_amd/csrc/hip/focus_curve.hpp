@@ -17,6 +17,7 @@
 //                         (one wave) walks the region's rows blockIdx.y, blockIdx.y + gridDim.y, … and stores its accumulators once, as
 //                         partial[candidate][workgroup].  A region too small to fill the GPU with one wave per 128 pixels of a row is also
 //                         split along the candidates (blockIdx.z): a wave's life is its candidates × images × 9 dependent taps.
+//   (focus_curve_sum and focus_curve_pick also finish lfi_focus_tiles' curves, focus_tiles.hpp: one more grid dimension, the tile)
 //   focus_curve_sum       one workgroup per candidate sums that candidate's partials in a fixed order → cost[candidate].
 //   focus_curve_pick      the first strict minimum of cost[] (MinDispersion's rule) → {best_index, best_focus, pixels}.
 // The candidates are a run-time loop (2 ≤ steps ≤ 256), not the estimate's unrolled 32.
@@ -37,7 +38,13 @@ struct FocusCurveArgs
     uint64_t pixels;
     uint64_t *partial;      // [steps][n_wg]
     uint64_t *cost;         // [steps], followed by the result (lfi_focus_curve_result's layout: i32, f32, u64)
+    int32_t tiled;          // lfi_focus_tiles: focus_curve_sum / focus_curve_pick run once per tile of a gridDim tiles_x × tiles_y grid — tile t's
+                            // partials are partial[t][steps][n_wg], its curve and result lie at cost + t · (steps + 2), its pixels are its rectangle's
 };
+
+// focus_curve_sum's grid is steps × tiles_x × tiles_y, focus_curve_pick's tiles_x × tiles_y; lfi_focus_curve launches them with one tile (tile 0)
+constexpr int FOCUS_CURVE_RESULT_WORDS = 2;
+static_assert(sizeof(lfi_focus_curve_result) == sizeof(uint64_t) * FOCUS_CURVE_RESULT_WORDS, "the result follows the curve in u64 words");
 
 __device__ __forceinline__ float focus_curve_candidate(const KernelArgs &a, const int steps, const int i)
 {
@@ -203,7 +210,8 @@ __global__ void __launch_bounds__(64, WPE) focus_curve_partial(const KernelArgs 
 __global__ void __launch_bounds__(256) focus_curve_sum(const FocusCurveArgs q)
 {
     __shared__ uint64_t part[256];
-    const uint64_t *src = q.partial + (size_t)blockIdx.x * q.n_wg;
+    const size_t tile = (size_t)blockIdx.z * gridDim.y + blockIdx.y;
+    const uint64_t *src = q.partial + (tile * gridDim.x + blockIdx.x) * q.n_wg;
     uint64_t s = 0;
     for(uint32_t w = threadIdx.x; w < q.n_wg; w += 256)
         s += src[w];
@@ -216,7 +224,7 @@ __global__ void __launch_bounds__(256) focus_curve_sum(const FocusCurveArgs q)
         __syncthreads();
     }
     if(threadIdx.x == 0)
-        q.cost[blockIdx.x] = part[0];
+        q.cost[tile * (gridDim.x + FOCUS_CURVE_RESULT_WORDS) + blockIdx.x] = part[0];
 }
 
 // the first candidate with the strictly smallest cost (MinDispersion::add, src/kernels.cu:225-231: strict <, candidates in ascending order)
@@ -225,7 +233,9 @@ __global__ void __launch_bounds__(256) focus_curve_pick(const KernelArgs a, cons
     __shared__ uint64_t best_cost[256];
     __shared__ int32_t best_at[256];
     const int t = threadIdx.x;
-    best_cost[t] = t < q.steps ? q.cost[t] : ~0ull;
+    const size_t tile = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
+    uint64_t *cost = q.cost + tile * (q.steps + FOCUS_CURVE_RESULT_WORDS);
+    best_cost[t] = t < q.steps ? cost[t] : ~0ull;
     best_at[t] = t < q.steps ? t : 0x7fffffff;
     __syncthreads();
     for(int m = 128; m >= 1; m >>= 1)
@@ -248,7 +258,12 @@ __global__ void __launch_bounds__(256) focus_curve_pick(const KernelArgs a, cons
         r.best_index = best_at[0];
         r.best_focus = focus_curve_candidate(a, q.steps, best_at[0]);
         r.pixels = q.pixels;
-        *reinterpret_cast<lfi_focus_curve_result *>(q.cost + q.steps) = r;
+        if(q.tiled) // tile (blockIdx.x, blockIdx.y) begins at floor(t · size / tiles) on either axis (lfi.h)
+        {
+            const int64_t bx = blockIdx.x, by = blockIdx.y, nx = gridDim.x, ny = gridDim.y;
+            r.pixels = uint64_t((bx + 1) * a.width / nx - bx * a.width / nx) * uint64_t((by + 1) * a.height / ny - by * a.height / ny);
+        }
+        *reinterpret_cast<lfi_focus_curve_result *>(cost + q.steps) = r;
     }
 }
 

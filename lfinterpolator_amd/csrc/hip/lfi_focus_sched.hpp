@@ -1,6 +1,6 @@
 // lfi_focus_sched.hpp — scheduling of the focus-map estimate: the factored pipeline's workspace and its two-stream pass graph
 // (focus_factored.hpp), and the choice between it, the row-window path and the other estimate variants; the focus curve's workspace and
-// its three launches (focus_curve.hpp).
+// its three launches (focus_curve.hpp); the focus tiles' pass behind the factored estimate (focus_tiles.hpp).
 // Replaces the FocusMap::estimate / FocusMap::filter launches (reference src/interpolator.cu:261-266).
 // Included by lfi_hip.hip only (one translation unit), after lfi_context.hpp.
 #pragma once
@@ -8,6 +8,7 @@
 #include "lfi_context.hpp"
 #include "focus_factored.hpp"
 #include "focus_curve.hpp"
+#include "focus_tiles.hpp"
 
 namespace {
 
@@ -43,11 +44,14 @@ bool focus_pad_shift(const lfi_ctx *ctx, const lfi_float2 *offsets, int n, int *
     return true;
 }
 
-// the factored estimate (focus_factored.hpp): carve the workspace, then plan → pad → E → exact keys → pick.
+// the factored estimate (focus_factored.hpp) up to and including focus_line_keys: carve the workspace, then plan → pad → E → exact keys.
+// Behind it the workspace *w_out holds E for every candidate and K for every flagged (pixel, candidate) pair; the consumer — the pick
+// (launch_focus_pick) or the tile costs (launch_focus_tiles) — is enqueued next on the compute stream.
 // Returns LFI_OK with *done = false when the padded planes would be unreasonably large (the caller takes another variant).
 // direct_range: the range pass by focus_range (rounds 1-4's kernel: every use loads and widens its own samples) even where focus_range_t
 // applies (variant "factored_direct": the second implementation in the parity tests, and the A/B partner)
-int launch_focus_factored(lfi_ctx *ctx, const KernelArgs &a, FocusJob &job, bool *done, bool direct_range)
+// *e_32bit_out: a candidate's plane of E lies behind one buffer descriptor (focus_pick_sep)
+int launch_focus_factored_keys(lfi_ctx *ctx, const KernelArgs &a, FocusJob &job, bool *done, bool direct_range, lfi::FocusWork *w_out, bool *e_32bit_out)
 {
     *done = false;
     job.padded = 0;
@@ -251,6 +255,17 @@ int launch_focus_factored(lfi_ctx *ctx, const KernelArgs &a, FocusJob &job, bool
     LFI_HIP(ctx, hipEventRecord(ctx->ev_join, aux));
     LFI_HIP(ctx, hipStreamWaitEvent(st, ctx->ev_join, 0));
     hipLaunchKernelGGL(lfi::focus_line_keys, dim3(ctx->cu_count * 8), dim3(256), 0, st, a, w);
+    *w_out = w;
+    *e_32bit_out = e_32bit;
+    *done = true;
+    return LFI_OK;
+}
+
+// the factored estimate's last pass: per pixel the first strict minimum of the keys → map 0 (the caller filters it into map 1)
+int launch_focus_pick(lfi_ctx *ctx, const KernelArgs &a, const lfi::FocusWork &w, bool e_32bit, bool direct_range)
+{
+    const int W = ctx->width, H = ctx->height, rx = ctx->radius[0], ry = ctx->radius[1];
+    hipStream_t st = ctx->stream;
     {
         // two pixels per lane need dword-aligned sample pairs: even radius_x (the reference's is)
         const int ppl = (rx % 2 == 0 && W >= 2) ? 2 : 1;
@@ -270,8 +285,19 @@ int launch_focus_factored(lfi_ctx *ctx, const KernelArgs &a, FocusJob &job, bool
             hipLaunchKernelGGL(lfi::focus_pick<1>, dim3(nblocks), dim3(256), 0, st, a, w, striped);
     }
     LFI_HIP(ctx, hipGetLastError());
-    *done = true;
     return LFI_OK;
+}
+
+// the whole factored estimate: plan → pad → E → exact keys → pick
+int launch_focus_factored(lfi_ctx *ctx, const KernelArgs &a, FocusJob &job, bool *done, bool direct_range)
+{
+    lfi::FocusWork w{};
+    bool e_32bit = false;
+    if(int rc = launch_focus_factored_keys(ctx, a, job, done, direct_range, &w, &e_32bit))
+        return rc;
+    if(!*done)
+        return LFI_OK;
+    return launch_focus_pick(ctx, a, w, e_32bit, direct_range);
 }
 
 // The focus curve of the region [x0, x1) × [y0, y1) (lfi_focus_curve; the caller has checked the arguments): partial sums per workgroup and
@@ -305,6 +331,93 @@ int launch_focus_curve(lfi_ctx *ctx, const KernelArgs &a, int x0, int y0, int x1
     hipLaunchKernelGGL((lfi::focus_curve_partial<PPL, 4>), dim3(blocks_x, blocks_y, blocks_z), dim3(64), 0, st, a, q);
     hipLaunchKernelGGL(lfi::focus_curve_sum, dim3(steps), dim3(256), 0, st, q);
     hipLaunchKernelGGL(lfi::focus_curve_pick, dim3(1), dim3(256), 0, st, a, q);
+    LFI_HIP(ctx, hipGetLastError());
+    *d_head = ctx->curve_ws.get();
+    return LFI_OK;
+}
+
+// The focus curves of the tiles_x × tiles_y tiles (lfi_focus_tiles; the caller has checked the arguments).  ctx->curve_ws holds, per tile, the
+// curve and its result back to back (FOCUS_TILE_HEAD bytes each, row-major over the tiles: what the host copies), then the partial sums.
+//   factored: behind launch_focus_factored_keys, focus_tile_costs in the pick's place, then focus_curve_sum / focus_curve_pick over all tiles —
+//             three launches whatever the grid;
+//   else (another estimate variant, or the factored estimate declined): lfi_focus_curve's three launches tile by tile — the same numbers.
+constexpr size_t FOCUS_TILE_HEAD = sizeof(uint64_t) * lfi::FOCUS_STEPS + sizeof(lfi_focus_curve_result);
+
+int launch_focus_tiles(lfi_ctx *ctx, const KernelArgs &a, int tiles_x, int tiles_y, const uint8_t **d_head)
+{
+    const int W = ctx->width, H = ctx->height;
+    const size_t tiles = size_t(tiles_x) * size_t(tiles_y);
+    const size_t head_bytes = (FOCUS_TILE_HEAD * tiles + 255) / 256 * 256;
+    hipStream_t st = ctx->stream;
+    lfi::FocusCurveArgs q{};
+    q.steps = lfi::FOCUS_STEPS;
+    bool done = false;
+    if((ctx->focus_variant == 0 || ctx->focus_variant == 4) && W <= 65535 && H <= 65535)
+    {
+        FocusJob job;
+        job.offsets = ctx->h_focus_offsets.data();
+        job.ids = ctx->h_focus_ids.data();
+        job.n_ids = ctx->n_focus_ids;
+        lfi::FocusWork w{};
+        bool e_32bit = false;
+        if(int rc = launch_focus_factored_keys(ctx, a, job, &done, ctx->focus_variant == 4, &w, &e_32bit))
+            return rc;
+        if(done)
+        {
+            const int ppl = (ctx->radius[0] % 2 == 0 && W >= 2) ? 2 : 1; // as the pick: dword sample pairs need an even radius_x
+            const int tile_w = (W + tiles_x - 1) / tiles_x, tile_h = (H + tiles_y - 1) / tiles_y; // the widest, the tallest
+            lfi::FocusTileArgs t{};
+            t.tiles_x = tiles_x, t.tiles_y = tiles_y;
+            t.chunks = (tile_w + (ppl - 1) + 64 * ppl - 1) / (64 * ppl); // (+1: a tile's first column rounded down to even)
+            // one row per wave (the pick's shape) while that keeps the partials small: beyond 64 Ki workgroups a wave walks more rows
+            const size_t wg_1 = tiles * t.chunks * ((tile_h + 3) / 4);
+            t.rows_per_wave = int(std::min<size_t>(lfi::FOCUS_TILE_MAX_ROWS_PER_WAVE, std::max<size_t>(1, (wg_1 + 65535) / 65536)));
+            t.rows_per_wave = std::min(t.rows_per_wave, (tile_h + 3) / 4);
+            t.bands = (tile_h + 4 * t.rows_per_wave - 1) / (4 * t.rows_per_wave);
+            t.n_wg = uint32_t(t.chunks) * uint32_t(t.bands);
+            const size_t n_blocks = tiles * t.n_wg;
+            if(n_blocks > 0x7fffffffu)
+                return fail(ctx, LFI_EINVAL, "lfi_focus_tiles: too many tiles for an image of this size");
+            LFI_HIP(ctx, ctx->curve_ws.reserve(head_bytes + sizeof(uint64_t) * lfi::FOCUS_STEPS * n_blocks));
+            q.cost = reinterpret_cast<uint64_t *>(ctx->curve_ws.get());
+            q.partial = t.partial = reinterpret_cast<uint64_t *>(ctx->curve_ws.get() + head_bytes);
+            q.n_wg = t.n_wg;
+            q.tiled = 1;
+            if(ppl == 2)
+                hipLaunchKernelGGL(lfi::focus_tile_costs<2>, dim3(uint32_t(n_blocks)), dim3(256), 0, st, a, w, t);
+            else
+                hipLaunchKernelGGL(lfi::focus_tile_costs<1>, dim3(uint32_t(n_blocks)), dim3(256), 0, st, a, w, t);
+            hipLaunchKernelGGL(lfi::focus_curve_sum, dim3(lfi::FOCUS_STEPS, tiles_x, tiles_y), dim3(256), 0, st, q);
+            hipLaunchKernelGGL(lfi::focus_curve_pick, dim3(tiles_x, tiles_y), dim3(256), 0, st, a, q);
+            LFI_HIP(ctx, hipGetLastError());
+            *d_head = ctx->curve_ws.get();
+            return LFI_OK;
+        }
+    }
+    // tile by tile: focus_curve_partial's shape as in launch_focus_curve, the partials' room shared (the launches follow each other on one stream)
+    constexpr int PPL = 2;
+    const int tile_w = (W + tiles_x - 1) / tiles_x, tile_h = (H + tiles_y - 1) / tiles_y;
+    const uint32_t blocks_x = uint32_t((tile_w + 64 * PPL - 1) / (64 * PPL));
+    const uint32_t blocks_y_max = std::min(uint32_t(tile_h), std::max(1u, 8192u / blocks_x));
+    LFI_HIP(ctx, ctx->curve_ws.reserve(head_bytes + sizeof(uint64_t) * lfi::FOCUS_STEPS * size_t(blocks_x) * blocks_y_max));
+    q.partial = reinterpret_cast<uint64_t *>(ctx->curve_ws.get() + head_bytes);
+    for(int ty = 0; ty < tiles_y; ty++)
+        for(int tx = 0; tx < tiles_x; tx++)
+        {
+            q.x0 = lfi::focus_tile_edge(tx, W, tiles_x), q.x1 = lfi::focus_tile_edge(tx + 1, W, tiles_x);
+            q.y0 = lfi::focus_tile_edge(ty, H, tiles_y), q.y1 = lfi::focus_tile_edge(ty + 1, H, tiles_y);
+            const uint32_t bx = uint32_t((q.x1 - q.x0 + 64 * PPL - 1) / (64 * PPL));
+            const uint32_t by = std::min(uint32_t(q.y1 - q.y0), blocks_y_max);
+            q.n_wg = bx * by;
+            const uint32_t want_z = std::min(uint32_t(q.steps), std::max(1u, uint32_t(ctx->cu_count) * 16u / q.n_wg));
+            q.steps_per_wg = (q.steps + int(want_z) - 1) / int(want_z);
+            const uint32_t bz = uint32_t((q.steps + q.steps_per_wg - 1) / q.steps_per_wg);
+            q.pixels = uint64_t(q.x1 - q.x0) * uint64_t(q.y1 - q.y0);
+            q.cost = reinterpret_cast<uint64_t *>(ctx->curve_ws.get() + FOCUS_TILE_HEAD * (size_t(ty) * tiles_x + tx));
+            hipLaunchKernelGGL((lfi::focus_curve_partial<PPL, 4>), dim3(bx, by, bz), dim3(64), 0, st, a, q);
+            hipLaunchKernelGGL(lfi::focus_curve_sum, dim3(q.steps), dim3(256), 0, st, q);
+            hipLaunchKernelGGL(lfi::focus_curve_pick, dim3(1), dim3(256), 0, st, a, q);
+        }
     LFI_HIP(ctx, hipGetLastError());
     *d_head = ctx->curve_ws.get();
     return LFI_OK;

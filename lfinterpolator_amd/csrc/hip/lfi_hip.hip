@@ -894,6 +894,47 @@ int lfi_focus_curve(lfi_ctx *ctx, int x0, int y0, int x1, int y1, int steps, uin
     return LFI_OK;
 }
 
+int lfi_focus_tiles(lfi_ctx *ctx, int tiles_x, int tiles_y, uint64_t *out_cost, lfi_focus_curve_result *out)
+{
+    if(!ctx)
+        return LFI_EINVAL;
+    if(ctx->inputs_released)
+        return fail(ctx, LFI_EINVAL, "the RGBA inputs were released (lfi_release_inputs): the focus tiles need them - upload the images again (lfi_set_grid)");
+    if(!ctx->grid || !ctx->have_params)
+        return fail(ctx, LFI_EINVAL, "lfi_set_grid / lfi_set_params have not been called");
+    if(ctx->windowed)
+        return fail(ctx, LFI_EINVAL, "lfi_focus_tiles does not work on a row window");
+    if(!out)
+        return fail(ctx, LFI_EINVAL, "lfi_focus_tiles: out is NULL");
+    if(ctx->n_focus_ids < 1)
+        return fail(ctx, LFI_EINVAL, "no focus_map_ids in the parameters");
+    if(!(ctx->range > 0.0f))
+        return fail(ctx, LFI_EINVAL, "focus range must be > 0 for the focus tiles: [focus, focus + range] is the search interval");
+    if(tiles_x < 1 || tiles_y < 1 || tiles_x > std::min(ctx->width, 256) || tiles_y > std::min(ctx->height, 256))
+        return fail(ctx, LFI_EINVAL, "lfi_focus_tiles: the grid must have 1 to min(width, 256) columns and 1 to min(height, 256) rows of tiles");
+    if(int rc = bind(ctx))
+        return rc;
+    if(int rc = join_uploads(ctx))
+        return rc;
+    const KernelArgs a = make_args(ctx, 0, ctx->views_n, LFI_METHOD_STD);
+    const uint8_t *d_head = nullptr;
+    if(int rc = launch_focus_tiles(ctx, a, tiles_x, tiles_y, &d_head))
+        return rc;
+    // per tile the curve and the result lie back to back: one copy of tiles · (32 · 8 + 16) bytes
+    const size_t tiles = size_t(tiles_x) * size_t(tiles_y);
+    constexpr size_t WORDS = FOCUS_TILE_HEAD / sizeof(uint64_t);
+    std::vector<uint64_t> head(tiles * WORDS);
+    LFI_HIP(ctx, hipMemcpyAsync(head.data(), d_head, FOCUS_TILE_HEAD * tiles, hipMemcpyDeviceToHost, ctx->stream));
+    LFI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for(size_t t = 0; t < tiles; t++)
+    {
+        if(out_cost)
+            std::memcpy(out_cost + t * LFI_FOCUS_TILE_STEPS, head.data() + t * WORDS, sizeof(uint64_t) * LFI_FOCUS_TILE_STEPS);
+        std::memcpy(out + t, head.data() + t * WORDS + LFI_FOCUS_TILE_STEPS, sizeof(lfi_focus_curve_result));
+    }
+    return LFI_OK;
+}
+
 // the per-view maps [views_n][2][H][W], allocated (or grown) on first use; renders in flight may read the old buffer
 static int ensure_view_maps(lfi_ctx *ctx)
 {

@@ -68,6 +68,36 @@ int lfi_host_focus_candidates(float focus, float range, int steps, float *out)
     return 0;
 }
 
+// tile (tx, ty) of lfi_focus_tiles' tiles_x × tiles_y grid over a width × height frame: rect = {x0, y0, x1, y1}; returns 0, or -1 for a grid
+// outside [1, width] × [1, height] or a tile outside the grid
+int lfi_host_focus_tile_rect(int width, int height, int tiles_x, int tiles_y, int tx, int ty, int32_t rect[4])
+{
+    if(!rect || tiles_x < 1 || tiles_y < 1 || tiles_x > width || tiles_y > height || tx < 0 || ty < 0 || tx >= tiles_x || ty >= tiles_y)
+        return -1;
+    const std::array<int, 4> r = lfi::focusTileRect(width, height, tiles_x, tiles_y, tx, ty);
+    for(int k = 0; k < 4; k++)
+        rect[k] = r[k];
+    return 0;
+}
+
+// the interval an all-focus render should search, from the tiles' best candidates of a search over [focus, focus + range] (--auto-range):
+// the candidates kept are lo_hi = {max(min index − 1, 0), min(max index + 1, 31)}, *out_focus = candidate lo, *out_range = candidate hi −
+// candidate lo in float; returns 0, or -1 for no tiles, an index outside [0, 31] or range <= 0
+int lfi_host_focus_auto_range(const int32_t *best_index, int tiles, float focus, float range, float *out_focus, float *out_range, int32_t lo_hi[2])
+{
+    if(!best_index || tiles < 1 || !out_focus || !out_range || !lo_hi || !(range > 0.0f))
+        return -1;
+    for(int t = 0; t < tiles; t++)
+        if(best_index[t] < 0 || best_index[t] >= LFI_FOCUS_TILE_STEPS)
+            return -1;
+    const lfi::FocusAutoRange r = lfi::focusAutoRange(best_index, static_cast<size_t>(tiles), focus, range);
+    *out_focus = r.focus;
+    *out_range = r.range;
+    lo_hi[0] = r.lo;
+    lo_hi[1] = r.hi;
+    return 0;
+}
+
 // per-view focus: out_vn[views][N] = the focused offsets of Parameterizer::offsets at focus_v[v] (the rows lfi_set_view_offsets takes)
 int lfi_host_build_view_offsets(int cols, int rows, int width, int height, const char *trajectory, float aspect, const float *focus_v,
                                 int views, lfi_int2 *out_vn, char *err, size_t err_len)

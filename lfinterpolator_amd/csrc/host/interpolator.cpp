@@ -126,6 +126,44 @@ void Interpolator::interpolate(std::string outputPath, std::string trajectory, f
         throw std::runtime_error("The specified interpolation method does not exist!");
 
     lfi::Parameterizer parameterizer(colsRows, resolution);
+    // the minima of a grid of focus tiles over the search interval [inFocus, inFocus + inRange], on the first GPU
+    const auto tilesOver = [&](lfi::IVec2 grid) {
+        if(!(inRange > 0))
+            throw std::runtime_error("Focus tiles need a search interval: a focusing range (-r) greater than zero!");
+        const lfi::HostParams search = parameterizer.build(trajectory, inFocus, inRange, effect, aspect, viewCount);
+        const lfi_params abi = search.abi();
+        check(lfi_set_params(context, &abi));
+        std::vector<lfi_focus_curve_result> found(static_cast<size_t>(std::max(grid.x, 0)) * std::max(grid.y, 0));
+        check(lfi_focus_tiles(context, grid.x, grid.y, nullptr, found.data()));
+        return found;
+    };
+    if(focusTiles.x != 0 || focusTiles.y != 0)
+    {
+        const std::vector<lfi_focus_curve_result> found = tilesOver(focusTiles);
+        std::cout << "focus tiles: " << focusTiles.x << " x " << focusTiles.y << std::endl;
+        for(int ty = 0; ty < focusTiles.y; ty++)
+            for(int tx = 0; tx < focusTiles.x; tx++)
+            {
+                const lfi_focus_curve_result &r = found[static_cast<size_t>(ty) * focusTiles.x + tx];
+                std::cout << "tile " << tx << " " << ty << " index " << r.best_index << " focus " << std::setprecision(9) << r.best_focus
+                          << std::setprecision(6) << std::endl;
+            }
+    }
+    if(autoRange.x != 0 || autoRange.y != 0)
+    {
+        if(autofocus)
+            throw std::runtime_error("Auto range (an all-focus render) cannot be combined with autofocus (a fixed-focus render)!");
+        const std::vector<lfi_focus_curve_result> found = tilesOver(autoRange);
+        std::vector<int32_t> best(found.size());
+        for(size_t t = 0; t < found.size(); t++)
+            best[t] = found[t].best_index;
+        const lfi::FocusAutoRange narrowed = lfi::focusAutoRange(best.data(), best.size(), inFocus, inRange);
+        // nine significant digits: the printed values read back as floats (-f, -r) are the same floats
+        std::cout << "auto-range: focus " << std::setprecision(9) << narrowed.focus << " range " << narrowed.range << std::setprecision(6)
+                  << " (candidates " << narrowed.lo << ".." << narrowed.hi << ")" << std::endl;
+        inFocus = narrowed.focus;
+        inRange = narrowed.range;
+    }
     if(autofocus)
     {
         // [inFocus, inFocus + inRange] is the search interval: the region's focus curve on the first GPU, then a fixed-focus render at its minimum

@@ -45,6 +45,12 @@ class Interpolator
         // views are rendered at its minimum as a fixed-focus render.  Not with setFocusEnd, setViewCentred, setViewMaps
         void setAutofocus(std::array<int, 4> region, int steps) { autofocus = true; autofocusRegion = region; autofocusSteps = steps; }
         float lastAutofocus() const { return focus; }
+        // focus tiles: before anything is rendered, the focus curve's minimum of every tile of a columns × rows grid over the frame
+        // (lfi_focus_tiles on the first GPU, over [focus, focus + range], range > 0) is printed, one line per tile
+        void setFocusTiles(lfi::IVec2 grid) { focusTiles = grid; }
+        // auto range, for all-focus renders: the tiles' minima over [focus, focus + range] give the interval the map is then estimated over
+        // and the views rendered with (lfi::focusAutoRange) instead of the interval given.  Not with setAutofocus
+        void setAutoRange(lfi::IVec2 grid) { autoRange = grid; }
 
         // synthetic cols×rows grid of width×height images instead of a directory
         Interpolator(lfi::IVec2 colsRows, lfi::IVec2 resolution, uint32_t seed, int device = 0);
@@ -65,6 +71,8 @@ class Interpolator
         bool autofocus{false};
         std::array<int, 4> autofocusRegion{0, 0, 0, 0}; // x0, y0, x1, y1
         int autofocusSteps{32};
+        lfi::IVec2 focusTiles{0, 0}; // 0: off
+        lfi::IVec2 autoRange{0, 0};  // 0: off
         std::vector<lfi_ctx *> contexts; // one per GPU; contexts[0] == context
         std::vector<int> viewStart;      // first view of each GPU's range (size gpuCount + 1)
         float focus{0};

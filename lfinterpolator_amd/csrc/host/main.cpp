@@ -1,6 +1,7 @@
 // main.cpp — command line of the interpolator; flags, defaults, messages and exit codes as in reference src/main.cpp:4-57
 // (-i -t -o -f -r -m -s -a -h), plus -n (views), -b (benchmark runs), -d (device), -F (focus at the last view), -c (shifts about each
-// view's own camera), --autofocus (the focus found from a region's focus curve) and --synthetic for runs without a dataset.
+// view's own camera), --autofocus (the focus found from a region's focus curve), --focus-tiles / --auto-range (the focus of every tile of a
+// grid; the search interval of an all-focus render found from it) and --synthetic for runs without a dataset.
 #include <array>
 #include <iostream>
 #include <memory>
@@ -38,6 +39,8 @@ int main(int argc, char **argv)
                           "--view-maps - with -c and -r: estimate every view's focus map at its own camera (the reference's focusMapCompare.sh second run, per view) instead of one map at the trajectory's centre; writes map0_NN.png / map1_NN.png per view\n"
                           "--autofocus [x0,y0,x1,y1] - find the focus of the region [x0,x1) x [y0,y1) (no value: the whole frame) and render all views at it (a fixed-focus render): -f and -r give the search interval [f, f+r] (-r required), the focus with the smallest colour dispersion over the region wins; prints \"autofocus: focus <value> ...\"; not with -F, -c, --view-maps\n"
                           "--autofocus-steps - number of focus candidates searched, 2 to 256 (default=32)\n"
+                          "--focus-tiles CxR - print the focus of every tile of a grid of C columns x R rows over the frame, searched in [f, f+r] (-r required): \"focus tiles: C x R\", then \"tile <tx> <ty> index <i> focus <value>\" per tile, row by row; the render follows as usual\n"
+                          "--auto-range [CxR] - for all-focus renders (-r): find the interval the scene occupies from the focus tiles of a C x R grid (default 16x9) over [f, f+r] - from one candidate below the nearest tile's focus to one above the farthest's - and estimate the map and render with it in place of -f, -r; prints \"auto-range: focus <f'> range <r'> (candidates <lo>..<hi>)\"; not with --autofocus\n"
                           "Additional arguments:\n"
                           "-n - number of views rendered along the trajectory (default=64)\n"
                           "-b - number of timed kernel launches (default=100)\n"
@@ -80,6 +83,18 @@ int main(int argc, char **argv)
     if(args["--autofocus-steps"] && !args["--autofocus"])
     {
         std::cerr << "--autofocus-steps needs --autofocus." << std::endl;
+        return EXIT_FAILURE;
+    }
+
+    if((args["--focus-tiles"] || args["--auto-range"]) && !(args["-r"] && range > 0))
+    {
+        std::cerr << "--focus-tiles and --auto-range search the interval [f, f+r]: they need -r with a value greater than zero." << std::endl;
+        return EXIT_FAILURE;
+    }
+
+    if(args["--auto-range"] && args["--autofocus"])
+    {
+        std::cerr << "--auto-range (an all-focus render) cannot be combined with --autofocus (a fixed-focus render)." << std::endl;
         return EXIT_FAILURE;
     }
 
@@ -149,6 +164,30 @@ int main(int argc, char **argv)
                     throw std::runtime_error("--autofocus expects x0,y0,x1,y1 with x0 < x1 and y0 < y1");
             }
             interpolator->setAutofocus(region, args["--autofocus-steps"] ? static_cast<int>(args["--autofocus-steps"]) : 32);
+        }
+        // a grid of tiles "CxR" (columns x rows)
+        const auto tileGrid = [](const std::string &text, const char *flag) {
+            const size_t cut = text.find_first_of("xX");
+            lfi::IVec2 grid{0, 0};
+            try
+            {
+                if(cut != std::string::npos)
+                    grid = {std::stoi(text.substr(0, cut)), std::stoi(text.substr(cut + 1))};
+            }
+            catch(const std::exception &)
+            {
+                grid = {0, 0};
+            }
+            if(grid.x < 1 || grid.y < 1)
+                throw std::runtime_error(std::string(flag) + " expects CxR, columns x rows of tiles, both at least 1");
+            return grid;
+        };
+        if(args["--focus-tiles"])
+            interpolator->setFocusTiles(tileGrid(static_cast<std::string>(args["--focus-tiles"]), "--focus-tiles"));
+        if(args["--auto-range"])
+        {
+            const std::string text = static_cast<std::string>(args["--auto-range"]);
+            interpolator->setAutoRange(text.empty() ? lfi::IVec2{16, 9} : tileGrid(text, "--auto-range"));
         }
         if(args["-q"])
         {

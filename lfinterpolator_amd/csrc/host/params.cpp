@@ -263,6 +263,30 @@ std::vector<float> focusCandidates(float focus, float range, int steps)
     return f;
 }
 
+std::array<int, 4> focusTileRect(int width, int height, int tilesX, int tilesY, int tx, int ty)
+{
+    const auto edge = [](int t, int size, int n) { return static_cast<int>(static_cast<int64_t>(t) * size / n); };
+    return {edge(tx, width, tilesX), edge(ty, height, tilesY), edge(tx + 1, width, tilesX), edge(ty + 1, height, tilesY)};
+}
+
+FocusAutoRange focusAutoRange(const int32_t *bestIndex, size_t tiles, float focus, float range)
+{
+    constexpr int STEPS = LFI_FOCUS_TILE_STEPS;
+    int lo = STEPS - 1, hi = 0;
+    for(size_t t = 0; t < tiles; t++)
+    {
+        lo = std::min(lo, static_cast<int>(bestIndex[t]));
+        hi = std::max(hi, static_cast<int>(bestIndex[t]));
+    }
+    FocusAutoRange r{};
+    r.lo = std::max(lo - 1, 0);
+    r.hi = std::min(hi + 1, STEPS - 1);
+    const std::vector<float> cand = focusCandidates(focus, range, STEPS);
+    r.focus = cand[r.lo];
+    r.range = cand[r.hi] - cand[r.lo];
+    return r;
+}
+
 // reference src/interpolator.cu:194-207; at most 32 ids (the reference indexes 32 unconditionally: SURVEY.md D4) and ties
 // ordered by id (std::sort leaves them unspecified there)
 std::vector<int32_t> Parameterizer::selectFocusMapViews(Vec4 startEndPoints) const

@@ -5,6 +5,7 @@
 
 #include <cstdint>
 #include <string>
+#include <array>
 #include <vector>
 
 #include "../../../include/lfi.h"
@@ -74,5 +75,17 @@ std::vector<float> focusRamp(float f0, float f1, int views);
 // The focus candidates of lfi_focus_curve (for 32 steps: of FocusMap::estimate, reference src/kernels.cu:245-250), steps ≥ 2:
 // f_i = fmaf(range / (steps − 1), i, focus) in float — the device's arithmetic, so that nobody recomputes them with other rounding
 std::vector<float> focusCandidates(float focus, float range, int steps);
+// Tile (tx, ty) of lfi_focus_tiles' tilesX × tilesY grid over a width × height frame: {x0, y0, x1, y1} with x0 = tx·width / tilesX,
+// x1 = (tx + 1)·width / tilesX (integer divisions of 64-bit products), likewise in y — the tiles cover the frame exactly once
+std::array<int, 4> focusTileRect(int width, int height, int tilesX, int tilesY, int tx, int ty);
+// The search interval an all-focus render needs, from the tiles' best candidates of a search over [focus, focus + range] (32 candidates):
+// lo / hi = the smallest / largest index, widened by one candidate on either side inside [0, 31]
+struct FocusAutoRange
+{
+    int lo, hi;   // the candidates kept: max(lo − 1, 0), min(hi + 1, 31)
+    float focus;  // candidate lo
+    float range;  // candidate hi − candidate lo in float: always > 0
+};
+FocusAutoRange focusAutoRange(const int32_t *bestIndex, size_t tiles, float focus, float range);
 
 } // namespace lfi

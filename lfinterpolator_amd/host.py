@@ -27,6 +27,10 @@ def load_host_library() -> C.CDLL:
         lib.lfi_host_focus_ramp.argtypes = [C.c_float, C.c_float, C.c_int, C.c_void_p]
         lib.lfi_host_focus_candidates.restype = C.c_int
         lib.lfi_host_focus_candidates.argtypes = [C.c_float, C.c_float, C.c_int, C.c_void_p]
+        lib.lfi_host_focus_tile_rect.restype = C.c_int
+        lib.lfi_host_focus_tile_rect.argtypes = [C.c_int] * 6 + [C.c_void_p]
+        lib.lfi_host_focus_auto_range.restype = C.c_int
+        lib.lfi_host_focus_auto_range.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p]
         lib.lfi_host_build_view_offsets.restype = C.c_int
         lib.lfi_host_build_view_offsets.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_float, C.c_void_p, C.c_int,
                                                     C.c_void_p, C.c_char_p, C.c_size_t]
@@ -101,6 +105,26 @@ def focus_candidates(focus: float, range: float, steps: int = 32) -> np.ndarray:
     if load_host_library().lfi_host_focus_candidates(focus, range, steps, out.ctypes.data) != 0:
         raise ValueError("steps must be at least 2")
     return out
+
+
+def focus_tile_rect(width: int, height: int, tiles_x: int, tiles_y: int, tx: int, ty: int):
+    """Tile (tx, ty) of Context.focus_tiles' grid as (x0, y0, x1, y1): x0 = tx·width // tiles_x, x1 = (tx + 1)·width // tiles_x, likewise in y."""
+    rect = np.zeros(4, dtype=np.int32)
+    if load_host_library().lfi_host_focus_tile_rect(width, height, tiles_x, tiles_y, tx, ty, rect.ctypes.data) != 0:
+        raise ValueError("the grid must fit the frame and the tile the grid")
+    return tuple(int(v) for v in rect)
+
+
+def focus_auto_range(best_index, focus: float, range: float):
+    """The interval an all-focus render should search, from the tiles' best candidates of a search over [focus, focus + range]: returns
+    (focus', range' as np.float32, lo', hi') with lo' = max(min − 1, 0), hi' = min(max + 1, 31), focus' = candidate lo',
+    range' = candidate hi' − candidate lo' in float32."""
+    idx = np.ascontiguousarray(best_index, dtype=np.int32).reshape(-1)
+    f, r = C.c_float(), C.c_float()
+    lo_hi = np.zeros(2, dtype=np.int32)
+    if load_host_library().lfi_host_focus_auto_range(idx.ctypes.data, len(idx), focus, range, C.byref(f), C.byref(r), lo_hi.ctypes.data) != 0:
+        raise ValueError("needs at least one tile, indices in [0, 31] and range > 0")
+    return np.float32(f.value), np.float32(r.value), int(lo_hi[0]), int(lo_hi[1])
 
 
 def build_view_offsets(cols: int, rows: int, width: int, height: int, trajectory: str, aspect: float, focus_v) -> np.ndarray:
