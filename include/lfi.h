@@ -400,6 +400,23 @@ int lfi_download_quilt(lfi_ctx *ctx, int tiles_x, int tiles_y, int v0, uint8_t *
  * the CLI's -g): every context fills its own tiles of one host image.  The tiles are assembled on the device by one kernel (the
  * planar view layout is expanded on the fly) and copied in at most three rectangles; lfi_download_quilt is this with every tile. */
 int lfi_download_quilt_tiles(lfi_ctx *ctx, int tiles_x, int tiles_y, int first_tile, int n, int v0, uint8_t *rgba, size_t pitch_bytes);
+/* The quilt with every view RESIZED on the device to a tile of tile_w × tile_h pixels, 1 ≤ tile_w ≤ W, 1 ≤ tile_h ≤ H (downscaling or
+ * identity; each axis on its own) — scripts/viewsToQuilt.sh's `montage -tile 5x9 -geometry 1920x1080+0+0` resizes on the way into the
+ * quilt too, and a Looking-Glass quilt of 4096² or 8192² pixels has 5 × 9 tiles of 819 × 455 or 1638 × 910.  Only the scaled bytes are
+ * copied to the host.  rgba: (tiles_y*tile_h) rows of pitch_bytes ≥ tiles_x*tile_w*4; tiles left to right, top to bottom.  Synchronous.
+ * The resize is an exact AREA (box) filter in integers: along x both images lie on a grid of W·tile_w units, output column ox covers
+ * [ox·W, (ox+1)·W), source column sx covers [sx·tile_w, (sx+1)·tile_w), and wx(ox, sx) is the length of their overlap (over sx it sums to
+ * W); wy likewise with H and tile_h; per colour channel
+ *     out = (Σ_sy Σ_sx wy·wx·p[sy][sx] + (W·H) / 2) / (W·H)        (integer division: the exact area mean, rounded half up)
+ * and alpha is 255.  So tile = W × H gives lfi_download_quilt's bytes, W = k·tile_w and H = l·tile_h the k × l block mean, and every value
+ * lies within 0.5 of the exact area mean.  ImageMagick's default resize filter is a different one: the bytes of `montage` are NOT
+ * reproduced.  A 1 × 1 quilt of view v (v0 = v) is that view, scaled: a thumbnail or preview.
+ * LFI_EINVAL for what lfi_download_quilt refuses, a tile size outside the limits, views of more than 65535 pixels along an axis, and while
+ * a row window is set (a tile's rows average source rows the band does not hold). */
+int lfi_download_quilt_scaled(lfi_ctx *ctx, int tiles_x, int tiles_y, int v0, int tile_w, int tile_h, uint8_t *rgba, size_t pitch_bytes);
+/* … and for PART of such a quilt, as lfi_download_quilt_tiles: views v0 … v0+n-1 become tiles first_tile … first_tile+n-1, one kernel launch
+ * for all n tiles (both view layouts are read as they are), at most three rectangles copied. */
+int lfi_download_quilt_tiles_scaled(lfi_ctx *ctx, int tiles_x, int tiles_y, int first_tile, int n, int v0, int tile_w, int tile_h, uint8_t *rgba, size_t pitch_bytes);
 int lfi_upload_map(lfi_ctx *ctx, int k, const uint8_t *rgba, size_t pitch_bytes); /* tests: inject a focus map */
 /* view v's map k (0 or 1) of the per-view maps (lfi_view_focus_maps).  Synchronous.  The upload is a test hook like lfi_upload_map (it
  * allocates the per-view maps if needed and does not put them in use: renders read them after a successful lfi_view_focus_maps). */

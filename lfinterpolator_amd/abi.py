@@ -35,7 +35,7 @@ ABI_SYMBOLS = [
     "lfi_set_variant", "lfi_list_variants", "lfi_download_coords", "lfi_download_prequant", "lfi_debug_mfma_f16",
     "lfi_grid_modified", "lfi_prepare", "lfi_memory_info", "lfi_last_kernel_name", "lfi_fill_synthetic_images", "lfi_set_output_layout", "lfi_view_layout", "lfi_fill_synthetic_scene", "lfi_upload_image_async", "lfi_upload_wait", "lfi_render_stream", "lfi_compare_view", "lfi_debug_mfma_f16_chain", "lfi_debug_pk_minmax3_f16", "lfi_std_band_info",
     "lfi_debug_poison", "lfi_set_view_offsets", "lfi_set_view_float_offsets", "lfi_view_focus_maps", "lfi_download_view_map",
-    "lfi_upload_view_map", "lfi_focus_curve", "lfi_focus_tiles",
+    "lfi_upload_view_map", "lfi_focus_curve", "lfi_focus_tiles", "lfi_download_quilt_scaled", "lfi_download_quilt_tiles_scaled",
 ]
 
 
@@ -137,6 +137,8 @@ def load_hip_library() -> C.CDLL:
         "lfi_release_inputs": (i, [vp]),
         "lfi_download_quilt": (i, [vp, i, i, i, vp, sz]),
         "lfi_download_quilt_tiles": (i, [vp, i, i, i, i, i, vp, sz]),
+        "lfi_download_quilt_scaled": (i, [vp, i, i, i, i, i, vp, sz]),
+        "lfi_download_quilt_tiles_scaled": (i, [vp, i, i, i, i, i, i, i, vp, sz]),
         "lfi_alloc_pinned": (i, [sz, C.POINTER(vp)]),
         "lfi_free_pinned": (i, [vp]),
         "lfi_grid_modified": (i, [vp]),
@@ -487,6 +489,21 @@ class Context:
     def download_quilt(self, tiles_x: int, tiles_y: int, v0: int = 0) -> np.ndarray:
         out = np.full((tiles_y * self.height, tiles_x * self.width, 4), 0xC3, dtype=np.uint8)   # a sentinel, not zeros: every byte is written
         self._check(self._lib.lfi_download_quilt(self._h, tiles_x, tiles_y, v0, _ptr(out), tiles_x * self.width * 4))
+        return out
+
+    def download_quilt_tiles_scaled(self, out: np.ndarray, tiles_x: int, tiles_y: int, first_tile: int, n: int, tile_w: int, tile_h: int, v0: int = 0) -> None:
+        """views v0 … v0+n-1, each resized to tile_w × tile_h by the exact area filter of lfi_download_quilt_scaled, into tiles first_tile … of
+        the quilt image `out`: (tiles_y·tile_h, P, 4) uint8 with rows of P ≥ tiles_x·tile_w pixels — the row pitch is out's; the library refuses one that is too small"""
+        assert out.dtype == np.uint8 and out.ndim == 3 and out.shape[0] == tiles_y * tile_h and out.shape[2] == 4 and (out.size == 0 or out.strides[1:] == (4, 1))
+        self._check(self._lib.lfi_download_quilt_tiles_scaled(self._h, tiles_x, tiles_y, first_tile, n, v0, tile_w, tile_h, _ptr(out), out.strides[0]))
+
+    def download_quilt_scaled(self, tiles_x: int, tiles_y: int, tile_w: int, tile_h: int, v0: int = 0, out: np.ndarray | None = None) -> np.ndarray:
+        """the quilt of views v0 … with every view resized to tile_w × tile_h on the device (a 1 × 1 quilt: view v0 as a thumbnail); `out` as in
+        download_quilt_tiles_scaled, by default a new (tiles_y·tile_h, tiles_x·tile_w, 4) array"""
+        if out is None:
+            out = np.full((tiles_y * max(tile_h, 0), tiles_x * max(tile_w, 0), 4), 0xC3, dtype=np.uint8)   # a sentinel, not zeros: every byte is written
+        assert out.dtype == np.uint8 and out.ndim == 3 and out.shape[0] == tiles_y * tile_h and out.shape[2] == 4 and (out.size == 0 or out.strides[1:] == (4, 1))
+        self._check(self._lib.lfi_download_quilt_scaled(self._h, tiles_x, tiles_y, v0, tile_w, tile_h, _ptr(out), out.strides[0]))
         return out
 
     def download_map(self, k: int) -> np.ndarray:

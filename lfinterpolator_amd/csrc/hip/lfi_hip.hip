@@ -8,6 +8,7 @@
 #include "lfi_context.hpp"
 #include "lfi_dispatch.hpp"
 #include "lfi_focus_sched.hpp"
+#include "quilt_scaled.hpp"
 #include "lfi_rccl.hpp"
 
 extern "C" {
@@ -1529,6 +1530,74 @@ int lfi_download_quilt(lfi_ctx *ctx, int tiles_x, int tiles_y, int v0, uint8_t *
     if(ctx && (tiles_x < 1 || tiles_y < 1))
         return fail(ctx, LFI_EINVAL, "quilt needs tiles_x*tiles_y views starting at v0 inside [0, views)");
     return lfi_download_quilt_tiles(ctx, tiles_x, tiles_y, 0, tiles_x * tiles_y, v0, rgba, pitch_bytes);
+}
+
+int lfi_download_quilt_tiles_scaled(lfi_ctx *ctx, int tiles_x, int tiles_y, int first_tile, int n, int v0, int tile_w, int tile_h, uint8_t *rgba, size_t pitch_bytes)
+{
+    if(!ctx)
+        return LFI_EINVAL;
+    if(!ctx->views || !ctx->have_params)
+        return fail(ctx, LFI_EINVAL, "nothing rendered yet");
+    if(ctx->windowed)
+        return fail(ctx, LFI_EINVAL, "a scaled quilt needs whole views: a tile's rows average source rows the row window's band does not hold");
+    if(tiles_x < 1 || tiles_y < 1 || first_tile < 0 || n < 1 || (long)first_tile + n > (long)tiles_x * tiles_y || v0 < 0 || (long)v0 + n > ctx->views_n)
+        return fail(ctx, LFI_EINVAL, "quilt needs the tiles inside the quilt and as many views starting at v0 inside [0, views)");
+    const int W = ctx->width, H = ctx->height;
+    if(tile_w < 1 || tile_w > W || tile_h < 1 || tile_h > H)
+        return fail(ctx, LFI_EINVAL, "scaled quilt tiles are 1 … width by 1 … height pixels (downscaling or identity only)");
+    if((uint32_t)W > lfi::LFI_AREA_SPAN_MAX || (uint32_t)H > lfi::LFI_AREA_SPAN_MAX)
+        return fail(ctx, LFI_EINVAL, "scaled quilts take views of up to 65535 pixels per axis");
+    if(!rgba || pitch_bytes < (size_t)tiles_x * tile_w * 4)
+        return fail(ctx, LFI_EINVAL, "bad quilt pointer or pitch");
+    if(int rc = bind(ctx))
+        return rc;
+    // As lfi_download_quilt_tiles: the rows of tiles these tiles touch are made on the device by ONE kernel, in the same buffer, and only
+    // their bytes — tile_w × tile_h per tile — are copied, in at most three rectangles.
+    const int tr0 = first_tile / tiles_x, tr1 = (first_tile + n - 1) / tiles_x;
+    const size_t qrow = (size_t)tiles_x * tile_w * 4;
+    LFI_HIP(ctx, ctx->quilt.reserve(qrow * tile_h * (size_t)(tr1 - tr0 + 1)));
+    const bool planar = ctx->out_layout == LFI_LAYOUT_PLANAR_RGB;
+    lfi::QuiltScaleArgs q{};
+    q.views = ctx->views.get();
+    q.quilt = ctx->quilt.as<uint32_t>();
+    q.view_stride = out_plane_bytes(ctx);
+    q.W = W, q.H = H, q.pitch = planar ? view_pitch(ctx) : 0;
+    q.tile_w = tile_w, q.tile_h = tile_h;
+    q.v0 = v0, q.first = first_tile, q.tiles_x = tiles_x;
+    LFI_HIP(ctx, lfi::launch_quilt_scale(ctx->stream, planar, q, n));
+    const int c_first = first_tile % tiles_x, c_last = (first_tile + n - 1) % tiles_x;
+    auto copy_rect = [&](int ra, int rb, int ca, int cb) -> hipError_t { // rows of tiles [ra, rb] × tile columns [ca, cb] → the host image
+        return hipMemcpy2DAsync(rgba + (size_t)ra * tile_h * pitch_bytes + (size_t)ca * tile_w * 4, pitch_bytes,
+                                ctx->quilt.get() + (size_t)(ra - tr0) * tile_h * qrow + (size_t)ca * tile_w * 4, qrow, (size_t)(cb - ca + 1) * tile_w * 4,
+                                (size_t)(rb - ra + 1) * tile_h, hipMemcpyDeviceToHost, ctx->stream);
+    };
+    if(tr0 == tr1)
+        LFI_HIP(ctx, copy_rect(tr0, tr0, c_first, c_last));
+    else
+    {
+        int full0 = tr0, full1 = tr1;
+        if(c_first != 0)
+        {
+            LFI_HIP(ctx, copy_rect(tr0, tr0, c_first, tiles_x - 1));
+            full0++;
+        }
+        if(c_last != tiles_x - 1)
+        {
+            LFI_HIP(ctx, copy_rect(tr1, tr1, 0, c_last));
+            full1--;
+        }
+        if(full0 <= full1)
+            LFI_HIP(ctx, copy_rect(full0, full1, 0, tiles_x - 1));
+    }
+    LFI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return LFI_OK;
+}
+
+int lfi_download_quilt_scaled(lfi_ctx *ctx, int tiles_x, int tiles_y, int v0, int tile_w, int tile_h, uint8_t *rgba, size_t pitch_bytes)
+{
+    if(ctx && (tiles_x < 1 || tiles_y < 1))
+        return fail(ctx, LFI_EINVAL, "quilt needs tiles_x*tiles_y views starting at v0 inside [0, views)");
+    return lfi_download_quilt_tiles_scaled(ctx, tiles_x, tiles_y, 0, tiles_x * tiles_y, v0, tile_w, tile_h, rgba, pitch_bytes);
 }
 
 int lfi_alloc_pinned(size_t bytes, void **out_ptr)

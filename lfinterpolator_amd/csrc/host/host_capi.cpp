@@ -5,6 +5,7 @@
 #include <stdexcept>
 #include <vector>
 
+#include "../area_span.h"
 #include "params.h"
 
 namespace {
@@ -77,6 +78,21 @@ int lfi_host_focus_tile_rect(int width, int height, int tiles_x, int tiles_y, in
     const std::array<int, 4> r = lfi::focusTileRect(width, height, tiles_x, tiles_y, tx, ty);
     for(int k = 0; k < 4; k++)
         rect[k] = r[k];
+    return 0;
+}
+
+// output pixel o of the area resize of lfi_download_quilt_scaled along one axis of src source pixels and dst output pixels (../area_span.h, the
+// code the kernel runs): out = {first, last, w_first, w_last} — the source pixels o overlaps and the overlaps with the first and the last
+// one; every source pixel between them weighs dst.  Returns 0, or -1 unless 1 <= dst <= src <= 65535 and 0 <= o < dst
+int lfi_host_area_span(int src, int dst, int o, int32_t out[4])
+{
+    if(!out || dst < 1 || src < dst || static_cast<uint32_t>(src) > lfi::LFI_AREA_SPAN_MAX || o < 0 || o >= dst)
+        return -1;
+    const lfi::AreaSpan s = lfi::area_span(static_cast<uint32_t>(src), static_cast<uint32_t>(dst), static_cast<uint32_t>(o));
+    out[0] = static_cast<int32_t>(s.first);
+    out[1] = static_cast<int32_t>(s.last);
+    out[2] = static_cast<int32_t>(s.w_first);
+    out[3] = static_cast<int32_t>(s.w_last);
     return 0;
 }
 

@@ -124,6 +124,14 @@ void Interpolator::interpolate(std::string outputPath, std::string trajectory, f
         methodID = LFI_METHOD_STD;
     else
         throw std::runtime_error("The specified interpolation method does not exist!");
+    if(quiltTile.x > 0 || quiltTile.y > 0)
+    {
+        if(!(quiltTiles.x > 0 && quiltTiles.y > 0))
+            throw std::runtime_error("A quilt tile size needs a quilt (-q cols,rows)!");
+        if(quiltTile.x < 1 || quiltTile.y < 1 || quiltTile.x > resolution.x || quiltTile.y > resolution.y)
+            throw std::runtime_error("The quilt tile size has to be between 1x1 and the views' " + std::to_string(resolution.x) + "x" + std::to_string(resolution.y) +
+                                     " pixels (views are only scaled down)!");
+    }
 
     lfi::Parameterizer parameterizer(colsRows, resolution);
     // the minima of a grid of focus tiles over the search interval [inFocus, inFocus + inRange], on the first GPU
@@ -383,17 +391,24 @@ void Interpolator::storeResults(std::string path)
         if(quiltTiles.x * quiltTiles.y > viewCount)
             throw std::runtime_error("The quilt has more tiles than rendered views!");
         std::cout << "Storing quilt..." << std::endl;
-        const size_t quiltPitch = pitch * quiltTiles.x;
-        std::vector<uint8_t> quilt(quiltPitch * resolution.y * quiltTiles.y);
+        // with a tile size every view is resized to it on the device (lfi_download_quilt_tiles_scaled): only the scaled bytes are copied
+        const bool scaled = quiltTile.x > 0;
+        const lfi::IVec2 tile = scaled ? quiltTile : lfi::IVec2{resolution.x, resolution.y};
+        const size_t quiltPitch = static_cast<size_t>(tile.x) * channels * quiltTiles.x;
+        std::vector<uint8_t> quilt(quiltPitch * tile.y * quiltTiles.y);
         // every GPU assembles the tiles of ITS views on the device and copies them into their place in the one host image
         const int tiles = quiltTiles.x * quiltTiles.y;
         for(int g = 0; g < gpuCount; g++)
         {
             const int first = viewStart[g], last = std::min(g + 1 < gpuCount ? viewStart[g + 1] : viewCount, tiles);
-            if(first < last)
+            if(first >= last)
+                continue;
+            if(scaled)
+                check(lfi_download_quilt_tiles_scaled(contexts[g], quiltTiles.x, quiltTiles.y, first, last - first, 0, tile.x, tile.y, quilt.data(), quiltPitch), contexts[g]);
+            else
                 check(lfi_download_quilt_tiles(contexts[g], quiltTiles.x, quiltTiles.y, first, last - first, 0, quilt.data(), quiltPitch), contexts[g]);
         }
-        lfi::writePng((std::filesystem::path(path) / "quilt.png").string(), resolution.x * quiltTiles.x, resolution.y * quiltTiles.y,
-                      static_cast<int>(channels), quilt.data(), quiltPitch);
+        lfi::writePng((std::filesystem::path(path) / "quilt.png").string(), tile.x * quiltTiles.x, tile.y * quiltTiles.y, static_cast<int>(channels), quilt.data(),
+                      quiltPitch);
     }
 }

@@ -27,6 +27,9 @@ class Interpolator
         void setUnifiedFocusMap(bool on) { unifiedFocusMap = on; }
         // also write quilt.png: the views as one image of cols × rows tiles (what scripts/viewsToQuilt.sh montages, 5×9 there)
         void setQuilt(lfi::IVec2 tiles) { quiltTiles = tiles; }
+        // … with every view resized to a tile of width × height pixels on the device first (lfi_download_quilt_tiles_scaled: an exact area
+        // filter, at most the views' size) — montage's -geometry; needs setQuilt
+        void setQuiltTile(lfi::IVec2 size) { quiltTile = size; }
         float lastAverageTime() const { return averageTime; }
         // render on GPUs 0 … count-1 of this node: views are split into contiguous ranges, the grid is broadcast once (RCCL)
         void setGpuCount(int count) { gpuCount = count; }
@@ -62,6 +65,7 @@ class Interpolator
         int device{defaultDevice};
         bool unifiedFocusMap{false};
         lfi::IVec2 quiltTiles{0, 0};
+        lfi::IVec2 quiltTile{0, 0}; // 0: the views' size, unscaled
         lfi_ctx *context{nullptr};
         int gpuCount{1};
         bool perViewFocus{false};

@@ -47,6 +47,7 @@ int main(int argc, char **argv)
                           "-d - GPU index (default=0)\n"
                           "-g - number of GPUs: the views are split over GPUs d … d+g-1, the input grid is broadcast once (default=1)\n"
                           "-q - also store quilt.png: the first cols*rows views as cols,rows tiles (e.g. 5,9 for a Looking Glass quilt)\n"
+                          "--quilt-tile WxH - with -q: resize every view to a tile of W x H pixels on the GPU before quilt.png is stored (an exact area filter; downscaling only, at most the views' size), e.g. -q 5,9 --quilt-tile 819x455 for a 4096 x 4096 quilt\n"
                           "--synthetic cols,rows,width,height[,seed] - use a generated light field instead of -i\n"
                           "--unified-map - all-focus TEN_WM reads the filtered focus map like STD (the reference reads the unfiltered one)\n"
                         };
@@ -95,6 +96,12 @@ int main(int argc, char **argv)
     if(args["--auto-range"] && args["--autofocus"])
     {
         std::cerr << "--auto-range (an all-focus render) cannot be combined with --autofocus (a fixed-focus render)." << std::endl;
+        return EXIT_FAILURE;
+    }
+
+    if(args["--quilt-tile"] && !args["-q"])
+    {
+        std::cerr << "--quilt-tile sets the tile size of the quilt: it needs -q cols,rows." << std::endl;
         return EXIT_FAILURE;
     }
 
@@ -166,7 +173,7 @@ int main(int argc, char **argv)
             interpolator->setAutofocus(region, args["--autofocus-steps"] ? static_cast<int>(args["--autofocus-steps"]) : 32);
         }
         // a grid of tiles "CxR" (columns x rows)
-        const auto tileGrid = [](const std::string &text, const char *flag) {
+        const auto tileGrid = [](const std::string &text, const char *flag, const char *meaning = "CxR, columns x rows of tiles, both at least 1") {
             const size_t cut = text.find_first_of("xX");
             lfi::IVec2 grid{0, 0};
             try
@@ -179,7 +186,7 @@ int main(int argc, char **argv)
                 grid = {0, 0};
             }
             if(grid.x < 1 || grid.y < 1)
-                throw std::runtime_error(std::string(flag) + " expects CxR, columns x rows of tiles, both at least 1");
+                throw std::runtime_error(std::string(flag) + " expects " + meaning);
             return grid;
         };
         if(args["--focus-tiles"])
@@ -197,6 +204,8 @@ int main(int argc, char **argv)
                 throw std::runtime_error("-q expects cols,rows");
             interpolator->setQuilt({std::stoi(a), std::stoi(b)});
         }
+        if(args["--quilt-tile"])
+            interpolator->setQuiltTile(tileGrid(static_cast<std::string>(args["--quilt-tile"]), "--quilt-tile", "WxH, the tile's width x height in pixels, both at least 1"));
         interpolator->interpolate(outputPath, trajectory, focus, range, method, effect, aspect);
     }
     catch(const std::exception &e)

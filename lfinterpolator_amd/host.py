@@ -31,6 +31,8 @@ def load_host_library() -> C.CDLL:
         lib.lfi_host_focus_tile_rect.argtypes = [C.c_int] * 6 + [C.c_void_p]
         lib.lfi_host_focus_auto_range.restype = C.c_int
         lib.lfi_host_focus_auto_range.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p]
+        lib.lfi_host_area_span.restype = C.c_int
+        lib.lfi_host_area_span.argtypes = [C.c_int] * 3 + [C.c_void_p]
         lib.lfi_host_build_view_offsets.restype = C.c_int
         lib.lfi_host_build_view_offsets.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_float, C.c_void_p, C.c_int,
                                                     C.c_void_p, C.c_char_p, C.c_size_t]
@@ -125,6 +127,16 @@ def focus_auto_range(best_index, focus: float, range: float):
     if load_host_library().lfi_host_focus_auto_range(idx.ctypes.data, len(idx), focus, range, C.byref(f), C.byref(r), lo_hi.ctypes.data) != 0:
         raise ValueError("needs at least one tile, indices in [0, 31] and range > 0")
     return np.float32(f.value), np.float32(r.value), int(lo_hi[0]), int(lo_hi[1])
+
+
+def area_span(src: int, dst: int, o: int):
+    """Output pixel o of Context.download_quilt_scaled's area resize along an axis of src source and dst output pixels, as (first, last,
+    w_first, w_last): the source pixels it overlaps on the grid of src·dst units and the overlaps with the first and the last one (every
+    source pixel between them weighs dst) — the arithmetic the kernel runs."""
+    out = np.zeros(4, dtype=np.int32)
+    if load_host_library().lfi_host_area_span(src, dst, o, out.ctypes.data) != 0:
+        raise ValueError("needs 1 <= dst <= src <= 65535 and 0 <= o < dst")
+    return tuple(int(v) for v in out)
 
 
 def build_view_offsets(cols: int, rows: int, width: int, height: int, trajectory: str, aspect: float, focus_v) -> np.ndarray:
