@@ -356,7 +356,8 @@ typedef struct lfi_memory {
     size_t views_bytes;     /* output planes */
     size_t maps_bytes;      /* focus maps (maps 0 / 1, and the per-view maps when allocated) */
     size_t workspace_bytes; /* focus-map workspace + lfi_focus_curve's / lfi_focus_tiles' curves and partial sums + (planar view layout) the RGBA scratch copy of the views that renders other than TEN_WM and
-                             * STD on more than 64 images go through, and the one-plane staging buffer of downloads */
+                             * STD on more than 64 images go through, and the one-plane staging buffer of downloads + the kept views (lfi_keep_views) and
+                             * lfi_compare_views' staging buffers and partial sums */
     float derived_build_ms;
 } lfi_memory;
 int lfi_memory_info(lfi_ctx *ctx, lfi_memory *out);
@@ -433,6 +434,48 @@ typedef struct lfi_quality {
 } lfi_quality;
 int lfi_compare_view(lfi_ctx *ctx, int v, const uint8_t *reference_rgba, size_t pitch_bytes, lfi_quality *out);
 
+/* Batch comparison: PSNR / SSIM of n views against n references in one device pass — replaces scripts/compareDirs.sh (a loop of
+ * imageQualityMetrics.sh over every file of two result directories: all views against ground truth, or a TEN_WM run against an STD run).
+ * The references are host images, or views kept on the device from an earlier render (lfi_keep_views): comparing two methods' renders
+ * then moves nothing but the results over PCIe.
+ *
+ * lfi_keep_views copies views [v0, v0 + n) as they are now, in the current layout, into a reference set the context owns: device to
+ * device, in stream order, no host synchronisation (unless the set's size changes: the old allocation is freed).  Later renders do not
+ * touch the kept set.  n == 0 frees it.  It is dropped by lfi_set_grid, lfi_set_row_window, lfi_set_output_layout (to another layout) and
+ * by a lfi_set_params that changes the number of views; its bytes are counted in lfi_memory.workspace_bytes.
+ *
+ * lfi_compare_views: out[k] compares view v0 + k with reference k, k in [0, n); out_all (may be NULL) is the aggregate.
+ *  - references_rgba != NULL: n host RGBA images, image k at references_rgba + k * image_stride_bytes, rows of pitch_bytes >= W * 4,
+ *    image_stride_bytes >= pitch_bytes * H.  They cross PCIe on the context's copy stream in chunks of several images (at most 64 MiB, at
+ *    least one image) through two device staging buffers: chunk k + 1 is copied while chunk k is reduced.  Page-locked sources
+ *    (lfi_alloc_pinned) are DMA'd in place;
+ *  - references_rgba == NULL: the references are the kept views, [v0, v0 + n) must lie inside the kept range (reference k = kept view
+ *    v0 + k); one launch covers all n views;
+ *  - out[k].q: mse, psnr, psnr_all, ssim, ssim_all exactly as lfi_compare_view defines them (+inf for identical images, ssim = 1.0 when no
+ *    window fits); sq_err, differing_bytes, max_abs_diff and windows are exact integers;
+ *  - out_all: mse[c] = (sum over the views of sq_err[c]) / (n * W * H), computed from the integers; psnr, psnr_all from it as above;
+ *    ssim[c] = the mean of the per-view ssim[c], added in view order; ssim_all = the mean of the three;
+ *  - deterministic: window SSIMs are added in a fixed order (per lane, wave, workgroup, then per view: csrc/hip/quality_batch.hpp), no
+ *    floating-point atomics: two calls on the same data return the same bits;
+ *  - both view layouts are read as they are (no staging plane), kept references in the layout they were kept in;
+ *  - synchronous; ordered after the work on the stream in use (a caller's too: lfi_set_stream) and after pending uploads; one
+ *    device-to-host copy carries all results.  It writes no view, map or kept view.  It only reads views: it works after
+ *    lfi_release_inputs and with per-view offsets or maps set.  The staging buffers and the partial sums belong to the context
+ *    (lfi_memory.workspace_bytes, LFI_POISON_SCRATCH); every byte a call reads of them it has written itself;
+ *  - LFI_EINVAL, the context stays usable: nothing rendered yet; a range outside [0, views) or n < 1; a pitch or stride too small;
+ *    out == NULL; a row window; NULL references without a kept set or with one that does not cover the range (a set kept in another
+ *    layout has been dropped). */
+typedef struct lfi_view_quality {
+    lfi_quality q;             /* the definitions of lfi_compare_view / quality.hpp, unchanged */
+    uint64_t sq_err[3];        /* sum of (a-b)^2 per colour channel: exact */
+    uint64_t differing_bytes;  /* colour bytes (R, G, B; alpha ignored) with a != b: exact */
+    uint64_t windows;          /* 8x8 windows at stride 4 that fit */
+    int32_t max_abs_diff;      /* largest |a-b| over the colour bytes: exact */
+} lfi_view_quality;
+int lfi_keep_views(lfi_ctx *ctx, int v0, int n);
+int lfi_compare_views(lfi_ctx *ctx, int v0, int n, const uint8_t *references_rgba, size_t pitch_bytes, size_t image_stride_bytes, lfi_view_quality *out,
+                      lfi_quality *out_all);
+
 /* Page-locked host memory for uploads / downloads at full PCIe rate (hipHostMalloc); optional — any host pointer works. */
 int lfi_alloc_pinned(size_t bytes, void **out_ptr);
 int lfi_free_pinned(void *ptr);
@@ -475,7 +518,8 @@ int lfi_debug_mfma_f16_chain(lfi_ctx *ctx, int shape, int k, const uint16_t *a_3
  * rebuilt in full by their next user (the estimate's padded planes; the planar copy, as after lfi_grid_modified).
  *   VIEWS            the views in the current layout (attached ones too)
  *   SCRATCH          the planar layout's RGBA scratch copy of the views, the download staging plane, the pre-quantisation buffer, the
- *                    quilt buffer and lfi_render_stream's second set of views
+ *                    quilt buffer, lfi_render_stream's second set of views and lfi_compare_views' staging buffers, partial sums and per-view records
+ *                    (not the kept views: they are data)
  *   MAPS             both focus maps
  *   FOCUS_WORKSPACE  all of the focus-map estimate's workspace, and lfi_focus_curve's / lfi_focus_tiles' (the curves, the results and the partial sums)
  *   DERIVED          the planar copy of the inputs — refused (LFI_EINVAL) after lfi_release_inputs: it is then the only copy

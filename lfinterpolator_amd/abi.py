@@ -36,6 +36,7 @@ ABI_SYMBOLS = [
     "lfi_grid_modified", "lfi_prepare", "lfi_memory_info", "lfi_last_kernel_name", "lfi_fill_synthetic_images", "lfi_set_output_layout", "lfi_view_layout", "lfi_fill_synthetic_scene", "lfi_upload_image_async", "lfi_upload_wait", "lfi_render_stream", "lfi_compare_view", "lfi_debug_mfma_f16_chain", "lfi_debug_pk_minmax3_f16", "lfi_std_band_info",
     "lfi_debug_poison", "lfi_set_view_offsets", "lfi_set_view_float_offsets", "lfi_view_focus_maps", "lfi_download_view_map",
     "lfi_upload_view_map", "lfi_focus_curve", "lfi_focus_tiles", "lfi_download_quilt_scaled", "lfi_download_quilt_tiles_scaled",
+    "lfi_keep_views", "lfi_compare_views",
 ]
 
 
@@ -66,6 +67,11 @@ class ViewLayout(C.Structure):
 
 class Quality(C.Structure):
     _fields_ = [("mse", C.c_double * 3), ("psnr", C.c_double * 3), ("psnr_all", C.c_double), ("ssim", C.c_double * 3), ("ssim_all", C.c_double)]
+
+
+class ViewQuality(C.Structure):
+    """lfi_view_quality: one view of lfi_compare_views"""
+    _fields_ = [("q", Quality), ("sq_err", C.c_uint64 * 3), ("differing_bytes", C.c_uint64), ("windows", C.c_uint64), ("max_abs_diff", C.c_int32)]
 
 
 class StdBandInfo(C.Structure):
@@ -152,6 +158,8 @@ def load_hip_library() -> C.CDLL:
         "lfi_prepare": (i, [vp, i, i, i, i]),
         "lfi_render_stream": (i, [vp, i, i, vp, i, vp, sz]),
         "lfi_compare_view": (i, [vp, i, vp, sz, C.POINTER(Quality)]),
+        "lfi_keep_views": (i, [vp, i, i]),
+        "lfi_compare_views": (i, [vp, i, i, vp, sz, sz, C.POINTER(ViewQuality), C.POINTER(Quality)]),
         "lfi_upload_image_async": (i, [vp, i, vp, sz]),
         "lfi_upload_wait": (i, [vp]),
         "lfi_fill_synthetic_scene": (i, [vp, C.c_uint32]),
@@ -423,6 +431,32 @@ class Context:
         q = Quality()
         self._check(self._lib.lfi_compare_view(self._h, v, _ptr(ref), self.width * 4, C.byref(q)))
         return q
+
+    def keep_views(self, v0: int = 0, n: int | None = None) -> None:
+        """Keep views [v0, v0 + n) (default: all from v0) as they are now on the device, as the references of compare_views(None)
+        (lfi_keep_views: stream-ordered device copy; later renders do not touch them)."""
+        self._check(self._lib.lfi_keep_views(self._h, v0, self.views - v0 if n is None else n))
+
+    def drop_kept_views(self) -> None:
+        self._check(self._lib.lfi_keep_views(self._h, 0, 0))
+
+    def compare_views(self, refs: np.ndarray | None = None, v0: int = 0, n: int | None = None):
+        """PSNR / SSIM of views [v0, v0 + n) in one device pass (lfi_compare_views) against refs — [n][H][W][4] uint8 whose pixels are
+        contiguous (row pitch and image stride are the array's: a slice of a larger array, or one from pinned_empty, is read in place) — or,
+        refs None, against the kept views (keep_views).  n defaults to len(refs), or to all views from v0.
+        Returns (the per-view records: a ctypes array of ViewQuality, the aggregate Quality)."""
+        if refs is not None:
+            assert refs.dtype == np.uint8 and refs.ndim == 4 and refs.shape[1:] == (self.height, self.width, 4), refs.shape
+            assert refs.strides[2:] == (4, 1) and refs.strides[0] >= 0 and refs.strides[1] >= 0, refs.strides
+            n = refs.shape[0] if n is None else n
+            assert n <= refs.shape[0]
+        elif n is None:
+            n = self.views - v0
+        out = (ViewQuality * max(n, 1))()
+        agg = Quality()
+        self._check(self._lib.lfi_compare_views(self._h, v0, n, _ptr(refs) if refs is not None else None, refs.strides[1] if refs is not None else 0,
+                                                refs.strides[0] if refs is not None else 0, out, C.byref(agg)))
+        return out, agg
 
     def benchmark(self, method, all_focus=False, v0=0, v1=None, warmup=3, runs=20) -> BenchStats:
         m = METHODS[method] if isinstance(method, str) else method

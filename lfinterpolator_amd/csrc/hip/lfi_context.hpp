@@ -17,6 +17,7 @@
 #include "../../../include/lfi.h"
 #include "lfi_device.hpp"
 #include "quality.hpp"
+#include "quality_batch.hpp"
 
 using lfi::KernelArgs;
 
@@ -305,6 +306,14 @@ struct lfi_ctx
     Event ev_h2d[2], ev_rendered[2], ev_d2h[2];
     DeviceBuffer quality_sums; // lfi_compare_view: one lfi::QualitySums, kept until the context goes
     DeviceBuffer quality_ref;
+    // lfi_keep_views: a copy of views [kept_v0, kept_v0 + kept_n) in the layout they were rendered in — lfi_compare_views' device-side references
+    DeviceBuffer kept;
+    int kept_v0 = 0, kept_n = 0;
+    // lfi_compare_views: two staging buffers for chunks of host references (a copy into one runs beside the reduction out of the other),
+    // and one workspace: the per-view records, then the per-workgroup partial sums (grows, kept)
+    DeviceBuffer cmp_stage[2];
+    Event ev_cmp_copied[2], ev_cmp_reduced[2];
+    DeviceBuffer cmp_ws;
     lfi_int2 *d_focused = nullptr;
     lfi_float2 *d_offsets = nullptr;
     uint16_t *d_w16 = nullptr, *d_w16s = nullptr;
@@ -676,6 +685,17 @@ void free_views(lfi_ctx *c)
     c->quilt.release();
     c->views2.release();
     c->quality_ref.release();
+    c->cmp_stage[0].release();
+    c->cmp_stage[1].release();
+    c->cmp_ws.release();
+}
+
+// the kept views belong to the views' count, size and layout: lfi_set_grid, lfi_set_row_window, lfi_set_output_layout, and a
+// lfi_set_params that changes the number of views (the callers have drained the stream)
+void drop_kept(lfi_ctx *c)
+{
+    c->kept.release();
+    c->kept_v0 = c->kept_n = 0;
 }
 
 // the one-image staging plane of uploads after lfi_release_inputs is sized by the row window in force when it was allocated, and the eager

@@ -126,6 +126,7 @@ int lfi_set_grid(lfi_ctx *ctx, int cols, int rows, int width, int height)
     free_params(ctx);
     free_view_rows(ctx);
     free_views(ctx);
+    drop_kept(ctx);
     free_grid(ctx);
     ctx->cols = cols;
     ctx->rows = rows;
@@ -159,6 +160,7 @@ int lfi_set_row_window(lfi_ctx *ctx, int out_y0, int out_y1, int in_y0, int in_y
     LFI_HIP(ctx, hipStreamSynchronize(ctx->stream));
     free_params(ctx);
     free_views(ctx);
+    drop_kept(ctx);
     drop_inputs(ctx); // the staging plane too: sized for the window in force when it was allocated (a larger window overflowed it)
     ctx->in_y0 = in_y0;
     ctx->in_rows = in_y1 - in_y0;
@@ -587,6 +589,8 @@ int lfi_set_params(lfi_ctx *ctx, const lfi_params *p)
     ctx->radius[1] = std::max(p->block_radius[1], 1);
     ctx->flags = p->flags & 0x7fffffffu; // (bit 31 is the dispatcher's own: LFI_KFLAG_PLAIN_TILE_ORDER, lfi_device.hpp)
 
+    if(views_changed)
+        drop_kept(ctx); // the kept views' indices belong to the old number of views (the stream has been drained above)
     if(views_changed || !ctx->views)
     {
         const bool was_attached = ctx->views && !ctx->views.owned();
@@ -707,6 +711,7 @@ int lfi_set_output_layout(lfi_ctx *ctx, int layout)
         return rc;
     LFI_HIP(ctx, hipStreamSynchronize(ctx->stream));
     free_views(ctx); // an attached buffer is dropped too: its size belongs to the old layout
+    drop_kept(ctx);  // kept in the old layout
     ctx->out_layout = layout;
     if(ctx->have_params)
     {
@@ -1178,7 +1183,8 @@ int lfi_memory_info(lfi_ctx *ctx, lfi_memory *out)
     out->derived_bytes = ctx->planar.bytes();
     out->views_bytes = ctx->views.bytes();
     out->maps_bytes = (ctx->maps ? plane_bytes(ctx) * 2 : 0) + ctx->view_maps.bytes();
-    out->workspace_bytes = ctx->focus_ws.bytes() + ctx->curve_ws.bytes() + ctx->rgba_scratch.bytes() + ctx->dl_plane.bytes();
+    out->workspace_bytes = ctx->focus_ws.bytes() + ctx->curve_ws.bytes() + ctx->rgba_scratch.bytes() + ctx->dl_plane.bytes() + ctx->kept.bytes() +
+                           ctx->cmp_stage[0].bytes() + ctx->cmp_stage[1].bytes() + ctx->cmp_ws.bytes();
     out->derived_build_ms = ctx->derived_build_ms;
     return LFI_OK;
 }
@@ -1325,6 +1331,182 @@ int lfi_compare_view(lfi_ctx *ctx, int v, const uint8_t *reference_rgba, size_t 
     }
     out->psnr_all = mse_all > 0 ? 10.0 * std::log10(255.0 * 255.0 / mse_all) : INFINITY;
     out->ssim_all = ssim_all;
+    return LFI_OK;
+}
+
+int lfi_keep_views(lfi_ctx *ctx, int v0, int n)
+{
+    if(!ctx)
+        return LFI_EINVAL;
+    if(n == 0)
+    {
+        if(int rc = bind(ctx))
+            return rc;
+        drop_kept(ctx); // hipFree waits for a copy into the set that is still in flight
+        return LFI_OK;
+    }
+    if(!ctx->views || !ctx->have_params)
+        return fail(ctx, LFI_EINVAL, "nothing rendered yet");
+    if(v0 < 0 || n < 0 || (long)v0 + n > ctx->views_n)
+        return fail(ctx, LFI_EINVAL, "lfi_keep_views: views [v0, v0 + n) must lie inside [0, views)");
+    if(int rc = bind(ctx))
+        return rc;
+    // Views are written on the stream in use only (renders, the planar conversion, poison), never on the copy or the side stream: the copy
+    // below needs no join with pending uploads or the focus map's filter.  With a row window the band's rows are kept, as the views hold them
+    // (lfi_compare_views refuses windows; lfi_set_row_window drops the set).
+    const size_t stride = out_plane_bytes(ctx), bytes = stride * n;
+    ctx->kept_v0 = ctx->kept_n = 0;
+    LFI_HIP(ctx, ctx->kept.fit(bytes)); // another size: the old set is freed (compares are synchronous: nothing reads it any more)
+    // behind the renders already enqueued, in front of the later ones: the views as they are at this point of the stream
+    LFI_HIP(ctx, hipMemcpyAsync(ctx->kept.get(), ctx->views.get() + (size_t)v0 * stride, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+    ctx->kept_v0 = v0;
+    ctx->kept_n = n;
+    return LFI_OK;
+}
+
+namespace {
+
+constexpr size_t COMPARE_CHUNK_BYTES = (size_t)64 << 20; // host references cross PCIe in chunks of at most this many bytes (at least one image)
+
+double psnr_of(double mse)
+{
+    return mse > 0 ? 10.0 * std::log10(255.0 * 255.0 / mse) : INFINITY;
+}
+
+// psnr, psnr_all and ssim_all from mse[] and ssim[]: lfi_compare_view's arithmetic
+void finish_quality(lfi_quality *q)
+{
+    double mse_all = 0, ssim_all = 0;
+    for(int c = 0; c < 3; c++)
+    {
+        q->psnr[c] = psnr_of(q->mse[c]);
+        mse_all += q->mse[c] / 3.0;
+        ssim_all += q->ssim[c] / 3.0;
+    }
+    q->psnr_all = psnr_of(mse_all);
+    q->ssim_all = ssim_all;
+}
+
+} // namespace
+
+int lfi_compare_views(lfi_ctx *ctx, int v0, int n, const uint8_t *references_rgba, size_t pitch_bytes, size_t image_stride_bytes, lfi_view_quality *out,
+                      lfi_quality *out_all)
+{
+    if(!ctx)
+        return LFI_EINVAL;
+    if(!out)
+        return fail(ctx, LFI_EINVAL, "lfi_compare_views: out is NULL");
+    if(!ctx->views || !ctx->have_params)
+        return fail(ctx, LFI_EINVAL, "nothing rendered yet");
+    if(ctx->windowed)
+        return fail(ctx, LFI_EINVAL, "lfi_compare_views needs whole views (no row window)");
+    if(v0 < 0 || n < 1 || (long)v0 + n > ctx->views_n)
+        return fail(ctx, LFI_EINVAL, "lfi_compare_views: views [v0, v0 + n), n >= 1, must lie inside [0, views)");
+    const int W = ctx->width, H = ctx->height;
+    if(references_rgba)
+    {
+        if(pitch_bytes < (size_t)W * 4 || image_stride_bytes / (size_t)H < pitch_bytes)
+            return fail(ctx, LFI_EINVAL, "lfi_compare_views: bad pitch (>= width * 4) or image stride (>= pitch * height)");
+    }
+    else if(!ctx->kept)
+        return fail(ctx, LFI_EINVAL, "lfi_compare_views: no reference images and no kept views (lfi_keep_views)");
+    else if(v0 < ctx->kept_v0 || v0 + n > ctx->kept_v0 + ctx->kept_n)
+        return fail(ctx, LFI_EINVAL, "lfi_compare_views: the kept views do not cover [v0, v0 + n)");
+    if(int rc = bind(ctx))
+        return rc;
+    if(int rc = join_uploads(ctx))
+        return rc;
+    // n <= views <= 4096 (lfi_set_params): the launch grid's z dimension stays far below its limit of 65535
+    const int tiles = lfi::quality_tiles_x(W) * lfi::quality_tiles_y(H);
+    const size_t records_bytes = sizeof(lfi::QualityViewSums) * (size_t)n;
+    LFI_HIP(ctx, ctx->cmp_ws.reserve(records_bytes + sizeof(lfi::QualityPartial) * (size_t)n * tiles));
+    lfi::QualityViewSums *const d_records = ctx->cmp_ws.as<lfi::QualityViewSums>();
+    lfi::QualityPartial *const d_partials = reinterpret_cast<lfi::QualityPartial *>(ctx->cmp_ws.get() + records_bytes);
+    const bool planar = ctx->out_layout == LFI_LAYOUT_PLANAR_RGB;
+    const size_t stride = out_plane_bytes(ctx);
+    const uint32_t view_row = planar ? (uint32_t)view_pitch(ctx) : (uint32_t)W * 4u;
+    const lfi::QualityImages a{ctx->views.get() + (size_t)v0 * stride, stride, view_row};
+    if(!references_rgba)
+    {
+        // kept views, in the views' layout: one launch for all n
+        const lfi::QualityImages b{ctx->kept.get() + (size_t)(v0 - ctx->kept_v0) * stride, stride, view_row};
+        LFI_HIP(ctx, lfi::launch_quality_tiles(ctx->stream, planar, planar, a, b, W, H, n, d_partials));
+    }
+    else
+    {
+        // chunks of `per` images through two staging buffers: the copy of chunk k + 1 (copy stream) runs beside the reduction of chunk k
+        const size_t image = plane_bytes(ctx), row = (size_t)W * 4;
+        const int per = (int)std::min<size_t>((size_t)n, std::max<size_t>(COMPARE_CHUNK_BYTES / image, 1));
+        if(int rc = ensure_copy_stream(ctx))
+            return rc;
+        for(int i = 0; i < 2; i++)
+        {
+            LFI_HIP(ctx, ctx->ev_cmp_copied[i].ensure());
+            LFI_HIP(ctx, ctx->ev_cmp_reduced[i].ensure());
+            if(i == 0 || per < n)
+                LFI_HIP(ctx, ctx->cmp_stage[i].reserve(image * per));
+        }
+        // the staging buffers are written on the copy stream: behind whatever the stream in use still has queued for them (a reserve's
+        // predecessor is gone, but lfi_debug_poison fills them in stream order) — one event, no host wait
+        LFI_HIP(ctx, hipEventRecord(ctx->ev_cmp_reduced[0], ctx->stream));
+        LFI_HIP(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->ev_cmp_reduced[0], 0));
+        for(int c0 = 0, k = 0; c0 < n; c0 += per, k++)
+        {
+            const int slot = k & 1, cnt = std::min(per, n - c0);
+            if(k >= 2) // the buffer is free again once the chunk before last has been reduced
+                LFI_HIP(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->ev_cmp_reduced[slot], 0));
+            const uint8_t *src = references_rgba + (size_t)c0 * image_stride_bytes;
+            if(image_stride_bytes == pitch_bytes * H) // the images' rows follow each other: one copy for the chunk
+                LFI_HIP(ctx, hipMemcpy2DAsync(ctx->cmp_stage[slot].get(), row, src, pitch_bytes, row, (size_t)cnt * H, hipMemcpyHostToDevice, ctx->copy_stream));
+            else
+                for(int i = 0; i < cnt; i++)
+                    LFI_HIP(ctx, hipMemcpy2DAsync(ctx->cmp_stage[slot].get() + (size_t)i * image, row, src + (size_t)i * image_stride_bytes, pitch_bytes, row, H,
+                                                  hipMemcpyHostToDevice, ctx->copy_stream));
+            LFI_HIP(ctx, hipEventRecord(ctx->ev_cmp_copied[slot], ctx->copy_stream));
+            LFI_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_cmp_copied[slot], 0));
+            const lfi::QualityImages ac{a.base + (size_t)c0 * stride, stride, view_row};
+            const lfi::QualityImages b{ctx->cmp_stage[slot].get(), image, (uint32_t)row};
+            LFI_HIP(ctx, lfi::launch_quality_tiles(ctx->stream, planar, false, ac, b, W, H, cnt, d_partials + (size_t)c0 * tiles));
+            LFI_HIP(ctx, hipEventRecord(ctx->ev_cmp_reduced[slot], ctx->stream));
+        }
+    }
+    hipLaunchKernelGGL(lfi::quality_views, dim3(n), dim3(256), 0, ctx->stream, d_partials, tiles, d_records);
+    LFI_HIP(ctx, hipGetLastError());
+    std::vector<lfi::QualityViewSums> sums(n);
+    LFI_HIP(ctx, hipMemcpyAsync(sums.data(), d_records, records_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    LFI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+
+    const double px = (double)W * H;
+    unsigned long long total[3] = {0ull, 0ull, 0ull};
+    double ssim_views[3] = {0.0, 0.0, 0.0};
+    for(int k = 0; k < n; k++)
+    {
+        const lfi::QualityViewSums &s = sums[k];
+        lfi_view_quality &o = out[k];
+        std::memset(&o, 0, sizeof(o)); // padding included: equal results are equal bytes
+        for(int c = 0; c < 3; c++)
+        {
+            o.sq_err[c] = s.sq_err[c];
+            o.q.mse[c] = (double)s.sq_err[c] / px;
+            o.q.ssim[c] = s.windows ? s.ssim[c] / (double)s.windows : 1.0;
+            total[c] += s.sq_err[c];
+            ssim_views[c] += o.q.ssim[c];
+        }
+        finish_quality(&o.q);
+        o.differing_bytes = s.differing;
+        o.windows = s.windows;
+        o.max_abs_diff = s.max_abs_diff;
+    }
+    if(out_all)
+    {
+        std::memset(out_all, 0, sizeof(*out_all));
+        for(int c = 0; c < 3; c++)
+        {
+            out_all->mse[c] = (double)total[c] / (double)((unsigned long long)n * (unsigned long long)W * (unsigned long long)H);
+            out_all->ssim[c] = ssim_views[c] / (double)n;
+        }
+        finish_quality(out_all);
+    }
     return LFI_OK;
 }
 
@@ -1848,6 +2030,9 @@ int lfi_debug_poison(lfi_ctx *ctx, uint32_t what, uint8_t byte)
         rc = rc ? rc : fill(ctx->prequant, ctx->prequant.bytes());
         rc = rc ? rc : fill(ctx->quilt, ctx->quilt.bytes());
         rc = rc ? rc : fill(ctx->views2, ctx->views2.bytes());
+        rc = rc ? rc : fill(ctx->cmp_stage[0], ctx->cmp_stage[0].bytes());
+        rc = rc ? rc : fill(ctx->cmp_stage[1], ctx->cmp_stage[1].bytes());
+        rc = rc ? rc : fill(ctx->cmp_ws, ctx->cmp_ws.bytes());
     }
     if(what & LFI_POISON_MAPS)
         rc = rc ? rc : fill(ctx->maps, ctx->maps ? plane_bytes(ctx) * 2 : 0);

@@ -200,6 +200,8 @@ void Interpolator::interpolate(std::string outputPath, std::string trajectory, f
         params.flags |= LFI_FLAG_UNIFIED_FOCUS_MAP;
     if(gpuCount < 1 || gpuCount > viewCount)
         throw std::runtime_error("The number of GPUs has to be between 1 and the number of views!");
+    if((compareMethods || !compareDir.empty()) && gpuCount > 1)
+        throw std::runtime_error("Comparing views (--compare, --compare-methods) works on one GPU only!");
     shardOverGpus(params);
     // The views never leave the library except through lfi_download_view / _quilt, which re-create the constant alpha: fixed-focus
     // TEN_WM renders therefore use the alpha-free byte-plane layout (a quarter fewer bytes written per launch, csrc/hip/blend_p3.hpp);
@@ -254,6 +256,14 @@ void Interpolator::interpolate(std::string outputPath, std::string trajectory, f
             check(lfi_focus_map(c), c);
     }
 
+    if(compareMethods)
+    {
+        // the other method's views of the same parameters stay on the device as the references of the comparison
+        std::cout << "Rendering the views to compare with (" << (methodID == LFI_METHOD_TEN_WM ? "STD" : "TEN_WM") << ")..." << std::endl;
+        check(lfi_render(context, methodID == LFI_METHOD_TEN_WM ? LFI_METHOD_STD : LFI_METHOD_TEN_WM, allFocus, 0, viewCount));
+        check(lfi_keep_views(context, 0, viewCount));
+    }
+
     std::cout << "Rendering views..." << std::endl;
     std::cout << "Elapsed time: " << std::endl;
     double medianMs;
@@ -296,7 +306,63 @@ void Interpolator::interpolate(std::string outputPath, std::string trajectory, f
     const double seconds = medianMs / 1000.0;
     std::cout << ": " << viewCount / seconds << " views/s, "
               << static_cast<double>(viewCount) * resolution.x * resolution.y / seconds / 1e9 << " Gpix/s" << std::endl;
+    if(compareMethods)
+        compareViews(true);
+    if(!compareDir.empty())
+        compareViews(false);
     storeResults(outputPath);
+}
+
+// All views against the kept views of the other method, or against NN.png of compareDir: one lfi_compare_views call, one line per view.
+void Interpolator::compareViews(bool withKept)
+{
+    const size_t pitch = static_cast<size_t>(resolution.x) * channels;
+    const size_t imageBytes = pitch * resolution.y;
+    uint8_t *references = nullptr;
+    bool pinned = false;
+    std::vector<uint8_t> pageable;
+    if(!withKept)
+    {
+        std::cout << "Loading the images to compare with..." << std::endl;
+        pinned = lfi_alloc_pinned(imageBytes * viewCount, reinterpret_cast<void **>(&references)) == LFI_OK;
+        if(!pinned)
+        {
+            pageable.resize(imageBytes * viewCount);
+            references = pageable.data();
+        }
+        try
+        {
+            for(int i = 0; i < viewCount; i++)
+            {
+                const auto fileName = std::filesystem::path(compareDir) / (std::string(((i < 10) ? "0" : "")) + std::to_string(i) + ".png");
+                if(!std::filesystem::exists(fileName))
+                    throw std::runtime_error("Cannot compare: " + fileName.string() + " does not exist!");
+                const lfi::Image image = lfi::loadImage(fileName.string());
+                if(image.width != resolution.x || image.height != resolution.y)
+                    throw std::runtime_error("Cannot compare: " + fileName.string() + " is " + std::to_string(image.width) + "x" + std::to_string(image.height) +
+                                             ", the views are " + std::to_string(resolution.x) + "x" + std::to_string(resolution.y) + "!");
+                std::copy(image.pixels.begin(), image.pixels.end(), references + imageBytes * i);
+            }
+        }
+        catch(...)
+        {
+            if(pinned)
+                lfi_free_pinned(references);
+            throw;
+        }
+    }
+    std::vector<lfi_view_quality> quality(viewCount);
+    lfi_quality all{};
+    const int status = lfi_compare_views(context, 0, viewCount, references, pitch, imageBytes, quality.data(), &all);
+    if(pinned)
+        lfi_free_pinned(references);
+    check(status);
+    // nine significant digits, as the other printed results
+    std::cout << std::setprecision(9);
+    for(int i = 0; i < viewCount; i++)
+        std::cout << "compare " << (i < 10 ? "0" : "") << i << " psnr " << quality[i].q.psnr_all << " ssim " << quality[i].q.ssim_all << " maxdiff "
+                  << quality[i].max_abs_diff << " differing " << quality[i].differing_bytes << std::endl;
+    std::cout << "compare all psnr " << all.psnr_all << " ssim " << all.ssim_all << std::setprecision(6) << std::endl;
 }
 
 void Interpolator::storeResults(std::string path)

@@ -54,6 +54,13 @@ class Interpolator
         // auto range, for all-focus renders: the tiles' minima over [focus, focus + range] give the interval the map is then estimated over
         // and the views rendered with (lfi::focusAutoRange) instead of the interval given.  Not with setAutofocus
         void setAutoRange(lfi::IVec2 grid) { autoRange = grid; }
+        // after the render, compare every view with NN.png of this directory (the names storeResults writes; the reference's
+        // scripts/compareDirs.sh) in one lfi_compare_views call and print "compare NN psnr … ssim … maxdiff … differing …" per view, then
+        // "compare all psnr … ssim …".  One GPU
+        void setCompareDir(std::string dir) { compareDir = dir; }
+        // render the views with the OTHER method first (same parameters, focus mode, layout, per-view settings), keep them on the device
+        // (lfi_keep_views), render with the method asked for and compare against the kept views there; the same lines.  One GPU
+        void setCompareMethods(bool on) { compareMethods = on; }
 
         // synthetic cols×rows grid of width×height images instead of a directory
         Interpolator(lfi::IVec2 colsRows, lfi::IVec2 resolution, uint32_t seed, int device = 0);
@@ -77,6 +84,8 @@ class Interpolator
         int autofocusSteps{32};
         lfi::IVec2 focusTiles{0, 0}; // 0: off
         lfi::IVec2 autoRange{0, 0};  // 0: off
+        std::string compareDir;      // empty: off
+        bool compareMethods{false};
         std::vector<lfi_ctx *> contexts; // one per GPU; contexts[0] == context
         std::vector<int> viewStart;      // first view of each GPU's range (size gpuCount + 1)
         float focus{0};
@@ -89,6 +98,7 @@ class Interpolator
         void init();
         void loadGPUData();
         void storeResults(std::string path);
+        void compareViews(bool withKept);
         void check(int status) const;
         void check(int status, lfi_ctx *where) const;
         void shardOverGpus(const lfi::HostParams &params);

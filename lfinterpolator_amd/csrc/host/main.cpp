@@ -1,7 +1,8 @@
 // main.cpp — command line of the interpolator; flags, defaults, messages and exit codes as in reference src/main.cpp:4-57
 // (-i -t -o -f -r -m -s -a -h), plus -n (views), -b (benchmark runs), -d (device), -F (focus at the last view), -c (shifts about each
 // view's own camera), --autofocus (the focus found from a region's focus curve), --focus-tiles / --auto-range (the focus of every tile of a
-// grid; the search interval of an all-focus render found from it) and --synthetic for runs without a dataset.
+// grid; the search interval of an all-focus render found from it), --compare / --compare-methods (PSNR / SSIM of all views against a
+// directory of images or against the other method's render) and --synthetic for runs without a dataset.
 #include <array>
 #include <iostream>
 #include <memory>
@@ -48,6 +49,8 @@ int main(int argc, char **argv)
                           "-g - number of GPUs: the views are split over GPUs d … d+g-1, the input grid is broadcast once (default=1)\n"
                           "-q - also store quilt.png: the first cols*rows views as cols,rows tiles (e.g. 5,9 for a Looking Glass quilt)\n"
                           "--quilt-tile WxH - with -q: resize every view to a tile of W x H pixels on the GPU before quilt.png is stored (an exact area filter; downscaling only, at most the views' size), e.g. -q 5,9 --quilt-tile 819x455 for a 4096 x 4096 quilt\n"
+                          "--compare DIR - after the render, compare every view with DIR/NN.png (the names -o writes; same size) on the GPU, all views in one pass: prints \"compare NN psnr <dB> ssim <index> maxdiff <largest byte difference> differing <colour bytes that differ>\" per view, then \"compare all psnr ... ssim ...\"; one GPU\n"
+                          "--compare-methods - render the views with the other method first (STD if -m TEN_WM, TEN_WM if -m STD; same parameters), keep them on the GPU, render with -m and compare the two there; prints the lines of --compare; the stored images are those of -m; one GPU; not with --compare\n"
                           "--synthetic cols,rows,width,height[,seed] - use a generated light field instead of -i\n"
                           "--unified-map - all-focus TEN_WM reads the filtered focus map like STD (the reference reads the unfiltered one)\n"
                         };
@@ -102,6 +105,24 @@ int main(int argc, char **argv)
     if(args["--quilt-tile"] && !args["-q"])
     {
         std::cerr << "--quilt-tile sets the tile size of the quilt: it needs -q cols,rows." << std::endl;
+        return EXIT_FAILURE;
+    }
+
+    if(args["--compare"] && args["--compare-methods"])
+    {
+        std::cerr << "--compare (against a directory) and --compare-methods (against the other method) print the same lines: use one of them." << std::endl;
+        return EXIT_FAILURE;
+    }
+
+    if(args["--compare"] && static_cast<std::string>(args["--compare"]).empty())
+    {
+        std::cerr << "--compare needs the directory of the images to compare with." << std::endl;
+        return EXIT_FAILURE;
+    }
+
+    if((args["--compare"] || args["--compare-methods"]) && args["-g"] && static_cast<int>(args["-g"]) > 1)
+    {
+        std::cerr << "--compare and --compare-methods work on one GPU only (-g 1)." << std::endl;
         return EXIT_FAILURE;
     }
 
@@ -206,6 +227,10 @@ int main(int argc, char **argv)
         }
         if(args["--quilt-tile"])
             interpolator->setQuiltTile(tileGrid(static_cast<std::string>(args["--quilt-tile"]), "--quilt-tile", "WxH, the tile's width x height in pixels, both at least 1"));
+        if(args["--compare"])
+            interpolator->setCompareDir(static_cast<std::string>(args["--compare"]));
+        if(args["--compare-methods"])
+            interpolator->setCompareMethods(true);
         interpolator->interpolate(outputPath, trajectory, focus, range, method, effect, aspect);
     }
     catch(const std::exception &e)
