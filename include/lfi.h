@@ -283,6 +283,26 @@ int lfi_views_device_ptr(lfi_ctx *ctx, void **out_ptr, size_t *out_bytes);
  * light field (the reference's focusMapCompare.sh loop) pads once.  The map is estimated at the trajectory's centre from lfi_params.offsets
  * and focus_map_ids, whether or not per-view float offsets (lfi_set_view_float_offsets) are set. */
 int lfi_focus_map(lfi_ctx *ctx);
+/* Fine focus maps: the number of focus candidates lfi_focus_map chooses every pixel's focus from.  The reference hard-codes 32
+ * (src/kernels.cu:245); the map byte has 256 levels and the all-focus kernels turn any byte into a focus, focus + byte / 255 * range.
+ * With `steps` candidates:
+ *  - f_i = fmaf(range / (float)(steps - 1), (float)i, focus), for i in [0, steps);
+ *  - a pixel's winner is the first i with the strictly smallest comparison key;
+ *  - the key is 16 * S_i, or, where S_i = 0, the number of FLT_MIN taps: the reference's MinDispersion (src/kernels.cu:219-237) over its float sum;
+ *  - map 0 byte = round((f_best - focus) / range * 255), in float32;
+ *  - map 1 is the unchanged filter of map 0.
+ * With steps = 32 every byte is what it is without the call.
+ *  - allowed: the multiples of 32 from 32 to 256; anything else returns LFI_EINVAL with a message and keeps the setting;
+ *  - a context setting, default 32, that lives until it is changed: lfi_set_grid, lfi_set_params and lfi_set_row_window do not touch it;
+ *  - it governs lfi_focus_map, whole frame and under a row window.  lfi_view_focus_maps and lfi_focus_tiles keep 32 candidates;
+ *    lfi_focus_curve keeps its own `steps` argument;
+ *  - the estimate variants "factored" (default), "factored_direct" and "packed_p2" honour it (as does the row-window path); with "lds" or
+ *    "plain" selected, lfi_focus_map returns LFI_EINVAL while the setting is not 32, and leaves the maps untouched;
+ *  - cost: the factored estimate runs one pass per 32 candidates over the same padded planes (a change of steps alone pads nothing) and
+ *    carries each pixel's minimum between the passes in one more plane of its workspace (4 bytes per pixel, lfi_memory.workspace_bytes,
+ *    LFI_POISON_FOCUS_WORKSPACE), which every call initialises itself. */
+int lfi_set_focus_steps(lfi_ctx *ctx, int steps);
+int lfi_focus_steps(lfi_ctx *ctx, int *out_steps);
 /* Autofocus: the focus CURVE of the region [x0, x1) x [y0, y1) and its minimum — "what is the focus of this object?" (click-to-focus, or the
  * whole frame for a fixed-focus render).  No counterpart in the reference, whose estimate keeps only each pixel's argmin of the cost
  * (MinDispersion, src/kernels.cu:219-237) and throws the cost away; here the cost is summed over the region per candidate instead, on the

@@ -36,7 +36,7 @@ ABI_SYMBOLS = [
     "lfi_grid_modified", "lfi_prepare", "lfi_memory_info", "lfi_last_kernel_name", "lfi_fill_synthetic_images", "lfi_set_output_layout", "lfi_view_layout", "lfi_fill_synthetic_scene", "lfi_upload_image_async", "lfi_upload_wait", "lfi_render_stream", "lfi_compare_view", "lfi_debug_mfma_f16_chain", "lfi_debug_pk_minmax3_f16", "lfi_std_band_info",
     "lfi_debug_poison", "lfi_set_view_offsets", "lfi_set_view_float_offsets", "lfi_view_focus_maps", "lfi_download_view_map",
     "lfi_upload_view_map", "lfi_focus_curve", "lfi_focus_tiles", "lfi_download_quilt_scaled", "lfi_download_quilt_tiles_scaled",
-    "lfi_keep_views", "lfi_compare_views",
+    "lfi_keep_views", "lfi_compare_views", "lfi_set_focus_steps", "lfi_focus_steps",
 ]
 
 
@@ -131,6 +131,8 @@ def load_hip_library() -> C.CDLL:
         "lfi_attach_views": (i, [vp, vp, sz]),
         "lfi_views_device_ptr": (i, [vp, C.POINTER(vp), C.POINTER(sz)]),
         "lfi_focus_map": (i, [vp]),
+        "lfi_set_focus_steps": (i, [vp, i]),
+        "lfi_focus_steps": (i, [vp, C.POINTER(i)]),
         "lfi_focus_curve": (i, [vp, i, i, i, i, i, vp, C.POINTER(FocusCurveResult)]),
         "lfi_focus_tiles": (i, [vp, i, i, vp, C.POINTER(FocusCurveResult)]),
         "lfi_render": (i, [vp, i, i, i, i]),
@@ -359,6 +361,16 @@ class Context:
     # -- kernels -------------------------------------------------------------------------------------------------
     def focus_map(self) -> None:
         self._check(self._lib.lfi_focus_map(self._h))
+
+    def set_focus_steps(self, steps: int) -> None:
+        """Fine focus maps (lfi_set_focus_steps): focus_map chooses every pixel's focus from `steps` candidates of [focus, focus + range], a
+        multiple of 32 from 32 (the default: the reference's) to 256.  A context setting; view_focus_maps and focus_tiles keep 32."""
+        self._check(self._lib.lfi_set_focus_steps(self._h, int(steps)))
+
+    def focus_steps(self) -> int:
+        out = C.c_int(0)
+        self._check(self._lib.lfi_focus_steps(self._h, C.byref(out)))
+        return out.value
 
     def focus_curve(self, x0: int, y0: int, x1: int, y1: int, steps: int = 32):
         """Autofocus (lfi_focus_curve): the focus curve of the region [x0, x1) x [y0, y1) over `steps` candidates of [focus, focus + range]

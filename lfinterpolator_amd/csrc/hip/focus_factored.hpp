@@ -38,7 +38,7 @@
 
 namespace lfi {
 
-constexpr int FOCUS_STEPS = 32; // src/kernels.cu:245
+// (FOCUS_STEPS = 32, lfi_device.hpp: the candidates of ONE pass.  Every use in this file means that — a sweep's length is KernelArgs::focus_steps)
 constexpr int FOCUS_MAX_IDS = 32;
 
 struct FocusWork
@@ -64,6 +64,7 @@ struct FocusWork
     int64_t *deltas;    // [32][32]  byte offset of (slot k's padded plane, row sy, column sx) from the padded base
     uint32_t *pad;      // [n_ids][Hp][Wp]  padded copies: pad[k][yy][xx] = I_ids[k][clamp(yy − Py)][clamp(xx − Px)]
     int32_t Wp, Hp, Px, Py;
+    uint32_t *carry;    // [H][W]  a sweep of more than one pass: key << 8 | sweep index of the first strict minimum over the passes so far
 };
 
 typedef const __attribute__((address_space(4))) int64_t *focus_const_i64_ptr;
@@ -72,10 +73,28 @@ typedef const __attribute__((address_space(4))) int32_t *focus_const_int_ptr;
 typedef const __attribute__((address_space(4))) float *focus_const_float_ptr;
 typedef const __attribute__((address_space(4))) uint32_t *focus_const_u32_ptr;
 
+// Candidate i of a sweep of div + 1 candidates over [focus, focus + range], and the integer shift it gives an image offset: the ONE place
+// either is formed — by the device (focus_candidate, focus_plan_shift) and by the host that sizes focus_range_t's LDS patches and the
+// padding from them (lfi_focus_sched.hpp), so the two cannot drift apart.  (The division is correctly rounded on both sides; the product
+// of two floats is exact in double: the shift every pixel far from a rounding boundary gets.)
+__host__ __device__ __forceinline__ float focus_sweep_value(const float focus, const float range, const float div, const int i)
+{
+#ifdef __HIP_DEVICE_COMPILE__
+    const float step = __fdiv_rn(range, div);
+#else
+    const float step = range / div;
+#endif
+    return __builtin_fmaf(step, static_cast<float>(i), focus);
+}
+__host__ __device__ __forceinline__ int focus_sweep_shift(const float f, const float offset)
+{
+    return static_cast<int>(floor(static_cast<double>(f) * static_cast<double>(offset)));
+}
+
+// candidate i of THIS PASS (i = 0 … 31; the pass starts at a.focus_i0 of the sweep's a.focus_div + 1 candidates)
 __device__ __forceinline__ float focus_candidate(const KernelArgs &a, int i)
 {
-    const float step = __fdiv_rn(a.range, static_cast<float>(FOCUS_STEPS - 1));
-    return __builtin_fmaf(step, static_cast<float>(i), a.focus);
+    return focus_sweep_value(a.focus, a.range, a.focus_div, a.focus_i0 + i);
 }
 
 struct FocusPatch;
@@ -108,9 +127,8 @@ __device__ __forceinline__ void focus_plan_shift(const KernelArgs &a, const Focu
     const float f = focus_candidate(a, i);
     const int g = a.focus_ids[k];
     const lfi_float2 off = a.offsets[g];
-    // the product of two floats is exact in double: the shift every pixel far from a rounding boundary gets
-    dst[0] = static_cast<int>(floor(static_cast<double>(f) * static_cast<double>(off.x)));
-    dst[1] = static_cast<int>(floor(static_cast<double>(f) * static_cast<double>(off.y)));
+    dst[0] = focus_sweep_shift(f, off.x);
+    dst[1] = focus_sweep_shift(f, off.y);
     dst[2] = g;
     dst[3] = 0;
     w.deltas[i * FOCUS_MAX_IDS + k] = (((int64_t)k * w.Hp + dst[1]) * w.Wp + dst[0]) * 4;
@@ -567,6 +585,20 @@ constexpr int FRT_PW = FRT_TW + FRT_MAX_DX;         // a view's patch in LDS: pi
 constexpr int FRT_PR = FRT_TH + FRT_MAX_DY;         // … × rows, at most
 constexpr int FRT_PR_LDS = FRT_PR + 2;              // rows of slots per view in LDS: the patches are fetched in blocks of four rows
 constexpr int FRT_VIEW_B = FRT_PW * FRT_PR_LDS * 8; // 39,936 bytes of 8-byte slots; two views per step, two steps in LDS: 159,744 bytes
+
+// focus_range_t's precondition for one view and the cpw candidates from sweep index i_first: the shifts span at most FRT_MAX_DX pixels and
+// FRT_MAX_DY rows (the patch then fits its slots in LDS).  The host chooses the group size with it; the shifts are focus_plan_shift's.
+__host__ __device__ __forceinline__ bool focus_group_fits(const float focus, const float range, const float div, const int i_first, const int cpw, const lfi_float2 off)
+{
+    int lo[2] = {INT32_MAX, INT32_MAX}, hi[2] = {INT32_MIN, INT32_MIN};
+    for(int i = i_first; i < i_first + cpw; i++)
+    {
+        const float f = focus_sweep_value(focus, range, div, i);
+        const int sx = focus_sweep_shift(f, off.x), sy = focus_sweep_shift(f, off.y);
+        lo[0] = sx < lo[0] ? sx : lo[0], hi[0] = sx > hi[0] ? sx : hi[0], lo[1] = sy < lo[1] ? sy : lo[1], hi[1] = sy > hi[1] ? sy : hi[1];
+    }
+    return hi[0] - lo[0] <= FRT_MAX_DX && hi[1] - lo[1] <= FRT_MAX_DY;
+}
 
 // per (candidate group, view): where the view's patch starts in the padded planes, its size, and where each candidate of the group reads
 struct FocusPatch
@@ -1537,8 +1569,35 @@ __global__ void __launch_bounds__(256) focus_line_keys(const KernelArgs a, const
 // Blocks of 4 rows × 64·PPL pixels, a lane owns PPL ∈ {1, 2} adjacent pixels; PPL = 2 reads both pixels' samples with one
 // dword load and needs an even radius_x (the E columns x + rx ± rx of an even x are then dword aligned) — the reference always
 // produces one (src/interpolator.cu:143-146).  Every sample is scalar plane base + per-lane tap offset.
-template <int PPL>
-__global__ void __launch_bounds__(256) focus_pick(const KernelArgs a, const FocusWork w, const int striped)
+//
+// CARRY (a sweep of more than one pass, lfi_set_focus_steps): a pass merges its 32 keys into the pixel's running minimum in w.carry, one dword
+// key << 8 | sweep index (keys are below 2^16, indices below 2^8): min() of two such words is the smaller key and, between equal keys, the
+// smaller index — the first strict minimum across a pass boundary, as within a pass.  The sweep's first pass (a.focus_i0 = 0) does not read
+// the plane, the last one writes the map byte from the sweep index instead of storing the word.  Both conditions are kernel arguments
+// (uniform); the word is loaded behind the candidate loop — held over the loop it would cost the registers the pick's occupancy lives on.
+template <bool CARRY>
+__device__ __forceinline__ void focus_pick_store(const KernelArgs &a, const FocusWork &w, const size_t px, const uint32_t best_key, int best_i)
+{
+    if constexpr(CARRY)
+    {
+        uint32_t word = (best_key << 8) | uint32_t(a.focus_i0 + best_i);
+        if(a.focus_i0 != 0)
+            word = min(word, w.carry[px]);
+        if(a.focus_i0 + FOCUS_STEPS < a.focus_steps)
+        {
+            w.carry[px] = word;
+            return;
+        }
+        best_i = int(word & 0xffu) - a.focus_i0; // (focus_candidate adds the pass's first index back)
+    }
+    const float best_f = focus_candidate(a, best_i);
+    const float normalized = __fdiv_rn(best_f - a.focus, a.range);
+    const uint32_t m = static_cast<uint32_t>(roundf(normalized * 255.0f)) & 0xffu;
+    reinterpret_cast<uint32_t *>(a.maps)[px] = m | (m << 8) | (m << 16) | 0xff000000u;
+}
+
+template <int PPL, bool CARRY>
+__device__ __forceinline__ void focus_pick_body(const KernelArgs &a, const FocusWork &w, const int striped)
 {
     const int W = a.width, H = a.height;
     const uint32_t blocks_x = uint32_t(W + 64 * PPL - 1) / uint32_t(64 * PPL);
@@ -1648,12 +1707,20 @@ __global__ void __launch_bounds__(256) focus_pick(const KernelArgs a, const Focu
 #pragma unroll
     for(int j = 0; j < PPL; j++)
         if(x + j < W)
-        {
-            const float best_f = focus_candidate(a, best_i[j]);
-            const float normalized = __fdiv_rn(best_f - a.focus, a.range);
-            const uint32_t m = static_cast<uint32_t>(roundf(normalized * 255.0f)) & 0xffu;
-            reinterpret_cast<uint32_t *>(a.maps)[(size_t)y * W + x + j] = m | (m << 8) | (m << 16) | 0xff000000u;
-        }
+            focus_pick_store<CARRY>(a, w, (size_t)y * W + x + j, best_key[j], best_i[j]);
+}
+
+template <int PPL>
+__global__ void __launch_bounds__(256) focus_pick(const KernelArgs a, const FocusWork w, const int striped)
+{
+    focus_pick_body<PPL, false>(a, w, striped);
+}
+
+// one pass of a sweep of several (see CARRY above)
+template <int PPL>
+__global__ void __launch_bounds__(256) focus_pick_carry(const KernelArgs a, const FocusWork w, const int striped)
+{
+    focus_pick_body<PPL, true>(a, w, striped);
 }
 
 // focus_pick with the tap block taken apart (round 5): the dispersion of a pixel is Σ_ty Σ_tx E(x + tx·rx, y + ty·ry) — a vertical three-sum
@@ -1680,7 +1747,8 @@ __host__ __device__ __forceinline__ uint32_t focus_pick_sep_block_rows(const int
     return uint32_t((H + FPS_WAVES * FPS_ROWS * d - 1) / (FPS_WAVES * FPS_ROWS * d)) * uint32_t(d);
 }
 
-__global__ void __launch_bounds__(64 * FPS_WAVES) focus_pick_sep(const KernelArgs a, const FocusWork w)
+template <bool CARRY>
+__device__ __forceinline__ void focus_pick_sep_body(const KernelArgs &a, const FocusWork &w)
 {
     constexpr int R = FPS_ROWS, NR = R + 2; // rows of the map per wave, rows of E it loads for them
     const int W = a.width, H = a.height;
@@ -1873,13 +1941,19 @@ __global__ void __launch_bounds__(64 * FPS_WAVES) focus_pick_sep(const KernelArg
 #pragma unroll
         for(int j = 0; j < 2; j++)
             if(x + j < W)
-            {
-                const float best_f = focus_candidate(a, best_i[r][j]);
-                const float normalized = __fdiv_rn(best_f - a.focus, a.range);
-                const uint32_t m = static_cast<uint32_t>(roundf(normalized * 255.0f)) & 0xffu;
-                reinterpret_cast<uint32_t *>(a.maps)[(size_t)y * W + x + j] = m | (m << 8) | (m << 16) | 0xff000000u;
-            }
+                focus_pick_store<CARRY>(a, w, (size_t)y * W + x + j, best_key[r][j], best_i[r][j]);
     }
+}
+
+__global__ void __launch_bounds__(64 * FPS_WAVES) focus_pick_sep(const KernelArgs a, const FocusWork w)
+{
+    focus_pick_sep_body<false>(a, w);
+}
+
+// one pass of a sweep of several (focus_pick_store's CARRY)
+__global__ void __launch_bounds__(64 * FPS_WAVES) focus_pick_sep_carry(const KernelArgs a, const FocusWork w)
+{
+    focus_pick_sep_body<true>(a, w);
 }
 
 } // namespace lfi

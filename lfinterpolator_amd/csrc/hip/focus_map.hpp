@@ -103,8 +103,9 @@ __device__ __forceinline__ u16x2 channel_pair(uint32_t px_a, uint32_t px_b)
 }
 
 // PPL pixels per lane (2 or 4); one wave per workgroup (a wave lives ~1 ms: fine-grained dispatch fills the tail)
-template <int PPL, int WPE>
-__global__ void __launch_bounds__(64, WPE) focus_estimate_packed(const KernelArgs a)
+// SWEEP: the candidates are the a.focus_steps of lfi_set_focus_steps (focus_estimate_packed_sweep) instead of the reference's 32
+template <int PPL, bool SWEEP>
+__device__ __forceinline__ void focus_estimate_packed_body(const KernelArgs &a)
 {
     constexpr int NP = PPL / 2; // pixel pairs per lane
     const int lane = threadIdx.x & 63;
@@ -114,8 +115,8 @@ __global__ void __launch_bounds__(64, WPE) focus_estimate_packed(const KernelArg
     if(y >= min(H, a.map_y0 + a.map_rows))
         return; // wave-uniform
     const bool lane_active = x0 < W;
-    constexpr int STEPS = 32; // src/kernels.cu:245
-    const float step = __fdiv_rn(a.range, static_cast<float>(STEPS - 1));
+    const int STEPS = SWEEP ? a.focus_steps : 32; // src/kernels.cu:245
+    const float step = __fdiv_rn(a.range, SWEEP ? a.focus_div : 31.0f);
     const int rx = a.radius_x, ry = a.radius_y;
     const uint32_t *grid32 = reinterpret_cast<const uint32_t *>(a.grid);
     const size_t plane_px = (size_t)W * (size_t)a.in_rows; // the rows this context holds (the host checked that they cover the samples)
@@ -264,6 +265,18 @@ __global__ void __launch_bounds__(64, WPE) focus_estimate_packed(const KernelArg
     for(int j = 0; j < PPL; j++)
         if(x0 + j < W)
             dst[j] = out[j];
+}
+
+template <int PPL, int WPE>
+__global__ void __launch_bounds__(64, WPE) focus_estimate_packed(const KernelArgs a)
+{
+    focus_estimate_packed_body<PPL, false>(a);
+}
+
+template <int PPL, int WPE>
+__global__ void __launch_bounds__(64, WPE) focus_estimate_packed_sweep(const KernelArgs a)
+{
+    focus_estimate_packed_body<PPL, true>(a);
 }
 
 // ------------------------------------------------------------------------------------------------------------------------

@@ -350,6 +350,10 @@ struct lfi_ctx
     uint64_t pad_version = 0;
     int pad_shift[2] = {0, 0}, pad_radius[2] = {0, 0};
     std::vector<int32_t> pad_ids, h_focus_ids;
+    // lfi_set_focus_steps: the candidates of lfi_focus_map's sweep, a multiple of 32 up to 256; a context setting that lfi_set_grid, lfi_set_params
+    // and lfi_set_row_window leave alone.  Above 32 the factored estimate runs one pass per 32 candidates and carries each pixel's minimum
+    // between them in focus_ws's carry plane (lfi_focus_sched.hpp)
+    int focus_steps = lfi::FOCUS_STEPS;
     DeviceBuffer curve_ws; // lfi_focus_curve: the curve and its result, then the per-workgroup partial sums (grows, kept)
     int ten_variant = 0, std_variant = 0, focus_variant = 0;
     mutable const char *last_kernel = ""; // the blend kernel the last render launched (lfi_last_kernel_name)
@@ -538,6 +542,10 @@ KernelArgs make_args(const lfi_ctx *c, int v0, int v1, int all_focus_method)
     a.focus = c->focus;
     a.range = c->range;
     a.flags = c->flags;
+    // the reference's sweep (32 candidates, one pass); lfi_focus_map alone sets the context's focus_steps
+    a.focus_steps = lfi::FOCUS_STEPS;
+    a.focus_div = float(lfi::FOCUS_STEPS - 1);
+    a.focus_i0 = 0;
     return a;
 }
 

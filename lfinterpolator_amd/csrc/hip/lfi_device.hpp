@@ -20,6 +20,11 @@ typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
 typedef uint32_t u32x2_a4 __attribute__((ext_vector_type(2), aligned(4)));
 
+// candidates of the reference's focus sweep (src/kernels.cu:245) = candidates per PASS of the factored estimate (focus_factored.hpp: its flag
+// words, E, K and lists are sized by it); a sweep of lfi_set_focus_steps' candidates is up to FOCUS_MAX_PASSES passes
+constexpr int FOCUS_STEPS = 32;
+constexpr int FOCUS_MAX_PASSES = 8;
+
 // Everything a blend / focus kernel reads besides pixels.  Passed by value as the kernel argument
 // (kernarg segment → scalar loads), where the reference uses cudaMemcpyToSymbol (src/interpolator.cu:134-136,151-153).
 struct KernelArgs
@@ -62,6 +67,11 @@ struct KernelArgs
     int32_t map_index;                      // which focus map an all-focus render reads
     float focus, range;                     // inFocus, inRange
     uint32_t flags;
+    // the focus sweep (focus_factored.hpp, focus_candidate): focus_steps candidates f_i = fma(range / focus_div, i, focus), focus_div = focus_steps − 1;
+    // this launch covers the candidates focus_i0 … focus_i0 + 31 of them (32, 31, 0 everywhere but under lfi_set_focus_steps)
+    int32_t focus_steps;
+    float focus_div;
+    int32_t focus_i0;
 };
 
 // The band method's bound on the matrix core's accumulation error per addend (in units of S, sums below 512) for MORE than 64 images

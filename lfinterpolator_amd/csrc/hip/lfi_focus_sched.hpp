@@ -27,11 +27,14 @@ struct FocusJob
     int padded = 0; // out: focus_pad slots enqueued
 };
 
-// largest |shift| any candidate gives any of the n offsets, +1 (candidates are monotone in i, so the ends bound them); false when absurd
+// largest |shift| any candidate gives any of the n offsets, +1 (candidates are monotone in i, so the ends bound them); false when absurd.
+// The bound is the INTERVAL's: the last candidate of every sweep length lfi_set_focus_steps allows (they differ by a rounding of
+// fma(range / (steps − 1), steps − 1, focus) at most), so a change of the number of candidates alone never asks for other planes.
 bool focus_pad_shift(const lfi_ctx *ctx, const lfi_float2 *offsets, int n, int *Sx, int *Sy)
 {
-    const float step = ctx->range / 31.0f;
-    const double fmax = std::max(std::fabs((double)ctx->focus), std::fabs((double)std::fmaf(step, 31.0f, ctx->focus)));
+    double fmax = std::fabs((double)ctx->focus);
+    for(int steps = lfi::FOCUS_STEPS; steps <= lfi::FOCUS_STEPS * lfi::FOCUS_MAX_PASSES; steps += lfi::FOCUS_STEPS)
+        fmax = std::max(fmax, std::fabs((double)lfi::focus_sweep_value(ctx->focus, ctx->range, float(steps - 1), steps - 1)));
     double ox = 0, oy = 0;
     for(int k = 0; k < n; k++)
     {
@@ -51,16 +54,23 @@ bool focus_pad_shift(const lfi_ctx *ctx, const lfi_float2 *offsets, int n, int *
 // direct_range: the range pass by focus_range (rounds 1-4's kernel: every use loads and widens its own samples) even where focus_range_t
 // applies (variant "factored_direct": the second implementation in the parity tests, and the A/B partner)
 // *e_32bit_out: a candidate's plane of E lies behind one buffer descriptor (focus_pick_sep)
+// The call covers the 32 candidates from a.focus_i0 of a sweep of a.focus_steps (one PASS; 0 of 32 everywhere but lfi_focus_map under
+// lfi_set_focus_steps).  A sweep's later passes (a.focus_i0 > 0) follow its first on the same streams: the padded planes and the geometry
+// are the first pass's — nothing is padded, whatever the bookkeeping says — while the plan, E, Er, Ec and K are rewritten.  Ordering: the
+// side stream's writers of pass g + 1 wait for ev_fork, recorded on the compute stream behind pass g's line keys and pick (and the new plan);
+// the compute stream's line keys and pick of pass g wait for ev_join, behind the side stream's passes — each pass's readers are done before
+// the next one's writers start, on either stream.
 int launch_focus_factored_keys(lfi_ctx *ctx, const KernelArgs &a, FocusJob &job, bool *done, bool direct_range, lfi::FocusWork *w_out, bool *e_32bit_out)
 {
     *done = false;
-    job.padded = 0;
+    const bool later_pass = a.focus_i0 > 0;
+    if(!later_pass)
+        job.padded = 0;
     const int W = ctx->width, H = ctx->height, rx = ctx->radius[0], ry = ctx->radius[1];
     const int n_ids = job.n_ids;
     lfi::FocusWork w{};
     w.We_p = (W + 2 * rx + 255) / 256 * 256;
     w.He_p = (H + 2 * ry + 3) / 4 * 4;
-    const float step = ctx->range / 31.0f;
     int Sx = 0, Sy = 0;
     if(!focus_pad_shift(ctx, job.offsets, n_ids, &Sx, &Sy))
         return LFI_OK;
@@ -71,9 +81,9 @@ int launch_focus_factored_keys(lfi_ctx *ctx, const KernelArgs &a, FocusJob &job,
     // that the neighbouring steps of a focus sweep find them large enough.
     // (also when only SOME images were replaced since — lfi_upload_image —: then only the planes of the sampled images among them are redone)
     const bool same_ids = job.slot_reuse ? ctx->pad_ids.size() == (size_t)n_ids : ctx->pad_ids == std::vector<int32_t>(job.ids, job.ids + n_ids);
-    const bool pad_kept = ctx->grid_tracked && ctx->focus_ws && ctx->pad_version != 0 && ctx->grid_full_version <= ctx->pad_version &&
-                          same_ids && ctx->pad_radius[0] == rx && ctx->pad_radius[1] == ry && ctx->pad_shift[0] >= Sx &&
-                          ctx->pad_shift[1] >= Sy;
+    const bool pad_kept = later_pass || (ctx->grid_tracked && ctx->focus_ws && ctx->pad_version != 0 && ctx->grid_full_version <= ctx->pad_version &&
+                                         same_ids && ctx->pad_radius[0] == rx && ctx->pad_radius[1] == ry && ctx->pad_shift[0] >= Sx &&
+                                         ctx->pad_shift[1] >= Sy);
     // Planes that have to GROW (an ascending sweep) grow by a quarter more than asked for: every change of the geometry rebuilds the planes
     // and may reallocate a workspace of gigabytes (≈ 80 ms per step when it happened on every step of a sweep).
     auto padded = [](const int need, const int had) { return ((had > 0 && need > had ? need + need / 4 : need) + 7) / 8 * 8; };
@@ -89,8 +99,8 @@ int launch_focus_factored_keys(lfi_ctx *ctx, const KernelArgs &a, FocusJob &job,
     if(pad_bytes > ((size_t)16 << 30))
         return LFI_OK;
     // Can the range pass unpack its samples once into LDS (focus_range_t)?  Within every group of CPW consecutive candidates a view's integer
-    // shifts — floor(f_i · offset), the device's own arithmetic (focus_plan_shifts) — must span at most FRT_MAX_DX pixels and FRT_MAX_DY rows:
-    // groups of 8 candidates if that holds, else groups of 4, else focus_range.  Typed loads address the planes with 32 bits.
+    // shifts — the device's own, by the helper it shares with this check (focus_group_fits) — must span at most FRT_MAX_DX pixels and FRT_MAX_DY
+    // rows: groups of 8 candidates if that holds, else groups of 4, else focus_range.  Typed loads address the planes with 32 bits.
     int range_cpw = 0;
     if(!direct_range && pad_bytes < ((size_t)1 << 32))
         for(int cpw : {8, 4})
@@ -98,17 +108,7 @@ int launch_focus_factored_keys(lfi_ctx *ctx, const KernelArgs &a, FocusJob &job,
             bool fits = true;
             for(int k = 0; k < n_ids && fits; k++)
                 for(int i0 = 0; i0 < lfi::FOCUS_STEPS && fits; i0 += cpw)
-                {
-                    int lo[2] = {INT32_MAX, INT32_MAX}, hi[2] = {INT32_MIN, INT32_MIN};
-                    for(int i = i0; i < i0 + cpw; i++)
-                    {
-                        const float f = std::fmaf(step, static_cast<float>(i), ctx->focus);
-                        const int sx = static_cast<int>(std::floor(static_cast<double>(f) * static_cast<double>(job.offsets[k].x)));
-                        const int sy = static_cast<int>(std::floor(static_cast<double>(f) * static_cast<double>(job.offsets[k].y)));
-                        lo[0] = std::min(lo[0], sx), hi[0] = std::max(hi[0], sx), lo[1] = std::min(lo[1], sy), hi[1] = std::max(hi[1], sy);
-                    }
-                    fits = hi[0] - lo[0] <= lfi::FRT_MAX_DX && hi[1] - lo[1] <= lfi::FRT_MAX_DY;
-                }
+                    fits = lfi::focus_group_fits(a.focus, a.range, a.focus_div, a.focus_i0 + i0, cpw, job.offsets[k]);
             if(fits)
             {
                 range_cpw = cpw;
@@ -138,6 +138,9 @@ int launch_focus_factored_keys(lfi_ctx *ctx, const KernelArgs &a, FocusJob &job,
     const size_t o_K = carve(sizeof(uint16_t) * lfi::FOCUS_STEPS * (size_t)H * W);
     const size_t o_deltas = carve(sizeof(int64_t) * lfi::FOCUS_STEPS * lfi::FOCUS_MAX_IDS);
     const size_t o_patches = carve(sizeof(lfi::FocusPatch) * (lfi::FOCUS_STEPS / 4) * lfi::FOCUS_MAX_IDS);
+    // the carry plane of a sweep of several passes (focus_pick_store).  Its room is carved whatever the sweep's length — in front of the padded
+    // planes, whose place in the workspace a change of lfi_set_focus_steps must not move — and touched only by such a sweep.
+    const size_t o_carry = carve(sizeof(uint32_t) * (size_t)H * W);
     const size_t o_pad = carve(pad_bytes);
     bool fresh = false;
     const hipError_t focus_ws_reserve = ctx->focus_ws.reserve(at, &fresh); // a larger workspace serves smaller geometries too
@@ -164,6 +167,7 @@ int launch_focus_factored_keys(lfi_ctx *ctx, const KernelArgs &a, FocusJob &job,
     w.K = reinterpret_cast<uint16_t *>(base + o_K);
     w.deltas = reinterpret_cast<int64_t *>(base + o_deltas);
     w.pad = reinterpret_cast<uint32_t *>(base + o_pad);
+    w.carry = reinterpret_cast<uint32_t *>(base + o_carry);
     lfi::FocusPatch *patches = reinterpret_cast<lfi::FocusPatch *>(base + o_patches);
     // Two streams: the plan and the flagged-pair passes are small, latency-bound kernels; they run beside the padded copy
     // and the range pass (bandwidth / VALU bound) instead of in front of them.
@@ -185,7 +189,9 @@ int launch_focus_factored_keys(lfi_ctx *ctx, const KernelArgs &a, FocusJob &job,
     hipLaunchKernelGGL(lfi::focus_plan_shifts, dim3(1), dim3(1024), 0, st, a, w, patches, range_cpw);
     LFI_HIP(ctx, hipEventRecord(ctx->ev_fork, st));
     bool padded_any = true; // something was enqueued between ev_fork and the range pass
-    if(pad_kept && ctx->pad_version != 0) // (a reallocated workspace cleared pad_version)
+    if(later_pass)
+        padded_any = false;
+    else if(pad_kept && ctx->pad_version != 0) // (a reallocated workspace cleared pad_version)
     {
         padded_any = false;
         for(int k = 0; k < n_ids; k++)
@@ -261,9 +267,11 @@ int launch_focus_factored_keys(lfi_ctx *ctx, const KernelArgs &a, FocusJob &job,
     return LFI_OK;
 }
 
-// the factored estimate's last pass: per pixel the first strict minimum of the keys → map 0 (the caller filters it into map 1)
+// the factored estimate's last pass: per pixel the first strict minimum of the keys → map 0 (the caller filters it into map 1).
+// A sweep of more than 32 candidates: the same kernels' carrying forms, once per pass (focus_pick_store)
 int launch_focus_pick(lfi_ctx *ctx, const KernelArgs &a, const lfi::FocusWork &w, bool e_32bit, bool direct_range)
 {
+    const bool carry = a.focus_steps > lfi::FOCUS_STEPS;
     const int W = ctx->width, H = ctx->height, rx = ctx->radius[0], ry = ctx->radius[1];
     hipStream_t st = ctx->stream;
     {
@@ -277,10 +285,17 @@ int launch_focus_pick(lfi_ctx *ctx, const KernelArgs &a, const lfi::FocusWork &w
         {
             // (row-major order of the workgroups, not stripes per XCD: this kernel's re-use of E's rows happens inside a workgroup)
             const uint32_t nb = blocks_x * lfi::focus_pick_sep_block_rows(H, ry);
-            hipLaunchKernelGGL(lfi::focus_pick_sep, dim3(nb), dim3(64 * lfi::FPS_WAVES), 0, st, a, w);
+            if(carry)
+                hipLaunchKernelGGL(lfi::focus_pick_sep_carry, dim3(nb), dim3(64 * lfi::FPS_WAVES), 0, st, a, w);
+            else
+                hipLaunchKernelGGL(lfi::focus_pick_sep, dim3(nb), dim3(64 * lfi::FPS_WAVES), 0, st, a, w);
         }
+        else if(ppl == 2 && carry)
+            hipLaunchKernelGGL(lfi::focus_pick_carry<2>, dim3(nblocks), dim3(256), 0, st, a, w, striped);
         else if(ppl == 2)
             hipLaunchKernelGGL(lfi::focus_pick<2>, dim3(nblocks), dim3(256), 0, st, a, w, striped);
+        else if(carry)
+            hipLaunchKernelGGL(lfi::focus_pick_carry<1>, dim3(nblocks), dim3(256), 0, st, a, w, striped);
         else
             hipLaunchKernelGGL(lfi::focus_pick<1>, dim3(nblocks), dim3(256), 0, st, a, w, striped);
     }
@@ -288,16 +303,22 @@ int launch_focus_pick(lfi_ctx *ctx, const KernelArgs &a, const lfi::FocusWork &w
     return LFI_OK;
 }
 
-// the whole factored estimate: plan → pad → E → exact keys → pick
+// the whole factored estimate: plan → pad → E → exact keys → pick, once per 32 candidates of a.focus_steps (the padding by the first pass only)
 int launch_focus_factored(lfi_ctx *ctx, const KernelArgs &a, FocusJob &job, bool *done, bool direct_range)
 {
-    lfi::FocusWork w{};
-    bool e_32bit = false;
-    if(int rc = launch_focus_factored_keys(ctx, a, job, done, direct_range, &w, &e_32bit))
-        return rc;
-    if(!*done)
-        return LFI_OK;
-    return launch_focus_pick(ctx, a, w, e_32bit, direct_range);
+    KernelArgs pass = a;
+    for(pass.focus_i0 = 0; pass.focus_i0 < a.focus_steps; pass.focus_i0 += lfi::FOCUS_STEPS)
+    {
+        lfi::FocusWork w{};
+        bool e_32bit = false;
+        if(int rc = launch_focus_factored_keys(ctx, pass, job, done, direct_range, &w, &e_32bit))
+            return rc;
+        if(!*done) // (declined: by the first pass — the later ones take its geometry)
+            return LFI_OK;
+        if(int rc = launch_focus_pick(ctx, pass, w, e_32bit, direct_range))
+            return rc;
+    }
+    return LFI_OK;
 }
 
 // The focus curve of the region [x0, x1) × [y0, y1) (lfi_focus_curve; the caller has checked the arguments): partial sums per workgroup and

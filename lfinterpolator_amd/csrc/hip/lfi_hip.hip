@@ -775,6 +775,24 @@ static void launch_focus_filter(lfi_ctx *ctx, const lfi::KernelArgs &a, hipStrea
         hipLaunchKernelGGL(lfi::focus_filter, dim3((ctx->width + 63) / 64, (a.map_rows + 3) / 4), dim3(256), 0, st, a);
 }
 
+int lfi_set_focus_steps(lfi_ctx *ctx, int steps)
+{
+    if(!ctx)
+        return LFI_EINVAL;
+    if(steps < lfi::FOCUS_STEPS || steps > lfi::FOCUS_STEPS * lfi::FOCUS_MAX_PASSES || steps % lfi::FOCUS_STEPS != 0)
+        return fail(ctx, LFI_EINVAL, "lfi_set_focus_steps: " + std::to_string(steps) + " candidates - the focus map takes a multiple of 32 from 32 to 256");
+    ctx->focus_steps = steps;
+    return LFI_OK;
+}
+
+int lfi_focus_steps(lfi_ctx *ctx, int *out_steps)
+{
+    if(!ctx || !out_steps)
+        return LFI_EINVAL;
+    *out_steps = ctx->focus_steps;
+    return LFI_OK;
+}
+
 int lfi_focus_map(lfi_ctx *ctx)
 {
     if(!ctx)
@@ -787,6 +805,12 @@ int lfi_focus_map(lfi_ctx *ctx)
         return fail(ctx, LFI_EINVAL, "no focus_map_ids in the parameters");
     if(!(ctx->range > 0.0f))
         return fail(ctx, LFI_EINVAL, "focus range must be > 0 for the focus map");
+    // lfi_set_focus_steps: the sweep's length.  The factored estimate (one pass per 32 candidates) and focus_estimate_packed_sweep honour it;
+    // the LDS-staged and the plain kernel are the reference's 32 candidates as written and refuse any other number
+    const bool fine = ctx->focus_steps != lfi::FOCUS_STEPS;
+    if(fine && !ctx->windowed && (ctx->focus_variant == 1 || ctx->focus_variant == 3))
+        return fail(ctx, LFI_EINVAL, std::string("lfi_focus_map: the estimate variant \"") + (ctx->focus_variant == 1 ? "lds" : "plain") +
+                                         "\" computes 32 candidates only (lfi_set_focus_steps is " + std::to_string(ctx->focus_steps) + ")");
     if(int rc = bind(ctx))
         return rc;
     if(int rc = join_uploads(ctx))
@@ -794,6 +818,8 @@ int lfi_focus_map(lfi_ctx *ctx)
     if(int rc = join_filter(ctx)) // the previous map's filter still reads map 0, which this call rewrites
         return rc;
     KernelArgs a = make_args(ctx, 0, ctx->views_n, LFI_METHOD_STD);
+    a.focus_steps = ctx->focus_steps;
+    a.focus_div = float(ctx->focus_steps - 1);
     if(ctx->windowed)
     {
         // Row window (spatial sharding): the maps are whole-image planes, but only the band's rows are computed — map 0 for the band
@@ -811,7 +837,10 @@ int lfi_focus_map(lfi_ctx *ctx)
         }
         a.map_y0 = e0;
         a.map_rows = e1 - e0;
-        hipLaunchKernelGGL((lfi::focus_estimate_packed<2, 4>), dim3((ctx->width + 127) / 128, a.map_rows), dim3(64), 0, ctx->stream, a);
+        if(fine)
+            hipLaunchKernelGGL((lfi::focus_estimate_packed_sweep<2, 4>), dim3((ctx->width + 127) / 128, a.map_rows), dim3(64), 0, ctx->stream, a);
+        else
+            hipLaunchKernelGGL((lfi::focus_estimate_packed<2, 4>), dim3((ctx->width + 127) / 128, a.map_rows), dim3(64), 0, ctx->stream, a);
         LFI_HIP(ctx, hipGetLastError());
         a.map_y0 = ctx->out_y0;
         a.map_rows = ctx->out_rows;
@@ -834,6 +863,8 @@ int lfi_focus_map(lfi_ctx *ctx)
     }
     if(done)
         ;
+    else if(fine) // "packed_p2", and where the factored estimate declined: the variant that takes any number of candidates
+        hipLaunchKernelGGL((lfi::focus_estimate_packed_sweep<2, 4>), dim3((ctx->width + 127) / 128, ctx->height), dim3(64), 0, ctx->stream, a);
     else if(ctx->focus_variant <= 1 && lds_fits) // "lds"
         hipLaunchKernelGGL(lfi::focus_estimate_lds, dim3((ctx->width + 127) / 128, ctx->height), dim3(64), 0, ctx->stream, a);
     else if(ctx->focus_variant == 3) // "plain": one pixel per lane, float min/max exactly as the reference writes it

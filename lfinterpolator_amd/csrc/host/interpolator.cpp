@@ -213,6 +213,8 @@ void Interpolator::interpolate(std::string outputPath, std::string trajectory, f
     if(perViewFocus && allFocus)
         throw std::runtime_error("A focus per view cannot be combined with all-focus rendering (-r)!");
     const size_t n = params.offsets.size();
+    if(mapSteps != 32 && (viewMaps || autofocus))
+        throw std::runtime_error("The candidates of the focus map (--map-steps) cannot be combined with per-view focus maps (--view-maps) or autofocus: those keep their own!");
     if(viewMaps && !(viewCentred && allFocus))
         throw std::runtime_error("A focus map per view needs view-centred shifts (-c) and all-focus rendering (-r)!");
     if(viewCentred)
@@ -253,7 +255,10 @@ void Interpolator::interpolate(std::string outputPath, std::string trajectory, f
     {
         std::cout << "Estimating focus map..." << std::endl;
         for(lfi_ctx *c : contexts)
+        {
+            check(lfi_set_focus_steps(c, mapSteps), c);
             check(lfi_focus_map(c), c);
+        }
     }
 
     if(compareMethods)

@@ -54,6 +54,9 @@ class Interpolator
         // auto range, for all-focus renders: the tiles' minima over [focus, focus + range] give the interval the map is then estimated over
         // and the views rendered with (lfi::focusAutoRange) instead of the interval given.  Not with setAutofocus
         void setAutoRange(lfi::IVec2 grid) { autoRange = grid; }
+        // the candidates the focus map (one map at the trajectory's centre) chooses from: a multiple of 32 up to 256 (lfi_set_focus_steps);
+        // per-view maps, the focus tiles and autofocus keep their own numbers
+        void setMapSteps(int steps) { mapSteps = steps; }
         // after the render, compare every view with NN.png of this directory (the names storeResults writes; the reference's
         // scripts/compareDirs.sh) in one lfi_compare_views call and print "compare NN psnr … ssim … maxdiff … differing …" per view, then
         // "compare all psnr … ssim …".  One GPU
@@ -84,6 +87,7 @@ class Interpolator
         int autofocusSteps{32};
         lfi::IVec2 focusTiles{0, 0}; // 0: off
         lfi::IVec2 autoRange{0, 0};  // 0: off
+        int mapSteps{32};
         std::string compareDir;      // empty: off
         bool compareMethods{false};
         std::vector<lfi_ctx *> contexts; // one per GPU; contexts[0] == context

@@ -1,7 +1,7 @@
 // main.cpp — command line of the interpolator; flags, defaults, messages and exit codes as in reference src/main.cpp:4-57
 // (-i -t -o -f -r -m -s -a -h), plus -n (views), -b (benchmark runs), -d (device), -F (focus at the last view), -c (shifts about each
 // view's own camera), --autofocus (the focus found from a region's focus curve), --focus-tiles / --auto-range (the focus of every tile of a
-// grid; the search interval of an all-focus render found from it), --compare / --compare-methods (PSNR / SSIM of all views against a
+// grid; the search interval of an all-focus render found from it), --map-steps (more than 32 candidates for the focus map), --compare / --compare-methods (PSNR / SSIM of all views against a
 // directory of images or against the other method's render) and --synthetic for runs without a dataset.
 #include <array>
 #include <iostream>
@@ -42,6 +42,7 @@ int main(int argc, char **argv)
                           "--autofocus-steps - number of focus candidates searched, 2 to 256 (default=32)\n"
                           "--focus-tiles CxR - print the focus of every tile of a grid of C columns x R rows over the frame, searched in [f, f+r] (-r required): \"focus tiles: C x R\", then \"tile <tx> <ty> index <i> focus <value>\" per tile, row by row; the render follows as usual\n"
                           "--auto-range [CxR] - for all-focus renders (-r): find the interval the scene occupies from the focus tiles of a C x R grid (default 16x9) over [f, f+r] - from one candidate below the nearest tile's focus to one above the farthest's - and estimate the map and render with it in place of -f, -r; prints \"auto-range: focus <f'> range <r'> (candidates <lo>..<hi>)\"; not with --autofocus\n"
+                          "--map-steps N - for all-focus renders (-r): choose every pixel's focus from N candidates of [f, f+r] instead of 32, N a multiple of 32 up to 256 (a finer focus map, about N/32 times the estimate's time); with --auto-range the tiles find the interval at 32 candidates and the map is estimated with N inside it; not with --view-maps, --autofocus\n"
                           "Additional arguments:\n"
                           "-n - number of views rendered along the trajectory (default=64)\n"
                           "-b - number of timed kernel launches (default=100)\n"
@@ -100,6 +101,26 @@ int main(int argc, char **argv)
     {
         std::cerr << "--auto-range (an all-focus render) cannot be combined with --autofocus (a fixed-focus render)." << std::endl;
         return EXIT_FAILURE;
+    }
+
+    if(args["--map-steps"])
+    {
+        const int steps = static_cast<int>(args["--map-steps"]);
+        if(!args["-r"])
+        {
+            std::cerr << "--map-steps (the candidates of the focus map) needs -r (all-focus rendering)." << std::endl;
+            return EXIT_FAILURE;
+        }
+        if(args["--view-maps"] || args["--autofocus"])
+        {
+            std::cerr << "--map-steps cannot be combined with --view-maps (per-view maps keep 32 candidates) or --autofocus (--autofocus-steps sets its candidates)." << std::endl;
+            return EXIT_FAILURE;
+        }
+        if(steps < 32 || steps > 256 || steps % 32 != 0)
+        {
+            std::cerr << "--map-steps expects a multiple of 32 from 32 to 256." << std::endl;
+            return EXIT_FAILURE;
+        }
     }
 
     if(args["--quilt-tile"] && !args["-q"])
@@ -210,6 +231,8 @@ int main(int argc, char **argv)
                 throw std::runtime_error(std::string(flag) + " expects " + meaning);
             return grid;
         };
+        if(args["--map-steps"])
+            interpolator->setMapSteps(static_cast<int>(args["--map-steps"]));
         if(args["--focus-tiles"])
             interpolator->setFocusTiles(tileGrid(static_cast<std::string>(args["--focus-tiles"]), "--focus-tiles"));
         if(args["--auto-range"])
