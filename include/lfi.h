@@ -294,8 +294,8 @@ int lfi_focus_map(lfi_ctx *ctx);
  * With steps = 32 every byte is what it is without the call.
  *  - allowed: the multiples of 32 from 32 to 256; anything else returns LFI_EINVAL with a message and keeps the setting;
  *  - a context setting, default 32, that lives until it is changed: lfi_set_grid, lfi_set_params and lfi_set_row_window do not touch it;
- *  - it governs lfi_focus_map, whole frame and under a row window.  lfi_view_focus_maps and lfi_focus_tiles keep 32 candidates;
- *    lfi_focus_curve keeps its own `steps` argument;
+ *  - it governs lfi_focus_map, whole frame and under a row window.  lfi_view_focus_maps keeps 32 candidates; lfi_focus_tiles keeps 32;
+ *    lfi_focus_tiles_steps takes its own argument; lfi_focus_curve keeps its own `steps` argument;
  *  - the estimate variants "factored" (default), "factored_direct" and "packed_p2" honour it (as does the row-window path); with "lds" or
  *    "plain" selected, lfi_focus_map returns LFI_EINVAL while the setting is not 32, and leaves the maps untouched;
  *  - cost: the factored estimate runs one pass per 32 candidates over the same padded planes (a change of steps alone pads nothing) and
@@ -351,6 +351,24 @@ int lfi_focus_curve(lfi_ctx *ctx, int x0, int y0, int x1, int y1, int steps, uin
  *    n_focus_ids == 0; out == NULL; a row window set; after lfi_release_inputs).  The context stays usable. */
 #define LFI_FOCUS_TILE_STEPS 32   /* the estimate's candidates, src/kernels.cu:245 */
 int lfi_focus_tiles(lfi_ctx *ctx, int tiles_x, int tiles_y, uint64_t *out_cost, lfi_focus_curve_result *out);
+/* Fine focus tiles: lfi_focus_tiles over `steps` candidates instead of 32.  lfi_focus_tiles(ctx, x, y, ...) is this call with steps = 32.
+ *  - out_cost[tile][i] ([tiles_y][tiles_x][steps], may be NULL) and out[tile] ([tiles_y][tiles_x]) are, BY DEFINITION, what
+ *    lfi_focus_curve(ctx, lfi_host_focus_tile_rect(...), steps, ...) returns for tile (tx, ty): the candidates
+ *    f_i = fmaf(range / (float)(steps - 1), (float)i, focus), the integer cost with the FLT_MIN terms dropped, the first strict minimum
+ *    (best_index, best_focus = f_best_index) and pixels = the tile's area;
+ *  - steps: a multiple of 32 from 32 to 256; anything else returns LFI_EINVAL with a message.  It is an argument of this call, as
+ *    lfi_focus_curve's is: lfi_set_focus_steps keeps governing lfi_focus_map only, and this call neither reads nor changes that setting;
+ *  - the factored estimate runs one pass per 32 candidates over the same padded planes, the tile-cost pass in the pick's place in each;
+ *    the per-workgroup partial sums stay those of 32 candidates, only the curves grow with steps.  The carry plane of a fine focus map is
+ *    neither read nor written.  A variant that is not a factored one (or a factored estimate that declines) takes lfi_focus_curve's kernels
+ *    tile by tile with all the steps — the same numbers, slower;
+ *  - everything else is lfi_focus_tiles': synchronous, one device-to-host copy of tiles * (steps * 8 + 16) bytes, neither maps nor views
+ *    written, the padded planes built or reused with lfi_focus_map's bookkeeping, the same refusals. */
+int lfi_focus_tiles_steps(lfi_ctx *ctx, int tiles_x, int tiles_y, int steps, uint64_t *out_cost, lfi_focus_curve_result *out);
+/* which way the last successful lfi_focus_tiles / lfi_focus_tiles_steps of this context took: the passes of the factored estimate it ran
+ * (steps / 32), or 0 where it computed the tiles with lfi_focus_curve's kernels tile by tile (0 before the first call, too) — lets a
+ * test or a measurement know that the numbers are the path's it means */
+int lfi_focus_tiles_passes(const lfi_ctx *ctx);
 /* One launch of Tensors::process / Standard::process (src/interpolator.cu:274-288) for views [v0, v1).
  * all_focus != 0 selects the <true> instantiations (per-pixel focus from the focus map). */
 int lfi_render(lfi_ctx *ctx, int method, int all_focus, int v0, int v1);

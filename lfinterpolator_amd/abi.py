@@ -35,7 +35,7 @@ ABI_SYMBOLS = [
     "lfi_set_variant", "lfi_list_variants", "lfi_download_coords", "lfi_download_prequant", "lfi_debug_mfma_f16",
     "lfi_grid_modified", "lfi_prepare", "lfi_memory_info", "lfi_last_kernel_name", "lfi_fill_synthetic_images", "lfi_set_output_layout", "lfi_view_layout", "lfi_fill_synthetic_scene", "lfi_upload_image_async", "lfi_upload_wait", "lfi_render_stream", "lfi_compare_view", "lfi_debug_mfma_f16_chain", "lfi_debug_pk_minmax3_f16", "lfi_std_band_info",
     "lfi_debug_poison", "lfi_set_view_offsets", "lfi_set_view_float_offsets", "lfi_view_focus_maps", "lfi_download_view_map",
-    "lfi_upload_view_map", "lfi_focus_curve", "lfi_focus_tiles", "lfi_download_quilt_scaled", "lfi_download_quilt_tiles_scaled",
+    "lfi_upload_view_map", "lfi_focus_curve", "lfi_focus_tiles", "lfi_focus_tiles_steps", "lfi_focus_tiles_passes", "lfi_download_quilt_scaled", "lfi_download_quilt_tiles_scaled",
     "lfi_keep_views", "lfi_compare_views", "lfi_set_focus_steps", "lfi_focus_steps",
 ]
 
@@ -135,6 +135,8 @@ def load_hip_library() -> C.CDLL:
         "lfi_focus_steps": (i, [vp, C.POINTER(i)]),
         "lfi_focus_curve": (i, [vp, i, i, i, i, i, vp, C.POINTER(FocusCurveResult)]),
         "lfi_focus_tiles": (i, [vp, i, i, vp, C.POINTER(FocusCurveResult)]),
+        "lfi_focus_tiles_steps": (i, [vp, i, i, i, vp, C.POINTER(FocusCurveResult)]),
+        "lfi_focus_tiles_passes": (i, [vp]),
         "lfi_render": (i, [vp, i, i, i, i]),
         "lfi_benchmark": (i, [vp, i, i, i, i, i, i, C.POINTER(BenchStats)]),
         "lfi_timer_start": (i, [vp]),
@@ -364,7 +366,7 @@ class Context:
 
     def set_focus_steps(self, steps: int) -> None:
         """Fine focus maps (lfi_set_focus_steps): focus_map chooses every pixel's focus from `steps` candidates of [focus, focus + range], a
-        multiple of 32 from 32 (the default: the reference's) to 256.  A context setting; view_focus_maps and focus_tiles keep 32."""
+        multiple of 32 from 32 (the default: the reference's) to 256.  A context setting; view_focus_maps keeps 32 and focus_tiles takes its own `steps`."""
         self._check(self._lib.lfi_set_focus_steps(self._h, int(steps)))
 
     def focus_steps(self) -> int:
@@ -382,20 +384,29 @@ class Context:
         self.focus_curve_pixels = int(res.pixels)   # the region's size as the library counted it
         return cost, int(res.best_index), np.float32(res.best_focus)
 
-    def focus_tiles(self, tiles_x: int, tiles_y: int):
-        """Focus tiles (lfi_focus_tiles): the focus curve of every tile of a tiles_x x tiles_y grid over the frame (the rectangles of
-        lfinterpolator_amd.focus_tile_rect), over the estimate's 32 candidates of the current parameters.  Returns (cost [tiles_y][tiles_x][32]
-        uint64, best_index [tiles_y][tiles_x] int32, best_focus [tiles_y][tiles_x] float32); every tile is what focus_curve gives for its rectangle."""
-        ny, nx = max(int(tiles_y), 0), max(int(tiles_x), 0)
-        cost = np.full((ny, nx, 32), 0xC3C3C3C3C3C3C3C3, dtype=np.uint64)   # a sentinel: every element is written
+    def focus_tiles(self, tiles_x: int, tiles_y: int, steps: int = 32):
+        """Focus tiles (lfi_focus_tiles; steps != 32: lfi_focus_tiles_steps): the focus curve of every tile of a tiles_x x tiles_y grid over the
+        frame (the rectangles of lfinterpolator_amd.focus_tile_rect), over `steps` candidates of the current parameters — a multiple of 32 from
+        32 (the estimate's) to 256, an argument of this call that set_focus_steps has nothing to do with.  Returns (cost
+        [tiles_y][tiles_x][steps] uint64, best_index [tiles_y][tiles_x] int32, best_focus [tiles_y][tiles_x] float32); every tile is what
+        focus_curve gives for its rectangle and `steps`."""
+        ny, nx, steps = max(int(tiles_y), 0), max(int(tiles_x), 0), int(steps)
+        cost = np.full((ny, nx, max(steps, 0)), 0xC3C3C3C3C3C3C3C3, dtype=np.uint64)   # a sentinel: every element is written
         res = (FocusCurveResult * max(nx * ny, 1))()
         for r in res:
             r.best_index, r.best_focus, r.pixels = -1, float("nan"), 0
-        self._check(self._lib.lfi_focus_tiles(self._h, tiles_x, tiles_y, _ptr(cost), res))
+        if steps == 32:
+            self._check(self._lib.lfi_focus_tiles(self._h, tiles_x, tiles_y, _ptr(cost), res))
+        else:
+            self._check(self._lib.lfi_focus_tiles_steps(self._h, tiles_x, tiles_y, steps, _ptr(cost), res))
         self.focus_tiles_pixels = np.array([r.pixels for r in res[:nx * ny]], dtype=np.uint64).reshape(ny, nx)
         best_index = np.array([r.best_index for r in res[:nx * ny]], dtype=np.int32).reshape(ny, nx)
         best_focus = np.array([r.best_focus for r in res[:nx * ny]], dtype=np.float32).reshape(ny, nx)
         return cost, best_index, best_focus
+
+    def focus_tiles_passes(self) -> int:
+        """The factored passes the last focus_tiles call ran (steps // 32), or 0 where it took focus_curve's kernels tile by tile."""
+        return int(self._lib.lfi_focus_tiles_passes(self._h))
 
     def view_focus_maps(self, ids_vk: np.ndarray) -> None:
         """Per-view focus maps (lfi_view_focus_maps): ids_vk is [views][n_ids] int32 — row v = the images view v's map samples

@@ -39,10 +39,12 @@ struct FocusCurveArgs
     uint64_t *partial;      // [steps][n_wg]
     uint64_t *cost;         // [steps], followed by the result (lfi_focus_curve_result's layout: i32, f32, u64)
     int32_t tiled;          // lfi_focus_tiles: focus_curve_sum / focus_curve_pick run once per tile of a gridDim tiles_x × tiles_y grid — tile t's
-                            // partials are partial[t][steps][n_wg], its curve and result lie at cost + t · (steps + 2), its pixels are its rectangle's
+                            // partials are partial[t][gridDim.x][n_wg], its curve and result lie at cost + t · (steps + 2), its pixels are its rectangle's
+    int32_t sum_at;         // focus_curve_sum: its gridDim.x candidates are sum_at … sum_at + gridDim.x − 1 of the curve's steps (0 and all of them
+                            // everywhere but lfi_focus_tiles_steps, whose partials hold one pass of 32 candidates at a time)
 };
 
-// focus_curve_sum's grid is steps × tiles_x × tiles_y, focus_curve_pick's tiles_x × tiles_y; lfi_focus_curve launches them with one tile (tile 0)
+// focus_curve_sum's grid is (candidates summed: steps, or one pass's 32) × tiles_x × tiles_y, focus_curve_pick's tiles_x × tiles_y; lfi_focus_curve launches them with one tile (tile 0)
 constexpr int FOCUS_CURVE_RESULT_WORDS = 2;
 static_assert(sizeof(lfi_focus_curve_result) == sizeof(uint64_t) * FOCUS_CURVE_RESULT_WORDS, "the result follows the curve in u64 words");
 
@@ -205,7 +207,7 @@ __global__ void __launch_bounds__(64, WPE) focus_curve_partial(const KernelArgs 
         q.partial[(size_t)i * q.n_wg + wg] = acc[i];
 }
 
-// cost[candidate] = Σ of the candidate's partials: thread t takes partials t, t + 256, …, then the 256 thread sums are added in a tree of
+// cost[sum_at + candidate] = Σ of the candidate's partials: thread t takes partials t, t + 256, …, then the 256 thread sums are added in a tree of
 // fixed shape — integer sums, so the order could not matter anyway
 __global__ void __launch_bounds__(256) focus_curve_sum(const FocusCurveArgs q)
 {
@@ -224,7 +226,7 @@ __global__ void __launch_bounds__(256) focus_curve_sum(const FocusCurveArgs q)
         __syncthreads();
     }
     if(threadIdx.x == 0)
-        q.cost[tile * (gridDim.x + FOCUS_CURVE_RESULT_WORDS) + blockIdx.x] = part[0];
+        q.cost[tile * (q.steps + FOCUS_CURVE_RESULT_WORDS) + q.sum_at + blockIdx.x] = part[0];
 }
 
 // the first candidate with the strictly smallest cost (MinDispersion::add, src/kernels.cu:225-231: strict <, candidates in ascending order)

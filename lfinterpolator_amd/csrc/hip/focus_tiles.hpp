@@ -15,6 +15,10 @@
 //                          leaves it in LDS; then eight threads per candidate add the 256 lane sums (u32: 256 lanes × 2 pixels × 64 rows ×
 //                          9 × 255 < 2^27) → partial[tile][candidate][workgroup] (u64).  No wave reduction inside the candidate loop, no atomics.
 //   focus_curve_sum / focus_curve_pick (focus_curve.hpp) with the tile in blockIdx.y finish: cost[tile][32] and the first strict minimum.
+// lfi_focus_tiles_steps (more than 32 candidates, a multiple of 32): the estimate runs one pass per 32 candidates (a.focus_i0 = 32g) and this
+// kernel, unchanged, once per pass on the pass's E, K and flag bits 0 … 31 — the pass's first index only enters upstream, through
+// focus_candidate; focus_curve_sum then writes the pass's slice cost[tile][32g … 32g + 31] (FocusCurveArgs::sum_at) and the partials are
+// overwritten by the next pass; focus_curve_pick runs once over all the steps.  The u32 bound below is per pass.
 // Every sum is an integer: exact in any order.
 #pragma once
 

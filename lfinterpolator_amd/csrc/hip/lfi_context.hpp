@@ -356,6 +356,7 @@ struct lfi_ctx
     int focus_steps = lfi::FOCUS_STEPS;
     DeviceBuffer curve_ws; // lfi_focus_curve: the curve and its result, then the per-workgroup partial sums (grows, kept)
     int ten_variant = 0, std_variant = 0, focus_variant = 0;
+    int tiles_passes = 0; // the factored passes lfi_focus_tiles_steps' last call ran; 0: it took focus_curve_partial tile by tile (lfi_focus_tiles_passes)
     mutable const char *last_kernel = ""; // the blend kernel the last render launched (lfi_last_kernel_name)
     mutable unsigned sweep_launches = 0;  // blend_p3 / blend_planar alternate their sweep direction from launch to launch
     float derived_build_ms = 0.0f;        // duration of the last planar_build (measured by lfi_prepare only)

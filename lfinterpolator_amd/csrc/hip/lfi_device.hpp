@@ -68,7 +68,7 @@ struct KernelArgs
     float focus, range;                     // inFocus, inRange
     uint32_t flags;
     // the focus sweep (focus_factored.hpp, focus_candidate): focus_steps candidates f_i = fma(range / focus_div, i, focus), focus_div = focus_steps − 1;
-    // this launch covers the candidates focus_i0 … focus_i0 + 31 of them (32, 31, 0 everywhere but under lfi_set_focus_steps)
+    // this launch covers the candidates focus_i0 … focus_i0 + 31 of them (32, 31, 0 everywhere but in lfi_focus_map under lfi_set_focus_steps and in lfi_focus_tiles_steps)
     int32_t focus_steps;
     float focus_div;
     int32_t focus_i0;

@@ -55,9 +55,10 @@ bool focus_pad_shift(const lfi_ctx *ctx, const lfi_float2 *offsets, int n, int *
 // applies (variant "factored_direct": the second implementation in the parity tests, and the A/B partner)
 // *e_32bit_out: a candidate's plane of E lies behind one buffer descriptor (focus_pick_sep)
 // The call covers the 32 candidates from a.focus_i0 of a sweep of a.focus_steps (one PASS; 0 of 32 everywhere but lfi_focus_map under
-// lfi_set_focus_steps).  A sweep's later passes (a.focus_i0 > 0) follow its first on the same streams: the padded planes and the geometry
+// lfi_set_focus_steps and lfi_focus_tiles_steps).  A sweep's later passes (a.focus_i0 > 0) follow its first on the same streams: the padded planes and the geometry
 // are the first pass's — nothing is padded, whatever the bookkeeping says — while the plan, E, Er, Ec and K are rewritten.  Ordering: the
-// side stream's writers of pass g + 1 wait for ev_fork, recorded on the compute stream behind pass g's line keys and pick (and the new plan);
+// side stream's writers of pass g + 1 wait for ev_fork, recorded on the compute stream behind pass g's line keys and pick — or whatever the caller enqueued in the pick's place: everything on
+// that stream so far — (and the new plan);
 // the compute stream's line keys and pick of pass g wait for ev_join, behind the side stream's passes — each pass's readers are done before
 // the next one's writers start, on either stream.
 int launch_focus_factored_keys(lfi_ctx *ctx, const KernelArgs &a, FocusJob &job, bool *done, bool direct_range, lfi::FocusWork *w_out, bool *e_32bit_out)
@@ -357,58 +358,79 @@ int launch_focus_curve(lfi_ctx *ctx, const KernelArgs &a, int x0, int y0, int x1
     return LFI_OK;
 }
 
-// The focus curves of the tiles_x × tiles_y tiles (lfi_focus_tiles; the caller has checked the arguments).  ctx->curve_ws holds, per tile, the
-// curve and its result back to back (FOCUS_TILE_HEAD bytes each, row-major over the tiles: what the host copies), then the partial sums.
-//   factored: behind launch_focus_factored_keys, focus_tile_costs in the pick's place, then focus_curve_sum / focus_curve_pick over all tiles —
-//             three launches whatever the grid;
-//   else (another estimate variant, or the factored estimate declined): lfi_focus_curve's three launches tile by tile — the same numbers.
-constexpr size_t FOCUS_TILE_HEAD = sizeof(uint64_t) * lfi::FOCUS_STEPS + sizeof(lfi_focus_curve_result);
+// The focus curves of the tiles_x × tiles_y tiles over `steps` candidates, a multiple of 32 up to 256 (lfi_focus_tiles: 32; lfi_focus_tiles_steps;
+// the caller has checked the arguments).  ctx->curve_ws holds, per tile, the curve and its result back to back (focus_tile_head(steps) bytes
+// each, row-major over the tiles: what the host copies), then the partial sums.
+//   factored: one pass per 32 candidates, as launch_focus_factored's — launch_focus_factored_keys with focus_i0 = 32g of focus_steps = steps,
+//             focus_tile_costs in the pick's place, then focus_curve_sum for the pass's slice cost[tile][32g … 32g + 31]; behind the last pass
+//             focus_curve_pick over all tiles and all steps.  2·passes + 1 launches behind the keys whatever the grid; at 32 steps the three
+//             launches lfi_focus_tiles has always made.  The partials stay [tiles][32][n_wg]: every pass overwrites them, behind the sum that
+//             read them (one stream).  Pass g + 1 rewrites E and K, which pass g's focus_tile_costs reads: launch_focus_factored_keys records
+//             ev_fork on the compute stream behind everything enqueued there so far — the tile costs and the sum, as the pick of a fine map —
+//             and the side stream's writers wait for it; the range pass follows the tile costs in the compute stream's own order.
+//   else (another estimate variant, or the factored estimate's first pass declined — then nothing has been enqueued): lfi_focus_curve's three
+//             launches tile by tile with all the steps — the same numbers.
+constexpr size_t focus_tile_head(const int steps) { return sizeof(uint64_t) * size_t(steps) + sizeof(lfi_focus_curve_result); }
 
-int launch_focus_tiles(lfi_ctx *ctx, const KernelArgs &a, int tiles_x, int tiles_y, const uint8_t **d_head)
+int launch_focus_tiles(lfi_ctx *ctx, const KernelArgs &a, int tiles_x, int tiles_y, int steps, const uint8_t **d_head)
 {
     const int W = ctx->width, H = ctx->height;
     const size_t tiles = size_t(tiles_x) * size_t(tiles_y);
-    const size_t head_bytes = (FOCUS_TILE_HEAD * tiles + 255) / 256 * 256;
+    const size_t tile_head = focus_tile_head(steps);
+    const size_t head_bytes = (tile_head * tiles + 255) / 256 * 256;
     hipStream_t st = ctx->stream;
     lfi::FocusCurveArgs q{};
-    q.steps = lfi::FOCUS_STEPS;
-    bool done = false;
+    q.steps = steps;
     if((ctx->focus_variant == 0 || ctx->focus_variant == 4) && W <= 65535 && H <= 65535)
     {
         FocusJob job;
         job.offsets = ctx->h_focus_offsets.data();
         job.ids = ctx->h_focus_ids.data();
         job.n_ids = ctx->n_focus_ids;
-        lfi::FocusWork w{};
-        bool e_32bit = false;
-        if(int rc = launch_focus_factored_keys(ctx, a, job, &done, ctx->focus_variant == 4, &w, &e_32bit))
-            return rc;
+        const int ppl = (ctx->radius[0] % 2 == 0 && W >= 2) ? 2 : 1; // as the pick: dword sample pairs need an even radius_x
+        const int tile_w = (W + tiles_x - 1) / tiles_x, tile_h = (H + tiles_y - 1) / tiles_y; // the widest, the tallest
+        lfi::FocusTileArgs t{};
+        t.tiles_x = tiles_x, t.tiles_y = tiles_y;
+        t.chunks = (tile_w + (ppl - 1) + 64 * ppl - 1) / (64 * ppl); // (+1: a tile's first column rounded down to even)
+        // one row per wave (the pick's shape) while that keeps the partials small: beyond 64 Ki workgroups a wave walks more rows
+        const size_t wg_1 = tiles * t.chunks * ((tile_h + 3) / 4);
+        t.rows_per_wave = int(std::min<size_t>(lfi::FOCUS_TILE_MAX_ROWS_PER_WAVE, std::max<size_t>(1, (wg_1 + 65535) / 65536)));
+        t.rows_per_wave = std::min(t.rows_per_wave, (tile_h + 3) / 4);
+        t.bands = (tile_h + 4 * t.rows_per_wave - 1) / (4 * t.rows_per_wave);
+        t.n_wg = uint32_t(t.chunks) * uint32_t(t.bands);
+        const size_t n_blocks = tiles * t.n_wg;
+        KernelArgs pass = a;
+        pass.focus_steps = steps;
+        pass.focus_div = float(steps - 1);
+        bool done = false;
+        for(pass.focus_i0 = 0; pass.focus_i0 < steps; pass.focus_i0 += lfi::FOCUS_STEPS)
+        {
+            lfi::FocusWork w{};
+            bool e_32bit = false;
+            if(int rc = launch_focus_factored_keys(ctx, pass, job, &done, ctx->focus_variant == 4, &w, &e_32bit))
+                return rc;
+            if(!done) // (declined: by the first pass — the later ones take its geometry)
+                break;
+            if(pass.focus_i0 == 0)
+            {
+                if(n_blocks > 0x7fffffffu)
+                    return fail(ctx, LFI_EINVAL, "lfi_focus_tiles: too many tiles for an image of this size");
+                LFI_HIP(ctx, ctx->curve_ws.reserve(head_bytes + sizeof(uint64_t) * lfi::FOCUS_STEPS * n_blocks));
+                q.cost = reinterpret_cast<uint64_t *>(ctx->curve_ws.get());
+                q.partial = t.partial = reinterpret_cast<uint64_t *>(ctx->curve_ws.get() + head_bytes);
+                q.n_wg = t.n_wg;
+                q.tiled = 1;
+            }
+            if(ppl == 2)
+                hipLaunchKernelGGL(lfi::focus_tile_costs<2>, dim3(uint32_t(n_blocks)), dim3(256), 0, st, pass, w, t);
+            else
+                hipLaunchKernelGGL(lfi::focus_tile_costs<1>, dim3(uint32_t(n_blocks)), dim3(256), 0, st, pass, w, t);
+            q.sum_at = pass.focus_i0;
+            hipLaunchKernelGGL(lfi::focus_curve_sum, dim3(lfi::FOCUS_STEPS, tiles_x, tiles_y), dim3(256), 0, st, q);
+        }
         if(done)
         {
-            const int ppl = (ctx->radius[0] % 2 == 0 && W >= 2) ? 2 : 1; // as the pick: dword sample pairs need an even radius_x
-            const int tile_w = (W + tiles_x - 1) / tiles_x, tile_h = (H + tiles_y - 1) / tiles_y; // the widest, the tallest
-            lfi::FocusTileArgs t{};
-            t.tiles_x = tiles_x, t.tiles_y = tiles_y;
-            t.chunks = (tile_w + (ppl - 1) + 64 * ppl - 1) / (64 * ppl); // (+1: a tile's first column rounded down to even)
-            // one row per wave (the pick's shape) while that keeps the partials small: beyond 64 Ki workgroups a wave walks more rows
-            const size_t wg_1 = tiles * t.chunks * ((tile_h + 3) / 4);
-            t.rows_per_wave = int(std::min<size_t>(lfi::FOCUS_TILE_MAX_ROWS_PER_WAVE, std::max<size_t>(1, (wg_1 + 65535) / 65536)));
-            t.rows_per_wave = std::min(t.rows_per_wave, (tile_h + 3) / 4);
-            t.bands = (tile_h + 4 * t.rows_per_wave - 1) / (4 * t.rows_per_wave);
-            t.n_wg = uint32_t(t.chunks) * uint32_t(t.bands);
-            const size_t n_blocks = tiles * t.n_wg;
-            if(n_blocks > 0x7fffffffu)
-                return fail(ctx, LFI_EINVAL, "lfi_focus_tiles: too many tiles for an image of this size");
-            LFI_HIP(ctx, ctx->curve_ws.reserve(head_bytes + sizeof(uint64_t) * lfi::FOCUS_STEPS * n_blocks));
-            q.cost = reinterpret_cast<uint64_t *>(ctx->curve_ws.get());
-            q.partial = t.partial = reinterpret_cast<uint64_t *>(ctx->curve_ws.get() + head_bytes);
-            q.n_wg = t.n_wg;
-            q.tiled = 1;
-            if(ppl == 2)
-                hipLaunchKernelGGL(lfi::focus_tile_costs<2>, dim3(uint32_t(n_blocks)), dim3(256), 0, st, a, w, t);
-            else
-                hipLaunchKernelGGL(lfi::focus_tile_costs<1>, dim3(uint32_t(n_blocks)), dim3(256), 0, st, a, w, t);
-            hipLaunchKernelGGL(lfi::focus_curve_sum, dim3(lfi::FOCUS_STEPS, tiles_x, tiles_y), dim3(256), 0, st, q);
+            ctx->tiles_passes = steps / lfi::FOCUS_STEPS;
             hipLaunchKernelGGL(lfi::focus_curve_pick, dim3(tiles_x, tiles_y), dim3(256), 0, st, a, q);
             LFI_HIP(ctx, hipGetLastError());
             *d_head = ctx->curve_ws.get();
@@ -417,10 +439,12 @@ int launch_focus_tiles(lfi_ctx *ctx, const KernelArgs &a, int tiles_x, int tiles
     }
     // tile by tile: focus_curve_partial's shape as in launch_focus_curve, the partials' room shared (the launches follow each other on one stream)
     constexpr int PPL = 2;
+    ctx->tiles_passes = 0;
+    q.tiled = 0, q.sum_at = 0; // one tile per launch, every candidate of it
     const int tile_w = (W + tiles_x - 1) / tiles_x, tile_h = (H + tiles_y - 1) / tiles_y;
     const uint32_t blocks_x = uint32_t((tile_w + 64 * PPL - 1) / (64 * PPL));
     const uint32_t blocks_y_max = std::min(uint32_t(tile_h), std::max(1u, 8192u / blocks_x));
-    LFI_HIP(ctx, ctx->curve_ws.reserve(head_bytes + sizeof(uint64_t) * lfi::FOCUS_STEPS * size_t(blocks_x) * blocks_y_max));
+    LFI_HIP(ctx, ctx->curve_ws.reserve(head_bytes + sizeof(uint64_t) * size_t(steps) * size_t(blocks_x) * blocks_y_max));
     q.partial = reinterpret_cast<uint64_t *>(ctx->curve_ws.get() + head_bytes);
     for(int ty = 0; ty < tiles_y; ty++)
         for(int tx = 0; tx < tiles_x; tx++)
@@ -434,7 +458,7 @@ int launch_focus_tiles(lfi_ctx *ctx, const KernelArgs &a, int tiles_x, int tiles
             q.steps_per_wg = (q.steps + int(want_z) - 1) / int(want_z);
             const uint32_t bz = uint32_t((q.steps + q.steps_per_wg - 1) / q.steps_per_wg);
             q.pixels = uint64_t(q.x1 - q.x0) * uint64_t(q.y1 - q.y0);
-            q.cost = reinterpret_cast<uint64_t *>(ctx->curve_ws.get() + FOCUS_TILE_HEAD * (size_t(ty) * tiles_x + tx));
+            q.cost = reinterpret_cast<uint64_t *>(ctx->curve_ws.get() + tile_head * (size_t(ty) * tiles_x + tx));
             hipLaunchKernelGGL((lfi::focus_curve_partial<PPL, 4>), dim3(bx, by, bz), dim3(64), 0, st, a, q);
             hipLaunchKernelGGL(lfi::focus_curve_sum, dim3(q.steps), dim3(256), 0, st, q);
             hipLaunchKernelGGL(lfi::focus_curve_pick, dim3(1), dim3(256), 0, st, a, q);

@@ -933,6 +933,17 @@ int lfi_focus_curve(lfi_ctx *ctx, int x0, int y0, int x1, int y1, int steps, uin
 
 int lfi_focus_tiles(lfi_ctx *ctx, int tiles_x, int tiles_y, uint64_t *out_cost, lfi_focus_curve_result *out)
 {
+    return lfi_focus_tiles_steps(ctx, tiles_x, tiles_y, LFI_FOCUS_TILE_STEPS, out_cost, out);
+}
+
+int lfi_focus_tiles_passes(const lfi_ctx *ctx)
+{
+    return ctx ? ctx->tiles_passes : 0;
+}
+
+// (steps is this call's argument: ctx->focus_steps, lfi_set_focus_steps' setting of lfi_focus_map, is neither read nor written)
+int lfi_focus_tiles_steps(lfi_ctx *ctx, int tiles_x, int tiles_y, int steps, uint64_t *out_cost, lfi_focus_curve_result *out)
+{
     if(!ctx)
         return LFI_EINVAL;
     if(ctx->inputs_released)
@@ -949,25 +960,27 @@ int lfi_focus_tiles(lfi_ctx *ctx, int tiles_x, int tiles_y, uint64_t *out_cost, 
         return fail(ctx, LFI_EINVAL, "focus range must be > 0 for the focus tiles: [focus, focus + range] is the search interval");
     if(tiles_x < 1 || tiles_y < 1 || tiles_x > std::min(ctx->width, 256) || tiles_y > std::min(ctx->height, 256))
         return fail(ctx, LFI_EINVAL, "lfi_focus_tiles: the grid must have 1 to min(width, 256) columns and 1 to min(height, 256) rows of tiles");
+    if(steps < lfi::FOCUS_STEPS || steps > lfi::FOCUS_STEPS * lfi::FOCUS_MAX_PASSES || steps % lfi::FOCUS_STEPS != 0)
+        return fail(ctx, LFI_EINVAL, "lfi_focus_tiles_steps: " + std::to_string(steps) + " candidates - the focus tiles take a multiple of 32 from 32 to 256");
     if(int rc = bind(ctx))
         return rc;
     if(int rc = join_uploads(ctx))
         return rc;
     const KernelArgs a = make_args(ctx, 0, ctx->views_n, LFI_METHOD_STD);
     const uint8_t *d_head = nullptr;
-    if(int rc = launch_focus_tiles(ctx, a, tiles_x, tiles_y, &d_head))
+    if(int rc = launch_focus_tiles(ctx, a, tiles_x, tiles_y, steps, &d_head))
         return rc;
-    // per tile the curve and the result lie back to back: one copy of tiles · (32 · 8 + 16) bytes
+    // per tile the curve and the result lie back to back: one copy of tiles · (steps · 8 + 16) bytes
     const size_t tiles = size_t(tiles_x) * size_t(tiles_y);
-    constexpr size_t WORDS = FOCUS_TILE_HEAD / sizeof(uint64_t);
-    std::vector<uint64_t> head(tiles * WORDS);
-    LFI_HIP(ctx, hipMemcpyAsync(head.data(), d_head, FOCUS_TILE_HEAD * tiles, hipMemcpyDeviceToHost, ctx->stream));
+    const size_t words = focus_tile_head(steps) / sizeof(uint64_t);
+    std::vector<uint64_t> head(tiles * words);
+    LFI_HIP(ctx, hipMemcpyAsync(head.data(), d_head, sizeof(uint64_t) * words * tiles, hipMemcpyDeviceToHost, ctx->stream));
     LFI_HIP(ctx, hipStreamSynchronize(ctx->stream));
     for(size_t t = 0; t < tiles; t++)
     {
         if(out_cost)
-            std::memcpy(out_cost + t * LFI_FOCUS_TILE_STEPS, head.data() + t * WORDS, sizeof(uint64_t) * LFI_FOCUS_TILE_STEPS);
-        std::memcpy(out + t, head.data() + t * WORDS + LFI_FOCUS_TILE_STEPS, sizeof(lfi_focus_curve_result));
+            std::memcpy(out_cost + t * steps, head.data() + t * words, sizeof(uint64_t) * steps);
+        std::memcpy(out + t, head.data() + t * words + steps, sizeof(lfi_focus_curve_result));
     }
     return LFI_OK;
 }

@@ -97,21 +97,32 @@ int lfi_host_area_span(int src, int dst, int o, int32_t out[4])
 }
 
 // the interval an all-focus render should search, from the tiles' best candidates of a search over [focus, focus + range] (--auto-range):
-// the candidates kept are lo_hi = {max(min index − 1, 0), min(max index + 1, 31)}, *out_focus = candidate lo, *out_range = candidate hi −
-// candidate lo in float; returns 0, or -1 for no tiles, an index outside [0, 31] or range <= 0
-int lfi_host_focus_auto_range(const int32_t *best_index, int tiles, float focus, float range, float *out_focus, float *out_range, int32_t lo_hi[2])
+// the tiles chose from `steps` candidates (lfi_focus_tiles_steps: a multiple of 32 from 32 to 256), those of lfi_host_focus_candidates(focus,
+// range, steps); the candidates kept are lo_hi = {max(min index − 1, 0), min(max index + 1, steps − 1)}, *out_focus = candidate lo,
+// *out_range = candidate hi − candidate lo in float; returns 0, or -1 for no tiles, steps the tiles do not take, an index outside
+// [0, steps − 1] or range <= 0
+int lfi_host_focus_auto_range_steps(const int32_t *best_index, int tiles, int steps, float focus, float range, float *out_focus, float *out_range,
+                                    int32_t lo_hi[2])
 {
     if(!best_index || tiles < 1 || !out_focus || !out_range || !lo_hi || !(range > 0.0f))
         return -1;
+    if(steps < LFI_FOCUS_TILE_STEPS || steps > 256 || steps % LFI_FOCUS_TILE_STEPS != 0)
+        return -1;
     for(int t = 0; t < tiles; t++)
-        if(best_index[t] < 0 || best_index[t] >= LFI_FOCUS_TILE_STEPS)
+        if(best_index[t] < 0 || best_index[t] >= steps)
             return -1;
-    const lfi::FocusAutoRange r = lfi::focusAutoRange(best_index, static_cast<size_t>(tiles), focus, range);
+    const lfi::FocusAutoRange r = lfi::focusAutoRange(best_index, static_cast<size_t>(tiles), focus, range, steps);
     *out_focus = r.focus;
     *out_range = r.range;
     lo_hi[0] = r.lo;
     lo_hi[1] = r.hi;
     return 0;
+}
+
+// (the 32 candidates of lfi_focus_tiles)
+int lfi_host_focus_auto_range(const int32_t *best_index, int tiles, float focus, float range, float *out_focus, float *out_range, int32_t lo_hi[2])
+{
+    return lfi_host_focus_auto_range_steps(best_index, tiles, LFI_FOCUS_TILE_STEPS, focus, range, out_focus, out_range, lo_hi);
 }
 
 // per-view focus: out_vn[views][N] = the focused offsets of Parameterizer::offsets at focus_v[v] (the rows lfi_set_view_offsets takes)

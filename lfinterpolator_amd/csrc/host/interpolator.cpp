@@ -142,7 +142,10 @@ void Interpolator::interpolate(std::string outputPath, std::string trajectory, f
         const lfi_params abi = search.abi();
         check(lfi_set_params(context, &abi));
         std::vector<lfi_focus_curve_result> found(static_cast<size_t>(std::max(grid.x, 0)) * std::max(grid.y, 0));
-        check(lfi_focus_tiles(context, grid.x, grid.y, nullptr, found.data()));
+        if(tileSteps == LFI_FOCUS_TILE_STEPS)
+            check(lfi_focus_tiles(context, grid.x, grid.y, nullptr, found.data()));
+        else
+            check(lfi_focus_tiles_steps(context, grid.x, grid.y, tileSteps, nullptr, found.data()));
         return found;
     };
     if(focusTiles.x != 0 || focusTiles.y != 0)
@@ -165,7 +168,7 @@ void Interpolator::interpolate(std::string outputPath, std::string trajectory, f
         std::vector<int32_t> best(found.size());
         for(size_t t = 0; t < found.size(); t++)
             best[t] = found[t].best_index;
-        const lfi::FocusAutoRange narrowed = lfi::focusAutoRange(best.data(), best.size(), inFocus, inRange);
+        const lfi::FocusAutoRange narrowed = lfi::focusAutoRange(best.data(), best.size(), inFocus, inRange, tileSteps);
         // nine significant digits: the printed values read back as floats (-f, -r) are the same floats
         std::cout << "auto-range: focus " << std::setprecision(9) << narrowed.focus << " range " << narrowed.range << std::setprecision(6)
                   << " (candidates " << narrowed.lo << ".." << narrowed.hi << ")" << std::endl;
@@ -186,7 +189,12 @@ void Interpolator::interpolate(std::string outputPath, std::string trajectory, f
         const lfi_params abi = search.abi();
         check(lfi_set_params(context, &abi));
         lfi_focus_curve_result found{};
-        check(lfi_focus_curve(context, r[0], r[1], r[2], r[3], autofocusSteps, nullptr, &found));
+        // the whole frame over a number of candidates the tiles take, asked for explicitly: the frame as one tile (the same result by definition)
+        const bool wholeFrame = autofocusRegion == std::array<int, 4>{0, 0, 0, 0};
+        if(wholeFrame && autofocusStepsGiven && autofocusSteps >= 32 && autofocusSteps <= 256 && autofocusSteps % 32 == 0)
+            check(lfi_focus_tiles_steps(context, 1, 1, autofocusSteps, nullptr, &found));
+        else
+            check(lfi_focus_curve(context, r[0], r[1], r[2], r[3], autofocusSteps, nullptr, &found));
         // nine significant digits: the printed value read back as a float (-f) is the same float
         std::cout << "autofocus: focus " << std::setprecision(9) << found.best_focus << std::setprecision(6) << " (candidate " << found.best_index << " of "
                   << autofocusSteps << ", " << found.pixels << " px)" << std::endl;

@@ -45,8 +45,16 @@ class Interpolator
         void setViewMaps(bool on) { viewMaps = on; }
         // autofocus: interpolate()'s focus and range give the SEARCH interval [focus, focus + range] (range > 0); the focus curve of the
         // region {x0, y0, x1, y1} (all zero: the whole frame) is taken over `steps` candidates on the first GPU (lfi_focus_curve) and the
-        // views are rendered at its minimum as a fixed-focus render.  Not with setFocusEnd, setViewCentred, setViewMaps
-        void setAutofocus(std::array<int, 4> region, int steps) { autofocus = true; autofocusRegion = region; autofocusSteps = steps; }
+        // views are rendered at its minimum as a fixed-focus render.  Not with setFocusEnd, setViewCentred, setViewMaps.
+        // stepsGiven (the caller chose `steps`, it is not a default): the whole frame over a multiple of 32 candidates up to 256 is taken as
+        // the one tile of lfi_focus_tiles_steps(1, 1, steps) — by definition the same focus and index, from the factored estimate
+        void setAutofocus(std::array<int, 4> region, int steps, bool stepsGiven = false)
+        {
+            autofocus = true;
+            autofocusRegion = region;
+            autofocusSteps = steps;
+            autofocusStepsGiven = stepsGiven;
+        }
         float lastAutofocus() const { return focus; }
         // focus tiles: before anything is rendered, the focus curve's minimum of every tile of a columns × rows grid over the frame
         // (lfi_focus_tiles on the first GPU, over [focus, focus + range], range > 0) is printed, one line per tile
@@ -54,8 +62,10 @@ class Interpolator
         // auto range, for all-focus renders: the tiles' minima over [focus, focus + range] give the interval the map is then estimated over
         // and the views rendered with (lfi::focusAutoRange) instead of the interval given.  Not with setAutofocus
         void setAutoRange(lfi::IVec2 grid) { autoRange = grid; }
+        // the candidates the focus tiles of setFocusTiles / setAutoRange choose from: a multiple of 32 up to 256 (lfi_focus_tiles_steps)
+        void setTileSteps(int steps) { tileSteps = steps; }
         // the candidates the focus map (one map at the trajectory's centre) chooses from: a multiple of 32 up to 256 (lfi_set_focus_steps);
-        // per-view maps, the focus tiles and autofocus keep their own numbers
+        // per-view maps, the focus tiles (setTileSteps) and autofocus keep their own numbers
         void setMapSteps(int steps) { mapSteps = steps; }
         // after the render, compare every view with NN.png of this directory (the names storeResults writes; the reference's
         // scripts/compareDirs.sh) in one lfi_compare_views call and print "compare NN psnr … ssim … maxdiff … differing …" per view, then
@@ -85,6 +95,8 @@ class Interpolator
         bool autofocus{false};
         std::array<int, 4> autofocusRegion{0, 0, 0, 0}; // x0, y0, x1, y1
         int autofocusSteps{32};
+        bool autofocusStepsGiven{false};
+        int tileSteps{32};
         lfi::IVec2 focusTiles{0, 0}; // 0: off
         lfi::IVec2 autoRange{0, 0};  // 0: off
         int mapSteps{32};

@@ -1,7 +1,7 @@
 // main.cpp — command line of the interpolator; flags, defaults, messages and exit codes as in reference src/main.cpp:4-57
 // (-i -t -o -f -r -m -s -a -h), plus -n (views), -b (benchmark runs), -d (device), -F (focus at the last view), -c (shifts about each
 // view's own camera), --autofocus (the focus found from a region's focus curve), --focus-tiles / --auto-range (the focus of every tile of a
-// grid; the search interval of an all-focus render found from it), --map-steps (more than 32 candidates for the focus map), --compare / --compare-methods (PSNR / SSIM of all views against a
+// grid; the search interval of an all-focus render found from it), --map-steps / --tile-steps (more than 32 candidates for the focus map / the focus tiles), --compare / --compare-methods (PSNR / SSIM of all views against a
 // directory of images or against the other method's render) and --synthetic for runs without a dataset.
 #include <array>
 #include <iostream>
@@ -39,10 +39,11 @@ int main(int argc, char **argv)
                           "-c - shift the images about each view's own camera position instead of the trajectory's centre (the default, as the reference does); with -r and with -f/-F\n"
                           "--view-maps - with -c and -r: estimate every view's focus map at its own camera (the reference's focusMapCompare.sh second run, per view) instead of one map at the trajectory's centre; writes map0_NN.png / map1_NN.png per view\n"
                           "--autofocus [x0,y0,x1,y1] - find the focus of the region [x0,x1) x [y0,y1) (no value: the whole frame) and render all views at it (a fixed-focus render): -f and -r give the search interval [f, f+r] (-r required), the focus with the smallest colour dispersion over the region wins; prints \"autofocus: focus <value> ...\"; not with -F, -c, --view-maps\n"
-                          "--autofocus-steps - number of focus candidates searched, 2 to 256 (default=32)\n"
+                          "--autofocus-steps - number of focus candidates searched, 2 to 256 (default=32); given as a multiple of 32 without a region, the whole frame is searched as one focus tile (the same result, faster)\n"
                           "--focus-tiles CxR - print the focus of every tile of a grid of C columns x R rows over the frame, searched in [f, f+r] (-r required): \"focus tiles: C x R\", then \"tile <tx> <ty> index <i> focus <value>\" per tile, row by row; the render follows as usual\n"
+                          "--tile-steps N - with --focus-tiles or --auto-range: the tiles choose from N candidates of [f, f+r] instead of 32, N a multiple of 32 up to 256 (indices in [0, N); about N/32 times the tiles' time); composes with --map-steps\n"
                           "--auto-range [CxR] - for all-focus renders (-r): find the interval the scene occupies from the focus tiles of a C x R grid (default 16x9) over [f, f+r] - from one candidate below the nearest tile's focus to one above the farthest's - and estimate the map and render with it in place of -f, -r; prints \"auto-range: focus <f'> range <r'> (candidates <lo>..<hi>)\"; not with --autofocus\n"
-                          "--map-steps N - for all-focus renders (-r): choose every pixel's focus from N candidates of [f, f+r] instead of 32, N a multiple of 32 up to 256 (a finer focus map, about N/32 times the estimate's time); with --auto-range the tiles find the interval at 32 candidates and the map is estimated with N inside it; not with --view-maps, --autofocus\n"
+                          "--map-steps N - for all-focus renders (-r): choose every pixel's focus from N candidates of [f, f+r] instead of 32, N a multiple of 32 up to 256 (a finer focus map, about N/32 times the estimate's time); with --auto-range the tiles find the interval at 32 candidates (--tile-steps: at more) and the map is estimated with N inside it; not with --view-maps, --autofocus\n"
                           "Additional arguments:\n"
                           "-n - number of views rendered along the trajectory (default=64)\n"
                           "-b - number of timed kernel launches (default=100)\n"
@@ -95,6 +96,21 @@ int main(int argc, char **argv)
     {
         std::cerr << "--focus-tiles and --auto-range search the interval [f, f+r]: they need -r with a value greater than zero." << std::endl;
         return EXIT_FAILURE;
+    }
+
+    if(args["--tile-steps"])
+    {
+        const int steps = static_cast<int>(args["--tile-steps"]);
+        if(!args["--focus-tiles"] && !args["--auto-range"])
+        {
+            std::cerr << "--tile-steps (the candidates of the focus tiles) needs --focus-tiles or --auto-range." << std::endl;
+            return EXIT_FAILURE;
+        }
+        if(steps < 32 || steps > 256 || steps % 32 != 0)
+        {
+            std::cerr << "--tile-steps expects a multiple of 32 from 32 to 256." << std::endl;
+            return EXIT_FAILURE;
+        }
     }
 
     if(args["--auto-range"] && args["--autofocus"])
@@ -212,7 +228,7 @@ int main(int argc, char **argv)
                 if(count != 4 || region[0] >= region[2] || region[1] >= region[3])
                     throw std::runtime_error("--autofocus expects x0,y0,x1,y1 with x0 < x1 and y0 < y1");
             }
-            interpolator->setAutofocus(region, args["--autofocus-steps"] ? static_cast<int>(args["--autofocus-steps"]) : 32);
+            interpolator->setAutofocus(region, args["--autofocus-steps"] ? static_cast<int>(args["--autofocus-steps"]) : 32, static_cast<bool>(args["--autofocus-steps"]));
         }
         // a grid of tiles "CxR" (columns x rows)
         const auto tileGrid = [](const std::string &text, const char *flag, const char *meaning = "CxR, columns x rows of tiles, both at least 1") {
@@ -233,6 +249,8 @@ int main(int argc, char **argv)
         };
         if(args["--map-steps"])
             interpolator->setMapSteps(static_cast<int>(args["--map-steps"]));
+        if(args["--tile-steps"])
+            interpolator->setTileSteps(static_cast<int>(args["--tile-steps"]));
         if(args["--focus-tiles"])
             interpolator->setFocusTiles(tileGrid(static_cast<std::string>(args["--focus-tiles"]), "--focus-tiles"));
         if(args["--auto-range"])

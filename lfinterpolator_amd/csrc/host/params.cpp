@@ -269,9 +269,9 @@ std::array<int, 4> focusTileRect(int width, int height, int tilesX, int tilesY, 
     return {edge(tx, width, tilesX), edge(ty, height, tilesY), edge(tx + 1, width, tilesX), edge(ty + 1, height, tilesY)};
 }
 
-FocusAutoRange focusAutoRange(const int32_t *bestIndex, size_t tiles, float focus, float range)
+FocusAutoRange focusAutoRange(const int32_t *bestIndex, size_t tiles, float focus, float range, int steps)
 {
-    constexpr int STEPS = LFI_FOCUS_TILE_STEPS;
+    const int STEPS = steps;
     int lo = STEPS - 1, hi = 0;
     for(size_t t = 0; t < tiles; t++)
     {

@@ -78,14 +78,15 @@ std::vector<float> focusCandidates(float focus, float range, int steps);
 // Tile (tx, ty) of lfi_focus_tiles' tilesX × tilesY grid over a width × height frame: {x0, y0, x1, y1} with x0 = tx·width / tilesX,
 // x1 = (tx + 1)·width / tilesX (integer divisions of 64-bit products), likewise in y — the tiles cover the frame exactly once
 std::array<int, 4> focusTileRect(int width, int height, int tilesX, int tilesY, int tx, int ty);
-// The search interval an all-focus render needs, from the tiles' best candidates of a search over [focus, focus + range] (32 candidates):
-// lo / hi = the smallest / largest index, widened by one candidate on either side inside [0, 31]
+// The search interval an all-focus render needs, from the tiles' best candidates of a search over [focus, focus + range] with `steps`
+// candidates (lfi_focus_tiles: 32; lfi_focus_tiles_steps): lo / hi = the smallest / largest index, widened by one candidate on either side
+// inside [0, steps − 1]; the values are focusCandidates(focus, range, steps)'
 struct FocusAutoRange
 {
-    int lo, hi;   // the candidates kept: max(lo − 1, 0), min(hi + 1, 31)
+    int lo, hi;   // the candidates kept: max(lo − 1, 0), min(hi + 1, steps − 1)
     float focus;  // candidate lo
     float range;  // candidate hi − candidate lo in float: always > 0
 };
-FocusAutoRange focusAutoRange(const int32_t *bestIndex, size_t tiles, float focus, float range);
+FocusAutoRange focusAutoRange(const int32_t *bestIndex, size_t tiles, float focus, float range, int steps = LFI_FOCUS_TILE_STEPS);
 
 } // namespace lfi

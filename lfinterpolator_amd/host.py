@@ -31,6 +31,9 @@ def load_host_library() -> C.CDLL:
         lib.lfi_host_focus_tile_rect.argtypes = [C.c_int] * 6 + [C.c_void_p]
         lib.lfi_host_focus_auto_range.restype = C.c_int
         lib.lfi_host_focus_auto_range.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p]
+        lib.lfi_host_focus_auto_range_steps.restype = C.c_int
+        lib.lfi_host_focus_auto_range_steps.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                                        C.c_void_p]
         lib.lfi_host_area_span.restype = C.c_int
         lib.lfi_host_area_span.argtypes = [C.c_int] * 3 + [C.c_void_p]
         lib.lfi_host_build_view_offsets.restype = C.c_int
@@ -117,15 +120,21 @@ def focus_tile_rect(width: int, height: int, tiles_x: int, tiles_y: int, tx: int
     return tuple(int(v) for v in rect)
 
 
-def focus_auto_range(best_index, focus: float, range: float):
-    """The interval an all-focus render should search, from the tiles' best candidates of a search over [focus, focus + range]: returns
-    (focus', range' as np.float32, lo', hi') with lo' = max(min − 1, 0), hi' = min(max + 1, 31), focus' = candidate lo',
-    range' = candidate hi' − candidate lo' in float32."""
+def focus_auto_range(best_index, focus: float, range: float, steps: int = 32):
+    """The interval an all-focus render should search, from the tiles' best candidates of a search over [focus, focus + range] with `steps`
+    candidates (Context.focus_tiles' steps: a multiple of 32 from 32 to 256): returns (focus', range' as np.float32, lo', hi') with
+    lo' = max(min − 1, 0), hi' = min(max + 1, steps − 1), focus' = candidate lo', range' = candidate hi' − candidate lo' in float32,
+    the candidates those of focus_candidates(focus, range, steps)."""
     idx = np.ascontiguousarray(best_index, dtype=np.int32).reshape(-1)
     f, r = C.c_float(), C.c_float()
     lo_hi = np.zeros(2, dtype=np.int32)
-    if load_host_library().lfi_host_focus_auto_range(idx.ctypes.data, len(idx), focus, range, C.byref(f), C.byref(r), lo_hi.ctypes.data) != 0:
-        raise ValueError("needs at least one tile, indices in [0, 31] and range > 0")
+    lib = load_host_library()
+    if steps == 32:
+        rc = lib.lfi_host_focus_auto_range(idx.ctypes.data, len(idx), focus, range, C.byref(f), C.byref(r), lo_hi.ctypes.data)
+    else:
+        rc = lib.lfi_host_focus_auto_range_steps(idx.ctypes.data, len(idx), steps, focus, range, C.byref(f), C.byref(r), lo_hi.ctypes.data)
+    if rc != 0:
+        raise ValueError(f"needs at least one tile, steps a multiple of 32 from 32 to 256, indices in [0, {steps - 1}] and range > 0")
     return np.float32(f.value), np.float32(r.value), int(lo_hi[0]), int(lo_hi[1])
 
 
