@@ -9,7 +9,8 @@
 // over a region and are dropped (S_i is the plain integer sum).
 //
 // Three kernels, no atomics, every sum an integer (exact, order-independent):
-//   focus_curve_partial   region × candidates.  The sampling arithmetic is focus_estimate_packed's, line for line: a lane owns PPL consecutive
+//   focus_curve_partial   region × candidates.  Sampled as focus_estimate_packed samples (focus_map.hpp; the candidate's value and a tap's dispersion by
+//                         its helpers focus_sweep_value and focus_tap_range, the tap loads written out again here): a lane owns PPL consecutive
 //                         pixels of a row, a tap is one wide load where the per-lane exactness check allows it (else per-pixel clamped
 //                         fetches), min / max over the images on v_pk_min_u16 / v_pk_max_u16.  Per candidate the lane's S of the pixels
 //                         INSIDE the region (the ragged right edge is masked out of the sum, not out of the sampling) is reduced over the
@@ -48,23 +49,29 @@ struct FocusCurveArgs
 constexpr int FOCUS_CURVE_RESULT_WORDS = 2;
 static_assert(sizeof(lfi_focus_curve_result) == sizeof(uint64_t) * FOCUS_CURVE_RESULT_WORDS, "the result follows the curve in u64 words");
 
-__device__ __forceinline__ float focus_curve_candidate(const KernelArgs &a, const int steps, const int i)
+// v + the values of the lanes whose number differs from this one's in the lowest STEPS bits (STEPS ≤ 5): a butterfly of ds_swizzle steps with
+// an immediate lane pattern (bit-mask mode: lane' = (lane & 0x1f) ^ m) — no address register, unlike ds_bpermute
+template <int STEPS>
+__device__ __forceinline__ uint32_t swizzle_sum_u32(uint32_t v)
 {
-    const float step = __fdiv_rn(a.range, static_cast<float>(steps - 1));
-    return __builtin_fmaf(step, static_cast<float>(i), a.focus);
+    static_assert(STEPS >= 1 && STEPS <= 5, "ds_swizzle's bit-mask mode reaches 32 lanes");
+    v += (uint32_t)__builtin_amdgcn_ds_swizzle((int)v, (1 << 10) | 0x1f);
+    if constexpr(STEPS > 1)
+        v += (uint32_t)__builtin_amdgcn_ds_swizzle((int)v, (2 << 10) | 0x1f);
+    if constexpr(STEPS > 2)
+        v += (uint32_t)__builtin_amdgcn_ds_swizzle((int)v, (4 << 10) | 0x1f);
+    if constexpr(STEPS > 3)
+        v += (uint32_t)__builtin_amdgcn_ds_swizzle((int)v, (8 << 10) | 0x1f);
+    if constexpr(STEPS > 4)
+        v += (uint32_t)__builtin_amdgcn_ds_swizzle((int)v, (16 << 10) | 0x1f);
+    return v;
 }
 
-// the sum of v over the wave's 64 lanes, wave-uniform: five butterfly steps inside each half (ds_swizzle with an immediate lane pattern — no
-// address register, unlike ds_bpermute, and this kernel lives at the edge of five waves per SIMD), then the two halves' sums by v_readlane
+// the sum of v over the wave's 64 lanes, wave-uniform: each half's sum by the butterfly (focus_curve_partial lives at the edge of five waves
+// per SIMD), then the two halves' sums by v_readlane
 __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v)
 {
-#define LFI_SWIZZLE_XOR(m) (((m) << 10) | 0x1f) // bit-mask mode: lane' = ((lane & 0x1f) | 0) ^ m
-    v += (uint32_t)__builtin_amdgcn_ds_swizzle((int)v, LFI_SWIZZLE_XOR(1));
-    v += (uint32_t)__builtin_amdgcn_ds_swizzle((int)v, LFI_SWIZZLE_XOR(2));
-    v += (uint32_t)__builtin_amdgcn_ds_swizzle((int)v, LFI_SWIZZLE_XOR(4));
-    v += (uint32_t)__builtin_amdgcn_ds_swizzle((int)v, LFI_SWIZZLE_XOR(8));
-    v += (uint32_t)__builtin_amdgcn_ds_swizzle((int)v, LFI_SWIZZLE_XOR(16));
-#undef LFI_SWIZZLE_XOR
+    v = swizzle_sum_u32<5>(v);
     return (uint32_t)__builtin_amdgcn_readlane((int)v, 0) + (uint32_t)__builtin_amdgcn_readlane((int)v, 32);
 }
 
@@ -78,7 +85,7 @@ __global__ void __launch_bounds__(64, WPE) focus_curve_partial(const KernelArgs 
     const int x0 = q.x0 + (blockIdx.x * 64 + lane) * PPL; // first of this lane's pixels: the region's left edge needs no alignment
     const bool lane_active = x0 < q.x1;
     const int steps = q.steps;
-    const float step = __fdiv_rn(a.range, static_cast<float>(steps - 1));
+    const float div = static_cast<float>(steps - 1);
     const int rx = a.radius_x, ry = a.radius_y;
     const uint32_t *grid32 = reinterpret_cast<const uint32_t *>(a.grid);
     const size_t plane_px = (size_t)W * (size_t)H; // no row window (the host refuses it)
@@ -100,7 +107,7 @@ __global__ void __launch_bounds__(64, WPE) focus_curve_partial(const KernelArgs 
     for(int y = q.y0 + (int)blockIdx.y; y < q.y1; y += (int)gridDim.y) // wave-uniform
         for(int i = i_begin; i < i_end; i++)
         {
-            const float f = __builtin_fmaf(step, static_cast<float>(i), a.focus);
+            const float f = focus_sweep_value(a.focus, a.range, div, i);
             // running min / max per tap (9), pixel pair and channel (3), as u16 pairs
             u16x2 lo[9][NP][3], hi[9][NP][3];
 #pragma unroll
@@ -188,10 +195,7 @@ __global__ void __launch_bounds__(64, WPE) focus_curve_partial(const KernelArgs 
                 u16x2 sum = as_u16x2(0u);
 #pragma unroll
                 for(int t = 0; t < 9; t++)
-                {
-                    const u16x2 d0 = hi[t][p][0] - lo[t][p][0], d1 = hi[t][p][1] - lo[t][p][1], d2 = hi[t][p][2] - lo[t][p][2];
-                    sum += __builtin_elementwise_max(__builtin_elementwise_max(d0, d1), d2);
-                }
+                    sum += focus_tap_range(lo[t][p], hi[t][p]);
                 const uint32_t s = as_u32(sum) & in_mask[p];
                 s_lane += (s & 0xffffu) + (s >> 16);
             }
@@ -258,7 +262,7 @@ __global__ void __launch_bounds__(256) focus_curve_pick(const KernelArgs a, cons
     {
         lfi_focus_curve_result r;
         r.best_index = best_at[0];
-        r.best_focus = focus_curve_candidate(a, q.steps, best_at[0]);
+        r.best_focus = focus_sweep_value(a.focus, a.range, static_cast<float>(q.steps - 1), best_at[0]);
         r.pixels = q.pixels;
         if(q.tiled) // tile (blockIdx.x, blockIdx.y) begins at floor(t · size / tiles) on either axis (lfi.h)
         {

@@ -73,19 +73,9 @@ typedef const __attribute__((address_space(4))) int32_t *focus_const_int_ptr;
 typedef const __attribute__((address_space(4))) float *focus_const_float_ptr;
 typedef const __attribute__((address_space(4))) uint32_t *focus_const_u32_ptr;
 
-// Candidate i of a sweep of div + 1 candidates over [focus, focus + range], and the integer shift it gives an image offset: the ONE place
-// either is formed — by the device (focus_candidate, focus_plan_shift) and by the host that sizes focus_range_t's LDS patches and the
-// padding from them (lfi_focus_sched.hpp), so the two cannot drift apart.  (The division is correctly rounded on both sides; the product
-// of two floats is exact in double: the shift every pixel far from a rounding boundary gets.)
-__host__ __device__ __forceinline__ float focus_sweep_value(const float focus, const float range, const float div, const int i)
-{
-#ifdef __HIP_DEVICE_COMPILE__
-    const float step = __fdiv_rn(range, div);
-#else
-    const float step = range / div;
-#endif
-    return __builtin_fmaf(step, static_cast<float>(i), focus);
-}
+// The integer shift a candidate's value f (focus_sweep_value, focus_map.hpp) gives an image offset: the ONE place it is formed — by the device
+// (focus_plan_shift) and by the host that sizes focus_range_t's LDS patches and the padding from it (lfi_focus_sched.hpp), so the two cannot
+// drift apart.  (The product of two floats is exact in double: the shift every pixel far from a rounding boundary gets.)
 __host__ __device__ __forceinline__ int focus_sweep_shift(const float f, const float offset)
 {
     return static_cast<int>(floor(static_cast<double>(f) * static_cast<double>(offset)));
@@ -1565,6 +1555,30 @@ __global__ void __launch_bounds__(256) focus_line_keys(const KernelArgs a, const
     }
 }
 
+// The nine-sample sum of E for a lane's PPL ∈ {1, 2} adjacent pixels — what focus_pick and focus_tile_costs (focus_tiles.hpp) take for an
+// unflagged pair (a flagged one takes the exact key K instead: each kernel's own select, on its own form of the flag).  sample(t) is the address of tap t's sample of the lane's first pixel; PPL = 2 reads both pixels' samples with one dword
+// load and adds them as a u16 pair (9 · 4081 < 65536 per half).
+template <int PPL, class Sample>
+__device__ __forceinline__ void focus_e_sum9(uint32_t (&sum)[PPL], const Sample sample)
+{
+    if constexpr(PPL == 2)
+    {
+        u16x2 acc = as_u16x2(0u);
+#pragma unroll
+        for(int t = 0; t < 9; t++)
+            acc += as_u16x2(*reinterpret_cast<const uint32_t *>(sample(t)));
+        sum[0] = as_u32(acc) & 0xffffu;
+        sum[1] = as_u32(acc) >> 16;
+    }
+    else
+    {
+        sum[0] = 0;
+#pragma unroll
+        for(int t = 0; t < 9; t++)
+            sum[0] += *reinterpret_cast<const uint16_t *>(sample(t));
+    }
+}
+
 // dispersion per candidate = nine samples of E, or K where the pair is flagged on either axis; first strict minimum → map 0.
 // Blocks of 4 rows × 64·PPL pixels, a lane owns PPL ∈ {1, 2} adjacent pixels; PPL = 2 reads both pixels' samples with one
 // dword load and needs an even radius_x (the E columns x + rx ± rx of an even x are then dword aligned) — the reference always
@@ -1658,22 +1672,7 @@ __device__ __forceinline__ void focus_pick_body(const KernelArgs &a, const Focus
     }
     auto candidate = [&](const int i, const bool with_exact) {
         uint32_t sum[PPL];
-        if constexpr(PPL == 2)
-        {
-            u16x2 acc = as_u16x2(0u); // 9 · 4081 < 65536 per half
-#pragma unroll
-            for(int t = 0; t < 9; t++)
-                acc += as_u16x2(*reinterpret_cast<const uint32_t *>(plane + tap[t]));
-            sum[0] = as_u32(acc) & 0xffffu;
-            sum[1] = as_u32(acc) >> 16;
-        }
-        else
-        {
-            sum[0] = 0;
-#pragma unroll
-            for(int t = 0; t < 9; t++)
-                sum[0] += *reinterpret_cast<const uint16_t *>(plane + tap[t]);
-        }
+        focus_e_sum9<PPL>(sum, [&](const int t) { return plane + tap[t]; });
 #pragma unroll
         for(int j = 0; j < PPL; j++)
         {

@@ -102,6 +102,27 @@ __device__ __forceinline__ u16x2 channel_pair(uint32_t px_a, uint32_t px_b)
     return as_u16x2(__builtin_amdgcn_perm(px_b, px_a, sel));
 }
 
+// Candidate i of a sweep of div + 1 candidates over [focus, focus + range]: the ONE place it is formed — one correctly rounded division, one
+// fma — by every kernel of the packed and the factored family (focus_curve.hpp, focus_factored.hpp) and by the host that sizes
+// focus_range_t's LDS patches and the padding from it (lfi_focus_sched.hpp), so they cannot drift apart.
+__host__ __device__ __forceinline__ float focus_sweep_value(const float focus, const float range, const float div, const int i)
+{
+#ifdef __HIP_DEVICE_COMPILE__
+    const float step = __fdiv_rn(range, div);
+#else
+    const float step = range / div;
+#endif
+    return __builtin_fmaf(step, static_cast<float>(i), focus);
+}
+
+// One tap's integer dispersion for a pixel pair, from the running min / max per channel (3) that focus_estimate_packed and focus_curve_partial
+// (focus_curve.hpp) keep as u16 pairs: the largest channel's max − min.  A pixel's S of the exactness argument above is the sum over its nine taps.
+__device__ __forceinline__ u16x2 focus_tap_range(const u16x2 (&lo)[3], const u16x2 (&hi)[3])
+{
+    const u16x2 d0 = hi[0] - lo[0], d1 = hi[1] - lo[1], d2 = hi[2] - lo[2];
+    return __builtin_elementwise_max(__builtin_elementwise_max(d0, d1), d2);
+}
+
 // PPL pixels per lane (2 or 4); one wave per workgroup (a wave lives ~1 ms: fine-grained dispatch fills the tail)
 // SWEEP: the candidates are the a.focus_steps of lfi_set_focus_steps (focus_estimate_packed_sweep) instead of the reference's 32
 template <int PPL, bool SWEEP>
@@ -116,7 +137,7 @@ __device__ __forceinline__ void focus_estimate_packed_body(const KernelArgs &a)
         return; // wave-uniform
     const bool lane_active = x0 < W;
     const int STEPS = SWEEP ? a.focus_steps : 32; // src/kernels.cu:245
-    const float step = __fdiv_rn(a.range, SWEEP ? a.focus_div : 31.0f);
+    const float div = SWEEP ? a.focus_div : 31.0f;
     const int rx = a.radius_x, ry = a.radius_y;
     const uint32_t *grid32 = reinterpret_cast<const uint32_t *>(a.grid);
     const size_t plane_px = (size_t)W * (size_t)a.in_rows; // the rows this context holds (the host checked that they cover the samples)
@@ -136,7 +157,7 @@ __device__ __forceinline__ void focus_estimate_packed_body(const KernelArgs &a)
 
     for(int i = 0; i < STEPS; i++)
     {
-        const float f = __builtin_fmaf(step, static_cast<float>(i), a.focus);
+        const float f = focus_sweep_value(a.focus, a.range, div, i);
         // running min / max per tap (9), pixel pair (2: pixels {0,1} and {2,3}) and channel (3), as u16 pairs
         u16x2 lo[9][NP][3], hi[9][NP][3];
 #pragma unroll
@@ -225,8 +246,7 @@ __device__ __forceinline__ void focus_estimate_packed_body(const KernelArgs &a)
 #pragma unroll
             for(int t = 0; t < 9; t++)
             {
-                const u16x2 d0 = hi[t][p][0] - lo[t][p][0], d1 = hi[t][p][1] - lo[t][p][1], d2 = hi[t][p][2] - lo[t][p][2];
-                const u16x2 dmax = __builtin_elementwise_max(__builtin_elementwise_max(d0, d1), d2);
+                const u16x2 dmax = focus_tap_range(lo[t][p], hi[t][p]);
                 const u16x2 hmin = __builtin_elementwise_min(__builtin_elementwise_min(hi[t][p][0], hi[t][p][1]), hi[t][p][2]);
                 sum += dmax;
                 // a tap is a "FLT_MIN tap" iff its range is 0 and some channel's maximum is 0; flag = 0 exactly then
@@ -255,7 +275,7 @@ __device__ __forceinline__ void focus_estimate_packed_body(const KernelArgs &a)
 #pragma unroll
     for(int j = 0; j < PPL; j++)
     {
-        const float best_f = __builtin_fmaf(step, static_cast<float>(best_i[j]), a.focus);
+        const float best_f = focus_sweep_value(a.focus, a.range, div, best_i[j]);
         const float normalized = __fdiv_rn(best_f - a.focus, a.range);
         const uint32_t m = static_cast<uint32_t>(roundf(normalized * 255.0f)) & 0xffu;
         out[j] = m | (m << 8) | (m << 16) | 0xff000000u;

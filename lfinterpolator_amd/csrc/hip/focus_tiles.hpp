@@ -88,22 +88,7 @@ __global__ void __launch_bounds__(256) focus_tile_costs(const KernelArgs a, cons
                 const uint32_t flagged_y = __builtin_amdgcn_readfirstlane(w.bady[y]);
                 const uint8_t *e = plane + (size_t(y) * w.We_p + xs) * 2;
                 uint32_t sum[PPL];
-                if constexpr(PPL == 2)
-                {
-                    u16x2 acc = as_u16x2(0u); // 9 · 4081 < 65536 per half
-#pragma unroll
-                    for(int t = 0; t < 9; t++)
-                        acc += as_u16x2(*reinterpret_cast<const uint32_t *>(e + uint32_t((t / 3) * ry * w.We_p + (t % 3) * rx) * 2u));
-                    sum[0] = as_u32(acc) & 0xffffu;
-                    sum[1] = as_u32(acc) >> 16;
-                }
-                else
-                {
-                    sum[0] = 0;
-#pragma unroll
-                    for(int t = 0; t < 9; t++)
-                        sum[0] += *reinterpret_cast<const uint16_t *>(e + uint32_t((t / 3) * ry * w.We_p + (t % 3) * rx) * 2u);
-                }
+                focus_e_sum9<PPL>(sum, [&](const int t) { return e + uint32_t((t / 3) * ry * w.We_p + (t % 3) * rx) * 2u; });
                 bool flagged[PPL], any = false;
 #pragma unroll
                 for(int j = 0; j < PPL; j++)
@@ -135,11 +120,7 @@ __global__ void __launch_bounds__(256) focus_tile_costs(const KernelArgs a, cons
 #pragma unroll 8
     for(int k = 0; k < 32; k++)
         s += lane_sum[c][k * 8 + p];
-#define LFI_SWIZZLE_XOR(m) (((m) << 10) | 0x1f)
-    s += (uint32_t)__builtin_amdgcn_ds_swizzle((int)s, LFI_SWIZZLE_XOR(1));
-    s += (uint32_t)__builtin_amdgcn_ds_swizzle((int)s, LFI_SWIZZLE_XOR(2));
-    s += (uint32_t)__builtin_amdgcn_ds_swizzle((int)s, LFI_SWIZZLE_XOR(4));
-#undef LFI_SWIZZLE_XOR
+    s = swizzle_sum_u32<3>(s); // the eight threads of a candidate are neighbours
     if(p == 0)
         q.partial[((size_t)tile * FOCUS_STEPS + c) * q.n_wg + band * uint32_t(q.chunks) + chunk] = s;
 }

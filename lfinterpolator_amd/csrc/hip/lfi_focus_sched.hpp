@@ -268,6 +268,9 @@ int launch_focus_factored_keys(lfi_ctx *ctx, const KernelArgs &a, FocusJob &job,
     return LFI_OK;
 }
 
+// pixels per lane of the kernels behind the keys (focus_pick, focus_tile_costs): two need dword-aligned sample pairs — an even radius_x (the reference's is)
+int focus_keys_ppl(const lfi_ctx *ctx) { return (ctx->radius[0] % 2 == 0 && ctx->width >= 2) ? 2 : 1; }
+
 // the factored estimate's last pass: per pixel the first strict minimum of the keys → map 0 (the caller filters it into map 1).
 // A sweep of more than 32 candidates: the same kernels' carrying forms, once per pass (focus_pick_store)
 int launch_focus_pick(lfi_ctx *ctx, const KernelArgs &a, const lfi::FocusWork &w, bool e_32bit, bool direct_range)
@@ -275,37 +278,37 @@ int launch_focus_pick(lfi_ctx *ctx, const KernelArgs &a, const lfi::FocusWork &w
     const bool carry = a.focus_steps > lfi::FOCUS_STEPS;
     const int W = ctx->width, H = ctx->height, rx = ctx->radius[0], ry = ctx->radius[1];
     hipStream_t st = ctx->stream;
+    const int ppl = focus_keys_ppl(ctx);
+    const uint32_t blocks_x = uint32_t((W + 64 * ppl - 1) / (64 * ppl)), blocks_y = uint32_t((H + 3) / 4);
+    const int striped = blocks_x >= 8;
+    const uint32_t nblocks = striped ? 8u * lfi::stripe_blocks_per_xcd(blocks_x, blocks_y, 1u) : blocks_x * blocks_y;
+    // the tap block taken apart (focus_pick_sep): even radius_x of at most 64; variant "factored_direct" keeps focus_pick<2>, the other implementation
+    if(ppl == 2 && rx <= 64 && e_32bit && !direct_range)
     {
-        // two pixels per lane need dword-aligned sample pairs: even radius_x (the reference's is)
-        const int ppl = (rx % 2 == 0 && W >= 2) ? 2 : 1;
-        const uint32_t blocks_x = uint32_t((W + 64 * ppl - 1) / (64 * ppl)), blocks_y = uint32_t((H + 3) / 4);
-        const int striped = blocks_x >= 8;
-        const uint32_t nblocks = striped ? 8u * lfi::stripe_blocks_per_xcd(blocks_x, blocks_y, 1u) : blocks_x * blocks_y;
-        // the tap block taken apart (focus_pick_sep): even radius_x of at most 64; variant "factored_direct" keeps focus_pick<2>, the other implementation
-        if(ppl == 2 && rx <= 64 && e_32bit && !direct_range)
-        {
-            // (row-major order of the workgroups, not stripes per XCD: this kernel's re-use of E's rows happens inside a workgroup)
-            const uint32_t nb = blocks_x * lfi::focus_pick_sep_block_rows(H, ry);
-            if(carry)
-                hipLaunchKernelGGL(lfi::focus_pick_sep_carry, dim3(nb), dim3(64 * lfi::FPS_WAVES), 0, st, a, w);
-            else
-                hipLaunchKernelGGL(lfi::focus_pick_sep, dim3(nb), dim3(64 * lfi::FPS_WAVES), 0, st, a, w);
-        }
-        else if(ppl == 2 && carry)
-            hipLaunchKernelGGL(lfi::focus_pick_carry<2>, dim3(nblocks), dim3(256), 0, st, a, w, striped);
-        else if(ppl == 2)
-            hipLaunchKernelGGL(lfi::focus_pick<2>, dim3(nblocks), dim3(256), 0, st, a, w, striped);
-        else if(carry)
-            hipLaunchKernelGGL(lfi::focus_pick_carry<1>, dim3(nblocks), dim3(256), 0, st, a, w, striped);
+        // (row-major order of the workgroups, not stripes per XCD: this kernel's re-use of E's rows happens inside a workgroup)
+        const uint32_t nb = blocks_x * lfi::focus_pick_sep_block_rows(H, ry);
+        if(carry)
+            hipLaunchKernelGGL(lfi::focus_pick_sep_carry, dim3(nb), dim3(64 * lfi::FPS_WAVES), 0, st, a, w);
         else
-            hipLaunchKernelGGL(lfi::focus_pick<1>, dim3(nblocks), dim3(256), 0, st, a, w, striped);
+            hipLaunchKernelGGL(lfi::focus_pick_sep, dim3(nb), dim3(64 * lfi::FPS_WAVES), 0, st, a, w);
     }
+    else if(ppl == 2 && carry)
+        hipLaunchKernelGGL(lfi::focus_pick_carry<2>, dim3(nblocks), dim3(256), 0, st, a, w, striped);
+    else if(ppl == 2)
+        hipLaunchKernelGGL(lfi::focus_pick<2>, dim3(nblocks), dim3(256), 0, st, a, w, striped);
+    else if(carry)
+        hipLaunchKernelGGL(lfi::focus_pick_carry<1>, dim3(nblocks), dim3(256), 0, st, a, w, striped);
+    else
+        hipLaunchKernelGGL(lfi::focus_pick<1>, dim3(nblocks), dim3(256), 0, st, a, w, striped);
     LFI_HIP(ctx, hipGetLastError());
     return LFI_OK;
 }
 
-// the whole factored estimate: plan → pad → E → exact keys → pick, once per 32 candidates of a.focus_steps (the padding by the first pass only)
-int launch_focus_factored(lfi_ctx *ctx, const KernelArgs &a, FocusJob &job, bool *done, bool direct_range)
+// The passes of a factored sweep: plan → pad → E → exact keys (launch_focus_factored_keys), then consume(pass, w, e_32bit) — whatever reads E
+// and K — once per 32 candidates of a.focus_steps, the padding by the first pass only.  *done = false when the first pass declined (the
+// later ones take its geometry): then nothing has been enqueued and consume has not been called.
+template <class Consume>
+int focus_factored_passes(lfi_ctx *ctx, const KernelArgs &a, FocusJob &job, bool *done, bool direct_range, Consume &&consume)
 {
     KernelArgs pass = a;
     for(pass.focus_i0 = 0; pass.focus_i0 < a.focus_steps; pass.focus_i0 += lfi::FOCUS_STEPS)
@@ -314,28 +317,37 @@ int launch_focus_factored(lfi_ctx *ctx, const KernelArgs &a, FocusJob &job, bool
         bool e_32bit = false;
         if(int rc = launch_focus_factored_keys(ctx, pass, job, done, direct_range, &w, &e_32bit))
             return rc;
-        if(!*done) // (declined: by the first pass — the later ones take its geometry)
+        if(!*done)
             return LFI_OK;
-        if(int rc = launch_focus_pick(ctx, pass, w, e_32bit, direct_range))
+        if(int rc = consume(pass, w, e_32bit))
             return rc;
     }
     return LFI_OK;
 }
 
-// The focus curve of the region [x0, x1) × [y0, y1) (lfi_focus_curve; the caller has checked the arguments): partial sums per workgroup and
-// candidate, their sum per candidate, the first strict minimum — three launches on the compute stream.  ctx->curve_ws holds the curve and the
-// result (FOCUS_CURVE_HEAD bytes: [steps] u64 + lfi_focus_curve_result) followed by the partials [steps][workgroups]; nothing of the estimate's
-// state (focus_ws, the padded planes, the maps) is touched.  *d_head = the device address of the curve.
-constexpr size_t FOCUS_CURVE_HEAD = (sizeof(uint64_t) * lfi::FOCUS_CURVE_MAX_STEPS + sizeof(lfi_focus_curve_result) + 255) / 256 * 256;
-
-int launch_focus_curve(lfi_ctx *ctx, const KernelArgs &a, int x0, int y0, int x1, int y1, int steps, const uint8_t **d_head)
+// the whole factored estimate: every pass's keys, then its pick
+int launch_focus_factored(lfi_ctx *ctx, const KernelArgs &a, FocusJob &job, bool *done, bool direct_range)
 {
-    constexpr int PPL = 2; // pixels per lane: focus_estimate_packed<2, 4>'s shape (row-window path, variant "packed_p2"), five waves per SIMD
-    const uint32_t blocks_x = uint32_t((x1 - x0 + 64 * PPL - 1) / (64 * PPL));
-    // One row per wave while the partials stay small (fine-grained dispatch fills the tail: a wave lives ≈ 1 ms per row at 32 images); beyond
-    // 2 Mi partials (16 MB) — whole 4K frames with more than 32 candidates — a wave walks several rows, never fewer than 8192 waves.
-    const uint32_t max_wg = std::min(65536u, std::max(8192u, (2u << 20) / uint32_t(steps)));
-    const uint32_t blocks_y = std::min(uint32_t(y1 - y0), std::max(1u, max_wg / blocks_x));
+    return focus_factored_passes(ctx, a, job, done, direct_range, [&](const KernelArgs &pass, const lfi::FocusWork &w, bool e_32bit) {
+        return launch_focus_pick(ctx, pass, w, e_32bit, direct_range);
+    });
+}
+
+// A focus curve in memory: cost[steps] (u64), then its lfi_focus_curve_result — what focus_curve_sum / focus_curve_pick write and the host
+// copies in one piece.  ctx->curve_ws holds one (lfi_focus_curve) or one per tile, row-major (lfi_focus_tiles), then the partial sums.
+constexpr size_t focus_curve_head(const int steps) { return sizeof(uint64_t) * size_t(steps) + sizeof(lfi_focus_curve_result); }
+constexpr size_t FOCUS_CURVE_HEAD = (focus_curve_head(lfi::FOCUS_CURVE_MAX_STEPS) + 255) / 256 * 256;
+
+constexpr int FOCUS_CURVE_PPL = 2; // pixels per lane: focus_estimate_packed<2, 4>'s shape (row-window path, variant "packed_p2"), five waves per SIMD
+inline uint32_t focus_curve_blocks_x(const int width) { return uint32_t((width + 64 * FOCUS_CURVE_PPL - 1) / (64 * FOCUS_CURVE_PPL)); }
+
+// The focus curve of the rectangle [x0, x1) × [y0, y1) over `steps` candidates: partial sums per workgroup and candidate, their sum per
+// candidate, the first strict minimum — three launches on the compute stream.  head: where the curve and its result go (focus_curve_head(steps)
+// bytes); partial: room for steps × blocks_x × min(rows, max_rows) u64.  max_rows caps the workgroups: a wave walks one row of the rectangle
+// while its rows are at most that many, else several.  Nothing of the estimate's state (focus_ws, the padded planes, the maps) is touched.
+void launch_focus_curve_rect(lfi_ctx *ctx, const KernelArgs &a, int x0, int y0, int x1, int y1, int steps, uint8_t *head, uint8_t *partial, uint32_t max_rows)
+{
+    const uint32_t blocks_x = focus_curve_blocks_x(x1 - x0), blocks_y = std::min(uint32_t(y1 - y0), max_rows);
     lfi::FocusCurveArgs q{};
     q.x0 = x0, q.y0 = y0, q.x1 = x1, q.y1 = y1;
     q.steps = steps;
@@ -346,49 +358,56 @@ int launch_focus_curve(lfi_ctx *ctx, const KernelArgs &a, int x0, int y0, int x1
     q.steps_per_wg = (steps + int(want_z) - 1) / int(want_z);
     const uint32_t blocks_z = uint32_t((steps + q.steps_per_wg - 1) / q.steps_per_wg);
     q.pixels = uint64_t(x1 - x0) * uint64_t(y1 - y0);
-    LFI_HIP(ctx, ctx->curve_ws.reserve(FOCUS_CURVE_HEAD + sizeof(uint64_t) * size_t(steps) * q.n_wg));
-    q.cost = reinterpret_cast<uint64_t *>(ctx->curve_ws.get());
-    q.partial = reinterpret_cast<uint64_t *>(ctx->curve_ws.get() + FOCUS_CURVE_HEAD);
+    q.cost = reinterpret_cast<uint64_t *>(head);
+    q.partial = reinterpret_cast<uint64_t *>(partial);
     hipStream_t st = ctx->stream;
-    hipLaunchKernelGGL((lfi::focus_curve_partial<PPL, 4>), dim3(blocks_x, blocks_y, blocks_z), dim3(64), 0, st, a, q);
+    hipLaunchKernelGGL((lfi::focus_curve_partial<FOCUS_CURVE_PPL, 4>), dim3(blocks_x, blocks_y, blocks_z), dim3(64), 0, st, a, q);
     hipLaunchKernelGGL(lfi::focus_curve_sum, dim3(steps), dim3(256), 0, st, q);
     hipLaunchKernelGGL(lfi::focus_curve_pick, dim3(1), dim3(256), 0, st, a, q);
+}
+
+// lfi_focus_curve (the caller has checked the arguments).  *d_head = the device address of the curve.
+int launch_focus_curve(lfi_ctx *ctx, const KernelArgs &a, int x0, int y0, int x1, int y1, int steps, const uint8_t **d_head)
+{
+    const uint32_t blocks_x = focus_curve_blocks_x(x1 - x0);
+    // One row per wave while the partials stay small (fine-grained dispatch fills the tail: a wave lives ≈ 1 ms per row at 32 images); beyond
+    // 2 Mi partials (16 MB) — whole 4K frames with more than 32 candidates — a wave walks several rows, never fewer than 8192 waves.
+    const uint32_t max_wg = std::min(65536u, std::max(8192u, (2u << 20) / uint32_t(steps)));
+    const uint32_t max_rows = std::max(1u, max_wg / blocks_x);
+    LFI_HIP(ctx, ctx->curve_ws.reserve(FOCUS_CURVE_HEAD + sizeof(uint64_t) * size_t(steps) * blocks_x * std::min(uint32_t(y1 - y0), max_rows)));
+    launch_focus_curve_rect(ctx, a, x0, y0, x1, y1, steps, ctx->curve_ws.get(), ctx->curve_ws.get() + FOCUS_CURVE_HEAD, max_rows);
     LFI_HIP(ctx, hipGetLastError());
     *d_head = ctx->curve_ws.get();
     return LFI_OK;
 }
 
 // The focus curves of the tiles_x × tiles_y tiles over `steps` candidates, a multiple of 32 up to 256 (lfi_focus_tiles: 32; lfi_focus_tiles_steps;
-// the caller has checked the arguments).  ctx->curve_ws holds, per tile, the curve and its result back to back (focus_tile_head(steps) bytes
+// the caller has checked the arguments).  ctx->curve_ws holds, per tile, the curve and its result back to back (focus_curve_head(steps) bytes
 // each, row-major over the tiles: what the host copies), then the partial sums.
-//   factored: one pass per 32 candidates, as launch_focus_factored's — launch_focus_factored_keys with focus_i0 = 32g of focus_steps = steps,
-//             focus_tile_costs in the pick's place, then focus_curve_sum for the pass's slice cost[tile][32g … 32g + 31]; behind the last pass
-//             focus_curve_pick over all tiles and all steps.  2·passes + 1 launches behind the keys whatever the grid; at 32 steps the three
-//             launches lfi_focus_tiles has always made.  The partials stay [tiles][32][n_wg]: every pass overwrites them, behind the sum that
-//             read them (one stream).  Pass g + 1 rewrites E and K, which pass g's focus_tile_costs reads: launch_focus_factored_keys records
-//             ev_fork on the compute stream behind everything enqueued there so far — the tile costs and the sum, as the pick of a fine map —
-//             and the side stream's writers wait for it; the range pass follows the tile costs in the compute stream's own order.
-//   else (another estimate variant, or the factored estimate's first pass declined — then nothing has been enqueued): lfi_focus_curve's three
-//             launches tile by tile with all the steps — the same numbers.
-constexpr size_t focus_tile_head(const int steps) { return sizeof(uint64_t) * size_t(steps) + sizeof(lfi_focus_curve_result); }
-
+//   factored: focus_factored_passes with focus_steps = steps and, in the pick's place, focus_tile_costs, then focus_curve_sum for the pass's
+//             slice cost[tile][32g … 32g + 31]; behind the last pass focus_curve_pick over all tiles and all steps.  2·passes + 1 launches
+//             behind the keys whatever the grid; at 32 steps the three launches lfi_focus_tiles has always made.  The partials stay
+//             [tiles][32][n_wg]: every pass overwrites them, behind the sum that read them (one stream).  Pass g + 1 rewrites E and K, which
+//             pass g's focus_tile_costs reads: launch_focus_factored_keys records ev_fork on the compute stream behind everything enqueued
+//             there so far — the tile costs and the sum — and the side stream's writers wait for it; the range pass follows the tile costs
+//             in the compute stream's own order.
+//   else (another estimate variant, or the factored estimate's first pass declined — then nothing has been enqueued):
+//             launch_focus_curve_rect tile by tile with all the steps — the same numbers; the partials' room is shared (one stream).
 int launch_focus_tiles(lfi_ctx *ctx, const KernelArgs &a, int tiles_x, int tiles_y, int steps, const uint8_t **d_head)
 {
     const int W = ctx->width, H = ctx->height;
     const size_t tiles = size_t(tiles_x) * size_t(tiles_y);
-    const size_t tile_head = focus_tile_head(steps);
+    const size_t tile_head = focus_curve_head(steps);
     const size_t head_bytes = (tile_head * tiles + 255) / 256 * 256;
+    const int tile_w = (W + tiles_x - 1) / tiles_x, tile_h = (H + tiles_y - 1) / tiles_y; // the widest, the tallest
     hipStream_t st = ctx->stream;
-    lfi::FocusCurveArgs q{};
-    q.steps = steps;
     if((ctx->focus_variant == 0 || ctx->focus_variant == 4) && W <= 65535 && H <= 65535)
     {
         FocusJob job;
         job.offsets = ctx->h_focus_offsets.data();
         job.ids = ctx->h_focus_ids.data();
         job.n_ids = ctx->n_focus_ids;
-        const int ppl = (ctx->radius[0] % 2 == 0 && W >= 2) ? 2 : 1; // as the pick: dword sample pairs need an even radius_x
-        const int tile_w = (W + tiles_x - 1) / tiles_x, tile_h = (H + tiles_y - 1) / tiles_y; // the widest, the tallest
+        const int ppl = focus_keys_ppl(ctx);
         lfi::FocusTileArgs t{};
         t.tiles_x = tiles_x, t.tiles_y = tiles_y;
         t.chunks = (tile_w + (ppl - 1) + 64 * ppl - 1) / (64 * ppl); // (+1: a tile's first column rounded down to even)
@@ -399,18 +418,15 @@ int launch_focus_tiles(lfi_ctx *ctx, const KernelArgs &a, int tiles_x, int tiles
         t.bands = (tile_h + 4 * t.rows_per_wave - 1) / (4 * t.rows_per_wave);
         t.n_wg = uint32_t(t.chunks) * uint32_t(t.bands);
         const size_t n_blocks = tiles * t.n_wg;
-        KernelArgs pass = a;
-        pass.focus_steps = steps;
-        pass.focus_div = float(steps - 1);
+        lfi::FocusCurveArgs q{};
+        q.steps = steps;
+        q.n_wg = t.n_wg;
+        q.tiled = 1;
+        KernelArgs sweep = a;
+        sweep.focus_steps = steps;
+        sweep.focus_div = float(steps - 1);
         bool done = false;
-        for(pass.focus_i0 = 0; pass.focus_i0 < steps; pass.focus_i0 += lfi::FOCUS_STEPS)
-        {
-            lfi::FocusWork w{};
-            bool e_32bit = false;
-            if(int rc = launch_focus_factored_keys(ctx, pass, job, &done, ctx->focus_variant == 4, &w, &e_32bit))
-                return rc;
-            if(!done) // (declined: by the first pass — the later ones take its geometry)
-                break;
+        const int rc = focus_factored_passes(ctx, sweep, job, &done, ctx->focus_variant == 4, [&](const KernelArgs &pass, const lfi::FocusWork &w, bool) {
             if(pass.focus_i0 == 0)
             {
                 if(n_blocks > 0x7fffffffu)
@@ -418,8 +434,6 @@ int launch_focus_tiles(lfi_ctx *ctx, const KernelArgs &a, int tiles_x, int tiles
                 LFI_HIP(ctx, ctx->curve_ws.reserve(head_bytes + sizeof(uint64_t) * lfi::FOCUS_STEPS * n_blocks));
                 q.cost = reinterpret_cast<uint64_t *>(ctx->curve_ws.get());
                 q.partial = t.partial = reinterpret_cast<uint64_t *>(ctx->curve_ws.get() + head_bytes);
-                q.n_wg = t.n_wg;
-                q.tiled = 1;
             }
             if(ppl == 2)
                 hipLaunchKernelGGL(lfi::focus_tile_costs<2>, dim3(uint32_t(n_blocks)), dim3(256), 0, st, pass, w, t);
@@ -427,7 +441,10 @@ int launch_focus_tiles(lfi_ctx *ctx, const KernelArgs &a, int tiles_x, int tiles
                 hipLaunchKernelGGL(lfi::focus_tile_costs<1>, dim3(uint32_t(n_blocks)), dim3(256), 0, st, pass, w, t);
             q.sum_at = pass.focus_i0;
             hipLaunchKernelGGL(lfi::focus_curve_sum, dim3(lfi::FOCUS_STEPS, tiles_x, tiles_y), dim3(256), 0, st, q);
-        }
+            return int(LFI_OK);
+        });
+        if(rc)
+            return rc;
         if(done)
         {
             ctx->tiles_passes = steps / lfi::FOCUS_STEPS;
@@ -437,32 +454,15 @@ int launch_focus_tiles(lfi_ctx *ctx, const KernelArgs &a, int tiles_x, int tiles
             return LFI_OK;
         }
     }
-    // tile by tile: focus_curve_partial's shape as in launch_focus_curve, the partials' room shared (the launches follow each other on one stream)
-    constexpr int PPL = 2;
     ctx->tiles_passes = 0;
-    q.tiled = 0, q.sum_at = 0; // one tile per launch, every candidate of it
-    const int tile_w = (W + tiles_x - 1) / tiles_x, tile_h = (H + tiles_y - 1) / tiles_y;
-    const uint32_t blocks_x = uint32_t((tile_w + 64 * PPL - 1) / (64 * PPL));
-    const uint32_t blocks_y_max = std::min(uint32_t(tile_h), std::max(1u, 8192u / blocks_x));
-    LFI_HIP(ctx, ctx->curve_ws.reserve(head_bytes + sizeof(uint64_t) * size_t(steps) * size_t(blocks_x) * blocks_y_max));
-    q.partial = reinterpret_cast<uint64_t *>(ctx->curve_ws.get() + head_bytes);
+    const uint32_t blocks_x = focus_curve_blocks_x(tile_w);
+    const uint32_t max_rows = std::max(1u, 8192u / blocks_x);
+    LFI_HIP(ctx, ctx->curve_ws.reserve(head_bytes + sizeof(uint64_t) * size_t(steps) * blocks_x * std::min(uint32_t(tile_h), max_rows)));
     for(int ty = 0; ty < tiles_y; ty++)
         for(int tx = 0; tx < tiles_x; tx++)
-        {
-            q.x0 = lfi::focus_tile_edge(tx, W, tiles_x), q.x1 = lfi::focus_tile_edge(tx + 1, W, tiles_x);
-            q.y0 = lfi::focus_tile_edge(ty, H, tiles_y), q.y1 = lfi::focus_tile_edge(ty + 1, H, tiles_y);
-            const uint32_t bx = uint32_t((q.x1 - q.x0 + 64 * PPL - 1) / (64 * PPL));
-            const uint32_t by = std::min(uint32_t(q.y1 - q.y0), blocks_y_max);
-            q.n_wg = bx * by;
-            const uint32_t want_z = std::min(uint32_t(q.steps), std::max(1u, uint32_t(ctx->cu_count) * 16u / q.n_wg));
-            q.steps_per_wg = (q.steps + int(want_z) - 1) / int(want_z);
-            const uint32_t bz = uint32_t((q.steps + q.steps_per_wg - 1) / q.steps_per_wg);
-            q.pixels = uint64_t(q.x1 - q.x0) * uint64_t(q.y1 - q.y0);
-            q.cost = reinterpret_cast<uint64_t *>(ctx->curve_ws.get() + tile_head * (size_t(ty) * tiles_x + tx));
-            hipLaunchKernelGGL((lfi::focus_curve_partial<PPL, 4>), dim3(bx, by, bz), dim3(64), 0, st, a, q);
-            hipLaunchKernelGGL(lfi::focus_curve_sum, dim3(q.steps), dim3(256), 0, st, q);
-            hipLaunchKernelGGL(lfi::focus_curve_pick, dim3(1), dim3(256), 0, st, a, q);
-        }
+            launch_focus_curve_rect(ctx, a, lfi::focus_tile_edge(tx, W, tiles_x), lfi::focus_tile_edge(ty, H, tiles_y), lfi::focus_tile_edge(tx + 1, W, tiles_x),
+                                    lfi::focus_tile_edge(ty + 1, H, tiles_y), steps, ctx->curve_ws.get() + tile_head * (size_t(ty) * tiles_x + tx),
+                                    ctx->curve_ws.get() + head_bytes, max_rows);
     LFI_HIP(ctx, hipGetLastError());
     *d_head = ctx->curve_ws.get();
     return LFI_OK;

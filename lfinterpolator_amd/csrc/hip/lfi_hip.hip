@@ -793,27 +793,42 @@ int lfi_focus_steps(lfi_ctx *ctx, int *out_steps)
     return LFI_OK;
 }
 
+// What every focus entry point asks before it enqueues anything, in this order: the RGBA inputs, the grid and the parameters; no row window
+// unless the call computes a band (window_allowed); the call's own arguments (args_error: empty when they are fine); sampled images
+// (centre_ids: the parameters' focus_map_ids — lfi_view_focus_maps brings its own) and a search interval; then the device is bound and the
+// uploads in flight are joined.  call: the entry point's name; noun: what it computes, as the messages name it.
+static int focus_entry(lfi_ctx *ctx, const char *call, const std::string &noun, bool window_allowed, const std::string &args_error, bool centre_ids = true)
+{
+    if(ctx->inputs_released)
+        return fail(ctx, LFI_EINVAL, "the RGBA inputs were released (lfi_release_inputs): the " + noun + (noun.back() == 's' ? " need" : " needs") +
+                                         " them - upload the images again (lfi_set_grid)");
+    if(!ctx->grid || !ctx->have_params)
+        return fail(ctx, LFI_EINVAL, "lfi_set_grid / lfi_set_params have not been called");
+    if(ctx->windowed && !window_allowed)
+        return fail(ctx, LFI_EINVAL, std::string(call) + " does not work on a row window");
+    if(!args_error.empty())
+        return fail(ctx, LFI_EINVAL, args_error);
+    if(centre_ids && ctx->n_focus_ids < 1)
+        return fail(ctx, LFI_EINVAL, "no focus_map_ids in the parameters");
+    if(!(ctx->range > 0.0f))
+        return fail(ctx, LFI_EINVAL, "focus range must be > 0 for the " + noun + ": [focus, focus + range] is the search interval");
+    if(int rc = bind(ctx))
+        return rc;
+    return join_uploads(ctx);
+}
+
 int lfi_focus_map(lfi_ctx *ctx)
 {
     if(!ctx)
         return LFI_EINVAL;
-    if(ctx->inputs_released)
-        return fail(ctx, LFI_EINVAL, "the RGBA inputs were released (lfi_release_inputs): the focus map needs them - upload the images again (lfi_set_grid)");
-    if(!ctx->grid || !ctx->have_params)
-        return fail(ctx, LFI_EINVAL, "lfi_set_grid / lfi_set_params have not been called");
-    if(ctx->n_focus_ids < 1)
-        return fail(ctx, LFI_EINVAL, "no focus_map_ids in the parameters");
-    if(!(ctx->range > 0.0f))
-        return fail(ctx, LFI_EINVAL, "focus range must be > 0 for the focus map");
     // lfi_set_focus_steps: the sweep's length.  The factored estimate (one pass per 32 candidates) and focus_estimate_packed_sweep honour it;
     // the LDS-staged and the plain kernel are the reference's 32 candidates as written and refuse any other number
     const bool fine = ctx->focus_steps != lfi::FOCUS_STEPS;
+    std::string bad;
     if(fine && !ctx->windowed && (ctx->focus_variant == 1 || ctx->focus_variant == 3))
-        return fail(ctx, LFI_EINVAL, std::string("lfi_focus_map: the estimate variant \"") + (ctx->focus_variant == 1 ? "lds" : "plain") +
-                                         "\" computes 32 candidates only (lfi_set_focus_steps is " + std::to_string(ctx->focus_steps) + ")");
-    if(int rc = bind(ctx))
-        return rc;
-    if(int rc = join_uploads(ctx))
+        bad = std::string("lfi_focus_map: the estimate variant \"") + (ctx->focus_variant == 1 ? "lds" : "plain") +
+              "\" computes 32 candidates only (lfi_set_focus_steps is " + std::to_string(ctx->focus_steps) + ")";
+    if(int rc = focus_entry(ctx, "lfi_focus_map", "focus map", true, bad))
         return rc;
     if(int rc = join_filter(ctx)) // the previous map's filter still reads map 0, which this call rewrites
         return rc;
@@ -896,34 +911,19 @@ int lfi_focus_curve(lfi_ctx *ctx, int x0, int y0, int x1, int y1, int steps, uin
 {
     if(!ctx)
         return LFI_EINVAL;
-    if(ctx->inputs_released)
-        return fail(ctx, LFI_EINVAL, "the RGBA inputs were released (lfi_release_inputs): the focus curve needs them - upload the images again (lfi_set_grid)");
-    if(!ctx->grid || !ctx->have_params)
-        return fail(ctx, LFI_EINVAL, "lfi_set_grid / lfi_set_params have not been called");
-    if(ctx->windowed)
-        return fail(ctx, LFI_EINVAL, "lfi_focus_curve does not work on a row window");
-    if(!out)
-        return fail(ctx, LFI_EINVAL, "lfi_focus_curve: out is NULL");
-    if(ctx->n_focus_ids < 1)
-        return fail(ctx, LFI_EINVAL, "no focus_map_ids in the parameters");
-    if(!(ctx->range > 0.0f))
-        return fail(ctx, LFI_EINVAL, "focus range must be > 0 for the focus curve: [focus, focus + range] is the search interval");
-    if(steps < 2 || steps > lfi::FOCUS_CURVE_MAX_STEPS)
-        return fail(ctx, LFI_EINVAL, "lfi_focus_curve: steps must be in [2, 256]");
-    if(x0 < 0 || y0 < 0 || x1 > ctx->width || y1 > ctx->height || x0 >= x1 || y0 >= y1)
-        return fail(ctx, LFI_EINVAL, "lfi_focus_curve: the region is empty or leaves the image");
-    if(int rc = bind(ctx))
-        return rc;
-    if(int rc = join_uploads(ctx))
+    const char *bad = !out ? "lfi_focus_curve: out is NULL"
+                      : steps < 2 || steps > lfi::FOCUS_CURVE_MAX_STEPS ? "lfi_focus_curve: steps must be in [2, 256]"
+                      : x0 < 0 || y0 < 0 || x1 > ctx->width || y1 > ctx->height || x0 >= x1 || y0 >= y1 ? "lfi_focus_curve: the region is empty or leaves the image"
+                                                                                                        : "";
+    if(int rc = focus_entry(ctx, "lfi_focus_curve", "focus curve", false, bad))
         return rc;
     const KernelArgs a = make_args(ctx, 0, ctx->views_n, LFI_METHOD_STD);
     const uint8_t *d_head = nullptr;
     if(int rc = launch_focus_curve(ctx, a, x0, y0, x1, y1, steps, &d_head))
         return rc;
     // the curve and the result lie back to back: one copy of steps · 8 + 16 bytes
-    uint64_t head[lfi::FOCUS_CURVE_MAX_STEPS + sizeof(lfi_focus_curve_result) / sizeof(uint64_t)];
-    const size_t head_bytes = sizeof(uint64_t) * steps + sizeof(lfi_focus_curve_result);
-    LFI_HIP(ctx, hipMemcpyAsync(head, d_head, head_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    uint64_t head[focus_curve_head(lfi::FOCUS_CURVE_MAX_STEPS) / sizeof(uint64_t)];
+    LFI_HIP(ctx, hipMemcpyAsync(head, d_head, focus_curve_head(steps), hipMemcpyDeviceToHost, ctx->stream));
     LFI_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if(out_cost)
         std::memcpy(out_cost, head, sizeof(uint64_t) * steps);
@@ -946,25 +946,14 @@ int lfi_focus_tiles_steps(lfi_ctx *ctx, int tiles_x, int tiles_y, int steps, uin
 {
     if(!ctx)
         return LFI_EINVAL;
-    if(ctx->inputs_released)
-        return fail(ctx, LFI_EINVAL, "the RGBA inputs were released (lfi_release_inputs): the focus tiles need them - upload the images again (lfi_set_grid)");
-    if(!ctx->grid || !ctx->have_params)
-        return fail(ctx, LFI_EINVAL, "lfi_set_grid / lfi_set_params have not been called");
-    if(ctx->windowed)
-        return fail(ctx, LFI_EINVAL, "lfi_focus_tiles does not work on a row window");
+    std::string bad;
     if(!out)
-        return fail(ctx, LFI_EINVAL, "lfi_focus_tiles: out is NULL");
-    if(ctx->n_focus_ids < 1)
-        return fail(ctx, LFI_EINVAL, "no focus_map_ids in the parameters");
-    if(!(ctx->range > 0.0f))
-        return fail(ctx, LFI_EINVAL, "focus range must be > 0 for the focus tiles: [focus, focus + range] is the search interval");
-    if(tiles_x < 1 || tiles_y < 1 || tiles_x > std::min(ctx->width, 256) || tiles_y > std::min(ctx->height, 256))
-        return fail(ctx, LFI_EINVAL, "lfi_focus_tiles: the grid must have 1 to min(width, 256) columns and 1 to min(height, 256) rows of tiles");
-    if(steps < lfi::FOCUS_STEPS || steps > lfi::FOCUS_STEPS * lfi::FOCUS_MAX_PASSES || steps % lfi::FOCUS_STEPS != 0)
-        return fail(ctx, LFI_EINVAL, "lfi_focus_tiles_steps: " + std::to_string(steps) + " candidates - the focus tiles take a multiple of 32 from 32 to 256");
-    if(int rc = bind(ctx))
-        return rc;
-    if(int rc = join_uploads(ctx))
+        bad = "lfi_focus_tiles: out is NULL";
+    else if(tiles_x < 1 || tiles_y < 1 || tiles_x > std::min(ctx->width, 256) || tiles_y > std::min(ctx->height, 256))
+        bad = "lfi_focus_tiles: the grid must have 1 to min(width, 256) columns and 1 to min(height, 256) rows of tiles";
+    else if(steps < lfi::FOCUS_STEPS || steps > lfi::FOCUS_STEPS * lfi::FOCUS_MAX_PASSES || steps % lfi::FOCUS_STEPS != 0)
+        bad = "lfi_focus_tiles_steps: " + std::to_string(steps) + " candidates - the focus tiles take a multiple of 32 from 32 to 256";
+    if(int rc = focus_entry(ctx, "lfi_focus_tiles", "focus tiles", false, bad))
         return rc;
     const KernelArgs a = make_args(ctx, 0, ctx->views_n, LFI_METHOD_STD);
     const uint8_t *d_head = nullptr;
@@ -972,7 +961,7 @@ int lfi_focus_tiles_steps(lfi_ctx *ctx, int tiles_x, int tiles_y, int steps, uin
         return rc;
     // per tile the curve and the result lie back to back: one copy of tiles · (steps · 8 + 16) bytes
     const size_t tiles = size_t(tiles_x) * size_t(tiles_y);
-    const size_t words = focus_tile_head(steps) / sizeof(uint64_t);
+    const size_t words = focus_curve_head(steps) / sizeof(uint64_t);
     std::vector<uint64_t> head(tiles * words);
     LFI_HIP(ctx, hipMemcpyAsync(head.data(), d_head, sizeof(uint64_t) * words * tiles, hipMemcpyDeviceToHost, ctx->stream));
     LFI_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -1027,29 +1016,19 @@ int lfi_view_focus_maps(lfi_ctx *ctx, const int32_t *focus_ids_vk, int views, in
 {
     if(!ctx)
         return LFI_EINVAL;
-    if(ctx->inputs_released)
-        return fail(ctx, LFI_EINVAL, "the RGBA inputs were released (lfi_release_inputs): the focus maps need them - upload the images again (lfi_set_grid)");
-    if(!ctx->grid || !ctx->have_params)
-        return fail(ctx, LFI_EINVAL, "lfi_set_grid / lfi_set_params have not been called");
+    std::string bad;
     if(!ctx->view_float_offsets.set)
-        return fail(ctx, LFI_EINVAL, "lfi_view_focus_maps: no per-view float offsets (lfi_set_view_float_offsets)");
-    if(views != ctx->views_n)
-        return fail(ctx, LFI_EINVAL, "lfi_view_focus_maps: views (" + std::to_string(views) + ") differs from lfi_params.views (" +
-                                         std::to_string(ctx->views_n) + ")");
-    if(n_ids < 1 || n_ids > LFI_MAX_FOCUS_IDS || !focus_ids_vk)
-        return fail(ctx, LFI_EINVAL, "lfi_view_focus_maps: n_ids must be in [1, LFI_MAX_FOCUS_IDS] and focus_ids_vk non-NULL");
-    for(size_t i = 0; i < (size_t)views * n_ids; i++)
+        bad = "lfi_view_focus_maps: no per-view float offsets (lfi_set_view_float_offsets)";
+    else if(views != ctx->views_n)
+        bad = "lfi_view_focus_maps: views (" + std::to_string(views) + ") differs from lfi_params.views (" + std::to_string(ctx->views_n) + ")";
+    else if(n_ids < 1 || n_ids > LFI_MAX_FOCUS_IDS || !focus_ids_vk)
+        bad = "lfi_view_focus_maps: n_ids must be in [1, LFI_MAX_FOCUS_IDS] and focus_ids_vk non-NULL";
+    for(size_t i = 0; bad.empty() && i < (size_t)views * n_ids; i++)
         if(focus_ids_vk[i] < 0 || focus_ids_vk[i] >= ctx->n)
-            return fail(ctx, LFI_EINVAL, "lfi_view_focus_maps: id outside the grid in view " + std::to_string(i / n_ids));
-    if(!(ctx->range > 0.0f))
-        return fail(ctx, LFI_EINVAL, "focus range must be > 0 for the focus map");
-    if(ctx->windowed)
-        return fail(ctx, LFI_EINVAL, "lfi_view_focus_maps: per-view focus maps are not supported with a row window");
-    if(ctx->width > 65535 || ctx->height > 65535)
-        return fail(ctx, LFI_EINVAL, "lfi_view_focus_maps: image too large for the factored estimate");
-    if(int rc = bind(ctx))
-        return rc;
-    if(int rc = join_uploads(ctx))
+            bad = "lfi_view_focus_maps: id outside the grid in view " + std::to_string(i / n_ids);
+    if(bad.empty() && (ctx->width > 65535 || ctx->height > 65535))
+        bad = "lfi_view_focus_maps: image too large for the factored estimate";
+    if(int rc = focus_entry(ctx, "lfi_view_focus_maps", "focus maps", false, bad, false))
         return rc;
     if(int rc = join_filter(ctx)) // the centre map's filter shares the side stream
         return rc;
