@@ -395,7 +395,7 @@ typedef struct lfi_memory {
     size_t maps_bytes;      /* focus maps (maps 0 / 1, and the per-view maps when allocated) */
     size_t workspace_bytes; /* focus-map workspace + lfi_focus_curve's / lfi_focus_tiles' curves and partial sums + (planar view layout) the RGBA scratch copy of the views that renders other than TEN_WM and
                              * STD on more than 64 images go through, and the one-plane staging buffer of downloads + the kept views (lfi_keep_views) and
-                             * lfi_compare_views' staging buffers and partial sums */
+                             * lfi_compare_views' staging buffers and partial sums + lfi_download_native's device image */
     float derived_build_ms;
 } lfi_memory;
 int lfi_memory_info(lfi_ctx *ctx, lfi_memory *out);
@@ -456,6 +456,34 @@ int lfi_download_quilt_scaled(lfi_ctx *ctx, int tiles_x, int tiles_y, int v0, in
 /* … and for PART of such a quilt, as lfi_download_quilt_tiles: views v0 … v0+n-1 become tiles first_tile … first_tile+n-1, one kernel launch
  * for all n tiles (both view layouts are read as they are), at most three rectangles copied. */
 int lfi_download_quilt_tiles_scaled(lfi_ctx *ctx, int tiles_x, int tiles_y, int first_tile, int n, int v0, int tile_w, int tile_h, uint8_t *rgba, size_t pitch_bytes);
+/* The NATIVE image of a lenticular (Looking-Glass-type) display, interlaced on the device: one picture of out_w × out_h pixels in which
+ * every SUBPIXEL takes its value from the one view that its position under the slanted lens sheet selects — what such a panel shows; a
+ * quilt is only the intermediate a host-side interlace would start from.  The lens sheet is given in fixed point: a phase is a u32 in
+ * units of 2^-32 lens periods, so the wrap of u32 arithmetic IS the fract() of the usual shader. */
+typedef struct lfi_lenticular {
+    uint32_t x_step;   /* phase advance per SUBPIXEL along x, in units of 2^-32 lens periods */
+    uint32_t y_step;   /* phase advance per pixel row (two's complement: a negative slant wraps) */
+    uint32_t phase0;   /* phase of subpixel 0 of pixel (0, 0) */
+    int32_t  views;    /* n: the views v0 … v0+n-1 spread over one lens period, 1 ≤ n */
+    uint32_t flags;    /* LFI_LENT_INVERT: view n-1-k where the phase selects k */
+} lfi_lenticular;
+#define LFI_LENT_INVERT 1u
+/* For output pixel (x, y) and colour channel c ∈ {0: R, 1: G, 2: B} (RGB subpixel order), all in unsigned integers:
+ *     phase = phase0 + (3·x + c)·x_step + y·y_step                       (mod 2^32)
+ *     k     = (u64(phase) · n) >> 32;   with LFI_LENT_INVERT  k = n − 1 − k
+ *     sx    = ((2·x + 1)·tile_w) / (2·out_w),   sy = ((2·y + 1)·tile_h) / (2·out_h)        (integer division)
+ *     out[y][x][c] = T_{v0+k}[sy][sx][c],   alpha = 255
+ * (sx, sy) is the tile pixel under the output pixel's centre (nearest; no filter), and T_v is view v resized to tile_w × tile_h by the
+ * exact area filter of lfi_download_quilt_scaled — with tile = W × H the view itself, read in place in either view layout.  The output may
+ * be smaller than, equal to or larger than the tile: 1 ≤ out_w, out_h ≤ 65535; the tile obeys lfi_download_quilt_scaled's limits.  With
+ * all sizes at most 65535 the kernel computes sx as q + (2·r + tile_w) / (2·out_w) with q, r = quotient and remainder of x·tile_w by
+ * out_w: every intermediate is below 2^32 (x·tile_w < 65535², 2·r + tile_w < 3·65535), so 32 bits suffice; sy likewise.
+ * The scaled tiles and the native image are made on the device (the tiles never leave it); only out_w·out_h·4 bytes are copied, as one
+ * rectangle.  rgba: out_h rows of pitch_bytes ≥ out_w·4.  Synchronous.  Attached views work as they do for quilts.
+ * LFI_EINVAL, the context usable and the host image untouched: what lfi_download_quilt_scaled refuses for a tile (a row window among it),
+ * lens NULL, n < 1 or v0 + n beyond the rendered views, unknown flag bits, an output size outside the limits, a NULL image or a pitch below
+ * out_w·4.  (A display calibration becomes an lfi_lenticular on the host: csrc/host/lenticular.h.) */
+int lfi_download_native(lfi_ctx *ctx, const lfi_lenticular *lens, int v0, int out_w, int out_h, int tile_w, int tile_h, uint8_t *rgba, size_t pitch_bytes);
 int lfi_upload_map(lfi_ctx *ctx, int k, const uint8_t *rgba, size_t pitch_bytes); /* tests: inject a focus map */
 /* view v's map k (0 or 1) of the per-view maps (lfi_view_focus_maps).  Synchronous.  The upload is a test hook like lfi_upload_map (it
  * allocates the per-view maps if needed and does not put them in use: renders read them after a successful lfi_view_focus_maps). */
@@ -556,7 +584,7 @@ int lfi_debug_mfma_f16_chain(lfi_ctx *ctx, int shape, int k, const uint16_t *a_3
  * rebuilt in full by their next user (the estimate's padded planes; the planar copy, as after lfi_grid_modified).
  *   VIEWS            the views in the current layout (attached ones too)
  *   SCRATCH          the planar layout's RGBA scratch copy of the views, the download staging plane, the pre-quantisation buffer, the
- *                    quilt buffer, lfi_render_stream's second set of views and lfi_compare_views' staging buffers, partial sums and per-view records
+ *                    quilt buffer (lfi_download_native's scaled tiles too) and its native image, lfi_render_stream's second set of views and lfi_compare_views' staging buffers, partial sums and per-view records
  *                    (not the kept views: they are data)
  *   MAPS             both focus maps
  *   FOCUS_WORKSPACE  all of the focus-map estimate's workspace, and lfi_focus_curve's / lfi_focus_tiles' (the curves, the results and the partial sums)

@@ -24,6 +24,7 @@ LFI_POISON_MAPS = 4
 LFI_POISON_FOCUS_WORKSPACE = 8
 LFI_POISON_DERIVED = 16
 LFI_POISON_VIEW_MAPS = 32
+LFI_LENT_INVERT = 1
 METHODS = {"STD": LFI_METHOD_STD, "TEN_WM": LFI_METHOD_TEN_WM, "FOCUS": LFI_KERNEL_FOCUS_ESTIMATE}
 
 # every symbol include/lfi.h declares
@@ -36,7 +37,7 @@ ABI_SYMBOLS = [
     "lfi_grid_modified", "lfi_prepare", "lfi_memory_info", "lfi_last_kernel_name", "lfi_fill_synthetic_images", "lfi_set_output_layout", "lfi_view_layout", "lfi_fill_synthetic_scene", "lfi_upload_image_async", "lfi_upload_wait", "lfi_render_stream", "lfi_compare_view", "lfi_debug_mfma_f16_chain", "lfi_debug_pk_minmax3_f16", "lfi_std_band_info",
     "lfi_debug_poison", "lfi_set_view_offsets", "lfi_set_view_float_offsets", "lfi_view_focus_maps", "lfi_download_view_map",
     "lfi_upload_view_map", "lfi_focus_curve", "lfi_focus_tiles", "lfi_focus_tiles_steps", "lfi_focus_tiles_passes", "lfi_download_quilt_scaled", "lfi_download_quilt_tiles_scaled",
-    "lfi_keep_views", "lfi_compare_views", "lfi_set_focus_steps", "lfi_focus_steps",
+    "lfi_keep_views", "lfi_compare_views", "lfi_set_focus_steps", "lfi_focus_steps", "lfi_download_native",
 ]
 
 
@@ -81,6 +82,11 @@ class StdBandInfo(C.Structure):
 
 class FocusCurveResult(C.Structure):
     _fields_ = [("best_index", C.c_int32), ("best_focus", C.c_float), ("pixels", C.c_uint64)]
+
+
+class Lenticular(C.Structure):
+    """lfi_lenticular: the lens sheet of lfi_download_native in units of 2^-32 lens periods (host.lenticular builds one from a calibration)"""
+    _fields_ = [("x_step", C.c_uint32), ("y_step", C.c_uint32), ("phase0", C.c_uint32), ("views", C.c_int32), ("flags", C.c_uint32)]
 
 
 class MemoryInfo(C.Structure):
@@ -149,6 +155,7 @@ def load_hip_library() -> C.CDLL:
         "lfi_download_quilt_tiles": (i, [vp, i, i, i, i, i, vp, sz]),
         "lfi_download_quilt_scaled": (i, [vp, i, i, i, i, i, vp, sz]),
         "lfi_download_quilt_tiles_scaled": (i, [vp, i, i, i, i, i, i, i, vp, sz]),
+        "lfi_download_native": (i, [vp, C.POINTER(Lenticular), i, i, i, i, i, vp, sz]),
         "lfi_alloc_pinned": (i, [sz, C.POINTER(vp)]),
         "lfi_free_pinned": (i, [vp]),
         "lfi_grid_modified": (i, [vp]),
@@ -561,6 +568,20 @@ class Context:
             out = np.full((tiles_y * max(tile_h, 0), tiles_x * max(tile_w, 0), 4), 0xC3, dtype=np.uint8)   # a sentinel, not zeros: every byte is written
         assert out.dtype == np.uint8 and out.ndim == 3 and out.shape[0] == tiles_y * tile_h and out.shape[2] == 4 and (out.size == 0 or out.strides[1:] == (4, 1))
         self._check(self._lib.lfi_download_quilt_scaled(self._h, tiles_x, tiles_y, v0, tile_w, tile_h, _ptr(out), out.strides[0]))
+        return out
+
+    def download_native(self, lens: "Lenticular | None", out_w: int, out_h: int, tile_w: int | None = None, tile_h: int | None = None, v0: int = 0,
+                        out: np.ndarray | None = None) -> np.ndarray:
+        """the native image of a lenticular display, out_w × out_h pixels, interlaced on the device from views v0 … v0+lens.views-1, each resized
+        to tile_w × tile_h first (default: the views' size, read in place); `out`: (out_h, P, 4) uint8 with rows of P ≥ out_w pixels — the row
+        pitch is out's; by default a new (out_h, out_w, 4) array"""
+        tile_w = self.width if tile_w is None else tile_w
+        tile_h = self.height if tile_h is None else tile_h
+        if out is None:
+            out = np.full((max(out_h, 0), max(out_w, 0), 4), 0xC3, dtype=np.uint8)   # a sentinel, not zeros: every byte is written
+        assert out.dtype == np.uint8 and out.ndim == 3 and out.shape[0] == out_h and out.shape[2] == 4 and (out.size == 0 or out.strides[1:] == (4, 1))
+        self._check(self._lib.lfi_download_native(self._h, C.byref(lens) if lens is not None else None, v0, out_w, out_h, tile_w, tile_h, _ptr(out),
+                                                  out.strides[0] if out.size else 0))
         return out
 
     def download_map(self, k: int) -> np.ndarray:

@@ -284,7 +284,8 @@ struct lfi_ctx
     int out_layout = LFI_LAYOUT_RGBA; // device layout of the views (lfi_set_output_layout)
     DeviceBuffer rgba_scratch;        // planar layout: RGBA planes of all views for the kernels that only write RGBA (converted after the launch)
     DeviceBuffer dl_plane;            // planar layout: one RGBA plane that downloads expand a view into
-    DeviceBuffer quilt;               // lfi_download_quilt[_tiles]: the quilt's rows of tiles as one RGBA image (grows, kept)
+    DeviceBuffer quilt;               // lfi_download_quilt[_tiles]: the quilt's rows of tiles as one RGBA image (grows, kept); lfi_download_native: its scaled tiles
+    DeviceBuffer native;              // lfi_download_native: the native image, out_h × out_w dwords (grows, kept)
     // parameter block
     bool have_params = false;
     int views_n = 0, k_pad = 0, v_pad = 0, n_focus_ids = 0;
@@ -692,6 +693,7 @@ void free_views(lfi_ctx *c)
     c->rgba_scratch.release();
     c->dl_plane.release();
     c->quilt.release();
+    c->native.release();
     c->views2.release();
     c->quality_ref.release();
     c->cmp_stage[0].release();

@@ -9,6 +9,7 @@
 #include "lfi_dispatch.hpp"
 #include "lfi_focus_sched.hpp"
 #include "quilt_scaled.hpp"
+#include "native_image.hpp"
 #include "lfi_rccl.hpp"
 
 extern "C" {
@@ -1207,7 +1208,7 @@ int lfi_memory_info(lfi_ctx *ctx, lfi_memory *out)
     out->views_bytes = ctx->views.bytes();
     out->maps_bytes = (ctx->maps ? plane_bytes(ctx) * 2 : 0) + ctx->view_maps.bytes();
     out->workspace_bytes = ctx->focus_ws.bytes() + ctx->curve_ws.bytes() + ctx->rgba_scratch.bytes() + ctx->dl_plane.bytes() + ctx->kept.bytes() +
-                           ctx->cmp_stage[0].bytes() + ctx->cmp_stage[1].bytes() + ctx->cmp_ws.bytes();
+                           ctx->cmp_stage[0].bytes() + ctx->cmp_stage[1].bytes() + ctx->cmp_ws.bytes() + ctx->native.bytes();
     out->derived_build_ms = ctx->derived_build_ms;
     return LFI_OK;
 }
@@ -1805,6 +1806,69 @@ int lfi_download_quilt_scaled(lfi_ctx *ctx, int tiles_x, int tiles_y, int v0, in
     return lfi_download_quilt_tiles_scaled(ctx, tiles_x, tiles_y, 0, tiles_x * tiles_y, v0, tile_w, tile_h, rgba, pitch_bytes);
 }
 
+int lfi_download_native(lfi_ctx *ctx, const lfi_lenticular *lens, int v0, int out_w, int out_h, int tile_w, int tile_h, uint8_t *rgba, size_t pitch_bytes)
+{
+    if(!ctx)
+        return LFI_EINVAL;
+    if(!ctx->views || !ctx->have_params)
+        return fail(ctx, LFI_EINVAL, "nothing rendered yet");
+    if(ctx->windowed)
+        return fail(ctx, LFI_EINVAL, "a native image needs whole views: its subpixels read rows the row window's band does not hold");
+    if(!lens)
+        return fail(ctx, LFI_EINVAL, "a native image needs a lens description (lfi_lenticular)");
+    if(lens->flags & ~uint32_t(LFI_LENT_INVERT))
+        return fail(ctx, LFI_EINVAL, "unknown lfi_lenticular flag bits");
+    if(lens->views < 1 || v0 < 0 || (long)v0 + lens->views > ctx->views_n)
+        return fail(ctx, LFI_EINVAL, "a native image needs lens views >= 1 and as many views starting at v0 inside [0, views)");
+    const int W = ctx->width, H = ctx->height;
+    if(tile_w < 1 || tile_w > W || tile_h < 1 || tile_h > H)
+        return fail(ctx, LFI_EINVAL, "scaled quilt tiles are 1 … width by 1 … height pixels (downscaling or identity only)");
+    if((uint32_t)W > lfi::LFI_AREA_SPAN_MAX || (uint32_t)H > lfi::LFI_AREA_SPAN_MAX)
+        return fail(ctx, LFI_EINVAL, "scaled quilts take views of up to 65535 pixels per axis");
+    if(out_w < 1 || out_h < 1 || (uint32_t)out_w > lfi::NATIVE_MAX || (uint32_t)out_h > lfi::NATIVE_MAX)
+        return fail(ctx, LFI_EINVAL, "native images are 1 … 65535 pixels per axis");
+    if(!rgba || pitch_bytes < (size_t)out_w * 4)
+        return fail(ctx, LFI_EINVAL, "bad native image pointer or pitch");
+    if(int rc = bind(ctx))
+        return rc;
+    const int n = lens->views;
+    const bool planar = ctx->out_layout == LFI_LAYOUT_PLANAR_RGB, scaled = tile_w != W || tile_h != H;
+    LFI_HIP(ctx, ctx->native.reserve((size_t)out_w * out_h * 4));
+    lfi::NativeArgs a{};
+    a.out = ctx->native.as<uint32_t>();
+    a.W = tile_w, a.H = tile_h;
+    a.out_w = out_w, a.out_h = out_h;
+    a.x_step = lens->x_step, a.y_step = lens->y_step, a.phase0 = lens->phase0, a.n = n;
+    a.invert = (lens->flags & LFI_LENT_INVERT) ? 1u : 0u;
+    if(scaled)
+    {
+        // stage 1: the n scaled tiles as a quilt ONE tile wide in the quilt buffer — RGBA planes [view][tile_h][tile_w]; none of it is copied
+        const size_t tile_bytes = (size_t)tile_w * tile_h * 4;
+        LFI_HIP(ctx, ctx->quilt.reserve(tile_bytes * n));
+        lfi::QuiltScaleArgs q{};
+        q.views = ctx->views.get();
+        q.quilt = ctx->quilt.as<uint32_t>();
+        q.view_stride = out_plane_bytes(ctx);
+        q.W = W, q.H = H, q.pitch = planar ? view_pitch(ctx) : 0;
+        q.tile_w = tile_w, q.tile_h = tile_h;
+        q.v0 = v0, q.first = 0, q.tiles_x = 1;
+        LFI_HIP(ctx, lfi::launch_quilt_scale(ctx->stream, planar, q, n));
+        a.src = ctx->quilt.get();
+        a.view_stride = tile_bytes;
+    }
+    else
+    {
+        // the views in place, in the layout they were rendered in
+        a.src = ctx->views.get() + (size_t)v0 * out_plane_bytes(ctx);
+        a.view_stride = out_plane_bytes(ctx);
+        a.pitch = planar ? view_pitch(ctx) : 0;
+    }
+    LFI_HIP(ctx, lfi::launch_native_interlace(ctx->stream, planar && !scaled, a));
+    LFI_HIP(ctx, hipMemcpy2DAsync(rgba, pitch_bytes, ctx->native.get(), (size_t)out_w * 4, (size_t)out_w * 4, out_h, hipMemcpyDeviceToHost, ctx->stream));
+    LFI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return LFI_OK;
+}
+
 int lfi_alloc_pinned(size_t bytes, void **out_ptr)
 {
     if(!out_ptr || bytes == 0)
@@ -2052,6 +2116,7 @@ int lfi_debug_poison(lfi_ctx *ctx, uint32_t what, uint8_t byte)
         rc = rc ? rc : fill(ctx->dl_plane, ctx->dl_plane.bytes());
         rc = rc ? rc : fill(ctx->prequant, ctx->prequant.bytes());
         rc = rc ? rc : fill(ctx->quilt, ctx->quilt.bytes());
+        rc = rc ? rc : fill(ctx->native, ctx->native.bytes());
         rc = rc ? rc : fill(ctx->views2, ctx->views2.bytes());
         rc = rc ? rc : fill(ctx->cmp_stage[0], ctx->cmp_stage[0].bytes());
         rc = rc ? rc : fill(ctx->cmp_stage[1], ctx->cmp_stage[1].bytes());

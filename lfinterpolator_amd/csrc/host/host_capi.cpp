@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "../area_span.h"
+#include "lenticular.h"
 #include "params.h"
 
 namespace {
@@ -94,6 +95,26 @@ int lfi_host_area_span(int src, int dst, int o, int32_t out[4])
     out[2] = static_cast<int32_t>(s.w_first);
     out[3] = static_cast<int32_t>(s.w_last);
     return 0;
+}
+
+// a lenticular display's calibration as the lens description of lfi_download_native (lenticular.h): pitch, slope, center, dpi and invert for
+// an output of out_w × out_h pixels interlacing n views; returns 0 or -1 (message in err)
+int lfi_host_lenticular(double pitch, double slope, double center, double dpi, int invert, int out_w, int out_h, int n, lfi_lenticular *out, char *err,
+                        size_t err_len)
+{
+    try
+    {
+        if(!out)
+            throw std::runtime_error("out must be non-NULL");
+        lfi::LensCalibration c;
+        c.pitch = pitch, c.slope = slope, c.center = center, c.dpi = dpi, c.invert = invert != 0;
+        *out = lfi::lenticularFromCalibration(c, out_w, out_h, n);
+        return 0;
+    }
+    catch(const std::exception &e)
+    {
+        return report(e, err, err_len);
+    }
 }
 
 // the interval an all-focus render should search, from the tiles' best candidates of a search over [focus, focus + range] (--auto-range):

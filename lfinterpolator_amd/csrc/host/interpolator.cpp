@@ -132,6 +132,21 @@ void Interpolator::interpolate(std::string outputPath, std::string trajectory, f
             throw std::runtime_error("The quilt tile size has to be between 1x1 and the views' " + std::to_string(resolution.x) + "x" + std::to_string(resolution.y) +
                                      " pixels (views are only scaled down)!");
     }
+    if(nativeSize.x != 0 || nativeSize.y != 0)
+    {
+        if(gpuCount > 1)
+            throw std::runtime_error("A native image needs every view in one context: it works on one GPU only!");
+        if(nativeSize.x < 1 || nativeSize.y < 1 || nativeSize.x > 65535 || nativeSize.y > 65535)
+            throw std::runtime_error("The native image size has to be between 1x1 and 65535x65535 pixels!");
+        if(nativeTile.x != 0 || nativeTile.y != 0)
+            if(nativeTile.x < 1 || nativeTile.y < 1 || nativeTile.x > resolution.x || nativeTile.y > resolution.y)
+                throw std::runtime_error("The native tile size has to be between 1x1 and the views' " + std::to_string(resolution.x) + "x" + std::to_string(resolution.y) +
+                                         " pixels (views are only scaled down)!");
+        if(nativeViews < 0 || nativeViews > viewCount)
+            throw std::runtime_error("The native image cannot interlace more views than are rendered!");
+        // the calibration is checked before anything is rendered
+        (void)lfi::lenticularFromCalibration(nativeLens, nativeSize.x, nativeSize.y, nativeViews > 0 ? nativeViews : viewCount);
+    }
 
     lfi::Parameterizer parameterizer(colsRows, resolution);
     // the minima of a grid of focus tiles over the search interval [inFocus, inFocus + inRange], on the first GPU
@@ -489,5 +504,16 @@ void Interpolator::storeResults(std::string path)
         }
         lfi::writePng((std::filesystem::path(path) / "quilt.png").string(), tile.x * quiltTiles.x, tile.y * quiltTiles.y, static_cast<int>(channels), quilt.data(),
                       quiltPitch);
+    }
+    if(nativeSize.x > 0 && nativeSize.y > 0)
+    {
+        std::cout << "Storing native image..." << std::endl;
+        // interlaced on the device (lfi_download_native): only the display's own pixels are copied
+        const lfi::IVec2 tile = nativeTile.x > 0 ? nativeTile : lfi::IVec2{resolution.x, resolution.y};
+        const lfi_lenticular lens = lfi::lenticularFromCalibration(nativeLens, nativeSize.x, nativeSize.y, nativeViews > 0 ? nativeViews : viewCount);
+        const size_t nativePitch = static_cast<size_t>(nativeSize.x) * channels;
+        std::vector<uint8_t> native(nativePitch * nativeSize.y);
+        check(lfi_download_native(context, &lens, 0, nativeSize.x, nativeSize.y, tile.x, tile.y, native.data(), nativePitch));
+        lfi::writePng((std::filesystem::path(path) / "native.png").string(), nativeSize.x, nativeSize.y, static_cast<int>(channels), native.data(), nativePitch);
     }
 }

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../../include/lfi.h"
+#include "lenticular.h"
 #include "params.h"
 #include "vec.h"
 
@@ -30,6 +31,16 @@ class Interpolator
         // … with every view resized to a tile of width × height pixels on the device first (lfi_download_quilt_tiles_scaled: an exact area
         // filter, at most the views' size) — montage's -geometry; needs setQuilt
         void setQuiltTile(lfi::IVec2 size) { quiltTile = size; }
+        // also write native.png: the native image of a lenticular display of width × height pixels whose lens sheet the calibration
+        // describes (lenticular.h), interlaced on the device from the first `views` views (0: all of them), each resized to a tile of
+        // tile.x × tile.y pixels first (0: the views' size, read in place) — lfi_download_native.  One GPU: every view in one context
+        void setNative(lfi::IVec2 size, lfi::LensCalibration lens, lfi::IVec2 tile = {0, 0}, int views = 0)
+        {
+            nativeSize = size;
+            nativeLens = lens;
+            nativeTile = tile;
+            nativeViews = views;
+        }
         float lastAverageTime() const { return averageTime; }
         // render on GPUs 0 … count-1 of this node: views are split into contiguous ranges, the grid is broadcast once (RCCL)
         void setGpuCount(int count) { gpuCount = count; }
@@ -86,6 +97,10 @@ class Interpolator
         bool unifiedFocusMap{false};
         lfi::IVec2 quiltTiles{0, 0};
         lfi::IVec2 quiltTile{0, 0}; // 0: the views' size, unscaled
+        lfi::IVec2 nativeSize{0, 0}; // 0: no native image
+        lfi::LensCalibration nativeLens;
+        lfi::IVec2 nativeTile{0, 0}; // 0: the views' size, read in place
+        int nativeViews{0};          // 0: all views
         lfi_ctx *context{nullptr};
         int gpuCount{1};
         bool perViewFocus{false};

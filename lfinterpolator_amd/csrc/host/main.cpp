@@ -2,7 +2,8 @@
 // (-i -t -o -f -r -m -s -a -h), plus -n (views), -b (benchmark runs), -d (device), -F (focus at the last view), -c (shifts about each
 // view's own camera), --autofocus (the focus found from a region's focus curve), --focus-tiles / --auto-range (the focus of every tile of a
 // grid; the search interval of an all-focus render found from it), --map-steps / --tile-steps (more than 32 candidates for the focus map / the focus tiles), --compare / --compare-methods (PSNR / SSIM of all views against a
-// directory of images or against the other method's render) and --synthetic for runs without a dataset.
+// directory of images or against the other method's render), --native / --lens / --native-tile / --native-views (the native image of a
+// lenticular display, interlaced on the GPU) and --synthetic for runs without a dataset.
 #include <array>
 #include <iostream>
 #include <memory>
@@ -51,6 +52,10 @@ int main(int argc, char **argv)
                           "-g - number of GPUs: the views are split over GPUs d … d+g-1, the input grid is broadcast once (default=1)\n"
                           "-q - also store quilt.png: the first cols*rows views as cols,rows tiles (e.g. 5,9 for a Looking Glass quilt)\n"
                           "--quilt-tile WxH - with -q: resize every view to a tile of W x H pixels on the GPU before quilt.png is stored (an exact area filter; downscaling only, at most the views' size), e.g. -q 5,9 --quilt-tile 819x455 for a 4096 x 4096 quilt\n"
+                          "--native WxH - also store native.png: the native image of a lenticular (Looking-Glass-type) display of W x H pixels, interlaced on the GPU - every subpixel (RGB order) takes its value from the one view its position under the lens sheet selects; needs --lens; one GPU\n"
+                          "--lens pitch,slope,center,dpi[,invert] - with --native: the display's calibration - lenses per inch, the slant, the phase offset in lens periods, the panel's pixels per inch, and 1 to reverse the order of the views (default 0)\n"
+                          "--native-tile WxH - with --native: resize every view to a tile of W x H pixels on the GPU first (the exact area filter of --quilt-tile; at most the views' size; default: the views' size, read in place)\n"
+                          "--native-views N - with --native: interlace the first N views (default: all of them)\n"
                           "--compare DIR - after the render, compare every view with DIR/NN.png (the names -o writes; same size) on the GPU, all views in one pass: prints \"compare NN psnr <dB> ssim <index> maxdiff <largest byte difference> differing <colour bytes that differ>\" per view, then \"compare all psnr ... ssim ...\"; one GPU\n"
                           "--compare-methods - render the views with the other method first (STD if -m TEN_WM, TEN_WM if -m STD; same parameters), keep them on the GPU, render with -m and compare the two there; prints the lines of --compare; the stored images are those of -m; one GPU; not with --compare\n"
                           "--synthetic cols,rows,width,height[,seed] - use a generated light field instead of -i\n"
@@ -142,6 +147,24 @@ int main(int argc, char **argv)
     if(args["--quilt-tile"] && !args["-q"])
     {
         std::cerr << "--quilt-tile sets the tile size of the quilt: it needs -q cols,rows." << std::endl;
+        return EXIT_FAILURE;
+    }
+
+    if(static_cast<bool>(args["--native"]) != static_cast<bool>(args["--lens"]))
+    {
+        std::cerr << "--native (the display's size) and --lens (its calibration) describe one display: give both." << std::endl;
+        return EXIT_FAILURE;
+    }
+
+    if((args["--native-tile"] || args["--native-views"]) && !args["--native"])
+    {
+        std::cerr << "--native-tile and --native-views belong to the native image: they need --native WxH." << std::endl;
+        return EXIT_FAILURE;
+    }
+
+    if(args["--native"] && args["-g"] && static_cast<int>(args["-g"]) > 1)
+    {
+        std::cerr << "--native needs every view in one context: it works on one GPU only (-g 1)." << std::endl;
         return EXIT_FAILURE;
     }
 
@@ -268,6 +291,36 @@ int main(int argc, char **argv)
         }
         if(args["--quilt-tile"])
             interpolator->setQuiltTile(tileGrid(static_cast<std::string>(args["--quilt-tile"]), "--quilt-tile", "WxH, the tile's width x height in pixels, both at least 1"));
+        if(args["--native"])
+        {
+            std::stringstream spec(static_cast<std::string>(args["--lens"]));
+            std::string token;
+            std::vector<double> numbers;
+            try
+            {
+                while(std::getline(spec, token, ','))
+                    numbers.push_back(std::stod(token));
+            }
+            catch(const std::exception &)
+            {
+                numbers.clear();
+            }
+            if(numbers.size() < 4 || numbers.size() > 5 || (numbers.size() == 5 && numbers[4] != 0.0 && numbers[4] != 1.0))
+                throw std::runtime_error("--lens expects pitch,slope,center,dpi[,invert] with invert 0 or 1");
+            lfi::LensCalibration lens;
+            lens.pitch = numbers[0], lens.slope = numbers[1], lens.center = numbers[2], lens.dpi = numbers[3];
+            lens.invert = numbers.size() == 5 && numbers[4] == 1.0;
+            int views = 0;
+            if(args["--native-views"])
+            {
+                views = static_cast<int>(args["--native-views"]);
+                if(views < 1)
+                    throw std::runtime_error("--native-views expects the number of views to interlace, at least 1");
+            }
+            const char *size = "WxH, width x height in pixels, both at least 1";
+            interpolator->setNative(tileGrid(static_cast<std::string>(args["--native"]), "--native", size), lens,
+                                    args["--native-tile"] ? tileGrid(static_cast<std::string>(args["--native-tile"]), "--native-tile", size) : lfi::IVec2{0, 0}, views);
+        }
         if(args["--compare"])
             interpolator->setCompareDir(static_cast<std::string>(args["--compare"]));
         if(args["--compare-methods"])

@@ -7,6 +7,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
+from .abi import LFI_LENT_INVERT, Lenticular
 from .build import HOST_LIB
 
 _lib = None
@@ -36,6 +37,8 @@ def load_host_library() -> C.CDLL:
                                                         C.c_void_p]
         lib.lfi_host_area_span.restype = C.c_int
         lib.lfi_host_area_span.argtypes = [C.c_int] * 3 + [C.c_void_p]
+        lib.lfi_host_lenticular.restype = C.c_int
+        lib.lfi_host_lenticular.argtypes = [C.c_double] * 4 + [C.c_int] * 4 + [C.POINTER(Lenticular), C.c_char_p, C.c_size_t]
         lib.lfi_host_build_view_offsets.restype = C.c_int
         lib.lfi_host_build_view_offsets.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_float, C.c_void_p, C.c_int,
                                                     C.c_void_p, C.c_char_p, C.c_size_t]
@@ -146,6 +149,17 @@ def area_span(src: int, dst: int, o: int):
     if load_host_library().lfi_host_area_span(src, dst, o, out.ctypes.data) != 0:
         raise ValueError("needs 1 <= dst <= src <= 65535 and 0 <= o < dst")
     return tuple(int(v) for v in out)
+
+
+def lenticular(pitch: float, slope: float, center: float, dpi: float, invert: bool, out_w: int, out_h: int, n: int) -> Lenticular:
+    """A lenticular display's calibration (lenses per inch, slant, phase offset in lens periods, pixels per inch, reversed view order) as the
+    Lenticular Context.download_native takes, for an out_w × out_h image interlacing n views (csrc/host/lenticular.h: doubles, +, −, ×, ÷ and sqrt)."""
+    lens = Lenticular()
+    err = C.create_string_buffer(512)
+    if load_host_library().lfi_host_lenticular(pitch, slope, center, dpi, int(bool(invert)), out_w, out_h, n, C.byref(lens), err, len(err)) != 0:
+        raise ValueError(err.value.decode())
+    assert lens.flags == (LFI_LENT_INVERT if invert else 0)
+    return lens
 
 
 def build_view_offsets(cols: int, rows: int, width: int, height: int, trajectory: str, aspect: float, focus_v) -> np.ndarray:
