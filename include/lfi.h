@@ -395,7 +395,8 @@ typedef struct lfi_memory {
     size_t maps_bytes;      /* focus maps (maps 0 / 1, and the per-view maps when allocated) */
     size_t workspace_bytes; /* focus-map workspace + lfi_focus_curve's / lfi_focus_tiles' curves and partial sums + (planar view layout) the RGBA scratch copy of the views that renders other than TEN_WM and
                              * STD on more than 64 images go through, and the one-plane staging buffer of downloads + the kept views (lfi_keep_views) and
-                             * lfi_compare_views' staging buffers and partial sums + lfi_download_native's device image */
+                             * lfi_compare_views' staging buffers and partial sums + lfi_download_native's device image + the device frames of
+                             * lfi_download_views_yuv420 / lfi_render_stream_yuv420 */
     float derived_build_ms;
 } lfi_memory;
 int lfi_memory_info(lfi_ctx *ctx, lfi_memory *out);
@@ -484,6 +485,40 @@ typedef struct lfi_lenticular {
  * lens NULL, n < 1 or v0 + n beyond the rendered views, unknown flag bits, an output size outside the limits, a NULL image or a pitch below
  * out_w·4.  (A display calibration becomes an lfi_lenticular on the host: csrc/host/lenticular.h.) */
 int lfi_download_native(lfi_ctx *ctx, const lfi_lenticular *lens, int v0, int out_w, int out_h, int tile_w, int tile_h, uint8_t *rgba, size_t pitch_bytes);
+/* Views as 8-bit YUV 4:2:0 video frames (I420), converted on the device before the copy: what every encoder and player takes, 1.5 bytes per
+ * pixel instead of the 4 of lfi_download_view (the alpha dropped is the constant 255, the chroma dropped is what an encoder's first step
+ * would drop).  A frame of a W x H view is the Y plane [H][W], then Cb [ch][cw], then Cr [ch][cw], cw = (W + 1) >> 1, ch = (H + 1) >> 1,
+ * tightly packed: frame_bytes = W*H + 2*cw*ch.  matrix and range select one of four coefficient sets in 16-bit fixed point:
+ *                   Y (R, G, B)           Cb (R, G, B)             Cr (R, G, B)            y_off
+ *   709 limited   11966, 40254, 4064    -6596, -22188, 28784     28784, -26145, -2639      16
+ *   709 full      13933, 46871, 4732    -7509, -25259, 32768     32768, -29763, -3005       0
+ *   601 limited   16829, 33039, 6416    -9714, -19070, 28784     28784, -24103, -4681      16
+ *   601 full      19595, 38470, 7471   -11058, -21710, 32768     32768, -27439, -5329       0
+ * Each entry is round(c * scale * 2^16) of the matrix's coefficient c, scale = 219/255 (limited luma), 224/255 (limited chroma), 1 (full
+ * range); G is then adjusted so that Y sums to 56284 (limited) or 65536 (full) and Cb and Cr to 0: every grey has chroma exactly 128, white
+ * is 235 (limited) or 255 (full).  Over all 2^24 colours limited range keeps Y in [16, 235] and chroma in [16, 240]; full-range chroma
+ * reaches 256 before the clamp.  All in integers:
+ *     Y[y][x]    = y_off + ((yR*R + yG*G + yB*B + 2^15) >> 16)
+ *     Cb[cy][cx] = min(255, (2^25 + 2^17 + uR*SR + uG*SG + uB*SB) >> 18)        Cr likewise with the Cr coefficients
+ * SR, SG, SB are the sums over the four pixels (min(2cx + i, W - 1), min(2cy + j, H - 1)), i, j in {0, 1}: centre siting (Y4M's C420jpeg),
+ * an odd last column or row replicated.  The bracket is positive and below 2^27: unsigned 32-bit arithmetic, one rounding. */
+enum { LFI_YUV_BT709 = 0, LFI_YUV_BT601 = 1 };
+enum { LFI_YUV_LIMITED = 0, LFI_YUV_FULL = 1 };
+/* Views [v0, v0 + n) as frames at out + k*frame_stride_bytes, k in [0, n).  One kernel launch converts all n views (both view layouts are
+ * read in place; attached views too) into device frames the context owns (lfi_memory.workspace_bytes, LFI_POISON_SCRATCH; every byte copied
+ * out the call has written); where W is a multiple of 8 and H is even the device frames are the host frames and one copy moves the batch
+ * (frame_stride_bytes == frame_bytes; else one per frame), other sizes take three 2D copies per frame.  Synchronous, ordered like
+ * lfi_download_quilt; writes no view and no map.
+ * LFI_EINVAL, the context usable and the host memory untouched: nothing rendered yet; n < 1 or a range outside [0, views); an unknown matrix
+ * or range; out NULL; frame_stride_bytes < frame_bytes; a row window (a 2x2 block may straddle the band). */
+int lfi_download_views_yuv420(lfi_ctx *ctx, int v0, int n, int matrix, int range, uint8_t *out, size_t frame_stride_bytes);
+/* lfi_render_stream with YUV 4:2:0 frames for its downloads: the same contract for weights, blocks and ordering; view i of the path becomes
+ * the frame at host_out + i*frame_stride_bytes.  Each block is rendered, then converted on the compute stream into one of two buffers of
+ * frames, which is copied on the copy stream while the next block renders: no second set of views, and the planar view layout is allowed.
+ * host_out must not be NULL (page-locked for the overlap).  LFI_EINVAL for what lfi_download_views_yuv420 refuses of matrix, range, pointer,
+ * stride and row window, and wherever lfi_render_stream refuses. */
+int lfi_render_stream_yuv420(lfi_ctx *ctx, int method, int all_focus, const uint16_t *weights_fp16, int total_views, int matrix, int range,
+                             uint8_t *host_out, size_t frame_stride_bytes);
 int lfi_upload_map(lfi_ctx *ctx, int k, const uint8_t *rgba, size_t pitch_bytes); /* tests: inject a focus map */
 /* view v's map k (0 or 1) of the per-view maps (lfi_view_focus_maps).  Synchronous.  The upload is a test hook like lfi_upload_map (it
  * allocates the per-view maps if needed and does not put them in use: renders read them after a successful lfi_view_focus_maps). */
@@ -584,7 +619,7 @@ int lfi_debug_mfma_f16_chain(lfi_ctx *ctx, int shape, int k, const uint16_t *a_3
  * rebuilt in full by their next user (the estimate's padded planes; the planar copy, as after lfi_grid_modified).
  *   VIEWS            the views in the current layout (attached ones too)
  *   SCRATCH          the planar layout's RGBA scratch copy of the views, the download staging plane, the pre-quantisation buffer, the
- *                    quilt buffer (lfi_download_native's scaled tiles too) and its native image, lfi_render_stream's second set of views and lfi_compare_views' staging buffers, partial sums and per-view records
+ *                    quilt buffer (lfi_download_native's scaled tiles too) and its native image, the YUV 4:2:0 device frames, lfi_render_stream's second set of views and lfi_compare_views' staging buffers, partial sums and per-view records
  *                    (not the kept views: they are data)
  *   MAPS             both focus maps
  *   FOCUS_WORKSPACE  all of the focus-map estimate's workspace, and lfi_focus_curve's / lfi_focus_tiles' (the curves, the results and the partial sums)

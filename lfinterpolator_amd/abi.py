@@ -25,6 +25,12 @@ LFI_POISON_FOCUS_WORKSPACE = 8
 LFI_POISON_DERIVED = 16
 LFI_POISON_VIEW_MAPS = 32
 LFI_LENT_INVERT = 1
+LFI_YUV_BT709 = 0
+LFI_YUV_BT601 = 1
+LFI_YUV_LIMITED = 0
+LFI_YUV_FULL = 1
+YUV_MATRICES = {"709": LFI_YUV_BT709, "601": LFI_YUV_BT601}
+YUV_RANGES = {"limited": LFI_YUV_LIMITED, "full": LFI_YUV_FULL}
 METHODS = {"STD": LFI_METHOD_STD, "TEN_WM": LFI_METHOD_TEN_WM, "FOCUS": LFI_KERNEL_FOCUS_ESTIMATE}
 
 # every symbol include/lfi.h declares
@@ -38,6 +44,7 @@ ABI_SYMBOLS = [
     "lfi_debug_poison", "lfi_set_view_offsets", "lfi_set_view_float_offsets", "lfi_view_focus_maps", "lfi_download_view_map",
     "lfi_upload_view_map", "lfi_focus_curve", "lfi_focus_tiles", "lfi_focus_tiles_steps", "lfi_focus_tiles_passes", "lfi_download_quilt_scaled", "lfi_download_quilt_tiles_scaled",
     "lfi_keep_views", "lfi_compare_views", "lfi_set_focus_steps", "lfi_focus_steps", "lfi_download_native",
+    "lfi_download_views_yuv420", "lfi_render_stream_yuv420",
 ]
 
 
@@ -156,6 +163,8 @@ def load_hip_library() -> C.CDLL:
         "lfi_download_quilt_scaled": (i, [vp, i, i, i, i, i, vp, sz]),
         "lfi_download_quilt_tiles_scaled": (i, [vp, i, i, i, i, i, i, i, vp, sz]),
         "lfi_download_native": (i, [vp, C.POINTER(Lenticular), i, i, i, i, i, vp, sz]),
+        "lfi_download_views_yuv420": (i, [vp, i, i, i, i, vp, sz]),
+        "lfi_render_stream_yuv420": (i, [vp, i, i, vp, i, i, i, vp, sz]),
         "lfi_alloc_pinned": (i, [sz, C.POINTER(vp)]),
         "lfi_free_pinned": (i, [vp]),
         "lfi_grid_modified": (i, [vp]),
@@ -583,6 +592,39 @@ class Context:
         self._check(self._lib.lfi_download_native(self._h, C.byref(lens) if lens is not None else None, v0, out_w, out_h, tile_w, tile_h, _ptr(out),
                                                   out.strides[0] if out.size else 0))
         return out
+
+    def yuv420_frame_bytes(self) -> int:
+        """bytes of one I420 frame of a view: W·H + 2·((W + 1) // 2)·((H + 1) // 2)"""
+        return self.width * self.height + 2 * ((self.width + 1) // 2) * ((self.height + 1) // 2)
+
+    def download_views_yuv420(self, v0: int = 0, n: int | None = None, matrix="709", range="limited", out: np.ndarray | None = None) -> np.ndarray:
+        """views [v0, v0 + n) (default: all from v0) as 8-bit YUV 4:2:0 frames (I420: Y, Cb, Cr planes, tightly packed), converted on the device
+        (lfi_download_views_yuv420).  matrix: "709" / "601" (or LFI_YUV_BT*), range: "limited" / "full" (or LFI_YUV_*).  `out`: [n][P] uint8 with
+        rows of P ≥ frame bytes — the frame stride is out's; by default a new [n][frame_bytes] array."""
+        n = self.views - v0 if n is None else n
+        fb = self.yuv420_frame_bytes()
+        if out is None:
+            out = np.full((max(n, 0), fb), 0xC3, dtype=np.uint8)   # a sentinel, not zeros: every byte is written
+        assert out.dtype == np.uint8 and out.ndim == 2 and out.shape[0] == n and (out.size == 0 or out.strides[1] == 1)
+        self._check(self._lib.lfi_download_views_yuv420(self._h, v0, n, YUV_MATRICES.get(matrix, matrix), YUV_RANGES.get(range, range), _ptr(out),
+                                                        out.strides[0] if out.size else 0))
+        return out[:, :fb] if out.size else out
+
+    def render_stream_yuv420(self, method, weights: np.ndarray, out: np.ndarray | None = None, all_focus: bool = False, matrix="709",
+                             range="limited") -> np.ndarray:
+        """render_stream with YUV 4:2:0 frames for its downloads (lfi_render_stream_yuv420): weights [total_views][N] fp16 bits of the whole
+        path; `out`: [total_views][P] uint8 with rows of P ≥ frame bytes (ideally from pinned_empty), by default a new [total_views][frame_bytes]
+        array.  Either view layout."""
+        m = METHODS[method] if isinstance(method, str) else method
+        w = np.ascontiguousarray(weights, dtype=np.uint16)
+        assert w.ndim == 2 and w.shape[1] == self.n_images
+        fb = self.yuv420_frame_bytes()
+        if out is None:
+            out = np.full((w.shape[0], fb), 0xC3, dtype=np.uint8)
+        assert out.dtype == np.uint8 and out.ndim == 2 and out.shape[0] == w.shape[0] and (out.size == 0 or out.strides[1] == 1)
+        self._check(self._lib.lfi_render_stream_yuv420(self._h, m, int(all_focus), _ptr(w), w.shape[0], YUV_MATRICES.get(matrix, matrix),
+                                                       YUV_RANGES.get(range, range), _ptr(out), out.strides[0] if out.size else 0))
+        return out[:, :fb] if out.size else out
 
     def download_map(self, k: int) -> np.ndarray:
         out = np.empty((self.height, self.width, 4), dtype=np.uint8)

@@ -286,6 +286,9 @@ struct lfi_ctx
     DeviceBuffer dl_plane;            // planar layout: one RGBA plane that downloads expand a view into
     DeviceBuffer quilt;               // lfi_download_quilt[_tiles]: the quilt's rows of tiles as one RGBA image (grows, kept); lfi_download_native: its scaled tiles
     DeviceBuffer native;              // lfi_download_native: the native image, out_h × out_w dwords (grows, kept)
+    // lfi_download_views_yuv420: the padded I420 frames of a call's views in yuv[0]; lfi_render_stream_yuv420: a block's frames in either,
+    // one copied to the host while the next block is converted into the other (grow, kept)
+    DeviceBuffer yuv[2];
     // parameter block
     bool have_params = false;
     int views_n = 0, k_pad = 0, v_pad = 0, n_focus_ids = 0;
@@ -694,6 +697,8 @@ void free_views(lfi_ctx *c)
     c->dl_plane.release();
     c->quilt.release();
     c->native.release();
+    c->yuv[0].release();
+    c->yuv[1].release();
     c->views2.release();
     c->quality_ref.release();
     c->cmp_stage[0].release();

@@ -10,6 +10,7 @@
 #include "lfi_focus_sched.hpp"
 #include "quilt_scaled.hpp"
 #include "native_image.hpp"
+#include "yuv420.hpp"
 #include "lfi_rccl.hpp"
 
 extern "C" {
@@ -1208,7 +1209,7 @@ int lfi_memory_info(lfi_ctx *ctx, lfi_memory *out)
     out->views_bytes = ctx->views.bytes();
     out->maps_bytes = (ctx->maps ? plane_bytes(ctx) * 2 : 0) + ctx->view_maps.bytes();
     out->workspace_bytes = ctx->focus_ws.bytes() + ctx->curve_ws.bytes() + ctx->rgba_scratch.bytes() + ctx->dl_plane.bytes() + ctx->kept.bytes() +
-                           ctx->cmp_stage[0].bytes() + ctx->cmp_stage[1].bytes() + ctx->cmp_ws.bytes() + ctx->native.bytes();
+                           ctx->cmp_stage[0].bytes() + ctx->cmp_stage[1].bytes() + ctx->cmp_ws.bytes() + ctx->native.bytes() + ctx->yuv[0].bytes() + ctx->yuv[1].bytes();
     out->derived_build_ms = ctx->derived_build_ms;
     return LFI_OK;
 }
@@ -1242,6 +1243,95 @@ const char *lfi_last_kernel_name(const lfi_ctx *ctx)
     return ctx ? ctx->last_kernel : "";
 }
 
+// ---- YUV 4:2:0 frames (yuv420.hpp) ----------------------------------------------------------------------------------------------------------
+
+// what lfi_download_views_yuv420 and lfi_render_stream_yuv420 refuse alike (the range of views aside); fills the geometry
+static int check_yuv_args(lfi_ctx *ctx, const char *who, int matrix, int range, const uint8_t *out, size_t frame_stride_bytes, lfi::YuvGeometry *geo)
+{
+    if(ctx->windowed)
+        return fail(ctx, LFI_EINVAL, std::string(who) + ": YUV 4:2:0 frames need whole views: a 2x2 chroma block may straddle the row window's band");
+    if((matrix != LFI_YUV_BT709 && matrix != LFI_YUV_BT601) || (range != LFI_YUV_LIMITED && range != LFI_YUV_FULL))
+        return fail(ctx, LFI_EINVAL, std::string(who) + ": unknown YUV matrix (LFI_YUV_BT709, LFI_YUV_BT601) or range (LFI_YUV_LIMITED, LFI_YUV_FULL)");
+    *geo = lfi::yuv_geometry(ctx->width, ctx->height);
+    if(!out || frame_stride_bytes < geo->frame_bytes)
+        return fail(ctx, LFI_EINVAL, std::string(who) + ": the frames' pointer is NULL or frame_stride_bytes is below W*H + 2*((W+1)/2)*((H+1)/2)");
+    return LFI_OK;
+}
+
+// views [v0, v0 + n) of `views` (in the context's layout) → n padded device frames at dev, one launch on st
+static hipError_t enqueue_yuv_convert(lfi_ctx *ctx, hipStream_t st, const uint8_t *views, int v0, int n, const lfi::YuvGeometry &g, int matrix, int range, uint8_t *dev)
+{
+    const bool planar = ctx->out_layout == LFI_LAYOUT_PLANAR_RGB;
+    lfi::YuvArgs a{};
+    a.src = views + (size_t)v0 * out_plane_bytes(ctx);
+    a.out = dev;
+    a.view_stride = out_plane_bytes(ctx);
+    a.frame_stride = g.dev_frame_bytes;
+    a.W = g.W, a.H = g.H, a.pitch = planar ? view_pitch(ctx) : 0;
+    a.y_pitch = g.y_pitch, a.c_pitch = g.c_pitch, a.ch = g.ch;
+    a.blocks_x = g.y_pitch / lfi::YUV_BLOCK_W;
+    a.rows16 = g.W % 4 == 0; // the views start on 16-byte boundaries (hipMalloc; lfi_attach_views checks), a view is W·H·4 bytes
+    a.k = lfi::YUV_COEFFS[matrix * 2 + range];
+    return lfi::launch_yuv420_convert(st, planar, a, n);
+}
+
+// n device frames at dev → tight host frames at out + k·stride, on st: one copy for all (or per frame) where the device layout is the
+// host's, else three 2D copies per frame out of the padded planes
+static hipError_t enqueue_yuv_copies(hipStream_t st, const uint8_t *dev, int n, const lfi::YuvGeometry &g, uint8_t *out, size_t stride)
+{
+    if(g.tight && stride == g.frame_bytes)
+        return hipMemcpyAsync(out, dev, g.frame_bytes * n, hipMemcpyDeviceToHost, st);
+    const size_t y_plane = (size_t)g.y_pitch * g.y_rows, c_plane = (size_t)g.c_pitch * g.ch;
+    for(int k = 0; k < n; k++)
+    {
+        const uint8_t *src = dev + g.dev_frame_bytes * k;
+        uint8_t *dst = out + stride * k;
+        hipError_t e = hipSuccess;
+        if(g.tight)
+            e = hipMemcpyAsync(dst, src, g.frame_bytes, hipMemcpyDeviceToHost, st);
+        else
+        {
+            e = hipMemcpy2DAsync(dst, g.W, src, g.y_pitch, g.W, g.H, hipMemcpyDeviceToHost, st);
+            for(int p = 0; p < 2 && e == hipSuccess; p++)
+                e = hipMemcpy2DAsync(dst + (size_t)g.W * g.H + (size_t)g.cw * g.ch * p, g.cw, src + y_plane + c_plane * p, g.c_pitch, g.cw, g.ch,
+                                     hipMemcpyDeviceToHost, st);
+        }
+        if(e != hipSuccess)
+            return e;
+    }
+    return hipSuccess;
+}
+
+int lfi_download_views_yuv420(lfi_ctx *ctx, int v0, int n, int matrix, int range, uint8_t *out, size_t frame_stride_bytes)
+{
+    if(!ctx)
+        return LFI_EINVAL;
+    if(!ctx->views || !ctx->have_params)
+        return fail(ctx, LFI_EINVAL, "nothing rendered yet");
+    if(n < 1 || v0 < 0 || (long)v0 + n > ctx->views_n)
+        return fail(ctx, LFI_EINVAL, "lfi_download_views_yuv420: needs n >= 1 views starting at v0 inside [0, views)");
+    lfi::YuvGeometry g{};
+    if(int rc = check_yuv_args(ctx, "lfi_download_views_yuv420", matrix, range, out, frame_stride_bytes, &g))
+        return rc;
+    if(int rc = bind(ctx))
+        return rc;
+    LFI_HIP(ctx, ctx->yuv[0].reserve(g.dev_frame_bytes * n));
+    LFI_HIP(ctx, enqueue_yuv_convert(ctx, ctx->stream, ctx->views.get(), v0, n, g, matrix, range, ctx->yuv[0].get()));
+    LFI_HIP(ctx, enqueue_yuv_copies(ctx->stream, ctx->yuv[0].get(), n, g, out, frame_stride_bytes));
+    LFI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return LFI_OK;
+}
+
+// where lfi_render_stream_yuv420's frames go; NULL: lfi_render_stream's RGBA downloads
+struct YuvSink
+{
+    lfi::YuvGeometry g;
+    int matrix, range;
+    size_t stride;
+};
+
+static int render_stream(lfi_ctx *ctx, int method, int all_focus, const uint16_t *weights_fp16, int total_views, uint8_t *host_out, size_t pitch_bytes, const YuvSink *yuv);
+
 int lfi_render_stream(lfi_ctx *ctx, int method, int all_focus, const uint16_t *weights_fp16, int total_views, uint8_t *host_out, size_t pitch_bytes)
 {
     if(int rc = check_render_args(ctx, method, 0, 1))
@@ -1252,6 +1342,31 @@ int lfi_render_stream(lfi_ctx *ctx, int method, int all_focus, const uint16_t *w
         return fail(ctx, LFI_EINVAL, "lfi_render_stream: weights are NULL or total_views < 1");
     if(host_out && (ctx->out_layout != LFI_LAYOUT_RGBA || pitch_bytes < (size_t)ctx->width * 4))
         return fail(ctx, LFI_EINVAL, "lfi_render_stream: downloads need the RGBA view layout and a pitch of at least width*4 bytes");
+    return render_stream(ctx, method, all_focus, weights_fp16, total_views, host_out, pitch_bytes, nullptr);
+}
+
+int lfi_render_stream_yuv420(lfi_ctx *ctx, int method, int all_focus, const uint16_t *weights_fp16, int total_views, int matrix, int range, uint8_t *host_out,
+                             size_t frame_stride_bytes)
+{
+    if(int rc = check_render_args(ctx, method, 0, 1))
+        return rc;
+    if(const ViewRowsKind rows = view_rows_of(ctx, all_focus))
+        return fail(ctx, LFI_EINVAL, view_rows_set(rows) + "lfi_render_stream_yuv420 is not supported - clear them with NULL");
+    if(!weights_fp16 || total_views < 1)
+        return fail(ctx, LFI_EINVAL, "lfi_render_stream_yuv420: weights are NULL or total_views < 1");
+    YuvSink sink{};
+    sink.matrix = matrix, sink.range = range, sink.stride = frame_stride_bytes;
+    if(int rc = check_yuv_args(ctx, "lfi_render_stream_yuv420", matrix, range, host_out, frame_stride_bytes, &sink.g))
+        return rc;
+    return render_stream(ctx, method, all_focus, weights_fp16, total_views, host_out, 0, &sink);
+}
+
+// The loop of both: block b's weights go up behind block b − 1's kernel, block b renders, and its result leaves on the copy stream while
+// block b + 1 renders.  RGBA (yuv == NULL): the blocks alternate between two sets of views, each copied out as it is.  YUV: every block
+// renders into the one set of views and is converted on the compute stream, in stream order before the next render overwrites it, into
+// one of two buffers of frames; that buffer is what the copy stream reads.
+static int render_stream(lfi_ctx *ctx, int method, int all_focus, const uint16_t *weights_fp16, int total_views, uint8_t *host_out, size_t pitch_bytes, const YuvSink *yuv)
+{
     if(int rc = bind(ctx))
         return rc;
     const int V = ctx->views_n, n = ctx->n, k_pad = ctx->k_pad, v_pad = ctx->v_pad;
@@ -1270,13 +1385,19 @@ int lfi_render_stream(lfi_ctx *ctx, int method, int all_focus, const uint16_t *w
     {
         if(int rc = ensure_copy_stream(ctx))
             return rc;
-        LFI_HIP(ctx, ctx->views2.fit(out_plane_bytes(ctx) * V));
+        if(yuv)
+        {
+            for(int i = 0; i < 2; i++)
+                LFI_HIP(ctx, ctx->yuv[i].reserve(yuv->g.dev_frame_bytes * V));
+        }
+        else
+            LFI_HIP(ctx, ctx->views2.fit(out_plane_bytes(ctx) * V));
     }
     if(int rc = join_uploads(ctx))
         return rc;
     const int n_blocks = (total_views + V - 1) / V;
     uint8_t *dev_weights = param_base(ctx) + ctx->blob_off_w16;
-    uint8_t *const vbuf[2] = {ctx->views.get(), host_out ? ctx->views2.get() : ctx->views.get()};
+    uint8_t *const vbuf[2] = {ctx->views.get(), host_out && !yuv ? ctx->views2.get() : ctx->views.get()};
     int status = LFI_OK;
     for(int b = 0; b < n_blocks && status == LFI_OK; b++)
     {
@@ -1293,15 +1414,27 @@ int lfi_render_stream(lfi_ctx *ctx, int method, int all_focus, const uint16_t *w
         // stream order protects the device arrays: the previous block's kernel is ahead of this copy on the same stream
         LFI_HIP(ctx, hipMemcpyAsync(dev_weights, ctx->stream_staging[slot].get(), wbytes, hipMemcpyHostToDevice, ctx->stream));
         LFI_HIP(ctx, hipEventRecord(ctx->ev_h2d[slot], ctx->stream));
-        if(host_out && b >= 2)
+        if(host_out && !yuv && b >= 2)
             LFI_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_d2h[slot], 0)); // block b − 2 has left this set of views
         KernelArgs a = make_args(ctx, 0, nv, method);
         a.views = vbuf[slot];
         status = launch_blend(ctx, method, all_focus, a);
         if(status != LFI_OK || !host_out)
             continue;
+        if(yuv)
+        {
+            if(b >= 2)
+                LFI_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_d2h[slot], 0)); // block b − 2 has left this buffer of frames
+            LFI_HIP(ctx, enqueue_yuv_convert(ctx, ctx->stream, vbuf[slot], 0, nv, yuv->g, yuv->matrix, yuv->range, ctx->yuv[slot].get()));
+        }
         LFI_HIP(ctx, hipEventRecord(ctx->ev_rendered[slot], ctx->stream));
         LFI_HIP(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->ev_rendered[slot], 0));
+        if(yuv)
+        {
+            LFI_HIP(ctx, enqueue_yuv_copies(ctx->copy_stream, ctx->yuv[slot].get(), nv, yuv->g, host_out + (size_t)b * V * yuv->stride, yuv->stride));
+            LFI_HIP(ctx, hipEventRecord(ctx->ev_d2h[slot], ctx->copy_stream));
+            continue;
+        }
         const size_t view_bytes = pitch_bytes * ctx->height;
         for(int v = 0; v < nv; v++)
             LFI_HIP(ctx, hipMemcpy2DAsync(host_out + ((size_t)b * V + v) * view_bytes + (size_t)ctx->out_y0 * pitch_bytes, pitch_bytes,
@@ -2117,6 +2250,8 @@ int lfi_debug_poison(lfi_ctx *ctx, uint32_t what, uint8_t byte)
         rc = rc ? rc : fill(ctx->prequant, ctx->prequant.bytes());
         rc = rc ? rc : fill(ctx->quilt, ctx->quilt.bytes());
         rc = rc ? rc : fill(ctx->native, ctx->native.bytes());
+        rc = rc ? rc : fill(ctx->yuv[0], ctx->yuv[0].bytes());
+        rc = rc ? rc : fill(ctx->yuv[1], ctx->yuv[1].bytes());
         rc = rc ? rc : fill(ctx->views2, ctx->views2.bytes());
         rc = rc ? rc : fill(ctx->cmp_stage[0], ctx->cmp_stage[0].bytes());
         rc = rc ? rc : fill(ctx->cmp_stage[1], ctx->cmp_stage[1].bytes());

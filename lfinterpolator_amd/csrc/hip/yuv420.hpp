@@ -1,0 +1,208 @@
+// yuv420.hpp — 8-bit YUV 4:2:0 frames (I420) of rendered views, converted on the device (lfi_download_views_yuv420,
+// lfi_render_stream_yuv420): what an encoder or player takes, 1.5 bytes per pixel instead of the 4 of an RGBA download.
+//
+// Definition (include/lfi.h), integers only.  A frame of a W × H view is the Y plane [H][W], then Cb and Cr [ch][cw] with cw = (W + 1) >> 1,
+// ch = (H + 1) >> 1.  With the coefficient row (matrix, range) of YUV_COEFFS:
+//     Y[y][x]  = y_off + ((yR·R + yG·G + yB·B + 2¹⁵) >> 16)
+//     Cb[cy][cx] = min(255, (2²⁵ + 2¹⁷ + uR·ΣR + uG·ΣG + uB·ΣB) >> 18),   Cr likewise with the Cr coefficients,
+// ΣR, ΣG, ΣB summed over the four pixels (min(2cx + i, W − 1), min(2cy + j, H − 1)), i, j ∈ {0, 1} (centre siting, Y4M's C420jpeg; an odd
+// last column or row is replicated).  The bracket lies in (0, 2²⁷): it is computed in u32 (the negative coefficients wrap, the sum does
+// not), one rounding, no shift of a negative number.
+//
+//   yuv420_convert<PLANAR>  one launch for all n views (the view is grid.z).  A lane owns a block of 8 columns × 2 rows of one view: from
+//     RGBA views it reads two rows of 32 bytes as 16-byte loads, from PLANAR views 3 planes × 2 rows × 8 bytes at the plane pitch (no RGBA
+//     copy of planar views); it writes two 8-byte pieces of Y and one dword each of Cb and Cr.  A wave is 64 neighbouring blocks of ONE
+//     block row (512 pixel columns): its loads are two runs of 2 KiB (planar: six of 512 bytes), its stores runs of 512 and 256 bytes —
+//     neighbouring lanes, neighbouring words of a row; the row's offsets are wave-uniform.  A workgroup is four waves = four block rows.
+//     Device rows are padded (Y pitch a multiple of 8, chroma pitch of 4, an even number of Y rows) so that every store is whole and
+//     stays inside its own row, and the kernel writes EVERY byte of the padded planes: columns and rows beyond the view replicate the
+//     last one, as the definition's clamp says.  Ragged blocks (and RGBA views whose width is no multiple of 4: rows not 16-byte aligned)
+//     read pixel by pixel with clamped coordinates; planar rows are as long as their pitch (a multiple of 128 ≥ the Y pitch), so the
+//     8-byte loads stay inside the row and the bytes beyond the view are replaced by the last column's.
+//     No LDS, no atomics, no byte stores, no scratch.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+namespace lfi {
+
+constexpr int YUV_LANES_X = 64;   // lanes (blocks) of a workgroup along x: one wave
+constexpr int YUV_BLOCK_ROWS = 4; // block rows of a workgroup: one wave each
+constexpr int YUV_BLOCK_W = 8;    // pixel columns of a lane's block
+constexpr int YUV_BLOCK_H = 2;    // pixel rows of a lane's block
+
+// 16-bit fixed point: round(c · scale · 2¹⁶), scale = 219/255 (limited luma), 224/255 (limited chroma), 1 (full); G adjusted so that Y sums
+// to 56284 (limited) / 65536 (full) and Cb, Cr to 0.  Row = matrix · 2 + range (LFI_YUV_BT709 / _BT601, LFI_YUV_LIMITED / _FULL).
+struct YuvCoeffs
+{
+    int32_t y[3], cb[3], cr[3]; // R, G, B
+    uint32_t y_off;
+};
+
+constexpr YuvCoeffs YUV_COEFFS[4] = {
+    {{11966, 40254, 4064}, {-6596, -22188, 28784}, {28784, -26145, -2639}, 16},  // BT.709 limited
+    {{13933, 46871, 4732}, {-7509, -25259, 32768}, {32768, -29763, -3005}, 0},   // BT.709 full
+    {{16829, 33039, 6416}, {-9714, -19070, 28784}, {28784, -24103, -4681}, 16},  // BT.601 limited
+    {{19595, 38470, 7471}, {-11058, -21710, 32768}, {32768, -27439, -5329}, 0},  // BT.601 full
+};
+
+// the padded device planes of one frame, and the tight host frame
+struct YuvGeometry
+{
+    uint32_t W, H, cw, ch;
+    uint32_t y_pitch, c_pitch, y_rows; // device: W rounded up to 8, half of it (= cw rounded up to 4), 2·ch
+    size_t frame_bytes;                // host: W·H + 2·cw·ch
+    size_t dev_frame_bytes;            // device: y_pitch·y_rows + 2·c_pitch·ch (a multiple of 8)
+    bool tight;                        // W a multiple of 8 and H even: the device frame IS the host frame
+};
+
+inline YuvGeometry yuv_geometry(const int width, const int height)
+{
+    YuvGeometry g{};
+    g.W = width, g.H = height;
+    g.cw = (g.W + 1) >> 1, g.ch = (g.H + 1) >> 1;
+    g.y_pitch = (g.W + YUV_BLOCK_W - 1) / YUV_BLOCK_W * YUV_BLOCK_W;
+    g.c_pitch = g.y_pitch / 2;
+    g.y_rows = g.ch * YUV_BLOCK_H;
+    g.frame_bytes = (size_t)g.W * g.H + 2 * (size_t)g.cw * g.ch;
+    g.dev_frame_bytes = (size_t)g.y_pitch * g.y_rows + 2 * (size_t)g.c_pitch * g.ch;
+    g.tight = g.y_pitch == g.W && g.y_rows == g.H;
+    return g;
+}
+
+struct YuvArgs
+{
+    const uint8_t *src;   // view 0 of the call: RGBA planes [view][H][W], or (PLANAR) byte planes [view][R,G,B][H][pitch]
+    uint8_t *out;         // frame 0 of the call: [frame][Y: y_rows × y_pitch | Cb: ch × c_pitch | Cr: ch × c_pitch]
+    size_t view_stride;   // bytes from view to view
+    size_t frame_stride;  // bytes from device frame to device frame
+    uint32_t W, H, pitch; // pitch: bytes per row of a byte plane (PLANAR)
+    uint32_t y_pitch, c_pitch, ch;
+    uint32_t blocks_x;    // y_pitch / 8
+    uint32_t rows16;      // RGBA: every pixel row starts on a 16-byte boundary (W a multiple of 4)
+    YuvCoeffs k;
+};
+
+__device__ inline uint32_t yuv_luma(const YuvCoeffs &k, const uint32_t r, const uint32_t g, const uint32_t b)
+{
+    return k.y_off + (((uint32_t)k.y[0] * r + (uint32_t)k.y[1] * g + (uint32_t)k.y[2] * b + 0x8000u) >> 16);
+}
+
+// c: the Cb or the Cr coefficients; sr, sg, sb: the sums over the four pixels.  u32 throughout: the products of the negative coefficients
+// wrap, the bracket (true value in (0, 2²⁷)) does not
+__device__ inline uint32_t yuv_chroma(const int32_t (&c)[3], const uint32_t sr, const uint32_t sg, const uint32_t sb)
+{
+    const uint32_t v = ((1u << 25) + (1u << 17) + (uint32_t)c[0] * sr + (uint32_t)c[1] * sg + (uint32_t)c[2] * sb) >> 18;
+    return v < 255u ? v : 255u;
+}
+
+template <bool PLANAR>
+__global__ void __launch_bounds__(YUV_LANES_X *YUV_BLOCK_ROWS) yuv420_convert(const YuvArgs a)
+{
+    const uint32_t bx = blockIdx.x * YUV_LANES_X + threadIdx.x;
+    const uint32_t by = blockIdx.y * YUV_BLOCK_ROWS + threadIdx.y; // wave-uniform
+    if(bx >= a.blocks_x || by >= a.ch)
+        return;
+    const uint32_t x0 = bx * YUV_BLOCK_W;
+    const uint32_t ya = by * YUV_BLOCK_H, yb = ya + 1u < a.H ? ya + 1u : a.H - 1u; // ya < H: by < ch
+    const uint8_t *view = a.src + (size_t)blockIdx.z * a.view_stride;
+    const bool whole = x0 + YUV_BLOCK_W <= a.W; // all 8 columns inside the view
+    uint32_t r[2][8], g[2][8], b[2][8];
+    if constexpr(PLANAR)
+    {
+        // every row is `pitch` bytes long and pitch ≥ y_pitch: the 8-byte load stays inside it; the bytes beyond the view are replaced
+        const uint32_t last = whole ? 7u : a.W - 1u - x0; // the block's last column inside the view (x0 < W: x0 < y_pitch < W + 8)
+        const size_t plane = (size_t)a.H * a.pitch;
+#pragma unroll
+        for(int j = 0; j < 2; j++)
+        {
+            const uint8_t *row = view + (size_t)(j ? yb : ya) * a.pitch + x0;
+            const uint2 pr = *reinterpret_cast<const uint2 *>(row);
+            const uint2 pg = *reinterpret_cast<const uint2 *>(row + plane);
+            const uint2 pb = *reinterpret_cast<const uint2 *>(row + 2 * plane);
+#pragma unroll
+            for(int i = 0; i < 8; i++)
+            {
+                r[j][i] = ((i < 4 ? pr.x : pr.y) >> (8 * (i & 3))) & 0xffu;
+                g[j][i] = ((i < 4 ? pg.x : pg.y) >> (8 * (i & 3))) & 0xffu;
+                b[j][i] = ((i < 4 ? pb.x : pb.y) >> (8 * (i & 3))) & 0xffu;
+            }
+            if(!whole)
+            {
+                const uint32_t sh = 8u * (last & 3u);
+                const uint32_t lr = ((last < 4u ? pr.x : pr.y) >> sh) & 0xffu, lg = ((last < 4u ? pg.x : pg.y) >> sh) & 0xffu,
+                               lb = ((last < 4u ? pb.x : pb.y) >> sh) & 0xffu;
+#pragma unroll
+                for(int i = 1; i < 8; i++)
+                    if((uint32_t)i > last)
+                        r[j][i] = lr, g[j][i] = lg, b[j][i] = lb;
+            }
+        }
+    }
+    else
+    {
+        const uint32_t *px = reinterpret_cast<const uint32_t *>(view);
+#pragma unroll
+        for(int j = 0; j < 2; j++)
+        {
+            const uint32_t *row = px + (size_t)(j ? yb : ya) * a.W;
+            uint32_t p[8];
+            if(whole && a.rows16)
+            {
+                const uint4 lo = *reinterpret_cast<const uint4 *>(row + x0), hi = *reinterpret_cast<const uint4 *>(row + x0 + 4);
+                p[0] = lo.x, p[1] = lo.y, p[2] = lo.z, p[3] = lo.w, p[4] = hi.x, p[5] = hi.y, p[6] = hi.z, p[7] = hi.w;
+            }
+            else
+            {
+#pragma unroll
+                for(int i = 0; i < 8; i++)
+                    p[i] = row[x0 + i < a.W ? x0 + i : a.W - 1u];
+            }
+#pragma unroll
+            for(int i = 0; i < 8; i++)
+                r[j][i] = p[i] & 0xffu, g[j][i] = (p[i] >> 8) & 0xffu, b[j][i] = (p[i] >> 16) & 0xffu;
+        }
+    }
+    uint8_t *frame = a.out + (size_t)blockIdx.z * a.frame_stride;
+#pragma unroll
+    for(int j = 0; j < 2; j++)
+    {
+        uint2 y{0u, 0u};
+#pragma unroll
+        for(int i = 0; i < 4; i++)
+        {
+            y.x |= yuv_luma(a.k, r[j][i], g[j][i], b[j][i]) << (8 * i);
+            y.y |= yuv_luma(a.k, r[j][i + 4], g[j][i + 4], b[j][i + 4]) << (8 * i);
+        }
+        *reinterpret_cast<uint2 *>(frame + (size_t)(ya + j) * a.y_pitch + x0) = y; // row ya + 1 < y_rows = 2·ch
+    }
+    uint32_t cb = 0, cr = 0;
+#pragma unroll
+    for(int i = 0; i < 4; i++)
+    {
+        const uint32_t sr = r[0][2 * i] + r[0][2 * i + 1] + r[1][2 * i] + r[1][2 * i + 1];
+        const uint32_t sg = g[0][2 * i] + g[0][2 * i + 1] + g[1][2 * i] + g[1][2 * i + 1];
+        const uint32_t sb = b[0][2 * i] + b[0][2 * i + 1] + b[1][2 * i] + b[1][2 * i + 1];
+        cb |= yuv_chroma(a.k.cb, sr, sg, sb) << (8 * i);
+        cr |= yuv_chroma(a.k.cr, sr, sg, sb) << (8 * i);
+    }
+    const size_t y_plane = (size_t)a.y_pitch * (2u * a.ch), c_plane = (size_t)a.c_pitch * a.ch;
+    uint8_t *c_row = frame + y_plane + (size_t)by * a.c_pitch + 4u * bx;
+    *reinterpret_cast<uint32_t *>(c_row) = cb;
+    *reinterpret_cast<uint32_t *>(c_row + c_plane) = cr;
+}
+
+// Enqueues the ONE yuv420_convert launch for n views.  The caller has checked the sizes: n ≥ 1, a.out holds n device frames.
+inline hipError_t launch_yuv420_convert(hipStream_t stream, const bool planar, const YuvArgs &a, const int n)
+{
+    const dim3 grid((a.blocks_x + YUV_LANES_X - 1) / YUV_LANES_X, (a.ch + YUV_BLOCK_ROWS - 1) / YUV_BLOCK_ROWS, n), block(YUV_LANES_X, YUV_BLOCK_ROWS);
+    if(planar)
+        hipLaunchKernelGGL(yuv420_convert<true>, grid, block, 0, stream, a);
+    else
+        hipLaunchKernelGGL(yuv420_convert<false>, grid, block, 0, stream, a);
+    return hipGetLastError();
+}
+
+} // namespace lfi

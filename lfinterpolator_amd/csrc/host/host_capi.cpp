@@ -8,6 +8,7 @@
 #include "../area_span.h"
 #include "lenticular.h"
 #include "params.h"
+#include "y4m.h"
 
 namespace {
 
@@ -202,6 +203,29 @@ int lfi_host_build_view_focus_ids(int cols, int rows, const char *trajectory, in
         const std::vector<int32_t> ids = p.viewFocusMapIDs(p.interpretTrajectory(trajectory), views);
         std::memcpy(ids_vk, ids.data(), sizeof(int32_t) * ids.size());
         *n_ids = static_cast<int32_t>(ids.size() / views);
+        return 0;
+    }
+    catch(const std::exception &e)
+    {
+        return report(e, err, err_len);
+    }
+}
+
+// the Y4M writer (y4m.h): bytes of one I420 frame (0 for a size below 1), and n frames — frame k at frames + k·frame_stride_bytes — written
+// as one file at fps_num:fps_den frames per second with XCOLORRANGE=FULL or LIMITED; returns 0 or -1 (message in err)
+size_t lfi_host_y4m_frame_bytes(int width, int height)
+{
+    return lfi::y4mFrameBytes(width, height);
+}
+
+int lfi_host_y4m_write(const char *path, const uint8_t *frames, int n, size_t frame_stride_bytes, int width, int height, int fps_num, int fps_den, int full_range,
+                       char *err, size_t err_len)
+{
+    try
+    {
+        if(!path)
+            throw std::runtime_error("path must be non-NULL");
+        lfi::writeY4m(path, frames, n, frame_stride_bytes, width, height, fps_num, fps_den, full_range != 0);
         return 0;
     }
     catch(const std::exception &e)

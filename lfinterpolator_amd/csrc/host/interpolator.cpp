@@ -17,6 +17,7 @@
 #include "image_io.h"
 #include "lfLoader.h"
 #include "loadingbar.hpp"
+#include "y4m.h"
 
 int Interpolator::defaultDevice = 0;
 
@@ -515,5 +516,34 @@ void Interpolator::storeResults(std::string path)
         std::vector<uint8_t> native(nativePitch * nativeSize.y);
         check(lfi_download_native(context, &lens, 0, nativeSize.x, nativeSize.y, tile.x, tile.y, native.data(), nativePitch));
         lfi::writePng((std::filesystem::path(path) / "native.png").string(), nativeSize.x, nativeSize.y, static_cast<int>(channels), native.data(), nativePitch);
+    }
+    if(!y4mPath.empty())
+    {
+        std::cout << "Storing video..." << std::endl;
+        // converted on the device (lfi_download_views_yuv420): every GPU's views arrive as frames in its part of one page-locked buffer
+        const size_t frameBytes = lfi::y4mFrameBytes(resolution.x, resolution.y);
+        uint8_t *frames = nullptr;
+        const bool framesPinned = lfi_alloc_pinned(frameBytes * viewCount, reinterpret_cast<void **>(&frames)) == LFI_OK;
+        std::vector<uint8_t> pageableFrames;
+        if(!framesPinned)
+        {
+            pageableFrames.resize(frameBytes * viewCount);
+            frames = pageableFrames.data();
+        }
+        try
+        {
+            for(int g = 0; g < gpuCount; g++)
+                check(lfi_download_views_yuv420(contexts[g], 0, viewStart[g + 1] - viewStart[g], yuvMatrix, yuvRange, frames + frameBytes * viewStart[g], frameBytes),
+                      contexts[g]);
+            lfi::writeY4m(y4mPath, frames, viewCount, frameBytes, resolution.x, resolution.y, y4mFps.x, y4mFps.y, yuvRange == LFI_YUV_FULL);
+        }
+        catch(...)
+        {
+            if(framesPinned)
+                lfi_free_pinned(frames);
+            throw;
+        }
+        if(framesPinned)
+            lfi_free_pinned(frames);
     }
 }

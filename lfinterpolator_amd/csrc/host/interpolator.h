@@ -41,6 +41,16 @@ class Interpolator
             nativeTile = tile;
             nativeViews = views;
         }
+        // also write the views as the frames of one Y4M video file, in view order: 8-bit YUV 4:2:0 converted on the device
+        // (lfi_download_views_yuv420; matrix: LFI_YUV_BT709 / _BT601, range: LFI_YUV_LIMITED / _FULL) at fpsNum / fpsDen frames per second; with
+        // several GPUs every one converts and downloads its own views into its part of one host buffer
+        void setY4m(std::string path, int fpsNum = 30, int fpsDen = 1, int matrix = LFI_YUV_BT709, int range = LFI_YUV_LIMITED)
+        {
+            y4mPath = path;
+            y4mFps = {fpsNum, fpsDen};
+            yuvMatrix = matrix;
+            yuvRange = range;
+        }
         float lastAverageTime() const { return averageTime; }
         // render on GPUs 0 … count-1 of this node: views are split into contiguous ranges, the grid is broadcast once (RCCL)
         void setGpuCount(int count) { gpuCount = count; }
@@ -101,6 +111,10 @@ class Interpolator
         lfi::LensCalibration nativeLens;
         lfi::IVec2 nativeTile{0, 0}; // 0: the views' size, read in place
         int nativeViews{0};          // 0: all views
+        std::string y4mPath;         // empty: no video file
+        lfi::IVec2 y4mFps{30, 1};
+        int yuvMatrix{LFI_YUV_BT709};
+        int yuvRange{LFI_YUV_LIMITED};
         lfi_ctx *context{nullptr};
         int gpuCount{1};
         bool perViewFocus{false};

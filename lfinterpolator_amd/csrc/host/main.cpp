@@ -3,7 +3,8 @@
 // view's own camera), --autofocus (the focus found from a region's focus curve), --focus-tiles / --auto-range (the focus of every tile of a
 // grid; the search interval of an all-focus render found from it), --map-steps / --tile-steps (more than 32 candidates for the focus map / the focus tiles), --compare / --compare-methods (PSNR / SSIM of all views against a
 // directory of images or against the other method's render), --native / --lens / --native-tile / --native-views (the native image of a
-// lenticular display, interlaced on the GPU) and --synthetic for runs without a dataset.
+// lenticular display, interlaced on the GPU), --y4m / --fps / --yuv-matrix / --yuv-range (the views as one YUV 4:2:0 video file, converted on
+// the GPU) and --synthetic for runs without a dataset.
 #include <array>
 #include <iostream>
 #include <memory>
@@ -56,6 +57,10 @@ int main(int argc, char **argv)
                           "--lens pitch,slope,center,dpi[,invert] - with --native: the display's calibration - lenses per inch, the slant, the phase offset in lens periods, the panel's pixels per inch, and 1 to reverse the order of the views (default 0)\n"
                           "--native-tile WxH - with --native: resize every view to a tile of W x H pixels on the GPU first (the exact area filter of --quilt-tile; at most the views' size; default: the views' size, read in place)\n"
                           "--native-views N - with --native: interlace the first N views (default: all of them)\n"
+                          "--y4m FILE - also store the views as the frames of one YUV4MPEG2 video FILE, in view order (ffmpeg -i FILE, or any player): 8-bit YUV 4:2:0 (I420, centre-sited chroma), converted on the GPU before the download - 1.5 bytes per pixel cross PCIe instead of 4; with -g every GPU converts its own views\n"
+                          "--fps N[:D] - with --y4m: the frame rate N/D frames per second (default=30:1)\n"
+                          "--yuv-matrix 709|601 - with --y4m: the colour matrix, BT.709 or BT.601 (default=709)\n"
+                          "--yuv-range limited|full - with --y4m: limited (Y 16..235, chroma 16..240) or full (0..255) range (default=limited)\n"
                           "--compare DIR - after the render, compare every view with DIR/NN.png (the names -o writes; same size) on the GPU, all views in one pass: prints \"compare NN psnr <dB> ssim <index> maxdiff <largest byte difference> differing <colour bytes that differ>\" per view, then \"compare all psnr ... ssim ...\"; one GPU\n"
                           "--compare-methods - render the views with the other method first (STD if -m TEN_WM, TEN_WM if -m STD; same parameters), keep them on the GPU, render with -m and compare the two there; prints the lines of --compare; the stored images are those of -m; one GPU; not with --compare\n"
                           "--synthetic cols,rows,width,height[,seed] - use a generated light field instead of -i\n"
@@ -166,6 +171,60 @@ int main(int argc, char **argv)
     {
         std::cerr << "--native needs every view in one context: it works on one GPU only (-g 1)." << std::endl;
         return EXIT_FAILURE;
+    }
+
+    if((args["--fps"] || args["--yuv-matrix"] || args["--yuv-range"]) && !args["--y4m"])
+    {
+        std::cerr << "--fps, --yuv-matrix and --yuv-range belong to the video file: they need --y4m FILE." << std::endl;
+        return EXIT_FAILURE;
+    }
+
+    if(args["--y4m"] && static_cast<std::string>(args["--y4m"]).empty())
+    {
+        std::cerr << "--y4m needs the name of the video file to write." << std::endl;
+        return EXIT_FAILURE;
+    }
+
+    int fpsNum = 30, fpsDen = 1;
+    if(args["--fps"])
+    {
+        // N or N:D, both whole numbers of at least 1 and nothing else
+        const std::string text = static_cast<std::string>(args["--fps"]);
+        const size_t cut = text.find(':');
+        const auto whole = [](const std::string &t, int &out) {
+            if(t.empty() || t.size() > 9 || t.find_first_not_of("0123456789") != std::string::npos)
+                return false;
+            out = std::stoi(t);
+            return out >= 1;
+        };
+        fpsDen = 1;
+        if(!whole(text.substr(0, cut), fpsNum) || (cut != std::string::npos && !whole(text.substr(cut + 1), fpsDen)))
+        {
+            std::cerr << "--fps expects N or N:D, whole numbers of at least 1 (e.g. 30 or 30000:1001)." << std::endl;
+            return EXIT_FAILURE;
+        }
+    }
+
+    int yuvMatrix = LFI_YUV_BT709, yuvRange = LFI_YUV_LIMITED;
+    if(args["--yuv-matrix"])
+    {
+        const std::string text = static_cast<std::string>(args["--yuv-matrix"]);
+        if(text != "709" && text != "601")
+        {
+            std::cerr << "--yuv-matrix expects 709 or 601." << std::endl;
+            return EXIT_FAILURE;
+        }
+        yuvMatrix = text == "601" ? LFI_YUV_BT601 : LFI_YUV_BT709;
+    }
+    if(args["--yuv-range"])
+    {
+        const std::string text = static_cast<std::string>(args["--yuv-range"]);
+        if(text != "limited" && text != "full")
+        {
+            std::cerr << "--yuv-range expects limited or full." << std::endl;
+            return EXIT_FAILURE;
+        }
+        yuvRange = text == "full" ? LFI_YUV_FULL : LFI_YUV_LIMITED;
     }
 
     if(args["--compare"] && args["--compare-methods"])
@@ -321,6 +380,8 @@ int main(int argc, char **argv)
             interpolator->setNative(tileGrid(static_cast<std::string>(args["--native"]), "--native", size), lens,
                                     args["--native-tile"] ? tileGrid(static_cast<std::string>(args["--native-tile"]), "--native-tile", size) : lfi::IVec2{0, 0}, views);
         }
+        if(args["--y4m"])
+            interpolator->setY4m(static_cast<std::string>(args["--y4m"]), fpsNum, fpsDen, yuvMatrix, yuvRange);
         if(args["--compare"])
             interpolator->setCompareDir(static_cast<std::string>(args["--compare"]));
         if(args["--compare-methods"])

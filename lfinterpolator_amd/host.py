@@ -39,6 +39,10 @@ def load_host_library() -> C.CDLL:
         lib.lfi_host_area_span.argtypes = [C.c_int] * 3 + [C.c_void_p]
         lib.lfi_host_lenticular.restype = C.c_int
         lib.lfi_host_lenticular.argtypes = [C.c_double] * 4 + [C.c_int] * 4 + [C.POINTER(Lenticular), C.c_char_p, C.c_size_t]
+        lib.lfi_host_y4m_frame_bytes.restype = C.c_size_t
+        lib.lfi_host_y4m_frame_bytes.argtypes = [C.c_int, C.c_int]
+        lib.lfi_host_y4m_write.restype = C.c_int
+        lib.lfi_host_y4m_write.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.c_size_t] + [C.c_int] * 5 + [C.c_char_p, C.c_size_t]
         lib.lfi_host_build_view_offsets.restype = C.c_int
         lib.lfi_host_build_view_offsets.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_float, C.c_void_p, C.c_int,
                                                     C.c_void_p, C.c_char_p, C.c_size_t]
@@ -160,6 +164,22 @@ def lenticular(pitch: float, slope: float, center: float, dpi: float, invert: bo
         raise ValueError(err.value.decode())
     assert lens.flags == (LFI_LENT_INVERT if invert else 0)
     return lens
+
+
+def write_y4m(path: str, frames: np.ndarray, width: int, height: int, fps=(30, 1), full_range: bool = False) -> None:
+    """The I420 frames of Context.download_views_yuv420 / render_stream_yuv420 — [n][P] uint8 with rows of P ≥ frame bytes, the frame stride is
+    the array's — as one Y4M file (csrc/host/y4m.h): `YUV4MPEG2 W H F<fps> Ip A1:1 C420jpeg XCOLORRANGE=LIMITED|FULL`, then `FRAME` + the
+    frame's bytes per frame.  fps: (numerator, denominator)."""
+    lib = load_host_library()
+    frames = np.asarray(frames)
+    if frames.dtype != np.uint8 or frames.ndim != 2 or (frames.size and frames.strides[1] != 1):
+        raise ValueError("frames must be [n][>= frame bytes] uint8 with contiguous rows")
+    if frames.shape[1] < lib.lfi_host_y4m_frame_bytes(width, height):
+        raise ValueError(f"a {width}x{height} frame has {lib.lfi_host_y4m_frame_bytes(width, height)} bytes, the rows have {frames.shape[1]}")
+    err = C.create_string_buffer(512)
+    if lib.lfi_host_y4m_write(str(path).encode(), frames.ctypes.data_as(C.c_void_p), frames.shape[0], frames.strides[0] if frames.size else 0, width, height,
+                              int(fps[0]), int(fps[1]), int(bool(full_range)), err, len(err)) != 0:
+        raise ValueError(err.value.decode())
 
 
 def build_view_offsets(cols: int, rows: int, width: int, height: int, trajectory: str, aspect: float, focus_v) -> np.ndarray:
