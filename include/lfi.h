@@ -147,6 +147,41 @@ int lfi_upload_image(lfi_ctx *ctx, int g, const uint8_t *rgba, size_t pitch_byte
 int lfi_upload_image_async(lfi_ctx *ctx, int g, const uint8_t *rgba, size_t pitch_bytes);
 /* host wait for the asynchronous uploads issued so far */
 int lfi_upload_wait(lfi_ctx *ctx);
+/* Images from 8-bit YUV 4:2:0 video frames (I420), expanded to RGBA on the device: decoded video goes in as it is, 1.5 bytes per pixel
+ * cross PCIe instead of the 4 of lfi_upload_image.  A frame has the layout lfi_download_views_yuv420 writes: the Y plane [H][W], then Cb
+ * [ch][cw], then Cr [ch][cw], cw = (W + 1) >> 1, ch = (H + 1) >> 1, tightly packed, frame_bytes = W*H + 2*cw*ch; chroma is centre-sited
+ * (Y4M's C420jpeg).  matrix and range (LFI_YUV_*) select one of four coefficient sets in 16-bit fixed point:
+ *                    cY       rV       gU       gV       bU     y_off
+ *   BT.709 limited 76309   117489   -13975   -34925   138438     16
+ *   BT.709 full    65536   103206   -12276   -30679   121609      0
+ *   BT.601 limited 76309   104597   -25675   -53279   132201     16
+ *   BT.601 full    65536    91881   -22553   -46802   116130      0
+ * Each entry is round(c * scale * 2^16), scale = 255/219 (limited luma), 255/224 (limited chroma), 1 (full range); with Kr, Kb of the
+ * matrix and Kg = 1 - Kr - Kb: rV = 2(1 - Kr), bU = 2(1 - Kb), gU = -2Kb(1 - Kb)/Kg, gV = -2Kr(1 - Kr)/Kg.
+ * The chroma of pixel (x, y) is taken in sixteenths; with cx = x >> 1, cy = y >> 1:
+ *   LFI_CHROMA_NEAREST    SU = 16*U[cy][cx]
+ *   LFI_CHROMA_BILINEAR   SU = 9*U[cy][cx] + 3*U[cy][nx] + 3*U[ny][cx] + U[ny][nx],  nx = clamp(cx + ((x & 1) ? 1 : -1), 0, cw - 1),
+ *                         ny = clamp(cy + ((y & 1) ? 1 : -1), 0, ch - 1): the triangle filter of centre siting (libjpeg's "fancy" h2v2
+ *                         upsampling)
+ * and SV the same from Cr.  With l = 16*cY*(Y - y_off), u = SU - 2048, v = SV - 2048, all in integers:
+ *     R = clamp(floor((l + rV*v        + 2^19) / 2^20), 0, 255)
+ *     G = clamp(floor((l + gU*u + gV*v + 2^19) / 2^20), 0, 255)
+ *     B = clamp(floor((l + bU*u        + 2^19) / 2^20), 0, 255)         A = 255
+ * One rounding; over all byte triples the bracket stays within +-573,111,632 before the rounding term (int32, arithmetic shift).  Chroma
+ * 128 gives R = G = B for every Y; limited 16 -> 0 and 235 -> 255; codes outside the nominal range are legal input and are clamped. */
+enum { LFI_CHROMA_BILINEAR = 0, LFI_CHROMA_NEAREST = 1 };
+/* Fills images [g0, g0 + n) of the grid from the frames at frames + k*frame_stride_bytes, k in [0, n): every byte of the n images, alpha
+ * included.  Ordered like lfi_upload_image_async: the work goes on the context's copy stream behind the renders already enqueued, a
+ * page-locked source must stay valid until lfi_upload_wait / lfi_sync, and everything that uses the planes afterwards is ordered after
+ * it by an event, without a host wait.  The frames are copied into a device staging buffer the context owns (lfi_memory.workspace_bytes,
+ * LFI_POISON_SCRATCH; the result depends on no byte of it the call did not copy) in chunks of at most 16 frames or 256 MiB, at least one
+ * frame, each followed by one kernel launch; where W is a multiple of 8 and H is even a chunk is one copy (frame_stride_bytes ==
+ * frame_bytes; else one per frame), other sizes take three 2D copies per frame.  An attached grid is written in place; the derived planar
+ * copy of the images is rebuilt by its next user, as after lfi_upload_image_async.
+ * LFI_EINVAL, the context usable and the grid untouched: no grid; released inputs (lfi_release_inputs); a row window (a 2x2 block may
+ * straddle the band); n < 1 or a range outside [0, N); an unknown matrix, range or chroma value; frames NULL; frame_stride_bytes <
+ * frame_bytes. */
+int lfi_upload_images_yuv420(lfi_ctx *ctx, int g0, int n, int matrix, int range, int chroma, const uint8_t *frames, size_t frame_stride_bytes);
 /* Use caller-owned device memory ([N][H][W][4] u8, ≥ N*H*W*4 bytes) for the input planes instead of the context's
  * own allocation — lets the caller fill it (e.g. an RCCL broadcast into a tensor it owns).  Call after lfi_set_grid. */
 int lfi_attach_grid(lfi_ctx *ctx, void *device_ptr, size_t bytes);
@@ -396,7 +431,7 @@ typedef struct lfi_memory {
     size_t workspace_bytes; /* focus-map workspace + lfi_focus_curve's / lfi_focus_tiles' curves and partial sums + (planar view layout) the RGBA scratch copy of the views that renders other than TEN_WM and
                              * STD on more than 64 images go through, and the one-plane staging buffer of downloads + the kept views (lfi_keep_views) and
                              * lfi_compare_views' staging buffers and partial sums + lfi_download_native's device image + the device frames of
-                             * lfi_download_views_yuv420 / lfi_render_stream_yuv420 */
+                             * lfi_download_views_yuv420 / lfi_render_stream_yuv420 + the staged frames of lfi_upload_images_yuv420 */
     float derived_build_ms;
 } lfi_memory;
 int lfi_memory_info(lfi_ctx *ctx, lfi_memory *out);
@@ -619,7 +654,7 @@ int lfi_debug_mfma_f16_chain(lfi_ctx *ctx, int shape, int k, const uint16_t *a_3
  * rebuilt in full by their next user (the estimate's padded planes; the planar copy, as after lfi_grid_modified).
  *   VIEWS            the views in the current layout (attached ones too)
  *   SCRATCH          the planar layout's RGBA scratch copy of the views, the download staging plane, the pre-quantisation buffer, the
- *                    quilt buffer (lfi_download_native's scaled tiles too) and its native image, the YUV 4:2:0 device frames, lfi_render_stream's second set of views and lfi_compare_views' staging buffers, partial sums and per-view records
+ *                    quilt buffer (lfi_download_native's scaled tiles too) and its native image, the YUV 4:2:0 device frames and lfi_upload_images_yuv420's staged frames, lfi_render_stream's second set of views and lfi_compare_views' staging buffers, partial sums and per-view records
  *                    (not the kept views: they are data)
  *   MAPS             both focus maps
  *   FOCUS_WORKSPACE  all of the focus-map estimate's workspace, and lfi_focus_curve's / lfi_focus_tiles' (the curves, the results and the partial sums)

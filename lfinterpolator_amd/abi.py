@@ -31,6 +31,9 @@ LFI_YUV_LIMITED = 0
 LFI_YUV_FULL = 1
 YUV_MATRICES = {"709": LFI_YUV_BT709, "601": LFI_YUV_BT601}
 YUV_RANGES = {"limited": LFI_YUV_LIMITED, "full": LFI_YUV_FULL}
+LFI_CHROMA_BILINEAR = 0
+LFI_CHROMA_NEAREST = 1
+YUV_CHROMAS = {"bilinear": LFI_CHROMA_BILINEAR, "nearest": LFI_CHROMA_NEAREST}
 METHODS = {"STD": LFI_METHOD_STD, "TEN_WM": LFI_METHOD_TEN_WM, "FOCUS": LFI_KERNEL_FOCUS_ESTIMATE}
 
 # every symbol include/lfi.h declares
@@ -44,7 +47,7 @@ ABI_SYMBOLS = [
     "lfi_debug_poison", "lfi_set_view_offsets", "lfi_set_view_float_offsets", "lfi_view_focus_maps", "lfi_download_view_map",
     "lfi_upload_view_map", "lfi_focus_curve", "lfi_focus_tiles", "lfi_focus_tiles_steps", "lfi_focus_tiles_passes", "lfi_download_quilt_scaled", "lfi_download_quilt_tiles_scaled",
     "lfi_keep_views", "lfi_compare_views", "lfi_set_focus_steps", "lfi_focus_steps", "lfi_download_native",
-    "lfi_download_views_yuv420", "lfi_render_stream_yuv420",
+    "lfi_download_views_yuv420", "lfi_render_stream_yuv420", "lfi_upload_images_yuv420",
 ]
 
 
@@ -165,6 +168,7 @@ def load_hip_library() -> C.CDLL:
         "lfi_download_native": (i, [vp, C.POINTER(Lenticular), i, i, i, i, i, vp, sz]),
         "lfi_download_views_yuv420": (i, [vp, i, i, i, i, vp, sz]),
         "lfi_render_stream_yuv420": (i, [vp, i, i, vp, i, i, i, vp, sz]),
+        "lfi_upload_images_yuv420": (i, [vp, i, i, i, i, i, vp, sz]),
         "lfi_alloc_pinned": (i, [sz, C.POINTER(vp)]),
         "lfi_free_pinned": (i, [vp]),
         "lfi_grid_modified": (i, [vp]),
@@ -291,6 +295,15 @@ class Context:
 
     def upload_wait(self) -> None:
         self._check(self._lib.lfi_upload_wait(self._h))
+
+    def upload_images_yuv420(self, frames: np.ndarray, g0: int = 0, matrix="709", range="limited", chroma="bilinear") -> None:
+        """Images [g0, g0 + n) from n 8-bit YUV 4:2:0 frames (I420: Y, Cb, Cr planes, tightly packed), expanded to RGBA on the device
+        (lfi_upload_images_yuv420).  frames: [n][P] uint8 with rows of P ≥ frame bytes — the frame stride is the array's; pageable (staged,
+        free on return) or from pinned_empty (keep it alive until upload_wait / sync).  matrix: "709" / "601", range: "limited" / "full",
+        chroma: "bilinear" / "nearest" (or the LFI_* values).  Ordered like upload_image_async."""
+        assert frames.dtype == np.uint8 and frames.ndim == 2 and (frames.size == 0 or frames.strides[1] == 1)
+        self._check(self._lib.lfi_upload_images_yuv420(self._h, g0, frames.shape[0], YUV_MATRICES.get(matrix, matrix), YUV_RANGES.get(range, range),
+                                                       YUV_CHROMAS.get(chroma, chroma), _ptr(frames), frames.strides[0] if frames.size else 0))
 
     def attach_grid(self, device_ptr: int, nbytes: int) -> None:
         self._check(self._lib.lfi_attach_grid(self._h, C.c_void_p(device_ptr), nbytes))

@@ -289,6 +289,9 @@ struct lfi_ctx
     // lfi_download_views_yuv420: the padded I420 frames of a call's views in yuv[0]; lfi_render_stream_yuv420: a block's frames in either,
     // one copied to the host while the next block is converted into the other (grow, kept)
     DeviceBuffer yuv[2];
+    // lfi_upload_images_yuv420: a chunk's I420 frames in the padded planes yuv420_expand reads; written and read on the copy stream only, in
+    // stream order (grows, kept)
+    DeviceBuffer yuv_in;
     // parameter block
     bool have_params = false;
     int views_n = 0, k_pad = 0, v_pad = 0, n_focus_ids = 0;
@@ -742,6 +745,7 @@ void free_grid(lfi_ctx *c)
     c->planar_version = 0;
     c->d_planar_phase.release();
     c->phase_ring.release();
+    c->yuv_in.release();
 }
 
 } // namespace

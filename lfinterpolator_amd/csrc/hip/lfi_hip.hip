@@ -11,6 +11,7 @@
 #include "quilt_scaled.hpp"
 #include "native_image.hpp"
 #include "yuv420.hpp"
+#include "yuv420_upload.hpp"
 #include "lfi_rccl.hpp"
 
 extern "C" {
@@ -253,6 +254,89 @@ int lfi_upload_wait(lfi_ctx *ctx)
         return rc;
     if(ctx->copy_stream)
         LFI_HIP(ctx, hipStreamSynchronize(ctx->copy_stream));
+    return LFI_OK;
+}
+
+// ---- YUV 4:2:0 input (yuv420_upload.hpp) ----------------------------------------------------------------------------------------------------
+
+int lfi_upload_images_yuv420(lfi_ctx *ctx, int g0, int n, int matrix, int range, int chroma, const uint8_t *frames, size_t frame_stride_bytes)
+{
+    if(!ctx)
+        return LFI_EINVAL;
+    if(ctx->inputs_released)
+        return fail(ctx, LFI_EINVAL, "lfi_upload_images_yuv420: the RGBA inputs were released (lfi_release_inputs): lfi_set_grid and upload the images again");
+    if(!ctx->grid)
+        return fail(ctx, LFI_EINVAL, "lfi_set_grid has not been called");
+    if(ctx->windowed)
+        return fail(ctx, LFI_EINVAL, "lfi_upload_images_yuv420: YUV 4:2:0 frames need whole images: a 2x2 chroma block may straddle the row window's band");
+    if(n < 1 || g0 < 0 || (long)g0 + n > ctx->n)
+        return fail(ctx, LFI_EINVAL, "lfi_upload_images_yuv420: needs n >= 1 images starting at g0 inside [0, N)");
+    if((matrix != LFI_YUV_BT709 && matrix != LFI_YUV_BT601) || (range != LFI_YUV_LIMITED && range != LFI_YUV_FULL) ||
+       (chroma != LFI_CHROMA_BILINEAR && chroma != LFI_CHROMA_NEAREST))
+        return fail(ctx, LFI_EINVAL, "lfi_upload_images_yuv420: unknown YUV matrix (LFI_YUV_BT709, LFI_YUV_BT601), range (LFI_YUV_LIMITED, LFI_YUV_FULL) or chroma "
+                                     "filter (LFI_CHROMA_BILINEAR, LFI_CHROMA_NEAREST)");
+    const lfi::YuvGeometry g = lfi::yuv_geometry(ctx->width, ctx->height);
+    if(!frames || frame_stride_bytes < g.frame_bytes)
+        return fail(ctx, LFI_EINVAL, "lfi_upload_images_yuv420: the frames' pointer is NULL or frame_stride_bytes is below W*H + 2*((W+1)/2)*((H+1)/2)");
+    if(int rc = bind(ctx))
+        return rc;
+    if(int rc = ensure_copy_stream(ctx))
+        return rc;
+    // chunks of at most 16 frames or 256 MiB, at least one frame: a chunk's copies and its launch follow each other on the copy stream, so
+    // stream order is all the staging buffer needs
+    const int chunk = (int)std::max<size_t>(1, std::min<size_t>(16, ((size_t)256 << 20) / g.dev_frame_bytes));
+    const size_t need = g.dev_frame_bytes * std::min(chunk, n);
+    if(ctx->yuv_in.bytes() < need)
+    {
+        LFI_HIP(ctx, hipStreamSynchronize(ctx->copy_stream)); // an earlier call's chunks may still be in the buffer that goes
+        LFI_HIP(ctx, ctx->yuv_in.reserve(need));
+    }
+    if(!ctx->uploads_pending)
+    {
+        // first copy of a batch: renders already enqueued on the compute stream may still read the planes
+        LFI_HIP(ctx, hipEventRecord(ctx->ev_order, ctx->stream));
+        LFI_HIP(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->ev_order, 0));
+    }
+    ctx->uploads_pending = true; // from here on something may be enqueued on the copy stream
+    hipStream_t st = ctx->copy_stream;
+    uint8_t *dev = ctx->yuv_in.get();
+    const size_t y_plane = (size_t)g.y_pitch * g.y_rows, c_plane = (size_t)g.c_pitch * g.ch;
+    for(int k0 = 0; k0 < n; k0 += chunk)
+    {
+        const int nk = std::min(chunk, n - k0);
+        const uint8_t *src = frames + frame_stride_bytes * k0;
+        // the frames' own bytes only: where W is a multiple of 8 and H is even the staged frame IS the host frame, else three 2D copies per
+        // frame into the padded planes (whose padding stays whatever it was: the kernel uses none of it)
+        if(g.tight && frame_stride_bytes == g.frame_bytes)
+            LFI_HIP(ctx, hipMemcpyAsync(dev, src, g.frame_bytes * nk, hipMemcpyHostToDevice, st));
+        else
+            for(int k = 0; k < nk; k++)
+            {
+                const uint8_t *f = src + frame_stride_bytes * k;
+                uint8_t *d = dev + g.dev_frame_bytes * k;
+                if(g.tight)
+                {
+                    LFI_HIP(ctx, hipMemcpyAsync(d, f, g.frame_bytes, hipMemcpyHostToDevice, st));
+                    continue;
+                }
+                LFI_HIP(ctx, hipMemcpy2DAsync(d, g.y_pitch, f, g.W, g.W, g.H, hipMemcpyHostToDevice, st));
+                for(int p = 0; p < 2; p++)
+                    LFI_HIP(ctx, hipMemcpy2DAsync(d + y_plane + c_plane * p, g.c_pitch, f + (size_t)g.W * g.H + (size_t)g.cw * g.ch * p, g.cw, g.cw, g.ch,
+                                                  hipMemcpyHostToDevice, st));
+            }
+        lfi::YuvInArgs a{};
+        a.src = dev;
+        a.dst = ctx->grid.get() + in_plane_bytes(ctx) * (size_t)(g0 + k0);
+        a.frame_stride = g.dev_frame_bytes;
+        a.image_stride = in_plane_bytes(ctx);
+        a.W = g.W, a.H = g.H, a.cw = g.cw, a.ch = g.ch;
+        a.y_pitch = g.y_pitch, a.c_pitch = g.c_pitch;
+        a.blocks_x = g.y_pitch / lfi::YUV_BLOCK_W;
+        a.rows16 = g.W % 4 == 0; // the grid starts on a 16-byte boundary (hipMalloc; lfi_attach_grid checks), an image is W·H·4 bytes
+        a.k = lfi::YUV_IN_COEFFS[matrix * 2 + range];
+        LFI_HIP(ctx, lfi::launch_yuv420_expand(st, chroma == LFI_CHROMA_NEAREST, a, nk));
+    }
+    touch_images(ctx, g0, g0 + n);
     return LFI_OK;
 }
 
@@ -1209,7 +1293,8 @@ int lfi_memory_info(lfi_ctx *ctx, lfi_memory *out)
     out->views_bytes = ctx->views.bytes();
     out->maps_bytes = (ctx->maps ? plane_bytes(ctx) * 2 : 0) + ctx->view_maps.bytes();
     out->workspace_bytes = ctx->focus_ws.bytes() + ctx->curve_ws.bytes() + ctx->rgba_scratch.bytes() + ctx->dl_plane.bytes() + ctx->kept.bytes() +
-                           ctx->cmp_stage[0].bytes() + ctx->cmp_stage[1].bytes() + ctx->cmp_ws.bytes() + ctx->native.bytes() + ctx->yuv[0].bytes() + ctx->yuv[1].bytes();
+                           ctx->cmp_stage[0].bytes() + ctx->cmp_stage[1].bytes() + ctx->cmp_ws.bytes() + ctx->native.bytes() + ctx->yuv[0].bytes() + ctx->yuv[1].bytes() +
+                           ctx->yuv_in.bytes();
     out->derived_build_ms = ctx->derived_build_ms;
     return LFI_OK;
 }
@@ -2252,6 +2337,7 @@ int lfi_debug_poison(lfi_ctx *ctx, uint32_t what, uint8_t byte)
         rc = rc ? rc : fill(ctx->native, ctx->native.bytes());
         rc = rc ? rc : fill(ctx->yuv[0], ctx->yuv[0].bytes());
         rc = rc ? rc : fill(ctx->yuv[1], ctx->yuv[1].bytes());
+        rc = rc ? rc : fill(ctx->yuv_in, ctx->yuv_in.bytes());
         rc = rc ? rc : fill(ctx->views2, ctx->views2.bytes());
         rc = rc ? rc : fill(ctx->cmp_stage[0], ctx->cmp_stage[0].bytes());
         rc = rc ? rc : fill(ctx->cmp_stage[1], ctx->cmp_stage[1].bytes());

@@ -234,6 +234,51 @@ int lfi_host_y4m_write(const char *path, const uint8_t *frames, int n, size_t fr
     }
 }
 
+// the Y4M reader (y4m.h): out = {width, height, fps_num, fps_den, frames, full_range (1, 0, -1: no XCOLORRANGE), centre_sited, 0}, the C tag
+// without its C into chroma_tag (may be NULL); returns 0 or -1 (message in err)
+int lfi_host_y4m_info(const char *path, int32_t out[8], char *chroma_tag, size_t chroma_tag_len, char *err, size_t err_len)
+{
+    try
+    {
+        if(!path || !out)
+            throw std::runtime_error("path and out must be non-NULL");
+        lfi::Y4mReader reader(path);
+        const lfi::Y4mInfo &info = reader.info();
+        const int32_t values[8] = {info.width, info.height, info.fpsNum, info.fpsDen, info.frames, info.fullRange, info.centreSited ? 1 : 0, 0};
+        std::memcpy(out, values, sizeof(values));
+        if(chroma_tag && chroma_tag_len)
+        {
+            std::strncpy(chroma_tag, info.chroma.c_str(), chroma_tag_len - 1);
+            chroma_tag[chroma_tag_len - 1] = 0;
+        }
+        return 0;
+    }
+    catch(const std::exception &e)
+    {
+        return report(e, err, err_len);
+    }
+}
+
+// frames [first, first + n) of a Y4M file, frame k at frames + k·frame_stride_bytes; returns 0 or -1 (message in err)
+int lfi_host_y4m_read(const char *path, int first, int n, uint8_t *frames, size_t frame_stride_bytes, char *err, size_t err_len)
+{
+    try
+    {
+        if(!path)
+            throw std::runtime_error("path must be non-NULL");
+        lfi::Y4mReader reader(path);
+        if(n < 0 || (n > 0 && (!frames || frame_stride_bytes < reader.frameBytes())))
+            throw std::runtime_error("Y4M frames are missing or closer together than a frame's bytes (" + std::string(path) + ")");
+        for(int k = 0; k < n; k++)
+            reader.readFrame(first + k, frames + frame_stride_bytes * k);
+        return 0;
+    }
+    catch(const std::exception &e)
+    {
+        return report(e, err, err_len);
+    }
+}
+
 uint16_t lfi_host_float_to_half(float v)
 {
     return lfi::floatToHalfBits(v);
@@ -300,6 +345,33 @@ int lfi_host_load_grid(const char *path, int *cols, int *rows, int *width, int *
             for(int col = 0; col < cr.x; col++)
                 for(int row = 0; row < cr.y; row++)
                     std::memcpy(planes + loader.imageSize() * (static_cast<size_t>(col) * cr.y + row), loader.image({col, row}).data(), loader.imageSize());
+        return 0;
+    }
+    catch(const std::exception &e)
+    {
+        return report(e, err, err_len);
+    }
+}
+
+// LfLoader on a directory of <row>_<col>.y4m files, a light-field video: out = {cols, rows, width, height, frames, full_range (1, 0, -1)},
+// and (if frames != NULL) frame t of every camera, image g = col*rows + row at frames + g·frame_stride_bytes; returns 0 or -1 (message in err;
+// a directory of images is refused here)
+int lfi_host_load_grid_y4m(const char *path, int t, int32_t out[6], uint8_t *frames, size_t frame_stride_bytes, char *err, size_t err_len)
+{
+    try
+    {
+        if(!path || !out)
+            throw std::runtime_error("path and out must be non-NULL");
+        LfLoader loader;
+        loader.loadData(path);
+        if(!loader.isVideo())
+            throw std::runtime_error(std::string("The directory ") + path + " holds images, not .y4m videos");
+        const lfi::IVec2 cr = loader.getColsRows();
+        const lfi::IVec3 res = loader.imageResolution();
+        const int32_t values[6] = {cr.x, cr.y, res.x, res.y, loader.frameCount(), loader.videoFullRange()};
+        std::memcpy(out, values, sizeof(values));
+        if(frames)
+            loader.loadFrames(t, frames, frame_stride_bytes);
         return 0;
     }
     catch(const std::exception &e)

@@ -37,6 +37,8 @@ Interpolator::Interpolator(lfi::IVec2 inColsRows, lfi::IVec2 inResolution, uint3
 
 Interpolator::~Interpolator()
 {
+    if(inFramesPinned)
+        lfi_free_pinned(inFrames);
     for(size_t i = 1; i < contexts.size(); i++)
         lfi_destroy(contexts[i]);
     if(context)
@@ -94,16 +96,77 @@ void Interpolator::init()
     loadGPUData();
 }
 
+bool Interpolator::isVideo() const
+{
+    return video != nullptr;
+}
+
+int Interpolator::frameCount() const
+{
+    return video ? video->frameCount() : 1;
+}
+
+void Interpolator::setInputFrame(int t)
+{
+    if(t < 0 || t >= frameCount())
+        throw std::runtime_error("The input has no time step " + std::to_string(t) + ": it has " + std::to_string(frameCount()) + "!");
+    inputFrame = t;
+}
+
+// Time step inputFrame of every camera: read into page-locked memory as the I420 frames they are, one call for the grid
+void Interpolator::uploadVideoFrame()
+{
+    if(contexts.size() > 1)
+        throw std::runtime_error("Several time steps of a light-field video work on one GPU only!");
+    const size_t frameBytes = video->frameBytes();
+    const size_t n = video->imageCount();
+    if(!inFrames)
+    {
+        inFramesPinned = lfi_alloc_pinned(frameBytes * n, reinterpret_cast<void **>(&inFrames)) == LFI_OK;
+        if(!inFramesPinned)
+        {
+            inFramesPageable.resize(frameBytes * n);
+            inFrames = inFramesPageable.data();
+        }
+    }
+    std::cout << "Uploading time step " << inputFrame << " to GPU..." << std::endl;
+    check(lfi_upload_wait(context)); // the previous step's copies have left the frames' memory
+    video->loadFrames(inputFrame, inFrames, frameBytes);
+    const int range = inRange >= 0 ? inRange : (video->videoFullRange() == 1 ? LFI_YUV_FULL : LFI_YUV_LIMITED);
+    check(lfi_upload_images_yuv420(context, 0, static_cast<int>(n), inMatrix, range, inChroma, inFrames, frameBytes));
+    check(lfi_upload_wait(context));
+    loadedFrame = inputFrame;
+}
+
+void Interpolator::finish()
+{
+    if(y4mWriter)
+    {
+        std::unique_ptr<lfi::Y4mWriter> writer = std::move(y4mWriter);
+        writer->close();
+    }
+}
+
 void Interpolator::loadGPUData()
 {
-    LfLoader lfLoader;
+    auto loader = std::make_unique<LfLoader>();
+    LfLoader &lfLoader = *loader;
     lfLoader.loadData(input);
     colsRows = lfLoader.getColsRows();
     resolution = lfLoader.imageResolution();
 
+    check(lfi_set_grid(context, colsRows.x, colsRows.y, resolution.x, resolution.y));
+    if(lfLoader.isVideo())
+    {
+        // a light-field video: interpolate() uploads the time step it renders
+        if(!lfLoader.videoCentreSited())
+            std::cout << "Note: the videos are C" << lfLoader.videoChroma()
+                      << "; their chroma is read as centre-sited (C420jpeg), at most a quarter pixel from where it was sampled." << std::endl;
+        video = std::move(loader);
+        return;
+    }
     std::cout << "Uploading data to GPU..." << std::endl;
     LoadingBar bar(lfLoader.imageCount());
-    check(lfi_set_grid(context, colsRows.x, colsRows.y, resolution.x, resolution.y));
     for(int col = 0; col < colsRows.x; col++)
         for(int row = 0; row < colsRows.y; row++)
         {
@@ -125,6 +188,8 @@ void Interpolator::interpolate(std::string outputPath, std::string trajectory, f
         methodID = LFI_METHOD_STD;
     else
         throw std::runtime_error("The specified interpolation method does not exist!");
+    if(video && loadedFrame != inputFrame)
+        uploadVideoFrame();
     if(quiltTile.x > 0 || quiltTile.y > 0)
     {
         if(!(quiltTiles.x > 0 && quiltTiles.y > 0))
@@ -535,7 +600,11 @@ void Interpolator::storeResults(std::string path)
             for(int g = 0; g < gpuCount; g++)
                 check(lfi_download_views_yuv420(contexts[g], 0, viewStart[g + 1] - viewStart[g], yuvMatrix, yuvRange, frames + frameBytes * viewStart[g], frameBytes),
                       contexts[g]);
-            lfi::writeY4m(y4mPath, frames, viewCount, frameBytes, resolution.x, resolution.y, y4mFps.x, y4mFps.y, yuvRange == LFI_YUV_FULL);
+            // one file for all time steps of a light-field video: opened by the first, appended to by the others, closed by finish()
+            if(!y4mWriter)
+                y4mWriter = std::make_unique<lfi::Y4mWriter>(y4mPath, resolution.x, resolution.y, y4mFps.x, y4mFps.y, yuvRange == LFI_YUV_FULL);
+            for(int i = 0; i < viewCount; i++)
+                y4mWriter->writeFrame(frames + frameBytes * i);
         }
         catch(...)
         {

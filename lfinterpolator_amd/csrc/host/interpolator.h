@@ -5,6 +5,7 @@
 #pragma once
 
 #include <array>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -12,6 +13,9 @@
 #include "lenticular.h"
 #include "params.h"
 #include "vec.h"
+#include "y4m.h"
+
+class LfLoader;
 
 class Interpolator
 {
@@ -51,6 +55,24 @@ class Interpolator
             yuvMatrix = matrix;
             yuvRange = range;
         }
+        // a light-field video as input (a directory of <row>_<col>.y4m files, one per camera): its frames go to the device as they are, 1.5
+        // bytes per pixel from page-locked memory, and become the RGBA images there (one lfi_upload_images_yuv420 call for the grid).
+        // interpolate() renders time step setInputFrame(t), 0 by default, t in [0, frameCount()); called again after another setInputFrame
+        // it uploads that step and renders it with everything else unchanged — and appends its views to the ONE video file of setY4m.
+        // matrix: LFI_YUV_BT709 / _BT601; range: LFI_YUV_LIMITED / _FULL, or -1 for the files' XCOLORRANGE tag (none: limited); chroma:
+        // LFI_CHROMA_BILINEAR / _NEAREST
+        bool isVideo() const;
+        int frameCount() const; // 1 for image inputs
+        void setInputFrame(int t);
+        void setInputYuv(int matrix, int range, int chroma)
+        {
+            inMatrix = matrix;
+            inRange = range;
+            inChroma = chroma;
+            loadedFrame = -1;
+        }
+        // closes the video file of setY4m (interpolate() leaves it open for the next time step's views); throws when that fails
+        void finish();
         float lastAverageTime() const { return averageTime; }
         // render on GPUs 0 … count-1 of this node: views are split into contiguous ranges, the grid is broadcast once (RCCL)
         void setGpuCount(int count) { gpuCount = count; }
@@ -115,6 +137,13 @@ class Interpolator
         lfi::IVec2 y4mFps{30, 1};
         int yuvMatrix{LFI_YUV_BT709};
         int yuvRange{LFI_YUV_LIMITED};
+        std::unique_ptr<lfi::Y4mWriter> y4mWriter; // open from the first stored step to finish()
+        std::unique_ptr<LfLoader> video;           // the input, where it is a light-field video
+        int inputFrame{0}, loadedFrame{-1};        // the time step to render / the one on the device
+        int inMatrix{LFI_YUV_BT709}, inRange{-1}, inChroma{LFI_CHROMA_BILINEAR};
+        uint8_t *inFrames{nullptr};                // one I420 frame per camera, page-locked where that works
+        bool inFramesPinned{false};
+        std::vector<uint8_t> inFramesPageable;
         lfi_ctx *context{nullptr};
         int gpuCount{1};
         bool perViewFocus{false};
@@ -142,6 +171,7 @@ class Interpolator
         std::string input;
         void init();
         void loadGPUData();
+        void uploadVideoFrame();
         void storeResults(std::string path);
         void compareViews(bool withKept);
         void check(int status) const;

@@ -86,6 +86,18 @@ void LfLoader::loadData(std::string path)
     }
     resolution = {};
     initGrid(extent);
+    videos.clear();
+    frames = 0;
+    size_t y4mFiles = 0;
+    for(auto const &file : files)
+        y4mFiles += file.extension() == ".y4m";
+    if(y4mFiles != 0)
+    {
+        if(y4mFiles != files.size())
+            throw std::runtime_error("The input directory mixes .y4m videos with images: a light-field video needs one .y4m file per camera and nothing else!");
+        openVideos(path, files);
+        return;
+    }
 
     std::cout << "Loading images..." << std::endl;
     LoadingBar bar(files.size());
@@ -131,4 +143,60 @@ void LfLoader::loadData(std::string path)
         for(int row = 0; row < colsRows.y; row++)
             if(grid[col][row].empty())
                 throw std::runtime_error("The grid image " + std::to_string(row) + "_" + std::to_string(col) + " is missing!");
+}
+
+// A light-field video: one Y4M file per camera.  Only the headers are read here.
+void LfLoader::openVideos(const std::string &path, const std::set<std::filesystem::path> &files)
+{
+    constexpr int RGBA_CHANNELS{4};
+    std::cout << "Opening videos..." << std::endl;
+    videos.resize(imageCount());
+    int longest = 0;
+    for(auto const &file : files)
+    {
+        const auto rowCol = parseFilename(file.string());
+        const std::string full = (std::filesystem::path(path) / file).string();
+        auto reader = std::make_unique<lfi::Y4mReader>(full);
+        const lfi::Y4mInfo &info = reader->info();
+        if(resolution.x != 0 && (resolution.x != info.width || resolution.y != info.height))
+            throw std::runtime_error("Video " + full + " does not have the same resolution as the others");
+        resolution = {info.width, info.height, RGBA_CHANNELS};
+        auto &cell = videos[static_cast<size_t>(rowCol.y) * colsRows.y + rowCol.x];
+        if(cell)
+            throw std::runtime_error("The grid video " + std::to_string(rowCol.x) + "_" + std::to_string(rowCol.y) + " is there twice (" + full + ")!");
+        cell = std::move(reader);
+    }
+    const lfi::Y4mReader *first = nullptr;
+    for(int col = 0; col < colsRows.x; col++)
+        for(int row = 0; row < colsRows.y; row++)
+        {
+            const auto &cell = videos[static_cast<size_t>(col) * colsRows.y + row];
+            if(!cell)
+                throw std::runtime_error("The grid video " + std::to_string(row) + "_" + std::to_string(col) + " is missing!");
+            if(!first)
+            {
+                first = cell.get();
+                frames = longest = cell->frameCount();
+            }
+            if(cell->info().fullRange != first->info().fullRange)
+                throw std::runtime_error("The grid video " + std::to_string(row) + "_" + std::to_string(col) + " does not have the same XCOLORRANGE tag as the others");
+            frames = std::min(frames, cell->frameCount());
+            longest = std::max(longest, cell->frameCount());
+        }
+    if(longest != frames)
+        std::cout << "The videos differ in length (" << frames << " to " << longest << " frames): the first " << frames << " frames are used." << std::endl;
+    if(frames < 1)
+        throw std::runtime_error("The videos of " + path + " hold no frame!");
+}
+
+void LfLoader::loadFrames(int t, uint8_t *out, size_t frameStrideBytes)
+{
+    if(!isVideo())
+        throw std::runtime_error("The input is not a light-field video!");
+    if(t < 0 || t >= frames)
+        throw std::runtime_error("The videos have no frame " + std::to_string(t) + " (they have " + std::to_string(frames) + ")!");
+    if(!out || frameStrideBytes < frameBytes())
+        throw std::runtime_error("The frames' memory is missing or the frames are closer together than a frame's bytes!");
+    for(size_t g = 0; g < videos.size(); g++)
+        videos[g]->readFrame(t, out + frameStrideBytes * g);
 }

@@ -4,7 +4,8 @@
 // grid; the search interval of an all-focus render found from it), --map-steps / --tile-steps (more than 32 candidates for the focus map / the focus tiles), --compare / --compare-methods (PSNR / SSIM of all views against a
 // directory of images or against the other method's render), --native / --lens / --native-tile / --native-views (the native image of a
 // lenticular display, interlaced on the GPU), --y4m / --fps / --yuv-matrix / --yuv-range (the views as one YUV 4:2:0 video file, converted on
-// the GPU) and --synthetic for runs without a dataset.
+// the GPU), --frames / --in-matrix / --in-range / --in-chroma (a light-field video as input: a directory of per-camera Y4M files whose frames
+// become the images on the GPU) and --synthetic for runs without a dataset.
 #include <array>
 #include <iostream>
 #include <memory>
@@ -61,6 +62,10 @@ int main(int argc, char **argv)
                           "--fps N[:D] - with --y4m: the frame rate N/D frames per second (default=30:1)\n"
                           "--yuv-matrix 709|601 - with --y4m: the colour matrix, BT.709 or BT.601 (default=709)\n"
                           "--yuv-range limited|full - with --y4m: limited (Y 16..235, chroma 16..240) or full (0..255) range (default=limited)\n"
+                          "--frames FIRST[:COUNT] - with -i a directory of <row>_<col>.y4m files (a light-field video, one 8-bit YUV 4:2:0 file per camera): render time steps FIRST ... FIRST+COUNT-1 (default=0:1); the frames cross PCIe as they are, 1.5 bytes per pixel, and become the images on the GPU; with COUNT above 1 every step's files go to <-o>/fTTTT/ and --y4m FILE takes all steps' views in step order (with -n 1: the video of the moving scene from one virtual camera); not with --compare, --compare-methods or -g above 1 then\n"
+                          "--in-matrix 709|601 - with a light-field video: the colour matrix of its files (default=709)\n"
+                          "--in-range limited|full - with a light-field video: the range of its files (default: their XCOLORRANGE tag, else limited)\n"
+                          "--in-chroma bilinear|nearest - with a light-field video: how chroma is brought to full resolution (default=bilinear, the triangle filter of centre-sited chroma)\n"
                           "--compare DIR - after the render, compare every view with DIR/NN.png (the names -o writes; same size) on the GPU, all views in one pass: prints \"compare NN psnr <dB> ssim <index> maxdiff <largest byte difference> differing <colour bytes that differ>\" per view, then \"compare all psnr ... ssim ...\"; one GPU\n"
                           "--compare-methods - render the views with the other method first (STD if -m TEN_WM, TEN_WM if -m STD; same parameters), keep them on the GPU, render with -m and compare the two there; prints the lines of --compare; the stored images are those of -m; one GPU; not with --compare\n"
                           "--synthetic cols,rows,width,height[,seed] - use a generated light field instead of -i\n"
@@ -227,6 +232,66 @@ int main(int argc, char **argv)
         yuvRange = text == "full" ? LFI_YUV_FULL : LFI_YUV_LIMITED;
     }
 
+    int firstFrame = 0, frameSteps = 1;
+    if(args["--frames"])
+    {
+        // FIRST or FIRST:COUNT, whole numbers, COUNT at least 1
+        const std::string text = static_cast<std::string>(args["--frames"]);
+        const size_t cut = text.find(':');
+        const auto whole = [](const std::string &t, int &out) {
+            if(t.empty() || t.size() > 9 || t.find_first_not_of("0123456789") != std::string::npos)
+                return false;
+            out = std::stoi(t);
+            return true;
+        };
+        if(!whole(text.substr(0, cut), firstFrame) || (cut != std::string::npos && (!whole(text.substr(cut + 1), frameSteps) || frameSteps < 1)))
+        {
+            std::cerr << "--frames expects FIRST or FIRST:COUNT, whole numbers with COUNT at least 1 (e.g. 0:30)." << std::endl;
+            return EXIT_FAILURE;
+        }
+        if(frameSteps > 1 && (args["--compare"] || args["--compare-methods"] || (args["-g"] && static_cast<int>(args["-g"]) > 1)))
+        {
+            std::cerr << "--frames with more than one time step cannot be combined with --compare, --compare-methods or -g above 1." << std::endl;
+            return EXIT_FAILURE;
+        }
+    }
+    if((args["--frames"] || args["--in-matrix"] || args["--in-range"] || args["--in-chroma"]) && synthetic)
+    {
+        std::cerr << "--frames, --in-matrix, --in-range and --in-chroma belong to a light-field video: they need -i with a directory of .y4m files." << std::endl;
+        return EXIT_FAILURE;
+    }
+    int inMatrix = LFI_YUV_BT709, inRange = -1, inChroma = LFI_CHROMA_BILINEAR;
+    if(args["--in-matrix"])
+    {
+        const std::string text = static_cast<std::string>(args["--in-matrix"]);
+        if(text != "709" && text != "601")
+        {
+            std::cerr << "--in-matrix expects 709 or 601." << std::endl;
+            return EXIT_FAILURE;
+        }
+        inMatrix = text == "601" ? LFI_YUV_BT601 : LFI_YUV_BT709;
+    }
+    if(args["--in-range"])
+    {
+        const std::string text = static_cast<std::string>(args["--in-range"]);
+        if(text != "limited" && text != "full")
+        {
+            std::cerr << "--in-range expects limited or full." << std::endl;
+            return EXIT_FAILURE;
+        }
+        inRange = text == "full" ? LFI_YUV_FULL : LFI_YUV_LIMITED;
+    }
+    if(args["--in-chroma"])
+    {
+        const std::string text = static_cast<std::string>(args["--in-chroma"]);
+        if(text != "bilinear" && text != "nearest")
+        {
+            std::cerr << "--in-chroma expects bilinear or nearest." << std::endl;
+            return EXIT_FAILURE;
+        }
+        inChroma = text == "nearest" ? LFI_CHROMA_NEAREST : LFI_CHROMA_BILINEAR;
+    }
+
     if(args["--compare"] && args["--compare-methods"])
     {
         std::cerr << "--compare (against a directory) and --compare-methods (against the other method) print the same lines: use one of them." << std::endl;
@@ -386,7 +451,29 @@ int main(int argc, char **argv)
             interpolator->setCompareDir(static_cast<std::string>(args["--compare"]));
         if(args["--compare-methods"])
             interpolator->setCompareMethods(true);
-        interpolator->interpolate(outputPath, trajectory, focus, range, method, effect, aspect);
+        if((args["--frames"] || args["--in-matrix"] || args["--in-range"] || args["--in-chroma"]) && !interpolator->isVideo())
+            throw std::runtime_error("--frames, --in-matrix, --in-range and --in-chroma belong to a light-field video: -i has to be a directory of .y4m files");
+        if(interpolator->isVideo())
+        {
+            if(firstFrame + frameSteps > interpolator->frameCount())
+                throw std::runtime_error("--frames asks for time steps " + std::to_string(firstFrame) + " to " + std::to_string(firstFrame + frameSteps - 1) +
+                                         ", the videos have " + std::to_string(interpolator->frameCount()) + " frames");
+            interpolator->setInputYuv(inMatrix, inRange, inChroma);
+        }
+        for(int step = 0; step < frameSteps; step++)
+        {
+            std::string stepPath = outputPath;
+            if(interpolator->isVideo())
+                interpolator->setInputFrame(firstFrame + step);
+            if(frameSteps > 1)
+            {
+                // every time step's files in a directory of its own: <-o>/fTTTT
+                const std::string number = std::to_string(firstFrame + step);
+                stepPath = outputPath + "/f" + std::string(number.size() < 4 ? 4 - number.size() : 0, '0') + number;
+            }
+            interpolator->interpolate(stepPath, trajectory, focus, range, method, effect, aspect);
+        }
+        interpolator->finish();
     }
     catch(const std::exception &e)
     {

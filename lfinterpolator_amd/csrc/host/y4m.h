@@ -1,5 +1,5 @@
 // y4m.h — a YUV4MPEG2 (Y4M) writer for the I420 frames of lfi_download_views_yuv420 / lfi_render_stream_yuv420 (include/lfi.h): the
-// uncompressed video file `ffmpeg -i path.y4m` and players open as it is.
+// uncompressed video file `ffmpeg -i path.y4m` and players open as it is — and a reader of such files for lfi_upload_images_yuv420.
 //
 //     YUV4MPEG2 W<w> H<h> F<num>:<den> Ip A1:1 C420jpeg XCOLORRANGE=LIMITED|FULL\n        the header: progressive, square pixels, 4:2:0
 //     FRAME\n <frame_bytes>                                                                with centre-sited chroma (what the device computes)
@@ -12,6 +12,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <string>
+#include <vector>
 
 namespace lfi {
 
@@ -39,5 +40,43 @@ class Y4mWriter
 
 // n frames, frame k at frames + k·frameStrideBytes, as one file
 void writeY4m(const std::string &path, const uint8_t *frames, int n, size_t frameStrideBytes, int width, int height, int fpsNum, int fpsDen, bool fullRange);
+
+// What a Y4M file's header says.  Tokens may come in any order; W and H are required, unknown X tokens are ignored.
+struct Y4mInfo
+{
+    int width{0}, height{0};
+    int fpsNum{0}, fpsDen{0}; // 0:0 — no F token
+    int frames{0};
+    std::string chroma{"420jpeg"}; // the C tag as written, without the C (no C token: Y4M's default, 420jpeg)
+    bool centreSited{true};        // 420jpeg; 420mpeg2, 420paldv and plain 420 site their chroma up to a quarter pixel off centre
+    int fullRange{-1};             // XCOLORRANGE: 1 FULL, 0 LIMITED, -1 no such token
+};
+
+// Reads 8-bit 4:2:0 progressive Y4M files frame by frame.  Accepts C420jpeg, C420mpeg2, C420paldv and C420 (the frames have one layout;
+// the tag is reported); throws std::runtime_error for any other subsampling or bit depth, interlaced material (It, Ib, Im), a size below
+// 1, a malformed header or FRAME line and a truncated last frame.  Where the frames carry no parameters the number of frames comes from
+// the file's size, otherwise from a walk over the FRAME lines.
+class Y4mReader
+{
+    public:
+        explicit Y4mReader(const std::string &path);
+        ~Y4mReader();
+        Y4mReader(const Y4mReader &) = delete;
+        Y4mReader &operator=(const Y4mReader &) = delete;
+
+        const Y4mInfo &info() const { return header; }
+        size_t frameBytes() const { return bytes; }
+        int frameCount() const { return header.frames; }
+        void readFrame(int t, uint8_t *frame); // frameBytes() bytes of frame t in [0, frameCount()); throws when t is outside or the read fails
+
+    private:
+        std::FILE *file{nullptr};
+        std::string name;
+        Y4mInfo header;
+        size_t bytes{0};
+        long long dataStart{0};         // offset of the first FRAME line
+        std::vector<long long> offsets; // of every frame's bytes, where FRAME lines carry parameters; empty: dataStart + t·(6 + bytes) + 6
+        std::string readLine(size_t limit, bool &eof);
+};
 
 } // namespace lfi

@@ -43,6 +43,12 @@ def load_host_library() -> C.CDLL:
         lib.lfi_host_y4m_frame_bytes.argtypes = [C.c_int, C.c_int]
         lib.lfi_host_y4m_write.restype = C.c_int
         lib.lfi_host_y4m_write.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.c_size_t] + [C.c_int] * 5 + [C.c_char_p, C.c_size_t]
+        lib.lfi_host_y4m_info.restype = C.c_int
+        lib.lfi_host_y4m_info.argtypes = [C.c_char_p, C.c_void_p, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t]
+        lib.lfi_host_y4m_read.restype = C.c_int
+        lib.lfi_host_y4m_read.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_char_p, C.c_size_t]
+        lib.lfi_host_load_grid_y4m.restype = C.c_int
+        lib.lfi_host_load_grid_y4m.argtypes = [C.c_char_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_char_p, C.c_size_t]
         lib.lfi_host_build_view_offsets.restype = C.c_int
         lib.lfi_host_build_view_offsets.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_float, C.c_void_p, C.c_int,
                                                     C.c_void_p, C.c_char_p, C.c_size_t]
@@ -180,6 +186,46 @@ def write_y4m(path: str, frames: np.ndarray, width: int, height: int, fps=(30, 1
     if lib.lfi_host_y4m_write(str(path).encode(), frames.ctypes.data_as(C.c_void_p), frames.shape[0], frames.strides[0] if frames.size else 0, width, height,
                               int(fps[0]), int(fps[1]), int(bool(full_range)), err, len(err)) != 0:
         raise ValueError(err.value.decode())
+
+
+def read_y4m_info(path: str) -> dict:
+    """The header of a Y4M file and its number of frames (csrc/host/y4m.h, Y4mReader): width, height, fps (numerator, denominator; (0, 0)
+    without an F token), frames, chroma (the C tag without its C), centre_sited, full_range (True, False, or None without XCOLORRANGE).
+    Raises ValueError for what the reader refuses."""
+    lib = load_host_library()
+    out = np.zeros(8, dtype=np.int32)
+    tag = C.create_string_buffer(32)
+    err = C.create_string_buffer(512)
+    if lib.lfi_host_y4m_info(str(path).encode(), out.ctypes.data_as(C.c_void_p), tag, len(tag), err, len(err)) != 0:
+        raise ValueError(err.value.decode())
+    return dict(width=int(out[0]), height=int(out[1]), fps=(int(out[2]), int(out[3])), frames=int(out[4]),
+                full_range=None if out[5] < 0 else bool(out[5]), centre_sited=bool(out[6]), chroma=tag.value.decode())
+
+
+def read_y4m(path: str, first: int = 0, n: int | None = None) -> np.ndarray:
+    """Frames [first, first + n) (default: all from `first`) of a Y4M file as [n][frame_bytes] uint8 — what Context.upload_images_yuv420 takes."""
+    lib = load_host_library()
+    info = read_y4m_info(path)
+    n = info["frames"] - first if n is None else n
+    fb = lib.lfi_host_y4m_frame_bytes(info["width"], info["height"])
+    out = np.empty((max(n, 0), fb), dtype=np.uint8)
+    err = C.create_string_buffer(512)
+    if lib.lfi_host_y4m_read(str(path).encode(), first, n, out.ctypes.data_as(C.c_void_p), fb, err, len(err)) != 0:
+        raise ValueError(err.value.decode())
+    return out
+
+
+def load_grid_y4m(path: str, t: int = 0):
+    """LfLoader on a directory of <row>_<col>.y4m files (a light-field video): returns (cols, rows, width, height, frames, full_range,
+    [N][frame_bytes] u8 — frame t of every camera, g = col*rows + row).  Raises RuntimeError for what the loader refuses."""
+    lib = load_host_library()
+    out = np.zeros(6, dtype=np.int32)
+    _err_call(lib.lfi_host_load_grid_y4m, str(path).encode(), t, out.ctypes.data_as(C.c_void_p), None, 0)
+    cols, rows, w, h, frames, rng = (int(v) for v in out)
+    fb = lib.lfi_host_y4m_frame_bytes(w, h)
+    data = np.empty((cols * rows, fb), dtype=np.uint8)
+    _err_call(lib.lfi_host_load_grid_y4m, str(path).encode(), t, out.ctypes.data_as(C.c_void_p), data.ctypes.data_as(C.c_void_p), fb)
+    return cols, rows, w, h, frames, None if rng < 0 else bool(rng), data
 
 
 def build_view_offsets(cols: int, rows: int, width: int, height: int, trajectory: str, aspect: float, focus_v) -> np.ndarray:
