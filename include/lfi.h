@@ -554,6 +554,60 @@ int lfi_download_views_yuv420(lfi_ctx *ctx, int v0, int n, int matrix, int range
  * stride and row window, and wherever lfi_render_stream refuses. */
 int lfi_render_stream_yuv420(lfi_ctx *ctx, int method, int all_focus, const uint16_t *weights_fp16, int total_views, int matrix, int range,
                              uint8_t *host_out, size_t frame_stride_bytes);
+
+/* Video surfaces: a batch of 8-bit YUV 4:2:0 frames as decoders deliver and encoders take them — I420 or NV12, rows with a pitch, planes at
+ * offsets inside a frame, in host memory or in memory of the context's own GPU.  The conversions are those defined above
+ * (lfi_upload_images_yuv420, lfi_download_views_yuv420), bit for bit; the descriptor only says where the bytes lie.
+ * Geometry of a W x H frame, cw = (W + 1) >> 1, ch = (H + 1) >> 1: the Y plane starts at the frame's base, H rows of y_pitch bytes.  I420:
+ * the Cb plane at c_offset and the Cr plane at cr_offset, ch rows of c_pitch bytes each.  NV12: one plane at c_offset, ch rows of c_pitch
+ * bytes, byte 2*cx of a row Cb and byte 2*cx + 1 Cr.  A plane occupies rows * pitch bytes, which the caller's memory must cover; only the
+ * first W bytes of a Y row (cw of an I420 chroma row, 2*cw of an NV12 one) carry data: the rest is padding, never used as a value and
+ * never written.  Frame k lies at base + k * frame_stride. */
+enum { LFI_YUV_I420 = 0, LFI_YUV_NV12 = 1 };
+enum { LFI_MEM_HOST = 0, LFI_MEM_DEVICE = 1 };   /* DEVICE: memory of the context's own GPU */
+typedef struct lfi_yuv_surfaces {
+    int32_t format, memory;
+    void   *base;          /* frame 0 */
+    size_t  frame_stride;  /* bytes from one frame's base to the next one's */
+    size_t  y_pitch;       /* >= W */
+    size_t  c_offset;      /* from a frame's base to its chroma: NV12 the CbCr plane, I420 the Cb plane */
+    size_t  c_pitch;       /* NV12 >= 2*cw, I420 >= cw */
+    size_t  cr_offset;     /* I420: the Cr plane; NV12: must be 0 */
+} lfi_yuv_surfaces;
+/* LFI_OK if s describes n frames of width x height, else LFI_EINVAL: an unknown format or memory value, s or base NULL, width, height or n
+ * below 1; a pitch below its minimum; planes of one frame that overlap or are not in the order Y, chroma (I420: Y, Cb, Cr); cr_offset != 0
+ * with NV12; n > 1 with frame_stride below the frame's extent (the end of its last plane).  Context-free, needs no GPU. */
+int lfi_yuv_surfaces_check(const lfi_yuv_surfaces *s, int width, int height, int n);
+/* the tight layout at base (which may be NULL here, to be set later): y_pitch = W, the chroma right behind the Y plane with c_pitch = cw
+ * (I420; Cr right behind Cb) or 2*cw (NV12), frame_stride = W*H + 2*cw*ch for both.  An I420 result is lfi_upload_images_yuv420's frame.
+ * LFI_EINVAL: an unknown format or memory value, a size below 1, out NULL. */
+int lfi_yuv_surfaces_packed(int format, int memory, void *base, int width, int height, lfi_yuv_surfaces *out);
+/* lfi_upload_images_yuv420 from surfaces: fills every byte of images [g0, g0 + n), alpha included, from frames [0, n) of src.  Ordered like
+ * lfi_upload_image_async: the work goes on the copy stream behind the renders already enqueued, later users of the planes are ordered
+ * after it by an event, the source must stay valid and unchanged until lfi_upload_wait / lfi_sync; device surfaces must be complete when
+ * the call is made (the call does not know the stream that wrote them).  The source is only read.
+ *  - LFI_MEM_HOST: the frames' own bytes are copied with 2D copies that honour the pitches (an NV12 chroma plane is one copy; a tight batch
+ *    whose W is a multiple of 8 and whose H is even is one copy per chunk) into the staging buffer of lfi_upload_images_yuv420, in its
+ *    chunks of at most 16 frames or 256 MiB, each followed by one launch.
+ *  - LFI_MEM_DEVICE: where base, frame_stride, both pitches and the offsets are multiples of 16 the surfaces are read in place: no copy, no
+ *    staging buffer, ONE launch for all n frames.  Otherwise device-to-device 2D copies bring the frames into the staging buffer, in the
+ *    same chunks.  Nothing crosses PCIe either way.  The pointer must be device memory of the context's GPU that covers the n frames.
+ * LFI_EINVAL, the context usable, the grid and the staging buffer untouched: whatever lfi_upload_images_yuv420 refuses of grid, released
+ * inputs, row window, range of images, matrix, range and chroma; src refused by lfi_yuv_surfaces_check; LFI_MEM_DEVICE with a pointer that
+ * is not device memory of the context's device or whose allocation ends before the last frame does. */
+int lfi_upload_images_yuv(lfi_ctx *ctx, int g0, int n, int matrix, int range, int chroma, const lfi_yuv_surfaces *src);
+/* lfi_download_views_yuv420 into surfaces: views [v0, v0 + n) become frames [0, n) of dst.  Synchronous, ordered like
+ * lfi_download_views_yuv420; both view layouts are read in place; writes no view and no map.  ONLY the planes' own bytes of dst are
+ * written: pitch padding and gaps between planes and frames keep their values.
+ *  - LFI_MEM_HOST: one launch converts the views into device frames the context owns (those of lfi_download_views_yuv420), 2D copies that
+ *    honour the pitches carry them out.
+ *  - LFI_MEM_DEVICE: where base, frame_stride, both pitches and the offsets are multiples of 16 the kernel writes the caller's surfaces
+ *    directly (whole blocks as words, a ragged last block of a row byte by byte); otherwise through the device frames and device-to-device
+ *    2D copies.  The frames are complete when the call returns.
+ * LFI_EINVAL, the context usable and dst untouched: whatever lfi_download_views_yuv420 refuses of views, matrix, range and row window; dst
+ * refused by lfi_yuv_surfaces_check; LFI_MEM_DEVICE with a pointer that is not device memory of the context's device or whose allocation
+ * ends before the last frame does. */
+int lfi_download_views_yuv(lfi_ctx *ctx, int v0, int n, int matrix, int range, const lfi_yuv_surfaces *dst);
 int lfi_upload_map(lfi_ctx *ctx, int k, const uint8_t *rgba, size_t pitch_bytes); /* tests: inject a focus map */
 /* view v's map k (0 or 1) of the per-view maps (lfi_view_focus_maps).  Synchronous.  The upload is a test hook like lfi_upload_map (it
  * allocates the per-view maps if needed and does not put them in use: renders read them after a successful lfi_view_focus_maps). */

@@ -34,6 +34,12 @@ YUV_RANGES = {"limited": LFI_YUV_LIMITED, "full": LFI_YUV_FULL}
 LFI_CHROMA_BILINEAR = 0
 LFI_CHROMA_NEAREST = 1
 YUV_CHROMAS = {"bilinear": LFI_CHROMA_BILINEAR, "nearest": LFI_CHROMA_NEAREST}
+LFI_YUV_I420 = 0
+LFI_YUV_NV12 = 1
+YUV_FORMATS = {"i420": LFI_YUV_I420, "nv12": LFI_YUV_NV12}
+LFI_MEM_HOST = 0
+LFI_MEM_DEVICE = 1
+YUV_MEMORIES = {"host": LFI_MEM_HOST, "device": LFI_MEM_DEVICE}
 METHODS = {"STD": LFI_METHOD_STD, "TEN_WM": LFI_METHOD_TEN_WM, "FOCUS": LFI_KERNEL_FOCUS_ESTIMATE}
 
 # every symbol include/lfi.h declares
@@ -48,6 +54,7 @@ ABI_SYMBOLS = [
     "lfi_upload_view_map", "lfi_focus_curve", "lfi_focus_tiles", "lfi_focus_tiles_steps", "lfi_focus_tiles_passes", "lfi_download_quilt_scaled", "lfi_download_quilt_tiles_scaled",
     "lfi_keep_views", "lfi_compare_views", "lfi_set_focus_steps", "lfi_focus_steps", "lfi_download_native",
     "lfi_download_views_yuv420", "lfi_render_stream_yuv420", "lfi_upload_images_yuv420",
+    "lfi_yuv_surfaces_check", "lfi_yuv_surfaces_packed", "lfi_upload_images_yuv", "lfi_download_views_yuv",
 ]
 
 
@@ -97,6 +104,41 @@ class FocusCurveResult(C.Structure):
 class Lenticular(C.Structure):
     """lfi_lenticular: the lens sheet of lfi_download_native in units of 2^-32 lens periods (host.lenticular builds one from a calibration)"""
     _fields_ = [("x_step", C.c_uint32), ("y_step", C.c_uint32), ("phase0", C.c_uint32), ("views", C.c_int32), ("flags", C.c_uint32)]
+
+
+class YuvSurfaces(C.Structure):
+    """lfi_yuv_surfaces: a batch of YUV 4:2:0 frames — format, memory space, pitches and plane offsets (include/lfi.h).  `keep` holds whatever
+    owns the memory (a numpy array, a tensor) alive as long as the descriptor."""
+    _fields_ = [("format", C.c_int32), ("memory", C.c_int32), ("base", C.c_void_p), ("frame_stride", C.c_size_t), ("y_pitch", C.c_size_t),
+                ("c_offset", C.c_size_t), ("c_pitch", C.c_size_t), ("cr_offset", C.c_size_t)]
+    keep = None
+
+    @classmethod
+    def make(cls, fmt, memory, base: int, frame_stride: int, y_pitch: int, c_offset: int, c_pitch: int, cr_offset: int = 0, keep=None) -> "YuvSurfaces":
+        """from a raw pointer (a device one: e.g. a torch tensor's data_ptr()) plus layout; fmt: "i420" / "nv12", memory: "host" / "device"
+        (or the LFI_* values)"""
+        s = cls(YUV_FORMATS.get(fmt, fmt), YUV_MEMORIES.get(memory, memory), base, frame_stride, y_pitch, c_offset, c_pitch, cr_offset)
+        s.keep = keep
+        return s
+
+    @classmethod
+    def from_array(cls, fmt, frames: np.ndarray, y_pitch: int, c_offset: int, c_pitch: int, cr_offset: int = 0) -> "YuvSurfaces":
+        """host surfaces in a numpy array [n][P] uint8: frame k is row k, the frame stride is the array's"""
+        assert frames.dtype == np.uint8 and frames.ndim == 2 and frames.size and frames.strides[1] == 1
+        return cls.make(fmt, LFI_MEM_HOST, frames.ctypes.data, frames.strides[0], y_pitch, c_offset, c_pitch, cr_offset, keep=frames)
+
+    def check(self, width: int, height: int, n: int) -> bool:
+        """lfi_yuv_surfaces_check: does this describe n frames of width x height?"""
+        return load_hip_library().lfi_yuv_surfaces_check(C.byref(self), width, height, n) == 0
+
+
+def yuv_surfaces_packed(fmt, memory, base: int | None, width: int, height: int, keep=None) -> YuvSurfaces:
+    """lfi_yuv_surfaces_packed: the tight layout of width x height frames at `base` (None: to be set later)"""
+    s = YuvSurfaces()
+    if load_hip_library().lfi_yuv_surfaces_packed(YUV_FORMATS.get(fmt, fmt), YUV_MEMORIES.get(memory, memory), base, width, height, C.byref(s)) != 0:
+        raise LfiError("lfi_yuv_surfaces_packed: unknown format or memory, or a size below 1")
+    s.keep = keep
+    return s
 
 
 class MemoryInfo(C.Structure):
@@ -169,6 +211,10 @@ def load_hip_library() -> C.CDLL:
         "lfi_download_views_yuv420": (i, [vp, i, i, i, i, vp, sz]),
         "lfi_render_stream_yuv420": (i, [vp, i, i, vp, i, i, i, vp, sz]),
         "lfi_upload_images_yuv420": (i, [vp, i, i, i, i, i, vp, sz]),
+        "lfi_yuv_surfaces_check": (i, [C.POINTER(YuvSurfaces), i, i, i]),
+        "lfi_yuv_surfaces_packed": (i, [i, i, vp, i, i, C.POINTER(YuvSurfaces)]),
+        "lfi_upload_images_yuv": (i, [vp, i, i, i, i, i, C.POINTER(YuvSurfaces)]),
+        "lfi_download_views_yuv": (i, [vp, i, i, i, i, C.POINTER(YuvSurfaces)]),
         "lfi_alloc_pinned": (i, [sz, C.POINTER(vp)]),
         "lfi_free_pinned": (i, [vp]),
         "lfi_grid_modified": (i, [vp]),
@@ -304,6 +350,17 @@ class Context:
         assert frames.dtype == np.uint8 and frames.ndim == 2 and (frames.size == 0 or frames.strides[1] == 1)
         self._check(self._lib.lfi_upload_images_yuv420(self._h, g0, frames.shape[0], YUV_MATRICES.get(matrix, matrix), YUV_RANGES.get(range, range),
                                                        YUV_CHROMAS.get(chroma, chroma), _ptr(frames), frames.strides[0] if frames.size else 0))
+
+    def upload_images_yuv(self, surfaces: YuvSurfaces, n: int, g0: int = 0, matrix="709", range="limited", chroma="bilinear") -> None:
+        """Images [g0, g0 + n) from n frames of `surfaces` (lfi_upload_images_yuv): I420 or NV12, pitched, host or device memory; device
+        surfaces whose base, pitches, offsets and stride are multiples of 16 are read in place.  Ordered like upload_image_async: keep the
+        memory alive and unchanged until upload_wait / sync."""
+        self._check(self._lib.lfi_upload_images_yuv(self._h, g0, n, YUV_MATRICES.get(matrix, matrix), YUV_RANGES.get(range, range),
+                                                    YUV_CHROMAS.get(chroma, chroma), C.byref(surfaces) if surfaces is not None else None))
+
+    def yuv_surfaces_packed(self, fmt, memory="host", base: int | None = None, keep=None) -> YuvSurfaces:
+        """the tight layout of this context's frames (lfi_yuv_surfaces_packed): frame stride yuv420_frame_bytes() for both formats"""
+        return yuv_surfaces_packed(fmt, memory, base, self.width, self.height, keep)
 
     def attach_grid(self, device_ptr: int, nbytes: int) -> None:
         self._check(self._lib.lfi_attach_grid(self._h, C.c_void_p(device_ptr), nbytes))
@@ -622,6 +679,13 @@ class Context:
         self._check(self._lib.lfi_download_views_yuv420(self._h, v0, n, YUV_MATRICES.get(matrix, matrix), YUV_RANGES.get(range, range), _ptr(out),
                                                         out.strides[0] if out.size else 0))
         return out[:, :fb] if out.size else out
+
+    def download_views_yuv(self, surfaces: YuvSurfaces, n: int | None = None, v0: int = 0, matrix="709", range="limited") -> None:
+        """views [v0, v0 + n) (default: all from v0) into n frames of `surfaces` (lfi_download_views_yuv): only the planes' own bytes are
+        written; device surfaces whose base, pitches, offsets and stride are multiples of 16 are written by the kernel itself."""
+        n = self.views - v0 if n is None else n
+        self._check(self._lib.lfi_download_views_yuv(self._h, v0, n, YUV_MATRICES.get(matrix, matrix), YUV_RANGES.get(range, range),
+                                                     C.byref(surfaces) if surfaces is not None else None))
 
     def render_stream_yuv420(self, method, weights: np.ndarray, out: np.ndarray | None = None, all_focus: bool = False, matrix="709",
                              range="limited") -> np.ndarray:

@@ -12,6 +12,7 @@
 #include "native_image.hpp"
 #include "yuv420.hpp"
 #include "yuv420_upload.hpp"
+#include "yuv_surfaces.hpp"
 #include "lfi_rccl.hpp"
 
 extern "C" {
@@ -335,6 +336,243 @@ int lfi_upload_images_yuv420(lfi_ctx *ctx, int g0, int n, int matrix, int range,
         a.rows16 = g.W % 4 == 0; // the grid starts on a 16-byte boundary (hipMalloc; lfi_attach_grid checks), an image is W·H·4 bytes
         a.k = lfi::YUV_IN_COEFFS[matrix * 2 + range];
         LFI_HIP(ctx, lfi::launch_yuv420_expand(st, chroma == LFI_CHROMA_NEAREST, a, nk));
+    }
+    touch_images(ctx, g0, g0 + n);
+    return LFI_OK;
+}
+
+// ---- YUV 4:2:0 surfaces (yuv_surfaces.hpp) ----------------------------------------------------------------------------------------------------
+
+namespace {
+
+// rows · pitch, SIZE_MAX where that overflows
+size_t plane_bytes(size_t rows, size_t pitch)
+{
+    return pitch > SIZE_MAX / rows ? SIZE_MAX : rows * pitch;
+}
+
+// a + b, SIZE_MAX where that overflows
+size_t add_sat(size_t a, size_t b)
+{
+    return a > SIZE_MAX - b ? SIZE_MAX : a + b;
+}
+
+// why s does not describe n frames of width × height (NULL: it does); *extent: the end of a frame's last plane
+const char *yuv_surfaces_fault(const lfi_yuv_surfaces *s, int width, int height, int n, size_t *extent)
+{
+    if(!s || !s->base)
+        return "the descriptor or its base is NULL";
+    if((s->format != LFI_YUV_I420 && s->format != LFI_YUV_NV12) || (s->memory != LFI_MEM_HOST && s->memory != LFI_MEM_DEVICE))
+        return "unknown format (LFI_YUV_I420, LFI_YUV_NV12) or memory (LFI_MEM_HOST, LFI_MEM_DEVICE)";
+    if(width < 1 || height < 1 || n < 1)
+        return "width, height and n must be at least 1";
+    const size_t W = (size_t)width, H = (size_t)height, cw = (W + 1) >> 1, ch = (H + 1) >> 1;
+    const bool nv12 = s->format == LFI_YUV_NV12;
+    if(s->y_pitch < W || s->c_pitch < (nv12 ? 2 * cw : cw))
+        return "a pitch is below its minimum (y_pitch >= W; c_pitch >= cw for I420, 2*cw for NV12)";
+    const size_t y_end = plane_bytes(H, s->y_pitch), c_bytes = plane_bytes(ch, s->c_pitch);
+    if(s->c_offset < y_end)
+        return "the planes overlap or are out of order: c_offset is below H * y_pitch";
+    size_t end = add_sat(s->c_offset, c_bytes);
+    if(nv12)
+    {
+        if(s->cr_offset != 0)
+            return "cr_offset must be 0 with NV12";
+    }
+    else
+    {
+        if(s->cr_offset < end)
+            return "the planes overlap or are out of order: cr_offset is below c_offset + ch * c_pitch";
+        end = add_sat(s->cr_offset, c_bytes);
+    }
+    if(end == SIZE_MAX)
+        return "the frame's extent does not fit size_t";
+    if(n > 1 && (s->frame_stride < end || s->frame_stride > (SIZE_MAX - end) / (size_t)(n - 1)))
+        return "frame_stride is below the frame's extent (the end of its last plane)";
+    if(extent)
+        *extent = end;
+    return nullptr;
+}
+
+// the staged frames of a chunk as surfaces: the padded planes of yuv_geometry; NV12's chroma rows are y_pitch bytes (2·c_pitch)
+lfi::YuvSurfaces staged_surfaces(const lfi::YuvGeometry &g, int format, uint8_t *dev)
+{
+    lfi::YuvSurfaces s{};
+    const size_t y_plane = (size_t)g.y_pitch * g.y_rows;
+    s.base = dev;
+    s.frame_stride = g.dev_frame_bytes;
+    s.y_pitch = g.y_pitch;
+    s.c_offset = y_plane;
+    s.c_pitch = format == LFI_YUV_NV12 ? g.y_pitch : g.c_pitch;
+    s.cr_offset = format == LFI_YUV_NV12 ? 0 : y_plane + (size_t)g.c_pitch * g.ch;
+    return s;
+}
+
+// device surfaces a kernel may address directly: every load and word store of yuv_surfaces.hpp is then aligned and inside its row
+bool yuv_surfaces_in_place(const lfi_yuv_surfaces &s)
+{
+    return s.memory == LFI_MEM_DEVICE && (reinterpret_cast<uintptr_t>(s.base) | s.frame_stride | s.y_pitch | s.c_offset | s.c_pitch | s.cr_offset) % 16 == 0 &&
+           s.y_pitch <= UINT32_MAX && s.c_pitch <= UINT32_MAX;
+}
+
+lfi::YuvSurfaces caller_surfaces(const lfi_yuv_surfaces &s)
+{
+    lfi::YuvSurfaces k{};
+    k.base = static_cast<uint8_t *>(s.base);
+    k.frame_stride = s.frame_stride, k.c_offset = s.c_offset, k.cr_offset = s.cr_offset;
+    k.y_pitch = (uint32_t)s.y_pitch, k.c_pitch = (uint32_t)s.c_pitch;
+    return k;
+}
+
+// the staged frame IS the caller's frame: one copy moves it (W a multiple of 8, H even, the tight layout)
+bool yuv_surfaces_like_staged(const lfi_yuv_surfaces &s, const lfi::YuvGeometry &g)
+{
+    const lfi::YuvSurfaces t = staged_surfaces(g, s.format, nullptr);
+    return g.tight && s.y_pitch == t.y_pitch && s.c_pitch == t.c_pitch && s.c_offset == t.c_offset && s.cr_offset == t.cr_offset;
+}
+
+// LFI_MEM_DEVICE: base must be device memory of the context's own device, in an allocation that covers the n frames
+int check_device_surfaces(lfi_ctx *ctx, const char *who, const lfi_yuv_surfaces &s, size_t extent, int n)
+{
+    hipPointerAttribute_t attr{};
+    if(hipPointerGetAttributes(&attr, s.base) != hipSuccess)
+    {
+        (void)hipGetLastError(); // a pointer the runtime does not know: not an error of the context's
+        return fail(ctx, LFI_EINVAL, std::string(who) + ": LFI_MEM_DEVICE needs a pointer to device memory, the runtime does not know this one");
+    }
+    if(attr.type != hipMemoryTypeDevice || attr.device != ctx->device)
+        return fail(ctx, LFI_EINVAL, std::string(who) + ": LFI_MEM_DEVICE needs a pointer to device memory of the context's own device");
+    hipDeviceptr_t a_base = nullptr;
+    size_t a_bytes = 0;
+    if(hipMemGetAddressRange(&a_base, &a_bytes, s.base) != hipSuccess)
+    {
+        (void)hipGetLastError();
+        return fail(ctx, LFI_EINVAL, std::string(who) + ": LFI_MEM_DEVICE needs a pointer into a device allocation");
+    }
+    const size_t before = (size_t)(static_cast<const uint8_t *>(s.base) - static_cast<const uint8_t *>(a_base));
+    if(before > a_bytes || s.frame_stride * (size_t)(n - 1) + extent > a_bytes - before)
+        return fail(ctx, LFI_EINVAL, std::string(who) + ": the device allocation ends before the last frame does");
+    return LFI_OK;
+}
+
+// the frames' own bytes between n caller frames (from frame k0 on) and n staged ones at dev, on st; to_staged: caller → staged
+hipError_t enqueue_surface_copies(hipStream_t st, const lfi_yuv_surfaces &s, int k0, int n, const lfi::YuvGeometry &g, uint8_t *dev, bool to_staged)
+{
+    const hipMemcpyKind kind = s.memory == LFI_MEM_DEVICE ? hipMemcpyDeviceToDevice : to_staged ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost;
+    const lfi::YuvSurfaces t = staged_surfaces(g, s.format, dev);
+    uint8_t *base = static_cast<uint8_t *>(s.base) + s.frame_stride * (size_t)k0;
+    const bool nv12 = s.format == LFI_YUV_NV12;
+    if(yuv_surfaces_like_staged(s, g))
+    {
+        if(s.frame_stride == g.frame_bytes || n == 1)
+            return to_staged ? hipMemcpyAsync(dev, base, g.frame_bytes * n, kind, st) : hipMemcpyAsync(base, dev, g.frame_bytes * n, kind, st);
+        return to_staged ? hipMemcpy2DAsync(dev, g.frame_bytes, base, s.frame_stride, g.frame_bytes, n, kind, st)
+                         : hipMemcpy2DAsync(base, s.frame_stride, dev, g.frame_bytes, g.frame_bytes, n, kind, st);
+    }
+    for(int k = 0; k < n; k++)
+    {
+        uint8_t *f = base + s.frame_stride * (size_t)k, *d = dev + t.frame_stride * (size_t)k;
+        // plane, caller's pitch, staged pitch, bytes per row, rows
+        const struct
+        {
+            size_t f_off, d_off, f_pitch, d_pitch, width, rows;
+        } planes[3] = {{0, 0, s.y_pitch, t.y_pitch, g.W, g.H},
+                       {s.c_offset, t.c_offset, s.c_pitch, t.c_pitch, nv12 ? 2 * (size_t)g.cw : g.cw, g.ch},
+                       {s.cr_offset, t.cr_offset, s.c_pitch, t.c_pitch, g.cw, g.ch}};
+        for(int p = 0; p < (nv12 ? 2 : 3); p++)
+        {
+            const auto &pl = planes[p];
+            const hipError_t e = to_staged ? hipMemcpy2DAsync(d + pl.d_off, pl.d_pitch, f + pl.f_off, pl.f_pitch, pl.width, pl.rows, kind, st)
+                                           : hipMemcpy2DAsync(f + pl.f_off, pl.f_pitch, d + pl.d_off, pl.d_pitch, pl.width, pl.rows, kind, st);
+            if(e != hipSuccess)
+                return e;
+        }
+    }
+    return hipSuccess;
+}
+
+} // namespace
+
+int lfi_yuv_surfaces_check(const lfi_yuv_surfaces *s, int width, int height, int n)
+{
+    return yuv_surfaces_fault(s, width, height, n, nullptr) ? LFI_EINVAL : LFI_OK;
+}
+
+int lfi_yuv_surfaces_packed(int format, int memory, void *base, int width, int height, lfi_yuv_surfaces *out)
+{
+    if((format != LFI_YUV_I420 && format != LFI_YUV_NV12) || (memory != LFI_MEM_HOST && memory != LFI_MEM_DEVICE) || width < 1 || height < 1 || !out)
+        return LFI_EINVAL;
+    const lfi::YuvGeometry g = lfi::yuv_geometry(width, height);
+    const bool nv12 = format == LFI_YUV_NV12;
+    out->format = format, out->memory = memory;
+    out->base = base;
+    out->frame_stride = g.frame_bytes;
+    out->y_pitch = g.W;
+    out->c_offset = (size_t)g.W * g.H;
+    out->c_pitch = nv12 ? 2 * (size_t)g.cw : g.cw;
+    out->cr_offset = nv12 ? 0 : out->c_offset + (size_t)g.cw * g.ch;
+    return LFI_OK;
+}
+
+int lfi_upload_images_yuv(lfi_ctx *ctx, int g0, int n, int matrix, int range, int chroma, const lfi_yuv_surfaces *src)
+{
+    if(!ctx)
+        return LFI_EINVAL;
+    if(ctx->inputs_released)
+        return fail(ctx, LFI_EINVAL, "lfi_upload_images_yuv: the RGBA inputs were released (lfi_release_inputs): lfi_set_grid and upload the images again");
+    if(!ctx->grid)
+        return fail(ctx, LFI_EINVAL, "lfi_set_grid has not been called");
+    if(ctx->windowed)
+        return fail(ctx, LFI_EINVAL, "lfi_upload_images_yuv: YUV 4:2:0 frames need whole images: a 2x2 chroma block may straddle the row window's band");
+    if(n < 1 || g0 < 0 || (long)g0 + n > ctx->n)
+        return fail(ctx, LFI_EINVAL, "lfi_upload_images_yuv: needs n >= 1 images starting at g0 inside [0, N)");
+    if((matrix != LFI_YUV_BT709 && matrix != LFI_YUV_BT601) || (range != LFI_YUV_LIMITED && range != LFI_YUV_FULL) ||
+       (chroma != LFI_CHROMA_BILINEAR && chroma != LFI_CHROMA_NEAREST))
+        return fail(ctx, LFI_EINVAL, "lfi_upload_images_yuv: unknown YUV matrix (LFI_YUV_BT709, LFI_YUV_BT601), range (LFI_YUV_LIMITED, LFI_YUV_FULL) or chroma "
+                                     "filter (LFI_CHROMA_BILINEAR, LFI_CHROMA_NEAREST)");
+    size_t extent = 0;
+    if(const char *fault = yuv_surfaces_fault(src, ctx->width, ctx->height, n, &extent))
+        return fail(ctx, LFI_EINVAL, std::string("lfi_upload_images_yuv: ") + fault);
+    if(int rc = bind(ctx))
+        return rc;
+    if(src->memory == LFI_MEM_DEVICE)
+        if(int rc = check_device_surfaces(ctx, "lfi_upload_images_yuv", *src, extent, n))
+            return rc;
+    if(int rc = ensure_copy_stream(ctx))
+        return rc;
+    const lfi::YuvGeometry g = lfi::yuv_geometry(ctx->width, ctx->height);
+    const bool in_place = yuv_surfaces_in_place(*src);
+    // staged: chunks of at most 16 frames or 256 MiB, at least one frame, in lfi_upload_images_yuv420's buffer and under its rules: a
+    // chunk's copies and its launch follow each other on the copy stream.  In place: one chunk of all n frames, no buffer
+    const int chunk = in_place ? n : (int)std::max<size_t>(1, std::min<size_t>(16, ((size_t)256 << 20) / g.dev_frame_bytes));
+    const size_t need = in_place ? 0 : g.dev_frame_bytes * std::min(chunk, n);
+    if(ctx->yuv_in.bytes() < need)
+    {
+        LFI_HIP(ctx, hipStreamSynchronize(ctx->copy_stream)); // an earlier call's chunks may still be in the buffer that goes
+        LFI_HIP(ctx, ctx->yuv_in.reserve(need));
+    }
+    if(!ctx->uploads_pending)
+    {
+        // first copy of a batch: renders already enqueued on the compute stream may still read the planes
+        LFI_HIP(ctx, hipEventRecord(ctx->ev_order, ctx->stream));
+        LFI_HIP(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->ev_order, 0));
+    }
+    ctx->uploads_pending = true; // from here on something may be enqueued on the copy stream
+    hipStream_t st = ctx->copy_stream;
+    for(int k0 = 0; k0 < n; k0 += chunk)
+    {
+        const int nk = std::min(chunk, n - k0);
+        if(!in_place)
+            LFI_HIP(ctx, enqueue_surface_copies(st, *src, k0, nk, g, ctx->yuv_in.get(), true));
+        lfi::YuvsInArgs a{};
+        a.s = in_place ? caller_surfaces(*src) : staged_surfaces(g, src->format, ctx->yuv_in.get());
+        a.dst = ctx->grid.get() + in_plane_bytes(ctx) * (size_t)(g0 + k0);
+        a.image_stride = in_plane_bytes(ctx);
+        a.W = g.W, a.H = g.H, a.cw = g.cw, a.ch = g.ch;
+        a.blocks_x = g.y_pitch / lfi::YUV_BLOCK_W;
+        a.rows16 = g.W % 4 == 0; // the grid starts on a 16-byte boundary (hipMalloc; lfi_attach_grid checks), an image is W·H·4 bytes
+        a.k = lfi::YUV_IN_COEFFS[matrix * 2 + range];
+        LFI_HIP(ctx, lfi::launch_yuvs_expand(st, src->format, chroma == LFI_CHROMA_NEAREST, a, nk));
     }
     touch_images(ctx, g0, g0 + n);
     return LFI_OK;
@@ -1403,6 +1641,46 @@ int lfi_download_views_yuv420(lfi_ctx *ctx, int v0, int n, int matrix, int range
     LFI_HIP(ctx, ctx->yuv[0].reserve(g.dev_frame_bytes * n));
     LFI_HIP(ctx, enqueue_yuv_convert(ctx, ctx->stream, ctx->views.get(), v0, n, g, matrix, range, ctx->yuv[0].get()));
     LFI_HIP(ctx, enqueue_yuv_copies(ctx->stream, ctx->yuv[0].get(), n, g, out, frame_stride_bytes));
+    LFI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return LFI_OK;
+}
+
+int lfi_download_views_yuv(lfi_ctx *ctx, int v0, int n, int matrix, int range, const lfi_yuv_surfaces *dst)
+{
+    if(!ctx)
+        return LFI_EINVAL;
+    if(!ctx->views || !ctx->have_params)
+        return fail(ctx, LFI_EINVAL, "nothing rendered yet");
+    if(n < 1 || v0 < 0 || (long)v0 + n > ctx->views_n)
+        return fail(ctx, LFI_EINVAL, "lfi_download_views_yuv: needs n >= 1 views starting at v0 inside [0, views)");
+    if(ctx->windowed)
+        return fail(ctx, LFI_EINVAL, "lfi_download_views_yuv: YUV 4:2:0 frames need whole views: a 2x2 chroma block may straddle the row window's band");
+    if((matrix != LFI_YUV_BT709 && matrix != LFI_YUV_BT601) || (range != LFI_YUV_LIMITED && range != LFI_YUV_FULL))
+        return fail(ctx, LFI_EINVAL, "lfi_download_views_yuv: unknown YUV matrix (LFI_YUV_BT709, LFI_YUV_BT601) or range (LFI_YUV_LIMITED, LFI_YUV_FULL)");
+    size_t extent = 0;
+    if(const char *fault = yuv_surfaces_fault(dst, ctx->width, ctx->height, n, &extent))
+        return fail(ctx, LFI_EINVAL, std::string("lfi_download_views_yuv: ") + fault);
+    if(int rc = bind(ctx))
+        return rc;
+    if(dst->memory == LFI_MEM_DEVICE)
+        if(int rc = check_device_surfaces(ctx, "lfi_download_views_yuv", *dst, extent, n))
+            return rc;
+    const lfi::YuvGeometry g = lfi::yuv_geometry(ctx->width, ctx->height);
+    const bool in_place = yuv_surfaces_in_place(*dst), planar = ctx->out_layout == LFI_LAYOUT_PLANAR_RGB;
+    if(!in_place)
+        LFI_HIP(ctx, ctx->yuv[0].reserve(g.dev_frame_bytes * n));
+    lfi::YuvsOutArgs a{};
+    a.src = ctx->views.get() + (size_t)v0 * out_plane_bytes(ctx);
+    a.s = in_place ? caller_surfaces(*dst) : staged_surfaces(g, dst->format, ctx->yuv[0].get());
+    a.view_stride = out_plane_bytes(ctx);
+    a.W = g.W, a.H = g.H, a.pitch = planar ? view_pitch(ctx) : 0;
+    a.cw = g.cw, a.ch = g.ch;
+    a.blocks_x = g.y_pitch / lfi::YUV_BLOCK_W;
+    a.rows16 = g.W % 4 == 0; // the views start on 16-byte boundaries (hipMalloc; lfi_attach_views checks), a view is W·H·4 bytes
+    a.k = lfi::YUV_COEFFS[matrix * 2 + range];
+    LFI_HIP(ctx, lfi::launch_yuvs_convert(ctx->stream, planar, dst->format, a, n));
+    if(!in_place)
+        LFI_HIP(ctx, enqueue_surface_copies(ctx->stream, *dst, 0, n, g, ctx->yuv[0].get(), false));
     LFI_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return LFI_OK;
 }

@@ -98,27 +98,22 @@ __device__ inline uint32_t yuv_chroma(const int32_t (&c)[3], const uint32_t sr, 
     return v < 255u ? v : 255u;
 }
 
+// The R, G, B of a lane's block of 8 columns × 2 rows (rows ya and yb, columns x0 … x0 + 7 clamped to W − 1) of one view: RGBA planes
+// [H][W], or (PLANAR) byte planes [R,G,B][H][pitch].  whole: all 8 columns lie inside the view
 template <bool PLANAR>
-__global__ void __launch_bounds__(YUV_LANES_X *YUV_BLOCK_ROWS) yuv420_convert(const YuvArgs a)
+__device__ __forceinline__ void yuv_load_block(const uint8_t *view, const uint32_t W, const uint32_t H, const uint32_t pitch, const uint32_t rows16,
+                                               const uint32_t x0, const uint32_t ya, const uint32_t yb, const bool whole, uint32_t (&r)[2][8],
+                                               uint32_t (&g)[2][8], uint32_t (&b)[2][8])
 {
-    const uint32_t bx = blockIdx.x * YUV_LANES_X + threadIdx.x;
-    const uint32_t by = blockIdx.y * YUV_BLOCK_ROWS + threadIdx.y; // wave-uniform
-    if(bx >= a.blocks_x || by >= a.ch)
-        return;
-    const uint32_t x0 = bx * YUV_BLOCK_W;
-    const uint32_t ya = by * YUV_BLOCK_H, yb = ya + 1u < a.H ? ya + 1u : a.H - 1u; // ya < H: by < ch
-    const uint8_t *view = a.src + (size_t)blockIdx.z * a.view_stride;
-    const bool whole = x0 + YUV_BLOCK_W <= a.W; // all 8 columns inside the view
-    uint32_t r[2][8], g[2][8], b[2][8];
     if constexpr(PLANAR)
     {
         // every row is `pitch` bytes long and pitch ≥ y_pitch: the 8-byte load stays inside it; the bytes beyond the view are replaced
-        const uint32_t last = whole ? 7u : a.W - 1u - x0; // the block's last column inside the view (x0 < W: x0 < y_pitch < W + 8)
-        const size_t plane = (size_t)a.H * a.pitch;
+        const uint32_t last = whole ? 7u : W - 1u - x0; // the block's last column inside the view (x0 < W: x0 < y_pitch < W + 8)
+        const size_t plane = (size_t)H * pitch;
 #pragma unroll
         for(int j = 0; j < 2; j++)
         {
-            const uint8_t *row = view + (size_t)(j ? yb : ya) * a.pitch + x0;
+            const uint8_t *row = view + (size_t)(j ? yb : ya) * pitch + x0;
             const uint2 pr = *reinterpret_cast<const uint2 *>(row);
             const uint2 pg = *reinterpret_cast<const uint2 *>(row + plane);
             const uint2 pb = *reinterpret_cast<const uint2 *>(row + 2 * plane);
@@ -147,9 +142,9 @@ __global__ void __launch_bounds__(YUV_LANES_X *YUV_BLOCK_ROWS) yuv420_convert(co
 #pragma unroll
         for(int j = 0; j < 2; j++)
         {
-            const uint32_t *row = px + (size_t)(j ? yb : ya) * a.W;
+            const uint32_t *row = px + (size_t)(j ? yb : ya) * W;
             uint32_t p[8];
-            if(whole && a.rows16)
+            if(whole && rows16)
             {
                 const uint4 lo = *reinterpret_cast<const uint4 *>(row + x0), hi = *reinterpret_cast<const uint4 *>(row + x0 + 4);
                 p[0] = lo.x, p[1] = lo.y, p[2] = lo.z, p[3] = lo.w, p[4] = hi.x, p[5] = hi.y, p[6] = hi.z, p[7] = hi.w;
@@ -158,13 +153,39 @@ __global__ void __launch_bounds__(YUV_LANES_X *YUV_BLOCK_ROWS) yuv420_convert(co
             {
 #pragma unroll
                 for(int i = 0; i < 8; i++)
-                    p[i] = row[x0 + i < a.W ? x0 + i : a.W - 1u];
+                    p[i] = row[x0 + i < W ? x0 + i : W - 1u];
             }
 #pragma unroll
             for(int i = 0; i < 8; i++)
                 r[j][i] = p[i] & 0xffu, g[j][i] = (p[i] >> 8) & 0xffu, b[j][i] = (p[i] >> 16) & 0xffu;
         }
     }
+}
+
+// Cb and Cr of the block's chroma column i: the sums over its four pixels
+__device__ __forceinline__ void yuv_block_chroma(const YuvCoeffs &k, const uint32_t (&r)[2][8], const uint32_t (&g)[2][8], const uint32_t (&b)[2][8], const int i,
+                                                 uint32_t &cb, uint32_t &cr)
+{
+    const uint32_t sr = r[0][2 * i] + r[0][2 * i + 1] + r[1][2 * i] + r[1][2 * i + 1];
+    const uint32_t sg = g[0][2 * i] + g[0][2 * i + 1] + g[1][2 * i] + g[1][2 * i + 1];
+    const uint32_t sb = b[0][2 * i] + b[0][2 * i + 1] + b[1][2 * i] + b[1][2 * i + 1];
+    cb = yuv_chroma(k.cb, sr, sg, sb);
+    cr = yuv_chroma(k.cr, sr, sg, sb);
+}
+
+template <bool PLANAR>
+__global__ void __launch_bounds__(YUV_LANES_X *YUV_BLOCK_ROWS) yuv420_convert(const YuvArgs a)
+{
+    const uint32_t bx = blockIdx.x * YUV_LANES_X + threadIdx.x;
+    const uint32_t by = blockIdx.y * YUV_BLOCK_ROWS + threadIdx.y; // wave-uniform
+    if(bx >= a.blocks_x || by >= a.ch)
+        return;
+    const uint32_t x0 = bx * YUV_BLOCK_W;
+    const uint32_t ya = by * YUV_BLOCK_H, yb = ya + 1u < a.H ? ya + 1u : a.H - 1u; // ya < H: by < ch
+    const uint8_t *view = a.src + (size_t)blockIdx.z * a.view_stride;
+    const bool whole = x0 + YUV_BLOCK_W <= a.W; // all 8 columns inside the view
+    uint32_t r[2][8], g[2][8], b[2][8];
+    yuv_load_block<PLANAR>(view, a.W, a.H, a.pitch, a.rows16, x0, ya, yb, whole, r, g, b);
     uint8_t *frame = a.out + (size_t)blockIdx.z * a.frame_stride;
 #pragma unroll
     for(int j = 0; j < 2; j++)
@@ -182,11 +203,10 @@ __global__ void __launch_bounds__(YUV_LANES_X *YUV_BLOCK_ROWS) yuv420_convert(co
 #pragma unroll
     for(int i = 0; i < 4; i++)
     {
-        const uint32_t sr = r[0][2 * i] + r[0][2 * i + 1] + r[1][2 * i] + r[1][2 * i + 1];
-        const uint32_t sg = g[0][2 * i] + g[0][2 * i + 1] + g[1][2 * i] + g[1][2 * i + 1];
-        const uint32_t sb = b[0][2 * i] + b[0][2 * i + 1] + b[1][2 * i] + b[1][2 * i + 1];
-        cb |= yuv_chroma(a.k.cb, sr, sg, sb) << (8 * i);
-        cr |= yuv_chroma(a.k.cr, sr, sg, sb) << (8 * i);
+        uint32_t u, v;
+        yuv_block_chroma(a.k, r, g, b, i, u, v);
+        cb |= u << (8 * i);
+        cr |= v << (8 * i);
     }
     const size_t y_plane = (size_t)a.y_pitch * (2u * a.ch), c_plane = (size_t)a.c_pitch * a.ch;
     uint8_t *c_row = frame + y_plane + (size_t)by * a.c_pitch + 4u * bx;

@@ -76,6 +76,70 @@ __device__ inline uint32_t yuv_in_pixel(const YuvInCoeffs &k, const int32_t y, c
     return r | (g << 8) | (b << 16) | 0xff000000u;
 }
 
+// the bytes of an 8-byte piece
+__device__ __forceinline__ void yuv_in_bytes(const uint2 p, uint32_t (&b)[8])
+{
+#pragma unroll
+    for(int i = 0; i < 8; i++)
+        b[i] = ((i < 4 ? p.x : p.y) >> (8 * (i & 3))) & 0xffu;
+}
+
+// BILINEAR: the six chroma columns 4bx − 1 … 4bx + 4 of a lane, clamped to [0, cw − 1], as bit positions in its window of six bytes
+// [column 4bx − 1 | the lane's own four | column 4bx + 4]: cw − 1 ≥ 4bx (x0 < W), so every clamped column lies in the window and a clamped
+// one is a byte of the lane's own four
+__device__ __forceinline__ void yuv_in_columns(const uint32_t bx, const uint32_t cw, uint32_t (&sh)[6])
+{
+    const int32_t c0 = 4 * (int32_t)bx - 1;
+#pragma unroll
+    for(int i = 0; i < 6; i++)
+    {
+        const int32_t c = c0 + i;
+        sh[i] = 8u * (uint32_t)((c < 0 ? 0 : c > (int32_t)cw - 1 ? (int32_t)cw - 1 : c) - c0);
+    }
+}
+
+// h[i] = 3·(centre column of pixel column i) + (its neighbour column) of one chroma row's window
+__device__ __forceinline__ void yuv_in_row(const uint64_t win, const uint32_t (&sh)[6], int32_t (&h)[8])
+{
+    int32_t c[6];
+#pragma unroll
+    for(int i = 0; i < 6; i++)
+        c[i] = (int32_t)((uint32_t)(win >> sh[i]) & 0xffu);
+#pragma unroll
+    for(int i = 0; i < 8; i++)
+        h[i] = 3 * c[1 + (i >> 1)] + c[(i & 1) ? 2 + (i >> 1) : (i >> 1)];
+}
+
+// a block's pixels into its image: out addresses pixel (x0, ya) of rows of W pixels.  Whole blocks of 16-byte aligned rows leave as 16-byte
+// stores, ragged ones and unaligned rows pixel by pixel; two_rows: row ya + 1 exists
+__device__ __forceinline__ void yuv_in_store(uint32_t *out, const uint32_t W, const uint32_t x0, const bool two_rows, const uint32_t rows16,
+                                             const uint32_t (&px)[2][8])
+{
+    if(x0 + YUV_BLOCK_W <= W && rows16)
+    {
+        uint4 *row = reinterpret_cast<uint4 *>(out);
+        row[0] = uint4{px[0][0], px[0][1], px[0][2], px[0][3]};
+        row[1] = uint4{px[0][4], px[0][5], px[0][6], px[0][7]};
+        if(two_rows)
+        {
+            row = reinterpret_cast<uint4 *>(out + W);
+            row[0] = uint4{px[1][0], px[1][1], px[1][2], px[1][3]};
+            row[1] = uint4{px[1][4], px[1][5], px[1][6], px[1][7]};
+        }
+    }
+    else
+    {
+#pragma unroll
+        for(int i = 0; i < 8; i++)
+            if(x0 + i < W)
+            {
+                out[i] = px[0][i];
+                if(two_rows)
+                    out[W + i] = px[1][i];
+            }
+    }
+}
+
 template <bool NEAREST>
 __global__ void __launch_bounds__(YUV_LANES_X *YUV_BLOCK_ROWS) yuv420_expand(const YuvInArgs a)
 {
@@ -90,12 +154,7 @@ __global__ void __launch_bounds__(YUV_LANES_X *YUV_BLOCK_ROWS) yuv420_expand(con
     uint32_t y[2][8];
 #pragma unroll
     for(int j = 0; j < 2; j++)
-    {
-        const uint2 p = *reinterpret_cast<const uint2 *>(frame + (size_t)(ya + j) * a.y_pitch + x0);
-#pragma unroll
-        for(int i = 0; i < 8; i++)
-            y[j][i] = ((i < 4 ? p.x : p.y) >> (8 * (i & 3))) & 0xffu;
-    }
+        yuv_in_bytes(*reinterpret_cast<const uint2 *>(frame + (size_t)(ya + j) * a.y_pitch + x0), y[j]);
     // chroma in sixteenths of the 16 pixels
     int32_t su[2][8], sv[2][8];
     if constexpr(NEAREST)
@@ -108,16 +167,8 @@ __global__ void __launch_bounds__(YUV_LANES_X *YUV_BLOCK_ROWS) yuv420_expand(con
     }
     else
     {
-        // the six chroma columns 4bx − 1 … 4bx + 4, clamped to [0, cw − 1], as byte positions of the window [left.3 | own.0-3 | right.0]:
-        // cw − 1 ≥ 4bx (x0 < W), so every clamped column lies in the window and a clamped one is a byte of the lane's own dword
-        const int32_t c0 = 4 * (int32_t)bx - 1;
         uint32_t sh[6];
-#pragma unroll
-        for(int i = 0; i < 6; i++)
-        {
-            const int32_t c = c0 + i;
-            sh[i] = 8u * (uint32_t)((c < 0 ? 0 : c > (int32_t)a.cw - 1 ? (int32_t)a.cw - 1 : c) - c0);
-        }
+        yuv_in_columns(bx, a.cw, sh);
         const bool has_l = bx > 0, has_r = bx + 1u < a.blocks_x;
         // rows by − 1, by, by + 1, clamped to [0, ch − 1]
         const uint32_t rows[3] = {by > 0 ? by - 1u : 0u, by, by + 1u < a.ch ? by + 1u : a.ch - 1u};
@@ -132,19 +183,7 @@ __global__ void __launch_bounds__(YUV_LANES_X *YUV_BLOCK_ROWS) yuv420_expand(con
                 const uint32_t *row = reinterpret_cast<const uint32_t *>((p ? cr_plane : cb_plane) + (size_t)rows[r] * a.c_pitch) + bx;
                 const uint32_t own = row[0], left = has_l ? row[-1] : 0u, right = has_r ? row[1] : 0u;
                 const uint64_t win = (uint64_t)(left >> 24) | ((uint64_t)own << 8) | ((uint64_t)(right & 0xffu) << 40);
-                int32_t c[6];
-#pragma unroll
-                for(int i = 0; i < 6; i++)
-                    c[i] = (int32_t)((uint32_t)(win >> sh[i]) & 0xffu);
-#pragma unroll
-                for(int i = 0; i < 8; i++)
-                {
-                    const int32_t v = 3 * c[1 + (i >> 1)] + c[(i & 1) ? 2 + (i >> 1) : (i >> 1)];
-                    if(p)
-                        hv[r][i] = v;
-                    else
-                        hu[r][i] = v;
-                }
+                yuv_in_row(win, sh, p ? hv[r] : hu[r]);
             }
         }
         // 9·a + 3·b + 3·c + d = 3·(3a + b) + (3c + d): an even row's neighbour row is the one above, an odd row's the one below
@@ -162,29 +201,7 @@ __global__ void __launch_bounds__(YUV_LANES_X *YUV_BLOCK_ROWS) yuv420_expand(con
             px[j][i] = yuv_in_pixel(a.k, (int32_t)y[j][i], su[j][i], sv[j][i]);
     uint32_t *out = reinterpret_cast<uint32_t *>(a.dst + (size_t)blockIdx.z * a.image_stride) + (size_t)ya * a.W + x0;
     const bool two_rows = ya + 1u < a.H; // an odd H's last block row has one pixel row
-    if(x0 + YUV_BLOCK_W <= a.W && a.rows16)
-    {
-        uint4 *row = reinterpret_cast<uint4 *>(out);
-        row[0] = uint4{px[0][0], px[0][1], px[0][2], px[0][3]};
-        row[1] = uint4{px[0][4], px[0][5], px[0][6], px[0][7]};
-        if(two_rows)
-        {
-            row = reinterpret_cast<uint4 *>(out + a.W);
-            row[0] = uint4{px[1][0], px[1][1], px[1][2], px[1][3]};
-            row[1] = uint4{px[1][4], px[1][5], px[1][6], px[1][7]};
-        }
-    }
-    else
-    {
-#pragma unroll
-        for(int i = 0; i < 8; i++)
-            if(x0 + i < a.W)
-            {
-                out[i] = px[0][i];
-                if(two_rows)
-                    out[a.W + i] = px[1][i];
-            }
-    }
+    yuv_in_store(out, a.W, x0, two_rows, a.rows16, px);
 }
 
 // Enqueues the ONE yuv420_expand launch for n staged frames.  The caller has checked the sizes: n ≥ 1, a.src holds n staged frames, a.dst n images.

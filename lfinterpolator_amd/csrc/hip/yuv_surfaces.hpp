@@ -1,0 +1,290 @@
+// yuv_surfaces.hpp — the YUV 4:2:0 kernels of yuv420.hpp and yuv420_upload.hpp over SURFACES (lfi_upload_images_yuv, lfi_download_views_yuv):
+// I420 or NV12 planes with a pitch, at offsets inside a frame, frames a stride apart — the staged frames of a host call or the caller's own
+// device surfaces, read and written in place.  The arithmetic is that of the two headers, bit for bit (their tables, yuv_in_pixel /
+// yuv_in_clamp, yuv_luma / yuv_chroma and the inline pieces of their kernels are shared); only where the bytes lie differs.
+//
+// Geometry (include/lfi.h).  cw = (W + 1) >> 1, ch = (H + 1) >> 1.  The Y plane is H rows of y_pitch ≥ W bytes.  I420: Cb at c_offset, Cr at
+// cr_offset, ch rows of c_pitch ≥ cw bytes each.  NV12: one plane at c_offset, ch rows of c_pitch ≥ 2·cw bytes, byte 2·cx Cb, 2·cx + 1 Cr.
+// The decomposition is the existing one: a lane owns 8 columns × 2 rows, a wave 64 neighbouring blocks of one block row, a workgroup four
+// waves, the frame or view is grid.z; no LDS, no atomics, no scratch.
+//
+// What the launches rely on (the entry points see to it): every plane base and the frame stride are multiples of 8, y_pitch is a multiple
+// of 8, c_pitch a multiple of 4 (I420) or 8 (NV12) — in-place surfaces have multiples of 16 throughout, the staged planes are those of
+// yuv_geometry (NV12: chroma rows of y_pitch bytes).  Then every load and every word store is aligned and lies inside its own row:
+//   Y      8 bytes at 8·bx:            8·bx + 8 ≤ round8(W) ≤ y_pitch
+//   I420   the dword at 4·bx:          4·bx + 4 ≤ round4(cw) ≤ c_pitch; the dword right of it only where bx + 1 < blocks_x
+//   NV12   8 bytes at 8·bx:            8·bx + 8 ≤ round8(2·cw) ≤ c_pitch; the dword right of it only where bx + 1 < blocks_x, and then
+//                                      2·cw ≥ 8·bx + 10, so 8·bx + 12 ≤ round4(2·cw) ≤ c_pitch
+// and rows are clamped to the plane's own (an odd H has no Y row 2·ch − 1).
+//
+//   yuvs_expand<FORMAT, NEAREST>   yuv420_expand over surfaces.  NV12: a lane's four chroma columns of both components are ONE 8-byte load
+//     of the CbCr row; bilinear takes, on rows by − 1, by, by + 1 (clamped), also the dword left of it (its upper two bytes are column
+//     4·bx − 1) and the dword right of it (its lower two: column 4·bx + 4).  The bytes are de-interleaved into the two six-byte windows of
+//     yuv_in_columns / yuv_in_row, so the definition's clamp is the same set of byte positions, computed once.  NO value comes from
+//     padding or from outside [0, cw − 1] × [0, ch − 1]: in-place padding is the caller's and may hold anything.
+//   yuvs_convert<PLANAR, FORMAT>   yuv420_convert over surfaces.  It writes ONLY the planes' own bytes — pitch padding keeps its value:
+//     every whole block stores words (Y two 8-byte pieces; I420 a dword each of Cb and Cr; NV12 one interleaved 8-byte piece), a ragged
+//     last block of a row stores its valid bytes one by one, and a row beyond H is not stored.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "yuv420.hpp"
+#include "yuv420_upload.hpp"
+
+namespace lfi {
+
+constexpr int YUVS_I420 = 0; // LFI_YUV_I420
+constexpr int YUVS_NV12 = 1; // LFI_YUV_NV12
+
+// frame 0 of a batch of surfaces as a kernel sees it
+struct YuvSurfaces
+{
+    uint8_t *base;                                 // the Y plane of frame 0
+    size_t frame_stride, c_offset, cr_offset;      // cr_offset: I420 only
+    uint32_t y_pitch, c_pitch;
+};
+
+struct YuvsInArgs
+{
+    YuvSurfaces s;       // read only
+    uint8_t *dst;        // RGBA plane [H][W] of the first image
+    size_t image_stride; // bytes from image to image
+    uint32_t W, H, cw, ch;
+    uint32_t blocks_x; // (W + 7) / 8
+    uint32_t rows16;   // every pixel row of an image starts on a 16-byte boundary (W a multiple of 4)
+    YuvInCoeffs k;
+};
+
+struct YuvsOutArgs
+{
+    const uint8_t *src;   // view 0 of the call: RGBA planes [view][H][W], or (PLANAR) byte planes [view][R,G,B][H][pitch]
+    YuvSurfaces s;        // written
+    size_t view_stride;   // bytes from view to view
+    uint32_t W, H, pitch; // pitch: bytes per row of a byte plane (PLANAR)
+    uint32_t cw, ch;
+    uint32_t blocks_x; // (W + 7) / 8
+    uint32_t rows16;   // RGBA: every pixel row starts on a 16-byte boundary (W a multiple of 4)
+    YuvCoeffs k;
+};
+
+// NV12: bytes 0, 2 (p = 0: Cb) or 1, 3 (p = 1: Cr) of lo, then of hi
+__device__ __forceinline__ uint32_t yuvs_component(const uint32_t lo, const uint32_t hi, const int p)
+{
+    const uint32_t a = lo >> (8 * p), b = hi >> (8 * p);
+    return (a & 0xffu) | ((a >> 8) & 0xff00u) | ((b & 0xffu) << 16) | ((b << 8) & 0xff000000u);
+}
+
+template <int FORMAT, bool NEAREST>
+__global__ void __launch_bounds__(YUV_LANES_X *YUV_BLOCK_ROWS) yuvs_expand(const YuvsInArgs a)
+{
+    const uint32_t bx = blockIdx.x * YUV_LANES_X + threadIdx.x;
+    const uint32_t by = blockIdx.y * YUV_BLOCK_ROWS + threadIdx.y; // wave-uniform
+    if(bx >= a.blocks_x || by >= a.ch)
+        return;
+    const uint32_t x0 = bx * YUV_BLOCK_W, ya = by * YUV_BLOCK_H; // x0 < W, ya < H
+    const bool two_rows = ya + 1u < a.H;                         // an odd H's last block row has one pixel row
+    const uint8_t *frame = a.s.base + (size_t)blockIdx.z * a.s.frame_stride;
+    const uint8_t *c_plane = frame + a.s.c_offset; // I420: Cb; NV12: CbCr
+    // Y: row ya and row ya + 1 (clamped to the plane: its pixels are not stored then), columns x0 … x0 + 7
+    uint32_t y[2][8];
+    yuv_in_bytes(*reinterpret_cast<const uint2 *>(frame + (size_t)ya * a.s.y_pitch + x0), y[0]);
+    yuv_in_bytes(*reinterpret_cast<const uint2 *>(frame + (size_t)(two_rows ? ya + 1u : ya) * a.s.y_pitch + x0), y[1]);
+    // chroma in sixteenths of the 16 pixels
+    int32_t su[2][8], sv[2][8];
+    if constexpr(NEAREST)
+    {
+        uint32_t u, v;
+        if constexpr(FORMAT == YUVS_NV12)
+        {
+            const uint2 c = *reinterpret_cast<const uint2 *>(c_plane + (size_t)by * a.s.c_pitch + 8u * bx);
+            u = yuvs_component(c.x, c.y, 0), v = yuvs_component(c.x, c.y, 1);
+        }
+        else
+        {
+            u = *reinterpret_cast<const uint32_t *>(c_plane + (size_t)by * a.s.c_pitch + 4u * bx);
+            v = *reinterpret_cast<const uint32_t *>(frame + a.s.cr_offset + (size_t)by * a.s.c_pitch + 4u * bx);
+        }
+#pragma unroll
+        for(int i = 0; i < 8; i++)
+            su[0][i] = su[1][i] = 16 * (int32_t)((u >> (8 * (i >> 1))) & 0xffu), sv[0][i] = sv[1][i] = 16 * (int32_t)((v >> (8 * (i >> 1))) & 0xffu);
+    }
+    else
+    {
+        uint32_t sh[6];
+        yuv_in_columns(bx, a.cw, sh);
+        const bool has_l = bx > 0, has_r = bx + 1u < a.blocks_x;
+        // rows by − 1, by, by + 1, clamped to [0, ch − 1]
+        const uint32_t rows[3] = {by > 0 ? by - 1u : 0u, by, by + 1u < a.ch ? by + 1u : a.ch - 1u};
+        int32_t hu[3][8], hv[3][8];
+#pragma unroll
+        for(int r = 0; r < 3; r++)
+        {
+            // the windows [column 4bx − 1 | own four | column 4bx + 4] of Cb and Cr; a column that does not exist reads as 0 and is never
+            // selected (yuv_in_columns)
+            uint64_t win[2];
+            if constexpr(FORMAT == YUVS_NV12)
+            {
+                const uint8_t *row = c_plane + (size_t)rows[r] * a.s.c_pitch + 8u * bx;
+                const uint2 own = *reinterpret_cast<const uint2 *>(row);
+                const uint32_t left = has_l ? *reinterpret_cast<const uint32_t *>(row - 4) : 0u;
+                const uint32_t right = has_r ? *reinterpret_cast<const uint32_t *>(row + 8) : 0u;
+#pragma unroll
+                for(int p = 0; p < 2; p++)
+                    win[p] = (uint64_t)((left >> (16 + 8 * p)) & 0xffu) | ((uint64_t)yuvs_component(own.x, own.y, p) << 8) |
+                             ((uint64_t)((right >> (8 * p)) & 0xffu) << 40);
+            }
+            else
+            {
+#pragma unroll
+                for(int p = 0; p < 2; p++)
+                {
+                    const uint32_t *row = reinterpret_cast<const uint32_t *>(frame + (p ? a.s.cr_offset : a.s.c_offset) + (size_t)rows[r] * a.s.c_pitch) + bx;
+                    const uint32_t own = row[0], left = has_l ? row[-1] : 0u, right = has_r ? row[1] : 0u;
+                    win[p] = (uint64_t)(left >> 24) | ((uint64_t)own << 8) | ((uint64_t)(right & 0xffu) << 40);
+                }
+            }
+            yuv_in_row(win[0], sh, hu[r]);
+            yuv_in_row(win[1], sh, hv[r]);
+        }
+        // 9·a + 3·b + 3·c + d = 3·(3a + b) + (3c + d): an even row's neighbour row is the one above, an odd row's the one below
+#pragma unroll
+        for(int j = 0; j < 2; j++)
+#pragma unroll
+            for(int i = 0; i < 8; i++)
+                su[j][i] = 3 * hu[1][i] + hu[j ? 2 : 0][i], sv[j][i] = 3 * hv[1][i] + hv[j ? 2 : 0][i];
+    }
+    uint32_t px[2][8];
+#pragma unroll
+    for(int j = 0; j < 2; j++)
+#pragma unroll
+        for(int i = 0; i < 8; i++)
+            px[j][i] = yuv_in_pixel(a.k, (int32_t)y[j][i], su[j][i], sv[j][i]);
+    uint32_t *out = reinterpret_cast<uint32_t *>(a.dst + (size_t)blockIdx.z * a.image_stride) + (size_t)ya * a.W + x0;
+    yuv_in_store(out, a.W, x0, two_rows, a.rows16, px);
+}
+
+template <bool PLANAR, int FORMAT>
+__global__ void __launch_bounds__(YUV_LANES_X *YUV_BLOCK_ROWS) yuvs_convert(const YuvsOutArgs a)
+{
+    const uint32_t bx = blockIdx.x * YUV_LANES_X + threadIdx.x;
+    const uint32_t by = blockIdx.y * YUV_BLOCK_ROWS + threadIdx.y; // wave-uniform
+    if(bx >= a.blocks_x || by >= a.ch)
+        return;
+    const uint32_t x0 = bx * YUV_BLOCK_W;
+    const bool two_rows = by * YUV_BLOCK_H + 1u < a.H;
+    const uint32_t ya = by * YUV_BLOCK_H, yb = two_rows ? ya + 1u : ya; // ya < H: by < ch
+    const bool whole = x0 + YUV_BLOCK_W <= a.W;                         // all 8 columns inside the view
+    uint32_t r[2][8], g[2][8], b[2][8];
+    yuv_load_block<PLANAR>(a.src + (size_t)blockIdx.z * a.view_stride, a.W, a.H, a.pitch, a.rows16, x0, ya, yb, whole, r, g, b);
+    uint8_t *frame = a.s.base + (size_t)blockIdx.z * a.s.frame_stride;
+    // Y: the row's own bytes only, and no row beyond H
+#pragma unroll
+    for(int j = 0; j < 2; j++)
+    {
+        uint32_t y[8];
+#pragma unroll
+        for(int i = 0; i < 8; i++)
+            y[i] = yuv_luma(a.k, r[j][i], g[j][i], b[j][i]);
+        uint8_t *row = frame + (size_t)(ya + j) * a.s.y_pitch + x0;
+        if(j && !two_rows)
+            continue;
+        if(whole)
+            *reinterpret_cast<uint2 *>(row) = uint2{y[0] | (y[1] << 8) | (y[2] << 16) | (y[3] << 24), y[4] | (y[5] << 8) | (y[6] << 16) | (y[7] << 24)};
+        else
+        {
+#pragma unroll
+            for(int i = 0; i < 7; i++) // a ragged block holds at most 7 columns
+                if(x0 + i < a.W)
+                    row[i] = (uint8_t)y[i];
+        }
+    }
+    uint32_t cb[4], cr[4];
+#pragma unroll
+    for(int i = 0; i < 4; i++)
+        yuv_block_chroma(a.k, r, g, b, i, cb[i], cr[i]);
+    const uint32_t c0 = 4u * bx; // < cw: x0 < W
+    const bool c_whole = c0 + 4u <= a.cw;
+    if constexpr(FORMAT == YUVS_NV12)
+    {
+        uint8_t *row = frame + a.s.c_offset + (size_t)by * a.s.c_pitch + 8u * bx;
+        if(c_whole)
+            *reinterpret_cast<uint2 *>(row) = uint2{cb[0] | (cr[0] << 8) | (cb[1] << 16) | (cr[1] << 24), cb[2] | (cr[2] << 8) | (cb[3] << 16) | (cr[3] << 24)};
+        else
+        {
+#pragma unroll
+            for(int i = 0; i < 3; i++)
+                if(c0 + i < a.cw)
+                    row[2 * i] = (uint8_t)cb[i], row[2 * i + 1] = (uint8_t)cr[i];
+        }
+    }
+    else
+    {
+        uint8_t *u_row = frame + a.s.c_offset + (size_t)by * a.s.c_pitch + c0, *v_row = frame + a.s.cr_offset + (size_t)by * a.s.c_pitch + c0;
+        if(c_whole)
+        {
+            *reinterpret_cast<uint32_t *>(u_row) = cb[0] | (cb[1] << 8) | (cb[2] << 16) | (cb[3] << 24);
+            *reinterpret_cast<uint32_t *>(v_row) = cr[0] | (cr[1] << 8) | (cr[2] << 16) | (cr[3] << 24);
+        }
+        else
+        {
+#pragma unroll
+            for(int i = 0; i < 3; i++)
+                if(c0 + i < a.cw)
+                    u_row[i] = (uint8_t)cb[i], v_row[i] = (uint8_t)cr[i];
+        }
+    }
+}
+
+inline dim3 yuvs_grid(const uint32_t blocks_x, const uint32_t ch, const int n)
+{
+    return dim3((blocks_x + YUV_LANES_X - 1) / YUV_LANES_X, (ch + YUV_BLOCK_ROWS - 1) / YUV_BLOCK_ROWS, n);
+}
+
+// Enqueues the ONE yuvs_expand launch for n frames.  The caller has checked sizes, alignment and memory: n ≥ 1, a.s describes n frames the
+// device may read, a.dst holds n images.
+inline hipError_t launch_yuvs_expand(hipStream_t stream, const int format, const bool nearest, const YuvsInArgs &a, const int n)
+{
+    const dim3 grid = yuvs_grid(a.blocks_x, a.ch, n), block(YUV_LANES_X, YUV_BLOCK_ROWS);
+    if(format == YUVS_NV12)
+    {
+        if(nearest)
+            hipLaunchKernelGGL((yuvs_expand<YUVS_NV12, true>), grid, block, 0, stream, a);
+        else
+            hipLaunchKernelGGL((yuvs_expand<YUVS_NV12, false>), grid, block, 0, stream, a);
+    }
+    else
+    {
+        if(nearest)
+            hipLaunchKernelGGL((yuvs_expand<YUVS_I420, true>), grid, block, 0, stream, a);
+        else
+            hipLaunchKernelGGL((yuvs_expand<YUVS_I420, false>), grid, block, 0, stream, a);
+    }
+    return hipGetLastError();
+}
+
+// Enqueues the ONE yuvs_convert launch for n views.  The caller has checked sizes, alignment and memory: a.s describes n frames the device
+// may write.
+inline hipError_t launch_yuvs_convert(hipStream_t stream, const bool planar, const int format, const YuvsOutArgs &a, const int n)
+{
+    const dim3 grid = yuvs_grid(a.blocks_x, a.ch, n), block(YUV_LANES_X, YUV_BLOCK_ROWS);
+    if(planar)
+    {
+        if(format == YUVS_NV12)
+            hipLaunchKernelGGL((yuvs_convert<true, YUVS_NV12>), grid, block, 0, stream, a);
+        else
+            hipLaunchKernelGGL((yuvs_convert<true, YUVS_I420>), grid, block, 0, stream, a);
+    }
+    else
+    {
+        if(format == YUVS_NV12)
+            hipLaunchKernelGGL((yuvs_convert<false, YUVS_NV12>), grid, block, 0, stream, a);
+        else
+            hipLaunchKernelGGL((yuvs_convert<false, YUVS_I420>), grid, block, 0, stream, a);
+    }
+    return hipGetLastError();
+}
+
+} // namespace lfi

@@ -145,6 +145,12 @@ void Interpolator::finish()
         std::unique_ptr<lfi::Y4mWriter> writer = std::move(y4mWriter);
         writer->close();
     }
+    if(nv12File.is_open())
+    {
+        nv12File.close();
+        if(nv12File.fail())
+            throw std::runtime_error("Cannot write " + nv12Path);
+    }
 }
 
 void Interpolator::loadGPUData()
@@ -605,6 +611,51 @@ void Interpolator::storeResults(std::string path)
                 y4mWriter = std::make_unique<lfi::Y4mWriter>(y4mPath, resolution.x, resolution.y, y4mFps.x, y4mFps.y, yuvRange == LFI_YUV_FULL);
             for(int i = 0; i < viewCount; i++)
                 y4mWriter->writeFrame(frames + frameBytes * i);
+        }
+        catch(...)
+        {
+            if(framesPinned)
+                lfi_free_pinned(frames);
+            throw;
+        }
+        if(framesPinned)
+            lfi_free_pinned(frames);
+    }
+    if(!nv12Path.empty())
+    {
+        std::cout << "Storing NV12 video..." << std::endl;
+        // converted on the device into the tight NV12 layout (lfi_download_views_yuv): every GPU's views arrive in its part of one buffer
+        const size_t frameBytes = lfi::y4mFrameBytes(resolution.x, resolution.y); // NV12 has I420's bytes
+        uint8_t *frames = nullptr;
+        const bool framesPinned = lfi_alloc_pinned(frameBytes * viewCount, reinterpret_cast<void **>(&frames)) == LFI_OK;
+        std::vector<uint8_t> pageableFrames;
+        if(!framesPinned)
+        {
+            pageableFrames.resize(frameBytes * viewCount);
+            frames = pageableFrames.data();
+        }
+        try
+        {
+            for(int g = 0; g < gpuCount; g++)
+            {
+                lfi_yuv_surfaces surfaces{};
+                check(lfi_yuv_surfaces_packed(LFI_YUV_NV12, LFI_MEM_HOST, frames + frameBytes * viewStart[g], resolution.x, resolution.y, &surfaces), contexts[g]);
+                check(lfi_download_views_yuv(contexts[g], 0, viewStart[g + 1] - viewStart[g], yuvMatrix, yuvRange, &surfaces), contexts[g]);
+            }
+            // one file for all time steps of a light-field video: opened by the first, appended to by the others, closed by finish()
+            if(!nv12File.is_open())
+            {
+                nv12File.open(nv12Path, std::ios::binary | std::ios::trunc);
+                if(!nv12File)
+                    throw std::runtime_error("Cannot write " + nv12Path);
+                std::cout << "NV12 video " << nv12Path << ": ffmpeg -f rawvideo -pix_fmt nv12 -s " << resolution.x << "x" << resolution.y << " -r " << y4mFps.x;
+                if(y4mFps.y != 1)
+                    std::cout << "/" << y4mFps.y;
+                std::cout << " -i " << nv12Path << std::endl;
+            }
+            nv12File.write(reinterpret_cast<const char *>(frames), static_cast<std::streamsize>(frameBytes * viewCount));
+            if(!nv12File)
+                throw std::runtime_error("Cannot write " + nv12Path);
         }
         catch(...)
         {

@@ -13,6 +13,8 @@
 #include "lenticular.h"
 #include "params.h"
 #include "vec.h"
+#include <fstream>
+
 #include "y4m.h"
 
 class LfLoader;
@@ -55,6 +57,16 @@ class Interpolator
             yuvMatrix = matrix;
             yuvRange = range;
         }
+        // also write the views as raw NV12 frames (the Y plane, then interleaved Cb/Cr; tightly packed) into one file, in view order:
+        // converted on the device into the tight NV12 layout (lfi_download_views_yuv), same matrix, range and rate as setY4m — the two may
+        // be combined and share them.  The file stays open over the time steps like the Y4M file; opening it prints the ffmpeg options
+        void setNv12(std::string path, int fpsNum = 30, int fpsDen = 1, int matrix = LFI_YUV_BT709, int range = LFI_YUV_LIMITED)
+        {
+            nv12Path = path;
+            y4mFps = {fpsNum, fpsDen};
+            yuvMatrix = matrix;
+            yuvRange = range;
+        }
         // a light-field video as input (a directory of <row>_<col>.y4m files, one per camera): its frames go to the device as they are, 1.5
         // bytes per pixel from page-locked memory, and become the RGBA images there (one lfi_upload_images_yuv420 call for the grid).
         // interpolate() renders time step setInputFrame(t), 0 by default, t in [0, frameCount()); called again after another setInputFrame
@@ -71,7 +83,7 @@ class Interpolator
             inChroma = chroma;
             loadedFrame = -1;
         }
-        // closes the video file of setY4m (interpolate() leaves it open for the next time step's views); throws when that fails
+        // closes the video files of setY4m and setNv12 (interpolate() leaves them open for the next time step's views); throws when that fails
         void finish();
         float lastAverageTime() const { return averageTime; }
         // render on GPUs 0 … count-1 of this node: views are split into contiguous ranges, the grid is broadcast once (RCCL)
@@ -138,6 +150,8 @@ class Interpolator
         int yuvMatrix{LFI_YUV_BT709};
         int yuvRange{LFI_YUV_LIMITED};
         std::unique_ptr<lfi::Y4mWriter> y4mWriter; // open from the first stored step to finish()
+        std::string nv12Path;                      // empty: no raw NV12 file
+        std::ofstream nv12File;                    // open from the first stored step to finish()
         std::unique_ptr<LfLoader> video;           // the input, where it is a light-field video
         int inputFrame{0}, loadedFrame{-1};        // the time step to render / the one on the device
         int inMatrix{LFI_YUV_BT709}, inRange{-1}, inChroma{LFI_CHROMA_BILINEAR};
