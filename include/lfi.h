@@ -176,7 +176,7 @@ enum { LFI_CHROMA_BILINEAR = 0, LFI_CHROMA_NEAREST = 1 };
  * it by an event, without a host wait.  The frames are copied into a device staging buffer the context owns (lfi_memory.workspace_bytes,
  * LFI_POISON_SCRATCH; the result depends on no byte of it the call did not copy) in chunks of at most 16 frames or 256 MiB, at least one
  * frame, each followed by one kernel launch; where W is a multiple of 8 and H is even a chunk is one copy (frame_stride_bytes ==
- * frame_bytes; else one per frame), other sizes take three 2D copies per frame.  An attached grid is written in place; the derived planar
+ * frame_bytes; else one 2D copy whose rows are whole frames), other sizes take three 2D copies per frame.  An attached grid is written in place; the derived planar
  * copy of the images is rebuilt by its next user, as after lfi_upload_image_async.
  * LFI_EINVAL, the context usable and the grid untouched: no grid; released inputs (lfi_release_inputs); a row window (a 2x2 block may
  * straddle the band); n < 1 or a range outside [0, N); an unknown matrix, range or chroma value; frames NULL; frame_stride_bytes <
@@ -542,7 +542,8 @@ enum { LFI_YUV_LIMITED = 0, LFI_YUV_FULL = 1 };
 /* Views [v0, v0 + n) as frames at out + k*frame_stride_bytes, k in [0, n).  One kernel launch converts all n views (both view layouts are
  * read in place; attached views too) into device frames the context owns (lfi_memory.workspace_bytes, LFI_POISON_SCRATCH; every byte copied
  * out the call has written); where W is a multiple of 8 and H is even the device frames are the host frames and one copy moves the batch
- * (frame_stride_bytes == frame_bytes; else one per frame), other sizes take three 2D copies per frame.  Synchronous, ordered like
+ * (frame_stride_bytes == frame_bytes; else one 2D copy whose rows are whole frames), other sizes take three 2D copies per frame.
+ * Synchronous, ordered like
  * lfi_download_quilt; writes no view and no map.
  * LFI_EINVAL, the context usable and the host memory untouched: nothing rendered yet; n < 1 or a range outside [0, views); an unknown matrix
  * or range; out NULL; frame_stride_bytes < frame_bytes; a row window (a 2x2 block may straddle the band). */

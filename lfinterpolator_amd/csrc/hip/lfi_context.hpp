@@ -286,11 +286,12 @@ struct lfi_ctx
     DeviceBuffer dl_plane;            // planar layout: one RGBA plane that downloads expand a view into
     DeviceBuffer quilt;               // lfi_download_quilt[_tiles]: the quilt's rows of tiles as one RGBA image (grows, kept); lfi_download_native: its scaled tiles
     DeviceBuffer native;              // lfi_download_native: the native image, out_h × out_w dwords (grows, kept)
-    // lfi_download_views_yuv420: the padded I420 frames of a call's views in yuv[0]; lfi_render_stream_yuv420: a block's frames in either,
-    // one copied to the host while the next block is converted into the other (grow, kept)
+    // lfi_download_views_yuv420, lfi_download_views_yuv into host or unaligned device surfaces: the staged frames of a call's views (the padded
+    // planes of yuv_geometry, dev_frame_bytes each, I420 or NV12) in yuv[0]; lfi_render_stream_yuv420: a block's staged frames in either, one
+    // copied to the host while the next block is converted into the other (grow, kept)
     DeviceBuffer yuv[2];
-    // lfi_upload_images_yuv420: a chunk's I420 frames in the padded planes yuv420_expand reads; written and read on the copy stream only, in
-    // stream order (grows, kept)
+    // lfi_upload_images_yuv420, lfi_upload_images_yuv from host or unaligned device surfaces: a chunk's staged frames, as yuvs_expand reads
+    // them; written and read on the copy stream only, in stream order (grows, kept)
     DeviceBuffer yuv_in;
     // parameter block
     bool have_params = false;

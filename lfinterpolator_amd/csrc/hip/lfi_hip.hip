@@ -258,90 +258,7 @@ int lfi_upload_wait(lfi_ctx *ctx)
     return LFI_OK;
 }
 
-// ---- YUV 4:2:0 input (yuv420_upload.hpp) ----------------------------------------------------------------------------------------------------
-
-int lfi_upload_images_yuv420(lfi_ctx *ctx, int g0, int n, int matrix, int range, int chroma, const uint8_t *frames, size_t frame_stride_bytes)
-{
-    if(!ctx)
-        return LFI_EINVAL;
-    if(ctx->inputs_released)
-        return fail(ctx, LFI_EINVAL, "lfi_upload_images_yuv420: the RGBA inputs were released (lfi_release_inputs): lfi_set_grid and upload the images again");
-    if(!ctx->grid)
-        return fail(ctx, LFI_EINVAL, "lfi_set_grid has not been called");
-    if(ctx->windowed)
-        return fail(ctx, LFI_EINVAL, "lfi_upload_images_yuv420: YUV 4:2:0 frames need whole images: a 2x2 chroma block may straddle the row window's band");
-    if(n < 1 || g0 < 0 || (long)g0 + n > ctx->n)
-        return fail(ctx, LFI_EINVAL, "lfi_upload_images_yuv420: needs n >= 1 images starting at g0 inside [0, N)");
-    if((matrix != LFI_YUV_BT709 && matrix != LFI_YUV_BT601) || (range != LFI_YUV_LIMITED && range != LFI_YUV_FULL) ||
-       (chroma != LFI_CHROMA_BILINEAR && chroma != LFI_CHROMA_NEAREST))
-        return fail(ctx, LFI_EINVAL, "lfi_upload_images_yuv420: unknown YUV matrix (LFI_YUV_BT709, LFI_YUV_BT601), range (LFI_YUV_LIMITED, LFI_YUV_FULL) or chroma "
-                                     "filter (LFI_CHROMA_BILINEAR, LFI_CHROMA_NEAREST)");
-    const lfi::YuvGeometry g = lfi::yuv_geometry(ctx->width, ctx->height);
-    if(!frames || frame_stride_bytes < g.frame_bytes)
-        return fail(ctx, LFI_EINVAL, "lfi_upload_images_yuv420: the frames' pointer is NULL or frame_stride_bytes is below W*H + 2*((W+1)/2)*((H+1)/2)");
-    if(int rc = bind(ctx))
-        return rc;
-    if(int rc = ensure_copy_stream(ctx))
-        return rc;
-    // chunks of at most 16 frames or 256 MiB, at least one frame: a chunk's copies and its launch follow each other on the copy stream, so
-    // stream order is all the staging buffer needs
-    const int chunk = (int)std::max<size_t>(1, std::min<size_t>(16, ((size_t)256 << 20) / g.dev_frame_bytes));
-    const size_t need = g.dev_frame_bytes * std::min(chunk, n);
-    if(ctx->yuv_in.bytes() < need)
-    {
-        LFI_HIP(ctx, hipStreamSynchronize(ctx->copy_stream)); // an earlier call's chunks may still be in the buffer that goes
-        LFI_HIP(ctx, ctx->yuv_in.reserve(need));
-    }
-    if(!ctx->uploads_pending)
-    {
-        // first copy of a batch: renders already enqueued on the compute stream may still read the planes
-        LFI_HIP(ctx, hipEventRecord(ctx->ev_order, ctx->stream));
-        LFI_HIP(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->ev_order, 0));
-    }
-    ctx->uploads_pending = true; // from here on something may be enqueued on the copy stream
-    hipStream_t st = ctx->copy_stream;
-    uint8_t *dev = ctx->yuv_in.get();
-    const size_t y_plane = (size_t)g.y_pitch * g.y_rows, c_plane = (size_t)g.c_pitch * g.ch;
-    for(int k0 = 0; k0 < n; k0 += chunk)
-    {
-        const int nk = std::min(chunk, n - k0);
-        const uint8_t *src = frames + frame_stride_bytes * k0;
-        // the frames' own bytes only: where W is a multiple of 8 and H is even the staged frame IS the host frame, else three 2D copies per
-        // frame into the padded planes (whose padding stays whatever it was: the kernel uses none of it)
-        if(g.tight && frame_stride_bytes == g.frame_bytes)
-            LFI_HIP(ctx, hipMemcpyAsync(dev, src, g.frame_bytes * nk, hipMemcpyHostToDevice, st));
-        else
-            for(int k = 0; k < nk; k++)
-            {
-                const uint8_t *f = src + frame_stride_bytes * k;
-                uint8_t *d = dev + g.dev_frame_bytes * k;
-                if(g.tight)
-                {
-                    LFI_HIP(ctx, hipMemcpyAsync(d, f, g.frame_bytes, hipMemcpyHostToDevice, st));
-                    continue;
-                }
-                LFI_HIP(ctx, hipMemcpy2DAsync(d, g.y_pitch, f, g.W, g.W, g.H, hipMemcpyHostToDevice, st));
-                for(int p = 0; p < 2; p++)
-                    LFI_HIP(ctx, hipMemcpy2DAsync(d + y_plane + c_plane * p, g.c_pitch, f + (size_t)g.W * g.H + (size_t)g.cw * g.ch * p, g.cw, g.cw, g.ch,
-                                                  hipMemcpyHostToDevice, st));
-            }
-        lfi::YuvInArgs a{};
-        a.src = dev;
-        a.dst = ctx->grid.get() + in_plane_bytes(ctx) * (size_t)(g0 + k0);
-        a.frame_stride = g.dev_frame_bytes;
-        a.image_stride = in_plane_bytes(ctx);
-        a.W = g.W, a.H = g.H, a.cw = g.cw, a.ch = g.ch;
-        a.y_pitch = g.y_pitch, a.c_pitch = g.c_pitch;
-        a.blocks_x = g.y_pitch / lfi::YUV_BLOCK_W;
-        a.rows16 = g.W % 4 == 0; // the grid starts on a 16-byte boundary (hipMalloc; lfi_attach_grid checks), an image is W·H·4 bytes
-        a.k = lfi::YUV_IN_COEFFS[matrix * 2 + range];
-        LFI_HIP(ctx, lfi::launch_yuv420_expand(st, chroma == LFI_CHROMA_NEAREST, a, nk));
-    }
-    touch_images(ctx, g0, g0 + n);
-    return LFI_OK;
-}
-
-// ---- YUV 4:2:0 surfaces (yuv_surfaces.hpp) ----------------------------------------------------------------------------------------------------
+// ---- YUV 4:2:0 surfaces and input (yuv_surfaces.hpp, yuv420_upload.hpp) ----------------------------------------------------------------
 
 namespace {
 
@@ -491,6 +408,85 @@ hipError_t enqueue_surface_copies(hipStream_t st, const lfi_yuv_surfaces &s, int
     return hipSuccess;
 }
 
+// the tight I420 host frames of the *_yuv420 calls, frame_stride_bytes apart, as surfaces; refuses what those calls refuse of them
+int host_i420_surfaces(lfi_ctx *ctx, const char *who, const uint8_t *frames, size_t frame_stride_bytes, lfi_yuv_surfaces *s)
+{
+    if(!frames || frame_stride_bytes < lfi::yuv_geometry(ctx->width, ctx->height).frame_bytes)
+        return fail(ctx, LFI_EINVAL, std::string(who) + ": the frames' pointer is NULL or frame_stride_bytes is below W*H + 2*((W+1)/2)*((H+1)/2)");
+    lfi_yuv_surfaces_packed(LFI_YUV_I420, LFI_MEM_HOST, const_cast<uint8_t *>(frames), ctx->width, ctx->height, s);
+    s->frame_stride = frame_stride_bytes;
+    return LFI_OK;
+}
+
+// what lfi_upload_images_yuv420 and lfi_upload_images_yuv refuse alike, before they look at the frames
+int check_yuv_upload(lfi_ctx *ctx, const char *who, int g0, int n, int matrix, int range, int chroma)
+{
+    const char *fault = nullptr;
+    if(ctx->inputs_released)
+        fault = ": the RGBA inputs were released (lfi_release_inputs): lfi_set_grid and upload the images again";
+    else if(!ctx->grid)
+        return fail(ctx, LFI_EINVAL, "lfi_set_grid has not been called");
+    else if(ctx->windowed)
+        fault = ": YUV 4:2:0 frames need whole images: a 2x2 chroma block may straddle the row window's band";
+    else if(n < 1 || g0 < 0 || (long)g0 + n > ctx->n)
+        fault = ": needs n >= 1 images starting at g0 inside [0, N)";
+    else if((matrix != LFI_YUV_BT709 && matrix != LFI_YUV_BT601) || (range != LFI_YUV_LIMITED && range != LFI_YUV_FULL) ||
+            (chroma != LFI_CHROMA_BILINEAR && chroma != LFI_CHROMA_NEAREST))
+        fault = ": unknown YUV matrix (LFI_YUV_BT709, LFI_YUV_BT601), range (LFI_YUV_LIMITED, LFI_YUV_FULL) or chroma "
+                "filter (LFI_CHROMA_BILINEAR, LFI_CHROMA_NEAREST)";
+    return fault ? fail(ctx, LFI_EINVAL, std::string(who) + fault) : LFI_OK;
+}
+
+// Behind both upload calls.  The arguments have passed check_yuv_upload; src is what host_i420_surfaces made, or has passed
+// yuv_surfaces_fault, which gave extent
+int upload_yuv_surfaces(lfi_ctx *ctx, const char *who, int g0, int n, int matrix, int range, int chroma, const lfi_yuv_surfaces &src, size_t extent)
+{
+    if(int rc = bind(ctx))
+        return rc;
+    if(src.memory == LFI_MEM_DEVICE)
+        if(int rc = check_device_surfaces(ctx, who, src, extent, n))
+            return rc;
+    if(int rc = ensure_copy_stream(ctx))
+        return rc;
+    const lfi::YuvGeometry g = lfi::yuv_geometry(ctx->width, ctx->height);
+    const bool in_place = yuv_surfaces_in_place(src);
+    // staged: chunks of at most 16 frames or 256 MiB, at least one frame: a chunk's copies and its launch follow each other on the copy
+    // stream, so stream order is all the staging buffer needs.  In place: one chunk of all n frames, no buffer
+    const int chunk = in_place ? n : (int)std::max<size_t>(1, std::min<size_t>(16, ((size_t)256 << 20) / g.dev_frame_bytes));
+    const size_t need = in_place ? 0 : g.dev_frame_bytes * std::min(chunk, n);
+    if(ctx->yuv_in.bytes() < need)
+    {
+        LFI_HIP(ctx, hipStreamSynchronize(ctx->copy_stream)); // an earlier call's chunks may still be in the buffer that goes
+        LFI_HIP(ctx, ctx->yuv_in.reserve(need));
+    }
+    if(!ctx->uploads_pending)
+    {
+        // first copy of a batch: renders already enqueued on the compute stream may still read the planes
+        LFI_HIP(ctx, hipEventRecord(ctx->ev_order, ctx->stream));
+        LFI_HIP(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->ev_order, 0));
+    }
+    ctx->uploads_pending = true; // from here on something may be enqueued on the copy stream
+    hipStream_t st = ctx->copy_stream;
+    for(int k0 = 0; k0 < n; k0 += chunk)
+    {
+        const int nk = std::min(chunk, n - k0);
+        // the frames' own bytes only: the staged planes' padding stays whatever it was, the kernel uses none of it
+        if(!in_place)
+            LFI_HIP(ctx, enqueue_surface_copies(st, src, k0, nk, g, ctx->yuv_in.get(), true));
+        lfi::YuvsInArgs a{};
+        a.s = in_place ? caller_surfaces(src) : staged_surfaces(g, src.format, ctx->yuv_in.get());
+        a.dst = ctx->grid.get() + in_plane_bytes(ctx) * (size_t)(g0 + k0);
+        a.image_stride = in_plane_bytes(ctx);
+        a.W = g.W, a.H = g.H, a.cw = g.cw, a.ch = g.ch;
+        a.blocks_x = g.y_pitch / lfi::YUV_BLOCK_W;
+        a.rows16 = g.W % 4 == 0; // the grid starts on a 16-byte boundary (hipMalloc; lfi_attach_grid checks), an image is W·H·4 bytes
+        a.k = lfi::YUV_IN_COEFFS[matrix * 2 + range];
+        LFI_HIP(ctx, lfi::launch_yuvs_expand(st, src.format, chroma == LFI_CHROMA_NEAREST, a, nk));
+    }
+    touch_images(ctx, g0, g0 + n);
+    return LFI_OK;
+}
+
 } // namespace
 
 int lfi_yuv_surfaces_check(const lfi_yuv_surfaces *s, int width, int height, int n)
@@ -514,68 +510,28 @@ int lfi_yuv_surfaces_packed(int format, int memory, void *base, int width, int h
     return LFI_OK;
 }
 
+int lfi_upload_images_yuv420(lfi_ctx *ctx, int g0, int n, int matrix, int range, int chroma, const uint8_t *frames, size_t frame_stride_bytes)
+{
+    if(!ctx)
+        return LFI_EINVAL;
+    if(int rc = check_yuv_upload(ctx, "lfi_upload_images_yuv420", g0, n, matrix, range, chroma))
+        return rc;
+    lfi_yuv_surfaces src{};
+    if(int rc = host_i420_surfaces(ctx, "lfi_upload_images_yuv420", frames, frame_stride_bytes, &src))
+        return rc;
+    return upload_yuv_surfaces(ctx, "lfi_upload_images_yuv420", g0, n, matrix, range, chroma, src, 0);
+}
+
 int lfi_upload_images_yuv(lfi_ctx *ctx, int g0, int n, int matrix, int range, int chroma, const lfi_yuv_surfaces *src)
 {
     if(!ctx)
         return LFI_EINVAL;
-    if(ctx->inputs_released)
-        return fail(ctx, LFI_EINVAL, "lfi_upload_images_yuv: the RGBA inputs were released (lfi_release_inputs): lfi_set_grid and upload the images again");
-    if(!ctx->grid)
-        return fail(ctx, LFI_EINVAL, "lfi_set_grid has not been called");
-    if(ctx->windowed)
-        return fail(ctx, LFI_EINVAL, "lfi_upload_images_yuv: YUV 4:2:0 frames need whole images: a 2x2 chroma block may straddle the row window's band");
-    if(n < 1 || g0 < 0 || (long)g0 + n > ctx->n)
-        return fail(ctx, LFI_EINVAL, "lfi_upload_images_yuv: needs n >= 1 images starting at g0 inside [0, N)");
-    if((matrix != LFI_YUV_BT709 && matrix != LFI_YUV_BT601) || (range != LFI_YUV_LIMITED && range != LFI_YUV_FULL) ||
-       (chroma != LFI_CHROMA_BILINEAR && chroma != LFI_CHROMA_NEAREST))
-        return fail(ctx, LFI_EINVAL, "lfi_upload_images_yuv: unknown YUV matrix (LFI_YUV_BT709, LFI_YUV_BT601), range (LFI_YUV_LIMITED, LFI_YUV_FULL) or chroma "
-                                     "filter (LFI_CHROMA_BILINEAR, LFI_CHROMA_NEAREST)");
+    if(int rc = check_yuv_upload(ctx, "lfi_upload_images_yuv", g0, n, matrix, range, chroma))
+        return rc;
     size_t extent = 0;
     if(const char *fault = yuv_surfaces_fault(src, ctx->width, ctx->height, n, &extent))
         return fail(ctx, LFI_EINVAL, std::string("lfi_upload_images_yuv: ") + fault);
-    if(int rc = bind(ctx))
-        return rc;
-    if(src->memory == LFI_MEM_DEVICE)
-        if(int rc = check_device_surfaces(ctx, "lfi_upload_images_yuv", *src, extent, n))
-            return rc;
-    if(int rc = ensure_copy_stream(ctx))
-        return rc;
-    const lfi::YuvGeometry g = lfi::yuv_geometry(ctx->width, ctx->height);
-    const bool in_place = yuv_surfaces_in_place(*src);
-    // staged: chunks of at most 16 frames or 256 MiB, at least one frame, in lfi_upload_images_yuv420's buffer and under its rules: a
-    // chunk's copies and its launch follow each other on the copy stream.  In place: one chunk of all n frames, no buffer
-    const int chunk = in_place ? n : (int)std::max<size_t>(1, std::min<size_t>(16, ((size_t)256 << 20) / g.dev_frame_bytes));
-    const size_t need = in_place ? 0 : g.dev_frame_bytes * std::min(chunk, n);
-    if(ctx->yuv_in.bytes() < need)
-    {
-        LFI_HIP(ctx, hipStreamSynchronize(ctx->copy_stream)); // an earlier call's chunks may still be in the buffer that goes
-        LFI_HIP(ctx, ctx->yuv_in.reserve(need));
-    }
-    if(!ctx->uploads_pending)
-    {
-        // first copy of a batch: renders already enqueued on the compute stream may still read the planes
-        LFI_HIP(ctx, hipEventRecord(ctx->ev_order, ctx->stream));
-        LFI_HIP(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->ev_order, 0));
-    }
-    ctx->uploads_pending = true; // from here on something may be enqueued on the copy stream
-    hipStream_t st = ctx->copy_stream;
-    for(int k0 = 0; k0 < n; k0 += chunk)
-    {
-        const int nk = std::min(chunk, n - k0);
-        if(!in_place)
-            LFI_HIP(ctx, enqueue_surface_copies(st, *src, k0, nk, g, ctx->yuv_in.get(), true));
-        lfi::YuvsInArgs a{};
-        a.s = in_place ? caller_surfaces(*src) : staged_surfaces(g, src->format, ctx->yuv_in.get());
-        a.dst = ctx->grid.get() + in_plane_bytes(ctx) * (size_t)(g0 + k0);
-        a.image_stride = in_plane_bytes(ctx);
-        a.W = g.W, a.H = g.H, a.cw = g.cw, a.ch = g.ch;
-        a.blocks_x = g.y_pitch / lfi::YUV_BLOCK_W;
-        a.rows16 = g.W % 4 == 0; // the grid starts on a 16-byte boundary (hipMalloc; lfi_attach_grid checks), an image is W·H·4 bytes
-        a.k = lfi::YUV_IN_COEFFS[matrix * 2 + range];
-        LFI_HIP(ctx, lfi::launch_yuvs_expand(st, src->format, chroma == LFI_CHROMA_NEAREST, a, nk));
-    }
-    touch_images(ctx, g0, g0 + n);
-    return LFI_OK;
+    return upload_yuv_surfaces(ctx, "lfi_upload_images_yuv", g0, n, matrix, range, chroma, *src, extent);
 }
 
 int lfi_attach_grid(lfi_ctx *ctx, void *device_ptr, size_t bytes)
@@ -1566,131 +1522,95 @@ const char *lfi_last_kernel_name(const lfi_ctx *ctx)
     return ctx ? ctx->last_kernel : "";
 }
 
-// ---- YUV 4:2:0 frames (yuv420.hpp) ----------------------------------------------------------------------------------------------------------
+// ---- YUV 4:2:0 frames (yuv_surfaces.hpp, yuv420.hpp) --------------------------------------------------------------------------------------
 
-// what lfi_download_views_yuv420 and lfi_render_stream_yuv420 refuse alike (the range of views aside); fills the geometry
-static int check_yuv_args(lfi_ctx *ctx, const char *who, int matrix, int range, const uint8_t *out, size_t frame_stride_bytes, lfi::YuvGeometry *geo)
+// what every call that writes YUV frames refuses alike
+static int check_yuv_out(lfi_ctx *ctx, const char *who, int matrix, int range)
 {
     if(ctx->windowed)
         return fail(ctx, LFI_EINVAL, std::string(who) + ": YUV 4:2:0 frames need whole views: a 2x2 chroma block may straddle the row window's band");
     if((matrix != LFI_YUV_BT709 && matrix != LFI_YUV_BT601) || (range != LFI_YUV_LIMITED && range != LFI_YUV_FULL))
         return fail(ctx, LFI_EINVAL, std::string(who) + ": unknown YUV matrix (LFI_YUV_BT709, LFI_YUV_BT601) or range (LFI_YUV_LIMITED, LFI_YUV_FULL)");
-    *geo = lfi::yuv_geometry(ctx->width, ctx->height);
-    if(!out || frame_stride_bytes < geo->frame_bytes)
-        return fail(ctx, LFI_EINVAL, std::string(who) + ": the frames' pointer is NULL or frame_stride_bytes is below W*H + 2*((W+1)/2)*((H+1)/2)");
     return LFI_OK;
 }
 
-// views [v0, v0 + n) of `views` (in the context's layout) → n padded device frames at dev, one launch on st
-static hipError_t enqueue_yuv_convert(lfi_ctx *ctx, hipStream_t st, const uint8_t *views, int v0, int n, const lfi::YuvGeometry &g, int matrix, int range, uint8_t *dev)
+// what lfi_download_views_yuv420 and lfi_download_views_yuv refuse alike, before they look at the frames
+static int check_yuv_download(lfi_ctx *ctx, const char *who, int v0, int n, int matrix, int range)
 {
-    const bool planar = ctx->out_layout == LFI_LAYOUT_PLANAR_RGB;
-    lfi::YuvArgs a{};
-    a.src = views + (size_t)v0 * out_plane_bytes(ctx);
-    a.out = dev;
-    a.view_stride = out_plane_bytes(ctx);
-    a.frame_stride = g.dev_frame_bytes;
-    a.W = g.W, a.H = g.H, a.pitch = planar ? view_pitch(ctx) : 0;
-    a.y_pitch = g.y_pitch, a.c_pitch = g.c_pitch, a.ch = g.ch;
-    a.blocks_x = g.y_pitch / lfi::YUV_BLOCK_W;
-    a.rows16 = g.W % 4 == 0; // the views start on 16-byte boundaries (hipMalloc; lfi_attach_views checks), a view is W·H·4 bytes
-    a.k = lfi::YUV_COEFFS[matrix * 2 + range];
-    return lfi::launch_yuv420_convert(st, planar, a, n);
+    if(!ctx->views || !ctx->have_params)
+        return fail(ctx, LFI_EINVAL, "nothing rendered yet");
+    if(n < 1 || v0 < 0 || (long)v0 + n > ctx->views_n)
+        return fail(ctx, LFI_EINVAL, std::string(who) + ": needs n >= 1 views starting at v0 inside [0, views)");
+    return check_yuv_out(ctx, who, matrix, range);
 }
 
-// n device frames at dev → tight host frames at out + k·stride, on st: one copy for all (or per frame) where the device layout is the
-// host's, else three 2D copies per frame out of the padded planes
-static hipError_t enqueue_yuv_copies(hipStream_t st, const uint8_t *dev, int n, const lfi::YuvGeometry &g, uint8_t *out, size_t stride)
+// views [v0, v0 + n) of `views` (in the context's layout) → the n frames of s (of `format`: staged ones, or the caller's in place), one
+// launch on st
+static hipError_t enqueue_views_convert(lfi_ctx *ctx, hipStream_t st, const uint8_t *views, int v0, int n, int matrix, int range, int format, const lfi::YuvSurfaces &s)
 {
-    if(g.tight && stride == g.frame_bytes)
-        return hipMemcpyAsync(out, dev, g.frame_bytes * n, hipMemcpyDeviceToHost, st);
-    const size_t y_plane = (size_t)g.y_pitch * g.y_rows, c_plane = (size_t)g.c_pitch * g.ch;
-    for(int k = 0; k < n; k++)
-    {
-        const uint8_t *src = dev + g.dev_frame_bytes * k;
-        uint8_t *dst = out + stride * k;
-        hipError_t e = hipSuccess;
-        if(g.tight)
-            e = hipMemcpyAsync(dst, src, g.frame_bytes, hipMemcpyDeviceToHost, st);
-        else
-        {
-            e = hipMemcpy2DAsync(dst, g.W, src, g.y_pitch, g.W, g.H, hipMemcpyDeviceToHost, st);
-            for(int p = 0; p < 2 && e == hipSuccess; p++)
-                e = hipMemcpy2DAsync(dst + (size_t)g.W * g.H + (size_t)g.cw * g.ch * p, g.cw, src + y_plane + c_plane * p, g.c_pitch, g.cw, g.ch,
-                                     hipMemcpyDeviceToHost, st);
-        }
-        if(e != hipSuccess)
-            return e;
-    }
-    return hipSuccess;
+    const bool planar = ctx->out_layout == LFI_LAYOUT_PLANAR_RGB;
+    lfi::YuvsOutArgs a{};
+    a.src = views + (size_t)v0 * out_plane_bytes(ctx);
+    a.s = s;
+    a.view_stride = out_plane_bytes(ctx);
+    a.W = ctx->width, a.H = ctx->height, a.pitch = planar ? view_pitch(ctx) : 0;
+    a.cw = (a.W + 1) >> 1, a.ch = (a.H + 1) >> 1;
+    a.blocks_x = (a.W + lfi::YUV_BLOCK_W - 1) / lfi::YUV_BLOCK_W;
+    a.rows16 = a.W % 4 == 0; // the views start on 16-byte boundaries (hipMalloc; lfi_attach_views checks), a view is W·H·4 bytes
+    a.k = lfi::YUV_COEFFS[matrix * 2 + range];
+    return lfi::launch_yuvs_convert(st, planar, format, a, n);
+}
+
+// Behind both download calls.  The arguments have passed check_yuv_download; dst is what host_i420_surfaces made, or has passed
+// yuv_surfaces_fault, which gave extent
+static int download_yuv_surfaces(lfi_ctx *ctx, const char *who, int v0, int n, int matrix, int range, const lfi_yuv_surfaces &dst, size_t extent)
+{
+    if(int rc = bind(ctx))
+        return rc;
+    if(dst.memory == LFI_MEM_DEVICE)
+        if(int rc = check_device_surfaces(ctx, who, dst, extent, n))
+            return rc;
+    const lfi::YuvGeometry g = lfi::yuv_geometry(ctx->width, ctx->height);
+    const bool in_place = yuv_surfaces_in_place(dst);
+    if(!in_place)
+        LFI_HIP(ctx, ctx->yuv[0].reserve(g.dev_frame_bytes * n));
+    LFI_HIP(ctx, enqueue_views_convert(ctx, ctx->stream, ctx->views.get(), v0, n, matrix, range, dst.format,
+                                       in_place ? caller_surfaces(dst) : staged_surfaces(g, dst.format, ctx->yuv[0].get())));
+    if(!in_place)
+        LFI_HIP(ctx, enqueue_surface_copies(ctx->stream, dst, 0, n, g, ctx->yuv[0].get(), false));
+    LFI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return LFI_OK;
 }
 
 int lfi_download_views_yuv420(lfi_ctx *ctx, int v0, int n, int matrix, int range, uint8_t *out, size_t frame_stride_bytes)
 {
     if(!ctx)
         return LFI_EINVAL;
-    if(!ctx->views || !ctx->have_params)
-        return fail(ctx, LFI_EINVAL, "nothing rendered yet");
-    if(n < 1 || v0 < 0 || (long)v0 + n > ctx->views_n)
-        return fail(ctx, LFI_EINVAL, "lfi_download_views_yuv420: needs n >= 1 views starting at v0 inside [0, views)");
-    lfi::YuvGeometry g{};
-    if(int rc = check_yuv_args(ctx, "lfi_download_views_yuv420", matrix, range, out, frame_stride_bytes, &g))
+    if(int rc = check_yuv_download(ctx, "lfi_download_views_yuv420", v0, n, matrix, range))
         return rc;
-    if(int rc = bind(ctx))
+    lfi_yuv_surfaces dst{};
+    if(int rc = host_i420_surfaces(ctx, "lfi_download_views_yuv420", out, frame_stride_bytes, &dst))
         return rc;
-    LFI_HIP(ctx, ctx->yuv[0].reserve(g.dev_frame_bytes * n));
-    LFI_HIP(ctx, enqueue_yuv_convert(ctx, ctx->stream, ctx->views.get(), v0, n, g, matrix, range, ctx->yuv[0].get()));
-    LFI_HIP(ctx, enqueue_yuv_copies(ctx->stream, ctx->yuv[0].get(), n, g, out, frame_stride_bytes));
-    LFI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return LFI_OK;
+    return download_yuv_surfaces(ctx, "lfi_download_views_yuv420", v0, n, matrix, range, dst, 0);
 }
 
 int lfi_download_views_yuv(lfi_ctx *ctx, int v0, int n, int matrix, int range, const lfi_yuv_surfaces *dst)
 {
     if(!ctx)
         return LFI_EINVAL;
-    if(!ctx->views || !ctx->have_params)
-        return fail(ctx, LFI_EINVAL, "nothing rendered yet");
-    if(n < 1 || v0 < 0 || (long)v0 + n > ctx->views_n)
-        return fail(ctx, LFI_EINVAL, "lfi_download_views_yuv: needs n >= 1 views starting at v0 inside [0, views)");
-    if(ctx->windowed)
-        return fail(ctx, LFI_EINVAL, "lfi_download_views_yuv: YUV 4:2:0 frames need whole views: a 2x2 chroma block may straddle the row window's band");
-    if((matrix != LFI_YUV_BT709 && matrix != LFI_YUV_BT601) || (range != LFI_YUV_LIMITED && range != LFI_YUV_FULL))
-        return fail(ctx, LFI_EINVAL, "lfi_download_views_yuv: unknown YUV matrix (LFI_YUV_BT709, LFI_YUV_BT601) or range (LFI_YUV_LIMITED, LFI_YUV_FULL)");
+    if(int rc = check_yuv_download(ctx, "lfi_download_views_yuv", v0, n, matrix, range))
+        return rc;
     size_t extent = 0;
     if(const char *fault = yuv_surfaces_fault(dst, ctx->width, ctx->height, n, &extent))
         return fail(ctx, LFI_EINVAL, std::string("lfi_download_views_yuv: ") + fault);
-    if(int rc = bind(ctx))
-        return rc;
-    if(dst->memory == LFI_MEM_DEVICE)
-        if(int rc = check_device_surfaces(ctx, "lfi_download_views_yuv", *dst, extent, n))
-            return rc;
-    const lfi::YuvGeometry g = lfi::yuv_geometry(ctx->width, ctx->height);
-    const bool in_place = yuv_surfaces_in_place(*dst), planar = ctx->out_layout == LFI_LAYOUT_PLANAR_RGB;
-    if(!in_place)
-        LFI_HIP(ctx, ctx->yuv[0].reserve(g.dev_frame_bytes * n));
-    lfi::YuvsOutArgs a{};
-    a.src = ctx->views.get() + (size_t)v0 * out_plane_bytes(ctx);
-    a.s = in_place ? caller_surfaces(*dst) : staged_surfaces(g, dst->format, ctx->yuv[0].get());
-    a.view_stride = out_plane_bytes(ctx);
-    a.W = g.W, a.H = g.H, a.pitch = planar ? view_pitch(ctx) : 0;
-    a.cw = g.cw, a.ch = g.ch;
-    a.blocks_x = g.y_pitch / lfi::YUV_BLOCK_W;
-    a.rows16 = g.W % 4 == 0; // the views start on 16-byte boundaries (hipMalloc; lfi_attach_views checks), a view is W·H·4 bytes
-    a.k = lfi::YUV_COEFFS[matrix * 2 + range];
-    LFI_HIP(ctx, lfi::launch_yuvs_convert(ctx->stream, planar, dst->format, a, n));
-    if(!in_place)
-        LFI_HIP(ctx, enqueue_surface_copies(ctx->stream, *dst, 0, n, g, ctx->yuv[0].get(), false));
-    LFI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return LFI_OK;
+    return download_yuv_surfaces(ctx, "lfi_download_views_yuv", v0, n, matrix, range, *dst, extent);
 }
 
 // where lfi_render_stream_yuv420's frames go; NULL: lfi_render_stream's RGBA downloads
 struct YuvSink
 {
-    lfi::YuvGeometry g;
+    lfi_yuv_surfaces frames; // host, I420, tight planes, the caller's stride
     int matrix, range;
-    size_t stride;
 };
 
 static int render_stream(lfi_ctx *ctx, int method, int all_focus, const uint16_t *weights_fp16, int total_views, uint8_t *host_out, size_t pitch_bytes, const YuvSink *yuv);
@@ -1718,8 +1638,10 @@ int lfi_render_stream_yuv420(lfi_ctx *ctx, int method, int all_focus, const uint
     if(!weights_fp16 || total_views < 1)
         return fail(ctx, LFI_EINVAL, "lfi_render_stream_yuv420: weights are NULL or total_views < 1");
     YuvSink sink{};
-    sink.matrix = matrix, sink.range = range, sink.stride = frame_stride_bytes;
-    if(int rc = check_yuv_args(ctx, "lfi_render_stream_yuv420", matrix, range, host_out, frame_stride_bytes, &sink.g))
+    sink.matrix = matrix, sink.range = range;
+    if(int rc = check_yuv_out(ctx, "lfi_render_stream_yuv420", matrix, range))
+        return rc;
+    if(int rc = host_i420_surfaces(ctx, "lfi_render_stream_yuv420", host_out, frame_stride_bytes, &sink.frames))
         return rc;
     return render_stream(ctx, method, all_focus, weights_fp16, total_views, host_out, 0, &sink);
 }
@@ -1734,6 +1656,7 @@ static int render_stream(lfi_ctx *ctx, int method, int all_focus, const uint16_t
         return rc;
     const int V = ctx->views_n, n = ctx->n, k_pad = ctx->k_pad, v_pad = ctx->v_pad;
     const size_t wbytes = ctx->blob_weights_bytes;
+    const lfi::YuvGeometry yuv_g = lfi::yuv_geometry(ctx->width, ctx->height);
     const size_t off_w16s = (sizeof(uint16_t) * (size_t)v_pad * k_pad + 15) / 16 * 16; // the layout lfi_set_params laid out
     const size_t off_w32 = (off_w16s + sizeof(uint16_t) * (size_t)v_pad * k_pad + 15) / 16 * 16;
     const size_t off_w32t = off_w32 + sizeof(float) * (size_t)v_pad * k_pad;
@@ -1751,7 +1674,7 @@ static int render_stream(lfi_ctx *ctx, int method, int all_focus, const uint16_t
         if(yuv)
         {
             for(int i = 0; i < 2; i++)
-                LFI_HIP(ctx, ctx->yuv[i].reserve(yuv->g.dev_frame_bytes * V));
+                LFI_HIP(ctx, ctx->yuv[i].reserve(yuv_g.dev_frame_bytes * V));
         }
         else
             LFI_HIP(ctx, ctx->views2.fit(out_plane_bytes(ctx) * V));
@@ -1788,13 +1711,14 @@ static int render_stream(lfi_ctx *ctx, int method, int all_focus, const uint16_t
         {
             if(b >= 2)
                 LFI_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_d2h[slot], 0)); // block b − 2 has left this buffer of frames
-            LFI_HIP(ctx, enqueue_yuv_convert(ctx, ctx->stream, vbuf[slot], 0, nv, yuv->g, yuv->matrix, yuv->range, ctx->yuv[slot].get()));
+            LFI_HIP(ctx, enqueue_views_convert(ctx, ctx->stream, vbuf[slot], 0, nv, yuv->matrix, yuv->range, LFI_YUV_I420,
+                                               staged_surfaces(yuv_g, LFI_YUV_I420, ctx->yuv[slot].get())));
         }
         LFI_HIP(ctx, hipEventRecord(ctx->ev_rendered[slot], ctx->stream));
         LFI_HIP(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->ev_rendered[slot], 0));
         if(yuv)
         {
-            LFI_HIP(ctx, enqueue_yuv_copies(ctx->copy_stream, ctx->yuv[slot].get(), nv, yuv->g, host_out + (size_t)b * V * yuv->stride, yuv->stride));
+            LFI_HIP(ctx, enqueue_surface_copies(ctx->copy_stream, yuv->frames, b * V, nv, yuv_g, ctx->yuv[slot].get(), false));
             LFI_HIP(ctx, hipEventRecord(ctx->ev_d2h[slot], ctx->copy_stream));
             continue;
         }
@@ -2160,21 +2084,76 @@ int lfi_download_map(lfi_ctx *ctx, int k, uint8_t *rgba, size_t pitch_bytes)
     return LFI_OK;
 }
 
+// the tiles and views the two quilt calls refuse alike
+static int check_quilt_tiles(lfi_ctx *ctx, int tiles_x, int tiles_y, int first_tile, int n, int v0)
+{
+    if(tiles_x < 1 || tiles_y < 1 || first_tile < 0 || n < 1 || (long)first_tile + n > (long)tiles_x * tiles_y || v0 < 0 || (long)v0 + n > ctx->views_n)
+        return fail(ctx, LFI_EINVAL, "quilt needs the tiles inside the quilt and as many views starting at v0 inside [0, views)");
+    return LFI_OK;
+}
+
+// the tile sizes and view spans the scaled quilt and the native image refuse alike
+static int check_scaled_tiles(lfi_ctx *ctx, int tile_w, int tile_h)
+{
+    if(tile_w < 1 || tile_w > ctx->width || tile_h < 1 || tile_h > ctx->height)
+        return fail(ctx, LFI_EINVAL, "scaled quilt tiles are 1 … width by 1 … height pixels (downscaling or identity only)");
+    if((uint32_t)ctx->width > lfi::LFI_AREA_SPAN_MAX || (uint32_t)ctx->height > lfi::LFI_AREA_SPAN_MAX)
+        return fail(ctx, LFI_EINVAL, "scaled quilts take views of up to 65535 pixels per axis");
+    return LFI_OK;
+}
+
+// Tiles [first, first + n) of a quilt tiles_x tiles wide → the host image, on the compute stream.  The quilt buffer holds the rows of tiles
+// they touch, from row first / tiles_x on, a tile tile_bytes wide and dev_rows high; in the host image a tile is host_rows high and the
+// device's rows are its rows from host_y0 on (a row window: only the band's rows of every tile exist).  One rectangle — or three when the
+// first / last row of tiles is only partly this context's (a trajectory sharded over several GPUs: every context fills its own tiles of
+// the same host image).
+static hipError_t enqueue_quilt_copies(lfi_ctx *ctx, int tiles_x, int first, int n, size_t tile_bytes, int dev_rows, int host_rows, int host_y0, uint8_t *rgba,
+                                       size_t pitch_bytes)
+{
+    const int tr0 = first / tiles_x, tr1 = (first + n - 1) / tiles_x, c_first = first % tiles_x, c_last = (first + n - 1) % tiles_x;
+    const size_t qrow = tiles_x * tile_bytes;
+    // rows of tiles [ra, rb] × tile columns [ca, cb]
+    auto copy_rect = [&](int ra, int rb, int ca, int cb) -> hipError_t {
+        // dev_rows == host_rows: the tiles' rows are contiguous in the host image too, one copy for all rows of tiles
+        const int step = dev_rows == host_rows ? rb - ra + 1 : 1;
+        for(int r = ra; r <= rb; r += step)
+        {
+            const hipError_t e = hipMemcpy2DAsync(rgba + ((size_t)r * host_rows + host_y0) * pitch_bytes + ca * tile_bytes, pitch_bytes,
+                                                  ctx->quilt.get() + (size_t)(r - tr0) * dev_rows * qrow + ca * tile_bytes, qrow, (cb - ca + 1) * tile_bytes,
+                                                  (size_t)step * dev_rows, hipMemcpyDeviceToHost, ctx->stream);
+            if(e != hipSuccess)
+                return e;
+        }
+        return hipSuccess;
+    };
+    if(tr0 == tr1)
+        return copy_rect(tr0, tr0, c_first, c_last);
+    // a partly filled first row of tiles, a partly filled last one, the whole rows between them
+    const int full0 = c_first != 0 ? tr0 + 1 : tr0, full1 = c_last != tiles_x - 1 ? tr1 - 1 : tr1;
+    hipError_t e = hipSuccess;
+    if(full0 != tr0)
+        e = copy_rect(tr0, tr0, c_first, tiles_x - 1);
+    if(e == hipSuccess && full1 != tr1)
+        e = copy_rect(tr1, tr1, 0, c_last);
+    if(e == hipSuccess && full0 <= full1)
+        e = copy_rect(full0, full1, 0, tiles_x - 1);
+    return e;
+}
+
 int lfi_download_quilt_tiles(lfi_ctx *ctx, int tiles_x, int tiles_y, int first_tile, int n, int v0, uint8_t *rgba, size_t pitch_bytes)
 {
     if(!ctx)
         return LFI_EINVAL;
     if(!ctx->views || !ctx->have_params)
         return fail(ctx, LFI_EINVAL, "nothing rendered yet");
-    if(tiles_x < 1 || tiles_y < 1 || first_tile < 0 || n < 1 || (long)first_tile + n > (long)tiles_x * tiles_y || v0 < 0 || (long)v0 + n > ctx->views_n)
-        return fail(ctx, LFI_EINVAL, "quilt needs the tiles inside the quilt and as many views starting at v0 inside [0, views)");
+    if(int rc = check_quilt_tiles(ctx, tiles_x, tiles_y, first_tile, n, v0))
+        return rc;
     if(!rgba || pitch_bytes < (size_t)tiles_x * ctx->width * 4)
         return fail(ctx, LFI_EINVAL, "bad quilt pointer or pitch");
     if(int rc = bind(ctx))
         return rc;
     // The rows of tiles these tiles touch, assembled on the device by ONE kernel (planar views are expanded on the fly: no per-view
-    // conversion pass), then copied to the host in one rectangle — or three when the first / last row of tiles is only partly this
-    // context's (a trajectory sharded over several GPUs: every context fills its own tiles of the same host image).
+    // conversion pass), then copied to the host (enqueue_quilt_copies).
     const int tr0 = first_tile / tiles_x, tr1 = (first_tile + n - 1) / tiles_x;
     const int W = ctx->width, rows = ctx->out_rows;
     const size_t qrow = (size_t)tiles_x * W * 4;
@@ -2188,41 +2167,7 @@ int lfi_download_quilt_tiles(lfi_ctx *ctx, int tiles_x, int tiles_y, int first_t
         hipLaunchKernelGGL(lfi::quilt_assemble<false>, grid, block, 0, ctx->stream, ctx->views.get(), ctx->quilt.as<uint32_t>(), W, rows, 0,
                            out_plane_bytes(ctx), v0, first_tile, tiles_x);
     LFI_HIP(ctx, hipGetLastError());
-    const int c_first = first_tile % tiles_x, c_last = (first_tile + n - 1) % tiles_x;
-    // rows of tiles [ra, rb] × tile columns [ca, cb] → the host image (a row window: only the band's rows of every tile exist)
-    auto copy_rect = [&](int ra, int rb, int ca, int cb) -> hipError_t {
-        const size_t w_bytes = (size_t)(cb - ca + 1) * W * 4;
-        if(rows == ctx->height) // the tiles' rows are contiguous in the host image too: one copy for all rows of tiles
-            return hipMemcpy2DAsync(rgba + (size_t)ra * ctx->height * pitch_bytes + (size_t)ca * W * 4, pitch_bytes,
-                                    ctx->quilt.get() + (size_t)(ra - tr0) * rows * qrow + (size_t)ca * W * 4, qrow, w_bytes, (size_t)(rb - ra + 1) * rows,
-                                    hipMemcpyDeviceToHost, ctx->stream);
-        for(int r = ra; r <= rb; r++)
-        {
-            const hipError_t e = hipMemcpy2DAsync(rgba + ((size_t)r * ctx->height + ctx->out_y0) * pitch_bytes + (size_t)ca * W * 4, pitch_bytes,
-                                                  ctx->quilt.get() + (size_t)(r - tr0) * rows * qrow + (size_t)ca * W * 4, qrow, w_bytes, rows, hipMemcpyDeviceToHost, ctx->stream);
-            if(e != hipSuccess)
-                return e;
-        }
-        return hipSuccess;
-    };
-    if(tr0 == tr1)
-        LFI_HIP(ctx, copy_rect(tr0, tr0, c_first, c_last));
-    else
-    {
-        int full0 = tr0, full1 = tr1;
-        if(c_first != 0)
-        {
-            LFI_HIP(ctx, copy_rect(tr0, tr0, c_first, tiles_x - 1));
-            full0++;
-        }
-        if(c_last != tiles_x - 1)
-        {
-            LFI_HIP(ctx, copy_rect(tr1, tr1, 0, c_last));
-            full1--;
-        }
-        if(full0 <= full1)
-            LFI_HIP(ctx, copy_rect(full0, full1, 0, tiles_x - 1));
-    }
+    LFI_HIP(ctx, enqueue_quilt_copies(ctx, tiles_x, first_tile, n, (size_t)W * 4, rows, ctx->height, ctx->out_y0, rgba, pitch_bytes));
     LFI_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return LFI_OK;
 }
@@ -2242,19 +2187,17 @@ int lfi_download_quilt_tiles_scaled(lfi_ctx *ctx, int tiles_x, int tiles_y, int 
         return fail(ctx, LFI_EINVAL, "nothing rendered yet");
     if(ctx->windowed)
         return fail(ctx, LFI_EINVAL, "a scaled quilt needs whole views: a tile's rows average source rows the row window's band does not hold");
-    if(tiles_x < 1 || tiles_y < 1 || first_tile < 0 || n < 1 || (long)first_tile + n > (long)tiles_x * tiles_y || v0 < 0 || (long)v0 + n > ctx->views_n)
-        return fail(ctx, LFI_EINVAL, "quilt needs the tiles inside the quilt and as many views starting at v0 inside [0, views)");
+    if(int rc = check_quilt_tiles(ctx, tiles_x, tiles_y, first_tile, n, v0))
+        return rc;
+    if(int rc = check_scaled_tiles(ctx, tile_w, tile_h))
+        return rc;
     const int W = ctx->width, H = ctx->height;
-    if(tile_w < 1 || tile_w > W || tile_h < 1 || tile_h > H)
-        return fail(ctx, LFI_EINVAL, "scaled quilt tiles are 1 … width by 1 … height pixels (downscaling or identity only)");
-    if((uint32_t)W > lfi::LFI_AREA_SPAN_MAX || (uint32_t)H > lfi::LFI_AREA_SPAN_MAX)
-        return fail(ctx, LFI_EINVAL, "scaled quilts take views of up to 65535 pixels per axis");
     if(!rgba || pitch_bytes < (size_t)tiles_x * tile_w * 4)
         return fail(ctx, LFI_EINVAL, "bad quilt pointer or pitch");
     if(int rc = bind(ctx))
         return rc;
     // As lfi_download_quilt_tiles: the rows of tiles these tiles touch are made on the device by ONE kernel, in the same buffer, and only
-    // their bytes — tile_w × tile_h per tile — are copied, in at most three rectangles.
+    // their bytes — tile_w × tile_h per tile — are copied.
     const int tr0 = first_tile / tiles_x, tr1 = (first_tile + n - 1) / tiles_x;
     const size_t qrow = (size_t)tiles_x * tile_w * 4;
     LFI_HIP(ctx, ctx->quilt.reserve(qrow * tile_h * (size_t)(tr1 - tr0 + 1)));
@@ -2267,30 +2210,7 @@ int lfi_download_quilt_tiles_scaled(lfi_ctx *ctx, int tiles_x, int tiles_y, int 
     q.tile_w = tile_w, q.tile_h = tile_h;
     q.v0 = v0, q.first = first_tile, q.tiles_x = tiles_x;
     LFI_HIP(ctx, lfi::launch_quilt_scale(ctx->stream, planar, q, n));
-    const int c_first = first_tile % tiles_x, c_last = (first_tile + n - 1) % tiles_x;
-    auto copy_rect = [&](int ra, int rb, int ca, int cb) -> hipError_t { // rows of tiles [ra, rb] × tile columns [ca, cb] → the host image
-        return hipMemcpy2DAsync(rgba + (size_t)ra * tile_h * pitch_bytes + (size_t)ca * tile_w * 4, pitch_bytes,
-                                ctx->quilt.get() + (size_t)(ra - tr0) * tile_h * qrow + (size_t)ca * tile_w * 4, qrow, (size_t)(cb - ca + 1) * tile_w * 4,
-                                (size_t)(rb - ra + 1) * tile_h, hipMemcpyDeviceToHost, ctx->stream);
-    };
-    if(tr0 == tr1)
-        LFI_HIP(ctx, copy_rect(tr0, tr0, c_first, c_last));
-    else
-    {
-        int full0 = tr0, full1 = tr1;
-        if(c_first != 0)
-        {
-            LFI_HIP(ctx, copy_rect(tr0, tr0, c_first, tiles_x - 1));
-            full0++;
-        }
-        if(c_last != tiles_x - 1)
-        {
-            LFI_HIP(ctx, copy_rect(tr1, tr1, 0, c_last));
-            full1--;
-        }
-        if(full0 <= full1)
-            LFI_HIP(ctx, copy_rect(full0, full1, 0, tiles_x - 1));
-    }
+    LFI_HIP(ctx, enqueue_quilt_copies(ctx, tiles_x, first_tile, n, (size_t)tile_w * 4, tile_h, tile_h, 0, rgba, pitch_bytes));
     LFI_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return LFI_OK;
 }
@@ -2316,11 +2236,9 @@ int lfi_download_native(lfi_ctx *ctx, const lfi_lenticular *lens, int v0, int ou
         return fail(ctx, LFI_EINVAL, "unknown lfi_lenticular flag bits");
     if(lens->views < 1 || v0 < 0 || (long)v0 + lens->views > ctx->views_n)
         return fail(ctx, LFI_EINVAL, "a native image needs lens views >= 1 and as many views starting at v0 inside [0, views)");
+    if(int rc = check_scaled_tiles(ctx, tile_w, tile_h))
+        return rc;
     const int W = ctx->width, H = ctx->height;
-    if(tile_w < 1 || tile_w > W || tile_h < 1 || tile_h > H)
-        return fail(ctx, LFI_EINVAL, "scaled quilt tiles are 1 … width by 1 … height pixels (downscaling or identity only)");
-    if((uint32_t)W > lfi::LFI_AREA_SPAN_MAX || (uint32_t)H > lfi::LFI_AREA_SPAN_MAX)
-        return fail(ctx, LFI_EINVAL, "scaled quilts take views of up to 65535 pixels per axis");
     if(out_w < 1 || out_h < 1 || (uint32_t)out_w > lfi::NATIVE_MAX || (uint32_t)out_h > lfi::NATIVE_MAX)
         return fail(ctx, LFI_EINVAL, "native images are 1 … 65535 pixels per axis");
     if(!rgba || pitch_bytes < (size_t)out_w * 4)

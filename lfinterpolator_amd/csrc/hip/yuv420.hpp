@@ -1,5 +1,6 @@
-// yuv420.hpp — 8-bit YUV 4:2:0 frames (I420) of rendered views, converted on the device (lfi_download_views_yuv420,
-// lfi_render_stream_yuv420): what an encoder or player takes, 1.5 bytes per pixel instead of the 4 of an RGBA download.
+// yuv420.hpp — 8-bit YUV 4:2:0 frames of rendered views: the definition's arithmetic, its coefficient tables and the geometry of a frame.  The
+// kernel that uses them is yuvs_convert (yuv_surfaces.hpp), behind lfi_download_views_yuv420, lfi_download_views_yuv and
+// lfi_render_stream_yuv420: what an encoder or player takes, 1.5 bytes per pixel instead of the 4 of an RGBA download.
 //
 // Definition (include/lfi.h), integers only.  A frame of a W × H view is the Y plane [H][W], then Cb and Cr [ch][cw] with cw = (W + 1) >> 1,
 // ch = (H + 1) >> 1.  With the coefficient row (matrix, range) of YUV_COEFFS:
@@ -9,17 +10,10 @@
 // last column or row is replicated).  The bracket lies in (0, 2²⁷): it is computed in u32 (the negative coefficients wrap, the sum does
 // not), one rounding, no shift of a negative number.
 //
-//   yuv420_convert<PLANAR>  one launch for all n views (the view is grid.z).  A lane owns a block of 8 columns × 2 rows of one view: from
-//     RGBA views it reads two rows of 32 bytes as 16-byte loads, from PLANAR views 3 planes × 2 rows × 8 bytes at the plane pitch (no RGBA
-//     copy of planar views); it writes two 8-byte pieces of Y and one dword each of Cb and Cr.  A wave is 64 neighbouring blocks of ONE
-//     block row (512 pixel columns): its loads are two runs of 2 KiB (planar: six of 512 bytes), its stores runs of 512 and 256 bytes —
-//     neighbouring lanes, neighbouring words of a row; the row's offsets are wave-uniform.  A workgroup is four waves = four block rows.
-//     Device rows are padded (Y pitch a multiple of 8, chroma pitch of 4, an even number of Y rows) so that every store is whole and
-//     stays inside its own row, and the kernel writes EVERY byte of the padded planes: columns and rows beyond the view replicate the
-//     last one, as the definition's clamp says.  Ragged blocks (and RGBA views whose width is no multiple of 4: rows not 16-byte aligned)
-//     read pixel by pixel with clamped coordinates; planar rows are as long as their pitch (a multiple of 128 ≥ the Y pitch), so the
-//     8-byte loads stay inside the row and the bytes beyond the view are replaced by the last column's.
-//     No LDS, no atomics, no byte stores, no scratch.
+// Here: YUV_COEFFS; the block shape of every YUV kernel (a lane owns 8 columns × 2 rows, a workgroup is 64 lanes × 4 block rows);
+// yuv_geometry, the tight host frame and the padded staged frame a host call's frames pass through on the device (Y pitch a multiple of 8,
+// chroma pitch of 4, an even number of Y rows: every word of a row lies inside it); yuv_luma and yuv_chroma; yuv_load_block, a lane's
+// 8 × 2 pixels out of RGBA or planar views with the definition's clamp; yuv_block_chroma.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -48,7 +42,7 @@ constexpr YuvCoeffs YUV_COEFFS[4] = {
     {{19595, 38470, 7471}, {-11058, -21710, 32768}, {32768, -27439, -5329}, 0},  // BT.601 full
 };
 
-// the padded device planes of one frame, and the tight host frame
+// the padded staged planes of one frame, and the tight host frame
 struct YuvGeometry
 {
     uint32_t W, H, cw, ch;
@@ -71,19 +65,6 @@ inline YuvGeometry yuv_geometry(const int width, const int height)
     g.tight = g.y_pitch == g.W && g.y_rows == g.H;
     return g;
 }
-
-struct YuvArgs
-{
-    const uint8_t *src;   // view 0 of the call: RGBA planes [view][H][W], or (PLANAR) byte planes [view][R,G,B][H][pitch]
-    uint8_t *out;         // frame 0 of the call: [frame][Y: y_rows × y_pitch | Cb: ch × c_pitch | Cr: ch × c_pitch]
-    size_t view_stride;   // bytes from view to view
-    size_t frame_stride;  // bytes from device frame to device frame
-    uint32_t W, H, pitch; // pitch: bytes per row of a byte plane (PLANAR)
-    uint32_t y_pitch, c_pitch, ch;
-    uint32_t blocks_x;    // y_pitch / 8
-    uint32_t rows16;      // RGBA: every pixel row starts on a 16-byte boundary (W a multiple of 4)
-    YuvCoeffs k;
-};
 
 __device__ inline uint32_t yuv_luma(const YuvCoeffs &k, const uint32_t r, const uint32_t g, const uint32_t b)
 {
@@ -171,58 +152,6 @@ __device__ __forceinline__ void yuv_block_chroma(const YuvCoeffs &k, const uint3
     const uint32_t sb = b[0][2 * i] + b[0][2 * i + 1] + b[1][2 * i] + b[1][2 * i + 1];
     cb = yuv_chroma(k.cb, sr, sg, sb);
     cr = yuv_chroma(k.cr, sr, sg, sb);
-}
-
-template <bool PLANAR>
-__global__ void __launch_bounds__(YUV_LANES_X *YUV_BLOCK_ROWS) yuv420_convert(const YuvArgs a)
-{
-    const uint32_t bx = blockIdx.x * YUV_LANES_X + threadIdx.x;
-    const uint32_t by = blockIdx.y * YUV_BLOCK_ROWS + threadIdx.y; // wave-uniform
-    if(bx >= a.blocks_x || by >= a.ch)
-        return;
-    const uint32_t x0 = bx * YUV_BLOCK_W;
-    const uint32_t ya = by * YUV_BLOCK_H, yb = ya + 1u < a.H ? ya + 1u : a.H - 1u; // ya < H: by < ch
-    const uint8_t *view = a.src + (size_t)blockIdx.z * a.view_stride;
-    const bool whole = x0 + YUV_BLOCK_W <= a.W; // all 8 columns inside the view
-    uint32_t r[2][8], g[2][8], b[2][8];
-    yuv_load_block<PLANAR>(view, a.W, a.H, a.pitch, a.rows16, x0, ya, yb, whole, r, g, b);
-    uint8_t *frame = a.out + (size_t)blockIdx.z * a.frame_stride;
-#pragma unroll
-    for(int j = 0; j < 2; j++)
-    {
-        uint2 y{0u, 0u};
-#pragma unroll
-        for(int i = 0; i < 4; i++)
-        {
-            y.x |= yuv_luma(a.k, r[j][i], g[j][i], b[j][i]) << (8 * i);
-            y.y |= yuv_luma(a.k, r[j][i + 4], g[j][i + 4], b[j][i + 4]) << (8 * i);
-        }
-        *reinterpret_cast<uint2 *>(frame + (size_t)(ya + j) * a.y_pitch + x0) = y; // row ya + 1 < y_rows = 2·ch
-    }
-    uint32_t cb = 0, cr = 0;
-#pragma unroll
-    for(int i = 0; i < 4; i++)
-    {
-        uint32_t u, v;
-        yuv_block_chroma(a.k, r, g, b, i, u, v);
-        cb |= u << (8 * i);
-        cr |= v << (8 * i);
-    }
-    const size_t y_plane = (size_t)a.y_pitch * (2u * a.ch), c_plane = (size_t)a.c_pitch * a.ch;
-    uint8_t *c_row = frame + y_plane + (size_t)by * a.c_pitch + 4u * bx;
-    *reinterpret_cast<uint32_t *>(c_row) = cb;
-    *reinterpret_cast<uint32_t *>(c_row + c_plane) = cr;
-}
-
-// Enqueues the ONE yuv420_convert launch for n views.  The caller has checked the sizes: n ≥ 1, a.out holds n device frames.
-inline hipError_t launch_yuv420_convert(hipStream_t stream, const bool planar, const YuvArgs &a, const int n)
-{
-    const dim3 grid((a.blocks_x + YUV_LANES_X - 1) / YUV_LANES_X, (a.ch + YUV_BLOCK_ROWS - 1) / YUV_BLOCK_ROWS, n), block(YUV_LANES_X, YUV_BLOCK_ROWS);
-    if(planar)
-        hipLaunchKernelGGL(yuv420_convert<true>, grid, block, 0, stream, a);
-    else
-        hipLaunchKernelGGL(yuv420_convert<false>, grid, block, 0, stream, a);
-    return hipGetLastError();
 }
 
 } // namespace lfi

@@ -1,12 +1,16 @@
-// yuv_surfaces.hpp — the YUV 4:2:0 kernels of yuv420.hpp and yuv420_upload.hpp over SURFACES (lfi_upload_images_yuv, lfi_download_views_yuv):
-// I420 or NV12 planes with a pitch, at offsets inside a frame, frames a stride apart — the staged frames of a host call or the caller's own
-// device surfaces, read and written in place.  The arithmetic is that of the two headers, bit for bit (their tables, yuv_in_pixel /
-// yuv_in_clamp, yuv_luma / yuv_chroma and the inline pieces of their kernels are shared); only where the bytes lie differs.
+// yuv_surfaces.hpp — the YUV 4:2:0 kernels, over SURFACES: I420 or NV12 planes with a pitch, at offsets inside a frame, frames a stride apart —
+// the staged frames of a host call (lfi_upload_images_yuv420, lfi_download_views_yuv420, lfi_render_stream_yuv420 and the host side of
+// lfi_upload_images_yuv, lfi_download_views_yuv) or the caller's own device surfaces, read and written in place.  The arithmetic is that of
+// yuv420.hpp (views → frames) and yuv420_upload.hpp (frames → images): their tables, yuv_in_pixel / yuv_in_clamp, yuv_luma / yuv_chroma and
+// their inline pieces; this header says where the bytes lie.
 //
 // Geometry (include/lfi.h).  cw = (W + 1) >> 1, ch = (H + 1) >> 1.  The Y plane is H rows of y_pitch ≥ W bytes.  I420: Cb at c_offset, Cr at
 // cr_offset, ch rows of c_pitch ≥ cw bytes each.  NV12: one plane at c_offset, ch rows of c_pitch ≥ 2·cw bytes, byte 2·cx Cb, 2·cx + 1 Cr.
-// The decomposition is the existing one: a lane owns 8 columns × 2 rows, a wave 64 neighbouring blocks of one block row, a workgroup four
-// waves, the frame or view is grid.z; no LDS, no atomics, no scratch.
+//
+// Decomposition, the same in both kernels: one launch for all frames of a chunk or views of a call (the frame or view is grid.z).  A lane
+// owns a block of 8 columns × 2 rows; a wave is 64 neighbouring blocks of ONE block row (512 pixel columns), so the row's offsets are
+// wave-uniform and neighbouring lanes touch neighbouring words of a row; a workgroup is four waves = four block rows.  No LDS, no atomics,
+// no scratch.
 //
 // What the launches rely on (the entry points see to it): every plane base and the frame stride are multiples of 8, y_pitch is a multiple
 // of 8, c_pitch a multiple of 4 (I420) or 8 (NV12) — in-place surfaces have multiples of 16 throughout, the staged planes are those of
@@ -17,14 +21,25 @@
 //                                      2·cw ≥ 8·bx + 10, so 8·bx + 12 ≤ round4(2·cw) ≤ c_pitch
 // and rows are clamped to the plane's own (an odd H has no Y row 2·ch − 1).
 //
-//   yuvs_expand<FORMAT, NEAREST>   yuv420_expand over surfaces.  NV12: a lane's four chroma columns of both components are ONE 8-byte load
-//     of the CbCr row; bilinear takes, on rows by − 1, by, by + 1 (clamped), also the dword left of it (its upper two bytes are column
-//     4·bx − 1) and the dword right of it (its lower two: column 4·bx + 4).  The bytes are de-interleaved into the two six-byte windows of
-//     yuv_in_columns / yuv_in_row, so the definition's clamp is the same set of byte positions, computed once.  NO value comes from
-//     padding or from outside [0, cw − 1] × [0, ch − 1]: in-place padding is the caller's and may hold anything.
-//   yuvs_convert<PLANAR, FORMAT>   yuv420_convert over surfaces.  It writes ONLY the planes' own bytes — pitch padding keeps its value:
-//     every whole block stores words (Y two 8-byte pieces; I420 a dword each of Cb and Cr; NV12 one interleaved 8-byte piece), a ragged
-//     last block of a row stores its valid bytes one by one, and a row beyond H is not stored.
+//   yuvs_expand<FORMAT, NEAREST>   frames → RGBA images.  A lane reads two 8-byte pieces of Y and its four chroma columns of chroma row by:
+//     I420 the dword at 4·bx of each chroma plane, NV12 ONE 8-byte load of the CbCr row.  BILINEAR reads them on rows by − 1, by, by + 1
+//     (clamped) and on each also the dword left of them (I420: its top byte is column 4·bx − 1; NV12: its upper two bytes) and the dword
+//     right of them (its lowest byte, NV12 its lower two: column 4·bx + 4).  The bytes go into the two six-byte windows of yuv_in_columns /
+//     yuv_in_row, so the definition's clamp is the same set of byte positions, computed once.  A wave's Y loads are two runs of 512 bytes,
+//     its chroma loads runs of 256 (NV12: 512) bytes that neighbouring lanes share (the repeats hit in cache), its stores two runs of
+//     2 KiB as 16-byte stores.  NO value comes from padding or from outside [0, cw − 1] × [0, ch − 1] — a host call copies only the
+//     frames' own bytes into the staged planes, and in-place padding is the caller's and may hold anything: the chroma neighbours are
+//     clamped as the definition says (a clamped neighbour is a byte of the lane's own columns or row), and the Y bytes beyond the image
+//     belong to pixels that are not stored.  Ragged blocks, an odd last row, and images whose rows are not 16-byte aligned (W no multiple
+//     of 4) store pixel by pixel as dwords; no lane stores outside the image.
+//   yuvs_convert<PLANAR, FORMAT>   views → frames.  From RGBA views a lane reads two rows of 32 bytes as 16-byte loads (a wave: two runs of
+//     2 KiB), from PLANAR views 3 planes × 2 rows × 8 bytes at the plane pitch (six runs of 512 bytes; no RGBA copy of planar views).
+//     Ragged blocks, and RGBA views whose rows are not 16-byte aligned, read pixel by pixel with clamped coordinates; planar rows are as
+//     long as their pitch (a multiple of 128 ≥ round8(W)), so the 8-byte loads stay inside the row and the bytes beyond the view are
+//     replaced by the last column's: an odd last column or row is replicated, as the definition's clamp says.  It writes ONLY the planes'
+//     own bytes — pitch padding keeps its value: every whole block stores words (Y two 8-byte pieces, a wave's run 512 bytes; I420 a dword
+//     each of Cb and Cr, runs of 256; NV12 one interleaved 8-byte piece), a ragged last block of a row stores its valid bytes one by one,
+//     and a row beyond H is not stored.
 #pragma once
 
 #include <hip/hip_runtime.h>

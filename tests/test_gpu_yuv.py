@@ -193,6 +193,48 @@ def test_refusals_leave_a_usable_context(gpu):
     fresh.close()
 
 
+@pytest.mark.parametrize("size", [(21, 11), (24, 6)], ids=lambda s: f"{s[0]}x{s[1]}")
+@pytest.mark.parametrize("layout", ["rgba", "planar"])
+def test_frames_equal_those_of_the_surface_call(layout, size, gpu):
+    """lfi_download_views_yuv420 is lfi_download_views_yuv into the equivalent descriptor — host memory, I420, tight planes, the array's frame
+    stride: 3 views from view 1, frames 5 bytes apart (21x11 padded staged planes, 24x6 the staged frame is the host frame), byte for
+    byte; the 5 bytes between the frames keep their poison under both"""
+    w, h = size
+    ctx, _ = _ctx(gpu, w, h, layout)
+    poison.render(ctx, "TEN_WM")
+    fb = ref.sizes(w, h)[2]
+    fmt = (ref.BT601, ref.FULL)
+    want = ref.frames(ctx.download_views(1, 4), *fmt)
+    hosts = poison.sentinel((3, fb + 5)), poison.sentinel((3, fb + 5))
+    ctx.poison(L.LFI_POISON_SCRATCH, PAD)
+    ctx.download_views_yuv420(1, 3, matrix=fmt[0], range=fmt[1], out=hosts[0])
+    surfaces = ctx.yuv_surfaces_packed("i420", "host", hosts[1].ctypes.data, keep=hosts[1])
+    surfaces.frame_stride = hosts[1].strides[0]
+    ctx.poison(L.LFI_POISON_SCRATCH, 0xFF ^ PAD)
+    ctx.download_views_yuv(surfaces, 3, v0=1, matrix=fmt[0], range=fmt[1])
+    assert (hosts[0] == hosts[1]).all(), int((hosts[0] != hosts[1]).sum())
+    assert (hosts[0][:, :fb] == want).all()
+    assert (hosts[0][:, fb:] == poison.SENTINEL).all()
+    ctx.close()
+
+
+def test_one_frame_with_a_stride_below_the_frame_is_refused(gpu):
+    """n = 1: no second frame starts a stride after the first, and a descriptor of surfaces says nothing about its stride then — the call
+    refuses a frame_stride_bytes below the frame's bytes all the same, and writes nothing"""
+    w, h = 17, 9
+    ctx, _ = _ctx(gpu, w, h, "rgba")
+    poison.render(ctx, "STD")
+    views = ctx.download_views()
+    fb = ref.sizes(w, h)[2]
+    host = poison.sentinel((1, fb))
+    assert _raw_download(ctx, 2, 1, 0, 0, host, fb - 1) == -1
+    assert ctx._lib.lfi_last_error(ctx._h).decode() == ("lfi_download_views_yuv420: the frames' pointer is NULL or frame_stride_bytes is below "
+                                                        "W*H + 2*((W+1)/2)*((H+1)/2)")
+    assert (host == poison.SENTINEL).all()
+    assert _raw_download(ctx, 2, 1, 0, 0, host, fb) == 0 and (host == ref.frames(views[2:3], ref.BT709, ref.LIMITED)).all()
+    ctx.close()
+
+
 @pytest.mark.parametrize("layout", ["rgba", "planar"])
 def test_the_buffers_are_counted_and_grow(layout, gpu):
     w, h = 17, 9

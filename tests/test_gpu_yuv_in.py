@@ -117,6 +117,37 @@ def test_range_of_images_stride_and_pageable_or_pinned_frames(gpu):
     del grid
 
 
+@pytest.mark.parametrize("size", [(21, 11), (24, 6)], ids=lambda s: f"{s[0]}x{s[1]}")
+def test_grid_equals_that_of_the_surface_call(size, gpu):
+    """lfi_upload_images_yuv420 is lfi_upload_images_yuv from the equivalent descriptor — host memory, I420, tight planes, the array's frame
+    stride: 3 frames 5 bytes apart into images 1 … 3 of 4 (21x11 padded staged planes, 24x6 the staged frame is the host frame), the
+    whole grid byte for byte; the 5 bytes between the frames keep their poison"""
+    import torch
+    w, h = size
+    shape = (2, 2, w, h)
+    fb = ref.sizes(w, h)[2]
+    frames = _frames(shape, seed=6)[:3]
+    host = np.full((3, fb + 5), poison.SENTINEL, np.uint8)
+    host[:, :fb] = frames
+    fmt = (ref.BT601, ref.FULL, ref.BILINEAR)
+    ctx, grid = _attached(gpu, shape)
+    ctx.poison(L.LFI_POISON_SCRATCH, 0xA5)
+    ctx.upload_images_yuv420(host, g0=1, matrix=fmt[0], range=fmt[1], chroma=fmt[2])
+    first = _read(ctx, grid)
+    grid.fill_(PATTERN)
+    torch.cuda.synchronize()
+    surfaces = ctx.yuv_surfaces_packed("i420", "host", host.ctypes.data, keep=host)
+    surfaces.frame_stride = host.strides[0]
+    ctx.poison(L.LFI_POISON_SCRATCH, 0x5A)
+    ctx.upload_images_yuv(surfaces, 3, g0=1, matrix=fmt[0], range=fmt[1], chroma=fmt[2])
+    second = _read(ctx, grid)
+    assert (first == second).all(), int((first != second).sum())
+    assert (first[1:] == ref.images(frames, w, h, *fmt)).all() and (first[0] == PATTERN).all()
+    assert (host[:, fb:] == poison.SENTINEL).all() and (host[:, :fb] == frames).all()
+    ctx.close()
+    del grid
+
+
 def test_the_staging_buffer_is_counted_and_kept(gpu):
     cols, rows, w, h = CHUNKS
     frames = _frames(CHUNKS)
@@ -235,3 +266,22 @@ def test_refusals_leave_the_grid_and_a_usable_context(gpu):
     poison.render(rel, "TEN_WM")
     assert (rel.download_views() == views).all()
     rel.close()
+
+
+def test_one_frame_with_a_stride_below_the_frame_is_refused(gpu):
+    """n = 1: no second frame starts a stride after the first, and a descriptor of surfaces says nothing about its stride then — the call
+    refuses a frame_stride_bytes below the frame's bytes all the same, and the grid and the staging buffer stay untouched"""
+    cols, rows, w, h = ODD
+    fb = ref.sizes(w, h)[2]
+    frames = _frames(ODD, seed=7)
+    ctx, grid = _attached(gpu, ODD)
+    before = ctx.memory_info().workspace_bytes
+    assert _raw(ctx, 2, 1, 0, 0, 0, frames, fb - 1) == -1
+    assert ctx._lib.lfi_last_error(ctx._h).decode() == ("lfi_upload_images_yuv420: the frames' pointer is NULL or frame_stride_bytes is below "
+                                                        "W*H + 2*((W+1)/2)*((H+1)/2)")
+    assert (_read(ctx, grid) == PATTERN).all() and ctx.memory_info().workspace_bytes == before
+    assert _raw(ctx, 2, 1, 0, 0, 0, frames, fb) == 0
+    got = _read(ctx, grid)
+    assert (got[2] == ref.images(frames[:1], w, h, ref.BT709, ref.LIMITED)[0]).all() and (got[:2] == PATTERN).all() and (got[3:] == PATTERN).all()
+    ctx.close()
+    del grid

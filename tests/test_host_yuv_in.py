@@ -393,8 +393,8 @@ def test_cli_help_names_the_flags(native):
 
 @pytest.mark.skipif(not os.path.exists(os.path.join(LLVM_BIN, "llvm-readelf")), reason="ROCm LLVM tools not installed")
 def test_yuv420_expand_uses_no_scratch_no_spills_and_no_lds(native, tmp_path):
-    """From the code object's notes: both instantiations of yuv420_expand (csrc/hip/yuv420_upload.hpp) exist, use no scratch and no LDS and
-    spill nothing; from its code: no atomics, no byte or short stores — a lane's two runs of 32 bytes leave as four 16-byte stores (ragged
+    """From the code object's notes: both I420 instantiations of yuvs_expand (csrc/hip/yuv_surfaces.hpp), the kernel behind
+    lfi_upload_images_yuv420, exist, use no scratch and no LDS and spill nothing; from its code: no atomics, no byte or short stores — a lane's two runs of 32 bytes leave as four 16-byte stores (ragged
     blocks: dwords) — Y arrives as two 8-byte loads, chroma as dwords: one per plane (nearest), nine per plane (bilinear)."""
     co = _gfx950_code_object(native, tmp_path)
     notes = subprocess.run([os.path.join(LLVM_BIN, "llvm-readelf"), "--notes", co], capture_output=True, text=True, check=True).stdout
@@ -407,7 +407,7 @@ def test_yuv420_expand_uses_no_scratch_no_spills_and_no_lds(native, tmp_path):
             kernels[name] = {}
         elif name and ":" in line and line.split(":")[0] in keys:
             kernels[name][line.split(":")[0]] = int(line.split(":")[1])
-    expand = {k: v for k, v in kernels.items() if "yuv420_expand" in k}
+    expand = {k: v for k, v in kernels.items() if "yuvs_expandILi0E" in k}   # <YUVS_I420, NEAREST>
     assert len(expand) == 2, sorted(expand)
     for k, v in expand.items():
         assert v[".private_segment_fixed_size"] == 0 and v[".vgpr_spill_count"] == 0 and v[".sgpr_spill_count"] == 0, (k, v)
@@ -429,4 +429,4 @@ def test_yuv420_expand_uses_no_scratch_no_spills_and_no_lds(native, tmp_path):
         assert "v_ashr_pk_u8_i32" not in text, k
         assert text.count("global_store_dwordx4") == 4 and len(re.findall(r"global_store_dword ", text)) == 16, k
         assert text.count("global_load_dwordx2") == 2 and "global_load_ubyte" not in text, k
-        assert len(re.findall(r"global_load_dword ", text)) == (2 if "ILb1E" in k else 18), k   # NEAREST / bilinear
+        assert len(re.findall(r"global_load_dword ", text)) == (2 if "ELb1E" in k else 18), k   # NEAREST / bilinear

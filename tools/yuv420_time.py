@@ -7,9 +7,9 @@ replaces.  Per case and view layout, in ONE process on one context at a time (th
   (c) the kernel alone comes from a SECOND run of this tool under
         rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/yuv420_time.py 3 1 a
       and  python tools/yuv420_time.py --kernels DIR/…_kernel_trace.csv
-      which prints, per grid of yuv420_convert launches (in the tool's order: per case, rgba then planar), the number of launches, the median
-      of End_Timestamp − Start_Timestamp (device clock), the bytes the kernel moves (4 read per pixel from RGBA views, 3 from planar ones, 1.5
-      written) and the rate as a fraction of 8 TB/s.
+      which prints, per grid of yuvs_convert launches (the kernel behind both calls, csrc/hip/yuv_surfaces.hpp; in the tool's order: per
+      case, rgba then planar), the number of launches, the median of End_Timestamp − Start_Timestamp (device clock), the bytes the kernel
+      moves (4 read per pixel from RGBA views, 3 from planar ones, 1.5 written) and the rate as a fraction of 8 TB/s.
 Before anything is timed the frames of (a) are held against the numpy restatement of the definition on view 0 and the last view.
 Reads nothing but the package and tests/yuv_ref.py.
 usage: python tools/yuv420_time.py [runs=20] [warm=3] [rows=ab] [path=256] [case ...]   cases: 1080p, 4k (default: both)"""
@@ -38,7 +38,7 @@ if len(sys.argv) > 2 and sys.argv[1] == "--kernels":
     groups = {}
     for r in trace:
         name = r["Kernel_Name"].split("(")[0]
-        if "yuv420_convert" not in name:
+        if "yuvs_convert" not in name:
             continue
         grid = (int(r.get("Grid_Size_X", r.get("Grid_Size", 0))), int(r.get("Grid_Size_Y", 0) or 0), int(r.get("Grid_Size_Z", 0) or 0))
         groups.setdefault((name, grid), []).append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e6)
@@ -48,7 +48,7 @@ if len(sys.argv) > 2 and sys.argv[1] == "--kernels":
         # grid = (64·⌈W/512⌉, 4·⌈H/8⌉, views) threads: the case is the one whose sizes give it
         for case, (_, _, W, H, _, _, _) in CASES.items():
             if grid in ((64 * -(-W // 512), 4 * -(-H // 8), V), (-(-W // 512), -(-H // 8), V)):   # in threads, or in workgroups
-                planar = "ILb1E" in name or "<true>" in name
+                planar = "ILb1E" in name or "<true" in name
                 moved = V * W * H * ((3 if planar else 4) + 1.5)
                 row.update(case=case, layout="planar" if planar else "rgba", bytes=int(moved), us_at_8TBs=round(moved / PEAK_BYTES_PER_S * 1e6, 1),
                            fraction_of_8TBs=round(moved / (float(np.median(ms)) * 1e-3) / PEAK_BYTES_PER_S, 4))

@@ -6,8 +6,9 @@ repetitions after `warm` warm-ups, host clock, from page-locked host memory (lfi
   (b) the kernel alone comes from a SECOND run of this tool under
         rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/yuv420_upload_time.py 3 1
       and  python tools/yuv420_upload_time.py --kernels DIR/…_kernel_trace.csv
-      which prints, per grid of yuv420_expand launches, the number of launches, the median of End_Timestamp − Start_Timestamp (device
-      clock), the bytes the kernel moves (1.5 read per pixel, 4 written) and the rate as a fraction of 8 TB/s.
+      which prints, per grid of yuvs_expand launches (the kernel behind the call, csrc/hip/yuv_surfaces.hpp), the number of launches, the
+      median of End_Timestamp − Start_Timestamp (device clock), the bytes the kernel moves (1.5 read per pixel, 4 written) and the rate as a
+      fraction of 8 TB/s.
 Before anything is timed the grid's first and last image after the YUV call are held against the numpy restatement of the definition.
 Reads nothing but the package and tests/yuv_in_ref.py.
 usage: python tools/yuv420_upload_time.py [runs=20] [warm=3] [case ...]   cases: 1080p, 4k (default: both)"""
@@ -35,7 +36,7 @@ if len(sys.argv) > 2 and sys.argv[1] == "--kernels":
     groups = {}
     for r in trace:
         name = r["Kernel_Name"].split("(")[0]
-        if "yuv420_expand" not in name:
+        if "yuvs_expand" not in name:
             continue
         grid = (int(r.get("Grid_Size_X", r.get("Grid_Size", 0))), int(r.get("Grid_Size_Y", 0) or 0), int(r.get("Grid_Size_Z", 0) or 0))
         groups.setdefault((name, grid), []).append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e6)

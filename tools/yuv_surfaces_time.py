@@ -1,10 +1,10 @@
 """Video surfaces (lfi_upload_images_yuv, lfi_download_views_yuv): what device-resident NV12 frames save, and what NV12 and pitches cost.
 Per case, in ONE process on one context (its grid a torch tensor attached with lfi_attach_grid, so that the result can be read back), medians
 of `runs` timed repetitions after `warm` warm-ups, host clock, host sides from page-locked memory (lfi_alloc_pinned):
-  (a) one time step: lfi_upload_images_yuv420 + lfi_upload_wait from host I420 frames (the path from before, the yardstick) against
-      lfi_upload_images_yuv + lfi_upload_wait from NV12 device surfaces read in place;
-  (b) host NV12 against host I420 through lfi_upload_images_yuv / lfi_download_views_yuv, next to the two *_yuv420 calls, both directions,
-      and lfi_download_views_yuv into NV12 device surfaces written in place;
+  (a) one time step: lfi_upload_images_yuv + lfi_upload_wait from host I420 surfaces (frames that cross PCIe, the yardstick;
+      lfi_upload_images_yuv420 is this call on a packed descriptor) against the same from NV12 device surfaces read in place;
+  (b) host NV12 against host I420 through lfi_upload_images_yuv / lfi_download_views_yuv, both directions, and lfi_download_views_yuv into
+      NV12 device surfaces written in place;
   (c) the kernels alone come from a SECOND run of this tool under
         rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/yuv_surfaces_time.py 3 1
       and  python tools/yuv_surfaces_time.py --kernels DIR/…_kernel_trace.csv
@@ -34,7 +34,7 @@ if len(sys.argv) > 2 and sys.argv[1] == "--kernels":
     groups = {}
     for r in trace:
         name = r["Kernel_Name"].split("(")[0]
-        if "yuvs_" not in name and "yuv420_" not in name:
+        if "yuvs_" not in name:
             continue
         grid = (int(r.get("Grid_Size_X", r.get("Grid_Size", 0))), int(r.get("Grid_Size_Y", 0) or 0), int(r.get("Grid_Size_Z", 0) or 0))
         groups.setdefault((name, grid), []).append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e6)
@@ -97,9 +97,8 @@ for name in names:
             return call
 
         up = {
-            "up_host_i420_yuv420_ms": wait(lambda: ctx.upload_images_yuv420(i420_host)),       # the path from before
             "up_device_nv12_in_place_ms": wait(lambda: ctx.upload_images_yuv(s_nv12_dev, n)),
-            "up_host_i420_surfaces_ms": wait(lambda: ctx.upload_images_yuv(s_i420_host, n)),
+            "up_host_i420_surfaces_ms": wait(lambda: ctx.upload_images_yuv(s_i420_host, n)),          # the yardstick
             "up_host_nv12_surfaces_ms": wait(lambda: ctx.upload_images_yuv(s_nv12_host, n)),
         }
         before = ctx.memory_info().workspace_bytes
@@ -110,9 +109,9 @@ for name in names:
             assert (grid[g].cpu().numpy() == ref.rgba(i420_host[g], W, H, ref.BT709, ref.LIMITED, ref.BILINEAR)).all(), (name, g)
         for key, fn in up.items():
             row[key] = timed(fn)
-        row["device_over_host"] = round(row["up_device_nv12_in_place_ms"] / row["up_host_i420_yuv420_ms"], 4)
-        row["condition_device_below_host"] = bool(row["up_device_nv12_in_place_ms"] < row["up_host_i420_yuv420_ms"])
-        row["host_GBps"] = round(n * fb / row["up_host_i420_yuv420_ms"] / 1e6, 1)
+        row["device_over_host"] = round(row["up_device_nv12_in_place_ms"] / row["up_host_i420_surfaces_ms"], 4)
+        row["condition_device_below_host"] = bool(row["up_device_nv12_in_place_ms"] < row["up_host_i420_surfaces_ms"])
+        row["host_GBps"] = round(n * fb / row["up_host_i420_surfaces_ms"] / 1e6, 1)
         row["device_read_write_GBps"] = round(n * W * H * 5.5 / row["up_device_nv12_in_place_ms"] / 1e6, 1)
         print(json.dumps(row), flush=True)
 
@@ -127,7 +126,6 @@ for name in names:
         d_nv12_host = ctx.yuv_surfaces_packed("nv12", "host", out_nv12.ctypes.data, keep=out_nv12)
         d_nv12_dev = ctx.yuv_surfaces_packed("nv12", "device", out_dev.data_ptr(), keep=out_dev)
         down = {
-            "down_host_i420_yuv420_ms": lambda: ctx.download_views_yuv420(out=out_i420),
             "down_host_i420_surfaces_ms": lambda: ctx.download_views_yuv(d_i420_host),
             "down_host_nv12_surfaces_ms": lambda: ctx.download_views_yuv(d_nv12_host),
             "down_device_nv12_in_place_ms": lambda: ctx.download_views_yuv(d_nv12_dev),
