@@ -431,7 +431,9 @@ typedef struct lfi_memory {
     size_t workspace_bytes; /* focus-map workspace + lfi_focus_curve's / lfi_focus_tiles' curves and partial sums + (planar view layout) the RGBA scratch copy of the views that renders other than TEN_WM and
                              * STD on more than 64 images go through, and the one-plane staging buffer of downloads + the kept views (lfi_keep_views) and
                              * lfi_compare_views' staging buffers and partial sums + lfi_download_native's device image + the device frames of
-                             * lfi_download_views_yuv420 / lfi_render_stream_yuv420 + the staged frames of lfi_upload_images_yuv420 */
+                             * lfi_download_views_yuv420 / lfi_render_stream_yuv420 + the staged frames of lfi_upload_images_yuv420 + the device image of the quilt calls
+                             * (lfi_download_quilt*, lfi_download_native's scaled tiles; lfi_download_quilt_yuv reserves it for odd tile sizes
+                             * only).  A change of this report: the quilt calls' device image was not counted before lfi_download_quilt_yuv */
     float derived_build_ms;
 } lfi_memory;
 int lfi_memory_info(lfi_ctx *ctx, lfi_memory *out);
@@ -609,6 +611,28 @@ int lfi_upload_images_yuv(lfi_ctx *ctx, int g0, int n, int matrix, int range, in
  * refused by lfi_yuv_surfaces_check; LFI_MEM_DEVICE with a pointer that is not device memory of the context's device or whose allocation
  * ends before the last frame does. */
 int lfi_download_views_yuv(lfi_ctx *ctx, int v0, int n, int matrix, int range, const lfi_yuv_surfaces *dst);
+/* A QUILT VIDEO frame: the scaled quilt as ONE 8-bit YUV 4:2:0 frame, made on the device — light-field video as holographic displays and
+ * players take it, one quilt per time step in ordinary 4:2:0 video.  No new arithmetic: let Q be the RGBA image that
+ * lfi_download_quilt_scaled(ctx, tiles_x, tiles_y, v0, tile_w, tile_h, ...) delivers — QW = tiles_x*tile_w by QH = tiles_y*tile_h pixels, tiles
+ * left to right and top to bottom, the exact area filter, tile = W x H the views themselves.  The frame is what lfi_download_views_yuv420's
+ * definition makes of Q taken as one view of QW x QH: Y per pixel; Cb and Cr from the sums over the four pixels of each 2 x 2 block of Q's
+ * coordinates (a block straddles two or four tiles where a tile size is odd); an odd last column or row replicated; matrix and range select
+ * one of the four coefficient sets.
+ * dst describes ONE frame (n = 1) of QW x QH: I420 or NV12, any pitches and offsets that lfi_yuv_surfaces_check(dst, QW, QH, 1) accepts, in
+ * host or device memory.  Synchronous, ordered like lfi_download_quilt_scaled; both view layouts, and attached views, are read in place; no
+ * view, map or kept view is written.  ONLY the planes' own bytes of dst are written: pitch padding and gaps keep their values.
+ *  - The destination is routed as lfi_download_views_yuv routes it: LFI_MEM_DEVICE with base, frame_stride, pitches and offsets multiples of 16 is written
+ *    by the kernel itself; everything else goes through one device frame the context owns (that of lfi_download_views_yuv420:
+ *    lfi_memory.workspace_bytes, LFI_POISON_SCRATCH) and copies of the frame's own bytes.
+ *  - EVEN tile_w and tile_h (what encoders take): every 2 x 2 block lies inside one tile, and ONE kernel resizes and converts — no RGBA quilt
+ *    exists anywhere, the quilt buffer of lfi_download_quilt_scaled is neither reserved nor touched.
+ *  - An ODD tile_w or tile_h: blocks straddle tiles; the RGBA quilt is made in lfi_download_quilt_scaled's device buffer and converted by the
+ *    kernel of lfi_download_views_yuv as one view of QW x QH (two launches).
+ * LFI_EINVAL, the context usable, dst and lfi_memory.workspace_bytes untouched: whatever lfi_download_quilt_scaled refuses (nothing rendered,
+ * the tiles or views out of range, a tile size outside the limits, views of more than 65535 pixels along an axis, a row window); an unknown
+ * matrix or range; dst refused by lfi_yuv_surfaces_check for (QW, QH, 1); LFI_MEM_DEVICE with a pointer that is not device memory of the
+ * context's device or whose allocation ends before the frame does. */
+int lfi_download_quilt_yuv(lfi_ctx *ctx, int tiles_x, int tiles_y, int v0, int tile_w, int tile_h, int matrix, int range, const lfi_yuv_surfaces *dst);
 int lfi_upload_map(lfi_ctx *ctx, int k, const uint8_t *rgba, size_t pitch_bytes); /* tests: inject a focus map */
 /* view v's map k (0 or 1) of the per-view maps (lfi_view_focus_maps).  Synchronous.  The upload is a test hook like lfi_upload_map (it
  * allocates the per-view maps if needed and does not put them in use: renders read them after a successful lfi_view_focus_maps). */

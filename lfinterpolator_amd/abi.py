@@ -55,6 +55,7 @@ ABI_SYMBOLS = [
     "lfi_keep_views", "lfi_compare_views", "lfi_set_focus_steps", "lfi_focus_steps", "lfi_download_native",
     "lfi_download_views_yuv420", "lfi_render_stream_yuv420", "lfi_upload_images_yuv420",
     "lfi_yuv_surfaces_check", "lfi_yuv_surfaces_packed", "lfi_upload_images_yuv", "lfi_download_views_yuv",
+    "lfi_download_quilt_yuv",
 ]
 
 
@@ -215,6 +216,7 @@ def load_hip_library() -> C.CDLL:
         "lfi_yuv_surfaces_packed": (i, [i, i, vp, i, i, C.POINTER(YuvSurfaces)]),
         "lfi_upload_images_yuv": (i, [vp, i, i, i, i, i, C.POINTER(YuvSurfaces)]),
         "lfi_download_views_yuv": (i, [vp, i, i, i, i, C.POINTER(YuvSurfaces)]),
+        "lfi_download_quilt_yuv": (i, [vp, i, i, i, i, i, i, i, C.POINTER(YuvSurfaces)]),
         "lfi_alloc_pinned": (i, [sz, C.POINTER(vp)]),
         "lfi_free_pinned": (i, [vp]),
         "lfi_grid_modified": (i, [vp]),
@@ -686,6 +688,13 @@ class Context:
         n = self.views - v0 if n is None else n
         self._check(self._lib.lfi_download_views_yuv(self._h, v0, n, YUV_MATRICES.get(matrix, matrix), YUV_RANGES.get(range, range),
                                                      C.byref(surfaces) if surfaces is not None else None))
+
+    def download_quilt_yuv(self, tiles_x: int, tiles_y: int, v0: int, tile_w: int, tile_h: int, matrix, range, surfaces: YuvSurfaces) -> None:
+        """the scaled quilt of views v0 … (download_quilt_scaled's tiles) as ONE YUV 4:2:0 frame of tiles_x·tile_w × tiles_y·tile_h in `surfaces`
+        (lfi_download_quilt_yuv): a frame of a quilt video.  Only the planes' own bytes are written; even tile sizes take one kernel and no RGBA
+        quilt; a device surface whose base, pitches and offsets are multiples of 16 is written by the kernel itself."""
+        self._check(self._lib.lfi_download_quilt_yuv(self._h, tiles_x, tiles_y, v0, tile_w, tile_h, YUV_MATRICES.get(matrix, matrix),
+                                                     YUV_RANGES.get(range, range), C.byref(surfaces) if surfaces is not None else None))
 
     def render_stream_yuv420(self, method, weights: np.ndarray, out: np.ndarray | None = None, all_focus: bool = False, matrix="709",
                              range="limited") -> np.ndarray:

@@ -9,6 +9,7 @@
 #include "lfi_dispatch.hpp"
 #include "lfi_focus_sched.hpp"
 #include "quilt_scaled.hpp"
+#include "quilt_yuv.hpp"
 #include "native_image.hpp"
 #include "yuv420.hpp"
 #include "yuv420_upload.hpp"
@@ -372,8 +373,19 @@ int check_device_surfaces(lfi_ctx *ctx, const char *who, const lfi_yuv_surfaces 
     return LFI_OK;
 }
 
-// the frames' own bytes between n caller frames (from frame k0 on) and n staged ones at dev, on st; to_staged: caller → staged
-hipError_t enqueue_surface_copies(hipStream_t st, const lfi_yuv_surfaces &s, int k0, int n, const lfi::YuvGeometry &g, uint8_t *dev, bool to_staged)
+// host frames whose rows are tight but which are not the staged frame (W no multiple of 8 or H odd): a 2D copy between the two moves row by
+// row; such a frame can go through a packed device copy of its planes instead (enqueue_surface_copies' pack)
+bool yuv_surfaces_packable(const lfi_yuv_surfaces &s, const lfi::YuvGeometry &g)
+{
+    return s.memory == LFI_MEM_HOST && !yuv_surfaces_like_staged(s, g) && s.y_pitch == g.W && s.c_pitch == (s.format == LFI_YUV_NV12 ? 2 * (size_t)g.cw : g.cw);
+}
+
+// the frames' own bytes between n caller frames (from frame k0 on) and n staged ones at dev, on st; to_staged: caller → staged.
+// pack (staged → caller only; NULL: none): device memory for one tight frame (g.frame_bytes), given only where the caller has found
+// yuv_surfaces_packable(s, g): each plane is first packed on the device (one device-to-device 2D copy) and then leaves as ONE contiguous
+// copy instead of a copy per row
+hipError_t enqueue_surface_copies(hipStream_t st, const lfi_yuv_surfaces &s, int k0, int n, const lfi::YuvGeometry &g, uint8_t *dev, bool to_staged,
+                                  uint8_t *pack = nullptr)
 {
     const hipMemcpyKind kind = s.memory == LFI_MEM_DEVICE ? hipMemcpyDeviceToDevice : to_staged ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost;
     const lfi::YuvSurfaces t = staged_surfaces(g, s.format, dev);
@@ -396,9 +408,20 @@ hipError_t enqueue_surface_copies(hipStream_t st, const lfi_yuv_surfaces &s, int
         } planes[3] = {{0, 0, s.y_pitch, t.y_pitch, g.W, g.H},
                        {s.c_offset, t.c_offset, s.c_pitch, t.c_pitch, nv12 ? 2 * (size_t)g.cw : g.cw, g.ch},
                        {s.cr_offset, t.cr_offset, s.c_pitch, t.c_pitch, g.cw, g.ch}};
+        size_t packed = 0; // the plane's offset in the packed frame
         for(int p = 0; p < (nv12 ? 2 : 3); p++)
         {
             const auto &pl = planes[p];
+            if(pack && !to_staged)
+            {
+                hipError_t e = hipMemcpy2DAsync(pack + packed, pl.width, d + pl.d_off, pl.d_pitch, pl.width, pl.rows, hipMemcpyDeviceToDevice, st);
+                if(e == hipSuccess)
+                    e = hipMemcpyAsync(f + pl.f_off, pack + packed, pl.width * pl.rows, hipMemcpyDeviceToHost, st);
+                if(e != hipSuccess)
+                    return e;
+                packed += pl.width * pl.rows;
+                continue;
+            }
             const hipError_t e = to_staged ? hipMemcpy2DAsync(d + pl.d_off, pl.d_pitch, f + pl.f_off, pl.f_pitch, pl.width, pl.rows, kind, st)
                                            : hipMemcpy2DAsync(f + pl.f_off, pl.f_pitch, d + pl.d_off, pl.d_pitch, pl.width, pl.rows, kind, st);
             if(e != hipSuccess)
@@ -1488,7 +1511,7 @@ int lfi_memory_info(lfi_ctx *ctx, lfi_memory *out)
     out->maps_bytes = (ctx->maps ? plane_bytes(ctx) * 2 : 0) + ctx->view_maps.bytes();
     out->workspace_bytes = ctx->focus_ws.bytes() + ctx->curve_ws.bytes() + ctx->rgba_scratch.bytes() + ctx->dl_plane.bytes() + ctx->kept.bytes() +
                            ctx->cmp_stage[0].bytes() + ctx->cmp_stage[1].bytes() + ctx->cmp_ws.bytes() + ctx->native.bytes() + ctx->yuv[0].bytes() + ctx->yuv[1].bytes() +
-                           ctx->yuv_in.bytes();
+                           ctx->yuv_in.bytes() + ctx->quilt.bytes();
     out->derived_build_ms = ctx->derived_build_ms;
     return LFI_OK;
 }
@@ -2102,6 +2125,18 @@ static int check_scaled_tiles(lfi_ctx *ctx, int tile_w, int tile_h)
     return LFI_OK;
 }
 
+// what lfi_download_quilt_tiles_scaled and lfi_download_quilt_yuv refuse alike before they look at the destination
+static int check_scaled_quilt(lfi_ctx *ctx, int tiles_x, int tiles_y, int first_tile, int n, int v0, int tile_w, int tile_h)
+{
+    if(!ctx->views || !ctx->have_params)
+        return fail(ctx, LFI_EINVAL, "nothing rendered yet");
+    if(ctx->windowed)
+        return fail(ctx, LFI_EINVAL, "a scaled quilt needs whole views: a tile's rows average source rows the row window's band does not hold");
+    if(int rc = check_quilt_tiles(ctx, tiles_x, tiles_y, first_tile, n, v0))
+        return rc;
+    return check_scaled_tiles(ctx, tile_w, tile_h);
+}
+
 // Tiles [first, first + n) of a quilt tiles_x tiles wide → the host image, on the compute stream.  The quilt buffer holds the rows of tiles
 // they touch, from row first / tiles_x on, a tile tile_bytes wide and dev_rows high; in the host image a tile is host_rows high and the
 // device's rows are its rows from host_y0 on (a row window: only the band's rows of every tile exist).  One rectangle — or three when the
@@ -2183,13 +2218,7 @@ int lfi_download_quilt_tiles_scaled(lfi_ctx *ctx, int tiles_x, int tiles_y, int 
 {
     if(!ctx)
         return LFI_EINVAL;
-    if(!ctx->views || !ctx->have_params)
-        return fail(ctx, LFI_EINVAL, "nothing rendered yet");
-    if(ctx->windowed)
-        return fail(ctx, LFI_EINVAL, "a scaled quilt needs whole views: a tile's rows average source rows the row window's band does not hold");
-    if(int rc = check_quilt_tiles(ctx, tiles_x, tiles_y, first_tile, n, v0))
-        return rc;
-    if(int rc = check_scaled_tiles(ctx, tile_w, tile_h))
+    if(int rc = check_scaled_quilt(ctx, tiles_x, tiles_y, first_tile, n, v0, tile_w, tile_h))
         return rc;
     const int W = ctx->width, H = ctx->height;
     if(!rgba || pitch_bytes < (size_t)tiles_x * tile_w * 4)
@@ -2220,6 +2249,77 @@ int lfi_download_quilt_scaled(lfi_ctx *ctx, int tiles_x, int tiles_y, int v0, in
     if(ctx && (tiles_x < 1 || tiles_y < 1))
         return fail(ctx, LFI_EINVAL, "quilt needs tiles_x*tiles_y views starting at v0 inside [0, views)");
     return lfi_download_quilt_tiles_scaled(ctx, tiles_x, tiles_y, 0, tiles_x * tiles_y, v0, tile_w, tile_h, rgba, pitch_bytes);
+}
+
+int lfi_download_quilt_yuv(lfi_ctx *ctx, int tiles_x, int tiles_y, int v0, int tile_w, int tile_h, int matrix, int range, const lfi_yuv_surfaces *dst)
+{
+    static const char *who = "lfi_download_quilt_yuv";
+    if(!ctx)
+        return LFI_EINVAL;
+    // what lfi_download_quilt_scaled refuses, in its words and order (n = 0, which the check refuses, where the product is no count of tiles)
+    const long tiles = (long)tiles_x * tiles_y;
+    const int n = tiles_x >= 1 && tiles_y >= 1 && tiles <= INT32_MAX ? (int)tiles : 0;
+    if(int rc = check_scaled_quilt(ctx, tiles_x, tiles_y, 0, n, v0, tile_w, tile_h))
+        return rc;
+    if(int rc = check_yuv_out(ctx, who, matrix, range))
+        return rc;
+    if((long)tiles_x * tile_w > INT32_MAX || (long)tiles_y * tile_h > INT32_MAX)
+        return fail(ctx, LFI_EINVAL, std::string(who) + ": the frame is more than 2^31 - 1 pixels wide or high");
+    const int QW = tiles_x * tile_w, QH = tiles_y * tile_h;
+    size_t extent = 0;
+    if(const char *fault = yuv_surfaces_fault(dst, QW, QH, 1, &extent))
+        return fail(ctx, LFI_EINVAL, std::string(who) + ": " + fault);
+    if(int rc = bind(ctx))
+        return rc;
+    if(dst->memory == LFI_MEM_DEVICE)
+        if(int rc = check_device_surfaces(ctx, who, *dst, extent, 1))
+            return rc;
+    // the destination, as download_yuv_surfaces routes it: the caller's frame in place, or the staged frame and the copies of its own bytes
+    const lfi::YuvGeometry g = lfi::yuv_geometry(QW, QH);
+    const bool in_place = yuv_surfaces_in_place(*dst);
+    // a host frame with tight rows that is not the staged frame (QW no multiple of 8, or QH odd) leaves through a packed device copy
+    // (yuv[1]): one contiguous copy per plane instead of one per row
+    const bool packs = !in_place && yuv_surfaces_packable(*dst, g);
+    if(!in_place)
+        LFI_HIP(ctx, ctx->yuv[0].reserve(g.dev_frame_bytes));
+    if(packs)
+        LFI_HIP(ctx, ctx->yuv[1].reserve(g.frame_bytes));
+    const lfi::YuvSurfaces frame = in_place ? caller_surfaces(*dst) : staged_surfaces(g, dst->format, ctx->yuv[0].get());
+    const bool planar = ctx->out_layout == LFI_LAYOUT_PLANAR_RGB;
+    lfi::QuiltScaleArgs q{};
+    q.views = ctx->views.get();
+    q.view_stride = out_plane_bytes(ctx);
+    q.W = ctx->width, q.H = ctx->height, q.pitch = planar ? view_pitch(ctx) : 0;
+    q.tile_w = tile_w, q.tile_h = tile_h;
+    q.v0 = v0, q.first = 0, q.tiles_x = tiles_x;
+    if(tile_w % 2 == 0 && tile_h % 2 == 0)
+    {
+        // every 2 x 2 block lies inside one tile: ONE launch, no RGBA quilt
+        lfi::QuiltYuvArgs a{};
+        a.q = q, a.s = frame, a.k = lfi::YUV_COEFFS[matrix * 2 + range];
+        LFI_HIP(ctx, lfi::launch_quilt_yuv_scale(ctx->stream, planar, dst->format, a, n));
+    }
+    else
+    {
+        // blocks straddle tiles: the RGBA quilt of lfi_download_quilt_scaled in the quilt buffer, converted as ONE RGBA view of QW x QH
+        LFI_HIP(ctx, ctx->quilt.reserve((size_t)QW * 4 * QH));
+        q.quilt = ctx->quilt.as<uint32_t>();
+        LFI_HIP(ctx, lfi::launch_quilt_scale(ctx->stream, planar, q, n));
+        lfi::YuvsOutArgs a{};
+        a.src = ctx->quilt.get();
+        a.s = frame;
+        a.view_stride = (size_t)QW * 4 * QH;
+        a.W = QW, a.H = QH, a.pitch = 0;
+        a.cw = g.cw, a.ch = g.ch;
+        a.blocks_x = g.y_pitch / lfi::YUV_BLOCK_W;
+        a.rows16 = QW % 4 == 0; // the quilt buffer starts on a 16-byte boundary (hipMalloc), a row is QW·4 bytes
+        a.k = lfi::YUV_COEFFS[matrix * 2 + range];
+        LFI_HIP(ctx, lfi::launch_yuvs_convert(ctx->stream, false, dst->format, a, 1));
+    }
+    if(!in_place)
+        LFI_HIP(ctx, enqueue_surface_copies(ctx->stream, *dst, 0, 1, g, ctx->yuv[0].get(), false, packs ? ctx->yuv[1].get() : nullptr));
+    LFI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return LFI_OK;
 }
 
 int lfi_download_native(lfi_ctx *ctx, const lfi_lenticular *lens, int v0, int out_w, int out_h, int tile_w, int tile_h, uint8_t *rgba, size_t pitch_bytes)

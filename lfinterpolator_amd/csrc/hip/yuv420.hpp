@@ -11,7 +11,7 @@
 // not), one rounding, no shift of a negative number.
 //
 // Here: YUV_COEFFS; the block shape of every YUV kernel (a lane owns 8 columns × 2 rows, a workgroup is 64 lanes × 4 block rows);
-// yuv_geometry, the tight host frame and the padded staged frame a host call's frames pass through on the device (Y pitch a multiple of 8,
+// YuvSurfaces, the planes of a batch of frames as a kernel sees them; yuv_geometry, the tight host frame and the padded staged frame a host call's frames pass through on the device (Y pitch a multiple of 8,
 // chroma pitch of 4, an even number of Y rows: every word of a row lies inside it); yuv_luma and yuv_chroma; yuv_load_block, a lane's
 // 8 × 2 pixels out of RGBA or planar views with the definition's clamp; yuv_block_chroma.
 #pragma once
@@ -65,6 +65,17 @@ inline YuvGeometry yuv_geometry(const int width, const int height)
     g.tight = g.y_pitch == g.W && g.y_rows == g.H;
     return g;
 }
+
+constexpr int YUVS_I420 = 0; // LFI_YUV_I420
+constexpr int YUVS_NV12 = 1; // LFI_YUV_NV12
+
+// frame 0 of a batch of surfaces as a kernel sees it (yuv_surfaces.hpp, quilt_yuv.hpp)
+struct YuvSurfaces
+{
+    uint8_t *base;                                 // the Y plane of frame 0
+    size_t frame_stride, c_offset, cr_offset;      // cr_offset: I420 only
+    uint32_t y_pitch, c_pitch;
+};
 
 __device__ inline uint32_t yuv_luma(const YuvCoeffs &k, const uint32_t r, const uint32_t g, const uint32_t b)
 {

@@ -51,17 +51,6 @@
 
 namespace lfi {
 
-constexpr int YUVS_I420 = 0; // LFI_YUV_I420
-constexpr int YUVS_NV12 = 1; // LFI_YUV_NV12
-
-// frame 0 of a batch of surfaces as a kernel sees it
-struct YuvSurfaces
-{
-    uint8_t *base;                                 // the Y plane of frame 0
-    size_t frame_stride, c_offset, cr_offset;      // cr_offset: I420 only
-    uint32_t y_pitch, c_pitch;
-};
-
 struct YuvsInArgs
 {
     YuvSurfaces s;       // read only

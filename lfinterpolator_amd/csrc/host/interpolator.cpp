@@ -145,6 +145,11 @@ void Interpolator::finish()
         std::unique_ptr<lfi::Y4mWriter> writer = std::move(y4mWriter);
         writer->close();
     }
+    if(quiltY4mWriter)
+    {
+        std::unique_ptr<lfi::Y4mWriter> writer = std::move(quiltY4mWriter);
+        writer->close();
+    }
     if(nv12File.is_open())
     {
         nv12File.close();
@@ -203,6 +208,13 @@ void Interpolator::interpolate(std::string outputPath, std::string trajectory, f
         if(quiltTile.x < 1 || quiltTile.y < 1 || quiltTile.x > resolution.x || quiltTile.y > resolution.y)
             throw std::runtime_error("The quilt tile size has to be between 1x1 and the views' " + std::to_string(resolution.x) + "x" + std::to_string(resolution.y) +
                                      " pixels (views are only scaled down)!");
+    }
+    if(!quiltY4mPath.empty())
+    {
+        if(!(quiltTiles.x > 0 && quiltTiles.y > 0))
+            throw std::runtime_error("A quilt video needs a quilt (-q cols,rows)!");
+        if(gpuCount > 1)
+            throw std::runtime_error("A quilt video frame needs every view in one context: it works on one GPU only!");
     }
     if(nativeSize.x != 0 || nativeSize.y != 0)
     {
@@ -576,6 +588,42 @@ void Interpolator::storeResults(std::string path)
         }
         lfi::writePng((std::filesystem::path(path) / "quilt.png").string(), tile.x * quiltTiles.x, tile.y * quiltTiles.y, static_cast<int>(channels), quilt.data(),
                       quiltPitch);
+    }
+    if(!quiltY4mPath.empty())
+    {
+        if(quiltTiles.x * quiltTiles.y > viewCount)
+            throw std::runtime_error("The quilt has more tiles than rendered views!");
+        std::cout << "Storing quilt video frame..." << std::endl;
+        // resized and converted on the device (lfi_download_quilt_yuv): the one frame arrives as tight I420 in a page-locked buffer
+        const lfi::IVec2 tile = quiltTile.x > 0 ? quiltTile : lfi::IVec2{resolution.x, resolution.y};
+        const int quiltW = tile.x * quiltTiles.x, quiltH = tile.y * quiltTiles.y;
+        const size_t frameBytes = lfi::y4mFrameBytes(quiltW, quiltH);
+        uint8_t *frame = nullptr;
+        const bool framePinned = lfi_alloc_pinned(frameBytes, reinterpret_cast<void **>(&frame)) == LFI_OK;
+        std::vector<uint8_t> pageableFrame;
+        if(!framePinned)
+        {
+            pageableFrame.resize(frameBytes);
+            frame = pageableFrame.data();
+        }
+        try
+        {
+            lfi_yuv_surfaces surface{};
+            check(lfi_yuv_surfaces_packed(LFI_YUV_I420, LFI_MEM_HOST, frame, quiltW, quiltH, &surface));
+            check(lfi_download_quilt_yuv(context, quiltTiles.x, quiltTiles.y, 0, tile.x, tile.y, yuvMatrix, yuvRange, &surface));
+            // one file for all time steps of a light-field video: opened by the first, appended to by the others, closed by finish()
+            if(!quiltY4mWriter)
+                quiltY4mWriter = std::make_unique<lfi::Y4mWriter>(quiltY4mPath, quiltW, quiltH, y4mFps.x, y4mFps.y, yuvRange == LFI_YUV_FULL);
+            quiltY4mWriter->writeFrame(frame);
+        }
+        catch(...)
+        {
+            if(framePinned)
+                lfi_free_pinned(frame);
+            throw;
+        }
+        if(framePinned)
+            lfi_free_pinned(frame);
     }
     if(nativeSize.x > 0 && nativeSize.y > 0)
     {

@@ -67,6 +67,16 @@ class Interpolator
             yuvMatrix = matrix;
             yuvRange = range;
         }
+        // also write the quilt of setQuilt (scaled by setQuiltTile) as ONE frame of a Y4M video file: resized and converted to 8-bit YUV 4:2:0
+        // on the device (lfi_download_quilt_yuv into a host I420 frame; even tile sizes take one kernel and no RGBA quilt), same matrix, range
+        // and rate as setY4m.  The file stays open over the time steps: a light-field video gives a quilt video, one frame per step.  One GPU
+        void setQuiltY4m(std::string path, int fpsNum = 30, int fpsDen = 1, int matrix = LFI_YUV_BT709, int range = LFI_YUV_LIMITED)
+        {
+            quiltY4mPath = path;
+            y4mFps = {fpsNum, fpsDen};
+            yuvMatrix = matrix;
+            yuvRange = range;
+        }
         // a light-field video as input (a directory of <row>_<col>.y4m files, one per camera): its frames go to the device as they are, 1.5
         // bytes per pixel from page-locked memory, and become the RGBA images there (one lfi_upload_images_yuv420 call for the grid).
         // interpolate() renders time step setInputFrame(t), 0 by default, t in [0, frameCount()); called again after another setInputFrame
@@ -83,7 +93,7 @@ class Interpolator
             inChroma = chroma;
             loadedFrame = -1;
         }
-        // closes the video files of setY4m and setNv12 (interpolate() leaves them open for the next time step's views); throws when that fails
+        // closes the video files of setY4m, setNv12 and setQuiltY4m (interpolate() leaves them open for the next time step's views); throws when that fails
         void finish();
         float lastAverageTime() const { return averageTime; }
         // render on GPUs 0 … count-1 of this node: views are split into contiguous ranges, the grid is broadcast once (RCCL)
@@ -151,6 +161,8 @@ class Interpolator
         int yuvRange{LFI_YUV_LIMITED};
         std::unique_ptr<lfi::Y4mWriter> y4mWriter; // open from the first stored step to finish()
         std::string nv12Path;                      // empty: no raw NV12 file
+        std::string quiltY4mPath;                  // empty: no quilt video
+        std::unique_ptr<lfi::Y4mWriter> quiltY4mWriter; // open from the first stored step to finish()
         std::ofstream nv12File;                    // open from the first stored step to finish()
         std::unique_ptr<LfLoader> video;           // the input, where it is a light-field video
         int inputFrame{0}, loadedFrame{-1};        // the time step to render / the one on the device

@@ -4,7 +4,7 @@
 // grid; the search interval of an all-focus render found from it), --map-steps / --tile-steps (more than 32 candidates for the focus map / the focus tiles), --compare / --compare-methods (PSNR / SSIM of all views against a
 // directory of images or against the other method's render), --native / --lens / --native-tile / --native-views (the native image of a
 // lenticular display, interlaced on the GPU), --y4m / --nv12 / --fps / --yuv-matrix / --yuv-range (the views as one YUV 4:2:0 video file, converted on
-// the GPU), --frames / --in-matrix / --in-range / --in-chroma (a light-field video as input: a directory of per-camera Y4M files whose frames
+// the GPU), --quilt-y4m (the quilt as one YUV 4:2:0 video frame per time step: a quilt video), --frames / --in-matrix / --in-range / --in-chroma (a light-field video as input: a directory of per-camera Y4M files whose frames
 // become the images on the GPU) and --synthetic for runs without a dataset.
 #include <array>
 #include <iostream>
@@ -60,9 +60,10 @@ int main(int argc, char **argv)
                           "--native-views N - with --native: interlace the first N views (default: all of them)\n"
                           "--y4m FILE - also store the views as the frames of one YUV4MPEG2 video FILE, in view order (ffmpeg -i FILE, or any player): 8-bit YUV 4:2:0 (I420, centre-sited chroma), converted on the GPU before the download - 1.5 bytes per pixel cross PCIe instead of 4; with -g every GPU converts its own views\n"
                           "--nv12 FILE - also store the views as raw NV12 frames in FILE, in view order, tightly packed (the Y plane, then one plane of interleaved Cb/Cr): what hardware encoders take; converted on the GPU like --y4m, may be given next to it, and with --frames COUNT above 1 FILE takes all steps' views; prints the ffmpeg options that open FILE (-f rawvideo -pix_fmt nv12 -s WxH -r N)\n"
-                          "--fps N[:D] - with --y4m or --nv12: the frame rate N/D frames per second (default=30:1)\n"
-                          "--yuv-matrix 709|601 - with --y4m or --nv12: the colour matrix, BT.709 or BT.601 (default=709)\n"
-                          "--yuv-range limited|full - with --y4m or --nv12: limited (Y 16..235, chroma 16..240) or full (0..255) range (default=limited)\n"
+                          "--quilt-y4m FILE - with -q: also store the quilt (scaled by --quilt-tile) as one frame of the YUV4MPEG2 video FILE, resized and converted to 8-bit YUV 4:2:0 on the GPU in one pass (even tile sizes) - with --frames FIRST:COUNT one frame per time step: a quilt video, what holographic players take; one GPU only\n"
+                          "--fps N[:D] - with --y4m, --nv12 or --quilt-y4m: the frame rate N/D frames per second (default=30:1)\n"
+                          "--yuv-matrix 709|601 - with --y4m, --nv12 or --quilt-y4m: the colour matrix, BT.709 or BT.601 (default=709)\n"
+                          "--yuv-range limited|full - with --y4m, --nv12 or --quilt-y4m: limited (Y 16..235, chroma 16..240) or full (0..255) range (default=limited)\n"
                           "--frames FIRST[:COUNT] - with -i a directory of <row>_<col>.y4m files (a light-field video, one 8-bit YUV 4:2:0 file per camera): render time steps FIRST ... FIRST+COUNT-1 (default=0:1); the frames cross PCIe as they are, 1.5 bytes per pixel, and become the images on the GPU; with COUNT above 1 every step's files go to <-o>/fTTTT/ and --y4m FILE takes all steps' views in step order (with -n 1: the video of the moving scene from one virtual camera); not with --compare, --compare-methods or -g above 1 then\n"
                           "--in-matrix 709|601 - with a light-field video: the colour matrix of its files (default=709)\n"
                           "--in-range limited|full - with a light-field video: the range of its files (default: their XCOLORRANGE tag, else limited)\n"
@@ -179,9 +180,27 @@ int main(int argc, char **argv)
         return EXIT_FAILURE;
     }
 
-    if((args["--fps"] || args["--yuv-matrix"] || args["--yuv-range"]) && !args["--y4m"] && !args["--nv12"])
+    if(args["--quilt-y4m"] && !args["-q"])
     {
-        std::cerr << "--fps, --yuv-matrix and --yuv-range belong to the video file: they need --y4m FILE or --nv12 FILE." << std::endl;
+        std::cerr << "--quilt-y4m stores the quilt as a video frame: it needs -q cols,rows." << std::endl;
+        return EXIT_FAILURE;
+    }
+
+    if(args["--quilt-y4m"] && static_cast<std::string>(args["--quilt-y4m"]).empty())
+    {
+        std::cerr << "--quilt-y4m needs the name of the video file to write." << std::endl;
+        return EXIT_FAILURE;
+    }
+
+    if(args["--quilt-y4m"] && args["-g"] && static_cast<int>(args["-g"]) > 1)
+    {
+        std::cerr << "--quilt-y4m needs every view in one context, which assembles the frame: it works on one GPU only (-g 1)." << std::endl;
+        return EXIT_FAILURE;
+    }
+
+    if((args["--fps"] || args["--yuv-matrix"] || args["--yuv-range"]) && !args["--y4m"] && !args["--nv12"] && !args["--quilt-y4m"])
+    {
+        std::cerr << "--fps, --yuv-matrix and --yuv-range belong to the video file: they need --y4m FILE, --nv12 FILE or --quilt-y4m FILE." << std::endl;
         return EXIT_FAILURE;
     }
 
@@ -456,6 +475,8 @@ int main(int argc, char **argv)
             interpolator->setY4m(static_cast<std::string>(args["--y4m"]), fpsNum, fpsDen, yuvMatrix, yuvRange);
         if(args["--nv12"])
             interpolator->setNv12(static_cast<std::string>(args["--nv12"]), fpsNum, fpsDen, yuvMatrix, yuvRange);
+        if(args["--quilt-y4m"])
+            interpolator->setQuiltY4m(static_cast<std::string>(args["--quilt-y4m"]), fpsNum, fpsDen, yuvMatrix, yuvRange);
         if(args["--compare"])
             interpolator->setCompareDir(static_cast<std::string>(args["--compare"]));
         if(args["--compare-methods"])
