@@ -640,9 +640,18 @@ int lfi_download_view_map(lfi_ctx *ctx, int v, int k, uint8_t *rgba, size_t pitc
 int lfi_upload_view_map(lfi_ctx *ctx, int v, int k, const uint8_t *rgba, size_t pitch_bytes);
 
 /* PSNR / SSIM of rendered view v against a reference image on the host, reduced on the device — replaces
- * scripts/imageQualityMetrics.sh:1-12 (ffmpeg psnr / ssim on two PNGs).  Definitions (csrc/hip/quality.hpp): PSNR per colour
- * channel from the mean squared error over all pixels, "all" from the mean of the three MSEs; SSIM per channel = mean over all 8×8
- * windows at stride 4 of the standard index with C1 = (0.01·255)², C2 = (0.03·255)², "all" = mean of the channels.  Synchronous. */
+ * scripts/imageQualityMetrics.sh:1-12 (ffmpeg psnr / ssim on two PNGs; scripts/compareDirs.sh loops it over directories).  ffmpeg is not
+ * part of this product, so the definitions are fixed HERE (the tests restate them in numpy: tests/quality_ref.py):
+ *   PSNR  per colour channel c: 10·log10(255² / MSE_c), MSE_c over all pixels; "all" from the mean of the three MSEs;
+ *   SSIM  per colour channel: the mean over all 8×8 windows at a stride of 4 pixels (the window set of ffmpeg's ssim filter) of
+ *         ((2·μa·μb + C1)(2·σab + C2)) / ((μa² + μb² + C1)(σa² + σb² + C2)), C1 = (0.01·255)², C2 = (0.03·255)², with the window's
+ *         biased moments (sums over its 64 pixels); "all" = the mean of the three channels; 1.0 when no window fits.  Alpha is ignored.
+ * Squared errors are summed exactly in integers; window SSIMs are summed in fp64.
+ * lfi_compare_view IS lfi_compare_views (below) for n = 1 and one host reference with image_stride_bytes = pitch_bytes · H: the same
+ * kernels, so out equals that call's out[0].q byte for byte, and the SSIM sums are added in a fixed order — two calls on the same data
+ * return the same bits (earlier versions added them with floating-point atomics and could differ in the last bits from run to run;
+ * MSE and PSNR, integer sums, are what they were).  Both view layouts are read as they are.  Synchronous.  LFI_EINVAL: nothing rendered
+ * yet; a bad view index, pointer or pitch; a row window. */
 typedef struct lfi_quality {
     double mse[3], psnr[3], psnr_all; /* identical images: mse 0, psnr +inf */
     double ssim[3], ssim_all;
@@ -681,7 +690,7 @@ int lfi_compare_view(lfi_ctx *ctx, int v, const uint8_t *reference_rgba, size_t 
  *    out == NULL; a row window; NULL references without a kept set or with one that does not cover the range (a set kept in another
  *    layout has been dropped). */
 typedef struct lfi_view_quality {
-    lfi_quality q;             /* the definitions of lfi_compare_view / quality.hpp, unchanged */
+    lfi_quality q;             /* the definitions at lfi_compare_view above, unchanged */
     uint64_t sq_err[3];        /* sum of (a-b)^2 per colour channel: exact */
     uint64_t differing_bytes;  /* colour bytes (R, G, B; alpha ignored) with a != b: exact */
     uint64_t windows;          /* 8x8 windows at stride 4 that fit */

@@ -16,8 +16,8 @@
 
 #include "../../../include/lfi.h"
 #include "lfi_device.hpp"
-#include "quality.hpp"
 #include "quality_batch.hpp"
+#include "views_src.hpp"
 
 using lfi::KernelArgs;
 
@@ -312,8 +312,6 @@ struct lfi_ctx
     PinnedBuffer stream_staging[2];
     DeviceBuffer views2;
     Event ev_h2d[2], ev_rendered[2], ev_d2h[2];
-    DeviceBuffer quality_sums; // lfi_compare_view: one lfi::QualitySums, kept until the context goes
-    DeviceBuffer quality_ref;
     // lfi_keep_views: a copy of views [kept_v0, kept_v0 + kept_n) in the layout they were rendered in — lfi_compare_views' device-side references
     DeviceBuffer kept;
     int kept_v0 = 0, kept_n = 0;
@@ -420,7 +418,15 @@ int fail(lfi_ctx *ctx, int code, const std::string &msg)
     return code;
 }
 
-#define LFI_HIP(ctx, call)                                                                                            \
+// what every call that reads the rendered views refuses first, in the same words
+int check_rendered(lfi_ctx *ctx)
+{
+    if(!ctx->views || !ctx->have_params)
+        return fail(ctx, LFI_EINVAL, "nothing rendered yet");
+    return LFI_OK;
+}
+
+#define LFI_HIP(ctx, call)                                                                                           \
     do                                                                                                                \
     {                                                                                                                 \
         hipError_t e_ = (call);                                                                                       \
@@ -492,6 +498,15 @@ size_t out_plane_bytes(const lfi_ctx *c) // one view as stored on the device
     if(c->out_layout == LFI_LAYOUT_PLANAR_RGB)
         return (size_t)3 * c->out_rows * view_pitch(c);
     return rgba_out_plane_bytes(c);
+}
+
+// The rendered views from view v0 on as a kernel reads them, H = the rows the views hold (out_rows).  *planar: the layout, which picks the
+// kernel's instantiation
+lfi::ViewsSrc rendered_views(const lfi_ctx *c, int v0, bool *planar)
+{
+    *planar = c->out_layout == LFI_LAYOUT_PLANAR_RGB;
+    const size_t stride = out_plane_bytes(c);
+    return lfi::ViewsSrc{c->views.get() + (size_t)v0 * stride, stride, (uint32_t)c->width, (uint32_t)c->out_rows, *planar ? (uint32_t)view_pitch(c) : 0u};
 }
 
 KernelArgs make_args(const lfi_ctx *c, int v0, int v1, int all_focus_method)
@@ -704,7 +719,6 @@ void free_views(lfi_ctx *c)
     c->yuv[0].release();
     c->yuv[1].release();
     c->views2.release();
-    c->quality_ref.release();
     c->cmp_stage[0].release();
     c->cmp_stage[1].release();
     c->cmp_ws.release();

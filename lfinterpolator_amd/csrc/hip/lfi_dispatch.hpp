@@ -845,21 +845,4 @@ int launch_view_rows(lfi_ctx *c, ViewRowsKind k, int method, int all_focus, cons
     return LFI_OK;
 }
 
-// device pointer and pitch of view v as an RGBA plane of out_rows rows: the view itself, or (planar layout) its expansion into the
-// context's one-plane staging buffer — valid until the next call, ordered on the context's stream
-int rgba_plane_of_view(lfi_ctx *c, int v, const uint8_t **out)
-{
-    if(c->out_layout != LFI_LAYOUT_PLANAR_RGB)
-    {
-        *out = c->views.get() + out_plane_bytes(c) * v;
-        return LFI_OK;
-    }
-    LFI_HIP(c, c->dl_plane.fit(rgba_out_plane_bytes(c)));
-    hipLaunchKernelGGL(lfi::view_planar_to_rgba, dim3(((c->width + 3) / 4 + 255) / 256, c->out_rows), dim3(256), 0, c->stream,
-                       c->views.get() + out_plane_bytes(c) * v, c->dl_plane.as<uint32_t>(), c->width, c->out_rows, view_pitch(c));
-    LFI_HIP(c, hipGetLastError());
-    *out = c->dl_plane.get();
-    return LFI_OK;
-}
-
 } // namespace

@@ -1560,49 +1560,76 @@ static int check_yuv_out(lfi_ctx *ctx, const char *who, int matrix, int range)
 // what lfi_download_views_yuv420 and lfi_download_views_yuv refuse alike, before they look at the frames
 static int check_yuv_download(lfi_ctx *ctx, const char *who, int v0, int n, int matrix, int range)
 {
-    if(!ctx->views || !ctx->have_params)
-        return fail(ctx, LFI_EINVAL, "nothing rendered yet");
+    if(int rc = check_rendered(ctx))
+        return rc;
     if(n < 1 || v0 < 0 || (long)v0 + n > ctx->views_n)
         return fail(ctx, LFI_EINVAL, std::string(who) + ": needs n >= 1 views starting at v0 inside [0, views)");
     return check_yuv_out(ctx, who, matrix, range);
 }
 
-// views [v0, v0 + n) of `views` (in the context's layout) → the n frames of s (of `format`: staged ones, or the caller's in place), one
-// launch on st
-static hipError_t enqueue_views_convert(lfi_ctx *ctx, hipStream_t st, const uint8_t *views, int v0, int n, int matrix, int range, int format, const lfi::YuvSurfaces &s)
+// The ONE yuvs_convert launch, on st: view i of src → frame i of s (of `format`), n of them.  src starts on a 16-byte boundary (the views:
+// hipMalloc, lfi_attach_views checks; the quilt buffer: hipMalloc) and a view is W·H·4 bytes, so with W a multiple of 4 every RGBA row
+// does.  blocks_x is yuv_geometry's y_pitch / YUV_BLOCK_W: the same number.
+static hipError_t enqueue_yuv_convert(hipStream_t st, const lfi::ViewsSrc &src, bool planar, int n, int matrix, int range, int format, const lfi::YuvSurfaces &s)
 {
-    const bool planar = ctx->out_layout == LFI_LAYOUT_PLANAR_RGB;
     lfi::YuvsOutArgs a{};
-    a.src = views + (size_t)v0 * out_plane_bytes(ctx);
-    a.s = s;
-    a.view_stride = out_plane_bytes(ctx);
-    a.W = ctx->width, a.H = ctx->height, a.pitch = planar ? view_pitch(ctx) : 0;
-    a.cw = (a.W + 1) >> 1, a.ch = (a.H + 1) >> 1;
-    a.blocks_x = (a.W + lfi::YUV_BLOCK_W - 1) / lfi::YUV_BLOCK_W;
-    a.rows16 = a.W % 4 == 0; // the views start on 16-byte boundaries (hipMalloc; lfi_attach_views checks), a view is W·H·4 bytes
+    a.src = src, a.s = s;
+    a.cw = (src.W + 1) >> 1, a.ch = (src.H + 1) >> 1;
+    a.blocks_x = (src.W + lfi::YUV_BLOCK_W - 1) / lfi::YUV_BLOCK_W;
+    a.rows16 = src.W % 4 == 0;
     a.k = lfi::YUV_COEFFS[matrix * 2 + range];
     return lfi::launch_yuvs_convert(st, planar, format, a, n);
 }
 
-// Behind both download calls.  The arguments have passed check_yuv_download; dst is what host_i420_surfaces made, or has passed
-// yuv_surfaces_fault, which gave extent
-static int download_yuv_surfaces(lfi_ctx *ctx, const char *who, int v0, int n, int matrix, int range, const lfi_yuv_surfaces &dst, size_t extent)
+// How n frames of W × H reach dst, which has passed yuv_surfaces_fault (that gave extent) or is what host_i420_surfaces made: the kernel
+// writes the caller's device surfaces in place, or staged frames in yuv[0] whose own bytes are then copied.  may_pack: a single host frame
+// with tight rows that is not the staged frame (W no multiple of 8, or H odd) leaves through a packed device copy (yuv[1]): one contiguous
+// copy per plane instead of one per row.
+struct YuvDelivery
+{
+    lfi::YuvGeometry g;
+    lfi::YuvSurfaces frames; // what the kernel writes
+    bool in_place, packs;
+};
+
+// binds the device, checks a device surface, picks the route and reserves its buffers
+static int open_yuv_delivery(lfi_ctx *ctx, const char *who, const lfi_yuv_surfaces &dst, size_t extent, int W, int H, int n, bool may_pack, YuvDelivery *d)
 {
     if(int rc = bind(ctx))
         return rc;
     if(dst.memory == LFI_MEM_DEVICE)
         if(int rc = check_device_surfaces(ctx, who, dst, extent, n))
             return rc;
-    const lfi::YuvGeometry g = lfi::yuv_geometry(ctx->width, ctx->height);
-    const bool in_place = yuv_surfaces_in_place(dst);
-    if(!in_place)
-        LFI_HIP(ctx, ctx->yuv[0].reserve(g.dev_frame_bytes * n));
-    LFI_HIP(ctx, enqueue_views_convert(ctx, ctx->stream, ctx->views.get(), v0, n, matrix, range, dst.format,
-                                       in_place ? caller_surfaces(dst) : staged_surfaces(g, dst.format, ctx->yuv[0].get())));
-    if(!in_place)
-        LFI_HIP(ctx, enqueue_surface_copies(ctx->stream, dst, 0, n, g, ctx->yuv[0].get(), false));
+    d->g = lfi::yuv_geometry(W, H);
+    d->in_place = yuv_surfaces_in_place(dst);
+    d->packs = may_pack && !d->in_place && yuv_surfaces_packable(dst, d->g);
+    if(!d->in_place)
+        LFI_HIP(ctx, ctx->yuv[0].reserve(d->g.dev_frame_bytes * n));
+    if(d->packs)
+        LFI_HIP(ctx, ctx->yuv[1].reserve(d->g.frame_bytes));
+    d->frames = d->in_place ? caller_surfaces(dst) : staged_surfaces(d->g, dst.format, ctx->yuv[0].get());
+    return LFI_OK;
+}
+
+// behind the kernel on the context's stream: the copies of the staged frames (none in place), then the wait for them
+static int finish_yuv_delivery(lfi_ctx *ctx, const lfi_yuv_surfaces &dst, int n, const YuvDelivery &d)
+{
+    if(!d.in_place)
+        LFI_HIP(ctx, enqueue_surface_copies(ctx->stream, dst, 0, n, d.g, ctx->yuv[0].get(), false, d.packs ? ctx->yuv[1].get() : nullptr));
     LFI_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return LFI_OK;
+}
+
+// Behind both download calls.  The arguments have passed check_yuv_download
+static int download_yuv_surfaces(lfi_ctx *ctx, const char *who, int v0, int n, int matrix, int range, const lfi_yuv_surfaces &dst, size_t extent)
+{
+    YuvDelivery d;
+    if(int rc = open_yuv_delivery(ctx, who, dst, extent, ctx->width, ctx->height, n, false, &d))
+        return rc;
+    bool planar;
+    const lfi::ViewsSrc src = rendered_views(ctx, v0, &planar);
+    LFI_HIP(ctx, enqueue_yuv_convert(ctx->stream, src, planar, n, matrix, range, dst.format, d.frames));
+    return finish_yuv_delivery(ctx, dst, n, d);
 }
 
 int lfi_download_views_yuv420(lfi_ctx *ctx, int v0, int n, int matrix, int range, uint8_t *out, size_t frame_stride_bytes)
@@ -1734,8 +1761,10 @@ static int render_stream(lfi_ctx *ctx, int method, int all_focus, const uint16_t
         {
             if(b >= 2)
                 LFI_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_d2h[slot], 0)); // block b − 2 has left this buffer of frames
-            LFI_HIP(ctx, enqueue_views_convert(ctx, ctx->stream, vbuf[slot], 0, nv, yuv->matrix, yuv->range, LFI_YUV_I420,
-                                               staged_surfaces(yuv_g, LFI_YUV_I420, ctx->yuv[slot].get())));
+            bool planar;
+            const lfi::ViewsSrc src = rendered_views(ctx, 0, &planar); // vbuf[slot]: YUV blocks all render into the one set of views
+            LFI_HIP(ctx, enqueue_yuv_convert(ctx->stream, src, planar, nv, yuv->matrix, yuv->range, LFI_YUV_I420,
+                                             staged_surfaces(yuv_g, LFI_YUV_I420, ctx->yuv[slot].get())));
         }
         LFI_HIP(ctx, hipEventRecord(ctx->ev_rendered[slot], ctx->stream));
         LFI_HIP(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->ev_rendered[slot], 0));
@@ -1758,49 +1787,6 @@ static int render_stream(lfi_ctx *ctx, int method, int all_focus, const uint16_t
     return status;
 }
 
-int lfi_compare_view(lfi_ctx *ctx, int v, const uint8_t *reference_rgba, size_t pitch_bytes, lfi_quality *out)
-{
-    if(!ctx || !out)
-        return LFI_EINVAL;
-    if(!ctx->views || !ctx->have_params)
-        return fail(ctx, LFI_EINVAL, "nothing rendered yet");
-    if(v < 0 || v >= ctx->views_n || !reference_rgba || pitch_bytes < (size_t)ctx->width * 4)
-        return fail(ctx, LFI_EINVAL, "bad view index, pointer or pitch");
-    if(ctx->windowed)
-        return fail(ctx, LFI_EINVAL, "lfi_compare_view needs the whole view (no row window)");
-    if(int rc = bind(ctx))
-        return rc;
-    LFI_HIP(ctx, ctx->quality_ref.fit(plane_bytes(ctx)));
-    LFI_HIP(ctx, ctx->quality_sums.reserve(sizeof(lfi::QualitySums)));
-    lfi::QualitySums *const d_sums = ctx->quality_sums.as<lfi::QualitySums>();
-    LFI_HIP(ctx, hipMemcpy2DAsync(ctx->quality_ref.get(), (size_t)ctx->width * 4, reference_rgba, pitch_bytes, (size_t)ctx->width * 4, ctx->height,
-                                  hipMemcpyHostToDevice, ctx->stream));
-    LFI_HIP(ctx, hipMemsetAsync(d_sums, 0, sizeof(lfi::QualitySums), ctx->stream));
-    const uint8_t *view = nullptr;
-    if(int rc = rgba_plane_of_view(ctx, v, &view))
-        return rc;
-    const int bw = (ctx->width + 3) / 4, bh = (ctx->height + 3) / 4; // 4×4 blocks
-    hipLaunchKernelGGL(lfi::quality_reduce, dim3((bw + 15) / 16, (bh + 15) / 16), dim3(256), 0, ctx->stream, reinterpret_cast<const uint32_t *>(view),
-                       ctx->quality_ref.as<const uint32_t>(), ctx->width, ctx->height, d_sums);
-    LFI_HIP(ctx, hipGetLastError());
-    lfi::QualitySums sums{};
-    LFI_HIP(ctx, hipMemcpyAsync(&sums, d_sums, sizeof(sums), hipMemcpyDeviceToHost, ctx->stream));
-    LFI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const double px = (double)ctx->width * ctx->height;
-    double mse_all = 0, ssim_all = 0;
-    for(int c = 0; c < 3; c++)
-    {
-        out->mse[c] = (double)sums.sq_err[c] / px;
-        out->psnr[c] = out->mse[c] > 0 ? 10.0 * std::log10(255.0 * 255.0 / out->mse[c]) : INFINITY;
-        out->ssim[c] = sums.windows ? sums.ssim[c] / (double)sums.windows : 1.0;
-        mse_all += out->mse[c] / 3.0;
-        ssim_all += out->ssim[c] / 3.0;
-    }
-    out->psnr_all = mse_all > 0 ? 10.0 * std::log10(255.0 * 255.0 / mse_all) : INFINITY;
-    out->ssim_all = ssim_all;
-    return LFI_OK;
-}
-
 int lfi_keep_views(lfi_ctx *ctx, int v0, int n)
 {
     if(!ctx)
@@ -1812,8 +1798,8 @@ int lfi_keep_views(lfi_ctx *ctx, int v0, int n)
         drop_kept(ctx); // hipFree waits for a copy into the set that is still in flight
         return LFI_OK;
     }
-    if(!ctx->views || !ctx->have_params)
-        return fail(ctx, LFI_EINVAL, "nothing rendered yet");
+    if(int rc = check_rendered(ctx))
+        return rc;
     if(v0 < 0 || n < 0 || (long)v0 + n > ctx->views_n)
         return fail(ctx, LFI_EINVAL, "lfi_keep_views: views [v0, v0 + n) must lie inside [0, views)");
     if(int rc = bind(ctx))
@@ -1840,7 +1826,7 @@ double psnr_of(double mse)
     return mse > 0 ? 10.0 * std::log10(255.0 * 255.0 / mse) : INFINITY;
 }
 
-// psnr, psnr_all and ssim_all from mse[] and ssim[]: lfi_compare_view's arithmetic
+// psnr, psnr_all and ssim_all from mse[] and ssim[]
 void finish_quality(lfi_quality *q)
 {
     double mse_all = 0, ssim_all = 0;
@@ -1854,31 +1840,12 @@ void finish_quality(lfi_quality *q)
     q->ssim_all = ssim_all;
 }
 
-} // namespace
-
-int lfi_compare_views(lfi_ctx *ctx, int v0, int n, const uint8_t *references_rgba, size_t pitch_bytes, size_t image_stride_bytes, lfi_view_quality *out,
+// Behind lfi_compare_views and lfi_compare_view, whose checks the arguments have passed: views [v0, v0 + n) against host references, or
+// (references_rgba NULL) against the kept views
+int run_compare_views(lfi_ctx *ctx, int v0, int n, const uint8_t *references_rgba, size_t pitch_bytes, size_t image_stride_bytes, lfi_view_quality *out,
                       lfi_quality *out_all)
 {
-    if(!ctx)
-        return LFI_EINVAL;
-    if(!out)
-        return fail(ctx, LFI_EINVAL, "lfi_compare_views: out is NULL");
-    if(!ctx->views || !ctx->have_params)
-        return fail(ctx, LFI_EINVAL, "nothing rendered yet");
-    if(ctx->windowed)
-        return fail(ctx, LFI_EINVAL, "lfi_compare_views needs whole views (no row window)");
-    if(v0 < 0 || n < 1 || (long)v0 + n > ctx->views_n)
-        return fail(ctx, LFI_EINVAL, "lfi_compare_views: views [v0, v0 + n), n >= 1, must lie inside [0, views)");
     const int W = ctx->width, H = ctx->height;
-    if(references_rgba)
-    {
-        if(pitch_bytes < (size_t)W * 4 || image_stride_bytes / (size_t)H < pitch_bytes)
-            return fail(ctx, LFI_EINVAL, "lfi_compare_views: bad pitch (>= width * 4) or image stride (>= pitch * height)");
-    }
-    else if(!ctx->kept)
-        return fail(ctx, LFI_EINVAL, "lfi_compare_views: no reference images and no kept views (lfi_keep_views)");
-    else if(v0 < ctx->kept_v0 || v0 + n > ctx->kept_v0 + ctx->kept_n)
-        return fail(ctx, LFI_EINVAL, "lfi_compare_views: the kept views do not cover [v0, v0 + n)");
     if(int rc = bind(ctx))
         return rc;
     if(int rc = join_uploads(ctx))
@@ -1889,10 +1856,11 @@ int lfi_compare_views(lfi_ctx *ctx, int v0, int n, const uint8_t *references_rgb
     LFI_HIP(ctx, ctx->cmp_ws.reserve(records_bytes + sizeof(lfi::QualityPartial) * (size_t)n * tiles));
     lfi::QualityViewSums *const d_records = ctx->cmp_ws.as<lfi::QualityViewSums>();
     lfi::QualityPartial *const d_partials = reinterpret_cast<lfi::QualityPartial *>(ctx->cmp_ws.get() + records_bytes);
-    const bool planar = ctx->out_layout == LFI_LAYOUT_PLANAR_RGB;
-    const size_t stride = out_plane_bytes(ctx);
-    const uint32_t view_row = planar ? (uint32_t)view_pitch(ctx) : (uint32_t)W * 4u;
-    const lfi::QualityImages a{ctx->views.get() + (size_t)v0 * stride, stride, view_row};
+    bool planar;
+    const lfi::ViewsSrc views = rendered_views(ctx, v0, &planar);
+    const size_t stride = views.view_stride;
+    const uint32_t view_row = planar ? views.pitch : (uint32_t)W * 4u;
+    const lfi::QualityImages a{views.base, stride, view_row};
     if(!references_rgba)
     {
         // kept views, in the views' layout: one launch for all n
@@ -1974,6 +1942,51 @@ int lfi_compare_views(lfi_ctx *ctx, int v0, int n, const uint8_t *references_rgb
         }
         finish_quality(out_all);
     }
+    return LFI_OK;
+}
+
+} // namespace
+
+int lfi_compare_views(lfi_ctx *ctx, int v0, int n, const uint8_t *references_rgba, size_t pitch_bytes, size_t image_stride_bytes, lfi_view_quality *out,
+                      lfi_quality *out_all)
+{
+    if(!ctx)
+        return LFI_EINVAL;
+    if(!out)
+        return fail(ctx, LFI_EINVAL, "lfi_compare_views: out is NULL");
+    if(int rc = check_rendered(ctx))
+        return rc;
+    if(ctx->windowed)
+        return fail(ctx, LFI_EINVAL, "lfi_compare_views needs whole views (no row window)");
+    if(v0 < 0 || n < 1 || (long)v0 + n > ctx->views_n)
+        return fail(ctx, LFI_EINVAL, "lfi_compare_views: views [v0, v0 + n), n >= 1, must lie inside [0, views)");
+    if(references_rgba)
+    {
+        if(pitch_bytes < (size_t)ctx->width * 4 || image_stride_bytes / (size_t)ctx->height < pitch_bytes)
+            return fail(ctx, LFI_EINVAL, "lfi_compare_views: bad pitch (>= width * 4) or image stride (>= pitch * height)");
+    }
+    else if(!ctx->kept)
+        return fail(ctx, LFI_EINVAL, "lfi_compare_views: no reference images and no kept views (lfi_keep_views)");
+    else if(v0 < ctx->kept_v0 || v0 + n > ctx->kept_v0 + ctx->kept_n)
+        return fail(ctx, LFI_EINVAL, "lfi_compare_views: the kept views do not cover [v0, v0 + n)");
+    return run_compare_views(ctx, v0, n, references_rgba, pitch_bytes, image_stride_bytes, out, out_all);
+}
+
+// lfi_compare_views' code for one view and one host reference whose rows follow each other: the same sums, in the same order
+int lfi_compare_view(lfi_ctx *ctx, int v, const uint8_t *reference_rgba, size_t pitch_bytes, lfi_quality *out)
+{
+    if(!ctx || !out)
+        return LFI_EINVAL;
+    if(int rc = check_rendered(ctx))
+        return rc;
+    if(v < 0 || v >= ctx->views_n || !reference_rgba || pitch_bytes < (size_t)ctx->width * 4)
+        return fail(ctx, LFI_EINVAL, "bad view index, pointer or pitch");
+    if(ctx->windowed)
+        return fail(ctx, LFI_EINVAL, "lfi_compare_view needs the whole view (no row window)");
+    lfi_view_quality one;
+    if(int rc = run_compare_views(ctx, v, 1, reference_rgba, pitch_bytes, pitch_bytes * ctx->height, &one, nullptr))
+        return rc;
+    *out = one.q;
     return LFI_OK;
 }
 
@@ -2069,20 +2082,39 @@ int lfi_benchmark(lfi_ctx *ctx, int method, int all_focus, int v0, int v1, int w
     return LFI_OK;
 }
 
+// ONE quilt_assemble launch on the context's stream: views v0 … v0 + n − 1 of src → tiles first … first + n − 1 of `quilt`
+static hipError_t enqueue_quilt_assemble(lfi_ctx *ctx, const lfi::ViewsSrc &src, bool planar, uint32_t *quilt, int n, int v0, int first, int tiles_x)
+{
+    const dim3 grid(((src.W + 3) / 4 + 255) / 256, src.H, n), block(256);
+    if(planar)
+        hipLaunchKernelGGL(lfi::quilt_assemble<true>, grid, block, 0, ctx->stream, src, quilt, v0, first, tiles_x);
+    else
+        hipLaunchKernelGGL(lfi::quilt_assemble<false>, grid, block, 0, ctx->stream, src, quilt, v0, first, tiles_x);
+    return hipGetLastError();
+}
+
 int lfi_download_view(lfi_ctx *ctx, int v, uint8_t *rgba, size_t pitch_bytes)
 {
     if(!ctx)
         return LFI_EINVAL;
-    if(!ctx->views || !ctx->have_params)
-        return fail(ctx, LFI_EINVAL, "nothing rendered yet");
+    if(int rc = check_rendered(ctx))
+        return rc;
     if(v < 0 || v >= ctx->views_n || !rgba || pitch_bytes < (size_t)ctx->width * 4)
         return fail(ctx, LFI_EINVAL, "bad view index, pointer or pitch");
     if(int rc = bind(ctx))
         return rc;
+    // the view as an RGBA plane of out_rows rows: the view itself, or (planar layout) its expansion into the context's one-plane staging
+    // buffer — the one tile of a quilt one tile wide
+    bool planar;
+    const lfi::ViewsSrc view = rendered_views(ctx, v, &planar);
+    const uint8_t *src = view.base;
+    if(planar)
+    {
+        LFI_HIP(ctx, ctx->dl_plane.fit(rgba_out_plane_bytes(ctx)));
+        LFI_HIP(ctx, enqueue_quilt_assemble(ctx, view, true, ctx->dl_plane.as<uint32_t>(), 1, 0, 0, 1));
+        src = ctx->dl_plane.get();
+    }
     // rgba addresses row 0 of the whole view; the rows this context rendered are written at their place
-    const uint8_t *src = nullptr;
-    if(int rc = rgba_plane_of_view(ctx, v, &src))
-        return rc;
     LFI_HIP(ctx, hipMemcpy2DAsync(rgba + (size_t)ctx->out_y0 * pitch_bytes, pitch_bytes, src,
                                   (size_t)ctx->width * 4, (size_t)ctx->width * 4, ctx->out_rows, hipMemcpyDeviceToHost, ctx->stream));
     LFI_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -2128,8 +2160,8 @@ static int check_scaled_tiles(lfi_ctx *ctx, int tile_w, int tile_h)
 // what lfi_download_quilt_tiles_scaled and lfi_download_quilt_yuv refuse alike before they look at the destination
 static int check_scaled_quilt(lfi_ctx *ctx, int tiles_x, int tiles_y, int first_tile, int n, int v0, int tile_w, int tile_h)
 {
-    if(!ctx->views || !ctx->have_params)
-        return fail(ctx, LFI_EINVAL, "nothing rendered yet");
+    if(int rc = check_rendered(ctx))
+        return rc;
     if(ctx->windowed)
         return fail(ctx, LFI_EINVAL, "a scaled quilt needs whole views: a tile's rows average source rows the row window's band does not hold");
     if(int rc = check_quilt_tiles(ctx, tiles_x, tiles_y, first_tile, n, v0))
@@ -2179,8 +2211,8 @@ int lfi_download_quilt_tiles(lfi_ctx *ctx, int tiles_x, int tiles_y, int first_t
 {
     if(!ctx)
         return LFI_EINVAL;
-    if(!ctx->views || !ctx->have_params)
-        return fail(ctx, LFI_EINVAL, "nothing rendered yet");
+    if(int rc = check_rendered(ctx))
+        return rc;
     if(int rc = check_quilt_tiles(ctx, tiles_x, tiles_y, first_tile, n, v0))
         return rc;
     if(!rgba || pitch_bytes < (size_t)tiles_x * ctx->width * 4)
@@ -2194,14 +2226,9 @@ int lfi_download_quilt_tiles(lfi_ctx *ctx, int tiles_x, int tiles_y, int first_t
     const size_t qrow = (size_t)tiles_x * W * 4;
     const size_t need = qrow * rows * (size_t)(tr1 - tr0 + 1);
     LFI_HIP(ctx, ctx->quilt.reserve(need));
-    const dim3 grid(((W + 3) / 4 + 255) / 256, rows, n), block(256);
-    if(ctx->out_layout == LFI_LAYOUT_PLANAR_RGB)
-        hipLaunchKernelGGL(lfi::quilt_assemble<true>, grid, block, 0, ctx->stream, ctx->views.get(), ctx->quilt.as<uint32_t>(), W, rows, view_pitch(ctx),
-                           out_plane_bytes(ctx), v0, first_tile, tiles_x);
-    else
-        hipLaunchKernelGGL(lfi::quilt_assemble<false>, grid, block, 0, ctx->stream, ctx->views.get(), ctx->quilt.as<uint32_t>(), W, rows, 0,
-                           out_plane_bytes(ctx), v0, first_tile, tiles_x);
-    LFI_HIP(ctx, hipGetLastError());
+    bool planar;
+    const lfi::ViewsSrc views = rendered_views(ctx, 0, &planar);
+    LFI_HIP(ctx, enqueue_quilt_assemble(ctx, views, planar, ctx->quilt.as<uint32_t>(), n, v0, first_tile, tiles_x));
     LFI_HIP(ctx, enqueue_quilt_copies(ctx, tiles_x, first_tile, n, (size_t)W * 4, rows, ctx->height, ctx->out_y0, rgba, pitch_bytes));
     LFI_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return LFI_OK;
@@ -2220,7 +2247,6 @@ int lfi_download_quilt_tiles_scaled(lfi_ctx *ctx, int tiles_x, int tiles_y, int 
         return LFI_EINVAL;
     if(int rc = check_scaled_quilt(ctx, tiles_x, tiles_y, first_tile, n, v0, tile_w, tile_h))
         return rc;
-    const int W = ctx->width, H = ctx->height;
     if(!rgba || pitch_bytes < (size_t)tiles_x * tile_w * 4)
         return fail(ctx, LFI_EINVAL, "bad quilt pointer or pitch");
     if(int rc = bind(ctx))
@@ -2230,12 +2256,10 @@ int lfi_download_quilt_tiles_scaled(lfi_ctx *ctx, int tiles_x, int tiles_y, int 
     const int tr0 = first_tile / tiles_x, tr1 = (first_tile + n - 1) / tiles_x;
     const size_t qrow = (size_t)tiles_x * tile_w * 4;
     LFI_HIP(ctx, ctx->quilt.reserve(qrow * tile_h * (size_t)(tr1 - tr0 + 1)));
-    const bool planar = ctx->out_layout == LFI_LAYOUT_PLANAR_RGB;
+    bool planar;
     lfi::QuiltScaleArgs q{};
-    q.views = ctx->views.get();
+    q.src = rendered_views(ctx, 0, &planar);
     q.quilt = ctx->quilt.as<uint32_t>();
-    q.view_stride = out_plane_bytes(ctx);
-    q.W = W, q.H = H, q.pitch = planar ? view_pitch(ctx) : 0;
     q.tile_w = tile_w, q.tile_h = tile_h;
     q.v0 = v0, q.first = first_tile, q.tiles_x = tiles_x;
     LFI_HIP(ctx, lfi::launch_quilt_scale(ctx->stream, planar, q, n));
@@ -2269,65 +2293,41 @@ int lfi_download_quilt_yuv(lfi_ctx *ctx, int tiles_x, int tiles_y, int v0, int t
     size_t extent = 0;
     if(const char *fault = yuv_surfaces_fault(dst, QW, QH, 1, &extent))
         return fail(ctx, LFI_EINVAL, std::string(who) + ": " + fault);
-    if(int rc = bind(ctx))
+    // the caller's frame in place, or the staged frame and the copies of its own bytes; a host frame may pack
+    YuvDelivery d;
+    if(int rc = open_yuv_delivery(ctx, who, *dst, extent, QW, QH, 1, true, &d))
         return rc;
-    if(dst->memory == LFI_MEM_DEVICE)
-        if(int rc = check_device_surfaces(ctx, who, *dst, extent, 1))
-            return rc;
-    // the destination, as download_yuv_surfaces routes it: the caller's frame in place, or the staged frame and the copies of its own bytes
-    const lfi::YuvGeometry g = lfi::yuv_geometry(QW, QH);
-    const bool in_place = yuv_surfaces_in_place(*dst);
-    // a host frame with tight rows that is not the staged frame (QW no multiple of 8, or QH odd) leaves through a packed device copy
-    // (yuv[1]): one contiguous copy per plane instead of one per row
-    const bool packs = !in_place && yuv_surfaces_packable(*dst, g);
-    if(!in_place)
-        LFI_HIP(ctx, ctx->yuv[0].reserve(g.dev_frame_bytes));
-    if(packs)
-        LFI_HIP(ctx, ctx->yuv[1].reserve(g.frame_bytes));
-    const lfi::YuvSurfaces frame = in_place ? caller_surfaces(*dst) : staged_surfaces(g, dst->format, ctx->yuv[0].get());
-    const bool planar = ctx->out_layout == LFI_LAYOUT_PLANAR_RGB;
+    bool planar;
     lfi::QuiltScaleArgs q{};
-    q.views = ctx->views.get();
-    q.view_stride = out_plane_bytes(ctx);
-    q.W = ctx->width, q.H = ctx->height, q.pitch = planar ? view_pitch(ctx) : 0;
+    q.src = rendered_views(ctx, 0, &planar);
     q.tile_w = tile_w, q.tile_h = tile_h;
     q.v0 = v0, q.first = 0, q.tiles_x = tiles_x;
     if(tile_w % 2 == 0 && tile_h % 2 == 0)
     {
         // every 2 x 2 block lies inside one tile: ONE launch, no RGBA quilt
         lfi::QuiltYuvArgs a{};
-        a.q = q, a.s = frame, a.k = lfi::YUV_COEFFS[matrix * 2 + range];
+        a.q = q, a.s = d.frames, a.k = lfi::YUV_COEFFS[matrix * 2 + range];
         LFI_HIP(ctx, lfi::launch_quilt_yuv_scale(ctx->stream, planar, dst->format, a, n));
     }
     else
     {
         // blocks straddle tiles: the RGBA quilt of lfi_download_quilt_scaled in the quilt buffer, converted as ONE RGBA view of QW x QH
-        LFI_HIP(ctx, ctx->quilt.reserve((size_t)QW * 4 * QH));
+        const size_t quilt_bytes = (size_t)QW * 4 * QH;
+        LFI_HIP(ctx, ctx->quilt.reserve(quilt_bytes));
         q.quilt = ctx->quilt.as<uint32_t>();
         LFI_HIP(ctx, lfi::launch_quilt_scale(ctx->stream, planar, q, n));
-        lfi::YuvsOutArgs a{};
-        a.src = ctx->quilt.get();
-        a.s = frame;
-        a.view_stride = (size_t)QW * 4 * QH;
-        a.W = QW, a.H = QH, a.pitch = 0;
-        a.cw = g.cw, a.ch = g.ch;
-        a.blocks_x = g.y_pitch / lfi::YUV_BLOCK_W;
-        a.rows16 = QW % 4 == 0; // the quilt buffer starts on a 16-byte boundary (hipMalloc), a row is QW·4 bytes
-        a.k = lfi::YUV_COEFFS[matrix * 2 + range];
-        LFI_HIP(ctx, lfi::launch_yuvs_convert(ctx->stream, false, dst->format, a, 1));
+        const lfi::ViewsSrc quilt{ctx->quilt.get(), quilt_bytes, (uint32_t)QW, (uint32_t)QH, 0u};
+        LFI_HIP(ctx, enqueue_yuv_convert(ctx->stream, quilt, false, 1, matrix, range, dst->format, d.frames));
     }
-    if(!in_place)
-        LFI_HIP(ctx, enqueue_surface_copies(ctx->stream, *dst, 0, 1, g, ctx->yuv[0].get(), false, packs ? ctx->yuv[1].get() : nullptr));
-    LFI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return LFI_OK;
+    return finish_yuv_delivery(ctx, *dst, 1, d);
 }
 
 int lfi_download_native(lfi_ctx *ctx, const lfi_lenticular *lens, int v0, int out_w, int out_h, int tile_w, int tile_h, uint8_t *rgba, size_t pitch_bytes)
 {
     if(!ctx)
         return LFI_EINVAL;
-    if(!ctx->views || !ctx->have_params)
-        return fail(ctx, LFI_EINVAL, "nothing rendered yet");
+    if(int rc = check_rendered(ctx))
+        return rc;
     if(ctx->windowed)
         return fail(ctx, LFI_EINVAL, "a native image needs whole views: its subpixels read rows the row window's band does not hold");
     if(!lens)
@@ -2346,36 +2346,27 @@ int lfi_download_native(lfi_ctx *ctx, const lfi_lenticular *lens, int v0, int ou
     if(int rc = bind(ctx))
         return rc;
     const int n = lens->views;
-    const bool planar = ctx->out_layout == LFI_LAYOUT_PLANAR_RGB, scaled = tile_w != W || tile_h != H;
+    const bool scaled = tile_w != W || tile_h != H;
     LFI_HIP(ctx, ctx->native.reserve((size_t)out_w * out_h * 4));
+    bool planar;
     lfi::NativeArgs a{};
+    a.src = rendered_views(ctx, v0, &planar); // the views in place, in the layout they were rendered in
     a.out = ctx->native.as<uint32_t>();
-    a.W = tile_w, a.H = tile_h;
     a.out_w = out_w, a.out_h = out_h;
     a.x_step = lens->x_step, a.y_step = lens->y_step, a.phase0 = lens->phase0, a.n = n;
     a.invert = (lens->flags & LFI_LENT_INVERT) ? 1u : 0u;
     if(scaled)
     {
-        // stage 1: the n scaled tiles as a quilt ONE tile wide in the quilt buffer — RGBA planes [view][tile_h][tile_w]; none of it is copied
+        // stage 1: the n scaled tiles as a quilt ONE tile wide in the quilt buffer — RGBA views of tile_w × tile_h; none of it is copied
         const size_t tile_bytes = (size_t)tile_w * tile_h * 4;
         LFI_HIP(ctx, ctx->quilt.reserve(tile_bytes * n));
         lfi::QuiltScaleArgs q{};
-        q.views = ctx->views.get();
+        q.src = rendered_views(ctx, 0, &planar);
         q.quilt = ctx->quilt.as<uint32_t>();
-        q.view_stride = out_plane_bytes(ctx);
-        q.W = W, q.H = H, q.pitch = planar ? view_pitch(ctx) : 0;
         q.tile_w = tile_w, q.tile_h = tile_h;
         q.v0 = v0, q.first = 0, q.tiles_x = 1;
         LFI_HIP(ctx, lfi::launch_quilt_scale(ctx->stream, planar, q, n));
-        a.src = ctx->quilt.get();
-        a.view_stride = tile_bytes;
-    }
-    else
-    {
-        // the views in place, in the layout they were rendered in
-        a.src = ctx->views.get() + (size_t)v0 * out_plane_bytes(ctx);
-        a.view_stride = out_plane_bytes(ctx);
-        a.pitch = planar ? view_pitch(ctx) : 0;
+        a.src = lfi::ViewsSrc{ctx->quilt.get(), tile_bytes, (uint32_t)tile_w, (uint32_t)tile_h, 0u};
     }
     LFI_HIP(ctx, lfi::launch_native_interlace(ctx->stream, planar && !scaled, a));
     LFI_HIP(ctx, hipMemcpy2DAsync(rgba, pitch_bytes, ctx->native.get(), (size_t)out_w * 4, (size_t)out_w * 4, out_h, hipMemcpyDeviceToHost, ctx->stream));

@@ -22,6 +22,8 @@
 
 #include <cstdint>
 
+#include "views_src.hpp"
+
 namespace lfi {
 
 constexpr int NATIVE_THREADS = 256;
@@ -29,10 +31,8 @@ constexpr uint32_t NATIVE_MAX = 65535u; // the largest output / tile size along 
 
 struct NativeArgs
 {
-    const uint8_t *src;  // RGBA planes [view][H][W], or (PLANAR) byte planes [view][R,G,B][H][pitch]; view 0 = the first view interlaced
-    uint32_t *out;       // the native image, out_h × out_w dwords
-    size_t view_stride;  // bytes from view to view
-    uint32_t W, H, pitch; // the size of T_v; pitch: bytes per row of a byte plane (PLANAR)
+    ViewsSrc src;  // the T_v, view 0 = the first view interlaced: the views in place, or their scaled tiles as a quilt one tile wide
+    uint32_t *out; // the native image, out_h × out_w dwords
     uint32_t out_w, out_h;
     uint32_t x_step, y_step, phase0, n;
     uint32_t invert; // 0 / 1
@@ -51,12 +51,12 @@ __global__ void __launch_bounds__(NATIVE_THREADS) native_interlace(const NativeA
     const uint32_t x = blockIdx.x * NATIVE_THREADS + threadIdx.x, y = blockIdx.y; // y < out_h: the grid has out_h rows
     if(x >= a.out_w)
         return;
-    const uint32_t sy = native_nearest(y, a.H, a.out_h);      // wave-uniform
+    const uint32_t sy = native_nearest(y, a.src.H, a.out_h);  // wave-uniform
     const uint32_t row_phase = a.phase0 + y * a.y_step;        // wave-uniform
-    const uint32_t sx = native_nearest(x, a.W, a.out_w);
+    const uint32_t sx = native_nearest(x, a.src.W, a.out_w);
     // byte (sy, sx, channel 0) inside a view
-    const size_t at = PLANAR ? (size_t)sy * a.pitch + sx : ((size_t)sy * a.W + sx) * 4u;
-    const size_t channel = PLANAR ? (size_t)a.H * a.pitch : 1u; // bytes from channel to channel
+    const size_t at = PLANAR ? (size_t)sy * a.src.pitch + sx : ((size_t)sy * a.src.W + sx) * 4u;
+    const size_t channel = PLANAR ? (size_t)a.src.H * a.src.pitch : 1u; // bytes from channel to channel
     uint32_t px = 0xff000000u;
 #pragma unroll
     for(uint32_t c = 0; c < 3; c++)
@@ -65,7 +65,7 @@ __global__ void __launch_bounds__(NATIVE_THREADS) native_interlace(const NativeA
         uint32_t k = __umulhi(phase, a.n); // < n
         if(a.invert)
             k = a.n - 1u - k;
-        px |= (uint32_t)a.src[(size_t)k * a.view_stride + at + c * channel] << (8u * c);
+        px |= (uint32_t)a.src.base[(size_t)k * a.src.view_stride + at + c * channel] << (8u * c);
     }
     a.out[(size_t)y * a.out_w + x] = px;
 }

@@ -1,6 +1,6 @@
-// quality_batch.hpp — PSNR / SSIM of MANY views against as many references in one launch (lfi_compare_views): what the reference's
+// quality_batch.hpp — PSNR / SSIM of MANY views against as many references in one launch (lfi_compare_views; lfi_compare_view is n = 1): what the reference's
 // scripts/compareDirs.sh gets from a loop of imageQualityMetrics.sh over two directories (reference scripts/compareDirs.sh,
-// scripts/imageQualityMetrics.sh:1-12).  The definitions are quality.hpp's (PSNR from the per-channel MSE over all pixels, SSIM = the mean
+// scripts/imageQualityMetrics.sh:1-12).  The definitions are include/lfi.h's, at lfi_compare_view (PSNR from the per-channel MSE over all pixels, SSIM = the mean
 // over all 8×8 windows at stride 4 of the standard index with the window's biased moments); on top of them, exactly: the squared error per
 // channel, the number of differing colour bytes and the largest difference.  Alpha is ignored.
 //
@@ -11,7 +11,7 @@
 //     instruction); the squared error is Σa² + Σb² − 2Σab, exact in integers.  The moments go to LDS as one 16-byte record per channel
 //     (Σa and Σb share a dword); an 8×8 window is the sum of four blocks: the lane's own, its right neighbour and the two above them,
 //     so a lane evaluates the window that ENDS in its block row — the row above is the previous step's last row, kept in a ring of three
-//     groups of rows (one barrier per step).  The SSIM expression is quality.hpp's, in fp64.  A tile owns 31 columns of windows and 63 rows:
+//     groups of rows (one barrier per step).  The SSIM expression is the definition's, in fp64.  A tile owns 31 columns of windows and 63 rows:
 //     neighbouring tiles overlap by one column and one row of blocks (the halo), whose pixels are counted by one of them only.
 //     Lane sums → wave (shuffles) → workgroup (LDS, waves in order) → ONE QualityPartial per workgroup, stored: no atomics.
 //   quality_views  one workgroup per view adds that view's partials: a lane its tiles in ascending order, then the same tree.  Every sum
@@ -31,6 +31,8 @@ constexpr int QB_STEPS = 8;                     // steps of QB_LY block rows dow
 constexpr int QB_TILE_BX = QB_LX - 1;           // block columns a tile owns (the 32nd is the right halo)
 constexpr int QB_TILE_BY = QB_LY * QB_STEPS - 1; // block rows a tile owns (its first row is the halo of the tile above)
 
+// Not a ViewsSrc (views_src.hpp): the references are host images or kept views with a stride of their own, and `pitch` is the bytes of a
+// row in BOTH layouts (RGBA references come with the caller's pitch), where a ViewsSrc's is 0 for RGBA.
 struct QualityImages
 {
     const uint8_t *base; // image 0: RGBA rows of `pitch` bytes, or (planar) byte planes [R,G,B][H][pitch]
@@ -116,7 +118,7 @@ __device__ inline void qb_load(const uint8_t *img, const uint32_t pitch, const i
 
 __device__ inline double qb_ssim(const qb_u32x4 m)
 {
-    // m = {Σa | Σb << 16, Σa², Σb², Σab} over the window's 64 pixels; the expression of quality.hpp:68-75
+    // m = {Σa | Σb << 16, Σa², Σb², Σab} over the window's 64 pixels; the definition's expression (include/lfi.h, lfi_compare_view)
     const uint32_t s1 = m.x & 0xffffu, s2 = m.x >> 16, s11 = m.y, s22 = m.z, s12 = m.w;
     const double C1 = 0.01 * 255.0 * 0.01 * 255.0, C2 = 0.03 * 255.0 * 0.03 * 255.0;
     const double mu1 = s1 / 64.0, mu2 = s2 / 64.0;

@@ -27,6 +27,7 @@
 #include <cstdint>
 
 #include "../area_span.h"
+#include "views_src.hpp"
 
 namespace lfi {
 
@@ -37,10 +38,8 @@ constexpr int QUILT_SCALE_ROWS = 4;                        // output rows per wo
 
 struct QuiltScaleArgs
 {
-    const uint8_t *views; // RGBA planes [view][H][W], or (PLANAR) byte planes [view][R,G,B][H][pitch]
-    uint32_t *quilt;      // RGBA image of the rows of tiles these tiles touch, tiles_x·tile_w pixels wide
-    size_t view_stride;   // bytes from view to view
-    uint32_t W, H, pitch; // pitch: bytes per row of a byte plane (PLANAR), a multiple of 4
+    ViewsSrc src;    // the context's views: tile i is made of view v0 + i
+    uint32_t *quilt; // RGBA image of the rows of tiles these tiles touch, tiles_x·tile_w pixels wide
     uint32_t tile_w, tile_h;
     int32_t v0, first, tiles_x;
     uint32_t cols_per_wg; // ≤ QUILT_SCALE_COLS
@@ -68,7 +67,7 @@ struct QuiltScaleChunk
 // workgroup leaves
 __device__ __forceinline__ bool quilt_scale_chunk(const QuiltScaleArgs &q, QuiltScaleChunk &c)
 {
-    const uint32_t W = q.W, tw = q.tile_w, t = threadIdx.x;
+    const uint32_t W = q.src.W, tw = q.tile_w, t = threadIdx.x;
     c.oc0 = blockIdx.x * q.cols_per_wg, c.oc1 = min(c.oc0 + q.cols_per_wg, tw);
     if(c.oc0 >= tw)
         return false;
@@ -89,7 +88,7 @@ template <bool PLANAR>
 __device__ __forceinline__ void quilt_scale_row(const QuiltScaleArgs &q, const uint8_t *view, uint32_t (*col)[QUILT_SCALE_PIECE], const QuiltScaleChunk &c,
                                                 const uint32_t oy, uint32_t (&out)[2])
 {
-    const uint32_t W = q.W, H = q.H, tw = q.tile_w, th = q.tile_h;
+    const uint32_t W = q.src.W, H = q.src.H, tw = q.tile_w, th = q.tile_h;
     const uint32_t t = threadIdx.x;
     const uint32_t s0 = c.s0, s1 = c.s1;
     const uint64_t area = (uint64_t)W * H;
@@ -108,7 +107,7 @@ __device__ __forceinline__ void quilt_scale_row(const QuiltScaleArgs &q, const u
                     uint32_t p[3];
 #pragma unroll
                     for(int ch = 0; ch < 3; ch++) // x is a multiple of 4 below W: the dword lies inside the row's pitch
-                        p[ch] = *reinterpret_cast<const uint32_t *>(view + ((size_t)ch * H + y) * q.pitch + x);
+                        p[ch] = *reinterpret_cast<const uint32_t *>(view + ((size_t)ch * H + y) * q.src.pitch + x);
 #pragma unroll
                     for(int ch = 0; ch < 3; ch++)
 #pragma unroll
@@ -181,7 +180,7 @@ __global__ void __launch_bounds__(QUILT_SCALE_THREADS) quilt_scale(const QuiltSc
     const uint32_t t = threadIdx.x;
     const int i = blockIdx.z;
     const int tile = q.first + i, trow = tile / q.tiles_x - q.first / q.tiles_x, tcol = tile % q.tiles_x;
-    const uint8_t *view = q.views + (size_t)(q.v0 + i) * q.view_stride;
+    const uint8_t *view = q.src.base + (size_t)(q.v0 + i) * q.src.view_stride;
     QuiltScaleChunk c;
     if(!quilt_scale_chunk(q, c))
         return;
@@ -206,7 +205,7 @@ inline dim3 quilt_scale_plan(QuiltScaleArgs &q, const int n, const bool even_col
     // the most output columns whose source columns fit one piece: m columns overlap at most m·W / tile_w + 2 source columns, and the
     // chunk starts up to 3 columns before its first one; then as many chunks as that takes, of equal width.  A ratio so high that no
     // column (even_cols: no two) fits takes chunks of one (two) and several pieces
-    const uint64_t fit = (uint64_t)(QUILT_SCALE_PIECE - 5) * q.tile_w / q.W;
+    const uint64_t fit = (uint64_t)(QUILT_SCALE_PIECE - 5) * q.tile_w / q.src.W;
     uint32_t most = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(fit, 1), QUILT_SCALE_COLS);
     if(even_cols)
         most = std::max(most & ~1u, 2u);
@@ -215,7 +214,7 @@ inline dim3 quilt_scale_plan(QuiltScaleArgs &q, const int n, const bool even_col
     if(even_cols)
         q.cols_per_wg = (q.cols_per_wg + 1u) & ~1u; // ≤ most, which is even
     q.rows_per_wg = QUILT_SCALE_ROWS;
-    q.rcp_area = 1.0f / (float)((uint64_t)q.W * q.H);
+    q.rcp_area = 1.0f / (float)((uint64_t)q.src.W * q.src.H);
     return dim3(chunks, (q.tile_h + q.rows_per_wg - 1) / q.rows_per_wg, n);
 }
 

@@ -61,7 +61,7 @@ __global__ void __launch_bounds__(QUILT_SCALE_THREADS) quilt_yuv_scale(const Qui
     const uint32_t t = threadIdx.x;
     const int i = blockIdx.z;
     const uint32_t trow = (uint32_t)(i / q.tiles_x), tcol = (uint32_t)(i % q.tiles_x);
-    const uint8_t *view = q.views + (size_t)(q.v0 + i) * q.view_stride;
+    const uint8_t *view = q.src.base + (size_t)(q.v0 + i) * q.src.view_stride;
     QuiltScaleChunk c;
     if(!quilt_scale_chunk(q, c))
         return;

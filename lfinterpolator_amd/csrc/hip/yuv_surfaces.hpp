@@ -46,6 +46,7 @@
 
 #include <cstdint>
 
+#include "views_src.hpp"
 #include "yuv420.hpp"
 #include "yuv420_upload.hpp"
 
@@ -64,10 +65,8 @@ struct YuvsInArgs
 
 struct YuvsOutArgs
 {
-    const uint8_t *src;   // view 0 of the call: RGBA planes [view][H][W], or (PLANAR) byte planes [view][R,G,B][H][pitch]
-    YuvSurfaces s;        // written
-    size_t view_stride;   // bytes from view to view
-    uint32_t W, H, pitch; // pitch: bytes per row of a byte plane (PLANAR)
+    ViewsSrc src;  // frame i is made of view i
+    YuvSurfaces s; // written
     uint32_t cw, ch;
     uint32_t blocks_x; // (W + 7) / 8
     uint32_t rows16;   // RGBA: every pixel row starts on a 16-byte boundary (W a multiple of 4)
@@ -178,11 +177,11 @@ __global__ void __launch_bounds__(YUV_LANES_X *YUV_BLOCK_ROWS) yuvs_convert(cons
     if(bx >= a.blocks_x || by >= a.ch)
         return;
     const uint32_t x0 = bx * YUV_BLOCK_W;
-    const bool two_rows = by * YUV_BLOCK_H + 1u < a.H;
+    const bool two_rows = by * YUV_BLOCK_H + 1u < a.src.H;
     const uint32_t ya = by * YUV_BLOCK_H, yb = two_rows ? ya + 1u : ya; // ya < H: by < ch
-    const bool whole = x0 + YUV_BLOCK_W <= a.W;                         // all 8 columns inside the view
+    const bool whole = x0 + YUV_BLOCK_W <= a.src.W;                       // all 8 columns inside the view
     uint32_t r[2][8], g[2][8], b[2][8];
-    yuv_load_block<PLANAR>(a.src + (size_t)blockIdx.z * a.view_stride, a.W, a.H, a.pitch, a.rows16, x0, ya, yb, whole, r, g, b);
+    yuv_load_block<PLANAR>(a.src.base + (size_t)blockIdx.z * a.src.view_stride, a.src.W, a.src.H, a.src.pitch, a.rows16, x0, ya, yb, whole, r, g, b);
     uint8_t *frame = a.s.base + (size_t)blockIdx.z * a.s.frame_stride;
     // Y: the row's own bytes only, and no row beyond H
 #pragma unroll
@@ -201,7 +200,7 @@ __global__ void __launch_bounds__(YUV_LANES_X *YUV_BLOCK_ROWS) yuvs_convert(cons
         {
 #pragma unroll
             for(int i = 0; i < 7; i++) // a ragged block holds at most 7 columns
-                if(x0 + i < a.W)
+                if(x0 + i < a.src.W)
                     row[i] = (uint8_t)y[i];
         }
     }

@@ -1,4 +1,4 @@
-"""The definitions of lfi_compare_views (include/lfi.h; csrc/hip/quality.hpp's header comment) restated in vectorised numpy — the reference the
+"""The definitions of lfi_compare_views (include/lfi.h, at lfi_compare_view) restated in vectorised numpy — the reference the
 GPU tests compare against.  tests/test_host_compare_views.py holds it against the window-by-window loop the project already asserts
 lfi_compare_view with (tests/test_gpu_plumbing.py::_ssim_psnr_numpy).
 

@@ -2,7 +2,8 @@
 
 Every record is held against the numpy restatement of the definitions (tests/quality_ref.py, anchored by tests/test_host_compare_views.py) applied to
 the views' own downloads: the integer fields and the MSE exactly (the MSE is one division of exact integers), SSIM to rtol 1e-9 and PSNR to 1e-9 dB —
-the tolerances tests/test_gpu_plumbing.py::test_compare_view_psnr_ssim uses for the same expressions."""
+the tolerances tests/test_gpu_plumbing.py::test_compare_view_psnr_ssim uses for the same expressions.  lfi_compare_view runs the same code for one view:
+its result is held against the batch call's byte for byte."""
 import ctypes
 import math
 
@@ -11,6 +12,7 @@ import pytest
 
 import lfinterpolator_amd as L
 import poison
+from lfinterpolator_amd.abi import Quality
 import quality_ref as ref
 
 pytestmark = pytest.mark.gpu
@@ -128,13 +130,14 @@ def test_compare_views_equals_the_restatement(w, h, layout, gpu):
     # the same numbers whether the STD view is the kept one or comes from the host
     assert _bytes(ctx.compare_views(v0=1, n=1)[0], 1) == host_first[:ctypes.sizeof(L.ViewQuality)]
 
-    # each view's q against lfi_compare_view of the same view and reference
+    # each view's q against lfi_compare_view of the same view and reference: the same code, the same bytes
     for k in range(3):
         one = ctx.compare_view(1 + k, np.ascontiguousarray(refs[k]))
-        for c in range(3):
-            assert recs[k].q.mse[c] == one.mse[c]
-            assert _same(recs[k].q.ssim[c], one.ssim[c], 1e-9, True) and _same(recs[k].q.psnr[c], one.psnr[c], 1e-9, False)
-        assert _same(recs[k].q.ssim_all, one.ssim_all, 1e-9, True) and _same(recs[k].q.psnr_all, one.psnr_all, 1e-9, False)
+        assert bytes(one) == bytes(recs[k].q), (w, h, layout, k)
+        if layout == "planar":
+            # … and again with the scratch buffers poisoned between two calls
+            ctx.poison(L.LFI_POISON_SCRATCH, poison._byte(None))
+            assert bytes(ctx.compare_view(1 + k, np.ascontiguousarray(refs[k]))) == bytes(one), (w, h, k, "poisoned")
 
     # the call wrote no view and no kept view
     assert (ctx.download_views() == ten).all()
@@ -270,6 +273,53 @@ def test_refusals_leave_a_usable_context(gpu):
     poison.render(win, "STD")
     with pytest.raises(gpu.LfiError, match="row window"):
         win.compare_views(refs)
+    assert (win.download_view(0)[band[0]:band[1]] == std[0][band[0]:band[1]]).all()      # … and the context goes on
+    win.close()
+
+
+def test_compare_view_refusals(gpu):
+    """lfi_compare_view's own checks, in its own words: nothing rendered, a bad index, a NULL reference, a short pitch, a row window — each
+    leaves out untouched and the context usable"""
+    w, h = 64, 32
+    ctx = _ctx(gpu, w, h, "planar")
+    lib, handle = ctx._lib, ctx._h
+    ref_img = np.zeros((h, w, 4), np.uint8)
+    ptr = ref_img.ctypes.data_as(ctypes.c_void_p)
+    out = Quality()
+    before = bytes(out)
+    assert lib.lfi_compare_view(handle, 0, ptr, w * 4, None) == -1
+    # nothing rendered yet: no grid; a grid but no parameters
+    fresh = gpu.Context(0)
+    assert lib.lfi_compare_view(fresh._h, 0, ptr, w * 4, ctypes.byref(out)) == -1 and lib.lfi_last_error(fresh._h) == b"nothing rendered yet"
+    fresh.set_grid(COLS, ROWS, w, h)
+    with pytest.raises(gpu.LfiError, match=": nothing rendered yet$"):
+        fresh.compare_view(0, ref_img)
+    fresh.close()
+
+    poison.render(ctx, "STD")
+    std = ctx.download_views()
+    for what, args in (("v < 0", (-1, ptr, w * 4)), ("v == views", (V, ptr, w * 4)), ("NULL reference", (0, None, w * 4)),
+                       ("short pitch", (0, ptr, w * 4 - 1))):
+        assert lib.lfi_compare_view(handle, *args, ctypes.byref(out)) == -1, what
+        assert lib.lfi_last_error(handle) == b"bad view index, pointer or pitch", what
+        assert bytes(out) == before, what
+        assert ctx.compare_view(2, std[2]).psnr_all == math.inf, what
+    ctx.close()
+    # a row window
+    hp = _params(gpu, w, h)
+    win = gpu.Context(0)
+    win.set_grid(COLS, ROWS, w, h)
+    band = (8, 24)
+    in_rows = gpu.input_rows(band, hp.focused_offsets, h)
+    win.set_row_window(band[0], band[1], in_rows[0], in_rows[1])
+    win.upload_grid(_light_field(w, h))
+    win.set_params(hp)
+    win.set_output_layout("planar")
+    poison.render(win, "STD")
+    with pytest.raises(gpu.LfiError, match=r": lfi_compare_view needs the whole view \(no row window\)$"):
+        win.compare_view(0, ref_img)
+    assert lib.lfi_compare_view(win._h, V, ptr, w * 4, ctypes.byref(out)) == -1      # the index is looked at before the window
+    assert lib.lfi_last_error(win._h) == b"bad view index, pointer or pitch" and bytes(out) == before
     assert (win.download_view(0)[band[0]:band[1]] == std[0][band[0]:band[1]]).all()      # … and the context goes on
     win.close()
 

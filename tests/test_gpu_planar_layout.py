@@ -257,3 +257,42 @@ def test_planar_layout_quilt_and_attached_views(gpu):
     poison.render(ctx, "TEN_WM")
     assert ctx.last_kernel_name().startswith("blend_planar") and (ctx.download_views() == views).all()
     ctx.close()
+
+
+@pytest.mark.parametrize("band", [None, (2, 5)], ids=["whole", "rows-2-5"])
+def test_download_view_of_planar_views(band, gpu):
+    """lfi_download_view of a planar view (quilt_assemble for one tile of a quilt one tile wide into the staging plane): W = 13 is no multiple
+    of the four pixels a lane moves, H = 7; view v is tile v of the 2 x 2 quilt and the view of the RGBA layout from the same render, without
+    a row window and with rows [2, 5)"""
+    cols = rows = 3
+    W, H, V = 13, 7, 4
+    hp = gpu.build_params(cols, rows, W, H, "0,0,1,1", 0.2, 0.0, 3.0, 1.5, V)
+    y0, y1 = band or (0, H)
+    lf = np.random.default_rng(SEED).integers(0, 256, (cols * rows, H, W, 4), dtype=np.uint8)
+
+    def rendered(layout):
+        ctx = gpu.Context(0)
+        ctx.set_grid(cols, rows, W, H)
+        if band:
+            in_rows = gpu.input_rows(band, hp.focused_offsets, H)
+            ctx.set_row_window(y0, y1, in_rows[0], in_rows[1])
+        ctx.upload_grid(lf)
+        ctx.set_params(hp)
+        ctx.set_output_layout(layout)
+        poison.render(ctx, "STD")
+        return ctx
+
+    rgba = rendered("rgba")
+    want = rgba.download_views()
+    rgba.close()
+    assert (want[:, y0:y1, :, 3] == 255).all() and len({want[v, y0:y1].tobytes() for v in range(V)}) == V     # four different views
+    ctx = rendered("planar")
+    quilt = ctx.download_quilt(2, 2)
+    for v in (3, 0, 2, 1):                                        # the staging plane is reused from call to call
+        ctx.poison(gpu.LFI_POISON_SCRATCH, poison._byte(None))
+        got = ctx.download_view(v)
+        tile = quilt[(v // 2) * H:(v // 2 + 1) * H, (v % 2) * W:(v % 2 + 1) * W]
+        assert (got[y0:y1] == tile[y0:y1]).all(), (band, v, "quilt tile")
+        assert (got[y0:y1] == want[v, y0:y1]).all(), (band, v, "RGBA layout")
+        assert (got[:y0] == 0).all() and (got[y1:] == 0).all(), (band, v, "rows outside the window were written")
+    ctx.close()

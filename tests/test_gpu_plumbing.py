@@ -333,7 +333,7 @@ def test_render_stream_matches_block_by_block_renders(gpu, oracle_c):
 
 
 def _ssim_psnr_numpy(a, b):
-    """The definitions of csrc/hip/quality.hpp restated: per channel MSE over all pixels; SSIM = mean over 8×8 windows at stride 4."""
+    """The definitions of lfi_compare_view (include/lfi.h) restated: per channel MSE over all pixels; SSIM = mean over 8×8 windows at stride 4."""
     a = a[..., :3].astype(np.float64)
     b = b[..., :3].astype(np.float64)
     mse = ((a - b) ** 2).mean(axis=(0, 1))

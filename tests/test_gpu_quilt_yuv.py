@@ -122,6 +122,26 @@ def test_wide_views(shape, layout, gpu):
     ctx.close()
 
 
+@pytest.mark.parametrize("layout", LAYOUTS)
+def test_odd_tiles_of_small_views(layout, gpu):
+    """four views of 13 x 7 as tiles of 5 x 3 in a 2 x 2 quilt: odd tile sizes take the RGBA quilt (quilt_scale, then yuvs_convert of the quilt as
+    ONE view of 10 x 6).  QW = 10 is no multiple of 8: a tight host I420 frame is not the staged frame and leaves through the packed copy; a
+    16-aligned device NV12 surface is written in place"""
+    tx, ty, tw, th = 2, 2, 5, 3
+    ctx = _rendered(gpu, layout, views=4, w=13, h=7)
+    views = ctx.download_views()
+    i420, nv12 = FORMATS
+    cases = [(i420, sref.HOST, sref.tight(i420, tx * tw, ty * th)), (nv12, sref.DEVICE, sref.pitched(nv12, tx * tw, ty * th, align=16, gap=16, tail=16))]
+    for k, (fmt, memory, lay) in enumerate(cases):
+        assert memory == sref.HOST or (lay.y_pitch | lay.c_offset | lay.c_pitch | lay.frame_stride) % 16 == 0
+        for conv in (yuv_ref.FORMATS[k], yuv_ref.FORMATS[k + 2]):
+            want = ref.frame(views, tx, ty, tw, th, *conv)
+            for byte in poison.POISON:
+                got = _frame(ctx, tx, ty, tw, th, conv, lay, memory, byte)
+                assert (got == want).all(), (layout, FORMAT_NAMES[fmt], MEMORY_NAMES[memory], conv, byte, int((got != want).sum()))
+    ctx.close()
+
+
 def _attached(gpu, layout, content):
     """a context whose views are a torch buffer that holds `content` ([n][h][w][4], alpha 255) in the layout's device form"""
     import torch
