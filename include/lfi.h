@@ -599,6 +599,20 @@ int lfi_yuv_surfaces_packed(int format, int memory, void *base, int width, int h
  * inputs, row window, range of images, matrix, range and chroma; src refused by lfi_yuv_surfaces_check; LFI_MEM_DEVICE with a pointer that
  * is not device memory of the context's device or whose allocation ends before the last frame does. */
 int lfi_upload_images_yuv(lfi_ctx *ctx, int g0, int n, int matrix, int range, int chroma, const lfi_yuv_surfaces *src);
+/* lfi_upload_images_yuv for a context that holds only the derived planar copy of its inputs (lfi_release_inputs): the n frames of src are
+ * expanded STRAIGHT into the three byte planes of images [g0, g0 + n) of that copy, padding included, in one pass and one kernel — 1.5 bytes
+ * read and 3 written per pixel, no RGBA image in between, no rebuild afterwards.  Every byte is what the copy would hold had the frames gone
+ * through lfi_upload_images_yuv before lfi_release_inputs: byte j of a row of plane (g, c) is channel c of pixel
+ * clamp(j - padx - phase[g], 0, W - 1) of the image the definition above gives (lfi_debug_derived_layout).  The copy keeps its layout, its
+ * phases and its validity; renders enqueued before the call read the old frames, renders enqueued after it the new ones, without a host wait.
+ * Source handling (host: staged in chunks of at most 16 frames or 256 MiB; device: in place in ONE launch where everything is a multiple of
+ * 16, else staged device-to-device), ordering (the copy stream, lfi_upload_wait / lfi_sync) and the arguments are lfi_upload_images_yuv's;
+ * tight I420 host frames go in through lfi_yuv_surfaces_packed.  The kernel works on spans of LFI_YUV_DERIVED_SPAN bytes of a plane row.
+ * LFI_EINVAL, the context usable, the copy and the staging buffer untouched: a context that still holds its RGBA planes (the call writes
+ * the planar copy alone: lfi_release_inputs first); no grid; a row window; and whatever lfi_upload_images_yuv refuses of the range of
+ * images, matrix, range, chroma and src. */
+#define LFI_YUV_DERIVED_SPAN 384
+int lfi_upload_images_yuv_derived(lfi_ctx *ctx, int g0, int n, int matrix, int range, int chroma, const lfi_yuv_surfaces *src);
 /* lfi_download_views_yuv420 into surfaces: views [v0, v0 + n) become frames [0, n) of dst.  Synchronous, ordered like
  * lfi_download_views_yuv420; both view layouts are read in place; writes no view and no map.  ONLY the planes' own bytes of dst are
  * written: pitch padding and gaps between planes and frames keep their values.
@@ -751,6 +765,19 @@ int lfi_debug_mfma_f16_chain(lfi_ctx *ctx, int shape, int k, const uint16_t *a_3
 enum { LFI_POISON_VIEWS = 1, LFI_POISON_SCRATCH = 2, LFI_POISON_MAPS = 4, LFI_POISON_FOCUS_WORKSPACE = 8, LFI_POISON_DERIVED = 16,
        LFI_POISON_VIEW_MAPS = 32 };
 int lfi_debug_poison(lfi_ctx *ctx, uint32_t what, uint8_t byte);
+/* Test hooks: the derived planar copy of the inputs, byte for byte.  The copy is [N][3][rows][pitch_bytes] bytes: per image three byte planes
+ * (R, G, B) of the rows the context holds; byte j of a plane row of image g holds pixel clamp(j - padx - phase[g], 0, W - 1), so every row is
+ * padded on both sides with its edge pixels; reach is the largest horizontal offset the padding serves.  Valid whenever the copy is current
+ * — after lfi_release_inputs, or once a render that reads the copy (or lfi_prepare) has brought it up to date with the RGBA planes — else
+ * LFI_EINVAL.  lfi_debug_derived_layout writes the layout and, where phases_n is not NULL, the N per-image phases; no device work.
+ * lfi_debug_download_derived copies the planes of images [g0, g0 + n) to out ([n][3][rows][pitch_bytes]); synchronous, in stream order
+ * behind renders and uploads. */
+typedef struct lfi_derived_layout {
+    size_t pitch_bytes;
+    int rows, padx, reach, n;
+} lfi_derived_layout;
+int lfi_debug_derived_layout(lfi_ctx *ctx, lfi_derived_layout *out, int32_t *phases_n);
+int lfi_debug_download_derived(lfi_ctx *ctx, int g0, int n, uint8_t *out);
 
 #ifdef __cplusplus
 }

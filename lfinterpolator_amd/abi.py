@@ -56,6 +56,7 @@ ABI_SYMBOLS = [
     "lfi_download_views_yuv420", "lfi_render_stream_yuv420", "lfi_upload_images_yuv420",
     "lfi_yuv_surfaces_check", "lfi_yuv_surfaces_packed", "lfi_upload_images_yuv", "lfi_download_views_yuv",
     "lfi_download_quilt_yuv",
+    "lfi_upload_images_yuv_derived", "lfi_debug_derived_layout", "lfi_debug_download_derived",
 ]
 
 
@@ -142,6 +143,22 @@ def yuv_surfaces_packed(fmt, memory, base: int | None, width: int, height: int, 
     return s
 
 
+LFI_YUV_DERIVED_SPAN = 384   # bytes (= pixels) of a plane row that a workgroup of lfi_upload_images_yuv_derived's kernel owns (include/lfi.h)
+
+
+class DerivedLayout(C.Structure):
+    """lfi_derived_layout: the derived planar copy of the inputs is [n][3][rows][pitch_bytes] bytes; byte j of a plane row of image g holds
+    pixel clamp(j - padx - phase[g], 0, W - 1).  `phases` ([n] int32) is filled in by Context.derived_layout."""
+    _fields_ = [("pitch_bytes", C.c_size_t), ("rows", C.c_int32), ("padx", C.c_int32), ("reach", C.c_int32), ("n", C.c_int32)]
+    phases = None
+
+    def __eq__(self, other):
+        return (isinstance(other, DerivedLayout) and all(getattr(self, f) == getattr(other, f) for f, _ in self._fields_)
+                and np.array_equal(self.phases, other.phases))
+
+    __hash__ = None
+
+
 class MemoryInfo(C.Structure):
     _fields_ = [("grid_bytes", C.c_size_t), ("derived_bytes", C.c_size_t), ("views_bytes", C.c_size_t), ("maps_bytes", C.c_size_t),
                 ("workspace_bytes", C.c_size_t), ("derived_build_ms", C.c_float)]
@@ -217,6 +234,9 @@ def load_hip_library() -> C.CDLL:
         "lfi_upload_images_yuv": (i, [vp, i, i, i, i, i, C.POINTER(YuvSurfaces)]),
         "lfi_download_views_yuv": (i, [vp, i, i, i, i, C.POINTER(YuvSurfaces)]),
         "lfi_download_quilt_yuv": (i, [vp, i, i, i, i, i, i, i, C.POINTER(YuvSurfaces)]),
+        "lfi_upload_images_yuv_derived": (i, [vp, i, i, i, i, i, C.POINTER(YuvSurfaces)]),
+        "lfi_debug_derived_layout": (i, [vp, C.POINTER(DerivedLayout), vp]),
+        "lfi_debug_download_derived": (i, [vp, i, i, vp]),
         "lfi_alloc_pinned": (i, [sz, C.POINTER(vp)]),
         "lfi_free_pinned": (i, [vp]),
         "lfi_grid_modified": (i, [vp]),
@@ -359,6 +379,29 @@ class Context:
         memory alive and unchanged until upload_wait / sync."""
         self._check(self._lib.lfi_upload_images_yuv(self._h, g0, n, YUV_MATRICES.get(matrix, matrix), YUV_RANGES.get(range, range),
                                                     YUV_CHROMAS.get(chroma, chroma), C.byref(surfaces) if surfaces is not None else None))
+
+    def upload_images_yuv_derived(self, surfaces: YuvSurfaces, n: int, g0: int = 0, matrix="709", range="limited", chroma="bilinear") -> None:
+        """upload_images_yuv for a context whose inputs were released (lfi_upload_images_yuv_derived): the n frames go straight into the
+        planes of images [g0, g0 + n) of the derived planar copy, padding included, in one pass.  Ordered like upload_images_yuv."""
+        self._check(self._lib.lfi_upload_images_yuv_derived(self._h, g0, n, YUV_MATRICES.get(matrix, matrix), YUV_RANGES.get(range, range),
+                                                            YUV_CHROMAS.get(chroma, chroma), C.byref(surfaces) if surfaces is not None else None))
+
+    def derived_layout(self) -> DerivedLayout:
+        """the layout and per-image phases of the derived planar copy (lfi_debug_derived_layout); LfiError where the copy is not current"""
+        lay = DerivedLayout()
+        phases = np.zeros(256, np.int32)   # LFI_MAX_IMAGES
+        self._check(self._lib.lfi_debug_derived_layout(self._h, C.byref(lay), _ptr(phases)))
+        lay.phases = phases[:lay.n].copy()
+        return lay
+
+    def download_derived(self, g0: int = 0, n: int | None = None) -> np.ndarray:
+        """the planes of images [g0, g0 + n) (default: all from g0) of the derived planar copy, [n][3][rows][pitch] uint8
+        (lfi_debug_download_derived); in stream order behind renders and uploads"""
+        lay = self.derived_layout()
+        n = lay.n - g0 if n is None else n
+        out = np.empty((max(n, 0), 3, lay.rows, lay.pitch_bytes), np.uint8)
+        self._check(self._lib.lfi_debug_download_derived(self._h, g0, n, _ptr(out)))
+        return out
 
     def yuv_surfaces_packed(self, fmt, memory="host", base: int | None = None, keep=None) -> YuvSurfaces:
         """the tight layout of this context's frames (lfi_yuv_surfaces_packed): frame stride yuv420_frame_bytes() for both formats"""

@@ -14,6 +14,7 @@
 #include "yuv420.hpp"
 #include "yuv420_upload.hpp"
 #include "yuv_surfaces.hpp"
+#include "yuv_derived.hpp"
 #include "lfi_rccl.hpp"
 
 extern "C" {
@@ -441,13 +442,22 @@ int host_i420_surfaces(lfi_ctx *ctx, const char *who, const uint8_t *frames, siz
     return LFI_OK;
 }
 
-// what lfi_upload_images_yuv420 and lfi_upload_images_yuv refuse alike, before they look at the frames
-int check_yuv_upload(lfi_ctx *ctx, const char *who, int g0, int n, int matrix, int range, int chroma)
+// what lfi_upload_images_yuv420, lfi_upload_images_yuv and lfi_upload_images_yuv_derived refuse alike, before they look at the frames.
+// derived: the call writes the planar copy of a context whose RGBA inputs were released, and is refused where the others are served
+int check_yuv_upload(lfi_ctx *ctx, const char *who, int g0, int n, int matrix, int range, int chroma, bool derived = false)
 {
     const char *fault = nullptr;
-    if(ctx->inputs_released)
+    if(derived && !ctx->inputs_released)
+    {
+        if(!ctx->grid)
+            return fail(ctx, LFI_EINVAL, "lfi_set_grid has not been called");
+        fault = ": the context still holds its RGBA inputs: the call writes the planar copy alone, which is valid only after lfi_release_inputs";
+    }
+    else if(derived && (!ctx->planar || (int)ctx->planar_phase.size() != ctx->n))
+        fault = ": the context holds no planar copy of the inputs";
+    else if(!derived && ctx->inputs_released)
         fault = ": the RGBA inputs were released (lfi_release_inputs): lfi_set_grid and upload the images again";
-    else if(!ctx->grid)
+    else if(!derived && !ctx->grid)
         return fail(ctx, LFI_EINVAL, "lfi_set_grid has not been called");
     else if(ctx->windowed)
         fault = ": YUV 4:2:0 frames need whole images: a 2x2 chroma block may straddle the row window's band";
@@ -460,9 +470,14 @@ int check_yuv_upload(lfi_ctx *ctx, const char *who, int g0, int n, int matrix, i
     return fault ? fail(ctx, LFI_EINVAL, std::string(who) + fault) : LFI_OK;
 }
 
-// Behind both upload calls.  The arguments have passed check_yuv_upload; src is what host_i420_surfaces made, or has passed
-// yuv_surfaces_fault, which gave extent
-int upload_yuv_surfaces(lfi_ctx *ctx, const char *who, int g0, int n, int matrix, int range, int chroma, const lfi_yuv_surfaces &src, size_t extent)
+// yuv_derived.hpp's launch, defined at the end of this file
+hipError_t launch_yuvs_derived_expand(hipStream_t stream, int format, bool nearest, const lfi::YuvsDerivedArgs &a, int n);
+
+// Behind the three upload calls.  The arguments have passed check_yuv_upload; src is what host_i420_surfaces made, or has passed
+// yuv_surfaces_fault, which gave extent.  derived: the frames go into the planar copy (yuvs_derived_expand), which stays the valid copy it
+// was — no version moves; else into the RGBA planes (yuvs_expand), and the copy is rebuilt from them by the next render that reads it
+int upload_yuv_surfaces(lfi_ctx *ctx, const char *who, int g0, int n, int matrix, int range, int chroma, const lfi_yuv_surfaces &src, size_t extent,
+                        bool derived = false)
 {
     if(int rc = bind(ctx))
         return rc;
@@ -498,15 +513,28 @@ int upload_yuv_surfaces(lfi_ctx *ctx, const char *who, int g0, int n, int matrix
             LFI_HIP(ctx, enqueue_surface_copies(st, src, k0, nk, g, ctx->yuv_in.get(), true));
         lfi::YuvsInArgs a{};
         a.s = in_place ? caller_surfaces(src) : staged_surfaces(g, src.format, ctx->yuv_in.get());
-        a.dst = ctx->grid.get() + in_plane_bytes(ctx) * (size_t)(g0 + k0);
-        a.image_stride = in_plane_bytes(ctx);
         a.W = g.W, a.H = g.H, a.cw = g.cw, a.ch = g.ch;
         a.blocks_x = g.y_pitch / lfi::YUV_BLOCK_W;
-        a.rows16 = g.W % 4 == 0; // the grid starts on a 16-byte boundary (hipMalloc; lfi_attach_grid checks), an image is W·H·4 bytes
         a.k = lfi::YUV_IN_COEFFS[matrix * 2 + range];
+        if(derived)
+        {
+            // whole images (check_yuv_upload refuses a row window): the copy's planes hold in_rows = H rows of planar_pitch bytes
+            lfi::YuvsDerivedArgs d{};
+            d.in = a;
+            d.planar = ctx->planar.get();
+            d.phase = ctx->d_planar_phase.as<int32_t>();
+            d.pitch = (uint32_t)ctx->planar_pitch, d.padx = (uint32_t)ctx->planar_padx;
+            d.g0 = (uint32_t)(g0 + k0);
+            LFI_HIP(ctx, launch_yuvs_derived_expand(st, src.format, chroma == LFI_CHROMA_NEAREST, d, nk));
+            continue;
+        }
+        a.dst = ctx->grid.get() + in_plane_bytes(ctx) * (size_t)(g0 + k0);
+        a.image_stride = in_plane_bytes(ctx);
+        a.rows16 = g.W % 4 == 0; // the grid starts on a 16-byte boundary (hipMalloc; lfi_attach_grid checks), an image is W·H·4 bytes
         LFI_HIP(ctx, lfi::launch_yuvs_expand(st, src.format, chroma == LFI_CHROMA_NEAREST, a, nk));
     }
-    touch_images(ctx, g0, g0 + n);
+    if(!derived)
+        touch_images(ctx, g0, g0 + n);
     return LFI_OK;
 }
 
@@ -555,6 +583,59 @@ int lfi_upload_images_yuv(lfi_ctx *ctx, int g0, int n, int matrix, int range, in
     if(const char *fault = yuv_surfaces_fault(src, ctx->width, ctx->height, n, &extent))
         return fail(ctx, LFI_EINVAL, std::string("lfi_upload_images_yuv: ") + fault);
     return upload_yuv_surfaces(ctx, "lfi_upload_images_yuv", g0, n, matrix, range, chroma, *src, extent);
+}
+
+int lfi_upload_images_yuv_derived(lfi_ctx *ctx, int g0, int n, int matrix, int range, int chroma, const lfi_yuv_surfaces *src)
+{
+    if(!ctx)
+        return LFI_EINVAL;
+    if(int rc = check_yuv_upload(ctx, "lfi_upload_images_yuv_derived", g0, n, matrix, range, chroma, true))
+        return rc;
+    size_t extent = 0;
+    if(const char *fault = yuv_surfaces_fault(src, ctx->width, ctx->height, n, &extent))
+        return fail(ctx, LFI_EINVAL, std::string("lfi_upload_images_yuv_derived: ") + fault);
+    return upload_yuv_surfaces(ctx, "lfi_upload_images_yuv_derived", g0, n, matrix, range, chroma, *src, extent, true);
+}
+
+namespace {
+
+// the planar copy holds the current inputs: the only copy of them (lfi_release_inputs), or one that a render has brought up to date
+bool derived_copy_current(const lfi_ctx *ctx)
+{
+    return ctx->planar && (int)ctx->planar_phase.size() == ctx->n && ctx->n > 0 && (ctx->inputs_released || ctx->planar_version == ctx->grid_version);
+}
+
+} // namespace
+
+int lfi_debug_derived_layout(lfi_ctx *ctx, lfi_derived_layout *out, int32_t *phases_n)
+{
+    if(!ctx || !out)
+        return LFI_EINVAL;
+    if(!derived_copy_current(ctx))
+        return fail(ctx, LFI_EINVAL, "lfi_debug_derived_layout: the context holds no current planar copy of the inputs");
+    out->pitch_bytes = (size_t)ctx->planar_pitch;
+    out->rows = ctx->in_rows, out->padx = ctx->planar_padx, out->reach = ctx->planar_reach, out->n = ctx->n;
+    if(phases_n)
+        std::copy(ctx->planar_phase.begin(), ctx->planar_phase.end(), phases_n);
+    return LFI_OK;
+}
+
+int lfi_debug_download_derived(lfi_ctx *ctx, int g0, int n, uint8_t *out)
+{
+    if(!ctx)
+        return LFI_EINVAL;
+    if(!derived_copy_current(ctx))
+        return fail(ctx, LFI_EINVAL, "lfi_debug_download_derived: the context holds no current planar copy of the inputs");
+    if(n < 1 || g0 < 0 || (long)g0 + n > ctx->n || !out)
+        return fail(ctx, LFI_EINVAL, "lfi_debug_download_derived: needs n >= 1 images starting at g0 inside [0, N) and a destination");
+    if(int rc = bind(ctx))
+        return rc;
+    if(int rc = join_uploads(ctx)) // in stream order behind the uploads, as a render is
+        return rc;
+    const size_t image = (size_t)3 * ctx->in_rows * ctx->planar_pitch;
+    LFI_HIP(ctx, hipMemcpyAsync(out, ctx->planar.get() + image * (size_t)g0, image * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    LFI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return LFI_OK;
 }
 
 int lfi_attach_grid(lfi_ctx *ctx, void *device_ptr, size_t bytes)
@@ -2670,5 +2751,31 @@ int lfi_debug_p3_trace(unsigned long long *out, int n_words)
     return hipMemcpyFromSymbol(out, HIP_SYMBOL(lfi::lfi_p3_trace_buf), sizeof(unsigned long long) * std::min(n_words, 1024 * 8)) == hipSuccess ? 0 : 1;
 }
 #endif
+namespace {
+
+// Enqueues the ONE yuvs_derived_expand launch for n frames.  The caller has checked sizes, alignment and memory as for launch_yuvs_expand;
+// a.planar holds images [g0, g0 + n) with a.in.H rows of a.pitch bytes per plane, a.pitch a multiple of 16.
+// (Defined here, at the end of the file, so that the four kernels are first used behind every other kernel: yuv_derived.hpp says why.)
+hipError_t launch_yuvs_derived_expand(hipStream_t stream, const int format, const bool nearest, const lfi::YuvsDerivedArgs &a, const int n)
+{
+    const dim3 grid((a.pitch + lfi::YUVD_SPAN - 1) / lfi::YUVD_SPAN, (a.in.ch + lfi::YUVD_ROWS - 1) / lfi::YUVD_ROWS, n), block(lfi::YUVD_THREADS);
+    if(format == lfi::YUVS_NV12)
+    {
+        if(nearest)
+            hipLaunchKernelGGL((lfi::yuvs_derived_expand<lfi::YUVS_NV12, true>), grid, block, 0, stream, a);
+        else
+            hipLaunchKernelGGL((lfi::yuvs_derived_expand<lfi::YUVS_NV12, false>), grid, block, 0, stream, a);
+    }
+    else
+    {
+        if(nearest)
+            hipLaunchKernelGGL((lfi::yuvs_derived_expand<lfi::YUVS_I420, true>), grid, block, 0, stream, a);
+        else
+            hipLaunchKernelGGL((lfi::yuvs_derived_expand<lfi::YUVS_I420, false>), grid, block, 0, stream, a);
+    }
+    return hipGetLastError();
+}
+
+} // namespace
 } // extern "C"
 

@@ -32,6 +32,8 @@
 //     clamped as the definition says (a clamped neighbour is a byte of the lane's own columns or row), and the Y bytes beyond the image
 //     belong to pixels that are not stored.  Ragged blocks, an odd last row, and images whose rows are not 16-byte aligned (W no multiple
 //     of 4) store pixel by pixel as dwords; no lane stores outside the image.
+//     Loads, clamps and arithmetic are yuvs_block_pixels, which ends with the block's 16 RGBA dwords; the kernel adds the stores.
+//     yuvs_derived_expand (yuv_derived.hpp) calls the same function and puts the pixels into the planar copy of the inputs instead.
 //   yuvs_convert<PLANAR, FORMAT>   views → frames.  From RGBA views a lane reads two rows of 32 bytes as 16-byte loads (a wave: two runs of
 //     2 KiB), from PLANAR views 3 planes × 2 rows × 8 bytes at the plane pitch (six runs of 512 bytes; no RGBA copy of planar views).
 //     Ragged blocks, and RGBA views whose rows are not 16-byte aligned, read pixel by pixel with clamped coordinates; planar rows are as
@@ -80,16 +82,14 @@ __device__ __forceinline__ uint32_t yuvs_component(const uint32_t lo, const uint
     return (a & 0xffu) | ((a >> 8) & 0xff00u) | ((b & 0xffu) << 16) | ((b << 8) & 0xff000000u);
 }
 
+// The RGBA dwords px of block (bx, by) of a frame: bx < a.blocks_x, by < a.ch.  Everything yuvs_expand reads and computes — its loads, its
+// clamps, its arithmetic —, for the kernels that differ only in where the pixels go: yuvs_expand (the RGBA planes) and yuvs_derived_expand
+// (yuv_derived.hpp: the planar copy).  Columns beyond W and the second row of an odd H's last block row hold values that are never stored.
 template <int FORMAT, bool NEAREST>
-__global__ void __launch_bounds__(YUV_LANES_X *YUV_BLOCK_ROWS) yuvs_expand(const YuvsInArgs a)
+__device__ __forceinline__ void yuvs_block_pixels(const YuvsInArgs &a, const uint8_t *frame, const uint32_t bx, const uint32_t by, uint32_t (&px)[2][8])
 {
-    const uint32_t bx = blockIdx.x * YUV_LANES_X + threadIdx.x;
-    const uint32_t by = blockIdx.y * YUV_BLOCK_ROWS + threadIdx.y; // wave-uniform
-    if(bx >= a.blocks_x || by >= a.ch)
-        return;
     const uint32_t x0 = bx * YUV_BLOCK_W, ya = by * YUV_BLOCK_H; // x0 < W, ya < H
     const bool two_rows = ya + 1u < a.H;                         // an odd H's last block row has one pixel row
-    const uint8_t *frame = a.s.base + (size_t)blockIdx.z * a.s.frame_stride;
     const uint8_t *c_plane = frame + a.s.c_offset; // I420: Cb; NV12: CbCr
     // Y: row ya and row ya + 1 (clamped to the plane: its pixels are not stored then), columns x0 … x0 + 7
     uint32_t y[2][8];
@@ -159,14 +159,25 @@ __global__ void __launch_bounds__(YUV_LANES_X *YUV_BLOCK_ROWS) yuvs_expand(const
             for(int i = 0; i < 8; i++)
                 su[j][i] = 3 * hu[1][i] + hu[j ? 2 : 0][i], sv[j][i] = 3 * hv[1][i] + hv[j ? 2 : 0][i];
     }
-    uint32_t px[2][8];
 #pragma unroll
     for(int j = 0; j < 2; j++)
 #pragma unroll
         for(int i = 0; i < 8; i++)
             px[j][i] = yuv_in_pixel(a.k, (int32_t)y[j][i], su[j][i], sv[j][i]);
+}
+
+template <int FORMAT, bool NEAREST>
+__global__ void __launch_bounds__(YUV_LANES_X *YUV_BLOCK_ROWS) yuvs_expand(const YuvsInArgs a)
+{
+    const uint32_t bx = blockIdx.x * YUV_LANES_X + threadIdx.x;
+    const uint32_t by = blockIdx.y * YUV_BLOCK_ROWS + threadIdx.y; // wave-uniform
+    if(bx >= a.blocks_x || by >= a.ch)
+        return;
+    const uint32_t x0 = bx * YUV_BLOCK_W, ya = by * YUV_BLOCK_H; // x0 < W, ya < H
+    uint32_t px[2][8];
+    yuvs_block_pixels<FORMAT, NEAREST>(a, a.s.base + (size_t)blockIdx.z * a.s.frame_stride, bx, by, px);
     uint32_t *out = reinterpret_cast<uint32_t *>(a.dst + (size_t)blockIdx.z * a.image_stride) + (size_t)ya * a.W + x0;
-    yuv_in_store(out, a.W, x0, two_rows, a.rows16, px);
+    yuv_in_store(out, a.W, x0, ya + 1u < a.H, a.rows16, px);
 }
 
 template <bool PLANAR, int FORMAT>

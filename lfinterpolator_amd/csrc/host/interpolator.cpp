@@ -133,7 +133,16 @@ void Interpolator::uploadVideoFrame()
     check(lfi_upload_wait(context)); // the previous step's copies have left the frames' memory
     video->loadFrames(inputFrame, inFrames, frameBytes);
     const int range = inRange >= 0 ? inRange : (video->videoFullRange() == 1 ? LFI_YUV_FULL : LFI_YUV_LIMITED);
-    check(lfi_upload_images_yuv420(context, 0, static_cast<int>(n), inMatrix, range, inChroma, inFrames, frameBytes));
+    if(inputsReleased)
+    {
+        // lean inputs: the context holds only the derived planar copy, the frames go straight into it
+        lfi_yuv_surfaces surfaces{};
+        check(lfi_yuv_surfaces_packed(LFI_YUV_I420, LFI_MEM_HOST, inFrames, resolution.x, resolution.y, &surfaces));
+        surfaces.frame_stride = frameBytes;
+        check(lfi_upload_images_yuv_derived(context, 0, static_cast<int>(n), inMatrix, range, inChroma, &surfaces));
+    }
+    else
+        check(lfi_upload_images_yuv420(context, 0, static_cast<int>(n), inMatrix, range, inChroma, inFrames, frameBytes));
     check(lfi_upload_wait(context));
     loadedFrame = inputFrame;
 }
@@ -199,6 +208,18 @@ void Interpolator::interpolate(std::string outputPath, std::string trajectory, f
         methodID = LFI_METHOD_STD;
     else
         throw std::runtime_error("The specified interpolation method does not exist!");
+    if(leanInputs)
+    {
+        // the context will hold only the planar copy of the inputs: whatever reads the RGBA planes, or needs a second context, is refused now
+        if(!video)
+            throw std::runtime_error("Lean inputs belong to a light-field video: the input has to be a directory of .y4m files!");
+        if(inRange > 0 || autofocus || autoRange.x != 0 || autoRange.y != 0 || focusTiles.x != 0 || focusTiles.y != 0 || viewMaps)
+            throw std::runtime_error("Lean inputs keep no RGBA planes: they cannot be combined with all-focus rendering (-r), autofocus, auto range, focus tiles or per-view focus maps!");
+        if(viewCentred || perViewFocus)
+            throw std::runtime_error("Lean inputs keep a planar copy padded for one set of shifts: they cannot be combined with view-centred shifts (-c) or a focus per view (-F)!");
+        if(gpuCount > 1)
+            throw std::runtime_error("Lean inputs work on one GPU only!");
+    }
     if(video && loadedFrame != inputFrame)
         uploadVideoFrame();
     if(quiltTile.x > 0 || quiltTile.y > 0)
@@ -310,6 +331,12 @@ void Interpolator::interpolate(std::string outputPath, std::string trajectory, f
     if((compareMethods || !compareDir.empty()) && gpuCount > 1)
         throw std::runtime_error("Comparing views (--compare, --compare-methods) works on one GPU only!");
     shardOverGpus(params);
+    if(leanInputs && !inputsReleased)
+    {
+        // the first time step is on the device and its parameters are set: from here on the planar copy, built for them, is the only copy
+        check(lfi_release_inputs(context));
+        inputsReleased = true;
+    }
     // The views never leave the library except through lfi_download_view / _quilt, which re-create the constant alpha: fixed-focus
     // TEN_WM renders therefore use the alpha-free byte-plane layout (a quarter fewer bytes written per launch, csrc/hip/blend_p3.hpp);
     // the other renders keep the reference's RGBA planes (they would pay a conversion pass).  Output files are identical.

@@ -93,6 +93,10 @@ class Interpolator
             inChroma = chroma;
             loadedFrame = -1;
         }
+        // a light-field video rendered at fixed focus on one GPU: after the first time step's parameters are set the context keeps only the
+        // derived planar copy of the inputs (lfi_release_inputs), and every later step's frames go straight into it
+        // (lfi_upload_images_yuv_derived) — less than half the device memory, one pass per step.  The files written are the same
+        void setLeanInputs(bool on) { leanInputs = on; }
         // closes the video files of setY4m, setNv12 and setQuiltY4m (interpolate() leaves them open for the next time step's views); throws when that fails
         void finish();
         float lastAverageTime() const { return averageTime; }
@@ -167,6 +171,7 @@ class Interpolator
         std::unique_ptr<LfLoader> video;           // the input, where it is a light-field video
         int inputFrame{0}, loadedFrame{-1};        // the time step to render / the one on the device
         int inMatrix{LFI_YUV_BT709}, inRange{-1}, inChroma{LFI_CHROMA_BILINEAR};
+        bool leanInputs{false}, inputsReleased{false}; // setLeanInputs / lfi_release_inputs has been called on the context
         uint8_t *inFrames{nullptr};                // one I420 frame per camera, page-locked where that works
         bool inFramesPinned{false};
         std::vector<uint8_t> inFramesPageable;

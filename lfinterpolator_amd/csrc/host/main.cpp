@@ -5,11 +5,12 @@
 // directory of images or against the other method's render), --native / --lens / --native-tile / --native-views (the native image of a
 // lenticular display, interlaced on the GPU), --y4m / --nv12 / --fps / --yuv-matrix / --yuv-range (the views as one YUV 4:2:0 video file, converted on
 // the GPU), --quilt-y4m (the quilt as one YUV 4:2:0 video frame per time step: a quilt video), --frames / --in-matrix / --in-range / --in-chroma (a light-field video as input: a directory of per-camera Y4M files whose frames
-// become the images on the GPU) and --synthetic for runs without a dataset.
+// become the images on the GPU), --lean-inputs (such a video at fixed focus from the planar copy of the inputs alone) and --synthetic for runs without a dataset.
 #include <array>
 #include <iostream>
 #include <memory>
 #include <sstream>
+#include <utility>
 #include <vector>
 
 #include "arguments.hpp"
@@ -68,6 +69,7 @@ int main(int argc, char **argv)
                           "--in-matrix 709|601 - with a light-field video: the colour matrix of its files (default=709)\n"
                           "--in-range limited|full - with a light-field video: the range of its files (default: their XCOLORRANGE tag, else limited)\n"
                           "--in-chroma bilinear|nearest - with a light-field video: how chroma is brought to full resolution (default=bilinear, the triangle filter of centre-sited chroma)\n"
+                          "--lean-inputs - with a light-field video rendered at fixed focus: after the first time step the GPU keeps only the planar copy of the inputs (3 bytes per pixel and image instead of 7) and every later step's frames are expanded straight into it in one pass; the files written are the same; not with -r, -F, -c, --autofocus, --auto-range, --focus-tiles, --view-maps, -g above 1 or --synthetic\n"
                           "--compare DIR - after the render, compare every view with DIR/NN.png (the names -o writes; same size) on the GPU, all views in one pass: prints \"compare NN psnr <dB> ssim <index> maxdiff <largest byte difference> differing <colour bytes that differ>\" per view, then \"compare all psnr ... ssim ...\"; one GPU\n"
                           "--compare-methods - render the views with the other method first (STD if -m TEN_WM, TEN_WM if -m STD; same parameters), keep them on the GPU, render with -m and compare the two there; prints the lines of --compare; the stored images are those of -m; one GPU; not with --compare\n"
                           "--synthetic cols,rows,width,height[,seed] - use a generated light field instead of -i\n"
@@ -89,6 +91,29 @@ int main(int argc, char **argv)
     {
         std::cerr << "Missing required parameters. Use -h for help." << std::endl;
         return EXIT_FAILURE;
+    }
+
+    if(args["--lean-inputs"])
+    {
+        // the context keeps only the planar copy of the inputs: nothing that reads the RGBA planes, pads the copy for other shifts or needs a
+        // second context
+        const std::pair<bool, const char *> refused[] = {
+            {synthetic, "--synthetic (it needs a light-field video: -i with a directory of .y4m files)"},
+            {static_cast<bool>(args["--autofocus"]), "--autofocus (the focus curve reads the RGBA planes)"},
+            {static_cast<bool>(args["--auto-range"]), "--auto-range (the focus tiles read the RGBA planes)"},
+            {static_cast<bool>(args["--focus-tiles"]), "--focus-tiles (the focus tiles read the RGBA planes)"},
+            {static_cast<bool>(args["--view-maps"]), "--view-maps (per-view focus maps read the RGBA planes)"},
+            {args["-r"] && range > 0, "-r above 0 (all-focus rendering reads the RGBA planes)"},
+            {static_cast<bool>(args["-c"]), "-c (the planar copy is padded for one set of shifts)"},
+            {static_cast<bool>(args["-F"]), "-F (the planar copy is padded for one set of shifts)"},
+            {args["-g"] && static_cast<int>(args["-g"]) > 1, "-g above 1 (it works in one context)"},
+        };
+        for(const auto &[given, what] : refused)
+            if(given)
+            {
+                std::cerr << "--lean-inputs (only the planar copy of the inputs stays on the GPU) cannot be combined with " << what << "." << std::endl;
+                return EXIT_FAILURE;
+            }
     }
 
     if(args["--autofocus"] && (args["-F"] || args["-c"] || args["--view-maps"]))
@@ -483,6 +508,12 @@ int main(int argc, char **argv)
             interpolator->setCompareMethods(true);
         if((args["--frames"] || args["--in-matrix"] || args["--in-range"] || args["--in-chroma"]) && !interpolator->isVideo())
             throw std::runtime_error("--frames, --in-matrix, --in-range and --in-chroma belong to a light-field video: -i has to be a directory of .y4m files");
+        if(args["--lean-inputs"])
+        {
+            if(!interpolator->isVideo())
+                throw std::runtime_error("--lean-inputs belongs to a light-field video: -i has to be a directory of .y4m files");
+            interpolator->setLeanInputs(true);
+        }
         if(interpolator->isVideo())
         {
             if(firstFrame + frameSteps > interpolator->frameCount())
