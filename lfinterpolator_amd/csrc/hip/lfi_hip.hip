@@ -470,9 +470,6 @@ int check_yuv_upload(lfi_ctx *ctx, const char *who, int g0, int n, int matrix, i
     return fault ? fail(ctx, LFI_EINVAL, std::string(who) + fault) : LFI_OK;
 }
 
-// yuv_derived.hpp's launch, defined at the end of this file
-hipError_t launch_yuvs_derived_expand(hipStream_t stream, int format, bool nearest, const lfi::YuvsDerivedArgs &a, int n);
-
 // Behind the three upload calls.  The arguments have passed check_yuv_upload; src is what host_i420_surfaces made, or has passed
 // yuv_surfaces_fault, which gave extent.  derived: the frames go into the planar copy (yuvs_derived_expand), which stays the valid copy it
 // was — no version moves; else into the RGBA planes (yuvs_expand), and the copy is rebuilt from them by the next render that reads it
@@ -525,7 +522,7 @@ int upload_yuv_surfaces(lfi_ctx *ctx, const char *who, int g0, int n, int matrix
             d.phase = ctx->d_planar_phase.as<int32_t>();
             d.pitch = (uint32_t)ctx->planar_pitch, d.padx = (uint32_t)ctx->planar_padx;
             d.g0 = (uint32_t)(g0 + k0);
-            LFI_HIP(ctx, launch_yuvs_derived_expand(st, src.format, chroma == LFI_CHROMA_NEAREST, d, nk));
+            LFI_HIP(ctx, lfi::launch_yuvs_derived_expand(st, src.format, chroma == LFI_CHROMA_NEAREST, d, nk));
             continue;
         }
         a.dst = ctx->grid.get() + in_plane_bytes(ctx) * (size_t)(g0 + k0);
@@ -2751,31 +2748,5 @@ int lfi_debug_p3_trace(unsigned long long *out, int n_words)
     return hipMemcpyFromSymbol(out, HIP_SYMBOL(lfi::lfi_p3_trace_buf), sizeof(unsigned long long) * std::min(n_words, 1024 * 8)) == hipSuccess ? 0 : 1;
 }
 #endif
-namespace {
-
-// Enqueues the ONE yuvs_derived_expand launch for n frames.  The caller has checked sizes, alignment and memory as for launch_yuvs_expand;
-// a.planar holds images [g0, g0 + n) with a.in.H rows of a.pitch bytes per plane, a.pitch a multiple of 16.
-// (Defined here, at the end of the file, so that the four kernels are first used behind every other kernel: yuv_derived.hpp says why.)
-hipError_t launch_yuvs_derived_expand(hipStream_t stream, const int format, const bool nearest, const lfi::YuvsDerivedArgs &a, const int n)
-{
-    const dim3 grid((a.pitch + lfi::YUVD_SPAN - 1) / lfi::YUVD_SPAN, (a.in.ch + lfi::YUVD_ROWS - 1) / lfi::YUVD_ROWS, n), block(lfi::YUVD_THREADS);
-    if(format == lfi::YUVS_NV12)
-    {
-        if(nearest)
-            hipLaunchKernelGGL((lfi::yuvs_derived_expand<lfi::YUVS_NV12, true>), grid, block, 0, stream, a);
-        else
-            hipLaunchKernelGGL((lfi::yuvs_derived_expand<lfi::YUVS_NV12, false>), grid, block, 0, stream, a);
-    }
-    else
-    {
-        if(nearest)
-            hipLaunchKernelGGL((lfi::yuvs_derived_expand<lfi::YUVS_I420, true>), grid, block, 0, stream, a);
-        else
-            hipLaunchKernelGGL((lfi::yuvs_derived_expand<lfi::YUVS_I420, false>), grid, block, 0, stream, a);
-    }
-    return hipGetLastError();
-}
-
-} // namespace
 } // extern "C"
 

@@ -119,8 +119,26 @@ __global__ void __launch_bounds__(YUVD_THREADS) yuvs_derived_expand(const YuvsDe
     }
 }
 
-// The launch is launch_yuvs_derived_expand at the END of lfi_hip.hip, not here: a code object lists its kernels in the order of their first
-// use in the translation unit, and the code-object tests of the kernels around yuv_surfaces.hpp read a kernel's LDS size from the record
-// that follows its name — so these four, the only YUV kernels with LDS, are first used behind every kernel those tests look at.
+// Enqueues the ONE yuvs_derived_expand launch for n frames.  The caller has checked sizes, alignment and memory as for launch_yuvs_expand;
+// a.planar holds images [g0, g0 + n) with a.in.H rows of a.pitch bytes per plane, a.pitch a multiple of 16.
+inline hipError_t launch_yuvs_derived_expand(hipStream_t stream, const int format, const bool nearest, const YuvsDerivedArgs &a, const int n)
+{
+    const dim3 grid((a.pitch + YUVD_SPAN - 1) / YUVD_SPAN, (a.in.ch + YUVD_ROWS - 1) / YUVD_ROWS, n), block(YUVD_THREADS);
+    if(format == YUVS_NV12)
+    {
+        if(nearest)
+            hipLaunchKernelGGL((yuvs_derived_expand<YUVS_NV12, true>), grid, block, 0, stream, a);
+        else
+            hipLaunchKernelGGL((yuvs_derived_expand<YUVS_NV12, false>), grid, block, 0, stream, a);
+    }
+    else
+    {
+        if(nearest)
+            hipLaunchKernelGGL((yuvs_derived_expand<YUVS_I420, true>), grid, block, 0, stream, a);
+        else
+            hipLaunchKernelGGL((yuvs_derived_expand<YUVS_I420, false>), grid, block, 0, stream, a);
+    }
+    return hipGetLastError();
+}
 
 } // namespace lfi

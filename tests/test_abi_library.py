@@ -6,6 +6,8 @@ import subprocess
 
 import pytest
 
+import code_object
+
 
 def _declared_symbols(root):
     text = open(os.path.join(root, "include", "lfi.h")).read()
@@ -70,54 +72,21 @@ def test_product_never_touches_the_oracle():
     assert not bad, bad
 
 
-def _gfx950_code_object(native, tmp_path):
-    """The gfx950 ELF inside the shared library's clang offload bundle."""
-    import struct
-    data = open(native.build.HIP_LIB, "rb").read()
-    i = data.find(b"__CLANG_OFFLOAD_BUNDLE__")
-    assert i >= 0
-    n = struct.unpack_from("<Q", data, i + 24)[0]
-    off = i + 32
-    for _ in range(n):
-        o, sz, tl = struct.unpack_from("<QQQ", data, off)
-        off += 24
-        triple = data[off:off + tl]
-        off += tl
-        if b"gfx950" in triple:
-            path = tmp_path / "gfx950.co"
-            path.write_bytes(data[i + o:i + o + sz])
-            return str(path)
-    raise AssertionError("no gfx950 code object in the bundle")
-
-
-LLVM_BIN = "/opt/rocm/lib/llvm/bin"
-
-
-@pytest.mark.skipif(not os.path.exists(os.path.join(LLVM_BIN, "llvm-readelf")), reason="ROCm LLVM tools not installed")
-def test_pipelined_kernels_use_no_scratch_and_the_counted_stores(native, tmp_path):
+@pytest.mark.skipif(not code_object.have_tools(), reason="ROCm LLVM tools not installed")
+def test_pipelined_kernels_use_no_scratch_and_the_counted_stores(native):
     """The LDS-DMA pipelines (blend_p3, blend_stdx, blend_planar, blend_persist, blend_wave) wait with HAND-COUNTED `s_waitcnt vmcnt(n)`: n is the
     number of vector-memory instructions the kernel itself issued after the DMA it waits for.  Anything the compiler adds to that
     queue behind our back breaks the count silently: register spills (scratch loads / stores are vector-memory operations), or an
     epilogue whose stores were merged or split.  So: none of these kernels may use scratch, and blend_p3's epilogues must consist of
     six 16-byte stores and its DMA issue sites of three LDS loads per octet of images (the compiler may clone a site, never change its size)."""
-    co = _gfx950_code_object(native, tmp_path)
-    notes = subprocess.run([os.path.join(LLVM_BIN, "llvm-readelf"), "--notes", co], capture_output=True, text=True, check=True).stdout
-    kernels = {}
-    name = None
-    for line in notes.splitlines():
-        line = line.strip()
-        if line.startswith(".name:"):
-            name = line.split(":", 1)[1].strip()
-            kernels[name] = {}
-        elif name and ":" in line and line.split(":")[0] in (".private_segment_fixed_size", ".vgpr_spill_count", ".sgpr_spill_count", ".vgpr_count"):
-            kernels[name][line.split(":")[0]] = int(line.split(":")[1])
+    kernels = code_object.kernels(native.build.HIP_LIB)
     # focus_range_t (round 5): hand-counted lgkmcnt waits on its LDS reads (no scratch), and at most 136 registers per lane — three of its
     # waves per SIMD must leave room for one wave of focus_flagged (at most 104), or the flagged passes queue behind the persistent kernel
-    range_t = [k for k in kernels if "focus_range_tI" in k]
+    range_t = list(code_object.named(kernels, "focus_range_t"))
     assert len(range_t) == 2, sorted(kernels)
     for k in range_t:
         assert kernels[k][".private_segment_fixed_size"] == 0 and kernels[k][".vgpr_spill_count"] == 0 and kernels[k][".vgpr_count"] <= 136, (k, kernels[k])
-    flagged = [k for k in kernels if "focus_flagged" in k]
+    flagged = list(code_object.named(kernels, "focus_flagged"))
     assert len(flagged) == 1 and kernels[flagged[0]][".vgpr_count"] <= 104, (flagged, kernels[flagged[0]] if flagged else None)
     pipelined = [k for k in kernels if any(s in k for s in ("blend_p3", "blend_planar", "blend_persist", "blend_wave", "blend_stdx", "blend_afs"))]
     assert sum("blend_afsI" in k for k in pipelined) == 2     # all-focus STD, every sample gathered once: three and four chunks
@@ -138,20 +107,11 @@ def test_pipelined_kernels_use_no_scratch_and_the_counted_stores(native, tmp_pat
         elif not m or m.group(3) == "1":
             assert kernels[k][".vgpr_count"] <= 256, (k, kernels[k])      # two waves per SIMD: two workgroups per CU
     assert n_two_groups >= 3
-    dis = subprocess.run([os.path.join(LLVM_BIN, "llvm-objdump"), "-d", co], capture_output=True, text=True, check=True).stdout
-    body = {}
-    cur = None
-    for line in dis.splitlines():
-        m = re.match(r"^[0-9a-f]+ <(\S+)>:", line)
-        if m:
-            cur = m.group(1)
-            body[cur] = []
-        elif cur:
-            body[cur].append(line)
+    body = code_object.bodies(native.build.HIP_LIB)
     rgba_out = [k for k in body if p3_name.search(k) and p3_name.search(k).group(2) == "0" and p3_name.search(k).group(5) == "1"]
     assert len(rgba_out) >= 3, sorted(body)  # the RGBA epilogue (round 4): two to four chunks of images at least
     for k in rgba_out:
-        text = "\n".join(body[k])
+        text = body[k]
         n_st16 = len(re.findall(r"global_store_dwordx4", text))
         assert n_st16 >= 8 and n_st16 % 8 == 0, (k, n_st16)  # two adjacent 16-byte stores per view (the ragged right edge: dword stores)
         assert "scratch_" not in text and "buffer_store" not in text and "buffer_load" not in text, k
@@ -159,7 +119,7 @@ def test_pipelined_kernels_use_no_scratch_and_the_counted_stores(native, tmp_pat
     assert len(shipped) >= 5, sorted(body)   # one chunk: one pass / up to four; two to four chunks: two waves of 32 views
     assert sum(p3_name.search(k).group(4) == "4" for k in shipped) == 1     # up to four view passes: one chunk of images, 16 views per wave
     for k in shipped:
-        text = "\n".join(body[k])
+        text = body[k]
         if p3_name.search(k).group(1) == "1" and p3_name.search(k).group(3) == "1" and p3_name.search(k).group(4) == "1":
             # the one-pass kernel lets all its fetches land between its last MFMA and its first store (profiles/r03_notes.md §11: −2 % at
             # config 2, −7 … −15 % per rank of config 4; round 2 had this wait by accident, a clean-up lost it once)

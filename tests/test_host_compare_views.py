@@ -6,6 +6,7 @@ import math
 import numpy as np
 import pytest
 
+import code_object
 import quality_ref as ref
 
 
@@ -99,47 +100,11 @@ def test_record_layout_matches_the_header(native):
     assert (q.sq_err.offset, q.differing_bytes.offset, q.windows.offset, q.max_abs_diff.offset, ctypes.sizeof(q)) == (88, 112, 120, 128, 136)
 
 
-def _llvm_readelf():
-    """llvm-readelf of the ROCm installation whose hipcc built the library: beside the compiler's own LLVM tools"""
-    import os
-    import shutil
-    hipcc = shutil.which(os.environ.get("HIPCC", "hipcc")) or "/opt/rocm/bin/hipcc"
-    roots = [os.path.dirname(os.path.dirname(os.path.realpath(hipcc))), os.environ.get("ROCM_PATH", "/opt/rocm"), "/opt/rocm"]
-    for root in roots:
-        for sub in ("lib/llvm/bin", "llvm/bin"):
-            tool = os.path.join(root, sub, "llvm-readelf")
-            if os.path.exists(tool):
-                return tool
-    raise AssertionError(f"llvm-readelf not found under {roots}: the library was built with ROCm's hipcc, its LLVM tools belong to the same installation")
-
-
-def test_the_new_kernels_use_no_scratch(native, tmp_path):
+def test_the_new_kernels_use_no_scratch(native):
     """quality_tiles (three layout pairs) and quality_views: no scratch, no spills, wave size 64 (the code object's notes)"""
-    import struct
-    import subprocess
-    data = open(native.build.HIP_LIB, "rb").read()
-    i = data.find(b"__CLANG_OFFLOAD_BUNDLE__")
-    assert i >= 0
-    count = struct.unpack_from("<Q", data, i + 24)[0]
-    off, co = i + 32, None
-    for _ in range(count):
-        o, sz, tl = struct.unpack_from("<QQQ", data, off)
-        off += 24
-        if b"gfx950" in data[off:off + tl]:
-            co = tmp_path / "gfx950.co"
-            co.write_bytes(data[i + o:i + o + sz])
-        off += tl
-    assert co is not None
-    notes = subprocess.run([_llvm_readelf(), "--notes", str(co)], capture_output=True, text=True, check=True).stdout
-    kernels, name = {}, None
-    for line in notes.splitlines():
-        line = line.strip()
-        if line.startswith(".name:"):
-            name = line.split(":", 1)[1].strip()
-            kernels[name] = {}
-        elif name and ":" in line and line.split(":")[0] in (".private_segment_fixed_size", ".vgpr_spill_count", ".sgpr_spill_count", ".wavefront_size"):
-            kernels[name][line.split(":")[0]] = int(line.split(":")[1])
-    ours = {k: v for k, v in kernels.items() if "quality_tiles" in k or "quality_views" in k}
-    assert sum("quality_tiles" in k for k in ours) == 3 and sum("quality_views" in k for k in ours) == 1, sorted(ours)
+    kernels = code_object.kernels(native.build.HIP_LIB)
+    tiles, views = code_object.named(kernels, "quality_tiles"), code_object.named(kernels, "quality_views")
+    ours = {**tiles, **views}
+    assert len(tiles) == 3 and len(views) == 1, sorted(ours)
     for k, v in ours.items():
         assert v[".private_segment_fixed_size"] == 0 and v[".vgpr_spill_count"] == 0 and v[".sgpr_spill_count"] == 0 and v[".wavefront_size"] == 64, (k, v)

@@ -1,14 +1,12 @@
 """CPU: the host side of autofocus (lfi_focus_curve) — the numpy restatement of the focus curve (tests/focus_curve_ref.py) anchored to the
 committed oracle, the candidate list of lfi_host_focus_candidates, the planted scene the GPU test uploads, the CLI's checks of --autofocus,
 and the new kernels' code objects."""
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import code_object
 import focus_curve_ref as ref
-from test_abi_library import LLVM_BIN, _gfx950_code_object
 from view_rows import run_cli
 
 # name, cols, rows, W, H, trajectory, focus, range, seed — hash-noise light fields (oracle synthetic_lf).  Small images have block radius 1
@@ -102,20 +100,11 @@ def test_cli_refuses_autofocus_steps_alone(native, tmp_path):
     assert res.returncode != 0 and "--autofocus" in res.stderr
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(LLVM_BIN, "llvm-readelf")), reason="ROCm LLVM tools not installed")
-def test_focus_curve_kernels_use_no_scratch_and_do_not_spill(native, tmp_path):
+@pytest.mark.skipif(not code_object.have_tools(), reason="ROCm LLVM tools not installed")
+def test_focus_curve_kernels_use_no_scratch_and_do_not_spill(native):
     """From the code object's metadata: the three kernels of csrc/hip/focus_curve.hpp exist, use no scratch and spill nothing; the partial-sum
     kernel keeps focus_estimate_packed<2, 4>'s five waves per SIMD (at most 96 registers per lane)."""
-    co = _gfx950_code_object(native, tmp_path)
-    notes = subprocess.run([os.path.join(LLVM_BIN, "llvm-readelf"), "--notes", co], capture_output=True, text=True, check=True).stdout
-    kernels, name = {}, None
-    for line in notes.splitlines():
-        line = line.strip()
-        if line.startswith(".name:"):
-            name = line.split(":", 1)[1].strip()
-            kernels[name] = {}
-        elif name and ":" in line and line.split(":")[0] in (".private_segment_fixed_size", ".vgpr_spill_count", ".sgpr_spill_count", ".vgpr_count"):
-            kernels[name][line.split(":")[0]] = int(line.split(":")[1])
+    kernels = code_object.kernels(native.build.HIP_LIB)
     curve = {k: v for k, v in kernels.items() if "focus_curve_" in k}
     assert sorted(k.split("focus_curve_")[1].split("I")[0].split("E")[0] for k in curve) == ["partial", "pick", "sum"], sorted(curve)
     for k, v in curve.items():

@@ -2,14 +2,12 @@
 lfi_host_focus_auto_range (--auto-range), the exported symbols, the two-depth planted scene the GPU test uploads, the CLI's checks of
 --focus-tiles / --auto-range, and the new kernel's code object."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import code_object
 import focus_curve_ref as ref
-from test_abi_library import LLVM_BIN, _gfx950_code_object
 from view_rows import run_cli
 
 
@@ -142,23 +140,13 @@ def test_cli_refuses_auto_range_with_autofocus(native, tmp_path):
 
 # ---- the code object ------------------------------------------------------------------------------------------------------------------
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(LLVM_BIN, "llvm-readelf")), reason="ROCm LLVM tools not installed")
-def test_focus_tile_costs_uses_no_scratch_and_keeps_eight_waves_per_simd(native, tmp_path):
+@pytest.mark.skipif(not code_object.have_tools(), reason="ROCm LLVM tools not installed")
+def test_focus_tile_costs_uses_no_scratch_and_keeps_eight_waves_per_simd(native):
     """From the code object's metadata: both instantiations of focus_tile_costs (csrc/hip/focus_tiles.hpp) exist, use no scratch, spill nothing
     and stay at or below 64 registers per lane (eight waves per SIMD; its 32 KiB of LDS per workgroup allow five workgroups per CU)."""
-    co = _gfx950_code_object(native, tmp_path)
-    notes = subprocess.run([os.path.join(LLVM_BIN, "llvm-readelf"), "--notes", co], capture_output=True, text=True, check=True).stdout
-    kernels, name = {}, None
-    keys = (".private_segment_fixed_size", ".vgpr_spill_count", ".sgpr_spill_count", ".vgpr_count")
-    for line in notes.splitlines():
-        line = line.strip()
-        if line.startswith(".name:"):
-            name = line.split(":", 1)[1].strip()
-            kernels[name] = {}
-        elif name and ":" in line and line.split(":")[0] in keys:
-            kernels[name][line.split(":")[0]] = int(line.split(":")[1])
-    tiles = {k: v for k, v in kernels.items() if "focus_tile_costs" in k}
+    kernels = code_object.kernels(native.build.HIP_LIB)
+    tiles = code_object.named(kernels, "focus_tile_costs")
     assert len(tiles) == 2, sorted(tiles)
     for k, v in tiles.items():
         assert v[".private_segment_fixed_size"] == 0 and v[".vgpr_spill_count"] == 0 and v[".sgpr_spill_count"] == 0, (k, v)
-        assert v[".vgpr_count"] <= 64, (k, v)
+        assert v[".vgpr_count"] <= 64 and v[".group_segment_fixed_size"] <= 32 * 1024, (k, v)

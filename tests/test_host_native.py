@@ -2,15 +2,13 @@
 written and against the properties that follow from it; the coverage of the cases the GPU test shares; the calibration function
 (csrc/host/lenticular.cpp through lfi_host_lenticular) against its restatement in Python floats, bit for bit; the exported symbols, the CLI's
 checks and the new kernel's code object."""
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import code_object
 import native_ref as ref
 import scaled_quilt_ref as quilt_ref
-from test_abi_library import LLVM_BIN, _gfx950_code_object
 from view_rows import run_cli
 
 
@@ -203,36 +201,19 @@ def test_cli_help_names_the_flags(native):
 
 # ---- the code object --------------------------------------------------------------------------------------------------------------------------
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(LLVM_BIN, "llvm-readelf")), reason="ROCm LLVM tools not installed")
-def test_native_interlace_uses_no_scratch_no_lds_and_whole_dword_stores(native, tmp_path):
+@pytest.mark.skipif(not code_object.have_tools(), reason="ROCm LLVM tools not installed")
+def test_native_interlace_uses_no_scratch_no_lds_and_whole_dword_stores(native):
     """From the code object: both instantiations of native_interlace (csrc/hip/native_image.hpp) exist, use no scratch and no LDS, spill nothing,
     stay at or below 64 registers per lane (eight waves per SIMD), load bytes and store dwords only, and contain no atomic instruction."""
-    co = _gfx950_code_object(native, tmp_path)
-    notes = subprocess.run([os.path.join(LLVM_BIN, "llvm-readelf"), "--notes", co], capture_output=True, text=True, check=True).stdout
-    kernels, name = {}, None
-    keys = (".private_segment_fixed_size", ".vgpr_spill_count", ".sgpr_spill_count", ".vgpr_count", ".group_segment_fixed_size")
-    for line in notes.splitlines():
-        line = line.strip()
-        if line.startswith(".name:"):
-            name = line.split(":", 1)[1].strip()
-            kernels[name] = {}
-        elif name and ":" in line and line.split(":")[0] in keys:
-            kernels[name][line.split(":")[0]] = int(line.split(":")[1])
-    interlace = {k: v for k, v in kernels.items() if "native_interlace" in k}
+    kernels = code_object.kernels(native.build.HIP_LIB)
+    interlace = code_object.named(kernels, "native_interlace")
     assert len(interlace) == 2, sorted(interlace)
     for k, v in interlace.items():
         assert v[".private_segment_fixed_size"] == 0 and v[".vgpr_spill_count"] == 0 and v[".sgpr_spill_count"] == 0, (k, v)
         assert v[".group_segment_fixed_size"] == 0 and v[".vgpr_count"] <= 64, (k, v)
-    dis = subprocess.run([os.path.join(LLVM_BIN, "llvm-objdump"), "-d", co], capture_output=True, text=True, check=True).stdout
-    cur, bodies = None, {}
-    for line in dis.splitlines():
-        if line.endswith(">:"):
-            cur = line.split("<")[1][:-2]
-        elif cur in interlace:
-            bodies.setdefault(cur, []).append(line)
+    bodies = {k: v for k, v in code_object.bodies(native.build.HIP_LIB).items() if k in interlace}
     assert set(bodies) == set(interlace)
-    for k, body in bodies.items():
-        text = "\n".join(body)
+    for k, text in bodies.items():
         assert "atomic" not in text and "scratch_" not in text and "ds_" not in text, k
         assert text.count("global_load_ubyte") == 3 and text.count("global_store_dword") == 1, k
         assert "global_store_byte" not in text and "global_store_short" not in text, k

@@ -3,14 +3,13 @@
 code object (csrc/hip/quilt_yuv.hpp)."""
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
+import code_object
 import quilt_yuv_ref as ref
 import yuv_ref
-from test_abi_library import LLVM_BIN, _gfx950_code_object
 from view_rows import run_cli
 
 HEADER = os.path.join(os.path.dirname(__file__), "..", "include", "lfi.h")
@@ -77,27 +76,12 @@ def test_cli_help_names_the_flag(native):
 
 # ---- the code object ------------------------------------------------------------------------------------------------------------------
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(LLVM_BIN, "llvm-readelf")), reason="ROCm LLVM tools not installed")
-def test_quilt_yuv_scale_uses_no_scratch_no_atomics_and_16_kib_of_lds(native, tmp_path):
+@pytest.mark.skipif(not code_object.have_tools(), reason="ROCm LLVM tools not installed")
+def test_quilt_yuv_scale_uses_no_scratch_no_atomics_and_16_kib_of_lds(native):
     """From the code object: the four instantiations of quilt_yuv_scale exist, use no scratch, spill nothing, hold at most 16 KiB of LDS, stay at
     or below 96 (RGBA views) / 128 (planar views) registers per lane — four waves per SIMD at least — and contain no atomic instruction."""
-    co = _gfx950_code_object(native, tmp_path)
-    notes = subprocess.run([os.path.join(LLVM_BIN, "llvm-readelf"), "--notes", co], capture_output=True, text=True, check=True).stdout
-    # a kernel's entry starts with "  - ." (its arguments' entries are indented further) and lists its keys in alphabetical order
-    kernels, cur = {}, None
-    keys = (".private_segment_fixed_size", ".vgpr_spill_count", ".sgpr_spill_count", ".vgpr_count", ".group_segment_fixed_size")
-    for line in notes.splitlines():
-        if line.startswith("  - ."):
-            cur = {}
-            line = "    " + line[4:]
-        if cur is None or not line.startswith("    .") or ":" not in line:
-            continue
-        key, value = line.strip().split(":", 1)
-        if key == ".name":
-            kernels[value.strip()] = cur
-        elif key in keys:
-            cur[key] = int(value)
-    fused = {k: v for k, v in kernels.items() if "quilt_yuv_scale" in k}
+    kernels = code_object.kernels(native.build.HIP_LIB)
+    fused = code_object.named(kernels, "quilt_yuv_scale")
     # <PLANAR, FORMAT>: Lb0 / Lb1, Li0 / Li1 in the mangled name
     assert sorted(re.search(r"ILb([01])ELi([01])E", k).groups() for k in fused) == [("0", "0"), ("0", "1"), ("1", "0"), ("1", "1")], sorted(fused)
     for k, v in fused.items():
@@ -105,15 +89,8 @@ def test_quilt_yuv_scale_uses_no_scratch_no_atomics_and_16_kib_of_lds(native, tm
         assert v[".private_segment_fixed_size"] == 0 and v[".vgpr_spill_count"] == 0 and v[".sgpr_spill_count"] == 0, (k, v)
         assert v[".group_segment_fixed_size"] <= 16 * 1024, (k, v)
         assert v[".vgpr_count"] <= (128 if "ILb1E" in k else 96), (k, v)
-    dis = subprocess.run([os.path.join(LLVM_BIN, "llvm-objdump"), "-d", co], capture_output=True, text=True, check=True).stdout
-    cur, bodies = None, {}
-    for line in dis.splitlines():
-        if line.endswith(">:"):
-            cur = line.split("<")[1][:-2]
-        elif cur in fused:
-            bodies.setdefault(cur, []).append(line)
+    bodies = {k: v for k, v in code_object.bodies(native.build.HIP_LIB).items() if k in fused}
     assert set(bodies) == set(fused)
-    for k, body in bodies.items():
-        text = "\n".join(body)
+    for k, text in bodies.items():
         assert "atomic" not in text and "scratch_" not in text, k
         assert "global_load_dword" in text and "ds_write_b128" in text, k   # phase 1 is quilt_scale's

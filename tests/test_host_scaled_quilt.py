@@ -1,14 +1,12 @@
 """CPU: the host side of scaled quilts (lfi_download_quilt_scaled) — the span arithmetic the kernel runs, through lfi_host_area_span, against
 overlaps computed by brute force; the numpy restatement (tests/scaled_quilt_ref.py) against the definition as written, the block mean, the
 identity and the float64 area mean; the exported symbols; the CLI's checks of --quilt-tile; the new kernel's code object."""
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import code_object
 import scaled_quilt_ref as ref
-from test_abi_library import LLVM_BIN, _gfx950_code_object
 from view_rows import run_cli
 
 # (src, dst): dst = 1, dst = src, integer ratios, coprime pairs, the tile sizes of 4096² and 8192² quilts from 1080p and 4K views
@@ -134,35 +132,18 @@ def test_cli_help_names_the_flag(native):
 
 # ---- the code object ------------------------------------------------------------------------------------------------------------------
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(LLVM_BIN, "llvm-readelf")), reason="ROCm LLVM tools not installed")
-def test_quilt_scale_uses_no_scratch_and_no_atomics(native, tmp_path):
+@pytest.mark.skipif(not code_object.have_tools(), reason="ROCm LLVM tools not installed")
+def test_quilt_scale_uses_no_scratch_and_no_atomics(native):
     """From the code object: both instantiations of quilt_scale (csrc/hip/quilt_scaled.hpp) exist, use no scratch, spill nothing, stay at or
     below 96 registers per lane (five waves per SIMD at least), and contain no atomic instruction."""
-    co = _gfx950_code_object(native, tmp_path)
-    notes = subprocess.run([os.path.join(LLVM_BIN, "llvm-readelf"), "--notes", co], capture_output=True, text=True, check=True).stdout
-    kernels, name = {}, None
-    keys = (".private_segment_fixed_size", ".vgpr_spill_count", ".sgpr_spill_count", ".vgpr_count")
-    for line in notes.splitlines():
-        line = line.strip()
-        if line.startswith(".name:"):
-            name = line.split(":", 1)[1].strip()
-            kernels[name] = {}
-        elif name and ":" in line and line.split(":")[0] in keys:
-            kernels[name][line.split(":")[0]] = int(line.split(":")[1])
-    scale = {k: v for k, v in kernels.items() if "quilt_scale" in k}
+    kernels = code_object.kernels(native.build.HIP_LIB)
+    scale = code_object.named(kernels, "quilt_scale")
     assert len(scale) == 2, sorted(scale)
     for k, v in scale.items():
         assert v[".private_segment_fixed_size"] == 0 and v[".vgpr_spill_count"] == 0 and v[".sgpr_spill_count"] == 0, (k, v)
         assert v[".vgpr_count"] <= 96, (k, v)
-    dis = subprocess.run([os.path.join(LLVM_BIN, "llvm-objdump"), "-d", co], capture_output=True, text=True, check=True).stdout
-    cur, bodies = None, {}
-    for line in dis.splitlines():
-        if line.endswith(">:"):
-            cur = line.split("<")[1][:-2]
-        elif cur in scale:
-            bodies.setdefault(cur, []).append(line)
+    bodies = {k: v for k, v in code_object.bodies(native.build.HIP_LIB).items() if k in scale}
     assert set(bodies) == set(scale)
-    for k, body in bodies.items():
-        text = "\n".join(body)
+    for k, text in bodies.items():
         assert "atomic" not in text and "scratch_" not in text, k
         assert "global_load_dword" in text and "ds_write_b128" in text, k

@@ -5,13 +5,12 @@ the new kernel's code object."""
 import math
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
+import code_object
 import yuv_ref as ref
-from test_abi_library import LLVM_BIN, _gfx950_code_object
 from view_rows import run_cli
 
 # (Kr, Kb) of Y = Kr·R + (1 − Kr − Kb)·G + Kb·B:  ITU-R BT.709 / BT.601
@@ -228,8 +227,8 @@ def test_cli_help_names_the_flags(native):
 
 # ---- the code object --------------------------------------------------------------------------------------------------------------------------
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(LLVM_BIN, "llvm-readelf")), reason="ROCm LLVM tools not installed")
-def test_yuv420_convert_uses_no_scratch_no_spills_and_no_lds(native, tmp_path):
+@pytest.mark.skipif(not code_object.have_tools(), reason="ROCm LLVM tools not installed")
+def test_yuv420_convert_uses_no_scratch_no_spills_and_no_lds(native):
     """From the code object's notes: both I420 instantiations of yuvs_convert (csrc/hip/yuv_surfaces.hpp), the kernel behind
     lfi_download_views_yuv420 and lfi_render_stream_yuv420, exist, use no scratch and no LDS and spill nothing; from its code: no atomics, no
     short stores — Y leaves as 8-byte pieces, chroma as dwords — and the aligned RGBA path reads 16 bytes per load, the planar path 8.
@@ -238,32 +237,15 @@ def test_yuv420_convert_uses_no_scratch_no_spills_and_no_lds(native, tmp_path):
     asserted.  yuvs_convert also writes the caller's surfaces in place, where pitch padding must keep its value: a ragged last block of a row
     stores its own bytes one by one.  The assertion is now the exact count of those: at most 7 Y columns × 2 rows + 3 chroma columns × 2
     planes = 20 byte stores, and every whole block still leaves as words."""
-    co = _gfx950_code_object(native, tmp_path)
-    notes = subprocess.run([os.path.join(LLVM_BIN, "llvm-readelf"), "--notes", co], capture_output=True, text=True, check=True).stdout
-    kernels, name = {}, None
-    keys = (".private_segment_fixed_size", ".vgpr_spill_count", ".sgpr_spill_count", ".vgpr_count", ".group_segment_fixed_size")
-    for line in notes.splitlines():
-        line = line.strip()
-        if line.startswith(".name:"):
-            name = line.split(":", 1)[1].strip()
-            kernels[name] = {}
-        elif name and ":" in line and line.split(":")[0] in keys:
-            kernels[name][line.split(":")[0]] = int(line.split(":")[1])
+    kernels = code_object.kernels(native.build.HIP_LIB)
     convert = {k: v for k, v in kernels.items() if re.search(r"yuvs_convertILb[01]ELi0E", k)}   # <PLANAR, YUVS_I420>
     assert len(convert) == 2, sorted(convert)
     for k, v in convert.items():
         assert v[".private_segment_fixed_size"] == 0 and v[".vgpr_spill_count"] == 0 and v[".sgpr_spill_count"] == 0, (k, v)
         assert v[".group_segment_fixed_size"] == 0 and v[".vgpr_count"] <= 128, (k, v)   # at least four waves per SIMD
-    dis = subprocess.run([os.path.join(LLVM_BIN, "llvm-objdump"), "-d", co], capture_output=True, text=True, check=True).stdout
-    cur, bodies = None, {}
-    for line in dis.splitlines():
-        if line.endswith(">:"):
-            cur = line.split("<")[1][:-2]
-        elif cur in convert:
-            bodies.setdefault(cur, []).append(line)
+    bodies = {k: v for k, v in code_object.bodies(native.build.HIP_LIB).items() if k in convert}
     assert set(bodies) == set(convert)
-    for k, body in bodies.items():
-        text = "\n".join(body)
+    for k, text in bodies.items():
         assert "atomic" not in text and "scratch_" not in text and "ds_" not in text, k
         assert "global_store_short" not in text and text.count("global_store_byte") == 20, k
         assert text.count("global_store_dwordx2") == 2 and len(re.findall(r"global_store_dword ", text)) == 2, k

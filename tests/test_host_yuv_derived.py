@@ -4,14 +4,13 @@ of --lean-inputs before a GPU is opened."""
 import ctypes as C
 import os
 import re
-import subprocess
 from types import SimpleNamespace
 
 import numpy as np
 import pytest
 
+import code_object
 import derived_ref
-from test_abi_library import LLVM_BIN, _gfx950_code_object
 from view_rows import run_cli
 
 
@@ -71,24 +70,12 @@ def test_null_arguments_are_refused_without_a_context(native):
     assert lib.lfi_debug_download_derived(None, 0, 1, None) == -1
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(LLVM_BIN, "llvm-readelf")), reason="ROCm LLVM tools not installed")
-def test_the_four_instantiations_use_no_scratch_and_fit_eight_workgroups_a_cu(native, tmp_path):
+@pytest.mark.skipif(not code_object.have_tools(), reason="ROCm LLVM tools not installed")
+def test_the_four_instantiations_use_no_scratch_and_fit_eight_workgroups_a_cu(native):
     """From the code object's notes: yuvs_derived_expand<FORMAT, NEAREST> (csrc/hip/yuv_derived.hpp) exists four times, uses no scratch, spills
     nothing, stays within 128 VGPRs and within 16 KiB of LDS — eight workgroups of 256 lanes fit a CU by registers and by LDS alike."""
-    co = _gfx950_code_object(native, tmp_path)
-    notes = subprocess.run([os.path.join(LLVM_BIN, "llvm-readelf"), "--notes", co], capture_output=True, text=True, check=True).stdout
-    # a kernel's record begins at "- .agpr_count:"; its keys are sorted, so .group_segment_fixed_size comes BEFORE its .name
-    keys = (".private_segment_fixed_size", ".vgpr_spill_count", ".sgpr_spill_count", ".vgpr_count", ".group_segment_fixed_size")
-    records, record = [], None
-    for line in notes.splitlines():
-        line = line.strip()
-        if line.startswith("- .agpr_count:"):
-            record = {}
-            records.append(record)
-        elif record is not None and ":" in line and line.split(":")[0] in keys + (".name",):
-            record[line.split(":")[0]] = line.split(":", 1)[1].strip()
-    kernels = {r[".name"]: {k: int(r[k]) for k in keys} for r in records if ".name" in r}
-    found = {k: v for k, v in kernels.items() if "yuvs_derived_expand" in k}
+    kernels = code_object.kernels(native.build.HIP_LIB)
+    found = code_object.named(kernels, "yuvs_derived_expand")
     assert len(found) == 4, sorted(found)
     for variant in ("ILi0ELb0E", "ILi0ELb1E", "ILi1ELb0E", "ILi1ELb1E"):
         assert any(variant in k for k in found), (variant, sorted(found))

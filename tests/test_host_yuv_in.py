@@ -6,14 +6,13 @@ exported symbols, the CLI's usage errors and the new kernel's code object."""
 import math
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
+import code_object
 import yuv_in_ref as ref
 import yuv_ref as out_ref
-from test_abi_library import LLVM_BIN, _gfx950_code_object
 from view_rows import run_cli
 
 # (Kr, Kb) of Y = Kr·R + (1 − Kr − Kb)·G + Kb·B:  ITU-R BT.709 / BT.601
@@ -391,37 +390,20 @@ def test_cli_help_names_the_flags(native):
 
 # ---- the code object --------------------------------------------------------------------------------------------------------------------------
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(LLVM_BIN, "llvm-readelf")), reason="ROCm LLVM tools not installed")
-def test_yuv420_expand_uses_no_scratch_no_spills_and_no_lds(native, tmp_path):
+@pytest.mark.skipif(not code_object.have_tools(), reason="ROCm LLVM tools not installed")
+def test_yuv420_expand_uses_no_scratch_no_spills_and_no_lds(native):
     """From the code object's notes: both I420 instantiations of yuvs_expand (csrc/hip/yuv_surfaces.hpp), the kernel behind
     lfi_upload_images_yuv420, exist, use no scratch and no LDS and spill nothing; from its code: no atomics, no byte or short stores — a lane's two runs of 32 bytes leave as four 16-byte stores (ragged
     blocks: dwords) — Y arrives as two 8-byte loads, chroma as dwords: one per plane (nearest), nine per plane (bilinear)."""
-    co = _gfx950_code_object(native, tmp_path)
-    notes = subprocess.run([os.path.join(LLVM_BIN, "llvm-readelf"), "--notes", co], capture_output=True, text=True, check=True).stdout
-    kernels, name = {}, None
-    keys = (".private_segment_fixed_size", ".vgpr_spill_count", ".sgpr_spill_count", ".vgpr_count", ".group_segment_fixed_size")
-    for line in notes.splitlines():
-        line = line.strip()
-        if line.startswith(".name:"):
-            name = line.split(":", 1)[1].strip()
-            kernels[name] = {}
-        elif name and ":" in line and line.split(":")[0] in keys:
-            kernels[name][line.split(":")[0]] = int(line.split(":")[1])
-    expand = {k: v for k, v in kernels.items() if "yuvs_expandILi0E" in k}   # <YUVS_I420, NEAREST>
+    kernels = code_object.kernels(native.build.HIP_LIB)
+    expand = {k: v for k, v in code_object.named(kernels, "yuvs_expand").items() if "yuvs_expandILi0E" in k}   # <YUVS_I420, NEAREST>
     assert len(expand) == 2, sorted(expand)
     for k, v in expand.items():
         assert v[".private_segment_fixed_size"] == 0 and v[".vgpr_spill_count"] == 0 and v[".sgpr_spill_count"] == 0, (k, v)
         assert v[".group_segment_fixed_size"] == 0 and v[".vgpr_count"] <= 128, (k, v)   # at least four waves per SIMD
-    dis = subprocess.run([os.path.join(LLVM_BIN, "llvm-objdump"), "-d", co], capture_output=True, text=True, check=True).stdout
-    cur, bodies = None, {}
-    for line in dis.splitlines():
-        if line.endswith(">:"):
-            cur = line.split("<")[1][:-2]
-        elif cur in expand:
-            bodies.setdefault(cur, []).append(line)
+    bodies = {k: v for k, v in code_object.bodies(native.build.HIP_LIB).items() if k in expand}
     assert set(bodies) == set(expand)
-    for k, body in bodies.items():
-        text = "\n".join(body)
+    for k, text in bodies.items():
         assert "atomic" not in text and "scratch_" not in text and "ds_" not in text, k
         assert "global_store_byte" not in text and "global_store_short" not in text, k
         # the channels are clamped before their shift: clamp(v >> 20, 0, 255) compiled to v_ashr_pk_u8_i32 for two channels with the third

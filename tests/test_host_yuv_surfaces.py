@@ -5,14 +5,13 @@ object."""
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
+import code_object
 import yuv_in_ref as in_ref
 import yuv_surfaces_ref as sref
-from test_abi_library import LLVM_BIN, _gfx950_code_object
 from view_rows import run_cli
 
 SIZES = [(8, 2), (18, 5), (520, 6), (24, 10), (1, 1)]
@@ -188,23 +187,13 @@ def test_cli_help_names_the_flag(native):
 
 # ---- the code object ------------------------------------------------------------------------------------------------------------------------------
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(LLVM_BIN, "llvm-readelf")), reason="ROCm LLVM tools not installed")
-def test_the_eight_instantiations_use_no_scratch_no_spills_and_no_lds(native, tmp_path):
+@pytest.mark.skipif(not code_object.have_tools(), reason="ROCm LLVM tools not installed")
+def test_the_eight_instantiations_use_no_scratch_no_spills_and_no_lds(native):
     """From the code object's notes only: yuvs_expand<FORMAT, NEAREST> and yuvs_convert<PLANAR, FORMAT> (csrc/hip/yuv_surfaces.hpp) exist four
     times each, use no scratch and no LDS, spill nothing and stay within 128 VGPRs (at least four waves per SIMD)."""
-    co = _gfx950_code_object(native, tmp_path)
-    notes = subprocess.run([os.path.join(LLVM_BIN, "llvm-readelf"), "--notes", co], capture_output=True, text=True, check=True).stdout
-    kernels, name = {}, None
-    keys = (".private_segment_fixed_size", ".vgpr_spill_count", ".sgpr_spill_count", ".vgpr_count", ".group_segment_fixed_size")
-    for line in notes.splitlines():
-        line = line.strip()
-        if line.startswith(".name:"):
-            name = line.split(":", 1)[1].strip()
-            kernels[name] = {}
-        elif name and ":" in line and line.split(":")[0] in keys:
-            kernels[name][line.split(":")[0]] = int(line.split(":")[1])
+    kernels = code_object.kernels(native.build.HIP_LIB)
     for stem, variants in (("yuvs_expand", ("ILi0ELb0E", "ILi0ELb1E", "ILi1ELb0E", "ILi1ELb1E")), ("yuvs_convert", ("ILb0ELi0E", "ILb0ELi1E", "ILb1ELi0E", "ILb1ELi1E"))):
-        found = {k: v for k, v in kernels.items() if stem in k}
+        found = code_object.named(kernels, stem)
         assert len(found) == 4, sorted(found)
         for variant in variants:
             assert any(variant in k for k in found), (stem, variant, sorted(found))

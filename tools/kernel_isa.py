@@ -1,20 +1,17 @@
 """Instruction mix of one kernel of the built library (gfx950 code object).  usage: python tools/kernel_isa.py <mangled-name-substring> [top N] [--dump]"""
-import subprocess, struct, sys, re, os
+import os
+import re
+import sys
 from collections import Counter
-lib = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "lfinterpolator_amd", "lib", "liblfi_hip.so")
-data = open(lib, 'rb').read()
-i = data.find(b"__CLANG_OFFLOAD_BUNDLE__")
-n = struct.unpack_from("<Q", data, i + 24)[0]
-off = i + 32
-for _ in range(n):
-    o, sz, tl = struct.unpack_from("<QQQ", data, off); off += 24
-    triple = data[off:off + tl]; off += tl
-    if b"gfx950" in triple:
-        open('/tmp/lfi_lib.co', 'wb').write(data[i + o:i + o + sz])
-dis = subprocess.run(['/opt/rocm/lib/llvm/bin/llvm-objdump', '-d', '--mcpu=gfx950', '/tmp/lfi_lib.co'], capture_output=True, text=True).stdout
+
+ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import code_object  # noqa: E402
+
+lib = os.path.join(ROOT, "lfinterpolator_amd", "lib", "liblfi_hip.so")
 name = sys.argv[1]
-sec = dis[dis.index(name):]
-sec = sec[:sec.index('\n\n', 100)]
+symbol, body = next((k, v) for k, v in code_object.bodies(lib).items() if name in k)   # the first in the code object's order
+sec = symbol[symbol.index(name):] + ">:\n" + body
 if "--dump" in sys.argv:
     print("\n".join(l.split('//')[0].rstrip() for l in sec.splitlines()))
     sys.exit(0)
