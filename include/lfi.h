@@ -647,6 +647,35 @@ int lfi_download_views_yuv(lfi_ctx *ctx, int v0, int n, int matrix, int range, c
  * matrix or range; dst refused by lfi_yuv_surfaces_check for (QW, QH, 1); LFI_MEM_DEVICE with a pointer that is not device memory of the
  * context's device or whose allocation ends before the frame does. */
 int lfi_download_quilt_yuv(lfi_ctx *ctx, int tiles_x, int tiles_y, int v0, int tile_w, int tile_h, int matrix, int range, const lfi_yuv_surfaces *dst);
+/* RGB-D VIDEO frames: a view and a focus map side by side in one 8-bit YUV 4:2:0 frame — the colour image with its depth map beside it, as
+ * holographic players ("RGB-D photo / video") and 2D-plus-depth displays take it.  Views [v0, v0 + n) become frames [0, n) of dst, each
+ * 2*tile_w x tile_h: the colour in the left half, the depth in the right half.  No new arithmetic.  For frame k:
+ *  - V is view v0 + k.
+ *  - M is the R byte plane of the chosen map, W x H: without LFI_RGBD_VIEW_MAPS the context's map map_k (0 or 1, what lfi_download_map
+ *    delivers), the same for every frame; with it, view v0 + k's own map map_k of lfi_view_focus_maps (what lfi_download_view_map delivers).
+ *  - d = M, or 255 - M with LFI_RGBD_INVERT.  The inversion happens BEFORE the resize: 255 - mean rounds ties the other way.
+ *  - D is the RGBA image (d, d, d, 255).
+ *  - Frame k is what lfi_download_quilt_yuv's definition makes of the 2 x 1 quilt whose tiles are V and D: the exact area filter to
+ *    tile_w x tile_h, then lfi_download_views_yuv420's arithmetic on the 2*tile_w x tile_h image taken as one view.
+ * Consequences of the coefficient tables, which the kernel relies on (csrc/hip/rgbd_yuv.hpp; the grey image D is never made):
+ *  - the resized D is grey with value s, the rounded area mean of d;
+ *  - the depth half's luma is Y = y_off + ((S*s + 2^15) >> 16) with S = 56284 (limited range) or 65536 (full range, so Y = s);
+ *  - every chroma sample of the depth half is exactly 128: the chroma coefficients sum to 0 and (2^25 + 2^17) >> 18 = 128.
+ * Limits: tile_w and tile_h EVEN (no 2 x 2 block may straddle the halves, and encoders take even sizes) and within
+ * lfi_download_quilt_scaled's limits; map_k 0 or 1; no flag bits other than the two below.
+ * dst is routed exactly as lfi_download_views_yuv routes n frames: LFI_MEM_DEVICE with base, frame_stride, pitches and offsets multiples of
+ * 16 is written by the kernel itself; everything else goes through device frames the context owns (lfi_memory.workspace_bytes,
+ * LFI_POISON_SCRATCH) and copies of the planes' own bytes.  ONLY the planes' own bytes are written: padding and gaps keep their values.
+ * ONE kernel launch makes all 2n halves; both view layouts, and attached views, are read in place; no view and no map is written.
+ * Synchronous.  The context's maps are read in the order lfi_download_map reads them (behind the filter that makes map 1), per-view maps
+ * in the order lfi_download_view_map reads them.
+ * LFI_EINVAL, the context usable, dst and lfi_memory.workspace_bytes untouched: nothing rendered; a row window; n < 1 or views outside
+ * [0, views); an odd or out-of-range tile size; a bad map_k or unknown flags; LFI_RGBD_VIEW_MAPS while the per-view maps are not in use (no
+ * successful lfi_view_focus_maps for the current parameters); an unknown matrix or range; dst refused by
+ * lfi_yuv_surfaces_check(dst, 2*tile_w, tile_h, n); LFI_MEM_DEVICE with a pointer that is not device memory of the context's device or
+ * whose allocation ends before the last frame does. */
+enum { LFI_RGBD_INVERT = 1u, LFI_RGBD_VIEW_MAPS = 2u };
+int lfi_download_rgbd_yuv(lfi_ctx *ctx, int v0, int n, int map_k, uint32_t flags, int tile_w, int tile_h, int matrix, int range, const lfi_yuv_surfaces *dst);
 int lfi_upload_map(lfi_ctx *ctx, int k, const uint8_t *rgba, size_t pitch_bytes); /* tests: inject a focus map */
 /* view v's map k (0 or 1) of the per-view maps (lfi_view_focus_maps).  Synchronous.  The upload is a test hook like lfi_upload_map (it
  * allocates the per-view maps if needed and does not put them in use: renders read them after a successful lfi_view_focus_maps). */

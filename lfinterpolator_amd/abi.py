@@ -25,6 +25,8 @@ LFI_POISON_FOCUS_WORKSPACE = 8
 LFI_POISON_DERIVED = 16
 LFI_POISON_VIEW_MAPS = 32
 LFI_LENT_INVERT = 1
+LFI_RGBD_INVERT = 1
+LFI_RGBD_VIEW_MAPS = 2
 LFI_YUV_BT709 = 0
 LFI_YUV_BT601 = 1
 LFI_YUV_LIMITED = 0
@@ -55,7 +57,7 @@ ABI_SYMBOLS = [
     "lfi_keep_views", "lfi_compare_views", "lfi_set_focus_steps", "lfi_focus_steps", "lfi_download_native",
     "lfi_download_views_yuv420", "lfi_render_stream_yuv420", "lfi_upload_images_yuv420",
     "lfi_yuv_surfaces_check", "lfi_yuv_surfaces_packed", "lfi_upload_images_yuv", "lfi_download_views_yuv",
-    "lfi_download_quilt_yuv",
+    "lfi_download_quilt_yuv", "lfi_download_rgbd_yuv",
     "lfi_upload_images_yuv_derived", "lfi_debug_derived_layout", "lfi_debug_download_derived",
 ]
 
@@ -234,6 +236,7 @@ def load_hip_library() -> C.CDLL:
         "lfi_upload_images_yuv": (i, [vp, i, i, i, i, i, C.POINTER(YuvSurfaces)]),
         "lfi_download_views_yuv": (i, [vp, i, i, i, i, C.POINTER(YuvSurfaces)]),
         "lfi_download_quilt_yuv": (i, [vp, i, i, i, i, i, i, i, C.POINTER(YuvSurfaces)]),
+        "lfi_download_rgbd_yuv": (i, [vp, i, i, i, C.c_uint32, i, i, i, i, C.POINTER(YuvSurfaces)]),
         "lfi_upload_images_yuv_derived": (i, [vp, i, i, i, i, i, C.POINTER(YuvSurfaces)]),
         "lfi_debug_derived_layout": (i, [vp, C.POINTER(DerivedLayout), vp]),
         "lfi_debug_download_derived": (i, [vp, i, i, vp]),
@@ -738,6 +741,13 @@ class Context:
         quilt; a device surface whose base, pitches and offsets are multiples of 16 is written by the kernel itself."""
         self._check(self._lib.lfi_download_quilt_yuv(self._h, tiles_x, tiles_y, v0, tile_w, tile_h, YUV_MATRICES.get(matrix, matrix),
                                                      YUV_RANGES.get(range, range), C.byref(surfaces) if surfaces is not None else None))
+
+    def download_rgbd_yuv(self, v0: int, n: int, map_k: int, flags: int, tile_w: int, tile_h: int, matrix, range, surfaces: YuvSurfaces) -> None:
+        """views [v0, v0 + n) with a focus map beside each as n YUV 4:2:0 frames of 2·tile_w × tile_h in `surfaces` (lfi_download_rgbd_yuv): RGB-D
+        video, the colour left, the depth right.  The depth is the R byte of the context's map map_k, or with LFI_RGBD_VIEW_MAPS of each view's
+        own map map_k; LFI_RGBD_INVERT takes 255 − it before the resize.  Tile sizes are even; only the planes' own bytes are written."""
+        self._check(self._lib.lfi_download_rgbd_yuv(self._h, v0, n, map_k, flags, tile_w, tile_h, YUV_MATRICES.get(matrix, matrix),
+                                                    YUV_RANGES.get(range, range), C.byref(surfaces) if surfaces is not None else None))
 
     def render_stream_yuv420(self, method, weights: np.ndarray, out: np.ndarray | None = None, all_focus: bool = False, matrix="709",
                              range="limited") -> np.ndarray:

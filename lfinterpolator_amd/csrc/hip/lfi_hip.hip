@@ -10,6 +10,7 @@
 #include "lfi_focus_sched.hpp"
 #include "quilt_scaled.hpp"
 #include "quilt_yuv.hpp"
+#include "rgbd_yuv.hpp"
 #include "native_image.hpp"
 #include "yuv420.hpp"
 #include "yuv420_upload.hpp"
@@ -2398,6 +2399,51 @@ int lfi_download_quilt_yuv(lfi_ctx *ctx, int tiles_x, int tiles_y, int v0, int t
         LFI_HIP(ctx, enqueue_yuv_convert(ctx->stream, quilt, false, 1, matrix, range, dst->format, d.frames));
     }
     return finish_yuv_delivery(ctx, *dst, 1, d);
+}
+
+int lfi_download_rgbd_yuv(lfi_ctx *ctx, int v0, int n, int map_k, uint32_t flags, int tile_w, int tile_h, int matrix, int range, const lfi_yuv_surfaces *dst)
+{
+    static const char *who = "lfi_download_rgbd_yuv";
+    if(!ctx)
+        return LFI_EINVAL;
+    // the views and the coefficient set as lfi_download_views_yuv refuses them (nothing rendered, the range of views, a row window, matrix
+    // and range), the tiles as lfi_download_quilt_scaled does
+    if(int rc = check_yuv_download(ctx, who, v0, n, matrix, range))
+        return rc;
+    if(int rc = check_scaled_tiles(ctx, tile_w, tile_h))
+        return rc;
+    if(tile_w % 2 || tile_h % 2)
+        return fail(ctx, LFI_EINVAL, std::string(who) + ": tile_w and tile_h must be even: no 2x2 chroma block may straddle the colour and the depth half");
+    if(map_k < 0 || map_k > 1 || (flags & ~(uint32_t)(LFI_RGBD_INVERT | LFI_RGBD_VIEW_MAPS)))
+        return fail(ctx, LFI_EINVAL, std::string(who) + ": bad map index (0 or 1) or unknown flags (LFI_RGBD_INVERT, LFI_RGBD_VIEW_MAPS)");
+    const bool view_maps = flags & LFI_RGBD_VIEW_MAPS;
+    if(view_maps && (!ctx->view_maps_set || !ctx->view_maps || ctx->view_maps.bytes() < plane_bytes(ctx) * 2 * ctx->views_n))
+        return fail(ctx, LFI_EINVAL, std::string(who) + ": LFI_RGBD_VIEW_MAPS needs the per-view focus maps in use (lfi_view_focus_maps)");
+    if(!view_maps && !ctx->maps)
+        return fail(ctx, LFI_EINVAL, std::string(who) + ": the context has no focus maps");
+    size_t extent = 0;
+    if(const char *fault = yuv_surfaces_fault(dst, 2 * tile_w, tile_h, n, &extent))
+        return fail(ctx, LFI_EINVAL, std::string(who) + ": " + fault);
+    // n frames routed as lfi_download_views_yuv routes them: the caller's surfaces in place, or the staged frames and copies of their bytes
+    YuvDelivery d;
+    if(int rc = open_yuv_delivery(ctx, who, *dst, extent, 2 * tile_w, tile_h, n, false, &d))
+        return rc;
+    if(!view_maps)
+        if(int rc = join_filter(ctx)) // map 1 may still be in the making on the side stream; the per-view maps are made on the compute stream
+            return rc;
+    bool planar;
+    lfi::RgbdYuvArgs a{};
+    a.q.src = rendered_views(ctx, 0, &planar);
+    a.q.tile_w = tile_w, a.q.tile_h = tile_h;
+    a.q.v0 = v0, a.q.first = 0, a.q.tiles_x = 2;
+    // the map as views of one RGBA plane each: the context's map for every frame, or plane map_k of each view's pair
+    const size_t plane = plane_bytes(ctx);
+    a.map = view_maps ? lfi::ViewsSrc{ctx->view_maps.get() + plane * (2 * (size_t)v0 + map_k), 2 * plane, (uint32_t)ctx->width, (uint32_t)ctx->height, 0u}
+                      : lfi::ViewsSrc{ctx->maps.get() + plane * map_k, 0, (uint32_t)ctx->width, (uint32_t)ctx->height, 0u};
+    a.s = d.frames, a.k = lfi::YUV_COEFFS[matrix * 2 + range];
+    a.flip = flags & LFI_RGBD_INVERT ? 255u : 0u;
+    LFI_HIP(ctx, lfi::launch_rgbd_yuv_scale(ctx->stream, planar, dst->format, a, n));
+    return finish_yuv_delivery(ctx, *dst, n, d);
 }
 
 int lfi_download_native(lfi_ctx *ctx, const lfi_lenticular *lens, int v0, int out_w, int out_h, int tile_w, int tile_h, uint8_t *rgba, size_t pitch_bytes)

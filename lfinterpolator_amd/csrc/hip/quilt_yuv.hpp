@@ -52,16 +52,18 @@ __device__ __forceinline__ uint32_t quilt_yuv_pair(const uint32_t v)
     return uint32_t(__builtin_amdgcn_mov_dpp(int(v), 0xB1, 0xf, 0xf, false)); // quad_perm [1, 0, 3, 2]
 }
 
+// One workgroup's rectangle of ONE tile — view v0 + v resized to tile `tile` of a frame s that is tiles_x tiles wide — both phases: the
+// body of quilt_yuv_scale, and of the colour half of rgbd_yuv_scale (rgbd_yuv.hpp).  Called by every thread of the workgroup; col is its
+// 12 KiB.  The arguments by VALUE: with references into the kernel's argument block the compiler keeps quilt_yuv_scale's I420
+// instantiations at 102 / 76 registers instead of 96 / 72
 template <bool PLANAR, int FORMAT>
-__global__ void __launch_bounds__(QUILT_SCALE_THREADS) quilt_yuv_scale(const QuiltYuvArgs a)
+__device__ __forceinline__ void quilt_yuv_tile(const QuiltScaleArgs q, const YuvSurfaces s, const YuvCoeffs kc, const int v, const int tile,
+                                               const int tiles_x, uint32_t (*col)[QUILT_SCALE_PIECE])
 {
-    __shared__ __attribute__((aligned(16))) uint32_t col[3][QUILT_SCALE_PIECE];
-    const QuiltScaleArgs &q = a.q;
     const uint32_t tw = q.tile_w, th = q.tile_h;
     const uint32_t t = threadIdx.x;
-    const int i = blockIdx.z;
-    const uint32_t trow = (uint32_t)(i / q.tiles_x), tcol = (uint32_t)(i % q.tiles_x);
-    const uint8_t *view = q.src.base + (size_t)(q.v0 + i) * q.src.view_stride;
+    const uint32_t trow = (uint32_t)(tile / tiles_x), tcol = (uint32_t)(tile % tiles_x);
+    const uint8_t *view = q.src.base + (size_t)(q.v0 + v) * q.src.view_stride;
     QuiltScaleChunk c;
     if(!quilt_scale_chunk(q, c))
         return;
@@ -85,30 +87,39 @@ __global__ void __launch_bounds__(QUILT_SCALE_THREADS) quilt_yuv_scale(const Qui
         {
             // the column's two pixels; every lane takes part in the exchange (a lane that owns no column holds alpha only and stores nothing)
             const uint32_t p0 = upper[k], p1 = out[k];
-            const uint32_t y = yuv_luma(a.k, p0 & 0xffu, (p0 >> 8) & 0xffu, (p0 >> 16) & 0xffu) |
-                               (yuv_luma(a.k, p1 & 0xffu, (p1 >> 8) & 0xffu, (p1 >> 16) & 0xffu) << 16);
+            const uint32_t y = yuv_luma(kc, p0 & 0xffu, (p0 >> 8) & 0xffu, (p0 >> 16) & 0xffu) |
+                               (yuv_luma(kc, p1 & 0xffu, (p1 >> 8) & 0xffu, (p1 >> 16) & 0xffu) << 16);
             const uint32_t rb = (p0 & 0x00ff00ffu) + (p1 & 0x00ff00ffu); // ΣR | ΣB << 16 of the column: ≤ 510 each
             const uint32_t g = ((p0 >> 8) & 0xffu) + ((p1 >> 8) & 0xffu);
             const uint32_t y_n = quilt_yuv_pair(y), rb_n = quilt_yuv_pair(rb), g_n = quilt_yuv_pair(g);
             if(stores && c.own[k])
             {
                 const uint32_t fx = fx0 + uint32_t(k) * QUILT_SCALE_THREADS; // even
-                uint8_t *y_row = a.s.base + (size_t)fy * a.s.y_pitch + fx;
+                uint8_t *y_row = s.base + (size_t)fy * s.y_pitch + fx;
                 *reinterpret_cast<uint16_t *>(y_row) = (uint16_t)((y & 0xffu) | ((y_n & 0xffu) << 8));
-                *reinterpret_cast<uint16_t *>(y_row + a.s.y_pitch) = (uint16_t)(((y >> 16) & 0xffu) | ((y_n >> 16) << 8));
+                *reinterpret_cast<uint16_t *>(y_row + s.y_pitch) = (uint16_t)(((y >> 16) & 0xffu) | ((y_n >> 16) << 8));
                 const uint32_t sum = rb + rb_n, sr = sum & 0xffffu, sb = sum >> 16, sg = g + g_n; // over the four pixels: ≤ 1020
-                const uint32_t cb = yuv_chroma(a.k.cb, sr, sg, sb), cr = yuv_chroma(a.k.cr, sr, sg, sb);
-                const size_t c_row = (size_t)(fy >> 1) * a.s.c_pitch;
+                const uint32_t cb = yuv_chroma(kc.cb, sr, sg, sb), cr = yuv_chroma(kc.cr, sr, sg, sb);
+                const size_t c_row = (size_t)(fy >> 1) * s.c_pitch;
                 if constexpr(FORMAT == YUVS_NV12)
-                    *reinterpret_cast<uint16_t *>(a.s.base + a.s.c_offset + c_row + fx) = (uint16_t)(cb | (cr << 8));
+                    *reinterpret_cast<uint16_t *>(s.base + s.c_offset + c_row + fx) = (uint16_t)(cb | (cr << 8));
                 else
                 {
-                    a.s.base[a.s.c_offset + c_row + (fx >> 1)] = (uint8_t)cb;
-                    a.s.base[a.s.cr_offset + c_row + (fx >> 1)] = (uint8_t)cr;
+                    s.base[s.c_offset + c_row + (fx >> 1)] = (uint8_t)cb;
+                    s.base[s.cr_offset + c_row + (fx >> 1)] = (uint8_t)cr;
                 }
             }
         }
     }
+}
+
+template <bool PLANAR, int FORMAT>
+__global__ void __launch_bounds__(QUILT_SCALE_THREADS) quilt_yuv_scale(const QuiltYuvArgs a)
+{
+    __shared__ __attribute__((aligned(16))) uint32_t col[3][QUILT_SCALE_PIECE];
+    const QuiltScaleArgs &q = a.q;
+    const int i = blockIdx.z;
+    quilt_yuv_tile<PLANAR, FORMAT>(q, a.s, a.k, i, i, q.tiles_x, col);
 }
 
 // Enqueues the ONE quilt_yuv_scale launch for the n = tiles_x·tiles_y tiles of a quilt.  The caller has checked what launch_quilt_scale's

@@ -159,6 +159,11 @@ void Interpolator::finish()
         std::unique_ptr<lfi::Y4mWriter> writer = std::move(quiltY4mWriter);
         writer->close();
     }
+    if(rgbdY4mWriter)
+    {
+        std::unique_ptr<lfi::Y4mWriter> writer = std::move(rgbdY4mWriter);
+        writer->close();
+    }
     if(nv12File.is_open())
     {
         nv12File.close();
@@ -236,6 +241,25 @@ void Interpolator::interpolate(std::string outputPath, std::string trajectory, f
             throw std::runtime_error("A quilt video needs a quilt (-q cols,rows)!");
         if(gpuCount > 1)
             throw std::runtime_error("A quilt video frame needs every view in one context: it works on one GPU only!");
+    }
+    if(!rgbdY4mPath.empty())
+    {
+        // everything is checked before anything is rendered or written
+        if(!(inRange > 0) || autofocus)
+            throw std::runtime_error("An RGB-D video frame needs a focus map: all-focus rendering (-r greater than zero)!");
+        if(gpuCount > 1)
+            throw std::runtime_error("An RGB-D video frame reads the view and the map in one context: it works on one GPU only!");
+        if(rgbdView < -1 || rgbdView >= viewCount)
+            throw std::runtime_error("The view of the RGB-D video (--rgbd-view) has to be one of the " + std::to_string(viewCount) + " rendered views!");
+        const lfi::IVec2 tile = rgbdTile.x > 0 ? rgbdTile : lfi::IVec2{resolution.x, resolution.y};
+        if(tile.x < 1 || tile.y < 1 || tile.x > resolution.x || tile.y > resolution.y)
+            throw std::runtime_error("The RGB-D tile size (--rgbd-tile) has to be between 1x1 and the views' " + std::to_string(resolution.x) + "x" +
+                                     std::to_string(resolution.y) + " pixels (views are only scaled down)!");
+        if(tile.x % 2 != 0 || tile.y % 2 != 0)
+            throw std::runtime_error("The RGB-D tile size (--rgbd-tile) has to be even in width and height, it is " + std::to_string(tile.x) + "x" +
+                                     std::to_string(tile.y) + "!");
+        if(rgbdMap != 0 && rgbdMap != 1)
+            throw std::runtime_error("The map of the RGB-D video (--rgbd-map) is 0 or 1!");
     }
     if(nativeSize.x != 0 || nativeSize.y != 0)
     {
@@ -642,6 +666,41 @@ void Interpolator::storeResults(std::string path)
             if(!quiltY4mWriter)
                 quiltY4mWriter = std::make_unique<lfi::Y4mWriter>(quiltY4mPath, quiltW, quiltH, y4mFps.x, y4mFps.y, yuvRange == LFI_YUV_FULL);
             quiltY4mWriter->writeFrame(frame);
+        }
+        catch(...)
+        {
+            if(framePinned)
+                lfi_free_pinned(frame);
+            throw;
+        }
+        if(framePinned)
+            lfi_free_pinned(frame);
+    }
+    if(!rgbdY4mPath.empty())
+    {
+        std::cout << "Storing RGB-D video frame..." << std::endl;
+        // the view and the map resized and converted on the device (lfi_download_rgbd_yuv): the one frame arrives as tight I420 in a page-locked buffer
+        const lfi::IVec2 tile = rgbdTile.x > 0 ? rgbdTile : lfi::IVec2{resolution.x, resolution.y};
+        const int frameW = 2 * tile.x, frameH = tile.y;
+        const size_t frameBytes = lfi::y4mFrameBytes(frameW, frameH);
+        uint8_t *frame = nullptr;
+        const bool framePinned = lfi_alloc_pinned(frameBytes, reinterpret_cast<void **>(&frame)) == LFI_OK;
+        std::vector<uint8_t> pageableFrame;
+        if(!framePinned)
+        {
+            pageableFrame.resize(frameBytes);
+            frame = pageableFrame.data();
+        }
+        try
+        {
+            lfi_yuv_surfaces surface{};
+            check(lfi_yuv_surfaces_packed(LFI_YUV_I420, LFI_MEM_HOST, frame, frameW, frameH, &surface));
+            const uint32_t flags = (rgbdInvert ? LFI_RGBD_INVERT : 0u) | (viewMaps ? LFI_RGBD_VIEW_MAPS : 0u);
+            check(lfi_download_rgbd_yuv(context, rgbdView >= 0 ? rgbdView : viewCount / 2, 1, rgbdMap, flags, tile.x, tile.y, yuvMatrix, yuvRange, &surface));
+            // one file for all time steps of a light-field video: opened by the first, appended to by the others, closed by finish()
+            if(!rgbdY4mWriter)
+                rgbdY4mWriter = std::make_unique<lfi::Y4mWriter>(rgbdY4mPath, frameW, frameH, y4mFps.x, y4mFps.y, yuvRange == LFI_YUV_FULL);
+            rgbdY4mWriter->writeFrame(frame);
         }
         catch(...)
         {

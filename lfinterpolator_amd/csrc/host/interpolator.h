@@ -77,6 +77,23 @@ class Interpolator
             yuvMatrix = matrix;
             yuvRange = range;
         }
+        // also write ONE view with a focus map beside it as one frame of a Y4M video file, 2·tile.x × tile.y: RGB-D, the colour left, the depth right
+        // (lfi_download_rgbd_yuv into a host I420 frame: one kernel resizes and converts both halves).  view: −1 = the middle one (views / 2);
+        // tile: {0, 0} = the views' size, else even and at most it; map: 0 as estimated, 1 filtered; invert: 255 − the map's value.  With
+        // setViewMaps the view's own map is stored.  Needs an all-focus render (range > 0) and one GPU; same matrix, range and rate as setY4m.
+        // The file stays open over the time steps: a light-field video gives an RGB-D video, one frame per step
+        void setRgbdY4m(std::string path, int view = -1, lfi::IVec2 tile = {0, 0}, int map = 1, bool invert = false, int fpsNum = 30, int fpsDen = 1,
+                        int matrix = LFI_YUV_BT709, int range = LFI_YUV_LIMITED)
+        {
+            rgbdY4mPath = path;
+            rgbdView = view;
+            rgbdTile = tile;
+            rgbdMap = map;
+            rgbdInvert = invert;
+            y4mFps = {fpsNum, fpsDen};
+            yuvMatrix = matrix;
+            yuvRange = range;
+        }
         // a light-field video as input (a directory of <row>_<col>.y4m files, one per camera): its frames go to the device as they are, 1.5
         // bytes per pixel from page-locked memory, and become the RGBA images there (one lfi_upload_images_yuv420 call for the grid).
         // interpolate() renders time step setInputFrame(t), 0 by default, t in [0, frameCount()); called again after another setInputFrame
@@ -97,7 +114,7 @@ class Interpolator
         // derived planar copy of the inputs (lfi_release_inputs), and every later step's frames go straight into it
         // (lfi_upload_images_yuv_derived) — less than half the device memory, one pass per step.  The files written are the same
         void setLeanInputs(bool on) { leanInputs = on; }
-        // closes the video files of setY4m, setNv12 and setQuiltY4m (interpolate() leaves them open for the next time step's views); throws when that fails
+        // closes the video files of setY4m, setNv12, setQuiltY4m and setRgbdY4m (interpolate() leaves them open for the next time step's views); throws when that fails
         void finish();
         float lastAverageTime() const { return averageTime; }
         // render on GPUs 0 … count-1 of this node: views are split into contiguous ranges, the grid is broadcast once (RCCL)
@@ -167,6 +184,11 @@ class Interpolator
         std::string nv12Path;                      // empty: no raw NV12 file
         std::string quiltY4mPath;                  // empty: no quilt video
         std::unique_ptr<lfi::Y4mWriter> quiltY4mWriter; // open from the first stored step to finish()
+        std::string rgbdY4mPath;                   // empty: no RGB-D video
+        int rgbdView{-1}, rgbdMap{1};              // -1: the middle view
+        lfi::IVec2 rgbdTile{0, 0};                 // 0: the views' size
+        bool rgbdInvert{false};
+        std::unique_ptr<lfi::Y4mWriter> rgbdY4mWriter; // open from the first stored step to finish()
         std::ofstream nv12File;                    // open from the first stored step to finish()
         std::unique_ptr<LfLoader> video;           // the input, where it is a light-field video
         int inputFrame{0}, loadedFrame{-1};        // the time step to render / the one on the device

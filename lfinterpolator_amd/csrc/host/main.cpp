@@ -4,7 +4,8 @@
 // grid; the search interval of an all-focus render found from it), --map-steps / --tile-steps (more than 32 candidates for the focus map / the focus tiles), --compare / --compare-methods (PSNR / SSIM of all views against a
 // directory of images or against the other method's render), --native / --lens / --native-tile / --native-views (the native image of a
 // lenticular display, interlaced on the GPU), --y4m / --nv12 / --fps / --yuv-matrix / --yuv-range (the views as one YUV 4:2:0 video file, converted on
-// the GPU), --quilt-y4m (the quilt as one YUV 4:2:0 video frame per time step: a quilt video), --frames / --in-matrix / --in-range / --in-chroma (a light-field video as input: a directory of per-camera Y4M files whose frames
+// the GPU), --quilt-y4m (the quilt as one YUV 4:2:0 video frame per time step: a quilt video), --rgbd-y4m / --rgbd-view / --rgbd-tile / --rgbd-map /
+// --rgbd-invert (a view with its focus map beside it as one YUV 4:2:0 video frame per time step: RGB-D video), --frames / --in-matrix / --in-range / --in-chroma (a light-field video as input: a directory of per-camera Y4M files whose frames
 // become the images on the GPU), --lean-inputs (such a video at fixed focus from the planar copy of the inputs alone) and --synthetic for runs without a dataset.
 #include <array>
 #include <iostream>
@@ -62,9 +63,14 @@ int main(int argc, char **argv)
                           "--y4m FILE - also store the views as the frames of one YUV4MPEG2 video FILE, in view order (ffmpeg -i FILE, or any player): 8-bit YUV 4:2:0 (I420, centre-sited chroma), converted on the GPU before the download - 1.5 bytes per pixel cross PCIe instead of 4; with -g every GPU converts its own views\n"
                           "--nv12 FILE - also store the views as raw NV12 frames in FILE, in view order, tightly packed (the Y plane, then one plane of interleaved Cb/Cr): what hardware encoders take; converted on the GPU like --y4m, may be given next to it, and with --frames COUNT above 1 FILE takes all steps' views; prints the ffmpeg options that open FILE (-f rawvideo -pix_fmt nv12 -s WxH -r N)\n"
                           "--quilt-y4m FILE - with -q: also store the quilt (scaled by --quilt-tile) as one frame of the YUV4MPEG2 video FILE, resized and converted to 8-bit YUV 4:2:0 on the GPU in one pass (even tile sizes) - with --frames FIRST:COUNT one frame per time step: a quilt video, what holographic players take; one GPU only\n"
-                          "--fps N[:D] - with --y4m, --nv12 or --quilt-y4m: the frame rate N/D frames per second (default=30:1)\n"
-                          "--yuv-matrix 709|601 - with --y4m, --nv12 or --quilt-y4m: the colour matrix, BT.709 or BT.601 (default=709)\n"
-                          "--yuv-range limited|full - with --y4m, --nv12 or --quilt-y4m: limited (Y 16..235, chroma 16..240) or full (0..255) range (default=limited)\n"
+                          "--rgbd-y4m FILE - with -r: also store one view with its focus map beside it as one frame of the YUV4MPEG2 video FILE, twice the tile's width: the colour left, the depth right (RGB-D, what holographic players and 2D-plus-depth displays take), both resized and converted to 8-bit YUV 4:2:0 on the GPU in one pass; the depth is the map's value as grey, and displays take white as near; with -c --view-maps the view's own map is used; with --frames FIRST:COUNT one frame per time step: an RGB-D video; one GPU only\n"
+                          "--rgbd-view N - with --rgbd-y4m: the view stored (default: the middle one, views/2)\n"
+                          "--rgbd-tile WxH - with --rgbd-y4m: resize the view and the map to W x H pixels each (the exact area filter of --quilt-tile; both even, at most the views' size; default: the views' size)\n"
+                          "--rgbd-map 0|1 - with --rgbd-y4m: the map stored, 0 as estimated or 1 filtered (default=1)\n"
+                          "--rgbd-invert - with --rgbd-y4m: store 255 minus the map's value, which swaps the near and the far end (inverted before the resize)\n"
+                          "--fps N[:D] - with --y4m, --nv12, --quilt-y4m or --rgbd-y4m: the frame rate N/D frames per second (default=30:1)\n"
+                          "--yuv-matrix 709|601 - with --y4m, --nv12, --quilt-y4m or --rgbd-y4m: the colour matrix, BT.709 or BT.601 (default=709)\n"
+                          "--yuv-range limited|full - with --y4m, --nv12, --quilt-y4m or --rgbd-y4m: limited (Y 16..235, chroma 16..240) or full (0..255) range (default=limited)\n"
                           "--frames FIRST[:COUNT] - with -i a directory of <row>_<col>.y4m files (a light-field video, one 8-bit YUV 4:2:0 file per camera): render time steps FIRST ... FIRST+COUNT-1 (default=0:1); the frames cross PCIe as they are, 1.5 bytes per pixel, and become the images on the GPU; with COUNT above 1 every step's files go to <-o>/fTTTT/ and --y4m FILE takes all steps' views in step order (with -n 1: the video of the moving scene from one virtual camera); not with --compare, --compare-methods or -g above 1 then\n"
                           "--in-matrix 709|601 - with a light-field video: the colour matrix of its files (default=709)\n"
                           "--in-range limited|full - with a light-field video: the range of its files (default: their XCOLORRANGE tag, else limited)\n"
@@ -223,9 +229,73 @@ int main(int argc, char **argv)
         return EXIT_FAILURE;
     }
 
-    if((args["--fps"] || args["--yuv-matrix"] || args["--yuv-range"]) && !args["--y4m"] && !args["--nv12"] && !args["--quilt-y4m"])
+    if((args["--rgbd-view"] || args["--rgbd-tile"] || args["--rgbd-map"] || args["--rgbd-invert"]) && !args["--rgbd-y4m"])
     {
-        std::cerr << "--fps, --yuv-matrix and --yuv-range belong to the video file: they need --y4m FILE, --nv12 FILE or --quilt-y4m FILE." << std::endl;
+        std::cerr << "--rgbd-view, --rgbd-tile, --rgbd-map and --rgbd-invert belong to the RGB-D video: they need --rgbd-y4m FILE." << std::endl;
+        return EXIT_FAILURE;
+    }
+
+    int rgbdView = -1, rgbdMap = 1, rgbdTileW = 0, rgbdTileH = 0;
+    if(args["--rgbd-y4m"])
+    {
+        if(!(args["-r"] && range > 0) || args["--autofocus"])
+        {
+            std::cerr << "--rgbd-y4m stores a view beside its focus map: it needs -r with a value greater than zero (an all-focus render, which estimates the map)." << std::endl;
+            return EXIT_FAILURE;
+        }
+        if(static_cast<std::string>(args["--rgbd-y4m"]).empty())
+        {
+            std::cerr << "--rgbd-y4m needs the name of the video file to write." << std::endl;
+            return EXIT_FAILURE;
+        }
+        if(args["-g"] && static_cast<int>(args["-g"]) > 1)
+        {
+            std::cerr << "--rgbd-y4m reads the view and the map in one context: it works on one GPU only (-g 1)." << std::endl;
+            return EXIT_FAILURE;
+        }
+        // whole numbers and nothing else
+        const auto whole = [](const std::string &t, int &out) {
+            if(t.empty() || t.size() > 9 || t.find_first_not_of("0123456789") != std::string::npos)
+                return false;
+            out = std::stoi(t);
+            return true;
+        };
+        if(args["--rgbd-tile"])
+        {
+            const std::string text = static_cast<std::string>(args["--rgbd-tile"]);
+            const size_t cut = text.find_first_of("xX");
+            if(cut == std::string::npos || !whole(text.substr(0, cut), rgbdTileW) || !whole(text.substr(cut + 1), rgbdTileH) || rgbdTileW < 1 || rgbdTileH < 1)
+            {
+                std::cerr << "--rgbd-tile expects WxH, the tile's width x height in pixels, both at least 1." << std::endl;
+                return EXIT_FAILURE;
+            }
+            if(rgbdTileW % 2 != 0 || rgbdTileH % 2 != 0)
+            {
+                std::cerr << "--rgbd-tile expects an even width and an even height: no 2x2 chroma block of the frame may straddle the colour and the depth half." << std::endl;
+                return EXIT_FAILURE;
+            }
+        }
+        const int views = args["-n"] ? static_cast<int>(args["-n"]) : LFI_REFERENCE_VIEWS;
+        if(args["--rgbd-view"] && (!whole(static_cast<std::string>(args["--rgbd-view"]), rgbdView) || rgbdView >= views))
+        {
+            std::cerr << "--rgbd-view expects the index of a rendered view, 0 to " << views - 1 << " (-n views)." << std::endl;
+            return EXIT_FAILURE;
+        }
+        if(args["--rgbd-map"])
+        {
+            const std::string text = static_cast<std::string>(args["--rgbd-map"]);
+            if(text != "0" && text != "1")
+            {
+                std::cerr << "--rgbd-map expects 0 (the map as estimated) or 1 (filtered)." << std::endl;
+                return EXIT_FAILURE;
+            }
+            rgbdMap = text == "1";
+        }
+    }
+
+    if((args["--fps"] || args["--yuv-matrix"] || args["--yuv-range"]) && !args["--y4m"] && !args["--nv12"] && !args["--quilt-y4m"] && !args["--rgbd-y4m"])
+    {
+        std::cerr << "--fps, --yuv-matrix and --yuv-range belong to the video file: they need --y4m FILE, --nv12 FILE, --quilt-y4m FILE or --rgbd-y4m FILE." << std::endl;
         return EXIT_FAILURE;
     }
 
@@ -502,6 +572,9 @@ int main(int argc, char **argv)
             interpolator->setNv12(static_cast<std::string>(args["--nv12"]), fpsNum, fpsDen, yuvMatrix, yuvRange);
         if(args["--quilt-y4m"])
             interpolator->setQuiltY4m(static_cast<std::string>(args["--quilt-y4m"]), fpsNum, fpsDen, yuvMatrix, yuvRange);
+        if(args["--rgbd-y4m"])
+            interpolator->setRgbdY4m(static_cast<std::string>(args["--rgbd-y4m"]), rgbdView, {rgbdTileW, rgbdTileH}, rgbdMap, static_cast<bool>(args["--rgbd-invert"]), fpsNum,
+                                     fpsDen, yuvMatrix, yuvRange);
         if(args["--compare"])
             interpolator->setCompareDir(static_cast<std::string>(args["--compare"]));
         if(args["--compare-methods"])
