@@ -2,8 +2,8 @@
  * lfi_oracle.c — scalar CPU restatement of the reference's shift-and-sum path.
  *
  * TEST INFRASTRUCTURE ONLY (see lfi_oracle.h): checker for tests/, smoke() and the cpu_baseline leg of
- * bench.py.  PARITY UNPINNED: no golden vectors exist in the reference and its CUDA code cannot be run
- * here; every function cites the reference lines (relative to /root/reference) whose arithmetic it restates.
+ * bench.py.  Every function cites the reference lines (relative to the reference tree) whose arithmetic it restates;
+ * the device-side ones are pinned to the reference's own kernels run on the CPU (tests/test_ref_kernels.py).
  *
  * Build: see oracle/Makefile (gcc -O2 -mfma -ffp-contract=off: explicit fmaf only, nothing contracted).
  */

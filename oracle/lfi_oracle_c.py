@@ -1,7 +1,7 @@
 """ctypes binding of the C oracle (oracle/lfi_oracle.c → oracle/build/liblfi_oracle.so).
 
 TEST INFRASTRUCTURE ONLY: used by tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg.
-PARITY UNPINNED — see oracle/lfi_oracle.h.
+PARITY: see oracle/lfi_oracle.h (the device-side functions are pinned by tests/test_ref_kernels.py).
 """
 from __future__ import annotations
 

@@ -3,9 +3,10 @@
 TEST INFRASTRUCTURE ONLY: imported by tests/ (and by tests/golden/make_golden.py) to cross-check the C oracle
 (oracle/lfi_oracle.c).  Never imported by the product package.
 
-PARITY UNPINNED: the reference ships no golden vectors and cannot be built here (CUDA); this file follows the
-reference source (citations relative to /root/reference) independently of the C restatement, vectorised over
-pixels, so that an error in one restatement shows up as a disagreement between the two.
+PARITY: this file follows the reference source (citations relative to the reference tree) independently of the C
+restatement, vectorised over pixels, so that an error in one restatement shows up as a disagreement between the two; its
+device-side functions are pinned, like the C oracle's, to the reference's own kernels run on the CPU
+(tests/test_ref_kernels.py).
 """
 from __future__ import annotations
 

@@ -1,8 +1,8 @@
 """Generates the golden fixtures in tests/golden/ from the CPU oracle (oracle/lfi_oracle.c), refusing to write
 anything the independent numpy restatement (oracle/lfi_oracle_np.py) disagrees with.
 
-PARITY UNPINNED: the reference ships no golden vectors and cannot be run in this pipeline, so these fixtures pin the
-oracle's behaviour (and through it the HIP kernels'), not the reference binary's.  Parameters follow the reference's
+These fixtures pin the oracle's behaviour (and through it the HIP kernels'), not the reference's: what the reference's own
+kernels compute is recorded in ref_kernels.npz (make_ref_kernel_golden.py), to which the oracle is pinned in turn.  Parameters follow the reference's
 README example (-t 0,0,1,1 -a 1.783 -f 0.23, default -s 3) and scripts/focusMapCompare.sh (-s 7, -t 0.071…0.93).
 
 Run from the repository root:  python tests/golden/make_golden.py

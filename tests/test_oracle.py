@@ -1,6 +1,6 @@
 """CPU: the oracle against its golden fixtures, the two restatements against each other, fp16 helpers.
 
-PARITY UNPINNED (see oracle/lfi_oracle.h): the reference has no golden vectors; these tests pin the oracle itself.
+These tests pin the oracle itself (the reference has no golden vectors); tests/test_ref_kernels.py pins it to the reference's kernels.
 """
 import os
 
