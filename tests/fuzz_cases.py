@@ -2,12 +2,14 @@
 tools/ (fuzz_parity.py, fuzz_focus.py, fuzz_allfocus.py: any number of cases, any seed).
 
 Every function renders random small shapes through the HIP library (the C-ABI) and checks them against the CPU oracle — STD and
-focus maps bit-exact, TEN_WM within one LSB of the fp16-accumulate model M16 — and returns the list of mismatches (empty = pass).
+focus maps bit-exact, TEN_WM within one LSB of the fp16-accumulate model M16 and inside the interval of the exact sum
+(tests/ten_interval.py) — and returns the list of mismatches (empty = pass).
 `L` is the lfinterpolator_amd package, `oc` the oracle binding (oracle/lfi_oracle_c.py): the checker, never the thing measured.
 """
 import numpy as np
 
 import poison
+import ten_interval
 
 TEN_TOL_LSB = 1
 
@@ -34,6 +36,7 @@ def fuzz_blend(L, oc, n_cases: int, seed: int, log=None) -> list:
         case = dict(kind="blend", cols=cols, rows=rows, W=W, H=H, V=V, focus=focus, traj=traj, effect=effect)
         want_std = oc.blend_std(lf, hp.focused_offsets, hp.offsets, hp.weights, threads=8)
         want_ten = oc.blend_ten(lf, hp.focused_offsets, hp.offsets, hp.weights, model=oc.TEN_M16, threads=8)
+        lo, hi = ten_interval.bounds(oc, lf, hp, threads=8)
         ctx = L.Context(0)
         ctx.set_grid(cols, rows, W, H)
         ctx.upload_grid(lf)
@@ -50,9 +53,10 @@ def fuzz_blend(L, oc, n_cases: int, seed: int, log=None) -> list:
             poison.render(ctx, "TEN_WM")
             full = ctx.download_views()
             d = int(np.abs(full.astype(int) - want_ten.astype(int)).max())
+            out = ten_interval.outside(full, lo, hi)
             b = poison.render(ctx, "TEN_WM", v0=v0, v1=v1)
-            if d > TEN_TOL_LSB or poison.written_outside(ctx, v0, v1, b) or not (ctx.download_views(v0, v1) == full[v0:v1]).all():
-                bad.append(dict(case, what="TEN_WM", variant=var, lsb=d, v0=v0, v1=v1))
+            if d > TEN_TOL_LSB or out or poison.written_outside(ctx, v0, v1, b) or not (ctx.download_views(v0, v1) == full[v0:v1]).all():
+                bad.append(dict(case, what="TEN_WM", variant=var, lsb=d, outside_interval=out, v0=v0, v1=v1))
         # the planar view layout: TEN_WM within one LSB of the oracle and byte-identical to the RGBA layout's default kernel, view ranges
         # included; STD bit-exact (round 4: blend_stdx writes the byte planes itself, one to four chunks of images), a view range over it too
         ctx.set_variant("TEN_WM", "auto")
@@ -70,8 +74,9 @@ def fuzz_blend(L, oc, n_cases: int, seed: int, log=None) -> list:
         b = poison.render(ctx, "STD", v0=v0, v1=v1)
         std_ok = std_ok and not poison.written_outside(ctx, v0, v1, b) and (ctx.download_views(v0, v1) == want_std[v0:v1]).all()
         d = int(np.abs(got.astype(int) - want_ten.astype(int)).max())
-        if d > TEN_TOL_LSB or not (got == want_rgba).all() or not part_ok or not std_ok:
-            bad.append(dict(case, what="planar layout", kernel=kernel, lsb=d, v0=v0, v1=v1))
+        out = ten_interval.outside(got, lo, hi)
+        if d > TEN_TOL_LSB or out or not (got == want_rgba).all() or not part_ok or not std_ok:
+            bad.append(dict(case, what="planar layout", kernel=kernel, lsb=d, outside_interval=out, v0=v0, v1=v1))
         # round 4: the quilt of a random tiling (assembled on the device, filled in two parts) is the montage of the views; and after
         # lfi_release_inputs — the planar copy is the only copy of the inputs — STD stays the oracle's and TEN_WM the same bytes
         poison.render(ctx, "TEN_WM")
@@ -170,6 +175,7 @@ def fuzz_allfocus(L, oc, n_cases: int, seed: int, log=None) -> list:
         case = dict(kind="allfocus", cols=cols, rows=rows, W=W, H=H, V=V, focus=focus, range=frange, traj=traj, effect=effect, map=kind)
         want_std = oc.blend_std(lf, hp.focused_offsets, hp.offsets, hp.weights, all_focus=True, map_plane=m, focus=hp.focus, rng=hp.range, threads=8)
         want_ten = oc.blend_ten(lf, hp.focused_offsets, hp.offsets, hp.weights, all_focus=True, map_plane=m, focus=hp.focus, rng=hp.range, threads=8)
+        lo, hi = ten_interval.bounds(oc, lf, hp, all_focus=True, map_plane=m, focus=hp.focus, rng=hp.range, threads=8)
         ctx = L.Context(0)
         ctx.set_grid(cols, rows, W, H)
         ctx.upload_grid(lf)
@@ -181,9 +187,11 @@ def fuzz_allfocus(L, oc, n_cases: int, seed: int, log=None) -> list:
             poison.render(ctx, "STD", all_focus=True)
             ok_std = bool((ctx.download_views() == want_std).all())
             poison.render(ctx, "TEN_WM", all_focus=True)
-            d = int(np.abs(ctx.download_views().astype(int) - want_ten.astype(int)).max())
-            if not ok_std or d > TEN_TOL_LSB:
-                bad.append(dict(case, what="all-focus", layout=layout, std_exact=ok_std, lsb=d, kernel=ctx.last_kernel_name()))
+            got = ctx.download_views()
+            d = int(np.abs(got.astype(int) - want_ten.astype(int)).max())
+            out = ten_interval.outside(got, lo, hi)
+            if not ok_std or d > TEN_TOL_LSB or out:
+                bad.append(dict(case, what="all-focus", layout=layout, std_exact=ok_std, lsb=d, outside_interval=out, kernel=ctx.last_kernel_name()))
             if cols * rows > 128 and layout == "rgba":
                 # three or four chunks of images: blend_afs (every sample gathered once; round 4) must give the same bytes
                 ctx.set_variant("STD", "filtered_gather_once")

@@ -3,8 +3,9 @@ instantiated for, compared against the oracle under poison (tests/poison.py).
 
 One table.  Each row names a shape, a view range, a method, all-focus or not, the view layout, the flags, the variant and the kind of
 weights, and the kernel that lfi_last_kernel_name() must report for it.  Every row renders twice, under both poison bytes (so both sweep
-directions of the kernels that alternate them): STD bit-exact, TEN_WM within one LSB of the oracle's M16 model, the per-batch rounding
-debug mode (LFI_FLAG_TEN_ROUND_PER_BATCH) byte for byte M16; views outside the range must still hold the poison.
+directions of the kernels that alternate them): STD bit-exact, TEN_WM within one LSB of the oracle's M16 model and inside the interval of
+the exact sum (tests/ten_interval.py; rows with `dyadic` weights: no accumulation error is possible, so byte for byte the exact model), the
+per-batch rounding debug mode (LFI_FLAG_TEN_ROUND_PER_BATCH) byte for byte M16; views outside the range must still hold the poison.
 
 Two more columns follow from the kernel and the layout: whether the launch reads the derived planar copy of the inputs (READS_COPY), and
 whether, in the planar view layout, it goes through the RGBA scratch copy and the conversion (every kernel outside WRITES_PLANES).  The
@@ -23,6 +24,7 @@ import numpy as np
 import pytest
 
 import poison
+import ten_interval
 from conftest import ROOT
 
 TEN_TOL_LSB = 1
@@ -50,11 +52,13 @@ class Row:
     layout: str          # "rgba" / "planar"
     flags: int
     variant: str         # of `method`; "auto" = the default
-    weights: str         # "default" (build_params: in [0, 2), sums ≤ 2) / "wide" (one weight of 2.5: outside [0, 2))
+    weights: str         # "default" (build_params: in [0, 2), sums ≤ 2) / "wide" (one weight of 2.5: outside [0, 2)) /
+                         # "dyadic" (the default ones floored to multiples of 2^-12: every fp32 partial sum is exact, see row_inputs)
     expect: str          # lfi_last_kernel_name()
     persistent: int = 0  # pixels per tile of the kernel when the row must run its tile loop, else 0
     order: str = ""      # blend_p3, planar layout: "plain" / "xcd" tile order (see test_dispatch_row)
     far: bool = False    # one image's focused x offset beyond the derived copy's reach (4·W + 4096): the route without the copy
+    quant: int = 1       # the input bytes rounded down to multiples of it (dyadic rows: 16 makes fp16 ties and integer sums common)
 
     @property
     def n(self):
@@ -74,9 +78,9 @@ class Row:
 
 
 def R(name, grid, W, H, V, method, expect, v=None, af=False, layout="rgba", flags=0, variant="auto", weights="default", persistent=0, order="",
-      far=False):
+      far=False, quant=1):
     v0, v1 = v if v else (0, V)
-    return Row(name, grid[0], grid[1], W, H, V, v0, v1, method, af, layout, flags, variant, weights, expect, persistent, order, far)
+    return Row(name, grid[0], grid[1], W, H, V, v0, v1, method, af, layout, flags, variant, weights, expect, persistent, order, far, quant)
 
 
 G1, G1S, G2, G3, G4 = (8, 8), (3, 3), (9, 9), (12, 12), (15, 15)   # k_pad 64, 16, 80..128 (2 chunks), 144 (3), 225 -> 240 (4)
@@ -163,6 +167,15 @@ MATRIX = [
     # ---- the default TEN_WM route when the derived copy cannot serve the offsets ----
     R("persist_ten_copy_out_of_reach", G1, 130, 4, 9, "TEN_WM", "blend_persist<TEN_WM>", far=True),
     R("scratch_persist_ten_copy_out_of_reach", G2, 130, 4, 9, "TEN_WM", "blend_persist<TEN_WM>", layout="planar", far=True),
+    # ---- TEN_WM with no accumulation error at all: byte for byte the exact sum's, fp16 ties and integer sums included ----
+    R("p3_1ch_dyadic", G1, 300, 5, 9, "TEN_WM", "blend_p3<TEN_WM>", layout="planar", weights="dyadic"),
+    R("p3_4ch_dyadic_q16", G4, 130, 3, 7, "TEN_WM", "blend_p3<TEN_WM>", layout="planar", weights="dyadic", quant=16),
+    R("p3_rgba_2ch_dyadic_q16", G2, 300, 5, 9, "TEN_WM", "blend_p3<TEN_WM,rgba>", weights="dyadic", quant=16),
+    R("planar_ten_dyadic", G1, 200, 6, 8, "TEN_WM", "blend_planar<TEN_WM>", weights="dyadic"),
+    R("persist_ten_af_dyadic_q16", G1, 200, 6, 8, "TEN_WM", "blend_persist<TEN_WM,allfocus>", af=True, weights="dyadic", quant=16),
+    R("persist_ten_dyadic", G2, 200, 4, 16, "TEN_WM", "blend_persist<TEN_WM>", variant="persist_m2_nt", weights="dyadic"),
+    R("wave_ten_dyadic_q16", (4, 4), 300, 5, 8, "TEN_WM", "blend_wave<TEN_WM>", variant="wave_m2_nt", weights="dyadic", quant=16),
+    R("ten_direct_dyadic", G2, 200, 6, 9, "TEN_WM", "blend_ten_direct", variant="direct_p1m2", weights="dyadic"),
 ]
 
 
@@ -232,29 +245,63 @@ def _map(W, H, seed):
     return m
 
 
+DYADIC_TIES = 50     # fp16 ties a dyadic row must hold before its launch, so that it does test the RN-even conversion
+
+
+def row_inputs(L, oc, row, H):
+    """A row's host parameters, input images and focus map (all-focus rows; else None) at image height H: what test_dispatch_row renders
+    and what tests/test_ten_interval.py holds the interval's own width to on the CPU."""
+    W, n = row.W, row.n
+    focus, frange = (0.1, 0.3) if row.all_focus else (0.23, 0.0)
+    hp = L.build_params(row.cols, row.rows, W, H, "0.071,0.071,0.93,0.93", focus, frange, 3.0, 1.783, row.V)
+    if row.weights == "wide":
+        hp.weights = hp.weights.copy()
+        hp.weights[:, n // 2] = 0x4100     # fp16 2.5
+    if row.weights == "dyadic":
+        # multiples of 2^-12 that sum to at most 2: every product with a byte and every partial sum is a multiple of 2^-12 below 512,
+        # 21 bits, exact in fp32 in any order of accumulation
+        w = np.floor(ten_interval.weights_f64(hp.weights) * 4096.0) / 4096.0
+        assert (w.astype(np.float16) == w).all()
+        hp.weights = w.astype(np.float16).view(np.uint16)
+    if row.far:
+        hp.focused_offsets = hp.focused_offsets.copy()
+        hp.focused_offsets[n // 2, 0] = 4 * W + 5000
+    lf = oc.synthetic_lf(n, W, H, 0x5EED + n + W)
+    if row.quant > 1:
+        lf = (lf // row.quant * row.quant).astype(np.uint8)
+        lf[..., 3] = 255
+    return hp, lf, _map(W, H, n + W) if row.all_focus else None
+
+
+def ten_row_interval(oc, row, hp, lf, m, threads=THREADS):
+    """S, ε, lo, hi of a TEN_WM row (all views; zero outside the row's range).  A dyadic row: ε = 0 after its preconditions are checked."""
+    S, eps = ten_interval.exact_sums(oc, lf, hp, v0=row.v0, v1=row.v1, threads=threads, all_focus=row.all_focus, map_plane=m, focus=hp.focus,
+                                     rng=hp.range)
+    if row.weights == "dyadic":
+        w = ten_interval.weights_f64(hp.weights)
+        assert (w * 4096.0 == np.floor(w * 4096.0)).all() and (w >= 0).all() and w.sum(axis=1).max() <= 2.0, row.name
+        assert (S * 4096.0 == np.floor(S * 4096.0)).all() and S.max() < 512.0
+        n_ties = ten_interval.ties(S[row.v0:row.v1])
+        assert n_ties >= DYADIC_TIES, (row.name, n_ties)
+        eps = np.zeros_like(eps)
+    lo, hi = ten_interval.interval(S, eps)
+    return S, eps, lo, hi
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("row", MATRIX, ids=lambda r: r.name)
 def test_dispatch_row(row, gpu, oracle_c):
     cu = _cu_count()
     H = _height(row, cu)
-    W, n = row.W, row.n
+    W = row.W
     if row.persistent:
         tiles = (W + row.persistent - 1) // row.persistent * H
         assert tiles > 2 * cu, (tiles, cu)
-    focus, frange = (0.1, 0.3) if row.all_focus else (0.23, 0.0)
-    hp = gpu.build_params(row.cols, row.rows, W, H, "0.071,0.071,0.93,0.93", focus, frange, 3.0, 1.783, row.V)
-    if row.weights == "wide":
-        hp.weights = hp.weights.copy()
-        hp.weights[:, n // 2] = 0x4100     # fp16 2.5
-    if row.far:
-        hp.focused_offsets = hp.focused_offsets.copy()
-        hp.focused_offsets[n // 2, 0] = 4 * W + 5000
-    lf = oracle_c.synthetic_lf(n, W, H, 0x5EED + n + W)
+    hp, lf, m = row_inputs(gpu, oracle_c, row, H)
     ctx = gpu.Context(0)
     ctx.set_grid(row.cols, row.rows, W, H)
     ctx.upload_grid(lf)
     ctx.set_output_layout(row.layout)
-    m = None
     if row.order == "xcd":
         # the planar copy built and tuned for a larger focus; then a focus sweep's next step: smaller offsets (the copy still covers
         # them), no re-tune — unless every image's integer offset moved by a multiple of 128 pixels, the phases no longer fit
@@ -268,7 +315,6 @@ def test_dispatch_row(row, gpu, oracle_c):
     if row.variant != "auto":
         ctx.set_variant(row.method, row.variant)
     if row.all_focus:
-        m = _map(W, H, n + W)
         ctx.upload_map(0, m)
         ctx.upload_map(1, m)
     kw = dict(v0=row.v0, v1=row.v1, threads=THREADS, all_focus=row.all_focus, map_plane=m, focus=hp.focus, rng=hp.range)
@@ -277,6 +323,10 @@ def test_dispatch_row(row, gpu, oracle_c):
     else:
         want = oracle_c.blend_ten(lf, hp.focused_offsets, hp.offsets, hp.weights, model=oracle_c.TEN_M16, **kw)
         tol = 0 if row.flags & ROUND else TEN_TOL_LSB
+    # TEN_WM outside the per-batch debug mode (M16 byte for byte, by design not the exact sum's bytes): the interval of the exact sum
+    S = eps = lo = hi = None
+    if row.method == "TEN_WM" and not row.flags & ROUND:
+        S, eps, lo, hi = (a[row.v0:row.v1] for a in ten_row_interval(oracle_c, row, hp, lf, m))
     outside = None if row.V <= 80 else [0, row.v0 - 1, row.v1, row.V - 1]
 
     def paths():
@@ -291,6 +341,11 @@ def test_dispatch_row(row, gpu, oracle_c):
         assert ctx.last_kernel_name() == row.expect, (row.name, ctx.last_kernel_name())
         bad = poison.mismatch(got, want[row.v0:row.v1], tol)
         assert bad == 0, (row.name, hex(byte), bad)
+        if lo is not None:
+            out = ten_interval.outside(got, lo, hi)
+            differ = int((got[..., :3] != ten_interval.quantise(S)).sum())
+            print(f"TEN_INTERVAL {row.name} {row.expect} {hex(byte)} bytes={lo.size} differ_from_exact={differ} outside={out}")
+            assert out == 0, (row.name, hex(byte), out, "needed multiples of eps, largest:", float(ten_interval.report(got, S, eps).max()))
     poison.twice(check)
     ctx.close()
 

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import poison
+import ten_interval
 from conftest import GOLDEN_DIR, SEED, SMALL_CASES
 
 pytestmark = pytest.mark.gpu
@@ -202,6 +203,7 @@ def test_ragged_shapes_all_variants(shape, gpu, oracle_c):
     ctx = _ctx(gpu, cols, rows, W, H, hp)
     std = oracle_c.blend_std(lf, hp.focused_offsets, hp.offsets, hp.weights, threads=8)
     m16 = oracle_c.blend_ten(lf, hp.focused_offsets, hp.offsets, hp.weights, threads=8)
+    lo, hi = ten_interval.bounds(oracle_c, lf, hp, threads=8)
     for variant in ctx.list_variants("STD"):
         ctx.set_variant("STD", variant)
         poison.render(ctx, "STD")
@@ -209,7 +211,9 @@ def test_ragged_shapes_all_variants(shape, gpu, oracle_c):
     for variant in ctx.list_variants("TEN_WM"):
         ctx.set_variant("TEN_WM", variant)
         poison.render(ctx, "TEN_WM")
-        assert np.abs(ctx.download_views().astype(int) - m16.astype(int)).max() <= TEN_TOL_LSB, variant
+        got = ctx.download_views()
+        assert np.abs(got.astype(int) - m16.astype(int)).max() <= TEN_TOL_LSB, variant
+        assert ten_interval.outside(got, lo, hi) == 0, (variant, ctx.last_kernel_name())
     ctx.close()
 
 
@@ -227,10 +231,13 @@ def test_offsets_larger_than_image_and_subnormal_weights(gpu, oracle_c):
         poison.render(ctx, "STD")
         assert (ctx.download_views() == oracle_c.blend_std(lf, hp.focused_offsets, hp.offsets, hp.weights)).all()
     m16 = oracle_c.blend_ten(lf, hp.focused_offsets, hp.offsets, hp.weights)
+    lo, hi = ten_interval.bounds(oracle_c, lf, hp)
     for variant in ctx.list_variants("TEN_WM"):
         ctx.set_variant("TEN_WM", variant)
         poison.render(ctx, "TEN_WM")
-        assert np.abs(ctx.download_views().astype(int) - m16.astype(int)).max() <= TEN_TOL_LSB
+        got = ctx.download_views()
+        assert np.abs(got.astype(int) - m16.astype(int)).max() <= TEN_TOL_LSB
+        assert ten_interval.outside(got, lo, hi) == 0, (variant, ctx.last_kernel_name())
     ctx.close()
 
 
@@ -627,7 +634,9 @@ def test_random_shapes_default_kernels(case, gpu, oracle_c):
     poison.render(ctx, "STD")
     assert (ctx.download_views() == want_std).all()
     poison.render(ctx, "TEN_WM")
-    assert np.abs(ctx.download_views().astype(int) - want_ten.astype(int)).max() <= TEN_TOL_LSB
+    got = ctx.download_views()
+    assert np.abs(got.astype(int) - want_ten.astype(int)).max() <= TEN_TOL_LSB
+    assert ten_interval.outside(got, *ten_interval.bounds(oracle_c, lf, hp)) == 0, ctx.last_kernel_name()
     if V >= 3:      # a view sub-range leaves the other views untouched (render_range: they still hold the poison)
         v0, v1 = 1, V - 1
         assert (poison.render_range(ctx, "STD", v0, v1) == want_std[v0:v1]).all()

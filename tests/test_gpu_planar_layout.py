@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import poison
+import ten_interval
 from conftest import GOLDEN_DIR, SEED, SMALL_CASES
 import os
 
@@ -82,6 +83,7 @@ def test_ragged_shapes_planar_equals_rgba(shape, gpu, oracle_c):
     assert ctx.last_kernel_name() == "blend_p3<TEN_WM>"
     got = ctx.download_views()
     assert np.abs(got.astype(int) - m16.astype(int)).max() <= TEN_TOL_LSB
+    assert ten_interval.outside(got, *ten_interval.bounds(oracle_c, lf, hp, threads=8)) == 0
     assert (got == want).all(), int((got != want).sum())
     # consecutive launches walk the image in opposite directions (Infinity Cache reuse): same bytes, with and without the alternation
     for flags in (0, gpu.LFI_FLAG_SINGLE_SWEEP_DIRECTION):
@@ -107,7 +109,9 @@ def test_planar_layout_offsets_larger_than_image(gpu, oracle_c):
     m16 = oracle_c.blend_ten(lf, hp.focused_offsets, hp.offsets, hp.weights)
     poison.render(ctx, "TEN_WM")
     assert ctx.last_kernel_name() == "blend_p3<TEN_WM>"
-    assert np.abs(ctx.download_views().astype(int) - m16.astype(int)).max() <= TEN_TOL_LSB
+    got = ctx.download_views()
+    assert np.abs(got.astype(int) - m16.astype(int)).max() <= TEN_TOL_LSB
+    assert ten_interval.outside(got, *ten_interval.bounds(oracle_c, lf, hp)) == 0
     ctx.close()
 
 
@@ -124,7 +128,9 @@ def test_planar_layout_weights_outside_unit_range_fall_back(gpu, oracle_c):
     poison.render(ctx, "TEN_WM")
     assert ctx.last_kernel_name() != "blend_p3<TEN_WM>"
     m16 = oracle_c.blend_ten(lf, hp.focused_offsets, hp.offsets, hp.weights)
-    assert np.abs(ctx.download_views().astype(int) - m16.astype(int)).max() <= TEN_TOL_LSB
+    got = ctx.download_views()
+    assert np.abs(got.astype(int) - m16.astype(int)).max() <= TEN_TOL_LSB
+    assert ten_interval.outside(got, *ten_interval.bounds(oracle_c, lf, hp)) == 0, ctx.last_kernel_name()
     ctx.close()
 
 
@@ -183,12 +189,14 @@ def test_planar_layout_three_and_more_view_passes(V, W, H, gpu, oracle_c):
     hp = gpu.build_params(cols, rows, W, H, "0,0,1,1", 0.15, 0.0, 3.0, 1.783, V)
     lf = oracle_c.synthetic_lf(cols * rows, W, H, SEED)
     m16 = oracle_c.blend_ten(lf, hp.focused_offsets, hp.offsets, hp.weights, model=oracle_c.TEN_M16, threads=8)
+    lo, hi = ten_interval.bounds(oracle_c, lf, hp, threads=8)
     ctx = _ctx(gpu, cols, rows, W, H, hp, lf=lf)
     for sweep in range(2):
         poison.render(ctx, "TEN_WM")
         assert ctx.last_kernel_name() == "blend_p3<TEN_WM>"
         got = ctx.download_views()
         assert np.abs(got.astype(int) - m16.astype(int)).max() <= TEN_TOL_LSB, sweep
+        assert ten_interval.outside(got, lo, hi) == 0, sweep
     # 3 or 4 passes from an odd first view
     assert (poison.render_range(ctx, "TEN_WM", 5, V - 3) == got[5:V - 3]).all()
     ctx.set_output_layout("rgba")
