@@ -1,5 +1,5 @@
 """Randomised parity cases shared by tests/test_gpu_fuzz.py (fixed seeds, a bounded number of cases) and the soak tools under
-tools/ (fuzz_parity.py, fuzz_focus.py, fuzz_allfocus.py: any number of cases, any seed).
+tools/ (fuzz_parity.py, fuzz_focus.py, fuzz_allfocus.py, fuzz_view_rows.py: any number of cases, any seed).
 
 Every function renders random small shapes through the HIP library (the C-ABI) and checks them against the CPU oracle — STD and
 focus maps bit-exact, TEN_WM within one LSB of the fp16-accumulate model M16 and inside the interval of the exact sum
@@ -10,6 +10,7 @@ import numpy as np
 
 import poison
 import ten_interval
+import view_rows
 
 TEN_TOL_LSB = 1
 
@@ -199,6 +200,102 @@ def fuzz_allfocus(L, oc, n_cases: int, seed: int, log=None) -> list:
                 if ctx.last_kernel_name() != "blend_afs<STD,allfocus>" or not (ctx.download_views() == want_std).all():
                     bad.append(dict(case, what="all-focus", layout=layout, std_exact=False, kernel=ctx.last_kernel_name()))
                 ctx.set_variant("STD", "auto")
+        ctx.close()
+        if log and (i + 1) % 20 == 0:
+            log(f"{i + 1} cases, {len(bad)} mismatches")
+    return bad
+
+
+def fuzz_view_rows(L, oc, n_cases: int, seed: int, log=None) -> list:
+    """Per-view rows (launch_view_rows: blend_vfocus, blend_vfocus_af): random grids (2–225 images), widths around the 256-pixel tile and
+    the 4-pixel quad, 1–9 rows, view counts around the chunk of 8 with a random sub-range, integer rows from either source, float rows
+    with the context's maps or a map pair per view, both view layouts, focus ramps of either sign.  Both methods: views outside the range
+    keep the poison, the kernel is the one expected, STD byte for byte, TEN_WM within one LSB of M16 and inside the interval of the exact sum."""
+    rng = np.random.default_rng(seed)
+    bad = []
+    for i in range(n_cases):
+        cols, rows = int(rng.integers(1, 16)), int(rng.integers(1, 16))
+        if cols * rows < 2:
+            cols, rows = 3, 4
+        n = cols * rows
+        W = int(rng.choice([1, 4, 33, 255, 256, 257, 259, 300, 513]))
+        H = int(rng.integers(1, 10))
+        V = int(rng.choice([1, 7, 8, 9, 64, 65]))
+        v0 = int(rng.integers(0, V))
+        v1 = int(rng.integers(v0 + 1, V + 1))
+        kind = str(rng.choice(view_rows.KINDS))
+        source = str(rng.choice(["planar", "rgba"])) if kind == "int" else ""
+        layout = str(rng.choice(["rgba", "planar"]))
+        f0, f1 = (float(x) for x in rng.choice([0.0, 0.03, 0.23, 0.6, 1.1, -0.4, -0.9], 2))
+        traj = str(rng.choice(["0,0,1,1", "0.071,0.071,0.93,0.93", "1,0,0,1", "0.2,0.9,0.8,0.1"]))
+        effect = float(rng.choice([1.0, 3.0, 7.0]))
+        lf = oc.synthetic_lf(n, W, H, int(rng.integers(1, 1 << 30)))
+        case = dict(kind=kind, source=source, layout=layout, cols=cols, rows=rows, W=W, H=H, V=V, v0=v0, v1=v1, f0=f0, f1=f1, traj=traj, effect=effect)
+        ctx = L.Context(0)
+        ctx.set_grid(cols, rows, W, H)
+        ctx.upload_grid(lf)
+        ctx.set_output_layout(layout)
+        if kind == "int":
+            hp = L.build_params(cols, rows, W, H, traj, f0, 0.0, effect, 1.783, V)
+            off = L.build_view_offsets(cols, rows, W, H, traj, 1.783, L.focus_ramp(f0, f1, V))
+            ctx.set_params(hp)
+            if source == "rgba":
+                ctx.grid_device_ptr()
+            ctx.set_view_offsets(off)
+            maps = None
+        else:
+            frange = f1 - f0 if f1 != f0 else 0.5      # (the per-view maps' estimate takes a range > 0)
+            if kind == "view_maps":
+                frange = abs(frange)
+            hp = L.build_params(cols, rows, W, H, traj, f0, frange, effect, 1.783, V)
+            off, _ = L.build_view_centred_offsets(cols, rows, W, H, traj, 1.783, np.full(V, f0, np.float32))
+            ctx.set_params(hp)
+            ctx.set_view_float_offsets(off)
+            map_seed = int(rng.integers(1, 1 << 30))
+            if kind == "float":
+                maps = view_rows.random_maps(H, W, map_seed)
+                for k in (0, 1):
+                    ctx.upload_map(k, maps[k])
+            else:
+                ctx.view_focus_maps(L.build_view_focus_ids(cols, rows, traj, V))
+                maps = {v: view_rows.random_maps(H, W, map_seed + v) for v in range(v0, v1)}
+                for v, pair in maps.items():
+                    for k in (0, 1):
+                        ctx.upload_view_map(v, k, pair[k])
+        for method in view_rows.METHODS:
+            want, S = [], []
+            for v in range(v0, v1):
+                w = hp.weights[v:v + 1]
+                if kind == "int":
+                    d = off[v].copy()
+                    d[:, 0], d[:, 1] = np.clip(d[:, 0], -W, W), np.clip(d[:, 1], -H, H)
+                    args, kw = (lf, d, hp.offsets, w), {}
+                else:
+                    pair = maps[v] if kind == "view_maps" else maps
+                    args = (lf, hp.focused_offsets, off[v], w)
+                    kw = dict(all_focus=True, map_plane=pair[1 if method == "STD" else 0], focus=hp.focus, rng=hp.range)
+                if method == "STD":
+                    want.append(oc.blend_std(*args, **kw)[0])
+                else:
+                    want.append(oc.blend_ten(*args, model=oc.TEN_M16, **kw)[0])
+                    S.append(oc.blend_f64(*args, **kw)[0])
+            want = np.stack(want)
+            b = poison.render(ctx, method, all_focus=kind != "int", v0=v0, v1=v1)
+            kernel = ctx.last_kernel_name()
+            stray = poison.written_outside(ctx, v0, v1, b)
+            got = ctx.download_views(v0, v1)
+            found = dict(case, what=method, kernel=kernel, written_outside=stray)
+            ok = kernel == view_rows.KERNEL[kind, source].format(method) and not stray
+            if method == "STD":
+                found["wrong"] = poison.mismatch(got, want)
+                ok = ok and found["wrong"] == 0
+            else:
+                lo, hi = ten_interval.interval(np.stack(S), ten_interval.epsilon(hp.weights[v0:v1], n))
+                found["lsb"] = int(np.abs(got.astype(int) - want.astype(int)).max())
+                found["outside_interval"] = ten_interval.outside(got, lo, hi)
+                ok = ok and found["lsb"] <= TEN_TOL_LSB and found["outside_interval"] == 0
+            if not ok:
+                bad.append(found)
         ctx.close()
         if log and (i + 1) % 20 == 0:
             log(f"{i + 1} cases, {len(bad)} mismatches")

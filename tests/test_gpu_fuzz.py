@@ -27,3 +27,8 @@ def test_fuzz_focus_maps(gpu):
 def test_fuzz_all_focus_renders(gpu):
     bad = fuzz_cases.fuzz_allfocus(gpu, _oracle(), n_cases=40, seed=3)
     assert not bad, bad[:5]
+
+
+def test_fuzz_view_rows(gpu):
+    bad = fuzz_cases.fuzz_view_rows(gpu, _oracle(), n_cases=24, seed=5)
+    assert not bad, bad[:5]

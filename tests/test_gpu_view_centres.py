@@ -3,8 +3,9 @@ about its own camera instead of the trajectory's centre.
 
 View v of an all-focus render samples image g at (int)fma(f(x,y), O[v][g], pixel); the oracle's all-focus render of weight row v with O[v] as
 its float offsets, over the map the context reads, is therefore the exact answer for view v: STD byte for byte, TEN_WM within the TEN_WM
-contract (≤ 1 LSB from the fp16-accumulator model M16, < 1e-3 of the bytes off the exactly-summed model).  Every render goes through
-tests/poison.py."""
+contract (≤ 1 LSB from the fp16-accumulator model M16, < 1e-3 of the bytes off the exactly-summed model, every byte inside the interval of
+the exact sum: tests/ten_interval.py).  Every render goes through tests/poison.py; the family's shapes and edges are the table of
+tests/view_rows.py (tests/test_gpu_view_rows_coverage.py)."""
 import os
 
 import numpy as np
@@ -12,7 +13,7 @@ import pytest
 
 import poison
 from conftest import SEED
-from view_rows import TEN_TOL_LSB, check_views, run_cli
+from view_rows import TEN_TOL_LSB, check_views, random_maps as _random_maps, run_cli, ten_want  # (_random_maps: test_gpu_view_maps.py imports it from here)
 
 pytestmark = pytest.mark.gpu
 
@@ -34,22 +35,8 @@ def _want(oc, lf, O, hp, method, maps, unified=False, v0=0, v1=None, focused=Non
         if method == "STD":
             out.append(oc.blend_std(lf, foc, O[v], hp.weights[v:v + 1], **kw)[0])
         else:
-            out.append((oc.blend_ten(lf, foc, O[v], hp.weights[v:v + 1], model=oc.TEN_M16, **kw)[0],
-                        oc.blend_ten(lf, foc, O[v], hp.weights[v:v + 1], model=oc.TEN_EXACT, **kw)[0]))
+            out.append(ten_want(oc, lf, foc, O[v], hp.weights[v:v + 1], **kw))
     return out
-
-
-def _random_maps(H, W, seed):
-    """Two different maps in which every focus byte 0…255 occurs (where the image has 256 pixels or more)."""
-    rng = np.random.default_rng(seed)
-    maps = []
-    for _ in range(2):
-        m = np.zeros((H, W, 4), np.uint8)
-        m[..., 0] = rng.permutation(np.arange(H * W) % 256).reshape(H, W)
-        m[..., 1:3] = m[..., :1]
-        m[..., 3] = 255
-        maps.append(m)
-    return maps
 
 
 def _ctx(gpu, cols, rows, W, H, hp, layout="rgba", flags=0, seed=SEED):

@@ -2,7 +2,9 @@
 
 View v of a fixed-focus render samples image g at pixel + D[v][g]; the oracle's fixed-focus render of weight row v with D[v] as its
 focused offsets is therefore the exact answer for view v: STD byte for byte, TEN_WM within the TEN_WM contract (≤ 1 LSB from the
-fp16-accumulator model M16, < 1e-3 of the bytes off the exactly-summed model).  Every render goes through tests/poison.py."""
+fp16-accumulator model M16, < 1e-3 of the bytes off the exactly-summed model, every byte inside the interval of the exact sum:
+tests/ten_interval.py).  Every render goes through tests/poison.py; the family's shapes, sources and edges are the table of
+tests/view_rows.py (tests/test_gpu_view_rows_coverage.py)."""
 import os
 
 import numpy as np
@@ -10,7 +12,7 @@ import pytest
 
 import poison
 from conftest import SEED
-from view_rows import check_views, run_cli
+from view_rows import check_views, run_cli, ten_want
 
 pytestmark = pytest.mark.gpu
 
@@ -24,8 +26,7 @@ def _want(oc, lf, D, hp, method, v0=0, v1=None, weights=None):
         if method == "STD":
             out.append(oc.blend_std(lf, D[v], hp.offsets, w[v:v + 1])[0])
         else:
-            out.append((oc.blend_ten(lf, D[v], hp.offsets, w[v:v + 1], model=oc.TEN_M16)[0],
-                        oc.blend_ten(lf, D[v], hp.offsets, w[v:v + 1], model=oc.TEN_EXACT)[0]))
+            out.append(ten_want(oc, lf, D[v], hp.offsets, w[v:v + 1]))
     return out
 
 

@@ -3,7 +3,9 @@ camera, as the reference's focusMapCompare.sh second run does per camera.
 
 View v's map 0 is the oracle's focus_estimate with the view's float offsets O[v] and its ids (build_view_focus_ids row v), map 1 its
 focus_filter; view v of an all-focus render is the oracle's all-focus render of weight row v at O[v] over view v's own map: STD byte for byte,
-TEN_WM within the TEN_WM contract.  Every map and view a check reads was poisoned first."""
+TEN_WM within the TEN_WM contract (≤ 1 LSB from M16, < 1e-3 of the bytes off the exactly-summed model, every byte inside the interval of the
+exact sum: tests/ten_interval.py).  Every map and view a check reads was poisoned first; the render kernel's shapes and edges are the table
+of tests/view_rows.py (tests/test_gpu_view_rows_coverage.py)."""
 import dataclasses
 import os
 
@@ -14,7 +16,7 @@ import lfinterpolator_amd as L
 import poison
 from conftest import SEED
 from test_gpu_view_centres import CASES, _random_maps
-from view_rows import check_views, run_cli
+from view_rows import check_views, run_cli, ten_want
 
 pytestmark = pytest.mark.gpu
 
@@ -64,7 +66,7 @@ def _check_maps(ctx, oc, lf, O, ids, hp, views=None):
 
 
 def _want_views(oc, lf, O, hp, method, maps_of, unified=False):
-    """maps_of(v) -> (map0, map1) of view v; per view the oracle's STD view, or the TEN_WM (M16, exact) pair."""
+    """maps_of(v) -> (map0, map1) of view v; per view the oracle's STD view, or the TEN_WM (M16, exact, S, ε) tuple of check_views."""
     out = []
     for v in range(len(O)):
         m = maps_of(v)[1 if (method == "STD" or unified) else 0]
@@ -73,8 +75,7 @@ def _want_views(oc, lf, O, hp, method, maps_of, unified=False):
         if method == "STD":
             out.append(oc.blend_std(lf, hp.focused_offsets, O[v], w, **kw)[0])
         else:
-            out.append((oc.blend_ten(lf, hp.focused_offsets, O[v], w, model=oc.TEN_M16, **kw)[0],
-                        oc.blend_ten(lf, hp.focused_offsets, O[v], w, model=oc.TEN_EXACT, **kw)[0]))
+            out.append(ten_want(oc, lf, hp.focused_offsets, O[v], w, **kw))
     return out
 
 
