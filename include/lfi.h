@@ -676,6 +676,38 @@ int lfi_download_quilt_yuv(lfi_ctx *ctx, int tiles_x, int tiles_y, int v0, int t
  * whose allocation ends before the last frame does. */
 enum { LFI_RGBD_INVERT = 1u, LFI_RGBD_VIEW_MAPS = 2u };
 int lfi_download_rgbd_yuv(lfi_ctx *ctx, int v0, int n, int map_k, uint32_t flags, int tile_w, int tile_h, int matrix, int range, const lfi_yuv_surfaces *dst);
+/* CHROMA SITING.  Everything above defines chroma as centre-sited (JPEG's and MPEG-1's convention, Y4M's C420jpeg).  MPEG-2, H.264, HEVC and
+ * AV1 video site chroma on the LEFT: a chroma sample is co-sited with the even luma column and lies between the two rows (Y4M's C420mpeg2;
+ * what decoders leave as NV12 surfaces and what encoders assume of untagged frames).  The siting is a context setting, one for frames that
+ * come in and one for frames that go out.  Under LFI_YUV_SITING_LEFT everything not named here stays as defined above: luma, the
+ * coefficient tables, the geometry of a frame, cw and ch.
+ *  - OUTPUT, left-sited.  For chroma sample (cx, cy): rows y_j = min(2cy + j, H - 1), j in {0, 1}; columns xl = max(2cx - 1, 0), xc = 2cx,
+ *    xr = min(2cx + 1, W - 1).  The sums are
+ *        SR = sum over j of [ R(xl, y_j) + 2*R(xc, y_j) + R(xr, y_j) ]          (SG, SB likewise; total weight 8)
+ *    and
+ *        Cb[cy][cx] = min(255, (2^26 + 2^18 + uR*SR + uG*SG + uB*SB) >> 19)     Cr likewise with the Cr coefficients
+ *    the [1 2 1]/4 filter of left siting horizontally, the box vertically, one rounding.  The bracket lies in (0, 2^28] (extremes 524,288
+ *    and 134,217,728 over the four rows): unsigned 32-bit arithmetic.  Limited range stays in [16, 240], full range reaches 256 before the
+ *    min, every grey gives exactly 128, and a uniform image gives exactly the centre-sited frame.
+ *  - INPUT, left-sited, LFI_CHROMA_BILINEAR.  With cx = x >> 1, cy = y >> 1 and ny as above:
+ *        h(r) = 4*U[r][cx]                                    (even x)
+ *        h(r) = 2*U[r][cx] + 2*U[r][min(cx + 1, cw - 1)]      (odd x)
+ *        SU   = 3*h(cy) + h(ny)
+ *    SU is in sixteenths as above, and R, G, B follow from it as above.  LFI_CHROMA_NEAREST gives the same bytes under either siting: an odd
+ *    column is equally far from both samples and keeps cx.
+ * in_siting governs lfi_upload_images_yuv420, lfi_upload_images_yuv and lfi_upload_images_yuv_derived; out_siting governs
+ * lfi_download_views_yuv420, lfi_download_views_yuv, lfi_render_stream_yuv420 and lfi_download_quilt_yuv.  Sources, destinations, routing,
+ * chunking, ordering and refusals of these calls are the same under both sitings, with two exceptions:
+ *  - lfi_download_quilt_yuv under LEFT output is by definition the left-sited frame of lfi_download_quilt_scaled's image taken as one view
+ *    (chroma filters across tile edges exactly as that says); it takes the two-launch route of odd tile sizes for even tile sizes too.
+ *  - lfi_download_rgbd_yuv under LEFT output returns LFI_EINVAL (the context stays usable): the filter would mix the colour half and the
+ *    depth half in the column between them.  Left-sited RGB-D frames are out of scope.
+ * The default is centre / centre, under which every call does exactly what it did before the setting existed.  The setting lives until it
+ * is changed: lfi_set_grid, lfi_set_params and lfi_set_row_window leave it alone.  LFI_EINVAL for an unknown value; the setting is kept.
+ * Not covered: top-left siting (co-sited both ways) and Y4M's C420paldv. */
+enum { LFI_YUV_SITING_CENTRE = 0, LFI_YUV_SITING_LEFT = 1 };
+int lfi_set_yuv_siting(lfi_ctx *ctx, int in_siting, int out_siting);
+int lfi_yuv_siting(lfi_ctx *ctx, int *in_siting, int *out_siting);
 int lfi_upload_map(lfi_ctx *ctx, int k, const uint8_t *rgba, size_t pitch_bytes); /* tests: inject a focus map */
 /* view v's map k (0 or 1) of the per-view maps (lfi_view_focus_maps).  Synchronous.  The upload is a test hook like lfi_upload_map (it
  * allocates the per-view maps if needed and does not put them in use: renders read them after a successful lfi_view_focus_maps). */

@@ -36,6 +36,9 @@ YUV_RANGES = {"limited": LFI_YUV_LIMITED, "full": LFI_YUV_FULL}
 LFI_CHROMA_BILINEAR = 0
 LFI_CHROMA_NEAREST = 1
 YUV_CHROMAS = {"bilinear": LFI_CHROMA_BILINEAR, "nearest": LFI_CHROMA_NEAREST}
+LFI_YUV_SITING_CENTRE = 0
+LFI_YUV_SITING_LEFT = 1
+YUV_SITINGS = {"centre": LFI_YUV_SITING_CENTRE, "left": LFI_YUV_SITING_LEFT}
 LFI_YUV_I420 = 0
 LFI_YUV_NV12 = 1
 YUV_FORMATS = {"i420": LFI_YUV_I420, "nv12": LFI_YUV_NV12}
@@ -57,7 +60,7 @@ ABI_SYMBOLS = [
     "lfi_keep_views", "lfi_compare_views", "lfi_set_focus_steps", "lfi_focus_steps", "lfi_download_native",
     "lfi_download_views_yuv420", "lfi_render_stream_yuv420", "lfi_upload_images_yuv420",
     "lfi_yuv_surfaces_check", "lfi_yuv_surfaces_packed", "lfi_upload_images_yuv", "lfi_download_views_yuv",
-    "lfi_download_quilt_yuv", "lfi_download_rgbd_yuv",
+    "lfi_download_quilt_yuv", "lfi_download_rgbd_yuv", "lfi_set_yuv_siting", "lfi_yuv_siting",
     "lfi_upload_images_yuv_derived", "lfi_debug_derived_layout", "lfi_debug_download_derived",
 ]
 
@@ -238,6 +241,8 @@ def load_hip_library() -> C.CDLL:
         "lfi_download_quilt_yuv": (i, [vp, i, i, i, i, i, i, i, C.POINTER(YuvSurfaces)]),
         "lfi_download_rgbd_yuv": (i, [vp, i, i, i, C.c_uint32, i, i, i, i, C.POINTER(YuvSurfaces)]),
         "lfi_upload_images_yuv_derived": (i, [vp, i, i, i, i, i, C.POINTER(YuvSurfaces)]),
+        "lfi_set_yuv_siting": (i, [vp, i, i]),
+        "lfi_yuv_siting": (i, [vp, C.POINTER(i), C.POINTER(i)]),
         "lfi_debug_derived_layout": (i, [vp, C.POINTER(DerivedLayout), vp]),
         "lfi_debug_download_derived": (i, [vp, i, i, vp]),
         "lfi_alloc_pinned": (i, [sz, C.POINTER(vp)]),
@@ -502,6 +507,20 @@ class Context:
         """Fine focus maps (lfi_set_focus_steps): focus_map chooses every pixel's focus from `steps` candidates of [focus, focus + range], a
         multiple of 32 from 32 (the default: the reference's) to 256.  A context setting; view_focus_maps keeps 32 and focus_tiles takes its own `steps`."""
         self._check(self._lib.lfi_set_focus_steps(self._h, int(steps)))
+
+    def set_yuv_siting(self, in_siting="centre", out_siting="centre") -> None:
+        """Chroma siting of YUV 4:2:0 frames (lfi_set_yuv_siting): "centre" (JPEG, MPEG-1, Y4M's C420jpeg; the default) or "left" (MPEG-2,
+        H.264, HEVC, AV1, Y4M's C420mpeg2) — in_siting for the frames the upload_images_yuv* calls read, out_siting for the frames
+        download_views_yuv*, render_stream_yuv420 and download_quilt_yuv write (download_rgbd_yuv refuses left).  A context setting: it lives
+        until it is changed.  Takes the names or the LFI_YUV_SITING_* values."""
+        self._check(self._lib.lfi_set_yuv_siting(self._h, YUV_SITINGS.get(in_siting, in_siting), YUV_SITINGS.get(out_siting, out_siting)))
+
+    def yuv_siting(self) -> tuple[str, str]:
+        """(in_siting, out_siting) as names (lfi_yuv_siting)"""
+        a, b = C.c_int(0), C.c_int(0)
+        self._check(self._lib.lfi_yuv_siting(self._h, C.byref(a), C.byref(b)))
+        names = {v: k for k, v in YUV_SITINGS.items()}
+        return names[a.value], names[b.value]
 
     def focus_steps(self) -> int:
         out = C.c_int(0)

@@ -360,6 +360,9 @@ struct lfi_ctx
     // and lfi_set_row_window leave alone.  Above 32 the factored estimate runs one pass per 32 candidates and carries each pixel's minimum
     // between them in focus_ws's carry plane (lfi_focus_sched.hpp)
     int focus_steps = lfi::FOCUS_STEPS;
+    // lfi_set_yuv_siting: where the chroma samples of YUV 4:2:0 frames lie (LFI_YUV_SITING_*), of the frames the upload calls read and of the
+    // frames the download calls write; a context setting like focus_steps
+    int yuv_in_siting = 0, yuv_out_siting = 0;
     DeviceBuffer curve_ws; // lfi_focus_curve: the curve and its result, then the per-workgroup partial sums (grows, kept)
     int ten_variant = 0, std_variant = 0, focus_variant = 0;
     int tiles_passes = 0; // the factored passes lfi_focus_tiles_steps' last call ran; 0: it took focus_curve_partial tile by tile (lfi_focus_tiles_passes)

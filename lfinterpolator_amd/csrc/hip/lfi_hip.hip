@@ -486,6 +486,7 @@ int upload_yuv_surfaces(lfi_ctx *ctx, const char *who, int g0, int n, int matrix
         return rc;
     const lfi::YuvGeometry g = lfi::yuv_geometry(ctx->width, ctx->height);
     const bool in_place = yuv_surfaces_in_place(src);
+    const bool left = ctx->yuv_in_siting == LFI_YUV_SITING_LEFT; // lfi_set_yuv_siting
     // staged: chunks of at most 16 frames or 256 MiB, at least one frame: a chunk's copies and its launch follow each other on the copy
     // stream, so stream order is all the staging buffer needs.  In place: one chunk of all n frames, no buffer
     const int chunk = in_place ? n : (int)std::max<size_t>(1, std::min<size_t>(16, ((size_t)256 << 20) / g.dev_frame_bytes));
@@ -523,13 +524,13 @@ int upload_yuv_surfaces(lfi_ctx *ctx, const char *who, int g0, int n, int matrix
             d.phase = ctx->d_planar_phase.as<int32_t>();
             d.pitch = (uint32_t)ctx->planar_pitch, d.padx = (uint32_t)ctx->planar_padx;
             d.g0 = (uint32_t)(g0 + k0);
-            LFI_HIP(ctx, lfi::launch_yuvs_derived_expand(st, src.format, chroma == LFI_CHROMA_NEAREST, d, nk));
+            LFI_HIP(ctx, lfi::launch_yuvs_derived_expand(st, src.format, chroma == LFI_CHROMA_NEAREST, left, d, nk));
             continue;
         }
         a.dst = ctx->grid.get() + in_plane_bytes(ctx) * (size_t)(g0 + k0);
         a.image_stride = in_plane_bytes(ctx);
         a.rows16 = g.W % 4 == 0; // the grid starts on a 16-byte boundary (hipMalloc; lfi_attach_grid checks), an image is W·H·4 bytes
-        LFI_HIP(ctx, lfi::launch_yuvs_expand(st, src.format, chroma == LFI_CHROMA_NEAREST, a, nk));
+        LFI_HIP(ctx, lfi::launch_yuvs_expand(st, src.format, chroma == LFI_CHROMA_NEAREST, left, a, nk));
     }
     if(!derived)
         touch_images(ctx, g0, g0 + n);
@@ -1167,6 +1168,26 @@ int lfi_set_focus_steps(lfi_ctx *ctx, int steps)
     return LFI_OK;
 }
 
+int lfi_set_yuv_siting(lfi_ctx *ctx, int in_siting, int out_siting)
+{
+    if(!ctx)
+        return LFI_EINVAL;
+    const auto known = [](int s) { return s == LFI_YUV_SITING_CENTRE || s == LFI_YUV_SITING_LEFT; };
+    if(!known(in_siting) || !known(out_siting))
+        return fail(ctx, LFI_EINVAL, "lfi_set_yuv_siting: unknown chroma siting (LFI_YUV_SITING_CENTRE, LFI_YUV_SITING_LEFT) - in " + std::to_string(in_siting) +
+                                         ", out " + std::to_string(out_siting));
+    ctx->yuv_in_siting = in_siting, ctx->yuv_out_siting = out_siting;
+    return LFI_OK;
+}
+
+int lfi_yuv_siting(lfi_ctx *ctx, int *in_siting, int *out_siting)
+{
+    if(!ctx || !in_siting || !out_siting)
+        return LFI_EINVAL;
+    *in_siting = ctx->yuv_in_siting, *out_siting = ctx->yuv_out_siting;
+    return LFI_OK;
+}
+
 int lfi_focus_steps(lfi_ctx *ctx, int *out_steps)
 {
     if(!ctx || !out_steps)
@@ -1648,8 +1669,9 @@ static int check_yuv_download(lfi_ctx *ctx, const char *who, int v0, int n, int 
 
 // The ONE yuvs_convert launch, on st: view i of src → frame i of s (of `format`), n of them.  src starts on a 16-byte boundary (the views:
 // hipMalloc, lfi_attach_views checks; the quilt buffer: hipMalloc) and a view is W·H·4 bytes, so with W a multiple of 4 every RGBA row
-// does.  blocks_x is yuv_geometry's y_pitch / YUV_BLOCK_W: the same number.
-static hipError_t enqueue_yuv_convert(hipStream_t st, const lfi::ViewsSrc &src, bool planar, int n, int matrix, int range, int format, const lfi::YuvSurfaces &s)
+// does.  blocks_x is yuv_geometry's y_pitch / YUV_BLOCK_W: the same number.  siting: the context's out_siting (lfi_set_yuv_siting).
+static hipError_t enqueue_yuv_convert(hipStream_t st, const lfi::ViewsSrc &src, bool planar, int n, int matrix, int range, int format, int siting,
+                                      const lfi::YuvSurfaces &s)
 {
     lfi::YuvsOutArgs a{};
     a.src = src, a.s = s;
@@ -1657,7 +1679,7 @@ static hipError_t enqueue_yuv_convert(hipStream_t st, const lfi::ViewsSrc &src, 
     a.blocks_x = (src.W + lfi::YUV_BLOCK_W - 1) / lfi::YUV_BLOCK_W;
     a.rows16 = src.W % 4 == 0;
     a.k = lfi::YUV_COEFFS[matrix * 2 + range];
-    return lfi::launch_yuvs_convert(st, planar, format, a, n);
+    return lfi::launch_yuvs_convert(st, planar, format, siting == LFI_YUV_SITING_LEFT, a, n);
 }
 
 // How n frames of W × H reach dst, which has passed yuv_surfaces_fault (that gave extent) or is what host_i420_surfaces made: the kernel
@@ -1707,7 +1729,7 @@ static int download_yuv_surfaces(lfi_ctx *ctx, const char *who, int v0, int n, i
         return rc;
     bool planar;
     const lfi::ViewsSrc src = rendered_views(ctx, v0, &planar);
-    LFI_HIP(ctx, enqueue_yuv_convert(ctx->stream, src, planar, n, matrix, range, dst.format, d.frames));
+    LFI_HIP(ctx, enqueue_yuv_convert(ctx->stream, src, planar, n, matrix, range, dst.format, ctx->yuv_out_siting, d.frames));
     return finish_yuv_delivery(ctx, dst, n, d);
 }
 
@@ -1842,7 +1864,7 @@ static int render_stream(lfi_ctx *ctx, int method, int all_focus, const uint16_t
                 LFI_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_d2h[slot], 0)); // block b − 2 has left this buffer of frames
             bool planar;
             const lfi::ViewsSrc src = rendered_views(ctx, 0, &planar); // vbuf[slot]: YUV blocks all render into the one set of views
-            LFI_HIP(ctx, enqueue_yuv_convert(ctx->stream, src, planar, nv, yuv->matrix, yuv->range, LFI_YUV_I420,
+            LFI_HIP(ctx, enqueue_yuv_convert(ctx->stream, src, planar, nv, yuv->matrix, yuv->range, LFI_YUV_I420, ctx->yuv_out_siting,
                                              staged_surfaces(yuv_g, LFI_YUV_I420, ctx->yuv[slot].get())));
         }
         LFI_HIP(ctx, hipEventRecord(ctx->ev_rendered[slot], ctx->stream));
@@ -2381,22 +2403,22 @@ int lfi_download_quilt_yuv(lfi_ctx *ctx, int tiles_x, int tiles_y, int v0, int t
     q.src = rendered_views(ctx, 0, &planar);
     q.tile_w = tile_w, q.tile_h = tile_h;
     q.v0 = v0, q.first = 0, q.tiles_x = tiles_x;
-    if(tile_w % 2 == 0 && tile_h % 2 == 0)
+    if(tile_w % 2 == 0 && tile_h % 2 == 0 && ctx->yuv_out_siting == LFI_YUV_SITING_CENTRE)
     {
-        // every 2 x 2 block lies inside one tile: ONE launch, no RGBA quilt
+        // centre-sited, every 2 x 2 block lies inside one tile: ONE launch, no RGBA quilt
         lfi::QuiltYuvArgs a{};
         a.q = q, a.s = d.frames, a.k = lfi::YUV_COEFFS[matrix * 2 + range];
         LFI_HIP(ctx, lfi::launch_quilt_yuv_scale(ctx->stream, planar, dst->format, a, n));
     }
     else
     {
-        // blocks straddle tiles: the RGBA quilt of lfi_download_quilt_scaled in the quilt buffer, converted as ONE RGBA view of QW x QH
+        // blocks straddle tiles, or (left-sited) the chroma filter reaches across tile edges: the RGBA quilt of lfi_download_quilt_scaled in the quilt buffer, converted as ONE RGBA view of QW x QH
         const size_t quilt_bytes = (size_t)QW * 4 * QH;
         LFI_HIP(ctx, ctx->quilt.reserve(quilt_bytes));
         q.quilt = ctx->quilt.as<uint32_t>();
         LFI_HIP(ctx, lfi::launch_quilt_scale(ctx->stream, planar, q, n));
         const lfi::ViewsSrc quilt{ctx->quilt.get(), quilt_bytes, (uint32_t)QW, (uint32_t)QH, 0u};
-        LFI_HIP(ctx, enqueue_yuv_convert(ctx->stream, quilt, false, 1, matrix, range, dst->format, d.frames));
+        LFI_HIP(ctx, enqueue_yuv_convert(ctx->stream, quilt, false, 1, matrix, range, dst->format, ctx->yuv_out_siting, d.frames));
     }
     return finish_yuv_delivery(ctx, *dst, 1, d);
 }
@@ -2410,6 +2432,9 @@ int lfi_download_rgbd_yuv(lfi_ctx *ctx, int v0, int n, int map_k, uint32_t flags
     // and range), the tiles as lfi_download_quilt_scaled does
     if(int rc = check_yuv_download(ctx, who, v0, n, matrix, range))
         return rc;
+    if(ctx->yuv_out_siting != LFI_YUV_SITING_CENTRE)
+        return fail(ctx, LFI_EINVAL, std::string(who) + ": left-sited output (lfi_set_yuv_siting) is not supported: the chroma filter would mix the colour "
+                                                        "and the depth half in the column between them");
     if(int rc = check_scaled_tiles(ctx, tile_w, tile_h))
         return rc;
     if(tile_w % 2 || tile_h % 2)

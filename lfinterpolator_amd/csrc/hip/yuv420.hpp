@@ -10,6 +10,11 @@
 // last column or row is replicated).  The bracket lies in (0, 2²⁷): it is computed in u32 (the negative coefficients wrap, the sum does
 // not), one rounding, no shift of a negative number.
 //
+// Left siting (lfi_set_yuv_siting, include/lfi.h): the sums become Σ_j [R(xl, y_j) + 2·R(xc, y_j) + R(xr, y_j)] with xl = max(2cx − 1, 0), xc = 2cx,
+// xr = min(2cx + 1, W − 1) (total weight 8) and the sample min(255, (2²⁶ + 2¹⁸ + …) >> 19): the bracket lies in (0, 2²⁸], still u32.
+// yuv_chroma_left, yuv_block_chroma_left, and yuv_pack_sums / yuv_load_column / yuv_column_sums for the one pixel column a block needs from
+// outside itself; the kernel is yuvs_convert_left (yuv_surfaces.hpp).
+//
 // Here: YUV_COEFFS; the block shape of every YUV kernel (a lane owns 8 columns × 2 rows, a workgroup is 64 lanes × 4 block rows);
 // YuvSurfaces, the planes of a batch of frames as a kernel sees them; yuv_geometry, the tight host frame and the padded staged frame a host call's frames pass through on the device (Y pitch a multiple of 8,
 // chroma pitch of 4, an even number of Y rows: every word of a row lies inside it); yuv_luma and yuv_chroma; yuv_load_block, a lane's
@@ -90,6 +95,13 @@ __device__ inline uint32_t yuv_chroma(const int32_t (&c)[3], const uint32_t sr, 
     return v < 255u ? v : 255u;
 }
 
+// left siting: sr, sg, sb are the sums of weight 8; the bracket's true value lies in (0, 2²⁸]
+__device__ inline uint32_t yuv_chroma_left(const int32_t (&c)[3], const uint32_t sr, const uint32_t sg, const uint32_t sb)
+{
+    const uint32_t v = ((1u << 26) + (1u << 18) + (uint32_t)c[0] * sr + (uint32_t)c[1] * sg + (uint32_t)c[2] * sb) >> 19;
+    return v < 255u ? v : 255u;
+}
+
 // The R, G, B of a lane's block of 8 columns × 2 rows (rows ya and yb, columns x0 … x0 + 7 clamped to W − 1) of one view: RGBA planes
 // [H][W], or (PLANAR) byte planes [R,G,B][H][pitch].  whole: all 8 columns lie inside the view
 template <bool PLANAR>
@@ -154,6 +166,53 @@ __device__ __forceinline__ void yuv_load_block(const uint8_t *view, const uint32
     }
 }
 
+// left siting: the two-row sums of a pixel column's R, G and B (≤ 510 each), ten bits apiece
+__device__ __forceinline__ uint32_t yuv_pack_sums(const uint32_t r, const uint32_t g, const uint32_t b)
+{
+    return r | (g << 10) | (b << 20);
+}
+
+// Pixel column x < W, rows ya and yb, of one view, as loaded: six bytes of PLANAR views (R, G, B of row ya, then of yb), two RGBA dwords.
+// The loads only — yuv_column_sums adds them up where the value is needed, so that the loads are in flight beside the block's own
+template <bool PLANAR>
+struct YuvColumn
+{
+    uint32_t v[PLANAR ? 6 : 2];
+};
+
+template <bool PLANAR>
+__device__ __forceinline__ YuvColumn<PLANAR> yuv_load_column(const uint8_t *view, const uint32_t W, const uint32_t H, const uint32_t pitch, const uint32_t x,
+                                                             const uint32_t ya, const uint32_t yb)
+{
+    YuvColumn<PLANAR> c;
+    if constexpr(PLANAR)
+    {
+        const size_t plane = (size_t)H * pitch;
+        const uint8_t *pa = view + (size_t)ya * pitch + x, *pb = view + (size_t)yb * pitch + x;
+#pragma unroll
+        for(int k = 0; k < 3; k++)
+            c.v[k] = pa[k * plane], c.v[3 + k] = pb[k * plane];
+    }
+    else
+    {
+        const uint32_t *px = reinterpret_cast<const uint32_t *>(view);
+        c.v[0] = px[(size_t)ya * W + x], c.v[1] = px[(size_t)yb * W + x];
+    }
+    return c;
+}
+
+template <bool PLANAR>
+__device__ __forceinline__ uint32_t yuv_column_sums(const YuvColumn<PLANAR> &c)
+{
+    if constexpr(PLANAR)
+        return yuv_pack_sums(c.v[0] + c.v[3], c.v[1] + c.v[4], c.v[2] + c.v[5]);
+    else
+    {
+        const uint32_t p = c.v[0], q = c.v[1];
+        return yuv_pack_sums((p & 0xffu) + (q & 0xffu), ((p >> 8) & 0xffu) + ((q >> 8) & 0xffu), ((p >> 16) & 0xffu) + ((q >> 16) & 0xffu));
+    }
+}
+
 // Cb and Cr of the block's chroma column i: the sums over its four pixels
 __device__ __forceinline__ void yuv_block_chroma(const YuvCoeffs &k, const uint32_t (&r)[2][8], const uint32_t (&g)[2][8], const uint32_t (&b)[2][8], const int i,
                                                  uint32_t &cb, uint32_t &cr)
@@ -163,6 +222,24 @@ __device__ __forceinline__ void yuv_block_chroma(const YuvCoeffs &k, const uint3
     const uint32_t sb = b[0][2 * i] + b[0][2 * i + 1] + b[1][2 * i] + b[1][2 * i + 1];
     cb = yuv_chroma(k.cb, sr, sg, sb);
     cr = yuv_chroma(k.cr, sr, sg, sb);
+}
+
+// Left siting: Cb and Cr of the block's chroma column i from v(2i − 1) + 2·v(2i) + v(2i + 1), v(k) the two-row sums of block column k.
+// left: v(−1) as yuv_pack_sums packs it — the sums of pixel column x0 − 1 (of column 0 where x0 = 0), all a block needs from outside itself
+__device__ __forceinline__ void yuv_block_chroma_left(const YuvCoeffs &k, const uint32_t (&r)[2][8], const uint32_t (&g)[2][8], const uint32_t (&b)[2][8],
+                                                      const uint32_t left, const int i, uint32_t &cb, uint32_t &cr)
+{
+    const int c = 2 * i, n = 2 * i + 1;
+    uint32_t lr, lg, lb;
+    if(i == 0)
+        lr = left & 0x3ffu, lg = (left >> 10) & 0x3ffu, lb = left >> 20;
+    else
+        lr = r[0][c - 1] + r[1][c - 1], lg = g[0][c - 1] + g[1][c - 1], lb = b[0][c - 1] + b[1][c - 1];
+    const uint32_t sr = lr + 2u * (r[0][c] + r[1][c]) + r[0][n] + r[1][n];
+    const uint32_t sg = lg + 2u * (g[0][c] + g[1][c]) + g[0][n] + g[1][n];
+    const uint32_t sb = lb + 2u * (b[0][c] + b[1][c]) + b[0][n] + b[1][n];
+    cb = yuv_chroma_left(k.cb, sr, sg, sb);
+    cr = yuv_chroma_left(k.cr, sr, sg, sb);
 }
 
 } // namespace lfi

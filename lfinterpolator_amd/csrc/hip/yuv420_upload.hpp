@@ -10,6 +10,10 @@
 //     R = clamp((l + rV·v + 2¹⁹) >> 20, 0, 255)    G = clamp((l + gU·u + gV·v + 2¹⁹) >> 20, 0, 255)    B = clamp((l + bU·u + 2¹⁹) >> 20, 0, 255)
 // A = 255.  The bracket stays within ±573,111,632: int32 with an arithmetic shift, one rounding.
 //
+// Left siting (lfi_set_yuv_siting, include/lfi.h), BILINEAR: h(r) = 4·U[r][cx] (even x), 2·U[r][cx] + 2·U[r][min(cx + 1, cw − 1)] (odd x) and
+// SU = 3·h(cy) + h(ny), again sixteenths; NEAREST is the same under either siting.  yuv_in_columns_left and yuv_in_row_left: the window
+// without its left column.
+//
 // Here: YUV_IN_COEFFS; yuv_in_pixel and yuv_in_clamp, one RGBA dword from a luma code and chroma in sixteenths; yuv_in_bytes; yuv_in_columns
 // and yuv_in_row, the bilinear filter's six-column window of a lane with the definition's clamp as byte positions; yuv_in_store, a lane's
 // 8 × 2 pixels into its image, 16-byte stores where the block is whole and the rows are aligned, else dwords, none outside the image.
@@ -87,6 +91,28 @@ __device__ __forceinline__ void yuv_in_row(const uint64_t win, const uint32_t (&
 #pragma unroll
     for(int i = 0; i < 8; i++)
         h[i] = 3 * c[1 + (i >> 1)] + c[(i & 1) ? 2 + (i >> 1) : (i >> 1)];
+}
+
+// Left siting: the five chroma columns 4bx … 4bx + 4 of a lane, clamped to cw − 1, as bit positions in its window of five bytes [the lane's
+// own four | column 4bx + 4]: a clamped column is a byte of the lane's own four (cw − 1 ≥ 4bx)
+__device__ __forceinline__ void yuv_in_columns_left(const uint32_t bx, const uint32_t cw, uint32_t (&sh)[5])
+{
+    const uint32_t c0 = 4u * bx;
+#pragma unroll
+    for(int i = 0; i < 5; i++)
+        sh[i] = 8u * ((c0 + i > cw - 1u ? cw - 1u : c0 + i) - c0);
+}
+
+// h[i] of pixel column i of one chroma row's window, in quarters: 4·(its own column) where i is even, else 2·(its own) + 2·(the next one)
+__device__ __forceinline__ void yuv_in_row_left(const uint64_t win, const uint32_t (&sh)[5], int32_t (&h)[8])
+{
+    int32_t c[5];
+#pragma unroll
+    for(int i = 0; i < 5; i++)
+        c[i] = (int32_t)((uint32_t)(win >> sh[i]) & 0xffu);
+#pragma unroll
+    for(int i = 0; i < 8; i++)
+        h[i] = (i & 1) ? 2 * c[i >> 1] + 2 * c[(i >> 1) + 1] : 4 * c[i >> 1];
 }
 
 // a block's pixels into its image: out addresses pixel (x0, ya) of rows of W pixels.  Whole blocks of 16-byte aligned rows leave as 16-byte

@@ -22,6 +22,10 @@
 // No atomics, no read of the destination, no store outside [0, pitch) of the rows the context holds: pieces at or beyond the pitch (a
 // multiple of 16), rows beyond H (an odd H's last block row) and block rows beyond ch are skipped.  W < 8 and ragged last blocks need no
 // path of their own: bytes of columns beyond W − 1 are in LDS and never picked (a piece inside the image ends at or before W − 1).
+//
+// Left-sited chroma (lfi_set_yuv_siting): yuvs_derived_expand_left<FORMAT>, a kernel of its own name (tests pin the four bodies of
+// yuvs_derived_expand) with the same body, yuvs_derived_spans — only step 1's pixels differ: yuvs_block_pixels<FORMAT, false, true>, one
+// chroma load fewer per row and plane.  NEAREST is the same bytes under either siting and launches yuvs_derived_expand<FORMAT, true>.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -52,8 +56,9 @@ struct YuvsDerivedArgs
     uint32_t g0;          // frame z is image g0 + z
 };
 
-template <int FORMAT, bool NEAREST>
-__global__ void __launch_bounds__(YUVD_THREADS) yuvs_derived_expand(const YuvsDerivedArgs a)
+// the whole kernel; LEFT: left-sited chroma (yuvs_block_pixels' filter), the staging and the stores are the same
+template <int FORMAT, bool NEAREST, bool LEFT>
+__device__ __forceinline__ void yuvs_derived_spans(const YuvsDerivedArgs &a)
 {
     __shared__ __attribute__((aligned(16))) uint8_t lds[YUVD_ROWS][2][3][YUVD_LDS_PITCH];
     const uint32_t tid = threadIdx.x;
@@ -72,7 +77,7 @@ __global__ void __launch_bounds__(YUVD_THREADS) yuvs_derived_expand(const YuvsDe
         if(r < (uint32_t)YUVD_ROWS && b < nb && by < a.in.ch)
         {
             uint32_t px[2][8];
-            yuvs_block_pixels<FORMAT, NEAREST>(a.in, a.in.s.base + (size_t)blockIdx.z * a.in.s.frame_stride, bx_lo + b, by, px);
+            yuvs_block_pixels<FORMAT, NEAREST, LEFT>(a.in, a.in.s.base + (size_t)blockIdx.z * a.in.s.frame_stride, bx_lo + b, by, px);
 #pragma unroll
             for(int j = 0; j < 2; j++)
 #pragma unroll
@@ -119,12 +124,33 @@ __global__ void __launch_bounds__(YUVD_THREADS) yuvs_derived_expand(const YuvsDe
     }
 }
 
+template <int FORMAT, bool NEAREST>
+__global__ void __launch_bounds__(YUVD_THREADS) yuvs_derived_expand(const YuvsDerivedArgs a)
+{
+    yuvs_derived_spans<FORMAT, NEAREST, false>(a);
+}
+
+// left-sited chroma, BILINEAR (NEAREST is yuvs_derived_expand's under either siting)
+template <int FORMAT>
+__global__ void __launch_bounds__(YUVD_THREADS) yuvs_derived_expand_left(const YuvsDerivedArgs a)
+{
+    yuvs_derived_spans<FORMAT, false, true>(a);
+}
+
 // Enqueues the ONE yuvs_derived_expand launch for n frames.  The caller has checked sizes, alignment and memory as for launch_yuvs_expand;
 // a.planar holds images [g0, g0 + n) with a.in.H rows of a.pitch bytes per plane, a.pitch a multiple of 16.
-inline hipError_t launch_yuvs_derived_expand(hipStream_t stream, const int format, const bool nearest, const YuvsDerivedArgs &a, const int n)
+inline hipError_t launch_yuvs_derived_expand(hipStream_t stream, const int format, const bool nearest, const bool left, const YuvsDerivedArgs &a,
+                                             const int n)
 {
     const dim3 grid((a.pitch + YUVD_SPAN - 1) / YUVD_SPAN, (a.in.ch + YUVD_ROWS - 1) / YUVD_ROWS, n), block(YUVD_THREADS);
-    if(format == YUVS_NV12)
+    if(left && !nearest)
+    {
+        if(format == YUVS_NV12)
+            hipLaunchKernelGGL((yuvs_derived_expand_left<YUVS_NV12>), grid, block, 0, stream, a);
+        else
+            hipLaunchKernelGGL((yuvs_derived_expand_left<YUVS_I420>), grid, block, 0, stream, a);
+    }
+    else if(format == YUVS_NV12)
     {
         if(nearest)
             hipLaunchKernelGGL((yuvs_derived_expand<YUVS_NV12, true>), grid, block, 0, stream, a);

@@ -42,6 +42,17 @@
 //     own bytes — pitch padding keeps its value: every whole block stores words (Y two 8-byte pieces, a wave's run 512 bytes; I420 a dword
 //     each of Cb and Cr, runs of 256; NV12 one interleaved 8-byte piece), a ragged last block of a row stores its valid bytes one by one,
 //     and a row beyond H is not stored.
+//
+// LEFT-SITED chroma (lfi_set_yuv_siting; MPEG-2 / H.264 siting, include/lfi.h) has kernels of its own names — tests pin the number of
+// yuvs_expand and yuvs_convert bodies — that ARE the bodies above (yuvs_expand_block, yuvs_convert_block) with the filter as a template
+// parameter; decomposition, alignment contract, loads of Y and of the views, and every store are the same.
+//   yuvs_convert_left<PLANAR, FORMAT>   chroma column i of a lane is v(2i − 1) + 2·v(2i) + v(2i + 1), v(k) the two-row sum of block column k.
+//     The one value from outside the block, v(−1), is the left neighbour lane's column 7: its three sums (≤ 510 each) packed into one dword
+//     cross with ONE DPP move (wave_shr:1) — no second read of the view.  Lane 0 of a wave with bx > 0 loads pixel column x0 − 1 itself (inside
+//     the view: x0 − 1 < W, rows ya and yb); bx = 0 clamps to its own column 0.  The clamp on the right is a column yuv_load_block replicated.
+//   yuvs_expand_left<FORMAT>            BILINEAR only (NEAREST is the same bytes under either siting: yuvs_expand<FORMAT, true> is launched).
+//     The window of yuv_in_columns / yuv_in_row without its left column: [own four | column 4bx + 4], one load fewer per chroma row and
+//     plane; the dword right of the lane's own is read only where bx + 1 < blocks_x, as above, and a clamped column is a byte of the lane's own.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -85,7 +96,7 @@ __device__ __forceinline__ uint32_t yuvs_component(const uint32_t lo, const uint
 // The RGBA dwords px of block (bx, by) of a frame: bx < a.blocks_x, by < a.ch.  Everything yuvs_expand reads and computes — its loads, its
 // clamps, its arithmetic —, for the kernels that differ only in where the pixels go: yuvs_expand (the RGBA planes) and yuvs_derived_expand
 // (yuv_derived.hpp: the planar copy).  Columns beyond W and the second row of an odd H's last block row hold values that are never stored.
-template <int FORMAT, bool NEAREST>
+template <int FORMAT, bool NEAREST, bool LEFT = false>
 __device__ __forceinline__ void yuvs_block_pixels(const YuvsInArgs &a, const uint8_t *frame, const uint32_t bx, const uint32_t by, uint32_t (&px)[2][8])
 {
     const uint32_t x0 = bx * YUV_BLOCK_W, ya = by * YUV_BLOCK_H; // x0 < W, ya < H
@@ -116,9 +127,14 @@ __device__ __forceinline__ void yuvs_block_pixels(const YuvsInArgs &a, const uin
     }
     else
     {
-        uint32_t sh[6];
-        yuv_in_columns(bx, a.cw, sh);
-        const bool has_l = bx > 0, has_r = bx + 1u < a.blocks_x;
+        // LEFT: the window without its left column — five columns, one load fewer per chroma row
+        uint32_t sh[LEFT ? 5 : 6];
+        if constexpr(LEFT)
+            yuv_in_columns_left(bx, a.cw, sh);
+        else
+            yuv_in_columns(bx, a.cw, sh);
+        constexpr int OWN = LEFT ? 0 : 8; // the bit of the window at which the lane's own four columns begin
+        const bool has_l = !LEFT && bx > 0, has_r = bx + 1u < a.blocks_x;
         // rows by − 1, by, by + 1, clamped to [0, ch − 1]
         const uint32_t rows[3] = {by > 0 ? by - 1u : 0u, by, by + 1u < a.ch ? by + 1u : a.ch - 1u};
         int32_t hu[3][8], hv[3][8];
@@ -132,12 +148,14 @@ __device__ __forceinline__ void yuvs_block_pixels(const YuvsInArgs &a, const uin
             {
                 const uint8_t *row = c_plane + (size_t)rows[r] * a.s.c_pitch + 8u * bx;
                 const uint2 own = *reinterpret_cast<const uint2 *>(row);
-                const uint32_t left = has_l ? *reinterpret_cast<const uint32_t *>(row - 4) : 0u;
+                uint32_t left = 0u;
+                if constexpr(!LEFT)
+                    left = has_l ? *reinterpret_cast<const uint32_t *>(row - 4) : 0u;
                 const uint32_t right = has_r ? *reinterpret_cast<const uint32_t *>(row + 8) : 0u;
 #pragma unroll
                 for(int p = 0; p < 2; p++)
-                    win[p] = (uint64_t)((left >> (16 + 8 * p)) & 0xffu) | ((uint64_t)yuvs_component(own.x, own.y, p) << 8) |
-                             ((uint64_t)((right >> (8 * p)) & 0xffu) << 40);
+                    win[p] = (uint64_t)((left >> (16 + 8 * p)) & 0xffu) | ((uint64_t)yuvs_component(own.x, own.y, p) << OWN) |
+                             ((uint64_t)((right >> (8 * p)) & 0xffu) << (32 + OWN));
             }
             else
             {
@@ -145,14 +163,20 @@ __device__ __forceinline__ void yuvs_block_pixels(const YuvsInArgs &a, const uin
                 for(int p = 0; p < 2; p++)
                 {
                     const uint32_t *row = reinterpret_cast<const uint32_t *>(frame + (p ? a.s.cr_offset : a.s.c_offset) + (size_t)rows[r] * a.s.c_pitch) + bx;
-                    const uint32_t own = row[0], left = has_l ? row[-1] : 0u, right = has_r ? row[1] : 0u;
-                    win[p] = (uint64_t)(left >> 24) | ((uint64_t)own << 8) | ((uint64_t)(right & 0xffu) << 40);
+                    uint32_t left = 0u;
+                    if constexpr(!LEFT)
+                        left = has_l ? row[-1] : 0u;
+                    const uint32_t own = row[0], right = has_r ? row[1] : 0u;
+                    win[p] = (uint64_t)(left >> 24) | ((uint64_t)own << OWN) | ((uint64_t)(right & 0xffu) << (32 + OWN));
                 }
             }
-            yuv_in_row(win[0], sh, hu[r]);
-            yuv_in_row(win[1], sh, hv[r]);
+            if constexpr(LEFT)
+                yuv_in_row_left(win[0], sh, hu[r]), yuv_in_row_left(win[1], sh, hv[r]);
+            else
+                yuv_in_row(win[0], sh, hu[r]), yuv_in_row(win[1], sh, hv[r]);
         }
-        // 9·a + 3·b + 3·c + d = 3·(3a + b) + (3c + d): an even row's neighbour row is the one above, an odd row's the one below
+        // 9·a + 3·b + 3·c + d = 3·(3a + b) + (3c + d): an even row's neighbour row is the one above, an odd row's the one below (LEFT: the
+        // rows' h are in quarters, 3·h(cy) + h(ny))
 #pragma unroll
         for(int j = 0; j < 2; j++)
 #pragma unroll
@@ -166,8 +190,8 @@ __device__ __forceinline__ void yuvs_block_pixels(const YuvsInArgs &a, const uin
             px[j][i] = yuv_in_pixel(a.k, (int32_t)y[j][i], su[j][i], sv[j][i]);
 }
 
-template <int FORMAT, bool NEAREST>
-__global__ void __launch_bounds__(YUV_LANES_X *YUV_BLOCK_ROWS) yuvs_expand(const YuvsInArgs a)
+template <int FORMAT, bool NEAREST, bool LEFT>
+__device__ __forceinline__ void yuvs_expand_block(const YuvsInArgs &a)
 {
     const uint32_t bx = blockIdx.x * YUV_LANES_X + threadIdx.x;
     const uint32_t by = blockIdx.y * YUV_BLOCK_ROWS + threadIdx.y; // wave-uniform
@@ -175,13 +199,26 @@ __global__ void __launch_bounds__(YUV_LANES_X *YUV_BLOCK_ROWS) yuvs_expand(const
         return;
     const uint32_t x0 = bx * YUV_BLOCK_W, ya = by * YUV_BLOCK_H; // x0 < W, ya < H
     uint32_t px[2][8];
-    yuvs_block_pixels<FORMAT, NEAREST>(a, a.s.base + (size_t)blockIdx.z * a.s.frame_stride, bx, by, px);
+    yuvs_block_pixels<FORMAT, NEAREST, LEFT>(a, a.s.base + (size_t)blockIdx.z * a.s.frame_stride, bx, by, px);
     uint32_t *out = reinterpret_cast<uint32_t *>(a.dst + (size_t)blockIdx.z * a.image_stride) + (size_t)ya * a.W + x0;
     yuv_in_store(out, a.W, x0, ya + 1u < a.H, a.rows16, px);
 }
 
-template <bool PLANAR, int FORMAT>
-__global__ void __launch_bounds__(YUV_LANES_X *YUV_BLOCK_ROWS) yuvs_convert(const YuvsOutArgs a)
+template <int FORMAT, bool NEAREST>
+__global__ void __launch_bounds__(YUV_LANES_X *YUV_BLOCK_ROWS) yuvs_expand(const YuvsInArgs a)
+{
+    yuvs_expand_block<FORMAT, NEAREST, false>(a);
+}
+
+// left-sited chroma, BILINEAR (NEAREST is yuvs_expand's under either siting)
+template <int FORMAT>
+__global__ void __launch_bounds__(YUV_LANES_X *YUV_BLOCK_ROWS) yuvs_expand_left(const YuvsInArgs a)
+{
+    yuvs_expand_block<FORMAT, false, true>(a);
+}
+
+template <bool PLANAR, int FORMAT, bool LEFT>
+__device__ __forceinline__ void yuvs_convert_block(const YuvsOutArgs &a)
 {
     const uint32_t bx = blockIdx.x * YUV_LANES_X + threadIdx.x;
     const uint32_t by = blockIdx.y * YUV_BLOCK_ROWS + threadIdx.y; // wave-uniform
@@ -192,7 +229,14 @@ __global__ void __launch_bounds__(YUV_LANES_X *YUV_BLOCK_ROWS) yuvs_convert(cons
     const uint32_t ya = by * YUV_BLOCK_H, yb = two_rows ? ya + 1u : ya; // ya < H: by < ch
     const bool whole = x0 + YUV_BLOCK_W <= a.src.W;                       // all 8 columns inside the view
     uint32_t r[2][8], g[2][8], b[2][8];
-    yuv_load_block<PLANAR>(a.src.base + (size_t)blockIdx.z * a.src.view_stride, a.src.W, a.src.H, a.src.pitch, a.rows16, x0, ya, yb, whole, r, g, b);
+    const uint8_t *view = a.src.base + (size_t)blockIdx.z * a.src.view_stride;
+    // LEFT: lane 0 of a wave has no lane to its left and loads pixel column x0 − 1 itself (bx > 0: it lies inside the view) — issued here, ahead
+    // of the block's own loads and added up only where the chroma needs it, so that it costs the wave no memory round trip of its own
+    [[maybe_unused]] YuvColumn<PLANAR> edge{};
+    if constexpr(LEFT)
+        if(threadIdx.x == 0 && bx)
+            edge = yuv_load_column<PLANAR>(view, a.src.W, a.src.H, a.src.pitch, x0 - 1u, ya, yb);
+    yuv_load_block<PLANAR>(view, a.src.W, a.src.H, a.src.pitch, a.rows16, x0, ya, yb, whole, r, g, b);
     uint8_t *frame = a.s.base + (size_t)blockIdx.z * a.s.frame_stride;
     // Y: the row's own bytes only, and no row beyond H
 #pragma unroll
@@ -216,9 +260,29 @@ __global__ void __launch_bounds__(YUV_LANES_X *YUV_BLOCK_ROWS) yuvs_convert(cons
         }
     }
     uint32_t cb[4], cr[4];
+    if constexpr(LEFT)
+    {
+        // The one value from outside the block: the two-row sums of pixel column x0 − 1, the left neighbour lane's column 7, which that lane
+        // holds in registers — ONE cross-lane move (DPP wave_shr:1: lane l takes lane l − 1's) in place of a second read of the view.  The
+        // move stands behind the early return: the lanes with bx ≥ blocks_x are off, but a source lane bx − 1 < bx is always on, and it is
+        // always a whole block (8·bx ≤ W − 1), so its column 7 is pixel column x0 − 1 and no replicated one.  Lane 0 of a wave has no
+        // source lane and keeps `old`: it takes the column x0 − 1 it loaded above, or clamps to its own column 0 where bx = 0
+        const uint32_t mine = yuv_pack_sums(r[0][7] + r[1][7], g[0][7] + g[1][7], b[0][7] + b[1][7]);
+        uint32_t left = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)mine, 0x138, 0xf, 0xf, false);
+        if(threadIdx.x == 0)
+            left = bx ? yuv_column_sums<PLANAR>(edge)
+                      : yuv_pack_sums(r[0][0] + r[1][0], g[0][0] + g[1][0], b[0][0] + b[1][0]);
+        // xr = min(2cx + 1, W − 1) is a column of the block: yuv_load_block has replicated the last column into those beyond the view
 #pragma unroll
-    for(int i = 0; i < 4; i++)
-        yuv_block_chroma(a.k, r, g, b, i, cb[i], cr[i]);
+        for(int i = 0; i < 4; i++)
+            yuv_block_chroma_left(a.k, r, g, b, left, i, cb[i], cr[i]);
+    }
+    else
+    {
+#pragma unroll
+        for(int i = 0; i < 4; i++)
+            yuv_block_chroma(a.k, r, g, b, i, cb[i], cr[i]);
+    }
     const uint32_t c0 = 4u * bx; // < cw: x0 < W
     const bool c_whole = c0 + 4u <= a.cw;
     if constexpr(FORMAT == YUVS_NV12)
@@ -252,6 +316,19 @@ __global__ void __launch_bounds__(YUV_LANES_X *YUV_BLOCK_ROWS) yuvs_convert(cons
     }
 }
 
+template <bool PLANAR, int FORMAT>
+__global__ void __launch_bounds__(YUV_LANES_X *YUV_BLOCK_ROWS) yuvs_convert(const YuvsOutArgs a)
+{
+    yuvs_convert_block<PLANAR, FORMAT, false>(a);
+}
+
+// left-sited chroma
+template <bool PLANAR, int FORMAT>
+__global__ void __launch_bounds__(YUV_LANES_X *YUV_BLOCK_ROWS) yuvs_convert_left(const YuvsOutArgs a)
+{
+    yuvs_convert_block<PLANAR, FORMAT, true>(a);
+}
+
 inline dim3 yuvs_grid(const uint32_t blocks_x, const uint32_t ch, const int n)
 {
     return dim3((blocks_x + YUV_LANES_X - 1) / YUV_LANES_X, (ch + YUV_BLOCK_ROWS - 1) / YUV_BLOCK_ROWS, n);
@@ -259,10 +336,17 @@ inline dim3 yuvs_grid(const uint32_t blocks_x, const uint32_t ch, const int n)
 
 // Enqueues the ONE yuvs_expand launch for n frames.  The caller has checked sizes, alignment and memory: n ≥ 1, a.s describes n frames the
 // device may read, a.dst holds n images.
-inline hipError_t launch_yuvs_expand(hipStream_t stream, const int format, const bool nearest, const YuvsInArgs &a, const int n)
+inline hipError_t launch_yuvs_expand(hipStream_t stream, const int format, const bool nearest, const bool left, const YuvsInArgs &a, const int n)
 {
     const dim3 grid = yuvs_grid(a.blocks_x, a.ch, n), block(YUV_LANES_X, YUV_BLOCK_ROWS);
-    if(format == YUVS_NV12)
+    if(left && !nearest) // a left-sited nearest upload is the nearest kernel: the same bytes
+    {
+        if(format == YUVS_NV12)
+            hipLaunchKernelGGL((yuvs_expand_left<YUVS_NV12>), grid, block, 0, stream, a);
+        else
+            hipLaunchKernelGGL((yuvs_expand_left<YUVS_I420>), grid, block, 0, stream, a);
+    }
+    else if(format == YUVS_NV12)
     {
         if(nearest)
             hipLaunchKernelGGL((yuvs_expand<YUVS_NV12, true>), grid, block, 0, stream, a);
@@ -281,10 +365,27 @@ inline hipError_t launch_yuvs_expand(hipStream_t stream, const int format, const
 
 // Enqueues the ONE yuvs_convert launch for n views.  The caller has checked sizes, alignment and memory: a.s describes n frames the device
 // may write.
-inline hipError_t launch_yuvs_convert(hipStream_t stream, const bool planar, const int format, const YuvsOutArgs &a, const int n)
+inline hipError_t launch_yuvs_convert(hipStream_t stream, const bool planar, const int format, const bool left, const YuvsOutArgs &a, const int n)
 {
     const dim3 grid = yuvs_grid(a.blocks_x, a.ch, n), block(YUV_LANES_X, YUV_BLOCK_ROWS);
-    if(planar)
+    if(left)
+    {
+        if(planar)
+        {
+            if(format == YUVS_NV12)
+                hipLaunchKernelGGL((yuvs_convert_left<true, YUVS_NV12>), grid, block, 0, stream, a);
+            else
+                hipLaunchKernelGGL((yuvs_convert_left<true, YUVS_I420>), grid, block, 0, stream, a);
+        }
+        else
+        {
+            if(format == YUVS_NV12)
+                hipLaunchKernelGGL((yuvs_convert_left<false, YUVS_NV12>), grid, block, 0, stream, a);
+            else
+                hipLaunchKernelGGL((yuvs_convert_left<false, YUVS_I420>), grid, block, 0, stream, a);
+        }
+    }
+    else if(planar)
     {
         if(format == YUVS_NV12)
             hipLaunchKernelGGL((yuvs_convert<true, YUVS_NV12>), grid, block, 0, stream, a);

@@ -234,6 +234,32 @@ int lfi_host_y4m_write(const char *path, const uint8_t *frames, int n, size_t fr
     }
 }
 
+// lfi_host_y4m_write with the chroma's siting: left_sited != 0 writes C420mpeg2 in place of C420jpeg
+int lfi_host_y4m_write_sited(const char *path, const uint8_t *frames, int n, size_t frame_stride_bytes, int width, int height, int fps_num, int fps_den,
+                             int full_range, int left_sited, char *err, size_t err_len)
+{
+    try
+    {
+        if(!path)
+            throw std::runtime_error("path must be non-NULL");
+        lfi::writeY4m(path, frames, n, frame_stride_bytes, width, height, fps_num, fps_den, full_range != 0, left_sited != 0);
+        return 0;
+    }
+    catch(const std::exception &e)
+    {
+        return report(e, err, err_len);
+    }
+}
+
+// y4mInputSiting (y4m.h): the siting (0 centre, 1 left) a file tagged C<chroma_tag> is read with under mode 0 centre, 1 left, 2 auto; -1 for
+// a NULL tag or an unknown mode
+int lfi_host_y4m_input_siting(const char *chroma_tag, int mode)
+{
+    if(!chroma_tag || mode < lfi::Y4M_SITE_CENTRE || mode > lfi::Y4M_SITE_AUTO)
+        return -1;
+    return lfi::y4mInputSiting(chroma_tag, mode);
+}
+
 // the Y4M reader (y4m.h): out = {width, height, fps_num, fps_den, frames, full_range (1, 0, -1: no XCOLORRANGE), centre_sited, 0}, the C tag
 // without its C into chroma_tag (may be NULL); returns 0 or -1 (message in err)
 int lfi_host_y4m_info(const char *path, int32_t out[8], char *chroma_tag, size_t chroma_tag_len, char *err, size_t err_len)

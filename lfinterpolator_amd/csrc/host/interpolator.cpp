@@ -21,7 +21,7 @@
 
 int Interpolator::defaultDevice = 0;
 
-Interpolator::Interpolator(std::string inputPath) : input{inputPath}
+Interpolator::Interpolator(std::string inputPath, int inChromaSite) : input{inputPath}, inSiteMode{inChromaSite}
 {
     init();
 }
@@ -133,6 +133,7 @@ void Interpolator::uploadVideoFrame()
     check(lfi_upload_wait(context)); // the previous step's copies have left the frames' memory
     video->loadFrames(inputFrame, inFrames, frameBytes);
     const int range = inRange >= 0 ? inRange : (video->videoFullRange() == 1 ? LFI_YUV_FULL : LFI_YUV_LIMITED);
+    check(lfi_set_yuv_siting(context, inSiting, outSiting)); // governs both calls below, lean inputs included
     if(inputsReleased)
     {
         // lean inputs: the context holds only the derived planar copy, the frames go straight into it
@@ -184,9 +185,15 @@ void Interpolator::loadGPUData()
     if(lfLoader.isVideo())
     {
         // a light-field video: interpolate() uploads the time step it renders
-        if(!lfLoader.videoCentreSited())
+        if(inSiteMode == lfi::Y4M_SITE_AUTO && !lfLoader.videoChromaAgrees())
+            throw std::runtime_error("--in-chroma-site auto: the videos of " + input + " do not carry the same chroma tag (C420jpeg, C420mpeg2, ...)!");
+        inSiting = lfi::y4mInputSiting(lfLoader.videoChroma(), inSiteMode);
+        if(inSiting == LFI_YUV_SITING_LEFT)
+            std::cout << "The videos' chroma is read as left-sited (C420mpeg2)." << std::endl;
+        else if(!lfLoader.videoCentreSited())
             std::cout << "Note: the videos are C" << lfLoader.videoChroma()
-                      << "; their chroma is read as centre-sited (C420jpeg), at most a quarter pixel from where it was sampled." << std::endl;
+                      << "; their chroma is read as centre-sited (C420jpeg), at most a quarter pixel from where it was sampled"
+                      << (inSiteMode == lfi::Y4M_SITE_AUTO ? "." : " (--in-chroma-site left or auto reads C420mpeg2 where it was sampled).") << std::endl;
         video = std::move(loader);
         return;
     }
@@ -225,6 +232,8 @@ void Interpolator::interpolate(std::string outputPath, std::string trajectory, f
         if(gpuCount > 1)
             throw std::runtime_error("Lean inputs work on one GPU only!");
     }
+    if(outSiting != LFI_YUV_SITING_CENTRE && !rgbdY4mPath.empty())
+        throw std::runtime_error("An RGB-D video frame cannot be left-sited: the chroma filter would mix the colour and the depth half (--chroma-site left with --rgbd-y4m)!");
     if(video && loadedFrame != inputFrame)
         uploadVideoFrame();
     if(quiltTile.x > 0 || quiltTile.y > 0)
@@ -661,10 +670,11 @@ void Interpolator::storeResults(std::string path)
         {
             lfi_yuv_surfaces surface{};
             check(lfi_yuv_surfaces_packed(LFI_YUV_I420, LFI_MEM_HOST, frame, quiltW, quiltH, &surface));
+            check(lfi_set_yuv_siting(context, inSiting, outSiting));
             check(lfi_download_quilt_yuv(context, quiltTiles.x, quiltTiles.y, 0, tile.x, tile.y, yuvMatrix, yuvRange, &surface));
             // one file for all time steps of a light-field video: opened by the first, appended to by the others, closed by finish()
             if(!quiltY4mWriter)
-                quiltY4mWriter = std::make_unique<lfi::Y4mWriter>(quiltY4mPath, quiltW, quiltH, y4mFps.x, y4mFps.y, yuvRange == LFI_YUV_FULL);
+                quiltY4mWriter = std::make_unique<lfi::Y4mWriter>(quiltY4mPath, quiltW, quiltH, y4mFps.x, y4mFps.y, yuvRange == LFI_YUV_FULL, outSiting == LFI_YUV_SITING_LEFT);
             quiltY4mWriter->writeFrame(frame);
         }
         catch(...)
@@ -738,11 +748,13 @@ void Interpolator::storeResults(std::string path)
         try
         {
             for(int g = 0; g < gpuCount; g++)
+                check(lfi_set_yuv_siting(contexts[g], inSiting, outSiting), contexts[g]);
+            for(int g = 0; g < gpuCount; g++)
                 check(lfi_download_views_yuv420(contexts[g], 0, viewStart[g + 1] - viewStart[g], yuvMatrix, yuvRange, frames + frameBytes * viewStart[g], frameBytes),
                       contexts[g]);
             // one file for all time steps of a light-field video: opened by the first, appended to by the others, closed by finish()
             if(!y4mWriter)
-                y4mWriter = std::make_unique<lfi::Y4mWriter>(y4mPath, resolution.x, resolution.y, y4mFps.x, y4mFps.y, yuvRange == LFI_YUV_FULL);
+                y4mWriter = std::make_unique<lfi::Y4mWriter>(y4mPath, resolution.x, resolution.y, y4mFps.x, y4mFps.y, yuvRange == LFI_YUV_FULL, outSiting == LFI_YUV_SITING_LEFT);
             for(int i = 0; i < viewCount; i++)
                 y4mWriter->writeFrame(frames + frameBytes * i);
         }
@@ -773,6 +785,7 @@ void Interpolator::storeResults(std::string path)
             for(int g = 0; g < gpuCount; g++)
             {
                 lfi_yuv_surfaces surfaces{};
+                check(lfi_set_yuv_siting(contexts[g], inSiting, outSiting), contexts[g]);
                 check(lfi_yuv_surfaces_packed(LFI_YUV_NV12, LFI_MEM_HOST, frames + frameBytes * viewStart[g], resolution.x, resolution.y, &surfaces), contexts[g]);
                 check(lfi_download_views_yuv(contexts[g], 0, viewStart[g + 1] - viewStart[g], yuvMatrix, yuvRange, &surfaces), contexts[g]);
             }

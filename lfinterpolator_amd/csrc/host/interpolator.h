@@ -22,7 +22,9 @@ class LfLoader;
 class Interpolator
 {
     public:
-        Interpolator(std::string inputPath);
+        // inChromaSite: how the chroma of a light-field video's frames is sited — lfi::Y4M_SITE_CENTRE, _LEFT or _AUTO (by the files' C tag:
+        // C420mpeg2 left, everything else centre; the cameras' tags must agree then)
+        Interpolator(std::string inputPath, int inChromaSite = lfi::Y4M_SITE_CENTRE);
         ~Interpolator();
         void interpolate(std::string outputPath, std::string trajectory, float focus, float range, std::string method, float effect, float aspect);
 
@@ -114,6 +116,10 @@ class Interpolator
         // derived planar copy of the inputs (lfi_release_inputs), and every later step's frames go straight into it
         // (lfi_upload_images_yuv_derived) — less than half the device memory, one pass per step.  The files written are the same
         void setLeanInputs(bool on) { leanInputs = on; }
+        // the chroma siting of the frames written by setY4m, setNv12 and setQuiltY4m (lfi_set_yuv_siting's out_siting): LFI_YUV_SITING_CENTRE
+        // (Y4M files say C420jpeg) or _LEFT (MPEG-2 / H.264 siting: C420mpeg2; what an encoder assumes of untagged NV12).  setRgbdY4m
+        // refuses left
+        void setChromaSite(int siting) { outSiting = siting; }
         // closes the video files of setY4m, setNv12, setQuiltY4m and setRgbdY4m (interpolate() leaves them open for the next time step's views); throws when that fails
         void finish();
         float lastAverageTime() const { return averageTime; }
@@ -193,6 +199,9 @@ class Interpolator
         std::unique_ptr<LfLoader> video;           // the input, where it is a light-field video
         int inputFrame{0}, loadedFrame{-1};        // the time step to render / the one on the device
         int inMatrix{LFI_YUV_BT709}, inRange{-1}, inChroma{LFI_CHROMA_BILINEAR};
+        int inSiteMode{lfi::Y4M_SITE_CENTRE}; // the constructor's inChromaSite
+        int inSiting{LFI_YUV_SITING_CENTRE};  // what it resolves to for the videos that were opened
+        int outSiting{LFI_YUV_SITING_CENTRE}; // setChromaSite
         bool leanInputs{false}, inputsReleased{false}; // setLeanInputs / lfi_release_inputs has been called on the context
         uint8_t *inFrames{nullptr};                // one I420 frame per camera, page-locked where that works
         bool inFramesPinned{false};

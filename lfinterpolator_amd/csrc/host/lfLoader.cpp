@@ -189,6 +189,14 @@ void LfLoader::openVideos(const std::string &path, const std::set<std::filesyste
         throw std::runtime_error("The videos of " + path + " hold no frame!");
 }
 
+bool LfLoader::videoChromaAgrees() const
+{
+    for(const auto &cell : videos)
+        if(cell->info().chroma != videos.front()->info().chroma)
+            return false;
+    return true;
+}
+
 void LfLoader::loadFrames(int t, uint8_t *out, size_t frameStrideBytes)
 {
     if(!isVideo())

@@ -46,6 +46,7 @@ class LfLoader
         int videoFullRange() const { return isVideo() ? videos.front()->info().fullRange : -1; } // XCOLORRANGE: 1, 0, -1 (no tag)
         std::string videoChroma() const { return isVideo() ? videos.front()->info().chroma : std::string(); }
         bool videoCentreSited() const { return !isVideo() || videos.front()->info().centreSited; }
+        bool videoChromaAgrees() const; // every camera's file carries the same C tag
         void loadFrames(int t, uint8_t *frames, size_t frameStrideBytes);
 
     private:

@@ -5,7 +5,7 @@
 // directory of images or against the other method's render), --native / --lens / --native-tile / --native-views (the native image of a
 // lenticular display, interlaced on the GPU), --y4m / --nv12 / --fps / --yuv-matrix / --yuv-range (the views as one YUV 4:2:0 video file, converted on
 // the GPU), --quilt-y4m (the quilt as one YUV 4:2:0 video frame per time step: a quilt video), --rgbd-y4m / --rgbd-view / --rgbd-tile / --rgbd-map /
-// --rgbd-invert (a view with its focus map beside it as one YUV 4:2:0 video frame per time step: RGB-D video), --frames / --in-matrix / --in-range / --in-chroma (a light-field video as input: a directory of per-camera Y4M files whose frames
+// --rgbd-invert (a view with its focus map beside it as one YUV 4:2:0 video frame per time step: RGB-D video), --chroma-site / --in-chroma-site (left-sited chroma, MPEG-2 / H.264 siting, for the frames written / read), --frames / --in-matrix / --in-range / --in-chroma (a light-field video as input: a directory of per-camera Y4M files whose frames
 // become the images on the GPU), --lean-inputs (such a video at fixed focus from the planar copy of the inputs alone) and --synthetic for runs without a dataset.
 #include <array>
 #include <iostream>
@@ -75,6 +75,8 @@ int main(int argc, char **argv)
                           "--in-matrix 709|601 - with a light-field video: the colour matrix of its files (default=709)\n"
                           "--in-range limited|full - with a light-field video: the range of its files (default: their XCOLORRANGE tag, else limited)\n"
                           "--in-chroma bilinear|nearest - with a light-field video: how chroma is brought to full resolution (default=bilinear, the triangle filter of centre-sited chroma)\n"
+                          "--in-chroma-site centre|left|auto - with a light-field video: where its chroma samples lie. centre (default): between the two columns and the two rows of their 2x2 block, as JPEG and MPEG-1 site them (C420jpeg). left: on the even column, between the two rows, as MPEG-2, H.264, HEVC and AV1 site them (C420mpeg2). auto: by the files' C tag - C420mpeg2 left, C420jpeg centre, C420paldv and plain C420 centre with a note; every camera's file must carry the same tag then\n"
+                          "--chroma-site centre|left - with --y4m, --nv12 or --quilt-y4m: the chroma siting of the frames written (default=centre, C420jpeg). left is what hardware encoders assume of untagged NV12 and what H.264 and its successors signal by default; the Y4M files then say C420mpeg2, and a quilt video takes two passes on the GPU for even tile sizes too. Not with --rgbd-y4m\n"
                           "--lean-inputs - with a light-field video rendered at fixed focus: after the first time step the GPU keeps only the planar copy of the inputs (3 bytes per pixel and image instead of 7) and every later step's frames are expanded straight into it in one pass; the files written are the same; not with -r, -F, -c, --autofocus, --auto-range, --focus-tiles, --view-maps, -g above 1 or --synthetic\n"
                           "--compare DIR - after the render, compare every view with DIR/NN.png (the names -o writes; same size) on the GPU, all views in one pass: prints \"compare NN psnr <dB> ssim <index> maxdiff <largest byte difference> differing <colour bytes that differ>\" per view, then \"compare all psnr ... ssim ...\"; one GPU\n"
                           "--compare-methods - render the views with the other method first (STD if -m TEN_WM, TEN_WM if -m STD; same parameters), keep them on the GPU, render with -m and compare the two there; prints the lines of --compare; the stored images are those of -m; one GPU; not with --compare\n"
@@ -299,6 +301,28 @@ int main(int argc, char **argv)
         return EXIT_FAILURE;
     }
 
+    int outSiting = LFI_YUV_SITING_CENTRE;
+    if(args["--chroma-site"])
+    {
+        const std::string text = static_cast<std::string>(args["--chroma-site"]);
+        if(text != "centre" && text != "left")
+        {
+            std::cerr << "--chroma-site expects centre or left." << std::endl;
+            return EXIT_FAILURE;
+        }
+        if(!args["--y4m"] && !args["--nv12"] && !args["--quilt-y4m"] && !args["--rgbd-y4m"])
+        {
+            std::cerr << "--chroma-site belongs to the video file: it needs --y4m FILE, --nv12 FILE or --quilt-y4m FILE." << std::endl;
+            return EXIT_FAILURE;
+        }
+        outSiting = text == "left" ? LFI_YUV_SITING_LEFT : LFI_YUV_SITING_CENTRE;
+        if(outSiting == LFI_YUV_SITING_LEFT && args["--rgbd-y4m"])
+        {
+            std::cerr << "--chroma-site left cannot be combined with --rgbd-y4m: the left-sited chroma filter would mix the colour and the depth half of the frame." << std::endl;
+            return EXIT_FAILURE;
+        }
+    }
+
     if(args["--y4m"] && static_cast<std::string>(args["--y4m"]).empty())
     {
         std::cerr << "--y4m needs the name of the video file to write." << std::endl;
@@ -376,9 +400,9 @@ int main(int argc, char **argv)
             return EXIT_FAILURE;
         }
     }
-    if((args["--frames"] || args["--in-matrix"] || args["--in-range"] || args["--in-chroma"]) && synthetic)
+    if((args["--frames"] || args["--in-matrix"] || args["--in-range"] || args["--in-chroma"] || args["--in-chroma-site"]) && synthetic)
     {
-        std::cerr << "--frames, --in-matrix, --in-range and --in-chroma belong to a light-field video: they need -i with a directory of .y4m files." << std::endl;
+        std::cerr << "--frames, --in-matrix, --in-range, --in-chroma and --in-chroma-site belong to a light-field video: they need -i with a directory of .y4m files." << std::endl;
         return EXIT_FAILURE;
     }
     int inMatrix = LFI_YUV_BT709, inRange = -1, inChroma = LFI_CHROMA_BILINEAR;
@@ -411,6 +435,17 @@ int main(int argc, char **argv)
             return EXIT_FAILURE;
         }
         inChroma = text == "nearest" ? LFI_CHROMA_NEAREST : LFI_CHROMA_BILINEAR;
+    }
+    int inChromaSite = lfi::Y4M_SITE_CENTRE;
+    if(args["--in-chroma-site"])
+    {
+        const std::string text = static_cast<std::string>(args["--in-chroma-site"]);
+        if(text != "centre" && text != "left" && text != "auto")
+        {
+            std::cerr << "--in-chroma-site expects centre, left or auto." << std::endl;
+            return EXIT_FAILURE;
+        }
+        inChromaSite = text == "left" ? lfi::Y4M_SITE_LEFT : text == "auto" ? lfi::Y4M_SITE_AUTO : lfi::Y4M_SITE_CENTRE;
     }
 
     if(args["--compare"] && args["--compare-methods"])
@@ -462,7 +497,7 @@ int main(int argc, char **argv)
         else
         {
             Interpolator::setDefaultDevice(device);
-            interpolator = std::make_unique<Interpolator>(path);
+            interpolator = std::make_unique<Interpolator>(path, inChromaSite);
         }
         if(args["-n"])
             interpolator->setViewCount(static_cast<int>(args["-n"]));
@@ -575,12 +610,13 @@ int main(int argc, char **argv)
         if(args["--rgbd-y4m"])
             interpolator->setRgbdY4m(static_cast<std::string>(args["--rgbd-y4m"]), rgbdView, {rgbdTileW, rgbdTileH}, rgbdMap, static_cast<bool>(args["--rgbd-invert"]), fpsNum,
                                      fpsDen, yuvMatrix, yuvRange);
+        interpolator->setChromaSite(outSiting);
         if(args["--compare"])
             interpolator->setCompareDir(static_cast<std::string>(args["--compare"]));
         if(args["--compare-methods"])
             interpolator->setCompareMethods(true);
-        if((args["--frames"] || args["--in-matrix"] || args["--in-range"] || args["--in-chroma"]) && !interpolator->isVideo())
-            throw std::runtime_error("--frames, --in-matrix, --in-range and --in-chroma belong to a light-field video: -i has to be a directory of .y4m files");
+        if((args["--frames"] || args["--in-matrix"] || args["--in-range"] || args["--in-chroma"] || args["--in-chroma-site"]) && !interpolator->isVideo())
+            throw std::runtime_error("--frames, --in-matrix, --in-range, --in-chroma and --in-chroma-site belong to a light-field video: -i has to be a directory of .y4m files");
         if(args["--lean-inputs"])
         {
             if(!interpolator->isVideo())

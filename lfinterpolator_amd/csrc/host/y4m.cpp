@@ -14,7 +14,7 @@ size_t y4mFrameBytes(int width, int height)
     return static_cast<size_t>(width) * height + 2 * ((static_cast<size_t>(width) + 1) / 2) * ((static_cast<size_t>(height) + 1) / 2);
 }
 
-Y4mWriter::Y4mWriter(const std::string &path, int width, int height, int fpsNum, int fpsDen, bool fullRange) : name{path}
+Y4mWriter::Y4mWriter(const std::string &path, int width, int height, int fpsNum, int fpsDen, bool fullRange, bool leftSited) : name{path}
 {
     if(width < 1 || height < 1 || fpsNum < 1 || fpsDen < 1)
         throw std::runtime_error("Y4M needs a frame size and a frame rate of at least 1 (" + path + ")");
@@ -22,7 +22,7 @@ Y4mWriter::Y4mWriter(const std::string &path, int width, int height, int fpsNum,
     file = std::fopen(path.c_str(), "wb");
     if(!file)
         throw std::runtime_error("Cannot write " + path);
-    if(std::fprintf(file, "YUV4MPEG2 W%d H%d F%d:%d Ip A1:1 C420jpeg XCOLORRANGE=%s\n", width, height, fpsNum, fpsDen, fullRange ? "FULL" : "LIMITED") < 0)
+    if(std::fprintf(file, "YUV4MPEG2 W%d H%d F%d:%d Ip A1:1 C420%s XCOLORRANGE=%s\n", width, height, fpsNum, fpsDen, leftSited ? "mpeg2" : "jpeg", fullRange ? "FULL" : "LIMITED") < 0)
     {
         std::fclose(file);
         file = nullptr;
@@ -54,15 +54,23 @@ void Y4mWriter::close()
         throw std::runtime_error("Cannot write " + name);
 }
 
-void writeY4m(const std::string &path, const uint8_t *frames, int n, size_t frameStrideBytes, int width, int height, int fpsNum, int fpsDen, bool fullRange)
+void writeY4m(const std::string &path, const uint8_t *frames, int n, size_t frameStrideBytes, int width, int height, int fpsNum, int fpsDen, bool fullRange,
+              bool leftSited)
 {
     // checked before the file is created
     if(n < 0 || (n > 0 && (!frames || frameStrideBytes < y4mFrameBytes(width, height))))
         throw std::runtime_error("Y4M frames are missing or closer together than a frame's bytes (" + path + ")");
-    Y4mWriter writer(path, width, height, fpsNum, fpsDen, fullRange);
+    Y4mWriter writer(path, width, height, fpsNum, fpsDen, fullRange, leftSited);
     for(int k = 0; k < n; k++)
         writer.writeFrame(frames + frameStrideBytes * k);
     writer.close();
+}
+
+int y4mInputSiting(const std::string &chromaTag, int mode)
+{
+    if(mode == Y4M_SITE_AUTO)
+        return chromaTag == "420mpeg2" ? Y4M_SITE_LEFT : Y4M_SITE_CENTRE;
+    return mode == Y4M_SITE_LEFT ? Y4M_SITE_LEFT : Y4M_SITE_CENTRE;
 }
 
 namespace {

@@ -4,6 +4,7 @@
 //     YUV4MPEG2 W<w> H<h> F<num>:<den> Ip A1:1 C420jpeg XCOLORRANGE=LIMITED|FULL\n        the header: progressive, square pixels, 4:2:0
 //     FRAME\n <frame_bytes>                                                                with centre-sited chroma (what the device computes)
 //     …
+// Left-sited frames (lfi_set_yuv_siting's out_siting: MPEG-2 / H.264 siting) are tagged C420mpeg2 in place of C420jpeg.
 // frame_bytes = w·h + 2·((w + 1) / 2)·((h + 1) / 2): the Y plane, then Cb, then Cr, tightly packed.  The colour matrix has no header field
 // in Y4M; the range goes into the XCOLORRANGE extension ffmpeg reads and writes.
 #pragma once
@@ -23,7 +24,8 @@ class Y4mWriter
 {
     public:
         // creates (truncates) the file and writes the header; throws std::runtime_error for a size or rate below 1 or a file that cannot be written
-        Y4mWriter(const std::string &path, int width, int height, int fpsNum, int fpsDen, bool fullRange);
+        // leftSited: the frames' chroma is left-sited, the header says C420mpeg2
+        Y4mWriter(const std::string &path, int width, int height, int fpsNum, int fpsDen, bool fullRange, bool leftSited = false);
         ~Y4mWriter();
         Y4mWriter(const Y4mWriter &) = delete;
         Y4mWriter &operator=(const Y4mWriter &) = delete;
@@ -39,7 +41,13 @@ class Y4mWriter
 };
 
 // n frames, frame k at frames + k·frameStrideBytes, as one file
-void writeY4m(const std::string &path, const uint8_t *frames, int n, size_t frameStrideBytes, int width, int height, int fpsNum, int fpsDen, bool fullRange);
+void writeY4m(const std::string &path, const uint8_t *frames, int n, size_t frameStrideBytes, int width, int height, int fpsNum, int fpsDen, bool fullRange,
+              bool leftSited = false);
+
+// How the chroma of a file tagged C<chromaTag> is read under --in-chroma-site centre | left | auto: Y4M_SITE_CENTRE or Y4M_SITE_LEFT
+// (= LFI_YUV_SITING_*).  auto: 420mpeg2 is left-sited, 420jpeg centre-sited; 420paldv and plain 420 have no definition here and stay centre
+enum { Y4M_SITE_CENTRE = 0, Y4M_SITE_LEFT = 1, Y4M_SITE_AUTO = 2 };
+int y4mInputSiting(const std::string &chromaTag, int mode);
 
 // What a Y4M file's header says.  Tokens may come in any order; W and H are required, unknown X tokens are ignored.
 struct Y4mInfo

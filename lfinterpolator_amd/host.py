@@ -43,6 +43,10 @@ def load_host_library() -> C.CDLL:
         lib.lfi_host_y4m_frame_bytes.argtypes = [C.c_int, C.c_int]
         lib.lfi_host_y4m_write.restype = C.c_int
         lib.lfi_host_y4m_write.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.c_size_t] + [C.c_int] * 5 + [C.c_char_p, C.c_size_t]
+        lib.lfi_host_y4m_write_sited.restype = C.c_int
+        lib.lfi_host_y4m_write_sited.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.c_size_t] + [C.c_int] * 6 + [C.c_char_p, C.c_size_t]
+        lib.lfi_host_y4m_input_siting.restype = C.c_int
+        lib.lfi_host_y4m_input_siting.argtypes = [C.c_char_p, C.c_int]
         lib.lfi_host_y4m_info.restype = C.c_int
         lib.lfi_host_y4m_info.argtypes = [C.c_char_p, C.c_void_p, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t]
         lib.lfi_host_y4m_read.restype = C.c_int
@@ -172,10 +176,11 @@ def lenticular(pitch: float, slope: float, center: float, dpi: float, invert: bo
     return lens
 
 
-def write_y4m(path: str, frames: np.ndarray, width: int, height: int, fps=(30, 1), full_range: bool = False) -> None:
+def write_y4m(path: str, frames: np.ndarray, width: int, height: int, fps=(30, 1), full_range: bool = False, left_sited: bool = False) -> None:
     """The I420 frames of Context.download_views_yuv420 / render_stream_yuv420 — [n][P] uint8 with rows of P ≥ frame bytes, the frame stride is
     the array's — as one Y4M file (csrc/host/y4m.h): `YUV4MPEG2 W H F<fps> Ip A1:1 C420jpeg XCOLORRANGE=LIMITED|FULL`, then `FRAME` + the
-    frame's bytes per frame.  fps: (numerator, denominator)."""
+    frame's bytes per frame.  fps: (numerator, denominator).  left_sited: the frames were made under Context.set_yuv_siting(out_siting="left"),
+    the header says C420mpeg2."""
     lib = load_host_library()
     frames = np.asarray(frames)
     if frames.dtype != np.uint8 or frames.ndim != 2 or (frames.size and frames.strides[1] != 1):
@@ -183,9 +188,26 @@ def write_y4m(path: str, frames: np.ndarray, width: int, height: int, fps=(30, 1
     if frames.shape[1] < lib.lfi_host_y4m_frame_bytes(width, height):
         raise ValueError(f"a {width}x{height} frame has {lib.lfi_host_y4m_frame_bytes(width, height)} bytes, the rows have {frames.shape[1]}")
     err = C.create_string_buffer(512)
-    if lib.lfi_host_y4m_write(str(path).encode(), frames.ctypes.data_as(C.c_void_p), frames.shape[0], frames.strides[0] if frames.size else 0, width, height,
-                              int(fps[0]), int(fps[1]), int(bool(full_range)), err, len(err)) != 0:
+    head = (str(path).encode(), frames.ctypes.data_as(C.c_void_p), frames.shape[0], frames.strides[0] if frames.size else 0, width, height, int(fps[0]),
+            int(fps[1]), int(bool(full_range)))
+    if left_sited:
+        rc = lib.lfi_host_y4m_write_sited(*head, 1, err, len(err))
+    else:
+        rc = lib.lfi_host_y4m_write(*head, err, len(err))
+    if rc != 0:
         raise ValueError(err.value.decode())
+
+
+Y4M_SITE_MODES = {"centre": 0, "left": 1, "auto": 2}
+
+
+def y4m_input_siting(chroma_tag: str, mode: str = "auto") -> str:
+    """How the command line's --in-chroma-site MODE ("centre", "left", "auto") reads a Y4M file tagged C<chroma_tag> (csrc/host/y4m.h,
+    y4mInputSiting): "centre" or "left".  auto: 420mpeg2 is left-sited; 420jpeg, 420paldv and plain 420 are read centre-sited."""
+    rc = load_host_library().lfi_host_y4m_input_siting(str(chroma_tag).encode(), Y4M_SITE_MODES[mode])
+    if rc < 0:
+        raise ValueError("unknown siting mode")
+    return ("centre", "left")[rc]
 
 
 def read_y4m_info(path: str) -> dict:
