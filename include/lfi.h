@@ -572,7 +572,7 @@ typedef struct lfi_yuv_surfaces {
     int32_t format, memory;
     void   *base;          /* frame 0 */
     size_t  frame_stride;  /* bytes from one frame's base to the next one's */
-    size_t  y_pitch;       /* >= W */
+    size_t  y_pitch;       /* >= W (10-bit formats, below: twice the minima here) */
     size_t  c_offset;      /* from a frame's base to its chroma: NV12 the CbCr plane, I420 the Cb plane */
     size_t  c_pitch;       /* NV12 >= 2*cw, I420 >= cw */
     size_t  cr_offset;     /* I420: the Cr plane; NV12: must be 0 */
@@ -708,6 +708,53 @@ int lfi_download_rgbd_yuv(lfi_ctx *ctx, int v0, int n, int map_k, uint32_t flags
 enum { LFI_YUV_SITING_CENTRE = 0, LFI_YUV_SITING_LEFT = 1 };
 int lfi_set_yuv_siting(lfi_ctx *ctx, int in_siting, int out_siting);
 int lfi_yuv_siting(lfi_ctx *ctx, int *in_siting, int *out_siting);
+/* 10-BIT SURFACES.  What HEVC Main10 and 10-bit AV1 decoders leave and Main10 encoders take: the 8-bit layouts with two bytes per sample.  The
+ * depth is a flag on the layout:
+ *   LFI_YUV_I010   planar; a sample is a little-endian u16 with the code in bits 9..0  (yuv420p10le, Y4M's C420p10)
+ *   LFI_YUV_P010   semi-planar (Cb, Cr interleaved); a sample is a little-endian u16 with the code in bits 15..6  (p010le)
+ * Any other value with LFI_YUV_10BIT set is an unknown format (and so is plain 2).  Geometry: that of I420 / NV12 with two bytes per sample;
+ * pitches, offsets and strides stay in bytes: y_pitch >= 2*W, c_pitch >= 2*cw (I010) or 4*cw (P010); the tight frame of
+ * lfi_yuv_surfaces_packed is 2*(W*H + 2*cw*ch) bytes.  lfi_yuv_surfaces_check additionally refuses, for these formats only, an odd base,
+ * pitch, offset or frame_stride (a sample must not straddle an odd address).  Reading: I010 code = word & 1023, P010 code = word >> 6 (the
+ * other six bits are ignored).  Writing: the other six bits are written as 0.  Device surfaces are used in place under the same rule as the
+ * 8-bit ones: base, frame_stride, pitches and offsets multiples of 16.
+ * OUTPUT (views -> frames).  Coefficients with 14 fractional bits: round(c * scale * 2^14), scale = 876/255 (limited luma), 896/255 (limited
+ * chroma), 1023/255 (full range); G adjusted so that Y sums to 56284 (limited) or 65729 (full) and Cb and Cr to 0.  The limited sets ARE the
+ * 8-bit sets (876/255 * 2^14 = 219/255 * 2^16); the full sets are
+ *                   Y (R, G, B)           Cb (R, G, B)             Cr (R, G, B)            y_off10
+ *   709 limited   11966, 40254, 4064    -6596, -22188, 28784     28784, -26145, -2639      64
+ *   709 full      13974, 47009, 4746    -7531, -25333, 32864     32864, -29851, -3013       0
+ *   601 limited   16829, 33039, 6416    -9714, -19070, 28784     28784, -24103, -4681      64
+ *   601 full      19653, 38583, 7493   -11091, -21773, 32864     32864, -27519, -5345       0
+ *     Y10 = y_off10 + ((yR*R + yG*G + yB*B + 2^13) >> 14)
+ *     centre siting:  C10 = min(1023, (2^25 + 2^15 + uR*SR + uG*SG + uB*SB) >> 16)      SR, SG, SB: the 8-bit definition's sums over the 2x2 block
+ *     left siting:    C10 = min(1023, (2^26 + 2^16 + uR*SR + uG*SG + uB*SB) >> 17)      SR, SG, SB: the left-sited definition's sums of weight 8
+ * Unsigned 32-bit arithmetic, one rounding; the brackets are positive and below 2^27 (centre) and at most 2^28 (left) as in the 8-bit
+ * definition.  Over all 2^24 colours: limited range keeps Y in [64, 940] and chroma in [64, 960], full range Y in [0, 1023] and chroma in
+ * [1, 1023] after the min; every grey has chroma exactly 512.  A uniform colour survives RGB8 -> 10-bit YUV -> RGB8 (below, nearest chroma)
+ * EXACTLY, for all 2^24 colours under all four sets.
+ * INPUT (frames -> images).  Chroma in sixteenths exactly as in the 8-bit definition (centre bilinear 9/3/3/1, left-sited 3*h(cy) + h(ny),
+ * nearest, the same clamps), of 10-bit codes.  Coefficients round(c * scale * 2^16), scale = 255/876 (limited luma), 255/896 (limited
+ * chroma), 255/1023 (full range):
+ *                    cY       rV      gU       gV      bU    y_off
+ *   709 limited    19077    29372   -3494    -8731   34610    64
+ *   709 full       16336    25726   -3060    -7647   30313     0
+ *   601 limited    19077    26149   -6419   -13320   33050    64
+ *   601 full       16336    22903   -5622   -11666   28947     0
+ *     l = 16*cY*(Y10 - y_off),  u = SU - 8192,  v = SV - 8192
+ *     R = clamp((l + rV*v + 2^19) >> 20, 0, 255)   G = clamp((l + gU*u + gV*v + 2^19) >> 20, 0, 255)   B = clamp((l + bU*u + 2^19) >> 20, 0, 255)
+ * A = 255.  Over all 10-bit code triples the bracket, rounding term included, stays within +-576,213,136 (709 limited, B, Y = U = 1023):
+ * int32 with an arithmetic shift, one rounding.  Chroma 512 gives R = G = B; limited 64 -> 0 and 940 -> 255, full 1023 -> 255; codes outside
+ * the nominal range are legal and clamped.
+ * CALLS.  lfi_upload_images_yuv takes the 10-bit formats under both input sitings and both chroma filters, lfi_download_views_yuv under both
+ * output sitings and both view layouts; sources, destinations, routing, chunking and refusals are those of the 8-bit formats.  The device
+ * frames the context owns grow to what a 10-bit call needs (lfi_memory.workspace_bytes, LFI_POISON_SCRATCH).  lfi_download_quilt_yuv with
+ * a 10-bit dst takes the two-launch route for every tile size: by definition the frame is the 10-bit frame of lfi_download_quilt_scaled's
+ * image taken as one view.  LFI_EINVAL, the context usable and nothing touched: a 10-bit format in lfi_upload_images_yuv_derived and in
+ * lfi_download_rgbd_yuv.  The ..._yuv420 calls and lfi_render_stream_yuv420 stay 8-bit.  Under the 8-bit formats every byte, launch and
+ * allocation is what it was before these formats existed. */
+#define LFI_YUV_10BIT 0x100
+enum { LFI_YUV_I010 = LFI_YUV_I420 | LFI_YUV_10BIT, LFI_YUV_P010 = LFI_YUV_NV12 | LFI_YUV_10BIT };
 int lfi_upload_map(lfi_ctx *ctx, int k, const uint8_t *rgba, size_t pitch_bytes); /* tests: inject a focus map */
 /* view v's map k (0 or 1) of the per-view maps (lfi_view_focus_maps).  Synchronous.  The upload is a test hook like lfi_upload_map (it
  * allocates the per-view maps if needed and does not put them in use: renders read them after a successful lfi_view_focus_maps). */

@@ -41,7 +41,10 @@ LFI_YUV_SITING_LEFT = 1
 YUV_SITINGS = {"centre": LFI_YUV_SITING_CENTRE, "left": LFI_YUV_SITING_LEFT}
 LFI_YUV_I420 = 0
 LFI_YUV_NV12 = 1
-YUV_FORMATS = {"i420": LFI_YUV_I420, "nv12": LFI_YUV_NV12}
+LFI_YUV_10BIT = 0x100      # the depth flag of a surface format: two bytes per sample (include/lfi.h)
+LFI_YUV_I010 = LFI_YUV_I420 | LFI_YUV_10BIT   # planar, code in bits 9..0 of a little-endian u16 (yuv420p10le)
+LFI_YUV_P010 = LFI_YUV_NV12 | LFI_YUV_10BIT   # semi-planar, code in bits 15..6 (p010le)
+YUV_FORMATS = {"i420": LFI_YUV_I420, "nv12": LFI_YUV_NV12, "i010": LFI_YUV_I010, "p010": LFI_YUV_P010}
 LFI_MEM_HOST = 0
 LFI_MEM_DEVICE = 1
 YUV_MEMORIES = {"host": LFI_MEM_HOST, "device": LFI_MEM_DEVICE}
@@ -382,7 +385,7 @@ class Context:
                                                        YUV_CHROMAS.get(chroma, chroma), _ptr(frames), frames.strides[0] if frames.size else 0))
 
     def upload_images_yuv(self, surfaces: YuvSurfaces, n: int, g0: int = 0, matrix="709", range="limited", chroma="bilinear") -> None:
-        """Images [g0, g0 + n) from n frames of `surfaces` (lfi_upload_images_yuv): I420 or NV12, pitched, host or device memory; device
+        """Images [g0, g0 + n) from n frames of `surfaces` (lfi_upload_images_yuv): I420 or NV12, or 10-bit I010 or P010, pitched, host or device memory; device
         surfaces whose base, pitches, offsets and stride are multiples of 16 are read in place.  Ordered like upload_image_async: keep the
         memory alive and unchanged until upload_wait / sync."""
         self._check(self._lib.lfi_upload_images_yuv(self._h, g0, n, YUV_MATRICES.get(matrix, matrix), YUV_RANGES.get(range, range),
@@ -412,7 +415,8 @@ class Context:
         return out
 
     def yuv_surfaces_packed(self, fmt, memory="host", base: int | None = None, keep=None) -> YuvSurfaces:
-        """the tight layout of this context's frames (lfi_yuv_surfaces_packed): frame stride yuv420_frame_bytes() for both formats"""
+        """the tight layout of this context's frames (lfi_yuv_surfaces_packed): frame stride yuv420_frame_bytes() for "i420" and "nv12", twice that
+        for the 10-bit "i010" and "p010" (two bytes per sample)"""
         return yuv_surfaces_packed(fmt, memory, base, self.width, self.height, keep)
 
     def attach_grid(self, device_ptr: int, nbytes: int) -> None:

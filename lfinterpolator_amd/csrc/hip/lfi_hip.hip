@@ -15,6 +15,7 @@
 #include "yuv420.hpp"
 #include "yuv420_upload.hpp"
 #include "yuv_surfaces.hpp"
+#include "yuv10.hpp"
 #include "yuv_derived.hpp"
 #include "lfi_rccl.hpp"
 
@@ -277,19 +278,39 @@ size_t add_sat(size_t a, size_t b)
     return a > SIZE_MAX - b ? SIZE_MAX : a + b;
 }
 
+// the layout of a surface format (LFI_YUV_I420 or LFI_YUV_NV12: the format without its depth flag) and its bytes per sample
+int yuv_layout(int format)
+{
+    return format & ~LFI_YUV_10BIT;
+}
+
+uint32_t yuv_bps(int format)
+{
+    return format & LFI_YUV_10BIT ? 2u : 1u;
+}
+
+bool yuv_format_known(int format)
+{
+    return format == LFI_YUV_I420 || format == LFI_YUV_NV12 || format == LFI_YUV_I010 || format == LFI_YUV_P010;
+}
+
 // why s does not describe n frames of width × height (NULL: it does); *extent: the end of a frame's last plane
 const char *yuv_surfaces_fault(const lfi_yuv_surfaces *s, int width, int height, int n, size_t *extent)
 {
     if(!s || !s->base)
         return "the descriptor or its base is NULL";
-    if((s->format != LFI_YUV_I420 && s->format != LFI_YUV_NV12) || (s->memory != LFI_MEM_HOST && s->memory != LFI_MEM_DEVICE))
-        return "unknown format (LFI_YUV_I420, LFI_YUV_NV12) or memory (LFI_MEM_HOST, LFI_MEM_DEVICE)";
+    if(!yuv_format_known(s->format) || (s->memory != LFI_MEM_HOST && s->memory != LFI_MEM_DEVICE))
+        return "unknown format (LFI_YUV_I420, LFI_YUV_NV12, LFI_YUV_I010, LFI_YUV_P010) or memory (LFI_MEM_HOST, LFI_MEM_DEVICE)";
     if(width < 1 || height < 1 || n < 1)
         return "width, height and n must be at least 1";
     const size_t W = (size_t)width, H = (size_t)height, cw = (W + 1) >> 1, ch = (H + 1) >> 1;
-    const bool nv12 = s->format == LFI_YUV_NV12;
-    if(s->y_pitch < W || s->c_pitch < (nv12 ? 2 * cw : cw))
-        return "a pitch is below its minimum (y_pitch >= W; c_pitch >= cw for I420, 2*cw for NV12)";
+    const bool nv12 = yuv_layout(s->format) == LFI_YUV_NV12;
+    const size_t bps = yuv_bps(s->format);
+    if(s->y_pitch < bps * W || s->c_pitch < bps * (nv12 ? 2 * cw : cw))
+        return bps == 1 ? "a pitch is below its minimum (y_pitch >= W; c_pitch >= cw for I420, 2*cw for NV12)"
+                        : "a pitch is below its minimum (y_pitch >= 2*W; c_pitch >= 2*cw for I010, 4*cw for P010)";
+    if(bps == 2 && (reinterpret_cast<uintptr_t>(s->base) | s->y_pitch | s->c_pitch | s->c_offset | s->cr_offset | s->frame_stride) % 2)
+        return "alignment: 16-bit samples need an even base, even pitches and offsets and an even frame_stride";
     const size_t y_end = plane_bytes(H, s->y_pitch), c_bytes = plane_bytes(ch, s->c_pitch);
     if(s->c_offset < y_end)
         return "the planes overlap or are out of order: c_offset is below H * y_pitch";
@@ -323,8 +344,8 @@ lfi::YuvSurfaces staged_surfaces(const lfi::YuvGeometry &g, int format, uint8_t 
     s.frame_stride = g.dev_frame_bytes;
     s.y_pitch = g.y_pitch;
     s.c_offset = y_plane;
-    s.c_pitch = format == LFI_YUV_NV12 ? g.y_pitch : g.c_pitch;
-    s.cr_offset = format == LFI_YUV_NV12 ? 0 : y_plane + (size_t)g.c_pitch * g.ch;
+    s.c_pitch = yuv_layout(format) == LFI_YUV_NV12 ? g.y_pitch : g.c_pitch;
+    s.cr_offset = yuv_layout(format) == LFI_YUV_NV12 ? 0 : y_plane + (size_t)g.c_pitch * g.ch;
     return s;
 }
 
@@ -379,7 +400,8 @@ int check_device_surfaces(lfi_ctx *ctx, const char *who, const lfi_yuv_surfaces 
 // row; such a frame can go through a packed device copy of its planes instead (enqueue_surface_copies' pack)
 bool yuv_surfaces_packable(const lfi_yuv_surfaces &s, const lfi::YuvGeometry &g)
 {
-    return s.memory == LFI_MEM_HOST && !yuv_surfaces_like_staged(s, g) && s.y_pitch == g.W && s.c_pitch == (s.format == LFI_YUV_NV12 ? 2 * (size_t)g.cw : g.cw);
+    return s.memory == LFI_MEM_HOST && !yuv_surfaces_like_staged(s, g) && s.y_pitch == (size_t)g.W * g.bps &&
+           s.c_pitch == (yuv_layout(s.format) == LFI_YUV_NV12 ? 2 * (size_t)g.cw : g.cw) * g.bps;
 }
 
 // the frames' own bytes between n caller frames (from frame k0 on) and n staged ones at dev, on st; to_staged: caller → staged.
@@ -392,7 +414,7 @@ hipError_t enqueue_surface_copies(hipStream_t st, const lfi_yuv_surfaces &s, int
     const hipMemcpyKind kind = s.memory == LFI_MEM_DEVICE ? hipMemcpyDeviceToDevice : to_staged ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost;
     const lfi::YuvSurfaces t = staged_surfaces(g, s.format, dev);
     uint8_t *base = static_cast<uint8_t *>(s.base) + s.frame_stride * (size_t)k0;
-    const bool nv12 = s.format == LFI_YUV_NV12;
+    const bool nv12 = yuv_layout(s.format) == LFI_YUV_NV12;
     if(yuv_surfaces_like_staged(s, g))
     {
         if(s.frame_stride == g.frame_bytes || n == 1)
@@ -407,9 +429,9 @@ hipError_t enqueue_surface_copies(hipStream_t st, const lfi_yuv_surfaces &s, int
         const struct
         {
             size_t f_off, d_off, f_pitch, d_pitch, width, rows;
-        } planes[3] = {{0, 0, s.y_pitch, t.y_pitch, g.W, g.H},
-                       {s.c_offset, t.c_offset, s.c_pitch, t.c_pitch, nv12 ? 2 * (size_t)g.cw : g.cw, g.ch},
-                       {s.cr_offset, t.cr_offset, s.c_pitch, t.c_pitch, g.cw, g.ch}};
+        } planes[3] = {{0, 0, s.y_pitch, t.y_pitch, (size_t)g.W * g.bps, g.H},
+                       {s.c_offset, t.c_offset, s.c_pitch, t.c_pitch, (nv12 ? 2 * (size_t)g.cw : g.cw) * g.bps, g.ch},
+                       {s.cr_offset, t.cr_offset, s.c_pitch, t.c_pitch, (size_t)g.cw * g.bps, g.ch}};
         size_t packed = 0; // the plane's offset in the packed frame
         for(int p = 0; p < (nv12 ? 2 : 3); p++)
         {
@@ -484,7 +506,8 @@ int upload_yuv_surfaces(lfi_ctx *ctx, const char *who, int g0, int n, int matrix
             return rc;
     if(int rc = ensure_copy_stream(ctx))
         return rc;
-    const lfi::YuvGeometry g = lfi::yuv_geometry(ctx->width, ctx->height);
+    const bool deep = yuv_bps(src.format) == 2; // I010 / P010: yuv10.hpp (never with derived: lfi_upload_images_yuv_derived refuses them)
+    const lfi::YuvGeometry g = lfi::yuv_geometry(ctx->width, ctx->height, yuv_bps(src.format));
     const bool in_place = yuv_surfaces_in_place(src);
     const bool left = ctx->yuv_in_siting == LFI_YUV_SITING_LEFT; // lfi_set_yuv_siting
     // staged: chunks of at most 16 frames or 256 MiB, at least one frame: a chunk's copies and its launch follow each other on the copy
@@ -513,8 +536,8 @@ int upload_yuv_surfaces(lfi_ctx *ctx, const char *who, int g0, int n, int matrix
         lfi::YuvsInArgs a{};
         a.s = in_place ? caller_surfaces(src) : staged_surfaces(g, src.format, ctx->yuv_in.get());
         a.W = g.W, a.H = g.H, a.cw = g.cw, a.ch = g.ch;
-        a.blocks_x = g.y_pitch / lfi::YUV_BLOCK_W;
-        a.k = lfi::YUV_IN_COEFFS[matrix * 2 + range];
+        a.blocks_x = (g.W + lfi::YUV_BLOCK_W - 1) / lfi::YUV_BLOCK_W;
+        a.k = deep ? lfi::YUV10_IN_COEFFS[matrix * 2 + range] : lfi::YUV_IN_COEFFS[matrix * 2 + range];
         if(derived)
         {
             // whole images (check_yuv_upload refuses a row window): the copy's planes hold in_rows = H rows of planar_pitch bytes
@@ -530,7 +553,10 @@ int upload_yuv_surfaces(lfi_ctx *ctx, const char *who, int g0, int n, int matrix
         a.dst = ctx->grid.get() + in_plane_bytes(ctx) * (size_t)(g0 + k0);
         a.image_stride = in_plane_bytes(ctx);
         a.rows16 = g.W % 4 == 0; // the grid starts on a 16-byte boundary (hipMalloc; lfi_attach_grid checks), an image is W·H·4 bytes
-        LFI_HIP(ctx, lfi::launch_yuvs_expand(st, src.format, chroma == LFI_CHROMA_NEAREST, left, a, nk));
+        if(deep)
+            LFI_HIP(ctx, lfi::launch_yuvs_expand10(st, yuv_layout(src.format), chroma == LFI_CHROMA_NEAREST, left, a, nk));
+        else
+            LFI_HIP(ctx, lfi::launch_yuvs_expand(st, src.format, chroma == LFI_CHROMA_NEAREST, left, a, nk));
     }
     if(!derived)
         touch_images(ctx, g0, g0 + n);
@@ -546,17 +572,17 @@ int lfi_yuv_surfaces_check(const lfi_yuv_surfaces *s, int width, int height, int
 
 int lfi_yuv_surfaces_packed(int format, int memory, void *base, int width, int height, lfi_yuv_surfaces *out)
 {
-    if((format != LFI_YUV_I420 && format != LFI_YUV_NV12) || (memory != LFI_MEM_HOST && memory != LFI_MEM_DEVICE) || width < 1 || height < 1 || !out)
+    if(!yuv_format_known(format) || (memory != LFI_MEM_HOST && memory != LFI_MEM_DEVICE) || width < 1 || height < 1 || !out)
         return LFI_EINVAL;
-    const lfi::YuvGeometry g = lfi::yuv_geometry(width, height);
-    const bool nv12 = format == LFI_YUV_NV12;
+    const lfi::YuvGeometry g = lfi::yuv_geometry(width, height, yuv_bps(format));
+    const bool nv12 = yuv_layout(format) == LFI_YUV_NV12;
     out->format = format, out->memory = memory;
     out->base = base;
     out->frame_stride = g.frame_bytes;
-    out->y_pitch = g.W;
-    out->c_offset = (size_t)g.W * g.H;
-    out->c_pitch = nv12 ? 2 * (size_t)g.cw : g.cw;
-    out->cr_offset = nv12 ? 0 : out->c_offset + (size_t)g.cw * g.ch;
+    out->y_pitch = (size_t)g.W * g.bps;
+    out->c_offset = (size_t)g.W * g.H * g.bps;
+    out->c_pitch = (nv12 ? 2 * (size_t)g.cw : g.cw) * g.bps;
+    out->cr_offset = nv12 ? 0 : out->c_offset + (size_t)g.cw * g.ch * g.bps;
     return LFI_OK;
 }
 
@@ -593,6 +619,9 @@ int lfi_upload_images_yuv_derived(lfi_ctx *ctx, int g0, int n, int matrix, int r
     size_t extent = 0;
     if(const char *fault = yuv_surfaces_fault(src, ctx->width, ctx->height, n, &extent))
         return fail(ctx, LFI_EINVAL, std::string("lfi_upload_images_yuv_derived: ") + fault);
+    if(src->format & LFI_YUV_10BIT)
+        return fail(ctx, LFI_EINVAL, "lfi_upload_images_yuv_derived: 10-bit frames (LFI_YUV_I010, LFI_YUV_P010) into the planar copy are not supported: "
+                                     "upload them with lfi_upload_images_yuv before lfi_release_inputs");
     return upload_yuv_surfaces(ctx, "lfi_upload_images_yuv_derived", g0, n, matrix, range, chroma, *src, extent, true);
 }
 
@@ -1678,6 +1707,11 @@ static hipError_t enqueue_yuv_convert(hipStream_t st, const lfi::ViewsSrc &src, 
     a.cw = (src.W + 1) >> 1, a.ch = (src.H + 1) >> 1;
     a.blocks_x = (src.W + lfi::YUV_BLOCK_W - 1) / lfi::YUV_BLOCK_W;
     a.rows16 = src.W % 4 == 0;
+    if(yuv_bps(format) == 2) // I010 / P010: yuv10.hpp
+    {
+        a.k = lfi::YUV10_COEFFS[matrix * 2 + range];
+        return lfi::launch_yuvs_convert10(st, planar, yuv_layout(format), siting == LFI_YUV_SITING_LEFT, a, n);
+    }
     a.k = lfi::YUV_COEFFS[matrix * 2 + range];
     return lfi::launch_yuvs_convert(st, planar, format, siting == LFI_YUV_SITING_LEFT, a, n);
 }
@@ -1701,7 +1735,7 @@ static int open_yuv_delivery(lfi_ctx *ctx, const char *who, const lfi_yuv_surfac
     if(dst.memory == LFI_MEM_DEVICE)
         if(int rc = check_device_surfaces(ctx, who, dst, extent, n))
             return rc;
-    d->g = lfi::yuv_geometry(W, H);
+    d->g = lfi::yuv_geometry(W, H, yuv_bps(dst.format));
     d->in_place = yuv_surfaces_in_place(dst);
     d->packs = may_pack && !d->in_place && yuv_surfaces_packable(dst, d->g);
     if(!d->in_place)
@@ -2403,7 +2437,7 @@ int lfi_download_quilt_yuv(lfi_ctx *ctx, int tiles_x, int tiles_y, int v0, int t
     q.src = rendered_views(ctx, 0, &planar);
     q.tile_w = tile_w, q.tile_h = tile_h;
     q.v0 = v0, q.first = 0, q.tiles_x = tiles_x;
-    if(tile_w % 2 == 0 && tile_h % 2 == 0 && ctx->yuv_out_siting == LFI_YUV_SITING_CENTRE)
+    if(tile_w % 2 == 0 && tile_h % 2 == 0 && ctx->yuv_out_siting == LFI_YUV_SITING_CENTRE && yuv_bps(dst->format) == 1)
     {
         // centre-sited, every 2 x 2 block lies inside one tile: ONE launch, no RGBA quilt
         lfi::QuiltYuvArgs a{};
@@ -2412,7 +2446,7 @@ int lfi_download_quilt_yuv(lfi_ctx *ctx, int tiles_x, int tiles_y, int v0, int t
     }
     else
     {
-        // blocks straddle tiles, or (left-sited) the chroma filter reaches across tile edges: the RGBA quilt of lfi_download_quilt_scaled in the quilt buffer, converted as ONE RGBA view of QW x QH
+        // blocks straddle tiles, or (left-sited) the chroma filter reaches across tile edges, or the frame is 10-bit (no fused kernel): the RGBA quilt of lfi_download_quilt_scaled in the quilt buffer, converted as ONE RGBA view of QW x QH
         const size_t quilt_bytes = (size_t)QW * 4 * QH;
         LFI_HIP(ctx, ctx->quilt.reserve(quilt_bytes));
         q.quilt = ctx->quilt.as<uint32_t>();
@@ -2432,6 +2466,8 @@ int lfi_download_rgbd_yuv(lfi_ctx *ctx, int v0, int n, int map_k, uint32_t flags
     // and range), the tiles as lfi_download_quilt_scaled does
     if(int rc = check_yuv_download(ctx, who, v0, n, matrix, range))
         return rc;
+    if(dst && (dst->format & LFI_YUV_10BIT))
+        return fail(ctx, LFI_EINVAL, std::string(who) + ": 10-bit frames (LFI_YUV_I010, LFI_YUV_P010) are not supported: RGB-D frames are 8-bit");
     if(ctx->yuv_out_siting != LFI_YUV_SITING_CENTRE)
         return fail(ctx, LFI_EINVAL, std::string(who) + ": left-sited output (lfi_set_yuv_siting) is not supported: the chroma filter would mix the colour "
                                                         "and the depth half in the column between them");

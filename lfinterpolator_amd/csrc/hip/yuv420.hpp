@@ -55,19 +55,20 @@ struct YuvGeometry
     size_t frame_bytes;                // host: W·H + 2·cw·ch
     size_t dev_frame_bytes;            // device: y_pitch·y_rows + 2·c_pitch·ch (a multiple of 8)
     bool tight;                        // W a multiple of 8 and H even: the device frame IS the host frame
+    uint32_t bps;                      // bytes per sample: 1, or 2 (the 10-bit formats, yuv10.hpp): both pitches and both sizes are bps times the above
 };
 
-inline YuvGeometry yuv_geometry(const int width, const int height)
+inline YuvGeometry yuv_geometry(const int width, const int height, const uint32_t bps = 1)
 {
     YuvGeometry g{};
-    g.W = width, g.H = height;
+    g.W = width, g.H = height, g.bps = bps;
     g.cw = (g.W + 1) >> 1, g.ch = (g.H + 1) >> 1;
-    g.y_pitch = (g.W + YUV_BLOCK_W - 1) / YUV_BLOCK_W * YUV_BLOCK_W;
+    g.y_pitch = (g.W + YUV_BLOCK_W - 1) / YUV_BLOCK_W * YUV_BLOCK_W * bps;
     g.c_pitch = g.y_pitch / 2;
     g.y_rows = g.ch * YUV_BLOCK_H;
-    g.frame_bytes = (size_t)g.W * g.H + 2 * (size_t)g.cw * g.ch;
+    g.frame_bytes = ((size_t)g.W * g.H + 2 * (size_t)g.cw * g.ch) * bps;
     g.dev_frame_bytes = (size_t)g.y_pitch * g.y_rows + 2 * (size_t)g.c_pitch * g.ch;
-    g.tight = g.y_pitch == g.W && g.y_rows == g.H;
+    g.tight = g.y_pitch == g.W * bps && g.y_rows == g.H;
     return g;
 }
 

@@ -251,6 +251,74 @@ int lfi_host_y4m_write_sited(const char *path, const uint8_t *frames, int n, siz
     }
 }
 
+// the 10-bit twins (y4m.h: C420p10, I010 frames of twice the bytes).  lfi_host_y4m_write_deep writes frames of `depth` bits (8 or 10; 10 ignores
+// left_sited: the tag has no siting); lfi_host_y4m_info_deep and lfi_host_y4m_read_deep accept C420p10 files beside the 8-bit ones, out[7] is
+// the depth and the frames are frame_bytes·(depth == 10 ? 2 : 1) long
+size_t lfi_host_y4m_frame_bytes_deep(int width, int height, int depth)
+{
+    return depth == 8 || depth == 10 ? lfi::y4mFrameBytes(width, height, depth) : 0;
+}
+
+int lfi_host_y4m_write_deep(const char *path, const uint8_t *frames, int n, size_t frame_stride_bytes, int width, int height, int fps_num, int fps_den,
+                            int full_range, int left_sited, int depth, char *err, size_t err_len)
+{
+    try
+    {
+        if(!path)
+            throw std::runtime_error("path must be non-NULL");
+        if(depth != 8 && depth != 10)
+            throw std::runtime_error("Y4M frames are written with 8 or 10 bits per sample");
+        lfi::writeY4m(path, frames, n, frame_stride_bytes, width, height, fps_num, fps_den, full_range != 0, left_sited != 0, depth);
+        return 0;
+    }
+    catch(const std::exception &e)
+    {
+        return report(e, err, err_len);
+    }
+}
+
+int lfi_host_y4m_info_deep(const char *path, int32_t out[8], char *chroma_tag, size_t chroma_tag_len, char *err, size_t err_len)
+{
+    try
+    {
+        if(!path || !out)
+            throw std::runtime_error("path and out must be non-NULL");
+        lfi::Y4mReader reader(path, true);
+        const lfi::Y4mInfo &info = reader.info();
+        const int32_t values[8] = {info.width, info.height, info.fpsNum, info.fpsDen, info.frames, info.fullRange, info.centreSited ? 1 : 0, info.depth};
+        std::memcpy(out, values, sizeof(values));
+        if(chroma_tag && chroma_tag_len)
+        {
+            std::strncpy(chroma_tag, info.chroma.c_str(), chroma_tag_len - 1);
+            chroma_tag[chroma_tag_len - 1] = 0;
+        }
+        return 0;
+    }
+    catch(const std::exception &e)
+    {
+        return report(e, err, err_len);
+    }
+}
+
+int lfi_host_y4m_read_deep(const char *path, int first, int n, uint8_t *frames, size_t frame_stride_bytes, char *err, size_t err_len)
+{
+    try
+    {
+        if(!path)
+            throw std::runtime_error("path must be non-NULL");
+        lfi::Y4mReader reader(path, true);
+        if(n < 0 || (n > 0 && (!frames || frame_stride_bytes < reader.frameBytes())))
+            throw std::runtime_error("Y4M frames are missing or closer together than a frame's bytes (" + std::string(path) + ")");
+        for(int k = 0; k < n; k++)
+            reader.readFrame(first + k, frames + frame_stride_bytes * k);
+        return 0;
+    }
+    catch(const std::exception &e)
+    {
+        return report(e, err, err_len);
+    }
+}
+
 // y4mInputSiting (y4m.h): the siting (0 centre, 1 left) a file tagged C<chroma_tag> is read with under mode 0 centre, 1 left, 2 auto; -1 for
 // a NULL tag or an unknown mode
 int lfi_host_y4m_input_siting(const char *chroma_tag, int mode)
@@ -392,6 +460,8 @@ int lfi_host_load_grid_y4m(const char *path, int t, int32_t out[6], uint8_t *fra
         loader.loadData(path);
         if(!loader.isVideo())
             throw std::runtime_error(std::string("The directory ") + path + " holds images, not .y4m videos");
+        if(loader.videoDepth() != 8)
+            throw std::runtime_error(std::string("The directory ") + path + " holds 10-bit videos (C420p10): this call delivers 8-bit frames");
         const lfi::IVec2 cr = loader.getColsRows();
         const lfi::IVec3 res = loader.imageResolution();
         const int32_t values[6] = {cr.x, cr.y, res.x, res.y, loader.frameCount(), loader.videoFullRange()};

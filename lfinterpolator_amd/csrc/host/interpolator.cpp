@@ -106,6 +106,11 @@ int Interpolator::frameCount() const
     return video ? video->frameCount() : 1;
 }
 
+int Interpolator::inputDepth() const
+{
+    return video ? video->videoDepth() : 8;
+}
+
 void Interpolator::setInputFrame(int t)
 {
     if(t < 0 || t >= frameCount())
@@ -134,7 +139,17 @@ void Interpolator::uploadVideoFrame()
     video->loadFrames(inputFrame, inFrames, frameBytes);
     const int range = inRange >= 0 ? inRange : (video->videoFullRange() == 1 ? LFI_YUV_FULL : LFI_YUV_LIMITED);
     check(lfi_set_yuv_siting(context, inSiting, outSiting)); // governs both calls below, lean inputs included
-    if(inputsReleased)
+    if(video->videoDepth() == 10)
+    {
+        // C420p10: the frames are tight I010 surfaces (main.cpp refuses lean inputs with them)
+        if(leanInputs)
+            throw std::runtime_error("Lean inputs cannot be combined with 10-bit videos (C420p10): 10-bit frames cannot be expanded straight into the planar copy of the inputs!");
+        lfi_yuv_surfaces surfaces{};
+        check(lfi_yuv_surfaces_packed(LFI_YUV_I010, LFI_MEM_HOST, inFrames, resolution.x, resolution.y, &surfaces));
+        surfaces.frame_stride = frameBytes;
+        check(lfi_upload_images_yuv(context, 0, static_cast<int>(n), inMatrix, range, inChroma, &surfaces));
+    }
+    else if(inputsReleased)
     {
         // lean inputs: the context holds only the derived planar copy, the frames go straight into it
         lfi_yuv_surfaces surfaces{};
@@ -171,6 +186,12 @@ void Interpolator::finish()
         if(nv12File.fail())
             throw std::runtime_error("Cannot write " + nv12Path);
     }
+    if(p010File.is_open())
+    {
+        p010File.close();
+        if(p010File.fail())
+            throw std::runtime_error("Cannot write " + p010Path);
+    }
 }
 
 void Interpolator::loadGPUData()
@@ -188,7 +209,10 @@ void Interpolator::loadGPUData()
         if(inSiteMode == lfi::Y4M_SITE_AUTO && !lfLoader.videoChromaAgrees())
             throw std::runtime_error("--in-chroma-site auto: the videos of " + input + " do not carry the same chroma tag (C420jpeg, C420mpeg2, ...)!");
         inSiting = lfi::y4mInputSiting(lfLoader.videoChroma(), inSiteMode);
-        if(inSiting == LFI_YUV_SITING_LEFT)
+        if(lfLoader.videoDepth() == 10)
+            std::cout << "The videos hold 10-bit frames (C420p10, which carries no siting): their chroma is read as " << (inSiting == LFI_YUV_SITING_LEFT ? "left" : "centre")
+                      << "-sited" << (inSiteMode == lfi::Y4M_SITE_AUTO ? " (--in-chroma-site auto: the siting of HEVC Main10 and AV1)." : ".") << std::endl;
+        else if(inSiting == LFI_YUV_SITING_LEFT)
             std::cout << "The videos' chroma is read as left-sited (C420mpeg2)." << std::endl;
         else if(!lfLoader.videoCentreSited())
             std::cout << "Note: the videos are C" << lfLoader.videoChroma()
@@ -657,7 +681,7 @@ void Interpolator::storeResults(std::string path)
         // resized and converted on the device (lfi_download_quilt_yuv): the one frame arrives as tight I420 in a page-locked buffer
         const lfi::IVec2 tile = quiltTile.x > 0 ? quiltTile : lfi::IVec2{resolution.x, resolution.y};
         const int quiltW = tile.x * quiltTiles.x, quiltH = tile.y * quiltTiles.y;
-        const size_t frameBytes = lfi::y4mFrameBytes(quiltW, quiltH);
+        const size_t frameBytes = lfi::y4mFrameBytes(quiltW, quiltH, yuvDepth);
         uint8_t *frame = nullptr;
         const bool framePinned = lfi_alloc_pinned(frameBytes, reinterpret_cast<void **>(&frame)) == LFI_OK;
         std::vector<uint8_t> pageableFrame;
@@ -669,12 +693,16 @@ void Interpolator::storeResults(std::string path)
         try
         {
             lfi_yuv_surfaces surface{};
-            check(lfi_yuv_surfaces_packed(LFI_YUV_I420, LFI_MEM_HOST, frame, quiltW, quiltH, &surface));
+            check(lfi_yuv_surfaces_packed(yuvDepth == 10 ? LFI_YUV_I010 : LFI_YUV_I420, LFI_MEM_HOST, frame, quiltW, quiltH, &surface));
             check(lfi_set_yuv_siting(context, inSiting, outSiting));
             check(lfi_download_quilt_yuv(context, quiltTiles.x, quiltTiles.y, 0, tile.x, tile.y, yuvMatrix, yuvRange, &surface));
             // one file for all time steps of a light-field video: opened by the first, appended to by the others, closed by finish()
             if(!quiltY4mWriter)
-                quiltY4mWriter = std::make_unique<lfi::Y4mWriter>(quiltY4mPath, quiltW, quiltH, y4mFps.x, y4mFps.y, yuvRange == LFI_YUV_FULL, outSiting == LFI_YUV_SITING_LEFT);
+            {
+                quiltY4mWriter = std::make_unique<lfi::Y4mWriter>(quiltY4mPath, quiltW, quiltH, y4mFps.x, y4mFps.y, yuvRange == LFI_YUV_FULL, outSiting == LFI_YUV_SITING_LEFT, yuvDepth);
+                if(yuvDepth == 10)
+                    announceDeepY4m(quiltY4mPath);
+            }
             quiltY4mWriter->writeFrame(frame);
         }
         catch(...)
@@ -688,6 +716,8 @@ void Interpolator::storeResults(std::string path)
     }
     if(!rgbdY4mPath.empty())
     {
+        if(yuvDepth == 10)
+            throw std::runtime_error("10-bit RGB-D frames are not supported: the RGB-D video is written with 8 bits per sample!");
         std::cout << "Storing RGB-D video frame..." << std::endl;
         // the view and the map resized and converted on the device (lfi_download_rgbd_yuv): the one frame arrives as tight I420 in a page-locked buffer
         const lfi::IVec2 tile = rgbdTile.x > 0 ? rgbdTile : lfi::IVec2{resolution.x, resolution.y};
@@ -736,7 +766,7 @@ void Interpolator::storeResults(std::string path)
     {
         std::cout << "Storing video..." << std::endl;
         // converted on the device (lfi_download_views_yuv420): every GPU's views arrive as frames in its part of one page-locked buffer
-        const size_t frameBytes = lfi::y4mFrameBytes(resolution.x, resolution.y);
+        const size_t frameBytes = lfi::y4mFrameBytes(resolution.x, resolution.y, yuvDepth);
         uint8_t *frames = nullptr;
         const bool framesPinned = lfi_alloc_pinned(frameBytes * viewCount, reinterpret_cast<void **>(&frames)) == LFI_OK;
         std::vector<uint8_t> pageableFrames;
@@ -750,11 +780,25 @@ void Interpolator::storeResults(std::string path)
             for(int g = 0; g < gpuCount; g++)
                 check(lfi_set_yuv_siting(contexts[g], inSiting, outSiting), contexts[g]);
             for(int g = 0; g < gpuCount; g++)
+            {
+                if(yuvDepth == 10)
+                {
+                    // 10-bit: tight I010 surfaces (lfi_download_views_yuv)
+                    lfi_yuv_surfaces surfaces{};
+                    check(lfi_yuv_surfaces_packed(LFI_YUV_I010, LFI_MEM_HOST, frames + frameBytes * viewStart[g], resolution.x, resolution.y, &surfaces), contexts[g]);
+                    check(lfi_download_views_yuv(contexts[g], 0, viewStart[g + 1] - viewStart[g], yuvMatrix, yuvRange, &surfaces), contexts[g]);
+                    continue;
+                }
                 check(lfi_download_views_yuv420(contexts[g], 0, viewStart[g + 1] - viewStart[g], yuvMatrix, yuvRange, frames + frameBytes * viewStart[g], frameBytes),
                       contexts[g]);
+            }
             // one file for all time steps of a light-field video: opened by the first, appended to by the others, closed by finish()
             if(!y4mWriter)
-                y4mWriter = std::make_unique<lfi::Y4mWriter>(y4mPath, resolution.x, resolution.y, y4mFps.x, y4mFps.y, yuvRange == LFI_YUV_FULL, outSiting == LFI_YUV_SITING_LEFT);
+            {
+                y4mWriter = std::make_unique<lfi::Y4mWriter>(y4mPath, resolution.x, resolution.y, y4mFps.x, y4mFps.y, yuvRange == LFI_YUV_FULL, outSiting == LFI_YUV_SITING_LEFT, yuvDepth);
+                if(yuvDepth == 10)
+                    announceDeepY4m(y4mPath);
+            }
             for(int i = 0; i < viewCount; i++)
                 y4mWriter->writeFrame(frames + frameBytes * i);
         }
@@ -770,47 +814,67 @@ void Interpolator::storeResults(std::string path)
     if(!nv12Path.empty())
     {
         std::cout << "Storing NV12 video..." << std::endl;
-        // converted on the device into the tight NV12 layout (lfi_download_views_yuv): every GPU's views arrive in its part of one buffer
-        const size_t frameBytes = lfi::y4mFrameBytes(resolution.x, resolution.y); // NV12 has I420's bytes
-        uint8_t *frames = nullptr;
-        const bool framesPinned = lfi_alloc_pinned(frameBytes * viewCount, reinterpret_cast<void **>(&frames)) == LFI_OK;
-        std::vector<uint8_t> pageableFrames;
-        if(!framesPinned)
+        storeRawFrames(nv12Path, nv12File, LFI_YUV_NV12, "nv12");
+    }
+    if(!p010Path.empty())
+    {
+        std::cout << "Storing P010 video..." << std::endl;
+        storeRawFrames(p010Path, p010File, LFI_YUV_P010, "p010le");
+    }
+}
+
+// Y4M's C420p10 says nothing about where the chroma lies: say it here, with the option that tells ffmpeg
+void Interpolator::announceDeepY4m(const std::string &filePath) const
+{
+    const bool left = outSiting == LFI_YUV_SITING_LEFT;
+    std::cout << "10-bit video " << filePath << ": C420p10 (yuv420p10le) carries no chroma siting; the frames are " << (left ? "left" : "centre")
+              << "-sited: ffmpeg -chroma_sample_location " << (left ? "left" : "center") << " -i " << filePath << std::endl;
+}
+
+// The views as raw semi-planar frames of `format` (LFI_YUV_NV12, or LFI_YUV_P010: two bytes per sample) appended to filePath: converted on
+// the device into the tight layout (lfi_download_views_yuv), every GPU's views arriving in its part of one buffer
+void Interpolator::storeRawFrames(const std::string &filePath, std::ofstream &file, int format, const char *pixFmt)
+{
+    const size_t frameBytes = lfi::y4mFrameBytes(resolution.x, resolution.y, format & LFI_YUV_10BIT ? 10 : 8); // the semi-planar frame has the planar one's bytes
+    uint8_t *frames = nullptr;
+    const bool framesPinned = lfi_alloc_pinned(frameBytes * viewCount, reinterpret_cast<void **>(&frames)) == LFI_OK;
+    std::vector<uint8_t> pageableFrames;
+    if(!framesPinned)
+    {
+        pageableFrames.resize(frameBytes * viewCount);
+        frames = pageableFrames.data();
+    }
+    try
+    {
+        for(int g = 0; g < gpuCount; g++)
         {
-            pageableFrames.resize(frameBytes * viewCount);
-            frames = pageableFrames.data();
+            lfi_yuv_surfaces surfaces{};
+            check(lfi_set_yuv_siting(contexts[g], inSiting, outSiting), contexts[g]);
+            check(lfi_yuv_surfaces_packed(format, LFI_MEM_HOST, frames + frameBytes * viewStart[g], resolution.x, resolution.y, &surfaces), contexts[g]);
+            check(lfi_download_views_yuv(contexts[g], 0, viewStart[g + 1] - viewStart[g], yuvMatrix, yuvRange, &surfaces), contexts[g]);
         }
-        try
+        // one file for all time steps of a light-field video: opened by the first, appended to by the others, closed by finish()
+        if(!file.is_open())
         {
-            for(int g = 0; g < gpuCount; g++)
-            {
-                lfi_yuv_surfaces surfaces{};
-                check(lfi_set_yuv_siting(contexts[g], inSiting, outSiting), contexts[g]);
-                check(lfi_yuv_surfaces_packed(LFI_YUV_NV12, LFI_MEM_HOST, frames + frameBytes * viewStart[g], resolution.x, resolution.y, &surfaces), contexts[g]);
-                check(lfi_download_views_yuv(contexts[g], 0, viewStart[g + 1] - viewStart[g], yuvMatrix, yuvRange, &surfaces), contexts[g]);
-            }
-            // one file for all time steps of a light-field video: opened by the first, appended to by the others, closed by finish()
-            if(!nv12File.is_open())
-            {
-                nv12File.open(nv12Path, std::ios::binary | std::ios::trunc);
-                if(!nv12File)
-                    throw std::runtime_error("Cannot write " + nv12Path);
-                std::cout << "NV12 video " << nv12Path << ": ffmpeg -f rawvideo -pix_fmt nv12 -s " << resolution.x << "x" << resolution.y << " -r " << y4mFps.x;
-                if(y4mFps.y != 1)
-                    std::cout << "/" << y4mFps.y;
-                std::cout << " -i " << nv12Path << std::endl;
-            }
-            nv12File.write(reinterpret_cast<const char *>(frames), static_cast<std::streamsize>(frameBytes * viewCount));
-            if(!nv12File)
-                throw std::runtime_error("Cannot write " + nv12Path);
+            file.open(filePath, std::ios::binary | std::ios::trunc);
+            if(!file)
+                throw std::runtime_error("Cannot write " + filePath);
+            std::cout << (format & LFI_YUV_10BIT ? "P010" : "NV12") << " video " << filePath << ": ffmpeg -f rawvideo -pix_fmt " << pixFmt << " -s " << resolution.x << "x"
+                      << resolution.y << " -r " << y4mFps.x;
+            if(y4mFps.y != 1)
+                std::cout << "/" << y4mFps.y;
+            std::cout << " -i " << filePath << std::endl;
         }
-        catch(...)
-        {
-            if(framesPinned)
-                lfi_free_pinned(frames);
-            throw;
-        }
+        file.write(reinterpret_cast<const char *>(frames), static_cast<std::streamsize>(frameBytes * viewCount));
+        if(!file)
+            throw std::runtime_error("Cannot write " + filePath);
+    }
+    catch(...)
+    {
         if(framesPinned)
             lfi_free_pinned(frames);
+        throw;
     }
+    if(framesPinned)
+        lfi_free_pinned(frames);
 }

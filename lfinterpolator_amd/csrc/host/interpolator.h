@@ -69,6 +69,22 @@ class Interpolator
             yuvMatrix = matrix;
             yuvRange = range;
         }
+        // also write the views as raw P010 frames (NV12's layout with 16-bit samples, the 10-bit code in the upper bits; tightly packed) into
+        // one file, in view order: converted on the device into the tight P010 layout (lfi_download_views_yuv with LFI_YUV_P010), same
+        // matrix, range and rate as setY4m; may be combined with the others.  Opening the file prints the ffmpeg options
+        void setP010(std::string path, int fpsNum = 30, int fpsDen = 1, int matrix = LFI_YUV_BT709, int range = LFI_YUV_LIMITED)
+        {
+            p010Path = path;
+            y4mFps = {fpsNum, fpsDen};
+            yuvMatrix = matrix;
+            yuvRange = range;
+        }
+        // the bits per sample of the frames setY4m and setQuiltY4m write: 8, or 10 — I010 samples (lfi_download_views_yuv /
+        // lfi_download_quilt_yuv with LFI_YUV_I010) under the tag C420p10, which carries no siting: opening the file prints the siting in use
+        // and the ffmpeg option that states it.  setRgbdY4m refuses 10
+        void setYuvDepth(int depth) { yuvDepth = depth; }
+        // 10 where the input is a light-field video whose files say C420p10 (they are uploaded as I010 frames: lfi_upload_images_yuv), else 8
+        int inputDepth() const;
         // also write the quilt of setQuilt (scaled by setQuiltTile) as ONE frame of a Y4M video file: resized and converted to 8-bit YUV 4:2:0
         // on the device (lfi_download_quilt_yuv into a host I420 frame; even tile sizes take one kernel and no RGBA quilt), same matrix, range
         // and rate as setY4m.  The file stays open over the time steps: a light-field video gives a quilt video, one frame per step.  One GPU
@@ -188,6 +204,9 @@ class Interpolator
         int yuvRange{LFI_YUV_LIMITED};
         std::unique_ptr<lfi::Y4mWriter> y4mWriter; // open from the first stored step to finish()
         std::string nv12Path;                      // empty: no raw NV12 file
+        std::string p010Path;                      // empty: no raw P010 file
+        std::ofstream p010File;                    // open from the first stored step to finish()
+        int yuvDepth{8};                           // setYuvDepth
         std::string quiltY4mPath;                  // empty: no quilt video
         std::unique_ptr<lfi::Y4mWriter> quiltY4mWriter; // open from the first stored step to finish()
         std::string rgbdY4mPath;                   // empty: no RGB-D video
@@ -235,6 +254,8 @@ class Interpolator
         void loadGPUData();
         void uploadVideoFrame();
         void storeResults(std::string path);
+        void storeRawFrames(const std::string &filePath, std::ofstream &file, int format, const char *pixFmt);
+        void announceDeepY4m(const std::string &filePath) const;
         void compareViews(bool withKept);
         void check(int status) const;
         void check(int status, lfi_ctx *where) const;

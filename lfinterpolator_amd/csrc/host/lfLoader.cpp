@@ -156,7 +156,7 @@ void LfLoader::openVideos(const std::string &path, const std::set<std::filesyste
     {
         const auto rowCol = parseFilename(file.string());
         const std::string full = (std::filesystem::path(path) / file).string();
-        auto reader = std::make_unique<lfi::Y4mReader>(full);
+        auto reader = std::make_unique<lfi::Y4mReader>(full, true); // C420p10 too
         const lfi::Y4mInfo &info = reader->info();
         if(resolution.x != 0 && (resolution.x != info.width || resolution.y != info.height))
             throw std::runtime_error("Video " + full + " does not have the same resolution as the others");
@@ -178,6 +178,9 @@ void LfLoader::openVideos(const std::string &path, const std::set<std::filesyste
                 first = cell.get();
                 frames = longest = cell->frameCount();
             }
+            if(cell->info().depth != first->info().depth)
+                throw std::runtime_error("The input directory mixes 8-bit and 10-bit (C420p10) videos: the grid video " + std::to_string(row) + "_" + std::to_string(col) +
+                                         " does not have the depth of the others!");
             if(cell->info().fullRange != first->info().fullRange)
                 throw std::runtime_error("The grid video " + std::to_string(row) + "_" + std::to_string(col) + " does not have the same XCOLORRANGE tag as the others");
             frames = std::min(frames, cell->frameCount());

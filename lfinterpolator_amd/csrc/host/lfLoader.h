@@ -47,6 +47,7 @@ class LfLoader
         std::string videoChroma() const { return isVideo() ? videos.front()->info().chroma : std::string(); }
         bool videoCentreSited() const { return !isVideo() || videos.front()->info().centreSited; }
         bool videoChromaAgrees() const; // every camera's file carries the same C tag
+        int videoDepth() const { return isVideo() ? videos.front()->info().depth : 8; } // 10: C420p10, I010 frames (every camera's, or loadData throws)
         void loadFrames(int t, uint8_t *frames, size_t frameStrideBytes);
 
     private:

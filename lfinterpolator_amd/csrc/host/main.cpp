@@ -4,7 +4,7 @@
 // grid; the search interval of an all-focus render found from it), --map-steps / --tile-steps (more than 32 candidates for the focus map / the focus tiles), --compare / --compare-methods (PSNR / SSIM of all views against a
 // directory of images or against the other method's render), --native / --lens / --native-tile / --native-views (the native image of a
 // lenticular display, interlaced on the GPU), --y4m / --nv12 / --fps / --yuv-matrix / --yuv-range (the views as one YUV 4:2:0 video file, converted on
-// the GPU), --quilt-y4m (the quilt as one YUV 4:2:0 video frame per time step: a quilt video), --rgbd-y4m / --rgbd-view / --rgbd-tile / --rgbd-map /
+// the GPU), --yuv-depth / --p010 (10-bit frames: C420p10 Y4M files and raw P010), --quilt-y4m (the quilt as one YUV 4:2:0 video frame per time step: a quilt video), --rgbd-y4m / --rgbd-view / --rgbd-tile / --rgbd-map /
 // --rgbd-invert (a view with its focus map beside it as one YUV 4:2:0 video frame per time step: RGB-D video), --chroma-site / --in-chroma-site (left-sited chroma, MPEG-2 / H.264 siting, for the frames written / read), --frames / --in-matrix / --in-range / --in-chroma (a light-field video as input: a directory of per-camera Y4M files whose frames
 // become the images on the GPU), --lean-inputs (such a video at fixed focus from the planar copy of the inputs alone) and --synthetic for runs without a dataset.
 #include <array>
@@ -62,6 +62,8 @@ int main(int argc, char **argv)
                           "--native-views N - with --native: interlace the first N views (default: all of them)\n"
                           "--y4m FILE - also store the views as the frames of one YUV4MPEG2 video FILE, in view order (ffmpeg -i FILE, or any player): 8-bit YUV 4:2:0 (I420, centre-sited chroma), converted on the GPU before the download - 1.5 bytes per pixel cross PCIe instead of 4; with -g every GPU converts its own views\n"
                           "--nv12 FILE - also store the views as raw NV12 frames in FILE, in view order, tightly packed (the Y plane, then one plane of interleaved Cb/Cr): what hardware encoders take; converted on the GPU like --y4m, may be given next to it, and with --frames COUNT above 1 FILE takes all steps' views; prints the ffmpeg options that open FILE (-f rawvideo -pix_fmt nv12 -s WxH -r N)\n"
+                          "--p010 FILE - also store the views as raw 10-bit P010 frames in FILE (the layout of --nv12 with every sample a little-endian 16-bit word, the code in its upper 10 bits): what Main10 hardware encoders take; converted on the GPU, may be given next to --y4m and --nv12 whatever --yuv-depth says; prints the ffmpeg options that open FILE (-f rawvideo -pix_fmt p010le -s WxH -r N)\n"
+                          "--yuv-depth 8|10 - with --y4m or --quilt-y4m: the bits per sample of the frames written (default=8). 10: the files hold I010 samples (yuv420p10le) under the tag C420p10, and an 8-bit colour survives the trip into them and back exactly; Y4M has no siting tag for 10-bit frames, so the siting in use (--chroma-site) is printed with the ffmpeg option that states it (-chroma_sample_location). Not with --rgbd-y4m: RGB-D frames are 8-bit. A light-field video whose files say C420p10 is read as 10-bit frames without any option (--in-chroma-site auto reads it left-sited and says so); not with --lean-inputs: 10-bit frames cannot go straight into the planar copy\n"
                           "--quilt-y4m FILE - with -q: also store the quilt (scaled by --quilt-tile) as one frame of the YUV4MPEG2 video FILE, resized and converted to 8-bit YUV 4:2:0 on the GPU in one pass (even tile sizes) - with --frames FIRST:COUNT one frame per time step: a quilt video, what holographic players take; one GPU only\n"
                           "--rgbd-y4m FILE - with -r: also store one view with its focus map beside it as one frame of the YUV4MPEG2 video FILE, twice the tile's width: the colour left, the depth right (RGB-D, what holographic players and 2D-plus-depth displays take), both resized and converted to 8-bit YUV 4:2:0 on the GPU in one pass; the depth is the map's value as grey, and displays take white as near; with -c --view-maps the view's own map is used; with --frames FIRST:COUNT one frame per time step: an RGB-D video; one GPU only\n"
                           "--rgbd-view N - with --rgbd-y4m: the view stored (default: the middle one, views/2)\n"
@@ -295,9 +297,37 @@ int main(int argc, char **argv)
         }
     }
 
-    if((args["--fps"] || args["--yuv-matrix"] || args["--yuv-range"]) && !args["--y4m"] && !args["--nv12"] && !args["--quilt-y4m"] && !args["--rgbd-y4m"])
+    if((args["--fps"] || args["--yuv-matrix"] || args["--yuv-range"]) && !args["--y4m"] && !args["--nv12"] && !args["--p010"] && !args["--quilt-y4m"] && !args["--rgbd-y4m"])
     {
-        std::cerr << "--fps, --yuv-matrix and --yuv-range belong to the video file: they need --y4m FILE, --nv12 FILE, --quilt-y4m FILE or --rgbd-y4m FILE." << std::endl;
+        std::cerr << "--fps, --yuv-matrix and --yuv-range belong to the video file: they need --y4m FILE, --nv12 FILE, --p010 FILE, --quilt-y4m FILE or --rgbd-y4m FILE." << std::endl;
+        return EXIT_FAILURE;
+    }
+
+    int yuvDepth = 8;
+    if(args["--yuv-depth"])
+    {
+        const std::string text = static_cast<std::string>(args["--yuv-depth"]);
+        if(text != "8" && text != "10")
+        {
+            std::cerr << "--yuv-depth expects 8 or 10." << std::endl;
+            return EXIT_FAILURE;
+        }
+        yuvDepth = text == "10" ? 10 : 8;
+        if(!args["--y4m"] && !args["--quilt-y4m"] && !args["--rgbd-y4m"])
+        {
+            std::cerr << "--yuv-depth belongs to the Y4M file: it needs --y4m FILE or --quilt-y4m FILE (--p010 FILE is 10-bit by itself)." << std::endl;
+            return EXIT_FAILURE;
+        }
+        if(yuvDepth == 10 && args["--rgbd-y4m"])
+        {
+            std::cerr << "--yuv-depth 10 cannot be combined with --rgbd-y4m: 10-bit RGB-D frames are not supported, the depth half is made for 8-bit luma." << std::endl;
+            return EXIT_FAILURE;
+        }
+    }
+
+    if(args["--p010"] && static_cast<std::string>(args["--p010"]).empty())
+    {
+        std::cerr << "--p010 needs the name of the video file to write." << std::endl;
         return EXIT_FAILURE;
     }
 
@@ -310,9 +340,9 @@ int main(int argc, char **argv)
             std::cerr << "--chroma-site expects centre or left." << std::endl;
             return EXIT_FAILURE;
         }
-        if(!args["--y4m"] && !args["--nv12"] && !args["--quilt-y4m"] && !args["--rgbd-y4m"])
+        if(!args["--y4m"] && !args["--nv12"] && !args["--p010"] && !args["--quilt-y4m"] && !args["--rgbd-y4m"])
         {
-            std::cerr << "--chroma-site belongs to the video file: it needs --y4m FILE, --nv12 FILE or --quilt-y4m FILE." << std::endl;
+            std::cerr << "--chroma-site belongs to the video file: it needs --y4m FILE, --nv12 FILE, --p010 FILE or --quilt-y4m FILE." << std::endl;
             return EXIT_FAILURE;
         }
         outSiting = text == "left" ? LFI_YUV_SITING_LEFT : LFI_YUV_SITING_CENTRE;
@@ -605,6 +635,9 @@ int main(int argc, char **argv)
             interpolator->setY4m(static_cast<std::string>(args["--y4m"]), fpsNum, fpsDen, yuvMatrix, yuvRange);
         if(args["--nv12"])
             interpolator->setNv12(static_cast<std::string>(args["--nv12"]), fpsNum, fpsDen, yuvMatrix, yuvRange);
+        if(args["--p010"])
+            interpolator->setP010(static_cast<std::string>(args["--p010"]), fpsNum, fpsDen, yuvMatrix, yuvRange);
+        interpolator->setYuvDepth(yuvDepth);
         if(args["--quilt-y4m"])
             interpolator->setQuiltY4m(static_cast<std::string>(args["--quilt-y4m"]), fpsNum, fpsDen, yuvMatrix, yuvRange);
         if(args["--rgbd-y4m"])
@@ -621,6 +654,8 @@ int main(int argc, char **argv)
         {
             if(!interpolator->isVideo())
                 throw std::runtime_error("--lean-inputs belongs to a light-field video: -i has to be a directory of .y4m files");
+            if(interpolator->inputDepth() == 10)
+                throw std::runtime_error("--lean-inputs cannot be combined with 10-bit videos (C420p10): 10-bit frames cannot be expanded straight into the planar copy of the inputs");
             interpolator->setLeanInputs(true);
         }
         if(interpolator->isVideo())

@@ -7,22 +7,24 @@
 
 namespace lfi {
 
-size_t y4mFrameBytes(int width, int height)
+size_t y4mFrameBytes(int width, int height, int depth)
 {
     if(width < 1 || height < 1)
         return 0;
-    return static_cast<size_t>(width) * height + 2 * ((static_cast<size_t>(width) + 1) / 2) * ((static_cast<size_t>(height) + 1) / 2);
+    return (static_cast<size_t>(width) * height + 2 * ((static_cast<size_t>(width) + 1) / 2) * ((static_cast<size_t>(height) + 1) / 2)) * (depth == 10 ? 2 : 1);
 }
 
-Y4mWriter::Y4mWriter(const std::string &path, int width, int height, int fpsNum, int fpsDen, bool fullRange, bool leftSited) : name{path}
+Y4mWriter::Y4mWriter(const std::string &path, int width, int height, int fpsNum, int fpsDen, bool fullRange, bool leftSited, int depth) : name{path}
 {
     if(width < 1 || height < 1 || fpsNum < 1 || fpsDen < 1)
         throw std::runtime_error("Y4M needs a frame size and a frame rate of at least 1 (" + path + ")");
-    bytes = y4mFrameBytes(width, height);
+    if(depth != 8 && depth != 10)
+        throw std::runtime_error("Y4M frames are written with 8 or 10 bits per sample (" + path + ")");
+    bytes = y4mFrameBytes(width, height, depth);
     file = std::fopen(path.c_str(), "wb");
     if(!file)
         throw std::runtime_error("Cannot write " + path);
-    if(std::fprintf(file, "YUV4MPEG2 W%d H%d F%d:%d Ip A1:1 C420%s XCOLORRANGE=%s\n", width, height, fpsNum, fpsDen, leftSited ? "mpeg2" : "jpeg", fullRange ? "FULL" : "LIMITED") < 0)
+    if(std::fprintf(file, "YUV4MPEG2 W%d H%d F%d:%d Ip A1:1 C420%s XCOLORRANGE=%s\n", width, height, fpsNum, fpsDen, depth == 10 ? "p10" : leftSited ? "mpeg2" : "jpeg", fullRange ? "FULL" : "LIMITED") < 0)
     {
         std::fclose(file);
         file = nullptr;
@@ -55,12 +57,12 @@ void Y4mWriter::close()
 }
 
 void writeY4m(const std::string &path, const uint8_t *frames, int n, size_t frameStrideBytes, int width, int height, int fpsNum, int fpsDen, bool fullRange,
-              bool leftSited)
+              bool leftSited, int depth)
 {
     // checked before the file is created
-    if(n < 0 || (n > 0 && (!frames || frameStrideBytes < y4mFrameBytes(width, height))))
+    if(n < 0 || (n > 0 && (!frames || frameStrideBytes < y4mFrameBytes(width, height, depth))))
         throw std::runtime_error("Y4M frames are missing or closer together than a frame's bytes (" + path + ")");
-    Y4mWriter writer(path, width, height, fpsNum, fpsDen, fullRange, leftSited);
+    Y4mWriter writer(path, width, height, fpsNum, fpsDen, fullRange, leftSited, depth);
     for(int k = 0; k < n; k++)
         writer.writeFrame(frames + frameStrideBytes * k);
     writer.close();
@@ -69,7 +71,7 @@ void writeY4m(const std::string &path, const uint8_t *frames, int n, size_t fram
 int y4mInputSiting(const std::string &chromaTag, int mode)
 {
     if(mode == Y4M_SITE_AUTO)
-        return chromaTag == "420mpeg2" ? Y4M_SITE_LEFT : Y4M_SITE_CENTRE;
+        return chromaTag == "420mpeg2" || chromaTag == "420p10" ? Y4M_SITE_LEFT : Y4M_SITE_CENTRE;
     return mode == Y4M_SITE_LEFT ? Y4M_SITE_LEFT : Y4M_SITE_CENTRE;
 }
 
@@ -110,7 +112,7 @@ std::string Y4mReader::readLine(size_t limit, bool &eof)
     }
 }
 
-Y4mReader::Y4mReader(const std::string &path) : name{path}
+Y4mReader::Y4mReader(const std::string &path, bool acceptDeep) : name{path}
 {
     file = std::fopen(path.c_str(), "rb");
     if(!file)
@@ -153,10 +155,18 @@ Y4mReader::Y4mReader(const std::string &path) : name{path}
             case 'A':
                 break; // the pixel aspect ratio changes no byte
             case 'C':
+                if(acceptDeep && value == "420p10")
+                {
+                    header.chroma = value;
+                    header.centreSited = false; // the tag carries no siting
+                    header.depth = 10;
+                    break;
+                }
                 if(value != "420jpeg" && value != "420mpeg2" && value != "420paldv" && value != "420")
                     throw std::runtime_error("Y4M file " + path + " is " + token + ": only 8-bit 4:2:0 (C420jpeg, C420mpeg2, C420paldv, C420) is read");
                 header.chroma = value;
                 header.centreSited = value == "420jpeg";
+                header.depth = 8;
                 break;
             case 'X':
                 if(value == "COLORRANGE=FULL")
@@ -170,7 +180,7 @@ Y4mReader::Y4mReader(const std::string &path) : name{path}
         }
         if(!haveW || !haveH || header.width < 1 || header.height < 1)
             throw std::runtime_error("Y4M file " + path + " needs a frame size of at least 1x1 (W and H)");
-        bytes = y4mFrameBytes(header.width, header.height);
+        bytes = y4mFrameBytes(header.width, header.height, header.depth);
         dataStart = static_cast<long long>(line.size()) + 1;
         if(std::fseek(file, 0, SEEK_END) != 0)
             throw std::runtime_error("Cannot read " + path);

@@ -7,6 +7,8 @@
 // Left-sited frames (lfi_set_yuv_siting's out_siting: MPEG-2 / H.264 siting) are tagged C420mpeg2 in place of C420jpeg.
 // frame_bytes = w·h + 2·((w + 1) / 2)·((h + 1) / 2): the Y plane, then Cb, then Cr, tightly packed.  The colour matrix has no header field
 // in Y4M; the range goes into the XCOLORRANGE extension ffmpeg reads and writes.
+// 10-bit frames (depth 10: LFI_YUV_I010, ffmpeg's yuv420p10le) are tagged C420p10: the same planes with every sample a little-endian u16
+// holding the code in bits 9..0, frame_bytes doubled.  Y4M has no siting tag for them: C420p10 says nothing about where the chroma lies.
 #pragma once
 
 #include <cstddef>
@@ -17,15 +19,16 @@
 
 namespace lfi {
 
-// w·h + 2·((w + 1) / 2)·((h + 1) / 2); 0 for a size below 1
-size_t y4mFrameBytes(int width, int height);
+// w·h + 2·((w + 1) / 2)·((h + 1) / 2), twice that for depth 10; 0 for a size below 1
+size_t y4mFrameBytes(int width, int height, int depth = 8);
 
 class Y4mWriter
 {
     public:
         // creates (truncates) the file and writes the header; throws std::runtime_error for a size or rate below 1 or a file that cannot be written
-        // leftSited: the frames' chroma is left-sited, the header says C420mpeg2
-        Y4mWriter(const std::string &path, int width, int height, int fpsNum, int fpsDen, bool fullRange, bool leftSited = false);
+        // leftSited: the frames' chroma is left-sited, the header says C420mpeg2; depth 10 (else 8): I010 frames, the header says C420p10
+        // whatever the siting
+        Y4mWriter(const std::string &path, int width, int height, int fpsNum, int fpsDen, bool fullRange, bool leftSited = false, int depth = 8);
         ~Y4mWriter();
         Y4mWriter(const Y4mWriter &) = delete;
         Y4mWriter &operator=(const Y4mWriter &) = delete;
@@ -42,10 +45,11 @@ class Y4mWriter
 
 // n frames, frame k at frames + k·frameStrideBytes, as one file
 void writeY4m(const std::string &path, const uint8_t *frames, int n, size_t frameStrideBytes, int width, int height, int fpsNum, int fpsDen, bool fullRange,
-              bool leftSited = false);
+              bool leftSited = false, int depth = 8);
 
 // How the chroma of a file tagged C<chromaTag> is read under --in-chroma-site centre | left | auto: Y4M_SITE_CENTRE or Y4M_SITE_LEFT
-// (= LFI_YUV_SITING_*).  auto: 420mpeg2 is left-sited, 420jpeg centre-sited; 420paldv and plain 420 have no definition here and stay centre
+// (= LFI_YUV_SITING_*).  auto: 420mpeg2 is left-sited, 420jpeg centre-sited; 420paldv and plain 420 have no definition here and stay centre;
+// 420p10 carries no siting and is read left-sited, the siting of the codecs that make 10-bit video (HEVC Main10, AV1)
 enum { Y4M_SITE_CENTRE = 0, Y4M_SITE_LEFT = 1, Y4M_SITE_AUTO = 2 };
 int y4mInputSiting(const std::string &chromaTag, int mode);
 
@@ -58,6 +62,7 @@ struct Y4mInfo
     std::string chroma{"420jpeg"}; // the C tag as written, without the C (no C token: Y4M's default, 420jpeg)
     bool centreSited{true};        // 420jpeg; 420mpeg2, 420paldv and plain 420 site their chroma up to a quarter pixel off centre
     int fullRange{-1};             // XCOLORRANGE: 1 FULL, 0 LIMITED, -1 no such token
+    int depth{8};                  // 10: C420p10 (only a reader opened with acceptDeep reports it)
 };
 
 // Reads 8-bit 4:2:0 progressive Y4M files frame by frame.  Accepts C420jpeg, C420mpeg2, C420paldv and C420 (the frames have one layout;
@@ -67,7 +72,9 @@ struct Y4mInfo
 class Y4mReader
 {
     public:
-        explicit Y4mReader(const std::string &path);
+        // acceptDeep: C420p10 files are read too (frames of twice the bytes, info().depth == 10); without it they are refused like every
+        // other tag that is not 8-bit 4:2:0
+        explicit Y4mReader(const std::string &path, bool acceptDeep = false);
         ~Y4mReader();
         Y4mReader(const Y4mReader &) = delete;
         Y4mReader &operator=(const Y4mReader &) = delete;

@@ -45,6 +45,14 @@ def load_host_library() -> C.CDLL:
         lib.lfi_host_y4m_write.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.c_size_t] + [C.c_int] * 5 + [C.c_char_p, C.c_size_t]
         lib.lfi_host_y4m_write_sited.restype = C.c_int
         lib.lfi_host_y4m_write_sited.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.c_size_t] + [C.c_int] * 6 + [C.c_char_p, C.c_size_t]
+        lib.lfi_host_y4m_frame_bytes_deep.restype = C.c_size_t
+        lib.lfi_host_y4m_frame_bytes_deep.argtypes = [C.c_int, C.c_int, C.c_int]
+        lib.lfi_host_y4m_write_deep.restype = C.c_int
+        lib.lfi_host_y4m_write_deep.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.c_size_t] + [C.c_int] * 7 + [C.c_char_p, C.c_size_t]
+        lib.lfi_host_y4m_info_deep.restype = C.c_int
+        lib.lfi_host_y4m_info_deep.argtypes = [C.c_char_p, C.c_void_p, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t]
+        lib.lfi_host_y4m_read_deep.restype = C.c_int
+        lib.lfi_host_y4m_read_deep.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_char_p, C.c_size_t]
         lib.lfi_host_y4m_input_siting.restype = C.c_int
         lib.lfi_host_y4m_input_siting.argtypes = [C.c_char_p, C.c_int]
         lib.lfi_host_y4m_info.restype = C.c_int
@@ -176,12 +184,22 @@ def lenticular(pitch: float, slope: float, center: float, dpi: float, invert: bo
     return lens
 
 
-def write_y4m(path: str, frames: np.ndarray, width: int, height: int, fps=(30, 1), full_range: bool = False, left_sited: bool = False) -> None:
+def write_y4m(path: str, frames: np.ndarray, width: int, height: int, fps=(30, 1), full_range: bool = False, left_sited: bool = False, depth: int = 8) -> None:
     """The I420 frames of Context.download_views_yuv420 / render_stream_yuv420 — [n][P] uint8 with rows of P ≥ frame bytes, the frame stride is
     the array's — as one Y4M file (csrc/host/y4m.h): `YUV4MPEG2 W H F<fps> Ip A1:1 C420jpeg XCOLORRANGE=LIMITED|FULL`, then `FRAME` + the
     frame's bytes per frame.  fps: (numerator, denominator).  left_sited: the frames were made under Context.set_yuv_siting(out_siting="left"),
-    the header says C420mpeg2."""
+    the header says C420mpeg2.  depth=10: the frames are I010 (every sample a little-endian u16, twice the bytes), the header says C420p10
+    whatever the siting."""
     lib = load_host_library()
+    if depth != 8:
+        frames = np.asarray(frames)
+        if frames.dtype != np.uint8 or frames.ndim != 2 or (frames.size and frames.strides[1] != 1):
+            raise ValueError("frames must be [n][>= frame bytes] uint8 with contiguous rows")
+        err = C.create_string_buffer(512)
+        if lib.lfi_host_y4m_write_deep(str(path).encode(), frames.ctypes.data_as(C.c_void_p), frames.shape[0], frames.strides[0] if frames.size else 0, width,
+                                       height, int(fps[0]), int(fps[1]), int(bool(full_range)), int(bool(left_sited)), int(depth), err, len(err)) != 0:
+            raise ValueError(err.value.decode())
+        return
     frames = np.asarray(frames)
     if frames.dtype != np.uint8 or frames.ndim != 2 or (frames.size and frames.strides[1] != 1):
         raise ValueError("frames must be [n][>= frame bytes] uint8 with contiguous rows")
@@ -210,29 +228,35 @@ def y4m_input_siting(chroma_tag: str, mode: str = "auto") -> str:
     return ("centre", "left")[rc]
 
 
-def read_y4m_info(path: str) -> dict:
+def read_y4m_info(path: str, deep: bool = False) -> dict:
     """The header of a Y4M file and its number of frames (csrc/host/y4m.h, Y4mReader): width, height, fps (numerator, denominator; (0, 0)
     without an F token), frames, chroma (the C tag without its C), centre_sited, full_range (True, False, or None without XCOLORRANGE).
-    Raises ValueError for what the reader refuses."""
+    Raises ValueError for what the reader refuses.  deep: C420p10 files are accepted too and the result has `depth` (8 or 10)."""
     lib = load_host_library()
     out = np.zeros(8, dtype=np.int32)
     tag = C.create_string_buffer(32)
     err = C.create_string_buffer(512)
+    if deep:
+        if lib.lfi_host_y4m_info_deep(str(path).encode(), out.ctypes.data_as(C.c_void_p), tag, len(tag), err, len(err)) != 0:
+            raise ValueError(err.value.decode())
+        return dict(width=int(out[0]), height=int(out[1]), fps=(int(out[2]), int(out[3])), frames=int(out[4]),
+                    full_range=None if out[5] < 0 else bool(out[5]), centre_sited=bool(out[6]), chroma=tag.value.decode(), depth=int(out[7]))
     if lib.lfi_host_y4m_info(str(path).encode(), out.ctypes.data_as(C.c_void_p), tag, len(tag), err, len(err)) != 0:
         raise ValueError(err.value.decode())
     return dict(width=int(out[0]), height=int(out[1]), fps=(int(out[2]), int(out[3])), frames=int(out[4]),
                 full_range=None if out[5] < 0 else bool(out[5]), centre_sited=bool(out[6]), chroma=tag.value.decode())
 
 
-def read_y4m(path: str, first: int = 0, n: int | None = None) -> np.ndarray:
-    """Frames [first, first + n) (default: all from `first`) of a Y4M file as [n][frame_bytes] uint8 — what Context.upload_images_yuv420 takes."""
+def read_y4m(path: str, first: int = 0, n: int | None = None, deep: bool = False) -> np.ndarray:
+    """Frames [first, first + n) (default: all from `first`) of a Y4M file as [n][frame_bytes] uint8 — what Context.upload_images_yuv420 takes.
+    deep: C420p10 files are accepted too; their frames are I010 bytes, twice as many."""
     lib = load_host_library()
-    info = read_y4m_info(path)
+    info = read_y4m_info(path, deep)
     n = info["frames"] - first if n is None else n
-    fb = lib.lfi_host_y4m_frame_bytes(info["width"], info["height"])
+    fb = lib.lfi_host_y4m_frame_bytes_deep(info["width"], info["height"], info.get("depth", 8))
     out = np.empty((max(n, 0), fb), dtype=np.uint8)
     err = C.create_string_buffer(512)
-    if lib.lfi_host_y4m_read(str(path).encode(), first, n, out.ctypes.data_as(C.c_void_p), fb, err, len(err)) != 0:
+    if (lib.lfi_host_y4m_read_deep if deep else lib.lfi_host_y4m_read)(str(path).encode(), first, n, out.ctypes.data_as(C.c_void_p), fb, err, len(err)) != 0:
         raise ValueError(err.value.decode())
     return out
 
