@@ -755,6 +755,59 @@ int lfi_yuv_siting(lfi_ctx *ctx, int *in_siting, int *out_siting);
  * allocation is what it was before these formats existed. */
 #define LFI_YUV_10BIT 0x100
 enum { LFI_YUV_I010 = LFI_YUV_I420 | LFI_YUV_10BIT, LFI_YUV_P010 = LFI_YUV_NV12 | LFI_YUV_10BIT };
+
+/* Mosaic input: ONE frame that holds all images of the grid as tiles — a camera array packed into one video stream (8 x 8 cameras of
+ * 1920 x 1080 in a 15360 x 8640 frame), a Looking-Glass quilt, or the frame lfi_download_quilt_yuv wrote — split into the grid's images on
+ * the device.  The inverse of lfi_download_quilt*.  The frame is tiles_x*W by tiles_y*H, W x H the grid's image size: no gutters, no crops.
+ *
+ * THE MAPPING.  k counts the call's tiles: tile t = first_tile + k of the frame in ROWS order (left to right, then the next tile row) sits at
+ * column tx = t % tiles_x of tile row r = t / tiles_x, which is the frame's tile row ty = r, or ty = tiles_y - 1 - r with
+ * LFI_MOSAIC_BOTTOM_UP (Looking-Glass quilts start at the bottom left).  tx and ty say where the tile's bytes lie: its top left pixel is
+ * (tx*W, ty*H) of the frame.
+ *  - LFI_MOSAIC_ROWS: the tile becomes image g0 + k.  The order of lfi_download_quilt*: a quilt of T views is a T x 1 grid.
+ *  - LFI_MOSAIC_GRID: the tile is the camera in column tx and row r (BOTTOM_UP: the cameras' rows run from the frame's bottom to its top),
+ *    the image the loader makes of the file <r>_<tx>: g = tx*rows + r.  Requires tiles_x == cols, tiles_y == rows, first_tile == 0,
+ *    n == cols*rows and g0 == 0.
+ * lfi_mosaic_map writes tx, ty and g of tile k (each pointer may be NULL) for a cols x rows grid; LFI_EINVAL, nothing written: m NULL; tiles_x,
+ * tiles_y, cols or rows below 1; an unknown order or flag; n < 1, first_tile < 0 or first_tile + n beyond the last tile; g0 < 0 or g0 + n
+ * beyond the last image; a GRID mosaic that breaks the rule above; k outside [0, n).  Context-free, needs no GPU.  It is the one definition
+ * the entry points, their kernel and the command-line program share. */
+enum { LFI_MOSAIC_ROWS = 0, LFI_MOSAIC_GRID = 1 };      /* order */
+enum { LFI_MOSAIC_BOTTOM_UP = 1u };                     /* flags */
+typedef struct lfi_mosaic {
+    int32_t tiles_x, tiles_y;   /* the frame is tiles_x*W by tiles_y*H, W x H the grid's image size */
+    int32_t first_tile, n;      /* tiles [first_tile, first_tile + n) in ROWS order */
+    int32_t order;
+    uint32_t flags;
+} lfi_mosaic;
+int lfi_mosaic_map(const lfi_mosaic *m, int cols, int rows, int g0, int k, int *tx, int *ty, int *g);
+/* A YUV 4:2:0 mosaic.  src describes ONE frame of MW x MH = tiles_x*W x tiles_y*H, LFI_YUV_I420 or LFI_YUV_NV12, host or device memory, any
+ * pitches and offsets lfi_yuv_surfaces_check(src, MW, MH, 1) accepts (frame_stride is not used).
+ * DEFINITION, no new arithmetic: image g of tile (tx, ty) is what lfi_upload_images_yuv makes of the tile taken as a frame of its own — Y rows
+ * [ty*H, ty*H + H) and columns [tx*W, tx*W + W), chroma rows [ty*H/2, ty*H/2 + H/2) and columns [tx*W/2, tx*W/2 + W/2) — under the
+ * context's input siting (lfi_set_yuv_siting) and the call's matrix, range and chroma filter.  Chroma neighbours are clamped at the TILE's
+ * edges: no value of a neighbouring tile, of pitch padding or of a tile outside [first_tile, first_tile + n) reaches any image.  Images
+ * other than the mapped ones are not touched.  W and H must be even (an odd size puts a 2 x 2 chroma block across two tiles).
+ * Ordering against uploads, renders, lfi_upload_wait and lfi_sync is lfi_upload_images_yuv's; the source is only read and must stay valid
+ * and unchanged until lfi_upload_wait / lfi_sync.
+ *  - LFI_MEM_DEVICE where base, both pitches and the offsets are multiples of 16: the frame is read where it lies by ONE launch for all n
+ *    tiles, whatever W is (a W that is no multiple of 8 takes a kernel that assembles its pieces from aligned words).  No staging buffer.
+ *  - Everything else (host memory, other device descriptors): the frame goes through the staging buffer of lfi_upload_images_yuv in chunks
+ *    of whole tile rows, at most 256 MiB and at least one tile row each; a chunk takes one 2D copy per plane of the rows' own bytes — never a
+ *    copy per tile — and one launch.
+ * LFI_EINVAL, the context usable, the grid and the staging buffer untouched: whatever lfi_upload_images_yuv refuses of grid, released
+ * inputs, row window, matrix, range and chroma; a mosaic lfi_mosaic_map refuses for the context's grid; an odd W or H; the 10-bit formats;
+ * src refused by lfi_yuv_surfaces_check for (MW, MH, 1); LFI_MEM_DEVICE with a pointer that is not device memory of the context's device
+ * or whose allocation ends before the frame does. */
+int lfi_upload_mosaic_yuv(lfi_ctx *ctx, const lfi_mosaic *m, int g0, int matrix, int range, int chroma, const lfi_yuv_surfaces *src);
+/* An RGBA mosaic in host memory (a quilt PNG): rows of pitch_bytes >= tiles_x*W*4.  By definition lfi_upload_image_async of every tile's
+ * rectangle into its mapped image: one 2D copy per tile on the copy stream, no kernel; odd sizes are allowed; ordering, the row window and
+ * the lifetime of rgba are lfi_upload_image_async's.  LFI_EINVAL: no grid, a mosaic lfi_mosaic_map refuses, rgba NULL, a pitch too small. */
+int lfi_upload_mosaic(lfi_ctx *ctx, const lfi_mosaic *m, int g0, const uint8_t *rgba, size_t pitch_bytes);
+/* tests: chunk `chunk` of lfi_upload_mosaic_yuv's staged route for tiles of tile_w x tile_h under a cap of cap_bytes (0: the call's own
+ * 256 MiB) — out5 = { first tile row in ROWS order, tile rows, the frame's first tile row copied, first tile k, tiles }.  LFI_EINVAL: a bad
+ * mosaic (judged for its natural grid: tiles_x x tiles_y under GRID, n x 1 under ROWS), an odd size, no such chunk.  Needs no GPU. */
+int lfi_debug_mosaic_chunk(const lfi_mosaic *m, int tile_w, int tile_h, size_t cap_bytes, int chunk, int32_t *out5);
 int lfi_upload_map(lfi_ctx *ctx, int k, const uint8_t *rgba, size_t pitch_bytes); /* tests: inject a focus map */
 /* view v's map k (0 or 1) of the per-view maps (lfi_view_focus_maps).  Synchronous.  The upload is a test hook like lfi_upload_map (it
  * allocates the per-view maps if needed and does not put them in use: renders read them after a successful lfi_view_focus_maps). */

@@ -48,6 +48,10 @@ YUV_FORMATS = {"i420": LFI_YUV_I420, "nv12": LFI_YUV_NV12, "i010": LFI_YUV_I010,
 LFI_MEM_HOST = 0
 LFI_MEM_DEVICE = 1
 YUV_MEMORIES = {"host": LFI_MEM_HOST, "device": LFI_MEM_DEVICE}
+LFI_MOSAIC_ROWS = 0
+LFI_MOSAIC_GRID = 1
+LFI_MOSAIC_BOTTOM_UP = 1
+MOSAIC_ORDERS = {"rows": LFI_MOSAIC_ROWS, "grid": LFI_MOSAIC_GRID}
 METHODS = {"STD": LFI_METHOD_STD, "TEN_WM": LFI_METHOD_TEN_WM, "FOCUS": LFI_KERNEL_FOCUS_ESTIMATE}
 
 # every symbol include/lfi.h declares
@@ -65,6 +69,7 @@ ABI_SYMBOLS = [
     "lfi_yuv_surfaces_check", "lfi_yuv_surfaces_packed", "lfi_upload_images_yuv", "lfi_download_views_yuv",
     "lfi_download_quilt_yuv", "lfi_download_rgbd_yuv", "lfi_set_yuv_siting", "lfi_yuv_siting",
     "lfi_upload_images_yuv_derived", "lfi_debug_derived_layout", "lfi_debug_download_derived",
+    "lfi_mosaic_map", "lfi_upload_mosaic_yuv", "lfi_upload_mosaic", "lfi_debug_mosaic_chunk",
 ]
 
 
@@ -149,6 +154,34 @@ def yuv_surfaces_packed(fmt, memory, base: int | None, width: int, height: int, 
         raise LfiError("lfi_yuv_surfaces_packed: unknown format or memory, or a size below 1")
     s.keep = keep
     return s
+
+
+class Mosaic(C.Structure):
+    """lfi_mosaic: one frame of tiles_x·W × tiles_y·H that holds the grid's images as tiles — tiles [first_tile, first_tile + n) in ROWS order,
+    mapped onto images by `order` (LFI_MOSAIC_ROWS: image g0 + k; LFI_MOSAIC_GRID: tile (tx, ty) is camera column tx, row ty) with
+    LFI_MOSAIC_BOTTOM_UP in `flags` where the tile rows count from the frame's bottom (include/lfi.h)."""
+    _fields_ = [("tiles_x", C.c_int32), ("tiles_y", C.c_int32), ("first_tile", C.c_int32), ("n", C.c_int32), ("order", C.c_int32), ("flags", C.c_uint32)]
+
+    @classmethod
+    def make(cls, tiles_x: int, tiles_y: int, order="rows", bottom_up: bool = False, first_tile: int = 0, n: int | None = None) -> "Mosaic":
+        """order: "rows" / "grid" (or the LFI_MOSAIC_* values); n defaults to all tiles from first_tile"""
+        return cls(tiles_x, tiles_y, first_tile, tiles_x * tiles_y - first_tile if n is None else n, MOSAIC_ORDERS.get(order, order),
+                   LFI_MOSAIC_BOTTOM_UP if bottom_up else 0)
+
+
+def mosaic_map(mosaic: Mosaic, cols: int, rows: int, g0: int = 0) -> np.ndarray:
+    """lfi_mosaic_map for every tile of the mosaic: [n][3] int32, row k = (tx, ty, g) — the tile's column and row in the frame and the image
+    it becomes in a cols × rows grid.  LfiError for what the call refuses."""
+    lib = load_hip_library()
+    out = np.zeros((max(mosaic.n, 0), 3), np.int32)
+    if lib.lfi_mosaic_map(C.byref(mosaic), cols, rows, g0, 0, None, None, None) != 0:
+        raise LfiError("lfi_mosaic_map: the mosaic does not map onto the grid (include/lfi.h)")
+    a, b, c = C.c_int(), C.c_int(), C.c_int()
+    for k in np.arange(mosaic.n):
+        if lib.lfi_mosaic_map(C.byref(mosaic), cols, rows, g0, int(k), C.byref(a), C.byref(b), C.byref(c)) != 0:
+            raise LfiError("lfi_mosaic_map refused a tile of a mosaic it accepted")
+        out[k] = a.value, b.value, c.value
+    return out
 
 
 LFI_YUV_DERIVED_SPAN = 384   # bytes (= pixels) of a plane row that a workgroup of lfi_upload_images_yuv_derived's kernel owns (include/lfi.h)
@@ -247,6 +280,10 @@ def load_hip_library() -> C.CDLL:
         "lfi_set_yuv_siting": (i, [vp, i, i]),
         "lfi_yuv_siting": (i, [vp, C.POINTER(i), C.POINTER(i)]),
         "lfi_debug_derived_layout": (i, [vp, C.POINTER(DerivedLayout), vp]),
+        "lfi_mosaic_map": (i, [C.POINTER(Mosaic), i, i, i, i, C.POINTER(i), C.POINTER(i), C.POINTER(i)]),
+        "lfi_upload_mosaic_yuv": (i, [vp, C.POINTER(Mosaic), i, i, i, i, C.POINTER(YuvSurfaces)]),
+        "lfi_upload_mosaic": (i, [vp, C.POINTER(Mosaic), i, vp, sz]),
+        "lfi_debug_mosaic_chunk": (i, [C.POINTER(Mosaic), i, i, sz, i, vp]),
         "lfi_debug_download_derived": (i, [vp, i, i, vp]),
         "lfi_alloc_pinned": (i, [sz, C.POINTER(vp)]),
         "lfi_free_pinned": (i, [vp]),
@@ -396,6 +433,23 @@ class Context:
         planes of images [g0, g0 + n) of the derived planar copy, padding included, in one pass.  Ordered like upload_images_yuv."""
         self._check(self._lib.lfi_upload_images_yuv_derived(self._h, g0, n, YUV_MATRICES.get(matrix, matrix), YUV_RANGES.get(range, range),
                                                             YUV_CHROMAS.get(chroma, chroma), C.byref(surfaces) if surfaces is not None else None))
+
+    def upload_mosaic_yuv(self, mosaic: Mosaic, surfaces: YuvSurfaces, g0: int = 0, matrix="709", range="limited", chroma="bilinear") -> None:
+        """The grid's images from ONE 8-bit YUV 4:2:0 frame of tiles_x·W × tiles_y·H in `surfaces` (lfi_upload_mosaic_yuv): every tile is expanded
+        as a frame of its own into the image `mosaic` maps it to; a device frame whose base, pitches and offsets are multiples of 16 is read
+        in place by one launch.  W and H must be even.  Ordered like upload_images_yuv: keep the memory alive and unchanged until
+        upload_wait / sync."""
+        self._check(self._lib.lfi_upload_mosaic_yuv(self._h, C.byref(mosaic) if mosaic is not None else None, g0, YUV_MATRICES.get(matrix, matrix),
+                                                    YUV_RANGES.get(range, range), YUV_CHROMAS.get(chroma, chroma),
+                                                    C.byref(surfaces) if surfaces is not None else None))
+
+    def upload_mosaic(self, mosaic: Mosaic, rgba: np.ndarray, g0: int = 0) -> None:
+        """The grid's images from one host RGBA image of tiles_y·H × tiles_x·W pixels (lfi_upload_mosaic): upload_image_async of every tile's
+        rectangle; `rgba`: (tiles_y·H, P, 4) uint8 with rows of P ≥ tiles_x·W pixels — the row pitch is the array's.  Keep it alive until
+        upload_wait / sync."""
+        assert rgba.dtype == np.uint8 and rgba.ndim == 3 and rgba.shape[2] == 4 and rgba.strides[1:] == (4, 1)
+        assert rgba.shape[0] == mosaic.tiles_y * self.height and rgba.shape[1] >= mosaic.tiles_x * self.width
+        self._check(self._lib.lfi_upload_mosaic(self._h, C.byref(mosaic), g0, _ptr(rgba), rgba.strides[0]))
 
     def derived_layout(self) -> DerivedLayout:
         """the layout and per-image phases of the derived planar copy (lfi_debug_derived_layout); LfiError where the copy is not current"""

@@ -16,6 +16,7 @@
 #include "yuv420_upload.hpp"
 #include "yuv_surfaces.hpp"
 #include "yuv10.hpp"
+#include "yuv_mosaic.hpp"
 #include "yuv_derived.hpp"
 #include "lfi_rccl.hpp"
 
@@ -623,6 +624,217 @@ int lfi_upload_images_yuv_derived(lfi_ctx *ctx, int g0, int n, int matrix, int r
         return fail(ctx, LFI_EINVAL, "lfi_upload_images_yuv_derived: 10-bit frames (LFI_YUV_I010, LFI_YUV_P010) into the planar copy are not supported: "
                                      "upload them with lfi_upload_images_yuv before lfi_release_inputs");
     return upload_yuv_surfaces(ctx, "lfi_upload_images_yuv_derived", g0, n, matrix, range, chroma, *src, extent, true);
+}
+
+// ---- mosaic input: one frame that holds the grid (yuv_mosaic.hpp) -------------------------------------------------------------------------
+
+namespace {
+
+// why m does not map onto images [g0, g0 + n) of a cols × rows grid (NULL: it does): the rules of lfi_mosaic_map
+const char *mosaic_fault(const lfi_mosaic *m, int cols, int rows, int g0)
+{
+    if(!m)
+        return "the mosaic is NULL";
+    if(m->tiles_x < 1 || m->tiles_y < 1 || cols < 1 || rows < 1)
+        return "tiles_x, tiles_y and the grid's columns and rows must be at least 1";
+    if(m->order != LFI_MOSAIC_ROWS && m->order != LFI_MOSAIC_GRID)
+        return "unknown order (LFI_MOSAIC_ROWS, LFI_MOSAIC_GRID)";
+    if(m->flags & ~(uint32_t)LFI_MOSAIC_BOTTOM_UP)
+        return "unknown flags (LFI_MOSAIC_BOTTOM_UP)";
+    const long long tiles = (long long)m->tiles_x * m->tiles_y, images = (long long)cols * rows;
+    if(m->n < 1 || m->first_tile < 0 || (long long)m->first_tile + m->n > tiles)
+        return "needs n >= 1 tiles starting at first_tile inside [0, tiles_x * tiles_y)";
+    if(g0 < 0 || (long long)g0 + m->n > images)
+        return "needs the n images starting at g0 inside [0, N)";
+    if(m->order == LFI_MOSAIC_GRID && (m->tiles_x != cols || m->tiles_y != rows || m->first_tile != 0 || m->n != images || g0 != 0))
+        return "LFI_MOSAIC_GRID needs tiles_x == cols, tiles_y == rows, first_tile == 0, n == cols * rows and g0 == 0";
+    return nullptr;
+}
+
+lfi::MosaicMap mosaic_map_of(const lfi_mosaic &m, int rows, int g0)
+{
+    lfi::MosaicMap k{};
+    k.tiles_x = (uint32_t)m.tiles_x, k.tiles_y = (uint32_t)m.tiles_y, k.first_tile = (uint32_t)m.first_tile;
+    k.grid = m.order == LFI_MOSAIC_GRID, k.bottom_up = (m.flags & LFI_MOSAIC_BOTTOM_UP) != 0;
+    k.rows = (uint32_t)rows, k.g0 = (uint32_t)g0;
+    return k;
+}
+
+// The staged route's plan: chunk c of a mosaic that has passed mosaic_fault.  A chunk is whole tile rows, as many as fit the cap (at least
+// one): tile rows [r0, r0 + nr) in ROWS order, which are the frame's tile rows [ty0, ty0 + nr) (BOTTOM_UP: counted from the other end), and
+// of the call's tiles those that lie in them, [k0, k0 + nk).  false: there is no chunk c
+struct MosaicChunk
+{
+    int r0, nr, ty0, k0, nk;
+};
+
+bool mosaic_chunk(const lfi_mosaic &m, size_t tile_row_bytes, size_t cap_bytes, int c, MosaicChunk *out)
+{
+    const long long r_first = m.first_tile / m.tiles_x, r_last = ((long long)m.first_tile + m.n - 1) / m.tiles_x;
+    const long long per = std::max<long long>(1, std::min<long long>(r_last - r_first + 1, (long long)(cap_bytes / tile_row_bytes)));
+    const long long r0 = r_first + (long long)c * per;
+    if(c < 0 || r0 > r_last)
+        return false;
+    const long long nr = std::min(per, r_last - r0 + 1);
+    const long long t_lo = std::max<long long>(m.first_tile, r0 * m.tiles_x), t_hi = std::min<long long>((long long)m.first_tile + m.n, (r0 + nr) * m.tiles_x);
+    out->r0 = (int)r0, out->nr = (int)nr;
+    out->ty0 = (int)(m.flags & LFI_MOSAIC_BOTTOM_UP ? m.tiles_y - (r0 + nr) : r0);
+    out->k0 = (int)(t_lo - m.first_tile), out->nk = (int)(t_hi - t_lo);
+    return true;
+}
+
+constexpr size_t MOSAIC_CHUNK_CAP = (size_t)256 << 20; // the cap of the YUV uploads' staging chunks
+
+// the staged bytes of one tile row of a frame MW wide: yuv_geometry's padded planes of MW × H
+size_t mosaic_tile_row_bytes(int MW, int H)
+{
+    return lfi::yuv_geometry(MW, H).dev_frame_bytes;
+}
+
+} // namespace
+
+int lfi_mosaic_map(const lfi_mosaic *m, int cols, int rows, int g0, int k, int *tx, int *ty, int *g)
+{
+    if(mosaic_fault(m, cols, rows, g0) || k < 0 || k >= m->n)
+        return LFI_EINVAL;
+    uint32_t x, y, image;
+    lfi::mosaic_tile(mosaic_map_of(*m, rows, g0), (uint32_t)k, x, y, image);
+    if(tx)
+        *tx = (int)x;
+    if(ty)
+        *ty = (int)y;
+    if(g)
+        *g = (int)image;
+    return LFI_OK;
+}
+
+int lfi_debug_mosaic_chunk(const lfi_mosaic *m, int tile_w, int tile_h, size_t cap_bytes, int chunk, int32_t *out5)
+{
+    if(!m || !out5 || tile_w < 2 || tile_h < 2 || tile_w % 2 || tile_h % 2 || m->tiles_x < 1 || (long long)m->tiles_x * tile_w > INT32_MAX)
+        return LFI_EINVAL;
+    // the natural grid of the order: GRID its own, ROWS one row of all tiles
+    const bool grid = m->order == LFI_MOSAIC_GRID;
+    if(mosaic_fault(m, grid ? m->tiles_x : m->n, grid ? m->tiles_y : 1, 0))
+        return LFI_EINVAL;
+    MosaicChunk c{};
+    if(!mosaic_chunk(*m, mosaic_tile_row_bytes(m->tiles_x * tile_w, tile_h), cap_bytes ? cap_bytes : MOSAIC_CHUNK_CAP, chunk, &c))
+        return LFI_EINVAL;
+    out5[0] = c.r0, out5[1] = c.nr, out5[2] = c.ty0, out5[3] = c.k0, out5[4] = c.nk;
+    return LFI_OK;
+}
+
+int lfi_upload_mosaic_yuv(lfi_ctx *ctx, const lfi_mosaic *m, int g0, int matrix, int range, int chroma, const lfi_yuv_surfaces *src)
+{
+    const char *who = "lfi_upload_mosaic_yuv";
+    if(!ctx)
+        return LFI_EINVAL;
+    if(!m)
+        return fail(ctx, LFI_EINVAL, std::string(who) + ": the mosaic is NULL");
+    if(int rc = check_yuv_upload(ctx, who, g0, m->n, matrix, range, chroma))
+        return rc;
+    if(const char *fault = mosaic_fault(m, ctx->cols, ctx->rows, g0))
+        return fail(ctx, LFI_EINVAL, std::string(who) + ": " + fault);
+    const int W = ctx->width, H = ctx->height;
+    if(W % 2 || H % 2)
+        return fail(ctx, LFI_EINVAL, std::string(who) + ": a YUV 4:2:0 mosaic needs an even image width and height: an odd size puts a 2x2 chroma block across two tiles");
+    if((long long)m->tiles_x * W > INT32_MAX || (long long)m->tiles_y * H > INT32_MAX)
+        return fail(ctx, LFI_EINVAL, std::string(who) + ": the frame's size tiles_x * W by tiles_y * H does not fit 31 bits");
+    const int MW = m->tiles_x * W, MH = m->tiles_y * H;
+    if(src && yuv_format_known(src->format) && (src->format & LFI_YUV_10BIT))
+        return fail(ctx, LFI_EINVAL, std::string(who) + ": 10-bit mosaics (LFI_YUV_I010, LFI_YUV_P010) are not supported: the frame must be LFI_YUV_I420 or LFI_YUV_NV12");
+    size_t extent = 0;
+    if(const char *fault = yuv_surfaces_fault(src, MW, MH, 1, &extent))
+        return fail(ctx, LFI_EINVAL, std::string(who) + ": " + fault + " (the frame is tiles_x * W by tiles_y * H)");
+    if(int rc = bind(ctx))
+        return rc;
+    if(src->memory == LFI_MEM_DEVICE)
+        if(int rc = check_device_surfaces(ctx, who, *src, extent, 1))
+            return rc;
+    if(int rc = ensure_copy_stream(ctx))
+        return rc;
+    lfi_yuv_surfaces one = *src;
+    one.frame_stride = 0; // one frame: its stride addresses nothing and need not be aligned
+    const bool in_place = yuv_surfaces_in_place(one);
+    const bool nv12 = src->format == LFI_YUV_NV12;
+    const size_t tile_row_bytes = mosaic_tile_row_bytes(MW, H);
+    MosaicChunk c{};
+    (void)mosaic_chunk(*m, tile_row_bytes, MOSAIC_CHUNK_CAP, 0, &c); // chunk 0 exists and is the largest
+    const size_t need = in_place ? 0 : lfi::yuv_geometry(MW, c.nr * H).dev_frame_bytes;
+    if(ctx->yuv_in.bytes() < need)
+    {
+        LFI_HIP(ctx, hipStreamSynchronize(ctx->copy_stream)); // an earlier call's chunks may still be in the buffer that goes
+        LFI_HIP(ctx, ctx->yuv_in.reserve(need));
+    }
+    if(!ctx->uploads_pending)
+    {
+        // first copy of a batch: renders already enqueued on the compute stream may still read the planes
+        LFI_HIP(ctx, hipEventRecord(ctx->ev_order, ctx->stream));
+        LFI_HIP(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->ev_order, 0));
+    }
+    ctx->uploads_pending = true;
+    hipStream_t st = ctx->copy_stream;
+    lfi::YuvsMosaicArgs a{};
+    a.in.W = (uint32_t)W, a.in.H = (uint32_t)H, a.in.cw = (uint32_t)W / 2, a.in.ch = (uint32_t)H / 2;
+    a.in.blocks_x = ((uint32_t)W + lfi::YUV_BLOCK_W - 1) / lfi::YUV_BLOCK_W;
+    a.in.k = lfi::YUV_IN_COEFFS[matrix * 2 + range];
+    a.in.dst = ctx->grid.get();
+    a.in.image_stride = in_plane_bytes(ctx);
+    a.in.rows16 = W % 4 == 0;
+    a.map = mosaic_map_of(*m, ctx->rows, g0);
+    const bool nearest = chroma == LFI_CHROMA_NEAREST, left = ctx->yuv_in_siting == LFI_YUV_SITING_LEFT, unaligned = W % lfi::YUV_BLOCK_W != 0;
+    if(in_place)
+    {
+        // the frame is read where it lies: ONE launch for all n tiles
+        a.in.s = caller_surfaces(*src);
+        LFI_HIP(ctx, lfi::launch_yuvs_mosaic_expand(st, src->format, nearest, left, unaligned, a, m->n));
+    }
+    else
+    {
+        // staged: chunks of whole tile rows, each ONE 2D copy per plane of the rows' own bytes and one launch; copies and launch follow each
+        // other on the copy stream, so stream order is all the staging buffer needs
+        const hipMemcpyKind kind = src->memory == LFI_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+        const uint8_t *base = static_cast<const uint8_t *>(src->base);
+        for(int i = 0; mosaic_chunk(*m, tile_row_bytes, MOSAIC_CHUNK_CAP, i, &c); i++)
+        {
+            const lfi::YuvGeometry g = lfi::yuv_geometry(MW, c.nr * H);
+            const lfi::YuvSurfaces t = staged_surfaces(g, src->format, ctx->yuv_in.get());
+            const size_t y0 = (size_t)c.ty0 * H, c0 = y0 / 2;
+            LFI_HIP(ctx, hipMemcpy2DAsync(t.base, t.y_pitch, base + y0 * src->y_pitch, src->y_pitch, (size_t)MW, g.H, kind, st));
+            LFI_HIP(ctx, hipMemcpy2DAsync(t.base + t.c_offset, t.c_pitch, base + src->c_offset + c0 * src->c_pitch, src->c_pitch,
+                                          nv12 ? (size_t)MW : (size_t)MW / 2, g.ch, kind, st));
+            if(!nv12)
+                LFI_HIP(ctx, hipMemcpy2DAsync(t.base + t.cr_offset, t.c_pitch, base + src->cr_offset + c0 * src->c_pitch, src->c_pitch, (size_t)MW / 2, g.ch, kind, st));
+            a.in.s = t;
+            a.k0 = (uint32_t)c.k0, a.ty_bias = (uint32_t)c.ty0;
+            LFI_HIP(ctx, lfi::launch_yuvs_mosaic_expand(st, src->format, nearest, left, unaligned, a, c.nk));
+        }
+    }
+    // the images the tiles became: a contiguous range under ROWS, the whole grid under GRID
+    touch_images(ctx, g0, g0 + m->n);
+    return LFI_OK;
+}
+
+int lfi_upload_mosaic(lfi_ctx *ctx, const lfi_mosaic *m, int g0, const uint8_t *rgba, size_t pitch_bytes)
+{
+    const char *who = "lfi_upload_mosaic";
+    if(!ctx)
+        return LFI_EINVAL;
+    if(!ctx->grid && !ctx->inputs_released)
+        return fail(ctx, LFI_EINVAL, "lfi_set_grid has not been called");
+    if(const char *fault = mosaic_fault(m, ctx->cols, ctx->rows, g0))
+        return fail(ctx, LFI_EINVAL, std::string(who) + ": " + fault);
+    if(!rgba || pitch_bytes / 4 / (size_t)m->tiles_x < (size_t)ctx->width)
+        return fail(ctx, LFI_EINVAL, std::string(who) + ": the image's pointer is NULL or pitch_bytes is below tiles_x * W * 4");
+    const lfi::MosaicMap map = mosaic_map_of(*m, ctx->rows, g0);
+    for(int k = 0; k < m->n; k++)
+    {
+        // lfi_upload_image_async of the tile's rectangle: one 2D copy on the copy stream
+        uint32_t tx, ty, g;
+        lfi::mosaic_tile(map, (uint32_t)k, tx, ty, g);
+        if(int rc = lfi_upload_image_async(ctx, (int)g, rgba + (size_t)ty * ctx->height * pitch_bytes + (size_t)tx * ctx->width * 4, pitch_bytes))
+            return rc;
+    }
+    return LFI_OK;
 }
 
 namespace {

@@ -26,6 +26,11 @@ Interpolator::Interpolator(std::string inputPath, int inChromaSite) : input{inpu
     init();
 }
 
+Interpolator::Interpolator(std::string inputPath, int inChromaSite, MosaicInput mosaic) : input{inputPath}, inSiteMode{inChromaSite}, mosaicInput{mosaic}
+{
+    loadMosaic();
+}
+
 Interpolator::Interpolator(lfi::IVec2 inColsRows, lfi::IVec2 inResolution, uint32_t seed, int inDevice)
     : device{inDevice}, colsRows{inColsRows}, resolution{inResolution.x, inResolution.y, 4}
 {
@@ -98,12 +103,12 @@ void Interpolator::init()
 
 bool Interpolator::isVideo() const
 {
-    return video != nullptr;
+    return video != nullptr || mosaicVideo != nullptr;
 }
 
 int Interpolator::frameCount() const
 {
-    return video ? video->frameCount() : 1;
+    return video ? video->frameCount() : mosaicVideo ? mosaicVideo->frameCount() : 1;
 }
 
 int Interpolator::inputDepth() const
@@ -118,9 +123,97 @@ void Interpolator::setInputFrame(int t)
     inputFrame = t;
 }
 
+lfi_mosaic Interpolator::mosaicMap() const
+{
+    lfi_mosaic m{};
+    m.tiles_x = mosaicInput.tiles.x, m.tiles_y = mosaicInput.tiles.y;
+    m.first_tile = 0, m.n = mosaicInput.tiles.x * mosaicInput.tiles.y;
+    m.order = mosaicInput.rowsOrder ? LFI_MOSAIC_ROWS : LFI_MOSAIC_GRID;
+    m.flags = mosaicInput.bottomUp ? LFI_MOSAIC_BOTTOM_UP : 0u;
+    return m;
+}
+
+// The mosaic file: everything that can be refused is refused from the file alone, then the context is created.  An image goes up at once
+// (one lfi_upload_mosaic), a Y4M's frames as interpolate() renders their time steps
+void Interpolator::loadMosaic()
+{
+    const lfi::IVec2 tiles = mosaicInput.tiles;
+    if(tiles.x < 1 || tiles.y < 1 || static_cast<long long>(tiles.x) * tiles.y > LFI_MAX_IMAGES)
+        throw std::runtime_error("A mosaic needs CxR tiles, both at least 1 and at most " + std::to_string(LFI_MAX_IMAGES) + " in all!");
+    const std::string ext = std::filesystem::path(input).extension().string();
+    const bool y4m = ext == ".y4m" || ext == ".Y4M";
+    lfi::Image image;
+    int frameW = 0, frameH = 0;
+    if(y4m)
+    {
+        mosaicVideo = std::make_unique<lfi::Y4mReader>(input, true);
+        if(mosaicVideo->info().depth == 10)
+            throw std::runtime_error("10-bit mosaics are not supported: " + input + " is C420p10, a mosaic video has to be 8-bit (C420jpeg, C420mpeg2)!");
+        frameW = mosaicVideo->info().width, frameH = mosaicVideo->info().height;
+    }
+    else
+    {
+        image = lfi::loadImage(input);
+        frameW = image.width, frameH = image.height;
+    }
+    if(frameW % tiles.x != 0 || frameH % tiles.y != 0)
+        throw std::runtime_error("The mosaic " + input + " is " + std::to_string(frameW) + "x" + std::to_string(frameH) + ": that does not divide into " +
+                                 std::to_string(tiles.x) + "x" + std::to_string(tiles.y) + " tiles without a remainder!");
+    resolution = {frameW / tiles.x, frameH / tiles.y, 4};
+    if(y4m && (resolution.x % 2 != 0 || resolution.y % 2 != 0))
+        throw std::runtime_error("The tiles of the mosaic video " + input + " are " + std::to_string(resolution.x) + "x" + std::to_string(resolution.y) +
+                                 ": a YUV 4:2:0 mosaic needs an even tile width and height (an odd size puts a 2x2 chroma block across two tiles)!");
+    colsRows = mosaicInput.rowsOrder ? lfi::IVec2{tiles.x * tiles.y, 1} : tiles;
+    check(lfi_create(device, &context));
+    check(lfi_set_grid(context, colsRows.x, colsRows.y, resolution.x, resolution.y));
+    if(y4m)
+    {
+        inSiting = lfi::y4mInputSiting(mosaicVideo->info().chroma, inSiteMode);
+        if(inSiting == LFI_YUV_SITING_LEFT)
+            std::cout << "The mosaic video's chroma is read as left-sited (C420mpeg2)." << std::endl;
+        return;
+    }
+    std::cout << "Uploading the mosaic to GPU..." << std::endl;
+    const lfi_mosaic m = mosaicMap();
+    check(lfi_upload_mosaic(context, &m, 0, image.pixels.data(), static_cast<size_t>(frameW) * channels));
+    check(lfi_upload_wait(context)); // the image's memory goes when this function returns
+}
+
+// Time step inputFrame of a Y4M mosaic: the frame read into page-locked memory as the I420 frame it is, split into the grid on the device
+void Interpolator::uploadMosaicFrame()
+{
+    if(contexts.size() > 1)
+        throw std::runtime_error("Several time steps of a light-field video work on one GPU only!");
+    if(leanInputs)
+        throw std::runtime_error("Lean inputs cannot be combined with a mosaic: a mosaic frame cannot be expanded straight into the planar copy of the inputs!");
+    const size_t frameBytes = mosaicVideo->frameBytes();
+    if(!inFrames)
+    {
+        inFramesPinned = lfi_alloc_pinned(frameBytes, reinterpret_cast<void **>(&inFrames)) == LFI_OK;
+        if(!inFramesPinned)
+        {
+            inFramesPageable.resize(frameBytes);
+            inFrames = inFramesPageable.data();
+        }
+    }
+    std::cout << "Uploading time step " << inputFrame << " to GPU..." << std::endl;
+    check(lfi_upload_wait(context)); // the previous step's copies have left the frame's memory
+    mosaicVideo->readFrame(inputFrame, inFrames);
+    const int range = inRange >= 0 ? inRange : (mosaicVideo->info().fullRange == 1 ? LFI_YUV_FULL : LFI_YUV_LIMITED);
+    check(lfi_set_yuv_siting(context, inSiting, outSiting));
+    lfi_yuv_surfaces surfaces{};
+    check(lfi_yuv_surfaces_packed(LFI_YUV_I420, LFI_MEM_HOST, inFrames, mosaicVideo->info().width, mosaicVideo->info().height, &surfaces));
+    const lfi_mosaic m = mosaicMap();
+    check(lfi_upload_mosaic_yuv(context, &m, 0, inMatrix, range, inChroma, &surfaces));
+    check(lfi_upload_wait(context));
+    loadedFrame = inputFrame;
+}
+
 // Time step inputFrame of every camera: read into page-locked memory as the I420 frames they are, one call for the grid
 void Interpolator::uploadVideoFrame()
 {
+    if(mosaicVideo)
+        return uploadMosaicFrame();
     if(contexts.size() > 1)
         throw std::runtime_error("Several time steps of a light-field video work on one GPU only!");
     const size_t frameBytes = video->frameBytes();
@@ -247,6 +340,8 @@ void Interpolator::interpolate(std::string outputPath, std::string trajectory, f
     if(leanInputs)
     {
         // the context will hold only the planar copy of the inputs: whatever reads the RGBA planes, or needs a second context, is refused now
+        if(mosaicVideo)
+            throw std::runtime_error("Lean inputs cannot be combined with a mosaic: a mosaic frame cannot be expanded straight into the planar copy of the inputs!");
         if(!video)
             throw std::runtime_error("Lean inputs belong to a light-field video: the input has to be a directory of .y4m files!");
         if(inRange > 0 || autofocus || autoRange.x != 0 || autoRange.y != 0 || focusTiles.x != 0 || focusTiles.y != 0 || viewMaps)
@@ -258,7 +353,7 @@ void Interpolator::interpolate(std::string outputPath, std::string trajectory, f
     }
     if(outSiting != LFI_YUV_SITING_CENTRE && !rgbdY4mPath.empty())
         throw std::runtime_error("An RGB-D video frame cannot be left-sited: the chroma filter would mix the colour and the depth half (--chroma-site left with --rgbd-y4m)!");
-    if(video && loadedFrame != inputFrame)
+    if(isVideo() && loadedFrame != inputFrame)
         uploadVideoFrame();
     if(quiltTile.x > 0 || quiltTile.y > 0)
     {

@@ -25,6 +25,18 @@ class Interpolator
         // inChromaSite: how the chroma of a light-field video's frames is sited — lfi::Y4M_SITE_CENTRE, _LEFT or _AUTO (by the files' C tag:
         // C420mpeg2 left, everything else centre; the cameras' tags must agree then)
         Interpolator(std::string inputPath, int inChromaSite = lfi::Y4M_SITE_CENTRE);
+        // A mosaic as input: inputPath is ONE file that holds every image as a tile of a frame of tiles.x × tiles.y tiles — an image (PNG,
+        // JPEG, PPM: lfi_upload_mosaic) or a .y4m whose every frame is such a frame (lfi_upload_mosaic_yuv; a light-field video: frame t is
+        // time step t, isVideo() is true).  rowsOrder false: the tiles are the cameras of a tiles.x × tiles.y grid (LFI_MOSAIC_GRID);
+        // true: they are the images of a (tiles.x·tiles.y) × 1 grid in reading order (LFI_MOSAIC_ROWS: a quilt); bottomUp: the tile rows
+        // count from the frame's bottom (Looking-Glass quilts).  The image size is the frame's divided by the tiles: a remainder throws,
+        // and so do an odd quotient and C420p10 for a .y4m — before any GPU is touched
+        struct MosaicInput
+        {
+            lfi::IVec2 tiles{0, 0};
+            bool rowsOrder{false}, bottomUp{false};
+        };
+        Interpolator(std::string inputPath, int inChromaSite, MosaicInput mosaic);
         ~Interpolator();
         void interpolate(std::string outputPath, std::string trajectory, float focus, float range, std::string method, float effect, float aspect);
 
@@ -216,6 +228,11 @@ class Interpolator
         std::unique_ptr<lfi::Y4mWriter> rgbdY4mWriter; // open from the first stored step to finish()
         std::ofstream nv12File;                    // open from the first stored step to finish()
         std::unique_ptr<LfLoader> video;           // the input, where it is a light-field video
+        MosaicInput mosaicInput;                   // tiles.x > 0: the input is a mosaic file
+        std::unique_ptr<lfi::Y4mReader> mosaicVideo; // the input, where it is a Y4M mosaic: a light-field video in one file
+        lfi_mosaic mosaicMap() const;
+        void loadMosaic();
+        void uploadMosaicFrame();
         int inputFrame{0}, loadedFrame{-1};        // the time step to render / the one on the device
         int inMatrix{LFI_YUV_BT709}, inRange{-1}, inChroma{LFI_CHROMA_BILINEAR};
         int inSiteMode{lfi::Y4M_SITE_CENTRE}; // the constructor's inChromaSite

@@ -6,7 +6,7 @@
 // lenticular display, interlaced on the GPU), --y4m / --nv12 / --fps / --yuv-matrix / --yuv-range (the views as one YUV 4:2:0 video file, converted on
 // the GPU), --yuv-depth / --p010 (10-bit frames: C420p10 Y4M files and raw P010), --quilt-y4m (the quilt as one YUV 4:2:0 video frame per time step: a quilt video), --rgbd-y4m / --rgbd-view / --rgbd-tile / --rgbd-map /
 // --rgbd-invert (a view with its focus map beside it as one YUV 4:2:0 video frame per time step: RGB-D video), --chroma-site / --in-chroma-site (left-sited chroma, MPEG-2 / H.264 siting, for the frames written / read), --frames / --in-matrix / --in-range / --in-chroma (a light-field video as input: a directory of per-camera Y4M files whose frames
-// become the images on the GPU), --lean-inputs (such a video at fixed focus from the planar copy of the inputs alone) and --synthetic for runs without a dataset.
+// become the images on the GPU), --lean-inputs (such a video at fixed focus from the planar copy of the inputs alone), --mosaic / --mosaic-order / --mosaic-bottom-up (one image or Y4M file that holds every image as a tile, split on the GPU) and --synthetic for runs without a dataset.
 #include <array>
 #include <iostream>
 #include <memory>
@@ -82,6 +82,9 @@ int main(int argc, char **argv)
                           "--lean-inputs - with a light-field video rendered at fixed focus: after the first time step the GPU keeps only the planar copy of the inputs (3 bytes per pixel and image instead of 7) and every later step's frames are expanded straight into it in one pass; the files written are the same; not with -r, -F, -c, --autofocus, --auto-range, --focus-tiles, --view-maps, -g above 1 or --synthetic\n"
                           "--compare DIR - after the render, compare every view with DIR/NN.png (the names -o writes; same size) on the GPU, all views in one pass: prints \"compare NN psnr <dB> ssim <index> maxdiff <largest byte difference> differing <colour bytes that differ>\" per view, then \"compare all psnr ... ssim ...\"; one GPU\n"
                           "--compare-methods - render the views with the other method first (STD if -m TEN_WM, TEN_WM if -m STD; same parameters), keep them on the GPU, render with -m and compare the two there; prints the lines of --compare; the stored images are those of -m; one GPU; not with --compare\n"
+                          "--mosaic CxR - -i is ONE file that holds every image as a tile of a frame of C x R tiles, split into the grid on the GPU: an image (PNG, JPEG, PPM; e.g. a quilt) or a .y4m whose every frame is such a frame - a light-field video in one stream: frame t is time step t under --frames, --in-matrix, --in-range, --in-chroma and --in-chroma-site apply (auto reads the file's tag), the output is that of a directory of per-camera videos. The image size is the frame's divided by the tiles (a remainder is an error; for a .y4m an odd quotient too). 10-bit .y4m mosaics (C420p10) are not supported; not with --lean-inputs (a mosaic frame cannot go straight into the planar copy) or --synthetic\n"
+                          "--mosaic-order grid|rows - with --mosaic: grid (default): the tile in column c and row r is the camera of the file <r>_<c> of a C x R grid. rows: the tiles in reading order are the images of a (C*R) x 1 grid - the order of -q's quilt\n"
+                          "--mosaic-bottom-up - with --mosaic: the tile rows count from the frame's bottom, as Looking-Glass quilts do\n"
                           "--synthetic cols,rows,width,height[,seed] - use a generated light field instead of -i\n"
                           "--unified-map - all-focus TEN_WM reads the filtered focus map like STD (the reference reads the unfiltered one)\n"
                         };
@@ -109,6 +112,7 @@ int main(int argc, char **argv)
         // second context
         const std::pair<bool, const char *> refused[] = {
             {synthetic, "--synthetic (it needs a light-field video: -i with a directory of .y4m files)"},
+            {static_cast<bool>(args["--mosaic"]), "--mosaic (a mosaic frame cannot be expanded straight into the planar copy of the inputs: use a directory of per-camera .y4m files)"},
             {static_cast<bool>(args["--autofocus"]), "--autofocus (the focus curve reads the RGBA planes)"},
             {static_cast<bool>(args["--auto-range"]), "--auto-range (the focus tiles read the RGBA planes)"},
             {static_cast<bool>(args["--focus-tiles"]), "--focus-tiles (the focus tiles read the RGBA planes)"},
@@ -124,6 +128,28 @@ int main(int argc, char **argv)
                 std::cerr << "--lean-inputs (only the planar copy of the inputs stays on the GPU) cannot be combined with " << what << "." << std::endl;
                 return EXIT_FAILURE;
             }
+    }
+
+    if((args["--mosaic-order"] || args["--mosaic-bottom-up"]) && !args["--mosaic"])
+    {
+        std::cerr << "--mosaic-order and --mosaic-bottom-up belong to a mosaic: they need --mosaic CxR." << std::endl;
+        return EXIT_FAILURE;
+    }
+    if(args["--mosaic"] && synthetic)
+    {
+        std::cerr << "--mosaic splits the file given with -i: it cannot be combined with --synthetic." << std::endl;
+        return EXIT_FAILURE;
+    }
+    bool mosaicRows = false;
+    if(args["--mosaic-order"])
+    {
+        const std::string text = static_cast<std::string>(args["--mosaic-order"]);
+        if(text != "grid" && text != "rows")
+        {
+            std::cerr << "--mosaic-order expects grid or rows." << std::endl;
+            return EXIT_FAILURE;
+        }
+        mosaicRows = text == "rows";
     }
 
     if(args["--autofocus"] && (args["-F"] || args["-c"] || args["--view-maps"]))
@@ -527,7 +553,29 @@ int main(int argc, char **argv)
         else
         {
             Interpolator::setDefaultDevice(device);
-            interpolator = std::make_unique<Interpolator>(path, inChromaSite);
+            if(args["--mosaic"])
+            {
+                // "CxR": columns x rows of tiles
+                const std::string text = static_cast<std::string>(args["--mosaic"]);
+                const size_t cut = text.find_first_of("xX");
+                Interpolator::MosaicInput mosaic;
+                try
+                {
+                    if(cut != std::string::npos)
+                        mosaic.tiles = {std::stoi(text.substr(0, cut)), std::stoi(text.substr(cut + 1))};
+                }
+                catch(const std::exception &)
+                {
+                    mosaic.tiles = {0, 0};
+                }
+                if(mosaic.tiles.x < 1 || mosaic.tiles.y < 1)
+                    throw std::runtime_error("--mosaic expects CxR, columns x rows of tiles, both at least 1");
+                mosaic.rowsOrder = mosaicRows;
+                mosaic.bottomUp = static_cast<bool>(args["--mosaic-bottom-up"]);
+                interpolator = std::make_unique<Interpolator>(path, inChromaSite, mosaic);
+            }
+            else
+                interpolator = std::make_unique<Interpolator>(path, inChromaSite);
         }
         if(args["-n"])
             interpolator->setViewCount(static_cast<int>(args["-n"]));
@@ -649,7 +697,7 @@ int main(int argc, char **argv)
         if(args["--compare-methods"])
             interpolator->setCompareMethods(true);
         if((args["--frames"] || args["--in-matrix"] || args["--in-range"] || args["--in-chroma"] || args["--in-chroma-site"]) && !interpolator->isVideo())
-            throw std::runtime_error("--frames, --in-matrix, --in-range, --in-chroma and --in-chroma-site belong to a light-field video: -i has to be a directory of .y4m files");
+            throw std::runtime_error("--frames, --in-matrix, --in-range, --in-chroma and --in-chroma-site belong to a light-field video: -i has to be a directory of .y4m files, or a .y4m mosaic (--mosaic)");
         if(args["--lean-inputs"])
         {
             if(!interpolator->isVideo())

@@ -7,7 +7,8 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from .abi import LFI_LENT_INVERT, Lenticular
+from .abi import LFI_LENT_INVERT, Lenticular, Mosaic, YuvSurfaces
+from .abi import mosaic_map as _abi_mosaic_map
 from .build import HOST_LIB
 
 _lib = None
@@ -214,6 +215,32 @@ def write_y4m(path: str, frames: np.ndarray, width: int, height: int, fps=(30, 1
         rc = lib.lfi_host_y4m_write(*head, err, len(err))
     if rc != 0:
         raise ValueError(err.value.decode())
+
+
+def mosaic_map(tiles_x: int, tiles_y: int, cols: int, rows: int, order="rows", bottom_up: bool = False, first_tile: int = 0, n: int | None = None,
+               g0: int = 0) -> np.ndarray:
+    """Where the tiles of a mosaic frame go (lfi_mosaic_map, include/lfi.h): [n][3] int32, row k = (tx, ty, g) — tile k's column and row in
+    the frame of tiles_x × tiles_y tiles and the image it becomes in a cols × rows grid."""
+    return _abi_mosaic_map(Mosaic.make(tiles_x, tiles_y, order, bottom_up, first_tile, n), cols, rows, g0)
+
+
+def upload_mosaic_yuv(ctx, frame: np.ndarray, tiles_x: int, tiles_y: int, fmt="i420", order="grid", bottom_up: bool = False, matrix="709",
+                      range="limited", chroma="bilinear") -> None:
+    """Context.upload_mosaic_yuv of one tight host frame ([frame bytes] uint8: I420 or NV12 planes of tiles_x·W × tiles_y·H) that holds the
+    whole grid of ctx: order "grid" for a cols × rows mosaic of cameras, "rows" for a quilt.  Keep `frame` alive until upload_wait / sync."""
+    assert frame.dtype == np.uint8 and frame.ndim == 1 and frame.strides[0] == 1
+    mw, mh = tiles_x * ctx.width, tiles_y * ctx.height
+    assert frame.size >= mw * mh * 3 // 2
+    nv12 = fmt in ("nv12", 1)
+    s = YuvSurfaces.make(fmt, "host", frame.ctypes.data, frame.size, mw, mw * mh, mw if nv12 else mw // 2, 0 if nv12 else mw * mh + (mw // 2) * (mh // 2),
+                         keep=frame)
+    ctx.upload_mosaic_yuv(Mosaic.make(tiles_x, tiles_y, order, bottom_up), s, 0, matrix, range, chroma)
+
+
+def upload_mosaic(ctx, rgba: np.ndarray, tiles_x: int, tiles_y: int, order="grid", bottom_up: bool = False) -> None:
+    """Context.upload_mosaic of one host RGBA image (tiles_y·H, tiles_x·W, 4) that holds the whole grid of ctx, e.g. a quilt loaded with
+    load_image (order "rows", bottom_up for a Looking-Glass quilt).  Keep `rgba` alive until upload_wait / sync."""
+    ctx.upload_mosaic(Mosaic.make(tiles_x, tiles_y, order, bottom_up), rgba, 0)
 
 
 Y4M_SITE_MODES = {"centre": 0, "left": 1, "auto": 2}
