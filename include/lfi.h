@@ -800,6 +800,21 @@ int lfi_mosaic_map(const lfi_mosaic *m, int cols, int rows, int g0, int k, int *
  * src refused by lfi_yuv_surfaces_check for (MW, MH, 1); LFI_MEM_DEVICE with a pointer that is not device memory of the context's device
  * or whose allocation ends before the frame does. */
 int lfi_upload_mosaic_yuv(lfi_ctx *ctx, const lfi_mosaic *m, int g0, int matrix, int range, int chroma, const lfi_yuv_surfaces *src);
+/* lfi_upload_mosaic_yuv for a context that holds only the derived planar copy of its inputs (lfi_release_inputs): the tiles of the frame are
+ * expanded STRAIGHT into the three byte planes of their mapped images of that copy, padding included, in one pass — 1.5 bytes read and 3
+ * written per pixel, no RGBA image in between, no rebuild afterwards.  DEFINITION, no new arithmetic: after the call the planes of every
+ * mapped image g hold what they would hold had the frame gone through lfi_upload_mosaic_yuv before lfi_release_inputs: byte j of a row of
+ * plane (g, c) is channel c of pixel clamp(j - padx - phase[g], 0, W - 1) of the image the mosaic definition above gives for g's tile
+ * (lfi_debug_derived_layout).  Chroma is clamped at the TILE's edges; no value of a neighbouring tile, of pitch padding or of a tile
+ * outside [first_tile, first_tile + n) reaches any plane; images other than the mapped ones keep every byte.  The copy keeps its layout,
+ * its phases and its validity, as in lfi_upload_images_yuv_derived, whose ordering this call has too: the work runs on the copy stream
+ * behind renders already enqueued, later renders read the new frames without a host wait.  The mosaic, g0, matrix, range, chroma, src and
+ * the routing (a device frame with multiples of 16 throughout: in place, ONE launch for all n tiles whatever W is; everything else: the
+ * staging buffer in chunks of whole tile rows, one 2D copy per plane and one launch each) are lfi_upload_mosaic_yuv's.
+ * LFI_EINVAL, the context usable, the copy, the staging buffer and lfi_memory.workspace_bytes untouched: a context that still holds its
+ * RGBA planes (lfi_release_inputs first); no grid; no planar copy; a row window; matrix, range and chroma; and whatever
+ * lfi_upload_mosaic_yuv refuses of the mosaic, of an odd W or H, of the frame's size, of the 10-bit formats, of src and of device memory. */
+int lfi_upload_mosaic_yuv_derived(lfi_ctx *ctx, const lfi_mosaic *m, int g0, int matrix, int range, int chroma, const lfi_yuv_surfaces *src);
 /* An RGBA mosaic in host memory (a quilt PNG): rows of pitch_bytes >= tiles_x*W*4.  By definition lfi_upload_image_async of every tile's
  * rectangle into its mapped image: one 2D copy per tile on the copy stream, no kernel; odd sizes are allowed; ordering, the row window and
  * the lifetime of rgba are lfi_upload_image_async's.  LFI_EINVAL: no grid, a mosaic lfi_mosaic_map refuses, rgba NULL, a pitch too small. */
@@ -808,6 +823,10 @@ int lfi_upload_mosaic(lfi_ctx *ctx, const lfi_mosaic *m, int g0, const uint8_t *
  * 256 MiB) — out5 = { first tile row in ROWS order, tile rows, the frame's first tile row copied, first tile k, tiles }.  LFI_EINVAL: a bad
  * mosaic (judged for its natural grid: tiles_x x tiles_y under GRID, n x 1 under ROWS), an odd size, no such chunk.  Needs no GPU. */
 int lfi_debug_mosaic_chunk(const lfi_mosaic *m, int tile_w, int tile_h, size_t cap_bytes, int chunk, int32_t *out5);
+/* tests: the cap of the staging chunks of lfi_upload_mosaic_yuv and lfi_upload_mosaic_yuv_derived, in place of their own 256 MiB, so that a
+ * small frame takes more than one chunk (lfi_debug_mosaic_chunk reports the plan for a cap).  0, the default: the calls' own cap, every
+ * byte, copy and launch as without this call.  A context setting; LFI_EINVAL: ctx NULL. */
+int lfi_debug_set_mosaic_chunk_cap(lfi_ctx *ctx, size_t cap_bytes);
 int lfi_upload_map(lfi_ctx *ctx, int k, const uint8_t *rgba, size_t pitch_bytes); /* tests: inject a focus map */
 /* view v's map k (0 or 1) of the per-view maps (lfi_view_focus_maps).  Synchronous.  The upload is a test hook like lfi_upload_map (it
  * allocates the per-view maps if needed and does not put them in use: renders read them after a successful lfi_view_focus_maps). */

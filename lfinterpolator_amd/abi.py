@@ -70,6 +70,7 @@ ABI_SYMBOLS = [
     "lfi_download_quilt_yuv", "lfi_download_rgbd_yuv", "lfi_set_yuv_siting", "lfi_yuv_siting",
     "lfi_upload_images_yuv_derived", "lfi_debug_derived_layout", "lfi_debug_download_derived",
     "lfi_mosaic_map", "lfi_upload_mosaic_yuv", "lfi_upload_mosaic", "lfi_debug_mosaic_chunk",
+    "lfi_upload_mosaic_yuv_derived", "lfi_debug_set_mosaic_chunk_cap",
 ]
 
 
@@ -282,6 +283,8 @@ def load_hip_library() -> C.CDLL:
         "lfi_debug_derived_layout": (i, [vp, C.POINTER(DerivedLayout), vp]),
         "lfi_mosaic_map": (i, [C.POINTER(Mosaic), i, i, i, i, C.POINTER(i), C.POINTER(i), C.POINTER(i)]),
         "lfi_upload_mosaic_yuv": (i, [vp, C.POINTER(Mosaic), i, i, i, i, C.POINTER(YuvSurfaces)]),
+        "lfi_upload_mosaic_yuv_derived": (i, [vp, C.POINTER(Mosaic), i, i, i, i, C.POINTER(YuvSurfaces)]),
+        "lfi_debug_set_mosaic_chunk_cap": (i, [vp, sz]),
         "lfi_upload_mosaic": (i, [vp, C.POINTER(Mosaic), i, vp, sz]),
         "lfi_debug_mosaic_chunk": (i, [C.POINTER(Mosaic), i, i, sz, i, vp]),
         "lfi_debug_download_derived": (i, [vp, i, i, vp]),
@@ -442,6 +445,18 @@ class Context:
         self._check(self._lib.lfi_upload_mosaic_yuv(self._h, C.byref(mosaic) if mosaic is not None else None, g0, YUV_MATRICES.get(matrix, matrix),
                                                     YUV_RANGES.get(range, range), YUV_CHROMAS.get(chroma, chroma),
                                                     C.byref(surfaces) if surfaces is not None else None))
+
+    def upload_mosaic_yuv_derived(self, mosaic: Mosaic, surfaces: YuvSurfaces, g0: int = 0, matrix="709", range="limited", chroma="bilinear") -> None:
+        """upload_mosaic_yuv for a context whose inputs were released (lfi_upload_mosaic_yuv_derived): the frame's tiles go straight into the
+        planes of their mapped images of the derived planar copy, padding included, in one pass.  Ordered like upload_images_yuv_derived."""
+        self._check(self._lib.lfi_upload_mosaic_yuv_derived(self._h, C.byref(mosaic) if mosaic is not None else None, g0, YUV_MATRICES.get(matrix, matrix),
+                                                            YUV_RANGES.get(range, range), YUV_CHROMAS.get(chroma, chroma),
+                                                            C.byref(surfaces) if surfaces is not None else None))
+
+    def set_mosaic_chunk_cap(self, cap_bytes: int = 0) -> None:
+        """tests: the cap of the staging chunks of upload_mosaic_yuv and upload_mosaic_yuv_derived (lfi_debug_set_mosaic_chunk_cap); 0: the
+        calls' own 256 MiB"""
+        self._check(self._lib.lfi_debug_set_mosaic_chunk_cap(self._h, cap_bytes))
 
     def upload_mosaic(self, mosaic: Mosaic, rgba: np.ndarray, g0: int = 0) -> None:
         """The grid's images from one host RGBA image of tiles_y·H × tiles_x·W pixels (lfi_upload_mosaic): upload_image_async of every tile's

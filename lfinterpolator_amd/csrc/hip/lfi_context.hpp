@@ -293,6 +293,8 @@ struct lfi_ctx
     // lfi_upload_images_yuv420, lfi_upload_images_yuv from host or unaligned device surfaces: a chunk's staged frames, as yuvs_expand reads
     // them; written and read on the copy stream only, in stream order (grows, kept)
     DeviceBuffer yuv_in;
+    // lfi_debug_set_mosaic_chunk_cap: the cap of the mosaic YUV uploads' staging chunks in bytes; 0: the calls' own 256 MiB
+    size_t mosaic_chunk_cap = 0;
     // parameter block
     bool have_params = false;
     int views_n = 0, k_pad = 0, v_pad = 0, n_focus_ids = 0;

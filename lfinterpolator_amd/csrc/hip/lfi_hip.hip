@@ -17,6 +17,7 @@
 #include "yuv_surfaces.hpp"
 #include "yuv10.hpp"
 #include "yuv_mosaic.hpp"
+#include "yuv_mosaic_derived.hpp"
 #include "yuv_derived.hpp"
 #include "lfi_rccl.hpp"
 
@@ -723,14 +724,19 @@ int lfi_debug_mosaic_chunk(const lfi_mosaic *m, int tile_w, int tile_h, size_t c
     return LFI_OK;
 }
 
-int lfi_upload_mosaic_yuv(lfi_ctx *ctx, const lfi_mosaic *m, int g0, int matrix, int range, int chroma, const lfi_yuv_surfaces *src)
+namespace {
+
+// Behind the two mosaic YUV calls, as upload_yuv_surfaces is behind the frame calls: every check, the staging buffer, the ordering preamble
+// and the routing.  derived: the tiles go into the planar copy (yuvs_mosaic_derived_expand), which stays the valid copy it was — no version
+// moves; else into the RGBA planes (yuvs_mosaic_expand), and the copy is rebuilt from them by the next render that reads it
+int upload_mosaic_yuv_surfaces(lfi_ctx *ctx, const char *who, const lfi_mosaic *m, int g0, int matrix, int range, int chroma, const lfi_yuv_surfaces *src,
+                               bool derived)
 {
-    const char *who = "lfi_upload_mosaic_yuv";
     if(!ctx)
         return LFI_EINVAL;
     if(!m)
         return fail(ctx, LFI_EINVAL, std::string(who) + ": the mosaic is NULL");
-    if(int rc = check_yuv_upload(ctx, who, g0, m->n, matrix, range, chroma))
+    if(int rc = check_yuv_upload(ctx, who, g0, m->n, matrix, range, chroma, derived))
         return rc;
     if(const char *fault = mosaic_fault(m, ctx->cols, ctx->rows, g0))
         return fail(ctx, LFI_EINVAL, std::string(who) + ": " + fault);
@@ -757,8 +763,9 @@ int lfi_upload_mosaic_yuv(lfi_ctx *ctx, const lfi_mosaic *m, int g0, int matrix,
     const bool in_place = yuv_surfaces_in_place(one);
     const bool nv12 = src->format == LFI_YUV_NV12;
     const size_t tile_row_bytes = mosaic_tile_row_bytes(MW, H);
+    const size_t cap = ctx->mosaic_chunk_cap ? ctx->mosaic_chunk_cap : MOSAIC_CHUNK_CAP; // lfi_debug_set_mosaic_chunk_cap
     MosaicChunk c{};
-    (void)mosaic_chunk(*m, tile_row_bytes, MOSAIC_CHUNK_CAP, 0, &c); // chunk 0 exists and is the largest
+    (void)mosaic_chunk(*m, tile_row_bytes, cap, 0, &c); // chunk 0 exists and is the largest
     const size_t need = in_place ? 0 : lfi::yuv_geometry(MW, c.nr * H).dev_frame_bytes;
     if(ctx->yuv_in.bytes() < need)
     {
@@ -777,16 +784,32 @@ int lfi_upload_mosaic_yuv(lfi_ctx *ctx, const lfi_mosaic *m, int g0, int matrix,
     a.in.W = (uint32_t)W, a.in.H = (uint32_t)H, a.in.cw = (uint32_t)W / 2, a.in.ch = (uint32_t)H / 2;
     a.in.blocks_x = ((uint32_t)W + lfi::YUV_BLOCK_W - 1) / lfi::YUV_BLOCK_W;
     a.in.k = lfi::YUV_IN_COEFFS[matrix * 2 + range];
-    a.in.dst = ctx->grid.get();
-    a.in.image_stride = in_plane_bytes(ctx);
-    a.in.rows16 = W % 4 == 0;
+    if(!derived)
+    {
+        a.in.dst = ctx->grid.get();
+        a.in.image_stride = in_plane_bytes(ctx);
+        a.in.rows16 = W % 4 == 0;
+    }
     a.map = mosaic_map_of(*m, ctx->rows, g0);
     const bool nearest = chroma == LFI_CHROMA_NEAREST, left = ctx->yuv_in_siting == LFI_YUV_SITING_LEFT, unaligned = W % lfi::YUV_BLOCK_W != 0;
+    // the ONE launch for the nk tiles from a.k0 on, from the surfaces a.in.s
+    auto launch = [&](int nk) -> hipError_t {
+        if(!derived)
+            return lfi::launch_yuvs_mosaic_expand(st, src->format, nearest, left, unaligned, a, nk);
+        // whole images (check_yuv_upload refuses a row window): the copy's planes hold in_rows = H rows of planar_pitch bytes
+        lfi::YuvsMosaicDerivedArgs d{};
+        d.d.in = a.in;
+        d.d.planar = ctx->planar.get();
+        d.d.phase = ctx->d_planar_phase.as<int32_t>();
+        d.d.pitch = (uint32_t)ctx->planar_pitch, d.d.padx = (uint32_t)ctx->planar_padx;
+        d.map = a.map, d.k0 = a.k0, d.ty_bias = a.ty_bias;
+        return lfi::launch_yuvs_mosaic_derived_expand(st, src->format, nearest, left, unaligned, d, nk);
+    };
     if(in_place)
     {
         // the frame is read where it lies: ONE launch for all n tiles
         a.in.s = caller_surfaces(*src);
-        LFI_HIP(ctx, lfi::launch_yuvs_mosaic_expand(st, src->format, nearest, left, unaligned, a, m->n));
+        LFI_HIP(ctx, launch(m->n));
     }
     else
     {
@@ -794,7 +817,7 @@ int lfi_upload_mosaic_yuv(lfi_ctx *ctx, const lfi_mosaic *m, int g0, int matrix,
         // other on the copy stream, so stream order is all the staging buffer needs
         const hipMemcpyKind kind = src->memory == LFI_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
         const uint8_t *base = static_cast<const uint8_t *>(src->base);
-        for(int i = 0; mosaic_chunk(*m, tile_row_bytes, MOSAIC_CHUNK_CAP, i, &c); i++)
+        for(int i = 0; mosaic_chunk(*m, tile_row_bytes, cap, i, &c); i++)
         {
             const lfi::YuvGeometry g = lfi::yuv_geometry(MW, c.nr * H);
             const lfi::YuvSurfaces t = staged_surfaces(g, src->format, ctx->yuv_in.get());
@@ -806,11 +829,32 @@ int lfi_upload_mosaic_yuv(lfi_ctx *ctx, const lfi_mosaic *m, int g0, int matrix,
                 LFI_HIP(ctx, hipMemcpy2DAsync(t.base + t.cr_offset, t.c_pitch, base + src->cr_offset + c0 * src->c_pitch, src->c_pitch, (size_t)MW / 2, g.ch, kind, st));
             a.in.s = t;
             a.k0 = (uint32_t)c.k0, a.ty_bias = (uint32_t)c.ty0;
-            LFI_HIP(ctx, lfi::launch_yuvs_mosaic_expand(st, src->format, nearest, left, unaligned, a, c.nk));
+            LFI_HIP(ctx, launch(c.nk));
         }
     }
     // the images the tiles became: a contiguous range under ROWS, the whole grid under GRID
-    touch_images(ctx, g0, g0 + m->n);
+    if(!derived)
+        touch_images(ctx, g0, g0 + m->n);
+    return LFI_OK;
+}
+
+} // namespace
+
+int lfi_upload_mosaic_yuv(lfi_ctx *ctx, const lfi_mosaic *m, int g0, int matrix, int range, int chroma, const lfi_yuv_surfaces *src)
+{
+    return upload_mosaic_yuv_surfaces(ctx, "lfi_upload_mosaic_yuv", m, g0, matrix, range, chroma, src, false);
+}
+
+int lfi_upload_mosaic_yuv_derived(lfi_ctx *ctx, const lfi_mosaic *m, int g0, int matrix, int range, int chroma, const lfi_yuv_surfaces *src)
+{
+    return upload_mosaic_yuv_surfaces(ctx, "lfi_upload_mosaic_yuv_derived", m, g0, matrix, range, chroma, src, true);
+}
+
+int lfi_debug_set_mosaic_chunk_cap(lfi_ctx *ctx, size_t cap_bytes)
+{
+    if(!ctx)
+        return LFI_EINVAL;
+    ctx->mosaic_chunk_cap = cap_bytes;
     return LFI_OK;
 }
 

@@ -56,13 +56,19 @@ struct YuvsDerivedArgs
     uint32_t g0;          // frame z is image g0 + z
 };
 
-// the whole kernel; LEFT: left-sited chroma (yuvs_block_pixels' filter), the staging and the stores are the same
-template <int FORMAT, bool NEAREST, bool LEFT>
-__device__ __forceinline__ void yuvs_derived_spans(const YuvsDerivedArgs &a)
+// The whole kernel, for any source of an image's pixels — a policy whose members inline:
+//   src.image()    the index in the copy of the image that grid.z stands for (wave-uniform)
+//   Source::ASSEMBLED = false: step 1 is yuvs_block_pixels itself, on src.args() and src.frame(), the image taken as a frame of its own
+//   Source::ASSEMBLED = true:  step 1 is src.template block_pixels<FORMAT, NEAREST, LEFT>(bx, by, px), which gives the same pixels by other loads
+// a.in.W, H and ch are the image's.  LEFT: left-sited chroma (yuvs_block_pixels' filter).  Steps 2 and 3, the staging and the stores, are the
+// same for every source: the frame kernels below and the mosaic kernels of yuv_mosaic_derived.hpp.  The call of yuvs_block_pixels stands here,
+// not behind a member of the source, so that the frame kernels keep the instructions they had (profiles/r26_mosaic_derived_notes.md)
+template <int FORMAT, bool NEAREST, bool LEFT, class Source>
+__device__ __forceinline__ void yuvs_derived_spans(const YuvsDerivedArgs &a, const Source &src)
 {
     __shared__ __attribute__((aligned(16))) uint8_t lds[YUVD_ROWS][2][3][YUVD_LDS_PITCH];
     const uint32_t tid = threadIdx.x;
-    const uint32_t g = a.g0 + blockIdx.z;
+    const uint32_t g = src.image();
     const int32_t W = (int32_t)a.in.W;
     const int32_t first = (int32_t)a.padx + a.phase[g]; // byte of pixel 0
     const int32_t j0 = (int32_t)(blockIdx.x * YUVD_SPAN);
@@ -77,7 +83,10 @@ __device__ __forceinline__ void yuvs_derived_spans(const YuvsDerivedArgs &a)
         if(r < (uint32_t)YUVD_ROWS && b < nb && by < a.in.ch)
         {
             uint32_t px[2][8];
-            yuvs_block_pixels<FORMAT, NEAREST, LEFT>(a.in, a.in.s.base + (size_t)blockIdx.z * a.in.s.frame_stride, bx_lo + b, by, px);
+            if constexpr(Source::ASSEMBLED)
+                src.template block_pixels<FORMAT, NEAREST, LEFT>(bx_lo + b, by, px);
+            else
+                yuvs_block_pixels<FORMAT, NEAREST, LEFT>(src.args(), src.frame(), bx_lo + b, by, px);
 #pragma unroll
             for(int j = 0; j < 2; j++)
 #pragma unroll
@@ -124,17 +133,27 @@ __device__ __forceinline__ void yuvs_derived_spans(const YuvsDerivedArgs &a)
     }
 }
 
+// the pixel source of the frame kernels: frame grid.z of a.in.s is image a.g0 + grid.z
+struct YuvsFrameSource
+{
+    static constexpr bool ASSEMBLED = false;
+    const YuvsDerivedArgs &a;
+    __device__ __forceinline__ uint32_t image() const { return a.g0 + blockIdx.z; }
+    __device__ __forceinline__ const YuvsInArgs &args() const { return a.in; }
+    __device__ __forceinline__ const uint8_t *frame() const { return a.in.s.base + (size_t)blockIdx.z * a.in.s.frame_stride; }
+};
+
 template <int FORMAT, bool NEAREST>
 __global__ void __launch_bounds__(YUVD_THREADS) yuvs_derived_expand(const YuvsDerivedArgs a)
 {
-    yuvs_derived_spans<FORMAT, NEAREST, false>(a);
+    yuvs_derived_spans<FORMAT, NEAREST, false>(a, YuvsFrameSource{a});
 }
 
 // left-sited chroma, BILINEAR (NEAREST is yuvs_derived_expand's under either siting)
 template <int FORMAT>
 __global__ void __launch_bounds__(YUVD_THREADS) yuvs_derived_expand_left(const YuvsDerivedArgs a)
 {
-    yuvs_derived_spans<FORMAT, false, true>(a);
+    yuvs_derived_spans<FORMAT, false, true>(a, YuvsFrameSource{a});
 }
 
 // Enqueues the ONE yuvs_derived_expand launch for n frames.  The caller has checked sizes, alignment and memory as for launch_yuvs_expand;

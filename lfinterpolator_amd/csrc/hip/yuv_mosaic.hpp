@@ -214,6 +214,22 @@ __device__ __forceinline__ void yuvs_mosaic_block_pixels(const YuvsInArgs &a, co
             px[j][i] = yuv_in_pixel(a.k, (int32_t)y[j][i], su[j][i], sv[j][i]);
 }
 
+// The aligned path's tile as a frame of its own (W a multiple of 8): t, the caller's copy of `in`, gets c_offset and cr_offset patched so that
+// yuvs_block_pixels, which reads Y at frame + row·y_pitch and chroma at frame + c_offset (cr_offset) + row·c_pitch, reaches the tile whose Y
+// origin is column ox of Y row oy of the frame in.s from the pointer returned, the tile's Y origin.  Called by yuv_mosaic_derived.hpp.
+// yuvs_mosaic_block below keeps the same six lines in its own body: a function of its own is simplified on its own before it is inlined, and
+// in every shape tried that reordered the offset arithmetic of two to six of the twelve yuvs_mosaic_expand[_left] kernels, which must stay
+// instruction for instruction what they were (profiles/r26_mosaic_derived_notes.md)
+template <int FORMAT>
+__device__ __forceinline__ const uint8_t *yuvs_mosaic_tile_frame(const YuvsInArgs &in, const uint32_t ox, const uint32_t oy, YuvsInArgs &t)
+{
+    const size_t y_origin = (size_t)oy * in.s.y_pitch + ox;
+    const size_t c_origin = (size_t)(oy >> 1) * in.s.c_pitch + (FORMAT == YUVS_NV12 ? ox : ox >> 1);
+    t.s.c_offset = in.s.c_offset + c_origin - y_origin; // ≥ 0: the chroma planes lie behind the Y plane
+    t.s.cr_offset = in.s.cr_offset + c_origin - y_origin;
+    return in.s.base + y_origin;
+}
+
 template <int FORMAT, bool NEAREST, bool LEFT, bool UNALIGNED>
 __device__ __forceinline__ void yuvs_mosaic_block(const YuvsMosaicArgs &a)
 {

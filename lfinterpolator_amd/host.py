@@ -224,17 +224,30 @@ def mosaic_map(tiles_x: int, tiles_y: int, cols: int, rows: int, order="rows", b
     return _abi_mosaic_map(Mosaic.make(tiles_x, tiles_y, order, bottom_up, first_tile, n), cols, rows, g0)
 
 
-def upload_mosaic_yuv(ctx, frame: np.ndarray, tiles_x: int, tiles_y: int, fmt="i420", order="grid", bottom_up: bool = False, matrix="709",
-                      range="limited", chroma="bilinear") -> None:
-    """Context.upload_mosaic_yuv of one tight host frame ([frame bytes] uint8: I420 or NV12 planes of tiles_x·W × tiles_y·H) that holds the
-    whole grid of ctx: order "grid" for a cols × rows mosaic of cameras, "rows" for a quilt.  Keep `frame` alive until upload_wait / sync."""
+def _tight_mosaic_surfaces(ctx, frame: np.ndarray, tiles_x: int, tiles_y: int, fmt) -> YuvSurfaces:
+    """one tight host frame of tiles_x·W × tiles_y·H as surfaces"""
     assert frame.dtype == np.uint8 and frame.ndim == 1 and frame.strides[0] == 1
     mw, mh = tiles_x * ctx.width, tiles_y * ctx.height
     assert frame.size >= mw * mh * 3 // 2
     nv12 = fmt in ("nv12", 1)
-    s = YuvSurfaces.make(fmt, "host", frame.ctypes.data, frame.size, mw, mw * mh, mw if nv12 else mw // 2, 0 if nv12 else mw * mh + (mw // 2) * (mh // 2),
-                         keep=frame)
+    return YuvSurfaces.make(fmt, "host", frame.ctypes.data, frame.size, mw, mw * mh, mw if nv12 else mw // 2,
+                            0 if nv12 else mw * mh + (mw // 2) * (mh // 2), keep=frame)
+
+
+def upload_mosaic_yuv(ctx, frame: np.ndarray, tiles_x: int, tiles_y: int, fmt="i420", order="grid", bottom_up: bool = False, matrix="709",
+                      range="limited", chroma="bilinear") -> None:
+    """Context.upload_mosaic_yuv of one tight host frame ([frame bytes] uint8: I420 or NV12 planes of tiles_x·W × tiles_y·H) that holds the
+    whole grid of ctx: order "grid" for a cols × rows mosaic of cameras, "rows" for a quilt.  Keep `frame` alive until upload_wait / sync."""
+    s = _tight_mosaic_surfaces(ctx, frame, tiles_x, tiles_y, fmt)
     ctx.upload_mosaic_yuv(Mosaic.make(tiles_x, tiles_y, order, bottom_up), s, 0, matrix, range, chroma)
+
+
+def upload_mosaic_yuv_derived(ctx, frame: np.ndarray, tiles_x: int, tiles_y: int, fmt="i420", order="grid", bottom_up: bool = False, matrix="709",
+                              range="limited", chroma="bilinear") -> None:
+    """upload_mosaic_yuv for a context whose inputs were released (Context.upload_mosaic_yuv_derived): the same tight host frame goes
+    straight into the derived planar copy.  Keep `frame` alive until upload_wait / sync."""
+    s = _tight_mosaic_surfaces(ctx, frame, tiles_x, tiles_y, fmt)
+    ctx.upload_mosaic_yuv_derived(Mosaic.make(tiles_x, tiles_y, order, bottom_up), s, 0, matrix, range, chroma)
 
 
 def upload_mosaic(ctx, rgba: np.ndarray, tiles_x: int, tiles_y: int, order="grid", bottom_up: bool = False) -> None:
