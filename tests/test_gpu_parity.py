@@ -601,6 +601,18 @@ def test_focus_map_padded_planes_are_kept_between_calls(gpu, oracle_c):
     ctx.upload_image(g, lf2[g])
     check(ctx, params(0.22, 0.17, (3, 1)), lf2, "a sampled image replaced")
     check(ctx, params(0.22, 0.17, (3, 1)), lf2, "and reused again")
+    lf3 = lf2.copy()
+    g = int(hp.focus_map_ids[2])
+    lf3[g] = lf3[g][::-1].copy()             # another sampled image, written through the raw grid pointer behind the library's back:
+    ptr, nbytes = ctx.grid_device_ptr()      # by a second context that takes the pointer as its attached grid
+    other = gpu.Context(0)
+    other.set_grid(cols, rows, W, H)
+    other.attach_grid(ptr, nbytes)
+    other.upload_image(g, lf3[g])            # synchronous
+    other.close()
+    ctx.grid_modified()
+    check(ctx, params(0.22, 0.17, (3, 1)), lf3, "a write through the raw grid pointer, announced by lfi_grid_modified")
+    check(ctx, params(0.22, 0.17, (3, 1)), lf3, "and reused once more")
     ctx.close()
 
 
