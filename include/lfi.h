@@ -226,8 +226,11 @@ int lfi_fill_synthetic_scene(lfi_ctx *ctx, uint32_t seed);
  *      (src/interpolator.cu:139-154, 194-246) ------------------------------------------------------------------
  * The arrays are copied before the call returns (the caller's memory is free again).  A call that keeps the number of views (a focus
  * sweep, another trajectory of the same length) replaces the device arrays IN STREAM ORDER through page-locked staging: renders already
- * enqueued keep the parameters they were enqueued with, later ones see the new ones, and the context's stream is not drained.  A call
- * that changes the number of views synchronises and reallocates. */
+ * enqueued keep the parameters they were enqueued with, later ones see the new ones, and the context's stream is not drained.  The staging
+ * has two buffers: a call may wait on the host until the copy of the call before the previous one has run, i.e. until the renders enqueued
+ * before THAT call have finished — two replacements are always in flight without a wait, a third in a row is not (lfi_set_view_offsets,
+ * lfi_set_view_float_offsets and lfi_view_focus_maps stage their rows the same way).  A call that changes the number of views synchronises
+ * and reallocates. */
 int lfi_set_params(lfi_ctx *ctx, const lfi_params *params);
 /* Per-view focus: focal stacks (one camera position at V focus values) and focus pulls (the focus changing along the trajectory) in
  * one launch.  No counterpart in the reference, whose kernels apply one focus to all views (focusedOffsets, src/interpolator.cu:226-246).
@@ -958,6 +961,11 @@ typedef struct lfi_derived_layout {
 } lfi_derived_layout;
 int lfi_debug_derived_layout(lfi_ctx *ctx, lfi_derived_layout *out, int32_t *phases_n);
 int lfi_debug_download_derived(lfi_ctx *ctx, int g0, int n, uint8_t *out);
+/* Test hook of the ordering tests (tests/stream_order.py): out3 receives the hipStream_t of the context's own compute stream, of its copy
+ * stream and of its side stream, in that order.  The copy and the side stream are created if they do not exist yet, exactly as their first
+ * user would create them (the side stream with the highest priority); no other effect, no device work.  The handles belong to the context
+ * and die with it.  A test may enqueue work of its own on them (a delay, an event) to hold the library to its stream order. */
+int lfi_debug_streams(lfi_ctx *ctx, void **out3);
 
 #ifdef __cplusplus
 }

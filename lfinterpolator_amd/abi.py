@@ -70,7 +70,7 @@ ABI_SYMBOLS = [
     "lfi_download_quilt_yuv", "lfi_download_rgbd_yuv", "lfi_set_yuv_siting", "lfi_yuv_siting",
     "lfi_upload_images_yuv_derived", "lfi_debug_derived_layout", "lfi_debug_download_derived",
     "lfi_mosaic_map", "lfi_upload_mosaic_yuv", "lfi_upload_mosaic", "lfi_debug_mosaic_chunk",
-    "lfi_upload_mosaic_yuv_derived", "lfi_debug_set_mosaic_chunk_cap",
+    "lfi_upload_mosaic_yuv_derived", "lfi_debug_set_mosaic_chunk_cap", "lfi_debug_streams",
 ]
 
 
@@ -288,6 +288,7 @@ def load_hip_library() -> C.CDLL:
         "lfi_upload_mosaic": (i, [vp, C.POINTER(Mosaic), i, vp, sz]),
         "lfi_debug_mosaic_chunk": (i, [C.POINTER(Mosaic), i, i, sz, i, vp]),
         "lfi_debug_download_derived": (i, [vp, i, i, vp]),
+        "lfi_debug_streams": (i, [vp, C.POINTER(vp)]),
         "lfi_alloc_pinned": (i, [sz, C.POINTER(vp)]),
         "lfi_free_pinned": (i, [vp]),
         "lfi_grid_modified": (i, [vp]),
@@ -903,6 +904,13 @@ class Context:
         out = C.c_uint32(0xffffffff)
         self._check(self._lib.lfi_debug_pk_minmax3_f16(self._h, C.byref(out)))
         return int(out.value)
+
+    def debug_streams(self) -> tuple[int, int, int]:
+        """tests: the hipStream_t handles of the context's own compute stream, its copy stream and its side stream (lfi_debug_streams);
+        the latter two are created if they do not exist yet"""
+        out = (C.c_void_p * 3)()
+        self._check(self._lib.lfi_debug_streams(self._h, out))
+        return tuple(int(v or 0) for v in out)
 
     def poison(self, what: int, byte: int) -> None:
         """Fill the buffers selected by the LFI_POISON_* bits in `what` with `byte` (stream-ordered; caches are rebuilt by their next user)."""

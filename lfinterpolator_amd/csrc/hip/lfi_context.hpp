@@ -474,6 +474,20 @@ int ensure_copy_stream(lfi_ctx *c)
     return LFI_OK;
 }
 
+// the side stream of the factored focus-map estimate and its fork / join events; high priority: the small passes should not queue behind the big ones
+int ensure_aux_stream(lfi_ctx *c)
+{
+    if(c->aux_stream)
+        return LFI_OK;
+    int prio_low = 0, prio_high = 0; // numerically lower = higher priority
+    LFI_HIP(c, hipDeviceGetStreamPriorityRange(&prio_low, &prio_high));
+    LFI_HIP(c, c->aux_stream.ensure_with_priority(prio_high));
+    LFI_HIP(c, c->ev_fork.ensure());
+    LFI_HIP(c, c->ev_pad.ensure());
+    LFI_HIP(c, c->ev_join.ensure());
+    return LFI_OK;
+}
+
 size_t plane_bytes(const lfi_ctx *c) // a whole-image plane (focus maps; inputs and outputs without a row window)
 {
     return (size_t)c->width * c->height * 4;

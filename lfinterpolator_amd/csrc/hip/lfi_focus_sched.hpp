@@ -174,15 +174,8 @@ int launch_focus_factored_keys(lfi_ctx *ctx, const KernelArgs &a, FocusJob &job,
     // and the range pass (bandwidth / VALU bound) instead of in front of them.
     //   main:  plan_shifts ─┬─ pad ─┬─ range ───────────────────────────────────────────┬─ line_keys → pick (→ filter, by the caller)
     //   aux:                └─ flags → lists → prefix ─┴─ {lines_rows, lines_cols, exact} ─┘
-    if(!ctx->aux_stream)
-    {
-        int prio_low = 0, prio_high = 0; // numerically lower = higher priority: the small passes should not queue behind the big ones
-        LFI_HIP(ctx, hipDeviceGetStreamPriorityRange(&prio_low, &prio_high));
-        LFI_HIP(ctx, ctx->aux_stream.ensure_with_priority(prio_high));
-        LFI_HIP(ctx, ctx->ev_fork.ensure());
-        LFI_HIP(ctx, ctx->ev_pad.ensure());
-        LFI_HIP(ctx, ctx->ev_join.ensure());
-    }
+    if(int rc = ensure_aux_stream(ctx))
+        return rc;
     hipStream_t st = ctx->stream;
     hipStream_t aux = ctx->aux_stream;
     // host launch order = the critical path first: the main stream's kernels are enqueued before the side stream's

@@ -891,6 +891,22 @@ bool derived_copy_current(const lfi_ctx *ctx)
 
 } // namespace
 
+int lfi_debug_streams(lfi_ctx *ctx, void **out3)
+{
+    if(!ctx || !out3)
+        return LFI_EINVAL;
+    if(int rc = bind(ctx))
+        return rc;
+    if(int rc = ensure_copy_stream(ctx))
+        return rc;
+    if(int rc = ensure_aux_stream(ctx))
+        return rc;
+    out3[0] = static_cast<hipStream_t>(ctx->own_stream);
+    out3[1] = static_cast<hipStream_t>(ctx->copy_stream);
+    out3[2] = static_cast<hipStream_t>(ctx->aux_stream);
+    return LFI_OK;
+}
+
 int lfi_debug_derived_layout(lfi_ctx *ctx, lfi_derived_layout *out, int32_t *phases_n)
 {
     if(!ctx || !out)

@@ -19,8 +19,7 @@ A reader is held to the CPU oracle on the shadow grid: STD renders, focus maps, 
 fuzz_cases.fuzz_blend holds it (within one LSB of M16 and inside the interval of the exact sum, tests/ten_interval.py).
 
 Limits: at these shapes a missing stream wait may go unobserved — the copies take microseconds.  The tests hold the version bookkeeping
-and the routing; they do not hold the races.  test_gpu_plumbing.py::test_stream_switch_orders_derived_state and the "no host wait in between"
-tests of the upload files remain the ordering tests.
+and the routing; they do not hold the races.  tests/stream_order.py does: every asynchronous writer here is issued there behind a stalled stream.
 """
 import hashlib
 from dataclasses import dataclass
