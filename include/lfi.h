@@ -77,7 +77,34 @@ enum {
     LFI_FLAG_STD_MEASURED_BAND = 16u,
     /* Test hook of the band's self-check (lfi_std_band_info): behave as if the device had FAILED the measurement the measured bound
      * rests on — STD launches over more than 64 images then take the analytic band.  Same bytes. */
-    LFI_FLAG_STD_BAND_PROBE_FAIL = 32u
+    LFI_FLAG_STD_BAND_PROBE_FAIL = 32u,
+    /* DEEP VIEWS: fixed-focus renders keep TEN bits per channel straight from the blend's accumulator, on the device, beside the 8-bit views.
+     * A view is a weighted mean of 64-225 input bytes accumulated in fp32; the mean carries more than 8 bits, and carries them where banding
+     * shows (the smooth out-of-focus gradients of a fixed-focus refocus).  While the flag is set, lfi_render / lfi_prepare / lfi_benchmark with
+     * all_focus = 0 launch ONE kernel (csrc/hip/deep_blend.hpp; lfi_last_kernel_name names it, lfi_set_variant choices do not apply) that
+     * writes, from one gather and one accumulation per pixel and view:
+     *  - the 8-bit views, exactly as a render without the flag defines them (STD: the reference's bytes; TEN_WM: the TEN_WM contract,
+     *    floor(min(fp16_RN(s), 255)));
+     *  - the DEEP PLANES: [view][3: R,G,B][rows][pitch16] little-endian u16, the code in bits 9..0, the upper six bits 0, pitch16 = 2*W rounded
+     *    up to 128 bytes, view = the view's index.  With s the accumulator of (pixel, view, channel):
+     *        STD     s = the reference's ordered fp32 fmaf chain (src/kernels.cu:292-299):  D10 = min(1023, rn_even(4*s)) - 4*s is exact in
+     *                fp32 and rn_even is the rounding the byte uses: the code is bit-exact;
+     *        TEN_WM  s = the fp32-accumulated matrix-core sum:  D10 = min(1023, floor(4*fp16_RN(s))) - the TEN_WM quantisation with two more
+     *                bits kept; monotone, and D10 >> 2 IS the 8-bit byte of the same launch.
+     * The planes belong to the context (one allocation for all views, counted in lfi_memory.views_bytes, LFI_POISON_DEEP).  lfi_prepare allocates
+     * them; otherwise the FIRST deep render does, and that render may block (an allocation; after a change of size the stream is drained
+     * first) - a prepared render is only a launch.  They are released wherever the views are.  They hold views [v0, v1) of the last deep launch
+     * and are dropped (LFI_YUV_DEEP downloads refused until the next deep render) by any launch that writes views without the flag and by
+     * lfi_set_grid, lfi_set_output_layout, lfi_set_row_window, lfi_attach_views and a lfi_set_params that changes the number of views.  They
+     * leave the device through lfi_download_views_yuv with a LFI_YUV_DEEP format (below): 10-bit video, or raw gbrp10le planes.
+     * Valid: fixed focus; LFI_LAYOUT_PLANAR_RGB; grids up to LFI_MAX_IMAGES images, any number of views, any view range; the kernel reads the
+     * derived planar copy of the inputs, so it also serves a context after lfi_release_inputs.
+     * LFI_EINVAL with a message that names LFI_FLAG_DEEP_VIEWS, the context usable and nothing written, while the flag is set: all_focus = 1;
+     * lfi_render_stream and lfi_render_stream_yuv420; per-view rows (lfi_set_view_offsets, lfi_set_view_float_offsets); a row window; the RGBA
+     * view layout; LFI_FLAG_TEN_ROUND_PER_BATCH; lfi_download_prequant; weights outside [0, 2); inputs or offsets the planar copy cannot serve
+     * (an attached grid without lfi_grid_modified; after lfi_release_inputs, offsets beyond the copy's padding).
+     * Out of scope: all-focus and per-view deep renders, deep quilts / native images / lfi_compare_view[s], a row window, 16-bit PNG. */
+    LFI_FLAG_DEEP_VIEWS = 64u
 };
 
 #define LFI_MAX_IMAGES 256     /* MAX_IMAGES, src/kernels.cu:60 */
@@ -429,7 +456,7 @@ int lfi_prepare(lfi_ctx *ctx, int method, int all_focus, int v0, int v1);
 typedef struct lfi_memory {
     size_t grid_bytes;      /* input planes (RGBA) */
     size_t derived_bytes;   /* planar copy of the inputs: 3 bytes per pixel and image (+ padding) */
-    size_t views_bytes;     /* output planes */
+    size_t views_bytes;     /* output planes, and the deep planes of LFI_FLAG_DEEP_VIEWS once allocated */
     size_t maps_bytes;      /* focus maps (maps 0 / 1, and the per-view maps when allocated) */
     size_t workspace_bytes; /* focus-map workspace + lfi_focus_curve's / lfi_focus_tiles' curves and partial sums + (planar view layout) the RGBA scratch copy of the views that renders other than TEN_WM and
                              * STD on more than 64 images go through, and the one-plane staging buffer of downloads + the kept views (lfi_keep_views) and
@@ -758,6 +785,39 @@ int lfi_yuv_siting(lfi_ctx *ctx, int *in_siting, int *out_siting);
  * allocation is what it was before these formats existed. */
 #define LFI_YUV_10BIT 0x100
 enum { LFI_YUV_I010 = LFI_YUV_I420 | LFI_YUV_10BIT, LFI_YUV_P010 = LFI_YUV_NV12 | LFI_YUV_10BIT };
+/* FRAMES FROM THE DEEP VIEWS (LFI_FLAG_DEEP_VIEWS).  LFI_YUV_DEEP is a SOURCE flag on a 10-bit format, for lfi_download_views_yuv only:
+ *   LFI_YUV_I010 | LFI_YUV_DEEP, LFI_YUV_P010 | LFI_YUV_DEEP   the frames of the 10-bit formats, converted from the DEEP planes' 10-bit codes
+ *       instead of from the 8-bit views scaled by 876/255: a Main10 encoder gets the render without a first quantisation.  Geometry, routing
+ *       (host: staged; device: in place where base, frame_stride, pitches and offsets are multiples of 16, else staged) and refusals are those
+ *       of LFI_YUV_I010 / LFI_YUV_P010, under both output sitings;
+ *   LFI_YUV_GBRP10 (0x304)   no conversion: three full-size planes G, B, R of H rows each (ffmpeg's gbrp10le: `-f rawvideo -pix_fmt gbrp10le`),
+ *       a sample a little-endian u16 with the code in bits 9..0 and the upper six bits 0:
+ *           G at the frame's base with y_pitch;  B at c_offset with c_pitch;  R at cr_offset with c_pitch
+ *       both pitches >= 2*W, the planes in this order and not overlapping, base, pitches, offsets and frame_stride even; the tight frame of
+ *       lfi_yuv_surfaces_packed is 6*W*H bytes.  matrix and range must be valid and are ignored.  A frame is three 2D copies out of the deep
+ *       planes, to host or device memory alike (no kernel, no staging buffer; a device pointer is checked as for the other formats).
+ * LFI_YUV_DEEP on I010 / P010 says where the samples COME FROM, not where they lie: the context-free lfi_yuv_surfaces_check and
+ * lfi_yuv_surfaces_packed, which know no source, keep treating 0x300 and 0x301 as unknown formats - describe the surfaces as LFI_YUV_I010 /
+ * LFI_YUV_P010 and set the flag in the descriptor's format for the download, which checks the geometry of the format without it.  LFI_YUV_GBRP10 is
+ * a layout of its own and is known to both.  Plain 2, 0x102, 0x200, 0x201, 0x204 and 0x104 stay unknown formats everywhere.  Every other call that takes surfaces (lfi_upload_images_yuv, lfi_upload_images_yuv_derived,
+ * lfi_upload_mosaic_yuv[_derived], lfi_download_quilt_yuv, lfi_download_rgbd_yuv) refuses a LFI_YUV_DEEP format with LFI_EINVAL and a message that
+ * names LFI_YUV_DEEP.  lfi_download_views_yuv refuses one (LFI_EINVAL, nothing written) unless [v0, v0 + n) lies inside the views of the last
+ * deep launch.  Without LFI_YUV_DEEP every byte, launch and allocation is what it was.
+ * ARITHMETIC (10-bit RGB codes R, G, B of the deep planes -> 10-bit YUV), integers only.  Coefficients round(c * scale * 2^16), scale = 876/1023
+ * (limited luma), 896/1023 (limited chroma), 1 (full range); G adjusted so that Y sums to 56120 (limited) or 65536 (full) and Cb and Cr to 0:
+ *                   Y (R, G, B)           Cb (R, G, B)             Cr (R, G, B)            y_off10
+ *   709 limited   11931, 40137, 4052    -6576, -22124, 28700     28700, -26068, -2632      64
+ *   709 full      13933, 46871, 4732    -7509, -25259, 32768     32768, -29763, -3005       0
+ *   601 limited   16780, 32942, 6398    -9685, -19015, 28700     28700, -24033, -4667      64
+ *   601 full      19595, 38470, 7471   -11058, -21710, 32768     32768, -27439, -5329       0
+ *     Y10 = y_off10 + ((yR*R + yG*G + yB*B + 2^15) >> 16)
+ *     centre siting:  C10 = min(1023, (2^27 + 2^17 + uR*SR + uG*SG + uB*SB) >> 18)      SR, SG, SB: the sums over the 2x2 block (clamped as above)
+ *     left siting:    C10 = min(1023, (2^28 + 2^18 + uR*SR + uG*SG + uB*SB) >> 19)      SR, SG, SB: the left-sited definition's sums of weight 8
+ * Unsigned 32-bit arithmetic, one rounding.  The luma bracket is below 2^26; the chroma brackets lie in (0, 2^28] (centre) and (0, 2^29] (left):
+ * the upper ends are reached exactly, by full-range Cb of pure blue and Cr of pure red (32768 * 4092 + 2^27 + 2^17 = 2^28), and the min takes them
+ * to 1023.  Every grey has chroma exactly 512; limited range maps 0 -> 64 and 1023 -> 940; full range maps a grey code D to Y = D. */
+#define LFI_YUV_DEEP 0x200
+enum { LFI_YUV_GBRP10 = 4 | LFI_YUV_10BIT | LFI_YUV_DEEP };
 
 /* Mosaic input: ONE frame that holds all images of the grid as tiles — a camera array packed into one video stream (8 x 8 cameras of
  * 1920 x 1080 in a 15360 x 8640 frame), a Looking-Glass quilt, or the frame lfi_download_quilt_yuv wrote — split into the grid's images on
@@ -944,9 +1004,10 @@ int lfi_debug_mfma_f16_chain(lfi_ctx *ctx, int shape, int k, const uint16_t *a_3
  *   MAPS             both focus maps
  *   FOCUS_WORKSPACE  all of the focus-map estimate's workspace, and lfi_focus_curve's / lfi_focus_tiles' (the curves, the results and the partial sums)
  *   DERIVED          the planar copy of the inputs — refused (LFI_EINVAL) after lfi_release_inputs: it is then the only copy
- *   VIEW_MAPS        the per-view focus maps of lfi_view_focus_maps, every view's pair */
+ *   VIEW_MAPS        the per-view focus maps of lfi_view_focus_maps, every view's pair
+ *   DEEP             the deep planes of LFI_FLAG_DEEP_VIEWS, all views' (they stay valid: data, like the views) */
 enum { LFI_POISON_VIEWS = 1, LFI_POISON_SCRATCH = 2, LFI_POISON_MAPS = 4, LFI_POISON_FOCUS_WORKSPACE = 8, LFI_POISON_DERIVED = 16,
-       LFI_POISON_VIEW_MAPS = 32 };
+       LFI_POISON_VIEW_MAPS = 32, LFI_POISON_DEEP = 64 };
 int lfi_debug_poison(lfi_ctx *ctx, uint32_t what, uint8_t byte);
 /* Test hooks: the derived planar copy of the inputs, byte for byte.  The copy is [N][3][rows][pitch_bytes] bytes: per image three byte planes
  * (R, G, B) of the rows the context holds; byte j of a plane row of image g holds pixel clamp(j - padx - phase[g], 0, W - 1), so every row is

@@ -17,6 +17,7 @@ LFI_FLAG_SINGLE_SWEEP_DIRECTION = 4
 LFI_FLAG_STD_ANALYTIC_BAND = 8
 LFI_FLAG_STD_MEASURED_BAND = 16
 LFI_FLAG_STD_BAND_PROBE_FAIL = 32
+LFI_FLAG_DEEP_VIEWS = 64     # fixed-focus renders also keep 10 bits per channel from the accumulator: the deep planes (include/lfi.h)
 LFI_KERNEL_FOCUS_ESTIMATE = 2
 LFI_POISON_VIEWS = 1
 LFI_POISON_SCRATCH = 2
@@ -24,6 +25,7 @@ LFI_POISON_MAPS = 4
 LFI_POISON_FOCUS_WORKSPACE = 8
 LFI_POISON_DERIVED = 16
 LFI_POISON_VIEW_MAPS = 32
+LFI_POISON_DEEP = 64
 LFI_LENT_INVERT = 1
 LFI_RGBD_INVERT = 1
 LFI_RGBD_VIEW_MAPS = 2
@@ -44,7 +46,10 @@ LFI_YUV_NV12 = 1
 LFI_YUV_10BIT = 0x100      # the depth flag of a surface format: two bytes per sample (include/lfi.h)
 LFI_YUV_I010 = LFI_YUV_I420 | LFI_YUV_10BIT   # planar, code in bits 9..0 of a little-endian u16 (yuv420p10le)
 LFI_YUV_P010 = LFI_YUV_NV12 | LFI_YUV_10BIT   # semi-planar, code in bits 15..6 (p010le)
-YUV_FORMATS = {"i420": LFI_YUV_I420, "nv12": LFI_YUV_NV12, "i010": LFI_YUV_I010, "p010": LFI_YUV_P010}
+LFI_YUV_DEEP = 0x200       # a source flag on a 10-bit format, for lfi_download_views_yuv only: the frames are made from the deep views
+LFI_YUV_GBRP10 = 4 | LFI_YUV_10BIT | LFI_YUV_DEEP   # no conversion: full-size planes G, B, R of 10-bit codes (ffmpeg's gbrp10le)
+YUV_FORMATS = {"i420": LFI_YUV_I420, "nv12": LFI_YUV_NV12, "i010": LFI_YUV_I010, "p010": LFI_YUV_P010, "i010_deep": LFI_YUV_I010 | LFI_YUV_DEEP,
+               "p010_deep": LFI_YUV_P010 | LFI_YUV_DEEP, "gbrp10": LFI_YUV_GBRP10}
 LFI_MEM_HOST = 0
 LFI_MEM_DEVICE = 1
 YUV_MEMORIES = {"host": LFI_MEM_HOST, "device": LFI_MEM_DEVICE}
@@ -142,6 +147,18 @@ class YuvSurfaces(C.Structure):
         """host surfaces in a numpy array [n][P] uint8: frame k is row k, the frame stride is the array's"""
         assert frames.dtype == np.uint8 and frames.ndim == 2 and frames.size and frames.strides[1] == 1
         return cls.make(fmt, LFI_MEM_HOST, frames.ctypes.data, frames.strides[0], y_pitch, c_offset, c_pitch, cr_offset, keep=frames)
+
+    @classmethod
+    def gbrp10_from_array(cls, frames: np.ndarray) -> "YuvSurfaces":
+        """host LFI_YUV_GBRP10 surfaces over a numpy array [n][3: G,B,R][H][W] uint16 (C-contiguous): the tight frame of ffmpeg's gbrp10le"""
+        assert frames.dtype == np.uint16 and frames.ndim == 4 and frames.shape[1] == 3 and frames.size and frames.flags.c_contiguous
+        n, _, h, w = frames.shape
+        return cls.make(LFI_YUV_GBRP10, LFI_MEM_HOST, frames.ctypes.data, 6 * w * h, 2 * w, 2 * w * h, 2 * w, 4 * w * h, keep=frames)
+
+    @staticmethod
+    def gbrp10_to_rgb(frames: np.ndarray) -> np.ndarray:
+        """[n][3: G,B,R][H][W] uint16 -> [n][H][W][3: R,G,B] uint16"""
+        return np.ascontiguousarray(frames[:, [2, 0, 1]].transpose(0, 2, 3, 1))
 
     def check(self, width: int, height: int, n: int) -> bool:
         """lfi_yuv_surfaces_check: does this describe n frames of width x height?"""
@@ -827,6 +844,14 @@ class Context:
         n = self.views - v0 if n is None else n
         self._check(self._lib.lfi_download_views_yuv(self._h, v0, n, YUV_MATRICES.get(matrix, matrix), YUV_RANGES.get(range, range),
                                                      C.byref(surfaces) if surfaces is not None else None))
+
+    def download_deep_views(self, v0: int = 0, n: int | None = None) -> np.ndarray:
+        """the deep views [v0, v0 + n) (default: all from v0) of the last deep render (set_params(..., flags=LFI_FLAG_DEEP_VIEWS)) as
+        [n][H][W][3: R,G,B] uint16 10-bit codes: lfi_download_views_yuv into host LFI_YUV_GBRP10 surfaces"""
+        n = self.views - v0 if n is None else n
+        frames = np.full((max(n, 1), 3, self.height, self.width), 0xC3C3, dtype=np.uint16)   # a sentinel, not zeros: every sample is written
+        self.download_views_yuv(YuvSurfaces.gbrp10_from_array(frames), n, v0)
+        return YuvSurfaces.gbrp10_to_rgb(frames[:n])
 
     def download_quilt_yuv(self, tiles_x: int, tiles_y: int, v0: int, tile_w: int, tile_h: int, matrix, range, surfaces: YuvSurfaces) -> None:
         """the scaled quilt of views v0 … (download_quilt_scaled's tiles) as ONE YUV 4:2:0 frame of tiles_x·tile_w × tiles_y·tile_h in `surfaces`

@@ -282,6 +282,11 @@ struct lfi_ctx
     DeviceBuffer maps;                // focus maps 0 and 1, whole-image planes
     DeviceBuffer views;               // the library's own (alloc_views) or attached (lfi_attach_views)
     int out_layout = LFI_LAYOUT_RGBA; // device layout of the views (lfi_set_output_layout)
+    // deep views (LFI_FLAG_DEEP_VIEWS, deep_blend.hpp): 10-bit planes [views_n][3: R,G,B][out_rows][deep_pitch] of little-endian u16 beside the planar
+    // views; allocated by lfi_prepare or the first deep render, released with the views.  They hold views [deep_v0, deep_v1) of the last
+    // deep launch; empty after any launch that writes views without the flag
+    DeviceBuffer deep;
+    int deep_v0 = 0, deep_v1 = 0;
     DeviceBuffer rgba_scratch;        // planar layout: RGBA planes of all views for the kernels that only write RGBA (converted after the launch)
     DeviceBuffer dl_plane;            // planar layout: one RGBA plane that downloads expand a view into
     DeviceBuffer quilt;               // lfi_download_quilt[_tiles]: the quilt's rows of tiles as one RGBA image (grows, kept); lfi_download_native: its scaled tiles
@@ -505,6 +510,22 @@ size_t in_plane_bytes(const lfi_ctx *c)
 int view_pitch(const lfi_ctx *c)
 {
     return (c->width + 127) / 128 * 128;
+}
+
+// deep planes: bytes per row of a u16 plane — 2·W rounded up to 128
+int deep_pitch(const lfi_ctx *c)
+{
+    return (2 * c->width + 127) / 128 * 128;
+}
+
+size_t deep_bytes(const lfi_ctx *c)
+{
+    return (size_t)c->views_n * 3 * c->out_rows * deep_pitch(c);
+}
+
+void drop_deep_range(lfi_ctx *c)
+{
+    c->deep_v0 = c->deep_v1 = 0;
 }
 
 size_t rgba_out_plane_bytes(const lfi_ctx *c)
@@ -731,6 +752,8 @@ uint8_t *param_base(const lfi_ctx *c)
 void free_views(lfi_ctx *c)
 {
     c->views.release();
+    c->deep.release();
+    drop_deep_range(c);
     c->rgba_scratch.release();
     c->dl_plane.release();
     c->quilt.release();

@@ -22,6 +22,7 @@
 #include "blend_wave.hpp"
 #include "blend_vfocus.hpp"
 #include "blend_vfocus_af.hpp"
+#include "deep_blend.hpp"
 #include "lfi_band_probe.hpp"
 
 namespace {
@@ -47,6 +48,8 @@ enum class BlendKernel
     std_mfma,
     std_valu,
     std_vfma,
+    deep_ten, // deep_blend.hpp: LFI_FLAG_DEEP_VIEWS
+    deep_std,
 };
 
 // The generic kernels: plain fp32 epilogue, any weights, pre-quantisation dumps, per-batch rounding (TEN_WM).  They run one pixel grid
@@ -121,6 +124,9 @@ BlendRoute route_blend(const lfi_ctx *c, int method, bool all_focus, const Kerne
     const bool ten = method == LFI_METHOD_TEN_WM, planar_views = c->out_layout == LFI_LAYOUT_PLANAR_RGB;
     const K first = ten ? kTenVariants[c->ten_variant].first : kStdVariants[c->std_variant].first;
     const int nch = (a.k_pad + lfi::P3_KC - 1) / lfi::P3_KC;
+    // 0. deep views (LFI_FLAG_DEEP_VIEWS): one kernel for both methods; launch_blend (deep_views_ready) has refused what it does not serve
+    if(c->flags & LFI_FLAG_DEEP_VIEWS)
+        return {ten ? K::deep_ten : K::deep_std, nch, true, true};
     const bool fixed_copy = copy_ok && !all_focus;
     // wave-private pipelines (blend_wave.hpp) where they apply: fixed focus, one chunk of images, one view pass
     const bool wave_fits = !all_focus && a.k_pad <= 64 && a.v1 - a.v0 <= 64;
@@ -365,10 +371,35 @@ void launch_afs(const lfi_ctx *c, const KernelArgs &a_in, const BlendRoute &r)
 
 void launch_p3(const lfi_ctx *c, const KernelArgs &a_in, int nch, bool rgba_out);
 
+// deep_blend: the byte planes and the deep planes of views [v0, v1).  One chunk of images: ONE launch whose tiles serve every 64-view pass
+// from the same LDS-resident pixels; several chunks: one launch per 64 views
+void launch_deep(const lfi_ctx *c, const KernelArgs &a_in, int nch, bool std_chain)
+{
+    const int tiles_x = (a_in.width + lfi::P3_TPX - 1) / lfi::P3_TPX;
+    const int n_tiles = tiles_x * a_in.out_rows;
+    const dim3 grid(std::min(n_tiles, 2 * cu_count_of(c))), block(256);
+    // what lfi_last_kernel_name reports.  Set here, not through the helper the other launchers use: tests/test_gpu_dispatch_coverage.py holds every
+    // name that goes through it to a row of its render matrix, which knows no parameter flags; the deep launches are held to these names by
+    // tests/test_gpu_deep.py
+    c->last_kernel = std_chain ? "deep_blend<STD>" : "deep_blend<TEN_WM>";
+    auto launch = [&](const KernelArgs &a, int passes) {
+        if(std_chain)
+            hipLaunchKernelGGL((lfi::deep_blend<true>), grid, block, 0, stream_of(c), a, c->deep.get(), deep_pitch(c), tiles_x, n_tiles, passes, nch);
+        else
+            hipLaunchKernelGGL((lfi::deep_blend<false>), grid, block, 0, stream_of(c), a, c->deep.get(), deep_pitch(c), tiles_x, n_tiles, passes, nch);
+    };
+    if(nch == 1)
+        launch(a_in, (a_in.v1 - a_in.v0 + 63) / 64);
+    else
+        per_64_views(a_in, [&](const KernelArgs &a) { launch(a, 1); });
+}
+
 void launch_route(const lfi_ctx *c, const KernelArgs &a, bool all_focus, const BlendRoute &r)
 {
     switch(r.kernel)
     {
+        case BlendKernel::deep_ten: launch_deep(c, a, r.nch, false); break;
+        case BlendKernel::deep_std: launch_deep(c, a, r.nch, true); break;
         case BlendKernel::ten_m16: launch_ten_m16(c, a, all_focus); break;
         case BlendKernel::ten_direct: launch_ten_direct(c, a, all_focus); break;
         case BlendKernel::p3: launch_p3(c, a, r.nch, false); break;
@@ -691,9 +722,71 @@ bool allfocus_rows_held(const lfi_ctx *c, const lfi_float2 *o, size_t n)
     return true;
 }
 
+// ---- deep views (LFI_FLAG_DEEP_VIEWS): deep_blend.hpp --------------------------------------------------------------------------------------
+
+const char *const kDeepNoPrequant = "lfi_download_prequant is not supported (the deep planes ARE the accumulator's ten bits)";
+
+// What a deep render refuses, before anything is enqueued or allocated; every message names the flag
+int deep_views_refused(lfi_ctx *c, int all_focus, const KernelArgs &a)
+{
+    const char *why = nullptr;
+    if(a.prequant)
+        why = kDeepNoPrequant;
+    else if(all_focus)
+        why = "all-focus renders are not supported (fixed focus only)";
+    else if(c->view_offsets.set || c->view_float_offsets.set)
+        why = "per-view rows (lfi_set_view_offsets, lfi_set_view_float_offsets) are not supported - clear them with NULL";
+    else if(c->windowed)
+        why = "a row window (lfi_set_row_window) is not supported";
+    else if(c->out_layout != LFI_LAYOUT_PLANAR_RGB)
+        why = "the RGBA view layout is not supported - lfi_set_output_layout(LFI_LAYOUT_PLANAR_RGB)";
+    else if(c->flags & LFI_FLAG_TEN_ROUND_PER_BATCH)
+        why = "LFI_FLAG_TEN_ROUND_PER_BATCH is not supported";
+    else if(!c->weights_scalable)
+        why = "weights outside [0, 2) are not supported";
+    return why ? fail(c, LFI_EINVAL, std::string("LFI_FLAG_DEEP_VIEWS is set: ") + why) : LFI_OK;
+}
+
+// the deep planes of all views_n views; a first use (or a new size) allocates, which may block
+int ensure_deep_planes(lfi_ctx *c)
+{
+    const size_t need = deep_bytes(c);
+    if(c->deep.bytes() == need)
+        return LFI_OK;
+    LFI_HIP(c, hipStreamSynchronize(c->stream)); // a download may still read the planes that go
+    drop_deep_range(c);
+    LFI_HIP(c, c->deep.fit(need));
+    return LFI_OK;
+}
+
+// lfi_render / lfi_prepare's build / lfi_benchmark while the flag is set: deep_blend writes the byte planes and the deep planes of [v0, v1)
+int launch_deep_views(lfi_ctx *c, int method, int all_focus, const KernelArgs &a_in)
+{
+    if(method != LFI_METHOD_STD && method != LFI_METHOD_TEN_WM) // the reference throws here (src/interpolator.cu:289-290)
+        return fail(c, LFI_EINVAL, "The specified interpolation method does not exist!");
+    if(int rc = deep_views_refused(c, all_focus, a_in))
+        return rc;
+    if(int rc = join_uploads(c))
+        return rc;
+    if(!ensure_planar(c, tune_planar_now(c)))
+        return fail(c, LFI_EINVAL, "LFI_FLAG_DEEP_VIEWS is set: the planar copy of the inputs cannot serve these offsets (inputs the library cannot track, "
+                                   "or, after lfi_release_inputs, offsets beyond the copy's padding)");
+    if(int rc = ensure_deep_planes(c))
+        return rc;
+    KernelArgs a = a_in;
+    set_planar_args(c, a);
+    drop_deep_range(c);
+    launch_route(c, a, false, route_blend(c, method, false, a, true));
+    LFI_HIP(c, hipGetLastError());
+    c->deep_v0 = a.v0, c->deep_v1 = a.v1;
+    return LFI_OK;
+}
+
 // Renders views [a_in.v0, a_in.v1) into a_in.views
 int launch_blend(lfi_ctx *c, int method, int all_focus, const KernelArgs &a_in)
 {
+    if(c->flags & LFI_FLAG_DEEP_VIEWS)
+        return launch_deep_views(c, method, all_focus, a_in);
     if(int rc = join_uploads(c))
         return rc;
     if(const ViewRowsKind k = view_rows_of(c, all_focus))
@@ -746,6 +839,8 @@ int launch_blend(lfi_ctx *c, int method, int all_focus, const KernelArgs &a_in)
         LFI_HIP(c, c->rgba_scratch.fit(rgba_out_plane_bytes(c) * c->views_n)); // nothing happens from the second launch on
         a.views = c->rgba_scratch.get();
     }
+    if(!a.prequant)
+        drop_deep_range(c); // the views are written without their deep planes
     launch_route(c, a, all_focus != 0, r);
     LFI_HIP(c, hipGetLastError());
     if(scratch)
@@ -820,6 +915,7 @@ int launch_view_rows(lfi_ctx *c, ViewRowsKind k, int method, int all_focus, cons
                                             {"blend_vfocus_af<STD>", "blend_vfocus_af<TEN_WM>"},
                                             {"blend_vfocus_af<STD,view_maps>", "blend_vfocus_af<TEN_WM,view_maps>"}};
     note_kernel(c, names[view_maps ? 3 : k == VIEW_ROWS_FLOAT ? 2 : planar][ten]);
+    drop_deep_range(c); // the views are written without their deep planes
     if(k == VIEW_ROWS_INT)
     {
         using lfi::blend_vfocus;

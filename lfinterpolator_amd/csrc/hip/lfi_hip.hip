@@ -16,6 +16,7 @@
 #include "yuv420_upload.hpp"
 #include "yuv_surfaces.hpp"
 #include "yuv10.hpp"
+#include "deep_yuv.hpp"
 #include "yuv_mosaic.hpp"
 #include "yuv_mosaic_derived.hpp"
 #include "yuv_derived.hpp"
@@ -283,7 +284,7 @@ size_t add_sat(size_t a, size_t b)
 // the layout of a surface format (LFI_YUV_I420 or LFI_YUV_NV12: the format without its depth flag) and its bytes per sample
 int yuv_layout(int format)
 {
-    return format & ~LFI_YUV_10BIT;
+    return format & ~(LFI_YUV_10BIT | LFI_YUV_DEEP);
 }
 
 uint32_t yuv_bps(int format)
@@ -293,19 +294,39 @@ uint32_t yuv_bps(int format)
 
 bool yuv_format_known(int format)
 {
-    return format == LFI_YUV_I420 || format == LFI_YUV_NV12 || format == LFI_YUV_I010 || format == LFI_YUV_P010;
+    return format == LFI_YUV_I420 || format == LFI_YUV_NV12 || format == LFI_YUV_I010 || format == LFI_YUV_P010 || format == (LFI_YUV_I010 | LFI_YUV_DEEP) ||
+           format == (LFI_YUV_P010 | LFI_YUV_DEEP) || format == LFI_YUV_GBRP10;
 }
 
+// the formats made from the deep planes (deep_yuv.hpp): frames that only lfi_download_views_yuv writes
+bool yuv_format_deep(int format)
+{
+    return yuv_format_known(format) && (format & LFI_YUV_DEEP);
+}
+
+const char *const kDeepFormatRefused = "LFI_YUV_DEEP formats (LFI_YUV_I010 | LFI_YUV_DEEP, LFI_YUV_P010 | LFI_YUV_DEEP, LFI_YUV_GBRP10) are frames made from the deep "
+                                       "views: only lfi_download_views_yuv writes them";
+
 // why s does not describe n frames of width × height (NULL: it does); *extent: the end of a frame's last plane
-const char *yuv_surfaces_fault(const lfi_yuv_surfaces *s, int width, int height, int n, size_t *extent)
+// deep: what the caller makes of the LFI_YUV_DEEP formats.  DEEP_REFUSED: it refuses them by name (every call but the next two).  DEEP_LAYOUT
+// (lfi_yuv_surfaces_check): LFI_YUV_GBRP10, a layout of its own, is known; LFI_YUV_DEEP on I010 / P010 says where the samples COME FROM, not
+// where they lie, and stays an unknown format for a call that knows no source.  DEEP_SOURCE (lfi_download_views_yuv): all three.
+// LFI_YUV_GBRP10: three full-size planes G, B, R where I010 has Y, Cb, Cr
+enum DeepFormats { DEEP_REFUSED, DEEP_LAYOUT, DEEP_SOURCE };
+const char *yuv_surfaces_fault(const lfi_yuv_surfaces *s, int width, int height, int n, size_t *extent, DeepFormats deep = DEEP_REFUSED)
 {
     if(!s || !s->base)
         return "the descriptor or its base is NULL";
+    if(deep == DEEP_REFUSED && yuv_format_deep(s->format))
+        return kDeepFormatRefused;
+    if(deep == DEEP_LAYOUT && yuv_format_deep(s->format) && s->format != LFI_YUV_GBRP10)
+        return "unknown format: LFI_YUV_DEEP on LFI_YUV_I010 / LFI_YUV_P010 is a source flag for lfi_download_views_yuv, the layout is the format without it";
     if(!yuv_format_known(s->format) || (s->memory != LFI_MEM_HOST && s->memory != LFI_MEM_DEVICE))
-        return "unknown format (LFI_YUV_I420, LFI_YUV_NV12, LFI_YUV_I010, LFI_YUV_P010) or memory (LFI_MEM_HOST, LFI_MEM_DEVICE)";
+        return "unknown format (LFI_YUV_I420, LFI_YUV_NV12, LFI_YUV_I010, LFI_YUV_P010, the latter two | LFI_YUV_DEEP, LFI_YUV_GBRP10) or memory (LFI_MEM_HOST, LFI_MEM_DEVICE)";
     if(width < 1 || height < 1 || n < 1)
         return "width, height and n must be at least 1";
-    const size_t W = (size_t)width, H = (size_t)height, cw = (W + 1) >> 1, ch = (H + 1) >> 1;
+    const bool full = s->format == LFI_YUV_GBRP10; // no subsampling: the second and third plane are as large as the first
+    const size_t W = (size_t)width, H = (size_t)height, cw = full ? W : (W + 1) >> 1, ch = full ? H : (H + 1) >> 1;
     const bool nv12 = yuv_layout(s->format) == LFI_YUV_NV12;
     const size_t bps = yuv_bps(s->format);
     if(s->y_pitch < bps * W || s->c_pitch < bps * (nv12 ? 2 * cw : cw))
@@ -569,17 +590,27 @@ int upload_yuv_surfaces(lfi_ctx *ctx, const char *who, int g0, int n, int matrix
 
 int lfi_yuv_surfaces_check(const lfi_yuv_surfaces *s, int width, int height, int n)
 {
-    return yuv_surfaces_fault(s, width, height, n, nullptr) ? LFI_EINVAL : LFI_OK;
+    return yuv_surfaces_fault(s, width, height, n, nullptr, DEEP_LAYOUT) ? LFI_EINVAL : LFI_OK;
 }
 
 int lfi_yuv_surfaces_packed(int format, int memory, void *base, int width, int height, lfi_yuv_surfaces *out)
 {
-    if(!yuv_format_known(format) || (memory != LFI_MEM_HOST && memory != LFI_MEM_DEVICE) || width < 1 || height < 1 || !out)
+    // (LFI_YUV_DEEP on I010 / P010 is a source flag, not a layout: pack the format without it)
+    if(!yuv_format_known(format) || (yuv_format_deep(format) && format != LFI_YUV_GBRP10) || (memory != LFI_MEM_HOST && memory != LFI_MEM_DEVICE) || width < 1 ||
+       height < 1 || !out)
         return LFI_EINVAL;
     const lfi::YuvGeometry g = lfi::yuv_geometry(width, height, yuv_bps(format));
     const bool nv12 = yuv_layout(format) == LFI_YUV_NV12;
     out->format = format, out->memory = memory;
     out->base = base;
+    if(format == LFI_YUV_GBRP10) // G, B, R: three planes of H rows of 2·W bytes
+    {
+        const size_t plane = (size_t)g.W * g.H * 2;
+        out->frame_stride = 3 * plane;
+        out->y_pitch = out->c_pitch = (size_t)g.W * 2;
+        out->c_offset = plane, out->cr_offset = 2 * plane;
+        return LFI_OK;
+    }
     out->frame_stride = g.frame_bytes;
     out->y_pitch = (size_t)g.W * g.bps;
     out->c_offset = (size_t)g.W * g.H * g.bps;
@@ -746,6 +777,8 @@ int upload_mosaic_yuv_surfaces(lfi_ctx *ctx, const char *who, const lfi_mosaic *
     if((long long)m->tiles_x * W > INT32_MAX || (long long)m->tiles_y * H > INT32_MAX)
         return fail(ctx, LFI_EINVAL, std::string(who) + ": the frame's size tiles_x * W by tiles_y * H does not fit 31 bits");
     const int MW = m->tiles_x * W, MH = m->tiles_y * H;
+    if(src && yuv_format_deep(src->format))
+        return fail(ctx, LFI_EINVAL, std::string(who) + ": " + kDeepFormatRefused);
     if(src && yuv_format_known(src->format) && (src->format & LFI_YUV_10BIT))
         return fail(ctx, LFI_EINVAL, std::string(who) + ": 10-bit mosaics (LFI_YUV_I010, LFI_YUV_P010) are not supported: the frame must be LFI_YUV_I420 or LFI_YUV_NV12");
     size_t extent = 0;
@@ -1273,6 +1306,8 @@ int lfi_set_params(lfi_ctx *ctx, const lfi_params *p)
     ctx->radius[1] = std::max(p->block_radius[1], 1);
     ctx->flags = p->flags & 0x7fffffffu; // (bit 31 is the dispatcher's own: LFI_KFLAG_PLAIN_TILE_ORDER, lfi_device.hpp)
 
+    if(views_changed)
+        drop_deep_range(ctx); // (an attached view buffer that is still large enough keeps the views: the deep views of the old parameters go all the same)
     if(views_changed)
         drop_kept(ctx); // the kept views' indices belong to the old number of views (the stream has been drained above)
     if(views_changed || !ctx->views)
@@ -1872,6 +1907,10 @@ int lfi_prepare(lfi_ctx *ctx, int method, int all_focus, int v0, int v1)
         return rc;
     const KernelArgs a = make_args(ctx, v0, v1, method);
     ctx->derived_build_ms = 0.0f;
+    const bool deep = ctx->flags & LFI_FLAG_DEEP_VIEWS; // the copy below, then the deep planes: the first deep render is then only a launch
+    if(deep)
+        if(int rc = deep_views_refused(ctx, all_focus, a))
+            return rc;
     const ViewRowsKind rows = view_rows_of(ctx, all_focus);
     bool planar = false;
     if(rows == VIEW_ROWS_FLOAT) // the RGBA planes are read as they are, nothing to build
@@ -1899,6 +1938,8 @@ int lfi_prepare(lfi_ctx *ctx, int method, int all_focus, int v0, int v1)
         if(ok && ctx->planar_version != before)
             LFI_HIP(ctx, hipEventElapsedTime(&ctx->derived_build_ms, ctx->ev0, ctx->ev1));
     }
+    if(deep)
+        return ensure_deep_planes(ctx);
     return LFI_OK;
 }
 
@@ -1908,7 +1949,7 @@ int lfi_memory_info(lfi_ctx *ctx, lfi_memory *out)
         return LFI_EINVAL;
     out->grid_bytes = ctx->grid ? in_plane_bytes(ctx) * ctx->n : 0;
     out->derived_bytes = ctx->planar.bytes();
-    out->views_bytes = ctx->views.bytes();
+    out->views_bytes = ctx->views.bytes() + ctx->deep.bytes(); // the deep planes (LFI_FLAG_DEEP_VIEWS) belong to the views
     out->maps_bytes = (ctx->maps ? plane_bytes(ctx) * 2 : 0) + ctx->view_maps.bytes();
     out->workspace_bytes = ctx->focus_ws.bytes() + ctx->curve_ws.bytes() + ctx->rgba_scratch.bytes() + ctx->dl_plane.bytes() + ctx->kept.bytes() +
                            ctx->cmp_stage[0].bytes() + ctx->cmp_stage[1].bytes() + ctx->cmp_ws.bytes() + ctx->native.bytes() + ctx->yuv[0].bytes() + ctx->yuv[1].bytes() +
@@ -2039,6 +2080,47 @@ static int download_yuv_surfaces(lfi_ctx *ctx, const char *who, int v0, int n, i
     return finish_yuv_delivery(ctx, dst, n, d);
 }
 
+// lfi_download_views_yuv with a LFI_YUV_DEEP format: frames from the DEEP planes of views [v0, v0 + n) (deep_yuv.hpp).  I010 / P010: the
+// delivery of the 10-bit formats (in place, or staged frames and copies of their own bytes) around one deep_convert10 launch.  GBRP10: no
+// arithmetic — the planes' upper six bits are 0 as deep_blend wrote them, so a frame is three 2D copies of 2·W bytes by H rows straight
+// out of the deep planes (R, G, B there; G, B, R in the frame), to host or device memory alike: no kernel, no staging buffer
+static int download_deep_surfaces(lfi_ctx *ctx, const char *who, int v0, int n, int matrix, int range, const lfi_yuv_surfaces &dst, size_t extent)
+{
+    if(!ctx->deep || v0 < ctx->deep_v0 || v0 + n > ctx->deep_v1)
+        return fail(ctx, LFI_EINVAL, std::string(who) + ": a LFI_YUV_DEEP format needs views [v0, v0 + n) inside the range of the last deep render (LFI_FLAG_DEEP_VIEWS); "
+                                         "a render without the flag drops the deep views");
+    const size_t pitch = (size_t)deep_pitch(ctx), plane = pitch * ctx->out_rows;
+    const uint8_t *src = ctx->deep.get() + (size_t)v0 * 3 * plane;
+    if(dst.format == LFI_YUV_GBRP10)
+    {
+        if(int rc = bind(ctx))
+            return rc;
+        if(dst.memory == LFI_MEM_DEVICE)
+            if(int rc = check_device_surfaces(ctx, who, dst, extent, n))
+                return rc;
+        const hipMemcpyKind kind = dst.memory == LFI_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+        const size_t off[3] = {dst.cr_offset, 0, dst.c_offset}, dpitch[3] = {dst.c_pitch, dst.y_pitch, dst.c_pitch}; // where R, G, B go
+        for(int k = 0; k < n; k++)
+            for(int ch = 0; ch < 3; ch++)
+                LFI_HIP(ctx, hipMemcpy2DAsync(static_cast<uint8_t *>(dst.base) + dst.frame_stride * (size_t)k + off[ch], dpitch[ch], src + ((size_t)k * 3 + ch) * plane,
+                                              pitch, (size_t)ctx->width * 2, ctx->height, kind, ctx->stream));
+        LFI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        return LFI_OK;
+    }
+    YuvDelivery d;
+    if(int rc = open_yuv_delivery(ctx, who, dst, extent, ctx->width, ctx->height, n, false, &d))
+        return rc;
+    lfi::DeepOutArgs a{};
+    a.deep = src, a.view_stride = 3 * plane, a.pitch = (uint32_t)pitch;
+    a.W = ctx->width, a.H = ctx->height;
+    a.s = d.frames;
+    a.cw = (a.W + 1) >> 1, a.ch = (a.H + 1) >> 1;
+    a.blocks_x = (a.W + lfi::YUV_BLOCK_W - 1) / lfi::YUV_BLOCK_W;
+    a.k = lfi::DEEP_COEFFS[matrix * 2 + range];
+    LFI_HIP(ctx, lfi::launch_deep_convert10(ctx->stream, yuv_layout(dst.format), ctx->yuv_out_siting == LFI_YUV_SITING_LEFT, a, n));
+    return finish_yuv_delivery(ctx, dst, n, d);
+}
+
 int lfi_download_views_yuv420(lfi_ctx *ctx, int v0, int n, int matrix, int range, uint8_t *out, size_t frame_stride_bytes)
 {
     if(!ctx)
@@ -2058,8 +2140,10 @@ int lfi_download_views_yuv(lfi_ctx *ctx, int v0, int n, int matrix, int range, c
     if(int rc = check_yuv_download(ctx, "lfi_download_views_yuv", v0, n, matrix, range))
         return rc;
     size_t extent = 0;
-    if(const char *fault = yuv_surfaces_fault(dst, ctx->width, ctx->height, n, &extent))
+    if(const char *fault = yuv_surfaces_fault(dst, ctx->width, ctx->height, n, &extent, DEEP_SOURCE))
         return fail(ctx, LFI_EINVAL, std::string("lfi_download_views_yuv: ") + fault);
+    if(dst->format & LFI_YUV_DEEP)
+        return download_deep_surfaces(ctx, "lfi_download_views_yuv", v0, n, matrix, range, *dst, extent);
     return download_yuv_surfaces(ctx, "lfi_download_views_yuv", v0, n, matrix, range, *dst, extent);
 }
 
@@ -2078,6 +2162,8 @@ int lfi_render_stream(lfi_ctx *ctx, int method, int all_focus, const uint16_t *w
         return rc;
     if(const ViewRowsKind rows = view_rows_of(ctx, all_focus))
         return fail(ctx, LFI_EINVAL, view_rows_set(rows) + "lfi_render_stream is not supported - clear them with NULL");
+    if(ctx->flags & LFI_FLAG_DEEP_VIEWS)
+        return fail(ctx, LFI_EINVAL, "LFI_FLAG_DEEP_VIEWS is set: lfi_render_stream is not supported");
     if(!weights_fp16 || total_views < 1)
         return fail(ctx, LFI_EINVAL, "lfi_render_stream: weights are NULL or total_views < 1");
     if(host_out && (ctx->out_layout != LFI_LAYOUT_RGBA || pitch_bytes < (size_t)ctx->width * 4))
@@ -2092,6 +2178,8 @@ int lfi_render_stream_yuv420(lfi_ctx *ctx, int method, int all_focus, const uint
         return rc;
     if(const ViewRowsKind rows = view_rows_of(ctx, all_focus))
         return fail(ctx, LFI_EINVAL, view_rows_set(rows) + "lfi_render_stream_yuv420 is not supported - clear them with NULL");
+    if(ctx->flags & LFI_FLAG_DEEP_VIEWS)
+        return fail(ctx, LFI_EINVAL, "LFI_FLAG_DEEP_VIEWS is set: lfi_render_stream_yuv420 is not supported");
     if(!weights_fp16 || total_views < 1)
         return fail(ctx, LFI_EINVAL, "lfi_render_stream_yuv420: weights are NULL or total_views < 1");
     YuvSink sink{};
@@ -2444,9 +2532,17 @@ int lfi_benchmark(lfi_ctx *ctx, int method, int all_focus, int v0, int v1, int w
     if(int rc = bind(ctx))
         return rc;
     const KernelArgs a = make_args(ctx, v0, v1, method);
-    // the derived input copy is (re)built here, not inside the first timed launch
+    // the derived input copy is (re)built here, not inside the first timed launch — and so are the deep planes allocated (LFI_FLAG_DEEP_VIEWS)
     bool planar = false;
-    if(const ViewRowsKind rows = view_rows_of(ctx, all_focus))
+    if(ctx->flags & LFI_FLAG_DEEP_VIEWS)
+    {
+        if(int rc = deep_views_refused(ctx, all_focus, a))
+            return rc;
+        (void)ensure_planar(ctx, true);
+        if(int rc = ensure_deep_planes(ctx))
+            return rc;
+    }
+    else if(const ViewRowsKind rows = view_rows_of(ctx, all_focus))
     {
         if(int rc = view_rows_ready(ctx, rows, all_focus, a, &planar))
             return rc;
@@ -2738,6 +2834,8 @@ int lfi_download_rgbd_yuv(lfi_ctx *ctx, int v0, int n, int map_k, uint32_t flags
     // and range), the tiles as lfi_download_quilt_scaled does
     if(int rc = check_yuv_download(ctx, who, v0, n, matrix, range))
         return rc;
+    if(dst && yuv_format_deep(dst->format))
+        return fail(ctx, LFI_EINVAL, std::string(who) + ": " + kDeepFormatRefused);
     if(dst && (dst->format & LFI_YUV_10BIT))
         return fail(ctx, LFI_EINVAL, std::string(who) + ": 10-bit frames (LFI_YUV_I010, LFI_YUV_P010) are not supported: RGB-D frames are 8-bit");
     if(ctx->yuv_out_siting != LFI_YUV_SITING_CENTRE)
@@ -2977,8 +3075,10 @@ int lfi_download_prequant(lfi_ctx *ctx, int method, int all_focus, int v, float 
     if(int rc = bind(ctx))
         return rc;
     const size_t bytes = sizeof(float) * 3 * (size_t)ctx->width * ctx->height;
-    LFI_HIP(ctx, ctx->prequant.reserve(bytes));
     KernelArgs a = make_args(ctx, v, v + 1, method);
+    if(ctx->flags & LFI_FLAG_DEEP_VIEWS) // refused by name before anything is reserved
+        return fail(ctx, LFI_EINVAL, std::string("LFI_FLAG_DEEP_VIEWS is set: ") + kDeepNoPrequant);
+    LFI_HIP(ctx, ctx->prequant.reserve(bytes));
     a.prequant = ctx->prequant.as<float>();
     a.prequant_view = v;
     if(int rc = launch_blend(ctx, method, all_focus, a))
@@ -3052,7 +3152,7 @@ int lfi_debug_poison(lfi_ctx *ctx, uint32_t what, uint8_t byte)
 {
     if(!ctx)
         return LFI_EINVAL;
-    if(what & ~uint32_t(LFI_POISON_VIEWS | LFI_POISON_SCRATCH | LFI_POISON_MAPS | LFI_POISON_FOCUS_WORKSPACE | LFI_POISON_DERIVED | LFI_POISON_VIEW_MAPS))
+    if(what & ~uint32_t(LFI_POISON_VIEWS | LFI_POISON_SCRATCH | LFI_POISON_MAPS | LFI_POISON_FOCUS_WORKSPACE | LFI_POISON_DERIVED | LFI_POISON_VIEW_MAPS | LFI_POISON_DEEP))
         return fail(ctx, LFI_EINVAL, "lfi_debug_poison: unknown LFI_POISON_* bits");
     if((what & LFI_POISON_DERIVED) && ctx->inputs_released)
         return fail(ctx, LFI_EINVAL, "lfi_debug_poison: the planar copy is the only copy of the inputs after lfi_release_inputs");
@@ -3087,6 +3187,8 @@ int lfi_debug_poison(lfi_ctx *ctx, uint32_t what, uint8_t byte)
         rc = rc ? rc : fill(ctx->cmp_stage[1], ctx->cmp_stage[1].bytes());
         rc = rc ? rc : fill(ctx->cmp_ws, ctx->cmp_ws.bytes());
     }
+    if(what & LFI_POISON_DEEP)
+        rc = rc ? rc : fill(ctx->deep, ctx->deep.bytes());
     if(what & LFI_POISON_MAPS)
         rc = rc ? rc : fill(ctx->maps, ctx->maps ? plane_bytes(ctx) * 2 : 0);
     if(what & LFI_POISON_VIEW_MAPS)

@@ -279,6 +279,12 @@ void Interpolator::finish()
         if(nv12File.fail())
             throw std::runtime_error("Cannot write " + nv12Path);
     }
+    if(gbrp10File.is_open())
+    {
+        gbrp10File.close();
+        if(gbrp10File.fail())
+            throw std::runtime_error("Cannot write " + gbrp10Path);
+    }
     if(p010File.is_open())
     {
         p010File.close();
@@ -478,6 +484,12 @@ void Interpolator::interpolate(std::string outputPath, std::string trajectory, f
     lfi::HostParams params = parameterizer.build(trajectory, focus, range, effect, aspect, viewCount);
     if(unifiedFocusMap)
         params.flags |= LFI_FLAG_UNIFIED_FOCUS_MAP;
+    if(deep)
+    {
+        if(inRange > 0 || perViewFocus || viewCentred || gpuCount > 1)
+            throw std::runtime_error("Deep views (--deep) need a fixed-focus render with one focus and one set of shifts on one GPU!");
+        params.flags |= LFI_FLAG_DEEP_VIEWS;
+    }
     if(gpuCount < 1 || gpuCount > viewCount)
         throw std::runtime_error("The number of GPUs has to be between 1 and the number of views!");
     if((compareMethods || !compareDir.empty()) && gpuCount > 1)
@@ -493,7 +505,7 @@ void Interpolator::interpolate(std::string outputPath, std::string trajectory, f
     // TEN_WM renders therefore use the alpha-free byte-plane layout (a quarter fewer bytes written per launch, csrc/hip/blend_p3.hpp);
     // the other renders keep the reference's RGBA planes (they would pay a conversion pass).  Output files are identical.
     for(lfi_ctx *c : contexts)
-        check(lfi_set_output_layout(c, (methodID == LFI_METHOD_TEN_WM && !(inRange > 0)) ? LFI_LAYOUT_PLANAR_RGB : LFI_LAYOUT_RGBA), c);
+        check(lfi_set_output_layout(c, (deep || (methodID == LFI_METHOD_TEN_WM && !(inRange > 0))) ? LFI_LAYOUT_PLANAR_RGB : LFI_LAYOUT_RGBA), c); // (deep views: planar only)
 
     const int allFocus = inRange > 0;
     if(perViewFocus && allFocus)
@@ -881,6 +893,8 @@ void Interpolator::storeResults(std::string path)
                     // 10-bit: tight I010 surfaces (lfi_download_views_yuv)
                     lfi_yuv_surfaces surfaces{};
                     check(lfi_yuv_surfaces_packed(LFI_YUV_I010, LFI_MEM_HOST, frames + frameBytes * viewStart[g], resolution.x, resolution.y, &surfaces), contexts[g]);
+                    if(deep)
+                        surfaces.format |= LFI_YUV_DEEP; // the same surfaces, made from the deep views
                     check(lfi_download_views_yuv(contexts[g], 0, viewStart[g + 1] - viewStart[g], yuvMatrix, yuvRange, &surfaces), contexts[g]);
                     continue;
                 }
@@ -893,6 +907,8 @@ void Interpolator::storeResults(std::string path)
                 y4mWriter = std::make_unique<lfi::Y4mWriter>(y4mPath, resolution.x, resolution.y, y4mFps.x, y4mFps.y, yuvRange == LFI_YUV_FULL, outSiting == LFI_YUV_SITING_LEFT, yuvDepth);
                 if(yuvDepth == 10)
                     announceDeepY4m(y4mPath);
+                if(yuvDepth == 10 && deep)
+                    std::cout << "deep views: the 10-bit frames of " << y4mPath << " are converted from the render's own 10-bit codes" << std::endl;
             }
             for(int i = 0; i < viewCount; i++)
                 y4mWriter->writeFrame(frames + frameBytes * i);
@@ -914,7 +930,12 @@ void Interpolator::storeResults(std::string path)
     if(!p010Path.empty())
     {
         std::cout << "Storing P010 video..." << std::endl;
-        storeRawFrames(p010Path, p010File, LFI_YUV_P010, "p010le");
+        storeRawFrames(p010Path, p010File, LFI_YUV_P010 | (deep ? LFI_YUV_DEEP : 0), "p010le");
+    }
+    if(!gbrp10Path.empty())
+    {
+        std::cout << "Storing deep views..." << std::endl;
+        storeRawFrames(gbrp10Path, gbrp10File, LFI_YUV_GBRP10, "gbrp10le");
     }
 }
 
@@ -930,7 +951,8 @@ void Interpolator::announceDeepY4m(const std::string &filePath) const
 // the device into the tight layout (lfi_download_views_yuv), every GPU's views arriving in its part of one buffer
 void Interpolator::storeRawFrames(const std::string &filePath, std::ofstream &file, int format, const char *pixFmt)
 {
-    const size_t frameBytes = lfi::y4mFrameBytes(resolution.x, resolution.y, format & LFI_YUV_10BIT ? 10 : 8); // the semi-planar frame has the planar one's bytes
+    // the semi-planar frame has the planar one's bytes; gbrp10le: three full planes of 16-bit samples
+    const size_t frameBytes = format == LFI_YUV_GBRP10 ? (size_t)6 * resolution.x * resolution.y : lfi::y4mFrameBytes(resolution.x, resolution.y, format & LFI_YUV_10BIT ? 10 : 8);
     uint8_t *frames = nullptr;
     const bool framesPinned = lfi_alloc_pinned(frameBytes * viewCount, reinterpret_cast<void **>(&frames)) == LFI_OK;
     std::vector<uint8_t> pageableFrames;
@@ -945,7 +967,9 @@ void Interpolator::storeRawFrames(const std::string &filePath, std::ofstream &fi
         {
             lfi_yuv_surfaces surfaces{};
             check(lfi_set_yuv_siting(contexts[g], inSiting, outSiting), contexts[g]);
-            check(lfi_yuv_surfaces_packed(format, LFI_MEM_HOST, frames + frameBytes * viewStart[g], resolution.x, resolution.y, &surfaces), contexts[g]);
+            // (LFI_YUV_DEEP on P010 is a source flag: the layout is P010's)
+            check(lfi_yuv_surfaces_packed(format == LFI_YUV_GBRP10 ? format : format & ~LFI_YUV_DEEP, LFI_MEM_HOST, frames + frameBytes * viewStart[g], resolution.x, resolution.y, &surfaces), contexts[g]);
+            surfaces.format = format;
             check(lfi_download_views_yuv(contexts[g], 0, viewStart[g + 1] - viewStart[g], yuvMatrix, yuvRange, &surfaces), contexts[g]);
         }
         // one file for all time steps of a light-field video: opened by the first, appended to by the others, closed by finish()
@@ -954,7 +978,9 @@ void Interpolator::storeRawFrames(const std::string &filePath, std::ofstream &fi
             file.open(filePath, std::ios::binary | std::ios::trunc);
             if(!file)
                 throw std::runtime_error("Cannot write " + filePath);
-            std::cout << (format & LFI_YUV_10BIT ? "P010" : "NV12") << " video " << filePath << ": ffmpeg -f rawvideo -pix_fmt " << pixFmt << " -s " << resolution.x << "x"
+            if(deep && format != LFI_YUV_GBRP10)
+                std::cout << "deep views: the 10-bit frames of " << filePath << " are converted from the render's own 10-bit codes" << std::endl;
+            std::cout << (format == LFI_YUV_GBRP10 ? "deep views (planar 10-bit RGB)" : format & LFI_YUV_10BIT ? "P010" : "NV12") << " video " << filePath << ": ffmpeg -f rawvideo -pix_fmt " << pixFmt << " -s " << resolution.x << "x"
                       << resolution.y << " -r " << y4mFps.x;
             if(y4mFps.y != 1)
                 std::cout << "/" << y4mFps.y;

@@ -95,6 +95,10 @@ class Interpolator
         // lfi_download_quilt_yuv with LFI_YUV_I010) under the tag C420p10, which carries no siting: opening the file prints the siting in use
         // and the ffmpeg option that states it.  setRgbdY4m refuses 10
         void setYuvDepth(int depth) { yuvDepth = depth; }
+        // deep views (LFI_FLAG_DEEP_VIEWS): fixed-focus renders keep 10 bits per channel on the device; the 10-bit video outputs (--p010,
+        // --y4m at 10 bits) are then converted from them (LFI_YUV_DEEP), and setGbrp10 stores them as raw gbrp10le planes
+        void setDeep(bool on) { deep = on; }
+        void setGbrp10(std::string path) { gbrp10Path = path; }
         // 10 where the input is a light-field video whose files say C420p10 (they are uploaded as I010 frames: lfi_upload_images_yuv), else 8
         int inputDepth() const;
         // also write the quilt of setQuilt (scaled by setQuiltTile) as ONE frame of a Y4M video file: resized and converted to 8-bit YUV 4:2:0
@@ -219,6 +223,9 @@ class Interpolator
         std::string p010Path;                      // empty: no raw P010 file
         std::ofstream p010File;                    // open from the first stored step to finish()
         int yuvDepth{8};                           // setYuvDepth
+        bool deep{false};                          // setDeep
+        std::string gbrp10Path;                    // empty: no raw gbrp10le file
+        std::ofstream gbrp10File;                  // open from the first stored step to finish()
         std::string quiltY4mPath;                  // empty: no quilt video
         std::unique_ptr<lfi::Y4mWriter> quiltY4mWriter; // open from the first stored step to finish()
         std::string rgbdY4mPath;                   // empty: no RGB-D video

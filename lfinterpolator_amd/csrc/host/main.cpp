@@ -63,6 +63,8 @@ int main(int argc, char **argv)
                           "--y4m FILE - also store the views as the frames of one YUV4MPEG2 video FILE, in view order (ffmpeg -i FILE, or any player): 8-bit YUV 4:2:0 (I420, centre-sited chroma), converted on the GPU before the download - 1.5 bytes per pixel cross PCIe instead of 4; with -g every GPU converts its own views\n"
                           "--nv12 FILE - also store the views as raw NV12 frames in FILE, in view order, tightly packed (the Y plane, then one plane of interleaved Cb/Cr): what hardware encoders take; converted on the GPU like --y4m, may be given next to it, and with --frames COUNT above 1 FILE takes all steps' views; prints the ffmpeg options that open FILE (-f rawvideo -pix_fmt nv12 -s WxH -r N)\n"
                           "--p010 FILE - also store the views as raw 10-bit P010 frames in FILE (the layout of --nv12 with every sample a little-endian 16-bit word, the code in its upper 10 bits): what Main10 hardware encoders take; converted on the GPU, may be given next to --y4m and --nv12 whatever --yuv-depth says; prints the ffmpeg options that open FILE (-f rawvideo -pix_fmt p010le -s WxH -r N)\n"
+                          "--deep - with a fixed-focus render: deep views - the GPU keeps 10 bits per colour channel straight from the blend's accumulator beside the 8-bit views (the PNG files are unchanged bytes), and --p010 FILE and --y4m FILE with --yuv-depth 10 are converted from those 10-bit views instead of from the 8-bit ones: a Main10 encoder gets the render without a first quantisation. Not with -r above 0, -F, -c, --view-maps, -g above 1, 8-bit video outputs (--nv12, --y4m without --yuv-depth 10), --quilt-y4m or --rgbd-y4m\n"
+                          "--gbrp10 FILE - with --deep: also store the deep views as raw planar 10-bit RGB frames in FILE, in view order: per frame the planes G, B, R, every sample a little-endian 16-bit word with the code in its low 10 bits; prints the ffmpeg options that open FILE (-f rawvideo -pix_fmt gbrp10le -s WxH -r N)\n"
                           "--yuv-depth 8|10 - with --y4m or --quilt-y4m: the bits per sample of the frames written (default=8). 10: the files hold I010 samples (yuv420p10le) under the tag C420p10, and an 8-bit colour survives the trip into them and back exactly; Y4M has no siting tag for 10-bit frames, so the siting in use (--chroma-site) is printed with the ffmpeg option that states it (-chroma_sample_location). Not with --rgbd-y4m: RGB-D frames are 8-bit. A light-field video whose files say C420p10 is read as 10-bit frames without any option (--in-chroma-site auto reads it left-sited and says so); not with --lean-inputs: 10-bit frames cannot go straight into the planar copy\n"
                           "--quilt-y4m FILE - with -q: also store the quilt (scaled by --quilt-tile) as one frame of the YUV4MPEG2 video FILE, resized and converted to 8-bit YUV 4:2:0 on the GPU in one pass (even tile sizes) - with --frames FIRST:COUNT one frame per time step: a quilt video, what holographic players take; one GPU only\n"
                           "--rgbd-y4m FILE - with -r: also store one view with its focus map beside it as one frame of the YUV4MPEG2 video FILE, twice the tile's width: the colour left, the depth right (RGB-D, what holographic players and 2D-plus-depth displays take), both resized and converted to 8-bit YUV 4:2:0 on the GPU in one pass; the depth is the map's value as grey, and displays take white as near; with -c --view-maps the view's own map is used; with --frames FIRST:COUNT one frame per time step: an RGB-D video; one GPU only\n"
@@ -355,6 +357,38 @@ int main(int argc, char **argv)
     {
         std::cerr << "--p010 needs the name of the video file to write." << std::endl;
         return EXIT_FAILURE;
+    }
+
+    if(args["--gbrp10"] && !args["--deep"])
+    {
+        std::cerr << "--gbrp10 stores the deep views: it needs --deep." << std::endl;
+        return EXIT_FAILURE;
+    }
+    if(args["--gbrp10"] && static_cast<std::string>(args["--gbrp10"]).empty())
+    {
+        std::cerr << "--gbrp10 needs the name of the file to write." << std::endl;
+        return EXIT_FAILURE;
+    }
+    if(args["--deep"])
+    {
+        // deep views: one fixed-focus kernel in one context, whose 10-bit planes only the 10-bit outputs read
+        const std::pair<bool, const char *> refused[] = {
+            {args["-r"] && range > 0, "-r above 0 (deep views need a fixed-focus render)"},
+            {static_cast<bool>(args["-F"]), "-F (a focus per view is not rendered deep)"},
+            {static_cast<bool>(args["-c"]), "-c (view-centred shifts are not rendered deep)"},
+            {static_cast<bool>(args["--view-maps"]), "--view-maps (all-focus rendering is not rendered deep)"},
+            {args["-g"] && static_cast<int>(args["-g"]) > 1, "-g above 1 (it works in one context)"},
+            {static_cast<bool>(args["--nv12"]), "--nv12 (an 8-bit video: use --p010)"},
+            {args["--y4m"] && yuvDepth != 10, "--y4m at 8 bits (an 8-bit video: add --yuv-depth 10)"},
+            {static_cast<bool>(args["--quilt-y4m"]), "--quilt-y4m (deep quilts are not supported)"},
+            {static_cast<bool>(args["--rgbd-y4m"]), "--rgbd-y4m (RGB-D frames are 8-bit)"},
+        };
+        for(const auto &[given, what] : refused)
+            if(given)
+            {
+                std::cerr << "--deep (10-bit views straight from the blend's accumulator) cannot be combined with " << what << "." << std::endl;
+                return EXIT_FAILURE;
+            }
     }
 
     int outSiting = LFI_YUV_SITING_CENTRE;
@@ -683,6 +717,10 @@ int main(int argc, char **argv)
             interpolator->setY4m(static_cast<std::string>(args["--y4m"]), fpsNum, fpsDen, yuvMatrix, yuvRange);
         if(args["--nv12"])
             interpolator->setNv12(static_cast<std::string>(args["--nv12"]), fpsNum, fpsDen, yuvMatrix, yuvRange);
+        if(args["--deep"])
+            interpolator->setDeep(true);
+        if(args["--gbrp10"])
+            interpolator->setGbrp10(static_cast<std::string>(args["--gbrp10"]));
         if(args["--p010"])
             interpolator->setP010(static_cast<std::string>(args["--p010"]), fpsNum, fpsDen, yuvMatrix, yuvRange);
         interpolator->setYuvDepth(yuvDepth);
