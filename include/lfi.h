@@ -533,9 +533,12 @@ typedef struct lfi_lenticular {
     uint32_t y_step;   /* phase advance per pixel row (two's complement: a negative slant wraps) */
     uint32_t phase0;   /* phase of subpixel 0 of pixel (0, 0) */
     int32_t  views;    /* n: the views v0 … v0+n-1 spread over one lens period, 1 ≤ n */
-    uint32_t flags;    /* LFI_LENT_INVERT: view n-1-k where the phase selects k */
+    uint32_t flags;    /* LFI_LENT_INVERT: view n-1-k where the phase selects k; LFI_LENT_BGR, LFI_LENT_BILINEAR, LFI_LENT_BLEND: below */
 } lfi_lenticular;
 #define LFI_LENT_INVERT 1u
+#define LFI_LENT_BGR      4u    /* the panel's subpixels run B, G, R from left to right */
+#define LFI_LENT_BILINEAR 8u    /* tile sampling: bilinear instead of nearest */
+#define LFI_LENT_BLEND    16u   /* every subpixel blends the two views nearest to its phase */
 /* For output pixel (x, y) and colour channel c ∈ {0: R, 1: G, 2: B} (RGB subpixel order), all in unsigned integers:
  *     phase = phase0 + (3·x + c)·x_step + y·y_step                       (mod 2^32)
  *     k     = (u64(phase) · n) >> 32;   with LFI_LENT_INVERT  k = n − 1 − k
@@ -550,7 +553,29 @@ typedef struct lfi_lenticular {
  * rectangle.  rgba: out_h rows of pitch_bytes ≥ out_w·4.  Synchronous.  Attached views work as they do for quilts.
  * LFI_EINVAL, the context usable and the host image untouched: what lfi_download_quilt_scaled refuses for a tile (a row window among it),
  * lens NULL, n < 1 or v0 + n beyond the rendered views, unknown flag bits, an output size outside the limits, a NULL image or a pitch below
- * out_w·4.  (A display calibration becomes an lfi_lenticular on the host: csrc/host/lenticular.h.) */
+ * out_w·4.  (A display calibration becomes an lfi_lenticular on the host: csrc/host/lenticular.h.)
+ *
+ * The three filter flags refine the definition above; every other argument keeps its meaning, limits and refusals, and a call with none of
+ * them computes exactly what is written above.  Still all in unsigned integers:
+ *   LFI_LENT_BGR       the subpixel of channel c is s = 2 − c instead of s = c:  phase = phase0 + (3·x + s)·x_step + y·y_step.  The output stays
+ *                      RGBA in memory; only which phase a channel has changes.
+ *   view selection     P = u64(phase)·n,  k = P >> 32,  f = (P >> 24) & 255 — the top eight bits of the fraction; in 32 bits the high word of
+ *                      phase·n and (phase·n mod 2^32) >> 24.
+ *   LFI_LENT_BLEND     view k's centre is at fraction ½:  f ≥ 128: ka = k, kb = min(k + 1, n − 1), wb = f − 128;  else ka = max(k, 1) − 1, kb = k,
+ *                      wb = f + 128.  The ends clamp and never wrap: views n − 1 and 0 are the two sides of the jump between lens periods.
+ *                      out[y][x][c] = ((256 − wb)·S_{v0+ka} + wb·S_{v0+kb} + 128) >> 8;  without the flag out[y][x][c] = S_{v0+k}.
+ *   LFI_LENT_INVERT    maps each selected index q (k, ka, kb) to n − 1 − q, after the selection.
+ *   LFI_LENT_BILINEAR  the tile sample S_v(x, y, c), pixel centres at +½ on both sides.  Along x, with D = 2·out_w:
+ *                        U  = clamp((2·x + 1)·tile_w − out_w, 0, (tile_w − 1)·D)          (the first term signed before the clamp)
+ *                        x0 = U / D,  r = U − x0·D,  fx = (256·r) / D ∈ [0, 255],  x1 = min(x0 + 1, tile_w − 1)
+ *                      along y likewise (y0, y1, fy), then
+ *                        h_j = (256 − fx)·T_v[y_j][x0][c] + fx·T_v[y_j][x1][c]   (j = 0, 1),   S = ((256 − fy)·h_0 + fy·h_1 + 2^15) >> 16.
+ *                      Without the flag S_v = T_v[sy][sx][c] as above.  Every intermediate is below 2^24 except (2·x + 1)·tile_w < 2^33, which the
+ *                      kernel splits as it does for sx: with q, r = quotient and remainder of x·tile_w by out_w, (2·x + 1)·tile_w − out_w + D =
+ *                      D·q + e with e = 2·r + tile_w + out_w < 4·65535, so 32 bits suffice (csrc/native_taps.h).
+ * Alpha is 255.  What follows from this: with tile = out_w × out_h, fx = fy = 0 everywhere and LFI_LENT_BILINEAR changes no byte (the call
+ * drops the flag there); a phase exactly on a view's centre (f = 128) has wb = 0, view k alone; a phase on a boundary (f = 0) is the rounded
+ * even mix of the two neighbours; n = 1 gives view v0 under any flags.  Flag bits other than these four are refused. */
 int lfi_download_native(lfi_ctx *ctx, const lfi_lenticular *lens, int v0, int out_w, int out_h, int tile_w, int tile_h, uint8_t *rgba, size_t pitch_bytes);
 /* Views as 8-bit YUV 4:2:0 video frames (I420), converted on the device before the copy: what every encoder and player takes, 1.5 bytes per
  * pixel instead of the 4 of lfi_download_view (the alpha dropped is the constant 255, the chroma dropped is what an encoder's first step

@@ -27,6 +27,9 @@ LFI_POISON_DERIVED = 16
 LFI_POISON_VIEW_MAPS = 32
 LFI_POISON_DEEP = 64
 LFI_LENT_INVERT = 1
+LFI_LENT_BGR = 4         # lfi_lenticular.flags: the panel's subpixels run B, G, R
+LFI_LENT_BILINEAR = 8    # … bilinear tile sampling
+LFI_LENT_BLEND = 16      # … every subpixel blends the two views nearest to its phase
 LFI_RGBD_INVERT = 1
 LFI_RGBD_VIEW_MAPS = 2
 LFI_YUV_BT709 = 0
@@ -123,7 +126,8 @@ class FocusCurveResult(C.Structure):
 
 
 class Lenticular(C.Structure):
-    """lfi_lenticular: the lens sheet of lfi_download_native in units of 2^-32 lens periods (host.lenticular builds one from a calibration)"""
+    """lfi_lenticular: the lens sheet of lfi_download_native in units of 2^-32 lens periods (host.lenticular builds one from a calibration,
+    host.lenticular_file from a display's calibration file); flags: LFI_LENT_INVERT | LFI_LENT_BGR | LFI_LENT_BILINEAR | LFI_LENT_BLEND"""
     _fields_ = [("x_step", C.c_uint32), ("y_step", C.c_uint32), ("phase0", C.c_uint32), ("views", C.c_int32), ("flags", C.c_uint32)]
 
 

@@ -11,6 +11,7 @@
 #include "quilt_scaled.hpp"
 #include "quilt_yuv.hpp"
 #include "rgbd_yuv.hpp"
+#include "native_filter.hpp"
 #include "native_image.hpp"
 #include "yuv420.hpp"
 #include "yuv420_upload.hpp"
@@ -2887,7 +2888,7 @@ int lfi_download_native(lfi_ctx *ctx, const lfi_lenticular *lens, int v0, int ou
         return fail(ctx, LFI_EINVAL, "a native image needs whole views: its subpixels read rows the row window's band does not hold");
     if(!lens)
         return fail(ctx, LFI_EINVAL, "a native image needs a lens description (lfi_lenticular)");
-    if(lens->flags & ~uint32_t(LFI_LENT_INVERT))
+    if(lens->flags & ~uint32_t(LFI_LENT_INVERT | LFI_LENT_BGR | LFI_LENT_BILINEAR | LFI_LENT_BLEND))
         return fail(ctx, LFI_EINVAL, "unknown lfi_lenticular flag bits");
     if(lens->views < 1 || v0 < 0 || (long)v0 + lens->views > ctx->views_n)
         return fail(ctx, LFI_EINVAL, "a native image needs lens views >= 1 and as many views starting at v0 inside [0, views)");
@@ -2923,7 +2924,15 @@ int lfi_download_native(lfi_ctx *ctx, const lfi_lenticular *lens, int v0, int ou
         LFI_HIP(ctx, lfi::launch_quilt_scale(ctx->stream, planar, q, n));
         a.src = lfi::ViewsSrc{ctx->quilt.get(), tile_bytes, (uint32_t)tile_w, (uint32_t)tile_h, 0u};
     }
-    LFI_HIP(ctx, lfi::launch_native_interlace(ctx->stream, planar && !scaled, a));
+    // any filter flag takes native_filter; bilinear taps of a tile of the output's size all have weight 0: nearest, the flag dropped
+    uint32_t filter = lens->flags & (LFI_LENT_BGR | LFI_LENT_BILINEAR | LFI_LENT_BLEND);
+    if(tile_w == out_w && tile_h == out_h)
+        filter &= ~uint32_t(LFI_LENT_BILINEAR);
+    if(filter)
+        LFI_HIP(ctx, lfi::launch_native_filter(ctx->stream, planar && !scaled, (filter & LFI_LENT_BILINEAR) != 0, (filter & LFI_LENT_BLEND) != 0,
+                                               lfi::NativeFilterArgs{a, (filter & LFI_LENT_BGR) ? 1u : 0u}));
+    else
+        LFI_HIP(ctx, lfi::launch_native_interlace(ctx->stream, planar && !scaled, a));
     LFI_HIP(ctx, hipMemcpy2DAsync(rgba, pitch_bytes, ctx->native.get(), (size_t)out_w * 4, (size_t)out_w * 4, out_h, hipMemcpyDeviceToHost, ctx->stream));
     LFI_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return LFI_OK;

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "../area_span.h"
+#include "../native_taps.h"
 #include "lenticular.h"
 #include "params.h"
 #include "y4m.h"
@@ -116,6 +117,42 @@ int lfi_host_lenticular(double pitch, double slope, double center, double dpi, i
     {
         return report(e, err, err_len);
     }
+}
+
+// lfi_host_lenticular from a display's calibration FILE (lenticular.h: a flat JSON object): the same arithmetic on the file's pitch, slope,
+// center and DPI; invView becomes LFI_LENT_INVERT and flipSubp LFI_LENT_BGR in out->flags; screen = {screenW, screenH} as the file states
+// them (0: not stated; may be NULL); returns 0 or -1 (message in err, naming the key at fault)
+int lfi_host_lenticular_json(const char *path, int out_w, int out_h, int n, lfi_lenticular *out, int32_t screen[2], char *err, size_t err_len)
+{
+    try
+    {
+        if(!path || !out)
+            throw std::runtime_error("path and out must be non-NULL");
+        const lfi::LensFile file = lfi::lensCalibrationFromFile(path);
+        *out = lfi::lenticularFromCalibration(file.lens, out_w, out_h, n);
+        out->flags |= file.flags;
+        if(screen)
+            screen[0] = file.screenW, screen[1] = file.screenH;
+        return 0;
+    }
+    catch(const std::exception &e)
+    {
+        return report(e, err, err_len);
+    }
+}
+
+// output pixel o of lfi_download_native's bilinear tile sampling along one axis of src tile pixels and dst output pixels (../native_taps.h, the
+// code the kernel runs): out = {p0, p1, f} — the two taps and the weight of p1 in 1/256.  Returns 0, or -1 unless 1 <= src, dst <= 65535 and
+// 0 <= o < dst
+int lfi_host_native_taps(int src, int dst, int o, int32_t out[3])
+{
+    if(!out || src < 1 || dst < 1 || src > 65535 || dst > 65535 || o < 0 || o >= dst)
+        return -1;
+    const lfi::NativeTaps t = lfi::native_taps(static_cast<uint32_t>(o), static_cast<uint32_t>(src), static_cast<uint32_t>(dst));
+    out[0] = static_cast<int32_t>(t.p0);
+    out[1] = static_cast<int32_t>(t.p1);
+    out[2] = static_cast<int32_t>(t.f);
+    return 0;
 }
 
 // the interval an all-focus render should search, from the tiles' best candidates of a search over [focus, focus + range] (--auto-range):

@@ -863,7 +863,8 @@ void Interpolator::storeResults(std::string path)
         std::cout << "Storing native image..." << std::endl;
         // interlaced on the device (lfi_download_native): only the display's own pixels are copied
         const lfi::IVec2 tile = nativeTile.x > 0 ? nativeTile : lfi::IVec2{resolution.x, resolution.y};
-        const lfi_lenticular lens = lfi::lenticularFromCalibration(nativeLens, nativeSize.x, nativeSize.y, nativeViews > 0 ? nativeViews : viewCount);
+        lfi_lenticular lens = lfi::lenticularFromCalibration(nativeLens, nativeSize.x, nativeSize.y, nativeViews > 0 ? nativeViews : viewCount);
+        lens.flags |= nativeFlags;
         const size_t nativePitch = static_cast<size_t>(nativeSize.x) * channels;
         std::vector<uint8_t> native(nativePitch * nativeSize.y);
         check(lfi_download_native(context, &lens, 0, nativeSize.x, nativeSize.y, tile.x, tile.y, native.data(), nativePitch));

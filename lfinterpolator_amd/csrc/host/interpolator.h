@@ -54,8 +54,10 @@ class Interpolator
         // also write native.png: the native image of a lenticular display of width × height pixels whose lens sheet the calibration
         // describes (lenticular.h), interlaced on the device from the first `views` views (0: all of them), each resized to a tile of
         // tile.x × tile.y pixels first (0: the views' size, read in place) — lfi_download_native.  One GPU: every view in one context
-        void setNative(lfi::IVec2 size, lfi::LensCalibration lens, lfi::IVec2 tile = {0, 0}, int views = 0)
+        // flags: LFI_LENT_BGR, LFI_LENT_BILINEAR, LFI_LENT_BLEND — the filtered native image (include/lfi.h)
+        void setNative(lfi::IVec2 size, lfi::LensCalibration lens, lfi::IVec2 tile = {0, 0}, int views = 0, uint32_t flags = 0)
         {
+            nativeFlags = flags;
             nativeSize = size;
             nativeLens = lens;
             nativeTile = tile;
@@ -214,6 +216,7 @@ class Interpolator
         lfi::LensCalibration nativeLens;
         lfi::IVec2 nativeTile{0, 0}; // 0: the views' size, read in place
         int nativeViews{0};          // 0: all views
+        uint32_t nativeFlags{0};     // LFI_LENT_BGR | LFI_LENT_BILINEAR | LFI_LENT_BLEND
         std::string y4mPath;         // empty: no video file
         lfi::IVec2 y4mFps{30, 1};
         int yuvMatrix{LFI_YUV_BT709};

@@ -17,7 +17,15 @@
 // Accuracy: a step is off by at most half a unit, 2⁻³³ of a lens period; along a row of 7680 pixels the phase adds x_step 3 · 7680 =
 // 23040 < 2¹⁵ times, so the accumulated error stays under 2⁻¹⁸ of a lens period — with n views a view is 1 / n of a period wide, so far
 // below one view for any n a display has.
+//
+// A calibration FILE (lensCalibrationFromJson) is the flat JSON object such displays report about themselves: every numeric entry is either
+// "name": {"value": x} or "name": x.  Taken: pitch, slope, center, DPI, invView (non-zero: reversed view order, LFI_LENT_INVERT), flipSubp
+// (non-zero: the subpixels run B, G, R — LFI_LENT_BGR), screenW and screenH (the panel's size, for the caller to compare with its own).
+// flipImageX / flipImageY non-zero are refused: mirrored panels are not built.  Strings, other keys and whatever they hold are skipped; the
+// order of the keys does not matter; a key given twice counts as its last entry.  Errors name the key.
 #pragma once
+
+#include <string>
 
 #include "../../../include/lfi.h"
 
@@ -31,5 +39,18 @@ struct LensCalibration
 
 // throws std::runtime_error unless pitch, dpi > 0, slope ≠ 0, all finite, out_w, out_h, n ≥ 1 and every rounded value is below 2⁵² in magnitude
 lfi_lenticular lenticularFromCalibration(const LensCalibration &c, int out_w, int out_h, int n);
+
+// a calibration file's content: the calibration, LFI_LENT_BGR or 0, and the panel's size (0: not stated)
+struct LensFile
+{
+    LensCalibration lens;
+    uint32_t flags = 0;
+    int screenW = 0, screenH = 0;
+};
+
+// throws std::runtime_error for text that is no JSON object, a taken key without a number, a missing pitch, slope, center or DPI, and a mirrored panel
+LensFile lensCalibrationFromJson(const std::string &text);
+// … of the file at path; throws also when it cannot be read
+LensFile lensCalibrationFromFile(const std::string &path);
 
 } // namespace lfi

@@ -2,8 +2,8 @@
 // (-i -t -o -f -r -m -s -a -h), plus -n (views), -b (benchmark runs), -d (device), -F (focus at the last view), -c (shifts about each
 // view's own camera), --autofocus (the focus found from a region's focus curve), --focus-tiles / --auto-range (the focus of every tile of a
 // grid; the search interval of an all-focus render found from it), --map-steps / --tile-steps (more than 32 candidates for the focus map / the focus tiles), --compare / --compare-methods (PSNR / SSIM of all views against a
-// directory of images or against the other method's render), --native / --lens / --native-tile / --native-views (the native image of a
-// lenticular display, interlaced on the GPU), --y4m / --nv12 / --fps / --yuv-matrix / --yuv-range (the views as one YUV 4:2:0 video file, converted on
+// directory of images or against the other method's render), --native / --lens / --lens-file / --lens-bgr / --native-tile / --native-views / --native-filter /
+// --native-blend (the native image of a lenticular display, interlaced on the GPU, nearest or filtered), --y4m / --nv12 / --fps / --yuv-matrix / --yuv-range (the views as one YUV 4:2:0 video file, converted on
 // the GPU), --yuv-depth / --p010 (10-bit frames: C420p10 Y4M files and raw P010), --quilt-y4m (the quilt as one YUV 4:2:0 video frame per time step: a quilt video), --rgbd-y4m / --rgbd-view / --rgbd-tile / --rgbd-map /
 // --rgbd-invert (a view with its focus map beside it as one YUV 4:2:0 video frame per time step: RGB-D video), --chroma-site / --in-chroma-site (left-sited chroma, MPEG-2 / H.264 siting, for the frames written / read), --frames / --in-matrix / --in-range / --in-chroma (a light-field video as input: a directory of per-camera Y4M files whose frames
 // become the images on the GPU), --lean-inputs (such a video at fixed focus from the planar copy of the inputs alone), --mosaic / --mosaic-order / --mosaic-bottom-up (one image or Y4M file that holds every image as a tile, split on the GPU) and --synthetic for runs without a dataset.
@@ -60,6 +60,10 @@ int main(int argc, char **argv)
                           "--lens pitch,slope,center,dpi[,invert] - with --native: the display's calibration - lenses per inch, the slant, the phase offset in lens periods, the panel's pixels per inch, and 1 to reverse the order of the views (default 0)\n"
                           "--native-tile WxH - with --native: resize every view to a tile of W x H pixels on the GPU first (the exact area filter of --quilt-tile; at most the views' size; default: the views' size, read in place)\n"
                           "--native-views N - with --native: interlace the first N views (default: all of them)\n"
+                          "--native-filter nearest|bilinear - with --native: how a tile is sampled under an output pixel's centre: nearest takes the one tile pixel there (default), bilinear weighs the four around it in 1/256 steps, as the display vendors' interlacing shaders sample a quilt; no difference where the tile has the display's size\n"
+                          "--native-blend - with --native: every subpixel blends the two views nearest to its position under the lens, weighted in 1/256 steps by its distance from their centres, instead of taking the one view it falls into: no hard jumps between views; the first and the last view do not blend into each other\n"
+                          "--lens-bgr - with --native: the panel's subpixels run B, G, R from left to right (native.png stays an RGB image; only which view a channel shows changes)\n"
+                          "--lens-file FILE - with --native, in place of --lens: read the calibration from FILE, the JSON object such a display reports (entries \"name\": x or \"name\": {\"value\": x}): pitch, slope, center, DPI, invView (the invert of --lens), flipSubp (--lens-bgr); screenW and screenH are compared with --native and a difference is noted; a mirrored panel (flipImageX, flipImageY) is refused\n"
                           "--y4m FILE - also store the views as the frames of one YUV4MPEG2 video FILE, in view order (ffmpeg -i FILE, or any player): 8-bit YUV 4:2:0 (I420, centre-sited chroma), converted on the GPU before the download - 1.5 bytes per pixel cross PCIe instead of 4; with -g every GPU converts its own views\n"
                           "--nv12 FILE - also store the views as raw NV12 frames in FILE, in view order, tightly packed (the Y plane, then one plane of interleaved Cb/Cr): what hardware encoders take; converted on the GPU like --y4m, may be given next to it, and with --frames COUNT above 1 FILE takes all steps' views; prints the ffmpeg options that open FILE (-f rawvideo -pix_fmt nv12 -s WxH -r N)\n"
                           "--p010 FILE - also store the views as raw 10-bit P010 frames in FILE (the layout of --nv12 with every sample a little-endian 16-bit word, the code in its upper 10 bits): what Main10 hardware encoders take; converted on the GPU, may be given next to --y4m and --nv12 whatever --yuv-depth says; prints the ffmpeg options that open FILE (-f rawvideo -pix_fmt p010le -s WxH -r N)\n"
@@ -225,9 +229,15 @@ int main(int argc, char **argv)
         return EXIT_FAILURE;
     }
 
-    if(static_cast<bool>(args["--native"]) != static_cast<bool>(args["--lens"]))
+    if(args["--lens"] && args["--lens-file"])
     {
-        std::cerr << "--native (the display's size) and --lens (its calibration) describe one display: give both." << std::endl;
+        std::cerr << "--lens and --lens-file both give the display's calibration: use one of them." << std::endl;
+        return EXIT_FAILURE;
+    }
+
+    if(static_cast<bool>(args["--native"]) != (args["--lens"] || args["--lens-file"]))
+    {
+        std::cerr << "--native (the display's size) and --lens or --lens-file (its calibration) describe one display: give both." << std::endl;
         return EXIT_FAILURE;
     }
 
@@ -235,6 +245,45 @@ int main(int argc, char **argv)
     {
         std::cerr << "--native-tile and --native-views belong to the native image: they need --native WxH." << std::endl;
         return EXIT_FAILURE;
+    }
+
+    if((args["--native-filter"] || args["--native-blend"] || args["--lens-bgr"]) && !args["--native"])
+    {
+        std::cerr << "--native-filter, --native-blend and --lens-bgr belong to the native image: they need --native WxH." << std::endl;
+        return EXIT_FAILURE;
+    }
+
+    uint32_t nativeFlags = 0;
+    if(args["--native-filter"])
+    {
+        const std::string text = static_cast<std::string>(args["--native-filter"]);
+        if(text != "nearest" && text != "bilinear")
+        {
+            std::cerr << "--native-filter expects nearest or bilinear." << std::endl;
+            return EXIT_FAILURE;
+        }
+        nativeFlags |= text == "bilinear" ? LFI_LENT_BILINEAR : 0u;
+    }
+    if(args["--native-blend"])
+        nativeFlags |= LFI_LENT_BLEND;
+    if(args["--lens-bgr"])
+        nativeFlags |= LFI_LENT_BGR;
+
+    lfi::LensFile lensFile;
+    if(args["--lens-file"])
+    {
+        try
+        {
+            if(static_cast<std::string>(args["--lens-file"]).empty())
+                throw std::runtime_error("--lens-file needs the name of the calibration file to read.");
+            lensFile = lfi::lensCalibrationFromFile(static_cast<std::string>(args["--lens-file"]));
+        }
+        catch(const std::exception &e)
+        {
+            std::cerr << "--lens-file: " << e.what() << std::endl;
+            return EXIT_FAILURE;
+        }
+        nativeFlags |= lensFile.flags;
     }
 
     if(args["--native"] && args["-g"] && static_cast<int>(args["-g"]) > 1)
@@ -685,23 +734,26 @@ int main(int argc, char **argv)
             interpolator->setQuiltTile(tileGrid(static_cast<std::string>(args["--quilt-tile"]), "--quilt-tile", "WxH, the tile's width x height in pixels, both at least 1"));
         if(args["--native"])
         {
-            std::stringstream spec(static_cast<std::string>(args["--lens"]));
-            std::string token;
-            std::vector<double> numbers;
-            try
+            lfi::LensCalibration lens = lensFile.lens;
+            if(args["--lens"])
             {
-                while(std::getline(spec, token, ','))
-                    numbers.push_back(std::stod(token));
+                std::stringstream spec(static_cast<std::string>(args["--lens"]));
+                std::string token;
+                std::vector<double> numbers;
+                try
+                {
+                    while(std::getline(spec, token, ','))
+                        numbers.push_back(std::stod(token));
+                }
+                catch(const std::exception &)
+                {
+                    numbers.clear();
+                }
+                if(numbers.size() < 4 || numbers.size() > 5 || (numbers.size() == 5 && numbers[4] != 0.0 && numbers[4] != 1.0))
+                    throw std::runtime_error("--lens expects pitch,slope,center,dpi[,invert] with invert 0 or 1");
+                lens.pitch = numbers[0], lens.slope = numbers[1], lens.center = numbers[2], lens.dpi = numbers[3];
+                lens.invert = numbers.size() == 5 && numbers[4] == 1.0;
             }
-            catch(const std::exception &)
-            {
-                numbers.clear();
-            }
-            if(numbers.size() < 4 || numbers.size() > 5 || (numbers.size() == 5 && numbers[4] != 0.0 && numbers[4] != 1.0))
-                throw std::runtime_error("--lens expects pitch,slope,center,dpi[,invert] with invert 0 or 1");
-            lfi::LensCalibration lens;
-            lens.pitch = numbers[0], lens.slope = numbers[1], lens.center = numbers[2], lens.dpi = numbers[3];
-            lens.invert = numbers.size() == 5 && numbers[4] == 1.0;
             int views = 0;
             if(args["--native-views"])
             {
@@ -710,8 +762,12 @@ int main(int argc, char **argv)
                     throw std::runtime_error("--native-views expects the number of views to interlace, at least 1");
             }
             const char *size = "WxH, width x height in pixels, both at least 1";
-            interpolator->setNative(tileGrid(static_cast<std::string>(args["--native"]), "--native", size), lens,
-                                    args["--native-tile"] ? tileGrid(static_cast<std::string>(args["--native-tile"]), "--native-tile", size) : lfi::IVec2{0, 0}, views);
+            const lfi::IVec2 display = tileGrid(static_cast<std::string>(args["--native"]), "--native", size);
+            if((lensFile.screenW && lensFile.screenW != display.x) || (lensFile.screenH && lensFile.screenH != display.y))
+                std::cout << "Note: the calibration file describes a panel of " << lensFile.screenW << "x" << lensFile.screenH << " pixels, --native asks for "
+                          << display.x << "x" << display.y << "." << std::endl;
+            interpolator->setNative(display, lens, args["--native-tile"] ? tileGrid(static_cast<std::string>(args["--native-tile"]), "--native-tile", size) : lfi::IVec2{0, 0},
+                                    views, nativeFlags);
         }
         if(args["--y4m"])
             interpolator->setY4m(static_cast<std::string>(args["--y4m"]), fpsNum, fpsDen, yuvMatrix, yuvRange);

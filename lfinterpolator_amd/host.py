@@ -7,7 +7,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from .abi import LFI_LENT_INVERT, Lenticular, Mosaic, YuvSurfaces
+from .abi import LFI_LENT_BGR, LFI_LENT_INVERT, Lenticular, Mosaic, YuvSurfaces
 from .abi import mosaic_map as _abi_mosaic_map
 from .build import HOST_LIB
 
@@ -40,6 +40,10 @@ def load_host_library() -> C.CDLL:
         lib.lfi_host_area_span.argtypes = [C.c_int] * 3 + [C.c_void_p]
         lib.lfi_host_lenticular.restype = C.c_int
         lib.lfi_host_lenticular.argtypes = [C.c_double] * 4 + [C.c_int] * 4 + [C.POINTER(Lenticular), C.c_char_p, C.c_size_t]
+        lib.lfi_host_lenticular_json.restype = C.c_int
+        lib.lfi_host_lenticular_json.argtypes = [C.c_char_p] + [C.c_int] * 3 + [C.POINTER(Lenticular), C.c_void_p, C.c_char_p, C.c_size_t]
+        lib.lfi_host_native_taps.restype = C.c_int
+        lib.lfi_host_native_taps.argtypes = [C.c_int] * 3 + [C.c_void_p]
         lib.lfi_host_y4m_frame_bytes.restype = C.c_size_t
         lib.lfi_host_y4m_frame_bytes.argtypes = [C.c_int, C.c_int]
         lib.lfi_host_y4m_write.restype = C.c_int
@@ -183,6 +187,29 @@ def lenticular(pitch: float, slope: float, center: float, dpi: float, invert: bo
         raise ValueError(err.value.decode())
     assert lens.flags == (LFI_LENT_INVERT if invert else 0)
     return lens
+
+
+def lenticular_file(path, out_w: int, out_h: int, n: int, with_screen: bool = False):
+    """lenticular() from a display's calibration file (csrc/host/lenticular.h): a flat JSON object whose numeric entries are "name": x or
+    "name": {"value": x}; pitch, slope, center and DPI are the calibration, invView sets LFI_LENT_INVERT and flipSubp LFI_LENT_BGR in the
+    Lenticular's flags.  with_screen: returns (Lenticular, (screenW, screenH)) — the panel's size as the file states it, 0 where it does not.
+    ValueError, naming the key, for a file that cannot be read, a key without a number, a missing key and a mirrored panel (flipImageX / Y)."""
+    lens = Lenticular()
+    screen = np.zeros(2, dtype=np.int32)
+    err = C.create_string_buffer(512)
+    if load_host_library().lfi_host_lenticular_json(os.fsencode(path), out_w, out_h, n, C.byref(lens), screen.ctypes.data, err, len(err)) != 0:
+        raise ValueError(err.value.decode())
+    assert lens.flags & ~(LFI_LENT_INVERT | LFI_LENT_BGR) == 0
+    return (lens, (int(screen[0]), int(screen[1]))) if with_screen else lens
+
+
+def native_taps(src: int, dst: int, o: int):
+    """Output pixel o of Context.download_native's bilinear tile sampling (LFI_LENT_BILINEAR) along an axis of src tile and dst output pixels,
+    as (p0, p1, f): the two tile pixels and the weight of p1 in 1/256 (p0 weighs 256 − f) — the arithmetic the kernel runs (csrc/native_taps.h)."""
+    out = np.zeros(3, dtype=np.int32)
+    if load_host_library().lfi_host_native_taps(src, dst, o, out.ctypes.data) != 0:
+        raise ValueError("needs 1 <= src, dst <= 65535 and 0 <= o < dst")
+    return tuple(int(v) for v in out)
 
 
 def write_y4m(path: str, frames: np.ndarray, width: int, height: int, fps=(30, 1), full_range: bool = False, left_sited: bool = False, depth: int = 8) -> None:
