@@ -104,7 +104,40 @@ enum {
      * view layout; LFI_FLAG_TEN_ROUND_PER_BATCH; lfi_download_prequant; weights outside [0, 2); inputs or offsets the planar copy cannot serve
      * (an attached grid without lfi_grid_modified; after lfi_release_inputs, offsets beyond the copy's padding).
      * Out of scope: all-focus and per-view deep renders, deep quilts / native images / lfi_compare_view[s], a row window, 16-bit PNG. */
-    LFI_FLAG_DEEP_VIEWS = 64u
+    LFI_FLAG_DEEP_VIEWS = 64u,
+    /* IN-FRAME BLENDING: a fixed-focus render takes image g at pixel + focused_offsets[g] and, by default, clamps that position to the frame
+     * (the reference's surf2Dread(..., cudaBoundaryModeClamp), src/kernels.cu:119-126), which smears each image's edge column or row across a
+     * band as wide as its shift.  With this flag the samples that fall outside their image are LEFT OUT and the rest are scaled back to the
+     * full weight.  While it is set, lfi_render / lfi_prepare / lfi_benchmark with all_focus = 0 launch ONE kernel (csrc/hip/blend_inframe.hpp;
+     * lfi_last_kernel_name names it, lfi_set_variant choices do not apply) that defines view v, channel c, pixel (x, y) as follows - images
+     * g = 0 ... N-1 in ascending order, w_g the view's fp16 weight widened to fp32, (ox_g, oy_g) = focused_offsets[g]:
+     *      in_g  = 0 <= x + ox_g < W  and  0 <= y + oy_g < H
+     *      wall  = fp32 chain  wall <- wall + w_g            over all g
+     *      den   = fp32 chain  den  <- den  + w_g            over the g with in_g
+     *      num_c = the method's sum of w_g * px_g,c          over the g with in_g
+     *              STD:    the ordered chain num <- fmaf(px, w_g, num), the reference's (src/kernels.cu:292-299), skipping the others
+     *              TEN_WM: the fp32-accumulated matrix-core sum with the left-out samples as zeros
+     *      den == 0:  s_c = 0          (no image has the pixel in frame, or only zero weights do)
+     *      otherwise: r = wall / den   (IEEE fp32 division, round to nearest even),  s_c = num_c * r  (one fp32 multiplication, RN)
+     *      byte_c = STD: rn_even(s_c) & 0xff      TEN_WM: floor(min(fp16_RN(s_c), 255))   - the epilogues of the two methods
+     *  - Where every image has the pixel in frame, den is wall bit for bit, r = 1.0 and the byte is the flag-free render's: STD the reference's
+     *    byte, TEN_WM a byte under the TEN_WM contract.
+     *  - den, wall and r are the same bits under both methods: the vector pipe forms them in ascending g under both.  Only num carries the
+     *    matrix core's accumulation error (a denominator summed on the matrix cores would carry it too, and at den = 0.2 ... 1 the byte would
+     *    then be open to three and more values; with the deterministic den it is open to two at the most).
+     * The output is ordinary 8-bit views: downloads, YUV frames, quilts, native images, lfi_compare_view[s] and RGB-D work on them unchanged.
+     * Without the flag no byte and no launch changes.  A launch with the flag drops the deep views of an earlier deep render.
+     * Valid: fixed focus; LFI_LAYOUT_PLANAR_RGB; grids up to LFI_MAX_IMAGES images, any number of views, any view range; the kernel reads the
+     * derived planar copy of the inputs (lfi_prepare builds it: a prepared render is only a launch), so it also serves a context after
+     * lfi_release_inputs.
+     * LFI_EINVAL with a message that starts "LFI_FLAG_IN_FRAME is set: ", the context usable and nothing written or allocated, while the flag is
+     * set: all_focus = 1; lfi_render_stream and lfi_render_stream_yuv420; per-view rows (lfi_set_view_offsets, lfi_set_view_float_offsets); a
+     * row window; the RGBA view layout; LFI_FLAG_TEN_ROUND_PER_BATCH; LFI_FLAG_DEEP_VIEWS set together with it; lfi_download_prequant; weights
+     * outside [0, 2); inputs or offsets the planar copy cannot serve (an attached grid without lfi_grid_modified; after lfi_release_inputs,
+     * offsets beyond the copy's padding).
+     * Out of scope: all-focus and per-view in-frame renders, the RGBA layout, row windows (and the program's -g above 1), the streaming calls,
+     * deep in-frame views, a validity mask taken from the inputs' alpha. */
+    LFI_FLAG_IN_FRAME = 128u
 };
 
 #define LFI_MAX_IMAGES 256     /* MAX_IMAGES, src/kernels.cu:60 */

@@ -23,6 +23,7 @@
 #include "blend_vfocus.hpp"
 #include "blend_vfocus_af.hpp"
 #include "deep_blend.hpp"
+#include "blend_inframe.hpp"
 #include "lfi_band_probe.hpp"
 
 namespace {
@@ -50,6 +51,8 @@ enum class BlendKernel
     std_vfma,
     deep_ten, // deep_blend.hpp: LFI_FLAG_DEEP_VIEWS
     deep_std,
+    inframe_ten, // blend_inframe.hpp: LFI_FLAG_IN_FRAME
+    inframe_std,
 };
 
 // The generic kernels: plain fp32 epilogue, any weights, pre-quantisation dumps, per-batch rounding (TEN_WM).  They run one pixel grid
@@ -127,6 +130,9 @@ BlendRoute route_blend(const lfi_ctx *c, int method, bool all_focus, const Kerne
     // 0. deep views (LFI_FLAG_DEEP_VIEWS): one kernel for both methods; launch_blend (deep_views_ready) has refused what it does not serve
     if(c->flags & LFI_FLAG_DEEP_VIEWS)
         return {ten ? K::deep_ten : K::deep_std, nch, true, true};
+    // 0b. in-frame blending (LFI_FLAG_IN_FRAME): likewise; launch_blend (inframe_refused) has refused what it does not serve
+    if(c->flags & LFI_FLAG_IN_FRAME)
+        return {ten ? K::inframe_ten : K::inframe_std, nch, true, true};
     const bool fixed_copy = copy_ok && !all_focus;
     // wave-private pipelines (blend_wave.hpp) where they apply: fixed focus, one chunk of images, one view pass
     const bool wave_fits = !all_focus && a.k_pad <= 64 && a.v1 - a.v0 <= 64;
@@ -394,10 +400,34 @@ void launch_deep(const lfi_ctx *c, const KernelArgs &a_in, int nch, bool std_cha
         per_64_views(a_in, [&](const KernelArgs &a) { launch(a, 1); });
 }
 
+// blend_inframe: the byte planes of views [v0, v1), out-of-frame samples left out.  Launches as launch_deep does: one chunk of images — ONE
+// launch whose tiles serve every 64-view pass; several chunks — one launch per 64 views
+void launch_inframe(const lfi_ctx *c, const KernelArgs &a_in, int nch, bool std_chain)
+{
+    const int tiles_x = (a_in.width + lfi::P3_TPX - 1) / lfi::P3_TPX;
+    const int n_tiles = tiles_x * a_in.out_rows;
+    const dim3 grid(std::min(n_tiles, 2 * cu_count_of(c))), block(256);
+    // set here, as launch_deep sets its names: the render matrix of tests/test_gpu_dispatch_coverage.py knows no parameter flags; these
+    // launches are held to their names by tests/test_gpu_inframe.py
+    c->last_kernel = std_chain ? "blend_inframe<STD>" : "blend_inframe<TEN_WM>";
+    auto launch = [&](const KernelArgs &a, int passes) {
+        if(std_chain)
+            hipLaunchKernelGGL((lfi::blend_inframe<true>), grid, block, 0, stream_of(c), a, tiles_x, n_tiles, passes, nch);
+        else
+            hipLaunchKernelGGL((lfi::blend_inframe<false>), grid, block, 0, stream_of(c), a, tiles_x, n_tiles, passes, nch);
+    };
+    if(nch == 1)
+        launch(a_in, (a_in.v1 - a_in.v0 + 63) / 64);
+    else
+        per_64_views(a_in, [&](const KernelArgs &a) { launch(a, 1); });
+}
+
 void launch_route(const lfi_ctx *c, const KernelArgs &a, bool all_focus, const BlendRoute &r)
 {
     switch(r.kernel)
     {
+        case BlendKernel::inframe_ten: launch_inframe(c, a, r.nch, false); break;
+        case BlendKernel::inframe_std: launch_inframe(c, a, r.nch, true); break;
         case BlendKernel::deep_ten: launch_deep(c, a, r.nch, false); break;
         case BlendKernel::deep_std: launch_deep(c, a, r.nch, true); break;
         case BlendKernel::ten_m16: launch_ten_m16(c, a, all_focus); break;
@@ -782,9 +812,58 @@ int launch_deep_views(lfi_ctx *c, int method, int all_focus, const KernelArgs &a
     return LFI_OK;
 }
 
+// ---- in-frame blending (LFI_FLAG_IN_FRAME): blend_inframe.hpp ------------------------------------------------------------------------------
+
+const char *const kInFrameNoPrequant = "lfi_download_prequant is not supported";
+
+// What an in-frame render refuses, before anything is enqueued or allocated; every message names the flag
+int inframe_refused(lfi_ctx *c, int all_focus, const KernelArgs &a)
+{
+    const char *why = nullptr;
+    if(c->flags & LFI_FLAG_DEEP_VIEWS)
+        why = "LFI_FLAG_DEEP_VIEWS is not supported together with it (no deep in-frame views)";
+    else if(a.prequant)
+        why = kInFrameNoPrequant;
+    else if(all_focus)
+        why = "all-focus renders are not supported (fixed focus only)";
+    else if(c->view_offsets.set || c->view_float_offsets.set)
+        why = "per-view rows (lfi_set_view_offsets, lfi_set_view_float_offsets) are not supported - clear them with NULL";
+    else if(c->windowed)
+        why = "a row window (lfi_set_row_window) is not supported";
+    else if(c->out_layout != LFI_LAYOUT_PLANAR_RGB)
+        why = "the RGBA view layout is not supported - lfi_set_output_layout(LFI_LAYOUT_PLANAR_RGB)";
+    else if(c->flags & LFI_FLAG_TEN_ROUND_PER_BATCH)
+        why = "LFI_FLAG_TEN_ROUND_PER_BATCH is not supported";
+    else if(!c->weights_scalable)
+        why = "weights outside [0, 2) are not supported";
+    return why ? fail(c, LFI_EINVAL, std::string("LFI_FLAG_IN_FRAME is set: ") + why) : LFI_OK;
+}
+
+// lfi_render / lfi_benchmark while the flag is set: blend_inframe writes the byte planes of [v0, v1)
+int launch_inframe_views(lfi_ctx *c, int method, int all_focus, const KernelArgs &a_in)
+{
+    if(method != LFI_METHOD_STD && method != LFI_METHOD_TEN_WM) // the reference throws here (src/interpolator.cu:289-290)
+        return fail(c, LFI_EINVAL, "The specified interpolation method does not exist!");
+    if(int rc = inframe_refused(c, all_focus, a_in))
+        return rc;
+    if(int rc = join_uploads(c))
+        return rc;
+    if(!ensure_planar(c, tune_planar_now(c)))
+        return fail(c, LFI_EINVAL, "LFI_FLAG_IN_FRAME is set: the planar copy of the inputs cannot serve these offsets (inputs the library cannot track, "
+                                   "or, after lfi_release_inputs, offsets beyond the copy's padding)");
+    KernelArgs a = a_in;
+    set_planar_args(c, a);
+    drop_deep_range(c); // the views are written without their deep planes
+    launch_route(c, a, false, route_blend(c, method, false, a, true));
+    LFI_HIP(c, hipGetLastError());
+    return LFI_OK;
+}
+
 // Renders views [a_in.v0, a_in.v1) into a_in.views
 int launch_blend(lfi_ctx *c, int method, int all_focus, const KernelArgs &a_in)
 {
+    if(c->flags & LFI_FLAG_IN_FRAME) // (with LFI_FLAG_DEEP_VIEWS beside it: refused there)
+        return launch_inframe_views(c, method, all_focus, a_in);
     if(c->flags & LFI_FLAG_DEEP_VIEWS)
         return launch_deep_views(c, method, all_focus, a_in);
     if(int rc = join_uploads(c))

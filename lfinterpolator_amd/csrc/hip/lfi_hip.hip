@@ -1908,6 +1908,10 @@ int lfi_prepare(lfi_ctx *ctx, int method, int all_focus, int v0, int v1)
         return rc;
     const KernelArgs a = make_args(ctx, v0, v1, method);
     ctx->derived_build_ms = 0.0f;
+    const bool in_frame = ctx->flags & LFI_FLAG_IN_FRAME; // the copy below: an in-frame render is then only a launch
+    if(in_frame)
+        if(int rc = inframe_refused(ctx, all_focus, a))
+            return rc;
     const bool deep = ctx->flags & LFI_FLAG_DEEP_VIEWS; // the copy below, then the deep planes: the first deep render is then only a launch
     if(deep)
         if(int rc = deep_views_refused(ctx, all_focus, a))
@@ -2165,6 +2169,8 @@ int lfi_render_stream(lfi_ctx *ctx, int method, int all_focus, const uint16_t *w
         return fail(ctx, LFI_EINVAL, view_rows_set(rows) + "lfi_render_stream is not supported - clear them with NULL");
     if(ctx->flags & LFI_FLAG_DEEP_VIEWS)
         return fail(ctx, LFI_EINVAL, "LFI_FLAG_DEEP_VIEWS is set: lfi_render_stream is not supported");
+    if(ctx->flags & LFI_FLAG_IN_FRAME)
+        return fail(ctx, LFI_EINVAL, "LFI_FLAG_IN_FRAME is set: lfi_render_stream is not supported");
     if(!weights_fp16 || total_views < 1)
         return fail(ctx, LFI_EINVAL, "lfi_render_stream: weights are NULL or total_views < 1");
     if(host_out && (ctx->out_layout != LFI_LAYOUT_RGBA || pitch_bytes < (size_t)ctx->width * 4))
@@ -2181,6 +2187,8 @@ int lfi_render_stream_yuv420(lfi_ctx *ctx, int method, int all_focus, const uint
         return fail(ctx, LFI_EINVAL, view_rows_set(rows) + "lfi_render_stream_yuv420 is not supported - clear them with NULL");
     if(ctx->flags & LFI_FLAG_DEEP_VIEWS)
         return fail(ctx, LFI_EINVAL, "LFI_FLAG_DEEP_VIEWS is set: lfi_render_stream_yuv420 is not supported");
+    if(ctx->flags & LFI_FLAG_IN_FRAME)
+        return fail(ctx, LFI_EINVAL, "LFI_FLAG_IN_FRAME is set: lfi_render_stream_yuv420 is not supported");
     if(!weights_fp16 || total_views < 1)
         return fail(ctx, LFI_EINVAL, "lfi_render_stream_yuv420: weights are NULL or total_views < 1");
     YuvSink sink{};
@@ -2535,7 +2543,13 @@ int lfi_benchmark(lfi_ctx *ctx, int method, int all_focus, int v0, int v1, int w
     const KernelArgs a = make_args(ctx, v0, v1, method);
     // the derived input copy is (re)built here, not inside the first timed launch — and so are the deep planes allocated (LFI_FLAG_DEEP_VIEWS)
     bool planar = false;
-    if(ctx->flags & LFI_FLAG_DEEP_VIEWS)
+    if(ctx->flags & LFI_FLAG_IN_FRAME)
+    {
+        if(int rc = inframe_refused(ctx, all_focus, a))
+            return rc;
+        (void)ensure_planar(ctx, true);
+    }
+    else if(ctx->flags & LFI_FLAG_DEEP_VIEWS)
     {
         if(int rc = deep_views_refused(ctx, all_focus, a))
             return rc;
@@ -3085,6 +3099,8 @@ int lfi_download_prequant(lfi_ctx *ctx, int method, int all_focus, int v, float 
         return rc;
     const size_t bytes = sizeof(float) * 3 * (size_t)ctx->width * ctx->height;
     KernelArgs a = make_args(ctx, v, v + 1, method);
+    if(ctx->flags & LFI_FLAG_IN_FRAME) // refused by name before anything is reserved
+        return fail(ctx, LFI_EINVAL, std::string("LFI_FLAG_IN_FRAME is set: ") + kInFrameNoPrequant);
     if(ctx->flags & LFI_FLAG_DEEP_VIEWS) // refused by name before anything is reserved
         return fail(ctx, LFI_EINVAL, std::string("LFI_FLAG_DEEP_VIEWS is set: ") + kDeepNoPrequant);
     LFI_HIP(ctx, ctx->prequant.reserve(bytes));

@@ -101,6 +101,9 @@ class Interpolator
         // --y4m at 10 bits) are then converted from them (LFI_YUV_DEEP), and setGbrp10 stores them as raw gbrp10le planes
         void setDeep(bool on) { deep = on; }
         void setGbrp10(std::string path) { gbrp10Path = path; }
+        // in-frame edges (LFI_FLAG_IN_FRAME): fixed-focus renders leave out the samples that fall outside their image and scale the rest back to
+        // the full weight, instead of clamping them to the image's edge; every output is then made of those views by the same calls
+        void setInFrame(bool on) { inFrame = on; }
         // 10 where the input is a light-field video whose files say C420p10 (they are uploaded as I010 frames: lfi_upload_images_yuv), else 8
         int inputDepth() const;
         // also write the quilt of setQuilt (scaled by setQuiltTile) as ONE frame of a Y4M video file: resized and converted to 8-bit YUV 4:2:0
@@ -227,6 +230,7 @@ class Interpolator
         std::ofstream p010File;                    // open from the first stored step to finish()
         int yuvDepth{8};                           // setYuvDepth
         bool deep{false};                          // setDeep
+        bool inFrame{false};                       // setInFrame
         std::string gbrp10Path;                    // empty: no raw gbrp10le file
         std::ofstream gbrp10File;                  // open from the first stored step to finish()
         std::string quiltY4mPath;                  // empty: no quilt video
