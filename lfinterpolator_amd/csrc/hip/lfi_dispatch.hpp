@@ -127,10 +127,10 @@ BlendRoute route_blend(const lfi_ctx *c, int method, bool all_focus, const Kerne
     const bool ten = method == LFI_METHOD_TEN_WM, planar_views = c->out_layout == LFI_LAYOUT_PLANAR_RGB;
     const K first = ten ? kTenVariants[c->ten_variant].first : kStdVariants[c->std_variant].first;
     const int nch = (a.k_pad + lfi::P3_KC - 1) / lfi::P3_KC;
-    // 0. deep views (LFI_FLAG_DEEP_VIEWS): one kernel for both methods; launch_blend (deep_views_ready) has refused what it does not serve
+    // 0. deep views (LFI_FLAG_DEEP_VIEWS): one kernel for both methods; launch_blend (flagged_refused) has refused what it does not serve
     if(c->flags & LFI_FLAG_DEEP_VIEWS)
         return {ten ? K::deep_ten : K::deep_std, nch, true, true};
-    // 0b. in-frame blending (LFI_FLAG_IN_FRAME): likewise; launch_blend (inframe_refused) has refused what it does not serve
+    // 0b. in-frame blending (LFI_FLAG_IN_FRAME): likewise; launch_blend (flagged_refused) has refused what it does not serve
     if(c->flags & LFI_FLAG_IN_FRAME)
         return {ten ? K::inframe_ten : K::inframe_std, nch, true, true};
     const bool fixed_copy = copy_ok && !all_focus;
@@ -377,44 +377,28 @@ void launch_afs(const lfi_ctx *c, const KernelArgs &a_in, const BlendRoute &r)
 
 void launch_p3(const lfi_ctx *c, const KernelArgs &a_in, int nch, bool rgba_out);
 
-// deep_blend: the byte planes and the deep planes of views [v0, v1).  One chunk of images: ONE launch whose tiles serve every 64-view pass
-// from the same LDS-resident pixels; several chunks: one launch per 64 views
-void launch_deep(const lfi_ctx *c, const KernelArgs &a_in, int nch, bool std_chain)
+// deep_blend (deep: the byte planes and the deep planes) or blend_inframe (the byte planes, out-of-frame samples left out) for views
+// [v0, v1).  One chunk of images: ONE launch whose tiles serve every 64-view pass from the same LDS-resident pixels; several chunks: one
+// launch per 64 views
+void launch_tile16(const lfi_ctx *c, const KernelArgs &a_in, int nch, bool deep, bool std_chain)
 {
     const int tiles_x = (a_in.width + lfi::P3_TPX - 1) / lfi::P3_TPX;
     const int n_tiles = tiles_x * a_in.out_rows;
     const dim3 grid(std::min(n_tiles, 2 * cu_count_of(c))), block(256);
     // what lfi_last_kernel_name reports.  Set here, not through the helper the other launchers use: tests/test_gpu_dispatch_coverage.py holds every
-    // name that goes through it to a row of its render matrix, which knows no parameter flags; the deep launches are held to these names by
-    // tests/test_gpu_deep.py
-    c->last_kernel = std_chain ? "deep_blend<STD>" : "deep_blend<TEN_WM>";
+    // name that goes through it to a row of its render matrix, which knows no parameter flags; these launches are held to their names by
+    // tests/test_gpu_deep.py and tests/test_gpu_inframe.py
+    c->last_kernel = deep ? (std_chain ? "deep_blend<STD>" : "deep_blend<TEN_WM>") : (std_chain ? "blend_inframe<STD>" : "blend_inframe<TEN_WM>");
     auto launch = [&](const KernelArgs &a, int passes) {
-        if(std_chain)
-            hipLaunchKernelGGL((lfi::deep_blend<true>), grid, block, 0, stream_of(c), a, c->deep.get(), deep_pitch(c), tiles_x, n_tiles, passes, nch);
+        auto go = [&](auto kernel, auto... extra) { hipLaunchKernelGGL(kernel, grid, block, 0, stream_of(c), a, extra..., tiles_x, n_tiles, passes, nch); };
+        if(deep && std_chain)
+            go(lfi::deep_blend<true>, c->deep.get(), deep_pitch(c));
+        else if(deep)
+            go(lfi::deep_blend<false>, c->deep.get(), deep_pitch(c));
+        else if(std_chain)
+            go(lfi::blend_inframe<true>);
         else
-            hipLaunchKernelGGL((lfi::deep_blend<false>), grid, block, 0, stream_of(c), a, c->deep.get(), deep_pitch(c), tiles_x, n_tiles, passes, nch);
-    };
-    if(nch == 1)
-        launch(a_in, (a_in.v1 - a_in.v0 + 63) / 64);
-    else
-        per_64_views(a_in, [&](const KernelArgs &a) { launch(a, 1); });
-}
-
-// blend_inframe: the byte planes of views [v0, v1), out-of-frame samples left out.  Launches as launch_deep does: one chunk of images — ONE
-// launch whose tiles serve every 64-view pass; several chunks — one launch per 64 views
-void launch_inframe(const lfi_ctx *c, const KernelArgs &a_in, int nch, bool std_chain)
-{
-    const int tiles_x = (a_in.width + lfi::P3_TPX - 1) / lfi::P3_TPX;
-    const int n_tiles = tiles_x * a_in.out_rows;
-    const dim3 grid(std::min(n_tiles, 2 * cu_count_of(c))), block(256);
-    // set here, as launch_deep sets its names: the render matrix of tests/test_gpu_dispatch_coverage.py knows no parameter flags; these
-    // launches are held to their names by tests/test_gpu_inframe.py
-    c->last_kernel = std_chain ? "blend_inframe<STD>" : "blend_inframe<TEN_WM>";
-    auto launch = [&](const KernelArgs &a, int passes) {
-        if(std_chain)
-            hipLaunchKernelGGL((lfi::blend_inframe<true>), grid, block, 0, stream_of(c), a, tiles_x, n_tiles, passes, nch);
-        else
-            hipLaunchKernelGGL((lfi::blend_inframe<false>), grid, block, 0, stream_of(c), a, tiles_x, n_tiles, passes, nch);
+            go(lfi::blend_inframe<false>);
     };
     if(nch == 1)
         launch(a_in, (a_in.v1 - a_in.v0 + 63) / 64);
@@ -426,10 +410,10 @@ void launch_route(const lfi_ctx *c, const KernelArgs &a, bool all_focus, const B
 {
     switch(r.kernel)
     {
-        case BlendKernel::inframe_ten: launch_inframe(c, a, r.nch, false); break;
-        case BlendKernel::inframe_std: launch_inframe(c, a, r.nch, true); break;
-        case BlendKernel::deep_ten: launch_deep(c, a, r.nch, false); break;
-        case BlendKernel::deep_std: launch_deep(c, a, r.nch, true); break;
+        case BlendKernel::inframe_ten: launch_tile16(c, a, r.nch, false, false); break;
+        case BlendKernel::inframe_std: launch_tile16(c, a, r.nch, false, true); break;
+        case BlendKernel::deep_ten: launch_tile16(c, a, r.nch, true, false); break;
+        case BlendKernel::deep_std: launch_tile16(c, a, r.nch, true, true); break;
         case BlendKernel::ten_m16: launch_ten_m16(c, a, all_focus); break;
         case BlendKernel::ten_direct: launch_ten_direct(c, a, all_focus); break;
         case BlendKernel::p3: launch_p3(c, a, r.nch, false); break;
@@ -752,16 +736,21 @@ bool allfocus_rows_held(const lfi_ctx *c, const lfi_float2 *o, size_t n)
     return true;
 }
 
-// ---- deep views (LFI_FLAG_DEEP_VIEWS): deep_blend.hpp --------------------------------------------------------------------------------------
+// ---- the flagged fixed-focus renders: deep views (LFI_FLAG_DEEP_VIEWS, deep_blend.hpp), in-frame blending (LFI_FLAG_IN_FRAME, blend_inframe.hpp) --
 
 const char *const kDeepNoPrequant = "lfi_download_prequant is not supported (the deep planes ARE the accumulator's ten bits)";
+const char *const kInFrameNoPrequant = "lfi_download_prequant is not supported";
 
-// What a deep render refuses, before anything is enqueued or allocated; every message names the flag
-int deep_views_refused(lfi_ctx *c, int all_focus, const KernelArgs &a)
+// What a render under `flag` (LFI_FLAG_DEEP_VIEWS or LFI_FLAG_IN_FRAME) refuses, before anything is enqueued or allocated; every message names
+// the flag
+int flagged_refused(lfi_ctx *c, unsigned flag, int all_focus, const KernelArgs &a)
 {
+    const bool deep = flag == LFI_FLAG_DEEP_VIEWS;
     const char *why = nullptr;
-    if(a.prequant)
-        why = kDeepNoPrequant;
+    if(!deep && (c->flags & LFI_FLAG_DEEP_VIEWS))
+        why = "LFI_FLAG_DEEP_VIEWS is not supported together with it (no deep in-frame views)";
+    else if(a.prequant)
+        why = deep ? kDeepNoPrequant : kInFrameNoPrequant;
     else if(all_focus)
         why = "all-focus renders are not supported (fixed focus only)";
     else if(c->view_offsets.set || c->view_float_offsets.set)
@@ -774,7 +763,7 @@ int deep_views_refused(lfi_ctx *c, int all_focus, const KernelArgs &a)
         why = "LFI_FLAG_TEN_ROUND_PER_BATCH is not supported";
     else if(!c->weights_scalable)
         why = "weights outside [0, 2) are not supported";
-    return why ? fail(c, LFI_EINVAL, std::string("LFI_FLAG_DEEP_VIEWS is set: ") + why) : LFI_OK;
+    return why ? fail(c, LFI_EINVAL, std::string(deep ? "LFI_FLAG_DEEP_VIEWS" : "LFI_FLAG_IN_FRAME") + " is set: " + why) : LFI_OK;
 }
 
 // the deep planes of all views_n views; a first use (or a new size) allocates, which may block
@@ -789,73 +778,31 @@ int ensure_deep_planes(lfi_ctx *c)
     return LFI_OK;
 }
 
-// lfi_render / lfi_prepare's build / lfi_benchmark while the flag is set: deep_blend writes the byte planes and the deep planes of [v0, v1)
-int launch_deep_views(lfi_ctx *c, int method, int all_focus, const KernelArgs &a_in)
+// lfi_render / lfi_prepare's build / lfi_benchmark while `flag` is set: deep_blend writes the byte planes and the deep planes of [v0, v1),
+// blend_inframe the byte planes.  The order of the steps decides what is allocated or dropped before a refusal
+int launch_flagged_views(lfi_ctx *c, unsigned flag, int method, int all_focus, const KernelArgs &a_in)
 {
+    const bool deep = flag == LFI_FLAG_DEEP_VIEWS;
     if(method != LFI_METHOD_STD && method != LFI_METHOD_TEN_WM) // the reference throws here (src/interpolator.cu:289-290)
         return fail(c, LFI_EINVAL, "The specified interpolation method does not exist!");
-    if(int rc = deep_views_refused(c, all_focus, a_in))
+    if(int rc = flagged_refused(c, flag, all_focus, a_in))
         return rc;
     if(int rc = join_uploads(c))
         return rc;
     if(!ensure_planar(c, tune_planar_now(c)))
-        return fail(c, LFI_EINVAL, "LFI_FLAG_DEEP_VIEWS is set: the planar copy of the inputs cannot serve these offsets (inputs the library cannot track, "
-                                   "or, after lfi_release_inputs, offsets beyond the copy's padding)");
-    if(int rc = ensure_deep_planes(c))
-        return rc;
+        return fail(c, LFI_EINVAL, std::string(deep ? "LFI_FLAG_DEEP_VIEWS" : "LFI_FLAG_IN_FRAME") +
+                                       " is set: the planar copy of the inputs cannot serve these offsets (inputs the library cannot track, "
+                                       "or, after lfi_release_inputs, offsets beyond the copy's padding)");
+    if(deep)
+        if(int rc = ensure_deep_planes(c))
+            return rc;
     KernelArgs a = a_in;
     set_planar_args(c, a);
-    drop_deep_range(c);
+    drop_deep_range(c); // in-frame: the views are written without their deep planes
     launch_route(c, a, false, route_blend(c, method, false, a, true));
     LFI_HIP(c, hipGetLastError());
-    c->deep_v0 = a.v0, c->deep_v1 = a.v1;
-    return LFI_OK;
-}
-
-// ---- in-frame blending (LFI_FLAG_IN_FRAME): blend_inframe.hpp ------------------------------------------------------------------------------
-
-const char *const kInFrameNoPrequant = "lfi_download_prequant is not supported";
-
-// What an in-frame render refuses, before anything is enqueued or allocated; every message names the flag
-int inframe_refused(lfi_ctx *c, int all_focus, const KernelArgs &a)
-{
-    const char *why = nullptr;
-    if(c->flags & LFI_FLAG_DEEP_VIEWS)
-        why = "LFI_FLAG_DEEP_VIEWS is not supported together with it (no deep in-frame views)";
-    else if(a.prequant)
-        why = kInFrameNoPrequant;
-    else if(all_focus)
-        why = "all-focus renders are not supported (fixed focus only)";
-    else if(c->view_offsets.set || c->view_float_offsets.set)
-        why = "per-view rows (lfi_set_view_offsets, lfi_set_view_float_offsets) are not supported - clear them with NULL";
-    else if(c->windowed)
-        why = "a row window (lfi_set_row_window) is not supported";
-    else if(c->out_layout != LFI_LAYOUT_PLANAR_RGB)
-        why = "the RGBA view layout is not supported - lfi_set_output_layout(LFI_LAYOUT_PLANAR_RGB)";
-    else if(c->flags & LFI_FLAG_TEN_ROUND_PER_BATCH)
-        why = "LFI_FLAG_TEN_ROUND_PER_BATCH is not supported";
-    else if(!c->weights_scalable)
-        why = "weights outside [0, 2) are not supported";
-    return why ? fail(c, LFI_EINVAL, std::string("LFI_FLAG_IN_FRAME is set: ") + why) : LFI_OK;
-}
-
-// lfi_render / lfi_benchmark while the flag is set: blend_inframe writes the byte planes of [v0, v1)
-int launch_inframe_views(lfi_ctx *c, int method, int all_focus, const KernelArgs &a_in)
-{
-    if(method != LFI_METHOD_STD && method != LFI_METHOD_TEN_WM) // the reference throws here (src/interpolator.cu:289-290)
-        return fail(c, LFI_EINVAL, "The specified interpolation method does not exist!");
-    if(int rc = inframe_refused(c, all_focus, a_in))
-        return rc;
-    if(int rc = join_uploads(c))
-        return rc;
-    if(!ensure_planar(c, tune_planar_now(c)))
-        return fail(c, LFI_EINVAL, "LFI_FLAG_IN_FRAME is set: the planar copy of the inputs cannot serve these offsets (inputs the library cannot track, "
-                                   "or, after lfi_release_inputs, offsets beyond the copy's padding)");
-    KernelArgs a = a_in;
-    set_planar_args(c, a);
-    drop_deep_range(c); // the views are written without their deep planes
-    launch_route(c, a, false, route_blend(c, method, false, a, true));
-    LFI_HIP(c, hipGetLastError());
+    if(deep)
+        c->deep_v0 = a.v0, c->deep_v1 = a.v1;
     return LFI_OK;
 }
 
@@ -863,9 +810,9 @@ int launch_inframe_views(lfi_ctx *c, int method, int all_focus, const KernelArgs
 int launch_blend(lfi_ctx *c, int method, int all_focus, const KernelArgs &a_in)
 {
     if(c->flags & LFI_FLAG_IN_FRAME) // (with LFI_FLAG_DEEP_VIEWS beside it: refused there)
-        return launch_inframe_views(c, method, all_focus, a_in);
+        return launch_flagged_views(c, LFI_FLAG_IN_FRAME, method, all_focus, a_in);
     if(c->flags & LFI_FLAG_DEEP_VIEWS)
-        return launch_deep_views(c, method, all_focus, a_in);
+        return launch_flagged_views(c, LFI_FLAG_DEEP_VIEWS, method, all_focus, a_in);
     if(int rc = join_uploads(c))
         return rc;
     if(const ViewRowsKind k = view_rows_of(c, all_focus))

@@ -1910,11 +1910,11 @@ int lfi_prepare(lfi_ctx *ctx, int method, int all_focus, int v0, int v1)
     ctx->derived_build_ms = 0.0f;
     const bool in_frame = ctx->flags & LFI_FLAG_IN_FRAME; // the copy below: an in-frame render is then only a launch
     if(in_frame)
-        if(int rc = inframe_refused(ctx, all_focus, a))
+        if(int rc = flagged_refused(ctx, LFI_FLAG_IN_FRAME, all_focus, a))
             return rc;
     const bool deep = ctx->flags & LFI_FLAG_DEEP_VIEWS; // the copy below, then the deep planes: the first deep render is then only a launch
     if(deep)
-        if(int rc = deep_views_refused(ctx, all_focus, a))
+        if(int rc = flagged_refused(ctx, LFI_FLAG_DEEP_VIEWS, all_focus, a))
             return rc;
     const ViewRowsKind rows = view_rows_of(ctx, all_focus);
     bool planar = false;
@@ -2545,13 +2545,13 @@ int lfi_benchmark(lfi_ctx *ctx, int method, int all_focus, int v0, int v1, int w
     bool planar = false;
     if(ctx->flags & LFI_FLAG_IN_FRAME)
     {
-        if(int rc = inframe_refused(ctx, all_focus, a))
+        if(int rc = flagged_refused(ctx, LFI_FLAG_IN_FRAME, all_focus, a))
             return rc;
         (void)ensure_planar(ctx, true);
     }
     else if(ctx->flags & LFI_FLAG_DEEP_VIEWS)
     {
-        if(int rc = deep_views_refused(ctx, all_focus, a))
+        if(int rc = flagged_refused(ctx, LFI_FLAG_DEEP_VIEWS, all_focus, a))
             return rc;
         (void)ensure_planar(ctx, true);
         if(int rc = ensure_deep_planes(ctx))

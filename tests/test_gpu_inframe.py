@@ -192,6 +192,29 @@ def test_a_prepared_render_is_only_a_launch_and_benchmark_reports_the_kernel(gpu
     ctx.close()
 
 
+@pytest.mark.parametrize("method", ["STD", "TEN_WM"])
+@pytest.mark.parametrize("cols,rows,w,h", [
+    (8, 8, 130, 5),   # one chunk of images: 70 views are two view passes of ONE launch; a ragged second tile
+    (9, 8, 64, 5),    # two chunks: one launch per 64 views; a tile half as wide as the kernels'
+], ids=["g8x8_130x5", "g9x8_64x5"])
+def test_offsets_zero_give_the_deep_renders_bytes(cols, rows, w, h, method, gpu):
+    """every offset zero: every tile is interior, and blend_inframe and deep_blend come to the byte through the same shared loops
+    (csrc/hip/blend_tile16.hpp) but each by its own epilogue — TEN_WM floor(min(512·h, 255)) here, floor(4·h) >> 2 there; STD quant_rn of
+    the same chain in both.  The byte planes are equal"""
+    case = (f"g{cols}x{rows}_{w}x{h}_zero", cols, rows, w, h, 70, np.zeros((cols * rows, 2), np.int32))
+    hp = L.build_params(cols, rows, w, h, "0.1,0.2,0.9,0.7", 0.0, 0.0, 3.0, 1.783, 70)
+    hp = L.host.HostParams(case[6], hp.offsets, hp.weights, hp.focus_map_ids, hp.focus, hp.range, hp.block_radius)
+    got = {}
+    for flag, name in ((FLAG, NAME[method]), (L.LFI_FLAG_DEEP_VIEWS, f"deep_blend<{method}>")):
+        ctx, _ = _context(gpu, case, hp=hp, flags=flag)
+        poison.render(ctx, method)
+        assert ctx.last_kernel_name() == name
+        got[flag] = ctx.download_views()
+        ctx.close()
+    assert got[FLAG].shape[0] == 70 and (got[FLAG][..., 3] == 255).all()
+    assert (got[FLAG] == got[L.LFI_FLAG_DEEP_VIEWS]).all(), int((got[FLAG] != got[L.LFI_FLAG_DEEP_VIEWS]).sum())
+
+
 # ---- the flag comes and goes ----------------------------------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("method", ["STD", "TEN_WM"])

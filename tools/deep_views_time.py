@@ -36,6 +36,7 @@ if len(sys.argv) > 2 and sys.argv[1] == "--kernels":
                           "min_ms": round(min(ms), 4), "max_ms": round(max(ms), 4)}), flush=True)
     sys.exit(0)
 
+import _ablib  # noqa: F401  (LFI_AB_LIB: another build's library, one process per library)
 import lfinterpolator_amd as L
 
 CASES = {

@@ -16,6 +16,7 @@ import sys
 sys.path.insert(0, ".")
 import numpy as np
 
+import _ablib  # noqa: F401  (LFI_AB_LIB: another build's library, one process per library)
 import lfinterpolator_amd as L
 
 CASES = {
