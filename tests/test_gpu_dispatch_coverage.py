@@ -288,24 +288,27 @@ def ten_row_interval(oc, row, hp, lf, m, threads=THREADS):
     return S, eps, lo, hi
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("row", MATRIX, ids=lambda r: r.name)
-def test_dispatch_row(row, gpu, oracle_c):
-    cu = _cu_count()
-    H = _height(row, cu)
-    W = row.W
-    if row.persistent:
-        tiles = (W + row.persistent - 1) // row.persistent * H
-        assert tiles > 2 * cu, (tiles, cu)
-    hp, lf, m = row_inputs(gpu, oracle_c, row, H)
-    ctx = gpu.Context(0)
-    ctx.set_grid(row.cols, row.rows, W, H)
+XCD_FIRST_FOCUS = 0.6   # order == "xcd": the focus the planar copy is built and tuned for before the row's own parameters are set
+
+
+def xcd_first_params(L, row, H):
+    """order == "xcd": the parameters of the focus sweep's first step (a larger focus than the row's own)."""
+    return L.build_params(row.cols, row.rows, row.W, H, "0.071,0.071,0.93,0.93", XCD_FIRST_FOCUS, 0.0, 3.0, 1.783, row.V)
+
+
+def row_context(L, row, hp, lf, m, H, window=None):
+    """A fresh context set up for the row at image height H, ready to render; window = (out_y0, out_y1, in_y0, in_y1): a row window
+    (lfi_set_row_window) set before the upload, so that only the held rows of the whole-image arrays are copied."""
+    ctx = L.Context(0)
+    ctx.set_grid(row.cols, row.rows, row.W, H)
+    if window is not None:
+        ctx.set_row_window(*window)
     ctx.upload_grid(lf)
     ctx.set_output_layout(row.layout)
     if row.order == "xcd":
         # the planar copy built and tuned for a larger focus; then a focus sweep's next step: smaller offsets (the copy still covers
         # them), no re-tune — unless every image's integer offset moved by a multiple of 128 pixels, the phases no longer fit
-        hp_first = gpu.build_params(row.cols, row.rows, W, H, "0.071,0.071,0.93,0.93", 0.6, 0.0, 3.0, 1.783, row.V)
+        hp_first = xcd_first_params(L, row, H)
         ctx.set_params(hp_first, row.flags)
         ctx.prepare(row.method)
         assert ((hp.focused_offsets[:, 0] - hp_first.focused_offsets[:, 0]) % 128 != 0).any()
@@ -317,35 +320,61 @@ def test_dispatch_row(row, gpu, oracle_c):
     if row.all_focus:
         ctx.upload_map(0, m)
         ctx.upload_map(1, m)
+    return ctx
+
+
+def row_expected(oc, row, hp, lf, m):
+    """The oracle's views [v0, v1) of the row, the LSB tolerance against them, and for TEN_WM outside the per-batch debug mode (M16 byte
+    for byte, by design not the exact sum's bytes) the interval of the exact sum: S, eps, lo, hi (else four times None)."""
     kw = dict(v0=row.v0, v1=row.v1, threads=THREADS, all_focus=row.all_focus, map_plane=m, focus=hp.focus, rng=hp.range)
     if row.method == "STD":
-        want, tol = oracle_c.blend_std(lf, hp.focused_offsets, hp.offsets, hp.weights, **kw), 0
+        want, tol = oc.blend_std(lf, hp.focused_offsets, hp.offsets, hp.weights, **kw), 0
     else:
-        want = oracle_c.blend_ten(lf, hp.focused_offsets, hp.offsets, hp.weights, model=oracle_c.TEN_M16, **kw)
+        want = oc.blend_ten(lf, hp.focused_offsets, hp.offsets, hp.weights, model=oc.TEN_M16, **kw)
         tol = 0 if row.flags & ROUND else TEN_TOL_LSB
-    # TEN_WM outside the per-batch debug mode (M16 byte for byte, by design not the exact sum's bytes): the interval of the exact sum
     S = eps = lo = hi = None
     if row.method == "TEN_WM" and not row.flags & ROUND:
-        S, eps, lo, hi = (a[row.v0:row.v1] for a in ten_row_interval(oracle_c, row, hp, lf, m))
-    outside = None if row.V <= 80 else [0, row.v0 - 1, row.v1, row.V - 1]
+        S, eps, lo, hi = (a[row.v0:row.v1] for a in ten_row_interval(oc, row, hp, lf, m))
+    return want[row.v0:row.v1], tol, S, eps, lo, hi
 
-    def paths():
-        # the row's fresh context after its first render, before any download (which may allocate a staging plane)
-        mi = ctx.memory_info()
-        got = {"reads_copy": mi.derived_bytes > 0, "scratch": mi.workspace_bytes > 0}
-        assert got == {"reads_copy": row.reads_copy, "scratch": row.scratch}, (row.name, got)
+
+def check_paths(ctx, row):
+    """The row's fresh context after its first render, before any download (which may allocate a staging plane)."""
+    mi = ctx.memory_info()
+    got = {"reads_copy": mi.derived_bytes > 0, "scratch": mi.workspace_bytes > 0}
+    assert got == {"reads_copy": row.reads_copy, "scratch": row.scratch}, (row.name, got)
+
+
+def check_rendered(row, tag, byte, got, want, tol, S, eps, lo, hi):
+    """Views [v0, v1) as downloaded (or a band of their rows) against row_expected's (the same rows): the table's contract."""
+    bad = poison.mismatch(got, want, tol)
+    assert bad == 0, (row.name, tag, hex(byte), bad)
+    if lo is not None:
+        out = ten_interval.outside(got, lo, hi)
+        differ = int((got[..., :3] != ten_interval.quantise(S)).sum())
+        print(f"TEN_INTERVAL {row.name}{tag} {row.expect} {hex(byte)} bytes={lo.size} differ_from_exact={differ} outside={out}")
+        assert out == 0, (row.name, tag, hex(byte), out, "needed multiples of eps, largest:", float(ten_interval.report(got, S, eps).max()))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("row", MATRIX, ids=lambda r: r.name)
+def test_dispatch_row(row, gpu, oracle_c):
+    cu = _cu_count()
+    H = _height(row, cu)
+    W = row.W
+    if row.persistent:
+        tiles = (W + row.persistent - 1) // row.persistent * H
+        assert tiles > 2 * cu, (tiles, cu)
+    hp, lf, m = row_inputs(gpu, oracle_c, row, H)
+    ctx = row_context(gpu, row, hp, lf, m, H)
+    want, tol, S, eps, lo, hi = row_expected(oracle_c, row, hp, lf, m)
+    outside = None if row.V <= 80 else [0, row.v0 - 1, row.v1, row.V - 1]
 
     def check(byte):
         got = poison.render_range(ctx, row.method, row.v0, row.v1, all_focus=row.all_focus, byte=byte, outside=outside,
-                                  inspect=paths if byte == poison.POISON[0] else None)
+                                  inspect=(lambda: check_paths(ctx, row)) if byte == poison.POISON[0] else None)
         assert ctx.last_kernel_name() == row.expect, (row.name, ctx.last_kernel_name())
-        bad = poison.mismatch(got, want[row.v0:row.v1], tol)
-        assert bad == 0, (row.name, hex(byte), bad)
-        if lo is not None:
-            out = ten_interval.outside(got, lo, hi)
-            differ = int((got[..., :3] != ten_interval.quantise(S)).sum())
-            print(f"TEN_INTERVAL {row.name} {row.expect} {hex(byte)} bytes={lo.size} differ_from_exact={differ} outside={out}")
-            assert out == 0, (row.name, hex(byte), out, "needed multiples of eps, largest:", float(ten_interval.report(got, S, eps).max()))
+        check_rendered(row, "", byte, got, want, tol, S, eps, lo, hi)
     poison.twice(check)
     ctx.close()
 
