@@ -797,9 +797,16 @@ void free_grid(lfi_ctx *c)
     c->prequant.release();
     c->focus_ws.release();
     c->pad_version = 0;
+    // the geometry the released planes had goes with them: left in place, the next grid's planes "grow" from it (a quarter more padding than
+    // asked for, or the old grid's larger reach) and a reused context allocates more than a fresh one
+    c->pad_shift[0] = c->pad_shift[1] = c->pad_radius[0] = c->pad_radius[1] = 0;
+    c->pad_ids.clear();
     c->curve_ws.release();
     c->planar.release();
     c->planar_version = 0;
+    c->planar_pitch = c->planar_padx = c->planar_reach = 0;
+    c->planar_phase.clear();
+    c->launches_with_offsets = 0;
     c->d_planar_phase.release();
     c->phase_ring.release();
     c->yuv_in.release();

@@ -86,23 +86,28 @@ class Shadow:
     layout: str = "rgba"
     siting: str = "centre"     # lfi_set_yuv_siting's in_siting
     released: bool = False
+    views: int = VIEWS         # lfi_params.views (tests/context_reuse.py takes a context from one view count to another)
+    wide: bool = False         # the weight column of image N // 2 is 2.5: outside [0, 2), weights_scalable is false
 
     def params(self, L):
         s = self.shape
-        hp = L.build_params(s.cols, s.rows, s.W, s.H, TRAJ, self.focus, self.rng, EFFECT, ASPECT, VIEWS)
+        hp = L.build_params(s.cols, s.rows, s.W, s.H, TRAJ, self.focus, self.rng, EFFECT, ASPECT, self.views)
         if s.ids:
             hp.focus_map_ids = hp.focus_map_ids[:s.ids].copy()
+        if self.wide:
+            hp.weights = hp.weights.copy()
+            hp.weights[:, s.n // 2] = 0x4100     # fp16 2.5
         if self.radius is not None:
             hp.block_radius = np.array(self.radius, np.int32)
         return hp
 
     def view_ids(self, L):
         s = self.shape
-        ids = L.build_view_focus_ids(s.cols, s.rows, TRAJ, VIEWS)
+        ids = L.build_view_focus_ids(s.cols, s.rows, TRAJ, self.views)
         return np.ascontiguousarray(ids[:, :s.ids] if s.ids else ids)
 
     def key(self):
-        return (self.shape.name, hashlib.sha1(self.grid.tobytes()).hexdigest(), self.focus, self.rng, self.radius, self.steps)
+        return (self.shape.name, self.shape.ids, hashlib.sha1(self.grid.tobytes()).hexdigest(), self.focus, self.rng, self.radius, self.steps, self.views, self.wide)
 
 
 def first_grid(oc, shape):
@@ -481,8 +486,8 @@ def _pixel_costs(L, s):
 
 def _view_offsets(L, s):
     sh = s.shape
-    D = L.build_view_offsets(sh.cols, sh.rows, sh.W, sh.H, TRAJ, ASPECT, L.focus_ramp(RAMP[0], RAMP[1], VIEWS))
-    O, _ = L.build_view_centred_offsets(sh.cols, sh.rows, sh.W, sh.H, TRAJ, ASPECT, np.full(VIEWS, s.focus, np.float32))
+    D = L.build_view_offsets(sh.cols, sh.rows, sh.W, sh.H, TRAJ, ASPECT, L.focus_ramp(RAMP[0], RAMP[1], s.views))
+    O, _ = L.build_view_centred_offsets(sh.cols, sh.rows, sh.W, sh.H, TRAJ, ASPECT, np.full(s.views, s.focus, np.float32))
     return D, O
 
 
@@ -585,7 +590,7 @@ class ViewRows(Reader):
         hp, sh = s.params(L), s.shape
         D = _view_offsets(L, s)[0].copy()
         D[..., 0], D[..., 1] = np.clip(D[..., 0], -sh.W, sh.W), np.clip(D[..., 1], -sh.H, sh.H)
-        return _cached("rows", s, lambda: np.stack([oc.blend_std(s.grid, np.ascontiguousarray(D[v]), hp.offsets, hp.weights[v:v + 1])[0] for v in range(VIEWS)]))
+        return _cached("rows", s, lambda: np.stack([oc.blend_std(s.grid, np.ascontiguousarray(D[v]), hp.offsets, hp.weights[v:v + 1])[0] for v in range(s.views)]))
 
     def prepare(self, L, ctx, s, fixed=True):
         _layout(ctx, s, "rgba", fixed)
@@ -671,7 +676,7 @@ class ViewFocusMaps(Reader):
 
         def compute():
             out = []
-            for v in range(VIEWS):
+            for v in range(s.views):
                 out += list(_want_maps(oc, L, s, np.ascontiguousarray(O[v]), np.ascontiguousarray(ids[v]), 32))   # the per-view maps keep 32 candidates
             return out + list(_want_maps(oc, L, s, hp.offsets, hp.focus_map_ids, s.steps))
         return _cached("view_maps", s, compute)
@@ -685,13 +690,13 @@ class ViewFocusMaps(Reader):
         ctx.view_focus_maps(s.view_ids(L))
         ctx.focus_map()
         out = []
-        for v in range(VIEWS):
+        for v in range(s.views):
             out += [ctx.download_view_map(v, 0), ctx.download_view_map(v, 1)]
         return out + [ctx.download_map(0), ctx.download_map(1)]
 
     def check(self, got, want):
         for i, (g, w) in enumerate(zip(got, want)):
-            what = ("view", i // 2, "map", i % 2) if i < 2 * VIEWS else ("lfi_focus_map behind the views", "map", i % 2)
+            what = ("view", i // 2, "map", i % 2) if i < len(got) - 2 else ("lfi_focus_map behind the views", "map", i % 2)
             assert (g == w).all(), (what, int((g != w).any(-1).sum()))
 
     def done(self, ctx):
