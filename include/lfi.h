@@ -137,7 +137,47 @@ enum {
      * offsets beyond the copy's padding).
      * Out of scope: all-focus and per-view in-frame renders, the RGBA layout, row windows (and the program's -g above 1), the streaming calls,
      * deep in-frame views, a validity mask taken from the inputs' alpha. */
-    LFI_FLAG_IN_FRAME = 128u
+    LFI_FLAG_IN_FRAME = 128u,
+    /* LINEAR-LIGHT BLENDING: a view is a weighted mean of 64-225 samples, and by default that mean is taken over the input BYTES, which are
+     * gamma-encoded (sRGB images, or video expanded by the YUV paths).  A synthetic-aperture refocus sums light, and a mean of encoded values is
+     * not the encoding of the mean of the light: out-of-focus regions come out too dark and bright points shrink.  With this flag every sample is
+     * DECODED to linear light before the sum and the sum is ENCODED afterwards.  While it is set, lfi_render / lfi_prepare / lfi_benchmark with
+     * all_focus = 0 launch ONE kernel (csrc/hip/blend_linear.hpp; lfi_last_kernel_name names it, lfi_set_variant choices do not apply) that
+     * defines view v, channel c, pixel (x, y) from two tables (csrc/linear_light.h holds them as literal bit patterns, generated once; these
+     * formulas are their specification):
+     *      eotf(u) = u / 12.92 for u <= 0.04045, else ((u + 0.055) / 1.055)^2.4                      (IEC 61966-2-1)
+     *      D[b] = fp16_RN(255 * eotf(b / 255)),          b = 0 ... 255     (D[0] = 0, D[255] = 255)
+     *      T[b] = fp32_RN(255 * eotf((b - 0.5) / 255)),  b = 1 ... 255     (the linear value whose encoding is exactly b - 0.5)
+     *    No D[b] is nearer than 1.1e-6 (relative) to an fp16 rounding tie and no T[b] nearer than 2.1e-10 to an fp32 tie, so any correctly
+     *    working pow gives the same bits.  Both tables increase strictly; T[b] <= D[b] < T[b+1] for every b, so decoding and encoding one
+     *    byte is the identity; every D[b] lies at least 0.46 of its bin's width from either edge.
+     *      s_c    = the method's sum of w_g * D[px_g,c] over the images g = 0 ... N-1, w_g the view's fp16 weight, px_g,c the samples of a
+     *               flag-free fixed-focus render: image g at pixel + focused_offsets[g], clamped to the frame
+     *               STD:    the ordered fp32 chain s <- fmaf(float(D[px]), w_g, s), g ascending.  An fp16 times an fp16 is exact in fp32
+     *                       (22 bits), so each link is one fp32 addition of an exact product
+     *               TEN_WM: the fp32-accumulated matrix-core sum; the operands are D[px] and the fp16 weights as given
+     *      byte_c = E(s_c) = #{ b in 1 ... 255 : T[b] <= s_c },   alpha 255
+     *    E is monotone, saturates at 255 and is the same under both methods: they differ only in how s is accumulated.
+     *  - STD bytes are fully determined.
+     *  - TEN_WM bytes lie in [E(max(0, S - eps)), E(S + eps)], S the exact sum (it fits a double) and eps the analytic accumulation bound of
+     *    the STD band (LFI_FLAG_STD_ANALYTIC_BAND): 2^-15 per addend times k_pad addends.  That bound rests only on the partial sums staying
+     *    below 512 and on exact products; both hold here.
+     *  - A weight row with a single 1.0, or with two weights of 0.5, is exact in fp32 in any order: such rows give the same bytes under both
+     *    methods, and a one-hot row returns the input image's own bytes.
+     * The output is ordinary 8-bit views: downloads, YUV frames, quilts, native images, lfi_compare_view[s] and RGB-D work on them unchanged.
+     * Without the flag no byte, launch or message changes.  A launch with the flag drops the deep views of an earlier deep render.
+     * Valid: fixed focus; LFI_LAYOUT_PLANAR_RGB; grids up to LFI_MAX_IMAGES images, any number of views, any view range; the kernel reads the
+     * derived planar copy of the inputs (lfi_prepare builds it: a prepared render is only a launch; lfi_benchmark builds it before its first
+     * timed launch), so it also serves a context after lfi_release_inputs.
+     * LFI_EINVAL with a message that starts "LFI_FLAG_LINEAR_LIGHT is set: ", the context usable and nothing written or allocated, while the flag
+     * is set: all_focus = 1; lfi_render_stream and lfi_render_stream_yuv420; per-view rows (lfi_set_view_offsets, lfi_set_view_float_offsets); a
+     * row window; the RGBA view layout; LFI_FLAG_TEN_ROUND_PER_BATCH; LFI_FLAG_DEEP_VIEWS or LFI_FLAG_IN_FRAME set together with it;
+     * lfi_download_prequant; weights outside [0, 2); inputs or offsets the planar copy cannot serve (an attached grid without
+     * lfi_grid_modified; after lfi_release_inputs, offsets beyond the copy's padding).
+     * Out of scope: all-focus and per-view linear renders; linear light together with in-frame blending or deep views (10 bits of a linear
+     * sum); the RGBA layout, row windows (and the program's -g above 1), the streaming calls; other transfer functions (BT.1886, PQ, HLG); a
+     * linear-light focus estimate; linear-light resizing in the quilt and native-image kernels. */
+    LFI_FLAG_LINEAR_LIGHT = 256u
 };
 
 #define LFI_MAX_IMAGES 256     /* MAX_IMAGES, src/kernels.cu:60 */

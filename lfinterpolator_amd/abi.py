@@ -19,6 +19,7 @@ LFI_FLAG_STD_MEASURED_BAND = 16
 LFI_FLAG_STD_BAND_PROBE_FAIL = 32
 LFI_FLAG_DEEP_VIEWS = 64     # fixed-focus renders also keep 10 bits per channel from the accumulator: the deep planes (include/lfi.h)
 LFI_FLAG_IN_FRAME = 128      # fixed-focus renders leave out the samples outside their image and renormalise the weights (include/lfi.h)
+LFI_FLAG_LINEAR_LIGHT = 256  # fixed-focus renders decode sRGB to linear light before the sum and encode the sum (include/lfi.h)
 LFI_KERNEL_FOCUS_ESTIMATE = 2
 LFI_POISON_VIEWS = 1
 LFI_POISON_SCRATCH = 2

@@ -24,6 +24,7 @@
 #include "blend_vfocus_af.hpp"
 #include "deep_blend.hpp"
 #include "blend_inframe.hpp"
+#include "blend_linear.hpp"
 #include "lfi_band_probe.hpp"
 
 namespace {
@@ -53,6 +54,8 @@ enum class BlendKernel
     deep_std,
     inframe_ten, // blend_inframe.hpp: LFI_FLAG_IN_FRAME
     inframe_std,
+    linear_ten, // blend_linear.hpp: LFI_FLAG_LINEAR_LIGHT
+    linear_std,
 };
 
 // The generic kernels: plain fp32 epilogue, any weights, pre-quantisation dumps, per-batch rounding (TEN_WM).  They run one pixel grid
@@ -127,6 +130,10 @@ BlendRoute route_blend(const lfi_ctx *c, int method, bool all_focus, const Kerne
     const bool ten = method == LFI_METHOD_TEN_WM, planar_views = c->out_layout == LFI_LAYOUT_PLANAR_RGB;
     const K first = ten ? kTenVariants[c->ten_variant].first : kStdVariants[c->std_variant].first;
     const int nch = (a.k_pad + lfi::P3_KC - 1) / lfi::P3_KC;
+    // 0a. linear-light blending (LFI_FLAG_LINEAR_LIGHT): one kernel for both methods; launch_blend (flagged_refused) has refused what it does not
+    // serve — the other two flags beside it among that
+    if(c->flags & LFI_FLAG_LINEAR_LIGHT)
+        return {ten ? K::linear_ten : K::linear_std, nch, true, true};
     // 0. deep views (LFI_FLAG_DEEP_VIEWS): one kernel for both methods; launch_blend (flagged_refused) has refused what it does not serve
     if(c->flags & LFI_FLAG_DEEP_VIEWS)
         return {ten ? K::deep_ten : K::deep_std, nch, true, true};
@@ -377,24 +384,30 @@ void launch_afs(const lfi_ctx *c, const KernelArgs &a_in, const BlendRoute &r)
 
 void launch_p3(const lfi_ctx *c, const KernelArgs &a_in, int nch, bool rgba_out);
 
-// deep_blend (deep: the byte planes and the deep planes) or blend_inframe (the byte planes, out-of-frame samples left out) for views
-// [v0, v1).  One chunk of images: ONE launch whose tiles serve every 64-view pass from the same LDS-resident pixels; several chunks: one
+// deep_blend (flag = LFI_FLAG_DEEP_VIEWS: the byte planes and the deep planes), blend_inframe (LFI_FLAG_IN_FRAME: the byte planes, out-of-frame
+// samples left out) or blend_linear (LFI_FLAG_LINEAR_LIGHT: the byte planes, blended in linear light) for views [v0, v1).  One chunk of images: ONE launch whose tiles serve every 64-view pass from the same LDS-resident pixels; several chunks: one
 // launch per 64 views
-void launch_tile16(const lfi_ctx *c, const KernelArgs &a_in, int nch, bool deep, bool std_chain)
+void launch_tile16(const lfi_ctx *c, const KernelArgs &a_in, int nch, unsigned flag, bool std_chain)
 {
+    const bool deep = flag == LFI_FLAG_DEEP_VIEWS, linear = flag == LFI_FLAG_LINEAR_LIGHT;
     const int tiles_x = (a_in.width + lfi::P3_TPX - 1) / lfi::P3_TPX;
     const int n_tiles = tiles_x * a_in.out_rows;
     const dim3 grid(std::min(n_tiles, 2 * cu_count_of(c))), block(256);
     // what lfi_last_kernel_name reports.  Set here, not through the helper the other launchers use: tests/test_gpu_dispatch_coverage.py holds every
     // name that goes through it to a row of its render matrix, which knows no parameter flags; these launches are held to their names by
-    // tests/test_gpu_deep.py and tests/test_gpu_inframe.py
-    c->last_kernel = deep ? (std_chain ? "deep_blend<STD>" : "deep_blend<TEN_WM>") : (std_chain ? "blend_inframe<STD>" : "blend_inframe<TEN_WM>");
+    // tests/test_gpu_deep.py, tests/test_gpu_inframe.py and tests/test_gpu_linear.py
+    c->last_kernel = linear ? (std_chain ? "blend_linear<STD>" : "blend_linear<TEN_WM>")
+                     : deep ? (std_chain ? "deep_blend<STD>" : "deep_blend<TEN_WM>") : (std_chain ? "blend_inframe<STD>" : "blend_inframe<TEN_WM>");
     auto launch = [&](const KernelArgs &a, int passes) {
         auto go = [&](auto kernel, auto... extra) { hipLaunchKernelGGL(kernel, grid, block, 0, stream_of(c), a, extra..., tiles_x, n_tiles, passes, nch); };
         if(deep && std_chain)
             go(lfi::deep_blend<true>, c->deep.get(), deep_pitch(c));
         else if(deep)
             go(lfi::deep_blend<false>, c->deep.get(), deep_pitch(c));
+        else if(linear && std_chain)
+            go(lfi::blend_linear<true>);
+        else if(linear)
+            go(lfi::blend_linear<false>);
         else if(std_chain)
             go(lfi::blend_inframe<true>);
         else
@@ -410,10 +423,12 @@ void launch_route(const lfi_ctx *c, const KernelArgs &a, bool all_focus, const B
 {
     switch(r.kernel)
     {
-        case BlendKernel::inframe_ten: launch_tile16(c, a, r.nch, false, false); break;
-        case BlendKernel::inframe_std: launch_tile16(c, a, r.nch, false, true); break;
-        case BlendKernel::deep_ten: launch_tile16(c, a, r.nch, true, false); break;
-        case BlendKernel::deep_std: launch_tile16(c, a, r.nch, true, true); break;
+        case BlendKernel::linear_ten: launch_tile16(c, a, r.nch, LFI_FLAG_LINEAR_LIGHT, false); break;
+        case BlendKernel::linear_std: launch_tile16(c, a, r.nch, LFI_FLAG_LINEAR_LIGHT, true); break;
+        case BlendKernel::inframe_ten: launch_tile16(c, a, r.nch, LFI_FLAG_IN_FRAME, false); break;
+        case BlendKernel::inframe_std: launch_tile16(c, a, r.nch, LFI_FLAG_IN_FRAME, true); break;
+        case BlendKernel::deep_ten: launch_tile16(c, a, r.nch, LFI_FLAG_DEEP_VIEWS, false); break;
+        case BlendKernel::deep_std: launch_tile16(c, a, r.nch, LFI_FLAG_DEEP_VIEWS, true); break;
         case BlendKernel::ten_m16: launch_ten_m16(c, a, all_focus); break;
         case BlendKernel::ten_direct: launch_ten_direct(c, a, all_focus); break;
         case BlendKernel::p3: launch_p3(c, a, r.nch, false); break;
@@ -736,21 +751,32 @@ bool allfocus_rows_held(const lfi_ctx *c, const lfi_float2 *o, size_t n)
     return true;
 }
 
-// ---- the flagged fixed-focus renders: deep views (LFI_FLAG_DEEP_VIEWS, deep_blend.hpp), in-frame blending (LFI_FLAG_IN_FRAME, blend_inframe.hpp) --
+// ---- the flagged fixed-focus renders: deep views (LFI_FLAG_DEEP_VIEWS, deep_blend.hpp), in-frame blending (LFI_FLAG_IN_FRAME, blend_inframe.hpp),
+// linear-light blending (LFI_FLAG_LINEAR_LIGHT, blend_linear.hpp) ----------------------------------------------------------------------------
 
 const char *const kDeepNoPrequant = "lfi_download_prequant is not supported (the deep planes ARE the accumulator's ten bits)";
 const char *const kInFrameNoPrequant = "lfi_download_prequant is not supported";
+const char *const kLinearNoPrequant = "lfi_download_prequant is not supported";
 
-// What a render under `flag` (LFI_FLAG_DEEP_VIEWS or LFI_FLAG_IN_FRAME) refuses, before anything is enqueued or allocated; every message names
+const char *flag_name(unsigned flag)
+{
+    return flag == LFI_FLAG_DEEP_VIEWS ? "LFI_FLAG_DEEP_VIEWS" : flag == LFI_FLAG_IN_FRAME ? "LFI_FLAG_IN_FRAME" : "LFI_FLAG_LINEAR_LIGHT";
+}
+
+// What a render under `flag` (LFI_FLAG_DEEP_VIEWS, LFI_FLAG_IN_FRAME or LFI_FLAG_LINEAR_LIGHT) refuses, before anything is enqueued or allocated; every message names
 // the flag
 int flagged_refused(lfi_ctx *c, unsigned flag, int all_focus, const KernelArgs &a)
 {
-    const bool deep = flag == LFI_FLAG_DEEP_VIEWS;
+    const bool deep = flag == LFI_FLAG_DEEP_VIEWS, linear = flag == LFI_FLAG_LINEAR_LIGHT;
     const char *why = nullptr;
-    if(!deep && (c->flags & LFI_FLAG_DEEP_VIEWS))
+    if(linear && (c->flags & LFI_FLAG_DEEP_VIEWS))
+        why = "LFI_FLAG_DEEP_VIEWS is not supported together with it (no deep linear-light views)";
+    else if(linear && (c->flags & LFI_FLAG_IN_FRAME))
+        why = "LFI_FLAG_IN_FRAME is not supported together with it (no in-frame linear-light blending)";
+    else if(!deep && !linear && (c->flags & LFI_FLAG_DEEP_VIEWS))
         why = "LFI_FLAG_DEEP_VIEWS is not supported together with it (no deep in-frame views)";
     else if(a.prequant)
-        why = deep ? kDeepNoPrequant : kInFrameNoPrequant;
+        why = deep ? kDeepNoPrequant : linear ? kLinearNoPrequant : kInFrameNoPrequant;
     else if(all_focus)
         why = "all-focus renders are not supported (fixed focus only)";
     else if(c->view_offsets.set || c->view_float_offsets.set)
@@ -763,7 +789,7 @@ int flagged_refused(lfi_ctx *c, unsigned flag, int all_focus, const KernelArgs &
         why = "LFI_FLAG_TEN_ROUND_PER_BATCH is not supported";
     else if(!c->weights_scalable)
         why = "weights outside [0, 2) are not supported";
-    return why ? fail(c, LFI_EINVAL, std::string(deep ? "LFI_FLAG_DEEP_VIEWS" : "LFI_FLAG_IN_FRAME") + " is set: " + why) : LFI_OK;
+    return why ? fail(c, LFI_EINVAL, std::string(flag_name(flag)) + " is set: " + why) : LFI_OK;
 }
 
 // the deep planes of all views_n views; a first use (or a new size) allocates, which may block
@@ -779,7 +805,7 @@ int ensure_deep_planes(lfi_ctx *c)
 }
 
 // lfi_render / lfi_prepare's build / lfi_benchmark while `flag` is set: deep_blend writes the byte planes and the deep planes of [v0, v1),
-// blend_inframe the byte planes.  The order of the steps decides what is allocated or dropped before a refusal
+// blend_inframe and blend_linear the byte planes.  The order of the steps decides what is allocated or dropped before a refusal
 int launch_flagged_views(lfi_ctx *c, unsigned flag, int method, int all_focus, const KernelArgs &a_in)
 {
     const bool deep = flag == LFI_FLAG_DEEP_VIEWS;
@@ -790,7 +816,7 @@ int launch_flagged_views(lfi_ctx *c, unsigned flag, int method, int all_focus, c
     if(int rc = join_uploads(c))
         return rc;
     if(!ensure_planar(c, tune_planar_now(c)))
-        return fail(c, LFI_EINVAL, std::string(deep ? "LFI_FLAG_DEEP_VIEWS" : "LFI_FLAG_IN_FRAME") +
+        return fail(c, LFI_EINVAL, std::string(flag_name(flag)) +
                                        " is set: the planar copy of the inputs cannot serve these offsets (inputs the library cannot track, "
                                        "or, after lfi_release_inputs, offsets beyond the copy's padding)");
     if(deep)
@@ -798,7 +824,7 @@ int launch_flagged_views(lfi_ctx *c, unsigned flag, int method, int all_focus, c
             return rc;
     KernelArgs a = a_in;
     set_planar_args(c, a);
-    drop_deep_range(c); // in-frame: the views are written without their deep planes
+    drop_deep_range(c); // in-frame, linear light: the views are written without their deep planes
     launch_route(c, a, false, route_blend(c, method, false, a, true));
     LFI_HIP(c, hipGetLastError());
     if(deep)
@@ -809,6 +835,8 @@ int launch_flagged_views(lfi_ctx *c, unsigned flag, int method, int all_focus, c
 // Renders views [a_in.v0, a_in.v1) into a_in.views
 int launch_blend(lfi_ctx *c, int method, int all_focus, const KernelArgs &a_in)
 {
+    if(c->flags & LFI_FLAG_LINEAR_LIGHT) // (with one of the other two beside it: refused there)
+        return launch_flagged_views(c, LFI_FLAG_LINEAR_LIGHT, method, all_focus, a_in);
     if(c->flags & LFI_FLAG_IN_FRAME) // (with LFI_FLAG_DEEP_VIEWS beside it: refused there)
         return launch_flagged_views(c, LFI_FLAG_IN_FRAME, method, all_focus, a_in);
     if(c->flags & LFI_FLAG_DEEP_VIEWS)

@@ -1908,6 +1908,9 @@ int lfi_prepare(lfi_ctx *ctx, int method, int all_focus, int v0, int v1)
         return rc;
     const KernelArgs a = make_args(ctx, v0, v1, method);
     ctx->derived_build_ms = 0.0f;
+    if(ctx->flags & LFI_FLAG_LINEAR_LIGHT) // the copy below: a linear-light render is then only a launch.  (First: it refuses the other two beside it)
+        if(int rc = flagged_refused(ctx, LFI_FLAG_LINEAR_LIGHT, all_focus, a))
+            return rc;
     const bool in_frame = ctx->flags & LFI_FLAG_IN_FRAME; // the copy below: an in-frame render is then only a launch
     if(in_frame)
         if(int rc = flagged_refused(ctx, LFI_FLAG_IN_FRAME, all_focus, a))
@@ -2167,6 +2170,8 @@ int lfi_render_stream(lfi_ctx *ctx, int method, int all_focus, const uint16_t *w
         return rc;
     if(const ViewRowsKind rows = view_rows_of(ctx, all_focus))
         return fail(ctx, LFI_EINVAL, view_rows_set(rows) + "lfi_render_stream is not supported - clear them with NULL");
+    if(ctx->flags & LFI_FLAG_LINEAR_LIGHT)
+        return fail(ctx, LFI_EINVAL, "LFI_FLAG_LINEAR_LIGHT is set: lfi_render_stream is not supported");
     if(ctx->flags & LFI_FLAG_DEEP_VIEWS)
         return fail(ctx, LFI_EINVAL, "LFI_FLAG_DEEP_VIEWS is set: lfi_render_stream is not supported");
     if(ctx->flags & LFI_FLAG_IN_FRAME)
@@ -2185,6 +2190,8 @@ int lfi_render_stream_yuv420(lfi_ctx *ctx, int method, int all_focus, const uint
         return rc;
     if(const ViewRowsKind rows = view_rows_of(ctx, all_focus))
         return fail(ctx, LFI_EINVAL, view_rows_set(rows) + "lfi_render_stream_yuv420 is not supported - clear them with NULL");
+    if(ctx->flags & LFI_FLAG_LINEAR_LIGHT)
+        return fail(ctx, LFI_EINVAL, "LFI_FLAG_LINEAR_LIGHT is set: lfi_render_stream_yuv420 is not supported");
     if(ctx->flags & LFI_FLAG_DEEP_VIEWS)
         return fail(ctx, LFI_EINVAL, "LFI_FLAG_DEEP_VIEWS is set: lfi_render_stream_yuv420 is not supported");
     if(ctx->flags & LFI_FLAG_IN_FRAME)
@@ -2543,7 +2550,13 @@ int lfi_benchmark(lfi_ctx *ctx, int method, int all_focus, int v0, int v1, int w
     const KernelArgs a = make_args(ctx, v0, v1, method);
     // the derived input copy is (re)built here, not inside the first timed launch — and so are the deep planes allocated (LFI_FLAG_DEEP_VIEWS)
     bool planar = false;
-    if(ctx->flags & LFI_FLAG_IN_FRAME)
+    if(ctx->flags & LFI_FLAG_LINEAR_LIGHT)
+    {
+        if(int rc = flagged_refused(ctx, LFI_FLAG_LINEAR_LIGHT, all_focus, a))
+            return rc;
+        (void)ensure_planar(ctx, true);
+    }
+    else if(ctx->flags & LFI_FLAG_IN_FRAME)
     {
         if(int rc = flagged_refused(ctx, LFI_FLAG_IN_FRAME, all_focus, a))
             return rc;
@@ -3099,6 +3112,8 @@ int lfi_download_prequant(lfi_ctx *ctx, int method, int all_focus, int v, float 
         return rc;
     const size_t bytes = sizeof(float) * 3 * (size_t)ctx->width * ctx->height;
     KernelArgs a = make_args(ctx, v, v + 1, method);
+    if(ctx->flags & LFI_FLAG_LINEAR_LIGHT) // refused by name before anything is reserved
+        return fail(ctx, LFI_EINVAL, std::string("LFI_FLAG_LINEAR_LIGHT is set: ") + kLinearNoPrequant);
     if(ctx->flags & LFI_FLAG_IN_FRAME) // refused by name before anything is reserved
         return fail(ctx, LFI_EINVAL, std::string("LFI_FLAG_IN_FRAME is set: ") + kInFrameNoPrequant);
     if(ctx->flags & LFI_FLAG_DEEP_VIEWS) // refused by name before anything is reserved

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "../area_span.h"
+#include "../linear_light.h"
 #include "../native_taps.h"
 #include "lenticular.h"
 #include "params.h"
@@ -96,6 +97,40 @@ int lfi_host_area_span(int src, int dst, int o, int32_t out[4])
     out[1] = static_cast<int32_t>(s.last);
     out[2] = static_cast<int32_t>(s.w_first);
     out[3] = static_cast<int32_t>(s.w_last);
+    return 0;
+}
+
+// the tables of linear-light blending (LFI_FLAG_LINEAR_LIGHT; ../linear_light.h, the bits the kernel loads): d16[256] the fp16 bit patterns of
+// the decode table D, t32[256] the fp32 bit patterns of the thresholds T (entry 0 a placeholder).  Returns 0, or -1 for a NULL pointer
+int lfi_host_linear_tables(uint16_t *d16, uint32_t *t32)
+{
+    if(!d16 || !t32)
+        return -1;
+    for(int b = 0; b < 256; b++)
+        d16[b] = lfi::LINEAR_D16_BITS[b], t32[b] = lfi::LINEAR_T_BITS[b];
+    return 0;
+}
+
+// out[i] = E(s[i]) for n fp32 sums, by the epilogue the kernel runs (../linear_light.h): the threshold array and the first-guess table set up as
+// the kernel sets them up, then linear_encode.  Returns 0, or -1 for a NULL pointer
+int lfi_host_linear_encode(const float *s, size_t n, uint8_t *out)
+{
+    if(!s || !out)
+        return -1;
+    static const struct Tables
+    {
+        float thr[257];
+        uint8_t guess[lfi::LINEAR_CELLS];
+        Tables()
+        {
+            for(int b = 0; b <= 256; b++)
+                thr[b] = lfi::linear_threshold(b);
+            for(int cell = 0; cell < lfi::LINEAR_CELLS; cell++)
+                guess[cell] = lfi::linear_guess(thr, cell);
+        }
+    } tables;
+    for(size_t i = 0; i < n; i++)
+        out[i] = static_cast<uint8_t>(lfi::linear_encode(s[i], tables.guess, tables.thr));
     return 0;
 }
 

@@ -496,6 +496,12 @@ void Interpolator::interpolate(std::string outputPath, std::string trajectory, f
             throw std::runtime_error("In-frame edges (--edges in-frame) need a fixed-focus render with one focus and one set of shifts on one GPU, without --deep!");
         params.flags |= LFI_FLAG_IN_FRAME;
     }
+    if(linearLight)
+    {
+        if(inRange > 0 || perViewFocus || viewCentred || deep || inFrame || gpuCount > 1)
+            throw std::runtime_error("Linear-light blending (--light linear) needs a fixed-focus render with one focus and one set of shifts on one GPU, without --deep and --edges in-frame!");
+        params.flags |= LFI_FLAG_LINEAR_LIGHT;
+    }
     if(gpuCount < 1 || gpuCount > viewCount)
         throw std::runtime_error("The number of GPUs has to be between 1 and the number of views!");
     if((compareMethods || !compareDir.empty()) && gpuCount > 1)
@@ -511,7 +517,7 @@ void Interpolator::interpolate(std::string outputPath, std::string trajectory, f
     // TEN_WM renders therefore use the alpha-free byte-plane layout (a quarter fewer bytes written per launch, csrc/hip/blend_p3.hpp);
     // the other renders keep the reference's RGBA planes (they would pay a conversion pass).  Output files are identical.
     for(lfi_ctx *c : contexts)
-        check(lfi_set_output_layout(c, (deep || inFrame || (methodID == LFI_METHOD_TEN_WM && !(inRange > 0))) ? LFI_LAYOUT_PLANAR_RGB : LFI_LAYOUT_RGBA), c); // (deep views, in-frame edges: planar only)
+        check(lfi_set_output_layout(c, (deep || inFrame || linearLight || (methodID == LFI_METHOD_TEN_WM && !(inRange > 0))) ? LFI_LAYOUT_PLANAR_RGB : LFI_LAYOUT_RGBA), c); // (deep views, in-frame edges, linear light: planar only)
 
     const int allFocus = inRange > 0;
     if(perViewFocus && allFocus)

@@ -104,6 +104,9 @@ class Interpolator
         // in-frame edges (LFI_FLAG_IN_FRAME): fixed-focus renders leave out the samples that fall outside their image and scale the rest back to
         // the full weight, instead of clamping them to the image's edge; every output is then made of those views by the same calls
         void setInFrame(bool on) { inFrame = on; }
+        // linear-light blending (LFI_FLAG_LINEAR_LIGHT): fixed-focus renders decode every sample from sRGB to linear light before the weighted
+        // sum and encode the sum; every output is then made of those views by the same calls
+        void setLinearLight(bool on) { linearLight = on; }
         // 10 where the input is a light-field video whose files say C420p10 (they are uploaded as I010 frames: lfi_upload_images_yuv), else 8
         int inputDepth() const;
         // also write the quilt of setQuilt (scaled by setQuiltTile) as ONE frame of a Y4M video file: resized and converted to 8-bit YUV 4:2:0
@@ -231,6 +234,7 @@ class Interpolator
         int yuvDepth{8};                           // setYuvDepth
         bool deep{false};                          // setDeep
         bool inFrame{false};                       // setInFrame
+        bool linearLight{false};                   // setLinearLight
         std::string gbrp10Path;                    // empty: no raw gbrp10le file
         std::ofstream gbrp10File;                  // open from the first stored step to finish()
         std::string quiltY4mPath;                  // empty: no quilt video

@@ -69,6 +69,7 @@ int main(int argc, char **argv)
                           "--p010 FILE - also store the views as raw 10-bit P010 frames in FILE (the layout of --nv12 with every sample a little-endian 16-bit word, the code in its upper 10 bits): what Main10 hardware encoders take; converted on the GPU, may be given next to --y4m and --nv12 whatever --yuv-depth says; prints the ffmpeg options that open FILE (-f rawvideo -pix_fmt p010le -s WxH -r N)\n"
                           "--deep - with a fixed-focus render: deep views - the GPU keeps 10 bits per colour channel straight from the blend's accumulator beside the 8-bit views (the PNG files are unchanged bytes), and --p010 FILE and --y4m FILE with --yuv-depth 10 are converted from those 10-bit views instead of from the 8-bit ones: a Main10 encoder gets the render without a first quantisation. Not with -r above 0, -F, -c, --view-maps, -g above 1, 8-bit video outputs (--nv12, --y4m without --yuv-depth 10), --quilt-y4m or --rgbd-y4m\n"
                           "--edges clamp|in-frame - what a fixed-focus render does with a sample that falls outside its image: clamp (default) takes the image's edge pixel, as the reference does, which smears every image's edge across a band as wide as its shift; in-frame leaves the sample out and scales the weights of the others back to their full sum (a pixel that no image covers is black), and the PNG, --y4m, --nv12, --p010, quilt and native outputs are made of those views; fixed focus on one GPU only: not with -r above 0, -F, -c, --view-maps, --deep or -g above 1\n"
+                          "--light encoded|linear - in what a fixed-focus render takes its weighted mean: encoded (default) averages the input bytes as they are (gamma-encoded values), as the reference does, which darkens out-of-focus regions and shrinks bright points; linear decodes every sample from sRGB (IEC 61966-2-1) to linear light before the sum and encodes the sum afterwards, and the PNG, --y4m, --nv12, quilt, native, RGB-D and compare outputs are made of those views; fixed focus on one GPU only: not with -r above 0, -F, -c, --view-maps, --deep, --edges in-frame or -g above 1\n"
                           "--gbrp10 FILE - with --deep: also store the deep views as raw planar 10-bit RGB frames in FILE, in view order: per frame the planes G, B, R, every sample a little-endian 16-bit word with the code in its low 10 bits; prints the ffmpeg options that open FILE (-f rawvideo -pix_fmt gbrp10le -s WxH -r N)\n"
                           "--yuv-depth 8|10 - with --y4m or --quilt-y4m: the bits per sample of the frames written (default=8). 10: the files hold I010 samples (yuv420p10le) under the tag C420p10, and an 8-bit colour survives the trip into them and back exactly; Y4M has no siting tag for 10-bit frames, so the siting in use (--chroma-site) is printed with the ffmpeg option that states it (-chroma_sample_location). Not with --rgbd-y4m: RGB-D frames are 8-bit. A light-field video whose files say C420p10 is read as 10-bit frames without any option (--in-chroma-site auto reads it left-sited and says so); not with --lean-inputs: 10-bit frames cannot go straight into the planar copy\n"
                           "--quilt-y4m FILE - with -q: also store the quilt (scaled by --quilt-tile) as one frame of the YUV4MPEG2 video FILE, resized and converted to 8-bit YUV 4:2:0 on the GPU in one pass (even tile sizes) - with --frames FIRST:COUNT one frame per time step: a quilt video, what holographic players take; one GPU only\n"
@@ -471,6 +472,37 @@ int main(int argc, char **argv)
             }
     }
 
+    bool linearLight = false;
+    if(args["--light"])
+    {
+        const std::string text = static_cast<std::string>(args["--light"]);
+        if(text != "encoded" && text != "linear")
+        {
+            std::cerr << "--light expects encoded or linear." << std::endl;
+            return EXIT_FAILURE;
+        }
+        linearLight = text == "linear";
+    }
+    if(linearLight)
+    {
+        // linear-light blending: one fixed-focus kernel in one context
+        const std::pair<bool, const char *> refused[] = {
+            {args["-r"] && range > 0, "-r above 0 (linear-light blending needs a fixed-focus render)"},
+            {static_cast<bool>(args["-F"]), "-F (a focus per view is not blended in linear light)"},
+            {static_cast<bool>(args["-c"]), "-c (view-centred shifts are not blended in linear light)"},
+            {static_cast<bool>(args["--view-maps"]), "--view-maps (all-focus rendering is not blended in linear light)"},
+            {static_cast<bool>(args["--deep"]), "--deep (deep linear-light views are not supported)"},
+            {inFrameEdges, "--edges in-frame (in-frame linear-light blending is not supported)"},
+            {args["-g"] && static_cast<int>(args["-g"]) > 1, "-g above 1 (it works in one context)"},
+        };
+        for(const auto &[given, what] : refused)
+            if(given)
+            {
+                std::cerr << "--light linear (samples decoded from sRGB before the sum, the sum encoded) cannot be combined with " << what << "." << std::endl;
+                return EXIT_FAILURE;
+            }
+    }
+
     int outSiting = LFI_YUV_SITING_CENTRE;
     if(args["--chroma-site"])
     {
@@ -809,6 +841,9 @@ int main(int argc, char **argv)
         interpolator->setInFrame(inFrameEdges);
         if(inFrameEdges)
             std::cout << "in-frame edges: samples outside their image are left out and the weights of the others renormalised" << std::endl;
+        interpolator->setLinearLight(linearLight);
+        if(linearLight)
+            std::cout << "linear-light blending: samples are decoded from sRGB before the weighted sum and the sum is encoded" << std::endl;
         if(args["--gbrp10"])
             interpolator->setGbrp10(static_cast<std::string>(args["--gbrp10"]));
         if(args["--p010"])

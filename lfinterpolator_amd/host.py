@@ -44,6 +44,10 @@ def load_host_library() -> C.CDLL:
         lib.lfi_host_lenticular_json.argtypes = [C.c_char_p] + [C.c_int] * 3 + [C.POINTER(Lenticular), C.c_void_p, C.c_char_p, C.c_size_t]
         lib.lfi_host_native_taps.restype = C.c_int
         lib.lfi_host_native_taps.argtypes = [C.c_int] * 3 + [C.c_void_p]
+        lib.lfi_host_linear_tables.restype = C.c_int
+        lib.lfi_host_linear_tables.argtypes = [C.c_void_p, C.c_void_p]
+        lib.lfi_host_linear_encode.restype = C.c_int
+        lib.lfi_host_linear_encode.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p]
         lib.lfi_host_y4m_frame_bytes.restype = C.c_size_t
         lib.lfi_host_y4m_frame_bytes.argtypes = [C.c_int, C.c_int]
         lib.lfi_host_y4m_write.restype = C.c_int
@@ -210,6 +214,25 @@ def native_taps(src: int, dst: int, o: int):
     if load_host_library().lfi_host_native_taps(src, dst, o, out.ctypes.data) != 0:
         raise ValueError("needs 1 <= src, dst <= 65535 and 0 <= o < dst")
     return tuple(int(v) for v in out)
+
+
+def linear_tables():
+    """The tables of linear-light blending (LFI_FLAG_LINEAR_LIGHT, csrc/linear_light.h) as the library holds them: (D, T) — D [256] uint16, the
+    fp16 bit patterns of the decode table; T [256] uint32, the fp32 bit patterns of the thresholds (T[0] is a placeholder, 0)."""
+    d, t = np.zeros(256, dtype=np.uint16), np.zeros(256, dtype=np.uint32)
+    if load_host_library().lfi_host_linear_tables(d.ctypes.data, t.ctypes.data) != 0:
+        raise ValueError("lfi_host_linear_tables failed")
+    return d, t
+
+
+def linear_encode(s) -> np.ndarray:
+    """E(s) of linear-light blending for every float32 of s, by the epilogue the kernel runs (csrc/linear_light.h: linear_encode over the
+    first-guess table linear_guess builds): uint8, the shape of s."""
+    s = np.ascontiguousarray(s, dtype=np.float32)
+    out = np.zeros(s.shape, dtype=np.uint8)
+    if load_host_library().lfi_host_linear_encode(s.ctypes.data, s.size, out.ctypes.data) != 0:
+        raise ValueError("lfi_host_linear_encode failed")
+    return out
 
 
 def write_y4m(path: str, frames: np.ndarray, width: int, height: int, fps=(30, 1), full_range: bool = False, left_sited: bool = False, depth: int = 8) -> None:
