@@ -39,6 +39,7 @@ import lfinterpolator_amd as L
 import deep_ref
 import inframe_ref
 import input_writers as iw
+import linear_ref
 import native_filter_ref
 import native_ref
 import poison
@@ -52,7 +53,10 @@ import yuv_left_ref
 import yuv_ref
 import yuv_surfaces_ref as sref
 
-DEEP, IN_FRAME, PER_BATCH = L.LFI_FLAG_DEEP_VIEWS, L.LFI_FLAG_IN_FRAME, L.LFI_FLAG_TEN_ROUND_PER_BATCH
+DEEP, IN_FRAME, PER_BATCH, LINEAR = L.LFI_FLAG_DEEP_VIEWS, L.LFI_FLAG_IN_FRAME, L.LFI_FLAG_TEN_ROUND_PER_BATCH, L.LFI_FLAG_LINEAR_LIGHT
+# the parameter flags that send a fixed-focus render to launch_flagged_views (deep_blend, blend_inframe, blend_linear): every predicate on "a
+# flagged state" goes through this one mask, so that the next such flag is added here and nowhere else
+VIEW_FLAGS = DEEP | IN_FRAME | LINEAR
 # what may be poisoned between the work and the change: never LFI_POISON_DERIVED or LFI_POISON_FOCUS_WORKSPACE — they reset grid_version and
 # pad_version, the bookkeeping under test (input_writers.Reader)
 POISON_BITS = L.LFI_POISON_VIEWS | L.LFI_POISON_SCRATCH | L.LFI_POISON_MAPS | L.LFI_POISON_VIEW_MAPS | L.LFI_POISON_DEEP
@@ -132,6 +136,12 @@ TALL = replace(SMALL, H=40)     # room for interior bands: at focus 0.05 the fix
 AUTO = ("auto", "auto")
 OTHER_KERNELS = ("persist_m2_nt", "wave_m2_nt")     # both honour a row window
 KERNEL_OF = {"persist_m2_nt": "blend_persist<STD>", "wave_m2_nt": "blend_wave<TEN_WM>"}
+
+
+def ten_kernel_of(st):
+    """the TEN_WM kernel of a state whose variant is not "auto": the wave-private kernels serve one view pass (route_blend: wave_fits needs
+    v1 − v0 <= 64 and one chunk of images), so over 64 views the variant gives way to the persistent kernel"""
+    return KERNEL_OF[st.variant[1]] if st.V <= 64 and st.n <= 64 else "blend_persist<TEN_WM>"
 
 _grids = {}
 
@@ -311,7 +321,7 @@ def _fixed_mode(st, released_ok=True):
     """what a plain fixed-focus render meets in the state"""
     if st.rows_kind:
         return SKIP(ROWS_STATE)
-    if st.flags & (DEEP | IN_FRAME) and st.layout != "planar":
+    if st.flags & VIEW_FLAGS and st.layout != "planar":
         return REFUSED(NEEDS_PLANAR)
     if st.inputs == "released" and not released_ok:
         return REFUSED(RELEASED)
@@ -384,19 +394,21 @@ class Std(FromReader):
         return _fixed_mode(st)
 
     def depends(self, st):
-        return super().depends(st) + (st.flags & IN_FRAME,)
+        return super().depends(st) + (st.flags & (IN_FRAME | LINEAR),)
 
     def read(self, oc, run, st):
         """by whatever STD variant the context holds: no lfi_set_variant here"""
         run.ctx.poison(L.LFI_POISON_VIEWS, iw._byte())
         run.ctx.render("STD")
-        if st.variant[0] != "auto" and not st.flags & (DEEP | IN_FRAME):
+        if st.variant[0] != "auto" and not st.flags & VIEW_FLAGS:
             assert run.ctx.last_kernel_name() == KERNEL_OF[st.variant[0]], ("the STD variant was lost", run.ctx.last_kernel_name())
         return run.ctx.download_views()
 
     def want(self, oc, st, run=None):
         if st.flags & IN_FRAME:
             return _cached("inframe_std", st, lambda: _rgba(_inframe(oc, st).bytes))
+        if st.flags & LINEAR:
+            return _cached("linear_std", st, lambda: _rgba(_linear(oc, st).bytes))
         return super().want(oc, st)
 
     def check(self, got, want, st):
@@ -410,7 +422,7 @@ class Ten(FromReader):
         self.name = "ten_wm"
 
     def mode(self, st):
-        if st.flags & (DEEP | IN_FRAME | PER_BATCH):
+        if st.flags & (VIEW_FLAGS | PER_BATCH):
             return SKIP(FLAGGED)
         return _fixed_mode(st)
 
@@ -420,7 +432,7 @@ class Ten(FromReader):
         run.ctx.render("TEN_WM")
         kernel = run.ctx.last_kernel_name()
         if st.variant[1] != "auto":
-            assert kernel == KERNEL_OF[st.variant[1]], ("the TEN_WM variant was lost", kernel)
+            assert kernel == ten_kernel_of(st), ("the TEN_WM variant was lost", kernel, ten_kernel_of(st))
         return run.ctx.download_views(), kernel
 
     def check(self, got, want, st):
@@ -438,7 +450,7 @@ class StdVariant(Std):
     def mode(self, st):
         if st.inputs == "released":
             return SKIP("the variant's kernel is not one of those the planar copy alone serves")
-        return SKIP(FLAGGED) if st.flags & (DEEP | IN_FRAME) else _fixed_mode(st)
+        return SKIP(FLAGGED) if st.flags & VIEW_FLAGS else _fixed_mode(st)
 
     def read(self, oc, run, st):
         run.ctx.poison(L.LFI_POISON_VIEWS, iw._byte())
@@ -476,7 +488,7 @@ class ViewRowsProbe(FromReader):
             return SKIP("the ramp's rows reach beyond the rows the window holds; tests/view_rows.py has windowed rows")
         if st.inputs == "released":
             return SKIP("served or refused by the copy's padding, which the history of the context decides; tests/view_rows.py holds both")
-        if st.flags & (DEEP | IN_FRAME):
+        if st.flags & VIEW_FLAGS:
             return REFUSED("per-view rows (lfi_set_view_offsets, lfi_set_view_float_offsets) are not supported")
         if st.flags & PER_BATCH:
             return REFUSED("LFI_FLAG_TEN_ROUND_PER_BATCH is not supported")
@@ -490,7 +502,7 @@ class AllFocusProbe(FromReader):
     def mode(self, st):
         if st.rows_kind:
             return SKIP(ROWS_STATE)
-        if st.flags & (DEEP | IN_FRAME):       # asked first: launch_blend turns to the flagged route before anything else
+        if st.flags & VIEW_FLAGS:       # asked first: launch_blend turns to the flagged route before anything else
             return REFUSED("all-focus renders are not supported")
         if st.inputs == "released":
             return REFUSED(RELEASED)
@@ -582,6 +594,11 @@ def _rgba(rgb):
 def _inframe(oc, st):
     s = shadow(oc, st)
     return _cached("inframe", st, lambda: inframe_ref.restate(s.grid, s.params(L)))
+
+
+def _linear(oc, st):
+    s = shadow(oc, st)
+    return _cached("linear", st, lambda: linear_ref.restate(s.grid, s.params(L)))
 
 
 class StateRows(Probe):
@@ -701,6 +718,60 @@ class InFrameTen(Probe):
         return [want[0]]
 
 
+class LinearStd(Probe):
+    """LFI_FLAG_LINEAR_LIGHT, STD: `==` linear_ref's restatement, by blend_linear; and the deep views of an earlier deep render are gone — a
+    linear-light launch writes the views without their deep planes (the hand-over linear <-> deep)"""
+    name = "linear_std"
+    calls = ("lfi_render", "lfi_download_view", "lfi_debug_poison", "lfi_last_kernel_name", "lfi_download_views_yuv")
+    method, kernel = "STD", "blend_linear<STD>"
+
+    def counterpart(self, st):
+        """the probe whose answer a context that ignored the flag would give"""
+        return "std"
+
+    def mode(self, st):
+        return RUN if st.flags & LINEAR and st.layout == "planar" else SKIP("LFI_FLAG_LINEAR_LIGHT is not set, or std holds its refusal of the RGBA layout")
+
+    def depends(self, st):
+        return super().depends(st) + (st.flags & LINEAR,)
+
+    def want(self, oc, st, run=None):
+        return _rgba(_linear(oc, st).bytes)
+
+    def read(self, oc, run, st):
+        poison.render(run.ctx, self.method)
+        kernel = run.ctx.last_kernel_name()
+        refused(run, "LFI_YUV_DEEP", lambda: run.ctx.download_deep_views())
+        return run.ctx.download_views(), kernel
+
+    def check(self, got, want, st):
+        views, kernel = got
+        assert kernel == self.kernel, kernel
+        assert (views == want).all(), ("linear-light STD", int((views != want).sum()))
+
+
+class LinearTen(LinearStd):
+    """LFI_FLAG_LINEAR_LIGHT, TEN_WM: inside linear_ref.ten_interval_of"""
+    name = "linear_ten_wm"
+    method, kernel = "TEN_WM", "blend_linear<TEN_WM>"
+
+    def counterpart(self, st):
+        return "ten_wm"
+
+    def want(self, oc, st, run=None):
+        s = shadow(oc, st)
+        return _cached("linear_ten", st, lambda: linear_ref.ten_interval_of(_linear(oc, st), s.params(L), st.n))
+
+    def check(self, got, want, st):
+        views, kernel = got
+        assert kernel == self.kernel, kernel
+        out = ten_interval.outside(views, *want)
+        assert out == 0, ("linear-light TEN_WM bytes outside their interval", out)
+
+    def flat(self, want):
+        return [want[0]]
+
+
 class PerBatch(Probe):
     """LFI_FLAG_TEN_ROUND_PER_BATCH: the M16 model byte for byte"""
     name = "ten_wm_per_batch"
@@ -730,7 +801,7 @@ class RenderStream(Probe):
     def mode(self, st):
         if st.rows_kind:
             return SKIP(ROWS_STATE)
-        if st.flags & (DEEP | IN_FRAME):
+        if st.flags & VIEW_FLAGS:
             return REFUSED("lfi_render_stream is not supported")
         if st.layout != "rgba":
             return REFUSED("downloads need the RGBA view layout")
@@ -779,7 +850,7 @@ class KeepCompare(Probe):
     calls = ("lfi_keep_views", "lfi_compare_views", "lfi_render", "lfi_download_view", "lfi_debug_poison", "lfi_sync")
 
     def mode(self, st):
-        if st.flags & (DEEP | IN_FRAME | PER_BATCH):
+        if st.flags & (VIEW_FLAGS | PER_BATCH):
             return SKIP(FLAGGED)
         if st.rows_kind:
             return SKIP(ROWS_STATE)
@@ -832,7 +903,7 @@ class OutputProbe(Probe):
     refusal = None     # under a row window
 
     def mode(self, st):
-        if st.flags & (DEEP | IN_FRAME):
+        if st.flags & VIEW_FLAGS:
             return SKIP(FLAGGED)
         if st.rows_kind:
             return SKIP(ROWS_STATE)
@@ -1032,7 +1103,7 @@ class YuvUpload(Probe):
     writer = next(w for w in iw.WRITERS if w.name == "upload_images_yuv_i420_host")
 
     def mode(self, st):
-        if st.flags & (DEEP | IN_FRAME):
+        if st.flags & VIEW_FLAGS:
             return SKIP(FLAGGED)
         if st.rows_kind:
             return SKIP(ROWS_STATE)
@@ -1078,7 +1149,7 @@ PROBES = [
     FocusProbe(_R["focus_map_plain"], _FOCUS, W_COVER, _FMAP),
     FocusProbe(_R["view_focus_maps_then_focus_map"], _FOCUS + ("lfi_set_view_float_offsets", "lfi_view_focus_maps", "lfi_download_view_map"), W_FOCUS, _FMAP + ("V",)),
     FocusProbe(_R["focus_tiles_3x2"], ("lfi_focus_tiles",), W_FOCUS, _F32), FocusProbe(_R["focus_curve_rectangle"], ("lfi_focus_curve",), W_FOCUS, _F32),
-    DerivedProbe(), StateRows(), DeepProbe(), InFrameTen(), PerBatch(), RenderStream(), KeepCompare(), QuiltTiles(), QuiltScaled(), Yuv420(),
+    DerivedProbe(), StateRows(), DeepProbe(), InFrameTen(), LinearStd(), LinearTen(), PerBatch(), RenderStream(), KeepCompare(), QuiltTiles(), QuiltScaled(), Yuv420(),
     ViewsYuv("i420"), ViewsYuv("nv12"), ViewsYuv("p010"), QuiltYuv(), RgbdYuv(), Native(False), Native(True), YuvUpload(),
 ]
 assert len({p.name for p in PROBES}) == len(PROBES)
@@ -1176,7 +1247,8 @@ BAND_LARGER = replace(TALL, window=(8, 24))      # held rows (7, 25)
 BAND_ELSEWHERE = replace(TALL, window=(22, 30))  # as many rows as BAND, other rows: every kept buffer has the right size and the wrong rows
 SMALL_P = replace(SMALL, layout="planar")
 FAR = replace(SMALL, focus=iw.FOCUS_LARGE)
-FAR_P = replace(FAR, layout="planar")            # the two flags want the planar layout, and offsets that leave the frame
+FAR_P = replace(FAR, layout="planar")            # the three view flags want the planar layout, and offsets that leave the frame
+LINEAR_P = replace(FAR_P, flags=LINEAR)
 VIEW_MAPS = replace(SMALL, rows_kind="view_maps")
 VARIANT = replace(SMALL, variant=OTHER_KERNELS)
 
@@ -1203,6 +1275,13 @@ CHANGES = (
     + _both("params_focus_far", "set_params", SMALL, FAR)                                # planar_reach and pad_shift grow, then are larger than needed
     + _both("params_flag_deep", "set_params", FAR_P, replace(FAR_P, flags=DEEP))
     + _both("params_flag_in_frame", "set_params", FAR_P, replace(FAR_P, flags=IN_FRAME))
+    + _both("params_flag_linear", "set_params", FAR_P, LINEAR_P)
+    # from one flagged kernel to another: linear <-> deep (the deep views go, the planes stay allocated with the views: _check_memory) and
+    # linear <-> in-frame; then the flag kept across another view count and across lfi_set_grid
+    + _both("params_flag_linear_deep", "set_params", LINEAR_P, replace(FAR_P, flags=DEEP))
+    + _both("params_flag_linear_in_frame", "set_params", LINEAR_P, replace(FAR_P, flags=IN_FRAME))
+    + [_c("linear_then_more_views", "set_params", LINEAR_P, replace(LINEAR_P, V=70), sizes=(("V", "grows"),)),
+       _c("linear_then_set_grid", "set_grid", LINEAR_P, replace(LINEAR_P, W=300), sizes=(("W", "grows"),))]
     + _both("params_flag_per_batch", "set_params", SMALL, replace(SMALL, flags=PER_BATCH))
     + _both("params_weights_wide", "set_params", SMALL, replace(SMALL, wide=True))       # weights_scalable
     # lfi_set_output_layout
@@ -1392,10 +1471,11 @@ STEPS = [
     ("set_params", "focus", lambda s: replace(s, focus=iw.FOCUS_LARGE if s.focus == 0.05 else 0.05) if not s.windowed and s.inputs != "released" else None, None),
     ("set_params", "deep", lambda s: replace(s, flags=DEEP, wide=False, rows_kind=None) if s.layout == "planar" and not s.windowed and not s.flags and s.variant == AUTO else None, None),
     ("set_params", "in_frame", lambda s: replace(s, flags=IN_FRAME, wide=False, rows_kind=None) if s.layout == "planar" and not s.windowed and not s.flags and s.variant == AUTO else None, None),
+    ("set_params", "linear", lambda s: replace(s, flags=LINEAR, wide=False, rows_kind=None) if s.layout == "planar" and not s.windowed and not s.flags and s.variant == AUTO else None, None),
     ("set_params", "per_batch", lambda s: replace(s, flags=PER_BATCH, rows_kind=None) if not s.windowed and not s.flags and s.inputs != "released" and s.variant == AUTO else None, None),
     ("set_params", "no_flags", lambda s: replace(s, flags=0) if s.flags else None, None),
-    ("set_params", "weights", lambda s: replace(s, wide=not s.wide) if not s.windowed and not s.flags & (DEEP | IN_FRAME) and s.inputs != "released" and s.variant == AUTO else None, None),
-    ("set_output_layout", "layout", lambda s: replace(s, layout="planar" if s.layout == "rgba" else "rgba", views=0) if not s.flags & (DEEP | IN_FRAME) else None, None),
+    ("set_params", "weights", lambda s: replace(s, wide=not s.wide) if not s.windowed and not s.flags & VIEW_FLAGS and s.inputs != "released" and s.variant == AUTO else None, None),
+    ("set_output_layout", "layout", lambda s: replace(s, layout="planar" if s.layout == "rgba" else "rgba", views=0) if not s.flags & VIEW_FLAGS else None, None),
     ("attach_views", "attach", lambda s: replace(s, views=max(s.V, 7)) if not s.views else None, None),
     ("attach_grid", "attach", lambda s: replace(s, inputs="attached", seed=s.seed ^ 0x3131) if s.inputs == "owned" else None, None),
     ("attach_grid", "back_to_owned", lambda s: _plain(s, layout=s.layout) if s.inputs == "attached" else None, "grid"),
@@ -1415,7 +1495,7 @@ def _rows_ok(s):
     return not s.windowed and s.inputs == "owned" and not s.flags and s.variant == AUTO
 
 
-def walk(n=40, seed=20320):
+def walk(n=40, seed=20992):
     """[(family, name, after-state, again)]: a seeded walk from SMALL; a drawn step that does not apply in the current state gives way to the
     next drawn one.  tests/test_context_reuse_table.py holds the walk to every family and to both directions of N, W, H, V and the held rows."""
     rng = np.random.default_rng(seed)

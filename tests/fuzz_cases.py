@@ -1,5 +1,5 @@
 """Randomised parity cases shared by tests/test_gpu_fuzz.py (fixed seeds, a bounded number of cases) and the soak tools under
-tools/ (fuzz_parity.py, fuzz_focus.py, fuzz_allfocus.py, fuzz_view_rows.py: any number of cases, any seed).
+tools/ (fuzz_parity.py, fuzz_focus.py, fuzz_allfocus.py, fuzz_view_rows.py, fuzz_flagged.py: any number of cases, any seed).
 
 Every function renders random small shapes through the HIP library (the C-ABI) and checks them against the CPU oracle — STD and
 focus maps bit-exact, TEN_WM within one LSB of the fp16-accumulate model M16 and inside the interval of the exact sum
@@ -8,6 +8,9 @@ focus maps bit-exact, TEN_WM within one LSB of the fp16-accumulate model M16 and
 """
 import numpy as np
 
+import deep_ref
+import inframe_ref
+import linear_ref
 import poison
 import ten_interval
 import view_rows
@@ -299,4 +302,223 @@ def fuzz_view_rows(L, oc, n_cases: int, seed: int, log=None) -> list:
         ctx.close()
         if log and (i + 1) % 20 == 0:
             log(f"{i + 1} cases, {len(bad)} mismatches")
+    return bad
+
+
+# ---- the flagged fixed-focus renders: deep_blend, blend_inframe, blend_linear (csrc/hip/blend_tile16.hpp) -------------------------------------------
+# The draw is stratified, not free: case i takes entry i (cyclically, after one seeded shuffle per list) of each list, so that 24 cases show every
+# value.  Images: one k-step of 16 (2, 3, 9: the lane-to-image clamp), of 32 (17, 32), a second k-step half unfetched (33, 48), one chunk (64), a
+# second chunk of 16 (65, 80), a third chunk of 16 (129), a last chunk of 48 (225).  Widths: the ragged 8-byte store and the pitch padding it
+# relies on (1, 4, 7, 9, 31, 100, 127, 129, 191, 257, 300), whole pieces (8, 64, 128).  Views: the wave boundaries (1, 15, 16, 17), one pass
+# (64), a second (65), a third (129, 150).
+FLAGGED_GRIDS = [(2, 1), (3, 1), (3, 3), (17, 1), (8, 4), (11, 3), (8, 6), (8, 8), (13, 5), (10, 8), (43, 3), (15, 15)]
+FLAGGED_WIDTHS = [1, 4, 7, 8, 9, 31, 64, 100, 127, 128, 129, 191, 257, 300]
+FLAGGED_VIEWS = [1, 3, 15, 16, 17, 64, 65, 129, 150]
+FLAGGED_BUDGET = 120_000      # V·W·H of a stratified case: its CPU reference stays cheap.  (A third of it bought no time — the tests' cost is per view — and lost W = 300 beside V = 150: DESIGN.md §7)
+# more tiles than the grid's 2 x CUs workgroups (512): every workgroup walks on to a second tile
+FLAGGED_TILE_WALK = [dict(cols=17, rows=1, W=300, H=200, V=2), dict(cols=11, rows=3, W=64, H=1100, V=3)]
+FLAGGED_KERNEL = {deep_ref.FLAG_DEEP_VIEWS: "deep_blend<{}>", inframe_ref.FLAG_IN_FRAME: "blend_inframe<{}>", linear_ref.FLAG_LINEAR_LIGHT: "blend_linear<{}>"}
+# the offset sets a flag renders, in order; lfi_release_inputs follows the last
+FLAGGED_SETS = {deep_ref.FLAG_DEEP_VIEWS: ("wide",), inframe_ref.FLAG_IN_FRAME: ("wide", "near"), linear_ref.FLAG_LINEAR_LIGHT: ("wide",)}
+PLANAR_REFUSAL = "the planar copy of the inputs cannot serve these offsets"
+# what tests/test_gpu_fuzz.py runs and tests/test_fuzz_flagged_table.py holds to the draw's conditions on the CPU
+FLAGGED_CASES = 24
+FLAGGED_SEED = {deep_ref.FLAG_DEEP_VIEWS: 7, inframe_ref.FLAG_IN_FRAME: 8, linear_ref.FLAG_LINEAR_LIGHT: 9}
+
+
+def flagged_wide(i, W, H):
+    """(ax, ay) of case i's `wide` offsets: none; one pixel; inside a lane's 8 pixels and beyond; the whole frame but one pixel; beyond the frame
+    (the clamp is served by the planar copy's padding, in-frame masks everything out)"""
+    return [(0, 0), (1, 1), (9, 2), (W - 1, H - 1), (W + 5, H + 2)][i % 5]
+
+
+def flagged_near(n, W, H):
+    """(ax, ay) of a case's `near` offsets: a quarter of the frame.  Narrowed for grids of fewer than 9 images to a sixteenth of the width: there
+    a view may rest on one image whose weight is tiny, r = wall / den reaches 64 wherever the other is out of frame and scales the TEN_WM bound
+    with it — at W // 4 the two-valued share of such a case (2 images, 300 x 6) was 2.8 %, over the cap of 2 %"""
+    return (max(1, W // (4 if n >= 9 else 16)), H // 4)
+
+
+def flagged_cases(n_cases, seed):
+    """the draw: n_cases stratified cases and the two tile-walk cases, as dicts of plain values and small arrays; numpy alone"""
+    rng = np.random.default_rng(seed)
+    grids, widths, views = ([lst[int(k)] for k in rng.permutation(len(lst))] for lst in (FLAGGED_GRIDS, FLAGGED_WIDTHS, FLAGGED_VIEWS))
+    flat = {int(k) for k in rng.choice(n_cases, min(2, n_cases), replace=False)}     # H = 1 forced
+    out, over64, crossing = [], 0, 0
+    for i in range(n_cases + len(FLAGGED_TILE_WALK)):
+        if i < n_cases:
+            (cols, rows), W, V = grids[i % len(grids)], widths[i % len(widths)], views[i % len(views)]
+            H = 1 if i in flat else int(rng.integers(1, 7))
+            tries = 0
+            while V * W * H > FLAGGED_BUDGET:     # redraw H (a forced H = 1 stays), then V: the lists of n and W never shrink
+                if tries < 8 and i not in flat:
+                    H = int(rng.integers(1, 7))
+                else:
+                    V = int(rng.choice(FLAGGED_VIEWS))
+                tries += 1
+        else:
+            t = FLAGGED_TILE_WALK[i - n_cases]
+            cols, rows, W, H, V = t["cols"], t["rows"], t["W"], t["H"], t["V"]
+        n = cols * rows
+        traj = str(rng.choice(["0,0,1,1", "0.071,0.071,0.93,0.93", "1,0,0,1", "0.5,0.5,0.5,0.5", "0.2,0.9,0.8,0.1"]))
+        effect = float(rng.choice([1.0, 3.0, 7.0]))
+        case = dict(kind="flagged", i=i, cols=cols, rows=rows, W=W, H=H, V=V, traj=traj, effect=effect, lf_seed=int(rng.integers(1, 1 << 30)))
+        case["reach"] = dict(wide=flagged_wide(i, W, H), near=flagged_near(n, W, H))
+        case["offsets"] = {k: np.stack([rng.integers(-ax, ax + 1, n), rng.integers(-ay, ay + 1, n)], axis=1).astype(np.int32) for k, (ax, ay) in case["reach"].items()}
+        # the exact rows (linear_ref.exact_rows): one-hot on a drawn image, one-hot on image n − 1, two halves on two drawn images
+        k = min(V, 3)
+        case["exact_views"] = [int(v) for v in rng.choice(V, k, replace=False)]
+        pair = [int(g) for g in rng.choice(n, 2, replace=False)]
+        case["exact_images"] = [(int(rng.integers(0, n)),), (n - 1,), tuple(pair)][:k]
+        # the view range; half of the cases with V > 64 cross a 64-view pass from an unaligned start, where there is room for one
+        v0 = int(rng.integers(0, V))
+        v1 = int(rng.integers(v0 + 1, V + 1))
+        if V > 64:
+            over64 += 1
+            if V >= 82 and 2 * crossing < over64:
+                crossing += 1
+                v0 = int(rng.integers(1, 16))
+                v1 = int(rng.integers(v0 + 65, V + 1))
+        case["v0"], case["v1"] = v0, v1
+        out.append(case)
+    return out
+
+
+def flagged_label(case, **more):
+    """a case as the plain values a mismatch reports"""
+    return dict({k: v for k, v in case.items() if k != "offsets"}, **more)
+
+
+def flagged_params(L, case, which):
+    """the host parameters of a case under its `wide` or `near` offsets: build_params' weights with the exact rows in place"""
+    hp = L.build_params(case["cols"], case["rows"], case["W"], case["H"], case["traj"], 0.0, 0.0, case["effect"], 1.783, case["V"])
+    w = hp.weights.copy()
+    one, half = np.float16(1.0).view(np.uint16), np.float16(0.5).view(np.uint16)
+    for v, images in zip(case["exact_views"], case["exact_images"]):
+        w[v, :] = 0
+        w[v, list(images)] = one if len(images) == 1 else half
+    return L.host.HostParams(np.ascontiguousarray(case["offsets"][which], np.int32), hp.offsets, w, hp.focus_map_ids, hp.focus, hp.range, hp.block_radius)
+
+
+class FlaggedWant:
+    """what a flag's renders of a case must be.  hp, lf; std [V][H][W][3] uint8: the STD bytes; lo, hi: the TEN_WM bytes' interval; exact
+    [rows][H][W][3]: the TEN_WM bytes of the exact rows.  Deep views also: codes (STD), lo10, hi10, exact10 (TEN_WM), and lo, hi are
+    ten_interval.bounds.  res: the restatement (in-frame, linear light)"""
+
+
+def flagged_reference(L, oc, case, flag, which):
+    want = FlaggedWant()
+    hp = want.hp = flagged_params(L, case, which)
+    n = case["cols"] * case["rows"]
+    lf = want.lf = oc.synthetic_lf(n, case["W"], case["H"], case["lf_seed"])
+    rows = case["exact_views"]
+    want.res = None
+    if flag == deep_ref.FLAG_DEEP_VIEWS:
+        std, pre = oc.blend_std(lf, hp.focused_offsets, hp.offsets, hp.weights, return_prequant=True, threads=8)
+        S, eps = ten_interval.exact_sums(oc, lf, hp, threads=8)
+        want.std, want.codes = std[..., :3], deep_ref.q10_std(pre)
+        want.lo10, want.hi10 = deep_ref.interval10(S, eps)
+        want.lo, want.hi = ten_interval.interval(S, eps)
+        want.exact10 = deep_ref.q10_ten(S[rows])
+        want.exact = (want.exact10 >> 2).astype(np.uint8)
+    elif flag == inframe_ref.FLAG_IN_FRAME:
+        res = want.res = inframe_ref.restate(lf, hp)
+        want.std = res.bytes
+        want.lo, want.hi = inframe_ref.ten_interval_of(res, hp, n)
+        want.exact = inframe_ref.ten_exact(res)[rows]
+    else:
+        res = want.res = linear_ref.restate(lf, hp)
+        want.std = res.bytes
+        want.lo, want.hi = linear_ref.ten_interval_of(res, hp, n)
+        want.exact = res.bytes[rows]
+    return want
+
+
+def _flagged_compare(method, views, codes, want, a, b, rows):
+    """the nonzero counts of what is wrong with views [a, b) as downloaded (codes: the deep views', or None)"""
+    c = views[..., :3]
+    found = dict(alpha_not_255=int((views[..., 3] != 255).sum()))
+    if method == "STD":
+        found["wrong_bytes"] = int((c != want.std[a:b]).sum())
+        if codes is not None:
+            found["wrong_codes"] = int((codes != want.codes[a:b]).sum())
+    else:
+        found["outside_interval"] = int(((c < want.lo[a:b]) | (c > want.hi[a:b])).sum())
+        inside = [(k, v) for k, v in enumerate(rows) if a <= v < b]
+        found["exact_rows_wrong"] = sum(int((c[v - a] != want.exact[k]).sum()) for k, v in inside)
+        if codes is not None:
+            found["codes_outside_interval"] = int(((codes < want.lo10[a:b]) | (codes > want.hi10[a:b])).sum())
+            found["code_is_not_the_byte"] = int((codes >> 2 != c).sum())
+            found["exact_rows_wrong"] += sum(int((codes[v - a] != want.exact10[k]).sum()) for k, v in inside)
+    return {k: v for k, v in found.items() if v}
+
+
+def fuzz_flagged(L, oc, flag, n_cases: int, seed: int, log=None) -> list:
+    """The flagged fixed-focus renders (launch_flagged_views: deep_blend under LFI_FLAG_DEEP_VIEWS, blend_inframe under LFI_FLAG_IN_FRAME,
+    blend_linear under LFI_FLAG_LINEAR_LIGHT): n_cases stratified cases (flagged_cases) and the two tile-walk cases, one context each, the inputs
+    uploaded, the planar layout, explicit integer offsets (`wide`; in-frame: `wide`, then `near`).  Every render under poison.  STD bytes (and
+    deep codes) `==` the reference; TEN_WM bytes (and codes) inside the flag's own interval, the exact rows `==`, alpha 255; a view range writes
+    its views only and the same bytes; the kernel is the flag's; after lfi_release_inputs the same bytes.  A release or a render refused
+    because the planar copy cannot serve the offsets is the case's outcome (log), not a mismatch."""
+    deep = flag == deep_ref.FLAG_DEEP_VIEWS
+    bad = []
+
+    def render(ctx, method, a=0, b=None):
+        if not deep:
+            return poison.render(ctx, method, v0=a, v1=b)
+        ctx.prepare(method, v0=a, v1=b)      # allocates the deep planes: they are poisoned with the views
+        byte = poison._byte(None)
+        ctx.poison(poison.RENDER | L.LFI_POISON_DEEP, byte)
+        ctx.render(method, v0=a, v1=b)
+        ctx.sync()
+        return byte
+
+    for case in flagged_cases(n_cases, seed):
+        V, v0, v1, rows = case["V"], case["v0"], case["v1"], case["exact_views"]
+        ctx = L.Context(0)
+        ctx.set_grid(case["cols"], case["rows"], case["W"], case["H"])
+        ctx.set_output_layout("planar")
+        outcome = "served"
+        for which in FLAGGED_SETS[flag]:
+            want = flagged_reference(L, oc, case, flag, which)
+            if which == FLAGGED_SETS[flag][0]:
+                ctx.upload_grid(want.lf)
+            ctx.set_params(want.hp, flags=flag)
+            last = which == FLAGGED_SETS[flag][-1]
+            before = codes_before = None     # the TEN_WM bytes (and codes) before the release; None where that render was refused
+            for released in ((False, True) if last else (False,)):
+                try:
+                    if released:
+                        ctx.release_inputs()
+                    for method in ("STD", "TEN_WM"):
+                        render(ctx, method)
+                        found = {} if ctx.last_kernel_name() == FLAGGED_KERNEL[flag].format(method) else dict(kernel=ctx.last_kernel_name())
+                        full, codes = ctx.download_views(), ctx.download_deep_views() if deep else None
+                        found.update(_flagged_compare(method, full, codes, want, 0, V, rows))
+                        if released:
+                            if method == "TEN_WM" and before is not None and (not (full == before).all() or (deep and not (codes == codes_before).all())):
+                                found["not_the_bytes_before_the_release"] = True
+                        else:
+                            if method == "TEN_WM":
+                                before, codes_before = full, codes
+                            byte = render(ctx, method, v0, v1)
+                            stray = poison.written_outside(ctx, v0, v1, byte)
+                            part, pcodes = ctx.download_views(v0, v1), ctx.download_deep_views(v0, v1 - v0) if deep else None
+                            ranged = _flagged_compare(method, part, pcodes, want, v0, v1, rows)
+                            if stray:
+                                ranged["written_outside"] = stray[:8]
+                            if method == "TEN_WM" and (not (part == full[v0:v1]).all() or (deep and not (pcodes == codes[v0:v1]).all())):
+                                ranged["not_the_full_renders_bytes"] = True
+                            if ranged:
+                                found["range"] = ranged
+                        if found:
+                            bad.append(flagged_label(case, what=method, offsets=which, released=released, **found))
+                except L.LfiError as e:
+                    if released and PLANAR_REFUSAL in str(e):
+                        outcome = "refused after the release: " + str(e)
+                    else:
+                        bad.append(flagged_label(case, what="refused", offsets=which, released=released, error=str(e)))
+        ctx.close()
+        if log:
+            log(f"case {case['i']}: {case['cols']}x{case['rows']} images, {case['W']}x{case['H']}, {V} views, range [{v0}, {v1}): {outcome}; {len(bad)} mismatches")
     return bad

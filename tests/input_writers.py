@@ -16,7 +16,8 @@ synthetic_lf, never from the device.  lfi_fill_synthetic_scene had no restatemen
 the formula in the comment above fill_scene (csrc/hip/focus_map.hpp).
 
 A reader is held to the CPU oracle on the shadow grid: STD renders, focus maps, per-view maps and focus curves byte for byte, TEN_WM as
-fuzz_cases.fuzz_blend holds it (within one LSB of M16 and inside the interval of the exact sum, tests/ten_interval.py).
+fuzz_cases.fuzz_blend holds it (within one LSB of M16 and inside the interval of the exact sum, tests/ten_interval.py); the flagged
+fixed-focus renders (LFI_FLAG_DEEP_VIEWS, LFI_FLAG_IN_FRAME, LFI_FLAG_LINEAR_LIGHT) as fuzz_cases.fuzz_flagged holds them.
 
 Limits: at these shapes a missing stream wait may go unobserved — the copies take microseconds.  The tests hold the version bookkeeping
 and the routing; they do not hold the races.  tests/stream_order.py does: every asynchronous writer here is issued there behind a stalled stream.
@@ -26,9 +27,12 @@ from dataclasses import dataclass
 
 import numpy as np
 
+import deep_ref
 import derived_ref
 import focus_curve_ref as fref
 import focus_steps_ref
+import inframe_ref
+import linear_ref
 import mosaic_ref as mref
 import ten_interval
 import view_rows
@@ -763,12 +767,79 @@ class Derived(Reader):
         assert (got == want).all(), ("the planar copy", int((got != want).sum()), np.argwhere((got != want).any(axis=(1, 2, 3))).ravel().tolist())
 
 
+class Flagged(Reader):
+    """a fixed-focus render under a parameter flag (launch_flagged_views, which has its own copy of the join_uploads / ensure_planar /
+    set_planar_args sequence): deep_blend, blend_inframe or blend_linear from the planar copy, before and after lfi_release_inputs.  prepare
+    sets the shadow's parameters with the flag — before the writer — and the planar view layout, which the flags need whatever the steps
+    left; done puts the parameters back without it.  The want is the reference tests/fuzz_cases.py::fuzz_flagged holds the kernels to:
+    deep STD bytes and codes `==` the oracle's chain, in-frame and linear-light STD `==` their restatements, linear-light TEN_WM inside the
+    interval of the exact sum"""
+    released = True
+    KERNEL = {deep_ref.FLAG_DEEP_VIEWS: "deep_blend", inframe_ref.FLAG_IN_FRAME: "blend_inframe", linear_ref.FLAG_LINEAR_LIGHT: "blend_linear"}
+
+    def __init__(self, name, flag, method):
+        self.name, self.flag, self.method = name, flag, method
+        self.deep = flag == deep_ref.FLAG_DEEP_VIEWS
+        self._hp = None
+
+    def want(self, oc, L, s, ctx=None):
+        hp = s.params(L)
+
+        def compute():
+            if self.deep:
+                out, pre = oc.blend_std(s.grid, hp.focused_offsets, hp.offsets, hp.weights, return_prequant=True, threads=8)
+                return out[..., :3], deep_ref.q10_std(pre)
+            if self.flag == inframe_ref.FLAG_IN_FRAME:
+                return (inframe_ref.restate(s.grid, hp).bytes,)
+            res = linear_ref.restate(s.grid, hp)
+            return (res.bytes,) if self.method == "STD" else linear_ref.ten_interval_of(res, hp, s.shape.n) + (res.bytes,)
+        return _cached(self.name, s, compute)
+
+    def flat(self, want):
+        """the stale-copy self-check compares bytes a render would write (TEN_WM: the restatement's, which lie inside the interval), not bounds"""
+        return [np.asarray(w) for w in (want[2:] if self.method == "TEN_WM" else want)]
+
+    def prepare(self, L, ctx, s, fixed=True):
+        if s.layout != "planar":
+            ctx.set_output_layout("planar")
+            s.layout = "planar"
+        self._hp = s.params(L)
+        ctx.set_params(self._hp, flags=self.flag)
+        ctx.poison(L.LFI_POISON_VIEWS | (L.LFI_POISON_DEEP if self.deep else 0), _byte())   # (the deep planes: where an earlier read left them)
+
+    def read(self, L, ctx, s):
+        ctx.render(self.method)
+        return ctx.download_views(), ctx.download_deep_views() if self.deep else None, ctx.last_kernel_name()
+
+    def check(self, got, want):
+        views, codes, kernel = got
+        assert kernel == f"{self.KERNEL[self.flag]}<{self.method}>", kernel
+        assert (views[..., 3] == 255).all(), (self.name, "alpha")
+        c = views[..., :3]
+        if self.method == "TEN_WM":
+            lo, hi, _ = want
+            out = int(((c < lo) | (c > hi)).sum())
+            assert out == 0, (self.name, "bytes outside the interval", out)
+            return
+        assert (c == want[0]).all(), (self.name, int((c != want[0]).sum()), np.argwhere((c != want[0]).any(axis=(1, 2, 3))).ravel().tolist())
+        if self.deep:
+            assert (codes == want[1]).all(), (self.name, "codes", int((codes != want[1]).sum()))
+
+    def done(self, ctx):
+        if self._hp is not None:
+            ctx.set_params(self._hp)
+            self._hp = None
+
+
 READERS = [Std(), TenPlanar(), ViewRows(), AllFocus(), FocusMap("factored"), FocusMap("factored_direct"), FocusMap("plain"), ViewFocusMaps(),
-           FocusTiles(), FocusCurve(), Derived()]
+           FocusTiles(), FocusCurve(), Derived(),
+           Flagged("deep_std", deep_ref.FLAG_DEEP_VIEWS, "STD"), Flagged("inframe_std", inframe_ref.FLAG_IN_FRAME, "STD"),
+           Flagged("linear_std", linear_ref.FLAG_LINEAR_LIGHT, "STD"), Flagged("linear_ten", linear_ref.FLAG_LINEAR_LIGHT, "TEN_WM")]
+FLAGGED_READERS = [r for r in READERS if isinstance(r, Flagged)]
 
 
 def readers_of(writer_or_released):
-    """the readers that apply: after lfi_release_inputs the two fixed-focus renders and the copy itself; else all but the copy's download
+    """the readers that apply: after lfi_release_inputs the fixed-focus renders, flagged ones included, and the copy itself; else all but the copy's download
     (lfi_debug_download_derived serves a current copy only, and whether it is current is what the renders show)"""
     released = writer_or_released.released if isinstance(writer_or_released, Writer) else bool(writer_or_released)
     return [r for r in READERS if (r.released if released else r.name != "download_derived")]

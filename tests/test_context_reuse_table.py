@@ -114,3 +114,22 @@ def test_the_walk_takes_every_family_and_both_directions_of_every_size():
                 ways.add((size, "grows" if y > x else "shrinks"))
         st = after
     assert ways == {(size, way) for size in ("N", "W", "H", "V", "held") for way in ("grows", "shrinks")}, sorted(ways)
+    # a linear-light state and a deep one are on the way
+    assert any(after.flags & cr.LINEAR for _, _, after, _ in steps) and any(after.flags & cr.DEEP for _, _, after, _ in steps)
+
+
+def test_the_linear_light_flag_is_a_view_flag_in_every_predicate():
+    """a linear-light state is a flagged state to every probe: none treats it as flag-free"""
+    assert cr.VIEW_FLAGS == cr.DEEP | cr.IN_FRAME | cr.LINEAR
+    plain, linear = cr.FAR_P, cr.LINEAR_P
+    modes = {p.name: (p.mode(plain), p.mode(linear)) for p in cr.PROBES}
+    assert modes["linear_std"] == (cr.SKIP("LFI_FLAG_LINEAR_LIGHT is not set, or std holds its refusal of the RGBA layout"), cr.RUN) and modes["linear_ten_wm"][1] == cr.RUN
+    assert modes["std"] == (cr.RUN, cr.RUN) and modes["std_view_range"] == (cr.RUN, cr.RUN)       # against linear_ref under the flag
+    for name in ("ten_wm", "std_variant_persist", "keep_and_compare_views", "download_quilt_scaled", "download_views_yuv420", "upload_images_yuv_then_std"):
+        assert modes[name] == (cr.RUN, cr.SKIP(cr.FLAGGED)), (name, modes[name])
+    for name in ("view_rows_planar_source", "all_focus_std_uploaded_map", "all_focus_ten_wm_uploaded_map", "render_stream"):
+        assert modes[name][1][0] == "refused", (name, modes[name])
+    assert cr.Std().mode(cr.replace(linear, layout="rgba")) == cr.REFUSED(cr.NEEDS_PLANAR)
+    assert {"params_flag_linear_up", "params_flag_linear_down", "params_flag_linear_deep_up", "params_flag_linear_deep_down", "params_flag_linear_in_frame_up",
+            "params_flag_linear_in_frame_down", "linear_then_more_views", "linear_then_set_grid"} <= {c.name for c in cr.CHANGES}
+    assert not any(c.name in cr.NO_OUTPUT_CHANGES for c in cr.CHANGES if "linear" in c.name)

@@ -129,23 +129,29 @@ CHANGERS = {"focus": _toggle_focus, "block_radius": _toggle_radius, "focus_steps
 def _schedule():
     rng = np.random.default_rng(20261)
     writers = [w for w in iw.WRITERS if not w.released]
-    readers, lean_readers = iw.readers_of(False), iw.readers_of(True)
+    flagged = iw.FLAGGED_READERS
+    readers = [r for r in iw.readers_of(False) if r not in flagged]
+    lean_readers = [r for r in iw.readers_of(True) if r not in flagged]
     steps = [("change", c) for c in CHANGERS if c != "prepare_ten_wm"] * 2 + [("change", "prepare_ten_wm")]
     steps += [("write", writers[i]) for i in rng.choice(len(writers), 11, replace=False)]
-    steps += [("read", r) for r in readers] + [("read", readers[i]) for i in rng.choice(len(readers), 12 - len(readers), replace=True)]
+    # every unflagged reader once; the two drawn reads are flagged ones — all four of which are also read before the release and at the end
+    steps += [("read", r) for r in readers] + [("read", flagged[i]) for i in rng.choice(len(flagged), 12 - len(readers), replace=False)]
     steps = [steps[i] for i in rng.permutation(len(steps))]
     lean = [w for w in iw.WRITERS if w.released]
     steps += [step for i, w in enumerate(lean) for step in (("write", w), ("read", lean_readers[i % len(lean_readers)]))]
-    assert len(steps) == 40 and len(lean) == 3
+    assert len(steps) == 40 and len(lean) == 3 and len(flagged) == 4
     return steps
 
 
 def test_long_lived_context_sequence(gpu, oracle_c):
     """40 steps on one context, fixed seed.  34 shuffled steps while the context holds its RGBA inputs: 11 writers, every state changer (each
-    toggle twice: there and back; lfi_prepare once) and 12 reads (every reader once, two more drawn).  Then every reader the state admits,
-    lfi_release_inputs, and 6 steps on the released context: each of its writers followed by a read.  The fixed-focus readers render in
-    the view layout the steps left; the plain estimate, which computes 32 candidates only, gives way to the factored one while
-    lfi_set_focus_steps is 64."""
+    toggle twice: there and back; lfi_prepare once) and 12 reads (every unflagged reader once, and two drawn flagged ones).  Then every
+    reader the state admits, the four flagged ones among them, lfi_release_inputs, and 6 steps on the released context: each of its writers
+    followed by a read; at the end every reader of a released context, the flagged ones again.  The fixed-focus readers render in the view
+    layout the steps left (the flagged ones set the planar layout, which their flags need); the plain estimate, which computes 32 candidates
+    only, gives way to the factored one while lfi_set_focus_steps is 64.  What the flagged readers cost the earlier ones, the 40 steps kept:
+    the two drawn reads used to be second reads of unflagged readers; and a flagged read leaves the view layout planar until the next
+    output_layout step, so the Std and Ten reads behind it render planar more often than a schedule without flagged reads would have them."""
     shape = iw.SHAPES[0]
     readers, lean_readers = iw.readers_of(False), iw.readers_of(True)
     steps = _schedule()

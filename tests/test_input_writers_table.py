@@ -80,7 +80,10 @@ def test_no_pair_passes_on_a_stale_copy(writer, shape, oracle_c, native):
     table = iw.stale_copy_check(oracle_c, L, shape, writer)
     assert {name for name, _, _ in table} == {r.name for r in iw.readers_of(writer)}, "a reader was skipped"
     # every reader that samples all images changes under every writer
-    assert all(must for name, _, must in table if name in ("std_rgba_layout", "ten_wm_planar_layout", "view_rows_planar_source", "all_focus_std_uploaded_map", "download_derived"))
+    assert all(must for name, _, must in table if name in ("std_rgba_layout", "ten_wm_planar_layout", "view_rows_planar_source", "all_focus_std_uploaded_map", "download_derived",
+                                                           "deep_std", "inframe_std", "linear_std", "linear_ten"))
+    # the flagged readers join every writer, released ones included
+    assert {r.name for r in iw.FLAGGED_READERS} == {"deep_std", "inframe_std", "linear_std", "linear_ten"} <= {name for name, _, _ in table}
 
 
 def test_some_pairs_must_not_change_and_most_must(native):
