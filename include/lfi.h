@@ -507,6 +507,49 @@ int lfi_focus_tiles_steps(lfi_ctx *ctx, int tiles_x, int tiles_y, int steps, uin
  * (steps / 32), or 0 where it computed the tiles with lfi_focus_curve's kernels tile by tile (0 before the first call, too) — lets a
  * test or a measurement know that the numbers are the path's it means */
 int lfi_focus_tiles_passes(const lfi_ctx *ctx);
+/* The route of the last ESTIMATE CALL of this context — lfi_focus_map, lfi_focus_tiles, lfi_focus_tiles_steps, lfi_view_focus_maps —: which
+ * estimate answered, with which kernels, over which geometry, and what the device's own plan counted.  Read-only: it lets a test (or a
+ * measurement) know that the bytes it compares are the path's it means, as lfi_last_kernel_name does for the blend.
+ *  - the names are static strings, set at the one place where each launch is chosen; "" = not applicable / nothing ran;
+ *  - estimate: "factored" | "factored_direct" (the factored estimate, focus_factored.hpp, with its own or the direct range pass) |
+ *    "packed_p2" | "lds" | "plain" (the one-kernel estimates, also where the factored one declined) | "row_window" (lfi_focus_map on a row
+ *    window) | "focus_curve" (lfi_focus_tiles* tile by tile with lfi_focus_curve's kernels);
+ *  - declined: "" or why the factored estimate declined before it reserved or enqueued anything: "shift" (a candidate's shift of a sampled
+ *    image is absurd: |focus| * |offset| >= 1e6 pixels) or "planes" (the padded planes would take more than 16 GiB);
+ *  - everything from `passes` on describes the factored estimate and is 0 / "" otherwise.  passes: the passes of 32 candidates it ran;
+ *    range_cpw[p]: the candidates per group of pass p's range pass — 8 or 4: focus_range_t<8|4>, 0: focus_range<4> —, range_kernel and
+ *    range_striped: the LAST pass's kernel and whether its work items were dealt in stripes per XCD; consumer: what read the keys in
+ *    the pick's place — "focus_pick_sep", "focus_pick_sep_carry", "focus_pick<2>", "focus_pick_carry<2>", "focus_pick<1>",
+ *    "focus_pick_carry<1>", "focus_tile_costs<2>", "focus_tile_costs<1>" — and consumer_striped likewise;
+ *  - planes_padded / planes_kept: the padded planes (one per sampled image) the call rebuilt / found current and left alone;
+ *    pad_shift, We_p, He_p, Wp, Hp, R_cap, C_cap: the geometry of the planes, of E and of the line buffers (csrc/hip/focus_factored.hpp);
+ *  - row_entries[p] / col_entries[p]: the flagged (row, candidate) and (column, candidate) pairs of pass p as the DEVICE's plan counted
+ *    them (focus_plan_prefix); more than R_cap / C_cap of them and the pairs beyond take the tap-by-tap path.  focus_plan_prefix stores
+ *    the two totals a second time, per pass, for this call to read: the estimate itself gains no launch and no host wait;
+ *  - lfi_view_focus_maps is a batch of `jobs` estimates (one per view; 1 for the other calls): planes_padded and planes_kept are the
+ *    batch's totals, everything else is the LAST job's;
+ *  - the call synchronises the context's streams and copies 64 bytes from the device when the factored estimate ran.  LFI_EINVAL: ctx or out
+ *    NULL.  Before the first estimate call: calls = 0 and everything empty. */
+#define LFI_FOCUS_ROUTE_PASSES 8
+typedef struct lfi_focus_route {
+    int32_t calls;              /* estimate calls of this context so far that passed their argument checks (this record is call number `calls`'s) */
+    int32_t jobs;
+    const char *estimate;
+    const char *declined;
+    int32_t passes;
+    int32_t range_striped;
+    const char *range_kernel;
+    const char *consumer;
+    int32_t consumer_striped;
+    int32_t planes_padded;
+    int32_t planes_kept;
+    int32_t pad_shift[2];
+    int32_t We_p, He_p, Wp, Hp, R_cap, C_cap;
+    int32_t range_cpw[LFI_FOCUS_ROUTE_PASSES];
+    uint32_t row_entries[LFI_FOCUS_ROUTE_PASSES];
+    uint32_t col_entries[LFI_FOCUS_ROUTE_PASSES];
+} lfi_focus_route;
+int lfi_focus_route_info(lfi_ctx *ctx, lfi_focus_route *out);
 /* One launch of Tensors::process / Standard::process (src/interpolator.cu:274-288) for views [v0, v1).
  * all_focus != 0 selects the <true> instantiations (per-pixel focus from the focus map). */
 int lfi_render(lfi_ctx *ctx, int method, int all_focus, int v0, int v1);

@@ -73,7 +73,7 @@ ABI_SYMBOLS = [
     "lfi_set_variant", "lfi_list_variants", "lfi_download_coords", "lfi_download_prequant", "lfi_debug_mfma_f16",
     "lfi_grid_modified", "lfi_prepare", "lfi_memory_info", "lfi_last_kernel_name", "lfi_fill_synthetic_images", "lfi_set_output_layout", "lfi_view_layout", "lfi_fill_synthetic_scene", "lfi_upload_image_async", "lfi_upload_wait", "lfi_render_stream", "lfi_compare_view", "lfi_debug_mfma_f16_chain", "lfi_debug_pk_minmax3_f16", "lfi_std_band_info",
     "lfi_debug_poison", "lfi_set_view_offsets", "lfi_set_view_float_offsets", "lfi_view_focus_maps", "lfi_download_view_map",
-    "lfi_upload_view_map", "lfi_focus_curve", "lfi_focus_tiles", "lfi_focus_tiles_steps", "lfi_focus_tiles_passes", "lfi_download_quilt_scaled", "lfi_download_quilt_tiles_scaled",
+    "lfi_upload_view_map", "lfi_focus_curve", "lfi_focus_tiles", "lfi_focus_tiles_steps", "lfi_focus_tiles_passes", "lfi_focus_route_info", "lfi_download_quilt_scaled", "lfi_download_quilt_tiles_scaled",
     "lfi_keep_views", "lfi_compare_views", "lfi_set_focus_steps", "lfi_focus_steps", "lfi_download_native",
     "lfi_download_views_yuv420", "lfi_render_stream_yuv420", "lfi_upload_images_yuv420",
     "lfi_yuv_surfaces_check", "lfi_yuv_surfaces_packed", "lfi_upload_images_yuv", "lfi_download_views_yuv",
@@ -125,6 +125,18 @@ class StdBandInfo(C.Structure):
 
 class FocusCurveResult(C.Structure):
     _fields_ = [("best_index", C.c_int32), ("best_focus", C.c_float), ("pixels", C.c_uint64)]
+
+
+LFI_FOCUS_ROUTE_PASSES = 8
+
+
+class FocusRoute(C.Structure):
+    """lfi_focus_route: the route of the context's last estimate call (include/lfi.h).  Context.focus_route returns it as a dict."""
+    _fields_ = [("calls", C.c_int32), ("jobs", C.c_int32), ("estimate", C.c_char_p), ("declined", C.c_char_p), ("passes", C.c_int32),
+                ("range_striped", C.c_int32), ("range_kernel", C.c_char_p), ("consumer", C.c_char_p), ("consumer_striped", C.c_int32),
+                ("planes_padded", C.c_int32), ("planes_kept", C.c_int32), ("pad_shift", C.c_int32 * 2), ("We_p", C.c_int32), ("He_p", C.c_int32),
+                ("Wp", C.c_int32), ("Hp", C.c_int32), ("R_cap", C.c_int32), ("C_cap", C.c_int32), ("range_cpw", C.c_int32 * LFI_FOCUS_ROUTE_PASSES),
+                ("row_entries", C.c_uint32 * LFI_FOCUS_ROUTE_PASSES), ("col_entries", C.c_uint32 * LFI_FOCUS_ROUTE_PASSES)]
 
 
 class Lenticular(C.Structure):
@@ -278,6 +290,7 @@ def load_hip_library() -> C.CDLL:
         "lfi_focus_tiles": (i, [vp, i, i, vp, C.POINTER(FocusCurveResult)]),
         "lfi_focus_tiles_steps": (i, [vp, i, i, i, vp, C.POINTER(FocusCurveResult)]),
         "lfi_focus_tiles_passes": (i, [vp]),
+        "lfi_focus_route_info": (i, [vp, C.POINTER(FocusRoute)]),
         "lfi_render": (i, [vp, i, i, i, i]),
         "lfi_benchmark": (i, [vp, i, i, i, i, i, i, C.POINTER(BenchStats)]),
         "lfi_timer_start": (i, [vp]),
@@ -657,6 +670,23 @@ class Context:
     def focus_tiles_passes(self) -> int:
         """The factored passes the last focus_tiles call ran (steps // 32), or 0 where it took focus_curve's kernels tile by tile."""
         return int(self._lib.lfi_focus_tiles_passes(self._h))
+
+    def focus_route(self) -> dict:
+        """The route of the last estimate call — focus_map, focus_tiles, view_focus_maps — (lfi_focus_route_info): a dict of the record's
+        fields, the names as str, the arrays as lists; the per-pass arrays hold `passes` entries."""
+        r = FocusRoute()
+        self._check(self._lib.lfi_focus_route_info(self._h, C.byref(r)))
+        out = {}
+        for name, kind in FocusRoute._fields_:
+            v = getattr(r, name)
+            if kind is C.c_char_p:
+                v = (v or b"").decode()
+            elif not isinstance(v, int):
+                v = [int(x) for x in v]
+                if len(v) == LFI_FOCUS_ROUTE_PASSES:
+                    v = v[:r.passes]
+            out[name] = v
+        return out
 
     def view_focus_maps(self, ids_vk: np.ndarray) -> None:
         """Per-view focus maps (lfi_view_focus_maps): ids_vk is [views][n_ids] int32 — row v = the images view v's map samples

@@ -52,7 +52,8 @@ struct FocusWork
     uint16_t *rows;     // [32][H]
     int32_t *ncols;     // [32]
     int32_t *nrows;     // [32]
-    uint32_t *prefix;   // [3][33] prefix sums over the candidates of nrows, of ncols and of ceil(ncols/64) (column chunks)
+    uint32_t *prefix;   // [3][33] prefix sums over the candidates of nrows, of ncols and of ceil(ncols/64) (column chunks); then, from
+                        // FOCUS_ROUTE_COUNTS, [FOCUS_MAX_PASSES][2]: every pass's totals of the first two (lfi_focus_route_info reads them)
     uint32_t *rowbase;  // [H]  line slot of (row y, candidate i) = rowbase[y] + popcount(bady[y] & ((1 << i) − 1)):
     uint32_t *colbase;  // [W]  exclusive prefix sums of popcount(bady / badx)
     uint16_t *Er;       // [R_cap][3][We_p]      E'(slot, ty)(qx): row lines of the flagged-row slots below R_cap
@@ -249,7 +250,9 @@ __global__ void __launch_bounds__(64) focus_plan_lists(const KernelArgs a, const
         (axis ? w.nrows : w.ncols)[i] = count;
 }
 
-// one thread: the three prefix tables (the line and exact kernels walk all candidates' lists as one sequence)
+// one thread: the three prefix tables (the line and exact kernels walk all candidates' lists as one sequence); the totals of the rows and of
+// the columns a second time, in the pass's own slot behind the tables — the next pass of a sweep rewrites the tables, the slots stay
+constexpr int FOCUS_ROUTE_COUNTS = 100; // dwords into FocusWork::prefix
 __global__ void focus_plan_prefix(const KernelArgs a, const FocusWork w)
 {
     uint32_t rows = 0, cols = 0, chunks = 0;
@@ -265,6 +268,9 @@ __global__ void focus_plan_prefix(const KernelArgs a, const FocusWork w)
     w.prefix[32] = rows;
     w.prefix[65] = cols;
     w.prefix[98] = chunks;
+    uint32_t *totals = w.prefix + FOCUS_ROUTE_COUNTS + 2 * (a.focus_i0 / FOCUS_STEPS);
+    totals[0] = rows;
+    totals[1] = cols;
 }
 
 // Two samples per instruction.  A u16 lane that holds a byte (0 … 255) is the bit pattern of a non-negative fp16 SUBNORMAL, and the

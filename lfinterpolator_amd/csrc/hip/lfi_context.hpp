@@ -372,6 +372,10 @@ struct lfi_ctx
     int yuv_in_siting = 0, yuv_out_siting = 0;
     DeviceBuffer curve_ws; // lfi_focus_curve: the curve and its result, then the per-workgroup partial sums (grows, kept)
     int ten_variant = 0, std_variant = 0, focus_variant = 0;
+    // lfi_focus_route_info: the last estimate call's route, noted where each launch is chosen (route_begin, lfi_focus_sched.hpp); the
+    // per-pass counts stay on the device, route_counts_at bytes into focus_ws, until the call asks for them
+    lfi_focus_route route = {0, 0, "", "", 0, 0, "", "", 0, 0, 0, {0, 0}, 0, 0, 0, 0, 0, 0, {0}, {0}, {0}};
+    size_t route_counts_at = 0;
     int tiles_passes = 0; // the factored passes lfi_focus_tiles_steps' last call ran; 0: it took focus_curve_partial tile by tile (lfi_focus_tiles_passes)
     mutable const char *last_kernel = ""; // the blend kernel the last render launched (lfi_last_kernel_name)
     mutable unsigned sweep_launches = 0;  // blend_p3 / blend_planar alternate their sweep direction from launch to launch

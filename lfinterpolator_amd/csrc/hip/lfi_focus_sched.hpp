@@ -27,6 +27,15 @@ struct FocusJob
     int padded = 0; // out: focus_pad slots enqueued
 };
 
+// lfi_focus_route_info's record: an estimate call that has passed its checks starts a new one; the launches below note into ctx->route what
+// they choose, each at the place where it is chosen (as note_kernel does for the blend)
+void route_begin(lfi_ctx *ctx)
+{
+    const int32_t calls = ctx->route.calls;
+    ctx->route = lfi_focus_route{calls + 1, 0, "", "", 0, 0, "", "", 0, 0, 0, {0, 0}, 0, 0, 0, 0, 0, 0, {0}, {0}, {0}};
+}
+static_assert(LFI_FOCUS_ROUTE_PASSES == lfi::FOCUS_MAX_PASSES, "lfi_focus_route holds one entry per pass of the longest sweep");
+
 // largest |shift| any candidate gives any of the n offsets, +1 (candidates are monotone in i, so the ends bound them); false when absurd.
 // The bound is the INTERVAL's: the last candidate of every sweep length lfi_set_focus_steps allows (they differ by a rounding of
 // fma(range / (steps − 1), steps − 1, focus) at most), so a change of the number of candidates alone never asks for other planes.
@@ -74,7 +83,10 @@ int launch_focus_factored_keys(lfi_ctx *ctx, const KernelArgs &a, FocusJob &job,
     w.He_p = (H + 2 * ry + 3) / 4 * 4;
     int Sx = 0, Sy = 0;
     if(!focus_pad_shift(ctx, job.offsets, n_ids, &Sx, &Sy))
+    {
+        ctx->route.declined = "shift";
         return LFI_OK;
+    }
     Sx = std::max(Sx, job.need_shift[0]);
     Sy = std::max(Sy, job.need_shift[1]);
     // The padded planes of an earlier call serve this one if the inputs have not changed since and their padding covers these shifts
@@ -98,7 +110,10 @@ int launch_focus_factored_keys(lfi_ctx *ctx, const KernelArgs &a, FocusJob &job,
     // lie below the extended image)
     const size_t pad_bytes = sizeof(uint32_t) * ((size_t)n_ids * w.Hp + lfi::FRT_PR + 16) * w.Wp;
     if(pad_bytes > ((size_t)16 << 30))
+    {
+        ctx->route.declined = "planes";
         return LFI_OK;
+    }
     // Can the range pass unpack its samples once into LDS (focus_range_t)?  Within every group of CPW consecutive candidates a view's integer
     // shifts — the device's own, by the helper it shares with this check (focus_group_fits) — must span at most FRT_MAX_DX pixels and FRT_MAX_DY
     // rows: groups of 8 candidates if that holds, else groups of 4, else focus_range.  Typed loads address the planes with 32 bits.
@@ -127,7 +142,8 @@ int launch_focus_factored_keys(lfi_ctx *ctx, const KernelArgs &a, FocusJob &job,
     const size_t o_tapx = carve(sizeof(uint32_t) * 3 * W), o_tapy = carve(sizeof(uint32_t) * 3 * H); // cleared with badx / bady: adjacent
     const size_t o_cols = carve(sizeof(uint16_t) * lfi::FOCUS_STEPS * W), o_rows = carve(sizeof(uint16_t) * lfi::FOCUS_STEPS * H);
     const size_t o_ncols = carve(sizeof(int32_t) * lfi::FOCUS_STEPS), o_nrows = carve(sizeof(int32_t) * lfi::FOCUS_STEPS);
-    const size_t o_prefix = carve(sizeof(uint32_t) * 3 * 33);
+    // (behind the three tables, prefix[100 … 115]: the two totals of each pass of a sweep, [FOCUS_MAX_PASSES][2], for lfi_focus_route_info)
+    const size_t o_prefix = carve(sizeof(uint32_t) * (lfi::FOCUS_ROUTE_COUNTS + 2 * lfi::FOCUS_MAX_PASSES));
     const size_t o_rowbase = carve(sizeof(uint32_t) * H), o_colbase = carve(sizeof(uint32_t) * (W + 1));
     // line buffers for 4× the typical number of flagged rows / columns (three bands of r per candidate ≈ 0.03·H each);
     // anything beyond takes the tap-by-tap path
@@ -212,6 +228,22 @@ int launch_focus_factored_keys(lfi_ctx *ctx, const KernelArgs &a, FocusJob &job,
     // (planes kept and nothing re-padded: ev_fork says all the side stream needs to know — one event packet less in front of the range pass)
     if(padded_any)
         LFI_HIP(ctx, hipEventRecord(ctx->ev_pad, st));
+    {
+        lfi_focus_route &r = ctx->route;
+        const int p = a.focus_i0 / lfi::FOCUS_STEPS;
+        if(!later_pass)
+        {
+            r.jobs++;
+            r.planes_padded += job.padded;
+            r.planes_kept += n_ids - job.padded;
+            r.pad_shift[0] = Sx, r.pad_shift[1] = Sy;
+            r.We_p = w.We_p, r.He_p = w.He_p, r.Wp = w.Wp, r.Hp = w.Hp, r.R_cap = w.R_cap, r.C_cap = w.C_cap;
+        }
+        r.estimate = direct_range ? "factored_direct" : "factored";
+        r.passes = p + 1;
+        r.range_cpw[p] = range_cpw;
+        ctx->route_counts_at = o_prefix + sizeof(uint32_t) * lfi::FOCUS_ROUTE_COUNTS;
+    }
     const uint32_t tiles_x = uint32_t(w.We_p / 256), tiles_y = uint32_t(w.He_p / 4);
     if(range_cpw)
     {
@@ -221,6 +253,8 @@ int launch_focus_factored_keys(lfi_ctx *ctx, const KernelArgs &a, FocusJob &job,
         const uint32_t nblocks = striped ? 8u * lfi::stripe_blocks_per_xcd(ttx, tty, groups) : ttx * tty * groups;
         // persistent: one workgroup per CU (it owns the whole LDS), a multiple of 8 so that a workgroup's work items stay on its XCD
         const uint32_t grid = std::min(nblocks, uint32_t(std::max(ctx->cu_count / 8 * 8, 8)));
+        ctx->route.range_kernel = range_cpw == 8 ? "focus_range_t<8>" : "focus_range_t<4>";
+        ctx->route.range_striped = striped;
         if(range_cpw == 8)
             hipLaunchKernelGGL(lfi::focus_range_t<8>, dim3(grid), dim3(64 * (lfi::FRT_NW + lfi::FRT_LW)), 0, st, a, w, patches, uint32_t(pad_bytes), nblocks, striped);
         else
@@ -231,6 +265,8 @@ int launch_focus_factored_keys(lfi_ctx *ctx, const KernelArgs &a, FocusJob &job,
         constexpr int CPW = 4, GROUPS = lfi::FOCUS_STEPS / CPW;
         const int striped = tiles_x >= 8;
         const uint32_t nblocks = striped ? 8u * lfi::stripe_blocks_per_xcd(tiles_x, tiles_y, GROUPS) : tiles_x * tiles_y * GROUPS;
+        ctx->route.range_kernel = "focus_range<4>";
+        ctx->route.range_striped = striped;
         hipLaunchKernelGGL(lfi::focus_range<CPW>, dim3(nblocks), dim3(256), 0, st, a, w, nblocks, striped);
     }
     LFI_HIP(ctx, hipStreamWaitEvent(aux, ctx->ev_fork, 0));
@@ -276,8 +312,12 @@ int launch_focus_pick(lfi_ctx *ctx, const KernelArgs &a, const lfi::FocusWork &w
     const int striped = blocks_x >= 8;
     const uint32_t nblocks = striped ? 8u * lfi::stripe_blocks_per_xcd(blocks_x, blocks_y, 1u) : blocks_x * blocks_y;
     // the tap block taken apart (focus_pick_sep): even radius_x of at most 64; variant "factored_direct" keeps focus_pick<2>, the other implementation
+    lfi_focus_route &r = ctx->route;
+    r.consumer_striped = striped;
     if(ppl == 2 && rx <= 64 && e_32bit && !direct_range)
     {
+        r.consumer = carry ? "focus_pick_sep_carry" : "focus_pick_sep";
+        r.consumer_striped = 0;
         // (row-major order of the workgroups, not stripes per XCD: this kernel's re-use of E's rows happens inside a workgroup)
         const uint32_t nb = blocks_x * lfi::focus_pick_sep_block_rows(H, ry);
         if(carry)
@@ -286,13 +326,25 @@ int launch_focus_pick(lfi_ctx *ctx, const KernelArgs &a, const lfi::FocusWork &w
             hipLaunchKernelGGL(lfi::focus_pick_sep, dim3(nb), dim3(64 * lfi::FPS_WAVES), 0, st, a, w);
     }
     else if(ppl == 2 && carry)
+    {
+        r.consumer = "focus_pick_carry<2>";
         hipLaunchKernelGGL(lfi::focus_pick_carry<2>, dim3(nblocks), dim3(256), 0, st, a, w, striped);
+    }
     else if(ppl == 2)
+    {
+        r.consumer = "focus_pick<2>";
         hipLaunchKernelGGL(lfi::focus_pick<2>, dim3(nblocks), dim3(256), 0, st, a, w, striped);
+    }
     else if(carry)
+    {
+        r.consumer = "focus_pick_carry<1>";
         hipLaunchKernelGGL(lfi::focus_pick_carry<1>, dim3(nblocks), dim3(256), 0, st, a, w, striped);
+    }
     else
+    {
+        r.consumer = "focus_pick<1>";
         hipLaunchKernelGGL(lfi::focus_pick<1>, dim3(nblocks), dim3(256), 0, st, a, w, striped);
+    }
     LFI_HIP(ctx, hipGetLastError());
     return LFI_OK;
 }
@@ -428,6 +480,7 @@ int launch_focus_tiles(lfi_ctx *ctx, const KernelArgs &a, int tiles_x, int tiles
                 q.cost = reinterpret_cast<uint64_t *>(ctx->curve_ws.get());
                 q.partial = t.partial = reinterpret_cast<uint64_t *>(ctx->curve_ws.get() + head_bytes);
             }
+            ctx->route.consumer = ppl == 2 ? "focus_tile_costs<2>" : "focus_tile_costs<1>";
             if(ppl == 2)
                 hipLaunchKernelGGL(lfi::focus_tile_costs<2>, dim3(uint32_t(n_blocks)), dim3(256), 0, st, pass, w, t);
             else
@@ -448,6 +501,7 @@ int launch_focus_tiles(lfi_ctx *ctx, const KernelArgs &a, int tiles_x, int tiles
         }
     }
     ctx->tiles_passes = 0;
+    ctx->route.estimate = "focus_curve";
     const uint32_t blocks_x = focus_curve_blocks_x(tile_w);
     const uint32_t max_rows = std::max(1u, 8192u / blocks_x);
     LFI_HIP(ctx, ctx->curve_ws.reserve(head_bytes + sizeof(uint64_t) * size_t(steps) * blocks_x * std::min(uint32_t(tile_h), max_rows)));

@@ -1572,6 +1572,7 @@ int lfi_focus_map(lfi_ctx *ctx)
         return rc;
     if(int rc = join_filter(ctx)) // the previous map's filter still reads map 0, which this call rewrites
         return rc;
+    route_begin(ctx);
     KernelArgs a = make_args(ctx, 0, ctx->views_n, LFI_METHOD_STD);
     a.focus_steps = ctx->focus_steps;
     a.focus_div = float(ctx->focus_steps - 1);
@@ -1592,6 +1593,7 @@ int lfi_focus_map(lfi_ctx *ctx)
         }
         a.map_y0 = e0;
         a.map_rows = e1 - e0;
+        ctx->route.estimate = "row_window";
         if(fine)
             hipLaunchKernelGGL((lfi::focus_estimate_packed_sweep<2, 4>), dim3((ctx->width + 127) / 128, a.map_rows), dim3(64), 0, ctx->stream, a);
         else
@@ -1619,13 +1621,25 @@ int lfi_focus_map(lfi_ctx *ctx)
     if(done)
         ;
     else if(fine) // "packed_p2", and where the factored estimate declined: the variant that takes any number of candidates
+    {
+        ctx->route.estimate = "packed_p2";
         hipLaunchKernelGGL((lfi::focus_estimate_packed_sweep<2, 4>), dim3((ctx->width + 127) / 128, ctx->height), dim3(64), 0, ctx->stream, a);
+    }
     else if(ctx->focus_variant <= 1 && lds_fits) // "lds"
+    {
+        ctx->route.estimate = "lds";
         hipLaunchKernelGGL(lfi::focus_estimate_lds, dim3((ctx->width + 127) / 128, ctx->height), dim3(64), 0, ctx->stream, a);
+    }
     else if(ctx->focus_variant == 3) // "plain": one pixel per lane, float min/max exactly as the reference writes it
+    {
+        ctx->route.estimate = "plain";
         hipLaunchKernelGGL(lfi::focus_estimate, pixel_grid(ctx), dim3(256), 0, ctx->stream, a);
+    }
     else // "packed_p2" (also the fallback of "lds" for very large radii)
+    {
+        ctx->route.estimate = "packed_p2";
         hipLaunchKernelGGL((lfi::focus_estimate_packed<2, 4>), dim3((ctx->width + 127) / 128, ctx->height), dim3(64), 0, ctx->stream, a);
+    }
     LFI_HIP(ctx, hipGetLastError());
     if(done && ctx->aux_stream)
     {
@@ -1681,6 +1695,24 @@ int lfi_focus_tiles_passes(const lfi_ctx *ctx)
     return ctx ? ctx->tiles_passes : 0;
 }
 
+int lfi_focus_route_info(lfi_ctx *ctx, lfi_focus_route *out)
+{
+    if(!ctx || !out)
+        return LFI_EINVAL;
+    *out = ctx->route;
+    if(out->passes < 1 || !ctx->focus_ws)
+        return LFI_OK;
+    if(int rc = bind(ctx))
+        return rc;
+    // the plan runs on the side stream, which the compute stream joins in front of the keys: behind the compute stream's work the counts stand
+    uint32_t totals[2 * LFI_FOCUS_ROUTE_PASSES];
+    LFI_HIP(ctx, hipMemcpyAsync(totals, ctx->focus_ws.get() + ctx->route_counts_at, sizeof(totals), hipMemcpyDeviceToHost, ctx->stream));
+    LFI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for(int p = 0; p < out->passes; p++)
+        out->row_entries[p] = totals[2 * p], out->col_entries[p] = totals[2 * p + 1];
+    return LFI_OK;
+}
+
 // (steps is this call's argument: ctx->focus_steps, lfi_set_focus_steps' setting of lfi_focus_map, is neither read nor written)
 int lfi_focus_tiles_steps(lfi_ctx *ctx, int tiles_x, int tiles_y, int steps, uint64_t *out_cost, lfi_focus_curve_result *out)
 {
@@ -1695,6 +1727,7 @@ int lfi_focus_tiles_steps(lfi_ctx *ctx, int tiles_x, int tiles_y, int steps, uin
         bad = "lfi_focus_tiles_steps: " + std::to_string(steps) + " candidates - the focus tiles take a multiple of 32 from 32 to 256";
     if(int rc = focus_entry(ctx, "lfi_focus_tiles", "focus tiles", false, bad))
         return rc;
+    route_begin(ctx);
     const KernelArgs a = make_args(ctx, 0, ctx->views_n, LFI_METHOD_STD);
     const uint8_t *d_head = nullptr;
     if(int rc = launch_focus_tiles(ctx, a, tiles_x, tiles_y, steps, &d_head))
@@ -1774,6 +1807,7 @@ int lfi_view_focus_maps(lfi_ctx *ctx, const int32_t *focus_ids_vk, int views, in
         return rc;
     if(int rc = ensure_view_maps(ctx))
         return rc;
+    route_begin(ctx);
     const int n = ctx->n, V = views;
     // every view's ids in slot order (slots stay with their images from view to view: only the images that change are padded again), the
     // offsets of its sampled images, and one pad geometry for the whole batch

@@ -1356,6 +1356,7 @@ EXCLUDED = {
     "lfi_yuv_siting": "the getter of lfi_set_yuv_siting: two integers",
     "lfi_focus_tiles_steps": "lfi_focus_tiles with another number of candidates: the same buffers (curve_ws, focus_ws), probed at 32",
     "lfi_focus_tiles_passes": "reads one integer of the last lfi_focus_tiles call",
+    "lfi_focus_route_info": "reads the record of the last estimate call and its counts on the device; writes nothing",
     "lfi_std_band_info": "a per-device measurement, no context state",
     "lfi_benchmark": "renders in a loop; what it leaves is what lfi_render leaves",
     "lfi_timer_start": "records an event; reads and changes no buffer",

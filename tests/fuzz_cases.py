@@ -9,6 +9,7 @@ focus maps bit-exact, TEN_WM within one LSB of the fp16-accumulate model M16 and
 import numpy as np
 
 import deep_ref
+import focus_routes
 import inframe_ref
 import linear_ref
 import poison
@@ -112,11 +113,9 @@ def fuzz_blend(L, oc, n_cases: int, seed: int, log=None) -> list:
     return bad
 
 
-def fuzz_focus(L, oc, n_cases: int, seed: int, log=None) -> list:
-    """Focus maps: the factored estimate, the LDS-staged one and the reference-shaped plain kernel on random shapes, radii, focus
-    ranges and contents (quantised and partly black inputs produce ties and FLT_MIN taps) — all against the oracle."""
+def focus_draws(L, oc, n_cases: int, seed: int):
+    """fuzz_focus' cases, (case, hp, lf) each: the draw alone, on the CPU (tests/test_focus_routes_table.py states the leaves a seed reaches)"""
     rng = np.random.default_rng(seed)
-    bad = []
     for i in range(n_cases):
         cols, rows = int(rng.integers(2, 10)), int(rng.integers(2, 10))
         W = int(rng.choice([8, 33, 64, 100, 130, 257, 300, 640]))
@@ -134,21 +133,58 @@ def fuzz_focus(L, oc, n_cases: int, seed: int, log=None) -> list:
             lf[:, : H // 2, : W // 3, :3] = 0
         lf[..., 3] = 255
         case = dict(kind="focus", cols=cols, rows=rows, W=W, H=H, focus=focus, range=frange, traj=traj, radius=[int(x) for x in hp.block_radius], q=q)
+        yield case, hp, lf
+
+
+def focus_leaves(L, oc, case, hp, plan=None):
+    """the leaves of tests/focus_routes.py a fuzz_focus case reaches, by the restatement"""
+    c = dict(case, steps=32, more=())
+    plan = plan or focus_routes.Plan(oc, case["W"], case["H"], hp.block_radius, hp.offsets[hp.focus_map_ids], hp.focus, hp.range)
+    return focus_routes.leaves_of(c, hp, plan)
+
+
+def fuzz_focus(L, oc, n_cases: int, seed: int, log=None) -> list:
+    """Focus maps: the factored estimate, the LDS-staged one and the reference-shaped plain kernel on random shapes, radii, focus
+    ranges and contents (quantised and partly black inputs produce ties and FLT_MIN taps) — all against the oracle; and the route each call
+    took (lfi_focus_route_info) against the restatement of tests/focus_routes.py, the device's per-pass counts included.  Logs the leaves of
+    that table the cases reached."""
+    bad = []
+    reached = set()
+    for i, (case, hp, lf) in enumerate(focus_draws(L, oc, n_cases, seed)):
+        cols, rows, W, H = case["cols"], case["rows"], case["W"], case["H"]
         want0 = oc.focus_estimate(lf, hp.offsets, hp.focus_map_ids, hp.focus, hp.range, hp.block_radius, threads=8)
         want1 = oc.focus_filter(want0, hp.block_radius)
+        plan = focus_routes.Plan(oc, W, H, hp.block_radius, hp.offsets[hp.focus_map_ids], hp.focus, hp.range)
+        reached |= focus_leaves(L, oc, case, hp, plan)
         ctx = L.Context(0)
         ctx.set_grid(cols, rows, W, H)
         ctx.upload_grid(lf)
         ctx.set_params(hp)
+        state = focus_routes.PadState()
         for var in ("factored", "factored_direct", "plain", "lds"):
             ctx.set_variant("FOCUS", var)
             poison.focus_map(ctx)
+            state.valid = False     # (the poison took the padded planes with the workspace: every call pads all of them)
             m0, m1 = ctx.download_map(0), ctx.download_map(1)
             if not ((m0 == want0).all() and (m1 == want1).all()):
                 bad.append(dict(case, what="focus map", variant=var, wrong=int((m0 != want0).any(-1).sum())))
+            got = ctx.focus_route()
+            if var.startswith("factored"):
+                want = focus_routes.expected_route(W, H, hp.block_radius, hp.offsets[hp.focus_map_ids], hp.focus_map_ids, hp.focus, hp.range, 32, var,
+                                                   state=state, plan=plan)
+                if want["declined"]:
+                    want = dict(declined=want["declined"], estimate="lds" if var == "factored" else "packed_p2", passes=0)
+            else:
+                lds_fits = 128 + 2 * int(hp.block_radius[0]) + 8 <= 256   # the LDS-staged kernel's window in its 256-pixel row, else packed_p2
+                want = dict(estimate="packed_p2" if var == "lds" and not lds_fits else var, declined="", passes=0)
+            wrong = focus_routes.route_matches(got, want)
+            if wrong:
+                bad.append(dict(case, what="focus route", variant=var, fields={n: (got[n], want[n]) for n in wrong}))
         ctx.close()
         if log and (i + 1) % 20 == 0:
             log(f"{i + 1} cases, {len(bad)} mismatches")
+    if log:
+        log("leaves reached: " + "; ".join(sorted(reached)))
     return bad
 
 

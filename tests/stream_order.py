@@ -80,6 +80,7 @@ CLASSES = {
     "lfi_set_focus_steps": (HOST, ""), "lfi_focus_steps": (HOST, ""),
     "lfi_focus_curve": (SYNC, "\"synchronous\""), "lfi_focus_tiles": (SYNC, "\"synchronous\""), "lfi_focus_tiles_steps": (SYNC, "\"synchronous\""),
     "lfi_focus_tiles_passes": (HOST, ""),
+    "lfi_focus_route_info": (SYNC, "\"synchronises the context's streams and copies 64 bytes\" where the factored estimate ran"),
     "lfi_render": (COND, "the first STD launch over more than 64 images on a device runs the band's self-check (lfi_std_band_info); a planar "
                          "copy that has to grow is reallocated behind a drained stream"),
     "lfi_render_stream": (SYNC, "\"Returns after everything has completed.\""),

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import focus_curve_ref as cref
+import focus_routes
 import focus_steps_ref as ref
 import lfinterpolator_amd as L
 import poison
@@ -97,6 +98,7 @@ def test_maps_equal_the_restatement_in_every_variant(gpu, name, steps):
         with _ctx(gpu, name, variant, steps) as ctx:
             assert ctx.focus_steps() == steps
             _check(ctx, name, steps, variant)
+            focus_routes.assert_variant(ctx, variant, _scene(name)[0], steps)   # the maps are the named estimate's
 
 
 def test_the_scenes_cover_what_they_claim():

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import focus_curve_ref as ref
+import focus_routes
 import focus_steps_ref as sref
 import lfinterpolator_amd as L
 import poison
@@ -120,6 +121,7 @@ def test_every_tiles_curve_equals_the_restatement(gpu, case, steps, variant):
     with _ctx(gpu, case, variant) as ctx:
         for grid in GRIDS:
             _check(ctx, hp, costs, grid, steps, factored=variant != "packed_p2")
+        focus_routes.assert_variant(ctx, variant, hp, steps, "tiles")   # the curves are the named estimate's
 
 
 # ---- 2. the pass boundary -------------------------------------------------------------------------------------------------------------

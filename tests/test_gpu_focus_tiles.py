@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import focus_curve_ref as ref
+import focus_routes
 import lfinterpolator_amd as L
 import poison
 from test_host_focus_tiles import two_depth_scene
@@ -87,6 +88,7 @@ def test_every_tiles_curve_equals_the_restatement(gpu, oracle_c, case, variant):
         ctx.set_variant("FOCUS", variant)
         for grid in GRIDS:
             _check(ctx, hp, costs, grid)
+        focus_routes.assert_variant(ctx, variant, hp, 32, "tiles")   # the curves are the named estimate's
         if ctx.width > 256:
             _check(ctx, hp, costs, (ctx.width // 2, ctx.height))   # two pixels per tile where one per tile exceeds the limit
         if case == "g3x3":

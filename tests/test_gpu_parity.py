@@ -501,16 +501,22 @@ def test_focus_filter_window_sizes(case, gpu, oracle_c):
     ctx.close()
 
 
-@pytest.mark.parametrize("case", [(1, 1, 64, 20, 0.2, 0.3, None), (1, 2, 100, 33, 0.1, 0.2, None), (2, 1, 7, 5, 0.3, 0.5, (1, 1)), (3, 3, 1024, 70, 0.22, 0.17, None),
-                                  (8, 8, 2048, 96, 0.05, 0.04, (20, 10)), (15, 15, 640, 64, 0.22, 0.17, (6, 4)), (6, 6, 513, 40, -0.3, 0.6, None),
-                                  (9, 9, 300, 48, 0.0, 1.0, (11, 5)), (4, 4, 4096, 36, 0.22, 0.17, None), (5, 3, 190, 130, 0.5, 0.01, None)],
-                         ids=lambda c: "x".join(str(v) for v in c[:4]))
+# (cols, rows, W, H, focus, range, radii, the range pass `factored` takes — lfi_focus_route_info's range_kernel — and whether its items go in stripes)
+@pytest.mark.parametrize("case", [(1, 1, 64, 20, 0.2, 0.3, None, "focus_range_t<8>", 0), (1, 2, 100, 33, 0.1, 0.2, None, "focus_range_t<8>", 0),
+                                  (2, 1, 7, 5, 0.3, 0.5, (1, 1), "focus_range_t<8>", 0), (3, 3, 1024, 70, 0.22, 0.17, None, "focus_range_t<8>", 1),
+                                  (8, 8, 2048, 96, 0.05, 0.04, (20, 10), "focus_range_t<8>", 1), (15, 15, 640, 64, 0.22, 0.17, (6, 4), "focus_range_t<8>", 1),
+                                  (6, 6, 513, 40, -0.3, 0.6, None, "focus_range_t<8>", 1), (9, 9, 300, 48, 0.0, 1.0, (11, 5), "focus_range_t<8>", 1),
+                                  (4, 4, 4096, 36, 0.22, 0.17, None, "focus_range_t<4>", 1), (5, 3, 190, 130, 0.5, 0.01, None, "focus_range_t<8>", 0),
+                                  (4, 4, 64, 16, -4, 8, (4, 2), "focus_range_t<4>", 0), (4, 4, 64, 16, -9, 18, (4, 2), "focus_range<4>", 0)],
+                         ids=lambda c: "x".join(str(v) for v in c[:4]) + ("_f%d" % c[4] if c[4] < -1 else ""))
 def test_focus_map_edge_shapes_both_range_passes(case, gpu, oracle_c):
     """Shapes at the edges of focus_range_t's dispatch (round 5): one and two sampled views (a single step, an odd tail), images narrower than
     a tile and as wide as the stripes' XCD mapping, shifts whose span per candidate group forces groups of four or the fall-back to
-    focus_range (range 1.0), negative focus, radii from 1 to 20 — `factored` (focus_range_t where its preconditions hold) and
-    `factored_direct` (focus_range), twice each (the padded planes kept), maps 0 and 1 against the oracle."""
-    cols, rows, W, H, f, r, rad = case
+    focus_range (the 4096-wide case and the two 64 x 16 cases of focus -4 and -9: range 1.0 on 300 pixels stays with groups of eight),
+    negative focus, radii from 1 to 20 — `factored` (focus_range_t where its preconditions hold) and
+    `factored_direct` (focus_range), twice each (the padded planes kept), maps 0 and 1 against the oracle; the range pass each call took is
+    asserted from the route record."""
+    cols, rows, W, H, f, r, rad, range_kernel, striped = case
     hp = gpu.build_params(cols, rows, W, H, "0.071,0.071,0.93,0.93", f, r, 3.0, 1.783, 2)
     if rad:
         hp.block_radius = np.array(rad, np.int32)
@@ -524,22 +530,34 @@ def test_focus_map_edge_shapes_both_range_passes(case, gpu, oracle_c):
         ctx.set_variant("FOCUS", variant)
         byte = poison.focus_map(ctx)
         ctx.poison(gpu.LFI_POISON_MAPS, poison.POISON[0] ^ poison.POISON[1] ^ byte)
+        first = ctx.focus_route()
         ctx.focus_map()         # the second call keeps the padded planes: only the maps are poisoned before it
         ctx.sync()
         assert (ctx.download_map(0) == want0).all() and (ctx.download_map(1) == want1).all(), variant
+        route = ctx.focus_route()
+        assert (route["estimate"], route["declined"], route["passes"]) == (variant, "", 1), route
+        assert route["range_kernel"] == first["range_kernel"] == (range_kernel if variant == "factored" else "focus_range<4>"), route
+        assert variant != "factored" or route["range_striped"] == striped
+        assert (first["planes_padded"], route["planes_padded"], route["planes_kept"]) == (len(hp.focus_map_ids), 0, len(hp.focus_map_ids)), (first, route)
     ctx.close()
 
 
-@pytest.mark.parametrize("case", [(129, 50, (2, 1)), (257, 70, (64, 3)), (300, 70, (66, 2)), (640, 200, (8, 6)), (1000, 33, (38, 22)), (130, 40, (40, 30)),
-                                  (256, 97, (4, 1)), (2050, 48, (20, 2))],
+# (W, H, radii, the pick `factored` takes — lfi_focus_route_info's consumer; `factored_direct` takes focus_pick<2> on every one; False: the plan
+# flags columns only — the offsets scale with the width, and vertical shifts of 50 to 239 rows (or none: the camera's own grid row) on 48 put every tap row on the same edge row by
+# the reference's coordinate and by the uniform shift alike —, no corner)
+@pytest.mark.parametrize("case", [(129, 50, (2, 1), "focus_pick_sep"), (257, 70, (64, 3), "focus_pick_sep"), (300, 70, (66, 2), "focus_pick<2>"),
+                                  (640, 200, (8, 6), "focus_pick_sep"), (1000, 33, (38, 22), "focus_pick_sep"), (130, 40, (40, 30), "focus_pick_sep"),
+                                  (256, 97, (4, 1), "focus_pick_sep"), (2050, 48, (20, 2), "focus_pick_sep", False)],
                          ids=lambda c: "%dx%d_r%dx%d" % (c[0], c[1], c[2][0], c[2][1]))
 def test_focus_map_pick_and_keys_at_their_dispatch_edges(case, gpu, oracle_c):
     """focus_pick_sep (round 5: the tap block taken apart, sixteen waves on rows radius_y apart, two rows of the map per wave) and the comb form
     of focus_line_keys' column part at the edges of their geometry: widths one past a multiple of 128, radius_x of 2 (one lane of extra columns),
     64 (the last radius the kernel takes: taps two whole waves further on) and 66 (focus_pick<2> instead), radius_y of 1 (a band of 32 rows) and
     above the image's height (one band, most waves idle; combs with a single row), heights that end inside a band.  Quantised inputs with a black
-    region (ties, FLT_MIN taps), a corner where rows AND columns are flagged; `factored` and `factored_direct` (the other pick), maps 0 and 1."""
-    W, H, rad = case
+    region (ties, FLT_MIN taps), a corner where rows AND columns are flagged; `factored` and `factored_direct` (the other pick), maps 0 and 1.
+    The pick each call took, and that rows and columns were flagged (in every case but the 2050-wide one), is asserted from the route record."""
+    W, H, rad, pick = case[:4]
+    corner = case[4] if len(case) > 4 else True
     cols, rows = 6, 5
     hp = gpu.build_params(cols, rows, W, H, "0.071,0.071,0.93,0.93", 0.22, 0.3, 7.0, 1.783, 2)
     hp.block_radius = np.array(rad, np.int32)
@@ -557,6 +575,9 @@ def test_focus_map_pick_and_keys_at_their_dispatch_edges(case, gpu, oracle_c):
         got0 = ctx.download_map(0)
         assert (got0 == want0).all(), (variant, int((got0 != want0).any(-1).sum()))
         assert (ctx.download_map(1) == want1).all(), variant
+        route = ctx.focus_route()
+        assert (route["estimate"], route["consumer"]) == (variant, pick if variant == "factored" else "focus_pick<2>"), route
+        assert route["col_entries"][0] > 0 and (route["row_entries"][0] > 0) == corner, route
     ctx.close()
 
 
